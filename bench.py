@@ -1,6 +1,6 @@
 """Benchmark of the linear auditory-attention-decoding hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
 
 One "step" = one complete ridge TRF fit of BASELINE.json's config[1] ("C2"): lagged-covariance
 accumulate (64 ch x 32 lags, never materialising the lag matrix) -> [N > 1: one RCCL all-reduce
@@ -23,6 +23,9 @@ subject), so by default they are software-pipelined on two HIP streams
 throughput-bound accumulate of fit i + 1.  All K fits, solves included, complete inside the
 timed region.  --serial runs them back to back on one stream; the serial figure is also
 measured after the timed region and reported as `serial_ms_per_step`.
+
+--dump-outputs DIR writes the W and b of the last timed fit as DIR/w.npy and DIR/b.npy (the
+inputs are seeded: two builds run with the same arguments can be compared output for output).
 
 Before the W warm-up steps, --spinup-steps (default 40, untimed, reported in the line) bring the
 device out of the idle of the set-up phase: after an idle moment the chip answers a burst of
@@ -1100,9 +1103,16 @@ def main():
   ap.add_argument('--dry-launch', action='store_true',
                   help='launch the ranks, rendezvous (gloo, CPU) and print the line without any '
                        'compute: checks the multi-rank plumbing where there is no GPU')
+  ap.add_argument('--dump-outputs', metavar='DIR',
+                  help='after the timed steps, rank 0 writes the solution of the last fit it solved in them '
+                       '(what ridge_solve hands a caller) as DIR/w.npy [lambdas, K, D] and DIR/b.npy '
+                       '[lambdas, D], float32; the inputs are seeded, so two builds can be compared output '
+                       'for output')
   args = ap.parse_args()
   if args.gpus < 1:
     raise SystemExit('--gpus must be >= 1')
+  if args.steps < 1:
+    raise SystemExit('--steps must be >= 1')
   if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
     # not under torch.distributed.run: start the N ranks from here (before any GPU call)
     sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -1273,6 +1283,12 @@ def main():
   h_prof.profile_enable(False)
   if out is not None:
     assert bool(torch.isfinite(out[0]).all()), 'non-finite TRF weights'
+  if args.dump_outputs and rank == 0:
+    if out is None:
+      raise SystemExit('--dump-outputs: rank 0 solved no fit in the timed steps')
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, t in zip(('w', 'b'), out):
+      np.save(os.path.join(args.dump_outputs, name + '.npy'), t.cpu().numpy().astype(np.float32))
 
   line = None
   if rank == 0:

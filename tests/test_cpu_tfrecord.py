@@ -1,5 +1,5 @@
 """F3: the dependency-free TFRecord / tf.train.Example reader."""
-import glob
+import gzip
 import os
 
 import numpy as np
@@ -7,7 +7,7 @@ import pytest
 
 from telluride_decoding_amd import tfrecord
 
-REF_MEG = '/root/reference/test_data/meg'
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
 def test_crc32c_known_answers():
@@ -111,18 +111,25 @@ def test_field_selection_matches_reference_semantics(tmp_path):
     tfrecord.dataset_from_files(names[:1], 'eeg', 'envelope', in2_fields=['nope'])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MEG), reason='reference test data not present')
-def test_reads_the_reference_meg_files():
+def test_reads_the_reference_meg_files(tmp_path):
   """The reference's own fixtures and expectations (test/brain_data_test.py:501-531):
   1001 records per file; meg 148, mel_spectrogram 64, phonemes 38, phonetic_features 19,
-  envelope 1 wide."""
-  files = sorted(glob.glob(os.path.join(REF_MEG, '*.tfrecords')))
-  assert len(files) == 3
-  assert tfrecord.count_tfrecords(files[0]) == (1001, False)
-  shapes = tfrecord.discover_feature_shapes(files[0])
+  envelope 1 wide.  The reference's three MEG files (subj01..03_1ksamples.tfrecords) are
+  byte-identical; tests/golden holds one of them, gzip-compressed (make_meg_fixture.py)."""
+  name = str(tmp_path / 'subj01_1ksamples.tfrecords')
+  with gzip.open(os.path.join(GOLDEN, 'meg_subj01_1ksamples.tfrecords.gz'), 'rb') as f:
+    raw = f.read()
+  assert len(raw) == 1213212
+  open(name, 'wb').write(raw)
+  assert tfrecord.count_tfrecords(name) == (1001, False)
+  shapes = tfrecord.discover_feature_shapes(name)
   for k, w in {'phonetic_features': 19, 'mel_spectrogram': 64, 'meg': 148, 'phonemes': 38,
                'envelope': 1}.items():
     assert shapes[k][0] == w
-  feats = tfrecord.read_file(files[0], fields=['meg', 'envelope'], verify=True)
+  feats = tfrecord.read_file(name, fields=['meg', 'envelope'], verify=True)
   assert feats['meg'].shape == (1001, 148) and feats['envelope'].shape == (1001, 1)
   assert np.isfinite(feats['meg']).all() and feats['meg'].std() > 0
+  # the 400-record cut used by the GPU tests is the head of this recording
+  cut = tfrecord.read_file(os.path.join(GOLDEN, 'meg_subj01_400.tfrecords'), verify=True)
+  for k in ('meg', 'envelope'):
+    np.testing.assert_array_equal(cut[k], feats[k][:400])

@@ -1,5 +1,5 @@
-import sys, time, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, time, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from telluride_decoding_amd import device, pipeline
 h = device.default_handle()

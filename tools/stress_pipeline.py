@@ -1,7 +1,8 @@
 """Stress of pipeline.FitPipeline (accumulate of fit i + 1 beside the deferred finalize + solve of fit i): 3 shapes x
 1160 fits, every fit compared bit for bit with the first pipelined fit of the same data and (2e-5) with the serial fit."""
+import os
 import sys
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from telluride_decoding_amd import device as dev, pipeline
 rng = np.random.default_rng(3)
