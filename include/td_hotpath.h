@@ -317,6 +317,9 @@ int td_set_solver(td_handle* h, int mode);
  *                     the one-kernel streaming form (float32 products); 0: the tiled kernels (A/B runs).
  * Unknown names are TD_ERR_INVALID. */
 int td_set_option(td_handle* h, const char* name, int64_t value);
+/* Bytes of device memory the handle's kernel scratch arena holds now (it grows to the largest request
+ * x 1.25 and never shrinks; the workspace arena of "reserve_workspace" is separate). */
+int td_scratch_bytes(td_handle* h, int64_t* bytes);
 int td_last_solve_info(td_handle* h, int* solver, int* iterations, int* cg_status);
 /* The same without waiting for the device.  *singular_flag_host points at a pinned host int
  * owned by the handle (a ring of 8: read it before the 8th later call; a call that would reuse a

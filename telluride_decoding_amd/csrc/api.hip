@@ -447,6 +447,12 @@ int td_use_own_stream(td_handle* h) {
   return TD_OK;
 }
 
+int td_scratch_bytes(td_handle* h, int64_t* bytes) {
+  if (!h || !bytes) return td_fail(h, TD_ERR_INVALID, "td_scratch_bytes: NULL argument");
+  *bytes = (int64_t)h->scratch_bytes;
+  return TD_OK;
+}
+
 int td_synchronize(td_handle* h) {
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "handle is NULL");
   TD_HIP(h, hipStreamSynchronize(h->stream));

@@ -41,6 +41,8 @@ constexpr int kNpfU2 = 13;     // 208 staged rows (e0 <= 72)
 constexpr int kNpfG = 9;       // general: 64 + 72 = 136 rows
 constexpr int kLagsPerWg = 8;  // lags per workgroup (2 per wave)
 constexpr int kHalo = 8;       // extra B rows (7 needed)
+// td_lagcov runs a call whose partial slabs need more scratch than this as pieces (at least one slab each)
+constexpr size_t kLagcovScratchCap = size_t(256) << 20;
 
 // Bijective XCD-aware remap: physical block b runs on XCD b % 8 (observed
 // round-robin dispatch; speed only).  Give each XCD a contiguous range of
@@ -3894,6 +3896,22 @@ int td_add_reversed_transposed(td_handle* h, const double* src, int e_count, int
   return TD_OK;
 }
 
+// The matrix kernel of a planned td_lagcov call and its float64 reduction into g_dev.
+static int lagcov_run(td_handle* h, LagcovPlan* plan, double* g_dev, bool accumulate, int ldg, int rows_dst) {
+  void* scratch = nullptr;
+  TD_TRY(td_scratch(h, plan->scratch_bytes, &scratch));
+  LagReduceJob job;
+  TD_TRY(td_lagcov_launch(h, plan, scratch, g_dev, accumulate, ldg, rows_dst, &job));
+  launch_lagcov_reduce<float>(h, reinterpret_cast<const float*>(job.partial), job.n_work, job.e_pad,
+                              job.ca_pad, job.cb_pad, plan->e_count, plan->ca_eff, plan->cb, g_dev, accumulate,
+                              rows_dst, ldg, job.scale_a, job.scale_b);
+  if (job.mirror)
+    hipLaunchKernelGGL(mirror_upper_kernel, dim3((unsigned)td_ceil_div((long long)plan->p.ca * plan->cb, 256)),
+                       dim3(256), 0, h->stream, g_dev, plan->p.ca, ldg);
+  TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
 int td_lagcov(td_handle* h, const float* a, int64_t lda, int ca, bool a_ones, const float* b,
               int64_t ldb, int cb, const std::vector<LagSeg>& segs, int e_min, int e_count,
               double* g_dev, bool accumulate, int ldg, int rows_dst, bool skinny, bool allow_f16,
@@ -3915,17 +3933,40 @@ int td_lagcov(td_handle* h, const float* a, int64_t lda, int ca, bool a_ones, co
     }
     return TD_OK;
   }
-  void* scratch = nullptr;
-  TD_TRY(td_scratch(h, plan.scratch_bytes, &scratch));
-  LagReduceJob job;
-  TD_TRY(td_lagcov_launch(h, &plan, scratch, g_dev, accumulate, ldg, rows_dst, &job));
-  launch_lagcov_reduce<float>(h, reinterpret_cast<const float*>(job.partial), job.n_work, job.e_pad,
-                              job.ca_pad, job.cb_pad, e_count, ca_eff, cb, g_dev, accumulate, rows_dst,
-                              ldg, job.scale_a, job.scale_b);
-  if (job.mirror)
-    hipLaunchKernelGGL(mirror_upper_kernel, dim3((unsigned)td_ceil_div((long long)ca * cb, 256)),
-                       dim3(256), 0, h->stream, g_dev, ca, ldg);
-  TD_HIP(h, hipGetLastError());
+  if (plan.scratch_bytes <= kLagcovScratchCap || plan.works.size() < 2)
+    return lagcov_run(h, &plan, g_dev, accumulate, ldg, rows_dst);
+  // Scratch bound.  Wide operands keep one [e_pad][ca_pad][cb_pad] float slab per <= 2048 rows
+  // (143 MB at 2049 context-free channels), so one long call -- a whole lagged recording handed
+  // over as one minibatch -- would leave gigabytes in the handle's scratch for good.  Such a call
+  // runs as consecutive pieces of the plan's own slabs, each planned on its own rows (the same
+  // slab cuts) under the cap -- at least one slab --, the first in the caller's mode and the rest
+  // accumulating: every slab is the same float32 chain, and slabs were summed in float64 anyway.
+  const size_t slab_bytes = plan.scratch_bytes / plan.works.size();
+  size_t per_piece = kLagcovScratchCap / slab_bytes;
+  if (per_piece < 1) per_piece = 1;
+  bool acc = accumulate;
+  for (size_t w0 = 0; w0 < plan.works.size(); w0 += per_piece) {
+    const size_t w1 = w0 + per_piece < plan.works.size() ? w0 + per_piece : plan.works.size();
+    // the rows of works [w0, w1) as segments (the works of one segment are adjacent slabs, in order)
+    std::vector<LagSeg> piece;
+    for (size_t w = w0; w < w1; ++w) {
+      const int f = plan.work_seg[w];
+      if (w > w0 && plan.work_seg[w - 1] == f) {
+        piece.back().u_end = plan.works[w].u_end;
+        continue;
+      }
+      piece.push_back(segs[f]);
+      piece.back().u_begin = plan.works[w].u_begin;
+      piece.back().u_end = plan.works[w].u_end;
+    }
+    LagcovPlan pp;
+    pp.force_small = skinny;
+    pp.allow_f16 = allow_f16;
+    pp.tab = chan_tab;
+    TD_TRY(td_lagcov_plan(h, a, lda, ca, a_ones, b, ldb, cb, piece, e_min, e_count, &pp));
+    TD_TRY(lagcov_run(h, &pp, g_dev, acc, ldg, rows_dst));
+    acc = true;
+  }
   return TD_OK;
 }
 

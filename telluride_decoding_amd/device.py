@@ -85,6 +85,12 @@ class Handle(object):
     CCA in one launch; 0: the chain of launches); 'reserve_workspace' (bytes: grow the workspace arena now)."""
     self.check(self.lib.td_set_option(self.ptr, name.encode(), int(value)))
 
+  def scratch_bytes(self):
+    """Bytes the handle's kernel scratch arena holds (td_scratch_bytes): its high-water mark x 1.25."""
+    n = ctypes.c_int64(0)
+    self.check(self.lib.td_scratch_bytes(self.ptr, ctypes.byref(n)))
+    return int(n.value)
+
   def last_solve_info(self):
     """What the last synchronous ridge solve on this handle did: {'solver': 'cholesky' | 'cg',
     'iterations': n, 'cg_status': 0 converged / 2 not converged / 3 aborted} (td_last_solve_info)."""

@@ -34,6 +34,7 @@ from telluride_decoding import attention_decoder as ref_ad  # noqa: E402
 from telluride_decoding import brain_model as ref_bm  # noqa: E402
 from telluride_decoding import cca as ref_cca  # noqa: E402
 from telluride_decoding import infer_decoder as ref_id  # noqa: E402
+from telluride_decoding import preprocess as ref_pre  # noqa: E402
 from telluride_decoding import result_store as ref_rs  # noqa: E402
 from telluride_decoding import scaled_lda as ref_lda  # noqa: E402
 
@@ -72,6 +73,33 @@ def g1_lag():
        off_m1_out=np.array([[3001], [3002], [3003]]),
        off_p2_in=np.array([[2, 1002], [3, 1003], [4, 1004]]),     # :267-272
        off_p2_out=np.array([[3000], [3001], [3002]]))
+
+
+# ----------------------------------------------------------------- G1b the second lag builder
+G1B_CASES = ((2, 2, 0), (2, 0, 2), (3, 1, 2), (64, 0, 31))
+G1B_ROWS = 150
+G1B_CHUNKS = (47, 120)            # three uneven calls: [0, 47), [47, 120), [120, 150)
+
+
+def g1b_preprocess_context():
+  """preprocess.Preprocessor.add_context (preprocess.py:487-522), the lag builder of the
+  reference's ingestion path, once on a whole array and once streamed in three uneven calls
+  (its _context_state carries the last pre + post rows of a call into the next).  Inputs are
+  distinct non-zero integers, x[t, c] = 1000 c + t + 1, so that a misplaced element or a
+  non-zero padding row cannot hide."""
+  out = {}
+  for c, pre, post in G1B_CASES:
+    x = (1000.0 * np.arange(c)[None, :] + np.arange(G1B_ROWS)[:, None] + 1.0)
+    p = ref_pre.Preprocessor('g1b', 100, 100, pre_context=pre, post_context=post)
+    whole = p.add_context(x)
+    p.context_reset()
+    bounds = (0,) + G1B_CHUNKS + (G1B_ROWS,)
+    streamed = np.concatenate([p.add_context(x[a:b]) for a, b in zip(bounds[:-1], bounds[1:])])
+    key = 'c%d_pre%d_post%d' % (c, pre, post)
+    out[key + '_x'] = x
+    out[key + '_whole'] = whole
+    out[key + '_streamed'] = streamed
+  save('g1b_preprocess_context', **out)
 
 
 # ----------------------------------------------------------------- G2 ridge
@@ -656,6 +684,7 @@ if __name__ == '__main__':
       globals()[name]()
     sys.exit(0)
   g1_lag()
+  g1b_preprocess_context()
   g2_ridge()
   g3_pearson()
   g4_cca()

@@ -193,3 +193,64 @@ def window_scores(sums, width, mode, reduction='first', mean_a=None, mean_b=None
             np.any(vb[:, sl] <= tiny * s[:, sl, 3], axis=1))
     r[zero, sl] = 0.0
   return torch.from_numpy(r)
+
+
+# ---- float64 references and distance metrics of the parity tests on already-lagged minibatches
+def gram64(x, y=None):
+  """Dense float64 moments of [x | 1] (the ones column last, like td_stats_moments): X1^T X1 and,
+  with y, X1^T y."""
+  x1 = np.hstack((np.asarray(x, np.float64), np.ones((x.shape[0], 1))))
+  g = x1.T @ x1
+  return (g, x1.T @ np.asarray(y, np.float64)) if y is not None else g
+
+
+def offset_moments(g, gxy, xl, y, offset, pre, post):
+  """The moments gram64 returns for lag_matrix(raw + offset) -- a per-channel constant added to a
+  recording whose lag matrix xl = lag_matrix(raw, pre, post) has moments (g, gxy) -- without a
+  second dense product.  lag_matrix(raw + o) = xl + B, B[t, l C + c] = o_c m_l(t) with m_l(t) = 1
+  where row t + l - pre exists (the padded rows stay zero), so with A = [xl | 1]
+  A'^T A' = A^T A + A^T B + B^T A + B^T B and A^T B = kron(A^T m, o^T), B^T B = kron(m^T m, o o^T)."""
+  n = xl.shape[0]
+  o = np.asarray(offset, np.float64)
+  lags = pre + 1 + post
+  t = np.arange(n)[:, None] + np.arange(lags)[None, :] - pre
+  m = ((t >= 0) & (t < n)).astype(np.float64)                     # [n, L]
+  a = np.hstack((np.asarray(xl, np.float64), np.ones((n, 1))))
+  k = lags * o.size
+  p = np.zeros_like(g)
+  p[:, :k] = np.kron(a.T @ m, o[None, :])
+  q = np.zeros_like(g)
+  q[:k, :k] = np.kron(m.T @ m, np.outer(o, o))
+  gxy_o = gxy.copy()
+  gxy_o[:k] += np.kron(m.T @ np.asarray(y, np.float64), o[:, None])
+  return g + p + p.T + q, gxy_o
+
+
+def ridge_from_moments(g, gxy, n, lamb):
+  """The ridge branch of the reference (brain_model.py:447-454, 477) from summed moments:
+  solve(G / n + lamb I, Gxy / n) -- the bias row regularised too.  Returns (W, b)."""
+  sol = np.linalg.solve(g / n + lamb * np.identity(g.shape[0]), gxy / n)
+  return sol[:-1], sol[-1:]
+
+
+def maxnorm_rel(got, want):
+  """|got - want| / max |want| (max-norm relative)."""
+  want = np.asarray(want, np.float64)
+  return float(np.max(np.abs(np.asarray(got, np.float64) - want)) / np.max(np.abs(want)))
+
+
+def moment_rel(got, want, diag_a=None, diag_b=None):
+  """Element-wise distance of moments: max |got_ij - want_ij| / sqrt(A_ii B_jj), with A, B the
+  Gram matrices of the two operands (by default the diagonal of a square `want`)."""
+  want = np.asarray(want, np.float64)
+  if diag_a is None:
+    diag_a = diag_b = np.diag(want)
+  scale = np.sqrt(np.outer(np.asarray(diag_a, np.float64), np.asarray(diag_b, np.float64)))
+  return float(np.max(np.abs(np.asarray(got, np.float64) - want) / scale))
+
+
+def weight_rel(got, want):
+  """Element-wise distance of weights: max |dW| / |W| over the entries with |W| > 1e-3 max |W|."""
+  want = np.asarray(want, np.float64)
+  keep = np.abs(want) > 1e-3 * np.max(np.abs(want))
+  return float(np.max(np.abs(np.asarray(got, np.float64)[keep] - want[keep]) / np.abs(want[keep])))

@@ -36,6 +36,23 @@ def test_g1_lag_literals():
   np.testing.assert_array_equal(m[0], [0, 0, 0, 1000, 1, 1001, 2, 1002])
 
 
+@pytest.mark.parametrize('c,pre,post', [(2, 2, 0), (2, 0, 2), (3, 1, 2), (64, 0, 31)])
+def test_g1b_lag_matches_the_preprocessor_context_builder(c, pre, post):
+  """A1 against the reference's second lag builder, preprocess.Preprocessor.add_context, whole
+  and streamed in three uneven calls: the same layout, zero-padded head rows included; the last
+  `post` rows are the ones that builder holds back for the next call."""
+  g = golden('g1b_preprocess_context')
+  key = 'c%d_pre%d_post%d' % (c, pre, post)
+  x = g[key + '_x']
+  n = x.shape[0]
+  want = o_lag.lag_matrix(x, pre, post)[:n - post]
+  assert want.shape == (n - post, c * (pre + 1 + post))
+  np.testing.assert_array_equal(g[key + '_whole'], want)
+  np.testing.assert_array_equal(g[key + '_streamed'], want)
+  if pre:
+    assert not np.any(want[0, :c])         # the padded head is really there
+
+
 def _c1_files(g, nf, dt):
   files = []
   for i in range(nf):
