@@ -588,6 +588,46 @@ int td_decode_fused(td_handle* h, const float* eeg_dev, int64_t ldx, int c, int 
                     int hop, const double* corr_host, double* scores_dev,
                     uint8_t* decisions_dev);
 
+/* ------------------------------------------------------------------ preprocessing
+ * preprocess.Preprocessor (preprocess.py:54-587): the signal conditioning before the fits.
+ *
+ * td_sos_filter: a cascade of num_sections <= 16 second-order sections (scipy.signal.sosfilt,
+ * direct form II transposed, a0 = 1; float64 arithmetic whatever the input) over x [N, c] (float32,
+ * or float64 when x_is_f64), files concatenated along time (file_offsets_host[F+1]).  sos_host
+ * [S][6]; zi_host [S][2] the sosfilt_zi of each STAGE (sections [0, stage_split) and
+ * [stage_split, S) -- the high-pass and the low-pass -- each designed on its own).
+ * state_dev [S, 2, c] float64 is the carried filter state (scipy's zi layout): read when reset == 0
+ * for the first file, written with the final state of the last file.  A reset (reset != 0 for the
+ * first file, always for the later ones) starts the first stage from zi * x[first row] and the second
+ * from zi * (the first stage's output at that row), preprocess.py:293-352.
+ * out_rows_dev (device, int64, may be NULL): the file-local input rows to store, nondecreasing, file f's
+ * at [out_offsets_host[f], out_offsets_host[f+1]) -- the nearest-neighbour resample
+ * (preprocess.py:376-389) fused into the store; y_dev row out_offsets[f] + i.  NULL: every row,
+ * y_dev row file_offsets[f] + t.  y_dev float64, row stride ldy. */
+int td_sos_filter(td_handle* h, const void* x_dev, int x_is_f64, int64_t ldx, int c,
+                  const int64_t* file_offsets_host, int num_files, const double* sos_host, int num_sections,
+                  int stage_split, const double* zi_host, int reset, double* state_dev,
+                  const int64_t* out_rows_dev, const int64_t* out_offsets_host, double* y_dev, int64_t ldy);
+/* Re-referencing by groups and channel selection in one pass (preprocess.py:417-443): row r of
+ * z_dev [m, cs] float64 is row rows_dev[r] of x (rows_dev NULL: row r), every channel of group g
+ * (chan_idx_host[chan_ptr_host[g] .. chan_ptr_host[g+1]]) minus the mean of that row's reference
+ * channels (ref_idx_host[ref_ptr_host[g] ..]) taken BEFORE any group is subtracted, groups in order;
+ * then output column j = channel sel_host[j] (NULL: j). */
+int td_reref_select(td_handle* h, const void* x_dev, int x_is_f64, int64_t ldx, int c, const int64_t* rows_dev,
+                    int64_t m, int num_groups, const int* ref_ptr_host, const int* ref_idx_host,
+                    const int* chan_ptr_host, const int* chan_idx_host, const int* sel_host, int cs,
+                    double* z_dev, int64_t ldz);
+/* The float64 mean of all m x cs entries of z (np.mean, preprocess.py:445-455) into mean_dev[0]. */
+int td_mean_f64(td_handle* h, const double* z_dev, int64_t m, int cs, int64_t ldz, double* mean_dev);
+/* Normalisation and temporal context in one pass (preprocess.py:463-527): the rows
+ * [state ; (z - mean) / std_dev] (state_dev [state_rows, cs], already normalised) become
+ * state_rows + m - pre - post output rows of (pre + post + 1) * cs columns, block b of row r = row
+ * r + b; written as float32 (out32_dev) and / or float64 (out64_dev), row stride ldout.  The last
+ * min(state_rows + m, pre + post) rows go to state_out_dev (not aliasing state_dev). */
+int td_context_out(td_handle* h, const double* z_dev, int64_t m, int cs, int64_t ldz, const double* state_dev,
+                   int64_t state_rows, int pre, int post, double mean, double std_dev, float* out32_dev,
+                   double* out64_dev, int64_t ldout, double* state_out_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -775,3 +775,80 @@ def decode_fused(eeg, env, trial_offsets, w, b, pre, post, width, hop, corr, han
                                 len(offs) - 1, int(width), int(hop), cr_p, _ptr(scores),
                                 _ptr(decisions)))
   return scores, decisions
+
+
+def sos_filter(x, file_offsets, sos, zi, stage_split, state, reset, out_rows=None, out_offsets=None, handle=None):
+  """The SOS cascade over x [N, C] (float32 / float64 device tensor), files concatenated along time:
+  float64 output [N, C], or only the file-local rows out_rows (device int64, file f's at
+  out_offsets[f]:out_offsets[f+1]) -- the resample fused into the store.  state [S, 2, C] float64 on the
+  device carries the filter between calls (td_sos_filter)."""
+  h = handle or default_handle()
+  offs, offs_p = _lib.i64_array(file_offsets)
+  sos_a, sos_p = _lib.f64_array(sos)
+  zi_a, zi_p = _lib.f64_array(zi)
+  c = int(x.shape[1])
+  if out_rows is not None:
+    oo, oo_p = _lib.i64_array(out_offsets)
+    y = h.empty((int(oo[-1]), c), 'float64')
+  else:
+    oo_p = None
+    y = h.empty((int(offs[-1]), c), 'float64')
+  is64 = 1 if x.dtype == _torch().float64 else 0
+  h.check(h.lib.td_sos_filter(h.ptr, _ptr(x), is64, x.stride(0), c, offs_p, len(offs) - 1, sos_p,
+                              int(sos_a.shape[0]), int(stage_split), zi_p, 1 if reset else 0, _ptr(state),
+                              _ptr(out_rows), oo_p, _ptr(y), y.stride(0)))
+  return y
+
+
+def _i32_array(values):
+  arr = np.ascontiguousarray(values, dtype=np.int32)
+  return arr, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+
+
+def reref_select(x, rows=None, groups=(), select=None, handle=None):
+  """Re-referencing by groups and channel selection (td_reref_select): float64 [M, len(select)].
+  groups: [(reference channels, channels to re-reference)] in order; rows: device int64 row gather."""
+  h = handle or default_handle()
+  c = int(x.shape[1])
+  m = int(rows.shape[0]) if rows is not None else int(x.shape[0])
+  sel = list(range(c)) if select is None else [int(v) for v in select]
+  ref_ptr, ref_idx, ch_ptr, ch_idx = [0], [], [0], []
+  for ref, chans in groups:
+    ref_idx += [int(v) for v in ref]
+    ch_idx += [int(v) for v in chans]
+    ref_ptr.append(len(ref_idx))
+    ch_ptr.append(len(ch_idx))
+  keep = [_i32_array(v or [0]) for v in (ref_ptr, ref_idx, ch_ptr, ch_idx, sel)]
+  z = h.empty((m, len(sel)), 'float64')
+  is64 = 1 if x.dtype == _torch().float64 else 0
+  h.check(h.lib.td_reref_select(h.ptr, _ptr(x), is64, x.stride(0), c, _ptr(rows), m, len(groups),
+                                keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1], len(sel), _ptr(z),
+                                z.stride(0)))
+  return z
+
+
+def mean_f64(z, handle=None):
+  """The float64 mean of every entry of z, as a device scalar tensor (td_mean_f64)."""
+  h = handle or default_handle()
+  out = h.empty((1,), 'float64')
+  h.check(h.lib.td_mean_f64(h.ptr, _ptr(z), int(z.shape[0]), int(z.shape[1]), z.stride(0), _ptr(out)))
+  return out
+
+
+def context_out(z, state, pre, post, mean, std, dtype='float32', handle=None):
+  """[state ; (z - mean) / std] with pre / post rows of temporal context (td_context_out):
+  returns (output [rows, (pre + post + 1) * C] of `dtype`, the new state [<= pre + post, C] float64)."""
+  h = handle or default_handle()
+  cs = int(z.shape[1])
+  state_rows = int(state.shape[0]) if state is not None else 0
+  rows = state_rows + int(z.shape[0]) - pre - post
+  if rows < 0:
+    raise ValueError('%d rows cannot hold %d + %d rows of temporal context' % (rows + pre + post, pre, post))
+  out = h.empty((rows, (pre + post + 1) * cs), dtype)
+  keep = min(state_rows + int(z.shape[0]), pre + post)
+  new_state = h.empty((keep, cs), 'float64') if keep else None
+  o32, o64 = (out, None) if dtype == 'float32' else (None, out)
+  h.check(h.lib.td_context_out(h.ptr, _ptr(z), int(z.shape[0]), cs, z.stride(0), _ptr(state), state_rows, int(pre),
+                               int(post), float(mean), float(std), _ptr(o32), _ptr(o64), out.stride(0) if rows else
+                               (pre + post + 1) * cs, _ptr(new_state)))
+  return out, new_state

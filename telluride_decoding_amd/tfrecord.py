@@ -384,9 +384,15 @@ def select_streams(features, in1_fields, out_field, in2_fields=None, attended_fi
 
 def dataset_from_files(filenames, in1_fields, out_field, in2_fields=None, attended_field=None,
                        batch_size=512, pre_context=0, post_context=0, in2_pre_context=0,
-                       in2_post_context=0, input_offset=0):
+                       in2_post_context=0, input_offset=0, preprocess=None, frame_rate=None):
   """TFRecord files -> brain_data.Dataset (one file = one recording; context never crosses
-  files, brain_data.py:722-724).  Files whose name contains '-bad-' are skipped (:677)."""
+  files, brain_data.py:722-724).  Files whose name contains '-bad-' are skipped (:677).
+
+  preprocess (opt-in): {field: preprocess.Preprocessor or 'name(key=val;...)' string} applied to that
+  field of every recording on the GPU before the fields are selected, its state reset at each file
+  (Preprocessor.process_files).  A string builds a Preprocessor at frame_rate in and out, as the
+  reference's brain_data.preprocess_list does (brain_data.py:766-774).  The steps must leave every field of
+  a recording with the same number of frames."""
   from telluride_decoding_amd import brain_data
   wanted = set([in1_fields] if isinstance(in1_fields, str) else in1_fields)
   wanted |= set([] if not in2_fields else ([in2_fields] if isinstance(in2_fields, str) else in2_fields))
@@ -394,12 +400,26 @@ def dataset_from_files(filenames, in1_fields, out_field, in2_fields=None, attend
     wanted.add(out_field)
   if attended_field:
     wanted.add(attended_field)
+  preprocessors = {}
+  for field, spec in (preprocess or {}).items():
+    if isinstance(spec, str):
+      if frame_rate is None:
+        raise ValueError('a preprocess string for %s needs frame_rate' % field)
+      from telluride_decoding_amd import preprocess as pp
+      spec = pp.Preprocessor(spec, frame_rate, frame_rate)
+    preprocessors[field] = spec
   files = []
   for name in filenames:
     if '-bad-' in name:
       continue
-    files.append(select_streams(read_file(name, fields=wanted), in1_fields, out_field, in2_fields,
-                                attended_field))
+    features = read_file(name, fields=wanted)
+    for field, p in preprocessors.items():
+      if field not in features:
+        raise ValueError('Could not find preprocess field %s in data (%s)' % (field, sorted(features)))
+      data = features[field]
+      out, _ = p.process_files(data, [0, data.shape[0]])
+      features[field] = np.asarray(out, np.float32)
+    files.append(select_streams(features, in1_fields, out_field, in2_fields, attended_field))
   return brain_data.Dataset(files, batch_size, pre_context=pre_context, post_context=post_context,
                             in2_pre_context=in2_pre_context, in2_post_context=in2_post_context,
                             input_offset=input_offset)
