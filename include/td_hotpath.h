@@ -608,6 +608,10 @@ int td_sos_filter(td_handle* h, const void* x_dev, int x_is_f64, int64_t ldx, in
                   const int64_t* file_offsets_host, int num_files, const double* sos_host, int num_sections,
                   int stage_split, const double* zi_host, int reset, double* state_dev,
                   const int64_t* out_rows_dev, const int64_t* out_offsets_host, double* y_dev, int64_t ldy);
+/* The plan td_sos_filter follows for files of n_total rows in all, the longest n_max, over c channels:
+ * the time-chunk length each (chunk, channel) lane filters, and the number of levels of the chunk
+ * scan (blocks of 64 chunks per level).  Read-only; no handle. */
+int td_sos_filter_plan(int64_t n_total, int64_t n_max, int c, int* chunk, int* levels);
 /* Re-referencing by groups and channel selection in one pass (preprocess.py:417-443): row r of
  * z_dev [m, cs] float64 is row rows_dev[r] of x (rows_dev NULL: row r), every channel of group g
  * (chan_idx_host[chan_ptr_host[g] .. chan_ptr_host[g+1]]) minus the mean of that row's reference

@@ -125,6 +125,7 @@ SIGNATURES = {
     'td_decode_fused': [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _pi64, _i, _i,
                         _i, _pd, _vp, _vp],
     'td_sos_filter': [_vp, _vp, _i, _i64, _i, _pi64, _i, _pd, _i, _i, _pd, _i, _vp, _vp, _pi64, _vp, _i64],
+    'td_sos_filter_plan': [_i64, _i64, _i, _c.POINTER(_i), _c.POINTER(_i)],
     'td_reref_select': [_vp, _vp, _i, _i64, _i, _vp, _i64, _i, _c.POINTER(_i), _c.POINTER(_i),
                         _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _i, _vp, _i64],
     'td_mean_f64': [_vp, _vp, _i64, _i, _i64, _vp],

@@ -16,7 +16,13 @@
 //      output rows the resample keeps (all rows without one); the last chunk leaves the final state.
 // Lanes go over (chunk, channel) pairs with the channel fastest: a row of 64 channels is one
 // coalesced 256-B (float32) load, and one channel (an audio envelope) still fills whole waves with
-// chunks.  The matrices P^j are built on the host in float64 (a few 32 x 32 products).
+// chunks.
+// The scan is compensated.  P is strongly non-normal for a narrow high-pass (poles near z = 1: ||P^j|| up to
+// 1e37 at 16 + 16 sections), and a plain float64 scan left outputs ~1e-8 of max|x| away from the sequential
+// filter at fixed positions in the blocks.  So the host builds P^j in long double and
+// stores each as an unevaluated sum hi + lo of two doubles, every scan item is such a pair, and the scan
+// kernels carry P acc + e in double-double arithmetic (error-free products and sums).  The two passes over
+// x stay in plain float64: each chunk's start state is rounded once to the nearest double.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -56,11 +62,12 @@ __device__ __forceinline__ double load_x(const T* x, long long ldx, long long ro
   return (double)x[row * ldx + c];
 }
 
-// Item k of a scan buffer: D x C doubles, [j][c] -- the [S, 2, C] layout of scipy's zi.
+// Item k of a scan buffer: D x C doubles, [j][c] -- the [S, 2, C] layout of scipy's zi -- holding the high
+// parts of the double-double values; their low parts sit `lo` doubles further on.
 template <int S, typename T>
 __global__ void __launch_bounds__(kThreads)
 sos_chunk_end_kernel(const T* __restrict__ x, long long ldx, int c_count, int chunk, long long lanes,
-                     SosCoef k, double* __restrict__ items) {
+                     SosCoef k, double* __restrict__ items, long long lo) {
   const long long g = (long long)blockIdx.x * kThreads + threadIdx.x;
   if (g >= lanes) return;
   const long long ck = g / c_count;
@@ -72,7 +79,10 @@ sos_chunk_end_kernel(const T* __restrict__ x, long long ldx, int c_count, int ch
   for (int t = 0; t < chunk; ++t) sos_step<S>(k, z, load_x(x, ldx, t0 + t, c));
   double* dst = items + (ck + 1) * (2 * S) * (long long)c_count + c;   // item k+1 holds e_k
 #pragma unroll
-  for (int j = 0; j < 2 * S; ++j) dst[(long long)j * c_count] = z[j];
+  for (int j = 0; j < 2 * S; ++j) {
+    dst[(long long)j * c_count] = z[j];
+    dst[(long long)j * c_count + lo] = 0.0;
+  }
 }
 
 // Item 0: the file's initial state.  reset: sections [0, split) from x[0] * zi, sections [split, S)
@@ -81,9 +91,10 @@ sos_chunk_end_kernel(const T* __restrict__ x, long long ldx, int c_count, int ch
 template <int S, typename T>
 __global__ void __launch_bounds__(kThreads)
 sos_init_kernel(const T* __restrict__ x, int c_count, SosCoef k, int split, int reset,
-                const double* __restrict__ state, double* __restrict__ item0) {
+                const double* __restrict__ state, double* __restrict__ item0, long long lo) {
   const int c = blockIdx.x * kThreads + threadIdx.x;
   if (c >= c_count) return;
+  for (int j = 0; j < 2 * S; ++j) item0[(long long)j * c_count + c + lo] = 0.0;
   if (!reset) {
     for (int j = 0; j < 2 * S; ++j) item0[(long long)j * c_count + c] = state[(long long)j * c_count + c];
     return;
@@ -99,24 +110,56 @@ sos_init_kernel(const T* __restrict__ x, int c_count, SosCoef k, int split, int 
   }
 }
 
+// ---- double-double arithmetic (value = hi + lo, |lo| <= ulp(hi) / 2) --------------------------------
+// Contraction stays off here: a product fused into a neighbouring sum would break the error-free terms.
+__device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {
+#pragma clang fp contract(off)
+  s = a + b;
+  const double bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
+}
+
+// (h, l) += (ph, pl) x (vh, vl): the product ph vh exact (fma), the cross terms and the sum's error into l.
+__device__ __forceinline__ void dd_mac(double& h, double& l, double ph, double pl, double vh, double vl) {
+#pragma clang fp contract(off)
+  const double m = ph * vh;
+  const double me = __builtin_fma(ph, vh, -m);
+  double s, e;
+  two_sum(h, m, s, e);
+  h = s;
+  l += e + (me + __builtin_fma(ph, vl, pl * vh));
+}
+
+__device__ __forceinline__ void dd_norm(double& h, double& l) {
+#pragma clang fp contract(off)
+  const double s = h + l;
+  l = l - (s - h);
+  h = s;
+}
+
+// acc += P v in double-double; P row-major D x D, its low parts pl_off doubles after its high parts.
 template <int S>
-__device__ __forceinline__ void matvec_add(const double* __restrict__ p, const double (&v)[2 * S],
-                                           double (&acc)[2 * S]) {
+__device__ __forceinline__ void matvec_add_dd(const double* __restrict__ p, long long pl_off,
+                                              const double (&vh)[2 * S], const double (&vl)[2 * S],
+                                              double (&ah)[2 * S], double (&al)[2 * S]) {
 #pragma unroll
   for (int r = 0; r < 2 * S; ++r) {
-    double s = acc[r];
+    double h = ah[r], l = al[r];
 #pragma unroll
-    for (int q = 0; q < 2 * S; ++q) s += p[r * 2 * S + q] * v[q];
-    acc[r] = s;
+    for (int q = 0; q < 2 * S; ++q) dd_mac(h, l, p[r * 2 * S + q], p[r * 2 * S + q + pl_off], vh[q], vl[q]);
+    dd_norm(h, l);
+    ah[r] = h;
+    al[r] = l;
   }
 }
 
 // Lanes over (block b, channel): items [bG, bG + G) become inclusive prefixes out_k = P out_(k-1) + v_k
-// within the block; tot[b] (if given) receives the block's last prefix.
+// within the block; tot[b] (if given) receives the block's last prefix.  Items, tot: low parts lo doubles
+// on; p: P^1 of this level, low parts pl_off doubles on.
 template <int S>
 __global__ void __launch_bounds__(kThreads)
-sos_scan_local_kernel(double* __restrict__ items, long long n_items, int c_count, long long lanes,
-                      const double* __restrict__ p, double* __restrict__ tot) {
+sos_scan_local_kernel(double* __restrict__ items, long long lo, long long n_items, int c_count, long long lanes,
+                      const double* __restrict__ p, long long pl_off, double* __restrict__ tot) {
   const long long g = (long long)blockIdx.x * kThreads + threadIdx.x;
   if (g >= lanes) return;
   const long long b = g / c_count;
@@ -124,26 +167,37 @@ sos_scan_local_kernel(double* __restrict__ items, long long n_items, int c_count
   constexpr int D = 2 * S;
   const long long k0 = b * kScanGroup;
   const long long k1 = k0 + kScanGroup < n_items ? k0 + kScanGroup : n_items;
-  double acc[D];
-  double* it = items + k0 * D * (long long)c_count + c;
+  double ah[D], al[D];
+  const double* it = items + k0 * D * (long long)c_count + c;
 #pragma unroll
-  for (int j = 0; j < D; ++j) acc[j] = it[(long long)j * c_count];
+  for (int j = 0; j < D; ++j) {
+    ah[j] = it[(long long)j * c_count];
+    al[j] = it[(long long)j * c_count + lo];
+  }
   for (long long kk = k0 + 1; kk < k1; ++kk) {
     double* cur = items + kk * D * (long long)c_count + c;
-    double nxt[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) nxt[j] = cur[(long long)j * c_count];
-    matvec_add<S>(p, acc, nxt);
+    double nh[D], nl[D];
 #pragma unroll
     for (int j = 0; j < D; ++j) {
-      acc[j] = nxt[j];
-      cur[(long long)j * c_count] = nxt[j];
+      nh[j] = cur[(long long)j * c_count];
+      nl[j] = cur[(long long)j * c_count + lo];
+    }
+    matvec_add_dd<S>(p, pl_off, ah, al, nh, nl);
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      ah[j] = nh[j];
+      al[j] = nl[j];
+      cur[(long long)j * c_count] = nh[j];
+      cur[(long long)j * c_count + lo] = nl[j];
     }
   }
   if (tot) {
     double* dst = tot + b * D * (long long)c_count + c;
 #pragma unroll
-    for (int j = 0; j < D; ++j) dst[(long long)j * c_count] = acc[j];
+    for (int j = 0; j < D; ++j) {
+      dst[(long long)j * c_count] = ah[j];
+      dst[(long long)j * c_count + lo] = al[j];
+    }
   }
 }
 
@@ -151,8 +205,8 @@ sos_scan_local_kernel(double* __restrict__ items, long long n_items, int c_count
 // block totals after their own (inclusive) scan: the true prefix at the end of block b-1.
 template <int S>
 __global__ void __launch_bounds__(kThreads)
-sos_scan_fix_kernel(double* __restrict__ items, long long n_items, int c_count, long long lanes,
-                    const double* __restrict__ ppow, const double* __restrict__ tot) {
+sos_scan_fix_kernel(double* __restrict__ items, long long lo, long long n_items, int c_count, long long lanes,
+                    const double* __restrict__ ppow, long long pl_off, const double* __restrict__ tot) {
   const long long g = (long long)blockIdx.x * kThreads + threadIdx.x;
   if (g >= lanes) return;
   constexpr int D = 2 * S;
@@ -161,16 +215,21 @@ sos_scan_fix_kernel(double* __restrict__ items, long long n_items, int c_count, 
   const long long b = kk / kScanGroup;
   const int j = (int)(kk - b * kScanGroup);
   const double* prev = tot + (b - 1) * D * (long long)c_count + c;
-  double v[D], acc[D];
+  double vh[D], vl[D], ah[D], al[D];
   double* cur = items + kk * D * (long long)c_count + c;
 #pragma unroll
   for (int q = 0; q < D; ++q) {
-    v[q] = prev[(long long)q * c_count];
-    acc[q] = cur[(long long)q * c_count];
+    vh[q] = prev[(long long)q * c_count];
+    vl[q] = prev[(long long)q * c_count + lo];
+    ah[q] = cur[(long long)q * c_count];
+    al[q] = cur[(long long)q * c_count + lo];
   }
-  matvec_add<S>(ppow + (long long)j * D * D, v, acc);
+  matvec_add_dd<S>(ppow + (long long)j * D * D, pl_off, vh, vl, ah, al);
 #pragma unroll
-  for (int q = 0; q < D; ++q) cur[(long long)q * c_count] = acc[q];
+  for (int q = 0; q < D; ++q) {
+    cur[(long long)q * c_count] = ah[q];
+    cur[(long long)q * c_count + lo] = al[q];
+  }
 }
 
 __device__ __forceinline__ long long lower_bound_rows(const long long* rows, long long m, long long t) {
@@ -187,7 +246,7 @@ __device__ __forceinline__ long long lower_bound_rows(const long long* rows, lon
 template <int S, typename T>
 __global__ void __launch_bounds__(kThreads)
 sos_chunk_out_kernel(const T* __restrict__ x, long long ldx, int c_count, long long n, int chunk,
-                     long long lanes, SosCoef k, const double* __restrict__ items,
+                     long long lanes, SosCoef k, const double* __restrict__ items, long long lo,
                      const long long* __restrict__ rows, long long m, double* __restrict__ y, long long ldy,
                      double* __restrict__ final_state) {
   const long long g = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -197,7 +256,7 @@ sos_chunk_out_kernel(const T* __restrict__ x, long long ldx, int c_count, long l
   double z[2 * S];
   const double* it = items + ck * (2 * S) * (long long)c_count + c;
 #pragma unroll
-  for (int j = 0; j < 2 * S; ++j) z[j] = it[(long long)j * c_count];
+  for (int j = 0; j < 2 * S; ++j) z[j] = it[(long long)j * c_count] + it[(long long)j * c_count + lo];
   const long long t0 = ck * chunk;
   const long long t1 = t0 + chunk < n ? t0 + chunk : n;
   if (rows) {
@@ -221,36 +280,83 @@ sos_chunk_out_kernel(const T* __restrict__ x, long long ldx, int c_count, long l
 }
 
 // ---- host: the cascade's state-transition matrix and its powers ----------------------------------
-void step_host(const double* sos, int s_count, double* z, double x) {
+// (long double: the x86-64 host's 64-bit significand, 11 bits past a double's)
+using ldouble = long double;
+
+void step_host(const double* sos, int s_count, ldouble* z, ldouble x) {
   for (int i = 0; i < s_count; ++i) {
     const double* c = sos + 6 * i;
-    const double y = c[0] * x + z[2 * i];
+    const ldouble y = c[0] * x + z[2 * i];
     z[2 * i] = c[1] * x - c[4] * y + z[2 * i + 1];
     z[2 * i + 1] = c[2] * x - c[5] * y;
     x = y;
   }
 }
 
-void matmul(const std::vector<double>& a, const std::vector<double>& b, int d, std::vector<double>* out) {
-  std::vector<double> r((size_t)d * d, 0.0);
+void matmul(const std::vector<ldouble>& a, const std::vector<ldouble>& b, int d, std::vector<ldouble>* out) {
+  std::vector<ldouble> r((size_t)d * d, 0.0L);
   for (int i = 0; i < d; ++i)
     for (int q = 0; q < d; ++q) {
-      const double aiq = a[(size_t)i * d + q];
-      if (aiq == 0.0) continue;
+      const ldouble aiq = a[(size_t)i * d + q];
+      if (aiq == 0.0L) continue;
       for (int j = 0; j < d; ++j) r[(size_t)i * d + j] += aiq * b[(size_t)q * d + j];
     }
   *out = std::move(r);
 }
 
-std::vector<double> mat_pow(const std::vector<double>& a, int d, long long e) {
-  std::vector<double> r((size_t)d * d, 0.0), base = a;
-  for (int i = 0; i < d; ++i) r[(size_t)i * d + i] = 1.0;
+std::vector<ldouble> mat_pow(const std::vector<ldouble>& a, int d, long long e) {
+  std::vector<ldouble> r((size_t)d * d, 0.0L), base = a;
+  for (int i = 0; i < d; ++i) r[(size_t)i * d + i] = 1.0L;
   while (e > 0) {
     if (e & 1) matmul(r, base, d, &r);
     e >>= 1;
     if (e) matmul(base, base, d, &base);
   }
   return r;
+}
+
+// The scan's tables for one cascade, chunk length and depth: level l's P_l^1 .. P_l^G (P_0 = A^chunk,
+// P_(l+1) = P_l^G), row-major D x D each, all high parts, then all low parts.  A stream of calls with one
+// Preprocessor asks for the same tables every time, so the last set built on this thread is kept.
+const std::vector<double>& scan_tables(const double* sos, int s_count, int chunk, int n_levels) {
+  thread_local std::vector<double> key, tables;
+  std::vector<double> want(sos, sos + 6 * s_count);
+  want.push_back(chunk);
+  want.push_back(n_levels);
+  if (want == key) return tables;
+  const int d = 2 * s_count;
+  std::vector<ldouble> a((size_t)d * d);       // the one-sample transition (x = 0)
+  for (int q = 0; q < d; ++q) {
+    std::vector<ldouble> z(d, 0.0L);
+    z[q] = 1.0L;
+    step_host(sos, s_count, z.data(), 0.0L);
+    for (int r = 0; r < d; ++r) a[(size_t)r * d + q] = z[r];
+  }
+  std::vector<ldouble> full;
+  std::vector<ldouble> p = mat_pow(a, d, chunk);
+  for (int l = 0; l < n_levels; ++l) {
+    std::vector<ldouble> pj = p;
+    for (int j = 0; j < kScanGroup; ++j) {      // P^1 .. P^G
+      full.insert(full.end(), pj.begin(), pj.end());
+      if (j + 1 < kScanGroup) matmul(pj, p, d, &pj);
+    }
+    p = pj;
+  }
+  tables.resize(2 * full.size());
+  for (size_t i = 0; i < full.size(); ++i) {
+    const double hi = (double)full[i];
+    tables[i] = hi;
+    tables[full.size() + i] = (double)(full[i] - (ldouble)hi);
+  }
+  key = std::move(want);
+  return tables;
+}
+
+// chunk length: enough (chunk, channel) lanes to fill the chip several times over, long chunks otherwise
+int sos_chunk(int64_t n_total, int c) {
+  int chunk = 256;
+  while (chunk > 16 && (n_total / chunk) * (int64_t)c < (int64_t)64 * 1024) chunk >>= 1;
+  return chunk;
 }
 
 struct ScanLevel {
@@ -280,17 +386,8 @@ int sos_filter_t(td_handle* h, const T* x, int64_t ldx, int c, const int64_t* of
     n_max = std::max(n_max, n);
     n_total += n;
   }
-  // chunk length: enough (chunk, channel) lanes to fill the chip several times over, long chunks otherwise
-  int chunk = 256;
-  while (chunk > 16 && (n_total / chunk) * (int64_t)c < (int64_t)64 * 1024) chunk >>= 1;
-  // the one-sample transition A (x = 0) and the level matrices P_l = A^(chunk G^l)
-  std::vector<double> a((size_t)D * D);
-  for (int q = 0; q < D; ++q) {
-    std::vector<double> z(D, 0.0);
-    z[q] = 1.0;
-    step_host(sos, S, z.data(), 0.0);
-    for (int r = 0; r < D; ++r) a[(size_t)r * D + q] = z[r];
-  }
+  const int chunk = sos_chunk(n_total, c);
+  // the levels of the scan (items are double-double: high parts in [0, work), low parts in [work, 2 work))
   std::vector<ScanLevel> levels;
   const long long n_chunks_max = (n_max + chunk - 1) / chunk;
   size_t work = 0;
@@ -299,21 +396,14 @@ int sos_filter_t(td_handle* h, const T* x, int64_t ldx, int c, const int64_t* of
     work += (size_t)n * D * c;
     if (n <= kScanGroup) break;
   }
-  std::vector<double> tables;
-  std::vector<double> p = mat_pow(a, D, chunk);
-  for (size_t l = 0; l < levels.size(); ++l) {
-    levels[l].pow_off = tables.size();
-    std::vector<double> pj = p;
-    for (int j = 0; j < kScanGroup; ++j) {      // P^1 .. P^G
-      tables.insert(tables.end(), pj.begin(), pj.end());
-      if (j + 1 < kScanGroup) matmul(pj, p, D, &pj);
-    }
-    p = pj;                    // P_(l+1) = P_l^G
-  }
+  const std::vector<double>& tables = scan_tables(sos, S, chunk, (int)levels.size());
+  const long long tab_lo = (long long)(tables.size() / 2);
+  for (size_t l = 0; l < levels.size(); ++l) levels[l].pow_off = l * kScanGroup * D * D;
+  const long long lo = (long long)work;
   void* scratch = nullptr;
-  TD_TRY(td_scratch(h, (work + tables.size()) * sizeof(double), &scratch));
+  TD_TRY(td_scratch(h, (2 * work + tables.size()) * sizeof(double), &scratch));
   double* wbuf = reinterpret_cast<double*>(scratch);
-  double* tab = wbuf + work;
+  double* tab = wbuf + 2 * work;
   TD_TRY(td_upload_async(h, tables.data(), tables.size() * sizeof(double), tab));
   for (int f = 0; f < num_files; ++f) {
     const int64_t n = offs[f + 1] - offs[f];
@@ -321,11 +411,11 @@ int sos_filter_t(td_handle* h, const T* x, int64_t ldx, int c, const int64_t* of
     const long long nch = (n + chunk - 1) / chunk;
     double* items = wbuf;
     hipLaunchKernelGGL((sos_init_kernel<S, T>), dim3((unsigned)td_ceil_div(c, kThreads)), dim3(kThreads), 0,
-                       h->stream, xf, c, k, split, (f > 0 || reset) ? 1 : 0, state, items);
+                       h->stream, xf, c, k, split, (f > 0 || reset) ? 1 : 0, state, items, lo);
     if (nch > 1) {
       const long long lanes = (nch - 1) * c;
       hipLaunchKernelGGL((sos_chunk_end_kernel<S, T>), dim3((unsigned)td_ceil_div(lanes, kThreads)),
-                         dim3(kThreads), 0, h->stream, xf, (long long)ldx, c, chunk, lanes, k, items);
+                         dim3(kThreads), 0, h->stream, xf, (long long)ldx, c, chunk, lanes, k, items, lo);
       // upward: scan every level's blocks, handing the block totals to the next level
       long long n_items = nch;
       int depth = 0;
@@ -337,8 +427,8 @@ int sos_filter_t(td_handle* h, const T* x, int64_t ldx, int c, const int64_t* of
         double* tot = nb > 1 ? wbuf + levels[depth + 1].items_off : nullptr;
         const long long lanes_l = nb * c;
         hipLaunchKernelGGL((sos_scan_local_kernel<S>), dim3((unsigned)td_ceil_div(lanes_l, kThreads)),
-                           dim3(kThreads), 0, h->stream, it, n_items, c, lanes_l,
-                           tab + levels[depth].pow_off, tot);
+                           dim3(kThreads), 0, h->stream, it, lo, n_items, c, lanes_l,
+                           tab + levels[depth].pow_off, tab_lo, tot);
         if (nb == 1) break;
         n_items = nb;
       }
@@ -346,8 +436,8 @@ int sos_filter_t(td_handle* h, const T* x, int64_t ldx, int c, const int64_t* of
       for (int l = depth - 1; l >= 0; --l) {
         const long long lanes_f = (n_at[l] - kScanGroup) * c;
         hipLaunchKernelGGL((sos_scan_fix_kernel<S>), dim3((unsigned)td_ceil_div(lanes_f, kThreads)),
-                           dim3(kThreads), 0, h->stream, wbuf + levels[l].items_off, n_at[l], c, lanes_f,
-                           tab + levels[l].pow_off, wbuf + levels[l + 1].items_off);
+                           dim3(kThreads), 0, h->stream, wbuf + levels[l].items_off, lo, n_at[l], c,
+                           lanes_f, tab + levels[l].pow_off, tab_lo, wbuf + levels[l + 1].items_off);
       }
     }
     const long long lanes = nch * c;
@@ -355,7 +445,7 @@ int sos_filter_t(td_handle* h, const T* x, int64_t ldx, int c, const int64_t* of
     const long long m = out_rows_dev ? out_offs[f + 1] - out_offs[f] : n;
     double* yf = y + (out_rows_dev ? out_offs[f] : offs[f]) * ldy;
     hipLaunchKernelGGL((sos_chunk_out_kernel<S, T>), dim3((unsigned)td_ceil_div(lanes, kThreads)), dim3(kThreads), 0,
-                       h->stream, xf, (long long)ldx, c, (long long)n, chunk, lanes, k, items, rows, m, yf,
+                       h->stream, xf, (long long)ldx, c, (long long)n, chunk, lanes, k, items, lo, rows, m, yf,
                        (long long)ldy, f == num_files - 1 ? state : nullptr);
   }
   TD_HIP(h, hipGetLastError());
@@ -488,6 +578,15 @@ context_state_kernel(const double* __restrict__ z, long long ldz, int cs, const 
 }  // namespace
 
 extern "C" {
+
+int td_sos_filter_plan(int64_t n_total, int64_t n_max, int c, int* chunk, int* levels) {
+  if (n_total < 1 || n_max < 1 || n_max > n_total || c < 1 || !chunk || !levels) return TD_ERR_INVALID;
+  *chunk = sos_chunk(n_total, c);
+  *levels = 1;
+  for (long long n = (n_max + *chunk - 1) / *chunk; n > kScanGroup; n = (n + kScanGroup - 1) / kScanGroup)
+    ++*levels;
+  return TD_OK;
+}
 
 int td_sos_filter(td_handle* h, const void* x_dev, int x_is_f64, int64_t ldx, int c,
                   const int64_t* file_offsets_host, int num_files, const double* sos_host, int num_sections,

@@ -800,6 +800,17 @@ def sos_filter(x, file_offsets, sos, zi, stage_split, state, reset, out_rows=Non
   return y
 
 
+def sos_filter_plan(n_total, n_max, c, handle=None):
+  """(chunk, scan levels) that sos_filter uses for files of n_total rows in all, the longest n_max, over c
+  channels (td_sos_filter_plan)."""
+  h = handle or default_handle()
+  chunk, levels = ctypes.c_int(0), ctypes.c_int(0)
+  rc = h.lib.td_sos_filter_plan(int(n_total), int(n_max), int(c), ctypes.byref(chunk), ctypes.byref(levels))
+  if rc != 0:
+    raise ValueError('sos_filter_plan: bad sizes (%d, %d, %d)' % (n_total, n_max, c))
+  return int(chunk.value), int(levels.value)
+
+
 def _i32_array(values):
   arr = np.ascontiguousarray(values, dtype=np.int32)
   return arr, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
@@ -844,6 +855,8 @@ def context_out(z, state, pre, post, mean, std, dtype='float32', handle=None):
   rows = state_rows + int(z.shape[0]) - pre - post
   if rows < 0:
     raise ValueError('%d rows cannot hold %d + %d rows of temporal context' % (rows + pre + post, pre, post))
+  if int(z.shape[0]) == 0:      # (a file that resampled to no rows: nothing to write, the state carries on)
+    return h.empty((0, (pre + post + 1) * cs), dtype), state
   out = h.empty((rows, (pre + post + 1) * cs), dtype)
   keep = min(state_rows + int(z.shape[0]), pre + post)
   new_state = h.empty((keep, cs), 'float64') if keep else None

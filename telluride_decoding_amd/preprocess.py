@@ -551,9 +551,12 @@ class Preprocessor(object):
     file as a fresh recording (filter states reset at its first row, resample phase and context restarted),
     as process(file, reset=True) after context_reset() would treat it.  Returns (output, output file
     offsets).  A frozen data_mean=None comes from the first file."""
+    offs = [int(v) for v in file_offsets]
+    if self.sos is not None and any(b == a for a, b in zip(offs, offs[1:])):
+      raise ValueError('process_files: an empty file with a filter on (its reset reads the first row, as '
+                       'the reference\'s highpass_filter_reset does)')
     x, on_dev = self._to_device(data)
     self.check_dims(x)
-    offs = [int(v) for v in file_offsets]
     if offs[0] != 0 or offs[-1] != int(x.shape[0]) or any(b < a for a, b in zip(offs, offs[1:])):
       raise ValueError('file_offsets must run from 0 to %d, nondecreasing' % int(x.shape[0]))
     self._next_frame_idx = 0

@@ -1,5 +1,7 @@
-"""Host float64 restatement of the preprocessing chain (scipy's sosfilt recurrence written out in NumPy,
-vectorised over channels), for the CPU tests against G16, and P1's input.  Test infrastructure."""
+"""Host float64 restatement of the preprocessing chain, for the CPU tests against G16 and the GPU sweep, and
+P1's input.  The sequential filter is scipy.signal.sosfilt (the reference's own routine) where scipy imports,
+else scipy's recurrence written out in NumPy (vectorised over channels, one Python step per frame: callers
+shorten long inputs to NUMPY_MAX_ROWS on that path).  REF_PATH says which one runs.  Test infrastructure."""
 import json
 
 import numpy as np
@@ -24,6 +26,32 @@ def sosfilt(sos, x, zi):
   return y, z
 
 
+def _scipy_signal():
+  try:
+    import scipy.signal as ss
+  except ImportError:
+    return None
+  return ss
+
+
+REF_PATH = 'scipy' if _scipy_signal() is not None else 'numpy'
+NUMPY_MAX_ROWS = 20000
+
+
+def ref_rows(n):
+  """The rows a long case keeps: all of them with scipy, at most NUMPY_MAX_ROWS on the NumPy path."""
+  return n if REF_PATH == 'scipy' else min(n, NUMPY_MAX_ROWS)
+
+
+def sosfilt_ref(sos, x, zi):
+  """The float64 sequential reference filter: (y, final state), x [N, C], zi [S, 2, C]."""
+  x = np.asarray(x, np.float64)
+  zi = np.asarray(zi, np.float64)
+  if REF_PATH == 'scipy':
+    return _scipy_signal().sosfilt(sos, x, axis=0, zi=zi)
+  return sosfilt(sos, x, zi)
+
+
 class HostPreprocessor(object):
   """The reference's Preprocessor.process, restated on the host with the package's own designer."""
 
@@ -45,7 +73,7 @@ class HostPreprocessor(object):
     for i, (sos, zi) in enumerate(self.stages):
       if self.states[i] is None or reset:
         self.states[i] = y[0, :].astype(np.float64) * zi[:, :, None]
-      y, self.states[i] = sosfilt(sos, y, self.states[i])
+      y, self.states[i] = sosfilt_ref(sos, y, self.states[i])
     y = y.astype(np.float64)
     if self.kw['fs_out'] != self.kw['fs_in']:
       assert self.next_idx == 0

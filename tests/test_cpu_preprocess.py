@@ -155,3 +155,27 @@ def test_host_restatement_against_g16(g16, name):
     s += m
   if h.stages:
     assert np.max(np.abs(h.state() - g16[name + '_stream_state'])) <= 1e-9 * scale
+
+
+def test_reference_paths_agree():
+  """The two host reference filters (scipy's sosfilt, the NumPy recurrence) agree on a small hard case: a
+  high-pass order 5 at 0.5 Hz and a low-pass order 7 at 3.75 Hz at 1 kHz, DC-offset input."""
+  signal = pytest.importorskip('scipy.signal')
+  sos = np.concatenate([iir.butter_sos(5, 0.5, 'hp', 1000), iir.butter_sos(7, 3.75, 'lp', 1000)])
+  rng = np.random.default_rng(3)
+  x = 2.0 + rng.standard_normal((3000, 3))
+  zi = iir.sosfilt_zi(sos)[:, :, None] * x[0]
+  y_np, z_np = hp.sosfilt(sos, x, zi)
+  y_sp, z_sp = signal.sosfilt(sos, x, axis=0, zi=zi)
+  scale = float(np.max(np.abs(x)))
+  d = max(float(np.max(np.abs(y_np - y_sp))), float(np.max(np.abs(z_np - z_sp)))) / scale
+  assert d <= 1e-12, d
+  assert hp.REF_PATH == 'scipy'
+  np.testing.assert_array_equal(hp.sosfilt_ref(sos, x, zi)[0], y_sp)
+
+
+def test_process_files_rejects_empty_file_with_filter():
+  p = pp.Preprocessor('eeg', 100, 100, highpass_cutoff=1, highpass_order=2)
+  x = np.ones((10, 2), np.float32)
+  with pytest.raises(ValueError, match='empty file'):
+    p.process_files(x, [0, 4, 4, 10])
