@@ -238,13 +238,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_resident_kernel(CgParams P) {
     int it = 0;
     bool check_pass = false;       // the product in flight is A x (true residual), not A r
     const bool done = bnorm2 == 0.0;         // b = 0: x = 0
-#ifdef TD_CG_TIMING
-    long long tph[6] = {0, 0, 0, 0, 0, 0};
-#define TD_CG_T(i) do { const long long now_ = wall_clock64(); tph[i] += now_ - tlast; tlast = now_; } while (0)
-    long long tlast = wall_clock64();
-#else
-#define TD_CG_T(i)
-#endif
     while (!done) {
       // -- my rows of the product with r (or with x for the final check, whose s^T x is summed here):
       // a thread multiplies the columns of the entries it owns, so the vector never leaves its registers
@@ -284,7 +277,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_resident_kernel(CgParams P) {
       } else {
         ++it;
       }
-      TD_CG_T(0);
       // 8 sums per lane -> 1: three exchange-and-halve steps (lane ^ 1, ^ 2, ^ 4) leave lane l with the
       // sum over its group of 8 lanes of row ((l & 1) << 2) | (l & 2) | ((l >> 2) & 1)
       double a4[4], a2[2], a1;
@@ -307,7 +299,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_resident_kernel(CgParams P) {
       if (lane < 8) red[wave * 8 + lane] = a1;     // lane l < 8: row ((l & 1) << 2) | (l & 2) | ((l >> 2) & 1)
       __syncthreads();
       if (check_pass) sdot = wave_parts(part_a, 1, 0);
-      TD_CG_T(1);
       ++round;
       unsigned long long* buf = P.packets + (size_t)(round & 1u) * 2 * k;
       if (t < R && i0 + t < k) {
@@ -315,10 +306,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_resident_kernel(CgParams P) {
         const double tot = wave_parts(red, 8, pi);
         ll_store(buf + 2 * (i0 + t), tot + lam * prow[t] - srow_t * (sdot * inv_ckk), round);
       }
-      TD_CG_T(2);
-#ifdef TD_CG_TIMING
-      if (it == 20 && t == 0) reinterpret_cast<long long*>(P.abort_word + 64)[w] = wall_clock64();
-#endif
       // -- every entry of the product.  256 workgroups x 2048 packets x 16 bytes are 8 MB per pass over the
       // buffer, and a pass that finds nothing is traffic in front of the very stores it waits for: a
       // thread first watches ONE packet (of a workgroup 32 j0 away from its first: the watched ones
@@ -371,10 +358,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_resident_kernel(CgParams P) {
         }
       }
       if (gave_up) s_abort = 1;
-#ifdef TD_CG_TIMING
-      if (it == 20 && t == 0) reinterpret_cast<long long*>(P.abort_word + 64)[512 + w] = wall_clock64();
-#endif
-      TD_CG_T(3);
       // -- ONE reduction: r^T r, w^T r, s^T w (in the check pass: |b - A x|^2)
       double e0 = 0.0, e1 = 0.0, e2 = 0.0;
 #pragma unroll
@@ -393,7 +376,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_resident_kernel(CgParams P) {
       const double gamma = wave_parts(part_b, 4, 0);
       const double delta = wave_parts(part_b, 4, 1);
       const double sw = wave_parts(part_b, 4, 2);
-      TD_CG_T(4);
       if (check_pass) {
         if (!(gamma <= P.accept * P.tol2 * bnorm2)) status = 2;   // (also catches NaN)
         break;
@@ -421,11 +403,7 @@ __global__ __launch_bounds__(kCgThreads) void cg_resident_kernel(CgParams P) {
       sdot -= alpha * sv;
       gamma_old = gamma;
       denom_old = denom;
-      TD_CG_T(5);
     }
-#ifdef TD_CG_TIMING
-    if (w == 0 && t == 0) for (int i = 0; i < 6; ++i) P.status[2 + i] = (int)tph[i];
-#endif
     iters_max = it > iters_max ? it : iters_max;
     if (aborted || status != 0) break;
     // bias = (b_k - s^T x) / c, and the weights (workgroup 0 writes)
@@ -669,13 +647,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_toeplitz_kernel(CgtParams P) {
     int it = 0;
     bool check_pass = false;
     const bool done = bnorm2 == 0.0;
-#ifdef TD_CGT_TIMING
-    long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    long long tlast = wall_clock64();
-#define TD_CGT_T(i) do { const long long now_ = wall_clock64(); tph[i] += now_ - tlast; tlast = now_; } while (0)
-#else
-#define TD_CGT_T(i)
-#endif
     while (!done) {
       // -- the multiplied vector (r, or x in the check pass) -> LDS
 #pragma unroll
@@ -695,7 +666,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_toeplitz_kernel(CgtParams P) {
       __syncthreads();
       if (check_pass) sdot = wave_parts(part_a, 1, 0);
       ++round;
-      TD_CGT_T(0);
       // -- my q numbers: published first, the T part runs while they travel
       unsigned long long* const qbuf = q_pk + (size_t)(round & 1u) * 2 * kCgtMaxQ;
       if (q_on) {                          // (wave-uniform)
@@ -729,7 +699,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_toeplitz_kernel(CgtParams P) {
         }
       }
       // -- T part of my rows a = 4 wave + r: lane j multiplies the columns (., j)
-      TD_CGT_T(1);
       // (row a = a0 + r needs G[l2 - a] against the column block l2: a window of kRw table rows that
       // slides by one per block -- one new 8-byte read per lane and block)
       double acc[kRw];
@@ -771,7 +740,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_toeplitz_kernel(CgtParams P) {
           wnd[0] = l2 + 1 < L ? gp[(l2 + 1) * 64] : 0.0;
         }
       }
-      TD_CGT_T(2);
       // -- every q number
       {
         const long long t_wait = wall_clock64();
@@ -784,7 +752,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_toeplitz_kernel(CgtParams P) {
         if (!ok) s_abort = 1;
       }
       __syncthreads();
-      TD_CGT_T(3);
       // -- E part: row a takes - sum_f sum_{s < a} x_f[s][i] q_f[s - a]  (wi holds the sign)
       if (has_rows && !s_abort) {
         const double* wi = wi_all + ci * kCgtMaxQ;
@@ -818,7 +785,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_toeplitz_kernel(CgtParams P) {
         }
       }
       __syncthreads();
-      TD_CGT_T(4);
       // -- publish my L rows: one contiguous run of packets (workgroup-major packet order)
       unsigned long long* const buf = row_pk + (size_t)(round & 1u) * 2 * kCgtRowPackets;
       if (pub) {
@@ -860,18 +826,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_toeplitz_kernel(CgtParams P) {
         }
         if (gave_up) s_abort = 1;
       }
-#ifdef TD_CGT_DEBUG      // development: the first product (and the vector it was taken with) instead of a solve
-      if (blockIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < kCgMaxCols; ++j) {
-          const int c = cg_col(t, j);
-          if (c < k) { P.w[c] = (float)wq[j]; P.w[k + c] = (float)r_[j]; }
-        }
-      }
-      status = 5;
-      break;
-#endif
-      TD_CGT_T(5);
       // -- ONE reduction: r^T r, w^T r, s^T w (in the check pass: |b - A x|^2)
       double e0 = 0.0, e1 = 0.0, e2 = 0.0;
 #pragma unroll
@@ -887,7 +841,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_toeplitz_kernel(CgtParams P) {
       if (lane == 0) { part_b[4 * wave] = e0; part_b[4 * wave + 1] = e1; part_b[4 * wave + 2] = e2; }
       __syncthreads();
       if (s_abort) { aborted = true; break; }
-      TD_CGT_T(6);
       const double gamma = wave_parts(part_b, 4, 0);
       const double delta = wave_parts(part_b, 4, 1);
       const double sw = wave_parts(part_b, 4, 2);
@@ -919,9 +872,6 @@ __global__ __launch_bounds__(kCgThreads) void cg_toeplitz_kernel(CgtParams P) {
       gamma_old = gamma;
       denom_old = denom;
     }
-#ifdef TD_CGT_TIMING
-    if (blockIdx.x == 0 && t == 0) for (int ii = 0; ii < 7; ++ii) P.status[2 + ii] = (int)tph[ii];
-#endif
     iters_max = it > iters_max ? it : iters_max;
     if (aborted || status != 0) break;
     __syncthreads();
@@ -990,7 +940,7 @@ int td_cg_solve_dense(td_handle* h, const double* xtx, int n, int ld, const doub
   p.inv = inv; p.tol2 = tol * tol; p.accept = accept;
   p.n = n; p.ld = ld; p.d = d; p.n_lambda = n_lambda; p.k = k; p.rows = rows; p.max_iter = max_iter;
   p.gate = gate ? 1 : 0;
-  p.trace_pk = h->cg_packets + 2 * 2 * kCgThreads * kCgMaxCols + (256 + 8192) / 8;      // behind the abort word and the timing area
+  p.trace_pk = h->cg_packets + 2 * 2 * kCgThreads * kCgMaxCols + (256 + 8192) / 8;      // behind the abort word and 8 KB once used by timing stamps
   p.epoch = h->cg_epoch;
   p.limit_ticks = 100000LL * 20;          // 20 ms at 100 MHz
   if (h->cg_limit_ticks >= 0) p.limit_ticks = h->cg_limit_ticks;      // td_set_option("cg_limit_ticks"): 0 = give up at the first empty poll
@@ -1081,14 +1031,5 @@ int td_cg_solve_compact(td_handle* h, const StatsCompact& sc, const double* lams
   else
     hipLaunchKernelGGL(cg_toeplitz_kernel<2>, dim3((unsigned)((C + 1) / 2)), dim3(kCgThreads), lds_bytes(2), h->stream, p);
   TD_HIP(h, hipGetLastError());
-#ifdef TD_CGT_TIMING
-  {
-    int st[9] = {0};
-    hipStreamSynchronize(h->stream);
-    hipMemcpy(st, status_dev, sizeof(st), hipMemcpyDeviceToHost);
-    fprintf(stderr, "cgt phases (10 ns ticks over %d iterations): vec+barrier %d q %d T %d poll-q+barrier %d E+sums+barrier %d publish+poll-rows %d reduction %d\n",
-            st[1], st[2], st[3], st[4], st[5], st[6], st[7], st[8]);
-  }
-#endif
   return TD_OK;
 }

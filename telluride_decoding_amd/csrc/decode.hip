@@ -1584,208 +1584,6 @@ __global__ __launch_bounds__(64 * kProjWaves, 3) void cca_project_kernel(ProjPar
   }
 }
 
-// ---- one-output FIR prediction without workgroup barriers ---------------------------------------
-//   out[t] = b + sum_l sum_c x~[t + l - pre][c] W[l][c]                       (brain_model.py:335-341)
-// P[u][l] = sum_c x[u][c] W[l][c] is a product with M = time, N = lag (<= 32), K = channel (<= 64),
-// and out[t] is the sum of the diagonal P[t + l - pre][l].  predict_fir_mfma_kernel above stages a
-// P tile in LDS and walks its diagonals (~300 non-matrix instructions per 32 rows that ADD to its
-// matrix and memory time: 73 us at C4, 4.2 TB/s).  Here, as in gram_bf16x3_kernel / cca_project_kernel:
-//   * a WAVE owns a strip of outputs and walks 16-row tiles of x; it loads them with whole-line
-//     float4s two tiles ahead, writes them row-major into a wave-private LDS tile (row stride 68
-//     floats: the b128 operand reads of 16 rows hit 64 different banks), reads back 8 consecutive
-//     channels of ITS row per lane -- the A operand of v_mfma_f32_16x16x32_bf16 after the exact
-//     three-way bf16 split -- against the weights held split in registers;
-//   * the diagonal sums stay in registers: a C register of lane (lag l, row quarter q) belongs to
-//     output u0 + 4 q + r - l, the (at most four) lanes of a diagonal are 20 lanes apart -- two
-//     shuffle-and-add steps -- and one more shuffle hands the sum to the lane that owns that
-//     output in a 64-lane ring of running sums (lane D <-> output u0 + D - 31 + pre).  After a
-//     tile the 16 oldest outputs are final, leave with the bias, and the ring moves down 16 lanes.
-// No workgroup barrier, no LDS atomics, 24 MFMAs + ~25 shuffles per 16 rows.
-constexpr int kFir16Ld = 68;
-#ifndef TD_FIR16_ABL
-#define TD_FIR16_ABL 0      // development: 1 no diagonal shuffles, 2 no split / MFMA, 3 no streaming loads
-#endif
-
-struct Fir16Params {
-  const float* x;
-  long long ldx;
-  const FileDesc* files;
-  int n_files;
-  long long n_strips;
-  int strip, c, pre, post;
-  const float* w;        // [nl * c][d]
-  const float* bias;     // [d] or null
-  int d, q0;             // outputs per weight row; which one this launch computes
-  float* out;
-  long long ldout;
-};
-
-__global__ __launch_bounds__(kThreads, 3) void fir_tile16_kernel(Fir16Params p) {
-  __shared__ __attribute__((aligned(16))) float lds[(kThreads / 64) * 16 * kFir16Ld];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long long sidx = blockIdx.x * (long long)(kThreads / 64) + wave;
-  if (sidx >= p.n_strips) return;
-  const FileDesc st = p.files[find_file(p.files, p.n_files, sidx)];
-  const long long s0 = (sidx - st.first) * p.strip;             // first output of the strip
-  const int st_len = (int)(st.nrows - s0 < p.strip ? st.nrows - s0 : p.strip);
-  const int nl = p.pre + 1 + p.post;
-  float* tile = lds + wave * 16 * kFir16Ld;
-  const int li = lane & 15, kq = lane >> 4;
-
-  // weights as the B operand: lane (lag n = li of n tile nt, k quarter kq): channels 32 s + 8 kq + kk
-  pj_u32x4 wh[2][2], wm[2][2], wl[2][2];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      float v[8];
-      const int l = 16 * nt + li;
-#pragma unroll
-      for (int kk = 0; kk < 8; ++kk) {
-        const int ch = 32 * s2 + 8 * kq + kk;
-        v[kk] = (l < nl && ch < p.c) ? p.w[((size_t)l * p.c + ch) * p.d + p.q0] : 0.f;
-      }
-#pragma unroll
-      for (int dd = 0; dd < 4; ++dd) {
-        unsigned a, b, c3;
-        td_split3(v[2 * dd], v[2 * dd + 1], a, b, c3);
-        wh[nt][s2][dd] = a; wm[nt][s2][dd] = b; wl[nt][s2][dd] = c3;
-      }
-    }
-  const float bq = p.bias ? p.bias[p.q0] : 0.f;
-
-  // diagonal bookkeeping (lane constants).  C register r of n tile nt in lane (l, q) is
-  // P[u0 + 4 q + r][16 nt + l], ring slot D = (4 q + r) - (16 nt + l) + 31.
-  //   step 1: + the lane 40 up (l + 8, q + 2), step 2: + the lane 20 up (l + 4, q + 1);
-  //   the lowest lane of a diagonal (l < 4 or q = 0) then holds its sum.
-  const float m40 = (li + 8 <= 15 && kq + 2 <= 3) ? 1.f : 0.f, m20 = (li + 4 <= 15 && kq + 1 <= 3) ? 1.f : 0.f;
-  // for ring slot D = lane and (nt, r): the diagonal e = 4 q - l = D - 31 - r + 16 nt; its lowest
-  // lane is q = max(0, ceil(e / 4)), l = 4 q - e (valid for -15 <= e <= 12)
-  int src[2][4];
-  float msrc[2][4];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int e = lane - 31 - r + 16 * nt;
-      const int q = e > 0 ? (e + 3) >> 2 : 0;
-      const int l = 4 * q - e;
-      const bool ok = e >= -15 && e <= 12 && l <= 15 && q <= 3;
-      msrc[nt][r] = ok ? 1.f : 0.f;
-      src[nt][r] = ok ? l + 16 * q : 0;
-    }
-
-  // tiles: x rows u0 = s0 - pre + 16 k; the last one that matters holds row s0 + st_len - 1 + post
-  const long long u_first = s0 - p.pre;
-  const int n_tiles = (st_len + nl - 1 + 15) / 16;
-  const int c4 = (lane & 15) * 4, r0 = lane >> 4;
-  const bool col_ok = c4 < p.c;
-  const float* xb = p.x + st.row0 * p.ldx + (col_ok ? c4 : 0);
-  // a tile wholly inside the trial, 64 real channels: no clamps, no masks
-  auto interior = [&](long long u0) -> bool { return p.c == 64 && u0 >= 0 && u0 + 16 <= st.nrows; };
-  const int ldx32 = (int)p.ldx;
-  auto load_tile = [&](int k, float4 (&pf)[4]) {
-    const long long u0 = u_first + 16LL * k;
-    if (interior(u0)) {
-      const float* tb = xb + u0 * p.ldx;               // wave-uniform base + 32-bit lane offsets
-#pragma unroll
-      for (int j = 0; j < 4; ++j) pf[j] = *reinterpret_cast<const float4*>(tb + (r0 + 4 * j) * ldx32);
-      return;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      long long u = u0 + r0 + 4 * j;
-      u = u < 0 ? 0 : (u >= st.nrows ? st.nrows - 1 : u);           // clamped: masked when stored
-      pf[j] = *reinterpret_cast<const float4*>(xb + u * p.ldx);
-    }
-  };
-  auto store_tile = [&](int k, const float4 (&pf)[4]) {
-    const long long u0 = u_first + 16LL * k;
-    if (interior(u0)) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) *reinterpret_cast<float4*>(tile + (r0 + 4 * j) * kFir16Ld + c4) = pf[j];
-      return;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long long u = u0 + r0 + 4 * j;
-      const bool ok = col_ok && u >= 0 && u < st.nrows;              // x~ is zero outside the trial
-      float4 v = pf[j];
-      v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f;
-      *reinterpret_cast<float4*>(tile + (r0 + 4 * j) * kFir16Ld + c4) = v;
-    }
-  };
-  float ring = 0.f;                                    // lane D: running sum of output u0 + D - 31 + pre
-  auto emit = [&](long long u0) {
-    // lanes 0..15 hold final outputs t = u0 + D - 31 + pre
-    const long long t = u0 + lane - 31 + p.pre;
-    if (lane < 16 && t >= s0 && t < s0 + st_len) p.out[(st.out0 + t) * p.ldout + p.q0] = ring + bq;
-    const float up = __shfl_down(ring, 16, 64);
-    ring = lane < 48 ? up : 0.f;
-  };
-  float4 pfa[4], pfb[4];                               // tiles k (even) / k + 1 (odd) in flight
-  load_tile(0, pfa);
-  if (n_tiles > 1) load_tile(1, pfb);
-#define TD_FIR16_TILE(K, PF)                                                                    \
-  {                                                                                             \
-    const int k_ = (K);                                                                         \
-    store_tile(k_, PF);                                                                         \
-    if (k_ + 2 < n_tiles && TD_FIR16_ABL != 3) load_tile(k_ + 2, PF);                           \
-    __builtin_amdgcn_wave_barrier();                                                            \
-    pj_f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};                              \
-    const float* row = tile + li * kFir16Ld + 8 * kq;                                           \
-    _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2) {                                          \
-      const float4 v0 = *reinterpret_cast<const float4*>(row + 32 * s2);                        \
-      const float4 v1 = *reinterpret_cast<const float4*>(row + 32 * s2 + 4);                    \
-      pj_u32x4 zh, zm, zl;                                                                      \
-      unsigned a_, b_, c_;                                                                      \
-      td_split3(v0.x, v0.y, a_, b_, c_); zh[0] = a_; zm[0] = b_; zl[0] = c_;                    \
-      td_split3(v0.z, v0.w, a_, b_, c_); zh[1] = a_; zm[1] = b_; zl[1] = c_;                    \
-      td_split3(v1.x, v1.y, a_, b_, c_); zh[2] = a_; zm[2] = b_; zl[2] = c_;                    \
-      td_split3(v1.z, v1.w, a_, b_, c_); zh[3] = a_; zm[3] = b_; zl[3] = c_;                    \
-      if (TD_FIR16_ABL == 2) { c0[0] += v0.x * v1.y; c1[1] += v0.z * v1.w; continue; }         \
-      TD_FIR16_MFMA(c0, zl, wh[0][s2]); TD_FIR16_MFMA(c1, zl, wh[1][s2]);                       \
-      TD_FIR16_MFMA(c0, zh, wl[0][s2]); TD_FIR16_MFMA(c1, zh, wl[1][s2]);                       \
-      TD_FIR16_MFMA(c0, zm, wm[0][s2]); TD_FIR16_MFMA(c1, zm, wm[1][s2]);                       \
-      TD_FIR16_MFMA(c0, zm, wh[0][s2]); TD_FIR16_MFMA(c1, zm, wh[1][s2]);                       \
-      TD_FIR16_MFMA(c0, zh, wm[0][s2]); TD_FIR16_MFMA(c1, zh, wm[1][s2]);                       \
-      TD_FIR16_MFMA(c0, zh, wh[0][s2]); TD_FIR16_MFMA(c1, zh, wh[1][s2]);                       \
-    }                                                                                           \
-    __builtin_amdgcn_wave_barrier();                   /* the tile may be overwritten */        \
-    float add = 0.f;                                                                            \
-    if (TD_FIR16_ABL == 1) add = c0[0] + c1[1] + c0[2] + c1[3];                                 \
-    else {                                                                                      \
-      /* the three shuffle levels of the eight (n tile, register) chains, level by level: the  \
-         eight shuffles of a level are in flight together (one LDS round trip per level, not   \
-         per shuffle); masks as 0/1 factors (one fma instead of select + add) */                \
-      float v_[8], t_[8];                                                                       \
-      _Pragma("unroll") for (int r = 0; r < 4; ++r) { v_[r] = c0[r]; v_[4 + r] = c1[r]; }       \
-      _Pragma("unroll") for (int i = 0; i < 8; ++i) t_[i] = __shfl_down(v_[i], 40, 64);         \
-      _Pragma("unroll") for (int i = 0; i < 8; ++i) v_[i] = fmaf(t_[i], m40, v_[i]);            \
-      _Pragma("unroll") for (int i = 0; i < 8; ++i) t_[i] = __shfl_down(v_[i], 20, 64);         \
-      _Pragma("unroll") for (int i = 0; i < 8; ++i) v_[i] = fmaf(t_[i], m20, v_[i]);            \
-      _Pragma("unroll") for (int i = 0; i < 8; ++i) t_[i] = __shfl(v_[i], src[i >> 2][i & 3], 64); \
-      _Pragma("unroll") for (int i = 0; i < 8; ++i) add = fmaf(t_[i], msrc[i >> 2][i & 3], add); \
-    }                                                                                           \
-    ring += add;                                                                                \
-    emit(u_first + 16LL * k_);                                                                  \
-  }
-#define TD_FIR16_MFMA(C, A, B) C = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                      \
-      __builtin_bit_cast(td_bf16x8, A), __builtin_bit_cast(td_bf16x8, B), C, 0, 0, 0)
-  int k = 0;
-  for (; k + 1 < n_tiles; k += 2) {
-    TD_FIR16_TILE(k, pfa)
-    TD_FIR16_TILE(k + 1, pfb)
-  }
-  if (k < n_tiles) TD_FIR16_TILE(k, pfa)
-#undef TD_FIR16_TILE
-#undef TD_FIR16_MFMA
-  // the ring still holds the outputs of the last 31 rows: two more emissions flush them
-  emit(u_first + 16LL * n_tiles);
-  emit(u_first + 16LL * (n_tiles + 1));
-}
-
 // ---- one-output FIR prediction, streamed through LDS by DMA (round 4) ---------------------------
 //   out[t] = b + sum_l sum_c x~[t + l - pre][c] W[l][c]                       (brain_model.py:335-341)
 // The same product as above with the operands SWAPPED: P[l][u] = sum_c W[l][c] x[u][c], M = lag,
@@ -1817,26 +1615,12 @@ __global__ __launch_bounds__(kThreads, 3) void fir_tile16_kernel(Fir16Params p) 
 // A wave owns a strip of outputs of one recording.  No workgroup barrier anywhere.
 typedef int fs_i32x4 __attribute__((ext_vector_type(4)));
 constexpr int kFsSlotFloats = 32 * 64;     // one tile: 32 rows x 64 channels
-#ifndef TD_FS_SLOTS
-#define TD_FS_SLOTS 2
-#endif
-#ifndef TD_FS_OCC
-#define TD_FS_OCC 2
-#endif
-#define FS_NODMA (TD_FS_ABL == 2 || (TD_FS_ABL >= 6 && TD_FS_ABL <= 9))   // (18 / 19: 8 / 9 with the DMA)
-#ifndef TD_FS_THREADS
-#define TD_FS_THREADS 256
-#endif
-constexpr int kFsThreads = TD_FS_THREADS;  // waves x 64 per workgroup
-constexpr int kFsSlots = TD_FS_SLOTS;      // tiles of LDS per wave (1 or 2)
-constexpr int kFsOcc = TD_FS_OCC;          // workgroups (of four waves) per CU
+constexpr int kFsThreads = 256;            // waves x 64 per workgroup
+constexpr int kFsSlots = 2;                // tiles of LDS per wave (1 or 2)
+constexpr int kFsOcc = 2;                  // workgroups (of four waves) per CU
 // (the DMA's LDS address goes through M0; every configuration measured and shipped keeps a workgroup's
 // tiles inside its first 64 KB -- larger offsets through M0 are not something this code has verified)
 static_assert(sizeof(float) * (kFsThreads / 64) * kFsSlots * kFsSlotFloats <= 65536, "fir_stream_kernel: LDS tiles past 64 KB");
-#ifndef TD_FS_ABL
-#define TD_FS_ABL 0     // development: 1 no matrix instructions, 2 no DMA after the first two tiles, 3 no chains, 4 DMA only,
-                        // 5 setup only, 6 = 2 + no products / chains, 7 = 2 + no chains
-#endif
 
 // A wave's strip: recording, first output, outputs.
 struct FsStrip {
@@ -1856,7 +1640,6 @@ struct FirStreamParams {
   float* out;
   long long ldout;
   const FsStrip* strips; // [n_strips]: recording, first output and length of every strip
-  long long* dbg;        // development (-DTD_FS_TIMING): [strip][2] start / end of every wave, 10 ns ticks
   // a slice of a wider / longer filter: this launch multiplies the channels [ch0, ch0 + c) of rows of
   // c_all channels by the lags [lag0, lag0 + nl) of a filter of c_all channels, and (accum) adds to out
   int ch0, c_all, lag0, accum;
@@ -1864,10 +1647,8 @@ struct FirStreamParams {
 };
 
 // the 8 DMA instructions of one tile: LDS slot at byte address lds (wave-uniform), lane offsets v[m]
-#ifndef TD_FS_AUX
 #define TD_FS_AUX " nt"  // cache policy of the DMA: the rows are read once -- non-temporal (C4 decode on inputs that
                          // no cache holds: 72.5 -> 67.7 us; replayed from the Infinity Cache: 66.2 -> 66.9; " sc1": 73.4)
-#endif
 __device__ __forceinline__ void fs_issue_tile(fs_i32x4 rs, unsigned lds, const unsigned (&v)[8]) {
   unsigned keep;
   asm volatile(
@@ -1965,9 +1746,6 @@ __global__ __launch_bounds__(kFsThreads, kOcc) void fir_stream_kernel(FirStreamP
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long long sidx = blockIdx.x * (long long)(kFsThreads / 64) + wave;
   if (sidx >= p.n_strips) return;
-#ifdef TD_FS_TIMING
-  const long long t_begin = wall_clock64();
-#endif
   const FsStrip sd = p.strips[sidx];
   const FileDesc st = p.files[__builtin_amdgcn_readfirstlane(sd.file)];
   const long long ts = __builtin_amdgcn_readfirstlane(sd.first);     // first output of the strip
@@ -2056,7 +1834,7 @@ __global__ __launch_bounds__(kFsThreads, kOcc) void fir_stream_kernel(FirStreamP
   auto fetch = [&](int t, float4 (&xb)[8]) {
     // (tiles t+1 .. t+kSlots-1 may still be on their way: 8 DMA instructions each)
     const int ahead = n_tiles - 1 - t < kSlots - 1 ? n_tiles - 1 - t : kSlots - 1;
-    if (FS_NODMA || ahead <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (ahead <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     else if (kDw) {
       // (32 instructions per tile, 40 with the narrow tile)
       if (ahead == 1 && kNar) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
@@ -2080,7 +1858,7 @@ __global__ __launch_bounds__(kFsThreads, kOcc) void fir_stream_kernel(FirStreamP
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
   auto refill = [&](int t) {
-    if (!FS_NODMA && t + kSlots < n_tiles) issue(t + kSlots);
+    if (t + kSlots < n_tiles) issue(t + kSlots);
   };
   // kF16: the power-of-two scale of a row (its 64 samples' largest magnitude into [2^13, 2^14)) and
   // the factor that takes a result back
@@ -2117,13 +1895,6 @@ __global__ __launch_bounds__(kFsThreads, kOcc) void fir_stream_kernel(FirStreamP
   auto products = [&](const float4 (&xa)[8], f32x16& a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) a[r] = 0.f;
-    if (TD_FS_ABL == 1 || TD_FS_ABL == 4 || TD_FS_ABL == 6 || TD_FS_ABL == 10 || TD_FS_ABL == 11) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) a[k] = xa[k].x + xa[k].y + xa[k].z + xa[k].w;
-      if (TD_FS_ABL == 10) __builtin_amdgcn_s_sleep(20);     // ~0.55 us of nothing per tile
-      if (TD_FS_ABL == 11) __builtin_amdgcn_s_sleep(40);     // ~1.1 us
-      return;
-    }
     if (kF16) {
       // every row as two float16 pieces (td_common.h): three products per k-step of 16 channels
       // instead of 8 float32 ones
@@ -2132,16 +1903,7 @@ __global__ __launch_bounds__(kFsThreads, kOcc) void fir_stream_kernel(FirStreamP
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         td_u32x4 ah, al;
-        if (TD_FS_ABL % 10 == 9) {        // no split: the rows' bits as they are
-          ah = __builtin_bit_cast(td_u32x4, xa[2 * j]); al = __builtin_bit_cast(td_u32x4, xa[2 * j + 1]);
-        } else {
-          split_step(xa, j, sa, ah, al);
-        }
-        if (TD_FS_ABL % 10 == 8) {        // no matrix instructions
-          a[4 * j] += __uint_as_float(ah[0] ^ al[1]); a[4 * j + 1] += __uint_as_float(ah[2] ^ al[3]);
-          a[4 * j + 2] += __uint_as_float(ah[1] ^ al[0]); a[4 * j + 3] += __uint_as_float(ah[3] ^ al[2]);
-          continue;
-        }
+        split_step(xa, j, sa, ah, al);
         a = td_mfma_f16(wl[j], ah, a);
         a = td_mfma_f16(wh[j], al, a);
         a = td_mfma_f16(wh[j], ah, a);
@@ -2232,7 +1994,6 @@ __global__ __launch_bounds__(kFsThreads, kOcc) void fir_stream_kernel(FirStreamP
     }
   }
   float low_prev = 0.f;
-  if (TD_FS_ABL == 5) { emit(0, wreg[0] + __uint_as_float(wh[0][0])); return; }
   // The 64 outputs of a pair leave one iteration late, BETWEEN the wait for a tile and the DMA that
   // refills its slot: vmcnt counts stores too and they retire out of order with the loads, so a wait
   // can only count the loads issued after the tile it needs -- a store issued just in front of such a
@@ -2250,14 +2011,6 @@ __global__ __launch_bounds__(kFsThreads, kOcc) void fir_stream_kernel(FirStreamP
       fetch(2 * pr + 1, xa);
       refill(2 * pr + 1);
       products(xa, b);
-    }
-    if (TD_FS_ABL >= 3) {
-      float sa = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sa += a[r] + b[r];
-      pend = low_prev + sa;
-      low_prev = sa;
-      continue;
     }
     // V[l]: lag l over the pair's 64 time columns
     float V[32];
@@ -2286,9 +2039,6 @@ __global__ __launch_bounds__(kFsThreads, kOcc) void fir_stream_kernel(FirStreamP
   }
   if (n_tiles >= 4) emit(n_tiles / 2 - 2, pend);
   emit(n_tiles / 2 - 1, low_prev);
-#ifdef TD_FS_TIMING
-  if (p.dbg && lane == 0) { p.dbg[2 * sidx] = t_begin; p.dbg[2 * sidx + 1] = wall_clock64(); }
-#endif
 }
 
 // ---- CCA transform without context, streamed (round 4) -------------------------------------------
@@ -2314,10 +2064,7 @@ struct ProjStreamParams {
   float* out;
 };
 constexpr int kPsWaveFloats = kFsSlotFloats + 32 * 8 + 32 * 17 + 16;   // x tile, x2 tile, result tile, bias
-#ifndef TD_PS_OCC
-#define TD_PS_OCC 3
-#endif
-constexpr int kPsOcc = TD_PS_OCC;          // workgroups (of four waves) per CU
+constexpr int kPsOcc = 3;                  // workgroups (of four waves) per CU
 static_assert(sizeof(float) * (kThreads / 64) * kPsWaveFloats <= 65536, "cca_project_stream_kernel: LDS tiles past 64 KB");
 
 template <int kOcc>
@@ -2596,9 +2343,6 @@ int launch_fir(td_handle* h, const float* x, int64_t ldx, const int64_t* offs, i
     bool stream_ok = !w_file_stride && d == 1 && nl <= 64 && c >= 1 && c <= 128 && ldx <= 8192;
     for (int f = 0; f < num_files && stream_ok; ++f)
       stream_ok = (offs[f + 1] - offs[f]) * ldx * 4 < (int64_t)0x7fc00000;
-#ifdef TD_DEV_SWITCHES
-    if (td_dev_env("TD_FIR_STREAM_OFF")) stream_ok = false;
-#endif
     if (stream_ok) {
       const int cus = h->cu_count > 0 ? h->cu_count : 256;
       // One strip per resident wave (kFsOcc workgroups of kFsThreads / 64 waves per CU): every recording
@@ -2641,42 +2385,6 @@ int launch_fir(td_handle* h, const float* x, int64_t ldx, const int64_t* offs, i
       fp.c = c; fp.pre = pre; fp.post = post; fp.w = w; fp.bias = bias; fp.d = d; fp.q0 = 0;
       fp.out = out; fp.ldout = ldout;
       fp.ch0 = 0; fp.c_all = c; fp.lag0 = 0; fp.accum = 0;
-      fp.dbg = nullptr;
-#ifdef TD_FS_TIMING
-      static long long* dbg_dev = nullptr;
-      static int dbg_calls = 0;
-      if (!dbg_dev) hipMalloc(reinterpret_cast<void**>(&dbg_dev), sizeof(long long) * 2 * 8192);
-      fp.dbg = n_strips <= 8192 ? dbg_dev : nullptr;
-      if (fp.dbg && ++dbg_calls == 50) {       // the 49th call's clocks: finish-time histogram
-        hipStreamSynchronize(h->stream);
-        std::vector<long long> hb(2 * n_strips);
-        hipMemcpy(hb.data(), dbg_dev, sizeof(long long) * 2 * n_strips, hipMemcpyDeviceToHost);
-        long long t0 = hb[0];
-        for (long long i = 0; i < n_strips; ++i) t0 = hb[2 * i] < t0 ? hb[2 * i] : t0;
-        int hs[16] = {0}, he[16] = {0};
-        for (long long i = 0; i < n_strips; ++i) {
-          int bs = (int)((hb[2 * i] - t0) / 500), be = (int)((hb[2 * i + 1] - t0) / 500);
-          hs[bs > 15 ? 15 : bs]++; he[be > 15 ? 15 : be]++;
-        }
-        fprintf(stderr, "fir_stream waves by 5 us bins since the first start:\n  start:");
-        for (int i = 0; i < 16; ++i) fprintf(stderr, " %d", hs[i]);
-        fprintf(stderr, "\n  end:  ");
-        for (int i = 0; i < 16; ++i) fprintf(stderr, " %d", he[i]);
-        fprintf(stderr, "\n  by wave of the workgroup (mean end, us):");
-        for (int k = 0; k < kFsThreads / 64; ++k) {
-          double m = 0; int cnt = 0;
-          for (long long i = k; i < n_strips; i += kFsThreads / 64) { m += (hb[2 * i + 1] - t0) * 0.01; ++cnt; }
-          fprintf(stderr, " %.1f", m / cnt);
-        }
-        fprintf(stderr, "\n  by block of 250 strips (mean start / end, us):");
-        for (long long k = 0; k < n_strips; k += 250) {
-          double ms = 0, me = 0; int cnt = 0;
-          for (long long i = k; i < k + 250 && i < n_strips; ++i) { ms += (hb[2 * i] - t0) * 0.01; me += (hb[2 * i + 1] - t0) * 0.01; ++cnt; }
-          fprintf(stderr, " %.1f/%.1f", ms / cnt, me / cnt);
-        }
-        fprintf(stderr, "\n");
-      }
-#endif
       constexpr size_t kLds = sizeof(float) * (kFsThreads / 64) * kFsSlots * kFsSlotFloats;
       constexpr size_t kLdsNar = kLds + sizeof(float) * (kFsThreads / 64) * kFsSlots * kFsNarFloats;
       if (!h->lds_opt_fir_stream) {
@@ -2713,36 +2421,9 @@ int launch_fir(td_handle* h, const float* x, int64_t ldx, const int64_t* offs, i
       return TD_OK;
     }
   }
-  // (Measured at C4, decode step: 90.1 us with fir_tile16_kernel against 86.3 us with
-  // predict_fir_mfma_kernel -- its split + MFMA cost 26 us and its loads 19 us that overlap only
-  // partly (ablations: profiles/NOTES.md 8) -- so the P-tile kernel stays the default and this one is opt-in.)
-  static const bool tile16 = td_dev_env("TD_FIR_TILE16") != nullptr;          // development: A/B runs
-  if (!w_file_stride && d == 1 && nl <= 32 && c >= 4 && c <= 64 && vec4 && tile16 && h->acc_mode != TD_ACC_F32) {
-    // one output: the barrier-free 16-row kernel (fir_tile16_kernel); 12 waves per CU, one round
-    const int cus = h->cu_count > 0 ? h->cu_count : 256;
-    int64_t strip = td_round_up(td_ceil_div(total, (int64_t)cus * 12), 16);
-    if (strip < 256) strip = 256;
-    std::vector<FileDesc> files(num_files);
-    long long n_strips = 0;
-    for (int f = 0; f < num_files; ++f) {
-      const int64_t n = offs[f + 1] - offs[f] - shift;
-      files[f].row0 = offs[f] + shift;
-      files[f].nrows = n > 0 ? n : 0;
-      files[f].out0 = offs[f];
-      files[f].first = n_strips;
-      if (n > 0) n_strips += td_ceil_div(n, strip);
-    }
-    TD_TRY(td_table_upload(h, files.data(), files.size() * sizeof(FileDesc), &table_dev));
-    Fir16Params fp;
-    fp.x = x; fp.ldx = ldx; fp.files = reinterpret_cast<const FileDesc*>(table_dev);
-    fp.n_files = num_files; fp.n_strips = n_strips; fp.strip = (int)strip;
-    fp.c = c; fp.pre = pre; fp.post = post; fp.w = w; fp.bias = bias; fp.d = d; fp.q0 = 0;
-    fp.out = out; fp.ldout = ldout;
-    hipLaunchKernelGGL(fir_tile16_kernel, dim3((unsigned)td_ceil_div(n_strips, kThreads / 64)),
-                       dim3(kThreads), 0, h->stream, fp);
-    TD_HIP(h, hipGetLastError());
-    return TD_OK;
-  }
+  // (A barrier-free one-output kernel on 16-row tiles, fir_tile16_kernel, measured 90.1 us at C4,
+  // decode step, against 86.3 us for predict_fir_mfma_kernel -- its split + MFMA cost 26 us and its
+  // loads 19 us that overlap only partly (ablations: profiles/NOTES.md 8); it was removed.)
   if (mfma_ok) {
     // strip length: one wave per resident slot -- the kernel holds kFirWavesPerCu waves per CU
     // (register / LDS limited), so total / (256 CUs * that) frames per wave runs the whole
@@ -2906,14 +2587,9 @@ int td_cca_transform(td_handle* h, const float* x_dev, int64_t ldx, int c1, int 
   TD_REQUIRE(h, ldout >= 2 * dims, "td_cca_transform: ldout too small");
   const int k1 = c1 * (pre1 + 1 + post1), k2 = c2 * (pre2 + 1 + post2);
   // no context on either view, aligned rows, at most 16 outputs: one fused pass (cca_project_kernel)
-#ifdef TD_DEV_SWITCHES
-  static const bool old_proj = td_dev_env("TD_PROJECT_F32") != nullptr;        // development: A/B runs
-#else
-  constexpr bool old_proj = false;
-#endif
   const bool aligned = (ldx % 4 == 0) && (c1 % 4 == 0) && ((reinterpret_cast<uintptr_t>(x_dev) & 15) == 0) &&
                        (ldx2 % 4 == 0) && (c2 % 4 == 0) && ((reinterpret_cast<uintptr_t>(x2_dev) & 15) == 0);
-  if (k1 == c1 && k2 == c2 && c1 <= 64 && c2 <= 32 && 2 * dims <= 16 && aligned && !old_proj &&
+  if (k1 == c1 && k2 == c2 && c1 <= 64 && c2 <= 32 && 2 * dims <= 16 && aligned &&
       h->acc_mode != TD_ACC_F32) {
     const int64_t dx = input_offset > 0 ? input_offset : 0, dy = input_offset < 0 ? -input_offset : 0;
     int64_t total = 0;
@@ -2926,9 +2602,6 @@ int td_cca_transform(td_handle* h, const float* x_dev, int64_t ldx, int c1, int 
       const int64_t n = file_offsets_host[f + 1] - file_offsets_host[f];
       stream_ok = n * ldx * 4 < (int64_t)0x7fc00000 && n * ldx2 * 4 < (int64_t)0x7fc00000;
     }
-#ifdef TD_DEV_SWITCHES
-    if (td_dev_env("TD_PROJECT_STREAM_OFF")) stream_ok = false;
-#endif
     if (stream_ok) {
       // one strip per resident wave (kPsOcc workgroups of four waves per CU), a multiple of 32 rows
       constexpr int wpg = kThreads / 64;

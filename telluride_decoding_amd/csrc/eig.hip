@@ -511,7 +511,7 @@ int sym_eig(td_handle* h, const double* a, int lda, int n, double* vals, double*
   hipLaunchKernelGGL(pad_sym_kernel, dim3(grid_for((long long)np * np)), dim3(256), 0, h->stream, a,
                      lda, n, np, ap, vp);
   P.a = ap; P.lda = np; P.n = np; P.direct = 0; P.nblocks = nblocks; P.jout = jm; P.vals = nullptr;
-  P.skip = skip; P.max_sweeps = td_dev_env("TD_EIG_INNER") ? atoi(td_dev_env("TD_EIG_INNER")) : kMaxInnerSweeps;
+  P.skip = skip; P.max_sweeps = kMaxInnerSweeps;
   BlockUpd U;
   U.a = ap; U.v = vp; U.np = np; U.nblocks = nblocks; U.j = jm; U.skip = skip;
   int sweep = 0;
@@ -535,7 +535,6 @@ int sym_eig(td_handle* h, const double* a, int lda, int n, double* vals, double*
     TD_HIP(h, hipMemcpyAsync(&rotated, counter, sizeof(unsigned int), hipMemcpyDeviceToHost,
                              h->stream));
     TD_HIP(h, hipStreamSynchronize(h->stream));
-    if (td_dev_env("TD_EIG_TRACE")) fprintf(stderr, "eig n=%d sweep %d: %u rotations\n", n, sweep, rotated);
     if (rotated == 0) break;
   }
   if (sweeps_out) *sweeps_out = sweep + 1;
@@ -823,8 +822,7 @@ int jacobi_svd(td_handle* h, double* g, int ldg, int k, int m, int dim, double* 
     if (sweeps_out) *sweeps_out = 0;
     return TD_OK;
   }
-  static const bool no_gram = td_dev_env("TD_SVD_JACOBI") != nullptr;         // development: A/B runs
-  if (k <= NB && k > 1 && m >= 4 * k && !no_gram) {
+  if (k <= NB && k > 1 && m >= 4 * k) {
     double* gg = norms + k;                              // [k][k]
     double* vals = gg + (size_t)k * k;                   // [k]; eigenvectors -> vt
     void* eig_ws = reinterpret_cast<char*>(vals + k);    // the eigen-solver's counter (256 bytes)
@@ -1050,12 +1048,6 @@ __global__ __launch_bounds__(256) void cca_small_kernel(CcaSmallParams P) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int k1 = P.k1, k2 = P.k2, dim = P.dim;
   const double* sum1 = P.sum1;
-#ifdef TD_CCA_STAMPS      // development: where the launch's time goes (100 MHz ticks behind the status word)
-#define TD_STAMP(i) do { if (tid == 0) reinterpret_cast<long long*>(P.status + 16)[i] = wall_clock64(); } while (0)
-#else
-#define TD_STAMP(i) do { } while (0)
-#endif
-  TD_STAMP(0);
   if (tid < k1) P.mean_x[tid] = (float)(sum1[tid] * P.inv_f);
   if (tid < k2) P.mean_y[tid] = (float)(P.sum2[tid] * P.inv_f);
   if (tid == 0) flag = 0;
@@ -1085,7 +1077,6 @@ __global__ __launch_bounds__(256) void cca_small_kernel(CcaSmallParams P) {
   };
   if (P.certificate && !factor(-P.eps)) { if (tid == 0) P.status[0] = 1; return; }
   if (!factor(0.0)) { if (tid == 0) P.status[0] = 1; return; }
-  TD_STAMP(1);
   // ---- cov_xy^T as rows, cov_yy + reg I and the identity
   for (int idx = tid; idx < k2 * NB; idx += 256) {
     const int q = idx >> 6, m = idx & 63;
@@ -1141,7 +1132,6 @@ __global__ __launch_bounds__(256) void cca_small_kernel(CcaSmallParams P) {
     }
   }
   __syncthreads();
-  TD_STAMP(2);
   if (!ychol) {
     // W = V f(lambda), f = lambda^-1/4 above eps, else 0 (cca.py:345-352); K22 = W W^T
     if (tid < k2 * k2) {
@@ -1170,7 +1160,6 @@ __global__ __launch_bounds__(256) void cca_small_kernel(CcaSmallParams P) {
   if (tid < 16 * 16) vs[(tid >> 4) * kCsLd + (tid & 15)] = (tid >> 4) == (tid & 15) ? 1.0 : 0.0;
   __syncthreads();
   const int k = k2, m = k1, kp = k + (k & 1);
-  TD_STAMP(3);
   // ---- the SVD through the k x k Gram matrix G = T^T T (jacobi_svd's route for long vectors): its eigenvalues
   // are the squared singular values, its eigenvectors the rotation side, the other side follows as
   // combinations of the rows.  The squaring costs relative accuracy ~eps (s_1 / s_i)^2 on the small ones: taken
@@ -1200,7 +1189,6 @@ __global__ __launch_bounds__(256) void cca_small_kernel(CcaSmallParams P) {
     const unsigned long long first = __ballot(lane < k && rank == 0), last = __ballot(lane < k && rank == dim - 1);
     const double top = __shfl(li, __ffsll((long long)first) - 1, 64), low = __shfl(li, __ffsll((long long)last) - 1, 64);
     gram_ok = top > 0.0 && low > 1e-8 * top;
-    TD_STAMP(4);
     if (gram_ok) {
       for (int want = wave; want < dim; want += 4) {
         const int pick = __ffsll((long long)__ballot(lane < k && rank == want)) - 1;
@@ -1286,7 +1274,6 @@ __global__ __launch_bounds__(256) void cca_small_kernel(CcaSmallParams P) {
     }
   }
   __syncthreads();
-  TD_STAMP(5);
   // ---- rot_x [k1][dim] = L^-T u, rot_y [k2][dim] = K22 v
   for (int idx = tid; idx < dim * NB; idx += 256) {
     const int d = idx >> 6, i = idx & 63;
@@ -1306,8 +1293,6 @@ __global__ __launch_bounds__(256) void cca_small_kernel(CcaSmallParams P) {
     P.rot_y[(size_t)j * dim + d] = (float)acc;
   }
   if (tid == 0) P.status[0] = 0;
-  TD_STAMP(6);
-#undef TD_STAMP
 }
 
 struct Carver {
@@ -1453,15 +1438,6 @@ int td_cca_solve(td_handle* h, td_stats* s, double denom, double regularization,
     int status = 0;
     TD_HIP(h, hipMemcpyAsync(&status, h->dev_flag, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     TD_HIP(h, hipStreamSynchronize(h->stream));
-#ifdef TD_CCA_STAMPS
-    {
-      long long st[7];
-      hipMemcpy(st, h->dev_flag + 16, sizeof(st), hipMemcpyDeviceToHost);
-      fprintf(stderr, "cca_small_kernel (us): factor %.1f  eig yy | forward %.1f  K22, T %.1f  gram + eig %.1f  extract / rounds %.1f  rotations %.1f\n",
-              (st[1] - st[0]) / 100.0, (st[2] - st[1]) / 100.0, (st[3] - st[2]) / 100.0, (st[4] - st[3]) / 100.0,
-              (st[5] - st[4]) / 100.0, (st[6] - st[5]) / 100.0);
-    }
-#endif
     if (status == 0) {
       if (info_host) { info_host[0] = info_host[1] = info_host[2] = 0; info_host[3] = 1 | 4; }   // bit 2: one launch
       return TD_OK;

@@ -426,11 +426,10 @@ constexpr int kBfTile = 128;            // time samples per tile
 template <int kRowDw, int kPieces> struct BfGeom {
   static constexpr int kRows = kRowDw == 83 ? 160 : 192;      // staged rows
   static constexpr int kPieceDw = 64 * kRowDw;
-  static constexpr int kYDw = 96;      // one piece of the staged targets: 160 float16 (+ slack)
-  // double-buffered tile + (float16 form) double-buffered two pieces of the tile's targets
-  // + (float16 form) the eight waves' 32 x 32 float32 blocks of target sums
+  // double-buffered tile (+ float16 form: the 33.5 KB in which a removed form of the kernel staged a
+  // target column and its sums -- unused, kept so that the launches keep their dynamic LDS size)
   static constexpr size_t kLdsBytes =
-      sizeof(unsigned) * (2 * kPieces * kPieceDw + (kPieces == 2 ? 2 * 2 * kYDw + 8 * 1024 : 0));
+      sizeof(unsigned) * (2 * kPieces * kPieceDw + (kPieces == 2 ? 2 * 2 * 96 + 8 * 1024 : 0));
 };
 constexpr int kBfThreads = 512;
 
@@ -450,8 +449,6 @@ __device__ __forceinline__ float comp4(const float4& v, int q) {
 // measurable: the -5e-8 the sums of squares come out low by is the matrix pipe truncating the
 // 22-bit products h h' when it aligns the 16 products of an instruction -- the same bias with
 // MFMA chains of 128, 64 and 32 samples; tools/bias_probe.py.)
-//
-// (The regression targets ride along in the same kernel: tgt_tile below.)
 template <bool kZero, int kBfPieceDw, bool kF16>
 __device__ __forceinline__ void bf_kstep(const unsigned* __restrict__ ap,
                                          const unsigned* __restrict__ bp,
@@ -477,14 +474,10 @@ __device__ __forceinline__ void bf_kstep(const unsigned* __restrict__ ap,
   for (int pc = 0; pc < kP; ++pc)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-#ifdef TD_ABL_NOALIGN   // timing ablations (wrong sums; tools/README.md, profiles/NOTES.md 8): no operand VALU
-      b[0][pc][i] = d[pc][i]; b[1][pc][i] = a[pc][i]; b[2][pc][i] = d[pc][i + 2]; b[3][pc][i] = a[kP - 1 - pc][i];
-#else
       b[0][pc][i] = d[pc][i];
       b[1][pc][i] = __builtin_amdgcn_alignbit(d[pc][i + 1], d[pc][i], 16);
       b[2][pc][i] = d[pc][i + 1];
       b[3][pc][i] = __builtin_amdgcn_alignbit(d[pc][i + 2], d[pc][i + 1], 16);
-#endif
     }
   f32x16 c[4];
 #pragma unroll
@@ -522,98 +515,18 @@ __device__ __forceinline__ void bf_ksteps(const unsigned* __restrict__ ap,
                                           f32x16 (&total)[4]) {
 #pragma unroll
   for (int s = kFrom; s < kTo; ++s) {
-#ifdef TD_ABL_NOLDS      // timing ablation: the same operand words for every k-step of a tile
-#define TD_KOFF(s) 0
-#else
-#define TD_KOFF(s) (8 * (s))
-#endif
-#ifdef TD_F16_LONGCHAIN   // experiment: ONE chain per slab (the kernel zeroes acc per work item and adds it to total there)
-    bf_kstep<false, kBfPieceDw, kF16>(ap + TD_KOFF(s), bp + TD_KOFF(s), nullptr, acc);
-#else
-    if (s % kChain == 0) bf_kstep<true, kBfPieceDw, kF16>(ap + TD_KOFF(s), bp + TD_KOFF(s), nullptr, acc);
-    else                 bf_kstep<false, kBfPieceDw, kF16>(ap + TD_KOFF(s), bp + TD_KOFF(s), nullptr, acc);
+    if (s % kChain == 0) bf_kstep<true, kBfPieceDw, kF16>(ap + 8 * s, bp + 8 * s, nullptr, acc);
+    else                 bf_kstep<false, kBfPieceDw, kF16>(ap + 8 * s, bp + 8 * s, nullptr, acc);
     if ((s + 1) % kChain == 0) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) total[r] += acc[r];
     }
-#endif
     // (without a fence hipcc hoists the LDS reads of all the unrolled steps to the top; fences
     // after every step, every other step or none at all time the same)
     __builtin_amdgcn_sched_barrier(0);
   }
 }
 
-// ---- the regression targets ride along (float16 form) -------------------------------------------
-// yT x~ per lag is the product T[e][j] = sum_v A[e][v] x~[v][j] with A[e][v] = y[v - e]
-// (Toeplitz): M = lag, K = time, N = channel -- and the B operand of that product (lane ->
-// channel, 8 consecutive samples of a 16-sample k-step) is exactly what a wave reads as the A
-// operand of its Gram tiles.  So the tile of x in LDS serves the targets too: no second pass
-// over x (the separate targets kernel read all of it again: 65 us at C2).
-//
-// Work split: the 8 k-steps of a tile are dealt to the lag groups (workgroups) of the slab --
-// step s belongs to group s % n_groups -- and the three products y_h x_h, y_h x_l, y_l x_h of a
-// step to three of the four waves that hold the same m tile (wi = 0..3), rotating from step to
-// step: one or two MFMAs per wave and tile, done at the END of the tile, when the 64 registers of
-// the Gram chains are free: one short MFMA chain, then ONE read-modify-write of the wave's 32 x 32
-// block of running float32 sums, which lives in LDS (16 more accumulator registers per lane do
-// not fit beside the 128 of the Gram tiles).
-//
-// The rows past the end: x~[v] for v = end .. end + 30 of a recording's summed range (real rows
-// when a remainder was dropped or another rank holds them) still pair with the last targets,
-// y[v - e] x~[v] for e > v - end.  A tile carries 32 staged rows past its 128 and the staged
-// targets are zero from `end` on, so the slab that ends a recording's range runs its k-steps over
-// those rows as well (steps 8 and 9 of a full tile), and keeps the rows >= nk of the step it cut.
-__device__ __forceinline__ int tgt_product(int s, int group, int n_groups, int wi) {
-  if (s % n_groups != group) return -1;
-  const int prod = (wi - 3 * (s / n_groups)) & 3;      // 0: y_h x_h, 1: y_h x_l, 2: y_l x_h
-  return prod == 3 ? -1 : prod;
-}
-
-struct TgtLane {
-  const unsigned* y;     // the lane's dword span of piece h of the staged targets at k-step 0
-  unsigned shift;        // 0 or 16: the span starts at an odd sample
-  float* sums;           // the lane's slot of the wave's block of running sums: [4][64 lanes][4]
-};
-
-// ap: the lane's A-operand span of piece h at k-step 0.  nk: rows of the tile that belong to the
-// slab (128, or fewer in its last tile); seg_end: the slab ends its recording's summed range.
-template <int kBfPieceDw, int kYDw>
-__device__ __forceinline__ void tgt_tile(const unsigned* __restrict__ ap, const TgtLane& tl, int nk,
-                                         bool seg_end, int group, int n_groups, int wi, int lg) {
-  f32x16 t;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) t[k] = 0.f;
-  bool any = false;
-#pragma unroll
-  for (int s = 0; s < 10; ++s) {
-    const int prod = tgt_product(s, group, n_groups, wi);
-    if (prod < 0 || !(16 * s < nk || (seg_end && 16 * s < nk + 31))) continue;     // (wave-uniform)
-    const int cnt = nk - 16 * s - 8 * lg;              // rows of this lane's k half inside the slab
-    const unsigned* xa = ap + 8 * s + (prod == 1 ? kBfPieceDw : 0);
-    const unsigned* ys = tl.y + 8 * s + (prod == 2 ? kYDw : 0);
-    u32x4 a, ya;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-      const unsigned keep = (seg_end || cnt >= 2 * d + 2) ? 0xffffffffu : cnt == 2 * d + 1 ? 0x0000ffffu : 0u;
-      a[d] = xa[d] & keep;
-      ya[d] = __builtin_amdgcn_alignbit(ys[d + 1], ys[d], tl.shift);
-    }
-    t = td_mfma_f16(ya, a, t);
-    any = true;
-  }
-  if (!any) return;
-#pragma unroll
-  for (int k4 = 0; k4 < 4; ++k4) {
-    float4* slot = reinterpret_cast<float4*>(tl.sums) + k4 * 64;
-    float4 v = *slot;
-    v.x += t[4 * k4]; v.y += t[4 * k4 + 1]; v.z += t[4 * k4 + 2]; v.w += t[4 * k4 + 3];
-    *slot = v;
-  }
-}
-
-// kTgt (float16 form only): one target column rides along (tgt_tile).  A variant of its own: the
-// extra code costs the plain kernel 20 registers and ~6 % of its time even when it is switched off.
-//
 // kVirt (float16 form): the workgroup stages a VIRTUAL image (td_common.h: VirtImage -- every staged
 // channel is a source channel of x read `shift` rows later) and its waves run the tasks of its
 // group's table instead of the fixed (tile pair, lag quad) of their wave number; the sums leave as
@@ -621,17 +534,13 @@ __device__ __forceinline__ void tgt_tile(const unsigned* __restrict__ ap, const 
 //
 // kKs (virtual images with <= 4 tasks: <= 16 channels): the waves kq = 0 .. kparts - 1 share a task, each runs
 // 8 / kparts of a tile's k-steps as one MFMA chain; their slab sums meet in LDS at the end (a fixed tree).
-template <bool kVec4, int kBfRowDw, bool kF16, bool kTgt, bool kVirt = false, bool kKs = false>
+template <bool kVec4, int kBfRowDw, bool kF16, bool kVirt = false, bool kKs = false>
 __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
-  static_assert(kF16 || !kTgt, "targets ride along in the float16 form only");
-  static_assert(!kVirt || (kF16 && !kTgt), "virtual images: the plain float16 form");
+  static_assert(!kVirt || kF16, "virtual images: the float16 form");
   static_assert(!kKs || kVirt, "shared tasks: virtual images");
-#ifndef TD_F16_CHAIN
-#define TD_F16_CHAIN 8
-#endif
-  // k-steps (of 16 samples) per MFMA chain: a whole tile for the bf16 pieces (16-bit products:
+  // k-steps (of 16 samples) per MFMA chain: a whole tile (for the bf16 pieces, 16-bit products:
   // nothing is lost aligning them to a 128-sample sum)
-  constexpr int kChain = kF16 ? TD_F16_CHAIN : 8;
+  constexpr int kChain = 8;
   constexpr int kP = kF16 ? 2 : 3;
   extern __shared__ __attribute__((aligned(16))) unsigned ldsu[];   // [2][kP][64][kBfRowDw]
   constexpr int kBfRows = BfGeom<kBfRowDw, kP>::kRows;
@@ -723,37 +632,15 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
     if (p.zero_tab && blockIdx.x == (gridDim.x > 1 ? 1 : 0))
       for (int i = tid; i < kChanTab; i += kBfThreads) p.zero_tab[i] = 0u;
   }
-  // float16 form with targets (p.ty): the staged targets and the wave's block of running sums
-  const bool t_on = kTgt && p.ty != nullptr;
-  const int wi = quad + 2 * nt;                        // which of the four waves of its m tile
-  constexpr int kYDw = BfGeom<kBfRowDw, kP>::kYDw;
-  unsigned* const ybuf = ldsu + 2 * kP * kBfPieceDw;   // [2 buffers][2 pieces][kYDw]
-  float* const tsums = reinterpret_cast<float*>(ybuf + 4 * kYDw) + wave * 1024;   // [4][64][4] per wave
-  TgtWork tw = {0, 0, 0, 0};
-  float sy = 1.f, pfy = 0.f;
-  if (t_on) {
-    tw = p.tworks[id];
-    sy = __builtin_bit_cast(float, (unsigned)(127 + td_f16_scale_exp(td_chan_max_of(p.ty_max, 0))) << 23);
-#pragma unroll
-    for (int k4 = 0; k4 < 4; ++k4)
-      reinterpret_cast<float4*>(tsums)[k4 * 64 + lane] = float4{0.f, 0.f, 0.f, 0.f};
-    // the slack behind the 160 staged targets of each piece is read by the k-steps past a
-    // recording's end (where every target is zero): it holds zeros, and nothing writes it again
-    if (tid < 64) ybuf[(tid >> 4) * kYDw + 80 + (tid & 15)] = 0u;
-  }
-  // sample u = ut - 31 + tid of the targets (tid < 160): zero outside the rows this call sums
-  auto prefetch_y = [&](long long ut) {
-    if (!t_on || tid >= 160) return;
-    const long long u = ut - 31 + tid;
-    const bool ok = u >= tw.seg_begin && u < tw.seg_end && u >= 0 && u < tw.y_valid;
-    pfy = ok ? p.ty[(tw.y_row0 + u) * p.ldty] : 0.f;
-  };
-  auto store_y = [&](unsigned* yb) {
-    if (!t_on || tid >= 160) return;
-    unsigned h, l;
-    td_split2_f16(pfy * sy, 0.f, h, l);
-    reinterpret_cast<unsigned short*>(yb)[tid] = (unsigned short)(h & 0xffffu);
-    reinterpret_cast<unsigned short*>(yb + kYDw)[tid] = (unsigned short)(l & 0xffffu);
+  // An inert call that never stores.  A removed form of this kernel staged a target column here, and
+  // deleting its last call moved hipcc's schedule of the unaligned virtual-image instances: their
+  // clamped row loads were issued out of the order they are used, and the unaligned 99-channel
+  // accumulate went from 3.04 to 3.07 ms.  With this call the instruction streams stay as they were.
+  const bool never = false;
+  float anchor_a = 0.f, anchor_b = 1.f;
+  auto sched_anchor = [&](unsigned* dst) {
+    if (!never || tid >= 160) return;
+    reinterpret_cast<unsigned short*>(dst)[tid] = (unsigned short)(anchor_a * anchor_b);
   };
   float4 pf[6];
   // a tile whose 160 staged rows all exist, 64 real channels: no clamps, no masks
@@ -786,9 +673,6 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
     return ut + v_min_shift >= lo && ut + kBfRows + v_max_shift <= hi;
   };
   auto prefetch_to = [&](long long ut, float4 (&pfr)[6]) {
-#ifdef TD_ABL_NOSTAGE
-    return;
-#endif
     if constexpr (kVirt) {
       if (vinside(ut)) {
         // rows from wave-uniform bases (one per row slot), the lane's channel and shift in ONE offset
@@ -872,9 +756,6 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
   };
   auto prefetch = [&](long long ut) { prefetch_to(ut, pf); };
   auto store_from = [&](long long ut, unsigned* buf, const float4 (&pfr)[6]) {
-#ifdef TD_ABL_NOSTAGE    // timing ablation: no staging at all (with prefetch below)
-    return;
-#endif
     if constexpr (kVirt && !kVec4) {
       // lane = channel: the pairs of rows this wave fetched, two samples a dword
       const float* pv = reinterpret_cast<const float*>(&pfr[0]);
@@ -943,11 +824,7 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
         unsigned h[2], l[2];
 #pragma unroll
         for (int d = 0; d < 2; ++d)
-#ifdef TD_ABL_NOSPLIT    // timing ablation: no split arithmetic
-        { h[d] = __builtin_bit_cast(unsigned, comp4(v[2 * d], q)); l[d] = __builtin_bit_cast(unsigned, comp4(v[2 * d + 1], q)); }
-#else
           td_split2_f16(comp4(v[2 * d], q) * sc[q], comp4(v[2 * d + 1], q) * sc[q], h[d], l[d]);
-#endif
         dst[0] = h[0]; dst[1] = h[1];
         dst[kBfPieceDw] = l[0]; dst[kBfPieceDw + 1] = l[1];
       } else {
@@ -985,17 +862,6 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
   const int a_off = (mt * 32 + lj) * kBfRowDw + 4 * lg;
   const int b_off = (nt * 32 + lj) * kBfRowDw + 4 * lg + (lag_off >> 1);
 
-  // Toeplitz operand of the targets: lane (lag m = lj, k half lg) reads y[v - m] for the 8 samples
-  // v of its k half: staged index 16 s + 8 lg - m + 31 (the buffer starts at sample ut - 31)
-  TgtLane tl;
-  tl.y = nullptr;
-  tl.shift = ((8 * lg - lj + 31) & 1) * 16;
-  tl.sums = tsums + 4 * lane;
-  const int y_lane = (8 * lg - lj + 31) >> 1;
-
-#ifdef TD_SETPRIO
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);      // experiment: static priority for the younger half
-#endif
   f32x16 acc[4];
   unsigned* const buf0 = ldsu;
   unsigned* const buf1 = ldsu + kP * kBfPieceDw;
@@ -1060,16 +926,8 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
     continue;
   }
   prefetch(w.u_begin);
-  prefetch_y(w.u_begin);
   store(w.u_begin, buf0);
-  store_y(ybuf);
   __syncthreads();
-#ifdef TD_F16_LONGCHAIN
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int k = 0; k < 16; ++k) acc[r][k] = 0.f;
-#endif
 
   // (virtual images: the tile loop of a recording's last slab runs past its end, where only the
   // shifted copies of the A-only channels are not zero; the other tasks stop at u_end)
@@ -1078,10 +936,8 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
   for (long long ut = w.u_begin; ut < u_stop; ut += kBfTile, parity ^= 1) {
     const unsigned* cur = parity ? buf1 : buf0;
     unsigned* nxt = parity ? buf0 : buf1;
-    unsigned* ynxt = ybuf + (parity ? 0 : 2 * kYDw);
-    tl.y = ybuf + (parity ? 2 * kYDw : 0) + y_lane;
     const bool more = ut + kBfTile < u_stop;
-    if (more) { prefetch(ut + kBfTile); prefetch_y(ut + kBfTile); }
+    if (more) prefetch(ut + kBfTile);
     long long left = w.u_end - ut;
     if constexpr (kVirt) {
       if (a_ext) left = u_stop - ut;
@@ -1094,19 +950,17 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
     if (left >= kBfTile) {
       // whole tile: unrolled k-steps
       bf_ksteps<0, 2, kBfPieceDw, kF16, kChain>(ap, bp, acc, total);
-      if (more && early) { store(ut + kBfTile, nxt); store_y(ynxt); }
+      if (more && early) { store(ut + kBfTile, nxt); sched_anchor(nxt); }
       bf_ksteps<2, 6, kBfPieceDw, kF16, kChain>(ap, bp, acc, total);
-      if (more && !early) { store(ut + kBfTile, nxt); store_y(ynxt); }
+      if (more && !early) { store(ut + kBfTile, nxt); sched_anchor(nxt); }
       bf_ksteps<6, 8, kBfPieceDw, kF16, kChain>(ap, bp, acc, total);
     } else {
       // the last, cut tile of a slab: A stops at nk
       const int nk = (int)left;
-#ifndef TD_F16_LONGCHAIN
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int k = 0; k < 16; ++k) acc[r][k] = 0.f;
-#endif
       for (int t0 = 0; t0 < nk; t0 += 16) {
         const int cnt = nk - t0 - 8 * lg;              // may be <= 0 or >= 8
         unsigned mask[4];
@@ -1115,27 +969,11 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
           mask[d] = cnt >= 2 * d + 2 ? 0xffffffffu : cnt == 2 * d + 1 ? 0x0000ffffu : 0u;
         bf_kstep<false, kBfPieceDw, kF16>(ap + (t0 >> 1), bp + (t0 >> 1), mask, acc);
       }
-#ifndef TD_F16_LONGCHAIN
 #pragma unroll
       for (int r = 0; r < 4; ++r) total[r] += acc[r];
-#endif
     }
-    if constexpr (kTgt) {
-      if (t_on)
-        tgt_tile<kBfPieceDw, kYDw>(ap, tl, left < kBfTile ? (int)left : kBfTile,
-                                   !more && w.u_end == tw.seg_end, group, p.n_groups, wi, lg);
-    }
-#ifndef TD_ABL_NOBAR      // timing ablation: no barrier per tile
     if (more) __syncthreads();
-#endif
-#ifdef TD_STAGGER         // experiment: the second wave of every SIMD starts each tile late (64 TD_STAGGER cycles)
-    if (more && wave >= 4) __builtin_amdgcn_s_sleep(TD_STAGGER);
-#endif
   }
-#ifdef TD_F16_LONGCHAIN
-#pragma unroll
-  for (int r = 0; r < 4; ++r) total[r] += acc[r];
-#endif
   }   // work items of this workgroup
 
   // Epilogue: the wave's 32 x 32 block of its four lags in the workgroup's partial slab.
@@ -1187,24 +1025,6 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
       const int i = mt * 32 + (k & 3) + 8 * (k >> 2) + 4 * lk;
       const int j = nt * 32 + lr;
       pe[(size_t)i * p.cb_pad + j] = total[r][k];
-    }
-  }
-  if (t_on) {
-    // targets: the blocks of the four waves of an m tile are summed (fixed order) and leave as
-    // ONE [32 lags][64 channels] float32 block per workgroup.  Wave block layout [k4][lane][4]:
-    // C/D register k = 4 k4 + q of lane (col = lane & 31, k half lk) is lag (k & 3) + 8 (k >> 2) +
-    // 4 lk = q + 8 k4 + 4 lk of channel mt * 32 + col.
-    __syncthreads();
-    const float* all = reinterpret_cast<const float*>(ybuf + 4 * kYDw);     // [8 waves][1024]
-    float* tp = p.tpartial + ((size_t)part * p.n_groups + group) * 32 * 64;
-#pragma unroll
-    for (int o = tid; o < 32 * 64; o += kBfThreads) {
-      const int e = o >> 6, ch = o & 63;
-      const int m_t = ch >> 5, col = ch & 31, lk = (e >> 2) & 1, q = e & 3, k4 = e >> 3;
-      const int idx = (k4 * 64 + lk * 32 + col) * 4 + q;
-      // waves of m tile m_t: wave = quad + 2 m_t + 4 nt
-      const float* b0 = all + (2 * m_t) * 1024 + idx;
-      tp[o] = (b0[0] + b0[1024]) + (b0[4 * 1024] + b0[5 * 1024]);
     }
   }
 }
@@ -1537,106 +1357,8 @@ __global__ __launch_bounds__(256) void chan_max_wide_kernel(const float* __restr
   }
 }
 
-// The streaming pre-pass of a float16 accumulate with targets: ONE read of x (and y) gives
-//   * the largest magnitude of every channel of x and of y (atomic max into tab: [0, 64) x
-//     channels, [64] y) -- the power-of-two scales of the float16 split,
-//   * per workgroup the float64 column sums of x over the rows this call sums (the bias moments:
-//     the all-ones row of [y | 1]^T x~ follows from them and the file ends, stats.hip) and the sum of y.
-// Workgroup b takes strips b, b + gridDim.x, ...; a strip's rows [u_begin, u_end) enter the sums,
-// the maxima also cover `halo` rows beyond it (what the lag kernel reads past a slab's end).
-__global__ __launch_bounds__(256) void chan_prepass_kernel(
-    const float* __restrict__ x, long long ldx, int c, const float* __restrict__ y, long long ldy,
-    const LagWork* __restrict__ strips, int n_strips, int halo, unsigned* __restrict__ tab,
-    double* __restrict__ csum, double* __restrict__ ysum, int vec4) {
-  __shared__ double red[16][65];
-  __shared__ unsigned redm[16][64];
-  const int tid = threadIdx.x, c4 = (tid & 15) * 4, rl = tid >> 4;
-  double cs[4] = {0.0, 0.0, 0.0, 0.0};
-  unsigned m[4] = {0u, 0u, 0u, 0u};
-  double ys = 0.0;
-  unsigned ym = 0u;
-  const bool col_ok = c4 < c;
-  for (int si = blockIdx.x; si < n_strips; si += gridDim.x) {
-    const LagWork w = strips[si];
-    // x: rows [u_begin, u_end) clipped to the stream
-    const long long r0 = w.u_begin < 0 ? 0 : w.u_begin;
-    const long long r1 = w.u_end < w.b_valid ? w.u_end : w.b_valid;
-    const long long r2 = r1 + halo < w.b_valid ? r1 + halo : w.b_valid;      // maxima only
-    const float* xb = x + w.b_row0 * ldx;
-    if (vec4 && col_ok) {
-      long long r = r0 + rl;
-      for (; r + 48 < r1; r += 64) {                   // four rows in flight per thread
-        float4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = *reinterpret_cast<const float4*>(xb + (r + 16 * k) * ldx + c4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          cs[0] += (double)v[k].x; cs[1] += (double)v[k].y; cs[2] += (double)v[k].z; cs[3] += (double)v[k].w;
-          m[0] = max(m[0], __float_as_uint(v[k].x) & 0x7fffffffu);
-          m[1] = max(m[1], __float_as_uint(v[k].y) & 0x7fffffffu);
-          m[2] = max(m[2], __float_as_uint(v[k].z) & 0x7fffffffu);
-          m[3] = max(m[3], __float_as_uint(v[k].w) & 0x7fffffffu);
-        }
-      }
-      for (; r < r2; r += 16) {
-        const float4 v = *reinterpret_cast<const float4*>(xb + r * ldx + c4);
-        const double in = r < r1 ? 1.0 : 0.0;
-        cs[0] += in * (double)v.x; cs[1] += in * (double)v.y; cs[2] += in * (double)v.z; cs[3] += in * (double)v.w;
-        m[0] = max(m[0], __float_as_uint(v.x) & 0x7fffffffu);
-        m[1] = max(m[1], __float_as_uint(v.y) & 0x7fffffffu);
-        m[2] = max(m[2], __float_as_uint(v.z) & 0x7fffffffu);
-        m[3] = max(m[3], __float_as_uint(v.w) & 0x7fffffffu);
-      }
-    } else if (!vec4) {
-      for (long long r = r0 + rl; r < r2; r += 16)
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if (c4 + q < c) {
-            const float v = xb[r * ldx + c4 + q];
-            if (r < r1) cs[q] += (double)v;
-            m[q] = max(m[q], __float_as_uint(v) & 0x7fffffffu);
-          }
-    }
-    // y: rows [u_begin, u_end) clipped to ITS stream
-    if (y) {
-      const long long y1 = w.u_end < w.a_valid ? w.u_end : w.a_valid;
-      for (long long u = r0 + tid; u < y1; u += 256) {
-        const float v = y[(w.a_row0 + u) * ldy];
-        ys += (double)v;
-        ym = max(ym, __float_as_uint(v) & 0x7fffffffu);
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { red[rl][c4 + q] = cs[q]; redm[rl][c4 + q] = m[q]; }
-  __syncthreads();
-  if (tid < 64) {
-    double t = 0.0;
-    unsigned tm = 0u;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) { t += red[k][tid]; tm = max(tm, redm[k][tid]); }
-    csum[(size_t)blockIdx.x * 64 + tid] = tid < c ? t : 0.0;
-    if (tid < c && tm) atomicMax(tab + (blockIdx.x % kChanShards) * 128 + tid, tm);
-  }
-  __syncthreads();
-  // sum and maximum of y over the workgroup
-  double* yr = &red[0][0];
-  unsigned* ymr = &redm[0][0];
-  yr[tid] = ys;
-  ymr[tid] = ym;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) { yr[tid] += yr[tid + off]; ymr[tid] = max(ymr[tid], ymr[tid + off]); }
-    __syncthreads();
-  }
-  if (tid == 0) {
-    ysum[blockIdx.x] = yr[0];
-    if (ymr[0]) atomicMax(tab + (blockIdx.x % kChanShards) * 128 + 64, ymr[0]);
-  }
-}
-
 // ---- measurement aid: what the bf16 matrix pipe sustains (td_probe_bf16_mfma) ----------------
-// A bare loop of the MFMA the kernel above issues, in its six-product order, operands in
+// A bare loop of the MFMA lagcov_split_kernel issues, in its six-product order, operands in
 // registers, no memory and no LDS: the rate the chip holds under that load for ~1 ms.  With
 // all-zero operands it runs at ~0.9 of the nominal peak, with operands shaped like the three
 // pieces of a float32 split at 0.66-0.70: the power / clock ceiling the accumulate is measured
@@ -2466,10 +2188,7 @@ __global__ __launch_bounds__(kThreads) void colsum_rows_kernel(LagParams p, doub
 constexpr int kTgtPrefetch = 16;     // steps (row pairs) of x in flight per wave
 constexpr int kTgtBody = 16;         // steps per flush (= the prefetch ring: static slots)
 constexpr int kTgtStrip = 4 * kWaveStrip;   // rows of one WORKGROUP's strip
-#ifndef TD_TGT_STRIP_MIN
-#define TD_TGT_STRIP_MIN 512
-#endif
-constexpr int kTgtStripMin = TD_TGT_STRIP_MIN;   // ... and the shortest the planner cuts (a short call: more, shorter strips)
+constexpr int kTgtStripMin = 512;    // ... and the shortest the planner cuts (a short call: more, shorter strips)
 
 // Geometry of a wave's share of a strip, the same in both kernels.
 struct TgtStrip {
@@ -2939,8 +2658,7 @@ int td_mirror_upper(td_handle* h, double* g_dev, int c, int ld) {
 static void lag_slab_counts(const td_handle* h, const std::vector<LagSeg>& segs, long long total,
                             long long per_item_wgs, bool split, std::vector<long long>* out,
                             long long want_items = 0) {
-  long long kMaxSlab = split ? 8192 : 2048;
-  if (const char* e = td_dev_env("TD_MAX_SLAB")) kMaxSlab = atoll(e);   // development
+  const long long kMaxSlab = split ? 8192 : 2048;
   std::vector<long long>& n_slabs = *out;
   n_slabs.assign(segs.size(), 0);
   long long min_items = 0, max_items = 0;
@@ -3004,8 +2722,7 @@ int td_lagcov_plan(td_handle* h, const float* a, int64_t lda, int ca, bool a_one
   // with the operands swapped -- force_small -- instead of as padded 64 x 64 tiles)
   // both operands narrow and enough lags to fill a workgroup's 32: the VALU kernel with a row of
   // outputs per thread (lagcov_narrow_kernel); it shares the skinny kernel's slab layout
-  static const bool no_narrow = td_dev_env("TD_LAG_NO_NARROW") != nullptr;     // development: A/B runs
-  const bool narrow = !a_ones && ca <= 8 && cb <= 8 && e_count >= 8 && !no_narrow;
+  const bool narrow = !a_ones && ca <= 8 && cb <= 8 && e_count >= 8;
   plan->narrow = narrow;
   const bool small = narrow || ((a_ones || plan->force_small) && ca_eff <= 8);
   // matrix-core path: 8 lags per workgroup, or 4 / 2 / 1 when fewer are asked for (the 8
@@ -3031,9 +2748,7 @@ int td_lagcov_plan(td_handle* h, const float* a, int64_t lda, int ca, bool a_one
   p.n_groups = (int)td_ceil_div(e_count, lags_per_wg);
   // The split kernels (lagcov_split_kernel): the same stream and channel tile on both sides,
   // lags 0 .. <= 63, 33 .. 64 channels.
-  // (the environment switches are for A/B runs inside one process tree; td_set_accumulate_mode is the API)
-  static const bool env_f32 = td_dev_env("TD_LAGCOV_F32") != nullptr;
-  const bool force_f32 = env_f32 || h->acc_mode == TD_ACC_F32;
+  const bool force_f32 = h->acc_mode == TD_ACC_F32;
   bool split = !small && !few && (a == b) && (lda == ldb) && (ca == cb) && !a_ones && e_min == 0 &&
                ca > 32 && ca <= 64 && e_count <= 64 && !force_f32;
   for (const LagSeg& sg : segs)
@@ -3046,8 +2761,7 @@ int td_lagcov_plan(td_handle* h, const float* a, int64_t lda, int ca, bool a_one
   plan->small = small; plan->few = few; plan->split = split; plan->few_g = few_g;
   // the two-piece float16 form of the split kernel (half the matrix instructions): for callers
   // that reduce through the finalize launch, which divides the channel scales out (allow_f16)
-  static const bool env_bf16 = td_dev_env("TD_LAGCOV_BF16X3") != nullptr;
-  plan->f16 = split && plan->allow_f16 && !env_bf16 && h->acc_mode == TD_ACC_F16X2;
+  plan->f16 = split && plan->allow_f16 && h->acc_mode == TD_ACC_F16X2;
 
   // Slab plan.  Every slab is ONE f32 accumulation chain (relative error ~ eps/2 *
   // sqrt(len/3)) and slabs are summed in float64, so at most 2048 samples per slab keep the
@@ -3107,46 +2821,8 @@ int td_chan_tab_scratch(td_handle* h, unsigned** tab) {
   return TD_OK;
 }
 
-bool td_lagcov_plan_targets(LagcovPlan* plan) {
-  if (!plan->f16 || plan->e_count > 32 || plan->p.e_min != 0 || plan->works.empty()) return false;
-  plan->tpartial_bytes = td_round_up((size_t)plan->p.n_work * plan->p.n_groups * 32 * 64 * sizeof(float), 256);
-  return true;
-}
-
-int td_chan_prepass_plan(td_handle* h, const std::vector<LagSeg>& syx, PrepassPlan* plan) {
-  long long total = 0;
-  for (const LagSeg& sg : syx) total += sg.u_end > sg.u_begin ? sg.u_end - sg.u_begin : 0;
-  // two workgroups of 256 threads per CU, one strip each; strips of at least 256 rows
-  const int cus = h->cu_count > 0 ? h->cu_count : 256;
-  long long strip = td_round_up(td_ceil_div(total > 0 ? total : 1, 2 * cus), 16);
-  if (strip < 256) strip = 256;
-  plan->strips = split_work(syx, strip);
-  plan->blocks = (int)(plan->strips.size() < (size_t)(2 * cus) ? plan->strips.size() : 2 * cus);
-  if (plan->blocks < 1) plan->blocks = 1;
-  plan->scratch_bytes = td_round_up((size_t)plan->blocks * 65 * sizeof(double), 256);
-  return TD_OK;
-}
-
-int td_chan_prepass_launch(td_handle* h, PrepassPlan* plan, const float* x, int64_t ldx, int c,
-                           const float* y, int64_t ldy, int halo, unsigned* tab, void* scratch,
-                           const double** csum, const double** ysum) {
-  double* cs = reinterpret_cast<double*>(scratch);
-  double* ys = cs + (size_t)plan->blocks * 64;
-  *csum = cs;
-  *ysum = ys;
-  const void* strips_dev = nullptr;
-  TD_TRY(td_table_upload(h, plan->strips.data(), plan->strips.size() * sizeof(LagWork), &strips_dev));
-  const bool vec4 = (ldx % 4 == 0) && (c % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
-  hipLaunchKernelGGL(chan_prepass_kernel, dim3((unsigned)plan->blocks), dim3(256), 0, h->stream, x,
-                     (long long)ldx, c, y, (long long)ldy, reinterpret_cast<const LagWork*>(strips_dev),
-                     (int)plan->strips.size(), halo, tab, cs, ys, vec4 ? 1 : 0);
-  TD_HIP(h, hipGetLastError());
-  return TD_OK;
-}
-
 int td_lagcov_launch(td_handle* h, LagcovPlan* plan, void* scratch, double* g_dev, bool accumulate,
-                     int ldg, int rows_dst, LagReduceJob* job, double* tg_dev, bool t_accumulate,
-                     int t_rows, LagReduceJob* tjob) {
+                     int ldg, int rows_dst, LagReduceJob* job) {
   LagParams& p = plan->p;
   const bool small = plan->small, few = plan->few, split = plan->split, aligned = plan->aligned;
   const int few_g = plan->few_g, e_count = plan->e_count, ca_eff = plan->ca_eff, cb = plan->cb;
@@ -3195,21 +2871,10 @@ int td_lagcov_launch(td_handle* h, LagcovPlan* plan, void* scratch, double* g_de
     for (const LagWork& wk : plan->works)
       if (wk.a_row0 != wk.b_row0 || wk.a_valid != wk.b_valid) unified = false;
     p.chan_max = nullptr;
-    p.ty = nullptr; p.ldty = 0; p.tworks = nullptr; p.tpartial = nullptr; p.ty_max = nullptr;
     p.scale_out = plan->f16 ? plan->scale_out : nullptr;
     p.zero_tab = plan->f16 ? plan->zero_tab : nullptr;
     if (plan->f16 && plan->tab) {
-      p.chan_max = plan->tab;          // the caller's pre-pass filled it
-      if (plan->ty && plan->tpartial_bytes) {
-        std::vector<TgtWork> tw(plan->works.size());
-        for (size_t i = 0; i < tw.size(); ++i) tw[i] = plan->tsegs[plan->work_seg[i]];
-        const void* tw_dev = nullptr;
-        TD_TRY(td_table_upload(h, tw.data(), tw.size() * sizeof(TgtWork), &tw_dev));
-        p.ty = plan->ty; p.ldty = plan->ldty;
-        p.tworks = reinterpret_cast<const TgtWork*>(tw_dev);
-        p.tpartial = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + plan->scratch_bytes);
-        p.ty_max = plan->tab + 64;
-      }
+      p.chan_max = plan->tab;          // the caller's measuring pass (the targets kernel) filled it
     } else if (plan->f16) {
       // channel scales of the float16 form: largest magnitude of every channel over the rows
       // of the array that hold this call's recordings (a superset of what the kernel reads)
@@ -3239,26 +2904,24 @@ int td_lagcov_launch(td_handle* h, LagcovPlan* plan, void* scratch, double* g_de
   } while (0)
     if (split) {
       if (!h->lds_opt_lagcov) {                          // 83 .. 152 KB of dynamic LDS: opt in once
-#define TD_BF_OPT(V, R, F, T)                                                                      \
-        TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&lagcov_split_kernel<V, R, F, T>), \
+#define TD_BF_OPT(V, R, F)                                                                         \
+        TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&lagcov_split_kernel<V, R, F>),   \
                                       hipFuncAttributeMaxDynamicSharedMemorySize,                  \
                                       (int)BfGeom<R, ((F) ? 2 : 3)>::kLdsBytes))
-        TD_BF_OPT(true, 83, false, false); TD_BF_OPT(false, 83, false, false);
-        TD_BF_OPT(true, 99, false, false); TD_BF_OPT(false, 99, false, false);
-        TD_BF_OPT(true, 83, true, false); TD_BF_OPT(false, 83, true, false);
-        TD_BF_OPT(true, 99, true, false); TD_BF_OPT(false, 99, true, false);
-        TD_BF_OPT(true, 83, true, true); TD_BF_OPT(false, 83, true, true);
+        TD_BF_OPT(true, 83, false); TD_BF_OPT(false, 83, false);
+        TD_BF_OPT(true, 99, false); TD_BF_OPT(false, 99, false);
+        TD_BF_OPT(true, 83, true); TD_BF_OPT(false, 83, true);
+        TD_BF_OPT(true, 99, true); TD_BF_OPT(false, 99, true);
 #undef TD_BF_OPT
         h->lds_opt_lagcov = true;
       }
       // More work items than CUs (the C2 plan: three slabs per CU): one workgroup per CU walks its
-      // share and leaves one partial slab (LagParams::n_part).  Not with the riding target column.
+      // share and leaves one partial slab (LagParams::n_part).
       long long grid_wgs = nwg;
-      static const bool no_persist = td_dev_env("TD_LAG_ONE_ITEM") != nullptr;   // development: A/B runs
       {
         const int cus = h->cu_count > 0 ? h->cu_count : 256;
         const long long per_round = (long long)(cus / p.n_groups) * p.n_groups;
-        if (!(plan->f16 && p.ty) && !no_persist && !plan->no_chains && per_round > 0 && nwg > per_round) {
+        if (!plan->no_chains && per_round > 0 && nwg > per_round) {
           // ... but a chain of float32 slab sums stays short: at most kMaxItemsPerChain items
           // (~256 tiles) per partial slab -- 4e7 samples in one call gave every CU 76 items and the
           // sums of squares came out 3e-7 off -- so very long inputs run several rounds of
@@ -3273,17 +2936,15 @@ int td_lagcov_launch(td_handle* h, LagcovPlan* plan, void* scratch, double* g_de
           }
         }
       }
-#define TD_BF_LAUNCH(V, R, F, T)                                                                   \
-      hipLaunchKernelGGL((lagcov_split_kernel<V, R, F, T>), dim3((unsigned)grid_wgs), dim3(kBfThreads), \
+#define TD_BF_LAUNCH(V, R, F)                                                                      \
+      hipLaunchKernelGGL((lagcov_split_kernel<V, R, F>), dim3((unsigned)grid_wgs), dim3(kBfThreads),  \
                          (BfGeom<R, ((F) ? 2 : 3)>::kLdsBytes), h->stream, p)
-      if (plan->f16 && p.ty) {   // (one target column rides along: <= 32 lags)
-        if (aligned) TD_BF_LAUNCH(true, 83, true, true); else TD_BF_LAUNCH(false, 83, true, true);
-      } else if (plan->f16) {
-        if (e_count <= 32) { if (aligned) TD_BF_LAUNCH(true, 83, true, false); else TD_BF_LAUNCH(false, 83, true, false); }
-        else               { if (aligned) TD_BF_LAUNCH(true, 99, true, false); else TD_BF_LAUNCH(false, 99, true, false); }
+      if (plan->f16) {
+        if (e_count <= 32) { if (aligned) TD_BF_LAUNCH(true, 83, true); else TD_BF_LAUNCH(false, 83, true); }
+        else               { if (aligned) TD_BF_LAUNCH(true, 99, true); else TD_BF_LAUNCH(false, 99, true); }
       } else {
-        if (e_count <= 32) { if (aligned) TD_BF_LAUNCH(true, 83, false, false); else TD_BF_LAUNCH(false, 83, false, false); }
-        else               { if (aligned) TD_BF_LAUNCH(true, 99, false, false); else TD_BF_LAUNCH(false, 99, false, false); }
+        if (e_count <= 32) { if (aligned) TD_BF_LAUNCH(true, 83, false); else TD_BF_LAUNCH(false, 83, false); }
+        else               { if (aligned) TD_BF_LAUNCH(true, 99, false); else TD_BF_LAUNCH(false, 99, false); }
       }
 #undef TD_BF_LAUNCH
     } else if (few) {
@@ -3310,15 +2971,6 @@ int td_lagcov_launch(td_handle* h, LagcovPlan* plan, void* scratch, double* g_de
   // the moment matrix is promised exactly symmetric).
   job->mirror = split ? 1 : 0;
   job->scale_a = job->scale_b = plan->f16 ? p.chan_max + kChanShards * 128 : nullptr;
-  if (tjob && p.ty) {
-    *tjob = LagReduceJob{};
-    tjob->partial = p.tpartial; tjob->is_f64 = 0;
-    tjob->n_work = p.n_work * p.n_groups;
-    tjob->e_pad = 32; tjob->ca_pad = 1; tjob->cb_pad = 64;
-    tjob->e_count = e_count; tjob->ca_eff = 1; tjob->cb = cb;
-    tjob->g = tg_dev; tjob->accumulate = t_accumulate ? 1 : 0; tjob->ca_dst = t_rows; tjob->ldg = cb;
-    tjob->scale_a = p.ty_max + kChanShards * 128; tjob->scale_b = p.chan_max + kChanShards * 128;
-  }
   return TD_OK;
 }
 
@@ -3440,8 +3092,7 @@ int td_lagcov_virt_plan(td_handle* h, const float* x, int64_t ldx, int c, const 
     virt_add(&tasks, 0, 1, nsa > 1, E, 0);
     // <= 4 tasks (<= 16 channels at 32 lags: two): the eight waves share them, each wave takes a run of the
     // tile's eight k-steps -- with two busy waves a tile cost 3.3 us, the matrix work of both 1.3
-    static const bool no_ks = td_dev_env("TD_VIRT_NO_KSPLIT") != nullptr;     // development: A/B runs
-    if (tasks.size() <= 4 && !no_ks) {
+    if (tasks.size() <= 4) {
       const int kparts = tasks.size() == 1 ? 8 : tasks.size() == 2 ? 4 : 2;
       std::vector<VirtTask> shared;
       for (const VirtTask& t : tasks)
@@ -3662,7 +3313,7 @@ int td_lagcov_virt_launch(td_handle* h, VirtPlan* plan, const float* x, int64_t 
   p.chan_max = tab;
   if (!h->lds_opt_virt) {
 #define TD_VOPT(V, R, K)                                                                                \
-    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&lagcov_split_kernel<V, R, true, false, true, K>), \
+    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&lagcov_split_kernel<V, R, true, true, K>), \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)BfGeom<R, 2>::kLdsBytes))
     TD_VOPT(true, 83, false); TD_VOPT(false, 83, false); TD_VOPT(true, 99, false); TD_VOPT(false, 99, false);
     TD_VOPT(true, 83, true); TD_VOPT(false, 83, true); TD_VOPT(true, 99, true); TD_VOPT(false, 99, true);
@@ -3671,7 +3322,7 @@ int td_lagcov_virt_launch(td_handle* h, VirtPlan* plan, const float* x, int64_t 
   }
   TD_TRY(td_profile_mark(h, true, (double)plan->total));
 #define TD_VLAUNCH(V, R, K)                                                                             \
-  hipLaunchKernelGGL((lagcov_split_kernel<V, R, true, false, true, K>), dim3((unsigned)plan->grid),     \
+  hipLaunchKernelGGL((lagcov_split_kernel<V, R, true, true, K>), dim3((unsigned)plan->grid),     \
                      dim3(kBfThreads), (BfGeom<R, 2>::kLdsBytes), h->stream, p)
 #define TD_VLAUNCH_K(V, R) do { if (plan->ksplit) TD_VLAUNCH(V, R, true); else TD_VLAUNCH(V, R, false); } while (0)
   if (plan->rowdw == 83) { if (plan->vec4) TD_VLAUNCH_K(true, 83); else TD_VLAUNCH_K(false, 83); }
@@ -4190,8 +3841,7 @@ int td_gram(td_handle* h, const float* x, int64_t ldx, int c1, const float* x2, 
                     (ldx2 % 4 == 0) && (c2 % 4 == 0) && ((reinterpret_cast<uintptr_t>(x2) & 15) == 0);
   // the bf16x3 kernel (aligned rows): slabs of whole 32-row chunks, two 4-wave workgroups per CU
   // (211 registers), a wave's MFMA chain <= 16 chunks
-  static const bool old_gram = td_dev_env("TD_GRAM_F32") != nullptr;          // development: A/B runs
-  const bool bf = vec4 && !old_gram && h->acc_mode != TD_ACC_F32;
+  const bool bf = vec4 && h->acc_mode != TD_ACC_F32;
   const int cus = h->cu_count > 0 ? h->cu_count : 256;
   // float32 kernel: slabs of whole 64-row tiles, at most 2048 rows (f32 chains of 512 row quads
   // per wave), whole rounds of 512 resident workgroups

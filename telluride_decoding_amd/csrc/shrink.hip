@@ -358,9 +358,6 @@ constexpr int kLuMaxN = 16320;        // the back substitution keeps the unknown
                                       // the limit of the blocked Cholesky (solve.hip)
 constexpr int kLuPanelThreads = 1024;
 constexpr int kLuRegThreads = 512, kLuRegMaxRows = 6;
-#ifndef TD_LU_INFLIGHT
-#define TD_LU_INFLIGHT 8
-#endif
 
 // The panel as a matrix of its own, pm [m = n - j0][32] (rows 256 bytes apart): the rows of `a` are n * 8 bytes
 // apart -- 16 KB at n = 2049, every row of a column panel in the same few memory channels, and a panel factored
@@ -448,7 +445,7 @@ __global__ __launch_bounds__(kLuPanelThreads) void lu_panel_kernel(double* __res
     int bi = 0x7fffffff;
     // (32 row pairs per trip -- 1024 rows of the panel: a store may alias the next load for all the compiler knows,
     //  so the loads of a trip are issued by hand before its stores; a column step is a handful of L2 round trips)
-    constexpr int kInFlight = TD_LU_INFLIGHT;
+    constexpr int kInFlight = 8;
     double* const pcol = pm + col;
     for (int r0 = jj + 1 + 2 * wave; r0 < m; r0 += 2 * kWaves * kInFlight) {
       double v[kInFlight];

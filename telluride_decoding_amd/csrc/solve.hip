@@ -596,14 +596,8 @@ int chol_factor_forward(td_handle* h, double* a_dev, double* rt_dev, double* sol
   // A single system is bound by the chain of launches, not by traffic: there the left-looking
   // column steps (whose tiles run KW GEMMs in sequence) only lengthen the chain
   // (n = 2049: 1.10 ms with 1 column per outer block, 1.28 ms with 4; 160 systems: 21.6 -> 16.8 ms).
-  int ow = batch <= 2 ? 1 : kOuterCols;
+  const int ow = batch <= 2 ? 1 : kOuterCols;
   const int panel_tiles = batch <= 2 ? 1 : kPanelTiles;
-#ifdef TD_DEV_SWITCHES                                       // development builds only: ablation of the blocking
-  if (const char* e = td_dev_env("TD_OUTER_COLS")) {
-    const int v = atoi(e);
-    if (v >= 1 && v <= 4) ow = v;
-  }
-#endif
   auto launch_update = [&](int kf, int kw, int jlo, int col_mode) {
     const int rem = nblk - jlo;                  // block rows jlo .. nblk-1
     const int tri = col_mode ? rem : rem * (rem + 1) / 2;
@@ -953,85 +947,10 @@ __global__ __launch_bounds__(256) void loso_matvec_kernel(LosoMatvec m) {
     }
 }
 
-struct LosoTrsm {
-  const double* l;        // [n_lambda][np][np] Cholesky factors (lower)
-  const double* linv;     // [n_lambda][nblk][64][64] inverses of the diagonal blocks
-  double* v;              // rows, updated in place (the not-yet-solved blocks)
-  double* out;            // rows: the solved blocks
-  int np, nblk, k, rows_per_lambda;
-};
-
-// One block step of a triangular substitution with many right-hand-side rows.
-//   forward (L y = b, k ascending):   y_k = b_k Linv_kk^T ; b_i -= y_k L_ik^T   for i > k
-//   backward (L^T w = y, k descending): w_k = y_k Linv_kk ; y_m -= w_k L_km     for m < k
-// grid: (blocks still to update + 1, n_lambda, row chunks); workgroup 0 publishes the solved
-// block to `out`, the others update their block in `v` (every workgroup forms the solved block
-// itself: one 32 x 64 x 64 product).
-template <bool kBack>
-__global__ __launch_bounds__(256) void loso_trsm_kernel(LosoTrsm t) {
-  __shared__ double as[kLosoRows * LS];
-  __shared__ double ys[kLosoRows * LS];
-  __shared__ double bs[NB * LS];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lam = blockIdx.y, chunk = blockIdx.z;
-  const int r0 = chunk * kLosoRows;
-  const int rows_valid = t.rows_per_lambda - r0 < kLosoRows ? t.rows_per_lambda - r0 : kLosoRows;
-  double* vrows = t.v + ((long long)lam * t.rows_per_lambda + r0) * t.np;
-  double* orows = t.out + ((long long)lam * t.rows_per_lambda + r0) * t.np;
-  const double* lmat = t.l + (size_t)lam * t.np * t.np;
-  const int k0 = t.k * NB;
-  // the block this workgroup updates: forward i = k + blockIdx.x, backward m = k - blockIdx.x
-  const int bi = kBack ? t.k - (int)blockIdx.x : t.k + (int)blockIdx.x;
-  // forward: tile L[bi][k] (rows of block bi, columns of block k), used as . L_ik^T  (NT)
-  // backward: tile L[k][bi], used as . L_km (NN)
-  const double* tile = kBack ? lmat + (size_t)k0 * t.np + (size_t)bi * NB
-                             : lmat + (size_t)bi * NB * t.np + k0;
-  // (its loads leave now and arrive under the first product: the step was two dependent round
-  // trips to memory)
-  f64x2 lt[8];
-  if (blockIdx.x != 0) tile_to_regs(lt, tile, t.np, NB, tid);
-  rows_to_lds(as, vrows + k0, t.np, rows_valid, NB, tid);
-  tile_to_lds(bs, t.linv + ((size_t)lam * t.nblk + t.k) * NB * NB, NB, NB, tid);
-  __syncthreads();
-  f64x4 acc[2];
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[s][r] = 0.0;
-  gemm_32x64<!kBack>(as, bs, wave, lane, acc);           // forward: . Linv^T ; backward: . Linv
-  const int ccol = 16 * wave + (lane & 15);
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ys[(16 * s + (lane >> 4) + 4 * r) * LS + ccol] = acc[s][r];
-  __syncthreads();
-  if (blockIdx.x == 0) {
-    for (int idx = tid; idx < kLosoRows * NB; idx += 256) {
-      const int r = idx >> 6, c = idx & 63;
-      if (r < rows_valid) orows[(long long)r * t.np + k0 + c] = ys[r * LS + c];
-    }
-    return;
-  }
-  regs_to_lds(bs, lt, tid);
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[s][r] = 0.0;
-  gemm_32x64<!kBack>(ys, bs, wave, lane, acc);
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * s + (lane >> 4) + 4 * r;
-      if (row < rows_valid) vrows[(long long)row * t.np + (size_t)bi * NB + ccol] -= acc[s][r];
-    }
-}
-
-// ---- the same substitutions in steps of FOUR block columns (256 unknowns) -----------------------
-// A substitution above is a chain of 33 dependent launches (n = 2049), ~17 us each whatever they
-// compute: 1.1 ms per application of the preconditioner, 8 of the C5 sweep's 24 ms.  With the
+// ---- the substitutions of the preconditioner, in steps of FOUR block columns (256 unknowns) -----
+// In steps of one 64-block a substitution was a chain of 33 dependent launches (n = 2049), ~17 us
+// each whatever they computed: 1.1 ms per application of the preconditioner, 8 of the C5 sweep's
+// 24 ms (that form has been removed).  With the
 // inverse of every 256 x 256 diagonal block of L at hand (four 64-blocks: X_ii = Linv_ii,
 // X_ij = -Linv_ii sum_{j <= p < i} L_ip X_pj, built once per factorisation: loso_binv_kernel) a
 // step solves 256 unknowns at a time -- one launch for the solved block (a sum of <= 4 products
@@ -1525,7 +1444,6 @@ static int ridge_solve_impl(td_handle* h, td_stats* s, const double* lambdas_hos
         TD_HIP(h, hipStreamSynchronize(h->stream));
         h->last_iterations = st[1]; h->last_cg_status = st[0];
         if (st[0] == 0) { h->last_solver = TD_SOLVER_CG; return TD_OK; }
-        if (st[0] == 5) return td_fail(h, TD_ERR_STATE, "cg_toeplitz_kernel: debug build (first product dumped)");
       }
     }
   }
@@ -1564,26 +1482,9 @@ static int ridge_solve_impl(td_handle* h, td_stats* s, const double* lambdas_hos
     else if (rc_cg != TD_OK) return rc_cg;
   }
   if (try_cg) {
-    int st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    TD_HIP(h, hipMemcpyAsync(st, h->cg_status, sizeof(int) * 8, hipMemcpyDeviceToHost, h->stream));
+    int st[2] = {0, 0};
+    TD_HIP(h, hipMemcpyAsync(st, h->cg_status, sizeof(int) * 2, hipMemcpyDeviceToHost, h->stream));
     TD_HIP(h, hipStreamSynchronize(h->stream));
-    if (td_dev_env("TD_CG_TIMING"))      // development (a -DTD_CG_TIMING build fills them): 10 ns ticks per phase
-      fprintf(stderr, "cg phases (10 ns ticks over %d iterations): pre %d matvec %d publish %d poll %d post %d update %d\n",
-              st[1], st[2], st[3], st[4], st[5], st[6], st[7]);
-    if (td_dev_env("TD_CG_TIMING") && h->cg_packets) {
-      static long long ts[1024];
-      hipMemcpy(ts, reinterpret_cast<char*>(h->cg_packets) + sizeof(unsigned long long) * 2 * 2 * 256 * 8 + 256, sizeof(ts),
-                hipMemcpyDeviceToHost);
-      long long p0 = ts[0], p1 = ts[0], d0 = ts[512], d1 = ts[512];
-      for (int i = 0; i < 256; ++i) {
-        if (ts[i] < p0) p0 = ts[i];
-        if (ts[i] > p1) p1 = ts[i];
-        if (ts[512 + i] < d0) d0 = ts[512 + i];
-        if (ts[512 + i] > d1) d1 = ts[512 + i];
-      }
-      fprintf(stderr, "iteration 20: publish spread %lld ticks, first done %lld after first publish, last done %lld; wg0 publish +%lld done +%lld\n",
-              p1 - p0, d0 - p0, d1 - p0, ts[0] - p0, ts[512] - p0);
-    }
     h->last_iterations = st[1]; h->last_cg_status = st[0];
     if (st[0] == 0) {
       h->last_solver = TD_SOLVER_CG;
@@ -1825,14 +1726,8 @@ static int ridge_solve_loso_impl(td_handle* h, td_stats* total, td_stats* const*
                      0LL, np, n, np, 1.0 / (double)frames_total, lams, pa);
   TD_HIP(h, hipMemsetAsync(rt, 0, sizeof(double) * (size_t)n_lambda * kMaxRhs * np, h->stream));
   TD_TRY(chol_factor_forward(h, pa, rt, sol, linv, tolv, np, 1, n_lambda, nullptr, kMaxRhs, n));
-#ifdef TD_DEV_SWITCHES
-  static const bool trsm64 = td_dev_env("TD_LOSO_TRSM64") != nullptr;        // development builds only: A/B runs
-#else
-  constexpr bool trsm64 = false;
-#endif
-  if (!trsm64)
-    hipLaunchKernelGGL(loso_binv_kernel, dim3((unsigned)nbig, (unsigned)n_lambda, kBig), dim3(256), 0, h->stream,
-                       pa, linv, xinv, np, nblk, nbig);
+  hipLaunchKernelGGL(loso_binv_kernel, dim3((unsigned)nbig, (unsigned)n_lambda, kBig), dim3(256), 0, h->stream,
+                     pa, linv, xinv, np, nblk, nbig);
   // the folds' dense moments and right-hand sides
   if (folds) {
     for (int f = 0; f < n_folds; ++f)
@@ -1853,43 +1748,26 @@ static int ridge_solve_loso_impl(td_handle* h, td_stats* total, td_stats* const*
   const unsigned chunks = (unsigned)td_ceil_div(rows_per_lambda, kLosoRows);
   auto precondition = [&]() -> int {        // Z = (P + lambda I)^-1 R
     TD_HIP(h, hipMemcpyAsync(V, R, sizeof(double) * (size_t)rows * np, hipMemcpyDeviceToDevice, h->stream));
-    if (!trsm64) {
-      LosoBig b;
-      b.l = pa; b.xinv = xinv; b.np = np; b.nblk = nblk; b.nbig = nbig; b.rows_per_lambda = rows_per_lambda;
-      b.v = V; b.out = Y;
-      for (int kb = 0; kb < nbig; ++kb) {
-        b.kb = kb; b.m = nblk - kBig * kb < kBig ? nblk - kBig * kb : kBig;
-        hipLaunchKernelGGL(loso_big_solve_kernel<false>, dim3((unsigned)b.m, (unsigned)n_lambda, chunks), dim3(256), 0,
-                           h->stream, b);
-        const int beyond = nblk - kBig * kb - b.m;
-        if (beyond > 0)
-          hipLaunchKernelGGL(loso_big_update_kernel<false>, dim3((unsigned)beyond, (unsigned)n_lambda, chunks),
-                             dim3(256), 0, h->stream, b);
-      }
-      b.v = Y; b.out = Z;
-      for (int kb = nbig - 1; kb >= 0; --kb) {
-        b.kb = kb; b.m = nblk - kBig * kb < kBig ? nblk - kBig * kb : kBig;
-        hipLaunchKernelGGL(loso_big_solve_kernel<true>, dim3((unsigned)b.m, (unsigned)n_lambda, chunks), dim3(256), 0,
-                           h->stream, b);
-        if (kb > 0)
-          hipLaunchKernelGGL(loso_big_update_kernel<true>, dim3((unsigned)(kBig * kb), (unsigned)n_lambda, chunks),
-                             dim3(256), 0, h->stream, b);
-      }
-      return TD_OK;
+    LosoBig b;
+    b.l = pa; b.xinv = xinv; b.np = np; b.nblk = nblk; b.nbig = nbig; b.rows_per_lambda = rows_per_lambda;
+    b.v = V; b.out = Y;
+    for (int kb = 0; kb < nbig; ++kb) {
+      b.kb = kb; b.m = nblk - kBig * kb < kBig ? nblk - kBig * kb : kBig;
+      hipLaunchKernelGGL(loso_big_solve_kernel<false>, dim3((unsigned)b.m, (unsigned)n_lambda, chunks), dim3(256), 0,
+                         h->stream, b);
+      const int beyond = nblk - kBig * kb - b.m;
+      if (beyond > 0)
+        hipLaunchKernelGGL(loso_big_update_kernel<false>, dim3((unsigned)beyond, (unsigned)n_lambda, chunks),
+                           dim3(256), 0, h->stream, b);
     }
-    LosoTrsm t;
-    t.l = pa; t.linv = linv; t.np = np; t.nblk = nblk; t.rows_per_lambda = rows_per_lambda;
-    t.v = V; t.out = Y;
-    for (int k = 0; k < nblk; ++k) {
-      t.k = k;
-      hipLaunchKernelGGL(loso_trsm_kernel<false>, dim3((unsigned)(nblk - k), (unsigned)n_lambda, chunks),
-                         dim3(256), 0, h->stream, t);
-    }
-    t.v = Y; t.out = Z;
-    for (int k = nblk - 1; k >= 0; --k) {
-      t.k = k;
-      hipLaunchKernelGGL(loso_trsm_kernel<true>, dim3((unsigned)(k + 1), (unsigned)n_lambda, chunks),
-                         dim3(256), 0, h->stream, t);
+    b.v = Y; b.out = Z;
+    for (int kb = nbig - 1; kb >= 0; --kb) {
+      b.kb = kb; b.m = nblk - kBig * kb < kBig ? nblk - kBig * kb : kBig;
+      hipLaunchKernelGGL(loso_big_solve_kernel<true>, dim3((unsigned)b.m, (unsigned)n_lambda, chunks), dim3(256), 0,
+                         h->stream, b);
+      if (kb > 0)
+        hipLaunchKernelGGL(loso_big_update_kernel<true>, dim3((unsigned)(kBig * kb), (unsigned)n_lambda, chunks),
+                           dim3(256), 0, h->stream, b);
     }
     return TD_OK;
   };

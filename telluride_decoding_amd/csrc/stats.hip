@@ -150,10 +150,7 @@ inline void launch_ones_rows(td_handle* h, double* g, int rows, int row, int c, 
 // `fresh` statistics (td_stats_reset pending) every job overwrites instead of adding and the
 // memset of the reset goes away too.
 constexpr int kFinThreads = 1024;
-#ifndef TD_FIN_VEC_PHASES
-#define TD_FIN_VEC_PHASES 8
-#endif
-constexpr int kFinVecPhases = TD_FIN_VEC_PHASES;   // slab phases of the float4 reduction (fin_reduce4)
+constexpr int kFinVecPhases = 8;    // slab phases of the float4 reduction (fin_reduce4)
 constexpr int kFinMaxReduce = 5;      // F'xx + up to 4 target columns
 
 struct FinalizeParams {
@@ -1157,7 +1154,8 @@ int td_stats_accumulate_parts(td_handle* h, td_stats* s, const float* x_dev, int
 // 6 for <= 128, each at the speed of the aligned 64-channel case; the copies cost a read and a
 // write of the input per pass.  (Before: two diagonal 64-channel blocks on the unaligned bf16x3
 // path and two off-diagonal ones on the float32 matrix kernel with A and B at different
-// channels of the same rows -- 1.15 ms of the codelab accumulate's 2.0; `TD_AUTO_BLOCKS` keeps it.)
+// channels of the same rows -- 1.15 ms of the codelab accumulate's 2.0; it remains the fallback,
+// lagcov_auto_blocks.)
 namespace {
 // out[r][k] = x[row_lo + r][32 (k < 32 ? ti : tj) + (k & 31)], zero past channel c; the largest
 // magnitude of every column of the copy goes into tab (the float16 kernel's channel scales:
@@ -1237,7 +1235,6 @@ int lagcov_auto(td_handle* h, const float* x, int64_t ldx, int c, const std::vec
   }
   if (c <= 64 || c > 128)
     return td_lagcov(h, x, ldx, c, false, x, ldx, c, segs, 0, l, g, true, 0, 0, false, true);
-  static const bool blocks = td_dev_env("TD_AUTO_BLOCKS") != nullptr;          // development: A/B runs
   long long lo = 0, hi = 0;
   bool any = false, same = true;
   for (const LagSeg& sg : segs) {
@@ -1249,7 +1246,7 @@ int lagcov_auto(td_handle* h, const float* x, int64_t ldx, int c, const std::vec
   }
   // (more than 64 lags: not the split kernel's case; > 2^33 bytes of copy: the caller's arrays
   // of that size are cut into calls anyway)
-  if (blocks || !any || !same || l > 64 || (hi - lo) > (1LL << 25)) return lagcov_auto_blocks(h, x, ldx, c, segs, l, g);
+  if (!any || !same || l > 64 || (hi - lo) > (1LL << 25)) return lagcov_auto_blocks(h, x, ldx, c, segs, l, g);
   const long long rows = hi - lo;
   std::vector<LagSeg> rel(segs);
   for (LagSeg& sg : rel) { sg.a_row0 -= lo; sg.b_row0 -= lo; }
@@ -1299,7 +1296,6 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
                      int64_t first_slot, bool do_main, bool do_targets, bool tgt_first, bool defer) {
   LagcovPlan mp;
   TargetsPlan tp;
-  PrepassPlan pp;
   VirtPlan vp;                   // <= 32 channels: the float16 kernel on virtual images (lagcov.hip)
   Narrow16Plan np16;             // <= 16 channels: matrix + targets in one streaming kernel (lagcov.hip)
   if (h->narrow16) TD_TRY(td_narrow16_plan(h, s->c1, s->d, s->pre1, s->l1, ldx, ldy, syx, &np16));
@@ -1312,31 +1308,23 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
     if (!vp.ok) TD_TRY(td_lagcov_plan(h, x_dev, ldx, s->c1, false, x_dev, ldx, s->c1, sxx, 0, s->l1, &mp));
   }
   const bool virt = do_main && !n16 && vp.ok;
-  // Two forms, 3 launches and two reads of x each:
-  //   default: targets kernel (yT x~, column sums, channel maxima) -> lag kernel -> finalize;
-  //   FOLDED (one target column, no pre-context, the float16 kernel): a streaming pre-pass
-  //   (channel maxima, column sums of x, sum of y) -> the lag kernel with the targets riding
-  //   along (tgt_tile, lagcov.hip) -> finalize.
-  // (Measured at C2: the targets inside the lag kernel cost it 42 us, 6 %, and still need the
-  // 49 us pre-pass; as a pass of their own -- which is HBM-bound, has the matrix pipe to spare
-  // and measures the channel maxima on the way -- they cost 62 us in all.  So the folded form is
-  // opt-in: TD_ACC_FOLDED.)
-  static const bool want_fold = td_dev_env("TD_ACC_FOLDED") != nullptr;      // development: A/B runs
-  const bool folded = do_main && !virt && !n16 && do_targets && s->d == 1 && s->pre1 == 0 && want_fold &&
-                      td_lagcov_plan_targets(&mp);
-  if (folded) {
-    TD_TRY(td_chan_prepass_plan(h, syx, &pp));
-  } else if (do_targets && !n16) {
+  // 3 launches and two reads of x: targets kernel (yT x~, column sums, channel maxima) -> lag kernel
+  // -> finalize.  (A folded form once carried one target column inside the float16 lag kernel behind
+  // a streaming pre-pass for the maxima and column sums.  Measured at C2, the targets cost the lag
+  // kernel 42 us, 6 %, plus the 49 us pre-pass; as a pass of their own -- which is HBM-bound, has
+  // the matrix pipe to spare and measures the channel maxima on the way -- they cost 62 us in all.
+  // The folded form was removed.)
+  if (do_targets && !n16) {
     TD_TRY(td_lagcov_targets_plan(h, y_dev, ldy, s->d, x_dev, ldx, s->c1, syx, -s->pre1, s->l1, &tp));
     TD_REQUIRE(h, tp.handled && tp.n_work > 0, "accumulate_fused: the targets kernel refused the shape");
   }
   const size_t main_bytes = n16 ? np16.scratch_bytes : virt ? vp.scratch_bytes
-                            : do_main ? mp.scratch_bytes + (folded ? mp.tpartial_bytes : 0) : 0;
+                            : do_main ? mp.scratch_bytes : 0;
   // TD_ACC_DEFER: the finalize launch is left to td_stats_complete (another stream, later): what it reads
   // then -- the partial slabs, the file table, the channel scales -- lives in blocks the statistics own,
   // not in the handle's scratch, which the next call of this stream overwrites.
-  const bool deferred = defer && do_main && !folded && !virt;
-  const size_t scratch_bytes = main_bytes + (folded ? pp.scratch_bytes : do_targets && !n16 ? tp.scratch_bytes : 0);
+  const bool deferred = defer && do_main && !virt;
+  const size_t scratch_bytes = main_bytes + (do_targets && !n16 ? tp.scratch_bytes : 0);
   void* scratch = nullptr;
   if (deferred) {
     if (scratch_bytes > s->dscratch_bytes) {
@@ -1389,19 +1377,6 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
   fp.jobs = reinterpret_cast<const WinJob*>(jobs_dev);
   fp.x = x_dev; fp.ldx = ldx; fp.c = s->c1; fp.n_files = num_files; fp.hw = s->hw;
   TargetsOutputs to;
-  const double* pre_csum = nullptr;
-  const double* pre_ysum = nullptr;
-  if (folded) {
-    unsigned* tab = nullptr;
-    TD_TRY(td_chan_tab(h, &tab));
-    // (the lag kernel stages up to 64 rows past a slab's end: they must not overflow float16)
-    TD_TRY(td_chan_prepass_launch(h, &pp, x_dev, ldx, s->c1, y_dev, ldy, 64, tab, base + main_bytes,
-                                  &pre_csum, &pre_ysum));
-    mp.tab = tab; mp.ty = y_dev; mp.ldty = ldy;
-    mp.tsegs.resize(syx.size());
-    for (size_t f = 0; f < syx.size(); ++f)
-      mp.tsegs[f] = TgtWork{syx[f].a_row0, syx[f].a_valid, syx[f].u_begin, syx[f].u_end};
-  }
   // The targets kernels run first: they stream every row the lag kernel will touch, so the first
   // of them also measures the channel maxima the float16 lag kernel scales by (no pre-context:
   // with one the lag kernel reaches further past a range's end than the targets do, and it
@@ -1413,7 +1388,7 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
     TD_TRY(td_narrow16_launch(h, &np16, x_dev, ldx, y_dev, ldy, base, do_main, do_targets, s->g + s->off_fxx,
                               !s->fresh_main, s->g + s->off_gxo, !s->fresh_tgt, &job16, &to));
   }
-  if (do_targets && !folded && !n16) {
+  if (do_targets && !n16) {
     to.maxtab = nullptr;
     if (do_main && (mp.f16 || virt) && s->pre1 == 0) {
       TD_TRY(td_chan_tab(h, &to.maxtab));
@@ -1433,7 +1408,7 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
     TD_TRY(td_lagcov_targets_launch(h, &tp, base + main_bytes, s->g + s->off_gxo, !s->fresh_tgt, &to));
   }
   if (do_main) {
-    LagReduceJob job, tjob;
+    LagReduceJob job;
     // (the maxima a TARGETS_FIRST call of these files left in the statistics: no pre-pass here)
     const bool ahead = !do_targets && s->tab_ready && (mp.f16 || virt) && s->pre1 == 0;
     if (ahead) mp.tab = s->chan_tab;
@@ -1464,12 +1439,10 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
         mp.scale_out = s->dscale;
         mp.zero_tab = h->chan_max + kChanTab * ((h->chan_phase + 1) & 1);
       }
-      TD_TRY(td_lagcov_launch(h, &mp, base, s->g + s->off_fxx, !s->fresh_main, 0, 0, &job,
-                              s->g + s->off_gxo, !s->fresh_tgt, s->d + 1, folded ? &tjob : nullptr));
+      TD_TRY(td_lagcov_launch(h, &mp, base, s->g + s->off_fxx, !s->fresh_main, 0, 0, &job));
     }
     if (mp.scale_out && job.scale_a) job.scale_a = job.scale_b = mp.scale_out;
     add_reduce(job);
-    if (folded) add_reduce(tjob);
     if ((mp.f16 || (virt && !own_tab)) && !ahead) {      // this call used table chan_phase & 1: clear the other for the next
       ++h->chan_phase;
       fp.zero_tab = mp.zero_tab ? nullptr : h->chan_max + kChanTab * (h->chan_phase & 1);
@@ -1480,12 +1453,12 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
     fp.n_value = (double)s->frames;
     s->fresh_main = false;
   }
-  if (do_targets && !folded)
+  if (do_targets)
     for (int i = 0; i < s->d; ++i) add_reduce(to.jobs[i]);
   fp.b_ysum = blocks;
   if (do_targets) {
-    if (folded) { fp.ysum[0] = pre_ysum; fp.ys_n_work = pp.blocks; }
-    else { for (int i = 0; i < s->d; ++i) fp.ysum[i] = to.ysum[i]; fp.ys_n_work = to.n_work; }
+    for (int i = 0; i < s->d; ++i) fp.ysum[i] = to.ysum[i];
+    fp.ys_n_work = to.n_work;
     fp.ys_cols = s->d; fp.ys_accumulate = s->fresh_tgt ? 0 : 1;
     fp.sy = s->g + s->off_sy;
     blocks += s->d;
@@ -1493,8 +1466,7 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
   fp.b_ones = blocks;
   if (do_targets) {
     fp.ones_l = s->l1;
-    if (folded) { fp.csum = pre_csum; fp.cs_n_work = pp.blocks; fp.cs_pad = 64; }
-    else { fp.csum = to.csum; fp.cs_n_work = to.n_work; fp.cs_pad = to.cb_pad; }
+    fp.csum = to.csum; fp.cs_n_work = to.n_work; fp.cs_pad = to.cb_pad;
     fp.e_min = -s->pre1; fp.rows = s->d + 1; fp.row = s->d; fp.ones_accumulate = s->fresh_tgt ? 0 : 1;
     fp.gxo = s->g + s->off_gxo;
     blocks += s->l1;
@@ -1521,9 +1493,7 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
       return TD_OK;
     }
   }
-#ifndef TD_ABL_NOFINALIZE     // timing ablation (wrong statistics): what the finalize launch costs the accumulate stream
   hipLaunchKernelGGL(stats_finalize_kernel, dim3((unsigned)blocks), dim3(kFinThreads), 0, h->stream, fp);
-#endif
   TD_HIP(h, hipGetLastError());
   return TD_OK;
 }
@@ -1584,8 +1554,7 @@ int accumulate_each(td_handle* h, td_stats* const* each, const float* x_dev, int
   }
   TD_TRY(td_lagcov_targets_launch(h, &tp, base + main_bytes, s0->g + s0->off_gxo, false, &to));
   LagReduceJob job;
-  TD_TRY(td_lagcov_launch(h, &mp, base, s0->g + s0->off_fxx, false, 0, 0, &job, s0->g + s0->off_gxo, false,
-                          s0->d + 1, nullptr));
+  TD_TRY(td_lagcov_launch(h, &mp, base, s0->g + s0->off_fxx, false, 0, 0, &job));
   TD_REQUIRE(h, job.n_work == (int)mp.works.size() && !job.vmap, "accumulate_each: the matrix kernel merged work items");
   bool zero_next = false;
   if (mp.f16) { ++h->chan_phase; zero_next = true; }
@@ -1817,8 +1786,7 @@ int td_stats_accumulate_ranges(td_handle* h, td_stats* s, const float* x_dev, in
   // (td_gram), done by MAIN; TARGETS then has nothing left to add.
   const bool one_pass = stats_one_pass(s);
 
-  static const bool no_fuse = td_dev_env("TD_ACC_UNFUSED") != nullptr;     // development: A/B runs
-  if (stats_fusable(s) && new_frames > 0 && !no_fuse)
+  if (stats_fusable(s) && new_frames > 0)
     return accumulate_fused(h, s, x_dev, ldx, y_dev, ldy, sxx, syx, j1, num_files, new_frames,
                             first_slot, do_main, do_targets, tgt_first, defer);
   TD_REQUIRE(h, !tgt_first, "td_stats_accumulate_parts: TARGETS_FIRST needs the fused accumulate path");
@@ -1897,9 +1865,8 @@ int td_stats_accumulate_ranges(td_handle* h, td_stats* s, const float* x_dev, in
       // (a one-column view -- an envelope -- is a "target column" against itself / against x: the
       // matrix-core targets kernel in windows of 32 lags, td_lagcov_column, instead of a padded
       // 64-channel tile for its auto-covariance (0.14 ms at the codelab's shape) and the skinny
-      // VALU kernel for the cross-covariance (0.28 ms); `TD_LAG_NO_COLUMN` keeps those)
-      static const bool no_column = td_dev_env("TD_LAG_NO_COLUMN") != nullptr;
-      const bool column = s->c2 == 1 && !no_column;
+      // VALU kernel for the cross-covariance (0.28 ms))
+      const bool column = s->c2 == 1;
       if (column)
         TD_TRY(td_lagcov_column(h, x2_dev, ldx2, x2_dev, ldx2, 1, syy, 0, s->l2, s->g + s->off_fyy));
       else
@@ -1915,8 +1882,7 @@ int td_stats_accumulate_ranges(td_handle* h, td_stats* s, const float* x_dev, in
       const int e_min_xy = -(s->post1 + s->pre2), e_cnt_xy = s->l1 + s->l2 - 1;
       bool swap = s->c2 <= 8 && s->c1 > 8;
       for (const LagSeg& sg : sxy) if (sg.u_begin != 0) swap = false;
-      static const bool no_swap = td_dev_env("TD_GXY_DIRECT") != nullptr;      // development: A/B runs
-      if (swap && !no_swap) {
+      if (swap) {
         const int e_max_xy = e_min_xy + e_cnt_xy - 1;
         std::vector<LagSeg> sw(sxy.size());
         for (size_t f = 0; f < sxy.size(); ++f) {
@@ -1978,9 +1944,8 @@ int td_stats_accumulate_ranges(td_handle* h, td_stats* s, const float* x_dev, in
     // general float32 matrix kernel on [y | 1] padded to 128 rows -- 3.4 ms per 1e6 samples for
     // 8 features x 32 lags against 64 targets, 1.3 ms for 64 channels against 8 targets -- and a
     // column sum that read the targets once per column.)
-    static const bool wide_general = td_dev_env("TD_TARGETS_GENERAL") != nullptr;   // development: A/B runs
     bool wide_done = false;
-    if (s->d > 4 && !wide_general) {
+    if (s->d > 4) {
       bool from_start = true;
       for (const LagSeg& sg : syx) if (sg.u_begin != 0) from_start = false;
       const int e_min = -s->pre1, e_max = s->post1;

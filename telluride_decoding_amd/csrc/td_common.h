@@ -13,16 +13,8 @@
 
 #include "td_hotpath.h"
 
-// Development switches (A/B runs of kernels inside one process tree, ablations) are read from the
-// environment ONLY in a -DTD_DEV_SWITCHES build (tools/build_variant.sh); the shipped library reads
-// TD_RCCL_LIB (comm.hip) and nothing else: a stray TD_* variable in a user's environment cannot change
-// which kernel runs.
-#ifdef TD_DEV_SWITCHES
-#include <cstdlib>
-static inline const char* td_dev_env(const char* name) { return getenv(name); }
-#else
-static inline const char* td_dev_env(const char*) { return nullptr; }
-#endif
+// The library reads one environment variable, TD_RCCL_LIB (comm.hip): no TD_* variable in a user's
+// environment can change which kernel runs.
 
 constexpr int kChanShards = 16;
 constexpr int kChanTab = (kChanShards + 1) * 128;     // unsigned per table
@@ -325,14 +317,6 @@ struct LagParams {
   int e_pad, ca_pad, cb_pad;
   int lag_g, lag_lg;   // lags per workgroup (8, or 4/2/1 with the 8 wave slots split over time) and log2
   const unsigned* chan_max;   // float16 form: largest magnitude of each channel, float bits [64]
-  // float16 form, optional: one regression target column rides along (see bf_kstep).  tworks[i]
-  // belongs to works[i]; tpartial [n_work * n_groups][32 lags][64 channels] float32 sums of
-  // (y s_y)(x_j s_j); ty_max[0] = largest |y| (float bits).
-  const float* ty;
-  long long ldty;
-  const struct TgtWork* tworks;
-  float* tpartial;
-  const unsigned* ty_max;
   // virtual images (kVirt): the images, the workgroups' task tables [n_groups], per work item the
   // recording's summed rows; slab_elems floats per partial slab
   // float16 form, optional (a finalize launch deferred to another stream, TD_ACC_DEFER): workgroup 0 also leaves
@@ -407,12 +391,6 @@ __host__ __device__ __forceinline__ long long td_virt_offset(const VirtMap* vm, 
   return ((long long)(P.slot0 + e1) * 32 + P.col_a + sa * P.wa + (i & 31)) * 32 + P.col_b + sb * P.wb + (j & 31);
 }
 
-// Where work item i finds its targets: y[u] = ty[(y_row0 + u) * ldty], zero outside
-// [seg_begin, seg_end) (the rows of the recording this call sums) and outside [0, y_valid).
-struct TgtWork {
-  long long y_row0, y_valid, seg_begin, seg_end;
-};
-
 // One float64 reduction of partial slabs, run by a reduction launch of its own (td_lagcov) or
 // as one job of the fused finalize kernel of an accumulate call (stats.hip):
 //   g[(e * ca_dst + i) * ldg + j] (+)= sum_w partial[w][e][i][j]
@@ -450,12 +428,8 @@ struct LagcovPlan {
   // float16 form, set by the caller between plan and launch:
   unsigned* scale_out = nullptr; // IN, optional: LagParams::scale_out / zero_tab of the float16 kernel
   unsigned* zero_tab = nullptr;
-  unsigned* tab = nullptr;       // channel maxima [0, 64) x, [64] y -- already filled (td_chan_prepass);
+  unsigned* tab = nullptr;       // channel maxima of x, already filled (by the targets kernel);
                                  // null: the launch measures the maxima of x itself (chan_max_kernel)
-  const float* ty = nullptr;     // one target column rides along (needs tab, e_min = 0, <= 32 lags)
-  long long ldty = 0;
-  std::vector<TgtWork> tsegs;    // per SEGMENT: where its targets are
-  size_t tpartial_bytes = 0;     // (set by td_lagcov_plan_targets) scratch behind the Gram slabs
   int few_g = 8, ca_eff = 0, cb = 0, e_count = 0;
   int small_lpt = 8;             // skinny kernel: lags per thread (4 x that per workgroup)
   long long total = 0, nwg = 0;
@@ -464,12 +438,9 @@ struct LagcovPlan {
 int td_lagcov_plan(td_handle* h, const float* a, int64_t lda, int ca, bool a_ones, const float* b,
                    int64_t ldb, int cb, const std::vector<LagSeg>& segs, int e_min, int e_count,
                    LagcovPlan* plan);
-// scratch: plan.scratch_bytes (+ plan.tpartial_bytes) of device memory that stays untouched until
-// the reduction ran.  tjob (with plan.ty): the reduction of the targets' sums into row 0 of
-// tg_dev [e][t_rows][cb].
+// scratch: plan.scratch_bytes of device memory that stays untouched until the reduction ran.
 int td_lagcov_launch(td_handle* h, LagcovPlan* plan, void* scratch, double* g_dev, bool accumulate,
-                     int ldg, int rows_dst, LagReduceJob* job, double* tg_dev = nullptr,
-                     bool t_accumulate = false, int t_rows = 0, LagReduceJob* tjob = nullptr);
+                     int ldg, int rows_dst, LagReduceJob* job);
 // The same for the shapes that run on virtual images (<= 32 or 65..128 channels of ONE stream, lags
 // 0 .. l - 1 <= 63, the float16 form): plan->ok says whether the shape is one of them.  The launch
 // queues the matrix kernel; `tab` holds the channel maxima of x (kChanTab layout, filled by the
@@ -497,23 +468,8 @@ int td_lagcov_virt_launch(td_handle* h, VirtPlan* plan, const float* x, int64_t 
 int td_lagcov_virt(td_handle* h, const float* x, int64_t ldx, int c, const std::vector<LagSeg>& segs,
                    int l, double* g_dev, bool accumulate, bool* handled);
 
-// Asks the planned float16 launch to carry a target column: sizes its scratch.  False when the
-// plan cannot (not the float16 split kernel, or more than 32 lags).
-bool td_lagcov_plan_targets(LagcovPlan* plan);
-
-// The streaming pre-pass of a float16 accumulate (chan_prepass_kernel, lagcov.hip): channel
-// maxima into tab, per-workgroup column sums of x and sums of y into scratch.
-struct PrepassPlan {
-  std::vector<LagWork> strips;   // a_* = y stream, b_* = x stream
-  int blocks = 0;
-  size_t scratch_bytes = 0;
-};
 // The handle's channel-maximum table for the call that is being queued (allocated on first use).
 int td_chan_tab(td_handle* h, unsigned** tab);
-int td_chan_prepass_plan(td_handle* h, const std::vector<LagSeg>& syx, PrepassPlan* plan);
-int td_chan_prepass_launch(td_handle* h, PrepassPlan* plan, const float* x, int64_t ldx, int c,
-                           const float* y, int64_t ldy, int halo, unsigned* tab, void* scratch,
-                           const double** csum, const double** ysum);
 
 // The same for the targets path (td_lagcov_targets): one matrix-core kernel per target column.
 struct TargetsPlan {
