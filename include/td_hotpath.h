@@ -632,6 +632,36 @@ int td_context_out(td_handle* h, const double* z_dev, int64_t m, int cs, int64_t
                    int64_t state_rows, int pre, int post, double mean, double std_dev, float* out32_dev,
                    double* out64_dev, int64_t ldout, double* state_out_dev);
 
+/* ------------------------------------------------------------------ audio features
+ * preprocess.AudioFeatures (preprocess.py:589-755): the intensity envelope and the auditory spectrogram.
+ *
+ * td_audio_intensity: the windowed mean of audio_resample (preprocess.py:619-686) over the virtual rows
+ * [buf ; f(x)], tau = buf_rows, frames_in = buf_rows + n.  buf_dev [buf_rows, c] float64 (the carried buffer,
+ * contiguous); x_dev [n, c] float32 (float64 when x_is_f64), row stride ldx; f(x) = float32(x)^2 (squared in
+ * float32) when square != 0, else x.  Output row i < rows_out of out_dev [rows_out, c] float64 (contiguous) is
+ * the float64 mean over rows [t1, t2), t = i / fs_out, t1 = max(0, rint(fs_in (t - half_window)) + tau),
+ * t2 = min(frames_in, rint(fs_in (t + half_window)) + tau) in float64 in that order; NaN when t1 >= t2.
+ * post != 0: sqrt, then ** exponent (numpy's fast paths for 1, 2, 0.5, 0, -1).  windows_dev (may be NULL):
+ * [rows_out, 2] int64 receives (t1, t2). */
+int td_audio_intensity(td_handle* h, const double* buf_dev, int64_t buf_rows, const void* x_dev, int x_is_f64,
+                       int64_t ldx, int64_t n, int c, int square, int64_t rows_out, double fs_in, double fs_out,
+                       double half_window, int post, double exponent, double* out_dev, int64_t* windows_dev);
+/* Rows [row_begin, row_end) of the same [buf ; f(x)] (the pass-through of audio_resample and the new
+ * buffer), contiguous, into exactly one of out32_dev (rounded to float32; sqrt and ** exponent in float32
+ * when post != 0) or out64_dev (float64; post 1: sqrt and ** exponent in float64, post 2: the sqrt in
+ * float32 and ** exponent in float64 -- numpy's promotion of a float32 array to a float64 exponent). */
+int td_audio_passthrough(td_handle* h, const double* buf_dev, int64_t buf_rows, const void* x_dev, int x_is_f64,
+                         int64_t ldx, int64_t n, int c, int square, int64_t row_begin, int64_t row_end, int post,
+                         double exponent, float* out32_dev, double* out64_dev);
+/* compute_spectrogram (preprocess.py:712-755) of wave_dev [n] float32: scipy.signal.stft of the
+ * pre-emphasised wave (lfilter([1, -0.95])), periodic Hamming window of seg samples, hop, nfft-point
+ * one-sided DFT, seg // 2 zeros of boundary padding, `frames` frames; the power smoothed by the causal FIR
+ * taps_host[num_taps] along frequency then time, compressed to (off + P)^(1/4) - off^(1/4) with
+ * off = 1e-4 max P and scaled to 255 / max.  out_dev [nfft / 2 + 1, frames] float64.  Limits: seg <= 1024,
+ * seg <= nfft <= 4096, num_taps <= 16, n >= seg. */
+int td_audio_spectrogram(td_handle* h, const float* wave_dev, int64_t n, int seg, int hop, int nfft,
+                         const double* taps_host, int num_taps, int64_t frames, double* out_dev);
+
 #ifdef __cplusplus
 }
 #endif

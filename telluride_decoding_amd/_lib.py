@@ -130,6 +130,9 @@ SIGNATURES = {
                         _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _i, _vp, _i64],
     'td_mean_f64': [_vp, _vp, _i64, _i, _i64, _vp],
     'td_context_out': [_vp, _vp, _i64, _i, _i64, _vp, _i64, _i, _i, _d, _d, _vp, _vp, _i64, _vp],
+    'td_audio_intensity': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _d, _d, _d, _i, _d, _vp, _vp],
+    'td_audio_passthrough': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _i64, _i, _d, _vp, _vp],
+    'td_audio_spectrogram': [_vp, _vp, _i64, _i, _i, _i, _pd, _i, _i64, _vp],
 }
 _RESTYPE = {'td_last_error': _c.c_char_p}
 

@@ -800,6 +800,51 @@ def sos_filter(x, file_offsets, sos, zi, stage_split, state, reset, out_rows=Non
   return y
 
 
+def audio_intensity(x, buf, rows_out, fs_in, fs_out, half_window, square, post, exponent, windows=False,
+                    handle=None):
+  """The windowed means of AudioFeatures.audio_resample over [buf ; f(x)] (td_audio_intensity): float64
+  [rows_out, C].  x [N, C] float32 / float64 device tensor; buf [B, C] float64 (contiguous) or None;
+  f(x) = float32(x)^2 when square; post: sqrt then ** exponent fused into the store.  windows=True also
+  returns the (t1, t2) of every row as a device int64 [rows_out, 2]."""
+  h = handle or default_handle()
+  c = int(x.shape[1])
+  y = h.empty((int(rows_out), c), 'float64')
+  win = h.empty((int(rows_out), 2), 'int64') if windows else None
+  nb = int(buf.shape[0]) if buf is not None else 0
+  is64 = 1 if x.dtype == _torch().float64 else 0
+  h.check(h.lib.td_audio_intensity(h.ptr, _ptr(buf), nb, _ptr(x), is64, x.stride(0), int(x.shape[0]), c,
+                                   1 if square else 0, int(rows_out), float(fs_in), float(fs_out),
+                                   float(half_window), 1 if post else 0, float(exponent), _ptr(y), _ptr(win)))
+  return (y, win) if windows else y
+
+
+def audio_passthrough(x, buf, row_begin, row_end, square, post, exponent, dtype='float64', handle=None):
+  """Rows [row_begin, row_end) of [buf ; f(x)] as `dtype` -- the pass-through of audio_resample and its
+  carried buffer (td_audio_passthrough).  post 0: as they are; 1: sqrt and ** exponent in `dtype`; 2 (float64
+  only): sqrt in float32, ** exponent in float64."""
+  h = handle or default_handle()
+  c = int(x.shape[1])
+  y = h.empty((int(row_end) - int(row_begin), c), dtype)
+  o32, o64 = (y, None) if dtype == 'float32' else (None, y)
+  nb = int(buf.shape[0]) if buf is not None else 0
+  is64 = 1 if x.dtype == _torch().float64 else 0
+  h.check(h.lib.td_audio_passthrough(h.ptr, _ptr(buf), nb, _ptr(x), is64, x.stride(0), int(x.shape[0]), c,
+                                     1 if square else 0, int(row_begin), int(row_end), int(post),
+                                     float(exponent), _ptr(o32), _ptr(o64)))
+  return y
+
+
+def audio_spectrogram(wave, seg, hop, nfft, taps, frames, handle=None):
+  """AudioFeatures.compute_spectrogram of a float32 device wave [n] (td_audio_spectrogram): float64
+  [nfft // 2 + 1, frames]."""
+  h = handle or default_handle()
+  taps_a, taps_p = _lib.f64_array(taps)
+  y = h.empty((int(nfft) // 2 + 1, int(frames)), 'float64')
+  h.check(h.lib.td_audio_spectrogram(h.ptr, _ptr(wave), int(wave.shape[0]), int(seg), int(hop), int(nfft), taps_p,
+                                     int(taps_a.shape[0]), int(frames), _ptr(y)))
+  return y
+
+
 def sos_filter_plan(n_total, n_max, c, handle=None):
   """(chunk, scan levels) that sos_filter uses for files of n_total rows in all, the longest n_max, over c
   channels (td_sos_filter_plan)."""

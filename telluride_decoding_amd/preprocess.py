@@ -11,7 +11,10 @@ Return types follow the reference: a NumPy (or list) input gives a float64 NumPy
 on the GPU stays there: process() returns a device tensor (float32 by default, `device_dtype`), the route
 into the fits without a host round trip.
 
-Differences from the reference:
+AudioFeatures (preprocess.py:589-755): the intensity envelope and the spectrogram of
+audio, on the device (csrc/audio.hip); its quirks and its one difference are in its docstring.
+
+Differences of the Preprocessor from the reference:
   - The caller's array is never written: the reference's reref_data subtracts in place into its input
     when no filter ran before it (preprocess.py:428).
   - A name with parameters, 'eeg(highpass_cutoff=1;highpass_order=2;channel_numbers=0-31)', names the
@@ -567,3 +570,221 @@ class Preprocessor(object):
       return self._back(out, on_dev), [0, int(out.shape[0])]
     out, new_offs = self._run(x, offs, True, dtype)
     return self._back(out, on_dev), new_offs
+
+
+# ------------------------------------------------------------------------------------------------ audio
+# The device kernel's limits on compute_spectrogram (csrc/audio.hip); the reference has none.
+SPECTROGRAM_MAX_SEGMENT = 1024
+SPECTROGRAM_MAX_NFFT = 4096
+SPECTROGRAM_MAX_TAPS = 16
+
+
+def _np_dtype(torch_dtype):
+  return _torch().empty(0, dtype=torch_dtype).numpy().dtype
+
+
+def _torch_dtype(np_dtype):
+  return _torch().from_numpy(np.empty(0, np_dtype)).dtype
+
+
+class AudioFeatures(object):
+  """Drop-in for the reference's preprocess.AudioFeatures (preprocess.py:589-755): the RMS intensity
+  envelope of audio resampled by windowed means (audio_resample, compute_intensity) and an auditory
+  spectrogram (compute_spectrogram), on the MI355X (csrc/audio.hip).
+
+  A NumPy (or list) input returns NumPy in the reference's dtype; a torch tensor on the GPU stays there.
+  The reference's quirks are kept: every call transposes an input with more columns
+  than rows, the carried buffer holds the last int(fs_in * window / (2 fs_out)) rows of [buffer ; data]
+  (all of them when that is 0), each call's window centres restart at t = 0 and stop at its end, an empty
+  window gives NaN, and fs_out >= fs_in with window <= 1 passes the data through.  Means are summed in
+  float64 (the reference's float32 means sit up to ~2.3e-7 from that).
+
+  Difference: compute_spectrogram supports segment_size <= 1024, nfft <= 4096 and up to 16 smoothing taps
+  and raises ValueError beyond them.
+  """
+
+  def __init__(self, name, fs_in, fs_out, window=1, exponent=1, buff=None):
+    """Specifies desired parameters up front."""
+    self.check_params(name, fs_in, fs_out, window)
+    self._name = name
+    self._fs_in = fs_in
+    self._fs_out = fs_out
+    self._window = window
+    self._exponent = exponent
+    self._buff = buff            # the caller's until the first call, then a device float64 tensor
+    self._buff_dtype = None      # the dtype numpy's concatenation would give the buffer
+
+  def check_params(self, name, fs_in, fs_out, window):
+    """Checks correctness of parameters passed as input."""
+    if not isinstance(name, str):
+      raise TypeError('name must be a string, not %s' % name)
+    if fs_in <= 0:
+      raise ValueError('fs_in should not be less than 0.')
+    if fs_out <= 0:
+      raise ValueError('fs_out should not be less than 0.')
+    if window <= 0:
+      raise ValueError('window must be greater than than 0.')
+
+  # ---------------------------------------------------------------- plumbing
+  @staticmethod
+  def _frames(data, square):
+    """(x [N, C] float32 / float64 device tensor, was it a device tensor, the dtype numpy would see):
+    1-D becomes a column, more columns than rows is transposed (preprocess.py:637-646)."""
+    torch = _torch()
+    if _is_device_tensor(data):
+      x = data
+      if square and x.dtype not in (torch.float32, torch.float64):
+        x = x.to(torch.float32)
+      dtype = np.dtype(np.float32) if square else _np_dtype(x.dtype)
+      if x.dim() <= 1:
+        x = x.reshape(-1, 1)
+      elif x.dim() > 2:
+        raise ValueError('audio data must be 1-D or 2-D, not %s' % (tuple(x.shape),))
+      if x.shape[1] > x.shape[0]:
+        x = x.t()
+      if x.dtype not in (torch.float32, torch.float64):
+        x = x.to(torch.float64)
+      return x.contiguous(), True, dtype
+    arr = np.asarray(data)
+    if square:
+      arr = arr.astype(np.float32)
+    if arr.ndim <= 1:
+      arr = np.reshape(arr, (-1, 1))
+    elif arr.ndim > 2:
+      raise ValueError('audio data must be 1-D or 2-D, not %s' % (arr.shape,))
+    if arr.shape[1] > arr.shape[0]:
+      arr = np.transpose(arr)
+    dtype = arr.dtype
+    if dtype not in (np.float32, np.float64):
+      arr = arr.astype(np.float64)
+    h = device.default_handle()
+    return torch.from_numpy(np.ascontiguousarray(arr)).to(h.device), False, dtype
+
+  def _buffer(self, c):
+    """The carried buffer as a device float64 [B, c] tensor (None before any), checked against c channels
+    as np.concatenate would."""
+    if self._buff is None:
+      return None
+    if self._buff_dtype is None:       # the caller's buffer, first use
+      b = self._buff
+      if _is_device_tensor(b):
+        dtype, t = _np_dtype(b.dtype), b.to(_torch().float64)
+      else:
+        arr = np.asarray(b)
+        dtype = arr.dtype
+        t = _torch().from_numpy(np.ascontiguousarray(arr, dtype=np.float64)).to(device.default_handle().device)
+      if t.dim() != 2:
+        raise ValueError('all the input arrays must have same number of dimensions, but the buffer has %d '
+                         'dimension(s) and the data 2' % t.dim())
+      self._buff, self._buff_dtype = t.contiguous(), dtype
+    if int(self._buff.shape[1]) != c:
+      raise ValueError('all the input array dimensions except for the concatenation axis must match exactly, '
+                       'but along dimension 1, the buffer has size %d and the data %d' %
+                       (int(self._buff.shape[1]), c))
+    return self._buff
+
+  @staticmethod
+  def _back(t, on_device, dtype):
+    if on_device:
+      want = _torch_dtype(dtype)
+      return t if t.dtype == want else t.to(want)
+    return t.cpu().numpy().astype(dtype, copy=False)
+
+  def _resample(self, data, square):
+    """audio_resample of data (square=False) or of float32(data)^2 followed by sqrt and ** exponent
+    (square=True, compute_intensity)."""
+    x, on_dev, dtype = self._frames(data, square)
+    n, c = int(x.shape[0]), int(x.shape[1])
+    half_window_size = 0.5 * self._window / self._fs_out
+    buf = self._buffer(c)
+    tau = int(buf.shape[0]) if buf is not None else 0
+    cat_dtype = np.result_type(self._buff_dtype, dtype) if buf is not None else np.dtype(dtype)
+    frames_in = tau + n
+    frames_out = int(round((frames_in - tau) / self._fs_in * self._fs_out))
+    keep = int(self._fs_in * half_window_size)
+    begin = max(0, frames_in - keep) if keep > 0 else 0     # data[-keep:], data[-0:] being all of it
+    h = device.default_handle()
+    windowed = self._fs_out < self._fs_in or self._window > 1
+    post = 1 if square else 0
+    if windowed:
+      out_dtype = np.dtype(np.float64)
+    elif square:                   # numpy's dtypes of (data ** 0.5) ** exponent
+      sq = np.ones(1, cat_dtype) ** 0.5
+      out_dtype = (sq ** self._exponent).dtype
+      post = 2 if (sq.dtype == np.float32 and out_dtype == np.float64) else 1
+    else:
+      out_dtype = cat_dtype
+    if c == 0:                     # (an empty 1-D input, transposed to 1 x 0)
+      out = h.zeros((frames_out if windowed else frames_in, 0), 'float64')
+      new_buff = h.zeros((frames_in - begin, 0), 'float64')
+    else:
+      if windowed:
+        out = device.audio_intensity(x, buf, frames_out, self._fs_in, self._fs_out, half_window_size, square,
+                                     post, self._exponent)
+      else:
+        out = device.audio_passthrough(x, buf, 0, frames_in, square, post, self._exponent,
+                                       'float32' if out_dtype == np.float32 else 'float64')
+      new_buff = device.audio_passthrough(x, buf, begin, frames_in, square, 0, 1.0, 'float64')
+    self._buff, self._buff_dtype = new_buff, cat_dtype
+    return self._back(out, on_dev, out_dtype)
+
+  # ---------------------------------------------------------------- the reference's methods
+  def audio_resample(self, data):
+    """Resamples audio [frames_in, channels] from fs_in to fs_out by (overlapping, window > 1) windowed
+    means (preprocess.py:619-686): float64 [round(frames / fs_in * fs_out), channels], or the buffered rows
+    plus the data unchanged when fs_out >= fs_in and window <= 1."""
+    return self._resample(data, square=False)
+
+  def compute_intensity(self, data):
+    """The RMS intensity (the windowed mean of float32(data)^2, then sqrt) raised to `exponent`
+    (preprocess.py:688-708)."""
+    return self._resample(data, square=True)
+
+  def compute_spectrogram(self, wave, segment_size=128, n_overlap=8, n_trans=4,
+                          smoothing_filter=(.2, 1, .2)):
+    """An auditory spectrogram (preprocess.py:712-755): scipy's STFT of the pre-emphasised wave (Hamming
+    window, nfft = segment_size * n_trans), power smoothed by the causal FIR `smoothing_filter` along
+    frequency then time, fourth root with a 1e-4 x max offset, scaled to 0..255.  Returns (spectrogram
+    [nfft // 2 + 1, frames] float64, the bin frequencies numpy.fft.rfftfreq(nfft, 1.0))."""
+    torch = _torch()
+    on_dev = _is_device_tensor(wave)
+    if on_dev:
+      w = wave.squeeze().to(torch.float32)
+    else:
+      w = np.squeeze(np.asarray(wave)).astype(np.float32)
+    if len(w.shape) != 1:
+      raise ValueError('Wave.shape wrong:' + str(tuple(w.shape)))
+    n = int(w.shape[0])
+    if n == 0:
+      raise ValueError('compute_spectrogram: an empty wave')
+    seg = int(segment_size)
+    if seg < 1:
+      raise ValueError('nperseg must be a positive integer')
+    seg = min(seg, n)              # scipy's _triage_segments: a wave shorter than a segment is one segment
+    nfft = int(segment_size * n_trans)
+    if nfft < seg:
+      raise ValueError('nfft must be greater than or equal to nperseg.')
+    noverlap = int(segment_size - segment_size / n_overlap)
+    if noverlap >= seg:
+      raise ValueError('noverlap must be less than nperseg.')
+    taps = np.asarray(smoothing_filter, np.float64).ravel()
+    if seg > SPECTROGRAM_MAX_SEGMENT:
+      raise ValueError('compute_spectrogram: segment_size %d exceeds the device limit of %d' %
+                       (seg, SPECTROGRAM_MAX_SEGMENT))
+    if nfft > SPECTROGRAM_MAX_NFFT:
+      raise ValueError('compute_spectrogram: nfft = segment_size * n_trans = %d exceeds the device limit of %d' %
+                       (nfft, SPECTROGRAM_MAX_NFFT))
+    if not 1 <= taps.shape[0] <= SPECTROGRAM_MAX_TAPS:
+      raise ValueError('compute_spectrogram: %d smoothing taps, the device limit is 1 to %d' %
+                       (taps.shape[0], SPECTROGRAM_MAX_TAPS))
+    hop = seg - noverlap
+    padded = n + 2 * (seg // 2)
+    padded += (-(padded - seg) % hop) % seg
+    frames = (padded - seg) // hop + 1
+    if on_dev:
+      wd = w.contiguous()
+    else:
+      wd = torch.from_numpy(np.ascontiguousarray(w)).to(device.default_handle().device)
+    spec = device.audio_spectrogram(wd, seg, hop, nfft, taps, frames)
+    f = np.fft.rfftfreq(nfft, 1.0)
+    return (spec if on_dev else spec.cpu().numpy()), f

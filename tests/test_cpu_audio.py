@@ -1,0 +1,207 @@
+"""CPU side of the AudioFeatures drop-in (telluride_decoding_amd.preprocess.AudioFeatures) and of
+telluride_decoding_amd.preprocess_audio: the public surface against the reference's (G18), the host float64
+restatement (tests/host_audio.py) against the reference's outputs, the check_params errors, the window
+indices against the reference's Python-float loop, both stores, and an import without scipy."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from telluride_decoding_amd import preprocess as pp
+from telluride_decoding_amd import preprocess_audio
+from tests import host_audio as ha
+from tests import surface
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CASES = [c[0] for c in ha.INTENSITY_CASES]
+
+
+@pytest.fixture(scope='module')
+def g18(load_golden):
+  return load_golden('g18_audio')
+
+
+def case(name):
+  return next(c for c in ha.INTENSITY_CASES if c[0] == name)
+
+
+def test_surface_matches_reference():
+  with open(os.path.join(HERE, 'golden', 'g18_audio_surface.json')) as f:
+    want = json.load(f)
+  got = surface.module_surface(pp)['AudioFeatures']
+  assert got['bases'] == want['bases']
+  assert sorted(want['members']) == ['__init__', 'audio_resample', 'check_params', 'compute_intensity',
+                                     'compute_spectrogram']
+  for name, rows in want['members'].items():
+    assert got['members'].get(name) == rows, name
+
+
+def near(got, want, rtol):
+  got, want = np.asarray(got), np.asarray(want)
+  assert got.shape == want.shape and got.dtype == want.dtype, (got.shape, want.shape, got.dtype, want.dtype)
+  assert np.array_equal(np.isnan(got), np.isnan(want))
+  ok = ~np.isnan(want)
+  scale = float(np.max(np.abs(want[ok]))) if ok.any() else 1.0
+  return float(np.max(np.abs(got[ok] - want[ok]))) / scale if ok.any() else 0.0
+
+
+@pytest.mark.parametrize('name', CASES)
+def test_host_intensity_against_g18(g18, name):
+  """The restatement (float64 means of float32 squares) reproduces the reference's float32 means, whole and
+  streamed, with the buffer left after every call."""
+  _, fs_in, fs_out, window, exponent, c, _, calls, brows = case(name)
+  x = ha.case_input(g18, name)
+  buff = g18[name + '_buff'] if brows else None
+  h = ha.HostAudioFeatures(fs_in, fs_out, window, exponent, buff)
+  assert near(h.compute_intensity(x), g18[name + '_whole'], 0) <= 2e-6
+  np.testing.assert_array_equal(h.buff, g18[name + '_whole_buff'])
+  h = ha.HostAudioFeatures(fs_in, fs_out, window, exponent, buff)
+  s = 0
+  for i, m in enumerate(calls):
+    piece = x[s:s + m] if c > 1 else x[s:s + m, 0]
+    assert near(h.compute_intensity(piece), g18['%s_call%d' % (name, i)], 0) <= 2e-6
+    np.testing.assert_array_equal(h.buff, g18['%s_buff%d' % (name, i)])
+    s += m
+  h = ha.HostAudioFeatures(fs_in, fs_out, window, exponent)
+  assert near(h.audio_resample(x.astype(np.float64)), g18[name + '_resample'], 0) <= 2e-6
+
+
+def test_host_tone_against_g18(g18):
+  h = ha.HostAudioFeatures(16000, 100, 1, np.log10(2))
+  x, _ = ha.tone_440()
+  np.testing.assert_allclose(ha.checksum(x), g18['tone_xsum'], rtol=1e-12)
+  assert near(h.compute_intensity(x), g18['tone_out'], 0) <= 2e-6
+
+
+@pytest.mark.parametrize('name', [c[0] for c in ha.SPECTROGRAM_CASES])
+def test_host_spectrogram_against_g18(g18, name):
+  kw = json.loads(str(g18['spec_%s_kwargs' % name]))
+  with np.errstate(invalid='ignore', divide='ignore'):
+    s, f = ha.spectrogram(ha.case_wave(g18, name), **kw)
+  assert s.shape == tuple(g18['spec_%s_shape' % name])
+  np.testing.assert_array_equal(g18['spec_%s_cols' % name], ha.golden_columns(s.shape[1]))
+  assert near(s[:, g18['spec_%s_cols' % name]], g18['spec_%s_out' % name], 0) * 255 <= 1e-9
+  np.testing.assert_array_equal(f, g18['spec_%s_f' % name])
+
+
+def test_spectrogram_shape_rules(g18):
+  assert ha.spectrogram_shape(120)[3] == 16 and tuple(g18['spec_short120_shape']) == (257, 16)
+  assert int(g18['spec_short50_raises']) == 1
+  with pytest.raises(ValueError):
+    ha.spectrogram_shape(50)
+  assert ha.spectrogram_shape(16000, 128, 2, 2) == (128, 64, 256, 251)
+
+
+def test_check_params_errors():
+  with pytest.raises(TypeError):
+    pp.AudioFeatures(3, 16000, 100)
+  for args in ((0, 100), (-1, 100), (16000, 0), (16000, -5)):
+    with pytest.raises(ValueError):
+      pp.AudioFeatures('a', *args)
+  for window in (0, -1.5):
+    with pytest.raises(ValueError):
+      pp.AudioFeatures('a', 16000, 100, window=window)
+  p = pp.AudioFeatures('a', 44100, 100, window=2.5, exponent=0.3)
+  assert (p._fs_in, p._fs_out, p._window, p._exponent) == (44100, 100, 2.5, 0.3)
+
+
+WINDOW_SHAPES = [(16000, 100, 1, 0), (44100, 100, 2.5, 551), (48000, 64, 3, 1125), (44100, 64, 1, 344),
+                 (100, 1000, 1.5, 7), (22050, 100, 1, 110), (8000, 63, 1.7, 3), (11025.0, 99.5, 2, 0)]
+
+
+@pytest.mark.parametrize('fs_in,fs_out,window,tau', WINDOW_SHAPES)
+def test_window_indices_vectorised_match_loop(fs_in, fs_out, window, tau):
+  """numpy's rint over float64 arrays gives the reference's Python-float windows exactly (the half-even
+  ties included)."""
+  n = 3 * int(fs_in) + 17
+  rows = int(round(n / fs_in * fs_out))
+  np.testing.assert_array_equal(ha.windows_vec(n + tau, tau, rows, fs_in, fs_out, window),
+                                ha.windows_loop(n + tau, tau, rows, fs_in, fs_out, window))
+
+
+def test_intensity_store_reference_case():
+  """The reference's preprocess_audio_test.test_audio_intensity."""
+  fs = 1000
+  t = np.arange(fs)
+  window_step = 10
+  half_window_width = int(window_step * 1.5)
+  window_width = 2 * half_window_width + 1
+  storage = preprocess_audio.AudioIntensityStore(window_step=window_step, window_width=window_width,
+                                                 pre_context=half_window_width)
+  input_pos = 0
+  output_count = 0
+  data_width = 34
+  while input_pos < len(t):
+    e = min(input_pos + data_width, len(t))
+    storage.add_data(t[input_pos:e])
+    input_pos = e
+    for data in storage.next_window():
+      assert isinstance(data, float)
+      b = -1.5 * window_step + output_count * window_step
+      e = 1.5 * window_step + output_count * window_step + 1
+      expected = np.arange(b, e, dtype=np.int32)
+      if output_count == 0:
+        expected[0:int(half_window_width)] = 0
+      elif output_count == 1:
+        expected[0:int(half_window_width - window_step)] = 0
+      assert data == np.mean(np.square(expected))
+      output_count += 1
+  assert output_count == int((len(t) - half_window_width) / float(window_step) + 1)
+
+
+def test_loudness_mick_store():
+  rng = np.random.default_rng(3)
+  x = rng.standard_normal((257, 2))
+  storage = preprocess_audio.AudioLoudnessMick(window_step=20, window_width=50)
+  got = []
+  for s in range(0, 257, 31):
+    storage.add_data(x[s:s + 31])
+    got += list(storage.next_window())
+  want = [np.mean(np.abs(x[20 * i:20 * i + 50]) ** np.log10(2)) for i in range((257 - 50) // 20 + 1)]
+  assert len(got) == len(want)
+  np.testing.assert_allclose(got, want, rtol=1e-15, atol=0)
+
+
+def test_import_without_scipy():
+  """The audio features need no scipy at run time."""
+  code = ('import sys\n'
+          'class Block(object):\n'
+          '  def find_spec(self, name, path=None, target=None):\n'
+          '    if name == "scipy" or name.startswith("scipy."):\n'
+          '      raise ImportError("scipy is blocked")\n'
+          'sys.meta_path.insert(0, Block())\n'
+          'import telluride_decoding_amd.preprocess as pp\n'
+          'import telluride_decoding_amd.preprocess_audio\n'
+          'pp.AudioFeatures("a", 16000, 100)\n'
+          'assert not any(m == "scipy" or m.startswith("scipy.") for m in sys.modules)\n'
+          'print("ok")\n')
+  r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=300)
+  assert r.returncode == 0 and r.stdout.strip().endswith('ok'), r.stderr
+
+
+def test_spectrogram_errors_before_the_device():
+  """scipy's errors and the device kernel's documented limits, raised before anything runs."""
+  p = pp.AudioFeatures('a', 16000, 100)
+  with pytest.raises(ValueError, match='noverlap'):
+    p.compute_spectrogram(np.ones(50))
+  with pytest.raises(ValueError, match='Wave.shape wrong'):
+    p.compute_spectrogram(np.ones((2, 300)))
+  with pytest.raises(ValueError, match='1024'):
+    p.compute_spectrogram(np.ones(5000), segment_size=2048, n_trans=1)
+  with pytest.raises(ValueError, match='4096'):
+    p.compute_spectrogram(np.ones(5000), segment_size=1024, n_trans=8)
+  with pytest.raises(ValueError, match='16'):
+    p.compute_spectrogram(np.ones(5000), smoothing_filter=np.ones(17))
+
+
+def test_streamed_output_differs_from_whole(g18):
+  """The reference restarts t at 0 on every call and no window looks past its call's end: a streamed
+  envelope is not the whole-file one (the drop-in keeps that)."""
+  whole = g18['i44_whole']
+  streamed = np.concatenate([g18['i44_call0'], g18['i44_call1']])
+  assert whole.shape == streamed.shape
+  assert np.max(np.abs(whole - streamed)) > 1e-3 * np.max(whole)   # (0.0094 here; float error is ~1e-7)
