@@ -2,6 +2,8 @@
 against G18 and the GPU tests: the intensity with its buffer, window indices and quirks (squares in
 float32, means in float64), and the spectrogram as scipy's STFT recipe written out with numpy.fft.
 Test infrastructure."""
+import math
+
 import numpy as np
 
 # (name, fs_in, fs_out, window, exponent, channels, frames, streamed call lengths, user buffer rows)
@@ -26,6 +28,64 @@ SPECTROGRAM_CASES = (
 # G18 keeps every COLUMN_STEP-th frame of a spectrogram wider than this many frames (the golden stays small)
 GOLDEN_MAX_FRAMES, COLUMN_STEP = 64, 5
 SPECTROGRAM_RAISES = (('short50', 50),)
+
+
+def _sweep_taps(n):
+  return tuple(0.1 + 0.9 * ((7 * j) % 11) / 10.0 for j in range(n))
+
+
+# The spectrogram kernels' tile edges, for the GPU sweep and the scipy cross-check of `spectrogram`:
+# (name, samples, segment_size, n_overlap, n_trans, smoothing_filter); None: the reference's default filter.
+# The DFT runs 64 frames per workgroup, 16 bins per wave, 4 waves per workgroup and 64-sample LDS stages; the
+# FIR 16 x 64 tiles with a (taps - 1) halo.  Comments: (seg, hop, nfft, bins, frames).
+SPECTROGRAM_SWEEP = (
+    ('seg1', 65, 1, 4, 2, None),                    # (1, 1, 2, 2, 65)
+    ('seg2', 64, 2, 4, 2, None),                    # (2, 1, 4, 3, 65)
+    ('seg63', 1010, 63, 4, 2, None),                # (63, 16, 126, 64, 65): all four waves of one group
+    ('seg64', 1009, 64, 4, 2, None),                # (64, 16, 128, 65, 65)
+    ('seg65', 1073, 65, 4, 2, None),                # (65, 17, 130, 66, 65)
+    ('seg127', 2018, 127, 4, 2, None),              # (127, 32, 254, 128, 65)
+    ('seg129', 2081, 129, 4, 2, None),              # (129, 33, 258, 130, 65)
+    ('seg1023', 16130, 1023, 4, 2, None),           # (1023, 256, 2046, 1024, 65)
+    ('frames2', 2, 2, 1, 2, None),                  # (2, 2, 4, 3, 2): no wave gives one frame (1 sample raises)
+    ('frames63', 977, 64, 4, 2, None),              # (64, 16, 128, 65, 63)
+    ('frames64', 993, 64, 4, 2, None),              # (64, 16, 128, 65, 64)
+    ('frames129', 2033, 64, 4, 2, None),            # (64, 16, 128, 65, 129)
+    ('seg1_frames129', 129, 1, 1, 3, None),         # (1, 1, 3, 2, 129)
+    ('bins5', 500, 8, 2, 1, None),                  # (8, 4, 8, 5, 126)
+    ('bins16', 600, 15, 3, 2, None),                # (15, 5, 30, 16, 121)
+    ('bins17', 600, 16, 4, 2, None),                # (16, 4, 32, 17, 151)
+    ('bins32', 700, 31, 2, 2, None),                # (31, 16, 62, 32, 45)
+    ('bins33', 700, 32, 2, 2, None),                # (32, 16, 64, 33, 45)
+    ('bins256', 3000, 255, 4, 2, None),             # (255, 64, 510, 256, 48)
+    ('hop1_s64', 300, 64, 64, 2, None),             # (64, 1, 128, 65, 301)
+    ('hop1_s37', 200, 37, 37, 3, None),             # (37, 1, 111, 56, 200)
+    ('hopseg_s1', 100, 1, 1, 2, None),              # (1, 1, 2, 2, 100)
+    ('hopseg_s64', 3000, 64, 1, 2, None),           # (64, 64, 128, 65, 48)
+    ('hopseg_s100', 3000, 100, 1, 3, None),         # (100, 100, 300, 151, 31)
+    ('ntrans1_s128', 2000, 128, 8, 1, None),        # (128, 16, 128, 65, 126): nfft == seg
+    ('ntrans1_s129', 2081, 129, 4, 1, None),        # (129, 33, 129, 65, 65): odd nfft == seg
+    ('ntrans3_s64', 1009, 64, 4, 3, None),          # (64, 16, 192, 97, 65)
+    ('ntrans3_s65', 1073, 65, 4, 3, None),          # (65, 17, 195, 98, 65): odd nfft
+    ('ntrans4_s33', 800, 33, 2, 4, None),           # (33, 17, 132, 67, 48)
+    ('ntrans3_s1023', 9000, 1023, 2, 3, (1,)),      # (1023, 512, 3069, 1535, 19): odd nfft, 24 k groups
+    ('s1024_nfft4096_hop1', 1500, 1024, 1024, 4, None),   # (1024, 1, 4096, 2049, 1501)
+    ('short70', 70, 128, 2, 2, None),               # (70, 6, 256, 129, 13): seg shrunk to the wave
+    ('short127', 127, 128, 2, 2, None),             # (127, 63, 256, 129, 3)
+    ('short1000', 1000, 1024, 2, 4, None),          # (1000, 488, 4096, 2049, 4)
+    ('negtaps', 1009, 64, 4, 2, (1, -2, .5)),       # (64, 16, 128, 65, 65): negative power, NaN everywhere
+    ('negtaps_one', 1009, 64, 4, 2, (-1,)),
+    ('negtaps_mild', 1009, 64, 4, 2, (1, -0.02)),   # some cells below -off: NaN everywhere too
+) + tuple(('taps%d' % n, 2033, 64, 4, 2, _sweep_taps(n)) for n in range(1, 17))   # (64, 16, 128, 65, 129)
+
+
+def sweep_case(name):
+  """(wave, kwargs of compute_spectrogram) of SPECTROGRAM_SWEEP's case `name`."""
+  _, samples, seg, n_overlap, n_trans, taps = next(c for c in SPECTROGRAM_SWEEP if c[0] == name)
+  kw = dict(segment_size=seg, n_overlap=n_overlap, n_trans=n_trans)
+  if taps is not None:
+    kw['smoothing_filter'] = taps
+  return spectrogram_input(name, samples), kw
 
 
 def gaussian(m, std):
@@ -77,12 +137,43 @@ def window_means(data, windows):
   return out
 
 
+def window_means_exact(data, windows):
+  """Row i: the mean of data[t1_i:t2_i] with the window's sum exact, rounded once (NaN when empty).
+  Integer-valued data (float32 squares of integers are) take int64 prefix sums; other data math.fsum per
+  window and channel, on shapes small enough to afford it.  A window holding an inf or a NaN takes numpy's
+  sum, which is then exact too (inf, -inf or NaN)."""
+  data = np.asarray(data, np.float64)
+  windows = np.asarray(windows, np.int64)
+  n, c = data.shape
+  out = np.full((windows.shape[0], c), np.nan)
+  full = windows[:, 1] > windows[:, 0]
+  t1, t2 = windows[full, 0], windows[full, 1]
+  finite = np.isfinite(data)
+  if finite.all() and np.array_equal(data, np.round(data)) and (
+      n == 0 or float(np.max(np.abs(data), initial=0.0)) * (n + 1) < 2.0 ** 62):
+    cs = np.zeros((n + 1, c), np.int64)
+    np.cumsum(data.astype(np.int64), axis=0, out=cs[1:])
+    out[full] = (cs[t2] - cs[t1]).astype(np.float64) / (t2 - t1)[:, None]
+    return out
+  bad = np.zeros((n + 1, c), np.int64)
+  np.cumsum(~finite, axis=0, out=bad[1:])
+  for i, a, b in zip(np.flatnonzero(full), t1, t2):
+    for j in range(c):
+      col = data[a:b, j]
+      s = math.fsum(col) if bad[b, j] == bad[a, j] else float(np.sum(col))
+      out[i, j] = s / (b - a)
+  return out
+
+
 class HostAudioFeatures(object):
   """compute_intensity / audio_resample with the reference's buffer, in float64."""
 
-  def __init__(self, fs_in, fs_out, window=1, exponent=1, buff=None):
+  def __init__(self, fs_in, fs_out, window=1, exponent=1, buff=None, exact=False):
+    """exact: window sums exact (window_means_exact) rather than summed row after row (window_means)."""
     self.fs_in, self.fs_out, self.window, self.exponent = fs_in, fs_out, window, exponent
     self.buff = None if buff is None else np.asarray(buff)
+    self.means = window_means_exact if exact else window_means
+    self.windows = None           # the last windowed call's (t1, t2) rows
 
   def _resample(self, data, square):
     data = np.asarray(data)
@@ -105,7 +196,9 @@ class HostAudioFeatures(object):
     rows = int(round((frames_in - tau) / self.fs_in * self.fs_out))
     if not (self.fs_out < self.fs_in or self.window > 1):
       return (data ** 0.5) ** self.exponent if square else data
-    out = window_means(data, windows_loop(frames_in, tau, rows, self.fs_in, self.fs_out, self.window))
+    bounds = windows_vec if self.means is window_means_exact else windows_loop   # (equal: a CPU test)
+    self.windows = bounds(frames_in, tau, rows, self.fs_in, self.fs_out, self.window)
+    out = self.means(data, self.windows)
     return np.sqrt(out) ** self.exponent if square else out
 
   def audio_resample(self, data):

@@ -1,8 +1,10 @@
 """CPU side of the AudioFeatures drop-in (telluride_decoding_amd.preprocess.AudioFeatures) and of
 telluride_decoding_amd.preprocess_audio: the public surface against the reference's (G18), the host float64
 restatement (tests/host_audio.py) against the reference's outputs, the check_params errors, the window
-indices against the reference's Python-float loop, both stores, and an import without scipy."""
+indices against the reference's Python-float loop, both stores, and an import without scipy; and the GPU sweep's
+references: the spectrogram restatement against scipy on every shape of its grid, the exact window means."""
 import json
+import math
 import os
 import subprocess
 import sys
@@ -205,3 +207,114 @@ def test_streamed_output_differs_from_whole(g18):
   streamed = np.concatenate([g18['i44_call0'], g18['i44_call1']])
   assert whole.shape == streamed.shape
   assert np.max(np.abs(whole - streamed)) > 1e-3 * np.max(whole)   # (0.0094 here; float error is ~1e-7)
+
+
+# ------------------------------------------------------------------------------------------------ the sweep's
+# references, checked here so that the GPU sweep (tests/test_gpu_audio_sweep.py) compares the kernels with
+# checked restatements
+def scipy_spectrogram(wave, segment_size=128, n_overlap=8, n_trans=4, smoothing_filter=(.2, 1, .2)):
+  """The reference's recipe built from scipy: lfilter pre-emphasis, scipy.signal.stft with a Hamming window."""
+  import warnings
+  from scipy import signal
+  w = np.squeeze(wave).astype(np.float32)
+  pe = signal.lfilter([1, -0.95], [1], w)
+  with warnings.catch_warnings():
+    warnings.simplefilter('ignore')      # nperseg longer than the wave: scipy shortens it and warns
+    f, _, z = signal.stft(pe, fs=1.0, window='hamming', nperseg=segment_size,
+                          noverlap=segment_size - (segment_size / n_overlap), nfft=segment_size * n_trans,
+                          return_onesided=True)
+  p = np.real(z * np.conj(z))
+  p = signal.lfilter(smoothing_filter, [1], p, axis=0)
+  p = signal.lfilter(smoothing_filter, [1], p, axis=1)
+  with np.errstate(invalid='ignore', divide='ignore'):
+    off = 0.0001 * np.max(p)
+    s = (off + p) ** 0.25 - off ** 0.25
+    return 255 / np.max(s) * s, f
+
+
+@pytest.mark.parametrize('name', [c[0] for c in ha.SPECTROGRAM_SWEEP])
+def test_host_spectrogram_against_scipy(name):
+  pytest.importorskip('scipy.signal')
+  wave, kw = ha.sweep_case(name)
+  with np.errstate(invalid='ignore', divide='ignore'):
+    s, f = ha.spectrogram(wave, **kw)
+  want, want_f = scipy_spectrogram(wave, **kw)
+  assert s.shape == want.shape
+  np.testing.assert_allclose(f, want_f, rtol=0, atol=1e-15)
+  assert near(s, want, 0) * 255 <= 1e-9
+  if name.startswith('negtaps') and name != 'negtaps_one':     # (-1,) twice is the power again
+    assert np.isnan(s).all()
+
+
+def test_host_spectrogram_sweep_shapes():
+  """The grid reaches the edges it claims: one-wave and four-wave bin groups, 16 m and 16 m + 1 bins, 63 to 65
+  and 129 frames, hop 1 and hop = segment, nfft == segment, odd nfft, 1 to 16 taps, a shrunk segment."""
+  shapes = {}
+  for name, samples, seg, n_overlap, n_trans, taps in ha.SPECTROGRAM_SWEEP:
+    shapes[name] = ha.spectrogram_shape(samples, seg, n_overlap, n_trans) + (len(taps or (0, 0, 0)),)
+  bins = {v[2] // 2 + 1 for v in shapes.values()}
+  frames = {v[3] for v in shapes.values()}
+  segs = {v[0] for v in shapes.values()}
+  assert {1, 2, 63, 64, 65, 127, 129, 1023, 1024} <= segs
+  assert {2, 63, 64, 65, 129} <= frames
+  assert min(bins) < 16 and {16, 17, 32, 33, 64, 128, 256} <= bins
+  assert any(v[1] == 1 for v in shapes.values()) and any(v[1] == v[0] > 1 for v in shapes.values())
+  assert any(v[2] == v[0] for v in shapes.values()) and any(v[2] % 2 for v in shapes.values())
+  assert set(range(1, 17)) <= {v[4] for v in shapes.values()}
+  assert shapes['s1024_nfft4096_hop1'][:3] == (1024, 1, 4096)
+  assert shapes['short70'][0] == 70 and shapes['short1000'][0] == 1000
+  with pytest.raises(ValueError, match='Wave.shape wrong'):   # one sample squeezes to a 0-d wave
+    pp.AudioFeatures('a', 16000, 100).compute_spectrogram(np.ones(1), segment_size=1, n_overlap=1)
+
+
+def test_window_means_exact_against_window_means():
+  """On short windows the row-by-row sum is within a few ulps (of the largest mean) of the exact one; integer-valued data (int64
+  prefix sums) and math.fsum give the same exactly rounded sums; NaN and inf windows as numpy's sum."""
+  rng = np.random.default_rng(12)
+  for c in (1, 2, 3, 4, 8):
+    windows = ha.windows_loop(1300, 0, 140, 1000, 110, 1.37)
+    for data in (rng.standard_normal((1300, c)).astype(np.float32) ** 2,
+                 rng.standard_normal((1300, c)) * 1e3,
+                 rng.integers(-32768, 32768, size=(1300, c)).astype(np.float64)):
+      exact = ha.window_means_exact(data, windows)
+      assert near(exact, ha.window_means(data, windows), 0) <= 1e-14
+      for i in range(0, 140, 7):
+        t1, t2 = windows[i]
+        for j in range(c):
+          if t2 > t1:
+            assert exact[i, j] == math.fsum(data[t1:t2, j].astype(np.float64)) / (t2 - t1)
+          else:
+            assert np.isnan(exact[i, j])
+  x = np.arange(40, dtype=np.float64)[:, None] * np.ones((1, 2))
+  x[5, 0], x[17, 1], x[18, 1], x[30, 0] = np.nan, np.inf, -np.inf, np.inf
+  windows = np.array([[0, 10], [10, 20], [25, 35], [35, 40], [3, 3]])
+  with np.errstate(invalid='ignore'):       # inf - inf
+    got, want = ha.window_means_exact(x, windows), ha.window_means(x, windows)
+  np.testing.assert_array_equal(got, want)
+
+
+def test_window_means_exact_long_windows():
+  """2.5 s windows at 44.1 kHz (110 250 rows): the int64 prefix sums equal math.fsum, where the row-by-row
+  float64 sum need not."""
+  rng = np.random.default_rng(13)
+  x = rng.integers(-32768, 32768, size=(220500, 2)).astype(np.float32) ** 2
+  windows = ha.windows_loop(220500, 0, 10, 44100, 2, 5)
+  got = ha.window_means_exact(x, windows)
+  for i in (0, 3, 9):
+    t1, t2 = windows[i]
+    for j in range(2):
+      assert got[i, j] == math.fsum(x[t1:t2, j].astype(np.float64)) / (t2 - t1)
+
+
+def test_host_exact_intensity_matches_g18_restatement(g18):
+  """The exact host path (exact=True) keeps the G18 outputs and buffers of the row-by-row one."""
+  for name in CASES:
+    _, fs_in, fs_out, window, exponent, c, _, calls, brows = case(name)
+    x = ha.case_input(g18, name)
+    buff = g18[name + '_buff'] if brows else None
+    a = ha.HostAudioFeatures(fs_in, fs_out, window, exponent, buff)
+    b = ha.HostAudioFeatures(fs_in, fs_out, window, exponent, buff, exact=True)
+    got = b.compute_intensity(x)
+    assert near(got, a.compute_intensity(x), 0) <= 1e-13
+    np.testing.assert_array_equal(b.buff, a.buff)
+    assert near(got, g18[name + '_whole'], 0) <= 2e-6

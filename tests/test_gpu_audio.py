@@ -159,10 +159,21 @@ def test_intensity_quirks(pp, torch):
   r1 = pp.AudioFeatures('q', 16000, 100).compute_intensity(x.T.copy())
   r2 = pp.AudioFeatures('q', 16000, 100).compute_intensity(x)
   np.testing.assert_array_equal(r1, r2)
-  # non-contiguous channel layouts and three channels take the general kernel
+  # three contiguous channels take the lane-per-channel kernel
   y = rng.standard_normal((3000, 3)).astype(np.float32)
   got = pp.AudioFeatures('q', 16000, 100, window=2).compute_intensity(torch.from_numpy(y).cuda())
   want = ha.HostAudioFeatures(16000, 100, 2).compute_intensity(y)
+  assert dist(got.cpu().numpy(), want) <= 1e-12
+  # so does a non-contiguous layout, a channel slice of a wider tensor, through device.audio_intensity with its
+  # row stride (AudioFeatures copies such a slice first); the columns around it are NaN
+  from telluride_decoding_amd import device
+  wide = np.full((3000, 5), np.nan, np.float32)
+  wide[:, 1:4] = y
+  view = torch.from_numpy(wide).cuda()[:, 1:4]
+  assert not view.is_contiguous() and view.stride() == (5, 1)
+  got = device.audio_intensity(view, None, want.shape[0], 16000, 100, 0.5 * 2 / 100, True, True, 1)
+  assert dist(got.cpu().numpy(), want) <= 1e-12
+  got = pp.AudioFeatures('q', 16000, 100, window=2).compute_intensity(view)
   assert dist(got.cpu().numpy(), want) <= 1e-12
   # the pass-through in numpy's dtypes: a float64 exponent promotes the float32 square root, a Python float not
   z = rng.standard_normal((500, 1)).astype(np.float32)
