@@ -1,6 +1,6 @@
 """Benchmark of the linear auditory-attention-decoding hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 One "step" = one complete ridge TRF fit of BASELINE.json's config[1] ("C2"): lagged-covariance
 accumulate (64 ch x 32 lags, never materialising the lag matrix) -> [N > 1: one RCCL all-reduce
@@ -14,15 +14,22 @@ are resident in HBM before the timed region.
                    solved by rank i mod N); `value` is 1e6 x fits / time.  The JSON also
                    carries the accumulate-only time per rank (north_star's strong-scaling
                    target is on the covariance accumulate).
-At N > 1 the default (weak) run appends a short strong-scaling leg after the timed region
+At N > 1 a --full (weak) run appends a short strong-scaling leg after the timed region
 (`"strong": {...}`), so one driver run per N measures both.
+
+A plain run does only what the headline needs: set-up, spin-up and warm-up, the K timed steps,
+--dump-outputs, and the JSON line (headline, configuration, and the roofline of the timed steps'
+own launches).  Everything else it can measure or check -- the CPU baseline, the other
+accumulate precisions, the serial and single-fit figures, the strong-scaling legs and bounds, the
+C3 / C4 / C5 legs, the off-headline shapes -- runs after the timed region only with --full, which
+changes nothing before or inside it.
 
 Consecutive fits are independent (the reference refits from scratch per fold / lambda /
 subject), so by default they are software-pipelined on two HIP streams
 (pipeline.FitPipeline): the latency-bound solve of fit i runs underneath the
 throughput-bound accumulate of fit i + 1.  All K fits, solves included, complete inside the
-timed region.  --serial runs them back to back on one stream; the serial figure is also
-measured after the timed region and reported as `serial_ms_per_step`.
+timed region.  --serial runs them back to back on one stream; with --full the serial figure is
+also measured after the timed region and reported as `serial_ms_per_step`.
 
 --dump-outputs DIR writes the W and b of the last timed fit as DIR/w.npy and DIR/b.npy (the
 inputs are seeded: two builds run with the same arguments can be compared output for output).
@@ -38,6 +45,7 @@ The JSON line also carries
   roofline      the dominant kernel (lagcov MFMA accumulate) timed live with hipEvents on the
                 stream it runs on (td_profile_*); `traffic` is the HBM bytes per launch from
                 this round's rocprofv3 PMC pass (profiles/, `traffic_source` says which),
+and with --full
   cpu_baseline  the NumPy restatement of the reference algorithm (oracle/) timed on this host
                 on a bounded slice of the same workload (rank 0, N = 1): all cores, one thread
                 and the best of a thread sweep, with the BLAS the host runs,
@@ -47,7 +55,11 @@ The JSON line also carries
   cca, loso     configs C3 (CCA fit = accumulate + device solve, and transform; also at the
                 codelab's shape K1 = 2553, with context on both views, and a forward model on
                 the same recording) and C5 (LOSO x lambda sweep on one GPU)
-                (N = 1; --no-extra skips them).
+                (N = 1; --no-extra skips them),
+  f32_mode, bf16x3_mode, serial_ms_per_step, single_fit, accumulate_only_ms_per_step,
+  roofline_whole_chip, roofline.pipe_sustained, strong_share_bound_one_gpu, shapes, and at
+  N > 1 strong, strong_8e6, loso and decode.
+--no-cpu, --no-decode, --no-extra and --no-shapes leave legs out of a --full run.
 """
 import argparse
 import gc
@@ -1071,9 +1083,14 @@ def main():
   ap.add_argument('--strong-samples', type=int, default=FILES_PER_GPU * FRAMES_PER_FILE,
                   help='samples of the ONE job a strong-scaling run shares (default 1e6 = C2; SURVEY 8e: "state '
                        'N" -- at 8e6 a rank\'s 1/8 share is a whole C2 job and the fixed costs amortise)')
-  ap.add_argument('--no-decode', action='store_true', help='skip the informational decode leg')
-  ap.add_argument('--no-cpu', action='store_true', help='skip the CPU baseline')
-  ap.add_argument('--no-extra', action='store_true', help='skip the C3 / C5 legs')
+  ap.add_argument('--full', action='store_true',
+                  help='after the timed region, also run every other measurement and check of this file: the '
+                       'CPU baseline, the f32 / bf16x3 accumulate modes, the serial, accumulate-only and '
+                       'single-fit figures, the whole-chip roofline, the strong-scaling legs and bounds, the C3 / C4 / C5 and shapes '
+                       'legs (without it a run stops after the headline)')
+  ap.add_argument('--no-decode', action='store_true', help='--full: skip the informational decode leg')
+  ap.add_argument('--no-cpu', action='store_true', help='--full: skip the CPU baseline')
+  ap.add_argument('--no-extra', action='store_true', help='--full: skip the C3 / C5 legs')
   ap.add_argument('--targets-on-solve', action='store_true',
                   help='run the y^T x part of the accumulate on the solve streams (the round-2 '
                        'arrangement; the accumulate then measures its channel maxima in a pass of its own)')
@@ -1099,7 +1116,7 @@ def main():
   ap.add_argument('--launch-timeout', type=int, default=3000,
                   help='self-launched ranks (--gpus N without WORLD_SIZE): the launcher ends them all after '
                        'this many seconds and prints every rank\'s last progress mark')
-  ap.add_argument('--no-shapes', action='store_true', help='skip the off-headline shapes leg (N = 1)')
+  ap.add_argument('--no-shapes', action='store_true', help='--full: skip the off-headline shapes leg (N = 1)')
   ap.add_argument('--dry-launch', action='store_true',
                   help='launch the ranks, rendezvous (gloo, CPU) and print the line without any '
                        'compute: checks the multi-rank plumbing where there is no GPU')
@@ -1325,7 +1342,7 @@ def main():
         'launcher': os.environ.get('TD_BENCH_LAUNCHER',
                                    'torch.distributed.run' if world > 1 else 'direct'),
         'ms_per_step': elapsed / args.steps * 1e3, 'higher_is_better': True,
-        'scaling': args.scaling, 'vs_baseline': None,
+        'scaling': args.scaling, 'vs_baseline': None, 'full': args.full,
         'dtype': 'f32 (every product as 3 float16 products of a 2-piece split on the f16 MFMA, f32 '
                  'accumulate, f64 slab sums; f64 solve)',
         'data': 'synthetic',
@@ -1377,9 +1394,10 @@ def main():
         line['roofline']['frac_of_its_cus_peak'] = line['roofline']['frac'] / share
 
   # ---------------------------------------------------------------- after the timed region
+  # (only with --full: a plain run ends with the headline)
   del pipe, run
   torch.cuda.synchronize()
-  if not args.serial:
+  if args.full and not args.serial:
     # the same fits back to back on one stream, and the dominant kernel alone on the whole chip
     run_s, _, _ = make_runner(shard, reduce_fn, solves, True)
     h.profile_enable(True)
@@ -1417,11 +1435,12 @@ def main():
     e_a, _ = time_region(run_a, steps, 2)
     return e_a / steps * 1e3
 
-  acc_ms = accumulate_only(shard)
-  if rank == 0:
-    line['accumulate_only_ms_per_step'] = acc_ms
+  if args.full:
+    acc_ms = accumulate_only(shard)
+    if rank == 0:
+      line['accumulate_only_ms_per_step'] = acc_ms
 
-  if world == 1 and args.scaling == 'weak':
+  if args.full and world == 1 and args.scaling == 'weak':
     # ONE fit with nothing else in flight: accumulate -> solve -> weights on the host's side of a
     # synchronise (what a caller of BrainModelLinearRegression.fit waits for, minus the Python class
     # layer).  The pipelined `value` needs >= 3 independent fits in flight; this is the other end.
@@ -1472,7 +1491,7 @@ def main():
   if rank == 0:
     line['collective'] = (dict(distributed.LAST_COLLECTIVE) if distributed.LAST_COLLECTIVE else
                           {'route': 'none (one rank, no exchange)', 'ranks': 1})
-  if world == 1 and args.scaling == 'weak' and not args.no_extra:
+  if args.full and world == 1 and args.scaling == 'weak' and not args.no_extra:
     # What ONE GPU can say about strong scaling (no multi-GPU node was ever available to this
     # build): the accumulate call of rank 0's 1/8 share of the job against the whole job -- the
     # bound on the 8-GPU speed-up of the accumulate before the collective -- at 1e6 samples (C2) and
@@ -1520,7 +1539,7 @@ def main():
       bound['allreduce_one_rank_ms'] = None
       bound['allreduce_error'] = str(e)
     line['strong_share_bound_one_gpu'] = bound
-  if world > 1 and args.scaling == 'weak':
+  if args.full and world > 1 and args.scaling == 'weak':
     # informational strong-scaling leg: the ONE-GPU job cut into N time ranges
     _, shard2, reduce2, solves2, _ = strong_setup()
     run2, _, pipe2 = make_runner(shard2, reduce2, solves2, False)
@@ -1556,7 +1575,7 @@ def main():
                     '0.10 ideal (fixed launches) and the one-GPU bound is below 6 once the all-reduce is added' % n3),
       }
 
-  if world > 1 and args.scaling == 'weak' and not args.no_extra:
+  if args.full and world > 1 and args.scaling == 'weak' and not args.no_extra:
     # BASELINE configs C5 and C4 over the N ranks (C5 is DEFINED as sharded over the GPUs of a node;
     # the decode half of the metric is windows/s at 1 -> 8 GPUs)
     leg = loso_multi_leg(rank, world, dist, h, barrier)
@@ -1566,7 +1585,7 @@ def main():
       leg = decode_multi_leg(rank, world, dist, h, device, barrier)
       if rank == 0:
         line['decode'] = leg
-  if rank == 0:
+  if args.full and rank == 0:
     eeg, env = host_data
     if world == 1 and not args.no_cpu:
       progress('cpu baseline')

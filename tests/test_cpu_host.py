@@ -386,6 +386,17 @@ def test_bench_never_runs_fewer_ranks_than_asked():
   assert res.returncode != 0 and 'WORLD_SIZE=4' in (res.stderr + res.stdout)
 
 
+def test_bench_full_is_an_option_of_its_own():
+  """A plain run stops after the headline; everything else the file measures runs behind --full, and
+  the --no-* switches narrow that full run."""
+  res = _bench(['--help'])
+  assert res.returncode == 0, res.stderr[-2000:]
+  text = ' '.join(res.stdout.split())
+  assert '--full' in text
+  for flag in ('--no-decode', '--no-cpu', '--no-extra', '--no-shapes'):
+    assert flag + ' --full: skip' in text, flag
+
+
 def test_bench_watchdog_turns_a_hung_collective_into_a_diagnosis():
   """first contact with a multi-GPU node must be diagnosable.  A rank that never
   reaches a collective (here: sleeps in front of the final barrier of the dry launch) leaves the

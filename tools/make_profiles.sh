@@ -8,10 +8,10 @@ out=gpurun_out/profiles_$tag
 mkdir -p $out
 export TMPDIR=/tmp
 # 1. the bench command itself (pipelined, the default) and its serial variant
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -o t -- python3 bench.py --steps 20 --warmup 3 --no-extra > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -o t -- python3 bench.py --steps 20 --warmup 3 --full --no-extra > $out/bench.log 2>&1
 python3 tools/prof_summary.py $out/bench > $out/${tag}_bench_kernel_stats.txt
 cp $(ls $out/bench/*/t_kernel_stats.csv $out/bench/t_kernel_stats.csv 2>/dev/null | head -1) $out/${tag}_bench_rocprofv3_kernel_stats.csv
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/serial -o t -- python3 bench.py --steps 20 --warmup 3 --serial --no-cpu --no-extra > $out/serial.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/serial -o t -- python3 bench.py --steps 20 --warmup 3 --serial --full --no-cpu --no-extra > $out/serial.log 2>&1
 python3 tools/prof_summary.py $out/serial > $out/${tag}_bench_serial_kernel_stats.txt
 # 2. the hot kernels alone, whole chip: trace, then PMC in separate passes
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/hot -o t -- python3 tools/prof_kernels.py > $out/hot.log 2>&1
@@ -27,6 +27,6 @@ done
 # 3. (the bench line of an un-profiled run is taken AFTERWARDS, once profiles/<tag>_lagcov_pmc.json
 #    has been rebuilt from the PMC passes above -- bench.py reads its `traffic` from there:
 #      cp gpurun_out/profiles_<tag>/<tag>_* profiles/ ; python tools/make_pmc_json.py <tag>
-#      gpurun -- 'python bench.py > gpurun_out/bench_line.json' ; cp ... profiles/<tag>_bench_line.json)
+#      python bench.py --full > <tag>_bench_line.json on the GPU box, then copy it to profiles/)
 rm -rf $out/bench $out/serial $out/hot $out/pmc0 $out/pmc1 $out/pmc2
 ls -la $out

@@ -1,7 +1,7 @@
 #!/bin/bash
 # CU partition sweep of the pipelined fit:  tools/sweep_cus.sh 32 64 96
 for cus in "$@"; do
-  python bench.py --steps 100 --no-cpu --no-extra --no-decode --solve-cus $cus --solve-streams ${STREAMS:-2} 2>/dev/null | tail -1 > /tmp/sweep_$cus.json
+  python bench.py --steps 100 --full --no-cpu --no-extra --no-decode --solve-cus $cus --solve-streams ${STREAMS:-2} 2>/dev/null | tail -1 > /tmp/sweep_$cus.json
   python - $cus <<'PY'
 import json, sys
 d = json.loads(open('/tmp/sweep_%s.json' % sys.argv[1]).read())
