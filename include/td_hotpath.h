@@ -662,6 +662,50 @@ int td_audio_passthrough(td_handle* h, const double* buf_dev, int64_t buf_rows, 
 int td_audio_spectrogram(td_handle* h, const float* wave_dev, int64_t n, int seg, int hop, int nfft,
                          const double* taps_host, int num_taps, int64_t frames, double* out_dev);
 
+/* ------------------------------------------------------------------ fully connected regressor
+ * brain_model.BrainModelDNN (reference brain_model.py:486-549): Dense layers z = a.W + b in float32, ReLU on
+ * the num_hidden hidden layers (hidden_host[i] units each), a linear output layer of d units.  The input is
+ * the lagged view of x exactly as td_predict_fir reads it (column l*C + c = x~[t + l - pre, c], zero outside
+ * the file, input_offset, file_offsets_host) -- never materialised.
+ * Parameters: ONE packed float32 buffer in Keras order [W1 (K x h1, row-major, rows in the lag layout), b1,
+ * W2, b2, ..., WL, bL], K = c (pre + 1 + post).
+ * Limits (TD_ERR_INVALID before anything is queued): c <= 128 (context-free input, pre = post = 0: any c with
+ * K <= 8192), pre + 1 + post <= 64, K <= 8192, num_hidden <= 4, 1 <= hidden units <= 64, 1 <= d <= 8,
+ * 1 <= batch_rows <= 2048.
+ *
+ * td_mlp_train: `epochs` epochs of minibatch RMSprop (Keras, momentum 0: v = rho v + (1 - rho) g^2,
+ * w -= lr g / (sqrt(v) + eps)) on the loss mean((p - y)^2) over rows x outputs, every layer updated after the
+ * full backward pass.  The stream is the files' zipped rows, rows_used_host[f] of file f (NULL = all; the
+ * caller's drop_remainder), cut into minibatches of batch_rows (a shorter last one allowed).  shuffle_seed < 0:
+ * minibatch s of every epoch is stream rows [s B, (s + 1) B); >= 0: slot i of epoch e is stream row
+ * perm(i), a bijection of [0, n): 4 Feistel rounds on 2 x half bits (the smallest even bit count with
+ * 2^bits >= n), round key r = mix(lo ^ mix(hi ^ mix(4 e + r))) of the seed's 32-bit halves, round
+ * (L, R) -> (R, L ^ (mix(R ^ key) & mask)), mix = the 32-bit finaliser x ^= x >> 16, x *= 0x7feb352d,
+ * x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16, re-applied while the value is >= n (cycle walking).
+ * params_dev / state_dev (the RMSprop accumulators, same layout; zeros for a fresh optimizer) are read and,
+ * once every launch has been queued, overwritten; a failure leaves them unchanged.  stats_dev
+ * [epochs x steps][6] float64 receives per step, from the forward pass before that step's update: sum p,
+ * sum y, sum p^2, sum y^2, sum p y of output column 0 and sum (p - y)^2 over every output.
+ * Three launches per step and one per epoch, queued from the host without waiting (no persistent grid).
+ * Deterministic: fixed reduction orders, no atomics. */
+int td_mlp_train(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                 int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
+                 int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int epochs,
+                 float* params_dev, float* state_dev, float lr, float rho, float eps, int64_t shuffle_seed,
+                 double* stats_dev);
+/* The loss sums (stats_dev [6], as above) and the gradient of every parameter (grad_dev, the packed layout) of
+ * minibatch batch_index of the unshuffled stream at params_dev, without an update: the training step's own
+ * launches, the update launch writing the gradient instead of applying it. */
+int td_mlp_grad(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
+                int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int batch_index,
+                const float* params_dev, float* grad_dev, double* stats_dev);
+/* Inference over whole recordings: out_dev [rows, d] (row stride ldout), output row file_offsets[f] + t =
+ * frame t of file f (as td_predict_fir); three launches per 4096 rows. */
+int td_mlp_forward(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                   int c, int pre, int post, int input_offset, int d, const int* hidden_host, int num_hidden,
+                   const float* params_dev, float* out_dev, int64_t ldout);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,11 @@ SIGNATURES = {
     'td_audio_intensity': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _d, _d, _d, _i, _d, _vp, _vp],
     'td_audio_passthrough': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _i64, _i, _d, _vp, _vp],
     'td_audio_spectrogram': [_vp, _vp, _i64, _i, _i, _i, _pd, _i, _i64, _vp],
+    'td_mlp_train': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i, _c.POINTER(_i), _i, _i, _i,
+                     _vp, _vp, _f, _f, _f, _i64, _vp],
+    'td_mlp_grad': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i, _c.POINTER(_i), _i, _i, _i,
+                    _vp, _vp, _vp],
+    'td_mlp_forward': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i, _vp, _vp, _i64],
 }
 _RESTYPE = {'td_last_error': _c.c_char_p}
 

@@ -3,9 +3,9 @@
 Mirrors the call surface of the reference's brain_model.py for the linear path:
 `pearson_correlation[_first/_second]` (reference brain_model.py:34-91),
 `BrainModelLinearRegression` (:306-381) and
-`calculate_linear_regressor_parameters_from_dataset` (:384-481).  The Keras DNN /
-classifier shells and TensorBoard plumbing of that file are out of scope
-(SURVEY.md section 2).
+`calculate_linear_regressor_parameters_from_dataset` (:384-481); and the fully connected
+regressor `BrainModelDNN` (:486-549), trained on the GPU.  The classifier shell and the
+TensorBoard plumbing of that file are out of scope.
 """
 import numpy as np
 
@@ -366,6 +366,267 @@ class BrainModelLinearRegression(object):
     w, b = self._device_weights(h)
     x = _as_2d_device(h, lagged)
     return device.predict_fir(x, [0, int(x.shape[0])], w, b, 0, 0, handle=h)
+
+
+class RMSprop(object):
+  """The RMSprop settings BrainModelDNN trains with (Keras tf.keras.optimizers.RMSprop's arguments).  Only
+  momentum = 0 and centered = False are implemented (compile raises NotImplementedError otherwise)."""
+
+  def __init__(self, learning_rate=1e-3, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False):
+    self.learning_rate = float(learning_rate)
+    self.rho = float(rho)
+    self.momentum = float(momentum)
+    self.epsilon = float(epsilon)
+    self.centered = bool(centered)
+
+
+class History(object):
+  """What Keras' fit returns: `.history` = {metric: [one value per epoch]}."""
+
+  def __init__(self, history):
+    self.history = history
+    self.epoch = list(range(len(history.get('loss', []))))
+
+
+# td_mlp_* limits (include/td_hotpath.h)
+DNN_MAX_HIDDEN, DNN_MAX_UNITS, DNN_MAX_OUTPUTS, DNN_MAX_BATCH = 4, 64, 8, 2048
+DNN_MAX_CHANNELS, DNN_MAX_LAGS, DNN_MAX_INPUTS = 128, 64, 8192
+
+
+def _host(a):
+  if hasattr(a, 'is_cuda'):
+    return a.detach().cpu().numpy()
+  return np.asarray(a)
+
+
+def history_from_sums(sums, rows, d):
+  """Keras' per-epoch history from the six float64 sums of every step ([epochs, steps, 6]: sum p, y, p^2, y^2,
+  p y of output 0, sum (p - y)^2) of steps of `rows` rows and d outputs: each entry is the mean over the
+  epoch's steps of the step's value.  'pearson_correlation_first' is output 0's Pearson r with the zero rule of
+  pearson_correlation (a constant column gives 0)."""
+  s = np.asarray(sums, np.float64)
+  n = float(rows)
+  mse = s[..., 5] / (n * d)
+  va = s[..., 2] - s[..., 0] ** 2 / n
+  vb = s[..., 3] - s[..., 1] ** 2 / n
+  cov = s[..., 4] - s[..., 0] * s[..., 1] / n
+  tiny = 32 * np.finfo(np.float64).eps
+  zero = (va <= tiny * s[..., 2]) | (vb <= tiny * s[..., 3])
+  with np.errstate(invalid='ignore', divide='ignore'):
+    r = np.where(zero, 0.0, cov / (np.sqrt(np.maximum(va, 0)) * np.sqrt(np.maximum(vb, 0))))
+  loss = [float(v) for v in np.mean(mse, axis=-1)]
+  return {'loss': loss, 'pearson_correlation_first': [float(v) for v in np.mean(r, axis=-1)],
+          'mse': list(loss)}
+
+
+class BrainModelDNN(object):
+  """A fully connected regressor trained on the GPU (reference brain_model.py:486-549): Dense layers of
+  `num_hidden_list` ReLU units and a linear output layer, trained by minibatch RMSprop on the mean squared
+  error.  Training, inference and the lag gather run in the HIP kernels of td_mlp_* (csrc/mlp.hip); a fit
+  is one C call, with no host round trip between steps.
+
+  Differences from the reference, all documented:
+    * the initial weights are Keras' glorot_uniform (limit sqrt(6 / (fan_in + fan_out)), zero biases) drawn
+      with numpy.random.default_rng(seed): W1, W2, ... in layer order, each rng.uniform(-limit, limit,
+      (fan_in, fan_out)) as float32.  TF's random generator cannot be reproduced;
+    * fit(shuffle_seed=None) visits the stream's rows in order, minibatch s = rows [s B, (s + 1) B); with a
+      seed, epoch e visits them in the order of a bijection computed on the device from (seed, e) (a 4-round
+      Feistel network, cycle-walked; include/td_hotpath.h, td_mlp_train).  The reference shuffles frames
+      through a 1000-frame tf.data buffer, which cannot be reproduced;
+    * the only optimizer is RMSprop without momentum, the only loss 'mse'.
+  """
+
+  def __init__(self, input_dataset, num_hidden_list=None, *, seed=0, **kwargs):
+    kwargs.pop('tensorboard_dir', None)        # accepted and ignored, as BrainModelLinearRegression
+    del kwargs
+    if not _is_dataset(input_dataset):
+      raise ValueError('Dataset must be a tf.data.datasert, not a %s' % type(input_dataset))
+    if num_hidden_list is None:
+      num_hidden_list = []
+    if not isinstance(num_hidden_list, list):
+      raise TypeError('Num_hidden_list must be an list, not a %s.' % type(num_hidden_list))
+    self._input_width = int(input_dataset.element_spec[0]['input_1'].shape[-1])
+    self._output_width = int(input_dataset.element_spec[1].shape[-1])
+    self.num_hidden_list = [int(u) for u in num_hidden_list]
+    self._widths = [self._input_width] + self.num_hidden_list + [self._output_width]
+    rng = np.random.default_rng(seed)
+    weights = []
+    for fan_in, fan_out in zip(self._widths[:-1], self._widths[1:]):
+      limit = np.sqrt(6.0 / (fan_in + fan_out))
+      weights += [rng.uniform(-limit, limit, (fan_in, fan_out)).astype(np.float32),
+                  np.zeros((fan_out,), np.float32)]
+    self._host_weights = weights
+    self._params = None        # packed device parameters (the truth once on the device)
+    self._state = None         # RMSprop accumulators, same layout
+    self.optimizer = None
+    self.metrics_names = ['loss', 'pearson_correlation_first', 'mse']
+
+  # -- parameters ------------------------------------------------------------
+  def _shapes(self):
+    out = []
+    for fan_in, fan_out in zip(self._widths[:-1], self._widths[1:]):
+      out += [(fan_in, fan_out), (fan_out,)]
+    return out
+
+  def _device_params(self, h):
+    if self._params is None:
+      self._params = h.to_device(np.concatenate([w.reshape(-1) for w in self._host_weights])).reshape(-1)
+    return self._params
+
+  def get_weights(self):
+    """[W1, b1, ..., WL, bL] as float32 arrays (Keras order); W1's rows in input_1's lag layout."""
+    if self._params is not None:
+      flat, out, at = self._params.cpu().numpy(), [], 0
+      for shape in self._shapes():
+        size = int(np.prod(shape))
+        out.append(flat[at:at + size].reshape(shape).copy())
+        at += size
+      return out
+    return [w.copy() for w in self._host_weights]
+
+  def set_weights(self, weights):
+    shapes = self._shapes()
+    if len(weights) != len(shapes):
+      raise ValueError('Expected %d weight arrays, got %d' % (len(shapes), len(weights)))
+    arrays = []
+    for w, shape in zip(weights, shapes):
+      w = np.asarray(_host(w), np.float32)
+      if w.shape != shape:
+        raise ValueError('Weight of shape %s, expected %s' % (w.shape, shape))
+      arrays.append(w.copy())
+    self._host_weights = arrays
+    self._params = None
+
+  @property
+  def weight_matrices(self):
+    return self.get_weights()
+
+  # -- training ----------------------------------------------------------------
+  def compile(self, optimizer=RMSprop, loss='mse', metrics=(pearson_correlation_first, 'mse'),
+              learning_rate=1e-3, **kwargs):
+    """RMSprop (the class, an instance, 'rmsprop', or any callable that returns an RMSprop when called with
+    learning_rate=, as the reference's `if callable(optimizer)`) on loss 'mse' (or ['mse']).  The history
+    always reports loss, pearson_correlation_first and mse.  Starts a fresh optimizer state."""
+    del metrics, kwargs
+    if isinstance(optimizer, str):
+      if optimizer.lower() != 'rmsprop':
+        raise NotImplementedError('Optimizer %r is not supported: only RMSprop' % optimizer)
+      optimizer = RMSprop(learning_rate=learning_rate)
+    elif not isinstance(optimizer, RMSprop) and callable(optimizer):
+      optimizer = optimizer(learning_rate=learning_rate)
+    if not isinstance(optimizer, RMSprop):
+      raise NotImplementedError('Optimizer %r is not supported: only brain_model.RMSprop' % (optimizer,))
+    if optimizer.momentum != 0:
+      raise NotImplementedError('RMSprop momentum=%g is not supported: only momentum=0' % optimizer.momentum)
+    if optimizer.centered:
+      raise NotImplementedError('Centered RMSprop (centered=True) is not supported')
+    losses = list(loss) if isinstance(loss, (list, tuple)) else [loss]
+    if len(losses) != 1 or losses[0] != 'mse':
+      raise NotImplementedError('Loss %r is not supported: only mse' % (loss,))
+    self.optimizer = optimizer
+    self._state = None
+
+  def _check_limits(self, ds):
+    c, lags = ds.c1, ds.pre + 1 + ds.post
+    hidden = self.num_hidden_list
+    problems = []
+    if len(hidden) > DNN_MAX_HIDDEN:
+      problems.append('%d hidden layers (at most %d)' % (len(hidden), DNN_MAX_HIDDEN))
+    if any(u < 1 or u > DNN_MAX_UNITS for u in hidden):
+      problems.append('hidden layers of %s units (1 .. %d)' % (hidden, DNN_MAX_UNITS))
+    if not 1 <= self._output_width <= DNN_MAX_OUTPUTS:
+      problems.append('%d outputs (1 .. %d)' % (self._output_width, DNN_MAX_OUTPUTS))
+    if lags > DNN_MAX_LAGS:
+      problems.append('pre + 1 + post = %d (at most %d)' % (lags, DNN_MAX_LAGS))
+    if c > DNN_MAX_CHANNELS and lags > 1:
+      problems.append('%d channels with temporal context (at most %d)' % (c, DNN_MAX_CHANNELS))
+    if c * lags > DNN_MAX_INPUTS:
+      problems.append('%d lagged inputs (at most %d)' % (c * lags, DNN_MAX_INPUTS))
+    if not 1 <= ds.batch_size <= DNN_MAX_BATCH:
+      problems.append('batch of %d rows (1 .. %d)' % (ds.batch_size, DNN_MAX_BATCH))
+    if c * lags != self._input_width:
+      problems.append('input_1 is %d wide, the model %d' % (c * lags, self._input_width))
+    if problems:
+      raise ValueError('BrainModelDNN: ' + '; '.join(problems))
+
+  def _as_dataset(self, data):
+    """A brain_data.Dataset as the kernels read it (mixup_batch resolved), or an iterable of (dict, y)
+    minibatches materialised once as a context-free Dataset of the same batch size."""
+    if _is_dataset(data):
+      return data.resolved()
+    if not hasattr(data, '__iter__'):
+      raise TypeError('BrainModelDNN needs a brain_data.Dataset or an iterable of (dict, y) minibatches, '
+                      'not %s.' % type(data))
+    xs, ys = [], []
+    for feats, y in data:
+      x = np.asarray(_host(feats['input_1']), np.float32)
+      xs.append(x.reshape(x.shape[0], -1))
+      ys.append(np.asarray(_host(y), np.float32).reshape(x.shape[0], -1))
+    if not xs or xs[0].shape[0] == 0:
+      raise ValueError('No minibatches in dataset')
+    x, y = np.concatenate(xs), np.concatenate(ys)
+    zeros = np.zeros((x.shape[0], 1), np.float32)
+    return brain_data.Dataset([(x, zeros, y, zeros)], xs[0].shape[0])
+
+  def fit(self, input_dataset, *, epochs=1, shuffle_seed=None, **kwargs):
+    """Trains `epochs` epochs over the dataset's minibatches (reference brain_model.py:548-549 -> Keras fit).
+    Returns a History whose .history holds 'loss', 'pearson_correlation_first' and 'mse' per epoch: the mean
+    over the epoch's steps of each step's forward-pass value, before that step's update."""
+    del kwargs
+    if self.optimizer is None:
+      raise RuntimeError('You must compile your model before training/testing.')
+    if shuffle_seed is not None and not 0 <= int(shuffle_seed) < 2 ** 63:
+      raise ValueError('shuffle_seed must be in [0, 2^63), not %r' % (shuffle_seed,))
+    ds = self._as_dataset(input_dataset)
+    self._check_limits(ds)
+    epochs = int(epochs)
+    if ds.num_batches() == 0 or epochs <= 0:
+      return History({'loss': [], 'pearson_correlation_first': [], 'mse': []})
+    h = device.default_handle()
+    x, _, y, offs = ds.device_arrays(h)
+    params = self._device_params(h)
+    if self._state is None:
+      self._state = h.zeros((int(params.numel()),))
+    opt = self.optimizer
+    sums = device.mlp_train(x, y, offs, ds.pre, ds.post, self.num_hidden_list, params, self._state,
+                            ds.batch_size, epochs, opt.learning_rate, opt.rho, opt.epsilon,
+                            input_offset=ds.input_offset, rows_used=ds.rows_used(), shuffle_seed=shuffle_seed,
+                            handle=h)
+    return History(history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width))
+
+  # -- inference ---------------------------------------------------------------
+  def __call__(self, input_dataset):
+    return self.call(input_dataset)
+
+  def call(self, input_dataset):
+    """input_dataset: dict with an already-lagged 'input_1' [B, K] -> [B, D] (brain_model.py:524-528)."""
+    h = device.default_handle()
+    return brain_data._t(self._predict_lagged_device(input_dataset['input_1'], h).cpu().numpy())
+
+  def _predict_lagged_device(self, lagged, h):
+    x = _as_2d_device(h, lagged)
+    return device.mlp_forward(x, [0, int(x.shape[0])], 0, 0, self.num_hidden_list, self._output_width,
+                              self._device_params(h), handle=h)
+
+  def predict_device(self, dataset, handle=None):
+    """Predictions for every frame of every file, on the device: [rows, D] (row offs[f] + t = frame t of
+    file f's zipped streams, as BrainModelLinearRegression.predict_device)."""
+    h = handle or device.default_handle()
+    self._check_limits(dataset)
+    x, _, _, offs = dataset.device_arrays(h)
+    return device.mlp_forward(x, offs, dataset.pre, dataset.post, self.num_hidden_list, self._output_width,
+                              self._device_params(h), input_offset=dataset.input_offset, handle=h)
+
+  def predict(self, dataset):
+    pred = self.predict_device(dataset).cpu().numpy()
+    return rows_of_stream(pred, dataset.file_lengths(), dataset.rows_used())
+
+  def evaluate(self, dataset, **kwargs):
+    """{'loss', 'pearson_correlation_first', 'mse'}: means over minibatches, as Keras evaluate (the window-sums
+    route of BrainModelLinearRegression.evaluate)."""
+    out = BrainModelLinearRegression.evaluate(self, dataset, **kwargs)
+    out['mse'] = out['loss']
+    return out
 
 
 def _evaluate_minibatches(batches, h, predict, truth_from_y, metric_name='pearson_correlation_first'):

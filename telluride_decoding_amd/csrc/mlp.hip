@@ -1,0 +1,769 @@
+// Fully connected regressor (brain_model.BrainModelDNN; reference brain_model.py:486-549): training by
+// RMSprop, its gradients and inference, on the lagged view of the raw recordings -- the lag matrix is never
+// built.  Entry points td_mlp_train / td_mlp_grad / td_mlp_forward (include/td_hotpath.h).
+//
+// A training step is three launches, queued from C without a host round trip:
+//   slab  one workgroup per slice of W1's rows (K = lags x channels, <= 64 rows a slice): first the update of
+//         the PREVIOUS step -- dW1 of the slice = X~^T dZ1 over that step's rows, then RMSprop on the slice --
+//         then the partial first-layer pre-activations of THIS step's rows over the slice, zpart[slice][j][r].
+//         Extra workgroups reduce the previous step's partial gradients of the small layers (b1, W2, b2, ...)
+//         in a fixed order, apply RMSprop to them, and reduce its six loss sums.
+//   z1    thread per (unit, row): z1 = the slices' partials summed in slice order, + b1;
+//   head  one workgroup per 64 rows: the small layers (their parameters staged in LDS), the loss sums, the
+//         backward pass; dZ1 of its rows and its rows' partial gradients of the small layers.
+// Where each row of a step reads (file, frame, target row: through the shuffle) comes from a table built once
+// per epoch (mlp_rows_kernel).
+// Every reduction runs in a fixed order and there are no atomics: two runs are bitwise identical.  A step's
+// update is applied by the next step's slab launch, so every layer is updated after the full backward pass
+// (Keras); one slab launch after the last step applies the last update.
+#include "td_common.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int kMlpMaxHidden = 4, kMlpMaxWidth = 64, kMlpMaxD = 8, kMlpMaxB = 2048;
+constexpr int kMlpMaxK = 8192, kMlpMaxC = 128, kMlpMaxLags = 64;
+constexpr int kSlabThreads = 256;
+constexpr int kSlabMaxKs = 64;          // W1 rows per slab workgroup
+constexpr int kSlabRowChunk = 64;       // rows staged per pass of the update phase
+constexpr int kDzLd = kMlpMaxWidth + 4; // row stride of the staged dZ1 (float4 reads, rows on shifted banks)
+constexpr int kHeadRows = 64;           // rows (one per thread) per head workgroup
+constexpr int kFwdChunk = 4096;         // rows per step of td_mlp_forward
+// LDS of the head kernel at the largest shape: activations of 4 x 64 + 8 units, two dZ buffers, the targets, the
+// small parameters (b1, three 64 x 64 layers, the 64 x 8 output layer): 154 KB
+constexpr int kHeadMaxLds = 4 * ((4 * kMlpMaxWidth + kMlpMaxD) * kHeadRows + 2 * kMlpMaxWidth * kHeadRows +
+                                 kMlpMaxD * kHeadRows + kMlpMaxWidth + 3 * (kMlpMaxWidth + 1) * kMlpMaxWidth +
+                                 (kMlpMaxWidth + 1) * kMlpMaxD);
+
+struct MlpGeom {
+  const float* x;
+  long long ldx;
+  const float* y;
+  long long ldy;
+  const long long* file_offs;     // [nf + 1] rows of x / y
+  const long long* stream_offs;   // [nf + 1] rows of the zipped, batched stream (training)
+  int nf;
+  int c, pre, lags, k;
+  int dx, dy;                     // leading rows dropped of x / of y in every file (input_offset)
+  int nl;                         // dense layers (hidden + 1)
+  int w[kMlpMaxHidden + 2];       // widths: w[0] = k, ..., w[nl] = d
+  int off_w[kMlpMaxHidden + 1];   // offsets of W_l, b_l in the packed parameters
+  int off_b[kMlpMaxHidden + 1];
+  int n_params, small0, n_small;  // small parameters: everything after W1
+  long long n_rows;               // rows of the stream (training) / of x (inference)
+  int batch;                      // rows per step
+  int fwd;                        // 1: row i of chunk s is output row s * batch + i (inference)
+  int shuffle;
+  unsigned seed_lo, seed_hi;
+};
+
+// Where slot i of a pass reads: x rows [base, base + lags) clipped to [lo, hi), target row yrow (32-bit: the
+// tables are built once per epoch by mlp_rows_kernel, so the step kernels read one 16-B entry per row)
+typedef int4 RowEntry;
+
+// ---- the shuffle: a 4-round Feistel bijection on [0, 4^half), cycle-walked into [0, n) ----------------
+__device__ __forceinline__ unsigned mlp_mix32(unsigned z) {
+  z ^= z >> 16; z *= 0x7feb352dU; z ^= z >> 15; z *= 0x846ca68bU; z ^= z >> 16;
+  return z;
+}
+
+__device__ __forceinline__ long long mlp_permute(long long i, long long n, int epoch, unsigned seed_lo,
+                                                 unsigned seed_hi) {
+  int bits = 2;
+  while ((1LL << bits) < n) bits += 2;
+  const int half = bits / 2;
+  const unsigned mask = (1u << half) - 1u;
+  unsigned key[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    key[r] = mlp_mix32(seed_lo ^ mlp_mix32(seed_hi ^ mlp_mix32((unsigned)epoch * 4u + (unsigned)r)));
+  unsigned v = (unsigned)i;
+  do {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const unsigned left = v >> half, right = v & mask;
+      v = (right << half) | (left ^ (mlp_mix32(right ^ key[r]) & mask));
+    }
+  } while ((long long)v >= n);
+  return (long long)v;
+}
+
+struct RowInfo {
+  long long base, lo, hi, yrow;
+};
+
+// slot = step * batch + row of the step: where its lagged input and its target are
+__device__ __forceinline__ RowInfo mlp_row_search(const MlpGeom& g, long long slot, int epoch) {
+  const long long* offs = g.fwd ? g.file_offs : g.stream_offs;
+  long long q = slot;
+  if (!g.fwd && g.shuffle) q = mlp_permute(slot, g.n_rows, epoch, g.seed_lo, g.seed_hi);
+  int lo = 0, hi = g.nf;     // the last file f with offs[f] <= q
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (offs[mid] <= q) lo = mid; else hi = mid;
+  }
+  const long long t = q - offs[lo];
+  RowInfo ri;
+  ri.lo = g.file_offs[lo] + g.dx;
+  ri.hi = g.file_offs[lo + 1];
+  ri.base = ri.lo + t - g.pre;
+  ri.yrow = g.file_offs[lo] + g.dy + t;
+  return ri;
+}
+
+__device__ __forceinline__ RowInfo mlp_row(const RowEntry* tab, long long slot) {
+  const RowEntry e = tab[slot];
+  RowInfo ri;
+  ri.base = e.x; ri.lo = e.y; ri.hi = e.z; ri.yrow = e.w;
+  return ri;
+}
+
+// the row table of one epoch (or of every output row, inference)
+__global__ void mlp_rows_kernel(MlpGeom g, int epoch, RowEntry* tab) {
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < g.n_rows; i += (long long)gridDim.x * blockDim.x) {
+    const RowInfo ri = mlp_row_search(g, i, epoch);
+    tab[i] = make_int4((int)ri.base, (int)ri.lo, (int)ri.hi, (int)ri.yrow);
+  }
+}
+
+// lagged input k = l * c + ch of a row: x~[t + l - pre, ch], zero outside the file
+__device__ __forceinline__ float mlp_xt(const MlpGeom& g, long long base, long long lo, long long hi, int k) {
+  const int l = k / g.c, ch = k - l * g.c;
+  const long long row = base + l;
+  return (row >= lo && row < hi) ? g.x[row * g.ldx + ch] : 0.f;
+}
+
+struct SlabArgs {
+  MlpGeom g;
+  float* params;
+  float* state;
+  float* grad_out;        // non-null: the previous step's gradient is written here instead of applied
+  float* zpart;           // [nslices][w1][batch]
+  const float* dz1;       // [w1][batch] of the previous step
+  const float* gpart;     // [n_head][n_small]
+  const double* spart;    // [n_head][6]
+  double* stats_out;      // six sums of the previous step (may be null)
+  const RowEntry* prev_rows;   // row tables of the previous / current step's epoch
+  const RowEntry* cur_rows;
+  int ks, nslices, n_head;
+  int prev_epoch, prev_step;   // -1: no update
+  int cur_epoch, cur_step;     // -1: no forward
+  float lr, rho, eps;
+};
+
+__device__ __forceinline__ int mlp_rows_in_step(const MlpGeom& g, int step) {
+  const long long left = g.n_rows - (long long)step * g.batch;
+  return (int)(left < g.batch ? left : g.batch);
+}
+
+// Keras RMSprop without momentum: v = rho v + (1 - rho) g^2, w -= lr g / (sqrt(v) + eps); returns the new w
+__device__ __forceinline__ float mlp_rmsprop(float* p, float* v, float grad, float lr, float rho, float eps) {
+  const float vn = rho * *v + (1.f - rho) * (grad * grad);
+  const float pn = *p - lr * grad / (sqrtf(vn) + eps);
+  *v = vn;
+  *p = pn;
+  return pn;
+}
+
+constexpr int kW1Groups = kSlabMaxKs * kMlpMaxWidth / 4 / kSlabThreads;   // (row, 4 columns) groups per thread
+
+// dW1 of the rows [k0, k0 + ksl) over the rows of the previous step: thread group (kk, 4 columns); rows summed
+// in order within chunks of 64, the chunks in order
+__device__ void mlp_w1_grad(const SlabArgs& a, int k0, int ksl, float (*acc)[4], RowInfo* ri,
+                            float (*xs)[kSlabMaxKs + 1], float (*dzs)[kDzLd]) {
+  const MlpGeom& g = a.g;
+  const int w1 = g.w[1], w1q = (w1 + 3) / 4, tid = threadIdx.x;
+  const int rows = mlp_rows_in_step(g, a.prev_step);
+  const int n_groups = ksl * w1q;
+  for (int r0 = 0; r0 < rows; r0 += kSlabRowChunk) {
+    const int nr = rows - r0 < kSlabRowChunk ? rows - r0 : kSlabRowChunk;
+    __syncthreads();
+    if (tid < nr) ri[tid] = mlp_row(a.prev_rows, (long long)a.prev_step * g.batch + r0 + tid);
+    for (int i = tid; i < nr * w1q * 4; i += kSlabThreads) {
+      const int j = i / nr, r = i - j * nr;
+      dzs[r][j] = j < w1 ? a.dz1[(long long)j * g.batch + r0 + r] : 0.f;
+    }
+    __syncthreads();
+    for (int i = tid; i < nr * ksl; i += kSlabThreads) {
+      const int r = i / ksl, kk = i - r * ksl;
+      xs[r][kk] = mlp_xt(g, ri[r].base, ri[r].lo, ri[r].hi, k0 + kk);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int o = 0; o < kW1Groups; ++o) {
+      const int grp = tid + o * kSlabThreads;
+      if (grp < n_groups) {
+        const int kk = grp / w1q, j0 = (grp - kk * w1q) * 4;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        for (int r = 0; r < nr; ++r) {
+          const float xv = xs[r][kk];
+          const float4 dv = *reinterpret_cast<const float4*>(&dzs[r][j0]);
+          s0 = fmaf(xv, dv.x, s0); s1 = fmaf(xv, dv.y, s1); s2 = fmaf(xv, dv.z, s2); s3 = fmaf(xv, dv.w, s3);
+        }
+        acc[o][0] += s0; acc[o][1] += s1; acc[o][2] += s2; acc[o][3] += s3;
+      }
+    }
+  }
+}
+
+template <int NJ>
+__global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
+  __shared__ RowInfo ri[kSlabRowChunk];
+  __shared__ float xs[kSlabRowChunk][kSlabMaxKs + 1];   // (+1: the forward reads a column, rows on other banks)
+  __shared__ __attribute__((aligned(16))) float dzs[kSlabRowChunk][kDzLd];
+  __shared__ __attribute__((aligned(16))) float ws[kSlabMaxKs][NJ];
+  const MlpGeom& g = a.g;
+  const int tid = threadIdx.x, w1 = g.w[1];
+  const int wg = blockIdx.x;
+  if (wg >= a.nslices) {
+    // the small layers' update and the loss sums of the previous step
+    if (a.prev_step < 0) return;
+    const int p = (wg - a.nslices) * kSlabThreads + tid;
+    if (p < g.n_small) {
+      float s = 0.f;
+      for (int hw = 0; hw < a.n_head; ++hw) s += a.gpart[(long long)hw * g.n_small + p];
+      if (a.grad_out) a.grad_out[g.small0 + p] = s;
+      else mlp_rmsprop(&a.params[g.small0 + p], &a.state[g.small0 + p], s, a.lr, a.rho, a.eps);
+    }
+    if (wg == a.nslices && tid < 6 && a.stats_out) {
+      double s = 0.0;
+      for (int hw = 0; hw < a.n_head; ++hw) s += a.spart[hw * 6 + tid];
+      a.stats_out[tid] = s;
+    }
+    return;
+  }
+  const int k0 = wg * a.ks;
+  const int ksl = g.k - k0 < a.ks ? g.k - k0 : a.ks;
+  float* w1p = a.params;   // W1 [k][w1]
+  const bool fwd = a.cur_step >= 0;
+  // the slice of W1 the forward multiplies by, zero-padded to NJ columns; the update below refreshes it
+  if (fwd)
+    for (int i = tid; i < kSlabMaxKs * NJ; i += kSlabThreads) {
+      const int kk = i / NJ, j = i - kk * NJ;
+      ws[kk][j] = (kk < ksl && j < w1) ? w1p[(long long)(k0 + kk) * w1 + j] : 0.f;
+    }
+  if (a.prev_step >= 0) {
+    float acc[kW1Groups][4];
+#pragma unroll
+    for (int o = 0; o < kW1Groups; ++o) acc[o][0] = acc[o][1] = acc[o][2] = acc[o][3] = 0.f;
+    mlp_w1_grad(a, k0, ksl, acc, ri, xs, dzs);
+    const int w1q = (w1 + 3) / 4;
+#pragma unroll
+    for (int o = 0; o < kW1Groups; ++o) {
+      const int grp = tid + o * kSlabThreads;
+      if (grp < ksl * w1q) {
+        const int kk = grp / w1q, j0 = (grp - kk * w1q) * 4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          if (j0 + q < w1) {
+            const long long at = (long long)(k0 + kk) * w1 + j0 + q;
+            if (a.grad_out) {
+              a.grad_out[at] = acc[o][q];
+            } else {
+              const float nw = mlp_rmsprop(&w1p[at], &a.state[at], acc[o][q], a.lr, a.rho, a.eps);
+              if (fwd) ws[kk][j0 + q] = nw;
+            }
+          }
+        }
+      }
+    }
+  }
+  if (!fwd) return;
+  // partial z1 of this step's rows over the slice: chunks of 64 rows staged in LDS, thread = (row, 4 columns)
+  const int rows = mlp_rows_in_step(g, a.cur_step);
+  constexpr int kQ = NJ / 4;
+  for (int r0 = 0; r0 < rows; r0 += kSlabRowChunk) {
+    const int nr = rows - r0 < kSlabRowChunk ? rows - r0 : kSlabRowChunk;
+    __syncthreads();
+    if (tid < nr) ri[tid] = mlp_row(a.cur_rows, (long long)a.cur_step * g.batch + r0 + tid);
+    __syncthreads();
+    for (int i = tid; i < nr * ksl; i += kSlabThreads) {
+      const int r = i / ksl, kk = i - r * ksl;
+      xs[r][kk] = mlp_xt(g, ri[r].base, ri[r].lo, ri[r].hi, k0 + kk);
+    }
+    __syncthreads();
+    for (int t = tid; t < kSlabRowChunk * kQ; t += kSlabThreads) {
+      const int r = t % kSlabRowChunk, j0 = (t / kSlabRowChunk) * 4;
+      if (r >= nr || j0 >= w1) continue;
+      float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+      for (int kk = 0; kk < ksl; ++kk) {
+        const float xv = xs[r][kk];
+        const float4 wv = *reinterpret_cast<const float4*>(&ws[kk][j0]);
+        s0 = fmaf(xv, wv.x, s0); s1 = fmaf(xv, wv.y, s1); s2 = fmaf(xv, wv.z, s2); s3 = fmaf(xv, wv.w, s3);
+      }
+      float* zp = a.zpart + ((long long)wg * w1 + j0) * g.batch + r0 + r;
+      zp[0] = s0;
+      if (j0 + 1 < w1) zp[g.batch] = s1;
+      if (j0 + 2 < w1) zp[2 * (long long)g.batch] = s2;
+      if (j0 + 3 < w1) zp[3 * (long long)g.batch] = s3;
+    }
+  }
+}
+
+// z1 = sum of the slices' partials in slice order, + b1: thread per (unit, row)
+__global__ __launch_bounds__(256) void mlp_z1_kernel(const float* __restrict__ zpart, int nslices, int w1, int batch,
+                                                     int rows, const float* __restrict__ b1, float* __restrict__ z1) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= w1 * batch) return;
+  const int j = i / batch, r = i - j * batch;
+  if (r >= rows) return;
+  const float* zp = zpart + i;
+  const long long stride = (long long)w1 * batch;
+  float s = 0.f;
+#pragma unroll 8
+  for (int sl = 0; sl < nslices; ++sl) s += zp[sl * stride];
+  z1[i] = s + b1[j];
+}
+
+struct HeadArgs {
+  MlpGeom g;
+  const float* params;
+  const float* zpart;
+  int nslices;
+  int epoch, step;
+  int backward;
+  float* dz1;       // [w1][batch]
+  float* gpart;     // [n_head][n_small]
+  double* spart;    // [n_head][6]
+  float* out;       // inference: [rows, d] (row stride ldout)
+  long long ldout;
+  const RowEntry* rows_tab;
+  const float* z1;  // [w1][batch]: b1 + the slices' partials (mlp_z1_kernel)
+  int act_off[kMlpMaxHidden + 2];   // LDS offsets of the activations of layer l = 1 .. nl ([w_l][64])
+  int act_floats;
+  int maxw;
+};
+
+// z1 = b1 + partials, the small layers, the loss sums and the backward pass of 64 rows
+__global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
+  extern __shared__ float lds[];
+  const MlpGeom& g = a.g;
+  const int tid = threadIdx.x, nl = g.nl, d = g.w[nl];
+  float* act = lds;
+  float* dzb = lds + a.act_floats;                    // [2][maxw][64]
+  float* yb = dzb + 2 * a.maxw * kHeadRows;           // [d][64]
+  float* wsm = yb + d * kHeadRows;                    // the small parameters (b1, W2, b2, ...)
+  for (int i = tid; i < g.n_small; i += kHeadRows) wsm[i] = a.params[g.small0 + i];
+  const float* prm = wsm - g.small0;                  // indexed by parameter offset
+  __syncthreads();
+  const int rows = mlp_rows_in_step(g, a.step);
+  const int r = blockIdx.x * kHeadRows + tid;
+  const bool valid = r < rows;
+  long long yrow = 0;
+  if (valid && !a.out) yrow = mlp_row(a.rows_tab, (long long)a.step * g.batch + r).yrow;
+  // layer 1: b1 + the slices' partial sums (mlp_z1_kernel)
+  {
+    const int w1 = g.w[1];
+    float* a1 = act + a.act_off[1];
+    for (int j = 0; j < w1; ++j) {
+      const float s = valid ? a.z1[(long long)j * g.batch + r] : prm[g.off_b[0] + j];
+      a1[j * kHeadRows + tid] = (nl > 1 && s <= 0.f) ? 0.f : s;
+    }
+  }
+  for (int l = 2; l <= nl; ++l) {
+    const int wi = g.w[l - 1], wo = g.w[l];
+    const float* W = prm + g.off_w[l - 1];
+    const float* b = prm + g.off_b[l - 1];
+    const float* in = act + a.act_off[l - 1];
+    float* outp = act + a.act_off[l];
+    for (int o = 0; o < wo; ++o) {
+      float s = 0.f;
+      for (int i = 0; i < wi; ++i) s = fmaf(in[i * kHeadRows + tid], W[i * wo + o], s);
+      s += b[o];
+      outp[o * kHeadRows + tid] = (l < nl && s <= 0.f) ? 0.f : s;
+    }
+  }
+  const float* p = act + a.act_off[nl];
+  if (a.out) {
+    if (valid)
+      for (int o = 0; o < d; ++o) a.out[((long long)a.step * g.batch + r) * a.ldout + o] = p[o * kHeadRows + tid];
+    return;
+  }
+  for (int o = 0; o < d; ++o) yb[o * kHeadRows + tid] = valid ? g.y[yrow * g.ldy + o] : 0.f;
+  __syncthreads();
+  // the six loss sums of these rows in float64, rows in order: sum p, y, p^2, y^2, p y of output column 0 and
+  // sum (p - y)^2 over every column
+  if (tid < 6) {
+    double s = 0.0;
+    const int left = rows - blockIdx.x * kHeadRows;
+    const int n = left < kHeadRows ? left : kHeadRows;
+    for (int rr = 0; rr < n; ++rr) {
+      const double pv = p[rr], yv = yb[rr];
+      if (tid == 0) s += pv;
+      else if (tid == 1) s += yv;
+      else if (tid == 2) s += pv * pv;
+      else if (tid == 3) s += yv * yv;
+      else if (tid == 4) s += pv * yv;
+      else
+        for (int o = 0; o < d; ++o) {
+          const double e = (double)p[o * kHeadRows + rr] - (double)yb[o * kHeadRows + rr];
+          s += e * e;
+        }
+    }
+    a.spart[blockIdx.x * 6 + tid] = s;
+  }
+  if (!a.backward) return;
+  float* gp = a.gpart + (long long)blockIdx.x * g.n_small - g.small0;   // indexed by parameter offset
+  // dL/dp of Keras 'mse' (the mean over rows x outputs): 2 (p - y) / (rows d)
+  const float scale = 2.f / ((float)rows * (float)d);
+  int cur = 0;
+  for (int o = 0; o < d; ++o)
+    dzb[o * kHeadRows + tid] = valid ? (p[o * kHeadRows + tid] - yb[o * kHeadRows + tid]) * scale : 0.f;
+  for (int l = nl; l >= 1; --l) {
+    __syncthreads();
+    const int wo = g.w[l];
+    const float* dz = dzb + cur * a.maxw * kHeadRows;
+    // bias gradient: the sum over the 64 rows, in order
+    for (int o = tid; o < wo; o += kHeadRows) {
+      float s = 0.f;
+      for (int rr = 0; rr < kHeadRows; ++rr) s += dz[o * kHeadRows + rr];
+      gp[g.off_b[l - 1] + o] = s;
+    }
+    if (l == 1) {
+      if (valid)
+        for (int j = 0; j < wo; ++j) a.dz1[(long long)j * g.batch + r] = dz[j * kHeadRows + tid];
+      break;
+    }
+    const int wi = g.w[l - 1];
+    const float* in = act + a.act_off[l - 1];
+    for (int idx = tid; idx < wi * wo; idx += kHeadRows) {
+      const int i = idx / wo, o = idx - i * wo;
+      float s = 0.f;
+      for (int rr = 0; rr < kHeadRows; ++rr) s = fmaf(in[i * kHeadRows + rr], dz[o * kHeadRows + rr], s);
+      gp[g.off_w[l - 1] + idx] = s;
+    }
+    // dA_{l-1} = dZ_l W_l^T through the ReLU (ReLU'(0) = 0: the activation is 0 exactly where z <= 0)
+    const float* W = prm + g.off_w[l - 1];
+    float* dn = dzb + (cur ^ 1) * a.maxw * kHeadRows;
+    for (int i = 0; i < wi; ++i) {
+      float s = 0.f;
+      for (int o = 0; o < wo; ++o) s = fmaf(W[i * wo + o], dz[o * kHeadRows + tid], s);
+      dn[i * kHeadRows + tid] = in[i * kHeadRows + tid] > 0.f ? s : 0.f;
+    }
+    cur ^= 1;
+  }
+}
+
+struct MlpPlan {
+  MlpGeom g;
+  int ks = 0, nslices = 0, n_small_wg = 0, n_head = 0, nj = 0;
+  size_t head_lds = 0;
+  int act_off[kMlpMaxHidden + 2] = {};
+  int act_floats = 0, maxw = 0;
+};
+
+int mlp_check_and_plan(td_handle* h, const char* fn, const float* x_dev, int64_t ldx, const int64_t* offs, int nf,
+                       int c, int pre, int post, int input_offset, int d, const int* hidden, int num_hidden,
+                       int batch, MlpPlan* plan) {
+  if (!h) return td_fail(h, TD_ERR_INVALID, "%s: NULL handle", fn);
+  TD_REQUIRE(h, x_dev && offs && nf >= 1, "%s: NULL argument or no files", fn);
+  TD_REQUIRE(h, c >= 1 && pre >= 0 && post >= 0, "%s: bad sizes", fn);
+  const int64_t lags = (int64_t)pre + 1 + post;
+  TD_REQUIRE(h, lags <= kMlpMaxLags, "%s: pre + 1 + post = %lld exceeds %d", fn, (long long)lags, kMlpMaxLags);
+  TD_REQUIRE(h, c <= kMlpMaxC || lags == 1, "%s: %d channels exceed %d (only context-free input may be wider)", fn,
+             c, kMlpMaxC);
+  TD_REQUIRE(h, c * lags <= kMlpMaxK, "%s: %lld lagged inputs exceed %d", fn, (long long)(c * lags), kMlpMaxK);
+  TD_REQUIRE(h, ldx >= c, "%s: leading dimension of x too small", fn);
+  TD_REQUIRE(h, num_hidden >= 0 && num_hidden <= kMlpMaxHidden, "%s: %d hidden layers (at most %d)", fn, num_hidden,
+             kMlpMaxHidden);
+  TD_REQUIRE(h, num_hidden == 0 || hidden, "%s: NULL hidden widths", fn);
+  for (int i = 0; i < num_hidden; ++i)
+    TD_REQUIRE(h, hidden[i] >= 1 && hidden[i] <= kMlpMaxWidth, "%s: hidden layer of %d units (1 .. %d)", fn,
+               hidden[i], kMlpMaxWidth);
+  TD_REQUIRE(h, d >= 1 && d <= kMlpMaxD, "%s: %d outputs (1 .. %d)", fn, d, kMlpMaxD);
+  TD_REQUIRE(h, batch >= 1 && batch <= kFwdChunk, "%s: batch of %d rows", fn, batch);
+  TD_REQUIRE(h, offs[0] == 0, "%s: file offsets must start at 0", fn);
+  for (int f = 0; f < nf; ++f) TD_REQUIRE(h, offs[f + 1] >= offs[f], "%s: file offsets decrease", fn);
+  TD_REQUIRE(h, offs[nf] < (1LL << 31), "%s: more than 2^31 rows", fn);
+  MlpGeom& g = plan->g;
+  memset(&g, 0, sizeof(g));
+  g.x = x_dev; g.ldx = ldx; g.nf = nf;
+  g.c = c; g.pre = pre; g.lags = (int)lags; g.k = (int)(c * lags);
+  g.dx = input_offset > 0 ? input_offset : 0;
+  g.dy = input_offset < 0 ? -input_offset : 0;
+  g.nl = num_hidden + 1;
+  g.w[0] = g.k;
+  for (int i = 0; i < num_hidden; ++i) g.w[i + 1] = hidden[i];
+  g.w[g.nl] = d;
+  int at = 0;
+  for (int l = 1; l <= g.nl; ++l) {
+    g.off_w[l - 1] = at; at += g.w[l - 1] * g.w[l];
+    g.off_b[l - 1] = at; at += g.w[l];
+  }
+  g.n_params = at;
+  g.small0 = g.k * g.w[1];
+  g.n_small = at - g.small0;
+  g.batch = batch;
+  plan->ks = (int)td_round_up(td_ceil_div(g.k, 64), 4);
+  plan->ks = plan->ks > kSlabMaxKs ? kSlabMaxKs : plan->ks;
+  plan->nslices = (int)td_ceil_div(g.k, plan->ks);
+  plan->n_small_wg = (int)td_ceil_div(g.n_small, kSlabThreads);
+  plan->n_head = (int)td_ceil_div(batch, kHeadRows);
+  const int w1 = g.w[1];
+  plan->nj = w1 <= 4 ? 4 : w1 <= 8 ? 8 : w1 <= 16 ? 16 : w1 <= 24 ? 24 : w1 <= 32 ? 32 : w1 <= 48 ? 48 : 64;
+  int maxw = 0, off = 0;
+  for (int l = 1; l <= g.nl; ++l) {
+    plan->act_off[l] = off;
+    off += g.w[l] * kHeadRows;
+    maxw = g.w[l] > maxw ? g.w[l] : maxw;
+  }
+  plan->act_floats = off;
+  plan->maxw = maxw;
+  plan->head_lds = sizeof(float) * ((size_t)off + 2 * (size_t)maxw * kHeadRows + (size_t)d * kHeadRows + g.n_small);
+  return TD_OK;
+}
+
+int mlp_launch_slab(td_handle* h, const MlpPlan& plan, const SlabArgs& a, bool with_small) {
+  const int grid = plan.nslices + (with_small ? plan.n_small_wg : 0);
+  switch (plan.nj) {
+    case 4: hipLaunchKernelGGL(mlp_slab_kernel<4>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
+    case 8: hipLaunchKernelGGL(mlp_slab_kernel<8>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
+    case 16: hipLaunchKernelGGL(mlp_slab_kernel<16>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
+    case 24: hipLaunchKernelGGL(mlp_slab_kernel<24>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
+    case 32: hipLaunchKernelGGL(mlp_slab_kernel<32>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
+    case 48: hipLaunchKernelGGL(mlp_slab_kernel<48>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
+    default: hipLaunchKernelGGL(mlp_slab_kernel<64>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
+  }
+  TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
+int mlp_launch_head(td_handle* h, const MlpPlan& plan, const HeadArgs& a) {
+  const MlpGeom& g = a.g;
+  const int rows = (int)std::min<long long>(g.batch, g.n_rows - (long long)a.step * g.batch);
+  hipLaunchKernelGGL(mlp_z1_kernel, dim3((unsigned)td_ceil_div((int64_t)g.w[1] * g.batch, 256)), dim3(256), 0,
+                     h->stream, a.zpart, plan.nslices, g.w[1], g.batch, rows, a.params + g.off_b[0],
+                     const_cast<float*>(a.z1));
+  hipLaunchKernelGGL(mlp_head_kernel, dim3(plan.n_head), dim3(kHeadRows), plan.head_lds, h->stream, a);
+  TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
+// Device scratch of a call: working copies of the parameters and optimizer state, the exchange buffers
+// between the launches and the offset tables.
+struct MlpWork {
+  float *params, *state, *zpart, *dz1, *gpart, *z1;
+  RowEntry* rows[2];        // row tables of even / odd epochs
+  double* spart;
+  long long *file_offs, *stream_offs;
+};
+
+int mlp_work(td_handle* h, const MlpPlan& plan, int nf, MlpWork* w) {
+  const MlpGeom& g = plan.g;
+  const size_t n_par = td_round_up(g.n_params, 64);
+  const size_t n_z = td_round_up((int64_t)plan.nslices * g.w[1] * g.batch, 64);
+  const size_t n_dz = td_round_up((int64_t)g.w[1] * g.batch, 64);
+  const size_t n_gp = td_round_up((int64_t)plan.n_head * g.n_small, 64);
+  const size_t n_sp = td_round_up((int64_t)plan.n_head * 6, 32);
+  const size_t n_off = td_round_up((int64_t)nf + 1, 32);
+  const size_t n_tab = td_round_up(g.n_rows, 64);
+  const size_t bytes = 4 * (2 * n_par + n_z + 2 * n_dz + n_gp) + 8 * (n_sp + 2 * n_off) + 2 * 16 * n_tab;
+  void* base = nullptr;
+  TD_TRY(td_scratch(h, bytes, &base));
+  char* p = static_cast<char*>(base);
+  w->rows[0] = reinterpret_cast<RowEntry*>(p); p += 16 * n_tab;
+  w->rows[1] = reinterpret_cast<RowEntry*>(p); p += 16 * n_tab;
+  w->spart = reinterpret_cast<double*>(p); p += 8 * n_sp;
+  w->file_offs = reinterpret_cast<long long*>(p); p += 8 * n_off;
+  w->stream_offs = reinterpret_cast<long long*>(p); p += 8 * n_off;
+  w->params = reinterpret_cast<float*>(p); p += 4 * n_par;
+  w->state = reinterpret_cast<float*>(p); p += 4 * n_par;
+  w->zpart = reinterpret_cast<float*>(p); p += 4 * n_z;
+  w->dz1 = reinterpret_cast<float*>(p); p += 4 * n_dz;
+  w->z1 = reinterpret_cast<float*>(p); p += 4 * n_dz;
+  w->gpart = reinterpret_cast<float*>(p);
+  return TD_OK;
+}
+
+// the stream's rows per file (rows_used, else the zipped lengths) as offsets
+int mlp_stream_offsets(td_handle* h, const char* fn, const int64_t* offs, int nf, int input_offset,
+                       const int64_t* rows_used, std::vector<long long>* so) {
+  const int64_t off = input_offset < 0 ? -(int64_t)input_offset : input_offset;
+  so->assign(nf + 1, 0);
+  for (int f = 0; f < nf; ++f) {
+    const int64_t n = offs[f + 1] - offs[f];
+    const int64_t z = n - off > 0 ? n - off : 0;
+    int64_t u = z;
+    if (rows_used) {
+      TD_REQUIRE(h, rows_used[f] >= 0 && rows_used[f] <= z, "%s: rows_used[%d] = %lld, the file has %lld rows", fn,
+                 f, (long long)rows_used[f], (long long)z);
+      u = rows_used[f];
+    }
+    (*so)[f + 1] = (*so)[f] + u;
+  }
+  return TD_OK;
+}
+
+int mlp_setup(td_handle* h, MlpPlan* plan, int nf, const int64_t* offs, const std::vector<long long>& so,
+              MlpWork* w) {
+  TD_TRY(mlp_work(h, *plan, nf, w));
+  TD_TRY(td_upload_async(h, offs, sizeof(long long) * (nf + 1), w->file_offs));
+  if (!so.empty()) TD_TRY(td_upload_async(h, so.data(), sizeof(long long) * (nf + 1), w->stream_offs));
+  plan->g.file_offs = w->file_offs;
+  plan->g.stream_offs = so.empty() ? w->file_offs : w->stream_offs;
+  TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
+  return TD_OK;
+}
+
+void mlp_fill(const MlpPlan& plan, const MlpWork& w, SlabArgs* sa, HeadArgs* ha) {
+  memset(sa, 0, sizeof(*sa));
+  memset(ha, 0, sizeof(*ha));
+  sa->g = plan.g;
+  sa->params = w.params; sa->state = w.state;
+  sa->zpart = w.zpart; sa->dz1 = w.dz1; sa->gpart = w.gpart; sa->spart = w.spart;
+  sa->ks = plan.ks; sa->nslices = plan.nslices; sa->n_head = plan.n_head;
+  sa->prev_epoch = sa->prev_step = sa->cur_epoch = sa->cur_step = -1;
+  ha->g = plan.g;
+  ha->params = w.params; ha->zpart = w.zpart; ha->nslices = plan.nslices;
+  ha->dz1 = w.dz1; ha->gpart = w.gpart; ha->spart = w.spart;
+  for (int l = 0; l < kMlpMaxHidden + 2; ++l) ha->act_off[l] = plan.act_off[l];
+  ha->act_floats = plan.act_floats; ha->maxw = plan.maxw;
+  ha->z1 = w.z1;
+  ha->backward = 1;
+  sa->prev_rows = sa->cur_rows = ha->rows_tab = w.rows[0];
+}
+
+// the row table of `epoch` into tab (queued)
+int mlp_launch_rows(td_handle* h, const MlpGeom& g, int epoch, RowEntry* tab) {
+  const long long blocks = std::min<long long>(td_ceil_div(g.n_rows, 256), 4096);
+  hipLaunchKernelGGL(mlp_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, g, epoch, tab);
+  TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
+}  // namespace
+
+int td_mlp_train(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                 int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
+                 int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int epochs,
+                 float* params_dev, float* state_dev, float lr, float rho, float eps, int64_t shuffle_seed,
+                 double* stats_dev) {
+  static const char* fn = "td_mlp_train";
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, batch_rows, &plan));
+  TD_REQUIRE(h, batch_rows <= kMlpMaxB, "%s: batch of %d rows exceeds %d", fn, batch_rows, kMlpMaxB);
+  TD_REQUIRE(h, y_dev && params_dev && state_dev && ldy >= d, "%s: NULL argument or ldy too small", fn);
+  TD_REQUIRE(h, epochs >= 0, "%s: negative epoch count", fn);
+  TD_REQUIRE(h, std::isfinite(lr) && std::isfinite(rho) && std::isfinite(eps), "%s: non-finite optimizer setting",
+             fn);
+  std::vector<long long> so;
+  TD_TRY(mlp_stream_offsets(h, fn, file_offsets_host, num_files, input_offset, rows_used_host, &so));
+  const long long n_rows = so[num_files];
+  TD_REQUIRE(h, n_rows >= 1, "%s: no rows to train on", fn);
+  const int steps = (int)td_ceil_div(n_rows, batch_rows);
+  TD_REQUIRE(h, epochs == 0 || stats_dev, "%s: NULL stats buffer", fn);
+  if (epochs == 0) return TD_OK;
+  plan.g.y = y_dev; plan.g.ldy = ldy;
+  plan.g.n_rows = n_rows;
+  plan.g.shuffle = shuffle_seed >= 0;
+  plan.g.seed_lo = (unsigned)((uint64_t)shuffle_seed & 0xffffffffu);
+  plan.g.seed_hi = (unsigned)((uint64_t)shuffle_seed >> 32);
+  MlpWork w;
+  TD_TRY(mlp_setup(h, &plan, num_files, file_offsets_host, so, &w));
+  // work on copies: the caller's parameters change only when every launch has been queued
+  const size_t pbytes = sizeof(float) * plan.g.n_params;
+  TD_HIP(h, hipMemcpyAsync(w.params, params_dev, pbytes, hipMemcpyDeviceToDevice, h->stream));
+  TD_HIP(h, hipMemcpyAsync(w.state, state_dev, pbytes, hipMemcpyDeviceToDevice, h->stream));
+  SlabArgs sa;
+  HeadArgs ha;
+  mlp_fill(plan, w, &sa, &ha);
+  sa.lr = lr; sa.rho = rho; sa.eps = eps;
+  int pe = -1, ps = -1;
+  for (int e = 0; e < epochs; ++e) {
+    // in order, one table serves every epoch; shuffled, epochs alternate between two (the first step of
+    // epoch e still updates with the last rows of epoch e - 1)
+    RowEntry* tab = plan.g.shuffle ? w.rows[e & 1] : w.rows[0];
+    if (e == 0 || plan.g.shuffle) TD_TRY(mlp_launch_rows(h, plan.g, e, tab));
+    sa.prev_rows = sa.cur_rows;
+    sa.cur_rows = ha.rows_tab = tab;
+    for (int s = 0; s < steps; ++s) {
+      if (s == 1) sa.prev_rows = tab;
+      sa.prev_epoch = pe; sa.prev_step = ps; sa.cur_epoch = e; sa.cur_step = s;
+      sa.stats_out = ps >= 0 ? stats_dev + 6 * ((long long)pe * steps + ps) : nullptr;
+      TD_TRY(mlp_launch_slab(h, plan, sa, ps >= 0));
+      ha.epoch = e; ha.step = s;
+      TD_TRY(mlp_launch_head(h, plan, ha));
+      pe = e; ps = s;
+    }
+  }
+  sa.prev_epoch = pe; sa.prev_step = ps; sa.cur_epoch = sa.cur_step = -1;
+  sa.prev_rows = sa.cur_rows;
+  sa.stats_out = stats_dev + 6 * ((long long)pe * steps + ps);
+  TD_TRY(mlp_launch_slab(h, plan, sa, true));
+  TD_HIP(h, hipMemcpyAsync(params_dev, w.params, pbytes, hipMemcpyDeviceToDevice, h->stream));
+  TD_HIP(h, hipMemcpyAsync(state_dev, w.state, pbytes, hipMemcpyDeviceToDevice, h->stream));
+  return TD_OK;
+}
+
+int td_mlp_grad(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
+                int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int batch_index,
+                const float* params_dev, float* grad_dev, double* stats_dev) {
+  static const char* fn = "td_mlp_grad";
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, batch_rows, &plan));
+  TD_REQUIRE(h, batch_rows <= kMlpMaxB, "%s: batch of %d rows exceeds %d", fn, batch_rows, kMlpMaxB);
+  TD_REQUIRE(h, y_dev && params_dev && grad_dev && stats_dev && ldy >= d, "%s: NULL argument or ldy too small", fn);
+  std::vector<long long> so;
+  TD_TRY(mlp_stream_offsets(h, fn, file_offsets_host, num_files, input_offset, rows_used_host, &so));
+  const long long n_rows = so[num_files];
+  TD_REQUIRE(h, batch_index >= 0 && (long long)batch_index * batch_rows < n_rows,
+             "%s: minibatch %d is outside the stream's %lld rows", fn, batch_index, n_rows);
+  plan.g.y = y_dev; plan.g.ldy = ldy;
+  plan.g.n_rows = n_rows;
+  MlpWork w;
+  TD_TRY(mlp_setup(h, &plan, num_files, file_offsets_host, so, &w));
+  TD_HIP(h, hipMemcpyAsync(w.params, params_dev, sizeof(float) * plan.g.n_params, hipMemcpyDeviceToDevice,
+                           h->stream));
+  SlabArgs sa;
+  HeadArgs ha;
+  mlp_fill(plan, w, &sa, &ha);
+  // the training step's launches: forward, head, and the update launch writing the gradient instead
+  TD_TRY(mlp_launch_rows(h, plan.g, 0, w.rows[0]));
+  sa.cur_epoch = 0; sa.cur_step = batch_index;
+  TD_TRY(mlp_launch_slab(h, plan, sa, false));
+  ha.epoch = 0; ha.step = batch_index;
+  TD_TRY(mlp_launch_head(h, plan, ha));
+  sa.cur_epoch = sa.cur_step = -1;
+  sa.prev_epoch = 0; sa.prev_step = batch_index;
+  sa.grad_out = grad_dev;
+  sa.stats_out = stats_dev;
+  TD_TRY(mlp_launch_slab(h, plan, sa, true));
+  return TD_OK;
+}
+
+int td_mlp_forward(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                   int c, int pre, int post, int input_offset, int d, const int* hidden_host, int num_hidden,
+                   const float* params_dev, float* out_dev, int64_t ldout) {
+  static const char* fn = "td_mlp_forward";
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, kFwdChunk, &plan));
+  TD_REQUIRE(h, params_dev && out_dev && ldout >= d, "%s: NULL argument or ldout too small", fn);
+  const long long n_rows = file_offsets_host[num_files];
+  if (n_rows == 0) return TD_OK;
+  // every row of x: output row file_offsets[f] + t is frame t of file f (as td_predict_fir)
+  plan.g.fwd = 1;
+  plan.g.n_rows = n_rows;
+  MlpWork w;
+  TD_TRY(mlp_setup(h, &plan, num_files, file_offsets_host, std::vector<long long>(), &w));
+  SlabArgs sa;
+  HeadArgs ha;
+  mlp_fill(plan, w, &sa, &ha);
+  sa.params = const_cast<float*>(params_dev);   // read only: no update phase
+  ha.params = params_dev;
+  ha.out = out_dev; ha.ldout = ldout; ha.backward = 0;
+  TD_TRY(mlp_launch_rows(h, plan.g, 0, w.rows[0]));
+  const int chunks = (int)td_ceil_div(n_rows, kFwdChunk);
+  for (int s = 0; s < chunks; ++s) {
+    sa.cur_epoch = 0; sa.cur_step = s;
+    TD_TRY(mlp_launch_slab(h, plan, sa, false));
+    ha.epoch = 0; ha.step = s;
+    TD_TRY(mlp_launch_head(h, plan, ha));
+  }
+  return TD_OK;
+}

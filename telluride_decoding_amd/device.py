@@ -910,3 +910,56 @@ def context_out(z, state, pre, post, mean, std, dtype='float32', handle=None):
                                int(post), float(mean), float(std), _ptr(o32), _ptr(o64), out.stride(0) if rows else
                                (pre + post + 1) * cs, _ptr(new_state)))
   return out, new_state
+
+
+# ---------------------------------------------------------------- fully connected regressor
+def _mlp_rows(file_offsets, input_offset, rows_used):
+  offs, offs_p = _lib.i64_array(file_offsets)
+  if rows_used is None:
+    return offs, offs_p, None, None, int(np.sum(np.maximum(np.diff(offs) - abs(int(input_offset)), 0)))
+  used, used_p = _lib.i64_array(rows_used)
+  return offs, offs_p, used, used_p, int(np.sum(used))
+
+
+def mlp_train(x, y, file_offsets, pre, post, hidden, params, state, batch_rows, epochs, lr, rho, eps,
+              input_offset=0, rows_used=None, shuffle_seed=None, handle=None):
+  """`epochs` epochs of minibatch RMSprop on the lagged view of x (td_mlp_train): params / state are the packed
+  float32 parameters and RMSprop accumulators (device, updated in place).  Returns the device float64 sums
+  [epochs, steps, 6] of every step's forward pass (sum p, y, p^2, y^2, p y of output 0; sum (p - y)^2)."""
+  h = handle or default_handle()
+  offs, offs_p, used, used_p, n = _mlp_rows(file_offsets, input_offset, rows_used)
+  steps = -(-n // int(batch_rows)) if batch_rows > 0 else 0
+  stats = h.empty((max(int(epochs), 0) * steps, 6), 'float64')
+  hid, hid_p = _i32_array(list(hidden) or [0])
+  seed = -1 if shuffle_seed is None else int(shuffle_seed)
+  h.check(h.lib.td_mlp_train(h.ptr, _ptr(x), x.stride(0), offs_p, len(offs) - 1, int(x.shape[1]), int(pre),
+                             int(post), int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p,
+                             len(hidden), int(batch_rows), int(epochs), _ptr(params), _ptr(state), float(lr),
+                             float(rho), float(eps), seed, _ptr(stats)))
+  return stats.reshape(max(int(epochs), 0), steps, 6)
+
+
+def mlp_grad(x, y, file_offsets, pre, post, hidden, params, batch_rows, batch_index, input_offset=0,
+             rows_used=None, handle=None):
+  """(gradient [P] float32, sums [6] float64) of minibatch `batch_index` at params, no update (td_mlp_grad)."""
+  h = handle or default_handle()
+  offs, offs_p, used, used_p, _ = _mlp_rows(file_offsets, input_offset, rows_used)
+  grad = h.empty((int(params.numel()),), 'float32')
+  stats = h.empty((6,), 'float64')
+  hid, hid_p = _i32_array(list(hidden) or [0])
+  h.check(h.lib.td_mlp_grad(h.ptr, _ptr(x), x.stride(0), offs_p, len(offs) - 1, int(x.shape[1]), int(pre),
+                            int(post), int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p,
+                            len(hidden), int(batch_rows), int(batch_index), _ptr(params), _ptr(grad), _ptr(stats)))
+  return grad, stats
+
+
+def mlp_forward(x, file_offsets, pre, post, hidden, d, params, input_offset=0, handle=None):
+  """The network on every row of x (td_mlp_forward): [rows, d]; row file_offsets[f] + t = frame t of file f."""
+  h = handle or default_handle()
+  offs, offs_p = _lib.i64_array(file_offsets)
+  out = h.empty((int(x.shape[0]), int(d)), 'float32')
+  hid, hid_p = _i32_array(list(hidden) or [0])
+  h.check(h.lib.td_mlp_forward(h.ptr, _ptr(x), x.stride(0), offs_p, len(offs) - 1, int(x.shape[1]), int(pre),
+                               int(post), int(input_offset), int(d), hid_p, len(hidden), _ptr(params), _ptr(out),
+                               out.stride(0)))
+  return out

@@ -78,7 +78,7 @@ class Decoder(object):
     """model_inputs / model_output of one of this package's estimators.  The reference fills them
     from the SavedModel's signature in load_decoding_model (:250-286, a TF file format: out of
     scope); a decoder built around a live estimator gets the same shapes from it."""
-    if isinstance(model, brain_model.BrainModelLinearRegression):
+    if isinstance(model, (brain_model.BrainModelLinearRegression, brain_model.BrainModelDNN)):
       self.set_model_signature({'input_1': (None, model._input_width)}, (None, model._output_width))
     elif hasattr(model, '_input1_width') and hasattr(model, 'output_dims'):
       self.set_model_signature({'input_1': (None, model._input1_width),
@@ -413,7 +413,7 @@ class LinearRegressionDecoder(Decoder):
   def _decode_dataset_device(self, data, h):
     model = self._decoding_model
     if not (isinstance(data, brain_data.Dataset) and
-            isinstance(model, brain_model.BrainModelLinearRegression)):
+            isinstance(model, (brain_model.BrainModelLinearRegression, brain_model.BrainModelDNN))):
       return None
     ds = data.resolved()
     if ds.num_batches() == 0:
