@@ -315,6 +315,9 @@ int td_set_solver(td_handle* h, int mode);
  *                     well as 0 / 1.  0 (default): the factorisation, flags 0 / 1 only.
  *   "narrow16"        1 (default): regression statistics of <= 16 channels x <= 16 lags are accumulated by
  *                     the one-kernel streaming form (float32 products); 0: the tiled kernels (A/B runs).
+ *   "targets_f16"     1 (default): y^T x~ of 33 .. 64 channels per tile (rows of whole 8-byte pairs, <= 32 lags)
+ *                     is multiplied as two float16 pieces under per-body scales (lagcov_targets_split_kernel);
+ *                     0: the float32 matrix instruction (lagcov_targets_mfma_kernel; A/B runs).
  * Unknown names are TD_ERR_INVALID. */
 int td_set_option(td_handle* h, const char* name, int64_t value);
 /* Bytes of device memory the handle's kernel scratch arena holds now (it grows to the largest request

@@ -2237,6 +2237,68 @@ __device__ __forceinline__ void tgt_stage_targets(const LagParams& p, const LagW
   }
 }
 
+// What both targets kernels end with: the channel maxima into the table, the four waves' float64
+// sums into wave 0 (LDS, fixed order), the strip's slab and column sums stored.  e_lo: first lag
+// of the window (0 without windows).
+template <bool kHalf>
+__device__ __forceinline__ void tgt_combine_store(const LagParams& p, double* __restrict__ part64,
+                                                  double* csum, unsigned* maxtab,
+                                                  double (&comb)[3][16][64], int slab_i, int e_lo, int c0,
+                                                  bool ok0, bool ok1, double (&big0)[16],
+                                                  double (&big1)[16], double cs0, double cs1, float mx0,
+                                                  float mx1) {
+  const int lane = threadIdx.x & 63, g = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // the two row parities of a channel sit in lanes n and n + 32
+  cs0 += __shfl_xor(cs0, 32, 64);
+  cs1 += __shfl_xor(cs1, 32, 64);
+  mx0 = fmaxf(mx0, __shfl_xor(mx0, 32, 64));
+  mx1 = fmaxf(mx1, __shfl_xor(mx1, 32, 64));
+  // (per WAVE here: four of them max into the row of their workgroup's shard)
+  if (maxtab && g == 0) {
+    unsigned* row = maxtab + (blockIdx.x % kChanShards) * 128;
+    if (ok0 && mx0 > 0.f) atomicMax(row + c0, __float_as_uint(mx0));
+    if (ok1 && mx1 > 0.f) atomicMax(row + c0 + 1, __float_as_uint(mx1));
+  }
+  // the four waves' sums -> wave 0 (fixed order), 16 registers at a time: big0, big1, column sums
+#pragma unroll
+  for (int round = 0; round < 3; ++round) {
+    if (kHalf && round == 1) continue;
+    __syncthreads();
+    if (wave > 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r)
+        comb[wave - 1][r][lane] = round == 0 ? big0[r] : round == 1 ? big1[r] : (r == 0 ? cs0 : r == 1 ? cs1 : 0.0);
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const double others = comb[0][r][lane] + (comb[1][r][lane] + comb[2][r][lane]);
+        if (round == 0) big0[r] += others;
+        else if (round == 1) big1[r] += others;
+        else if (r == 0) cs0 += others;
+        else if (r == 1) cs1 += others;
+      }
+    }
+  }
+  if (wave != 0) return;
+  // C/D map: col = lane & 31 (channel pair n), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (lag)
+  double* slab = part64 + (size_t)slab_i * p.e_pad * p.ca_pad * p.cb_pad;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int k = e_lo + (r & 3) + 8 * (r >> 2) + 4 * g;
+    if (k < p.e_count) {
+      slab[(size_t)k * p.ca_pad * p.cb_pad + c0] = big0[r];
+      if (!kHalf) slab[(size_t)k * p.ca_pad * p.cb_pad + c0 + 1] = big1[r];
+    }
+  }
+  if (g == 0 && csum) {
+    csum[(size_t)slab_i * p.cb_pad + c0] = cs0;
+    if (!kHalf) csum[(size_t)slab_i * p.cb_pad + c0 + 1] = cs1;
+  }
+}
+
 // The four waves of a workgroup share one strip of up to kTgtStrip rows and take its 32-row
 // bodies in turn (wave w: bodies w, w + 4, ...); every wave owns a private slab (index
 // 4 * strip + wave), so nothing is combined across waves here.
@@ -2386,54 +2448,272 @@ __global__ __launch_bounds__(kThreads) void lagcov_targets_mfma_kernel(LagParams
       if (!kHalf) { big1[r] += (double)acc1[r]; acc1[r] = 0.f; }
     }
   }
-  // the two row parities of a channel sit in lanes n and n + 32
-  cs0 += __shfl_xor(cs0, 32, 64);
-  cs1 += __shfl_xor(cs1, 32, 64);
-  mx0 = fmaxf(mx0, __shfl_xor(mx0, 32, 64));
-  mx1 = fmaxf(mx1, __shfl_xor(mx1, 32, 64));
-  // (per WAVE here: four of them max into the row of their workgroup's shard)
-  if (maxtab && g == 0) {
-    unsigned* row = maxtab + (blockIdx.x % kChanShards) * 128;
-    if (ok0 && mx0 > 0.f) atomicMax(row + c0, __float_as_uint(mx0));
-    if (ok1 && mx1 > 0.f) atomicMax(row + c0 + 1, __float_as_uint(mx1));
-  }
-  // the four waves' sums -> wave 0 (fixed order), 16 registers at a time: big0, big1, column sums
+  tgt_combine_store<kHalf>(p, part64, csum, maxtab, comb, slab_i, e_lo, c0, ok0, ok1, big0, big1, cs0, cs1,
+                           mx0, mx1);
+}
+
+// The 64-channel form on the float16 matrix pipe.  The float32 instruction of the kernel above takes
+// 128 matrix cycles for a pair of rows (two v_mfma_f32_32x32x2_f32): a CU cannot stream more than 16
+// bytes a cycle through it, and with the float64 flush it ran at 0.42 of that.  Here a body (32 rows
+// x 64 channels) is 12 v_mfma_f32_32x32x16_f16 (384 cycles against 2048): x and y as two float16
+// pieces each, three products (l h', h l', h h'; td_split2_f16).
+//
+// Scales.  The B operand gives a lane 8 rows of ONE channel and the result gives it the 16 lags of
+// that same channel, so the scale of x is private to the lane: a power of two per (body, channel)
+// that puts the body's largest magnitude into [2^14, 2^15), taken from the lane's 16 values and its
+// partner's (lane ^ 32).  No maximum over the whole stream is needed -- which is why this kernel can
+// measure the channel maxima and use the float16 pipe in the same pass.  y: one power of two per
+// strip, found while the strip is staged.  Both are divided out exactly when a body's 32-row chain
+// is added to the float64 sums.  A body whose channel holds a NaN or an infinity (or a strip whose
+// targets do) takes the factor NaN: the pieces are clamped and would lose it.
+//
+// Rows.  K index 8 g + i of k-step ks is stream row 32 b + 2 (8 ks + i) + g (g = lane >> 5): any
+// pairing of K with rows is right as long as A uses the same one, and this one makes a lane's 16
+// loads of a body the loads of the float32 kernel -- two whole 256-byte rows per wave instruction,
+// the same float32 partial column sums in the same order (csum, ysum and maxtab are bit-identical
+// to that kernel's).  The A operand is then 8 targets at stride 2 from y[row - lag]: the staged
+// pieces are kept de-interleaved by parity and, for each parity, at the two half-word alignments, so
+// that every lane reads its 8 float16 as four aligned words from an image that is fixed per lane.
+constexpr int kTgtBodiesMax = (kTgtStrip + 31 + 31) / 32;
+constexpr int kTgtImage = (32 + kTgtBodiesMax * 32) / 2 + 8;     // float16 per image of the targets
+
+// k with max 2^k in [2^14, 2^15); 0 for nothing seen and for a NaN / infinity.  (td_f16_scale_exp
+// stops at 2^126 because its scale is a float factor; this one is applied by v_ldexp_f32 and follows
+// a denormal maximum all the way.)
+__device__ __forceinline__ int tgt_scale_exp(unsigned max_bits) {
+  if (max_bits == 0 || td_chan_not_finite(max_bits)) return 0;
+  return 15 - __builtin_amdgcn_frexp_expf(__uint_as_float(max_bits));
+}
+
+// td_split2_f16 without its clamp (the body's own scale keeps every finite value below 2^15; what
+// is not finite poisons the body through its factor) and with the residual as ONE mixed-precision
+// fma per value (v_fma_mix_f32 reads the float16 piece in place).
+__device__ __forceinline__ void tgt_split2(float x0, float x1, unsigned& h, unsigned& l) {
+  h = td_pack_f16(x0, x1);
+  const td_f16x2 hv = __builtin_bit_cast(td_f16x2, h);
+  l = td_pack_f16(__builtin_fmaf((float)hv[0], -1.f, x0), __builtin_fmaf((float)hv[1], -1.f, x1));
+}
+
+// One body: x[s][t] = row 2 s + g of channel tile t (masked already), mb0 / mb1 = the float bits of
+// the largest magnitude among this lane's 16 values of either tile.  refill(s) is called when step
+// s's registers are free (the fast loop loads the wave's next body into them).
+template <class Refill>
+__device__ __forceinline__ void tgt_split_body(float (&x)[kTgtBody][2], unsigned mb0, unsigned mb1,
+                                               const unsigned* ah, const unsigned* al, int ky, bool y_bad,
+                                               double (&big0)[16], double (&big1)[16], Refill refill) {
+  mb0 = max(mb0, (unsigned)__shfl_xor((int)mb0, 32, 64));
+  mb1 = max(mb1, (unsigned)__shfl_xor((int)mb1, 32, 64));
+  const int k0 = tgt_scale_exp(mb0), k1 = tgt_scale_exp(mb1);
+  td_u32x4 h0[2], l0[2], h1[2], l1[2];
 #pragma unroll
-  for (int round = 0; round < 3; ++round) {
-    if (kHalf && round == 1) continue;
-    __syncthreads();
-    if (wave > 0) {
+  for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-      for (int r = 0; r < 16; ++r)
-        comb[wave - 1][r][lane] = round == 0 ? big0[r] : round == 1 ? big1[r] : (r == 0 ? cs0 : r == 1 ? cs1 : 0.0);
+    for (int j = 0; j < 4; ++j) {
+      const int s = 8 * ks + 2 * j;
+      unsigned h, l;
+      tgt_split2(ldexpf(x[s][0], k0), ldexpf(x[s + 1][0], k0), h, l);
+      h0[ks][j] = h; l0[ks][j] = l;
+      tgt_split2(ldexpf(x[s][1], k1), ldexpf(x[s + 1][1], k1), h, l);
+      h1[ks][j] = h; l1[ks][j] = l;
+      refill(s);
+      refill(s + 1);
     }
-    __syncthreads();
-    if (wave == 0) {
+  __builtin_amdgcn_sched_barrier(0);    // (the refills stay above the matrix instructions and the flush)
+  td_f32x16 acc0, acc1;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const double others = comb[0][r][lane] + (comb[1][r][lane] + comb[2][r][lane]);
-        if (round == 0) big0[r] += others;
-        else if (round == 1) big1[r] += others;
-        else if (r == 0) cs0 += others;
-        else if (r == 1) cs1 += others;
-      }
-    }
+  for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    const td_u32x4 yh = {ah[4 * ks], ah[4 * ks + 1], ah[4 * ks + 2], ah[4 * ks + 3]};
+    const td_u32x4 yl = {al[4 * ks], al[4 * ks + 1], al[4 * ks + 2], al[4 * ks + 3]};
+    acc0 = td_mfma_f16(yl, h0[ks], acc0);
+    acc1 = td_mfma_f16(yl, h1[ks], acc1);
+    acc0 = td_mfma_f16(yh, l0[ks], acc0);
+    acc1 = td_mfma_f16(yh, l1[ks], acc1);
+    acc0 = td_mfma_f16(yh, h0[ks], acc0);
+    acc1 = td_mfma_f16(yh, h1[ks], acc1);
   }
-  if (wave != 0) return;
-  // C/D map: col = lane & 31 (channel pair n), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (lag)
-  double* slab = part64 + (size_t)slab_i * p.e_pad * p.ca_pad * p.cb_pad;
+  // 2^-(k_x + k_y) as a float64 (|k_x + k_y| <= 328), or NaN
+  const double nan = __hiloint2double(0x7ff80000, 0);
+  const double f0 = (y_bad || td_chan_not_finite(mb0)) ? nan : __hiloint2double((1023 - k0 - ky) << 20, 0);
+  const double f1 = (y_bad || td_chan_not_finite(mb1)) ? nan : __hiloint2double((1023 - k1 - ky) << 20, 0);
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int k = e_lo + (r & 3) + 8 * (r >> 2) + 4 * g;
-    if (k < p.e_count) {
-      slab[(size_t)k * p.ca_pad * p.cb_pad + c0] = big0[r];
-      if (!kHalf) slab[(size_t)k * p.ca_pad * p.cb_pad + c0 + 1] = big1[r];
+    big0[r] = fma((double)acc0[r], f0, big0[r]);
+    big1[r] = fma((double)acc1[r], f1, big1[r]);
+  }
+}
+
+__global__ __launch_bounds__(kThreads, 2) void lagcov_targets_split_kernel(LagParams p,
+                                                                           double* __restrict__ part64,
+                                                                           double* csum, double* ysum,
+                                                                           unsigned* maxtab) {
+  constexpr int kPad = 32, kRowsBody = 2 * kTgtBody;
+  __shared__ float ya[kPad + kTgtBodiesMax * kRowsBody];
+  __shared__ __attribute__((aligned(16))) _Float16 yimg[2][2][2][kTgtImage];   // [piece h, l][parity of the target][alignment]
+  __shared__ double comb[3][16][64];
+  __shared__ unsigned ymax_w[kThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  // work item = (strip, 64-channel tile), one window of lags
+  const int item = (int)blockIdx.x;
+  if (item >= p.n_work * p.n_cbt) return;              // (the grid is padded to whole XCD rounds)
+  const int cbt = item % p.n_cbt;
+  const int wi = item / p.n_cbt;                       // strip = slab
+  const LagWork w = p.works[wi];
+  const TgtStrip ts = tgt_strip(p, w);
+  const int n = lane & 31, g = lane >> 5;
+  const int c0 = cbt * 64 + 2 * n;                     // this lane's channels: c0 (tile 0), c0 + 1
+  const bool ok0 = c0 < p.cb, ok1 = c0 + 1 < p.cb;
+  const int off0 = ok0 ? c0 : 0;
+  // A operand of (body b, k-step ks): targets y[32 b + 16 ks + 2 i + g - n], i < 8 = D[q][j + i] with
+  // kPad + 32 b + 16 ks + g - n = 2 j + q: words 8 b + 4 ks + 8 + ((g - n) >> 2) .. + 3 of the image
+  // (q, j & 1) -- the image and the offset are the lane's own
+  const int dg = g - n;
+  const unsigned* ah = reinterpret_cast<const unsigned*>(&yimg[0][dg & 1][(dg >> 1) & 1][0]) + 8 + (dg >> 2);
+  const unsigned* al = reinterpret_cast<const unsigned*>(&yimg[1][dg & 1][(dg >> 1) & 1][0]) + 8 + (dg >> 2);
+  // this wave's fast bodies: b0, b0 + 4, ... (fast bodies are a contiguous run of the strip)
+  int b0 = wave, nb = 0;
+  while (b0 < ts.n_body && !tgt_body_fast(ts, b0)) b0 += 4;
+  for (int b = b0; b < ts.n_body && tgt_body_fast(ts, b); b += 4) ++nb;
+
+  // x through a buffer descriptor: one per-lane offset and a scalar one per load (no 64-bit address
+  // arithmetic in the loop), and a load the compiler does not merge with the prologue's -- given
+  // plain pointers it turns "loaded at the end of a pass, used at the start of the next" into ONE
+  // load at the top of the loop, waited for on the spot: nothing in flight under the arithmetic.
+  // (The float32 kernel's ring gets the same treatment; its refills fly for a third of a pass.)
+  const long long rows_here = ts.last - ts.r_lo + 1;   // valid rows from ts.strip on
+  const long long rows_need = (long long)ts.n_body * kRowsBody;   // (fast bodies lie below n_body)
+  const unsigned buf_bytes =      // (no fast body: an empty descriptor, nothing is loaded)
+      nb > 0 ? (unsigned)(((rows_here < rows_need ? rows_here : rows_need) - 1) * ts.ldb32 + p.cb) * 4u : 0u;
+  const __amdgpu_buffer_rsrc_t rs =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(ts.strip), 0, buf_bytes, 0x00020000);
+  const unsigned voff = (unsigned)(g * ts.ldb32 + off0) * 4u;
+  // Two register images of a body, used in turn: while one is multiplied the other (the wave's next
+  // body) is on its way, and the first is refilled -- with the wave's next body but one -- as soon
+  // as its values are split.  A wave keeps 8 .. 16 KB in flight all the time; with one image the
+  // loads flew only under the matrix instructions and the flush, and the launch took the same time
+  // on 192 and on 256 CUs.  (A refill past the wave's last fast body loads that body again: every
+  // address stays inside the strip, the descriptor's range check is never what keeps a load in.)
+  float xa[kTgtBody][2], xb[kTgtBody][2];
+  auto load_step = [&](float (&xr)[kTgtBody][2], unsigned body_off, int s) {
+    const td_f32x2 v = __builtin_bit_cast(
+        td_f32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff, body_off + (unsigned)(s * 2 * ts.ldb32) * 4u, 0));
+    xr[s][0] = v[0]; xr[s][1] = v[1];
+  };
+  const int b_last = b0 + 4 * (nb - 1);
+  auto body_off = [&](int b) { return (unsigned)(((b < b_last ? b : b_last) * kRowsBody - ts.r_lo) * ts.ldb32) * 4u; };
+  // the first two bodies start their way here, under the staging of the targets
+  if (nb > 0) {
+    const unsigned bo0 = body_off(b0), bo1 = body_off(b0 + 4);
+#pragma unroll
+    for (int s = 0; s < kTgtBody; ++s) load_step(xa, bo0, s);
+#pragma unroll
+    for (int s = 0; s < kTgtBody; ++s) load_step(xb, bo1, s);
+  }
+  const int n_y = kPad + ts.n_body * kRowsBody;
+  tgt_stage_targets(p, w, ts.len, ts.n_body, kPad, ya, tid);
+  __syncthreads();
+  {
+    unsigned ym = 0u;
+    for (int t = tid; t < n_y; t += kThreads) ym = max(ym, __float_as_uint(ya[t]) & 0x7fffffffu);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ym = max(ym, (unsigned)__shfl_xor((int)ym, off, 64));
+    if (lane == 0) ymax_w[wave] = ym;
+  }
+  if (cbt == 0 && ysum && wave == 0) {
+    // the strip's column sum of y
+    double sy = 0.0;
+    for (int t = lane; t < ts.len; t += 64) sy += (double)ya[kPad + t];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sy += __shfl_down(sy, off, 64);
+    if (lane == 0) ysum[wi] = sy;
+  }
+  __syncthreads();
+  const unsigned ymax = max(max(ymax_w[0], ymax_w[1]), max(ymax_w[2], ymax_w[3]));
+  const bool y_bad = td_chan_not_finite(ymax);
+  const int ky = tgt_scale_exp(ymax);
+  // images: D[q][t] = y[2 t + q]; alignment 0 holds D[q][t] at t, alignment 1 holds D[q][t + 1]
+  for (int t = tid; t < n_y / 2; t += kThreads) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const float v = ldexpf(ya[2 * t + q], ky);
+      const _Float16 hv = (_Float16)v;
+      const _Float16 lv = (_Float16)(v - (float)hv);
+      yimg[0][q][0][t] = hv;
+      yimg[1][q][0][t] = lv;
+      if (t > 0) { yimg[0][q][1][t - 1] = hv; yimg[1][q][1][t - 1] = lv; }
     }
   }
-  if (g == 0 && csum) {
-    csum[(size_t)slab_i * p.cb_pad + c0] = cs0;
-    if (!kHalf) csum[(size_t)slab_i * p.cb_pad + c0 + 1] = cs1;
+  __syncthreads();
+
+  double big0[16], big1[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { big0[r] = 0.0; big1[r] = 0.0; }
+  double cs0 = 0.0, cs1 = 0.0;        // column sums of x over [u_begin, u_end)
+  float mx0 = 0.f, mx1 = 0.f;         // largest magnitudes of the two channels (every row streamed)
+  if (nb > 0) {
+    // body b from image xr, which then receives body b + 8
+    auto pass = [&](float (&xr)[kTgtBody][2], int b) {
+      const unsigned bo = body_off(b + 8);
+      float c0s = 0.f, c1s = 0.f, m0 = 0.f, m1 = 0.f;
+#pragma unroll
+      for (int s = 0; s < kTgtBody; ++s) {
+        c0s += xr[s][0]; c1s += xr[s][1];
+        m0 = fmaxf(m0, fabsf(xr[s][0])); m1 = fmaxf(m1, fabsf(xr[s][1]));
+      }
+      cs0 += (double)c0s;
+      cs1 += (double)c1s;
+      mx0 = fmaxf(mx0, m0); mx1 = fmaxf(mx1, m1);
+      // fmaxf passes over a NaN, the sum does not: a finite sum of the lane's 16 values says that all of
+      // them were finite.  (A sum of finite values that overflows poisons the body too -- the channel's
+      // column sum is then infinite in either kernel.  No branch here: with one in the loop the
+      // compiler sinks the refills below it, next to their use, and nothing is prefetched.)
+      const unsigned mb0 = fabsf(c0s) <= 3.402823466e38f ? __float_as_uint(m0) : 0x7fc00000u;
+      const unsigned mb1 = fabsf(c1s) <= 3.402823466e38f ? __float_as_uint(m1) : 0x7fc00000u;
+      tgt_split_body(xr, mb0, mb1, ah + 8 * b, al + 8 * b, ky, y_bad, big0, big1,
+                     [&](int s) { load_step(xr, bo, s); });
+    };
+    // (whole pairs in the loop, an odd body behind it: with "if (it + 1 < nb)" around the second pass
+    // the compiler's wait for the first image also waits for the refills of the second)
+    for (int it = 0; it + 1 < nb; it += 2) {
+      pass(xa, b0 + 4 * it);
+      pass(xb, b0 + 4 * it + 4);
+    }
+    if (nb & 1) pass(xa, b0 + 4 * (nb - 1));
   }
+  // The bodies left out above (first / last of a strip: rows outside the file or outside
+  // [u_begin, u_end), or a prefetch that would run past the file): clamped loads, the rows that do
+  // not exist set to zero, the same arithmetic.
+  for (int b = wave; b < ts.n_body; b += 4) {
+    if (tgt_body_fast(ts, b)) continue;
+    float xe[kTgtBody][2];
+#pragma unroll
+    for (int s = 0; s < kTgtBody; ++s) {
+      const int r = (b * kTgtBody + s) * 2 + g;
+      const int rc = min(max(r, ts.r_lo), ts.r_hi) - ts.r_lo;
+      const float2 v = *reinterpret_cast<const float2*>(ts.strip + rc * ts.ldb32 + off0);
+      xe[s][0] = v.x; xe[s][1] = v.y;
+    }
+    float c0s = 0.f, c1s = 0.f;
+    unsigned mb0 = 0u, mb1 = 0u;
+#pragma unroll
+    for (int s = 0; s < kTgtBody; ++s) {
+      const int r = (b * kTgtBody + s) * 2 + g;
+      const bool there = r >= ts.r_lo && (long long)r <= ts.last;
+      xe[s][0] = there ? xe[s][0] : 0.f;
+      xe[s][1] = there ? xe[s][1] : 0.f;
+      mx0 = fmaxf(mx0, fabsf(xe[s][0])); mx1 = fmaxf(mx1, fabsf(xe[s][1]));
+      mb0 = max(mb0, __float_as_uint(xe[s][0]) & 0x7fffffffu);
+      mb1 = max(mb1, __float_as_uint(xe[s][1]) & 0x7fffffffu);
+      const float in = (r >= ts.t_lo && r < ts.t_hi) ? 1.f : 0.f;
+      c0s = fmaf(in, xe[s][0], c0s); c1s = fmaf(in, xe[s][1], c1s);
+    }
+    cs0 += (double)c0s;
+    cs1 += (double)c1s;
+    tgt_split_body(xe, mb0, mb1, ah + 8 * b, al + 8 * b, ky, y_bad, big0, big1, [](int) {});
+  }
+  tgt_combine_store<false>(p, part64, csum, maxtab, comb, wi, 0, c0, ok0, ok1, big0, big1, cs0, cs1, mx0, mx1);
 }
 
 // per-file float64 column sums from the per-strip float32 ones: out[f][j] (+)= sum over the
@@ -3649,6 +3929,7 @@ int td_lagcov_targets_plan(td_handle* h, const float* y, int64_t ldy, int d, con
     if (d > 0 ? (e_count > 32 * 8 || (e_count > 32 && e_min < -31)) : -e_min > 31) return TD_OK;
   }
   plan->handled = true;
+  plan->lag_window = any_lag_window;
   const int n_segs = (int)segs.size();
   plan->d = d; plan->cb = cb; plan->e_count = e_count; plan->n_segs = n_segs;
   // Strips.  Without targets (column sums only: lagcov_wave_kernel) a strip is kWaveStrip rows
@@ -3665,6 +3946,16 @@ int td_lagcov_targets_plan(td_handle* h, const float* y, int64_t ldy, int d, con
   const int cus = h->cu_count > 0 ? h->cu_count : 256;
   long long t_strip = td_round_up(td_ceil_div(total > 0 ? total : 1, 4 * cus), 32);
   t_strip = t_strip < kTgtStripMin ? kTgtStripMin : (t_strip > kTgtStrip ? kTgtStrip : t_strip);
+  // ... and really no more than 4 per CU: every recording ends in a short strip of its own, which put the C2
+  // call on 192 CUs at 770 workgroups for 768 places -- the float16 kernel, two workgroups on a CU at a time,
+  // ran a third round for the last two
+  const long long n_tiles = td_ceil_div(cb, 64);
+  auto strips_at = [&](long long t) {
+    long long k = 0;
+    for (const LagSeg& sg : segs) k += sg.u_end > sg.u_begin ? td_ceil_div(sg.u_end - sg.u_begin, t) : 1;
+    return k;
+  };
+  while (t_strip < kTgtStrip && strips_at(t_strip) * n_tiles > 4LL * cus) t_strip += 32;
   // strips of the column-sum kernel (one WAVE each): <= kWaveStrip rows, shorter when the call is
   // short, down to 128 (a strip streams 31 .. 62 rows more than it sums) -- 200k rows in strips of
   // 512 were 391 waves on 1024 SIMDs: 52 us for a 55 MB read
@@ -3736,7 +4027,10 @@ int td_lagcov_targets_launch(td_handle* h, TargetsPlan* plan, void* scratch, dou
       double* part64 = reinterpret_cast<double*>(col);
       double* ysum = reinterpret_cast<double*>(col + plan->part_bytes);
       unsigned* maxtab = i == 0 ? out->maxtab : nullptr;        // (one column's pass is enough)
-      if (cb <= 32)
+      if (h->targets_f16 && !plan->lag_window && cb > 32 && vec2 && n_win == 1)
+        hipLaunchKernelGGL(lagcov_targets_split_kernel, grid, dim3(kThreads), 0, h->stream, pi, part64, csum,
+                           ysum, maxtab);
+      else if (cb <= 32)
         hipLaunchKernelGGL((lagcov_targets_mfma_kernel<false, true>), grid, dim3(kThreads), 0, h->stream,
                            pi, part64, csum, ysum, maxtab);
       else if (vec2)

@@ -1527,6 +1527,9 @@ int td_set_option(td_handle* h, const char* name, int64_t value) {
   } else if (!strcmp(name, "narrow16")) {
     TD_REQUIRE(h, value == 0 || value == 1, "td_set_option: narrow16 is 0 or 1");
     h->narrow16 = (int)value;
+  } else if (!strcmp(name, "targets_f16")) {
+    TD_REQUIRE(h, value == 0 || value == 1, "td_set_option: targets_f16 is 0 or 1");
+    h->targets_f16 = (int)value;
   } else if (!strcmp(name, "async_cg")) {
     TD_REQUIRE(h, value == 0 || value == 1, "td_set_option: async_cg is 0 or 1");
     h->async_cg = (int)value;

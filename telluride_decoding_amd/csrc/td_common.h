@@ -93,6 +93,7 @@ struct td_handle {
   long long cg_limit_ticks = -1;
   int async_cg = 0;             // "async_cg": td_ridge_solve_async may use the compact-statistics CG (flag 2 = gave up)
   int narrow16 = 1;             // "narrow16": <= 16 channels take the one-kernel streaming accumulate (0: the tiled kernels)
+  int targets_f16 = 1;          // "targets_f16": 33 .. 64 channels per tile take the float16 targets kernel (0: the float32 one)
   int last_solver = 0, last_iterations = 0, last_cg_status = 0;
   // Optional per-kernel hipEvent timing of the dominant kernel (td_profile_*):
   // event pairs recorded on h->stream around every lagcov MFMA launch.
@@ -480,6 +481,7 @@ struct TargetsPlan {
   size_t part_bytes = 0, cs_bytes = 0, ys_bytes = 0;   // per target column / once / per column
   size_t scratch_bytes = 0;
   bool handled = false;
+  bool lag_window = false;   // td_lagcov_column's plan: lags that need not contain 0 (float32 kernel only)
 };
 int td_lagcov_targets_plan(td_handle* h, const float* y, int64_t ldy, int d, const float* b,
                            int64_t ldb, int cb, const std::vector<LagSeg>& segs, int e_min,

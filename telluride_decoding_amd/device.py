@@ -82,7 +82,8 @@ class Handle(object):
     kernels) and 'async_cg' (1: ridge_solve_async may run conjugate gradients on the compact statistics; its
     flag can then be 2 = the solver gave up, W and b are NOT usable -- solve again with ridge_solve, as
     pipeline.FitPipeline does; 0 default: flags 0 / 1 only); 'cca_fused' (1 default: the dense stage of a small
-    CCA in one launch; 0: the chain of launches); 'reserve_workspace' (bytes: grow the workspace arena now)."""
+    CCA in one launch; 0: the chain of launches); 'reserve_workspace' (bytes: grow the workspace arena now);
+    'targets_f16' (1 default: y^T x~ of 33 .. 64 channels per tile on the float16 matrix pipe; 0: the float32 kernel)."""
     self.check(self.lib.td_set_option(self.ptr, name.encode(), int(value)))
 
   def scratch_bytes(self):
