@@ -709,6 +709,49 @@ int td_mlp_forward(td_handle* h, const float* x_dev, int64_t ldx, const int64_t*
                    int c, int pre, int post, int input_offset, int d, const int* hidden_host, int num_hidden,
                    const float* params_dev, float* out_dev, int64_t ldout);
 
+/* ------------------------------------------------------------------ match-mismatch classifier
+ * brain_model.BrainModelClassifier (reference brain_model.py:554-620): the td_mlp_* network and kernels with
+ *  - a second lagged view behind the first: input = [input_1 | input_2], input_2 column l*c2 + ch =
+ *    x2~[t + l - pre2, ch] of x2_dev (the files of file_offsets_host, row stride ldx2), zero outside the file;
+ *    a negative input_offset drops the leading rows of x2 as it does the target's.  W1 has K1 + K2 rows,
+ *    K1 = c (pre + 1 + post) first, then K2 = c2 (pre2 + 1 + post2);
+ *  - a sigmoid on the d output units and the binary cross-entropy, evaluated on the output logit z:
+ *    entry loss = max(z, 0) - z y + log1p(exp(-|z|)) (expf / log1pf), the loss its mean over rows x outputs,
+ *    dL/dz = (sigma(z) - y) / (rows d);
+ *  - Adam (Keras, no amsgrad): m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2, w -= lr_t m / (sqrt(v) + eps),
+ *    lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) computed per update in double on the host and rounded to float32
+ *    (as are 1 - b1 and 1 - b2); update i of the call has t = step0 + i + 1, step0 = the updates already
+ *    applied.  state_dev holds 2 P floats: m [P], then v [P] (zeros for a fresh optimizer).
+ * The six float64 sums per step are, for this family: slot 0 = the number of entries with
+ * (z > 0) == (y > 0.5) (binary accuracy at threshold 0.5 times rows x d), slot 5 = the sum of the entry
+ * losses, slots 1 - 4 = 0.
+ * Everything else -- the stream, rows_used_host, shuffle_seed, the packed parameter layout, working on copies
+ * and committing them once every launch is queued, determinism -- is as td_mlp_train.
+ * Limits: those of td_mlp_*, plus K1 + K2 <= 8192, c2 <= 128 (context-free second input: any c2 within K),
+ * pre2 + 1 + post2 <= 64.
+ *
+ * td_mlpc_train: update != 0 trains; update == 0 runs the forward passes only (params_dev is not written,
+ * state_dev may be NULL) and fills stats_dev -- what evaluate uses. */
+int td_mlpc_train(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
+                  const int64_t* file_offsets_host, int num_files, int c, int pre, int post, int c2, int pre2,
+                  int post2, int input_offset, const int64_t* rows_used_host, const float* y_dev, int64_t ldy, int d,
+                  const int* hidden_host, int num_hidden, int batch_rows, int epochs, float* params_dev,
+                  float* state_dev, double lr, double beta1, double beta2, double eps, int64_t step0, int update,
+                  int64_t shuffle_seed, double* stats_dev);
+/* The sums (stats_dev [6], as above) and the gradient of the mean binary cross-entropy in every parameter of
+ * minibatch batch_index of the unshuffled stream, without an update (as td_mlp_grad). */
+int td_mlpc_grad(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
+                 const int64_t* file_offsets_host, int num_files, int c, int pre, int post, int c2, int pre2,
+                 int post2, int input_offset, const int64_t* rows_used_host, const float* y_dev, int64_t ldy, int d,
+                 const int* hidden_host, int num_hidden, int batch_rows, int batch_index, const float* params_dev,
+                 float* grad_dev, double* stats_dev);
+/* Inference over whole recordings: out_dev [rows, d] receives the probabilities sigma(z) of every frame of
+ * every file (rows as td_mlp_forward). */
+int td_mlpc_forward(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
+                    const int64_t* file_offsets_host, int num_files, int c, int pre, int post, int c2, int pre2,
+                    int post2, int input_offset, int d, const int* hidden_host, int num_hidden,
+                    const float* params_dev, float* out_dev, int64_t ldout);
+
 #ifdef __cplusplus
 }
 #endif

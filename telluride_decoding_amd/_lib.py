@@ -138,6 +138,12 @@ SIGNATURES = {
     'td_mlp_grad': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i, _c.POINTER(_i), _i, _i, _i,
                     _vp, _vp, _vp],
     'td_mlp_forward': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i, _vp, _vp, _i64],
+    'td_mlpc_train': [_vp, _vp, _i64, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i,
+                      _c.POINTER(_i), _i, _i, _i, _vp, _vp, _d, _d, _d, _d, _i64, _i, _i64, _vp],
+    'td_mlpc_grad': [_vp, _vp, _i64, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i,
+                     _c.POINTER(_i), _i, _i, _i, _vp, _vp, _vp],
+    'td_mlpc_forward': [_vp, _vp, _i64, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i,
+                        _vp, _vp, _i64],
 }
 _RESTYPE = {'td_last_error': _c.c_char_p}
 

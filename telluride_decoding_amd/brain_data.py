@@ -48,6 +48,22 @@ def lag_view(x, pre, post):
   return out
 
 
+def mismatch_batch_randomization(x, x2, y, a, rng=None):
+  """Turns one minibatch into match-mismatch training data (reference brain_data.py:45-77): the even rows of
+  x2 stay where they are and become class 0 (matched), the odd rows are shuffled among themselves and become
+  class 1 (mismatched); the two halves are concatenated, matched first.  x and a are returned unchanged, y is
+  ignored and rewritten.  `rng`: a numpy Generator or a seed (the reference draws from tf.random.shuffle).
+  Like the reference, nothing in this package applies it to a dataset: its create_dataset maps it and throws
+  the mapped dataset away (brain_data.py:372)."""
+  del y
+  x2 = np.asarray(x2)
+  rng = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+  even, odd = x2[0::2, :], x2[1::2, :]
+  new_x2 = np.concatenate((even, odd[rng.permutation(odd.shape[0])]), axis=0)
+  new_y = np.concatenate((0 * even[:, :1], 1 + 0 * odd[:, :1]), axis=0)
+  return x, _t(new_x2), _t(new_y), a
+
+
 class Dataset(object):
   """Raw recordings + context spec; stands in for tf.data.Dataset.
 

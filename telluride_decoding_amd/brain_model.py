@@ -4,8 +4,9 @@ Mirrors the call surface of the reference's brain_model.py for the linear path:
 `pearson_correlation[_first/_second]` (reference brain_model.py:34-91),
 `BrainModelLinearRegression` (:306-381) and
 `calculate_linear_regressor_parameters_from_dataset` (:384-481); and the fully connected
-regressor `BrainModelDNN` (:486-549), trained on the GPU.  The classifier shell and the
-TensorBoard plumbing of that file are out of scope.
+regressor `BrainModelDNN` (:486-549) and the match-mismatch classifier `BrainModelClassifier`
+(:554-620), both trained on the GPU.  The Keras `BrainModel` base class and the TensorBoard
+plumbing of that file are out of scope.
 """
 import numpy as np
 
@@ -627,6 +628,239 @@ class BrainModelDNN(object):
     out = BrainModelLinearRegression.evaluate(self, dataset, **kwargs)
     out['mse'] = out['loss']
     return out
+
+
+class Adam(object):
+  """The Adam settings BrainModelClassifier trains with (Keras tf.keras.optimizers.Adam's arguments).  amsgrad is
+  not implemented (compile raises NotImplementedError)."""
+
+  def __init__(self, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, amsgrad=False):
+    self.learning_rate = float(learning_rate)
+    self.beta_1 = float(beta_1)
+    self.beta_2 = float(beta_2)
+    self.epsilon = float(epsilon)
+    self.amsgrad = bool(amsgrad)
+
+
+class BinaryCrossentropy(object):
+  """Stands in for tf.keras.losses.BinaryCrossentropy() in BrainModelClassifier.compile.  Only the defaults are
+  implemented: from_logits=False (the model's last op is the sigmoid) and no label smoothing."""
+
+  def __init__(self, from_logits=False, label_smoothing=0.0):
+    if from_logits or label_smoothing != 0.0:
+      raise NotImplementedError('BinaryCrossentropy(from_logits=%r, label_smoothing=%r) is not supported: only '
+                                'the defaults' % (from_logits, label_smoothing))
+    self.from_logits = False
+    self.label_smoothing = 0.0
+
+
+def classifier_history_from_sums(sums, rows, d):
+  """Keras' per-epoch history of the classifier from the sums of every step ([epochs, steps, 6]: slot 0 = the
+  correct entries at threshold 0.5, slot 5 = the sum of the entry losses) of steps of `rows` rows and d outputs:
+  each entry is the mean over the epoch's steps of the step's value."""
+  s = np.asarray(sums, np.float64)
+  n = float(rows) * d
+  return {'loss': [float(v) for v in np.mean(s[..., 5] / n, axis=-1)],
+          'accuracy': [float(v) for v in np.mean(s[..., 0] / n, axis=-1)]}
+
+
+class BrainModelClassifier(object):
+  """The match-mismatch classifier trained on the GPU (reference brain_model.py:554-620): the concatenation of
+  `input_1` and `input_2` through Dense layers of `num_hidden_list` ReLU units into a sigmoid output layer,
+  trained by minibatch Adam on the binary cross-entropy.  It decides directly whether a stretch of EEG
+  (input_1) and a stretch of audio (input_2) belong together (de Cheveigne et al. 2021).  Training, inference
+  and both lag gathers run in the HIP kernels of td_mlpc_* (csrc/mlp.hip, shared with BrainModelDNN); a fit is
+  one C call.
+
+  The contract, and where it may differ from the reference:
+    * the loss is evaluated on the output logit z in the stable form max(z, 0) - z y + log1p(exp(-|z|)), which
+      is what Keras computes when a sigmoid is the model's last op (it backtracks to the logits).  Keras'
+      clipped-probability form differs only where |z| >~ 16.  There is no TensorFlow to check this against;
+    * 'accuracy' is binary accuracy at threshold 0.5: an entry is correct when (z > 0) == (y > 0.5).  (A float32
+      sigma(z) rounds to exactly 0.5 for 0 < z <~ 2^-24, where Keras would say "not > 0.5": measure zero);
+    * Adam as Keras without amsgrad, lr_t = lr sqrt(1 - b2^t) / (1 - b1^t); t, m and v persist across fit
+      calls and compile() resets them;
+    * initial weights, fit(shuffle_seed=) and determinism exactly as BrainModelDNN (glorot_uniform with
+      fan_in = K1 + K2 drawn with numpy.random.default_rng(seed); in-order minibatches or the Feistel shuffle).
+  """
+
+  def __init__(self, input_dataset, num_hidden_list=None, *, seed=0, **kwargs):
+    kwargs.pop('tensorboard_dir', None)
+    del kwargs
+    if not _is_dataset(input_dataset):
+      raise TypeError('Dataset must be a tf.data.datasert, not a %s' % type(input_dataset))
+    if num_hidden_list is None:
+      num_hidden_list = []
+    if not isinstance(num_hidden_list, list):
+      raise TypeError('Num_hidden_list must be an list, not a %s.' % type(num_hidden_list))
+    self._input_width = int(input_dataset.element_spec[0]['input_1'].shape[-1])
+    self._input2_width = int(input_dataset.element_spec[0]['input_2'].shape[-1])
+    self._output_width = int(input_dataset.element_spec[1].shape[-1])
+    self.num_hidden_list = [int(u) for u in num_hidden_list]
+    self._widths = [self._input_width + self._input2_width] + self.num_hidden_list + [self._output_width]
+    rng = np.random.default_rng(seed)
+    weights = []
+    for fan_in, fan_out in zip(self._widths[:-1], self._widths[1:]):
+      limit = np.sqrt(6.0 / (fan_in + fan_out))
+      weights += [rng.uniform(-limit, limit, (fan_in, fan_out)).astype(np.float32),
+                  np.zeros((fan_out,), np.float32)]
+    self._host_weights = weights
+    self._params = None        # packed device parameters (the truth once on the device)
+    self._state = None         # Adam's m, then v, each in the parameters' layout
+    self._updates = 0          # Adam's t: updates applied since compile
+    self.optimizer = None
+    self.metrics_names = ['loss', 'accuracy']
+
+  # -- parameters: the packed layout and the accessors of BrainModelDNN (W1's rows: input_1's, then input_2's)
+  _shapes = BrainModelDNN._shapes
+  _device_params = BrainModelDNN._device_params
+  get_weights = BrainModelDNN.get_weights
+  set_weights = BrainModelDNN.set_weights
+  weight_matrices = BrainModelDNN.weight_matrices
+
+  # -- training ----------------------------------------------------------------
+  def compile(self, optimizer=Adam, loss=BinaryCrossentropy(), metrics='accuracy', learning_rate=1e-3, **kwargs):
+    """Adam (the class, an instance, 'adam', or any callable that returns an Adam when called with
+    learning_rate=, as the reference's `if callable(optimizer)`) on the binary cross-entropy (a
+    BinaryCrossentropy instance, 'binary_crossentropy', or a one-element list of either).  The history always
+    reports loss and accuracy.  Starts a fresh optimizer state (t = 0, m = v = 0)."""
+    del metrics, kwargs
+    if isinstance(optimizer, str):
+      if optimizer.lower() != 'adam':
+        raise NotImplementedError('Optimizer %r is not supported: only Adam' % optimizer)
+      optimizer = Adam(learning_rate=learning_rate)
+    elif not isinstance(optimizer, Adam) and callable(optimizer):
+      optimizer = optimizer(learning_rate=learning_rate)
+    if not isinstance(optimizer, Adam):
+      raise NotImplementedError('Optimizer %r is not supported: only brain_model.Adam' % (optimizer,))
+    if optimizer.amsgrad:
+      raise NotImplementedError('Adam with amsgrad=True is not supported')
+    losses = list(loss) if isinstance(loss, (list, tuple)) else [loss]
+    if len(losses) != 1 or not (isinstance(losses[0], BinaryCrossentropy) or losses[0] == 'binary_crossentropy'):
+      raise NotImplementedError('Loss %r is not supported: only binary cross-entropy' % (loss,))
+    self.optimizer = optimizer
+    self._state = None
+    self._updates = 0
+
+  def _check_limits(self, ds):
+    c, lags = ds.c1, ds.pre + 1 + ds.post
+    c2, lags2 = ds.c2, ds.pre2 + 1 + ds.post2
+    hidden = self.num_hidden_list
+    problems = []
+    if len(hidden) > DNN_MAX_HIDDEN:
+      problems.append('%d hidden layers (at most %d)' % (len(hidden), DNN_MAX_HIDDEN))
+    if any(u < 1 or u > DNN_MAX_UNITS for u in hidden):
+      problems.append('hidden layers of %s units (1 .. %d)' % (hidden, DNN_MAX_UNITS))
+    if not 1 <= self._output_width <= DNN_MAX_OUTPUTS:
+      problems.append('%d outputs (1 .. %d)' % (self._output_width, DNN_MAX_OUTPUTS))
+    if lags > DNN_MAX_LAGS or lags2 > DNN_MAX_LAGS:
+      problems.append('pre + 1 + post = %d / %d (at most %d)' % (lags, lags2, DNN_MAX_LAGS))
+    if (c > DNN_MAX_CHANNELS and lags > 1) or (c2 > DNN_MAX_CHANNELS and lags2 > 1):
+      problems.append('%d / %d channels with temporal context (at most %d)' % (c, c2, DNN_MAX_CHANNELS))
+    if c * lags + c2 * lags2 > DNN_MAX_INPUTS:
+      problems.append('%d lagged inputs (at most %d)' % (c * lags + c2 * lags2, DNN_MAX_INPUTS))
+    if not 1 <= ds.batch_size <= DNN_MAX_BATCH:
+      problems.append('batch of %d rows (1 .. %d)' % (ds.batch_size, DNN_MAX_BATCH))
+    if c * lags != self._input_width or c2 * lags2 != self._input2_width:
+      problems.append('input_1 / input_2 are %d / %d wide, the model %d / %d' % (
+          c * lags, c2 * lags2, self._input_width, self._input2_width))
+    if ds.d != self._output_width:
+      problems.append('the output is %d wide, the model %d' % (ds.d, self._output_width))
+    if problems:
+      raise ValueError('BrainModelClassifier: ' + '; '.join(problems))
+
+  def _as_dataset(self, data):
+    """A brain_data.Dataset as the kernels read it (mixup_batch resolved: input_2 then carries its context), or
+    an iterable of (dict, y) minibatches materialised once as a context-free Dataset of the same batch size."""
+    if _is_dataset(data):
+      return data.resolved()
+    if not hasattr(data, '__iter__'):
+      raise TypeError('BrainModelClassifier needs a brain_data.Dataset or an iterable of (dict, y) minibatches, '
+                      'not %s.' % type(data))
+    xs, x2s, ys = [], [], []
+    for feats, y in data:
+      x = np.asarray(_host(feats['input_1']), np.float32)
+      xs.append(x.reshape(x.shape[0], -1))
+      x2s.append(np.asarray(_host(feats['input_2']), np.float32).reshape(x.shape[0], -1))
+      ys.append(np.asarray(_host(y), np.float32).reshape(x.shape[0], -1))
+    if not xs or xs[0].shape[0] == 0:
+      raise ValueError('No minibatches in dataset')
+    x, x2, y = np.concatenate(xs), np.concatenate(x2s), np.concatenate(ys)
+    return brain_data.Dataset([(x, x2, y, np.zeros((x.shape[0], 1), np.float32))], xs[0].shape[0])
+
+  def _run(self, ds, h, epochs, update, shuffle_seed=None):
+    x, x2, y, offs = ds.device_arrays(h)
+    opt = self.optimizer or Adam()
+    return device.mlpc_train(x, x2, y, offs, ds.pre, ds.post, ds.pre2, ds.post2, self.num_hidden_list,
+                             self._device_params(h), self._state, ds.batch_size, epochs, opt.learning_rate,
+                             opt.beta_1, opt.beta_2, opt.epsilon, step0=self._updates, update=update,
+                             input_offset=ds.input_offset, rows_used=ds.rows_used(), shuffle_seed=shuffle_seed,
+                             handle=h)
+
+  def fit(self, input_dataset, *, epochs=1, shuffle_seed=None, **kwargs):
+    """Trains `epochs` epochs over the dataset's minibatches (reference brain_model.py:619-620 -> Keras fit).
+    Returns a History whose .history holds 'loss' and 'accuracy' per epoch: the mean over the epoch's steps of
+    each step's forward-pass value, before that step's update."""
+    del kwargs
+    if self.optimizer is None:
+      raise RuntimeError('You must compile your model before training/testing.')
+    if shuffle_seed is not None and not 0 <= int(shuffle_seed) < 2 ** 63:
+      raise ValueError('shuffle_seed must be in [0, 2^63), not %r' % (shuffle_seed,))
+    ds = self._as_dataset(input_dataset)
+    self._check_limits(ds)
+    epochs = int(epochs)
+    if ds.num_batches() == 0 or epochs <= 0:
+      return History({'loss': [], 'accuracy': []})
+    h = device.default_handle()
+    if self._state is None:
+      self._state = h.zeros((2 * int(self._device_params(h).numel()),))
+    sums = self._run(ds, h, epochs, True, shuffle_seed)
+    self._updates += epochs * ds.num_batches()
+    return History(classifier_history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width))
+
+  def evaluate(self, dataset, **kwargs):
+    """{'loss', 'accuracy'}: the means over the dataset's minibatches of the binary cross-entropy and the binary
+    accuracy, without an update (one pass of the training kernels with the update off)."""
+    del kwargs
+    ds = self._as_dataset(dataset)
+    self._check_limits(ds)
+    if ds.num_batches() == 0:
+      return {'loss': float('nan'), 'accuracy': float('nan')}
+    h = device.default_handle()
+    sums = self._run(ds, h, 1, False)
+    hist = classifier_history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width)
+    return {'loss': hist['loss'][0], 'accuracy': hist['accuracy'][0]}
+
+  # -- inference ---------------------------------------------------------------
+  def __call__(self, input_dataset):
+    return self.call(input_dataset)
+
+  def call(self, input_dataset):
+    """input_dataset: dict with already-lagged 'input_1' [B, K1] and 'input_2' [B, K2] -> probabilities [B, D]
+    (brain_model.py:611-617)."""
+    h = device.default_handle()
+    x = _as_2d_device(h, input_dataset['input_1'])
+    x2 = _as_2d_device(h, input_dataset['input_2'])
+    if int(x.shape[1]) != self._input_width or int(x2.shape[1]) != self._input2_width:
+      raise ValueError('input_1 / input_2 are %d / %d wide, the model %d / %d' % (
+          int(x.shape[1]), int(x2.shape[1]), self._input_width, self._input2_width))
+    out = device.mlpc_forward(x, x2, [0, int(x.shape[0])], 0, 0, 0, 0, self.num_hidden_list, self._output_width,
+                              self._device_params(h), handle=h)
+    return brain_data._t(out.cpu().numpy())
+
+  def predict_device(self, dataset, handle=None):
+    """Probabilities for every frame of every file, on the device: [rows, D] (row offs[f] + t = frame t of file
+    f's zipped streams, as BrainModelDNN.predict_device)."""
+    h = handle or device.default_handle()
+    ds = dataset.resolved()
+    self._check_limits(ds)
+    x, x2, _, offs = ds.device_arrays(h)
+    return device.mlpc_forward(x, x2, offs, ds.pre, ds.post, ds.pre2, ds.post2, self.num_hidden_list,
+                               self._output_width, self._device_params(h), input_offset=ds.input_offset, handle=h)
+
+  def predict(self, dataset):
+    pred = self.predict_device(dataset).cpu().numpy()
+    return rows_of_stream(pred, dataset.file_lengths(), dataset.rows_used())
 
 
 def _evaluate_minibatches(batches, h, predict, truth_from_y, metric_name='pearson_correlation_first'):

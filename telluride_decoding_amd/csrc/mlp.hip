@@ -1,6 +1,10 @@
 // Fully connected regressor (brain_model.BrainModelDNN; reference brain_model.py:486-549): training by
 // RMSprop, its gradients and inference, on the lagged view of the raw recordings -- the lag matrix is never
 // built.  Entry points td_mlp_train / td_mlp_grad / td_mlp_forward (include/td_hotpath.h).
+// The match-mismatch classifier (brain_model.BrainModelClassifier; reference :554-620) is the same kernels with
+// a second lagged view (x2) concatenated behind the first, a sigmoid output with binary cross-entropy, and Adam:
+// td_mlpc_train / td_mlpc_grad / td_mlpc_forward.  The flags below only select: neither family's arithmetic or
+// reduction order depends on the other's being there.
 //
 // A training step is three launches, queued from C without a host round trip:
 //   slab  one workgroup per slice of W1's rows (K = lags x channels, <= 64 rows a slice): first the update of
@@ -56,6 +60,13 @@ struct MlpGeom {
   int fwd;                        // 1: row i of chunk s is output row s * batch + i (inference)
   int shuffle;
   unsigned seed_lo, seed_hi;
+  // the second view (classifier): inputs k >= k1 are x2~[yrow + l - pre2, ch], l = (k - k1) / c2, zero outside
+  // the file's rows that survive the offset.  The regressor has k1 = k and never looks at it.
+  const float* x2;
+  long long ldx2;
+  int c2, pre2, k1;
+  int dxy;                        // dy - dx: x2's first row of a file = (x's first row) + dxy
+  int bce;                        // 1: sigmoid output, binary cross-entropy (0: linear output, mse)
 };
 
 // Where slot i of a pass reads: x rows [base, base + lags) clipped to [lo, hi), target row yrow (32-bit: the
@@ -127,12 +138,19 @@ __global__ void mlp_rows_kernel(MlpGeom g, int epoch, RowEntry* tab) {
   }
 }
 
-// lagged input k = l * c + ch of a row: x~[t + l - pre, ch], zero outside the file
-__device__ __forceinline__ float mlp_xt(const MlpGeom& g, long long base, long long lo, long long hi, int k) {
+// lagged input k = l * c + ch of a row: x~[t + l - pre, ch], zero outside the file; k >= k1: the second view
+__device__ __forceinline__ float mlp_xt(const MlpGeom& g, const RowInfo& ri, int k) {
+  if (k >= g.k1) {
+    const int k2 = k - g.k1, l = k2 / g.c2, ch = k2 - l * g.c2;
+    const long long row = ri.yrow - g.pre2 + l;
+    return (row >= ri.lo + g.dxy && row < ri.hi) ? g.x2[row * g.ldx2 + ch] : 0.f;
+  }
   const int l = k / g.c, ch = k - l * g.c;
-  const long long row = base + l;
-  return (row >= lo && row < hi) ? g.x[row * g.ldx + ch] : 0.f;
+  const long long row = ri.base + l;
+  return (row >= ri.lo && row < ri.hi) ? g.x[row * g.ldx + ch] : 0.f;
 }
+
+enum { kUpdRmsprop = 0, kUpdAdam = 1, kUpdNone = 2 };
 
 struct SlabArgs {
   MlpGeom g;
@@ -149,7 +167,9 @@ struct SlabArgs {
   int ks, nslices, n_head;
   int prev_epoch, prev_step;   // -1: no update
   int cur_epoch, cur_step;     // -1: no forward
-  float lr, rho, eps;
+  float lr, rho, eps;          // RMSprop; Adam: lr = this update's lr_t, rho = beta_1
+  float beta2, omb1, omb2;     // Adam: beta_2, 1 - beta_1, 1 - beta_2 (each rounded once from double)
+  int update;                  // kUpdRmsprop / kUpdAdam (state = m [P], then v [P]) / kUpdNone (the sums only)
 };
 
 __device__ __forceinline__ int mlp_rows_in_step(const MlpGeom& g, int step) {
@@ -164,6 +184,23 @@ __device__ __forceinline__ float mlp_rmsprop(float* p, float* v, float grad, flo
   *v = vn;
   *p = pn;
   return pn;
+}
+
+// Keras Adam without amsgrad: m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2, w -= lr_t m / (sqrt(v) + eps)
+__device__ __forceinline__ float mlp_adam(float* p, float* m, float* v, float grad, const SlabArgs& a) {
+  const float mn = a.rho * *m + a.omb1 * grad;
+  const float vn = a.beta2 * *v + a.omb2 * (grad * grad);
+  const float pn = *p - a.lr * mn / (sqrtf(vn) + a.eps);
+  *m = mn;
+  *v = vn;
+  *p = pn;
+  return pn;
+}
+
+// the update rule of the call on parameter `at`; returns the new value
+__device__ __forceinline__ float mlp_apply(const SlabArgs& a, long long at, float grad) {
+  if (a.update == kUpdAdam) return mlp_adam(&a.params[at], &a.state[at], &a.state[a.g.n_params + at], grad, a);
+  return mlp_rmsprop(&a.params[at], &a.state[at], grad, a.lr, a.rho, a.eps);
 }
 
 constexpr int kW1Groups = kSlabMaxKs * kMlpMaxWidth / 4 / kSlabThreads;   // (row, 4 columns) groups per thread
@@ -187,7 +224,7 @@ __device__ void mlp_w1_grad(const SlabArgs& a, int k0, int ksl, float (*acc)[4],
     __syncthreads();
     for (int i = tid; i < nr * ksl; i += kSlabThreads) {
       const int r = i / ksl, kk = i - r * ksl;
-      xs[r][kk] = mlp_xt(g, ri[r].base, ri[r].lo, ri[r].hi, k0 + kk);
+      xs[r][kk] = mlp_xt(g, ri[r], k0 + kk);
     }
     __syncthreads();
 #pragma unroll
@@ -220,11 +257,11 @@ __global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
     // the small layers' update and the loss sums of the previous step
     if (a.prev_step < 0) return;
     const int p = (wg - a.nslices) * kSlabThreads + tid;
-    if (p < g.n_small) {
+    if (p < g.n_small && a.update != kUpdNone) {
       float s = 0.f;
       for (int hw = 0; hw < a.n_head; ++hw) s += a.gpart[(long long)hw * g.n_small + p];
       if (a.grad_out) a.grad_out[g.small0 + p] = s;
-      else mlp_rmsprop(&a.params[g.small0 + p], &a.state[g.small0 + p], s, a.lr, a.rho, a.eps);
+      else mlp_apply(a, g.small0 + p, s);
     }
     if (wg == a.nslices && tid < 6 && a.stats_out) {
       double s = 0.0;
@@ -243,7 +280,7 @@ __global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
       const int kk = i / NJ, j = i - kk * NJ;
       ws[kk][j] = (kk < ksl && j < w1) ? w1p[(long long)(k0 + kk) * w1 + j] : 0.f;
     }
-  if (a.prev_step >= 0) {
+  if (a.prev_step >= 0 && a.update != kUpdNone) {
     float acc[kW1Groups][4];
 #pragma unroll
     for (int o = 0; o < kW1Groups; ++o) acc[o][0] = acc[o][1] = acc[o][2] = acc[o][3] = 0.f;
@@ -261,7 +298,7 @@ __global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
             if (a.grad_out) {
               a.grad_out[at] = acc[o][q];
             } else {
-              const float nw = mlp_rmsprop(&w1p[at], &a.state[at], acc[o][q], a.lr, a.rho, a.eps);
+              const float nw = mlp_apply(a, at, acc[o][q]);
               if (fwd) ws[kk][j0 + q] = nw;
             }
           }
@@ -280,7 +317,7 @@ __global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
     __syncthreads();
     for (int i = tid; i < nr * ksl; i += kSlabThreads) {
       const int r = i / ksl, kk = i - r * ksl;
-      xs[r][kk] = mlp_xt(g, ri[r].base, ri[r].lo, ri[r].hi, k0 + kk);
+      xs[r][kk] = mlp_xt(g, ri[r], k0 + kk);
     }
     __syncthreads();
     for (int t = tid; t < kSlabRowChunk * kQ; t += kSlabThreads) {
@@ -335,6 +372,16 @@ struct HeadArgs {
   int maxw;
 };
 
+// the classifier's output: sigma(z), and the binary cross-entropy of a logit in its stable form
+__device__ __forceinline__ float mlp_sigmoid(float z) {
+  const float e = expf(-fabsf(z));
+  return z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+}
+
+__device__ __forceinline__ float mlp_bce(float z, float y) {
+  return fmaxf(z, 0.f) - z * y + log1pf(expf(-fabsf(z)));
+}
+
 // z1 = b1 + partials, the small layers, the loss sums and the backward pass of 64 rows
 __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
   extern __shared__ float lds[];
@@ -377,14 +424,36 @@ __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
   const float* p = act + a.act_off[nl];
   if (a.out) {
     if (valid)
-      for (int o = 0; o < d; ++o) a.out[((long long)a.step * g.batch + r) * a.ldout + o] = p[o * kHeadRows + tid];
+      for (int o = 0; o < d; ++o) {
+        const float pv = p[o * kHeadRows + tid];
+        a.out[((long long)a.step * g.batch + r) * a.ldout + o] = g.bce ? mlp_sigmoid(pv) : pv;
+      }
     return;
   }
   for (int o = 0; o < d; ++o) yb[o * kHeadRows + tid] = valid ? g.y[yrow * g.ldy + o] : 0.f;
+  // classifier: p holds the logits; every row's entry losses go to the second dZ buffer (free until the
+  // backward pass, which starts behind a barrier)
+  float* lossb = dzb + a.maxw * kHeadRows;
+  if (g.bce)
+    for (int o = 0; o < d; ++o)
+      lossb[o * kHeadRows + tid] = valid ? mlp_bce(p[o * kHeadRows + tid], yb[o * kHeadRows + tid]) : 0.f;
   __syncthreads();
   // the six loss sums of these rows in float64, rows in order: sum p, y, p^2, y^2, p y of output column 0 and
   // sum (p - y)^2 over every column
-  if (tid < 6) {
+  // (classifier: slot 0 = the number of entries with (z > 0) == (y > 0.5), slot 5 = the sum of the entry
+  // losses, slots 1 - 4 = 0; rows in order, outputs in order within a row)
+  if (tid < 6 && g.bce) {
+    double s = 0.0;
+    const int left = rows - blockIdx.x * kHeadRows;
+    const int n = left < kHeadRows ? left : kHeadRows;
+    if (tid == 0 || tid == 5)
+      for (int rr = 0; rr < n; ++rr)
+        for (int o = 0; o < d; ++o) {
+          if (tid == 5) s += (double)lossb[o * kHeadRows + rr];
+          else if ((p[o * kHeadRows + rr] > 0.f) == (yb[o * kHeadRows + rr] > 0.5f)) s += 1.0;
+        }
+    a.spart[blockIdx.x * 6 + tid] = s;
+  } else if (tid < 6) {
     double s = 0.0;
     const int left = rows - blockIdx.x * kHeadRows;
     const int n = left < kHeadRows ? left : kHeadRows;
@@ -406,10 +475,13 @@ __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
   if (!a.backward) return;
   float* gp = a.gpart + (long long)blockIdx.x * g.n_small - g.small0;   // indexed by parameter offset
   // dL/dp of Keras 'mse' (the mean over rows x outputs): 2 (p - y) / (rows d)
-  const float scale = 2.f / ((float)rows * (float)d);
+  // (classifier: dL/dz of the mean binary cross-entropy through the sigmoid: (sigma(z) - y) / (rows d))
+  const float scale = (g.bce ? 1.f : 2.f) / ((float)rows * (float)d);
   int cur = 0;
-  for (int o = 0; o < d; ++o)
-    dzb[o * kHeadRows + tid] = valid ? (p[o * kHeadRows + tid] - yb[o * kHeadRows + tid]) * scale : 0.f;
+  for (int o = 0; o < d; ++o) {
+    const float pv = g.bce ? mlp_sigmoid(p[o * kHeadRows + tid]) : p[o * kHeadRows + tid];
+    dzb[o * kHeadRows + tid] = valid ? (pv - yb[o * kHeadRows + tid]) * scale : 0.f;
+  }
   for (int l = nl; l >= 1; --l) {
     __syncthreads();
     const int wo = g.w[l];
@@ -453,9 +525,16 @@ struct MlpPlan {
   int act_floats = 0, maxw = 0;
 };
 
+// the classifier's second input (NULL for the regressor)
+struct MlpView2 {
+  const float* x2;
+  int64_t ldx2;
+  int c2, pre2, post2;
+};
+
 int mlp_check_and_plan(td_handle* h, const char* fn, const float* x_dev, int64_t ldx, const int64_t* offs, int nf,
                        int c, int pre, int post, int input_offset, int d, const int* hidden, int num_hidden,
-                       int batch, MlpPlan* plan) {
+                       int batch, MlpPlan* plan, const MlpView2* v2 = nullptr) {
   if (!h) return td_fail(h, TD_ERR_INVALID, "%s: NULL handle", fn);
   TD_REQUIRE(h, x_dev && offs && nf >= 1, "%s: NULL argument or no files", fn);
   TD_REQUIRE(h, c >= 1 && pre >= 0 && post >= 0, "%s: bad sizes", fn);
@@ -465,6 +544,20 @@ int mlp_check_and_plan(td_handle* h, const char* fn, const float* x_dev, int64_t
              c, kMlpMaxC);
   TD_REQUIRE(h, c * lags <= kMlpMaxK, "%s: %lld lagged inputs exceed %d", fn, (long long)(c * lags), kMlpMaxK);
   TD_REQUIRE(h, ldx >= c, "%s: leading dimension of x too small", fn);
+  int64_t k2 = 0;
+  if (v2) {
+    TD_REQUIRE(h, v2->x2, "%s: NULL second input", fn);
+    TD_REQUIRE(h, v2->c2 >= 1 && v2->pre2 >= 0 && v2->post2 >= 0, "%s: bad sizes of the second input", fn);
+    const int64_t lags2 = (int64_t)v2->pre2 + 1 + v2->post2;
+    TD_REQUIRE(h, lags2 <= kMlpMaxLags, "%s: pre2 + 1 + post2 = %lld exceeds %d", fn, (long long)lags2, kMlpMaxLags);
+    TD_REQUIRE(h, v2->c2 <= kMlpMaxC || lags2 == 1,
+               "%s: %d channels of the second input exceed %d (only context-free input may be wider)", fn, v2->c2,
+               kMlpMaxC);
+    k2 = v2->c2 * lags2;
+    TD_REQUIRE(h, k2 <= kMlpMaxK && c * lags + k2 <= kMlpMaxK, "%s: %lld lagged inputs of both views exceed %d", fn,
+               (long long)(c * lags + k2), kMlpMaxK);
+    TD_REQUIRE(h, v2->ldx2 >= v2->c2, "%s: leading dimension of x2 too small", fn);
+  }
   TD_REQUIRE(h, num_hidden >= 0 && num_hidden <= kMlpMaxHidden, "%s: %d hidden layers (at most %d)", fn, num_hidden,
              kMlpMaxHidden);
   TD_REQUIRE(h, num_hidden == 0 || hidden, "%s: NULL hidden widths", fn);
@@ -479,9 +572,16 @@ int mlp_check_and_plan(td_handle* h, const char* fn, const float* x_dev, int64_t
   MlpGeom& g = plan->g;
   memset(&g, 0, sizeof(g));
   g.x = x_dev; g.ldx = ldx; g.nf = nf;
-  g.c = c; g.pre = pre; g.lags = (int)lags; g.k = (int)(c * lags);
+  g.c = c; g.pre = pre; g.lags = (int)lags; g.k = (int)(c * lags + k2);
+  g.k1 = (int)(c * lags);
+  g.c2 = 1;
+  if (v2) {
+    g.x2 = v2->x2; g.ldx2 = v2->ldx2; g.c2 = v2->c2; g.pre2 = v2->pre2;
+    g.bce = 1;
+  }
   g.dx = input_offset > 0 ? input_offset : 0;
   g.dy = input_offset < 0 ? -input_offset : 0;
+  g.dxy = g.dy - g.dx;
   g.nl = num_hidden + 1;
   g.w[0] = g.k;
   for (int i = 0; i < num_hidden; ++i) g.w[i + 1] = hidden[i];
@@ -558,7 +658,8 @@ int mlp_work(td_handle* h, const MlpPlan& plan, int nf, MlpWork* w) {
   const size_t n_sp = td_round_up((int64_t)plan.n_head * 6, 32);
   const size_t n_off = td_round_up((int64_t)nf + 1, 32);
   const size_t n_tab = td_round_up(g.n_rows, 64);
-  const size_t bytes = 4 * (2 * n_par + n_z + 2 * n_dz + n_gp) + 8 * (n_sp + 2 * n_off) + 2 * 16 * n_tab;
+  const size_t n_st = td_round_up(2 * (int64_t)g.n_params, 64);   // Adam keeps two accumulators per parameter
+  const size_t bytes = 4 * (n_par + n_st + n_z + 2 * n_dz + n_gp) + 8 * (n_sp + 2 * n_off) + 2 * 16 * n_tab;
   void* base = nullptr;
   TD_TRY(td_scratch(h, bytes, &base));
   char* p = static_cast<char*>(base);
@@ -568,7 +669,7 @@ int mlp_work(td_handle* h, const MlpPlan& plan, int nf, MlpWork* w) {
   w->file_offs = reinterpret_cast<long long*>(p); p += 8 * n_off;
   w->stream_offs = reinterpret_cast<long long*>(p); p += 8 * n_off;
   w->params = reinterpret_cast<float*>(p); p += 4 * n_par;
-  w->state = reinterpret_cast<float*>(p); p += 4 * n_par;
+  w->state = reinterpret_cast<float*>(p); p += 4 * n_st;
   w->zpart = reinterpret_cast<float*>(p); p += 4 * n_z;
   w->dz1 = reinterpret_cast<float*>(p); p += 4 * n_dz;
   w->z1 = reinterpret_cast<float*>(p); p += 4 * n_dz;
@@ -633,22 +734,34 @@ int mlp_launch_rows(td_handle* h, const MlpGeom& g, int epoch, RowEntry* tab) {
   return TD_OK;
 }
 
-}  // namespace
+// The optimizer of a training call.  RMSprop: lr, b1 = rho, eps.  Adam: lr_t of update t = step0 + 1, ... is
+// computed here in double and rounded once, as are 1 - beta_1 and 1 - beta_2.
+struct MlpOpt {
+  int update;
+  double lr, b1, b2, eps;
+  int64_t step0;
+};
 
-int td_mlp_train(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
-                 int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
-                 int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int epochs,
-                 float* params_dev, float* state_dev, float lr, float rho, float eps, int64_t shuffle_seed,
-                 double* stats_dev) {
-  static const char* fn = "td_mlp_train";
-  MlpPlan plan;
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, batch_rows, &plan));
+void mlp_set_update(SlabArgs* sa, const MlpOpt& opt, int64_t index) {
+  if (opt.update != kUpdAdam) return;
+  const double t = (double)(opt.step0 + index + 1);
+  sa->lr = (float)(opt.lr * std::sqrt(1.0 - std::pow(opt.b2, t)) / (1.0 - std::pow(opt.b1, t)));
+}
+
+// plan: checked, with its second view if any.  Queues every launch of the call.
+int mlp_train_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* file_offsets_host, int num_files,
+                  int input_offset, const int64_t* rows_used_host, const float* y_dev, int64_t ldy, int d,
+                  int batch_rows, int epochs, float* params_dev, float* state_dev, const MlpOpt& opt,
+                  int64_t shuffle_seed, double* stats_dev) {
+  const bool update = opt.update != kUpdNone;
   TD_REQUIRE(h, batch_rows <= kMlpMaxB, "%s: batch of %d rows exceeds %d", fn, batch_rows, kMlpMaxB);
-  TD_REQUIRE(h, y_dev && params_dev && state_dev && ldy >= d, "%s: NULL argument or ldy too small", fn);
+  TD_REQUIRE(h, y_dev && params_dev && (state_dev || !update) && ldy >= d, "%s: NULL argument or ldy too small", fn);
   TD_REQUIRE(h, epochs >= 0, "%s: negative epoch count", fn);
-  TD_REQUIRE(h, std::isfinite(lr) && std::isfinite(rho) && std::isfinite(eps), "%s: non-finite optimizer setting",
-             fn);
+  TD_REQUIRE(h, std::isfinite(opt.lr) && std::isfinite(opt.b1) && std::isfinite(opt.b2) && std::isfinite(opt.eps),
+             "%s: non-finite optimizer setting", fn);
+  if (opt.update == kUpdAdam)
+    TD_REQUIRE(h, opt.b1 >= 0.0 && opt.b1 < 1.0 && opt.b2 >= 0.0 && opt.b2 < 1.0 && opt.step0 >= 0,
+               "%s: Adam needs 0 <= beta < 1 and step0 >= 0", fn);
   std::vector<long long> so;
   TD_TRY(mlp_stream_offsets(h, fn, file_offsets_host, num_files, input_offset, rows_used_host, &so));
   const long long n_rows = so[num_files];
@@ -665,12 +778,16 @@ int td_mlp_train(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* f
   TD_TRY(mlp_setup(h, &plan, num_files, file_offsets_host, so, &w));
   // work on copies: the caller's parameters change only when every launch has been queued
   const size_t pbytes = sizeof(float) * plan.g.n_params;
+  const size_t sbytes = opt.update == kUpdAdam ? 2 * pbytes : pbytes;
   TD_HIP(h, hipMemcpyAsync(w.params, params_dev, pbytes, hipMemcpyDeviceToDevice, h->stream));
-  TD_HIP(h, hipMemcpyAsync(w.state, state_dev, pbytes, hipMemcpyDeviceToDevice, h->stream));
+  if (update) TD_HIP(h, hipMemcpyAsync(w.state, state_dev, sbytes, hipMemcpyDeviceToDevice, h->stream));
   SlabArgs sa;
   HeadArgs ha;
   mlp_fill(plan, w, &sa, &ha);
-  sa.lr = lr; sa.rho = rho; sa.eps = eps;
+  sa.update = opt.update;
+  sa.lr = (float)opt.lr; sa.rho = (float)opt.b1; sa.eps = (float)opt.eps;
+  sa.beta2 = (float)opt.b2; sa.omb1 = (float)(1.0 - opt.b1); sa.omb2 = (float)(1.0 - opt.b2);
+  ha.backward = update;
   int pe = -1, ps = -1;
   for (int e = 0; e < epochs; ++e) {
     // in order, one table serves every epoch; shuffled, epochs alternate between two (the first step of
@@ -683,6 +800,7 @@ int td_mlp_train(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* f
       if (s == 1) sa.prev_rows = tab;
       sa.prev_epoch = pe; sa.prev_step = ps; sa.cur_epoch = e; sa.cur_step = s;
       sa.stats_out = ps >= 0 ? stats_dev + 6 * ((long long)pe * steps + ps) : nullptr;
+      if (ps >= 0) mlp_set_update(&sa, opt, (int64_t)pe * steps + ps);
       TD_TRY(mlp_launch_slab(h, plan, sa, ps >= 0));
       ha.epoch = e; ha.step = s;
       TD_TRY(mlp_launch_head(h, plan, ha));
@@ -692,20 +810,18 @@ int td_mlp_train(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* f
   sa.prev_epoch = pe; sa.prev_step = ps; sa.cur_epoch = sa.cur_step = -1;
   sa.prev_rows = sa.cur_rows;
   sa.stats_out = stats_dev + 6 * ((long long)pe * steps + ps);
+  mlp_set_update(&sa, opt, (int64_t)pe * steps + ps);
   TD_TRY(mlp_launch_slab(h, plan, sa, true));
-  TD_HIP(h, hipMemcpyAsync(params_dev, w.params, pbytes, hipMemcpyDeviceToDevice, h->stream));
-  TD_HIP(h, hipMemcpyAsync(state_dev, w.state, pbytes, hipMemcpyDeviceToDevice, h->stream));
+  if (update) {
+    TD_HIP(h, hipMemcpyAsync(params_dev, w.params, pbytes, hipMemcpyDeviceToDevice, h->stream));
+    TD_HIP(h, hipMemcpyAsync(state_dev, w.state, sbytes, hipMemcpyDeviceToDevice, h->stream));
+  }
   return TD_OK;
 }
 
-int td_mlp_grad(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
-                int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
-                int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int batch_index,
-                const float* params_dev, float* grad_dev, double* stats_dev) {
-  static const char* fn = "td_mlp_grad";
-  MlpPlan plan;
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, batch_rows, &plan));
+int mlp_grad_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* file_offsets_host, int num_files,
+                 int input_offset, const int64_t* rows_used_host, const float* y_dev, int64_t ldy, int d,
+                 int batch_rows, int batch_index, const float* params_dev, float* grad_dev, double* stats_dev) {
   TD_REQUIRE(h, batch_rows <= kMlpMaxB, "%s: batch of %d rows exceeds %d", fn, batch_rows, kMlpMaxB);
   TD_REQUIRE(h, y_dev && params_dev && grad_dev && stats_dev && ldy >= d, "%s: NULL argument or ldy too small", fn);
   std::vector<long long> so;
@@ -736,13 +852,8 @@ int td_mlp_grad(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* fi
   return TD_OK;
 }
 
-int td_mlp_forward(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
-                   int c, int pre, int post, int input_offset, int d, const int* hidden_host, int num_hidden,
-                   const float* params_dev, float* out_dev, int64_t ldout) {
-  static const char* fn = "td_mlp_forward";
-  MlpPlan plan;
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, kFwdChunk, &plan));
+int mlp_forward_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* file_offsets_host, int num_files,
+                    int d, const float* params_dev, float* out_dev, int64_t ldout) {
   TD_REQUIRE(h, params_dev && out_dev && ldout >= d, "%s: NULL argument or ldout too small", fn);
   const long long n_rows = file_offsets_host[num_files];
   if (n_rows == 0) return TD_OK;
@@ -766,4 +877,84 @@ int td_mlp_forward(td_handle* h, const float* x_dev, int64_t ldx, const int64_t*
     TD_TRY(mlp_launch_head(h, plan, ha));
   }
   return TD_OK;
+}
+
+}  // namespace
+
+int td_mlp_train(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                 int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
+                 int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int epochs,
+                 float* params_dev, float* state_dev, float lr, float rho, float eps, int64_t shuffle_seed,
+                 double* stats_dev) {
+  static const char* fn = "td_mlp_train";
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, batch_rows, &plan));
+  const MlpOpt opt = {kUpdRmsprop, lr, rho, 0.0, eps, 0};
+  return mlp_train_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
+                       batch_rows, epochs, params_dev, state_dev, opt, shuffle_seed, stats_dev);
+}
+
+int td_mlp_grad(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
+                int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int batch_index,
+                const float* params_dev, float* grad_dev, double* stats_dev) {
+  static const char* fn = "td_mlp_grad";
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, batch_rows, &plan));
+  return mlp_grad_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
+                      batch_rows, batch_index, params_dev, grad_dev, stats_dev);
+}
+
+int td_mlp_forward(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                   int c, int pre, int post, int input_offset, int d, const int* hidden_host, int num_hidden,
+                   const float* params_dev, float* out_dev, int64_t ldout) {
+  static const char* fn = "td_mlp_forward";
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, kFwdChunk, &plan));
+  return mlp_forward_run(h, fn, plan, file_offsets_host, num_files, d, params_dev, out_dev, ldout);
+}
+
+int td_mlpc_train(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
+                  const int64_t* file_offsets_host, int num_files, int c, int pre, int post, int c2, int pre2,
+                  int post2, int input_offset, const int64_t* rows_used_host, const float* y_dev, int64_t ldy, int d,
+                  const int* hidden_host, int num_hidden, int batch_rows, int epochs, float* params_dev,
+                  float* state_dev, double lr, double beta1, double beta2, double eps, int64_t step0, int update,
+                  int64_t shuffle_seed, double* stats_dev) {
+  static const char* fn = "td_mlpc_train";
+  MlpPlan plan;
+  const MlpView2 v2 = {x2_dev, ldx2, c2, pre2, post2};
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, batch_rows, &plan, &v2));
+  const MlpOpt opt = {update ? kUpdAdam : kUpdNone, lr, beta1, beta2, eps, step0};
+  return mlp_train_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
+                       batch_rows, epochs, params_dev, state_dev, opt, shuffle_seed, stats_dev);
+}
+
+int td_mlpc_grad(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
+                 const int64_t* file_offsets_host, int num_files, int c, int pre, int post, int c2, int pre2,
+                 int post2, int input_offset, const int64_t* rows_used_host, const float* y_dev, int64_t ldy, int d,
+                 const int* hidden_host, int num_hidden, int batch_rows, int batch_index, const float* params_dev,
+                 float* grad_dev, double* stats_dev) {
+  static const char* fn = "td_mlpc_grad";
+  MlpPlan plan;
+  const MlpView2 v2 = {x2_dev, ldx2, c2, pre2, post2};
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, batch_rows, &plan, &v2));
+  return mlp_grad_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
+                      batch_rows, batch_index, params_dev, grad_dev, stats_dev);
+}
+
+int td_mlpc_forward(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
+                    const int64_t* file_offsets_host, int num_files, int c, int pre, int post, int c2, int pre2,
+                    int post2, int input_offset, int d, const int* hidden_host, int num_hidden,
+                    const float* params_dev, float* out_dev, int64_t ldout) {
+  static const char* fn = "td_mlpc_forward";
+  MlpPlan plan;
+  const MlpView2 v2 = {x2_dev, ldx2, c2, pre2, post2};
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, kFwdChunk, &plan, &v2));
+  return mlp_forward_run(h, fn, plan, file_offsets_host, num_files, d, params_dev, out_dev, ldout);
 }

@@ -964,3 +964,63 @@ def mlp_forward(x, file_offsets, pre, post, hidden, d, params, input_offset=0, h
                                int(post), int(input_offset), int(d), hid_p, len(hidden), _ptr(params), _ptr(out),
                                out.stride(0)))
   return out
+
+
+# ---------------------------------------------------------------- match-mismatch classifier
+def _check_x2(x, x2):
+  if int(x2.shape[0]) != int(x.shape[0]):
+    raise ValueError('x2 has %d rows, x %d: both inputs cover the same files' % (int(x2.shape[0]), int(x.shape[0])))
+
+
+def mlpc_train(x, x2, y, file_offsets, pre, post, pre2, post2, hidden, params, state, batch_rows, epochs,
+               lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-7, step0=0, update=True, input_offset=0, rows_used=None,
+               shuffle_seed=None, handle=None):
+  """`epochs` epochs of minibatch Adam on the binary cross-entropy of the sigmoid network over
+  [lagged x | lagged x2] (td_mlpc_train): params [P] and state [2 P] (Adam's m, then v) are updated in place;
+  `step0` = the updates already applied.  update=False runs the forward passes only (state may be None).
+  Returns the device float64 sums [epochs, steps, 6] of every step's forward pass: slot 0 = the correct
+  entries at threshold 0.5, slot 5 = the sum of the entry losses."""
+  h = handle or default_handle()
+  _check_x2(x, x2)
+  offs, offs_p, used, used_p, n = _mlp_rows(file_offsets, input_offset, rows_used)
+  steps = -(-n // int(batch_rows)) if batch_rows > 0 else 0
+  stats = h.empty((max(int(epochs), 0) * steps, 6), 'float64')
+  hid, hid_p = _i32_array(list(hidden) or [0])
+  seed = -1 if shuffle_seed is None else int(shuffle_seed)
+  h.check(h.lib.td_mlpc_train(h.ptr, _ptr(x), x.stride(0), _ptr(x2), x2.stride(0), offs_p, len(offs) - 1,
+                              int(x.shape[1]), int(pre), int(post), int(x2.shape[1]), int(pre2), int(post2),
+                              int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p, len(hidden),
+                              int(batch_rows), int(epochs), _ptr(params), _ptr(state), float(lr), float(beta1),
+                              float(beta2), float(eps), int(step0), 1 if update else 0, seed, _ptr(stats)))
+  return stats.reshape(max(int(epochs), 0), steps, 6)
+
+
+def mlpc_grad(x, x2, y, file_offsets, pre, post, pre2, post2, hidden, params, batch_rows, batch_index,
+              input_offset=0, rows_used=None, handle=None):
+  """(gradient [P] float32, sums [6] float64) of minibatch `batch_index` at params, no update (td_mlpc_grad)."""
+  h = handle or default_handle()
+  _check_x2(x, x2)
+  offs, offs_p, used, used_p, _ = _mlp_rows(file_offsets, input_offset, rows_used)
+  grad = h.empty((int(params.numel()),), 'float32')
+  stats = h.empty((6,), 'float64')
+  hid, hid_p = _i32_array(list(hidden) or [0])
+  h.check(h.lib.td_mlpc_grad(h.ptr, _ptr(x), x.stride(0), _ptr(x2), x2.stride(0), offs_p, len(offs) - 1,
+                             int(x.shape[1]), int(pre), int(post), int(x2.shape[1]), int(pre2), int(post2),
+                             int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p, len(hidden),
+                             int(batch_rows), int(batch_index), _ptr(params), _ptr(grad), _ptr(stats)))
+  return grad, stats
+
+
+def mlpc_forward(x, x2, file_offsets, pre, post, pre2, post2, hidden, d, params, input_offset=0, handle=None):
+  """The classifier's probabilities on every row of (x, x2) (td_mlpc_forward): [rows, d]; row
+  file_offsets[f] + t = frame t of file f."""
+  h = handle or default_handle()
+  _check_x2(x, x2)
+  offs, offs_p = _lib.i64_array(file_offsets)
+  out = h.empty((int(x.shape[0]), int(d)), 'float32')
+  hid, hid_p = _i32_array(list(hidden) or [0])
+  h.check(h.lib.td_mlpc_forward(h.ptr, _ptr(x), x.stride(0), _ptr(x2), x2.stride(0), offs_p, len(offs) - 1,
+                                int(x.shape[1]), int(pre), int(post), int(x2.shape[1]), int(pre2), int(post2),
+                                int(input_offset), int(d), hid_p, len(hidden), _ptr(params), _ptr(out),
+                                out.stride(0)))
+  return out
