@@ -703,6 +703,31 @@ int td_mlp_grad(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* fi
                 int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
                 int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int batch_index,
                 const float* params_dev, float* grad_dev, double* stats_dev);
+/* td_mlp_train / td_mlp_grad with the loss as an argument: loss 0 = mse (the same launches and bits as the
+ * entry points above), loss 1 = the Pearson correlation loss (reference brain_model.py:94-126 under Keras'
+ * mean over frames); any other value is TD_ERR_INVALID.  Loss 1, for a step of B rows, per output column o:
+ * pm = p - mean p, ym = y - mean y over the step's rows, Spp = sum pm^2, Syy = sum ym^2, Spy = sum pm ym,
+ * r_o = Spy / sqrt(Spp Syy),
+ *   L = -(1 / B) sum_o r_o,   dL/dp[i, o] = -(1 / B) (ym[i, o] / sqrt(Spp Syy) - r_o pm[i, o] / Spp).
+ * The five raw sums per column (sum p, y, p^2, y^2, p y of the float32 p and y) are float64, rows in order
+ * within a workgroup's 64 rows, the workgroups' partials in workgroup order; r_o and the coefficients are
+ * float64; each dL/dp entry is formed in float64 and rounded once to float32.  The backward pass and RMSprop
+ * are those of loss 0, except that the output layer's bias gradient -- identically zero, the loss does not
+ * change with a shift of p -- is written as exact 0.  Zero rule: a column with
+ * sum p^2 - (sum p)^2 / B <= 32 eps64 sum p^2 (or the same in y), that is, constant within the step, has
+ * r_o = 0 and a zero dL/dp column for that step (the reference divides by zero there).
+ * stats_dev holds SEVEN float64 per step with loss 1 ([epochs x steps][7]; td_mlp_grad_loss: [7]): the six
+ * sums above, then the step's L.  With loss 0 the stride stays six.  Loss 1 is four launches a step (the
+ * head runs twice: moments, then the backward pass); no launch waits on another workgroup. */
+int td_mlp_train_loss(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host,
+                      int num_files, int c, int pre, int post, int input_offset, const int64_t* rows_used_host,
+                      const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden,
+                      int batch_rows, int epochs, float* params_dev, float* state_dev, float lr, float rho,
+                      float eps, int64_t shuffle_seed, double* stats_dev, int loss);
+int td_mlp_grad_loss(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host,
+                     int num_files, int c, int pre, int post, int input_offset, const int64_t* rows_used_host,
+                     const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows,
+                     int batch_index, const float* params_dev, float* grad_dev, double* stats_dev, int loss);
 /* Inference over whole recordings: out_dev [rows, d] (row stride ldout), output row file_offsets[f] + t =
  * frame t of file f (as td_predict_fir); three launches per 4096 rows. */
 int td_mlp_forward(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,

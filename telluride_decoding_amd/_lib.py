@@ -137,6 +137,10 @@ SIGNATURES = {
                      _vp, _vp, _f, _f, _f, _i64, _vp],
     'td_mlp_grad': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i, _c.POINTER(_i), _i, _i, _i,
                     _vp, _vp, _vp],
+    'td_mlp_train_loss': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i, _c.POINTER(_i), _i, _i,
+                          _i, _vp, _vp, _f, _f, _f, _i64, _vp, _i],
+    'td_mlp_grad_loss': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i, _c.POINTER(_i), _i, _i,
+                         _i, _vp, _vp, _vp, _i],
     'td_mlp_forward': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i, _vp, _vp, _i64],
     'td_mlpc_train': [_vp, _vp, _i64, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i,
                       _c.POINTER(_i), _i, _i, _i, _vp, _vp, _d, _d, _d, _d, _i64, _i, _i64, _vp],

@@ -69,7 +69,8 @@ class PearsonCorrelationLoss(object):
   the frames is minus the sum of the columns' correlations.  (The reference subclasses
   tf.keras.losses.Loss; there is no Keras here, the arithmetic is the class.)  Column means and
   powers are the five float64 window sums of the HIP window-sums kernel over the whole block, the
-  per-frame products td_frame_scores."""
+  per-frame products td_frame_scores.  `BrainModelDNN.compile(loss=PearsonCorrelationLoss())`
+  trains on it (Keras' mean over the frames: L = -(1 / B) sum of the columns' correlations)."""
 
   def call(self, x, y):
     h = device.default_handle()
@@ -340,12 +341,18 @@ class BrainModelLinearRegression(object):
     (whole recordings in a few launches) or any iterable of (dict, y) minibatches whose 'input_1'
     already carries its context (one prediction + one window-sums launch per minibatch)."""
     del kwargs
+    return self._evaluate(dataset, False)
+
+  def _evaluate(self, dataset, _pearson_loss):
+    """evaluate; _pearson_loss (BrainModelDNN compiled for it): 'loss' is the Pearson correlation loss from
+    the same sums, and the mean squared error is returned as 'mse'."""
     h = device.default_handle()
     if not _is_dataset(dataset):
       if not hasattr(dataset, '__iter__'):
         raise TypeError('BrainModel.evaluate must be called with tf.data.Dataset object.')
       return _evaluate_minibatches(
-          dataset, h, lambda feats: self._predict_lagged_device(feats['input_1'], h), truth_from_y=True)
+          dataset, h, lambda feats: self._predict_lagged_device(feats['input_1'], h), truth_from_y=True,
+          pearson_loss=_pearson_loss)
     dataset = dataset.resolved()     # mixup_batch: evaluate against the shuffled output
     pred = self.predict_device(dataset, handle=h)
     _, _, y, offs = dataset.device_arrays(h)
@@ -355,12 +362,18 @@ class BrainModelLinearRegression(object):
     y_all, p_all = zipped_rows(dataset, h, y, pred)
     rows = int(p_all.shape[0])
     if rows == 0:
-      return {'loss': float('nan'), 'pearson_correlation_first': float('nan')}
+      out = {'loss': float('nan'), 'pearson_correlation_first': float('nan')}
+      if _pearson_loss:
+        out['mse'] = float('nan')
+      return out
     sums = device.window_sums(y_all, p_all, [0, rows], bsz, bsz, handle=h)
     r = device.window_scores(sums, bsz, mode=1, handle=h).cpu().numpy()
     s = sums.cpu().numpy()
     sq = s[:, :, 2] - 2 * s[:, :, 4] + s[:, :, 3]     # sum (y - p)^2 per batch and column
     loss = float(np.mean(np.sum(sq, axis=1) / (bsz * s.shape[1])))
+    if _pearson_loss:
+      return {'loss': float(np.mean(pearson_loss_from_sums(s, bsz))),
+              'pearson_correlation_first': float(np.mean(r[:, 0])), 'mse': loss}
     return {'loss': loss, 'pearson_correlation_first': float(np.mean(r[:, 0]))}
 
   def _predict_lagged_device(self, lagged, h):
@@ -400,11 +413,28 @@ def _host(a):
   return np.asarray(a)
 
 
+def pearson_loss_from_sums(s, rows):
+  """-(1 / rows) sum_o r_o from the five raw float64 sums of every output column (s [..., d, 5]: sum a, b, a^2,
+  b^2, a b over `rows` rows), with the zero rule of pearson_correlation per column: a constant column
+  contributes r_o = 0."""
+  s = np.asarray(s, np.float64)
+  n = float(rows)
+  va = s[..., 2] - s[..., 0] ** 2 / n
+  vb = s[..., 3] - s[..., 1] ** 2 / n
+  cov = s[..., 4] - s[..., 0] * s[..., 1] / n
+  tiny = 32 * np.finfo(np.float64).eps
+  zero = (va <= tiny * s[..., 2]) | (vb <= tiny * s[..., 3])
+  with np.errstate(invalid='ignore', divide='ignore'):
+    r = np.where(zero, 0.0, cov / np.sqrt(np.where(zero, 1.0, va * vb)))
+  return -np.sum(r, axis=-1) / n
+
+
 def history_from_sums(sums, rows, d):
   """Keras' per-epoch history from the six float64 sums of every step ([epochs, steps, 6]: sum p, y, p^2, y^2,
   p y of output 0, sum (p - y)^2) of steps of `rows` rows and d outputs: each entry is the mean over the
   epoch's steps of the step's value.  'pearson_correlation_first' is output 0's Pearson r with the zero rule of
-  pearson_correlation (a constant column gives 0)."""
+  pearson_correlation (a constant column gives 0).  With a seventh slot (a fit on the Pearson correlation
+  loss: the step's loss) 'loss' is the mean of that slot; 'mse' stays the mean squared error."""
   s = np.asarray(sums, np.float64)
   n = float(rows)
   mse = s[..., 5] / (n * d)
@@ -415,15 +445,16 @@ def history_from_sums(sums, rows, d):
   zero = (va <= tiny * s[..., 2]) | (vb <= tiny * s[..., 3])
   with np.errstate(invalid='ignore', divide='ignore'):
     r = np.where(zero, 0.0, cov / (np.sqrt(np.maximum(va, 0)) * np.sqrt(np.maximum(vb, 0))))
-  loss = [float(v) for v in np.mean(mse, axis=-1)]
+  mse = [float(v) for v in np.mean(mse, axis=-1)]
+  loss = [float(v) for v in np.mean(s[..., 6], axis=-1)] if s.shape[-1] == 7 else list(mse)
   return {'loss': loss, 'pearson_correlation_first': [float(v) for v in np.mean(r, axis=-1)],
-          'mse': list(loss)}
+          'mse': mse}
 
 
 class BrainModelDNN(object):
   """A fully connected regressor trained on the GPU (reference brain_model.py:486-549): Dense layers of
   `num_hidden_list` ReLU units and a linear output layer, trained by minibatch RMSprop on the mean squared
-  error.  Training, inference and the lag gather run in the HIP kernels of td_mlp_* (csrc/mlp.hip); a fit
+  error or on the Pearson correlation loss.  Training, inference and the lag gather run in the HIP kernels of td_mlp_* (csrc/mlp.hip); a fit
   is one C call, with no host round trip between steps.
 
   Differences from the reference, all documented:
@@ -434,7 +465,11 @@ class BrainModelDNN(object):
       seed, epoch e visits them in the order of a bijection computed on the device from (seed, e) (a 4-round
       Feistel network, cycle-walked; include/td_hotpath.h, td_mlp_train).  The reference shuffles frames
       through a 1000-frame tf.data buffer, which cannot be reproduced;
-    * the only optimizer is RMSprop without momentum, the only loss 'mse'.
+    * the only optimizer is RMSprop without momentum; the losses are 'mse' and the Pearson correlation loss;
+    * on the Pearson loss, a column that is constant within a minibatch (prediction or target) contributes
+      r = 0 and no gradient for that step, where the reference divides by zero and every weight becomes NaN;
+      and the output layer's bias gradient, identically zero in exact arithmetic, is exactly 0 rather than a
+      rounding residue: the output bias does not move, which cannot change any prediction's correlation.
   """
 
   def __init__(self, input_dataset, num_hidden_list=None, *, seed=0, **kwargs):
@@ -460,6 +495,7 @@ class BrainModelDNN(object):
     self._params = None        # packed device parameters (the truth once on the device)
     self._state = None         # RMSprop accumulators, same layout
     self.optimizer = None
+    self.loss = 'mse'          # 'mse' or 'pearson' (compile)
     self.metrics_names = ['loss', 'pearson_correlation_first', 'mse']
 
   # -- parameters ------------------------------------------------------------
@@ -506,8 +542,9 @@ class BrainModelDNN(object):
   def compile(self, optimizer=RMSprop, loss='mse', metrics=(pearson_correlation_first, 'mse'),
               learning_rate=1e-3, **kwargs):
     """RMSprop (the class, an instance, 'rmsprop', or any callable that returns an RMSprop when called with
-    learning_rate=, as the reference's `if callable(optimizer)`) on loss 'mse' (or ['mse']).  The history
-    always reports loss, pearson_correlation_first and mse.  Starts a fresh optimizer state."""
+    learning_rate=, as the reference's `if callable(optimizer)`) on loss 'mse', a PearsonCorrelationLoss
+    instance or 'pearson' (the reference's decoding.py flag value), or a one-element list of one of them.  The
+    history always reports loss, pearson_correlation_first and mse.  Starts a fresh optimizer state."""
     del metrics, kwargs
     if isinstance(optimizer, str):
       if optimizer.lower() != 'rmsprop':
@@ -522,9 +559,15 @@ class BrainModelDNN(object):
     if optimizer.centered:
       raise NotImplementedError('Centered RMSprop (centered=True) is not supported')
     losses = list(loss) if isinstance(loss, (list, tuple)) else [loss]
-    if len(losses) != 1 or losses[0] != 'mse':
-      raise NotImplementedError('Loss %r is not supported: only mse' % (loss,))
+    if len(losses) == 1 and isinstance(losses[0], str) and losses[0] == 'mse':
+      compiled = 'mse'
+    elif len(losses) == 1 and (isinstance(losses[0], PearsonCorrelationLoss) or
+                               (isinstance(losses[0], str) and losses[0] == 'pearson')):
+      compiled = 'pearson'
+    else:
+      raise NotImplementedError('Loss %r is not supported: only mse and the Pearson correlation loss' % (loss,))
     self.optimizer = optimizer
+    self.loss = compiled
     self._state = None
 
   def _check_limits(self, ds):
@@ -572,7 +615,8 @@ class BrainModelDNN(object):
   def fit(self, input_dataset, *, epochs=1, shuffle_seed=None, **kwargs):
     """Trains `epochs` epochs over the dataset's minibatches (reference brain_model.py:548-549 -> Keras fit).
     Returns a History whose .history holds 'loss', 'pearson_correlation_first' and 'mse' per epoch: the mean
-    over the epoch's steps of each step's forward-pass value, before that step's update."""
+    over the epoch's steps of each step's forward-pass value, before that step's update.  'loss' is the loss
+    the model was compiled for; 'mse' is reported either way."""
     del kwargs
     if self.optimizer is None:
       raise RuntimeError('You must compile your model before training/testing.')
@@ -592,7 +636,7 @@ class BrainModelDNN(object):
     sums = device.mlp_train(x, y, offs, ds.pre, ds.post, self.num_hidden_list, params, self._state,
                             ds.batch_size, epochs, opt.learning_rate, opt.rho, opt.epsilon,
                             input_offset=ds.input_offset, rows_used=ds.rows_used(), shuffle_seed=shuffle_seed,
-                            handle=h)
+                            handle=h, loss=self.loss)
     return History(history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width))
 
   # -- inference ---------------------------------------------------------------
@@ -624,9 +668,11 @@ class BrainModelDNN(object):
 
   def evaluate(self, dataset, **kwargs):
     """{'loss', 'pearson_correlation_first', 'mse'}: means over minibatches, as Keras evaluate (the window-sums
-    route of BrainModelLinearRegression.evaluate)."""
-    out = BrainModelLinearRegression.evaluate(self, dataset, **kwargs)
-    out['mse'] = out['loss']
+    route of BrainModelLinearRegression.evaluate).  'loss' is the loss the model was compiled for: the mean
+    squared error, or the mean over minibatches of -(1 / B) sum_o r_o."""
+    del kwargs
+    out = BrainModelLinearRegression._evaluate(self, dataset, self.loss == 'pearson')
+    out.setdefault('mse', out['loss'])
     return out
 
 
@@ -863,14 +909,16 @@ class BrainModelClassifier(object):
     return rows_of_stream(pred, dataset.file_lengths(), dataset.rows_used())
 
 
-def _evaluate_minibatches(batches, h, predict, truth_from_y, metric_name='pearson_correlation_first'):
+def _evaluate_minibatches(batches, h, predict, truth_from_y, metric_name='pearson_correlation_first',
+                          pearson_loss=False):
   """Keras-style evaluation of an iterable of (dict, y) minibatches (reference
   brain_model.py:206-253): per minibatch the mean squared error and the first column's Pearson
   correlation (with the reference's zero rule, :72-79) of truth against prediction, both from ONE
   window-sums launch (the minibatch is the window); the unweighted mean over minibatches.
   truth_from_y False: the prediction carries both halves (CCA: correlate them, cca.py:61-68) and
-  the loss is the metric itself (cca.py:196-199)."""
-  losses, metrics = [], []
+  the loss is the metric itself (cca.py:196-199).  pearson_loss (with truth_from_y): 'loss' is the mean of the
+  minibatches' Pearson correlation loss and the mean squared error comes back as 'mse'."""
+  losses, metrics, plosses = [], [], []
   for feats, y in batches:
     pred = predict(feats)
     rows = int(pred.shape[0])
@@ -887,8 +935,14 @@ def _evaluate_minibatches(batches, h, predict, truth_from_y, metric_name='pearso
     if truth_from_y:
       s = sums.cpu().numpy()[0]
       losses.append(float(np.sum(s[:, 2] - 2 * s[:, 4] + s[:, 3]) / (rows * s.shape[0])))
+      if pearson_loss:
+        plosses.append(float(pearson_loss_from_sums(s, rows)))
     else:
       losses.append(float(r[0]))
+  if pearson_loss:
+    if not metrics:
+      return {'loss': float('nan'), metric_name: float('nan'), 'mse': float('nan')}
+    return {'loss': float(np.mean(plosses)), metric_name: float(np.mean(metrics)), 'mse': float(np.mean(losses))}
   if not metrics:
     return {'loss': float('nan'), metric_name: float('nan')}
   return {'loss': float(np.mean(losses)), metric_name: float(np.mean(metrics))}

@@ -5,6 +5,9 @@
 // a second lagged view (x2) concatenated behind the first, a sigmoid output with binary cross-entropy, and Adam:
 // td_mlpc_train / td_mlpc_grad / td_mlpc_forward.  The flags below only select: neither family's arithmetic or
 // reduction order depends on the other's being there.
+// The regressor also trains on the Pearson correlation loss (td_mlp_train_loss / td_mlp_grad_loss, loss 1):
+// L = -(1 / B) sum_o r_o over the step's B rows.  dL/dp of a row needs the step's moments of every output
+// column, so the head runs as two launches (below).
 //
 // A training step is three launches, queued from C without a host round trip:
 //   slab  one workgroup per slice of W1's rows (K = lags x channels, <= 64 rows a slice): first the update of
@@ -20,6 +23,12 @@
 // Every reduction runs in a fixed order and there are no atomics: two runs are bitwise identical.  A step's
 // update is applied by the next step's slab launch, so every layer is updated after the full backward pass
 // (Keras); one slab launch after the last step applies the last update.
+// With the Pearson loss the head is two launches of the same kernel (four launches a step):
+//   head<1>  the forward of its 64 rows, the six history sums, and the workgroup's five float64 raw moments
+//            (sum p, y, p^2, y^2, p y) of every output column over its valid rows, rows in order;
+//   head<2>  every workgroup sums the <= 32 partial moments in workgroup order, forms r_o and the two
+//            coefficients of dL/dp per column in float64, recomputes its rows' forward (the same code on the
+//            same inputs: the same bits) and runs the backward pass.  No workgroup waits for another.
 #include "td_common.h"
 
 #include <cmath>
@@ -67,6 +76,7 @@ struct MlpGeom {
   int c2, pre2, k1;
   int dxy;                        // dy - dx: x2's first row of a file = (x's first row) + dxy
   int bce;                        // 1: sigmoid output, binary cross-entropy (0: linear output, mse)
+  int pearson;                    // 1: linear output, the Pearson correlation loss (regressor only)
 };
 
 // Where slot i of a pass reads: x rows [base, base + lags) clipped to [lo, hi), target row yrow (32-bit: the
@@ -161,7 +171,8 @@ struct SlabArgs {
   const float* dz1;       // [w1][batch] of the previous step
   const float* gpart;     // [n_head][n_small]
   const double* spart;    // [n_head][6]
-  double* stats_out;      // six sums of the previous step (may be null)
+  const double* lstat;    // Pearson: the previous step's loss L (written by head<2>)
+  double* stats_out;      // six sums of the previous step (may be null); Pearson: seven, the last one L
   const RowEntry* prev_rows;   // row tables of the previous / current step's epoch
   const RowEntry* cur_rows;
   int ks, nslices, n_head;
@@ -268,6 +279,7 @@ __global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
       for (int hw = 0; hw < a.n_head; ++hw) s += a.spart[hw * 6 + tid];
       a.stats_out[tid] = s;
     }
+    if (wg == a.nslices && tid == 6 && a.stats_out && g.pearson) a.stats_out[6] = a.lstat[0];
     return;
   }
   const int k0 = wg * a.ks;
@@ -363,6 +375,8 @@ struct HeadArgs {
   float* dz1;       // [w1][batch]
   float* gpart;     // [n_head][n_small]
   double* spart;    // [n_head][6]
+  double* mpart;    // Pearson: [n_head][d][5] raw moments of the workgroups' valid rows
+  double* lstat;    // Pearson: the step's loss
   float* out;       // inference: [rows, d] (row stride ldout)
   long long ldout;
   const RowEntry* rows_tab;
@@ -382,7 +396,10 @@ __device__ __forceinline__ float mlp_bce(float z, float y) {
   return fmaxf(z, 0.f) - z * y + log1pf(expf(-fabsf(z)));
 }
 
-// z1 = b1 + partials, the small layers, the loss sums and the backward pass of 64 rows
+// z1 = b1 + partials, the small layers, the loss sums and the backward pass of 64 rows.
+// PP 0: all of it in one launch (mse, bce).  The Pearson loss: PP 1 = forward, sums and the partial moments;
+// PP 2 = forward again, the moments' reduction, dL/dp and the backward pass.
+template <int PP>
 __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
   extern __shared__ float lds[];
   const MlpGeom& g = a.g;
@@ -442,7 +459,9 @@ __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
   // sum (p - y)^2 over every column
   // (classifier: slot 0 = the number of entries with (z > 0) == (y > 0.5), slot 5 = the sum of the entry
   // losses, slots 1 - 4 = 0; rows in order, outputs in order within a row)
-  if (tid < 6 && g.bce) {
+  if constexpr (PP == 2) {
+    // (written by the first pass)
+  } else if (tid < 6 && g.bce) {
     double s = 0.0;
     const int left = rows - blockIdx.x * kHeadRows;
     const int n = left < kHeadRows ? left : kHeadRows;
@@ -472,15 +491,72 @@ __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
     }
     a.spart[blockIdx.x * 6 + tid] = s;
   }
+  if constexpr (PP == 1) {
+    // the raw moments of every output column over this workgroup's valid rows (none: zeros), rows in order
+    if (tid < 5 * d) {
+      const int o = tid / 5, q = tid - o * 5;
+      const int left = rows - blockIdx.x * kHeadRows;
+      const int n = left < kHeadRows ? left : kHeadRows;
+      double s = 0.0;
+      for (int rr = 0; rr < n; ++rr) {
+        const double pv = p[o * kHeadRows + rr], yv = yb[o * kHeadRows + rr];
+        s += q == 0 ? pv : q == 1 ? yv : q == 2 ? pv * pv : q == 3 ? yv * yv : pv * yv;
+      }
+      a.mpart[((long long)blockIdx.x * d + o) * 5 + q] = s;
+    }
+    return;
+  }
   if (!a.backward) return;
   float* gp = a.gpart + (long long)blockIdx.x * g.n_small - g.small0;   // indexed by parameter offset
   // dL/dp of Keras 'mse' (the mean over rows x outputs): 2 (p - y) / (rows d)
   // (classifier: dL/dz of the mean binary cross-entropy through the sigmoid: (sigma(z) - y) / (rows d))
   const float scale = (g.bce ? 1.f : 2.f) / ((float)rows * (float)d);
   int cur = 0;
-  for (int o = 0; o < d; ++o) {
-    const float pv = g.bce ? mlp_sigmoid(p[o * kHeadRows + tid]) : p[o * kHeadRows + tid];
-    dzb[o * kHeadRows + tid] = valid ? (pv - yb[o * kHeadRows + tid]) * scale : 0.f;
+  if constexpr (PP == 2) {
+    // L = -(1 / B) sum_o r_o with r_o = Spy / sqrt(Spp Syy) of the step's B rows, so
+    // dL/dp[i, o] = -(1 / B) ((y - mean y) / sqrt(Spp Syy) - r_o (p - mean p) / Spp): the coefficients in
+    // float64 from the step's raw moments (the workgroups' partials summed in workgroup order), each entry
+    // formed in float64 from the float32 p and y and rounded once.  A column that is constant within the step
+    // (Spp or Syy within 32 eps of its raw sum of squares: the zero rule of pearson_correlation) has r_o = 0
+    // and a zero dZ column.
+    __shared__ double mom[kMlpMaxD * 5];
+    __shared__ double coef[kMlpMaxD][5];   // mean p, mean y, the coefficients of (y - mean y) and (p - mean p), r
+    if (tid < 5 * d) {
+      double s = 0.0;
+      for (int hw = 0; hw < (int)gridDim.x; ++hw) s += a.mpart[(long long)hw * 5 * d + tid];
+      mom[tid] = s;
+    }
+    __syncthreads();
+    if (tid < d) {
+      const double* m = mom + 5 * tid;
+      const double n = (double)rows;
+      const double spp = m[2] - m[0] * m[0] / n, syy = m[3] - m[1] * m[1] / n, spy = m[4] - m[0] * m[1] / n;
+      const double tiny = 32.0 * 2.220446049250313e-16;
+      double r = 0.0, cy = 0.0, cp = 0.0;
+      if (!(spp <= tiny * m[2] || syy <= tiny * m[3])) {
+        const double q = sqrt(spp * syy);
+        r = spy / q;
+        cy = -1.0 / (n * q);
+        cp = r / (n * spp);
+      }
+      coef[tid][0] = m[0] / n; coef[tid][1] = m[1] / n; coef[tid][2] = cy; coef[tid][3] = cp; coef[tid][4] = r;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid == 0) {
+      double s = 0.0;
+      for (int o = 0; o < d; ++o) s += coef[o][4];
+      a.lstat[0] = -s / (double)rows;
+    }
+    for (int o = 0; o < d; ++o) {
+      const double pm = (double)p[o * kHeadRows + tid] - coef[o][0];
+      const double ym = (double)yb[o * kHeadRows + tid] - coef[o][1];
+      dzb[o * kHeadRows + tid] = valid ? (float)(coef[o][2] * ym + coef[o][3] * pm) : 0.f;
+    }
+  } else {
+    for (int o = 0; o < d; ++o) {
+      const float pv = g.bce ? mlp_sigmoid(p[o * kHeadRows + tid]) : p[o * kHeadRows + tid];
+      dzb[o * kHeadRows + tid] = valid ? (pv - yb[o * kHeadRows + tid]) * scale : 0.f;
+    }
   }
   for (int l = nl; l >= 1; --l) {
     __syncthreads();
@@ -490,7 +566,10 @@ __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
     for (int o = tid; o < wo; o += kHeadRows) {
       float s = 0.f;
       for (int rr = 0; rr < kHeadRows; ++rr) s += dz[o * kHeadRows + rr];
-      gp[g.off_b[l - 1] + o] = s;
+      // (the correlation does not change with a shift of p: the output bias' gradient is identically zero,
+      // and is written as such rather than as the rounding residue of the sum)
+      if constexpr (PP == 2) gp[g.off_b[l - 1] + o] = l == nl ? 0.f : s;
+      else gp[g.off_b[l - 1] + o] = s;
     }
     if (l == 1) {
       if (valid)
@@ -635,7 +714,13 @@ int mlp_launch_head(td_handle* h, const MlpPlan& plan, const HeadArgs& a) {
   hipLaunchKernelGGL(mlp_z1_kernel, dim3((unsigned)td_ceil_div((int64_t)g.w[1] * g.batch, 256)), dim3(256), 0,
                      h->stream, a.zpart, plan.nslices, g.w[1], g.batch, rows, a.params + g.off_b[0],
                      const_cast<float*>(a.z1));
-  hipLaunchKernelGGL(mlp_head_kernel, dim3(plan.n_head), dim3(kHeadRows), plan.head_lds, h->stream, a);
+  if (g.pearson && !a.out) {
+    hipLaunchKernelGGL(mlp_head_kernel<1>, dim3(plan.n_head), dim3(kHeadRows), plan.head_lds, h->stream, a);
+    if (a.backward)
+      hipLaunchKernelGGL(mlp_head_kernel<2>, dim3(plan.n_head), dim3(kHeadRows), plan.head_lds, h->stream, a);
+  } else {
+    hipLaunchKernelGGL(mlp_head_kernel<0>, dim3(plan.n_head), dim3(kHeadRows), plan.head_lds, h->stream, a);
+  }
   TD_HIP(h, hipGetLastError());
   return TD_OK;
 }
@@ -645,7 +730,7 @@ int mlp_launch_head(td_handle* h, const MlpPlan& plan, const HeadArgs& a) {
 struct MlpWork {
   float *params, *state, *zpart, *dz1, *gpart, *z1;
   RowEntry* rows[2];        // row tables of even / odd epochs
-  double* spart;
+  double *spart, *mpart, *lstat;   // (mpart, lstat: the Pearson loss)
   long long *file_offs, *stream_offs;
 };
 
@@ -656,16 +741,19 @@ int mlp_work(td_handle* h, const MlpPlan& plan, int nf, MlpWork* w) {
   const size_t n_dz = td_round_up((int64_t)g.w[1] * g.batch, 64);
   const size_t n_gp = td_round_up((int64_t)plan.n_head * g.n_small, 64);
   const size_t n_sp = td_round_up((int64_t)plan.n_head * 6, 32);
+  const size_t n_mp = td_round_up((int64_t)plan.n_head * 5 * kMlpMaxD, 32);
   const size_t n_off = td_round_up((int64_t)nf + 1, 32);
   const size_t n_tab = td_round_up(g.n_rows, 64);
   const size_t n_st = td_round_up(2 * (int64_t)g.n_params, 64);   // Adam keeps two accumulators per parameter
-  const size_t bytes = 4 * (n_par + n_st + n_z + 2 * n_dz + n_gp) + 8 * (n_sp + 2 * n_off) + 2 * 16 * n_tab;
+  const size_t bytes = 4 * (n_par + n_st + n_z + 2 * n_dz + n_gp) + 8 * (n_sp + n_mp + 32 + 2 * n_off) + 2 * 16 * n_tab;
   void* base = nullptr;
   TD_TRY(td_scratch(h, bytes, &base));
   char* p = static_cast<char*>(base);
   w->rows[0] = reinterpret_cast<RowEntry*>(p); p += 16 * n_tab;
   w->rows[1] = reinterpret_cast<RowEntry*>(p); p += 16 * n_tab;
   w->spart = reinterpret_cast<double*>(p); p += 8 * n_sp;
+  w->mpart = reinterpret_cast<double*>(p); p += 8 * n_mp;
+  w->lstat = reinterpret_cast<double*>(p); p += 8 * 32;
   w->file_offs = reinterpret_cast<long long*>(p); p += 8 * n_off;
   w->stream_offs = reinterpret_cast<long long*>(p); p += 8 * n_off;
   w->params = reinterpret_cast<float*>(p); p += 4 * n_par;
@@ -703,8 +791,14 @@ int mlp_setup(td_handle* h, MlpPlan* plan, int nf, const int64_t* offs, const st
   if (!so.empty()) TD_TRY(td_upload_async(h, so.data(), sizeof(long long) * (nf + 1), w->stream_offs));
   plan->g.file_offs = w->file_offs;
   plan->g.stream_offs = so.empty() ? w->file_offs : w->stream_offs;
-  TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_kernel),
+  TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_kernel<0>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
+  if (plan->g.pearson) {
+    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_kernel<1>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
+    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_kernel<2>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
+  }
   return TD_OK;
 }
 
@@ -713,12 +807,12 @@ void mlp_fill(const MlpPlan& plan, const MlpWork& w, SlabArgs* sa, HeadArgs* ha)
   memset(ha, 0, sizeof(*ha));
   sa->g = plan.g;
   sa->params = w.params; sa->state = w.state;
-  sa->zpart = w.zpart; sa->dz1 = w.dz1; sa->gpart = w.gpart; sa->spart = w.spart;
+  sa->zpart = w.zpart; sa->dz1 = w.dz1; sa->gpart = w.gpart; sa->spart = w.spart; sa->lstat = w.lstat;
   sa->ks = plan.ks; sa->nslices = plan.nslices; sa->n_head = plan.n_head;
   sa->prev_epoch = sa->prev_step = sa->cur_epoch = sa->cur_step = -1;
   ha->g = plan.g;
   ha->params = w.params; ha->zpart = w.zpart; ha->nslices = plan.nslices;
-  ha->dz1 = w.dz1; ha->gpart = w.gpart; ha->spart = w.spart;
+  ha->dz1 = w.dz1; ha->gpart = w.gpart; ha->spart = w.spart; ha->mpart = w.mpart; ha->lstat = w.lstat;
   for (int l = 0; l < kMlpMaxHidden + 2; ++l) ha->act_off[l] = plan.act_off[l];
   ha->act_floats = plan.act_floats; ha->maxw = plan.maxw;
   ha->z1 = w.z1;
@@ -788,6 +882,7 @@ int mlp_train_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* fi
   sa.lr = (float)opt.lr; sa.rho = (float)opt.b1; sa.eps = (float)opt.eps;
   sa.beta2 = (float)opt.b2; sa.omb1 = (float)(1.0 - opt.b1); sa.omb2 = (float)(1.0 - opt.b2);
   ha.backward = update;
+  const int nstat = plan.g.pearson ? 7 : 6;
   int pe = -1, ps = -1;
   for (int e = 0; e < epochs; ++e) {
     // in order, one table serves every epoch; shuffled, epochs alternate between two (the first step of
@@ -799,7 +894,7 @@ int mlp_train_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* fi
     for (int s = 0; s < steps; ++s) {
       if (s == 1) sa.prev_rows = tab;
       sa.prev_epoch = pe; sa.prev_step = ps; sa.cur_epoch = e; sa.cur_step = s;
-      sa.stats_out = ps >= 0 ? stats_dev + 6 * ((long long)pe * steps + ps) : nullptr;
+      sa.stats_out = ps >= 0 ? stats_dev + nstat * ((long long)pe * steps + ps) : nullptr;
       if (ps >= 0) mlp_set_update(&sa, opt, (int64_t)pe * steps + ps);
       TD_TRY(mlp_launch_slab(h, plan, sa, ps >= 0));
       ha.epoch = e; ha.step = s;
@@ -809,7 +904,7 @@ int mlp_train_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* fi
   }
   sa.prev_epoch = pe; sa.prev_step = ps; sa.cur_epoch = sa.cur_step = -1;
   sa.prev_rows = sa.cur_rows;
-  sa.stats_out = stats_dev + 6 * ((long long)pe * steps + ps);
+  sa.stats_out = stats_dev + nstat * ((long long)pe * steps + ps);
   mlp_set_update(&sa, opt, (int64_t)pe * steps + ps);
   TD_TRY(mlp_launch_slab(h, plan, sa, true));
   if (update) {
@@ -881,30 +976,79 @@ int mlp_forward_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* 
 
 }  // namespace
 
+namespace {
+
+// loss: 0 = mse, 1 = the Pearson correlation loss
+int mlp_loss_plan(td_handle* h, const char* fn, int loss, MlpPlan* plan) {
+  TD_REQUIRE(h, loss == 0 || loss == 1, "%s: loss %d (0 = mse, 1 = Pearson)", fn, loss);
+  plan->g.pearson = loss;
+  return TD_OK;
+}
+
+int mlp_train_entry(td_handle* h, const char* fn, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host,
+                    int num_files, int c, int pre, int post, int input_offset, const int64_t* rows_used_host,
+                    const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows,
+                    int epochs, float* params_dev, float* state_dev, float lr, float rho, float eps,
+                    int64_t shuffle_seed, double* stats_dev, int loss) {
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, batch_rows, &plan));
+  TD_TRY(mlp_loss_plan(h, fn, loss, &plan));
+  const MlpOpt opt = {kUpdRmsprop, lr, rho, 0.0, eps, 0};
+  return mlp_train_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
+                       batch_rows, epochs, params_dev, state_dev, opt, shuffle_seed, stats_dev);
+}
+
+int mlp_grad_entry(td_handle* h, const char* fn, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host,
+                   int num_files, int c, int pre, int post, int input_offset, const int64_t* rows_used_host,
+                   const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows,
+                   int batch_index, const float* params_dev, float* grad_dev, double* stats_dev, int loss) {
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
+                            hidden_host, num_hidden, batch_rows, &plan));
+  TD_TRY(mlp_loss_plan(h, fn, loss, &plan));
+  return mlp_grad_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
+                      batch_rows, batch_index, params_dev, grad_dev, stats_dev);
+}
+
+}  // namespace
+
 int td_mlp_train(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
                  int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
                  int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int epochs,
                  float* params_dev, float* state_dev, float lr, float rho, float eps, int64_t shuffle_seed,
                  double* stats_dev) {
-  static const char* fn = "td_mlp_train";
-  MlpPlan plan;
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, batch_rows, &plan));
-  const MlpOpt opt = {kUpdRmsprop, lr, rho, 0.0, eps, 0};
-  return mlp_train_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
-                       batch_rows, epochs, params_dev, state_dev, opt, shuffle_seed, stats_dev);
+  return mlp_train_entry(h, "td_mlp_train", x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset,
+                         rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, epochs, params_dev,
+                         state_dev, lr, rho, eps, shuffle_seed, stats_dev, 0);
+}
+
+int td_mlp_train_loss(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host,
+                      int num_files, int c, int pre, int post, int input_offset, const int64_t* rows_used_host,
+                      const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden,
+                      int batch_rows, int epochs, float* params_dev, float* state_dev, float lr, float rho,
+                      float eps, int64_t shuffle_seed, double* stats_dev, int loss) {
+  return mlp_train_entry(h, "td_mlp_train_loss", x_dev, ldx, file_offsets_host, num_files, c, pre, post,
+                         input_offset, rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, epochs,
+                         params_dev, state_dev, lr, rho, eps, shuffle_seed, stats_dev, loss);
 }
 
 int td_mlp_grad(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
                 int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
                 int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int batch_index,
                 const float* params_dev, float* grad_dev, double* stats_dev) {
-  static const char* fn = "td_mlp_grad";
-  MlpPlan plan;
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, batch_rows, &plan));
-  return mlp_grad_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
-                      batch_rows, batch_index, params_dev, grad_dev, stats_dev);
+  return mlp_grad_entry(h, "td_mlp_grad", x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset,
+                        rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, batch_index, params_dev,
+                        grad_dev, stats_dev, 0);
+}
+
+int td_mlp_grad_loss(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host,
+                     int num_files, int c, int pre, int post, int input_offset, const int64_t* rows_used_host,
+                     const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows,
+                     int batch_index, const float* params_dev, float* grad_dev, double* stats_dev, int loss) {
+  return mlp_grad_entry(h, "td_mlp_grad_loss", x_dev, ldx, file_offsets_host, num_files, c, pre, post,
+                        input_offset, rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows,
+                        batch_index, params_dev, grad_dev, stats_dev, loss);
 }
 
 int td_mlp_forward(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,

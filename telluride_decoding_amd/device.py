@@ -922,35 +922,52 @@ def _mlp_rows(file_offsets, input_offset, rows_used):
   return offs, offs_p, used, used_p, int(np.sum(used))
 
 
+MLP_LOSSES = {'mse': 0, 'pearson': 1}
+
+
+def _mlp_loss(loss):
+  if loss not in MLP_LOSSES:
+    raise ValueError('loss %r: one of %s' % (loss, sorted(MLP_LOSSES)))
+  return MLP_LOSSES[loss]
+
+
 def mlp_train(x, y, file_offsets, pre, post, hidden, params, state, batch_rows, epochs, lr, rho, eps,
-              input_offset=0, rows_used=None, shuffle_seed=None, handle=None):
+              input_offset=0, rows_used=None, shuffle_seed=None, handle=None, loss='mse'):
   """`epochs` epochs of minibatch RMSprop on the lagged view of x (td_mlp_train): params / state are the packed
   float32 parameters and RMSprop accumulators (device, updated in place).  Returns the device float64 sums
-  [epochs, steps, 6] of every step's forward pass (sum p, y, p^2, y^2, p y of output 0; sum (p - y)^2)."""
+  [epochs, steps, 6] of every step's forward pass (sum p, y, p^2, y^2, p y of output 0; sum (p - y)^2).
+  loss='pearson' minimises the Pearson correlation loss instead (td_mlp_train_loss) and returns
+  [epochs, steps, 7]: the six sums, then the step's loss -(1 / B) sum_o r_o."""
   h = handle or default_handle()
+  code = _mlp_loss(loss)
+  nstat = 7 if code else 6
   offs, offs_p, used, used_p, n = _mlp_rows(file_offsets, input_offset, rows_used)
   steps = -(-n // int(batch_rows)) if batch_rows > 0 else 0
-  stats = h.empty((max(int(epochs), 0) * steps, 6), 'float64')
+  stats = h.empty((max(int(epochs), 0) * steps, nstat), 'float64')
   hid, hid_p = _i32_array(list(hidden) or [0])
   seed = -1 if shuffle_seed is None else int(shuffle_seed)
-  h.check(h.lib.td_mlp_train(h.ptr, _ptr(x), x.stride(0), offs_p, len(offs) - 1, int(x.shape[1]), int(pre),
-                             int(post), int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p,
-                             len(hidden), int(batch_rows), int(epochs), _ptr(params), _ptr(state), float(lr),
-                             float(rho), float(eps), seed, _ptr(stats)))
-  return stats.reshape(max(int(epochs), 0), steps, 6)
+  args = (h.ptr, _ptr(x), x.stride(0), offs_p, len(offs) - 1, int(x.shape[1]), int(pre), int(post),
+          int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p, len(hidden), int(batch_rows),
+          int(epochs), _ptr(params), _ptr(state), float(lr), float(rho), float(eps), seed, _ptr(stats))
+  h.check(h.lib.td_mlp_train_loss(*args, code) if code else h.lib.td_mlp_train(*args))
+  return stats.reshape(max(int(epochs), 0), steps, nstat)
 
 
 def mlp_grad(x, y, file_offsets, pre, post, hidden, params, batch_rows, batch_index, input_offset=0,
-             rows_used=None, handle=None):
-  """(gradient [P] float32, sums [6] float64) of minibatch `batch_index` at params, no update (td_mlp_grad)."""
+             rows_used=None, handle=None, loss='mse'):
+  """(gradient [P] float32, sums [6] float64) of minibatch `batch_index` at params, no update (td_mlp_grad).
+  loss='pearson': the gradient of the Pearson correlation loss and sums [7], the last one the loss
+  (td_mlp_grad_loss)."""
   h = handle or default_handle()
+  code = _mlp_loss(loss)
   offs, offs_p, used, used_p, _ = _mlp_rows(file_offsets, input_offset, rows_used)
   grad = h.empty((int(params.numel()),), 'float32')
-  stats = h.empty((6,), 'float64')
+  stats = h.empty((7 if code else 6,), 'float64')
   hid, hid_p = _i32_array(list(hidden) or [0])
-  h.check(h.lib.td_mlp_grad(h.ptr, _ptr(x), x.stride(0), offs_p, len(offs) - 1, int(x.shape[1]), int(pre),
-                            int(post), int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p,
-                            len(hidden), int(batch_rows), int(batch_index), _ptr(params), _ptr(grad), _ptr(stats)))
+  args = (h.ptr, _ptr(x), x.stride(0), offs_p, len(offs) - 1, int(x.shape[1]), int(pre), int(post),
+          int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p, len(hidden), int(batch_rows),
+          int(batch_index), _ptr(params), _ptr(grad), _ptr(stats))
+  h.check(h.lib.td_mlp_grad_loss(*args, code) if code else h.lib.td_mlp_grad(*args))
   return grad, stats
 
 
