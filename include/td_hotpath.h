@@ -375,6 +375,26 @@ int td_ridge_solve_loso_terms(td_handle* h, td_stats* total, td_stats* const* te
                               int max_iter, double tol, int w_k_major, float* w_dev, float* b_dev,
                               int* status_host, int* iterations_host);
 
+/* The CCA dense stage of a leave-one-file-out x regularisation sweep (regression.py:326-420 over
+ * cca.calculate_cca_parameters_from_dataset, cca.py:337-367): one CCA model per (fold, lambda), the folds given as
+ * td_ridge_solve_loso_terms takes them (fold f = total + signed terms, at most 4).  fold_batches[f] minibatches of
+ * batch_size frames make fold f's training stream: means over fold_batches[f] * batch_size frames (which the fold's
+ * statistics must hold), covariances S / (frames - 1) - mean^T mean, + lambda I on BOTH auto-covariances.  The x side
+ * is whitened by its Cholesky factor (valid when no eigenvalue of cov_xx is dropped), the other side (k2 <= 64) by
+ * the reference's eigen route in one workgroup per pair; no k1-sized eigen-decomposition.  Outputs, float32 on the
+ * device: rot_x [n_folds][k1][n_lambda * dim] and rot_y [n_folds][k2][n_lambda * dim] (k-major: a fold's models are
+ * the output columns of one filter, what td_predict_fir takes), mean_x [n_folds][k1], mean_y [n_folds][k2], bias_x /
+ * bias_y [n_folds][n_lambda * dim] = -mean . rot, e [n_folds][n_lambda][dim] (the canonical correlations,
+ * descending); status_dev int32 [n_folds][n_lambda]: 0 solved, 1 = cov_xx + lambda I has no Cholesky factor, an
+ * eigenvalue of cov_yy + lambda I is <= eps_eig, or sigma_dim <= 1e-6 sigma_1 -- that pair's outputs are not to be
+ * used (td_cca_solve on the fold's summed statistics decides).  Queued on the handle's stream, no wait.
+ * TD_ERR_INVALID: k2 > 64, more than 4 terms in a fold, dim outside [1, min(k1, k2)]. */
+int td_cca_solve_loso_terms(td_handle* h, td_stats* total, td_stats* const* terms, const int* term_begin,
+                            const double* signs, int n_folds, const int64_t* fold_batches, int batch_size,
+                            const double* lambdas_host, int n_lambda, int dim, double eps_eig, float* rot_x_dev,
+                            float* rot_y_dev, float* mean_x_dev, float* mean_y_dev, float* bias_x_dev,
+                            float* bias_y_dev, float* e_dev, int* status_dev);
+
 /* Generic SPD solve used by the above and by the shrinkage branch
  * (brain_model.py:456-477): a_dev [batch, n, n] float64 (destroyed),
  * rhs_dev [batch, n, nrhs] float64 (overwritten with the solution). */

@@ -1299,6 +1299,23 @@ int td_chol_back(td_handle* h, const td_chol_state* st, const double* ut_dev, in
   return TD_OK;
 }
 
+// The batched factorisation and the backward substitution for callers that fill the padded buffers
+// themselves (cca_sweep.hip): a [batch][np][np], rt / sol [batch][rt_rows][np], linv [batch][np / 64][64][64],
+// tol [batch].  Up to 64 right-hand-side rows ride along the factorisation; the backward pass takes at most 8.
+// A non-positive pivot sets the handle's flag only: the caller looks at each system's own pivots.
+int td_chol_batch_forward(td_handle* h, double* a_dev, double* rt_dev, double* linv_dev, double* tol_dev, int np,
+                          int n_real, int nrhs, int batch, int rt_rows) {
+  TD_REQUIRE(h, np % NB == 0 && nrhs > 0 && nrhs <= 64 && nrhs <= rt_rows && batch > 0, "td_chol_batch_forward: bad sizes");
+  return chol_factor_forward(h, a_dev, rt_dev, nullptr, linv_dev, tol_dev, np, nrhs, batch, nullptr, rt_rows, n_real);
+}
+
+int td_chol_batch_backward(td_handle* h, double* a_dev, double* rt_dev, double* sol_dev, double* linv_dev, int np,
+                           int nrhs, int batch, int rt_rows) {
+  TD_REQUIRE(h, np % NB == 0 && nrhs > 0 && nrhs <= kMaxRhs && nrhs <= rt_rows && batch > 0,
+             "td_chol_batch_backward: bad sizes");
+  return chol_backward(h, a_dev, rt_dev, sol_dev, linv_dev, np, nrhs, batch, rt_rows);
+}
+
 // ---- ridge solve with more than kMaxRhs outputs (a forward model: D = EEG channels) --------------
 // The batched solver carries at most kMaxRhs right-hand-side rows per system (they ride in its
 // panel and update kernels).  Wider targets go through the Cholesky helpers above, one lambda at

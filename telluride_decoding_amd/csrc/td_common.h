@@ -89,7 +89,7 @@ struct td_handle {
   // "cg_limit_ticks" (< 0: the default wait limit of the conjugate-gradient kernel's polls)
   int cca_whitening = 0;
   int cca_fused = 1;            // "cca_fused": k1 <= 64, k2 <= 16 take the one-launch dense stage (0: the chain of launches)
-  bool lds_opt_cca = false, lds_opt_lu = false;
+  bool lds_opt_cca = false, lds_opt_lu = false, lds_opt_cca_tail = false;
   long long cg_limit_ticks = -1;
   int async_cg = 0;             // "async_cg": td_ridge_solve_async may use the compact-statistics CG (flag 2 = gave up)
   int narrow16 = 1;             // "narrow16": <= 16 channels take the one-kernel streaming accumulate (0: the tiled kernels)
@@ -575,3 +575,9 @@ size_t td_chol_ws_bytes(int n);
 int td_chol_factor(td_handle* h, void* ws, const double* c_dev, int n, const double* bt_dev, int nb,
                    td_chol_state* st, double diag_shift = 0.0, double scale = 1.0);
 int td_chol_back(td_handle* h, const td_chol_state* st, const double* ut_dev, int nu, double* xt_dev);
+// (solve.hip) the batched factorisation (forward substitution of up to 64 right-hand-side rows included) and the
+// backward substitution (at most 8 rows) on padded buffers the caller filled; see there.
+int td_chol_batch_forward(td_handle* h, double* a_dev, double* rt_dev, double* linv_dev, double* tol_dev, int np,
+                          int n_real, int nrhs, int batch, int rt_rows);
+int td_chol_batch_backward(td_handle* h, double* a_dev, double* rt_dev, double* sol_dev, double* linv_dev, int np,
+                           int nrhs, int batch, int rt_rows);

@@ -433,6 +433,36 @@ class LagStats(object):
       return None
     return w, b, int(iters.value)
 
+  @staticmethod
+  def cca_solve_loso_terms(total, fold_terms, fold_batches, batch_size, lambdas, dim, eps_eig=1e-12, handle=None):
+    """One CCA model per (fold, lambda) of a leave-one-file-out sweep (td_cca_solve_loso_terms): `total` = the CCA
+    statistics of all recordings, fold_terms[f] = [(LagStats, +1 or -1), ...] as ridge_solve_loso_terms takes them,
+    fold_batches[f] = minibatches of `batch_size` frames in fold f's training stream.  Returns float32 device tensors
+    (rot_x [F, k1, L * dim], rot_y [F, k2, L * dim], mean_x [F, k1], mean_y [F, k2], bias_x [F, L * dim],
+    bias_y [F, L * dim], e [F, L, dim]) and the int32 device tensor status [F, L] (0 solved, 1 refit that pair with
+    cca_solve); nothing waits for the device.  ValueError: k2 > 64, a fold of more than four terms, a bad dim."""
+    h = handle or total.h
+    lam, lam_p = _lib.f64_array(np.atleast_1d(lambdas))
+    n_folds, n_lam, dim = len(fold_terms), len(lam), int(dim)
+    k1, k2 = total.k1, total.k2
+    rot_x = h.empty((n_folds, k1, n_lam * dim), 'float32')
+    rot_y = h.empty((n_folds, k2, n_lam * dim), 'float32')
+    mean_x, mean_y = h.empty((n_folds, k1), 'float32'), h.empty((n_folds, k2), 'float32')
+    bias_x, bias_y = h.empty((n_folds, n_lam * dim), 'float32'), h.empty((n_folds, n_lam * dim), 'float32')
+    e = h.empty((n_folds, n_lam, dim), 'float32')
+    status = h.empty((n_folds, n_lam), 'int32')
+    flat = [t for terms in fold_terms for t in terms]
+    arr = (ctypes.c_void_p * max(1, len(flat)))(*[s.ptr for s, _ in flat])
+    begin = np.concatenate(([0], np.cumsum([len(t) for t in fold_terms]))).astype(np.int32)
+    signs = np.asarray([float(sg) for _, sg in flat] or [0.0], np.float64)
+    nb, nb_p = _lib.i64_array(fold_batches)
+    h.check(h.lib.td_cca_solve_loso_terms(
+        h.ptr, total.ptr, arr, begin.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+        signs.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n_folds, nb_p, int(batch_size), lam_p, n_lam, dim,
+        float(eps_eig), _ptr(rot_x), _ptr(rot_y), _ptr(mean_x), _ptr(mean_y), _ptr(bias_x), _ptr(bias_y), _ptr(e),
+        _ptr(status)))
+    return rot_x, rot_y, mean_x, mean_y, bias_x, bias_y, e, status
+
   def cca_solve(self, denom, regularization, dim, eps_eig=1e-12, handle=None):
     """CCA dense stage on the device (td_cca_solve; reference cca.py:337-367): returns float32
     device tensors (rot_x [k1, dim], rot_y [k2, dim], mean_x [1, k1], mean_y [1, k2], e [dim])
