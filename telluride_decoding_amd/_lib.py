@@ -37,6 +37,21 @@ _vp, _i, _i64, _f, _d, _sz = (_c.c_void_p, _c.c_int, _c.c_int64, _c.c_float,
 _pi64 = _c.POINTER(_c.c_int64)
 _pd = _c.POINTER(_c.c_double)
 
+# The td_mlp_* / td_mlpc_* prototypes are built from the groups their parameter lists share, so each entry below
+# reads as its prototype in include/td_hotpath.h does (tests/test_cpu_dnn.py checks them against the header).
+_X = [_vp, _i64]                        # x_dev, ldx (x2_dev, ldx2)
+_FILES = [_pi64, _i]                    # file_offsets_host, num_files
+_VIEW = [_i, _i, _i]                    # c, pre, post (c2, pre2, post2)
+_TARGETS = [_vp, _i64, _i]              # y_dev, ldy, d
+_NETWORK = [_c.POINTER(_i), _i]         # hidden_host, num_hidden
+_MLP = [_vp] + _X + _FILES + _VIEW                      # the handle, then one view of the files
+_MLPC = [_vp] + _X + _X + _FILES + _VIEW + _VIEW        # ... two views
+_FIT = [_i, _pi64] + _TARGETS + _NETWORK + [_i]         # input_offset, rows_used_host, ..., batch_rows
+_EPOCHS = [_i, _vp, _vp]                # epochs, params_dev, state_dev (the optimizer's settings follow)
+_SEED_STATS = [_i64, _vp]               # shuffle_seed, stats_dev
+_GRAD = [_i, _vp, _vp, _vp]             # batch_index, params_dev, grad_dev, stats_dev
+_FORWARD = [_i, _i] + _NETWORK + [_vp, _vp, _i64]       # input_offset, d, ..., params_dev, out_dev, ldout
+
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 SIGNATURES = {
     'td_version': [],
@@ -135,21 +150,14 @@ SIGNATURES = {
     'td_audio_intensity': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _d, _d, _d, _i, _d, _vp, _vp],
     'td_audio_passthrough': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _i64, _i, _d, _vp, _vp],
     'td_audio_spectrogram': [_vp, _vp, _i64, _i, _i, _i, _pd, _i, _i64, _vp],
-    'td_mlp_train': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i, _c.POINTER(_i), _i, _i, _i,
-                     _vp, _vp, _f, _f, _f, _i64, _vp],
-    'td_mlp_grad': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i, _c.POINTER(_i), _i, _i, _i,
-                    _vp, _vp, _vp],
-    'td_mlp_train_loss': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i, _c.POINTER(_i), _i, _i,
-                          _i, _vp, _vp, _f, _f, _f, _i64, _vp, _i],
-    'td_mlp_grad_loss': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i, _c.POINTER(_i), _i, _i,
-                         _i, _vp, _vp, _vp, _i],
-    'td_mlp_forward': [_vp, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i, _vp, _vp, _i64],
-    'td_mlpc_train': [_vp, _vp, _i64, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i,
-                      _c.POINTER(_i), _i, _i, _i, _vp, _vp, _d, _d, _d, _d, _i64, _i, _i64, _vp],
-    'td_mlpc_grad': [_vp, _vp, _i64, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _i, _i, _pi64, _vp, _i64, _i,
-                     _c.POINTER(_i), _i, _i, _i, _vp, _vp, _vp],
-    'td_mlpc_forward': [_vp, _vp, _i64, _vp, _i64, _pi64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _c.POINTER(_i), _i,
-                        _vp, _vp, _i64],
+    'td_mlp_train': _MLP + _FIT + _EPOCHS + [_f, _f, _f] + _SEED_STATS,
+    'td_mlp_grad': _MLP + _FIT + _GRAD,
+    'td_mlp_train_loss': _MLP + _FIT + _EPOCHS + [_f, _f, _f] + _SEED_STATS + [_i],
+    'td_mlp_grad_loss': _MLP + _FIT + _GRAD + [_i],
+    'td_mlp_forward': _MLP + _FORWARD,
+    'td_mlpc_train': _MLPC + _FIT + _EPOCHS + [_d, _d, _d, _d, _i64, _i] + _SEED_STATS,
+    'td_mlpc_grad': _MLPC + _FIT + _GRAD,
+    'td_mlpc_forward': _MLPC + _FORWARD,
 }
 _RESTYPE = {'td_last_error': _c.c_char_p}
 

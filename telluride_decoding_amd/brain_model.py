@@ -341,45 +341,46 @@ class BrainModelLinearRegression(object):
     (whole recordings in a few launches) or any iterable of (dict, y) minibatches whose 'input_1'
     already carries its context (one prediction + one window-sums launch per minibatch)."""
     del kwargs
-    return self._evaluate(dataset, False)
-
-  def _evaluate(self, dataset, _pearson_loss):
-    """evaluate; _pearson_loss (BrainModelDNN compiled for it): 'loss' is the Pearson correlation loss from
-    the same sums, and the mean squared error is returned as 'mse'."""
-    h = device.default_handle()
-    if not _is_dataset(dataset):
-      if not hasattr(dataset, '__iter__'):
-        raise TypeError('BrainModel.evaluate must be called with tf.data.Dataset object.')
-      return _evaluate_minibatches(
-          dataset, h, lambda feats: self._predict_lagged_device(feats['input_1'], h), truth_from_y=True,
-          pearson_loss=_pearson_loss)
-    dataset = dataset.resolved()     # mixup_batch: evaluate against the shuffled output
-    pred = self.predict_device(dataset, handle=h)
-    _, _, y, offs = dataset.device_arrays(h)
-    bsz = dataset.batch_size
-    # Minibatches run across file boundaries in the reference; gather the zipped
-    # stream once (device copies), then window it with hop = width = batch.
-    y_all, p_all = zipped_rows(dataset, h, y, pred)
-    rows = int(p_all.shape[0])
-    if rows == 0:
-      out = {'loss': float('nan'), 'pearson_correlation_first': float('nan')}
-      if _pearson_loss:
-        out['mse'] = float('nan')
-      return out
-    sums = device.window_sums(y_all, p_all, [0, rows], bsz, bsz, handle=h)
-    r = device.window_scores(sums, bsz, mode=1, handle=h).cpu().numpy()
-    s = sums.cpu().numpy()
-    sq = s[:, :, 2] - 2 * s[:, :, 4] + s[:, :, 3]     # sum (y - p)^2 per batch and column
-    loss = float(np.mean(np.sum(sq, axis=1) / (bsz * s.shape[1])))
-    if _pearson_loss:
-      return {'loss': float(np.mean(pearson_loss_from_sums(s, bsz))),
-              'pearson_correlation_first': float(np.mean(r[:, 0])), 'mse': loss}
-    return {'loss': loss, 'pearson_correlation_first': float(np.mean(r[:, 0]))}
+    return _evaluate_regression(self, dataset, False)
 
   def _predict_lagged_device(self, lagged, h):
     w, b = self._device_weights(h)
     x = _as_2d_device(h, lagged)
     return device.predict_fir(x, [0, int(x.shape[0])], w, b, 0, 0, handle=h)
+
+
+def _evaluate_regression(model, dataset, pearson_loss):
+  """The evaluate of BrainModelLinearRegression and BrainModelDNN, from the model's predict_device and
+  _predict_lagged_device.  pearson_loss (BrainModelDNN compiled for it): 'loss' is the Pearson correlation loss
+  from the same sums, and the mean squared error is returned as 'mse'."""
+  h = device.default_handle()
+  if not _is_dataset(dataset):
+    if not hasattr(dataset, '__iter__'):
+      raise TypeError('BrainModel.evaluate must be called with tf.data.Dataset object.')
+    return _evaluate_minibatches(
+        dataset, h, lambda feats: model._predict_lagged_device(feats['input_1'], h), truth_from_y=True,
+        pearson_loss=pearson_loss)
+  dataset = dataset.resolved()     # mixup_batch: evaluate against the shuffled output
+  pred = model.predict_device(dataset, handle=h)
+  _, _, y, offs = dataset.device_arrays(h)
+  bsz = dataset.batch_size
+  # Minibatches run across file boundaries in the reference; gather the zipped
+  # stream once (device copies), then window it with hop = width = batch.
+  y_all, p_all = zipped_rows(dataset, h, y, pred)
+  rows = int(p_all.shape[0])
+  loss = ploss = r = float('nan')
+  if rows:
+    sums = device.window_sums(y_all, p_all, [0, rows], bsz, bsz, handle=h)
+    r = float(np.mean(device.window_scores(sums, bsz, mode=1, handle=h).cpu().numpy()[:, 0]))
+    s = sums.cpu().numpy()
+    sq = s[:, :, 2] - 2 * s[:, :, 4] + s[:, :, 3]     # sum (y - p)^2 per batch and column
+    loss = float(np.mean(np.sum(sq, axis=1) / (bsz * s.shape[1])))
+    if pearson_loss:
+      ploss = float(np.mean(pearson_loss_from_sums(s, bsz)))
+  out = {'loss': ploss if pearson_loss else loss, 'pearson_correlation_first': r}
+  if pearson_loss:
+    out['mse'] = loss
+  return out
 
 
 class RMSprop(object):
@@ -413,17 +414,23 @@ def _host(a):
   return np.asarray(a)
 
 
-def pearson_loss_from_sums(s, rows):
-  """-(1 / rows) sum_o r_o from the five raw float64 sums of every output column (s [..., d, 5]: sum a, b, a^2,
-  b^2, a b over `rows` rows), with the zero rule of pearson_correlation per column: a constant column
-  contributes r_o = 0."""
-  s = np.asarray(s, np.float64)
-  n = float(rows)
+def _centred_moments(s, n):
+  """(va, vb, cov, zero) of the raw sums s[..., 0:5] = sum a, b, a^2, b^2, a b over n rows: the two sums of
+  squared deviations, the sum of their products, and where the zero rule of pearson_correlation applies (a
+  constant column: its sum of squared deviations lies within 32 eps of its raw sum of squares)."""
   va = s[..., 2] - s[..., 0] ** 2 / n
   vb = s[..., 3] - s[..., 1] ** 2 / n
   cov = s[..., 4] - s[..., 0] * s[..., 1] / n
   tiny = 32 * np.finfo(np.float64).eps
-  zero = (va <= tiny * s[..., 2]) | (vb <= tiny * s[..., 3])
+  return va, vb, cov, (va <= tiny * s[..., 2]) | (vb <= tiny * s[..., 3])
+
+
+def pearson_loss_from_sums(s, rows):
+  """-(1 / rows) sum_o r_o from the five raw float64 sums of every output column (s [..., d, 5]: sum a, b, a^2,
+  b^2, a b over `rows` rows), with the zero rule of pearson_correlation per column: a constant column
+  contributes r_o = 0."""
+  n = float(rows)
+  va, vb, cov, zero = _centred_moments(np.asarray(s, np.float64), n)
   with np.errstate(invalid='ignore', divide='ignore'):
     r = np.where(zero, 0.0, cov / np.sqrt(np.where(zero, 1.0, va * vb)))
   return -np.sum(r, axis=-1) / n
@@ -438,11 +445,7 @@ def history_from_sums(sums, rows, d):
   s = np.asarray(sums, np.float64)
   n = float(rows)
   mse = s[..., 5] / (n * d)
-  va = s[..., 2] - s[..., 0] ** 2 / n
-  vb = s[..., 3] - s[..., 1] ** 2 / n
-  cov = s[..., 4] - s[..., 0] * s[..., 1] / n
-  tiny = 32 * np.finfo(np.float64).eps
-  zero = (va <= tiny * s[..., 2]) | (vb <= tiny * s[..., 3])
+  va, vb, cov, zero = _centred_moments(s, n)
   with np.errstate(invalid='ignore', divide='ignore'):
     r = np.where(zero, 0.0, cov / (np.sqrt(np.maximum(va, 0)) * np.sqrt(np.maximum(vb, 0))))
   mse = [float(v) for v in np.mean(mse, axis=-1)]
@@ -451,40 +454,34 @@ def history_from_sums(sums, rows, d):
           'mse': mse}
 
 
-class BrainModelDNN(object):
-  """A fully connected regressor trained on the GPU (reference brain_model.py:486-549): Dense layers of
-  `num_hidden_list` ReLU units and a linear output layer, trained by minibatch RMSprop on the mean squared
-  error or on the Pearson correlation loss (DESIGN section 16).  Training, inference and the lag gather run in the HIP kernels of td_mlp_* (csrc/mlp.hip); a fit
-  is one C call, with no host round trip between steps (DESIGN section 14).
+class _BrainModelMlp(object):
+  """What BrainModelDNN and BrainModelClassifier share: the constructor, the packed parameters, the limits of the
+  td_mlp_* kernels, the guards of fit and the optimizer argument of compile.  A subclass describes itself by the
+  class attributes below and supplies its loss parsing, its device calls (_train, predict_device), its history
+  and evaluate."""
 
-  Differences from the reference, all documented:
-    * the initial weights are Keras' glorot_uniform (limit sqrt(6 / (fan_in + fan_out)), zero biases) drawn
-      with numpy.random.default_rng(seed): W1, W2, ... in layer order, each rng.uniform(-limit, limit,
-      (fan_in, fan_out)) as float32.  TF's random generator cannot be reproduced;
-    * fit(shuffle_seed=None) visits the stream's rows in order, minibatch s = rows [s B, (s + 1) B); with a
-      seed, epoch e visits them in the order of a bijection computed on the device from (seed, e) (a 4-round
-      Feistel network, cycle-walked; include/td_hotpath.h, td_mlp_train).  The reference shuffles frames
-      through a 1000-frame tf.data buffer, which cannot be reproduced;
-    * the only optimizer is RMSprop without momentum; the losses are 'mse' and the Pearson correlation loss;
-    * on the Pearson loss, a column that is constant within a minibatch (prediction or target) contributes
-      r = 0 and no gradient for that step, where the reference divides by zero and every weight becomes NaN;
-      and the output layer's bias gradient, identically zero in exact arithmetic, is exactly 0 rather than a
-      rounding residue: the output bias does not move, which cannot change any prediction's correlation.
-  """
+  # one row per input view: the feature's name, the model attribute that holds its lagged width, and the
+  # Dataset's channel / pre / post fields of that view
+  _VIEWS = (('input_1', '_input_width', 'c1', 'pre', 'post'),)
+  _OPTIMIZER = None            # the optimizer class; compile also takes its name in lower case
+  _HISTORY_KEYS = ()           # = metrics_names
+  _DATASET_ERROR = ValueError  # what the constructor raises on anything but a Dataset (the reference's type)
 
   def __init__(self, input_dataset, num_hidden_list=None, *, seed=0, **kwargs):
     kwargs.pop('tensorboard_dir', None)        # accepted and ignored, as BrainModelLinearRegression
     del kwargs
     if not _is_dataset(input_dataset):
-      raise ValueError('Dataset must be a tf.data.datasert, not a %s' % type(input_dataset))
+      raise self._DATASET_ERROR('Dataset must be a tf.data.datasert, not a %s' % type(input_dataset))
     if num_hidden_list is None:
       num_hidden_list = []
     if not isinstance(num_hidden_list, list):
       raise TypeError('Num_hidden_list must be an list, not a %s.' % type(num_hidden_list))
-    self._input_width = int(input_dataset.element_spec[0]['input_1'].shape[-1])
+    for feature, width, _, _, _ in self._VIEWS:
+      setattr(self, width, int(input_dataset.element_spec[0][feature].shape[-1]))
     self._output_width = int(input_dataset.element_spec[1].shape[-1])
     self.num_hidden_list = [int(u) for u in num_hidden_list]
-    self._widths = [self._input_width] + self.num_hidden_list + [self._output_width]
+    self._widths = ([sum(getattr(self, view[1]) for view in self._VIEWS)] + self.num_hidden_list +
+                    [self._output_width])
     rng = np.random.default_rng(seed)
     weights = []
     for fan_in, fan_out in zip(self._widths[:-1], self._widths[1:]):
@@ -493,12 +490,11 @@ class BrainModelDNN(object):
                   np.zeros((fan_out,), np.float32)]
     self._host_weights = weights
     self._params = None        # packed device parameters (the truth once on the device)
-    self._state = None         # RMSprop accumulators, same layout
+    self._state = None         # the optimizer's accumulators, in the parameters' layout
     self.optimizer = None
-    self.loss = 'mse'          # 'mse' or 'pearson' (compile)
-    self.metrics_names = ['loss', 'pearson_correlation_first', 'mse']
+    self.metrics_names = list(self._HISTORY_KEYS)
 
-  # -- parameters ------------------------------------------------------------
+  # -- parameters (W1's rows: input_1's lag layout, then input_2's) ------------
   def _shapes(self):
     out = []
     for fan_in, fan_out in zip(self._widths[:-1], self._widths[1:]):
@@ -539,6 +535,115 @@ class BrainModelDNN(object):
     return self.get_weights()
 
   # -- training ----------------------------------------------------------------
+  def _compiled_optimizer(self, optimizer, learning_rate):
+    """compile's optimizer argument (the class, an instance, its name, or a callable taking learning_rate=) as an
+    instance of the model's optimizer class."""
+    cls = self._OPTIMIZER
+    if isinstance(optimizer, str):
+      if optimizer.lower() != cls.__name__.lower():
+        raise NotImplementedError('Optimizer %r is not supported: only %s' % (optimizer, cls.__name__))
+      optimizer = cls(learning_rate=learning_rate)
+    elif not isinstance(optimizer, cls) and callable(optimizer):
+      optimizer = optimizer(learning_rate=learning_rate)
+    if not isinstance(optimizer, cls):
+      raise NotImplementedError('Optimizer %r is not supported: only brain_model.%s' % (optimizer, cls.__name__))
+    return optimizer
+
+  def _check_limits(self, ds, problems=()):
+    hidden = self.num_hidden_list
+    problems = list(problems)
+    if len(hidden) > DNN_MAX_HIDDEN:
+      problems.append('%d hidden layers (at most %d)' % (len(hidden), DNN_MAX_HIDDEN))
+    if any(u < 1 or u > DNN_MAX_UNITS for u in hidden):
+      problems.append('hidden layers of %s units (1 .. %d)' % (hidden, DNN_MAX_UNITS))
+    if not 1 <= self._output_width <= DNN_MAX_OUTPUTS:
+      problems.append('%d outputs (1 .. %d)' % (self._output_width, DNN_MAX_OUTPUTS))
+    inputs = 0
+    for feature, width, c, pre, post in self._VIEWS:
+      c, lags = getattr(ds, c), getattr(ds, pre) + 1 + getattr(ds, post)
+      if lags > DNN_MAX_LAGS:
+        problems.append('%s: pre + 1 + post = %d (at most %d)' % (feature, lags, DNN_MAX_LAGS))
+      if c > DNN_MAX_CHANNELS and lags > 1:
+        problems.append('%s: %d channels with temporal context (at most %d)' % (feature, c, DNN_MAX_CHANNELS))
+      if c * lags != getattr(self, width):
+        problems.append('%s is %d wide, the model %d' % (feature, c * lags, getattr(self, width)))
+      inputs += c * lags
+    if inputs > DNN_MAX_INPUTS:
+      problems.append('%d lagged inputs (at most %d)' % (inputs, DNN_MAX_INPUTS))
+    if not 1 <= ds.batch_size <= DNN_MAX_BATCH:
+      problems.append('batch of %d rows (1 .. %d)' % (ds.batch_size, DNN_MAX_BATCH))
+    if problems:
+      raise ValueError('%s: %s' % (type(self).__name__, '; '.join(problems)))
+
+  def _as_dataset(self, data):
+    """A brain_data.Dataset as the kernels read it (mixup_batch resolved: input_2 then carries its context), or
+    an iterable of (dict, y) minibatches materialised once as a context-free Dataset of the same batch size."""
+    if _is_dataset(data):
+      return data.resolved()
+    if not hasattr(data, '__iter__'):
+      raise TypeError('%s needs a brain_data.Dataset or an iterable of (dict, y) minibatches, not %s.' % (
+          type(self).__name__, type(data)))
+    streams = [[] for _ in range(len(self._VIEWS) + 1)]       # one per view, then the targets
+    for feats, y in data:
+      x = np.asarray(_host(feats['input_1']), np.float32)
+      for stream, a in zip(streams, [x] + [feats[view[0]] for view in self._VIEWS[1:]] + [y]):
+        stream.append(np.asarray(_host(a), np.float32).reshape(x.shape[0], -1))
+    if not streams[0] or streams[0][0].shape[0] == 0:
+      raise ValueError('No minibatches in dataset')
+    *xs, y = [np.concatenate(stream) for stream in streams]
+    zeros = np.zeros((y.shape[0], 1), np.float32)
+    return brain_data.Dataset([(xs[0], xs[1] if len(xs) > 1 else zeros, y, zeros)], streams[0][0].shape[0])
+
+  def _fit(self, input_dataset, epochs, shuffle_seed):
+    """The guards of fit, then self._train(dataset, handle, epochs, shuffle_seed) -> the History's dict."""
+    if self.optimizer is None:
+      raise RuntimeError('You must compile your model before training/testing.')
+    if shuffle_seed is not None and not 0 <= int(shuffle_seed) < 2 ** 63:
+      raise ValueError('shuffle_seed must be in [0, 2^63), not %r' % (shuffle_seed,))
+    ds = self._as_dataset(input_dataset)
+    self._check_limits(ds)
+    epochs = int(epochs)
+    if ds.num_batches() == 0 or epochs <= 0:
+      return History({key: [] for key in self._HISTORY_KEYS})
+    return History(self._train(ds, device.default_handle(), epochs, shuffle_seed))
+
+  # -- inference ---------------------------------------------------------------
+  def __call__(self, input_dataset):
+    return self.call(input_dataset)
+
+  def predict(self, dataset):
+    pred = self.predict_device(dataset).cpu().numpy()
+    return rows_of_stream(pred, dataset.file_lengths(), dataset.rows_used())
+
+
+class BrainModelDNN(_BrainModelMlp):
+  """A fully connected regressor trained on the GPU (reference brain_model.py:486-549): Dense layers of
+  `num_hidden_list` ReLU units and a linear output layer, trained by minibatch RMSprop on the mean squared
+  error or on the Pearson correlation loss (DESIGN section 16).  Training, inference and the lag gather run in the HIP kernels of td_mlp_* (csrc/mlp.hip); a fit
+  is one C call, with no host round trip between steps (DESIGN section 14).
+
+  Differences from the reference, all documented:
+    * the initial weights are Keras' glorot_uniform (limit sqrt(6 / (fan_in + fan_out)), zero biases) drawn
+      with numpy.random.default_rng(seed): W1, W2, ... in layer order, each rng.uniform(-limit, limit,
+      (fan_in, fan_out)) as float32.  TF's random generator cannot be reproduced;
+    * fit(shuffle_seed=None) visits the stream's rows in order, minibatch s = rows [s B, (s + 1) B); with a
+      seed, epoch e visits them in the order of a bijection computed on the device from (seed, e) (a 4-round
+      Feistel network, cycle-walked; include/td_hotpath.h, td_mlp_train).  The reference shuffles frames
+      through a 1000-frame tf.data buffer, which cannot be reproduced;
+    * the only optimizer is RMSprop without momentum; the losses are 'mse' and the Pearson correlation loss;
+    * on the Pearson loss, a column that is constant within a minibatch (prediction or target) contributes
+      r = 0 and no gradient for that step, where the reference divides by zero and every weight becomes NaN;
+      and the output layer's bias gradient, identically zero in exact arithmetic, is exactly 0 rather than a
+      rounding residue: the output bias does not move, which cannot change any prediction's correlation.
+  """
+
+  _OPTIMIZER = RMSprop
+  _HISTORY_KEYS = ('loss', 'pearson_correlation_first', 'mse')
+
+  def __init__(self, input_dataset, num_hidden_list=None, *, seed=0, **kwargs):
+    super().__init__(input_dataset, num_hidden_list, seed=seed, **kwargs)
+    self.loss = 'mse'          # 'mse' or 'pearson' (compile)
+
   def compile(self, optimizer=RMSprop, loss='mse', metrics=(pearson_correlation_first, 'mse'),
               learning_rate=1e-3, **kwargs):
     """RMSprop (the class, an instance, 'rmsprop', or any callable that returns an RMSprop when called with
@@ -546,14 +651,7 @@ class BrainModelDNN(object):
     instance or 'pearson' (the reference's decoding.py flag value), or a one-element list of one of them.  The
     history always reports loss, pearson_correlation_first and mse.  Starts a fresh optimizer state."""
     del metrics, kwargs
-    if isinstance(optimizer, str):
-      if optimizer.lower() != 'rmsprop':
-        raise NotImplementedError('Optimizer %r is not supported: only RMSprop' % optimizer)
-      optimizer = RMSprop(learning_rate=learning_rate)
-    elif not isinstance(optimizer, RMSprop) and callable(optimizer):
-      optimizer = optimizer(learning_rate=learning_rate)
-    if not isinstance(optimizer, RMSprop):
-      raise NotImplementedError('Optimizer %r is not supported: only brain_model.RMSprop' % (optimizer,))
+    optimizer = self._compiled_optimizer(optimizer, learning_rate)
     if optimizer.momentum != 0:
       raise NotImplementedError('RMSprop momentum=%g is not supported: only momentum=0' % optimizer.momentum)
     if optimizer.centered:
@@ -570,64 +668,15 @@ class BrainModelDNN(object):
     self.loss = compiled
     self._state = None
 
-  def _check_limits(self, ds):
-    c, lags = ds.c1, ds.pre + 1 + ds.post
-    hidden = self.num_hidden_list
-    problems = []
-    if len(hidden) > DNN_MAX_HIDDEN:
-      problems.append('%d hidden layers (at most %d)' % (len(hidden), DNN_MAX_HIDDEN))
-    if any(u < 1 or u > DNN_MAX_UNITS for u in hidden):
-      problems.append('hidden layers of %s units (1 .. %d)' % (hidden, DNN_MAX_UNITS))
-    if not 1 <= self._output_width <= DNN_MAX_OUTPUTS:
-      problems.append('%d outputs (1 .. %d)' % (self._output_width, DNN_MAX_OUTPUTS))
-    if lags > DNN_MAX_LAGS:
-      problems.append('pre + 1 + post = %d (at most %d)' % (lags, DNN_MAX_LAGS))
-    if c > DNN_MAX_CHANNELS and lags > 1:
-      problems.append('%d channels with temporal context (at most %d)' % (c, DNN_MAX_CHANNELS))
-    if c * lags > DNN_MAX_INPUTS:
-      problems.append('%d lagged inputs (at most %d)' % (c * lags, DNN_MAX_INPUTS))
-    if not 1 <= ds.batch_size <= DNN_MAX_BATCH:
-      problems.append('batch of %d rows (1 .. %d)' % (ds.batch_size, DNN_MAX_BATCH))
-    if c * lags != self._input_width:
-      problems.append('input_1 is %d wide, the model %d' % (c * lags, self._input_width))
-    if problems:
-      raise ValueError('BrainModelDNN: ' + '; '.join(problems))
-
-  def _as_dataset(self, data):
-    """A brain_data.Dataset as the kernels read it (mixup_batch resolved), or an iterable of (dict, y)
-    minibatches materialised once as a context-free Dataset of the same batch size."""
-    if _is_dataset(data):
-      return data.resolved()
-    if not hasattr(data, '__iter__'):
-      raise TypeError('BrainModelDNN needs a brain_data.Dataset or an iterable of (dict, y) minibatches, '
-                      'not %s.' % type(data))
-    xs, ys = [], []
-    for feats, y in data:
-      x = np.asarray(_host(feats['input_1']), np.float32)
-      xs.append(x.reshape(x.shape[0], -1))
-      ys.append(np.asarray(_host(y), np.float32).reshape(x.shape[0], -1))
-    if not xs or xs[0].shape[0] == 0:
-      raise ValueError('No minibatches in dataset')
-    x, y = np.concatenate(xs), np.concatenate(ys)
-    zeros = np.zeros((x.shape[0], 1), np.float32)
-    return brain_data.Dataset([(x, zeros, y, zeros)], xs[0].shape[0])
-
   def fit(self, input_dataset, *, epochs=1, shuffle_seed=None, **kwargs):
     """Trains `epochs` epochs over the dataset's minibatches (reference brain_model.py:548-549 -> Keras fit).
     Returns a History whose .history holds 'loss', 'pearson_correlation_first' and 'mse' per epoch: the mean
     over the epoch's steps of each step's forward-pass value, before that step's update.  'loss' is the loss
     the model was compiled for; 'mse' is reported either way."""
     del kwargs
-    if self.optimizer is None:
-      raise RuntimeError('You must compile your model before training/testing.')
-    if shuffle_seed is not None and not 0 <= int(shuffle_seed) < 2 ** 63:
-      raise ValueError('shuffle_seed must be in [0, 2^63), not %r' % (shuffle_seed,))
-    ds = self._as_dataset(input_dataset)
-    self._check_limits(ds)
-    epochs = int(epochs)
-    if ds.num_batches() == 0 or epochs <= 0:
-      return History({'loss': [], 'pearson_correlation_first': [], 'mse': []})
-    h = device.default_handle()
+    return self._fit(input_dataset, epochs, shuffle_seed)
+
+  def _train(self, ds, h, epochs, shuffle_seed):
     x, _, y, offs = ds.device_arrays(h)
     params = self._device_params(h)
     if self._state is None:
@@ -637,11 +686,7 @@ class BrainModelDNN(object):
                             ds.batch_size, epochs, opt.learning_rate, opt.rho, opt.epsilon,
                             input_offset=ds.input_offset, rows_used=ds.rows_used(), shuffle_seed=shuffle_seed,
                             handle=h, loss=self.loss)
-    return History(history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width))
-
-  # -- inference ---------------------------------------------------------------
-  def __call__(self, input_dataset):
-    return self.call(input_dataset)
+    return history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width)
 
   def call(self, input_dataset):
     """input_dataset: dict with an already-lagged 'input_1' [B, K] -> [B, D] (brain_model.py:524-528)."""
@@ -662,16 +707,12 @@ class BrainModelDNN(object):
     return device.mlp_forward(x, offs, dataset.pre, dataset.post, self.num_hidden_list, self._output_width,
                               self._device_params(h), input_offset=dataset.input_offset, handle=h)
 
-  def predict(self, dataset):
-    pred = self.predict_device(dataset).cpu().numpy()
-    return rows_of_stream(pred, dataset.file_lengths(), dataset.rows_used())
-
   def evaluate(self, dataset, **kwargs):
     """{'loss', 'pearson_correlation_first', 'mse'}: means over minibatches, as Keras evaluate (the window-sums
     route of BrainModelLinearRegression.evaluate).  'loss' is the loss the model was compiled for: the mean
     squared error, or the mean over minibatches of -(1 / B) sum_o r_o."""
     del kwargs
-    out = BrainModelLinearRegression._evaluate(self, dataset, self.loss == 'pearson')
+    out = _evaluate_regression(self, dataset, self.loss == 'pearson')
     out.setdefault('mse', out['loss'])
     return out
 
@@ -710,7 +751,7 @@ def classifier_history_from_sums(sums, rows, d):
           'accuracy': [float(v) for v in np.mean(s[..., 0] / n, axis=-1)]}
 
 
-class BrainModelClassifier(object):
+class BrainModelClassifier(_BrainModelMlp):
   """The match-mismatch classifier trained on the GPU (reference brain_model.py:554-620): the concatenation of
   `input_1` and `input_2` through Dense layers of `num_hidden_list` ReLU units into a sigmoid output layer,
   trained by minibatch Adam on the binary cross-entropy.  It decides directly whether a stretch of EEG
@@ -730,55 +771,22 @@ class BrainModelClassifier(object):
       fan_in = K1 + K2 drawn with numpy.random.default_rng(seed); in-order minibatches or the Feistel shuffle).
   """
 
+  _VIEWS = _BrainModelMlp._VIEWS + (('input_2', '_input2_width', 'c2', 'pre2', 'post2'),)
+  _OPTIMIZER = Adam
+  _HISTORY_KEYS = ('loss', 'accuracy')
+  _DATASET_ERROR = TypeError
+
   def __init__(self, input_dataset, num_hidden_list=None, *, seed=0, **kwargs):
-    kwargs.pop('tensorboard_dir', None)
-    del kwargs
-    if not _is_dataset(input_dataset):
-      raise TypeError('Dataset must be a tf.data.datasert, not a %s' % type(input_dataset))
-    if num_hidden_list is None:
-      num_hidden_list = []
-    if not isinstance(num_hidden_list, list):
-      raise TypeError('Num_hidden_list must be an list, not a %s.' % type(num_hidden_list))
-    self._input_width = int(input_dataset.element_spec[0]['input_1'].shape[-1])
-    self._input2_width = int(input_dataset.element_spec[0]['input_2'].shape[-1])
-    self._output_width = int(input_dataset.element_spec[1].shape[-1])
-    self.num_hidden_list = [int(u) for u in num_hidden_list]
-    self._widths = [self._input_width + self._input2_width] + self.num_hidden_list + [self._output_width]
-    rng = np.random.default_rng(seed)
-    weights = []
-    for fan_in, fan_out in zip(self._widths[:-1], self._widths[1:]):
-      limit = np.sqrt(6.0 / (fan_in + fan_out))
-      weights += [rng.uniform(-limit, limit, (fan_in, fan_out)).astype(np.float32),
-                  np.zeros((fan_out,), np.float32)]
-    self._host_weights = weights
-    self._params = None        # packed device parameters (the truth once on the device)
-    self._state = None         # Adam's m, then v, each in the parameters' layout
-    self._updates = 0          # Adam's t: updates applied since compile
-    self.optimizer = None
-    self.metrics_names = ['loss', 'accuracy']
+    super().__init__(input_dataset, num_hidden_list, seed=seed, **kwargs)
+    self._updates = 0          # Adam's t: updates applied since compile (_state: Adam's m, then v)
 
-  # -- parameters: the packed layout and the accessors of BrainModelDNN (W1's rows: input_1's, then input_2's)
-  _shapes = BrainModelDNN._shapes
-  _device_params = BrainModelDNN._device_params
-  get_weights = BrainModelDNN.get_weights
-  set_weights = BrainModelDNN.set_weights
-  weight_matrices = BrainModelDNN.weight_matrices
-
-  # -- training ----------------------------------------------------------------
   def compile(self, optimizer=Adam, loss=BinaryCrossentropy(), metrics='accuracy', learning_rate=1e-3, **kwargs):
     """Adam (the class, an instance, 'adam', or any callable that returns an Adam when called with
     learning_rate=, as the reference's `if callable(optimizer)`) on the binary cross-entropy (a
     BinaryCrossentropy instance, 'binary_crossentropy', or a one-element list of either).  The history always
     reports loss and accuracy.  Starts a fresh optimizer state (t = 0, m = v = 0)."""
     del metrics, kwargs
-    if isinstance(optimizer, str):
-      if optimizer.lower() != 'adam':
-        raise NotImplementedError('Optimizer %r is not supported: only Adam' % optimizer)
-      optimizer = Adam(learning_rate=learning_rate)
-    elif not isinstance(optimizer, Adam) and callable(optimizer):
-      optimizer = optimizer(learning_rate=learning_rate)
-    if not isinstance(optimizer, Adam):
-      raise NotImplementedError('Optimizer %r is not supported: only brain_model.Adam' % (optimizer,))
+    optimizer = self._compiled_optimizer(optimizer, learning_rate)
     if optimizer.amsgrad:
       raise NotImplementedError('Adam with amsgrad=True is not supported')
     losses = list(loss) if isinstance(loss, (list, tuple)) else [loss]
@@ -789,50 +797,8 @@ class BrainModelClassifier(object):
     self._updates = 0
 
   def _check_limits(self, ds):
-    c, lags = ds.c1, ds.pre + 1 + ds.post
-    c2, lags2 = ds.c2, ds.pre2 + 1 + ds.post2
-    hidden = self.num_hidden_list
-    problems = []
-    if len(hidden) > DNN_MAX_HIDDEN:
-      problems.append('%d hidden layers (at most %d)' % (len(hidden), DNN_MAX_HIDDEN))
-    if any(u < 1 or u > DNN_MAX_UNITS for u in hidden):
-      problems.append('hidden layers of %s units (1 .. %d)' % (hidden, DNN_MAX_UNITS))
-    if not 1 <= self._output_width <= DNN_MAX_OUTPUTS:
-      problems.append('%d outputs (1 .. %d)' % (self._output_width, DNN_MAX_OUTPUTS))
-    if lags > DNN_MAX_LAGS or lags2 > DNN_MAX_LAGS:
-      problems.append('pre + 1 + post = %d / %d (at most %d)' % (lags, lags2, DNN_MAX_LAGS))
-    if (c > DNN_MAX_CHANNELS and lags > 1) or (c2 > DNN_MAX_CHANNELS and lags2 > 1):
-      problems.append('%d / %d channels with temporal context (at most %d)' % (c, c2, DNN_MAX_CHANNELS))
-    if c * lags + c2 * lags2 > DNN_MAX_INPUTS:
-      problems.append('%d lagged inputs (at most %d)' % (c * lags + c2 * lags2, DNN_MAX_INPUTS))
-    if not 1 <= ds.batch_size <= DNN_MAX_BATCH:
-      problems.append('batch of %d rows (1 .. %d)' % (ds.batch_size, DNN_MAX_BATCH))
-    if c * lags != self._input_width or c2 * lags2 != self._input2_width:
-      problems.append('input_1 / input_2 are %d / %d wide, the model %d / %d' % (
-          c * lags, c2 * lags2, self._input_width, self._input2_width))
-    if ds.d != self._output_width:
-      problems.append('the output is %d wide, the model %d' % (ds.d, self._output_width))
-    if problems:
-      raise ValueError('BrainModelClassifier: ' + '; '.join(problems))
-
-  def _as_dataset(self, data):
-    """A brain_data.Dataset as the kernels read it (mixup_batch resolved: input_2 then carries its context), or
-    an iterable of (dict, y) minibatches materialised once as a context-free Dataset of the same batch size."""
-    if _is_dataset(data):
-      return data.resolved()
-    if not hasattr(data, '__iter__'):
-      raise TypeError('BrainModelClassifier needs a brain_data.Dataset or an iterable of (dict, y) minibatches, '
-                      'not %s.' % type(data))
-    xs, x2s, ys = [], [], []
-    for feats, y in data:
-      x = np.asarray(_host(feats['input_1']), np.float32)
-      xs.append(x.reshape(x.shape[0], -1))
-      x2s.append(np.asarray(_host(feats['input_2']), np.float32).reshape(x.shape[0], -1))
-      ys.append(np.asarray(_host(y), np.float32).reshape(x.shape[0], -1))
-    if not xs or xs[0].shape[0] == 0:
-      raise ValueError('No minibatches in dataset')
-    x, x2, y = np.concatenate(xs), np.concatenate(x2s), np.concatenate(ys)
-    return brain_data.Dataset([(x, x2, y, np.zeros((x.shape[0], 1), np.float32))], xs[0].shape[0])
+    super()._check_limits(ds, [] if ds.d == self._output_width else [
+        'the output is %d wide, the model %d' % (ds.d, self._output_width)])
 
   def _run(self, ds, h, epochs, update, shuffle_seed=None):
     x, x2, y, offs = ds.device_arrays(h)
@@ -848,21 +814,14 @@ class BrainModelClassifier(object):
     Returns a History whose .history holds 'loss' and 'accuracy' per epoch: the mean over the epoch's steps of
     each step's forward-pass value, before that step's update."""
     del kwargs
-    if self.optimizer is None:
-      raise RuntimeError('You must compile your model before training/testing.')
-    if shuffle_seed is not None and not 0 <= int(shuffle_seed) < 2 ** 63:
-      raise ValueError('shuffle_seed must be in [0, 2^63), not %r' % (shuffle_seed,))
-    ds = self._as_dataset(input_dataset)
-    self._check_limits(ds)
-    epochs = int(epochs)
-    if ds.num_batches() == 0 or epochs <= 0:
-      return History({'loss': [], 'accuracy': []})
-    h = device.default_handle()
+    return self._fit(input_dataset, epochs, shuffle_seed)
+
+  def _train(self, ds, h, epochs, shuffle_seed):
     if self._state is None:
       self._state = h.zeros((2 * int(self._device_params(h).numel()),))
     sums = self._run(ds, h, epochs, True, shuffle_seed)
     self._updates += epochs * ds.num_batches()
-    return History(classifier_history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width))
+    return classifier_history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width)
 
   def evaluate(self, dataset, **kwargs):
     """{'loss', 'accuracy'}: the means over the dataset's minibatches of the binary cross-entropy and the binary
@@ -876,10 +835,6 @@ class BrainModelClassifier(object):
     sums = self._run(ds, h, 1, False)
     hist = classifier_history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width)
     return {'loss': hist['loss'][0], 'accuracy': hist['accuracy'][0]}
-
-  # -- inference ---------------------------------------------------------------
-  def __call__(self, input_dataset):
-    return self.call(input_dataset)
 
   def call(self, input_dataset):
     """input_dataset: dict with already-lagged 'input_1' [B, K1] and 'input_2' [B, K2] -> probabilities [B, D]
@@ -903,10 +858,6 @@ class BrainModelClassifier(object):
     x, x2, _, offs = ds.device_arrays(h)
     return device.mlpc_forward(x, x2, offs, ds.pre, ds.post, ds.pre2, ds.post2, self.num_hidden_list,
                                self._output_width, self._device_params(h), input_offset=ds.input_offset, handle=h)
-
-  def predict(self, dataset):
-    pred = self.predict_device(dataset).cpu().numpy()
-    return rows_of_stream(pred, dataset.file_lengths(), dataset.rows_used())
 
 
 def _evaluate_minibatches(batches, h, predict, truth_from_y, metric_name='pearson_correlation_first',
@@ -939,10 +890,8 @@ def _evaluate_minibatches(batches, h, predict, truth_from_y, metric_name='pearso
         plosses.append(float(pearson_loss_from_sums(s, rows)))
     else:
       losses.append(float(r[0]))
+  mean = lambda values: float(np.mean(values)) if metrics else float('nan')
+  out = {'loss': mean(plosses if pearson_loss else losses), metric_name: mean(metrics)}
   if pearson_loss:
-    if not metrics:
-      return {'loss': float('nan'), metric_name: float('nan'), 'mse': float('nan')}
-    return {'loss': float(np.mean(plosses)), metric_name: float(np.mean(metrics)), 'mse': float(np.mean(losses))}
-  if not metrics:
-    return {'loss': float('nan'), metric_name: float('nan')}
-  return {'loss': float(np.mean(losses)), metric_name: float(np.mean(metrics))}
+    out['mse'] = mean(losses)
+  return out

@@ -29,6 +29,10 @@
 //   head<2>  every workgroup sums the <= 32 partial moments in workgroup order, forms r_o and the two
 //            coefficients of dL/dp per column in float64, recomputes its rows' forward (the same code on the
 //            same inputs: the same bits) and runs the backward pass.  No workgroup waits for another.
+//
+// Host side (from struct MlpPlan on): every exported entry point packs its arguments into one MlpCall and calls
+// mlp_train, mlp_grad or mlp_forward; each of those checks the call (mlp_check_and_plan first, then its own
+// arguments, in the order a caller observes), lays out the scratch and queues the launches.
 #include "td_common.h"
 
 #include <cmath>
@@ -604,66 +608,85 @@ struct MlpPlan {
   int act_floats = 0, maxw = 0;
 };
 
-// the classifier's second input (NULL for the regressor)
-struct MlpView2 {
-  const float* x2;
-  int64_t ldx2;
-  int c2, pre2, post2;
+// What a caller passes, as the prototypes of include/td_hotpath.h name it.  Every exported entry point fills one
+// and calls mlp_train / mlp_grad / mlp_forward.
+struct MlpView {
+  const float* x;
+  int64_t ldx;
+  int c, pre, post;
 };
 
-int mlp_check_and_plan(td_handle* h, const char* fn, const float* x_dev, int64_t ldx, const int64_t* offs, int nf,
-                       int c, int pre, int post, int input_offset, int d, const int* hidden, int num_hidden,
-                       int batch, MlpPlan* plan, const MlpView2* v2 = nullptr) {
+struct MlpCall {
+  MlpView v1, v2;                 // v2.x == nullptr: no second view
+  const int64_t* file_offsets;    // host
+  int num_files, input_offset;
+  const int64_t* rows_used;       // host, or nullptr
+  const float* y;
+  int64_t ldy;
+  int d;
+  const int* hidden;              // host
+  int num_hidden;
+  int batch_rows;
+  int loss;                       // 0 = mse, 1 = the Pearson correlation loss
+  bool classifier;                // td_mlpc_*: the second view is required; sigmoid output, binary cross-entropy
+};
+
+int mlp_check_and_plan(td_handle* h, const char* fn, const MlpCall& a, MlpPlan* plan) {
+  const MlpView &v1 = a.v1, &v2 = a.v2;
+  const int64_t* offs = a.file_offsets;
+  const int nf = a.num_files, c = v1.c, d = a.d, num_hidden = a.num_hidden, batch = a.batch_rows;
   if (!h) return td_fail(h, TD_ERR_INVALID, "%s: NULL handle", fn);
-  TD_REQUIRE(h, x_dev && offs && nf >= 1, "%s: NULL argument or no files", fn);
-  TD_REQUIRE(h, c >= 1 && pre >= 0 && post >= 0, "%s: bad sizes", fn);
-  const int64_t lags = (int64_t)pre + 1 + post;
+  TD_REQUIRE(h, v1.x && offs && nf >= 1, "%s: NULL argument or no files", fn);
+  TD_REQUIRE(h, c >= 1 && v1.pre >= 0 && v1.post >= 0, "%s: bad sizes", fn);
+  const int64_t lags = (int64_t)v1.pre + 1 + v1.post;
   TD_REQUIRE(h, lags <= kMlpMaxLags, "%s: pre + 1 + post = %lld exceeds %d", fn, (long long)lags, kMlpMaxLags);
   TD_REQUIRE(h, c <= kMlpMaxC || lags == 1, "%s: %d channels exceed %d (only context-free input may be wider)", fn,
              c, kMlpMaxC);
   TD_REQUIRE(h, c * lags <= kMlpMaxK, "%s: %lld lagged inputs exceed %d", fn, (long long)(c * lags), kMlpMaxK);
-  TD_REQUIRE(h, ldx >= c, "%s: leading dimension of x too small", fn);
+  TD_REQUIRE(h, v1.ldx >= c, "%s: leading dimension of x too small", fn);
   int64_t k2 = 0;
-  if (v2) {
-    TD_REQUIRE(h, v2->x2, "%s: NULL second input", fn);
-    TD_REQUIRE(h, v2->c2 >= 1 && v2->pre2 >= 0 && v2->post2 >= 0, "%s: bad sizes of the second input", fn);
-    const int64_t lags2 = (int64_t)v2->pre2 + 1 + v2->post2;
+  if (a.classifier) {
+    TD_REQUIRE(h, v2.x, "%s: NULL second input", fn);
+    TD_REQUIRE(h, v2.c >= 1 && v2.pre >= 0 && v2.post >= 0, "%s: bad sizes of the second input", fn);
+    const int64_t lags2 = (int64_t)v2.pre + 1 + v2.post;
     TD_REQUIRE(h, lags2 <= kMlpMaxLags, "%s: pre2 + 1 + post2 = %lld exceeds %d", fn, (long long)lags2, kMlpMaxLags);
-    TD_REQUIRE(h, v2->c2 <= kMlpMaxC || lags2 == 1,
-               "%s: %d channels of the second input exceed %d (only context-free input may be wider)", fn, v2->c2,
+    TD_REQUIRE(h, v2.c <= kMlpMaxC || lags2 == 1,
+               "%s: %d channels of the second input exceed %d (only context-free input may be wider)", fn, v2.c,
                kMlpMaxC);
-    k2 = v2->c2 * lags2;
+    k2 = v2.c * lags2;
     TD_REQUIRE(h, k2 <= kMlpMaxK && c * lags + k2 <= kMlpMaxK, "%s: %lld lagged inputs of both views exceed %d", fn,
                (long long)(c * lags + k2), kMlpMaxK);
-    TD_REQUIRE(h, v2->ldx2 >= v2->c2, "%s: leading dimension of x2 too small", fn);
+    TD_REQUIRE(h, v2.ldx >= v2.c, "%s: leading dimension of x2 too small", fn);
   }
   TD_REQUIRE(h, num_hidden >= 0 && num_hidden <= kMlpMaxHidden, "%s: %d hidden layers (at most %d)", fn, num_hidden,
              kMlpMaxHidden);
-  TD_REQUIRE(h, num_hidden == 0 || hidden, "%s: NULL hidden widths", fn);
+  TD_REQUIRE(h, num_hidden == 0 || a.hidden, "%s: NULL hidden widths", fn);
   for (int i = 0; i < num_hidden; ++i)
-    TD_REQUIRE(h, hidden[i] >= 1 && hidden[i] <= kMlpMaxWidth, "%s: hidden layer of %d units (1 .. %d)", fn,
-               hidden[i], kMlpMaxWidth);
+    TD_REQUIRE(h, a.hidden[i] >= 1 && a.hidden[i] <= kMlpMaxWidth, "%s: hidden layer of %d units (1 .. %d)", fn,
+               a.hidden[i], kMlpMaxWidth);
   TD_REQUIRE(h, d >= 1 && d <= kMlpMaxD, "%s: %d outputs (1 .. %d)", fn, d, kMlpMaxD);
   TD_REQUIRE(h, batch >= 1 && batch <= kFwdChunk, "%s: batch of %d rows", fn, batch);
   TD_REQUIRE(h, offs[0] == 0, "%s: file offsets must start at 0", fn);
   for (int f = 0; f < nf; ++f) TD_REQUIRE(h, offs[f + 1] >= offs[f], "%s: file offsets decrease", fn);
   TD_REQUIRE(h, offs[nf] < (1LL << 31), "%s: more than 2^31 rows", fn);
+  TD_REQUIRE(h, a.loss == 0 || a.loss == 1, "%s: loss %d (0 = mse, 1 = Pearson)", fn, a.loss);
   MlpGeom& g = plan->g;
   memset(&g, 0, sizeof(g));
-  g.x = x_dev; g.ldx = ldx; g.nf = nf;
-  g.c = c; g.pre = pre; g.lags = (int)lags; g.k = (int)(c * lags + k2);
+  g.x = v1.x; g.ldx = v1.ldx; g.nf = nf;
+  g.c = c; g.pre = v1.pre; g.lags = (int)lags; g.k = (int)(c * lags + k2);
   g.k1 = (int)(c * lags);
   g.c2 = 1;
-  if (v2) {
-    g.x2 = v2->x2; g.ldx2 = v2->ldx2; g.c2 = v2->c2; g.pre2 = v2->pre2;
+  if (a.classifier) {
+    g.x2 = v2.x; g.ldx2 = v2.ldx; g.c2 = v2.c; g.pre2 = v2.pre;
     g.bce = 1;
   }
-  g.dx = input_offset > 0 ? input_offset : 0;
-  g.dy = input_offset < 0 ? -input_offset : 0;
+  g.pearson = a.loss;
+  g.dx = a.input_offset > 0 ? a.input_offset : 0;
+  g.dy = a.input_offset < 0 ? -a.input_offset : 0;
   g.dxy = g.dy - g.dx;
   g.nl = num_hidden + 1;
   g.w[0] = g.k;
-  for (int i = 0; i < num_hidden; ++i) g.w[i + 1] = hidden[i];
+  for (int i = 0; i < num_hidden; ++i) g.w[i + 1] = a.hidden[i];
   g.w[g.nl] = d;
   int at = 0;
   for (int l = 1; l <= g.nl; ++l) {
@@ -766,28 +789,27 @@ int mlp_work(td_handle* h, const MlpPlan& plan, int nf, MlpWork* w) {
 }
 
 // the stream's rows per file (rows_used, else the zipped lengths) as offsets
-int mlp_stream_offsets(td_handle* h, const char* fn, const int64_t* offs, int nf, int input_offset,
-                       const int64_t* rows_used, std::vector<long long>* so) {
-  const int64_t off = input_offset < 0 ? -(int64_t)input_offset : input_offset;
-  so->assign(nf + 1, 0);
-  for (int f = 0; f < nf; ++f) {
-    const int64_t n = offs[f + 1] - offs[f];
+int mlp_stream_offsets(td_handle* h, const char* fn, const MlpCall& a, std::vector<long long>* so) {
+  const int64_t off = a.input_offset < 0 ? -(int64_t)a.input_offset : a.input_offset;
+  so->assign(a.num_files + 1, 0);
+  for (int f = 0; f < a.num_files; ++f) {
+    const int64_t n = a.file_offsets[f + 1] - a.file_offsets[f];
     const int64_t z = n - off > 0 ? n - off : 0;
     int64_t u = z;
-    if (rows_used) {
-      TD_REQUIRE(h, rows_used[f] >= 0 && rows_used[f] <= z, "%s: rows_used[%d] = %lld, the file has %lld rows", fn,
-                 f, (long long)rows_used[f], (long long)z);
-      u = rows_used[f];
+    if (a.rows_used) {
+      TD_REQUIRE(h, a.rows_used[f] >= 0 && a.rows_used[f] <= z, "%s: rows_used[%d] = %lld, the file has %lld rows",
+                 fn, f, (long long)a.rows_used[f], (long long)z);
+      u = a.rows_used[f];
     }
     (*so)[f + 1] = (*so)[f] + u;
   }
   return TD_OK;
 }
 
-int mlp_setup(td_handle* h, MlpPlan* plan, int nf, const int64_t* offs, const std::vector<long long>& so,
-              MlpWork* w) {
+int mlp_setup(td_handle* h, MlpPlan* plan, const MlpCall& a, const std::vector<long long>& so, MlpWork* w) {
+  const int nf = a.num_files;
   TD_TRY(mlp_work(h, *plan, nf, w));
-  TD_TRY(td_upload_async(h, offs, sizeof(long long) * (nf + 1), w->file_offs));
+  TD_TRY(td_upload_async(h, a.file_offsets, sizeof(long long) * (nf + 1), w->file_offs));
   if (!so.empty()) TD_TRY(td_upload_async(h, so.data(), sizeof(long long) * (nf + 1), w->stream_offs));
   plan->g.file_offs = w->file_offs;
   plan->g.stream_offs = so.empty() ? w->file_offs : w->stream_offs;
@@ -842,14 +864,16 @@ void mlp_set_update(SlabArgs* sa, const MlpOpt& opt, int64_t index) {
   sa->lr = (float)(opt.lr * std::sqrt(1.0 - std::pow(opt.b2, t)) / (1.0 - std::pow(opt.b1, t)));
 }
 
-// plan: checked, with its second view if any.  Queues every launch of the call.
-int mlp_train_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* file_offsets_host, int num_files,
-                  int input_offset, const int64_t* rows_used_host, const float* y_dev, int64_t ldy, int d,
-                  int batch_rows, int epochs, float* params_dev, float* state_dev, const MlpOpt& opt,
-                  int64_t shuffle_seed, double* stats_dev) {
+// Checks the call, then queues every launch of it.
+int mlp_train(td_handle* h, const char* fn, const MlpCall& a, int epochs, float* params_dev, float* state_dev,
+              const MlpOpt& opt, int64_t shuffle_seed, double* stats_dev) {
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, a, &plan));
+  const int batch_rows = a.batch_rows;
   const bool update = opt.update != kUpdNone;
   TD_REQUIRE(h, batch_rows <= kMlpMaxB, "%s: batch of %d rows exceeds %d", fn, batch_rows, kMlpMaxB);
-  TD_REQUIRE(h, y_dev && params_dev && (state_dev || !update) && ldy >= d, "%s: NULL argument or ldy too small", fn);
+  TD_REQUIRE(h, a.y && params_dev && (state_dev || !update) && a.ldy >= a.d, "%s: NULL argument or ldy too small",
+             fn);
   TD_REQUIRE(h, epochs >= 0, "%s: negative epoch count", fn);
   TD_REQUIRE(h, std::isfinite(opt.lr) && std::isfinite(opt.b1) && std::isfinite(opt.b2) && std::isfinite(opt.eps),
              "%s: non-finite optimizer setting", fn);
@@ -857,19 +881,19 @@ int mlp_train_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* fi
     TD_REQUIRE(h, opt.b1 >= 0.0 && opt.b1 < 1.0 && opt.b2 >= 0.0 && opt.b2 < 1.0 && opt.step0 >= 0,
                "%s: Adam needs 0 <= beta < 1 and step0 >= 0", fn);
   std::vector<long long> so;
-  TD_TRY(mlp_stream_offsets(h, fn, file_offsets_host, num_files, input_offset, rows_used_host, &so));
-  const long long n_rows = so[num_files];
+  TD_TRY(mlp_stream_offsets(h, fn, a, &so));
+  const long long n_rows = so[a.num_files];
   TD_REQUIRE(h, n_rows >= 1, "%s: no rows to train on", fn);
   const int steps = (int)td_ceil_div(n_rows, batch_rows);
   TD_REQUIRE(h, epochs == 0 || stats_dev, "%s: NULL stats buffer", fn);
   if (epochs == 0) return TD_OK;
-  plan.g.y = y_dev; plan.g.ldy = ldy;
+  plan.g.y = a.y; plan.g.ldy = a.ldy;
   plan.g.n_rows = n_rows;
   plan.g.shuffle = shuffle_seed >= 0;
   plan.g.seed_lo = (unsigned)((uint64_t)shuffle_seed & 0xffffffffu);
   plan.g.seed_hi = (unsigned)((uint64_t)shuffle_seed >> 32);
   MlpWork w;
-  TD_TRY(mlp_setup(h, &plan, num_files, file_offsets_host, so, &w));
+  TD_TRY(mlp_setup(h, &plan, a, so, &w));
   // work on copies: the caller's parameters change only when every launch has been queued
   const size_t pbytes = sizeof(float) * plan.g.n_params;
   const size_t sbytes = opt.update == kUpdAdam ? 2 * pbytes : pbytes;
@@ -914,20 +938,22 @@ int mlp_train_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* fi
   return TD_OK;
 }
 
-int mlp_grad_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* file_offsets_host, int num_files,
-                 int input_offset, const int64_t* rows_used_host, const float* y_dev, int64_t ldy, int d,
-                 int batch_rows, int batch_index, const float* params_dev, float* grad_dev, double* stats_dev) {
-  TD_REQUIRE(h, batch_rows <= kMlpMaxB, "%s: batch of %d rows exceeds %d", fn, batch_rows, kMlpMaxB);
-  TD_REQUIRE(h, y_dev && params_dev && grad_dev && stats_dev && ldy >= d, "%s: NULL argument or ldy too small", fn);
+int mlp_grad(td_handle* h, const char* fn, const MlpCall& a, int batch_index, const float* params_dev,
+             float* grad_dev, double* stats_dev) {
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, a, &plan));
+  TD_REQUIRE(h, a.batch_rows <= kMlpMaxB, "%s: batch of %d rows exceeds %d", fn, a.batch_rows, kMlpMaxB);
+  TD_REQUIRE(h, a.y && params_dev && grad_dev && stats_dev && a.ldy >= a.d, "%s: NULL argument or ldy too small",
+             fn);
   std::vector<long long> so;
-  TD_TRY(mlp_stream_offsets(h, fn, file_offsets_host, num_files, input_offset, rows_used_host, &so));
-  const long long n_rows = so[num_files];
-  TD_REQUIRE(h, batch_index >= 0 && (long long)batch_index * batch_rows < n_rows,
+  TD_TRY(mlp_stream_offsets(h, fn, a, &so));
+  const long long n_rows = so[a.num_files];
+  TD_REQUIRE(h, batch_index >= 0 && (long long)batch_index * a.batch_rows < n_rows,
              "%s: minibatch %d is outside the stream's %lld rows", fn, batch_index, n_rows);
-  plan.g.y = y_dev; plan.g.ldy = ldy;
+  plan.g.y = a.y; plan.g.ldy = a.ldy;
   plan.g.n_rows = n_rows;
   MlpWork w;
-  TD_TRY(mlp_setup(h, &plan, num_files, file_offsets_host, so, &w));
+  TD_TRY(mlp_setup(h, &plan, a, so, &w));
   TD_HIP(h, hipMemcpyAsync(w.params, params_dev, sizeof(float) * plan.g.n_params, hipMemcpyDeviceToDevice,
                            h->stream));
   SlabArgs sa;
@@ -947,16 +973,19 @@ int mlp_grad_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* fil
   return TD_OK;
 }
 
-int mlp_forward_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* file_offsets_host, int num_files,
-                    int d, const float* params_dev, float* out_dev, int64_t ldout) {
-  TD_REQUIRE(h, params_dev && out_dev && ldout >= d, "%s: NULL argument or ldout too small", fn);
-  const long long n_rows = file_offsets_host[num_files];
+// (a.batch_rows: the rows of a chunk, kFwdChunk)
+int mlp_forward(td_handle* h, const char* fn, const MlpCall& a, const float* params_dev, float* out_dev,
+                int64_t ldout) {
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, a, &plan));
+  TD_REQUIRE(h, params_dev && out_dev && ldout >= a.d, "%s: NULL argument or ldout too small", fn);
+  const long long n_rows = a.file_offsets[a.num_files];
   if (n_rows == 0) return TD_OK;
   // every row of x: output row file_offsets[f] + t is frame t of file f (as td_predict_fir)
   plan.g.fwd = 1;
   plan.g.n_rows = n_rows;
   MlpWork w;
-  TD_TRY(mlp_setup(h, &plan, num_files, file_offsets_host, std::vector<long long>(), &w));
+  TD_TRY(mlp_setup(h, &plan, a, std::vector<long long>(), &w));
   SlabArgs sa;
   HeadArgs ha;
   mlp_fill(plan, w, &sa, &ha);
@@ -976,51 +1005,17 @@ int mlp_forward_run(td_handle* h, const char* fn, MlpPlan& plan, const int64_t* 
 
 }  // namespace
 
-namespace {
-
-// loss: 0 = mse, 1 = the Pearson correlation loss
-int mlp_loss_plan(td_handle* h, const char* fn, int loss, MlpPlan* plan) {
-  TD_REQUIRE(h, loss == 0 || loss == 1, "%s: loss %d (0 = mse, 1 = Pearson)", fn, loss);
-  plan->g.pearson = loss;
-  return TD_OK;
-}
-
-int mlp_train_entry(td_handle* h, const char* fn, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host,
-                    int num_files, int c, int pre, int post, int input_offset, const int64_t* rows_used_host,
-                    const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows,
-                    int epochs, float* params_dev, float* state_dev, float lr, float rho, float eps,
-                    int64_t shuffle_seed, double* stats_dev, int loss) {
-  MlpPlan plan;
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, batch_rows, &plan));
-  TD_TRY(mlp_loss_plan(h, fn, loss, &plan));
-  const MlpOpt opt = {kUpdRmsprop, lr, rho, 0.0, eps, 0};
-  return mlp_train_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
-                       batch_rows, epochs, params_dev, state_dev, opt, shuffle_seed, stats_dev);
-}
-
-int mlp_grad_entry(td_handle* h, const char* fn, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host,
-                   int num_files, int c, int pre, int post, int input_offset, const int64_t* rows_used_host,
-                   const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows,
-                   int batch_index, const float* params_dev, float* grad_dev, double* stats_dev, int loss) {
-  MlpPlan plan;
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, batch_rows, &plan));
-  TD_TRY(mlp_loss_plan(h, fn, loss, &plan));
-  return mlp_grad_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
-                      batch_rows, batch_index, params_dev, grad_dev, stats_dev);
-}
-
-}  // namespace
-
+// The exported entry points: each packs its arguments into an MlpCall, group by group in the struct's order
+// ({first view}, {second view}, files, targets, network, step, loss, classifier).
 int td_mlp_train(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
                  int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
                  int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int epochs,
                  float* params_dev, float* state_dev, float lr, float rho, float eps, int64_t shuffle_seed,
                  double* stats_dev) {
-  return mlp_train_entry(h, "td_mlp_train", x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset,
-                         rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, epochs, params_dev,
-                         state_dev, lr, rho, eps, shuffle_seed, stats_dev, 0);
+  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, rows_used_host,
+                     y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, false};
+  return mlp_train(h, "td_mlp_train", a, epochs, params_dev, state_dev, {kUpdRmsprop, lr, rho, 0.0, eps, 0},
+                   shuffle_seed, stats_dev);
 }
 
 int td_mlp_train_loss(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host,
@@ -1028,37 +1023,36 @@ int td_mlp_train_loss(td_handle* h, const float* x_dev, int64_t ldx, const int64
                       const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden,
                       int batch_rows, int epochs, float* params_dev, float* state_dev, float lr, float rho,
                       float eps, int64_t shuffle_seed, double* stats_dev, int loss) {
-  return mlp_train_entry(h, "td_mlp_train_loss", x_dev, ldx, file_offsets_host, num_files, c, pre, post,
-                         input_offset, rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, epochs,
-                         params_dev, state_dev, lr, rho, eps, shuffle_seed, stats_dev, loss);
+  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, rows_used_host,
+                     y_dev, ldy, d, hidden_host, num_hidden, batch_rows, loss, false};
+  return mlp_train(h, "td_mlp_train_loss", a, epochs, params_dev, state_dev, {kUpdRmsprop, lr, rho, 0.0, eps, 0},
+                   shuffle_seed, stats_dev);
 }
 
 int td_mlp_grad(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
                 int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
                 int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int batch_index,
                 const float* params_dev, float* grad_dev, double* stats_dev) {
-  return mlp_grad_entry(h, "td_mlp_grad", x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset,
-                        rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, batch_index, params_dev,
-                        grad_dev, stats_dev, 0);
+  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, rows_used_host,
+                     y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, false};
+  return mlp_grad(h, "td_mlp_grad", a, batch_index, params_dev, grad_dev, stats_dev);
 }
 
 int td_mlp_grad_loss(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host,
                      int num_files, int c, int pre, int post, int input_offset, const int64_t* rows_used_host,
                      const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows,
                      int batch_index, const float* params_dev, float* grad_dev, double* stats_dev, int loss) {
-  return mlp_grad_entry(h, "td_mlp_grad_loss", x_dev, ldx, file_offsets_host, num_files, c, pre, post,
-                        input_offset, rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows,
-                        batch_index, params_dev, grad_dev, stats_dev, loss);
+  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, rows_used_host,
+                     y_dev, ldy, d, hidden_host, num_hidden, batch_rows, loss, false};
+  return mlp_grad(h, "td_mlp_grad_loss", a, batch_index, params_dev, grad_dev, stats_dev);
 }
 
 int td_mlp_forward(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
                    int c, int pre, int post, int input_offset, int d, const int* hidden_host, int num_hidden,
                    const float* params_dev, float* out_dev, int64_t ldout) {
-  static const char* fn = "td_mlp_forward";
-  MlpPlan plan;
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, kFwdChunk, &plan));
-  return mlp_forward_run(h, fn, plan, file_offsets_host, num_files, d, params_dev, out_dev, ldout);
+  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, nullptr,
+                     nullptr, 0, d, hidden_host, num_hidden, kFwdChunk, 0, false};
+  return mlp_forward(h, "td_mlp_forward", a, params_dev, out_dev, ldout);
 }
 
 int td_mlpc_train(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
@@ -1067,14 +1061,10 @@ int td_mlpc_train(td_handle* h, const float* x_dev, int64_t ldx, const float* x2
                   const int* hidden_host, int num_hidden, int batch_rows, int epochs, float* params_dev,
                   float* state_dev, double lr, double beta1, double beta2, double eps, int64_t step0, int update,
                   int64_t shuffle_seed, double* stats_dev) {
-  static const char* fn = "td_mlpc_train";
-  MlpPlan plan;
-  const MlpView2 v2 = {x2_dev, ldx2, c2, pre2, post2};
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, batch_rows, &plan, &v2));
-  const MlpOpt opt = {update ? kUpdAdam : kUpdNone, lr, beta1, beta2, eps, step0};
-  return mlp_train_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
-                       batch_rows, epochs, params_dev, state_dev, opt, shuffle_seed, stats_dev);
+  const MlpCall a = {{x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host, num_files,
+                     input_offset, rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, true};
+  return mlp_train(h, "td_mlpc_train", a, epochs, params_dev, state_dev,
+                   {update ? kUpdAdam : kUpdNone, lr, beta1, beta2, eps, step0}, shuffle_seed, stats_dev);
 }
 
 int td_mlpc_grad(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
@@ -1082,23 +1072,16 @@ int td_mlpc_grad(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_
                  int post2, int input_offset, const int64_t* rows_used_host, const float* y_dev, int64_t ldy, int d,
                  const int* hidden_host, int num_hidden, int batch_rows, int batch_index, const float* params_dev,
                  float* grad_dev, double* stats_dev) {
-  static const char* fn = "td_mlpc_grad";
-  MlpPlan plan;
-  const MlpView2 v2 = {x2_dev, ldx2, c2, pre2, post2};
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, batch_rows, &plan, &v2));
-  return mlp_grad_run(h, fn, plan, file_offsets_host, num_files, input_offset, rows_used_host, y_dev, ldy, d,
-                      batch_rows, batch_index, params_dev, grad_dev, stats_dev);
+  const MlpCall a = {{x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host, num_files,
+                     input_offset, rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, true};
+  return mlp_grad(h, "td_mlpc_grad", a, batch_index, params_dev, grad_dev, stats_dev);
 }
 
 int td_mlpc_forward(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
                     const int64_t* file_offsets_host, int num_files, int c, int pre, int post, int c2, int pre2,
                     int post2, int input_offset, int d, const int* hidden_host, int num_hidden,
                     const float* params_dev, float* out_dev, int64_t ldout) {
-  static const char* fn = "td_mlpc_forward";
-  MlpPlan plan;
-  const MlpView2 v2 = {x2_dev, ldx2, c2, pre2, post2};
-  TD_TRY(mlp_check_and_plan(h, fn, x_dev, ldx, file_offsets_host, num_files, c, pre, post, input_offset, d,
-                            hidden_host, num_hidden, kFwdChunk, &plan, &v2));
-  return mlp_forward_run(h, fn, plan, file_offsets_host, num_files, d, params_dev, out_dev, ldout);
+  const MlpCall a = {{x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host, num_files,
+                     input_offset, nullptr, nullptr, 0, d, hidden_host, num_hidden, kFwdChunk, 0, true};
+  return mlp_forward(h, "td_mlpc_forward", a, params_dev, out_dev, ldout);
 }

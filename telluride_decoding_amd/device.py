@@ -943,15 +943,7 @@ def context_out(z, state, pre, post, mean, std, dtype='float32', handle=None):
   return out, new_state
 
 
-# ---------------------------------------------------------------- fully connected regressor
-def _mlp_rows(file_offsets, input_offset, rows_used):
-  offs, offs_p = _lib.i64_array(file_offsets)
-  if rows_used is None:
-    return offs, offs_p, None, None, int(np.sum(np.maximum(np.diff(offs) - abs(int(input_offset)), 0)))
-  used, used_p = _lib.i64_array(rows_used)
-  return offs, offs_p, used, used_p, int(np.sum(used))
-
-
+# ---------------------------------------------------------------- fully connected regressor / match-mismatch classifier
 MLP_LOSSES = {'mse': 0, 'pearson': 1}
 
 
@@ -959,6 +951,49 @@ def _mlp_loss(loss):
   if loss not in MLP_LOSSES:
     raise ValueError('loss %r: one of %s' % (loss, sorted(MLP_LOSSES)))
   return MLP_LOSSES[loss]
+
+
+def _check_x2(x, x2):
+  if int(x2.shape[0]) != int(x.shape[0]):
+    raise ValueError('x2 has %d rows, x %d: both inputs cover the same files' % (int(x2.shape[0]), int(x.shape[0])))
+
+
+def _mlp_views(h, x, x2, context, file_offsets, input_offset, hidden):
+  """What every td_mlp_* (x2 None) / td_mlpc_* prototype begins with, as ctypes arguments: (the handle through
+  input_offset, [hidden_host, num_hidden], the host arrays those point into -- file offsets first -- which the
+  caller keeps alive over the call).  context = (pre, post) or (pre, post, pre2, post2)."""
+  offs, offs_p = _lib.i64_array(file_offsets)
+  hid, hid_p = _i32_array(list(hidden) or [0])
+  ptrs, sizes = [_ptr(x), x.stride(0)], [int(x.shape[1]), int(context[0]), int(context[1])]
+  if x2 is not None:
+    ptrs += [_ptr(x2), x2.stride(0)]
+    sizes += [int(x2.shape[1]), int(context[2]), int(context[3])]
+  return [h.ptr] + ptrs + [offs_p, len(offs) - 1] + sizes + [int(input_offset)], [hid_p, len(hidden)], [offs, hid]
+
+
+def _mlp_fit(h, x, x2, y, context, file_offsets, input_offset, hidden, rows_used, batch_rows, nstat, epochs=None):
+  """A train (epochs given) or grad call: (its arguments through batch_rows, the stats buffer -- [epochs, steps,
+  nstat] or [nstat] float64 -- and the host arrays to keep alive over the call)."""
+  head, net, keep = _mlp_views(h, x, x2, context, file_offsets, input_offset, hidden)
+  used_p = None
+  if rows_used is None:
+    n = int(np.sum(np.maximum(np.diff(keep[0]) - abs(int(input_offset)), 0)))
+  else:
+    used, used_p = _lib.i64_array(rows_used)
+    keep.append(used)
+    n = int(np.sum(used))
+  shape = (nstat,)
+  if epochs is not None:
+    shape = (max(int(epochs), 0), -(-n // int(batch_rows)) if batch_rows > 0 else 0, nstat)
+  args = head + [used_p, _ptr(y), y.stride(0), int(y.shape[1])] + net + [int(batch_rows)]
+  return args, h.empty(shape, 'float64'), keep
+
+
+def _mlp_forward(h, fn, x, x2, context, file_offsets, input_offset, hidden, d, params):
+  head, net, keep = _mlp_views(h, x, x2, context, file_offsets, input_offset, hidden)
+  out = h.empty((int(x.shape[0]), int(d)), 'float32')
+  h.check(fn(*head, int(d), *net, _ptr(params), _ptr(out), out.stride(0)))
+  return out
 
 
 def mlp_train(x, y, file_offsets, pre, post, hidden, params, state, batch_rows, epochs, lr, rho, eps,
@@ -970,17 +1005,12 @@ def mlp_train(x, y, file_offsets, pre, post, hidden, params, state, batch_rows, 
   [epochs, steps, 7]: the six sums, then the step's loss -(1 / B) sum_o r_o."""
   h = handle or default_handle()
   code = _mlp_loss(loss)
-  nstat = 7 if code else 6
-  offs, offs_p, used, used_p, n = _mlp_rows(file_offsets, input_offset, rows_used)
-  steps = -(-n // int(batch_rows)) if batch_rows > 0 else 0
-  stats = h.empty((max(int(epochs), 0) * steps, nstat), 'float64')
-  hid, hid_p = _i32_array(list(hidden) or [0])
-  seed = -1 if shuffle_seed is None else int(shuffle_seed)
-  args = (h.ptr, _ptr(x), x.stride(0), offs_p, len(offs) - 1, int(x.shape[1]), int(pre), int(post),
-          int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p, len(hidden), int(batch_rows),
-          int(epochs), _ptr(params), _ptr(state), float(lr), float(rho), float(eps), seed, _ptr(stats))
+  args, stats, keep = _mlp_fit(h, x, None, y, (pre, post), file_offsets, input_offset, hidden, rows_used, batch_rows,
+                               7 if code else 6, epochs)
+  args += [int(epochs), _ptr(params), _ptr(state), float(lr), float(rho), float(eps),
+           -1 if shuffle_seed is None else int(shuffle_seed), _ptr(stats)]
   h.check(h.lib.td_mlp_train_loss(*args, code) if code else h.lib.td_mlp_train(*args))
-  return stats.reshape(max(int(epochs), 0), steps, nstat)
+  return stats
 
 
 def mlp_grad(x, y, file_offsets, pre, post, hidden, params, batch_rows, batch_index, input_offset=0,
@@ -990,13 +1020,10 @@ def mlp_grad(x, y, file_offsets, pre, post, hidden, params, batch_rows, batch_in
   (td_mlp_grad_loss)."""
   h = handle or default_handle()
   code = _mlp_loss(loss)
-  offs, offs_p, used, used_p, _ = _mlp_rows(file_offsets, input_offset, rows_used)
+  args, stats, keep = _mlp_fit(h, x, None, y, (pre, post), file_offsets, input_offset, hidden, rows_used, batch_rows,
+                               7 if code else 6)
   grad = h.empty((int(params.numel()),), 'float32')
-  stats = h.empty((7 if code else 6,), 'float64')
-  hid, hid_p = _i32_array(list(hidden) or [0])
-  args = (h.ptr, _ptr(x), x.stride(0), offs_p, len(offs) - 1, int(x.shape[1]), int(pre), int(post),
-          int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p, len(hidden), int(batch_rows),
-          int(batch_index), _ptr(params), _ptr(grad), _ptr(stats))
+  args += [int(batch_index), _ptr(params), _ptr(grad), _ptr(stats)]
   h.check(h.lib.td_mlp_grad_loss(*args, code) if code else h.lib.td_mlp_grad(*args))
   return grad, stats
 
@@ -1004,19 +1031,7 @@ def mlp_grad(x, y, file_offsets, pre, post, hidden, params, batch_rows, batch_in
 def mlp_forward(x, file_offsets, pre, post, hidden, d, params, input_offset=0, handle=None):
   """The network on every row of x (td_mlp_forward): [rows, d]; row file_offsets[f] + t = frame t of file f."""
   h = handle or default_handle()
-  offs, offs_p = _lib.i64_array(file_offsets)
-  out = h.empty((int(x.shape[0]), int(d)), 'float32')
-  hid, hid_p = _i32_array(list(hidden) or [0])
-  h.check(h.lib.td_mlp_forward(h.ptr, _ptr(x), x.stride(0), offs_p, len(offs) - 1, int(x.shape[1]), int(pre),
-                               int(post), int(input_offset), int(d), hid_p, len(hidden), _ptr(params), _ptr(out),
-                               out.stride(0)))
-  return out
-
-
-# ---------------------------------------------------------------- match-mismatch classifier
-def _check_x2(x, x2):
-  if int(x2.shape[0]) != int(x.shape[0]):
-    raise ValueError('x2 has %d rows, x %d: both inputs cover the same files' % (int(x2.shape[0]), int(x.shape[0])))
+  return _mlp_forward(h, h.lib.td_mlp_forward, x, None, (pre, post), file_offsets, input_offset, hidden, d, params)
 
 
 def mlpc_train(x, x2, y, file_offsets, pre, post, pre2, post2, hidden, params, state, batch_rows, epochs,
@@ -1029,17 +1044,12 @@ def mlpc_train(x, x2, y, file_offsets, pre, post, pre2, post2, hidden, params, s
   entries at threshold 0.5, slot 5 = the sum of the entry losses."""
   h = handle or default_handle()
   _check_x2(x, x2)
-  offs, offs_p, used, used_p, n = _mlp_rows(file_offsets, input_offset, rows_used)
-  steps = -(-n // int(batch_rows)) if batch_rows > 0 else 0
-  stats = h.empty((max(int(epochs), 0) * steps, 6), 'float64')
-  hid, hid_p = _i32_array(list(hidden) or [0])
-  seed = -1 if shuffle_seed is None else int(shuffle_seed)
-  h.check(h.lib.td_mlpc_train(h.ptr, _ptr(x), x.stride(0), _ptr(x2), x2.stride(0), offs_p, len(offs) - 1,
-                              int(x.shape[1]), int(pre), int(post), int(x2.shape[1]), int(pre2), int(post2),
-                              int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p, len(hidden),
-                              int(batch_rows), int(epochs), _ptr(params), _ptr(state), float(lr), float(beta1),
-                              float(beta2), float(eps), int(step0), 1 if update else 0, seed, _ptr(stats)))
-  return stats.reshape(max(int(epochs), 0), steps, 6)
+  args, stats, keep = _mlp_fit(h, x, x2, y, (pre, post, pre2, post2), file_offsets, input_offset, hidden, rows_used,
+                               batch_rows, 6, epochs)
+  h.check(h.lib.td_mlpc_train(*args, int(epochs), _ptr(params), _ptr(state), float(lr), float(beta1), float(beta2),
+                              float(eps), int(step0), 1 if update else 0,
+                              -1 if shuffle_seed is None else int(shuffle_seed), _ptr(stats)))
+  return stats
 
 
 def mlpc_grad(x, x2, y, file_offsets, pre, post, pre2, post2, hidden, params, batch_rows, batch_index,
@@ -1047,14 +1057,10 @@ def mlpc_grad(x, x2, y, file_offsets, pre, post, pre2, post2, hidden, params, ba
   """(gradient [P] float32, sums [6] float64) of minibatch `batch_index` at params, no update (td_mlpc_grad)."""
   h = handle or default_handle()
   _check_x2(x, x2)
-  offs, offs_p, used, used_p, _ = _mlp_rows(file_offsets, input_offset, rows_used)
+  args, stats, keep = _mlp_fit(h, x, x2, y, (pre, post, pre2, post2), file_offsets, input_offset, hidden, rows_used,
+                               batch_rows, 6)
   grad = h.empty((int(params.numel()),), 'float32')
-  stats = h.empty((6,), 'float64')
-  hid, hid_p = _i32_array(list(hidden) or [0])
-  h.check(h.lib.td_mlpc_grad(h.ptr, _ptr(x), x.stride(0), _ptr(x2), x2.stride(0), offs_p, len(offs) - 1,
-                             int(x.shape[1]), int(pre), int(post), int(x2.shape[1]), int(pre2), int(post2),
-                             int(input_offset), used_p, _ptr(y), y.stride(0), int(y.shape[1]), hid_p, len(hidden),
-                             int(batch_rows), int(batch_index), _ptr(params), _ptr(grad), _ptr(stats)))
+  h.check(h.lib.td_mlpc_grad(*args, int(batch_index), _ptr(params), _ptr(grad), _ptr(stats)))
   return grad, stats
 
 
@@ -1063,11 +1069,5 @@ def mlpc_forward(x, x2, file_offsets, pre, post, pre2, post2, hidden, d, params,
   file_offsets[f] + t = frame t of file f."""
   h = handle or default_handle()
   _check_x2(x, x2)
-  offs, offs_p = _lib.i64_array(file_offsets)
-  out = h.empty((int(x.shape[0]), int(d)), 'float32')
-  hid, hid_p = _i32_array(list(hidden) or [0])
-  h.check(h.lib.td_mlpc_forward(h.ptr, _ptr(x), x.stride(0), _ptr(x2), x2.stride(0), offs_p, len(offs) - 1,
-                                int(x.shape[1]), int(pre), int(post), int(x2.shape[1]), int(pre2), int(post2),
-                                int(input_offset), int(d), hid_p, len(hidden), _ptr(params), _ptr(out),
-                                out.stride(0)))
-  return out
+  return _mlp_forward(h, h.lib.td_mlpc_forward, x, x2, (pre, post, pre2, post2), file_offsets, input_offset, hidden,
+                      d, params)

@@ -18,6 +18,22 @@ def _signature_rows(fn):
   return rows
 
 
+def member(cls, name):
+  """What the first class of cls's MRO that defines `name` holds under it (None: none does)."""
+  for klass in cls.__mro__:
+    if name in vars(klass):
+      return vars(klass)[name]
+  return None
+
+
+def member_rows(cls, name):
+  """The signature rows of method `name` of cls, inherited or not."""
+  attr = member(cls, name)
+  if isinstance(attr, (staticmethod, classmethod)):
+    attr = attr.__func__
+  return _signature_rows(attr)
+
+
 def module_surface(module):
   """{public name: signature rows | {'bases': [...], 'members': {name: rows | 'property'}}} of the
   functions and classes a module DEFINES (imports are skipped)."""

@@ -7,7 +7,7 @@ import pytest
 
 from tests import host_classifier as hc
 from tests import host_dnn
-from tests.surface import _signature_rows
+from tests.surface import member_rows
 from tests.test_cpu_surface import _golden, _leading_matches
 
 
@@ -28,7 +28,7 @@ def test_surface_matches_the_reference():
   for name, rows in ref['members'].items():
     assert hasattr(brain_model.BrainModelClassifier, name), name
     where = ('brain_model', 'BrainModelClassifier', name)
-    ours = _signature_rows(vars(brain_model.BrainModelClassifier)[name])
+    ours = member_rows(brain_model.BrainModelClassifier, name)
     if name == 'compile':        # the optimizer and loss defaults name TF objects there
       theirs = {r[0]: r[2] for r in rows}
       ours = [r if r[0] not in ('optimizer', 'loss') else [r[0], r[1], theirs[r[0]]] for r in ours]

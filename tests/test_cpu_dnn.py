@@ -1,11 +1,15 @@
 """BrainModelDNN without a GPU: the call surface against the reference's (G14), the constructor and compile
-errors, the seeded Glorot initialisation, the history the six per-step sums give, and the float64 oracle of
-tests/host_dnn.py itself (finite differences, a hand-computed RMSprop step, the shuffle bijection)."""
+errors, the seeded Glorot initialisation, the history the six per-step sums give, the ctypes prototypes of the
+td_mlp_* / td_mlpc_* entry points against the C header, and the float64 oracle of tests/host_dnn.py itself
+(finite differences, a hand-computed RMSprop step, the shuffle bijection)."""
+import ctypes
+import re
+
 import numpy as np
 import pytest
 
 from tests import host_dnn
-from tests.surface import _signature_rows
+from tests.surface import member_rows
 from tests.test_cpu_surface import _golden, _leading_matches
 
 
@@ -25,7 +29,7 @@ def test_surface_matches_the_reference():
   for name, rows in ref['members'].items():
     assert hasattr(brain_model.BrainModelDNN, name), name
     where = ('brain_model', 'BrainModelDNN', name)
-    ours = _signature_rows(vars(brain_model.BrainModelDNN)[name])
+    ours = member_rows(brain_model.BrainModelDNN, name)
     if name == 'compile':        # the optimizer default names a TF class there
       ours = [r if r[0] != 'optimizer' else ['optimizer', r[1], rows[1][2]] for r in ours]
     problems += _leading_matches(rows, ours, where)
@@ -73,6 +77,34 @@ def test_compile_forms_and_errors():
     m.compile(loss=['mse', 'mse'])
   with pytest.raises(RuntimeError, match='compile'):
     brain_model.BrainModelDNN(_dataset(), [4]).fit(_dataset())
+
+
+MLP_ENTRY_POINTS = ['td_mlp_train', 'td_mlp_grad', 'td_mlp_train_loss', 'td_mlp_grad_loss', 'td_mlp_forward',
+                    'td_mlpc_train', 'td_mlpc_grad', 'td_mlpc_forward']
+
+
+def _kind_of_ctype(t):
+  if t is ctypes.c_void_p or t is ctypes.c_char_p or issubclass(t, ctypes._Pointer):
+    return 'pointer'
+  return {ctypes.c_int64: 'int64_t', ctypes.c_int: 'int', ctypes.c_float: 'float', ctypes.c_double: 'double'}[t]
+
+
+def test_argtypes_match_the_header_prototypes():
+  """Each of the eight entry points: as many argtypes as the prototype of include/td_hotpath.h has parameters,
+  each of the parameter's kind (pointer, int64_t, int, float, double).  A slip here is a silent ABI mismatch."""
+  from telluride_decoding_amd import _lib
+  with open(_lib.HEADER) as f:
+    text = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
+  protos = dict(re.findall(r'\bint\s+(td_mlpc?_\w+)\s*\(([^)]*)\)\s*;', text))
+  assert sorted(protos) == sorted(MLP_ENTRY_POINTS)
+  for name in MLP_ENTRY_POINTS:
+    kinds = []
+    for param in protos[name].split(','):
+      words = param.replace('*', ' * ').split()
+      assert len(words) >= 2 and words[-1].isidentifier(), (name, param)
+      kinds.append('pointer' if '*' in words else ' '.join(w for w in words[:-1] if w != 'const'))
+    assert set(kinds) <= {'pointer', 'int64_t', 'int', 'float', 'double'}, (name, kinds)
+    assert [_kind_of_ctype(t) for t in _lib.SIGNATURES[name]] == kinds, name
 
 
 def test_glorot_initialisation_is_seeded():

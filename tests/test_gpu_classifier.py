@@ -13,37 +13,15 @@ import pytest
 from tests import host_classifier as hc
 from tests import host_dnn
 from tests import parity_log
+from tests.dnn_common import GRAD_BOUND, assert_within, flat, grad_distances, make_files, split, tensor_names
 
 pytestmark = pytest.mark.gpu
 
 MARGIN = 1e-6        # gradients, inference, evaluation
 MARGIN_TRAJ = 1e-5   # trajectories
 MAX_DRAWS = 3
-GRAD_BOUND = 5e-5    # max|g - g64| / max|g64| per tensor: the project's own bound
 LOSS_BOUND = 1e-5   # a step's loss against float64, relative: the bound of the history's loss, saturated case included
 EPS32 = 2.0 ** -24   # half an ulp of a float32 in [1, 2): the relative error of one rounding
-
-
-def _files(rng, lengths, c, c2, d):
-  out = []
-  for n in lengths:
-    x = rng.standard_normal((n, c)).astype(np.float32)
-    x2 = rng.standard_normal((n, c2)).astype(np.float32)
-    y = (rng.standard_normal((n, d)) > 0.3).astype(np.float32)
-    out.append((x, x2, y, np.zeros((n, 1), np.float32)))
-  return out
-
-
-def _flat(ws):
-  return np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in ws])
-
-
-def _split(flat, widths):
-  out, at = [], 0
-  for fi, fo in zip(widths[:-1], widths[1:]):
-    out.append(flat[at:at + fi * fo].reshape(fi, fo)); at += fi * fo
-    out.append(flat[at:at + fo]); at += fo
-  return out
 
 
 def _counts(accuracies, entries):
@@ -51,10 +29,6 @@ def _counts(accuracies, entries):
   counts = [a * entries for a in accuracies]
   assert all(abs(c - round(c)) < 1e-6 for c in counts), counts
   return [int(round(c)) for c in counts]
-
-
-def _names(n):
-  return ['W%d' % (i // 2 + 1) if i % 2 == 0 else 'b%d' % (i // 2 + 1) for i in range(n)]
 
 
 def _x64(feats):
@@ -84,7 +58,7 @@ def grad_case(hidden, c, pre, post, c2, pre2, post2, batch, d, off, mixup=False,
   for seed in range(MAX_DRAWS):
     rng = np.random.default_rng(2000 + seed)
     lengths = [int(batch * f) + 7 for f in (0.6, 1.3, 0.45, 1.9)]          # ragged files
-    files = _files(rng, lengths, c, c2, d)
+    files = make_files(rng, lengths, c, d, c2=c2)
     ds = brain_data.Dataset(files, batch, pre, post, pre2, post2, input_offset=off, mixup_batch=mixup,
                             mixup_seed=seed)
     batches = list(ds)
@@ -110,19 +84,15 @@ def _run_grad(case, hidden, batch, d, off):
   h = device.default_handle()
   res = case['ds'].resolved()
   x, x2, y, offs = res.device_arrays(h)
-  params = h.to_device(_flat(case['weights']))
+  params = h.to_device(flat(case['weights']))
   grad, sums = device.mlpc_grad(x, x2, y, offs, res.pre, res.post, res.pre2, res.post2, hidden, params, batch,
                                 case['s'], input_offset=off, rows_used=res.rows_used(), handle=h)
-  got = _split(grad.cpu().numpy(), case['widths'])
   s6 = sums.cpu().numpy()
-  dists = {}
-  for name, gg, gw in zip(_names(len(got)), got, case['g64']):
-    dists[name] = float(np.max(np.abs(gg - gw)) / max(np.max(np.abs(gw)), 1e-30))
+  dists = grad_distances(split(grad.cpu().numpy(), case['widths']), case['g64'])
   loss32 = s6[5] / (batch * d)
   loss_rel = abs(loss32 - case['loss']) / case['loss']
   print('classifier grad', hidden, dists, 'loss rel', loss_rel, 'correct', s6[0], case['ok'], 'margin', case['margin'])
-  for name, dist in dists.items():
-    assert dist <= GRAD_BOUND, (name, dist)
+  assert_within(dists, GRAD_BOUND)
   assert np.isfinite(loss32)
   assert list(s6[1:5]) == [0.0] * 4
   assert s6[0] == case['ok']                           # exact under the redraw rule
@@ -182,10 +152,10 @@ def test_one_adam_step_from_the_devices_own_gradient(lr):
   hidden, c, pre, post, c2, pre2, post2, batch, d = [20], 4, 2, 2, 2, 1, 1, 128, 1
   b1, b2, eps, step0 = 0.9, 0.999, 1e-7, 7
   rng = np.random.default_rng(77)
-  files = _files(rng, [150], c, c2, d)
+  files = make_files(rng, [150], c, d, c2=c2)
   ds = brain_data.Dataset(files, batch, pre, post, pre2, post2).take(1)          # one step
   widths = [c * (pre + 1 + post) + c2 * (pre2 + 1 + post2)] + hidden + [d]
-  w0 = _flat(host_dnn.glorot(widths, 1))
+  w0 = flat(host_dnn.glorot(widths, 1))
   w0[w0 == 0] = np.float32(0.01)                                                   # (the zero biases)
   x, x2, y, offs = ds.device_arrays(h)
   params = h.to_device(w0)
@@ -229,7 +199,7 @@ def trajectory_case(shuffle_seed, epochs=3):
   widths = [t['c'] * (t['pre'] + 1 + t['post']) + t['c2'] * (t['pre2'] + 1 + t['post2'])] + t['hidden'] + [t['d']]
   for seed in range(MAX_DRAWS):
     rng = np.random.default_rng(60 + seed)
-    files = _files(rng, t['lengths'], t['c'], t['c2'], t['d'])
+    files = make_files(rng, t['lengths'], t['c'], t['d'], c2=t['c2'])
     x64, y64 = hc.stream(files, t['batch'], t['pre'], t['post'], t['pre2'], t['post2'])
     assert x64.shape[0] == 10 * t['batch']
     w0 = host_dnn.glorot(widths, seed)
@@ -260,7 +230,7 @@ def _trajectory(shuffle_seed):
   assert runs[0][1] == runs[1][1]
   w64 = case['w64']
   wmax = max(float(np.max(np.abs(b))) for b in w64)
-  per_tensor = {n: float(np.max(np.abs(a - b))) / wmax for n, a, b in zip(_names(len(w64)), runs[0][0], w64)}
+  per_tensor = {n: float(np.max(np.abs(a - b))) / wmax for n, a, b in zip(tensor_names(len(w64)), runs[0][0], w64)}
   got, want = runs[0][1], case['hist64']
   assert sorted(got) == ['accuracy', 'loss'] and len(got['loss']) == 3
   hdist = float(np.max(np.abs(np.asarray(got['loss']) - want['loss']) / np.abs(want['loss'])))
@@ -318,7 +288,7 @@ def inference_case():
   widths = [c * (pre + 1 + post) + c2 * (pre2 + 1 + post2)] + hidden + [d]
   for seed in range(MAX_DRAWS):
     rng = np.random.default_rng(7 + seed)
-    files = _files(rng, [300, 5000, 170], c, c2, d)
+    files = make_files(rng, [300, 5000, 170], c, d, c2=c2)
     w = host_dnn.glorot(widths, seed + 1)
     w = [a + np.float32(0.05) * rng.standard_normal(a.shape).astype(np.float32) for a in w]
     parts, margin = [], np.inf
@@ -407,7 +377,7 @@ def test_limits_raise_before_any_launch():
   rng = np.random.default_rng(3)
 
   def ds_of(c, pre, post, c2, pre2, post2, d, batch, n=4200):
-    return brain_data.Dataset(_files(rng, [n], c, c2, d), batch, pre, post, pre2, post2)
+    return brain_data.Dataset(make_files(rng, [n], c, d, c2=c2), batch, pre, post, pre2, post2)
   cases = [
       (ds_of(128, 31, 31, 3, 21, 21, 1, 64), [4]),          # K1 + K2 = 8064 + 129 = 8193
       (ds_of(2, 0, 0, 129, 1, 0, 1, 64), [4]),              # c2 > 128 with context

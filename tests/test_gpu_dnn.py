@@ -7,37 +7,10 @@ import pytest
 
 from tests import host_dnn
 from tests import parity_log
+from tests.dnn_common import (GRAD_BOUND, KINK, assert_within, flat, grad_distances, iir, make_files, simply_scaled,
+                              split)
 
 pytestmark = pytest.mark.gpu
-
-KINK = 1e-6          # a hidden pre-activation closer than this (relative to its sum of |terms|) to 0: redraw
-# max|g - g64| / max|g64| per tensor.  Observed: <= 1e-6 on every tensor but one scalar, b1 of
-# the one-layer K = 8192, D = 1 case (1.8e-5): the sum over 512 rows of p - y cancels to a few percent of its
-# terms, and each float32 prediction carries the rounding of an 8192-term sum.
-GRAD_BOUND = 5e-5
-
-
-def _files(rng, lengths, c, d, scale=1.0):
-  out = []
-  for n in lengths:
-    x = (scale * rng.standard_normal((n, c))).astype(np.float32)
-    y = np.tanh(rng.standard_normal((n, d))).astype(np.float32)
-    z = np.zeros((n, 1), np.float32)
-    out.append((x, z, y, z))
-  return out
-
-
-def _flat(ws):
-  return np.concatenate([np.asarray(w, np.float32).reshape(-1) for w in ws])
-
-
-def _split(flat, widths):
-  out, at = [], 0
-  for fi, fo in zip(widths[:-1], widths[1:]):
-    out.append(flat[at:at + fi * fo].reshape(fi, fo)); at += fi * fo
-    out.append(flat[at:at + fo]); at += fo
-  return out
-
 
 # (hidden, channels, pre, post, batch, outputs, input_offset): every value of each axis next to small and
 # large partners
@@ -62,7 +35,7 @@ def _grad_case(hidden, c, pre, post, batch, d, off, mixup=False):
   for seed in range(8):
     rng = np.random.default_rng(1000 + seed)
     lengths = [int(batch * f) + 7 for f in (0.6, 1.3, 0.45, 1.9)]          # ragged files
-    files = _files(rng, lengths, c, d)
+    files = make_files(rng, lengths, c, d)
     ds = brain_data.Dataset(files, batch, pre, post, input_offset=off, mixup_batch=mixup, mixup_seed=seed)
     batches = list(ds)
     # the minibatch that straddles the first file boundary
@@ -79,16 +52,12 @@ def _grad_case(hidden, c, pre, post, batch, d, off, mixup=False):
     pytest.fail('no seed keeps the ReLU inputs %g away from their kinks' % KINK)
   res = ds.resolved()
   x, _, y, offs = res.device_arrays(h)
-  params = h.to_device(_flat(weights))
+  params = h.to_device(flat(weights))
   grad, sums = device.mlp_grad(x, y, offs, pre, post, hidden, params, batch, s, input_offset=off,
                                rows_used=res.rows_used(), handle=h)
-  got = _split(grad.cpu().numpy(), widths)
-  worst = 0.0
-  for name, gg, gw in zip(['W%d' % (i // 2 + 1) if i % 2 == 0 else 'b%d' % (i // 2 + 1) for i in range(len(g64))],
-                          got, g64):
-    dist = float(np.max(np.abs(gg - gw)) / max(np.max(np.abs(gw)), 1e-30))
-    worst = max(worst, dist)
-    assert dist <= GRAD_BOUND, (name, dist)
+  dists = grad_distances(split(grad.cpu().numpy(), widths), g64)
+  worst = max(dists.values())
+  assert_within(dists, GRAD_BOUND)
   s6 = sums.cpu().numpy()
   assert abs(s6[5] / (batch * d) - loss) <= 1e-6 * loss
   return worst, kink
@@ -113,7 +82,7 @@ def _trajectory(shuffle_seed):
   widths = [k] + hidden + [d]
   for seed in range(8):
     rng = np.random.default_rng(50 + seed)
-    files = _files(rng, [101, 130, 95], c, d)
+    files = make_files(rng, [101, 130, 95], c, d)
     ds = brain_data.Dataset(files, batch, pre, post)
     x64, y64 = host_dnn.stream(files, batch, pre, post)
     w0 = host_dnn.glorot(widths, seed)
@@ -154,22 +123,6 @@ def test_trajectory_shuffled():
 
 
 # ---- the reference's behaviour tests (test/brain_model_test.py), recipes and thresholds unchanged ----------
-def _simply_scaled(data_offset=0, channels=2, pre=0, post=0, batch=1000):
-  from telluride_decoding_amd import brain_data
-  rs = np.random.RandomState(0)
-  n = 10000
-  inp = rs.randn(n + 2 * abs(data_offset), channels).astype(np.float32)
-  out = np.sin(inp[:, 0:1] * 2 * np.pi)
-  if data_offset >= 0:
-    inp, out = inp[0:n, :], out[data_offset:data_offset + n, :]
-  else:
-    inp, out = inp[-data_offset:-data_offset + n, :], out[0:n, :]
-  bd = brain_data.TestBrainData('input', 'output', 100.0, pre_context=pre, post_context=post,
-                                final_batch_size=batch)
-  bd.preserve_test_data(inp, out, None)
-  return bd.create_dataset('program_test')
-
-
 def _fit_dnn(ds, hidden, epochs):
   from telluride_decoding_amd import brain_model
   m = brain_model.BrainModelDNN(ds, hidden)
@@ -181,7 +134,7 @@ def _fit_dnn(ds, hidden, epochs):
 
 def test_regression_fullyconnected():          # brain_model_test.py:336-357
   from telluride_decoding_amd import brain_model
-  ds = _simply_scaled()
+  ds = simply_scaled()
   _, hist, metrics = _fit_dnn(ds, [40, 20, 10], 100)
   assert len(hist.history['loss']) == 100 and np.all(np.isfinite(hist.history['loss']))
   assert metrics['loss'] < 0.35
@@ -194,30 +147,18 @@ def test_regression_fullyconnected():          # brain_model_test.py:336-357
 
 @pytest.mark.parametrize('offset,r_min', [(1, 0.9), (-1, 0.88)])
 def test_offset_regression(offset, r_min):     # :360-492
-  ds = _simply_scaled(data_offset=offset, channels=1, pre=1, post=1, batch=128)
+  ds = simply_scaled(data_offset=offset, channels=1, pre=1, post=1, batch=128)
   _, _, metrics = _fit_dnn(ds, [40, 20, 10], 100)
   assert metrics['loss'] < 0.4
   assert metrics['pearson_correlation_first'] > r_min
   parity_log.record('dnn_ref_offset', offset=offset, **metrics)
 
 
-def _iir(pre):                                 # :494-503
-  from telluride_decoding_amd import brain_data
-  rs = np.random.RandomState(0)
-  n = 10000
-  inp = rs.randn(n + 1, 1).astype(np.float32)
-  out = 0.4 * inp[0:-1, ] + 0.6 * inp[1:, :]
-  bd = brain_data.TestBrainData('input', 'output', 100.0, pre_context=pre, post_context=0,
-                                final_batch_size=128)
-  bd.preserve_test_data(inp[1:n + 1, :], out, None)
-  return bd.create_dataset('program_test')
-
-
 def test_simple_iir_regression():              # :505-566
-  _, _, m32 = _fit_dnn(_iir(32), [40, 20, 10], 10)
+  _, _, m32 = _fit_dnn(iir(32), [40, 20, 10], 10)
   assert m32['loss'] < 0.025
   assert m32['pearson_correlation_first'] > 0.95
-  _, _, m0 = _fit_dnn(_iir(0), [40, 20, 10], 10)
+  _, _, m0 = _fit_dnn(iir(0), [40, 20, 10], 10)
   assert m0['loss'] > 0.025
   assert m0['pearson_correlation_first'] > 0.8
   parity_log.record('dnn_ref_iir', loss32=m32['loss'], r32=m32['pearson_correlation_first'], loss0=m0['loss'],
@@ -230,7 +171,7 @@ def test_inference_matches_float64():
   from telluride_decoding_amd import brain_data, brain_model
   rng = np.random.default_rng(7)
   c, pre, post, d, batch, hidden, off = 6, 3, 2, 2, 64, [16, 8], 1
-  files = _files(rng, [300, 5000, 170], c, d)
+  files = make_files(rng, [300, 5000, 170], c, d)
   ds = brain_data.Dataset(files, batch, pre, post, input_offset=off)
   m = brain_model.BrainModelDNN(ds, hidden, seed=1)
   w = m.get_weights()
@@ -312,7 +253,7 @@ def test_limits_raise_before_any_launch():
   rng = np.random.default_rng(3)
 
   def ds_of(c, pre, post, d, batch, n=4200):
-    return brain_data.Dataset(_files(rng, [n], c, d), batch, pre, post)
+    return brain_data.Dataset(make_files(rng, [n], c, d), batch, pre, post)
   cases = [(ds_of(129, 1, 0, 1, 64), [4]), (ds_of(2, 32, 32, 1, 64), [4]), (ds_of(2, 0, 0, 9, 64), [4]),
            (ds_of(2, 0, 0, 1, 2049), [4]), (ds_of(2, 0, 0, 1, 64), [4] * 5), (ds_of(2, 0, 0, 1, 64), [65])]
   for ds, hidden in cases:

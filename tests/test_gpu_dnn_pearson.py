@@ -8,7 +8,8 @@ import pytest
 from tests import host_dnn
 from tests import host_dnn_pearson
 from tests import parity_log
-from tests.test_gpu_dnn import GRAD_BOUND, KINK, _files, _flat, _iir, _simply_scaled, _split
+from tests.dnn_common import (GRAD_BOUND, KINK, assert_within, flat, grad_distances, iir, make_files, simply_scaled,
+                              split)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,10 +27,6 @@ GRID = [
 ]
 
 
-def _names(n):
-  return ['W%d' % (i // 2 + 1) if i % 2 == 0 else 'b%d' % (i // 2 + 1) for i in range(n)]
-
-
 def _grad_case(hidden, c, pre, post, batch, d, off, mixup=False):
   from telluride_decoding_amd import brain_data, device
   h = device.default_handle()
@@ -39,7 +36,7 @@ def _grad_case(hidden, c, pre, post, batch, d, off, mixup=False):
   for seed in range(8):
     rng = np.random.default_rng(1000 + seed)
     lengths = [int(batch * f) + 7 for f in (0.6, 1.3, 0.45, 1.9)]          # ragged files
-    files = _files(rng, lengths, c, d)
+    files = make_files(rng, lengths, c, d)
     ds = brain_data.Dataset(files, batch, pre, post, input_offset=off, mixup_batch=mixup, mixup_seed=seed)
     batches = list(ds)
     # the minibatch that straddles the first file boundary
@@ -56,15 +53,13 @@ def _grad_case(hidden, c, pre, post, batch, d, off, mixup=False):
     pytest.fail('no seed keeps the ReLU inputs %g away from their kinks' % KINK)
   res = ds.resolved()
   x, _, y, offs = res.device_arrays(h)
-  params = h.to_device(_flat(weights))
+  params = h.to_device(flat(weights))
   grad, sums = device.mlp_grad(x, y, offs, pre, post, hidden, params, batch, s, input_offset=off,
                                rows_used=res.rows_used(), handle=h, loss='pearson')
-  got = _split(grad.cpu().numpy(), widths)
+  got = split(grad.cpu().numpy(), widths)
   s7 = sums.cpu().numpy()
   assert s7.shape == (7,)
-  dists = {}
-  for name, gg, gw in zip(_names(len(g64)), got[:-1], g64[:-1]):
-    dists[name] = float(np.max(np.abs(gg - gw)) / max(np.max(np.abs(gw)), 1e-30))
+  dists = grad_distances(got, g64[:-1])
   worst = max(dists.values())
   loss_dist = abs(batch * s7[6] - batch * loss)
   mse64 = float(np.mean((p64 - y64) ** 2))
@@ -75,8 +70,7 @@ def _grad_case(hidden, c, pre, post, batch, d, off, mixup=False):
   parity_log.record('dnn_pearson_grad', shape=str((hidden, c, pre, post, batch, d, off, mixup)), rel=worst,
                     loss_times_b=loss_dist, mse_rel=mse_dist, r_abs=r_dist, kink=kink)
   assert all(np.all(np.isfinite(g)) for g in got) and np.all(np.isfinite(s7))
-  for name, dist in dists.items():
-    assert dist <= GRAD_BOUND, (name, dist)
+  assert_within(dists, GRAD_BOUND)
   assert np.all(got[-1] == 0.0), got[-1]                       # the output bias: exactly zero
   assert np.all(g64[-1] == 0.0)
   assert loss_dist <= 1e-5 * d, loss_dist
@@ -112,7 +106,7 @@ def _trajectory_data(shuffle_seed, scale=1.0):
   from telluride_decoding_amd import brain_data
   for seed in range(8):
     rng = np.random.default_rng(50 + seed)
-    files = _files(rng, [101, 130, 95], C, D)
+    files = make_files(rng, [101, 130, 95], C, D)
     if scale != 1.0:
       files = [(x, z, (np.float32(scale) * y).astype(np.float32), a) for x, z, y, a in files]
     ds = brain_data.Dataset(files, BATCH, PRE, POST)
@@ -230,7 +224,7 @@ def test_a_constant_target_column_contributes_nothing():
   h = device.default_handle()
   rng = np.random.default_rng(5)
   files = [(x, z, np.concatenate([y[:, :1], np.zeros_like(y[:, :1])], axis=1), a)
-           for x, z, y, a in _files(rng, [70, 90], C, D)]
+           for x, z, y, a in make_files(rng, [70, 90], C, D)]
   ds = brain_data.Dataset(files, BATCH, PRE, POST)
   batches = list(ds)
   for seed in range(8):
@@ -244,9 +238,9 @@ def test_a_constant_target_column_contributes_nothing():
     pytest.fail('no seed keeps the ReLU inputs away from their kinks')
   assert np.all(y64[:, 1] == 0.0) and np.all(g64[-2][:, 1] == 0.0)
   x, _, y, offs = ds.device_arrays(h)
-  grad, sums = device.mlp_grad(x, y, offs, PRE, POST, HIDDEN, h.to_device(_flat(weights)), BATCH, 2,
+  grad, sums = device.mlp_grad(x, y, offs, PRE, POST, HIDDEN, h.to_device(flat(weights)), BATCH, 2,
                                rows_used=ds.rows_used(), handle=h, loss='pearson')
-  got, s7 = _split(grad.cpu().numpy(), WIDTHS), sums.cpu().numpy()
+  got, s7 = split(grad.cpu().numpy(), WIDTHS), sums.cpu().numpy()
   assert all(np.all(np.isfinite(g)) for g in got) and np.all(np.isfinite(s7))
   assert np.all(got[-2][:, 1] == 0.0) and np.all(got[-1] == 0.0)
   dists = [float(np.max(np.abs(gg - gw)) / np.max(np.abs(gw))) for gg, gw in zip(got[:-1], g64[:-1])]
@@ -262,7 +256,7 @@ def test_a_constant_target_column_contributes_nothing():
 def test_a_constant_prediction_leaves_every_weight_as_it_was():
   from telluride_decoding_amd import brain_data, brain_model
   rng = np.random.default_rng(6)
-  ds = brain_data.Dataset(_files(rng, [BATCH + 5], C, D), BATCH, PRE, POST)
+  ds = brain_data.Dataset(make_files(rng, [BATCH + 5], C, D), BATCH, PRE, POST)
   assert ds.num_batches() == 1
   m = brain_model.BrainModelDNN(ds, HIDDEN, seed=1)
   w0 = m.get_weights()
@@ -288,7 +282,7 @@ def _abi_args(h, ds, weights):
   keep = (x, y, offs_a, used_a, hid_a)
   head = (h.ptr, device._ptr(x), x.stride(0), offs_p, len(offs_a) - 1, C, PRE, POST, 0, used_p, device._ptr(y),
           y.stride(0), D, hid_p, len(HIDDEN), BATCH)
-  return keep, head, h.to_device(_flat(weights))
+  return keep, head, h.to_device(flat(weights))
 
 
 def test_loss_zero_of_the_new_entry_points_is_the_old_path_bitwise():
@@ -312,7 +306,7 @@ def test_loss_zero_of_the_new_entry_points_is_the_old_path_bitwise():
   for a, b in zip(*out):
     np.testing.assert_array_equal(a, b)
   assert np.all(out[0][2][:, 5] > 0.0)                         # (every step reported its sums)
-  assert not np.array_equal(out[0][0], _flat(w0))             # (it did train)
+  assert not np.array_equal(out[0][0], flat(w0))             # (it did train)
 
 
 # ---- the reference's recipes trained on the new loss ------------------------------------------------------------
@@ -328,7 +322,7 @@ def _fit_dnn(ds, hidden, epochs):
 def test_sin_target_trained_on_the_correlation():
   """Thresholds from the float64 restatement: r = 0.832 .. 0.862 over glorot seeds 0 - 4 (a float32 emulation:
   0.830 .. 0.871); its mse stays near 0.47, which an mse-trained net brings to 0.12."""
-  ds = _simply_scaled()
+  ds = simply_scaled()
   _, hist, metrics = _fit_dnn(ds, [40, 20, 10], 100)
   print('pearson sin target: %s' % metrics)
   parity_log.record('dnn_pearson_sin', **metrics)
@@ -340,8 +334,8 @@ def test_sin_target_trained_on_the_correlation():
 
 def test_iir_target_trained_on_the_correlation():
   """Thresholds from the float64 restatement: r = 0.9993 with 32 frames of context, 0.831 without."""
-  _, _, m32 = _fit_dnn(_iir(32), [40, 20, 10], 10)
-  _, _, m0 = _fit_dnn(_iir(0), [40, 20, 10], 10)
+  _, _, m32 = _fit_dnn(iir(32), [40, 20, 10], 10)
+  _, _, m0 = _fit_dnn(iir(0), [40, 20, 10], 10)
   print('pearson iir target: pre 32 %s, pre 0 %s' % (m32, m0))
   parity_log.record('dnn_pearson_iir', r32=m32['pearson_correlation_first'], loss32=m32['loss'],
                     r0=m0['pearson_correlation_first'], loss0=m0['loss'])
@@ -356,7 +350,7 @@ def test_limits_and_a_wrong_loss_code():
   rng = np.random.default_rng(3)
 
   def ds_of(c, pre, post, d, batch, n=4200):
-    return brain_data.Dataset(_files(rng, [n], c, d), batch, pre, post)
+    return brain_data.Dataset(make_files(rng, [n], c, d), batch, pre, post)
   for ds, hidden in [(ds_of(2, 0, 0, 9, 64), [4]), (ds_of(2, 0, 0, 1, 2049), [4]), (ds_of(2, 0, 0, 1, 64), [65])]:
     m = brain_model.BrainModelDNN(ds, hidden)
     m.compile(loss='pearson')
@@ -374,7 +368,7 @@ def test_limits_and_a_wrong_loss_code():
     device.mlp_train(x, y, offs, 0, 0, [65], params, state, 64, 1, 1e-3, 0.9, 1e-7, handle=h, loss='pearson')
   with pytest.raises(ValueError, match='batch'):
     device.mlp_train(x, y, offs, 0, 0, [4], params, state, 2049, 1, 1e-3, 0.9, 1e-7, handle=h, loss='pearson')
-  ds = brain_data.Dataset(_files(rng, [200], C, D), BATCH, PRE, POST)
+  ds = brain_data.Dataset(make_files(rng, [200], C, D), BATCH, PRE, POST)
   keep, head, params = _abi_args(h, ds, host_dnn.glorot(WIDTHS, 0))
   state = h.zeros((int(params.numel()),))
   stats = h.zeros((ds.num_batches(), 7), 'float64')
