@@ -797,6 +797,35 @@ int td_mlpc_forward(td_handle* h, const float* x_dev, int64_t ldx, const float* 
                     int post2, int input_offset, int d, const int* hidden_host, int num_hidden,
                     const float* params_dev, float* out_dev, int64_t ldout);
 
+/* ------------------------------------------------------------------ many regressors in one fit
+ * td_mlp_train_loss for num_models regressors of ONE architecture on the same recordings, in one chain of
+ * launches: the folds of a jackknife (brain_model.fit_many, regression.jackknife_dnn), the learning rates of
+ * a sweep.  Shared: x, y, the files, c / pre / post / input_offset, d, the hidden widths, batch_rows, epochs
+ * and the loss (0 = mse, 1 = Pearson).  Per model m, as host arrays of num_models entries:
+ * rows_used_host[m][num_files] (its stream; a file the model does not train on has 0 rows, at any position),
+ * params_dev_host[m] / state_dev_host[m] (DEVICE pointers to its packed parameters and RMSprop accumulators,
+ * as td_mlp_train), lr_host[m], rho_host[m], eps_host[m], shuffle_seed_host[m] (< 0: in order).
+ * Model m has steps_m = ceil(its rows / batch_rows) steps an epoch.  Round t of the call carries launch t of
+ * every model's own fit -- the update of its step t - 1 and the forward of its step t, epoch t / steps_m --
+ * with the models in the grid's second dimension; a model whose epochs x steps_m launches are done idles.  The
+ * call queues max_m(epochs steps_m) + 1 rounds.  No atomics, no wait between workgroups, the reduction orders
+ * of td_mlp_train: model m's parameters, state and sums are bit for bit those of its own td_mlp_train_loss.
+ * stats_dev: [num_models][epochs][max_steps][6 (loss 0) or 7 (loss 1)] float64, max_steps = max_m steps_m;
+ * model m fills its first steps_m entries of every epoch, the others are not written.
+ * Every argument of every model is checked before anything is queued (TD_ERR_INVALID: nothing has changed);
+ * the call works on copies and overwrites params / state of every model once the last launch is queued.  Two
+ * models may not share a buffer.  At most TD_DNN_MANY_MAX_MODELS models a call: a model's scratch is its row
+ * tables (16 B per stream row; two of them when shuffled), the first layer's partial sums
+ * (4 B x ceil(K / 64 .. ) slices x h1 x batch_rows) and the copies -- 11 MB at 240 000 rows, K = 2368,
+ * [20, 20], batch 512, so 0.7 GB at the cap.  Limits otherwise as td_mlp_train. */
+#define TD_DNN_MANY_MAX_MODELS 64
+int td_dnn_train_many(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                      int c, int pre, int post, int input_offset, const float* y_dev, int64_t ldy, int d,
+                      const int* hidden_host, int num_hidden, int batch_rows, int epochs, int loss, int num_models,
+                      const int64_t* rows_used_host, float* const* params_dev_host, float* const* state_dev_host,
+                      const float* lr_host, const float* rho_host, const float* eps_host,
+                      const int64_t* shuffle_seed_host, double* stats_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,9 @@ _EPOCHS = [_i, _vp, _vp]                # epochs, params_dev, state_dev (the opt
 _SEED_STATS = [_i64, _vp]               # shuffle_seed, stats_dev
 _GRAD = [_i, _vp, _vp, _vp]             # batch_index, params_dev, grad_dev, stats_dev
 _FORWARD = [_i, _i] + _NETWORK + [_vp, _vp, _i64]       # input_offset, d, ..., params_dev, out_dev, ldout
+_pf = _c.POINTER(_f)
+# per model, host arrays: rows_used, params_dev / state_dev pointers, lr, rho, eps, shuffle_seed
+_MANY = [_pi64, _c.POINTER(_vp), _c.POINTER(_vp), _pf, _pf, _pf, _pi64]
 
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -158,6 +161,8 @@ SIGNATURES = {
     'td_mlpc_train': _MLPC + _FIT + _EPOCHS + [_d, _d, _d, _d, _i64, _i] + _SEED_STATS,
     'td_mlpc_grad': _MLPC + _FIT + _GRAD,
     'td_mlpc_forward': _MLPC + _FORWARD,
+    # (the shared arguments of td_mlp_train_loss, then epochs, loss, num_models, the per-model arrays, stats_dev)
+    'td_dnn_train_many': _MLP + [_i] + _TARGETS + _NETWORK + [_i, _i, _i, _i] + _MANY + [_vp],
 }
 _RESTYPE = {'td_last_error': _c.c_char_p}
 

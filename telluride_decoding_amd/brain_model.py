@@ -717,6 +717,94 @@ class BrainModelDNN(_BrainModelMlp):
     return out
 
 
+
+def fold_rows_used(dataset, held_out=None):
+  """Per-file rows of the training stream of a fold: the concatenation of the dataset's files without those in
+  `held_out` (file indices; None or empty: every file), cut into minibatches with drop_remainder=True -- only the
+  tail of the stream is lost, and it may swallow whole trailing files (the fold rule of regression.py's module
+  docstring).  A held-out file has 0 rows: the list equals Dataset(the other files, ...).rows_used() with zeros
+  spliced in.  Pure host arithmetic."""
+  held = set(int(f) for f in (held_out or ()))
+  n_files = len(dataset.files)
+  if any(f < 0 or f >= n_files for f in held):
+    raise ValueError('held_out must name files of the dataset (0..%d), not %s' % (n_files - 1, sorted(held)))
+  zipped = [0 if f in held else n for f, n in enumerate(dataset.zipped_lengths())]
+  keep = (sum(zipped) // dataset.batch_size) * dataset.batch_size
+  used = []
+  for n in zipped:
+    u = min(n, keep)
+    used.append(u)
+    keep -= u
+  return used
+
+
+def fit_many(models, dataset, *, held_out=None, epochs=1, shuffle_seeds=None):
+  """Trains several BrainModelDNNs on one dataset at once (td_dnn_train_many): every launch of the
+  fit carries all the models, which a single fit cannot do for the GPU (a step is three launches of a few dozen
+  workgroups).  `models`: compiled BrainModelDNNs of identical widths and the same compiled loss, each with its own
+  weights, RMSprop settings and state; state persists as fit keeps it.  held_out[m]: the file indices model m does
+  not train on (None or empty: all files) -- its stream is fold_rows_used(dataset, held_out[m]).  shuffle_seeds: None,
+  one seed for every model, or one per model (None: in order), as fit's shuffle_seed.
+  Returns one History per model.  Model m ends bit for bit where
+  models[m].fit(Dataset(the files it trains on, ...), epochs=epochs, shuffle_seed=...) would."""
+  models = list(models)
+  n = len(models)
+  if n == 0:
+    return []
+  for i, m in enumerate(models):
+    if not isinstance(m, BrainModelDNN):
+      raise TypeError('fit_many trains BrainModelDNN models, not %s (model %d)' % (type(m), i))
+    if m.optimizer is None:
+      raise RuntimeError('You must compile your model before training/testing (model %d).' % i)
+  first = models[0]
+  for i, m in enumerate(models):
+    if m._widths != first._widths or m.loss != first.loss:
+      raise ValueError('fit_many: model %d has widths %s and loss %r, model 0 %s and %r: one architecture and one '
+                       'loss per call' % (i, m._widths, m.loss, first._widths, first.loss))
+  if not _is_dataset(dataset):
+    raise TypeError('fit_many needs a brain_data.Dataset, not %s.' % type(dataset))
+  if dataset.mixup_batch:
+    raise ValueError('fit_many needs streams that are subsets of the files: a mixup_batch dataset shuffles input_2 '
+                     'and the output inside the minibatches of the full stream')
+  if dataset.max_batches is not None:
+    raise ValueError('fit_many: the dataset is limited to %r minibatches (take()); a fold\'s stream is cut from '
+                     'its own files' % (dataset.max_batches,))
+  first._check_limits(dataset)
+  held = [None] * n if held_out is None else list(held_out)
+  if len(held) != n:
+    raise ValueError('fit_many: %d models but %d held_out entries' % (n, len(held)))
+  if shuffle_seeds is None or not hasattr(shuffle_seeds, '__len__'):
+    seeds = [shuffle_seeds] * n
+  else:
+    seeds = list(shuffle_seeds)
+    if len(seeds) != n:
+      raise ValueError('fit_many: %d models but %d shuffle seeds' % (n, len(seeds)))
+  for seed in seeds:
+    if seed is not None and not 0 <= int(seed) < 2 ** 63:
+      raise ValueError('shuffle_seed must be in [0, 2^63), not %r' % (seed,))
+  used = [fold_rows_used(dataset, h) for h in held]
+  for i, u in enumerate(used):
+    if sum(u) < dataset.batch_size:
+      raise ValueError('fit_many: model %d is left with %d frames, no full minibatch of %d' % (
+          i, sum(n for f, n in enumerate(dataset.zipped_lengths()) if f not in set(held[i] or ())),
+          dataset.batch_size))
+  epochs = int(epochs)
+  if epochs <= 0:
+    return [History({key: [] for key in BrainModelDNN._HISTORY_KEYS}) for _ in models]
+  h = device.default_handle()
+  x, _, y, offs = dataset.device_arrays(h)
+  params = [m._device_params(h) for m in models]
+  for m, p in zip(models, params):
+    if m._state is None:
+      m._state = h.zeros((int(p.numel()),))
+  opts = [m.optimizer for m in models]
+  sums = device.dnn_train_many(x, y, offs, dataset.pre, dataset.post, first.num_hidden_list, params,
+                               [m._state for m in models], dataset.batch_size, epochs,
+                               [o.learning_rate for o in opts], [o.rho for o in opts], [o.epsilon for o in opts],
+                               used, input_offset=dataset.input_offset, shuffle_seeds=seeds, handle=h, loss=first.loss)
+  return [History(history_from_sums(s.cpu().numpy(), dataset.batch_size, first._output_width)) for s in sums]
+
+
 class Adam(object):
   """The Adam settings BrainModelClassifier trains with (Keras tf.keras.optimizers.Adam's arguments).  amsgrad is
   not implemented (compile raises NotImplementedError)."""

@@ -33,6 +33,12 @@
 // Host side (from struct MlpPlan on): every exported entry point packs its arguments into one MlpCall and calls
 // mlp_train, mlp_grad or mlp_forward; each of those checks the call (mlp_check_and_plan first, then its own
 // arguments, in the order a caller observes), lays out the scratch and queues the launches.
+//
+// td_dnn_train_many trains many regressors of one architecture on the same recordings at once (the folds of a
+// jackknife, a few learning rates): the same three (four) launches per step with the models in blockIdx.y.  The
+// kernels' bodies are __device__ functions of (the arguments, the launch's step); a single fit's kernels pass
+// their own kernel argument, the batched ones (mlp_*_many_kernel) the model's entry of a device table and a step
+// derived from the launch index.  Models share nothing but x and y, so each comes out as its own single fit.
 #include "td_common.h"
 
 #include <cmath>
@@ -166,6 +172,16 @@ __device__ __forceinline__ float mlp_xt(const MlpGeom& g, const RowInfo& ri, int
 
 enum { kUpdRmsprop = 0, kUpdAdam = 1, kUpdNone = 2 };
 
+// What changes from one slab launch of a call to the next.  The host loop of a single fit sets it in SlabArgs::at;
+// the batched kernels derive it per model from the launch index (mlp_many_step).
+struct SlabStep {
+  double* stats_out;      // six sums of the previous step (may be null); Pearson: seven, the last one L
+  const RowEntry* prev_rows;   // row tables of the previous / current step's epoch
+  const RowEntry* cur_rows;
+  int prev_epoch, prev_step;   // -1: no update
+  int cur_epoch, cur_step;     // -1: no forward
+};
+
 struct SlabArgs {
   MlpGeom g;
   float* params;
@@ -176,12 +192,8 @@ struct SlabArgs {
   const float* gpart;     // [n_head][n_small]
   const double* spart;    // [n_head][6]
   const double* lstat;    // Pearson: the previous step's loss L (written by head<2>)
-  double* stats_out;      // six sums of the previous step (may be null); Pearson: seven, the last one L
-  const RowEntry* prev_rows;   // row tables of the previous / current step's epoch
-  const RowEntry* cur_rows;
+  SlabStep at;
   int ks, nslices, n_head;
-  int prev_epoch, prev_step;   // -1: no update
-  int cur_epoch, cur_step;     // -1: no forward
   float lr, rho, eps;          // RMSprop; Adam: lr = this update's lr_t, rho = beta_1
   float beta2, omb1, omb2;     // Adam: beta_2, 1 - beta_1, 1 - beta_2 (each rounded once from double)
   int update;                  // kUpdRmsprop / kUpdAdam (state = m [P], then v [P]) / kUpdNone (the sums only)
@@ -194,7 +206,9 @@ __device__ __forceinline__ int mlp_rows_in_step(const MlpGeom& g, int step) {
 
 // Keras RMSprop without momentum: v = rho v + (1 - rho) g^2, w -= lr g / (sqrt(v) + eps); returns the new w
 __device__ __forceinline__ float mlp_rmsprop(float* p, float* v, float grad, float lr, float rho, float eps) {
-  const float vn = rho * *v + (1.f - rho) * (grad * grad);
+  // (the roundings spelled out -- rho v rounded, then one fused multiply-add -- so that every kernel this is
+  // inlined into computes the same bits; left to the compiler, which of the two products it fuses varies)
+  const float vn = fmaf(1.f - rho, grad * grad, rho * *v);
   const float pn = *p - lr * grad / (sqrtf(vn) + eps);
   *v = vn;
   *p = pn;
@@ -222,16 +236,16 @@ constexpr int kW1Groups = kSlabMaxKs * kMlpMaxWidth / 4 / kSlabThreads;   // (ro
 
 // dW1 of the rows [k0, k0 + ksl) over the rows of the previous step: thread group (kk, 4 columns); rows summed
 // in order within chunks of 64, the chunks in order
-__device__ void mlp_w1_grad(const SlabArgs& a, int k0, int ksl, float (*acc)[4], RowInfo* ri,
+__device__ void mlp_w1_grad(const SlabArgs& a, const SlabStep& st, int k0, int ksl, float (*acc)[4], RowInfo* ri,
                             float (*xs)[kSlabMaxKs + 1], float (*dzs)[kDzLd]) {
   const MlpGeom& g = a.g;
   const int w1 = g.w[1], w1q = (w1 + 3) / 4, tid = threadIdx.x;
-  const int rows = mlp_rows_in_step(g, a.prev_step);
+  const int rows = mlp_rows_in_step(g, st.prev_step);
   const int n_groups = ksl * w1q;
   for (int r0 = 0; r0 < rows; r0 += kSlabRowChunk) {
     const int nr = rows - r0 < kSlabRowChunk ? rows - r0 : kSlabRowChunk;
     __syncthreads();
-    if (tid < nr) ri[tid] = mlp_row(a.prev_rows, (long long)a.prev_step * g.batch + r0 + tid);
+    if (tid < nr) ri[tid] = mlp_row(st.prev_rows, (long long)st.prev_step * g.batch + r0 + tid);
     for (int i = tid; i < nr * w1q * 4; i += kSlabThreads) {
       const int j = i / nr, r = i - j * nr;
       dzs[r][j] = j < w1 ? a.dz1[(long long)j * g.batch + r0 + r] : 0.f;
@@ -259,8 +273,10 @@ __device__ void mlp_w1_grad(const SlabArgs& a, int k0, int ksl, float (*acc)[4],
   }
 }
 
+// The slab launch of one model: `a` is the launch's kernel argument (a single fit) or the model's entry of the
+// device table (the batched kernels); `st` says which steps this launch updates and runs forward.
 template <int NJ>
-__global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
+__device__ __forceinline__ void mlp_slab_body(const SlabArgs& a, const SlabStep& st) {
   __shared__ RowInfo ri[kSlabRowChunk];
   __shared__ float xs[kSlabRowChunk][kSlabMaxKs + 1];   // (+1: the forward reads a column, rows on other banks)
   __shared__ __attribute__((aligned(16))) float dzs[kSlabRowChunk][kDzLd];
@@ -270,7 +286,7 @@ __global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
   const int wg = blockIdx.x;
   if (wg >= a.nslices) {
     // the small layers' update and the loss sums of the previous step
-    if (a.prev_step < 0) return;
+    if (st.prev_step < 0) return;
     const int p = (wg - a.nslices) * kSlabThreads + tid;
     if (p < g.n_small && a.update != kUpdNone) {
       float s = 0.f;
@@ -278,29 +294,29 @@ __global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
       if (a.grad_out) a.grad_out[g.small0 + p] = s;
       else mlp_apply(a, g.small0 + p, s);
     }
-    if (wg == a.nslices && tid < 6 && a.stats_out) {
+    if (wg == a.nslices && tid < 6 && st.stats_out) {
       double s = 0.0;
       for (int hw = 0; hw < a.n_head; ++hw) s += a.spart[hw * 6 + tid];
-      a.stats_out[tid] = s;
+      st.stats_out[tid] = s;
     }
-    if (wg == a.nslices && tid == 6 && a.stats_out && g.pearson) a.stats_out[6] = a.lstat[0];
+    if (wg == a.nslices && tid == 6 && st.stats_out && g.pearson) st.stats_out[6] = a.lstat[0];
     return;
   }
   const int k0 = wg * a.ks;
   const int ksl = g.k - k0 < a.ks ? g.k - k0 : a.ks;
   float* w1p = a.params;   // W1 [k][w1]
-  const bool fwd = a.cur_step >= 0;
+  const bool fwd = st.cur_step >= 0;
   // the slice of W1 the forward multiplies by, zero-padded to NJ columns; the update below refreshes it
   if (fwd)
     for (int i = tid; i < kSlabMaxKs * NJ; i += kSlabThreads) {
       const int kk = i / NJ, j = i - kk * NJ;
       ws[kk][j] = (kk < ksl && j < w1) ? w1p[(long long)(k0 + kk) * w1 + j] : 0.f;
     }
-  if (a.prev_step >= 0 && a.update != kUpdNone) {
+  if (st.prev_step >= 0 && a.update != kUpdNone) {
     float acc[kW1Groups][4];
 #pragma unroll
     for (int o = 0; o < kW1Groups; ++o) acc[o][0] = acc[o][1] = acc[o][2] = acc[o][3] = 0.f;
-    mlp_w1_grad(a, k0, ksl, acc, ri, xs, dzs);
+    mlp_w1_grad(a, st, k0, ksl, acc, ri, xs, dzs);
     const int w1q = (w1 + 3) / 4;
 #pragma unroll
     for (int o = 0; o < kW1Groups; ++o) {
@@ -324,12 +340,12 @@ __global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
   }
   if (!fwd) return;
   // partial z1 of this step's rows over the slice: chunks of 64 rows staged in LDS, thread = (row, 4 columns)
-  const int rows = mlp_rows_in_step(g, a.cur_step);
+  const int rows = mlp_rows_in_step(g, st.cur_step);
   constexpr int kQ = NJ / 4;
   for (int r0 = 0; r0 < rows; r0 += kSlabRowChunk) {
     const int nr = rows - r0 < kSlabRowChunk ? rows - r0 : kSlabRowChunk;
     __syncthreads();
-    if (tid < nr) ri[tid] = mlp_row(a.cur_rows, (long long)a.cur_step * g.batch + r0 + tid);
+    if (tid < nr) ri[tid] = mlp_row(st.cur_rows, (long long)st.cur_step * g.batch + r0 + tid);
     __syncthreads();
     for (int i = tid; i < nr * ksl; i += kSlabThreads) {
       const int r = i / ksl, kk = i - r * ksl;
@@ -354,9 +370,14 @@ __global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
   }
 }
 
+template <int NJ>
+__global__ __launch_bounds__(kSlabThreads) void mlp_slab_kernel(SlabArgs a) {
+  mlp_slab_body<NJ>(a, a.at);
+}
+
 // z1 = sum of the slices' partials in slice order, + b1: thread per (unit, row)
-__global__ __launch_bounds__(256) void mlp_z1_kernel(const float* __restrict__ zpart, int nslices, int w1, int batch,
-                                                     int rows, const float* __restrict__ b1, float* __restrict__ z1) {
+__device__ __forceinline__ void mlp_z1_body(const float* __restrict__ zpart, int nslices, int w1, int batch, int rows,
+                                            const float* __restrict__ b1, float* __restrict__ z1) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= w1 * batch) return;
   const int j = i / batch, r = i - j * batch;
@@ -369,12 +390,23 @@ __global__ __launch_bounds__(256) void mlp_z1_kernel(const float* __restrict__ z
   z1[i] = s + b1[j];
 }
 
+__global__ __launch_bounds__(256) void mlp_z1_kernel(const float* __restrict__ zpart, int nslices, int w1, int batch,
+                                                     int rows, const float* __restrict__ b1, float* __restrict__ z1) {
+  mlp_z1_body(zpart, nslices, w1, batch, rows, b1, z1);
+}
+
+// What changes from one head launch of a call to the next (as SlabStep).
+struct HeadStep {
+  const RowEntry* rows_tab;
+  int epoch, step;
+};
+
 struct HeadArgs {
   MlpGeom g;
   const float* params;
   const float* zpart;
   int nslices;
-  int epoch, step;
+  HeadStep at;
   int backward;
   float* dz1;       // [w1][batch]
   float* gpart;     // [n_head][n_small]
@@ -383,7 +415,6 @@ struct HeadArgs {
   double* lstat;    // Pearson: the step's loss
   float* out;       // inference: [rows, d] (row stride ldout)
   long long ldout;
-  const RowEntry* rows_tab;
   const float* z1;  // [w1][batch]: b1 + the slices' partials (mlp_z1_kernel)
   int act_off[kMlpMaxHidden + 2];   // LDS offsets of the activations of layer l = 1 .. nl ([w_l][64])
   int act_floats;
@@ -403,8 +434,9 @@ __device__ __forceinline__ float mlp_bce(float z, float y) {
 // z1 = b1 + partials, the small layers, the loss sums and the backward pass of 64 rows.
 // PP 0: all of it in one launch (mse, bce).  The Pearson loss: PP 1 = forward, sums and the partial moments;
 // PP 2 = forward again, the moments' reduction, dL/dp and the backward pass.
+// (`a`, `st`: as mlp_slab_body)
 template <int PP>
-__global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
+__device__ __forceinline__ void mlp_head_body(const HeadArgs& a, const HeadStep& st) {
   extern __shared__ float lds[];
   const MlpGeom& g = a.g;
   const int tid = threadIdx.x, nl = g.nl, d = g.w[nl];
@@ -415,11 +447,11 @@ __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
   for (int i = tid; i < g.n_small; i += kHeadRows) wsm[i] = a.params[g.small0 + i];
   const float* prm = wsm - g.small0;                  // indexed by parameter offset
   __syncthreads();
-  const int rows = mlp_rows_in_step(g, a.step);
+  const int rows = mlp_rows_in_step(g, st.step);
   const int r = blockIdx.x * kHeadRows + tid;
   const bool valid = r < rows;
   long long yrow = 0;
-  if (valid && !a.out) yrow = mlp_row(a.rows_tab, (long long)a.step * g.batch + r).yrow;
+  if (valid && !a.out) yrow = mlp_row(st.rows_tab, (long long)st.step * g.batch + r).yrow;
   // layer 1: b1 + the slices' partial sums (mlp_z1_kernel)
   {
     const int w1 = g.w[1];
@@ -447,7 +479,7 @@ __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
     if (valid)
       for (int o = 0; o < d; ++o) {
         const float pv = p[o * kHeadRows + tid];
-        a.out[((long long)a.step * g.batch + r) * a.ldout + o] = g.bce ? mlp_sigmoid(pv) : pv;
+        a.out[((long long)st.step * g.batch + r) * a.ldout + o] = g.bce ? mlp_sigmoid(pv) : pv;
       }
     return;
   }
@@ -600,6 +632,76 @@ __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
   }
 }
 
+template <int PP>
+__global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
+  mlp_head_body<PP>(a, a.at);
+}
+
+// ---- many models in one launch (td_dnn_train_many): blockIdx.y = model --------------------------------------
+// A model's entry of the device table: the arguments its own launches of a single fit would carry (their `at`
+// is not read), and what derives `at` from the launch index.  Models share x, y and the architecture; each has
+// its own stream (stream_offs, n_rows), parameters, state, scratch, optimizer settings and row tables.
+struct ManyModel {
+  SlabArgs slab;
+  HeadArgs head;
+  RowEntry* rows[2];      // row tables of even / odd epochs (in order: rows[0] serves every epoch)
+  double* stats;          // [epochs][max_steps][nstat]
+  int steps, total;       // steps per epoch of this model; epochs x steps
+  int max_steps, nstat;
+};
+
+// Round t of the call runs this model's step t (epoch t / steps, step t % steps, while t < total) forward and
+// applies the update of its step t - 1, exactly the pair a single fit's launch t carries.  False: nothing to do
+// (a model with fewer steps than the call's longest has finished).
+__device__ __forceinline__ bool mlp_many_step(const ManyModel& m, int t, SlabStep* st) {
+  const bool cur = t < m.total, prev = t >= 1 && t - 1 < m.total;
+  if (!cur && !prev) return false;
+  const int shuffle = m.slab.g.shuffle;
+  st->cur_epoch = st->cur_step = st->prev_epoch = st->prev_step = -1;
+  st->stats_out = nullptr;
+  st->prev_rows = st->cur_rows = m.rows[0];
+  if (cur) {
+    st->cur_epoch = t / m.steps;
+    st->cur_step = t - st->cur_epoch * m.steps;
+    if (shuffle) st->cur_rows = m.rows[st->cur_epoch & 1];
+  }
+  if (prev) {
+    st->prev_epoch = (t - 1) / m.steps;
+    st->prev_step = t - 1 - st->prev_epoch * m.steps;
+    if (shuffle) st->prev_rows = m.rows[st->prev_epoch & 1];
+    st->stats_out = m.stats + (long long)m.nstat * ((long long)st->prev_epoch * m.max_steps + st->prev_step);
+  }
+  return true;
+}
+
+template <int NJ>
+__global__ __launch_bounds__(kSlabThreads) void mlp_slab_many_kernel(const ManyModel* __restrict__ tab, int t) {
+  const ManyModel& m = tab[blockIdx.y];
+  SlabStep st;
+  if (!mlp_many_step(m, t, &st)) return;
+  mlp_slab_body<NJ>(m.slab, st);
+}
+
+__global__ __launch_bounds__(256) void mlp_z1_many_kernel(const ManyModel* __restrict__ tab, int t) {
+  const ManyModel& m = tab[blockIdx.y];
+  if (t >= m.total) return;
+  const MlpGeom& g = m.head.g;
+  const int step = t % m.steps;
+  mlp_z1_body(m.head.zpart, m.head.nslices, g.w[1], g.batch, mlp_rows_in_step(g, step), m.head.params + g.off_b[0],
+              const_cast<float*>(m.head.z1));
+}
+
+template <int PP>
+__global__ __launch_bounds__(kHeadRows) void mlp_head_many_kernel(const ManyModel* __restrict__ tab, int t) {
+  const ManyModel& m = tab[blockIdx.y];
+  if (t >= m.total) return;
+  HeadStep st;
+  st.epoch = t / m.steps;
+  st.step = t - st.epoch * m.steps;
+  st.rows_tab = m.rows[m.head.g.shuffle ? st.epoch & 1 : 0];
+  mlp_head_body<PP>(m.head, st);
+}
+
 struct MlpPlan {
   MlpGeom g;
   int ks = 0, nslices = 0, n_small_wg = 0, n_head = 0, nj = 0;
@@ -733,7 +835,7 @@ int mlp_launch_slab(td_handle* h, const MlpPlan& plan, const SlabArgs& a, bool w
 
 int mlp_launch_head(td_handle* h, const MlpPlan& plan, const HeadArgs& a) {
   const MlpGeom& g = a.g;
-  const int rows = (int)std::min<long long>(g.batch, g.n_rows - (long long)a.step * g.batch);
+  const int rows = (int)std::min<long long>(g.batch, g.n_rows - (long long)a.at.step * g.batch);
   hipLaunchKernelGGL(mlp_z1_kernel, dim3((unsigned)td_ceil_div((int64_t)g.w[1] * g.batch, 256)), dim3(256), 0,
                      h->stream, a.zpart, plan.nslices, g.w[1], g.batch, rows, a.params + g.off_b[0],
                      const_cast<float*>(a.z1));
@@ -831,7 +933,7 @@ void mlp_fill(const MlpPlan& plan, const MlpWork& w, SlabArgs* sa, HeadArgs* ha)
   sa->params = w.params; sa->state = w.state;
   sa->zpart = w.zpart; sa->dz1 = w.dz1; sa->gpart = w.gpart; sa->spart = w.spart; sa->lstat = w.lstat;
   sa->ks = plan.ks; sa->nslices = plan.nslices; sa->n_head = plan.n_head;
-  sa->prev_epoch = sa->prev_step = sa->cur_epoch = sa->cur_step = -1;
+  sa->at.prev_epoch = sa->at.prev_step = sa->at.cur_epoch = sa->at.cur_step = -1;
   ha->g = plan.g;
   ha->params = w.params; ha->zpart = w.zpart; ha->nslices = plan.nslices;
   ha->dz1 = w.dz1; ha->gpart = w.gpart; ha->spart = w.spart; ha->mpart = w.mpart; ha->lstat = w.lstat;
@@ -839,7 +941,7 @@ void mlp_fill(const MlpPlan& plan, const MlpWork& w, SlabArgs* sa, HeadArgs* ha)
   ha->act_floats = plan.act_floats; ha->maxw = plan.maxw;
   ha->z1 = w.z1;
   ha->backward = 1;
-  sa->prev_rows = sa->cur_rows = ha->rows_tab = w.rows[0];
+  sa->at.prev_rows = sa->at.cur_rows = ha->at.rows_tab = w.rows[0];
 }
 
 // the row table of `epoch` into tab (queued)
@@ -913,22 +1015,22 @@ int mlp_train(td_handle* h, const char* fn, const MlpCall& a, int epochs, float*
     // epoch e still updates with the last rows of epoch e - 1)
     RowEntry* tab = plan.g.shuffle ? w.rows[e & 1] : w.rows[0];
     if (e == 0 || plan.g.shuffle) TD_TRY(mlp_launch_rows(h, plan.g, e, tab));
-    sa.prev_rows = sa.cur_rows;
-    sa.cur_rows = ha.rows_tab = tab;
+    sa.at.prev_rows = sa.at.cur_rows;
+    sa.at.cur_rows = ha.at.rows_tab = tab;
     for (int s = 0; s < steps; ++s) {
-      if (s == 1) sa.prev_rows = tab;
-      sa.prev_epoch = pe; sa.prev_step = ps; sa.cur_epoch = e; sa.cur_step = s;
-      sa.stats_out = ps >= 0 ? stats_dev + nstat * ((long long)pe * steps + ps) : nullptr;
+      if (s == 1) sa.at.prev_rows = tab;
+      sa.at.prev_epoch = pe; sa.at.prev_step = ps; sa.at.cur_epoch = e; sa.at.cur_step = s;
+      sa.at.stats_out = ps >= 0 ? stats_dev + nstat * ((long long)pe * steps + ps) : nullptr;
       if (ps >= 0) mlp_set_update(&sa, opt, (int64_t)pe * steps + ps);
       TD_TRY(mlp_launch_slab(h, plan, sa, ps >= 0));
-      ha.epoch = e; ha.step = s;
+      ha.at.epoch = e; ha.at.step = s;
       TD_TRY(mlp_launch_head(h, plan, ha));
       pe = e; ps = s;
     }
   }
-  sa.prev_epoch = pe; sa.prev_step = ps; sa.cur_epoch = sa.cur_step = -1;
-  sa.prev_rows = sa.cur_rows;
-  sa.stats_out = stats_dev + nstat * ((long long)pe * steps + ps);
+  sa.at.prev_epoch = pe; sa.at.prev_step = ps; sa.at.cur_epoch = sa.at.cur_step = -1;
+  sa.at.prev_rows = sa.at.cur_rows;
+  sa.at.stats_out = stats_dev + nstat * ((long long)pe * steps + ps);
   mlp_set_update(&sa, opt, (int64_t)pe * steps + ps);
   TD_TRY(mlp_launch_slab(h, plan, sa, true));
   if (update) {
@@ -961,14 +1063,14 @@ int mlp_grad(td_handle* h, const char* fn, const MlpCall& a, int batch_index, co
   mlp_fill(plan, w, &sa, &ha);
   // the training step's launches: forward, head, and the update launch writing the gradient instead
   TD_TRY(mlp_launch_rows(h, plan.g, 0, w.rows[0]));
-  sa.cur_epoch = 0; sa.cur_step = batch_index;
+  sa.at.cur_epoch = 0; sa.at.cur_step = batch_index;
   TD_TRY(mlp_launch_slab(h, plan, sa, false));
-  ha.epoch = 0; ha.step = batch_index;
+  ha.at.epoch = 0; ha.at.step = batch_index;
   TD_TRY(mlp_launch_head(h, plan, ha));
-  sa.cur_epoch = sa.cur_step = -1;
-  sa.prev_epoch = 0; sa.prev_step = batch_index;
+  sa.at.cur_epoch = sa.at.cur_step = -1;
+  sa.at.prev_epoch = 0; sa.at.prev_step = batch_index;
   sa.grad_out = grad_dev;
-  sa.stats_out = stats_dev;
+  sa.at.stats_out = stats_dev;
   TD_TRY(mlp_launch_slab(h, plan, sa, true));
   return TD_OK;
 }
@@ -995,10 +1097,191 @@ int mlp_forward(td_handle* h, const char* fn, const MlpCall& a, const float* par
   TD_TRY(mlp_launch_rows(h, plan.g, 0, w.rows[0]));
   const int chunks = (int)td_ceil_div(n_rows, kFwdChunk);
   for (int s = 0; s < chunks; ++s) {
-    sa.cur_epoch = 0; sa.cur_step = s;
+    sa.at.cur_epoch = 0; sa.at.cur_step = s;
     TD_TRY(mlp_launch_slab(h, plan, sa, false));
-    ha.epoch = 0; ha.step = s;
+    ha.at.epoch = 0; ha.at.step = s;
     TD_TRY(mlp_launch_head(h, plan, ha));
+  }
+  return TD_OK;
+}
+
+// ---- td_dnn_train_many ------------------------------------------------------------------------------------
+struct ManyCall {
+  int num_models;
+  const int64_t* rows_used;        // host [num_models][num_files]
+  float* const* params;            // host [num_models] device pointers
+  float* const* state;
+  const float *lr, *rho, *eps;     // host [num_models]
+  const int64_t* shuffle_seed;     // host [num_models], < 0: in order
+};
+
+// a call's scratch, sized on a first pass (base null) and handed out on a second
+struct MlpBump {
+  char* base;
+  size_t at;
+  template <typename T>
+  T* take(size_t n) {
+    at = td_round_up(at, 256);
+    T* p = base ? reinterpret_cast<T*>(base + at) : nullptr;
+    at += n * sizeof(T);
+    return p;
+  }
+};
+
+int mlp_launch_slab_many(td_handle* h, const MlpPlan& plan, int num_models, const ManyModel* tab, int t) {
+  const dim3 grid(plan.nslices + plan.n_small_wg, num_models), block(kSlabThreads);
+  switch (plan.nj) {
+    case 4: hipLaunchKernelGGL(mlp_slab_many_kernel<4>, grid, block, 0, h->stream, tab, t); break;
+    case 8: hipLaunchKernelGGL(mlp_slab_many_kernel<8>, grid, block, 0, h->stream, tab, t); break;
+    case 16: hipLaunchKernelGGL(mlp_slab_many_kernel<16>, grid, block, 0, h->stream, tab, t); break;
+    case 24: hipLaunchKernelGGL(mlp_slab_many_kernel<24>, grid, block, 0, h->stream, tab, t); break;
+    case 32: hipLaunchKernelGGL(mlp_slab_many_kernel<32>, grid, block, 0, h->stream, tab, t); break;
+    case 48: hipLaunchKernelGGL(mlp_slab_many_kernel<48>, grid, block, 0, h->stream, tab, t); break;
+    default: hipLaunchKernelGGL(mlp_slab_many_kernel<64>, grid, block, 0, h->stream, tab, t); break;
+  }
+  TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
+int mlp_launch_head_many(td_handle* h, const MlpPlan& plan, int num_models, const ManyModel* tab, int t) {
+  const MlpGeom& g = plan.g;
+  hipLaunchKernelGGL(mlp_z1_many_kernel, dim3((unsigned)td_ceil_div((int64_t)g.w[1] * g.batch, 256), num_models),
+                     dim3(256), 0, h->stream, tab, t);
+  const dim3 grid(plan.n_head, num_models), block(kHeadRows);
+  if (g.pearson) {
+    hipLaunchKernelGGL(mlp_head_many_kernel<1>, grid, block, plan.head_lds, h->stream, tab, t);
+    hipLaunchKernelGGL(mlp_head_many_kernel<2>, grid, block, plan.head_lds, h->stream, tab, t);
+  } else {
+    hipLaunchKernelGGL(mlp_head_many_kernel<0>, grid, block, plan.head_lds, h->stream, tab, t);
+  }
+  TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
+// mlp_train for num_models regressors at once: every check of every model first, then working copies, the rounds
+// of launches (round t = launch t of every model's own fit, models in blockIdx.y) and the commit.
+int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, const ManyCall& mc, double* stats_dev) {
+  MlpPlan plan;
+  TD_TRY(mlp_check_and_plan(h, fn, a, &plan));
+  const int nm = mc.num_models, nf = a.num_files, batch_rows = a.batch_rows;
+  TD_REQUIRE(h, batch_rows <= kMlpMaxB, "%s: batch of %d rows exceeds %d", fn, batch_rows, kMlpMaxB);
+  TD_REQUIRE(h, nm >= 1 && nm <= TD_DNN_MANY_MAX_MODELS, "%s: %d models (1 .. %d a call)", fn, nm,
+             TD_DNN_MANY_MAX_MODELS);
+  TD_REQUIRE(h, a.y && a.ldy >= a.d && mc.rows_used && mc.params && mc.state && mc.lr && mc.rho && mc.eps &&
+                    mc.shuffle_seed, "%s: NULL argument or ldy too small", fn);
+  TD_REQUIRE(h, epochs >= 0, "%s: negative epoch count", fn);
+  std::vector<std::vector<long long>> so(nm);
+  int max_steps = 0;
+  long long max_total = 0;
+  for (int m = 0; m < nm; ++m) {
+    TD_REQUIRE(h, mc.params[m] && mc.state[m], "%s: model %d: NULL parameters or state", fn, m);
+    for (int j = 0; j < m; ++j)
+      TD_REQUIRE(h, mc.params[j] != mc.params[m] && mc.state[j] != mc.state[m],
+                 "%s: models %d and %d share their parameters or state", fn, j, m);
+    TD_REQUIRE(h, std::isfinite(mc.lr[m]) && std::isfinite(mc.rho[m]) && std::isfinite(mc.eps[m]),
+               "%s: model %d: non-finite optimizer setting", fn, m);
+    MlpCall am = a;
+    am.rows_used = mc.rows_used + (size_t)m * nf;
+    TD_TRY(mlp_stream_offsets(h, fn, am, &so[m]));
+    const long long n_rows = so[m][nf];
+    TD_REQUIRE(h, n_rows >= 1, "%s: model %d: no rows to train on", fn, m);
+    const long long steps = td_ceil_div(n_rows, batch_rows);
+    TD_REQUIRE(h, (long long)epochs * steps < (1LL << 31) - 1, "%s: model %d: %lld launches", fn, m,
+               (long long)epochs * steps);
+    max_steps = std::max<int>(max_steps, (int)steps);
+    max_total = std::max<long long>(max_total, (long long)epochs * steps);
+  }
+  TD_REQUIRE(h, epochs == 0 || stats_dev, "%s: NULL stats buffer", fn);
+  if (epochs == 0) return TD_OK;
+  MlpGeom& g = plan.g;
+  g.y = a.y; g.ldy = a.ldy;
+  const int nstat = g.pearson ? 7 : 6;
+  const size_t n_off = nf + 1;
+  // the scratch: the table, the offsets, then every model's own block
+  std::vector<MlpWork> work(nm);
+  long long* so_dev = nullptr;
+  ManyModel* tab_dev = nullptr;
+  MlpBump bump = {nullptr, 0};
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass) {
+      void* base = nullptr;
+      TD_TRY(td_scratch(h, bump.at, &base));
+      bump = {static_cast<char*>(base), 0};
+    }
+    tab_dev = bump.take<ManyModel>(nm);
+    so_dev = bump.take<long long>((size_t)(nm + 1) * n_off);     // the file offsets, then every model's stream
+    for (int m = 0; m < nm; ++m) {
+      MlpWork& w = work[m];
+      const long long n_rows = so[m][nf];
+      w.rows[0] = bump.take<RowEntry>(n_rows);
+      w.rows[1] = mc.shuffle_seed[m] >= 0 ? bump.take<RowEntry>(n_rows) : w.rows[0];
+      w.spart = bump.take<double>((size_t)plan.n_head * 6);
+      w.mpart = bump.take<double>((size_t)plan.n_head * 5 * kMlpMaxD);
+      w.lstat = bump.take<double>(1);
+      w.params = bump.take<float>(g.n_params);
+      w.state = bump.take<float>(g.n_params);
+      w.zpart = bump.take<float>((size_t)plan.nslices * g.w[1] * g.batch);
+      w.dz1 = bump.take<float>((size_t)g.w[1] * g.batch);
+      w.z1 = bump.take<float>((size_t)g.w[1] * g.batch);
+      w.gpart = bump.take<float>((size_t)plan.n_head * g.n_small);
+      w.file_offs = so_dev;
+      w.stream_offs = so_dev + (size_t)(m + 1) * n_off;
+    }
+  }
+  std::vector<long long> so_host((size_t)(nm + 1) * n_off);
+  for (size_t f = 0; f < n_off; ++f) so_host[f] = a.file_offsets[f];
+  for (int m = 0; m < nm; ++m) std::copy(so[m].begin(), so[m].end(), so_host.begin() + (size_t)(m + 1) * n_off);
+  std::vector<ManyModel> tab(nm);
+  std::vector<MlpGeom> geom(nm);
+  for (int m = 0; m < nm; ++m) {
+    const MlpWork& w = work[m];
+    MlpPlan pm = plan;
+    pm.g.file_offs = w.file_offs; pm.g.stream_offs = w.stream_offs;
+    pm.g.n_rows = so[m][nf];
+    pm.g.shuffle = mc.shuffle_seed[m] >= 0;
+    pm.g.seed_lo = (unsigned)((uint64_t)mc.shuffle_seed[m] & 0xffffffffu);
+    pm.g.seed_hi = (unsigned)((uint64_t)mc.shuffle_seed[m] >> 32);
+    geom[m] = pm.g;
+    ManyModel& t = tab[m];
+    memset(&t, 0, sizeof(t));
+    mlp_fill(pm, w, &t.slab, &t.head);
+    t.slab.update = kUpdRmsprop;
+    t.slab.lr = mc.lr[m]; t.slab.rho = mc.rho[m]; t.slab.eps = mc.eps[m];
+    t.rows[0] = w.rows[0]; t.rows[1] = w.rows[1];
+    t.steps = (int)td_ceil_div(pm.g.n_rows, batch_rows);
+    t.total = epochs * t.steps;
+    t.max_steps = max_steps; t.nstat = nstat;
+    t.stats = stats_dev + (size_t)m * epochs * max_steps * nstat;
+  }
+  TD_TRY(td_upload_async(h, so_host.data(), sizeof(long long) * so_host.size(), so_dev));
+  TD_TRY(td_upload_async(h, tab.data(), sizeof(ManyModel) * nm, tab_dev));
+  TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_many_kernel<0>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
+  TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_many_kernel<1>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
+  TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_many_kernel<2>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
+  // work on copies: the callers' parameters change only when every launch has been queued
+  const size_t pbytes = sizeof(float) * g.n_params;
+  for (int m = 0; m < nm; ++m) {
+    TD_HIP(h, hipMemcpyAsync(work[m].params, mc.params[m], pbytes, hipMemcpyDeviceToDevice, h->stream));
+    TD_HIP(h, hipMemcpyAsync(work[m].state, mc.state[m], pbytes, hipMemcpyDeviceToDevice, h->stream));
+    if (!geom[m].shuffle) TD_TRY(mlp_launch_rows(h, geom[m], 0, work[m].rows[0]));
+  }
+  for (long long t = 0; t <= max_total; ++t) {
+    // shuffled: the table of a model's epoch e, in front of the round that starts it (its other table still
+    // serves the update of the last step of epoch e - 1)
+    for (int m = 0; m < nm; ++m)
+      if (geom[m].shuffle && t < tab[m].total && t % tab[m].steps == 0) {
+        const int e = (int)(t / tab[m].steps);
+        TD_TRY(mlp_launch_rows(h, geom[m], e, work[m].rows[e & 1]));
+      }
+    TD_TRY(mlp_launch_slab_many(h, plan, nm, tab_dev, (int)t));
+    if (t < max_total) TD_TRY(mlp_launch_head_many(h, plan, nm, tab_dev, (int)t));
+  }
+  for (int m = 0; m < nm; ++m) {
+    TD_HIP(h, hipMemcpyAsync(mc.params[m], work[m].params, pbytes, hipMemcpyDeviceToDevice, h->stream));
+    TD_HIP(h, hipMemcpyAsync(mc.state[m], work[m].state, pbytes, hipMemcpyDeviceToDevice, h->stream));
   }
   return TD_OK;
 }
@@ -1084,4 +1367,17 @@ int td_mlpc_forward(td_handle* h, const float* x_dev, int64_t ldx, const float* 
   const MlpCall a = {{x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host, num_files,
                      input_offset, nullptr, nullptr, 0, d, hidden_host, num_hidden, kFwdChunk, 0, true};
   return mlp_forward(h, "td_mlpc_forward", a, params_dev, out_dev, ldout);
+}
+
+int td_dnn_train_many(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
+                      int c, int pre, int post, int input_offset, const float* y_dev, int64_t ldy, int d,
+                      const int* hidden_host, int num_hidden, int batch_rows, int epochs, int loss, int num_models,
+                      const int64_t* rows_used_host, float* const* params_dev_host, float* const* state_dev_host,
+                      const float* lr_host, const float* rho_host, const float* eps_host,
+                      const int64_t* shuffle_seed_host, double* stats_dev) {
+  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, nullptr,
+                     y_dev, ldy, d, hidden_host, num_hidden, batch_rows, loss, false};
+  const ManyCall mc = {num_models, rows_used_host, params_dev_host, state_dev_host, lr_host, rho_host, eps_host,
+                       shuffle_seed_host};
+  return mlp_train_many(h, "td_dnn_train_many", a, epochs, mc, stats_dev);
 }

@@ -1071,3 +1071,44 @@ def mlpc_forward(x, x2, file_offsets, pre, post, pre2, post2, hidden, d, params,
   _check_x2(x, x2)
   return _mlp_forward(h, h.lib.td_mlpc_forward, x, x2, (pre, post, pre2, post2), file_offsets, input_offset, hidden,
                       d, params)
+
+
+# td_dnn_train_many: models per call (TD_DNN_MANY_MAX_MODELS of include/td_hotpath.h); dnn_train_many splits a longer
+# list into calls of this many.  A module attribute so that a test can lower it.
+DNN_MANY_MAX_MODELS = 64
+
+
+def dnn_train_many(x, y, file_offsets, pre, post, hidden, params, states, batch_rows, epochs, lrs, rhos, epss,
+                   rows_used, input_offset=0, shuffle_seeds=None, handle=None, loss='mse'):
+  """mlp_train for many regressors of one architecture at once (td_dnn_train_many): params[m] / states[m] are model
+  m's packed float32 parameters and RMSprop accumulators (device, updated in place), lrs / rhos / epss / shuffle_seeds
+  (None: in order) its settings, rows_used[m][f] the rows of file f in its stream (0: a file it does not train on).
+  Returns one device float64 tensor per model, [epochs, its steps, 6 or 7] as mlp_train returns it.  More than
+  DNN_MANY_MAX_MODELS models go through several calls."""
+  h = handle or default_handle()
+  code = _mlp_loss(loss)
+  nstat = 7 if code else 6
+  n_models, epochs, batch_rows = len(params), int(epochs), int(batch_rows)
+  seeds = [None] * n_models if shuffle_seeds is None else list(shuffle_seeds)
+  used_all = np.ascontiguousarray(rows_used, dtype=np.int64).reshape(n_models, -1)
+  if not (len(states) == len(lrs) == len(rhos) == len(epss) == len(seeds) == n_models):
+    raise ValueError('dnn_train_many: %d models, but a per-model argument of another length' % n_models)
+  head, net, keep = _mlp_views(h, x, None, (pre, post), file_offsets, input_offset, hidden)
+  if used_all.shape[1] != len(keep[0]) - 1:
+    raise ValueError('dnn_train_many: rows_used has %d files, the recordings %d' % (used_all.shape[1], len(keep[0]) - 1))
+  out = []
+  cap = max(1, int(DNN_MANY_MAX_MODELS))
+  for m0 in range(0, n_models, cap):
+    m1 = min(m0 + cap, n_models)
+    n = m1 - m0
+    used, used_p = _lib.i64_array(used_all[m0:m1])
+    steps = [-(-int(u.sum()) // batch_rows) if batch_rows > 0 else 0 for u in used]
+    stats = h.zeros((n, max(epochs, 0), max(steps + [0]), nstat), 'float64')
+    par = (ctypes.c_void_p * n)(*[p.data_ptr() for p in params[m0:m1]])
+    sta = (ctypes.c_void_p * n)(*[s.data_ptr() for s in states[m0:m1]])
+    f32 = lambda values: (ctypes.c_float * n)(*[float(v) for v in values[m0:m1]])
+    seed, seed_p = _lib.i64_array([-1 if s is None else int(s) for s in seeds[m0:m1]])
+    h.check(h.lib.td_dnn_train_many(*head, _ptr(y), y.stride(0), int(y.shape[1]), *net, batch_rows, epochs, code, n,
+                                    used_p, par, sta, f32(lrs), f32(rhos), f32(epss), seed_p, _ptr(stats)))
+    out += [stats[i, :, :steps[i]] for i in range(n)]
+  return out

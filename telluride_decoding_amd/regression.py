@@ -514,6 +514,97 @@ def _jackknife_cca(dataset, regularization_list, world_size, device, folds, mode
   return results
 
 
+# The route jackknife_dnn takes without _route: the folds in batched fit_many calls, or 'per_fold' (DESIGN section 18
+# has the measurement that decides it)
+DNN_ROUTE = 'batched'
+DNN_METRICS = ('loss', 'pearson_correlation_first', 'mse')
+
+
+def _subset(dataset, files):
+  """A Dataset of some of `dataset`'s recordings with its batch size, contexts and offset."""
+  from telluride_decoding_amd import brain_data
+  return brain_data.Dataset([dataset.files[f] for f in files], dataset.batch_size, dataset.pre, dataset.post,
+                            dataset.pre2, dataset.post2, dataset.input_offset)
+
+
+def jackknife_dnn(dataset, num_hidden_list=None, *, learning_rates=(1e-3,), epochs=1, loss='mse', seed=0,
+                  shuffle_seed=None, folds=None, test_metric='pearson_correlation_first', _route=None):
+  """The leave-one-file-out jackknife of the fully connected regressor (reference regression.jackknife_one_model
+  with dnn_regressor='fullyconnected', regression.py:196-214, one fit after another there): one BrainModelDNN of
+  `num_hidden_list` per (learning rate, held-out file), all trained together by brain_model.fit_many -- every launch
+  carries every model -- then each scored on its held-out file.
+
+  Returns the sweeps' OrderedDict {learning rate: (mean, std)} of the held-out `test_metric` plus 'all_runs'
+  [len(learning_rates), F], and 'models' ([learning rate][fold], trained and usable) and 'history' (the same shape,
+  each a fit's History.history).  Every model starts from the weights of `seed` (the reference builds the model once)
+  and is compiled with RMSprop(learning_rate) on `loss` ('mse' or 'pearson'); `shuffle_seed` (None: in order) is
+  shared.  A fold's training stream is brain_model.fold_rows_used's; its held-out file is scored as
+  BrainModelDNN.evaluate scores a Dataset of that file alone (same batch, context and offset).
+  folds: as jackknife_over_regularizations.  _route: 'batched', or 'per_fold' = one fit after another on a Dataset of
+  the fold's files (the same bits; what a sweep falls back to when the batched call's scratch does not fit);
+  None = DNN_ROUTE.  LAST_SWEEP['dnn_route'] says which one ran."""
+  from telluride_decoding_amd import brain_model
+  if test_metric not in DNN_METRICS:
+    raise ValueError('Could not find metric %s in results %s.' % (test_metric, list(DNN_METRICS)))
+  route = DNN_ROUTE if _route is None else _route
+  if route not in ('batched', 'per_fold'):
+    raise ValueError('_route must be \'batched\' or \'per_fold\', not %r' % (route,))
+  n_files = len(dataset.files)
+  if n_files < 2:
+    raise ValueError('Need at least two files for a jackknife test.')
+  fold_list = list(range(n_files)) if folds is None else sorted(set(int(f) for f in folds))
+  if not fold_list or fold_list[0] < 0 or fold_list[-1] >= n_files:
+    raise ValueError('folds must name files of the dataset (0..%d), not %s' % (n_files - 1, folds))
+  rates = [float(lr) for lr in learning_rates]
+  if not rates:
+    raise ValueError('Need at least one learning rate.')
+
+  def build():
+    grid = []
+    for lr in rates:
+      row = [brain_model.BrainModelDNN(dataset, num_hidden_list, seed=seed) for _ in fold_list]
+      for m in row:
+        m.compile(optimizer=brain_model.RMSprop(learning_rate=lr), loss=loss)
+      grid.append(row)
+    return grid
+
+  def per_fold(grid):
+    out = [[] for _ in rates]
+    for fi, f in enumerate(fold_list):
+      train = _subset(dataset, [g for g in range(n_files) if g != f])
+      for li in range(len(rates)):
+        out[li].append(grid[li][fi].fit(train, epochs=epochs, shuffle_seed=shuffle_seed))
+    return out
+
+  models = build()
+  if route == 'batched':
+    try:
+      flat = brain_model.fit_many([m for row in models for m in row], dataset,
+                                  held_out=[[f] for _ in rates for f in fold_list], epochs=epochs,
+                                  shuffle_seeds=shuffle_seed)
+      hist = [flat[li * len(fold_list):(li + 1) * len(fold_list)] for li in range(len(rates))]
+    except MemoryError:
+      # the scratch of the batched call did not fit; models of an earlier chunk may have trained: start again
+      route = 'per_fold'
+      models = build()
+  if route == 'per_fold':
+    hist = per_fold(models)
+  LAST_SWEEP['dnn_route'] = route
+  runs = np.zeros((len(rates), len(fold_list)))
+  for fi, f in enumerate(fold_list):
+    held = _subset(dataset, [f])
+    for li in range(len(rates)):
+      runs[li, fi] = models[li][fi].evaluate(held)[test_metric]
+  results = collections.OrderedDict()
+  run_mean, run_std = calculate_stats(runs)
+  for li, lr in enumerate(rates):
+    results[lr] = (float(run_mean[li]), float(run_std[li]))
+  results['all_runs'] = runs
+  results['models'] = models
+  results['history'] = [[h.history for h in row] for row in hist]
+  return results
+
+
 def jackknife_one_model(dataset, regularization_lambda, max_test_count=-1, test_name='telluride4',
                         trial_number=0, summary_file=None, test_file=None,
                         test_metric='pearson_correlation_first', experiment_parameters='',
