@@ -826,6 +826,36 @@ int td_dnn_train_many(td_handle* h, const float* x_dev, int64_t ldx, const int64
                       const float* lr_host, const float* rho_host, const float* eps_host,
                       const int64_t* shuffle_seed_host, double* stats_dev);
 
+/* ------------------------------------------------------------------ many classifiers in one fit, or one scoring
+ * td_mlpc_train for num_models classifiers of ONE architecture on the same recordings, with the structure of
+ * td_dnn_train_many: round t carries launch t of every model's own td_mlpc_train, models in the grid's second
+ * dimension, a model whose launches are done idles; no atomics, no wait between workgroups.  Shared: x, x2, y,
+ * the files, both views' c / pre / post, input_offset, d, the hidden widths, batch_rows, epochs and update.
+ * Per model m, as host arrays of num_models entries: rows_used_host[m][num_files], params_dev_host[m],
+ * state_dev_host[m] (DEVICE pointers; the state is 2 P floats, Adam's m then v), lr_host[m], beta1_host[m],
+ * beta2_host[m], eps_host[m] (doubles, each rounded once as td_mlpc_train rounds them), step0_host[m] (the
+ * updates the model has already had) and shuffle_seed_host[m] (< 0: in order).
+ * update != 0 trains: model m's parameters, m, v and six sums per step are bit for bit those of its own
+ * td_mlpc_train with its rows_used, settings and step0.  lr_t of update k of model m (t = step0 + k + 1) is
+ * computed on the host in double and rounded once, exactly as td_mlpc_train computes it per launch, for every
+ * update of the call; the table travels in the call's scratch and the update of step k reads entry k.
+ * update == 0 scores: epochs must be 1, rows are visited in order (the seeds are not read), no parameter is
+ * written, the optimizer's arrays and state_dev_host (or its entries) may be NULL, and two entries may name the
+ * same parameters.  Model m's six sums per step are those of td_mlpc_train(..., update = 0) on its rows_used:
+ * what brain_model.evaluate_many uses, rows_used zero everywhere but on the files scored.
+ * stats_dev: [num_models][epochs][max_steps][6] float64, as td_dnn_train_many.
+ * Checks, copies and the commit as td_dnn_train_many; at most TD_DNN_MANY_MAX_MODELS models a call.  A model's
+ * scratch is that of td_dnn_train_many with the doubled state (8 B a parameter) and its lr_t table (4 B per
+ * update of the call). */
+int td_clf_train_many(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
+                      const int64_t* file_offsets_host, int num_files, int c, int pre, int post, int c2, int pre2,
+                      int post2, int input_offset, const float* y_dev, int64_t ldy, int d, const int* hidden_host,
+                      int num_hidden, int batch_rows, int epochs, int update, int num_models,
+                      const int64_t* rows_used_host, float* const* params_dev_host, float* const* state_dev_host,
+                      const double* lr_host, const double* beta1_host, const double* beta2_host,
+                      const double* eps_host, const int64_t* step0_host, const int64_t* shuffle_seed_host,
+                      double* stats_dev);
+
 #ifdef __cplusplus
 }
 #endif

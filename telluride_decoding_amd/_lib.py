@@ -54,6 +54,8 @@ _FORWARD = [_i, _i] + _NETWORK + [_vp, _vp, _i64]       # input_offset, d, ..., 
 _pf = _c.POINTER(_f)
 # per model, host arrays: rows_used, params_dev / state_dev pointers, lr, rho, eps, shuffle_seed
 _MANY = [_pi64, _c.POINTER(_vp), _c.POINTER(_vp), _pf, _pf, _pf, _pi64]
+# ... the classifier's: rows_used, params_dev / state_dev pointers, lr, beta1, beta2, eps, step0, shuffle_seed
+_MANY_ADAM = [_pi64, _c.POINTER(_vp), _c.POINTER(_vp), _pd, _pd, _pd, _pd, _pi64, _pi64]
 
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -163,6 +165,8 @@ SIGNATURES = {
     'td_mlpc_forward': _MLPC + _FORWARD,
     # (the shared arguments of td_mlp_train_loss, then epochs, loss, num_models, the per-model arrays, stats_dev)
     'td_dnn_train_many': _MLP + [_i] + _TARGETS + _NETWORK + [_i, _i, _i, _i] + _MANY + [_vp],
+    # (the shared arguments of td_mlpc_train, then epochs, update, num_models, the per-model arrays, stats_dev)
+    'td_clf_train_many': _MLPC + [_i] + _TARGETS + _NETWORK + [_i, _i, _i, _i] + _MANY_ADAM + [_vp],
 }
 _RESTYPE = {'td_last_error': _c.c_char_p}
 

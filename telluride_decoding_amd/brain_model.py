@@ -739,36 +739,40 @@ def fold_rows_used(dataset, held_out=None):
 
 
 def fit_many(models, dataset, *, held_out=None, epochs=1, shuffle_seeds=None):
-  """Trains several BrainModelDNNs on one dataset at once (td_dnn_train_many): every launch of the
-  fit carries all the models, which a single fit cannot do for the GPU (a step is three launches of a few dozen
-  workgroups).  `models`: compiled BrainModelDNNs of identical widths and the same compiled loss, each with its own
-  weights, RMSprop settings and state; state persists as fit keeps it.  held_out[m]: the file indices model m does
-  not train on (None or empty: all files) -- its stream is fold_rows_used(dataset, held_out[m]).  shuffle_seeds: None,
-  one seed for every model, or one per model (None: in order), as fit's shuffle_seed.
+  """Trains several models of one family on one dataset at once (td_dnn_train_many, DESIGN section 18;
+  td_clf_train_many, section 19): every launch of the fit carries all the models, which a single fit cannot do for
+  the GPU (a step is three launches of a few dozen workgroups).  `models`: all compiled BrainModelDNNs of identical
+  widths and the same compiled loss, or all compiled BrainModelClassifiers of identical widths; each has its own
+  weights, optimizer settings (RMSprop / Adam) and state, which persists as fit keeps it -- a classifier's `_updates`
+  advances by epochs x its steps.  held_out[m]: the file indices model m does not train on (None or empty: all
+  files) -- its stream is fold_rows_used(dataset, held_out[m]).  shuffle_seeds: None, one seed for every model, or
+  one per model (None: in order), as fit's shuffle_seed.
   Returns one History per model.  Model m ends bit for bit where
-  models[m].fit(Dataset(the files it trains on, ...), epochs=epochs, shuffle_seed=...) would."""
+  models[m].fit(Dataset(the files it trains on, ...), epochs=epochs, shuffle_seed=...) would.  (More models than one
+  device call takes go through several; if a later one fails, the models of the earlier ones have trained.)"""
   models = list(models)
   n = len(models)
   if n == 0:
     return []
   for i, m in enumerate(models):
-    if not isinstance(m, BrainModelDNN):
-      raise TypeError('fit_many trains BrainModelDNN models, not %s (model %d)' % (type(m), i))
+    if not isinstance(m, (BrainModelDNN, BrainModelClassifier)):
+      raise TypeError('fit_many trains BrainModelDNN or BrainModelClassifier models, not %s (model %d)' % (type(m), i))
     if m.optimizer is None:
       raise RuntimeError('You must compile your model before training/testing (model %d).' % i)
   first = models[0]
+  classifier = isinstance(first, BrainModelClassifier)
   for i, m in enumerate(models):
-    if m._widths != first._widths or m.loss != first.loss:
+    if isinstance(m, BrainModelClassifier) != classifier:
+      raise ValueError('fit_many: model %d is a %s, model 0 a %s: one model family per call' % (
+          i, type(m).__name__, type(first).__name__))
+    if classifier and m.optimizer.amsgrad:
+      raise NotImplementedError('Adam with amsgrad=True is not supported (model %d)' % i)
+  loss_of = lambda m: getattr(m, 'loss', 'binary_crossentropy')
+  for i, m in enumerate(models):
+    if m._widths != first._widths or loss_of(m) != loss_of(first):
       raise ValueError('fit_many: model %d has widths %s and loss %r, model 0 %s and %r: one architecture and one '
-                       'loss per call' % (i, m._widths, m.loss, first._widths, first.loss))
-  if not _is_dataset(dataset):
-    raise TypeError('fit_many needs a brain_data.Dataset, not %s.' % type(dataset))
-  if dataset.mixup_batch:
-    raise ValueError('fit_many needs streams that are subsets of the files: a mixup_batch dataset shuffles input_2 '
-                     'and the output inside the minibatches of the full stream')
-  if dataset.max_batches is not None:
-    raise ValueError('fit_many: the dataset is limited to %r minibatches (take()); a fold\'s stream is cut from '
-                     'its own files' % (dataset.max_batches,))
+                       'loss per call' % (i, m._widths, loss_of(m), first._widths, loss_of(first)))
+  _check_shared_dataset('fit_many', dataset)
   first._check_limits(dataset)
   held = [None] * n if held_out is None else list(held_out)
   if len(held) != n:
@@ -790,19 +794,93 @@ def fit_many(models, dataset, *, held_out=None, epochs=1, shuffle_seeds=None):
           dataset.batch_size))
   epochs = int(epochs)
   if epochs <= 0:
-    return [History({key: [] for key in BrainModelDNN._HISTORY_KEYS}) for _ in models]
+    return [History({key: [] for key in first._HISTORY_KEYS}) for _ in models]
   h = device.default_handle()
-  x, _, y, offs = dataset.device_arrays(h)
+  x, x2, y, offs = dataset.device_arrays(h)
   params = [m._device_params(h) for m in models]
+  opts = [m.optimizer for m in models]
+  if classifier:
+    for m, p in zip(models, params):
+      if m._state is None:
+        m._state = h.zeros((2 * int(p.numel()),))
+    sums = device.clf_train_many(x, x2, y, offs, dataset.pre, dataset.post, dataset.pre2, dataset.post2,
+                                 first.num_hidden_list, params, [m._state for m in models], dataset.batch_size,
+                                 epochs, used, [o.learning_rate for o in opts], [o.beta_1 for o in opts],
+                                 [o.beta_2 for o in opts], [o.epsilon for o in opts], [m._updates for m in models],
+                                 input_offset=dataset.input_offset, shuffle_seeds=seeds, handle=h)
+    for m, u in zip(models, used):
+      m._updates += epochs * (sum(u) // dataset.batch_size)
+    return [History(classifier_history_from_sums(s.cpu().numpy(), dataset.batch_size, first._output_width))
+            for s in sums]
   for m, p in zip(models, params):
     if m._state is None:
       m._state = h.zeros((int(p.numel()),))
-  opts = [m.optimizer for m in models]
   sums = device.dnn_train_many(x, y, offs, dataset.pre, dataset.post, first.num_hidden_list, params,
                                [m._state for m in models], dataset.batch_size, epochs,
                                [o.learning_rate for o in opts], [o.rho for o in opts], [o.epsilon for o in opts],
                                used, input_offset=dataset.input_offset, shuffle_seeds=seeds, handle=h, loss=first.loss)
   return [History(history_from_sums(s.cpu().numpy(), dataset.batch_size, first._output_width)) for s in sums]
+
+
+def _check_shared_dataset(who, dataset):
+  """What fit_many and evaluate_many ask of the dataset their models share: a brain_data.Dataset whose streams are
+  subsets of its files."""
+  if not _is_dataset(dataset):
+    raise TypeError('%s needs a brain_data.Dataset, not %s.' % (who, type(dataset)))
+  if dataset.mixup_batch:
+    raise ValueError('%s needs streams that are subsets of the files: a mixup_batch dataset shuffles input_2 '
+                     'and the output inside the minibatches of the full stream' % who)
+  if dataset.max_batches is not None:
+    raise ValueError('%s: the dataset is limited to %r minibatches (take()); a fold\'s stream is cut from '
+                     'its own files' % (who, dataset.max_batches))
+
+
+def evaluate_many(models, dataset, *, files):
+  """Scores several BrainModelClassifiers of identical widths in one pass of the training kernels with the update
+  off (td_clf_train_many with update = 0): model m on the files `files[m]` (file indices; the
+  stream visits them in the dataset's order) of `dataset`.  Returns one {'loss', 'accuracy'} per model, each equal
+  to models[m].evaluate(Dataset(those files, the same batch / context / offset)).  A model whose files hold no full
+  minibatch gets NaN for both, as evaluate gives, and takes no part in the device call.  One model may be named
+  more than once; nothing is written to any of them."""
+  models = list(models)
+  n = len(models)
+  for i, m in enumerate(models):
+    if not isinstance(m, BrainModelClassifier):
+      raise TypeError('evaluate_many scores BrainModelClassifier models, not %s (model %d)' % (type(m), i))
+  for i, m in enumerate(models):
+    if m._widths != models[0]._widths:
+      raise ValueError('evaluate_many: model %d has widths %s, model 0 %s: one architecture per call' % (
+          i, m._widths, models[0]._widths))
+  _check_shared_dataset('evaluate_many', dataset)
+  files = list(files)
+  if len(files) != n:
+    raise ValueError('evaluate_many: %d models but %d files entries' % (n, len(files)))
+  if n == 0:
+    return []
+  models[0]._check_limits(dataset)
+  n_files = len(dataset.files)
+  used = []
+  for i, scored in enumerate(files):
+    scored = set(int(f) for f in scored)
+    if any(f < 0 or f >= n_files for f in scored):
+      raise ValueError('evaluate_many: files[%d] must name files of the dataset (0..%d), not %s' % (
+          i, n_files - 1, sorted(scored)))
+    used.append(fold_rows_used(dataset, [f for f in range(n_files) if f not in scored]))
+  out = [{'loss': float('nan'), 'accuracy': float('nan')} for _ in models]
+  live = [i for i, u in enumerate(used) if sum(u) >= dataset.batch_size]
+  if not live:
+    return out
+  h = device.default_handle()
+  x, x2, y, offs = dataset.device_arrays(h)
+  first = models[0]
+  sums = device.clf_train_many(x, x2, y, offs, dataset.pre, dataset.post, dataset.pre2, dataset.post2,
+                               first.num_hidden_list, [models[i]._device_params(h) for i in live], None,
+                               dataset.batch_size, 1, [used[i] for i in live], update=False,
+                               input_offset=dataset.input_offset, handle=h)
+  for i, s in zip(live, sums):
+    hist = classifier_history_from_sums(s.cpu().numpy(), dataset.batch_size, first._output_width)
+    out[i] = {'loss': hist['loss'][0], 'accuracy': hist['accuracy'][0]}
+  return out
 
 
 class Adam(object):

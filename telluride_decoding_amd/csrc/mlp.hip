@@ -39,6 +39,8 @@
 // kernels' bodies are __device__ functions of (the arguments, the launch's step); a single fit's kernels pass
 // their own kernel argument, the batched ones (mlp_*_many_kernel) the model's entry of a device table and a step
 // derived from the launch index.  Models share nothing but x and y, so each comes out as its own single fit.
+// td_clf_train_many is the same for classifiers: Adam with every model's own settings, lr_t of every update from a
+// host-computed table (ManyModel::lr_t), or, with the update off, the scoring of many models in one chain.
 #include "td_common.h"
 
 #include <cmath>
@@ -180,6 +182,7 @@ struct SlabStep {
   const RowEntry* cur_rows;
   int prev_epoch, prev_step;   // -1: no update
   int cur_epoch, cur_step;     // -1: no forward
+  float lr;                    // the update's learning rate: RMSprop's lr; Adam's lr_t of this very update
 };
 
 struct SlabArgs {
@@ -194,7 +197,7 @@ struct SlabArgs {
   const double* lstat;    // Pearson: the previous step's loss L (written by head<2>)
   SlabStep at;
   int ks, nslices, n_head;
-  float lr, rho, eps;          // RMSprop; Adam: lr = this update's lr_t, rho = beta_1
+  float rho, eps;              // RMSprop; Adam: rho = beta_1 (the learning rate is the step's: SlabStep::lr)
   float beta2, omb1, omb2;     // Adam: beta_2, 1 - beta_1, 1 - beta_2 (each rounded once from double)
   int update;                  // kUpdRmsprop / kUpdAdam (state = m [P], then v [P]) / kUpdNone (the sums only)
 };
@@ -216,10 +219,13 @@ __device__ __forceinline__ float mlp_rmsprop(float* p, float* v, float grad, flo
 }
 
 // Keras Adam without amsgrad: m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2, w -= lr_t m / (sqrt(v) + eps)
-__device__ __forceinline__ float mlp_adam(float* p, float* m, float* v, float grad, const SlabArgs& a) {
-  const float mn = a.rho * *m + a.omb1 * grad;
-  const float vn = a.beta2 * *v + a.omb2 * (grad * grad);
-  const float pn = *p - a.lr * mn / (sqrtf(vn) + a.eps);
+__device__ __forceinline__ float mlp_adam(float* p, float* m, float* v, float grad, const SlabArgs& a, float lr_t) {
+  // (the roundings spelled out, as in mlp_rmsprop: b1 m and b2 v rounded, the other product of each sum fused,
+  // lr_t m rounded before the division and the subtraction -- the form the compiler's contraction had given the
+  // single-model kernels, so that a single fit keeps its bits and the batched kernels compute the same)
+  const float mn = fmaf(a.omb1, grad, a.rho * *m);
+  const float vn = fmaf(a.omb2, grad * grad, a.beta2 * *v);
+  const float pn = *p - (lr_t * mn) / (sqrtf(vn) + a.eps);
   *m = mn;
   *v = vn;
   *p = pn;
@@ -227,9 +233,10 @@ __device__ __forceinline__ float mlp_adam(float* p, float* m, float* v, float gr
 }
 
 // the update rule of the call on parameter `at`; returns the new value
-__device__ __forceinline__ float mlp_apply(const SlabArgs& a, long long at, float grad) {
-  if (a.update == kUpdAdam) return mlp_adam(&a.params[at], &a.state[at], &a.state[a.g.n_params + at], grad, a);
-  return mlp_rmsprop(&a.params[at], &a.state[at], grad, a.lr, a.rho, a.eps);
+__device__ __forceinline__ float mlp_apply(const SlabArgs& a, const SlabStep& st, long long at, float grad) {
+  if (a.update == kUpdAdam)
+    return mlp_adam(&a.params[at], &a.state[at], &a.state[a.g.n_params + at], grad, a, st.lr);
+  return mlp_rmsprop(&a.params[at], &a.state[at], grad, st.lr, a.rho, a.eps);
 }
 
 constexpr int kW1Groups = kSlabMaxKs * kMlpMaxWidth / 4 / kSlabThreads;   // (row, 4 columns) groups per thread
@@ -292,7 +299,7 @@ __device__ __forceinline__ void mlp_slab_body(const SlabArgs& a, const SlabStep&
       float s = 0.f;
       for (int hw = 0; hw < a.n_head; ++hw) s += a.gpart[(long long)hw * g.n_small + p];
       if (a.grad_out) a.grad_out[g.small0 + p] = s;
-      else mlp_apply(a, g.small0 + p, s);
+      else mlp_apply(a, st, g.small0 + p, s);
     }
     if (wg == a.nslices && tid < 6 && st.stats_out) {
       double s = 0.0;
@@ -330,7 +337,7 @@ __device__ __forceinline__ void mlp_slab_body(const SlabArgs& a, const SlabStep&
             if (a.grad_out) {
               a.grad_out[at] = acc[o][q];
             } else {
-              const float nw = mlp_apply(a, at, acc[o][q]);
+              const float nw = mlp_apply(a, st, at, acc[o][q]);
               if (fwd) ws[kk][j0 + q] = nw;
             }
           }
@@ -637,7 +644,7 @@ __global__ __launch_bounds__(kHeadRows) void mlp_head_kernel(HeadArgs a) {
   mlp_head_body<PP>(a, a.at);
 }
 
-// ---- many models in one launch (td_dnn_train_many): blockIdx.y = model --------------------------------------
+// ---- many models in one launch (td_dnn_train_many, td_clf_train_many): blockIdx.y = model --------------------------------------
 // A model's entry of the device table: the arguments its own launches of a single fit would carry (their `at`
 // is not read), and what derives `at` from the launch index.  Models share x, y and the architecture; each has
 // its own stream (stream_offs, n_rows), parameters, state, scratch, optimizer settings and row tables.
@@ -645,6 +652,8 @@ struct ManyModel {
   SlabArgs slab;
   HeadArgs head;
   RowEntry* rows[2];      // row tables of even / odd epochs (in order: rows[0] serves every epoch)
+  const float* lr_t;      // Adam: [total] the learning rate of every update of the call, from the host (else null)
+  float lr;               // RMSprop: the learning rate of every update
   double* stats;          // [epochs][max_steps][nstat]
   int steps, total;       // steps per epoch of this model; epochs x steps
   int max_steps, nstat;
@@ -659,6 +668,7 @@ __device__ __forceinline__ bool mlp_many_step(const ManyModel& m, int t, SlabSte
   const int shuffle = m.slab.g.shuffle;
   st->cur_epoch = st->cur_step = st->prev_epoch = st->prev_step = -1;
   st->stats_out = nullptr;
+  st->lr = 0.f;
   st->prev_rows = st->cur_rows = m.rows[0];
   if (cur) {
     st->cur_epoch = t / m.steps;
@@ -670,6 +680,7 @@ __device__ __forceinline__ bool mlp_many_step(const ManyModel& m, int t, SlabSte
     st->prev_step = t - 1 - st->prev_epoch * m.steps;
     if (shuffle) st->prev_rows = m.rows[st->prev_epoch & 1];
     st->stats_out = m.stats + (long long)m.nstat * ((long long)st->prev_epoch * m.max_steps + st->prev_step);
+    st->lr = m.lr_t ? m.lr_t[t - 1] : m.lr;
   }
   return true;
 }
@@ -960,10 +971,16 @@ struct MlpOpt {
   int64_t step0;
 };
 
+// Adam's lr_t of update `index` of a call (t = step0 + index + 1): double arithmetic, rounded once.  The one
+// expression both mlp_train (per launch) and mlp_train_many (its per-model table) use.
+float mlp_adam_lr(const MlpOpt& opt, int64_t index) {
+  const double t = (double)(opt.step0 + index + 1);
+  return (float)(opt.lr * std::sqrt(1.0 - std::pow(opt.b2, t)) / (1.0 - std::pow(opt.b1, t)));
+}
+
 void mlp_set_update(SlabArgs* sa, const MlpOpt& opt, int64_t index) {
   if (opt.update != kUpdAdam) return;
-  const double t = (double)(opt.step0 + index + 1);
-  sa->lr = (float)(opt.lr * std::sqrt(1.0 - std::pow(opt.b2, t)) / (1.0 - std::pow(opt.b1, t)));
+  sa->at.lr = mlp_adam_lr(opt, index);
 }
 
 // Checks the call, then queues every launch of it.
@@ -1005,7 +1022,7 @@ int mlp_train(td_handle* h, const char* fn, const MlpCall& a, int epochs, float*
   HeadArgs ha;
   mlp_fill(plan, w, &sa, &ha);
   sa.update = opt.update;
-  sa.lr = (float)opt.lr; sa.rho = (float)opt.b1; sa.eps = (float)opt.eps;
+  sa.at.lr = (float)opt.lr; sa.rho = (float)opt.b1; sa.eps = (float)opt.eps;
   sa.beta2 = (float)opt.b2; sa.omb1 = (float)(1.0 - opt.b1); sa.omb2 = (float)(1.0 - opt.b2);
   ha.backward = update;
   const int nstat = plan.g.pearson ? 7 : 6;
@@ -1105,14 +1122,14 @@ int mlp_forward(td_handle* h, const char* fn, const MlpCall& a, const float* par
   return TD_OK;
 }
 
-// ---- td_dnn_train_many ------------------------------------------------------------------------------------
+// ---- td_dnn_train_many, td_clf_train_many ---------------------------------------------------------------------
 struct ManyCall {
   int num_models;
   const int64_t* rows_used;        // host [num_models][num_files]
   float* const* params;            // host [num_models] device pointers
-  float* const* state;
-  const float *lr, *rho, *eps;     // host [num_models]
-  const int64_t* shuffle_seed;     // host [num_models], < 0: in order
+  float* const* state;             // (score only: may be null, as may its entries)
+  const MlpOpt* opt;               // host [num_models]: one update rule for all, every model its own settings
+  const int64_t* shuffle_seed;     // host [num_models], < 0: in order (score only: not read)
 };
 
 // a call's scratch, sized on a first pass (base null) and handed out on a second
@@ -1158,8 +1175,9 @@ int mlp_launch_head_many(td_handle* h, const MlpPlan& plan, int num_models, cons
   return TD_OK;
 }
 
-// mlp_train for num_models regressors at once: every check of every model first, then working copies, the rounds
-// of launches (round t = launch t of every model's own fit, models in blockIdx.y) and the commit.
+// mlp_train for num_models models at once (regressors on RMSprop, classifiers on Adam or scored only, kUpdNone):
+// every check of every model first, then working copies, the rounds of launches (round t = launch t of every
+// model's own fit, models in blockIdx.y) and the commit.
 int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, const ManyCall& mc, double* stats_dev) {
   MlpPlan plan;
   TD_TRY(mlp_check_and_plan(h, fn, a, &plan));
@@ -1167,19 +1185,27 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
   TD_REQUIRE(h, batch_rows <= kMlpMaxB, "%s: batch of %d rows exceeds %d", fn, batch_rows, kMlpMaxB);
   TD_REQUIRE(h, nm >= 1 && nm <= TD_DNN_MANY_MAX_MODELS, "%s: %d models (1 .. %d a call)", fn, nm,
              TD_DNN_MANY_MAX_MODELS);
-  TD_REQUIRE(h, a.y && a.ldy >= a.d && mc.rows_used && mc.params && mc.state && mc.lr && mc.rho && mc.eps &&
-                    mc.shuffle_seed, "%s: NULL argument or ldy too small", fn);
+  const int rule = mc.opt ? mc.opt[0].update : kUpdNone;
+  const bool update = rule != kUpdNone, adam = rule == kUpdAdam;
+  TD_REQUIRE(h, a.y && a.ldy >= a.d && mc.rows_used && mc.params && (mc.state || !update) && mc.opt &&
+                    (mc.shuffle_seed || !update), "%s: NULL argument or ldy too small", fn);
   TD_REQUIRE(h, epochs >= 0, "%s: negative epoch count", fn);
+  TD_REQUIRE(h, update || epochs == 1, "%s: scoring is one pass (epochs = 1), not %d", fn, epochs);
   std::vector<std::vector<long long>> so(nm);
   int max_steps = 0;
   long long max_total = 0;
   for (int m = 0; m < nm; ++m) {
-    TD_REQUIRE(h, mc.params[m] && mc.state[m], "%s: model %d: NULL parameters or state", fn, m);
-    for (int j = 0; j < m; ++j)
+    const MlpOpt& opt = mc.opt[m];
+    TD_REQUIRE(h, mc.params[m] && (!update || mc.state[m]), "%s: model %d: NULL parameters or state", fn, m);
+    // (scoring writes to no model, so two entries may score one model on different files)
+    for (int j = 0; update && j < m; ++j)
       TD_REQUIRE(h, mc.params[j] != mc.params[m] && mc.state[j] != mc.state[m],
                  "%s: models %d and %d share their parameters or state", fn, j, m);
-    TD_REQUIRE(h, std::isfinite(mc.lr[m]) && std::isfinite(mc.rho[m]) && std::isfinite(mc.eps[m]),
+    TD_REQUIRE(h, std::isfinite(opt.lr) && std::isfinite(opt.b1) && std::isfinite(opt.b2) && std::isfinite(opt.eps),
                "%s: model %d: non-finite optimizer setting", fn, m);
+    if (adam)
+      TD_REQUIRE(h, opt.b1 >= 0.0 && opt.b1 < 1.0 && opt.b2 >= 0.0 && opt.b2 < 1.0 && opt.step0 >= 0,
+                 "%s: model %d: Adam needs 0 <= beta < 1 and step0 >= 0", fn, m);
     MlpCall am = a;
     am.rows_used = mc.rows_used + (size_t)m * nf;
     TD_TRY(mlp_stream_offsets(h, fn, am, &so[m]));
@@ -1197,8 +1223,14 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
   g.y = a.y; g.ldy = a.ldy;
   const int nstat = g.pearson ? 7 : 6;
   const size_t n_off = nf + 1;
+  const auto seed_of = [&](int m) -> int64_t { return update ? mc.shuffle_seed[m] : -1; };
+  // Adam: lr_t of every update of the call, model after model (model m's at lr_at[m])
+  std::vector<size_t> lr_at(nm + 1, 0);
+  for (int m = 0; adam && m < nm; ++m)
+    lr_at[m + 1] = lr_at[m] + (size_t)(epochs * td_ceil_div(so[m][nf], batch_rows));
   // the scratch: the table, the offsets, then every model's own block
   std::vector<MlpWork> work(nm);
+  float* lr_dev = nullptr;
   long long* so_dev = nullptr;
   ManyModel* tab_dev = nullptr;
   MlpBump bump = {nullptr, 0};
@@ -1210,16 +1242,17 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
     }
     tab_dev = bump.take<ManyModel>(nm);
     so_dev = bump.take<long long>((size_t)(nm + 1) * n_off);     // the file offsets, then every model's stream
+    lr_dev = bump.take<float>(lr_at[nm]);
     for (int m = 0; m < nm; ++m) {
       MlpWork& w = work[m];
       const long long n_rows = so[m][nf];
       w.rows[0] = bump.take<RowEntry>(n_rows);
-      w.rows[1] = mc.shuffle_seed[m] >= 0 ? bump.take<RowEntry>(n_rows) : w.rows[0];
+      w.rows[1] = seed_of(m) >= 0 ? bump.take<RowEntry>(n_rows) : w.rows[0];
       w.spart = bump.take<double>((size_t)plan.n_head * 6);
       w.mpart = bump.take<double>((size_t)plan.n_head * 5 * kMlpMaxD);
       w.lstat = bump.take<double>(1);
       w.params = bump.take<float>(g.n_params);
-      w.state = bump.take<float>(g.n_params);
+      w.state = bump.take<float>(adam ? 2 * (size_t)g.n_params : g.n_params);   // Adam: m, then v
       w.zpart = bump.take<float>((size_t)plan.nslices * g.w[1] * g.batch);
       w.dz1 = bump.take<float>((size_t)g.w[1] * g.batch);
       w.z1 = bump.take<float>((size_t)g.w[1] * g.batch);
@@ -1238,15 +1271,19 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
     MlpPlan pm = plan;
     pm.g.file_offs = w.file_offs; pm.g.stream_offs = w.stream_offs;
     pm.g.n_rows = so[m][nf];
-    pm.g.shuffle = mc.shuffle_seed[m] >= 0;
-    pm.g.seed_lo = (unsigned)((uint64_t)mc.shuffle_seed[m] & 0xffffffffu);
-    pm.g.seed_hi = (unsigned)((uint64_t)mc.shuffle_seed[m] >> 32);
+    pm.g.shuffle = seed_of(m) >= 0;
+    pm.g.seed_lo = (unsigned)((uint64_t)seed_of(m) & 0xffffffffu);
+    pm.g.seed_hi = (unsigned)((uint64_t)seed_of(m) >> 32);
     geom[m] = pm.g;
     ManyModel& t = tab[m];
     memset(&t, 0, sizeof(t));
     mlp_fill(pm, w, &t.slab, &t.head);
-    t.slab.update = kUpdRmsprop;
-    t.slab.lr = mc.lr[m]; t.slab.rho = mc.rho[m]; t.slab.eps = mc.eps[m];
+    const MlpOpt& opt = mc.opt[m];
+    t.slab.update = rule;
+    t.slab.rho = (float)opt.b1; t.slab.eps = (float)opt.eps;
+    t.slab.beta2 = (float)opt.b2; t.slab.omb1 = (float)(1.0 - opt.b1); t.slab.omb2 = (float)(1.0 - opt.b2);
+    t.head.backward = update;
+    t.lr = (float)opt.lr; t.lr_t = adam ? lr_dev + lr_at[m] : nullptr;
     t.rows[0] = w.rows[0]; t.rows[1] = w.rows[1];
     t.steps = (int)td_ceil_div(pm.g.n_rows, batch_rows);
     t.total = epochs * t.steps;
@@ -1255,6 +1292,14 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
   }
   TD_TRY(td_upload_async(h, so_host.data(), sizeof(long long) * so_host.size(), so_dev));
   TD_TRY(td_upload_async(h, tab.data(), sizeof(ManyModel) * nm, tab_dev));
+  if (adam) {
+    // lr_t of update k of model m, k = 0 .. total_m - 1: mlp_train's own expression on the host (the device's pow
+    // is not the host's), read by the update of step k
+    std::vector<float> lr_t(lr_at[nm]);
+    for (int m = 0; m < nm; ++m)
+      for (int k = 0; k < tab[m].total; ++k) lr_t[lr_at[m] + k] = mlp_adam_lr(mc.opt[m], k);
+    TD_TRY(td_upload_async(h, lr_t.data(), sizeof(float) * lr_t.size(), lr_dev));
+  }
   TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_many_kernel<0>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
   TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_many_kernel<1>),
@@ -1262,10 +1307,10 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
   TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_many_kernel<2>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
   // work on copies: the callers' parameters change only when every launch has been queued
-  const size_t pbytes = sizeof(float) * g.n_params;
+  const size_t pbytes = sizeof(float) * g.n_params, sbytes = adam ? 2 * pbytes : pbytes;
   for (int m = 0; m < nm; ++m) {
     TD_HIP(h, hipMemcpyAsync(work[m].params, mc.params[m], pbytes, hipMemcpyDeviceToDevice, h->stream));
-    TD_HIP(h, hipMemcpyAsync(work[m].state, mc.state[m], pbytes, hipMemcpyDeviceToDevice, h->stream));
+    if (update) TD_HIP(h, hipMemcpyAsync(work[m].state, mc.state[m], sbytes, hipMemcpyDeviceToDevice, h->stream));
     if (!geom[m].shuffle) TD_TRY(mlp_launch_rows(h, geom[m], 0, work[m].rows[0]));
   }
   for (long long t = 0; t <= max_total; ++t) {
@@ -1279,9 +1324,9 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
     TD_TRY(mlp_launch_slab_many(h, plan, nm, tab_dev, (int)t));
     if (t < max_total) TD_TRY(mlp_launch_head_many(h, plan, nm, tab_dev, (int)t));
   }
-  for (int m = 0; m < nm; ++m) {
+  for (int m = 0; update && m < nm; ++m) {
     TD_HIP(h, hipMemcpyAsync(mc.params[m], work[m].params, pbytes, hipMemcpyDeviceToDevice, h->stream));
-    TD_HIP(h, hipMemcpyAsync(mc.state[m], work[m].state, pbytes, hipMemcpyDeviceToDevice, h->stream));
+    TD_HIP(h, hipMemcpyAsync(mc.state[m], work[m].state, sbytes, hipMemcpyDeviceToDevice, h->stream));
   }
   return TD_OK;
 }
@@ -1377,7 +1422,37 @@ int td_dnn_train_many(td_handle* h, const float* x_dev, int64_t ldx, const int64
                       const int64_t* shuffle_seed_host, double* stats_dev) {
   const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, nullptr,
                      y_dev, ldy, d, hidden_host, num_hidden, batch_rows, loss, false};
-  const ManyCall mc = {num_models, rows_used_host, params_dev_host, state_dev_host, lr_host, rho_host, eps_host,
-                       shuffle_seed_host};
-  return mlp_train_many(h, "td_dnn_train_many", a, epochs, mc, stats_dev);
+  const char* fn = "td_dnn_train_many";
+  TD_REQUIRE(h, lr_host && rho_host && eps_host && num_models <= TD_DNN_MANY_MAX_MODELS,
+             "%s: NULL argument or more than %d models", fn, TD_DNN_MANY_MAX_MODELS);
+  std::vector<MlpOpt> opt;
+  for (int m = 0; m < num_models; ++m) opt.push_back({kUpdRmsprop, lr_host[m], rho_host[m], 0.0, eps_host[m], 0});
+  opt.resize(std::max(num_models, 1), {kUpdRmsprop, 0.0, 0.0, 0.0, 0.0, 0});
+  const ManyCall mc = {num_models, rows_used_host, params_dev_host, state_dev_host, opt.data(), shuffle_seed_host};
+  return mlp_train_many(h, fn, a, epochs, mc, stats_dev);
+}
+
+int td_clf_train_many(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_dev, int64_t ldx2,
+                      const int64_t* file_offsets_host, int num_files, int c, int pre, int post, int c2, int pre2,
+                      int post2, int input_offset, const float* y_dev, int64_t ldy, int d, const int* hidden_host,
+                      int num_hidden, int batch_rows, int epochs, int update, int num_models,
+                      const int64_t* rows_used_host, float* const* params_dev_host, float* const* state_dev_host,
+                      const double* lr_host, const double* beta1_host, const double* beta2_host,
+                      const double* eps_host, const int64_t* step0_host, const int64_t* shuffle_seed_host,
+                      double* stats_dev) {
+  const MlpCall a = {{x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host, num_files,
+                     input_offset, nullptr, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, true};
+  const char* fn = "td_clf_train_many";
+  TD_REQUIRE(h, num_models <= TD_DNN_MANY_MAX_MODELS, "%s: more than %d models", fn, TD_DNN_MANY_MAX_MODELS);
+  // score only: the optimizer's arrays are not read
+  const int rule = update ? kUpdAdam : kUpdNone;
+  TD_REQUIRE(h, !update || (lr_host && beta1_host && beta2_host && eps_host && step0_host), "%s: NULL argument", fn);
+  std::vector<MlpOpt> opt;
+  for (int m = 0; m < num_models; ++m) {
+    if (update) opt.push_back({rule, lr_host[m], beta1_host[m], beta2_host[m], eps_host[m], step0_host[m]});
+    else opt.push_back({rule, 0.0, 0.0, 0.0, 0.0, 0});
+  }
+  opt.resize(std::max(num_models, 1), {rule, 0.0, 0.0, 0.0, 0.0, 0});
+  const ManyCall mc = {num_models, rows_used_host, params_dev_host, state_dev_host, opt.data(), shuffle_seed_host};
+  return mlp_train_many(h, fn, a, epochs, mc, stats_dev);
 }

@@ -1112,3 +1112,46 @@ def dnn_train_many(x, y, file_offsets, pre, post, hidden, params, states, batch_
                                     used_p, par, sta, f32(lrs), f32(rhos), f32(epss), seed_p, _ptr(stats)))
     out += [stats[i, :, :steps[i]] for i in range(n)]
   return out
+
+
+def clf_train_many(x, x2, y, file_offsets, pre, post, pre2, post2, hidden, params, states, batch_rows, epochs,
+                   rows_used, lrs=None, beta1s=None, beta2s=None, epss=None, step0s=None, update=True,
+                   input_offset=0, shuffle_seeds=None, handle=None):
+  """mlpc_train for many classifiers of one architecture at once (td_clf_train_many): params[m] / states[m] are
+  model m's packed float32 parameters and Adam state [2 P] (device, updated in place), lrs / beta1s / beta2s / epss /
+  step0s / shuffle_seeds (None: in order) its settings, rows_used[m][f] the rows of file f in its stream.
+  update=False scores instead: one pass in order with nothing written; states and the settings may be None.
+  Returns one device float64 tensor per model, [epochs, its steps, 6] as mlpc_train returns it.  More than
+  DNN_MANY_MAX_MODELS models go through several calls."""
+  h = handle or default_handle()
+  _check_x2(x, x2)
+  n_models, epochs, batch_rows = len(params), int(epochs), int(batch_rows)
+  seeds = [None] * n_models if shuffle_seeds is None else list(shuffle_seeds)
+  used_all = np.ascontiguousarray(rows_used, dtype=np.int64).reshape(n_models, -1)
+  per_model = [seeds] + ([states, lrs, beta1s, beta2s, epss, step0s] if update else [])
+  if any(v is None or len(v) != n_models for v in per_model):
+    raise ValueError('clf_train_many: %d models, but a per-model argument of another length' % n_models)
+  head, net, keep = _mlp_views(h, x, x2, (pre, post, pre2, post2), file_offsets, input_offset, hidden)
+  if used_all.shape[1] != len(keep[0]) - 1:
+    raise ValueError('clf_train_many: rows_used has %d files, the recordings %d' % (used_all.shape[1], len(keep[0]) - 1))
+  out = []
+  cap = max(1, int(DNN_MANY_MAX_MODELS))
+  for m0 in range(0, n_models, cap):
+    m1 = min(m0 + cap, n_models)
+    n = m1 - m0
+    used, used_p = _lib.i64_array(used_all[m0:m1])
+    steps = [-(-int(u.sum()) // batch_rows) if batch_rows > 0 else 0 for u in used]
+    stats = h.zeros((n, max(epochs, 0), max(steps + [0]), 6), 'float64')
+    par = (ctypes.c_void_p * n)(*[p.data_ptr() for p in params[m0:m1]])
+    sta, settings, step0_p = None, [None] * 4, None          # scoring reads none of them
+    if update:
+      sta = (ctypes.c_void_p * n)(*[s.data_ptr() for s in states[m0:m1]])
+      settings = [(ctypes.c_double * n)(*[float(v) for v in values[m0:m1]])
+                  for values in (lrs, beta1s, beta2s, epss)]
+      step0, step0_p = _lib.i64_array([int(v) for v in step0s[m0:m1]])
+    seed, seed_p = _lib.i64_array([-1 if s is None else int(s) for s in seeds[m0:m1]])
+    h.check(h.lib.td_clf_train_many(*head, _ptr(y), y.stride(0), int(y.shape[1]), *net, batch_rows, epochs,
+                                    1 if update else 0, n, used_p, par, sta, *settings, step0_p,
+                                    seed_p, _ptr(stats)))
+    out += [stats[i, :, :steps[i]] for i in range(n)]
+  return out

@@ -605,6 +605,89 @@ def jackknife_dnn(dataset, num_hidden_list=None, *, learning_rates=(1e-3,), epoc
   return results
 
 
+# The route jackknife_classifier takes without _route, as DNN_ROUTE
+CLASSIFIER_ROUTE = 'batched'
+CLASSIFIER_METRICS = ('loss', 'accuracy')
+
+
+def jackknife_classifier(dataset, num_hidden_list=None, *, learning_rates=(1e-3,), epochs=1, seed=0,
+                         shuffle_seed=None, folds=None, test_metric='accuracy', _route=None):
+  """The leave-one-file-out jackknife of the match-mismatch classifier, as jackknife_dnn: one BrainModelClassifier of
+  `num_hidden_list` per (learning rate, held-out file), all trained together by one brain_model.fit_many and all
+  scored on their held-out files by one brain_model.evaluate_many.
+
+  Returns the sweeps' OrderedDict {learning rate: (mean, std)} of the held-out `test_metric` ('accuracy' or 'loss')
+  plus 'all_runs' [len(learning_rates), F], 'models' ([learning rate][fold], trained and usable) and 'history' (the
+  same shape, each a fit's History.history).  Every model starts from the weights of `seed` and is compiled with
+  Adam(learning_rate); `shuffle_seed` (None: in order) is shared.  A fold's training stream is
+  brain_model.fold_rows_used's; its held-out file is scored as BrainModelClassifier.evaluate scores a Dataset of that
+  file alone (a file without a full minibatch: NaN).
+  folds: as jackknife_over_regularizations.  _route: 'batched', or 'per_fold' = one fit and one evaluate after
+  another on Datasets of the fold's files (the same bits; what a sweep falls back to when a batched call's scratch
+  does not fit); None = CLASSIFIER_ROUTE.  LAST_SWEEP['classifier_route'] says which one ran."""
+  from telluride_decoding_amd import brain_model
+  if test_metric not in CLASSIFIER_METRICS:
+    raise ValueError('Could not find metric %s in results %s.' % (test_metric, list(CLASSIFIER_METRICS)))
+  route = CLASSIFIER_ROUTE if _route is None else _route
+  if route not in ('batched', 'per_fold'):
+    raise ValueError('_route must be \'batched\' or \'per_fold\', not %r' % (route,))
+  n_files = len(dataset.files)
+  if n_files < 2:
+    raise ValueError('Need at least two files for a jackknife test.')
+  fold_list = list(range(n_files)) if folds is None else sorted(set(int(f) for f in folds))
+  if not fold_list or fold_list[0] < 0 or fold_list[-1] >= n_files:
+    raise ValueError('folds must name files of the dataset (0..%d), not %s' % (n_files - 1, folds))
+  rates = [float(lr) for lr in learning_rates]
+  if not rates:
+    raise ValueError('Need at least one learning rate.')
+
+  def build():
+    grid = []
+    for lr in rates:
+      row = [brain_model.BrainModelClassifier(dataset, num_hidden_list, seed=seed) for _ in fold_list]
+      for m in row:
+        m.compile(optimizer=brain_model.Adam(learning_rate=lr))
+      grid.append(row)
+    return grid
+
+  def rows(flat):
+    return [flat[li * len(fold_list):(li + 1) * len(fold_list)] for li in range(len(rates))]
+
+  def per_fold(grid):
+    hist, scores = [[] for _ in rates], [[] for _ in rates]
+    for fi, f in enumerate(fold_list):
+      train = _subset(dataset, [g for g in range(n_files) if g != f])
+      held = _subset(dataset, [f])
+      for li in range(len(rates)):
+        hist[li].append(grid[li][fi].fit(train, epochs=epochs, shuffle_seed=shuffle_seed))
+        scores[li].append(grid[li][fi].evaluate(held))
+    return hist, scores
+
+  models = build()
+  if route == 'batched':
+    try:
+      flat = [m for row in models for m in row]
+      hist = rows(brain_model.fit_many(flat, dataset, held_out=[[f] for _ in rates for f in fold_list],
+                                       epochs=epochs, shuffle_seeds=shuffle_seed))
+      scores = rows(brain_model.evaluate_many(flat, dataset, files=[[f] for _ in rates for f in fold_list]))
+    except MemoryError:
+      # the scratch of a batched call did not fit; models of an earlier chunk may have trained: start again
+      route = 'per_fold'
+      models = build()
+  if route == 'per_fold':
+    hist, scores = per_fold(models)
+  LAST_SWEEP['classifier_route'] = route
+  runs = np.array([[score[test_metric] for score in row] for row in scores], np.float64)
+  results = collections.OrderedDict()
+  run_mean, run_std = calculate_stats(runs)
+  for li, lr in enumerate(rates):
+    results[lr] = (float(run_mean[li]), float(run_std[li]))
+  results['all_runs'] = runs
+  results['models'] = models
+  results['history'] = [[h.history for h in row] for row in hist]
+  return results
+
+
 def jackknife_one_model(dataset, regularization_lambda, max_test_count=-1, test_name='telluride4',
                         trial_number=0, summary_file=None, test_file=None,
                         test_metric='pearson_correlation_first', experiment_parameters='',
