@@ -563,6 +563,22 @@ int td_frame_scores(td_handle* h, const float* a_dev, int64_t lda, const float* 
 int td_window_means(td_handle* h, const double* v_dev, const int64_t* trial_offsets_host,
                     int num_trials, int width, int hop, double* out_dev);
 
+/* Decoder.train with a window (infer_decoder.py:330-400): the per-frame value of
+ * td_frame_scores' reduction 5, v = ((double)a - mean_a[c]) ((double)b - mean_b[c]) / power[c], its means
+ * m[w][c] over the non-overlapping windows [w width, (w + 1) width) of the whole stream (average_data,
+ * :748-783: the tail of rows % width frames is dropped, n_win = rows / width) and the moments of those
+ * means, [[M^T M, sum_w m], [sum_w m^T, n_win]] row-major float64 -- what the LDA's scatter matrices are
+ * made of -- in one pass over a and b and one finishing launch.
+ *   means_dev   [n_win, cols] float64, or NULL when only the moments are wanted
+ *   moments_dev [(cols + 1) (cols + 1)] float64; all zero when n_win == 0 (not an error)
+ * All arithmetic is float64 in a fixed order without atomics, and the grid follows from (rows, width)
+ * alone: two calls give the same bits.  TD_ERR_INVALID: cols outside [1, 32], width < 2, lda or
+ * ldb < cols. */
+int td_window_class_moments(td_handle* h, const float* a_dev, int64_t lda, const float* b_dev, int64_t ldb,
+                            int cols, int64_t rows, int width,
+                            const double* mean_a_host, const double* mean_b_host, const double* power_host,
+                            double* means_dev, double* moments_dev);
+
 /* ------------------------------------------------------------------ A8 / A9
  * Winner-take-all: out[i] = s1[i] > s2[i] (strict; ties -> speaker 2)
  * (attention_decoder.AttentionDecoder.attention, attention_decoder.py:128-134). */

@@ -139,6 +139,7 @@ SIGNATURES = {
     'td_frame_scores': [_vp, _vp, _i64, _vp, _i64, _i, _i64, _i, _pd, _pd, _pd, _pd, _d,
                         _d, _vp],
     'td_window_means': [_vp, _vp, _pi64, _i, _i, _i, _vp],
+    'td_window_class_moments': [_vp, _vp, _i64, _vp, _i64, _i, _i64, _i, _pd, _pd, _pd, _vp, _vp],
     'td_decide_wta': [_vp, _vp, _vp, _i64, _vp],
     'td_decide_step': [_vp, _vp, _vp, _pi64, _i, _vp, _pd],
     'td_decode_ssd': [_vp, _vp, _vp, _pi64, _i, _pd, _pd, _vp],

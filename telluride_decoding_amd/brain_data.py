@@ -17,6 +17,9 @@ Numerical contract reproduced here (reference brain_data.py):
   * minibatches are cut from the concatenated stream with drop_remainder=True
     (:369-370), so only the tail of the last file is lost.
 """
+import os
+import re
+
 import numpy as np
 
 
@@ -318,12 +321,14 @@ class Dataset(object):
 
 class BrainData(object):
   """Describes an experiment's data (reference brain_data.BrainData.__init__,
-  brain_data.py:99-199); only the in-memory variant is provided."""
+  brain_data.py:99-199): the fields, the contexts and the train / validate / test file patterns."""
 
   def __init__(self, in_fields, out_field, frame_rate, pre_context=0, post_context=0,
                in2_fields=None, in2_pre_context=0, in2_post_context=0, input_offset=0,
                attended_field=None, initial_batch_size=1000000, final_batch_size=1000,
-               repeat_count=1, shuffle_buffer_size=0, **unused_file_args):
+               repeat_count=1, shuffle_buffer_size=0, data_dir=None, data_pattern='',
+               train_file_pattern='', validate_file_pattern='', test_file_pattern='',
+               **unused_file_args):
     if not in_fields:
       raise ValueError('Must specify at least one input field.')
     if not out_field:
@@ -346,9 +351,64 @@ class BrainData(object):
     self.final_batch_size = final_batch_size
     self.repeat_count = repeat_count
     self.shuffle_buffer_size = shuffle_buffer_size   # closed-form fits ignore order
+    self.data_dir = data_dir
+    self.data_pattern = data_pattern
+    self.train_file_pattern = train_file_pattern
+    self.validate_file_pattern = validate_file_pattern
+    self.test_file_pattern = test_file_pattern
+    self._cached_file_names = []     # filled on the first all_files()
 
   def create_dataset(self, mode='train', temporal_context=True, mixup_batch=False):
     raise NotImplementedError
+
+  # -- files of an experiment (reference brain_data.py:201-323) -------------------
+  def _get_data_file_names(self):
+    """Fills self._cached_file_names; nothing for the classes that hold their data in memory."""
+    self._cached_file_names = []
+
+  def all_files(self, max_count=0):
+    """The files this object can draw on (found once, then cached); at most `max_count` of them when
+    that is positive.  The list is sorted, where the reference shuffles whatever order the
+    directory walk gave: a run here is reproducible."""
+    if not self._cached_file_names:
+      self._get_data_file_names()
+    if max_count > 0 and len(self._cached_file_names) > max_count:
+      return self._cached_file_names[:max_count]
+    return self._cached_file_names
+
+  def set_file_patterns(self, train, validate, test):
+    self.train_file_pattern = train
+    self.validate_file_pattern = validate
+    self.test_file_pattern = test
+
+  def filter_file_names(self, mode):
+    """The files of one phase of an experiment: those whose path matches (re.search) the phase's
+    pattern.  'program_test' means 'test'.  A train pattern of 'allbut' takes every file that matches
+    neither the test nor the validate pattern (both must then be given); 'allbut_N' keeps the first N
+    of those."""
+    if mode == 'program_test':
+      mode = 'test'
+    if mode not in ('test', 'validate', 'train'):
+      raise ValueError('mode must be one of test, validate or train')
+    names = self.all_files()
+    if not isinstance(names, list):
+      raise TypeError('Filename_list is a %s, not a list.' % type(names))
+    train_pattern = self.train_file_pattern or ''
+    if mode == 'train' and train_pattern.startswith('allbut'):
+      if not (self.test_file_pattern and self.validate_file_pattern):
+        raise ValueError('Both test and validate must be specified if using allbut pattern')
+      held_out = (re.compile(self.test_file_pattern), re.compile(self.validate_file_pattern))
+      names = [f for f in names if not any(p.search(f) for p in held_out)]
+      if train_pattern.startswith('allbut_'):
+        count = train_pattern.replace('allbut_', '', 1)
+        if not count.isdigit():
+          raise ValueError('allbut_ spec must be an integer, not %s.' % count)
+        names = names[:int(count)]
+      return names
+    pattern = {'test': self.test_file_pattern, 'validate': self.validate_file_pattern,
+               'train': train_pattern}[mode]
+    pattern = re.compile(pattern or '')
+    return [f for f in names if pattern.search(f)]
 
 
 class TestBrainData(BrainData):
@@ -409,3 +469,99 @@ class TestBrainData(BrainData):
                    self.in1_pre_context if ctx else 0, self.in1_post_context if ctx else 0,
                    self.in2_pre_context if ctx else 0, self.in2_post_context if ctx else 0,
                    self.input_offset if ctx else 0, mixup_batch=mixup_batch)
+
+
+class TFExampleData(BrainData):
+  """An experiment whose recordings are TFRecord files of tf.train.Example frames under `data_dir`
+  (reference brain_data.TFExampleData, brain_data.py:645-731), read by the dependency-free parser of
+  tfrecord.py.  `features` is {name: (width, dtype)} of the first file's first record."""
+
+  def __init__(self, *args, **kwargs):
+    super(TFExampleData, self).__init__(*args, **kwargs)
+    self.all_files()             # find the files and the feature shapes now: a bad data_dir fails here
+
+  def _get_data_file_names(self):
+    if not self.data_dir:
+      raise ValueError('Missing data_dir in TFExampleData initialization. '
+                       'Must specify the source of the data (FLAGS.tfrecords).')
+    if not isinstance(self.data_dir, str):
+      raise TypeError('data_dir must be a string, not a %s (**%s**)' %
+                      (type(self.data_dir), self.data_dir))
+    from telluride_decoding_amd import tfrecord
+    pattern = self.data_pattern or ''
+    names = []
+    for path, _, files in os.walk(self.data_dir):
+      names += [os.path.join(path, f) for f in files
+                if f.endswith('.tfrecords') and '-bad-' not in f and pattern in f]
+    self._cached_file_names = sorted(names)
+    if not self._cached_file_names:
+      raise ValueError('Should not have an empty list of data files from %s.' % self.data_dir)
+    self.features = tfrecord.discover_feature_shapes(self._cached_file_names[0])
+
+  def input_fields_width(self, input_number=1):
+    """Width of input 1 or 2 with its temporal context (reference :505-541)."""
+    if input_number not in (1, 2):
+      raise ValueError('Only 1st or 2nd input is supported here.')
+    fields = self.in1_fields if input_number == 1 else self.in2_fields
+    if isinstance(fields, str) and fields:
+      fields = [fields]
+    widths = [1]
+    if fields:
+      for k in fields:
+        if k not in self.features:
+          raise TypeError('Can\'t find **%s** in valid features: %s' %
+                          (k, [','.join(list(self.features.keys()))]))
+      widths = [self.features[k][0] for k in fields]
+    if input_number == 1:
+      return sum(widths) * (self.in1_pre_context + 1 + self.in1_post_context)
+    return sum(widths) * (self.in2_pre_context + 1 + self.in2_post_context)
+
+  def output_field_width(self):
+    if self.out_field not in self.features:
+      raise ValueError('Could not find output_field **%s** in %s' %
+                       (self.out_field, self.features.keys()))
+    return self.features[self.out_field][0]
+
+  def create_dataset(self, mode='train', temporal_context=True, mixup_batch=False):
+    """The Dataset of one phase: the files filter_file_names(mode) picks, one recording per file
+    (context never crosses files), in minibatches of final_batch_size."""
+    from telluride_decoding_amd import tfrecord
+    names = self.filter_file_names(mode)
+    if not names:
+      raise ValueError('No files to process in mode %s from directory %s: %s' %
+                       (mode, self.data_dir, self.all_files()))
+    ctx = temporal_context
+    ds = tfrecord.dataset_from_files(
+        names, self.in1_fields, self.out_field, in2_fields=self.in2_fields or None,
+        attended_field=self.attended_field or None, batch_size=self.final_batch_size,
+        pre_context=self.in1_pre_context if ctx else 0, post_context=self.in1_post_context if ctx else 0,
+        in2_pre_context=self.in2_pre_context if ctx else 0,
+        in2_post_context=self.in2_post_context if ctx else 0,
+        input_offset=self.input_offset if ctx else 0)
+    ds.mixup_batch = bool(mixup_batch)
+    return ds
+
+
+def create_brain_dataset(data_type, in_fields, out_field, frame_rate, pre_context=0, post_context=0,
+                         in2_fields=None, in2_pre_context=0, in2_post_context=0, input_offset=0,
+                         attended_field=None, initial_batch_size=1000000, final_batch_size=1000,
+                         repeat_count=1, shuffle_buffer_size=1000, data_dir=None, data_pattern='',
+                         train_file_pattern=None, validate_file_pattern=None, test_file_pattern=None):
+  """Any of the BrainData classes by name (reference brain_data.py:959-1040): 'tfrecord', 'tfrecords' or
+  'tfexample' -> TFExampleData, 'test' -> TestBrainData."""
+  if not isinstance(data_type, str):
+    raise TypeError('create_brain_dataset type must be a string.')
+  if frame_rate <= 0:
+    raise ValueError('frame_rate must be greater than 0.')
+  kwargs = dict(pre_context=pre_context, post_context=post_context, in2_fields=in2_fields,
+                in2_pre_context=in2_pre_context, in2_post_context=in2_post_context,
+                input_offset=input_offset, initial_batch_size=initial_batch_size,
+                final_batch_size=final_batch_size, repeat_count=repeat_count,
+                shuffle_buffer_size=shuffle_buffer_size, data_dir=data_dir, data_pattern=data_pattern,
+                train_file_pattern=train_file_pattern, validate_file_pattern=validate_file_pattern,
+                test_file_pattern=test_file_pattern)
+  if data_type in ('tfrecord', 'tfrecords', 'tfexample'):
+    return TFExampleData(in_fields, out_field, frame_rate, attended_field=attended_field, **kwargs)
+  if data_type == 'test':
+    return TestBrainData(in_fields, out_field, frame_rate, **kwargs)
+  raise TypeError('create_brain_dataset unknown data type %s' % data_type)

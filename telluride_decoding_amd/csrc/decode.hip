@@ -1031,6 +1031,93 @@ __global__ void frame_scores_kernel(const float* __restrict__ a, long long lda,
   }
 }
 
+// ---------------------------------------------------------------- windowed class moments
+// Decoder.train with a window (infer_decoder.py:330-400, average_data :748-783): the per-frame value
+// of frame_scores_kernel's 'all' branch, its means over consecutive windows of `width` frames, and
+// the moments [[M^T M, sum m], [sum m^T, n_win]] of those means that the LDA's scatter matrices are
+// made of -- the frames are read once and nothing per frame is written.
+// A lane is a COLUMN (block_sums_cols_kernel's layout): lane = rs * cols + col reads rows rs,
+// rs + per, ... of its window (per = 64 / cols rows per wave step, contiguous when the stream is
+// dense) and sums them in that order; the per row phases of a column are then summed in ascending
+// order through LDS.  A wave owns win_per_wave consecutive windows and adds m_i m_j of each, in window
+// order, to its own (cols + 1)^2 tile in LDS; the four tiles of a workgroup are summed pairwise in a
+// fixed order into the workgroup's partial.  Which wave sees which window follows from (rows, width)
+// alone, and nothing is atomic: the same bits on every call, whatever the CU count.
+constexpr int kWcmMaxCols = 32;
+constexpr int kWcmEntMax = (kWcmMaxCols + 1) * (kWcmMaxCols + 1);
+constexpr int kWcmWaves = kThreads / 64;
+constexpr int kWcmMinWinPerWave = 4;
+constexpr int kWcmMaxGroups = 1024;     // partials: at most 1024 x 33^2 float64 (8.9 MB of scratch)
+
+__global__ __launch_bounds__(kThreads) void window_class_moments_kernel(
+    const float* __restrict__ a, long long lda, const float* __restrict__ b, long long ldb, int cols,
+    long long n_win, int width, int win_per_wave, ScoreParams sp, double* __restrict__ means,
+    double* __restrict__ partials) {
+  __shared__ double tile[kWcmWaves][kWcmEntMax];
+  __shared__ double part[kWcmWaves][64];
+  __shared__ double mvec[kWcmWaves][kWcmMaxCols + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n1 = cols + 1, n_ent = n1 * n1;
+  for (int e = lane; e < n_ent; e += 64) tile[wave][e] = 0.0;
+  const int per = 64 / cols;                              // rows per wave step (cols <= 32: >= 2)
+  const int col = lane % cols, rs = lane / cols;
+  const bool reads = rs < per;
+  const double ma = sp.mean_a[col], mb = sp.mean_b[col], pw = sp.power[col];
+  const long long w0 = ((long long)blockIdx.x * kWcmWaves + wave) * win_per_wave;
+  // (every wave of the workgroup walks win_per_wave steps, past the last window too: the
+  // workgroup barriers below are met by all of them)
+  for (int it = 0; it < win_per_wave; ++it) {
+    const long long w = w0 + it;
+    const bool live = w < n_win;                          // wave-uniform
+    double s = 0.0;
+    if (live && reads) {
+      const long long r0 = w * width;
+      int r = rs;
+      for (; r + 3 * (long long)per < width; r += 4 * per) {   // four loads of each array in flight
+        float av[4], bv[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          av[q] = a[(r0 + r + q * per) * lda + col];
+          bv[q] = b[(r0 + r + q * per) * ldb + col];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) s += ((double)av[q] - ma) * ((double)bv[q] - mb) / pw;
+      }
+      for (; r < width; r += per)
+        s += ((double)a[(r0 + r) * lda + col] - ma) * ((double)b[(r0 + r) * ldb + col] - mb) / pw;
+    }
+    part[wave][lane] = s;
+    __syncthreads();
+    if (lane <= cols) {
+      double m = 1.0;                                     // lane == cols: the count's column
+      if (lane < cols) {
+        m = part[wave][lane];
+        for (int q = 1; q < per; ++q) m += part[wave][q * cols + lane];
+        m /= (double)width;
+        if (live && means) means[w * cols + lane] = m;
+      }
+      mvec[wave][lane] = live ? m : 0.0;
+    }
+    __syncthreads();
+    if (live)
+      for (int e = lane; e < n_ent; e += 64) tile[wave][e] += mvec[wave][e / n1] * mvec[wave][e % n1];
+  }
+  __syncthreads();
+  static_assert(kWcmWaves == 4, "the pairwise sum below is written for four waves");
+  for (int e = tid; e < n_ent; e += kThreads)
+    partials[(long long)blockIdx.x * n_ent + e] = (tile[0][e] + tile[1][e]) + (tile[2][e] + tile[3][e]);
+}
+
+// moments[e] = the workgroups' partials in workgroup order (none: zeros).
+__global__ void window_class_moments_finish_kernel(const double* __restrict__ partials, int n_groups,
+                                                   int n_ent, double* __restrict__ moments) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_ent) return;
+  double s = 0.0;
+  for (int g = 0; g < n_groups; ++g) s += partials[(long long)g * n_ent + e];
+  moments[e] = s;
+}
+
 // ---------------------------------------------------------------- decisions
 __global__ void decide_wta_kernel(const double* __restrict__ s1, const double* __restrict__ s2,
                                   long long n, unsigned char* __restrict__ out) {
@@ -2872,6 +2959,41 @@ int td_frame_scores(td_handle* h, const float* a_dev, int64_t lda, const float* 
   hipLaunchKernelGGL(frame_scores_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, a_dev,
                      (long long)lda, b_dev, (long long)ldb, cols, (long long)rows, reduction, sp,
                      out_dev);
+  TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
+int td_window_class_moments(td_handle* h, const float* a_dev, int64_t lda, const float* b_dev,
+                            int64_t ldb, int cols, int64_t rows, int width,
+                            const double* mean_a_host, const double* mean_b_host,
+                            const double* power_host, double* means_dev, double* moments_dev) {
+  if (!h || !a_dev || !b_dev || !moments_dev)
+    return td_fail(h, TD_ERR_INVALID, "td_window_class_moments: NULL argument");
+  TD_REQUIRE(h, cols >= 1 && cols <= kWcmMaxCols,
+             "td_window_class_moments: 1 to %d columns, not %d", kWcmMaxCols, cols);
+  TD_REQUIRE(h, width >= 2, "td_window_class_moments: window of %d frames (at least 2)", width);
+  TD_REQUIRE(h, rows >= 0 && lda >= cols && ldb >= cols, "td_window_class_moments: bad sizes");
+  ScoreParams sp;
+  TD_TRY(fill_score_params(h, &sp, cols, mean_a_host, mean_b_host, power_host, nullptr, 1.0, 0.0));
+  const int n_ent = (cols + 1) * (cols + 1);
+  const int64_t n_win = rows / width;
+  // the grid follows from (rows, width) alone
+  int64_t wpw = td_ceil_div(n_win, (int64_t)kWcmWaves * kWcmMaxGroups);
+  if (wpw < kWcmMinWinPerWave) wpw = kWcmMinWinPerWave;
+  const int64_t groups = td_ceil_div(n_win, wpw * kWcmWaves);
+  TD_REQUIRE(h, wpw <= 0x7fffffff, "td_window_class_moments: too many windows");
+  double* partials = nullptr;
+  if (groups > 0) {
+    void* scratch = nullptr;
+    TD_TRY(td_scratch(h, (size_t)groups * n_ent * sizeof(double), &scratch));
+    partials = reinterpret_cast<double*>(scratch);
+    hipLaunchKernelGGL(window_class_moments_kernel, dim3((unsigned)groups), dim3(kThreads), 0,
+                       h->stream, a_dev, (long long)lda, b_dev, (long long)ldb, cols,
+                       (long long)n_win, width, (int)wpw, sp, means_dev, partials);
+    TD_HIP(h, hipGetLastError());
+  }
+  hipLaunchKernelGGL(window_class_moments_finish_kernel, dim3((unsigned)td_ceil_div(n_ent, 256)),
+                     dim3(256), 0, h->stream, partials, (int)groups, n_ent, moments_dev);
   TD_HIP(h, hipGetLastError());
   return TD_OK;
 }

@@ -747,6 +747,54 @@ def window_means(v, trial_offsets, width, hop, handle=None):
   return out
 
 
+WINDOW_CLASS_MOMENTS_MAX_COLS = 32
+
+
+def window_class_moments(a, b, width, mean_a, mean_b, power, want_means=False, handle=None):
+  """Decoder.train's windowed training data in one pass (td_window_class_moments): the per-frame values
+  frame_scores(a, b, 'all', ...) would give, averaged over consecutive windows of `width` frames
+  (infer_decoder.average_data: the tail is dropped), and the moments [[M^T M, sum m], [sum m^T, n_win]] of
+  those window means -- the layout scaled_lda._moments_to_scatter takes.  a, b: float32 device tensors
+  [rows, cols] with unit column stride (row stride free), cols <= 32, width >= 2.  Returns the float64
+  device tensor [cols + 1, cols + 1], or (moments, means [rows // width, cols]) with want_means.  Queued,
+  not waited for."""
+  h = handle or default_handle()
+  rows, cols = int(a.shape[0]), int(a.shape[1])
+  if tuple(b.shape) != (rows, cols):
+    raise ValueError('window_class_moments: a is %s and b is %s' % (tuple(a.shape), tuple(b.shape)))
+  torch = _torch()
+  for name, t in (('a', a), ('b', b)):
+    if t.dtype != torch.float32 or t.device != h.device:
+      raise TypeError('window_class_moments: %s must be a float32 tensor on %s, not %s on %s' %
+                      (name, h.device, t.dtype, t.device))
+  if cols > 1 and (a.stride(1) != 1 or b.stride(1) != 1):
+    raise ValueError('window_class_moments: the columns of a and b must be contiguous')
+  width = int(width)
+  if rows == 0 and 1 <= cols <= WINDOW_CLASS_MOMENTS_MAX_COLS and width >= 2:
+    # (an empty tensor has no address to hand to the kernel: no window, all-zero moments)
+    moments = h.zeros((cols + 1, cols + 1), 'float64')
+    return (moments, h.zeros((0, cols), 'float64')) if want_means else moments
+
+  def vec(v):
+    v = np.asarray(v, np.float64).reshape(-1)
+    if v.size == 1:
+      v = np.repeat(v, cols)
+    if v.size != cols:
+      raise ValueError('window_class_moments: %d statistics for %d columns' % (v.size, cols))
+    return _lib.f64_array(v)
+
+  ma, mb, pw = vec(mean_a), vec(mean_b), vec(power)
+  moments = h.empty((cols + 1, cols + 1), 'float64')
+  means = h.empty((rows // width if width > 0 else 0, cols), 'float64') if want_means else None
+  # (a one-column view's row stride is whatever the tensor says; an empty tensor has no rows to step over)
+  lda = int(a.stride(0)) if rows > 1 else max(cols, int(a.stride(0)))
+  ldb = int(b.stride(0)) if rows > 1 else max(cols, int(b.stride(0)))
+  h.check(h.lib.td_window_class_moments(h.ptr, _ptr(a), lda, _ptr(b), ldb, cols, rows, width,
+                                        ma[1], mb[1], pw[1], _ptr(means) if want_means else None,
+                                        _ptr(moments)))
+  return (moments, means) if want_means else moments
+
+
 def decide_wta(s1, s2, handle=None):
   h = handle or default_handle()
   out = h.zeros((int(s1.shape[0]),), 'uint8')

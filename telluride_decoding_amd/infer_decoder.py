@@ -255,6 +255,18 @@ class Decoder(object):
       # kernels' Gram matrix per class) and d' follows from the same moments -- nothing of the
       # [frames, dims] arrays comes to the host (1e6 frames x 5 dims: 57 -> ~5 ms).
       return self._compute_lda_model_device([self._correlation_device(s[0], s[1]) for s in decoded])
+    if window_size > 1 and all(s is not None and int(s[0].shape[0]) > 0 for s in decoded):
+      # Windowed training data (decoding.train_lda_model: correlation_frames = 100 by default): the
+      # per-frame correlations, their window means and the class moments of those means in one
+      # pass per class (device.window_class_moments) -- two (dims + 1)^2 matrices come to the host.
+      # Only more columns than the kernel's moments tile holds take the host route below.
+      if window_size != int(window_size):
+        raise ValueError('Window size (%s) must be a whole number of frames.' % window_size)
+      h = device.default_handle()
+      streams = [(brain_model._as_2d_device(h, s[0]), brain_model._as_2d_device(h, s[1]))
+                 for s in decoded]
+      if all(int(x.shape[1]) <= device.WINDOW_CLASS_MOMENTS_MAX_COLS for x, _ in streams):
+        return self._compute_lda_model_windowed_device(streams, int(window_size))
     correlations = [None if streams is None else self.compute_correlation(streams[0], streams[1])
                     for streams in decoded]
     for label, c in enumerate(correlations):
@@ -270,6 +282,23 @@ class Decoder(object):
     import torch
     self._lda = scaled_lda.ScaledLinearDiscriminantAnalysis()
     self._lda.fit_device_classes(correlations[0].to(torch.float32), correlations[1].to(torch.float32))
+    (m1, v1), (m2, v2) = self._lda.projected_class_stats()
+    return (m2 - m1) / np.sqrt((v1 + v2) / 2.0)
+
+  def _compute_lda_model_windowed_device(self, streams, window_size):
+    """compute_lda_model(average_data(compute_correlation(...), window_size), ...) for the two decoded
+    stream pairs of train(), as [frames, dims] float32 device tensors: class 1 = streams[0], class 2 =
+    streams[1].  Both classes are queued before the first is waited for."""
+    h = device.default_handle()
+    for label, (xd, _) in enumerate(streams):
+      if int(xd.shape[0]) // window_size == 0:
+        raise ValueError('No data for class %d' % label)
+    queued = []
+    for xd, yd in streams:
+      mx, my, pw = self._stat_vectors(int(xd.shape[1]))
+      queued.append(device.window_class_moments(xd, yd, window_size, mx, my, pw, handle=h))
+    self._lda = scaled_lda.ScaledLinearDiscriminantAnalysis()
+    self._lda.fit_class_moments([q.cpu().numpy() for q in queued])
     (m1, v1), (m2, v2) = self._lda.projected_class_stats()
     return (m2 - m1) / np.sqrt((v1 + v2) / 2.0)
 

@@ -276,6 +276,13 @@ class ScaledLinearDiscriminantAnalysis(LinearDiscriminantAnalysis):
     self._fit_from_moments(_class_moments_of(list(labels), [class0.contiguous(), class1.contiguous()]))
     self._scale(y0, y1)
 
+  def fit_class_moments(self, moments, labels=(1, 2), y0=0, y1=1):
+    """fit() from the classes' moment matrices [[X^T X, sum], [sum^T, n]] ([dims + 1, dims + 1] float64 host
+    arrays, labels sorted) -- what device.window_class_moments returns for windowed training data."""
+    moments = [np.asarray(m, np.float64) for m in moments]
+    self._fit_from_moments(_moments_to_scatter(list(labels), moments, moments[0].shape[0] - 1))
+    self._scale(y0, y1)
+
   def fit(self, x, y, y0=0, y1=1):
     super(ScaledLinearDiscriminantAnalysis, self).fit(x, y)
     self._scale(y0, y1)
