@@ -701,6 +701,42 @@ int td_audio_passthrough(td_handle* h, const double* buf_dev, int64_t buf_rows, 
 int td_audio_spectrogram(td_handle* h, const float* wave_dev, int64_t n, int seg, int hop, int nfft,
                          const double* taps_host, int num_taps, int64_t frames, double* out_dev);
 
+/* ------------------------------------------------------------------ ingestion
+ * ingest.find_mean_std, ingest.normalize_data and ingest.convert_data_to_tfrecords (ingest.py:1061-1172).
+ *
+ * td_ingest_moments: the joint moments of num arrays of `width` columns: data_dev[t] is [rows_host[t], width]
+ * float32 (float64 when is_f64_host[t]), row stride ld_host[t].  Two passes in float64: the column sums give the
+ * means, then the sums of centred squares against those means (never sum x^2).  out_dev [2 + 2 width] float64:
+ * the mean and the standard deviation of everything, the column means, the column standard deviations (all
+ * population moments, divided by the count).  A fixed number of launches whatever num. */
+int td_ingest_moments(td_handle* h, const void* const* data_dev, const int64_t* rows_host, const int64_t* ld_host,
+                      const int* is_f64_host, int num, int width, double* out_dev);
+/* (a - mean) / std_dev: a_dev [rows, width] float32 (float64 when a_is_f64), row stride lda; mean_host / std_host
+ * one value, or `width` values when per_column.  sub_f64: the subtraction in float64 (float32 otherwise, the mean
+ * rounded to float32 first); out_f64: the division and out_dev in float64 (float32 otherwise).  A float64 input
+ * needs both, and sub_f64 needs out_f64.  divide == 0: only centred.  Both operations are the correctly rounded
+ * IEEE ones, so the result is numpy's bit for bit. */
+int td_ingest_normalize(td_handle* h, const void* a_dev, int a_is_f64, int64_t lda, int64_t rows, int width,
+                        const double* mean_host, const double* std_host, int per_column, int sub_f64, int out_f64,
+                        int divide, void* out_dev, int64_t ldout);
+/* The TFRecord file image of one trial, one tf.train.Example per frame: out_dev [frames * stride] bytes (16-byte
+ * aligned).  template_host [stride]: one whole record with zero payloads -- the 8 length bytes (= stride - 16),
+ * the masked CRC of those, the serialized Example; the last 4 bytes (the data CRC) are ignored.  Feature f is
+ * feature_dev[f] [frames, width_host[f]] float32 (float64 when is_f64_host[f]: rounded to nearest even, overflow
+ * to +-Inf, NaN stays NaN; float32 is copied bit for bit), row stride ld_host[f] elements; its row lands as
+ * little-endian float32 at byte offset_host[f] of the record (any alignment; >= 12, inside the data).
+ * reversed_host[f]: record r takes row frames - 1 - r.  Every record's data CRC (masked CRC-32C) is computed on
+ * the device.  1 <= num_features <= 16. */
+int td_tfrecord_encode(td_handle* h, const uint8_t* template_host, int stride, int num_features,
+                       const void* const* feature_dev, const int64_t* ld_host, const int* width_host,
+                       const int* offset_host, const int* is_f64_host, const int* reversed_host, int64_t frames,
+                       uint8_t* out_dev);
+/* The route td_tfrecord_encode takes for records of `stride` bytes.  staged 1: workgroups build `group` records
+ * at a time in LDS (group * stride is a multiple of 16 and at most 48 KB) and store them with 16-byte stores;
+ * staged 0 (group 0): the smallest such group does not fit, one workgroup per record writes it directly.  lanes:
+ * the lanes that share one record's CRC.  Read-only; no handle. */
+int td_tfrecord_route(int stride, int* staged, int* group, int* lanes);
+
 /* ------------------------------------------------------------------ fully connected regressor
  * brain_model.BrainModelDNN (reference brain_model.py:486-549): Dense layers z = a.W + b in float32, ReLU on
  * the num_hidden hidden layers (hidden_host[i] units each), a linear output layer of d units.  The input is

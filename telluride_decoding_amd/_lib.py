@@ -156,6 +156,11 @@ SIGNATURES = {
     'td_audio_intensity': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _d, _d, _d, _i, _d, _vp, _vp],
     'td_audio_passthrough': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _i64, _i, _d, _vp, _vp],
     'td_audio_spectrogram': [_vp, _vp, _i64, _i, _i, _i, _pd, _i, _i64, _vp],
+    'td_ingest_moments': [_vp, _c.POINTER(_vp), _pi64, _pi64, _c.POINTER(_i), _i, _i, _vp],
+    'td_ingest_normalize': [_vp, _vp, _i, _i64, _i64, _i, _pd, _pd, _i, _i, _i, _i, _vp, _i64],
+    'td_tfrecord_encode': [_vp, _c.c_char_p, _i, _i, _c.POINTER(_vp), _pi64, _c.POINTER(_i), _c.POINTER(_i),
+                           _c.POINTER(_i), _c.POINTER(_i), _i64, _vp],
+    'td_tfrecord_route': [_i, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)],
     'td_mlp_train': _MLP + _FIT + _EPOCHS + [_f, _f, _f] + _SEED_STATS,
     'td_mlp_grad': _MLP + _FIT + _GRAD,
     'td_mlp_train_loss': _MLP + _FIT + _EPOCHS + [_f, _f, _f] + _SEED_STATS + [_i],

@@ -924,6 +924,92 @@ def audio_spectrogram(wave, seg, hop, nfft, taps, frames, handle=None):
   return y
 
 
+def _check_rows(t, what):
+  """A 2-D float32 / float64 device tensor whose rows are contiguous."""
+  torch = _torch()
+  if t.dim() != 2 or t.dtype not in (torch.float32, torch.float64) or (t.shape[1] > 1 and t.stride(1) != 1):
+    raise ValueError('%s: a 2-D float32 / float64 device tensor with contiguous rows is needed, not %s %s' %
+                     (what, tuple(t.shape), t.dtype))
+  return t
+
+
+def _row_stride(t):
+  """Elements between rows (a one-row tensor's stride may be anything: report its width)."""
+  return max(int(t.stride(0)), int(t.shape[1])) if t.shape[0] > 1 else int(t.shape[1])
+
+
+def ingest_moments(arrays, handle=None):
+  """The joint two-pass float64 moments of a list of [rows_i, W] float32 / float64 device tensors (row-strided
+  is fine): a device float64 [2 + 2 W] = mean and std of everything, the W column means, the W column stds
+  (td_ingest_moments)."""
+  h = handle or default_handle()
+  arrays = [_check_rows(a, 'ingest_moments') for a in arrays]
+  width = int(arrays[0].shape[1])
+  if any(int(a.shape[1]) != width for a in arrays):
+    raise ValueError('ingest_moments: the arrays differ in width: %s' % [tuple(a.shape) for a in arrays])
+  n = len(arrays)
+  ptrs = (ctypes.c_void_p * n)(*[a.data_ptr() for a in arrays])
+  keep_rows_p, rows_p = _lib.i64_array([int(a.shape[0]) for a in arrays])
+  keep_ld_p, ld_p = _lib.i64_array([_row_stride(a) for a in arrays])
+  keep_f64_p, f64_p = _i32_array([1 if a.dtype == _torch().float64 else 0 for a in arrays])
+  out = h.empty((2 + 2 * width,), 'float64')
+  h.check(h.lib.td_ingest_moments(h.ptr, ptrs, rows_p, ld_p, f64_p, n, width, _ptr(out)))
+  return out
+
+
+def ingest_normalize(a, mean, std, sub_f64, out_f64, divide=True, handle=None):
+  """(a - mean) / std of a [rows, W] float32 / float64 device tensor (td_ingest_normalize).  mean / std: one value
+  or W values (host).  sub_f64 / out_f64: the dtype of the subtraction and of the division (and the result), as
+  numpy would choose them; divide=False only centres."""
+  h = handle or default_handle()
+  a = _check_rows(a, 'ingest_normalize')
+  rows, width = int(a.shape[0]), int(a.shape[1])
+  mean_a, mean_p = _lib.f64_array(np.asarray(mean, np.float64).reshape(-1))
+  std_a, std_p = _lib.f64_array(np.asarray(std, np.float64).reshape(-1))
+  if mean_a.size != std_a.size or mean_a.size not in (1, width):
+    raise ValueError('ingest_normalize: mean and std need 1 or %d values, not %d and %d' %
+                     (width, mean_a.size, std_a.size))
+  per_column = 1 if (mean_a.size == width and width > 1) else 0
+  out = h.empty((rows, width), 'float64' if out_f64 else 'float32')
+  h.check(h.lib.td_ingest_normalize(h.ptr, _ptr(a), 1 if a.dtype == _torch().float64 else 0, _row_stride(a), rows,
+                                    width, mean_p, std_p, per_column, 1 if sub_f64 else 0, 1 if out_f64 else 0,
+                                    1 if divide else 0, _ptr(out), width))
+  return out
+
+
+def tfrecord_route(stride):
+  """(staged, records per workgroup, lanes per record's CRC) of tfrecord_encode for records of `stride` bytes
+  (td_tfrecord_route).  staged False: the record does not fit the LDS staging area; one workgroup writes each
+  record directly.  Needs the library, not a GPU."""
+  lib = _lib.load()
+  staged, group, lanes = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+  if lib.td_tfrecord_route(int(stride), ctypes.byref(staged), ctypes.byref(group), ctypes.byref(lanes)) != 0:
+    raise ValueError('tfrecord_route: bad record stride %d' % stride)
+  return bool(staged.value), int(group.value), int(lanes.value)
+
+
+def tfrecord_encode(template, features, frames, handle=None):
+  """The TFRecord file image of one trial as a device uint8 [frames * len(template)] tensor
+  (td_tfrecord_encode).  template: the bytes of one record with zero payloads (tfrecord.record_template);
+  features: [(device tensor [frames, width] float32 / float64, payload byte offset, reversed)]."""
+  h = handle or default_handle()
+  template = bytes(template)
+  stride, n = len(template), len(features)
+  tensors = [_check_rows(t, 'tfrecord_encode') for t, _, _ in features]
+  if any(int(t.shape[0]) != int(frames) for t in tensors):
+    raise ValueError('tfrecord_encode: every feature needs %d rows: %s' % (frames, [tuple(t.shape) for t in tensors]))
+  ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
+  keep_ld_p, ld_p = _lib.i64_array([_row_stride(t) for t in tensors])
+  keep_width_p, width_p = _i32_array([int(t.shape[1]) for t in tensors])
+  keep_off_p, off_p = _i32_array([int(o) for _, o, _ in features])
+  keep_f64_p, f64_p = _i32_array([1 if t.dtype == _torch().float64 else 0 for t in tensors])
+  keep_rev_p, rev_p = _i32_array([1 if r else 0 for _, _, r in features])
+  out = h.empty((int(frames) * stride,), 'uint8')
+  h.check(h.lib.td_tfrecord_encode(h.ptr, template, stride, n, ptrs, ld_p, width_p, off_p, f64_p, rev_p, int(frames),
+                                   _ptr(out)))
+  return out
+
+
 def sos_filter_plan(n_total, n_max, c, handle=None):
   """(chunk, scan levels) that sos_filter uses for files of n_total rows in all, the longest n_max, over c
   channels (td_sos_filter_plan)."""

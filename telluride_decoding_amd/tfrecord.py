@@ -353,6 +353,54 @@ def write_file(filename, data):
               struct.pack('<I', masked_crc32c(rec)))
 
 
+def record_template(widths):
+  """({name: floats per frame}) -> (template, layout) of the file write_file gives such features: template is one
+  whole record with zero payloads -- 8 bytes of length, the masked CRC of those, the serialized Example, 4 zero
+  bytes where the data CRC goes -- and layout [(name, byte offset of the payload in the record, floats)] in the
+  record's order.  Every record of the file is these bytes but for its payloads and its data CRC: what a
+  device-side encoder (device.tfrecord_encode) needs."""
+  rec = serialize_example({k: np.zeros(int(w), np.float32) for k, w in widths.items()})
+  layout = _float_layout(rec)
+  if layout is None:
+    raise ValueError('no fixed record layout for feature widths %s' % dict(widths))
+  head = struct.pack('<Q', len(rec))
+  template = head + struct.pack('<I', masked_crc32c(head)) + rec + b'\0\0\0\0'
+  return template, [(k, 12 + start, count) for k, start, count in layout]
+
+
+def _enc_int64(x):
+  return _enc_varint(int(x) & 0xffffffffffffffff)
+
+
+def serialize_example_typed(features):
+  """serialize_example for rows of mixed kinds: a float row becomes a packed FloatList, an integer row a packed
+  Int64List (convert_data_to_tfrecords, ingest.py:1155-1169)."""
+  entries = b''
+  for name in sorted(features):
+    vals = np.asarray(features[name]).reshape(-1)
+    if vals.dtype.kind in 'iu':
+      feature = _ld(3, _ld(1, b''.join(_enc_int64(v) for v in vals)))
+    else:
+      feature = _ld(2, _ld(1, vals.astype('<f4').tobytes()))
+    entries += _ld(1, _ld(1, name.encode('utf-8')) + _ld(2, feature))
+  return _ld(1, entries)
+
+
+def write_file_typed(filename, data):
+  """write_file that keeps integer features as Int64Lists ({name: [frames, width]} of float or integer arrays)."""
+  arrays = {k: np.asarray(v) for k, v in data.items()}
+  n = {a.shape[0] for a in arrays.values()}
+  if len(n) != 1:
+    raise ValueError('all features need the same number of frames, not %s' % sorted(n))
+  arrays = {k: a.reshape(a.shape[0], -1) for k, a in arrays.items()}
+  with open(filename, 'wb') as f:
+    for i in range(n.pop()):
+      rec = serialize_example_typed({k: a[i] for k, a in arrays.items()})
+      head = struct.pack('<Q', len(rec))
+      f.write(head + struct.pack('<I', masked_crc32c(head)) + rec +
+              struct.pack('<I', masked_crc32c(rec)))
+
+
 # ---------------------------------------------------------------- field selection
 def select_streams(features, in1_fields, out_field, in2_fields=None, attended_field=None):
   """(input_1, input_2, output, attended_speaker) of one recording, as
