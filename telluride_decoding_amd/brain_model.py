@@ -457,14 +457,16 @@ def history_from_sums(sums, rows, d):
 class _BrainModelMlp(object):
   """What BrainModelDNN and BrainModelClassifier share: the constructor, the packed parameters, the limits of the
   td_mlp_* kernels, the guards of fit and the optimizer argument of compile.  A subclass describes itself by the
-  class attributes below and supplies its loss parsing, its device calls (_train, predict_device), its history
-  and evaluate."""
+  class attributes below and supplies its loss parsing, its device calls (_train, _train_many for fit_many,
+  predict_device), what it records after a fit (_trained) and evaluate."""
 
   # one row per input view: the feature's name, the model attribute that holds its lagged width, and the
   # Dataset's channel / pre / post fields of that view
   _VIEWS = (('input_1', '_input_width', 'c1', 'pre', 'post'),)
   _OPTIMIZER = None            # the optimizer class; compile also takes its name in lower case
   _HISTORY_KEYS = ()           # = metrics_names
+  _STATE_SLOTS = 1             # the optimizer's accumulators per parameter (RMSprop: one; Adam: m and v)
+  # and _history: a staticmethod (sums, rows, d) -> the History's dict of a fit's step sums
   _DATASET_ERROR = ValueError  # what the constructor raises on anything but a Dataset (the reference's type)
 
   def __init__(self, input_dataset, num_hidden_list=None, *, seed=0, **kwargs):
@@ -505,6 +507,11 @@ class _BrainModelMlp(object):
     if self._params is None:
       self._params = h.to_device(np.concatenate([w.reshape(-1) for w in self._host_weights])).reshape(-1)
     return self._params
+
+  def _device_state(self, h):
+    if self._state is None:
+      self._state = h.zeros((self._STATE_SLOTS * int(self._device_params(h).numel()),))
+    return self._state
 
   def get_weights(self):
     """[W1, b1, ..., WL, bL] as float32 arrays (Keras order); W1's rows in input_1's lag layout."""
@@ -594,8 +601,11 @@ class _BrainModelMlp(object):
     zeros = np.zeros((y.shape[0], 1), np.float32)
     return brain_data.Dataset([(xs[0], xs[1] if len(xs) > 1 else zeros, y, zeros)], streams[0][0].shape[0])
 
+  def _trained(self, epochs, steps):
+    """What a model records after `epochs` epochs of `steps` updates, besides its parameters and state."""
+
   def _fit(self, input_dataset, epochs, shuffle_seed):
-    """The guards of fit, then self._train(dataset, handle, epochs, shuffle_seed) -> the History's dict."""
+    """The guards of fit, then self._train(dataset, handle, epochs, shuffle_seed) -> every step's sums, as fit_many."""
     if self.optimizer is None:
       raise RuntimeError('You must compile your model before training/testing.')
     if shuffle_seed is not None and not 0 <= int(shuffle_seed) < 2 ** 63:
@@ -605,7 +615,9 @@ class _BrainModelMlp(object):
     epochs = int(epochs)
     if ds.num_batches() == 0 or epochs <= 0:
       return History({key: [] for key in self._HISTORY_KEYS})
-    return History(self._train(ds, device.default_handle(), epochs, shuffle_seed))
+    sums = self._train(ds, device.default_handle(), epochs, shuffle_seed)
+    self._trained(epochs, ds.num_batches())
+    return History(self._history(sums.cpu().numpy(), ds.batch_size, self._output_width))
 
   # -- inference ---------------------------------------------------------------
   def __call__(self, input_dataset):
@@ -639,10 +651,8 @@ class BrainModelDNN(_BrainModelMlp):
 
   _OPTIMIZER = RMSprop
   _HISTORY_KEYS = ('loss', 'pearson_correlation_first', 'mse')
-
-  def __init__(self, input_dataset, num_hidden_list=None, *, seed=0, **kwargs):
-    super().__init__(input_dataset, num_hidden_list, seed=seed, **kwargs)
-    self.loss = 'mse'          # 'mse' or 'pearson' (compile)
+  _history = staticmethod(history_from_sums)
+  loss = 'mse'                 # 'mse' or 'pearson' (compile)
 
   def compile(self, optimizer=RMSprop, loss='mse', metrics=(pearson_correlation_first, 'mse'),
               learning_rate=1e-3, **kwargs):
@@ -678,15 +688,21 @@ class BrainModelDNN(_BrainModelMlp):
 
   def _train(self, ds, h, epochs, shuffle_seed):
     x, _, y, offs = ds.device_arrays(h)
-    params = self._device_params(h)
-    if self._state is None:
-      self._state = h.zeros((int(params.numel()),))
     opt = self.optimizer
-    sums = device.mlp_train(x, y, offs, ds.pre, ds.post, self.num_hidden_list, params, self._state,
-                            ds.batch_size, epochs, opt.learning_rate, opt.rho, opt.epsilon,
+    return device.mlp_train(x, y, offs, ds.pre, ds.post, self.num_hidden_list, self._device_params(h),
+                            self._device_state(h), ds.batch_size, epochs, opt.learning_rate, opt.rho, opt.epsilon,
                             input_offset=ds.input_offset, rows_used=ds.rows_used(), shuffle_seed=shuffle_seed,
                             handle=h, loss=self.loss)
-    return history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width)
+
+  def _train_many(self, models, ds, h, epochs, used, seeds):
+    """fit_many's device call for `models`, self the first: every model's own RMSprop settings, one loss."""
+    x, _, y, offs = ds.device_arrays(h)
+    opts = [m.optimizer for m in models]
+    return device.dnn_train_many(x, y, offs, ds.pre, ds.post, self.num_hidden_list,
+                                 [m._device_params(h) for m in models], [m._device_state(h) for m in models],
+                                 ds.batch_size, epochs, [o.learning_rate for o in opts], [o.rho for o in opts],
+                                 [o.epsilon for o in opts], used, input_offset=ds.input_offset, shuffle_seeds=seeds,
+                                 handle=h, loss=self.loss)
 
   def call(self, input_dataset):
     """input_dataset: dict with an already-lagged 'input_1' [B, K] -> [B, D] (brain_model.py:524-528)."""
@@ -754,24 +770,8 @@ def fit_many(models, dataset, *, held_out=None, epochs=1, shuffle_seeds=None):
   n = len(models)
   if n == 0:
     return []
-  for i, m in enumerate(models):
-    if not isinstance(m, (BrainModelDNN, BrainModelClassifier)):
-      raise TypeError('fit_many trains BrainModelDNN or BrainModelClassifier models, not %s (model %d)' % (type(m), i))
-    if m.optimizer is None:
-      raise RuntimeError('You must compile your model before training/testing (model %d).' % i)
+  _check_models('fit_many', 'trains', (BrainModelDNN, BrainModelClassifier), models, compiled=True, one_loss=True)
   first = models[0]
-  classifier = isinstance(first, BrainModelClassifier)
-  for i, m in enumerate(models):
-    if isinstance(m, BrainModelClassifier) != classifier:
-      raise ValueError('fit_many: model %d is a %s, model 0 a %s: one model family per call' % (
-          i, type(m).__name__, type(first).__name__))
-    if classifier and m.optimizer.amsgrad:
-      raise NotImplementedError('Adam with amsgrad=True is not supported (model %d)' % i)
-  loss_of = lambda m: getattr(m, 'loss', 'binary_crossentropy')
-  for i, m in enumerate(models):
-    if m._widths != first._widths or loss_of(m) != loss_of(first):
-      raise ValueError('fit_many: model %d has widths %s and loss %r, model 0 %s and %r: one architecture and one '
-                       'loss per call' % (i, m._widths, loss_of(m), first._widths, loss_of(first)))
   _check_shared_dataset('fit_many', dataset)
   first._check_limits(dataset)
   held = [None] * n if held_out is None else list(held_out)
@@ -795,31 +795,37 @@ def fit_many(models, dataset, *, held_out=None, epochs=1, shuffle_seeds=None):
   epochs = int(epochs)
   if epochs <= 0:
     return [History({key: [] for key in first._HISTORY_KEYS}) for _ in models]
-  h = device.default_handle()
-  x, x2, y, offs = dataset.device_arrays(h)
-  params = [m._device_params(h) for m in models]
-  opts = [m.optimizer for m in models]
-  if classifier:
-    for m, p in zip(models, params):
-      if m._state is None:
-        m._state = h.zeros((2 * int(p.numel()),))
-    sums = device.clf_train_many(x, x2, y, offs, dataset.pre, dataset.post, dataset.pre2, dataset.post2,
-                                 first.num_hidden_list, params, [m._state for m in models], dataset.batch_size,
-                                 epochs, used, [o.learning_rate for o in opts], [o.beta_1 for o in opts],
-                                 [o.beta_2 for o in opts], [o.epsilon for o in opts], [m._updates for m in models],
-                                 input_offset=dataset.input_offset, shuffle_seeds=seeds, handle=h)
-    for m, u in zip(models, used):
-      m._updates += epochs * (sum(u) // dataset.batch_size)
-    return [History(classifier_history_from_sums(s.cpu().numpy(), dataset.batch_size, first._output_width))
-            for s in sums]
-  for m, p in zip(models, params):
-    if m._state is None:
-      m._state = h.zeros((int(p.numel()),))
-  sums = device.dnn_train_many(x, y, offs, dataset.pre, dataset.post, first.num_hidden_list, params,
-                               [m._state for m in models], dataset.batch_size, epochs,
-                               [o.learning_rate for o in opts], [o.rho for o in opts], [o.epsilon for o in opts],
-                               used, input_offset=dataset.input_offset, shuffle_seeds=seeds, handle=h, loss=first.loss)
-  return [History(history_from_sums(s.cpu().numpy(), dataset.batch_size, first._output_width)) for s in sums]
+  sums = first._train_many(models, dataset, device.default_handle(), epochs, used, seeds)
+  for m, u in zip(models, used):
+    m._trained(epochs, sum(u) // dataset.batch_size)
+  return [History(first._history(s.cpu().numpy(), dataset.batch_size, first._output_width)) for s in sums]
+
+
+def _check_models(who, verb, families, models, compiled=False, one_loss=False):
+  """The guard fit_many and evaluate_many share: every model is of one of `families` and, for a call that trains,
+  compiled; all are of model 0's family and have its widths (one_loss: and its compiled loss)."""
+  first = models[0] if models else None
+  family = [f for f in families if isinstance(first, f)]
+  names = ' or '.join(f.__name__ for f in families)
+  loss_of = lambda m: getattr(m, 'loss', 'binary_crossentropy')
+  for i, m in enumerate(models):
+    if not isinstance(m, families):
+      raise TypeError('%s %s %s models, not %s (model %d)' % (who, verb, names, type(m), i))
+    if compiled and m.optimizer is None:
+      raise RuntimeError('You must compile your model before training/testing (model %d).' % i)
+  for i, m in enumerate(models):
+    if not isinstance(m, family[0]):
+      raise ValueError('%s: model %d is a %s, model 0 a %s: one model family per call' % (
+          who, i, type(m).__name__, type(first).__name__))
+    if compiled and isinstance(m.optimizer, Adam) and m.optimizer.amsgrad:
+      raise NotImplementedError('Adam with amsgrad=True is not supported (model %d)' % i)
+  for i, m in enumerate(models):
+    if one_loss and (m._widths != first._widths or loss_of(m) != loss_of(first)):
+      raise ValueError('%s: model %d has widths %s and loss %r, model 0 %s and %r: one architecture and one '
+                       'loss per call' % (who, i, m._widths, loss_of(m), first._widths, loss_of(first)))
+    if m._widths != first._widths:
+      raise ValueError('%s: model %d has widths %s, model 0 %s: one architecture per call' % (
+          who, i, m._widths, first._widths))
 
 
 def _check_shared_dataset(who, dataset):
@@ -844,13 +850,7 @@ def evaluate_many(models, dataset, *, files):
   more than once; nothing is written to any of them."""
   models = list(models)
   n = len(models)
-  for i, m in enumerate(models):
-    if not isinstance(m, BrainModelClassifier):
-      raise TypeError('evaluate_many scores BrainModelClassifier models, not %s (model %d)' % (type(m), i))
-  for i, m in enumerate(models):
-    if m._widths != models[0]._widths:
-      raise ValueError('evaluate_many: model %d has widths %s, model 0 %s: one architecture per call' % (
-          i, m._widths, models[0]._widths))
+  _check_models('evaluate_many', 'scores', (BrainModelClassifier,), models)
   _check_shared_dataset('evaluate_many', dataset)
   files = list(files)
   if len(files) != n:
@@ -870,15 +870,10 @@ def evaluate_many(models, dataset, *, files):
   live = [i for i, u in enumerate(used) if sum(u) >= dataset.batch_size]
   if not live:
     return out
-  h = device.default_handle()
-  x, x2, y, offs = dataset.device_arrays(h)
-  first = models[0]
-  sums = device.clf_train_many(x, x2, y, offs, dataset.pre, dataset.post, dataset.pre2, dataset.post2,
-                               first.num_hidden_list, [models[i]._device_params(h) for i in live], None,
-                               dataset.batch_size, 1, [used[i] for i in live], update=False,
-                               input_offset=dataset.input_offset, handle=h)
+  sums = models[0]._train_many([models[i] for i in live], dataset, device.default_handle(), 1,
+                               [used[i] for i in live], None, update=False)
   for i, s in zip(live, sums):
-    hist = classifier_history_from_sums(s.cpu().numpy(), dataset.batch_size, first._output_width)
+    hist = classifier_history_from_sums(s.cpu().numpy(), dataset.batch_size, models[0]._output_width)
     out[i] = {'loss': hist['loss'][0], 'accuracy': hist['accuracy'][0]}
   return out
 
@@ -940,11 +935,10 @@ class BrainModelClassifier(_BrainModelMlp):
   _VIEWS = _BrainModelMlp._VIEWS + (('input_2', '_input2_width', 'c2', 'pre2', 'post2'),)
   _OPTIMIZER = Adam
   _HISTORY_KEYS = ('loss', 'accuracy')
+  _STATE_SLOTS = 2
+  _history = staticmethod(classifier_history_from_sums)
   _DATASET_ERROR = TypeError
-
-  def __init__(self, input_dataset, num_hidden_list=None, *, seed=0, **kwargs):
-    super().__init__(input_dataset, num_hidden_list, seed=seed, **kwargs)
-    self._updates = 0          # Adam's t: updates applied since compile (_state: Adam's m, then v)
+  _updates = 0                 # Adam's t: updates applied since compile (_state: Adam's m, then v)
 
   def compile(self, optimizer=Adam, loss=BinaryCrossentropy(), metrics='accuracy', learning_rate=1e-3, **kwargs):
     """Adam (the class, an instance, 'adam', or any callable that returns an Adam when called with
@@ -962,6 +956,9 @@ class BrainModelClassifier(_BrainModelMlp):
     self._state = None
     self._updates = 0
 
+  def _trained(self, epochs, steps):
+    self._updates += epochs * steps
+
   def _check_limits(self, ds):
     super()._check_limits(ds, [] if ds.d == self._output_width else [
         'the output is %d wide, the model %d' % (ds.d, self._output_width)])
@@ -970,10 +967,10 @@ class BrainModelClassifier(_BrainModelMlp):
     x, x2, y, offs = ds.device_arrays(h)
     opt = self.optimizer or Adam()
     return device.mlpc_train(x, x2, y, offs, ds.pre, ds.post, ds.pre2, ds.post2, self.num_hidden_list,
-                             self._device_params(h), self._state, ds.batch_size, epochs, opt.learning_rate,
-                             opt.beta_1, opt.beta_2, opt.epsilon, step0=self._updates, update=update,
-                             input_offset=ds.input_offset, rows_used=ds.rows_used(), shuffle_seed=shuffle_seed,
-                             handle=h)
+                             self._device_params(h), self._device_state(h) if update else None, ds.batch_size,
+                             epochs, opt.learning_rate, opt.beta_1, opt.beta_2, opt.epsilon, step0=self._updates,
+                             update=update, input_offset=ds.input_offset, rows_used=ds.rows_used(),
+                             shuffle_seed=shuffle_seed, handle=h)
 
   def fit(self, input_dataset, *, epochs=1, shuffle_seed=None, **kwargs):
     """Trains `epochs` epochs over the dataset's minibatches (reference brain_model.py:619-620 -> Keras fit).
@@ -983,11 +980,19 @@ class BrainModelClassifier(_BrainModelMlp):
     return self._fit(input_dataset, epochs, shuffle_seed)
 
   def _train(self, ds, h, epochs, shuffle_seed):
-    if self._state is None:
-      self._state = h.zeros((2 * int(self._device_params(h).numel()),))
-    sums = self._run(ds, h, epochs, True, shuffle_seed)
-    self._updates += epochs * ds.num_batches()
-    return classifier_history_from_sums(sums.cpu().numpy(), ds.batch_size, self._output_width)
+    return self._run(ds, h, epochs, True, shuffle_seed)
+
+  def _train_many(self, models, ds, h, epochs, used, seeds, update=True):
+    """fit_many's device call for `models`, self the first: every model's own Adam settings and update count; and
+    evaluate_many's (update=False: one pass that reads neither, and touches no model's state)."""
+    x, x2, y, offs = ds.device_arrays(h)
+    opts = [m.optimizer or Adam() for m in models]
+    return device.clf_train_many(x, x2, y, offs, ds.pre, ds.post, ds.pre2, ds.post2, self.num_hidden_list,
+                                 [m._device_params(h) for m in models],
+                                 [m._device_state(h) for m in models] if update else None, ds.batch_size, epochs, used,
+                                 [o.learning_rate for o in opts], [o.beta_1 for o in opts], [o.beta_2 for o in opts],
+                                 [o.epsilon for o in opts], [m._updates for m in models], update=update,
+                                 input_offset=ds.input_offset, shuffle_seeds=seeds, handle=h)
 
   def evaluate(self, dataset, **kwargs):
     """{'loss', 'accuracy'}: the means over the dataset's minibatches of the binary cross-entropy and the binary

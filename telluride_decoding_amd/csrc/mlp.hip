@@ -744,6 +744,15 @@ struct MlpCall {
   bool classifier;                // td_mlpc_*: the second view is required; sigmoid output, binary cross-entropy
 };
 
+// An entry point's arguments as an MlpCall, group by group in the struct's order: the first view, the second ({}: a
+// regressor has none), the files, the targets, the network, the step, the loss and the family.
+MlpCall mlp_call(const MlpView& v1, const MlpView& v2, const int64_t* offsets, int num_files, int input_offset,
+                 const int64_t* rows_used, const float* y, int64_t ldy, int d, const int* hidden, int num_hidden,
+                 int batch_rows, int loss, bool classifier) {
+  return {v1, v2, offsets, num_files, input_offset, rows_used, y, ldy, d, hidden, num_hidden, batch_rows, loss,
+          classifier};
+}
+
 int mlp_check_and_plan(td_handle* h, const char* fn, const MlpCall& a, MlpPlan* plan) {
   const MlpView &v1 = a.v1, &v2 = a.v2;
   const int64_t* offs = a.file_offsets;
@@ -829,19 +838,25 @@ int mlp_check_and_plan(td_handle* h, const char* fn, const MlpCall& a, MlpPlan* 
   return TD_OK;
 }
 
-int mlp_launch_slab(td_handle* h, const MlpPlan& plan, const SlabArgs& a, bool with_small) {
-  const int grid = plan.nslices + (with_small ? plan.n_small_wg : 0);
-  switch (plan.nj) {
-    case 4: hipLaunchKernelGGL(mlp_slab_kernel<4>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
-    case 8: hipLaunchKernelGGL(mlp_slab_kernel<8>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
-    case 16: hipLaunchKernelGGL(mlp_slab_kernel<16>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
-    case 24: hipLaunchKernelGGL(mlp_slab_kernel<24>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
-    case 32: hipLaunchKernelGGL(mlp_slab_kernel<32>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
-    case 48: hipLaunchKernelGGL(mlp_slab_kernel<48>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
-    default: hipLaunchKernelGGL(mlp_slab_kernel<64>, dim3(grid), dim3(kSlabThreads), 0, h->stream, a); break;
-  }
+// The instantiations of the two kernel families as the host picks them, each table next to its launcher -- a single
+// fit's launches (One), and the many-model launches with the models in blockIdx.y (Many): the slab kernel whose tile
+// holds plan.nj first-layer units (kSlabNj), and the head kernel of a pass (0: mse and cross-entropy; 1, 2: Pearson).
+constexpr int kSlabNj[7] = {4, 8, 16, 24, 32, 48, 64};
+constexpr void (*kSlabOne[7])(SlabArgs) = {
+    mlp_slab_kernel<4>,  mlp_slab_kernel<8>,  mlp_slab_kernel<16>, mlp_slab_kernel<24>,
+    mlp_slab_kernel<32>, mlp_slab_kernel<48>, mlp_slab_kernel<64>};
+
+template <typename K, typename... Args>
+int mlp_launch_slab_of(td_handle* h, const MlpPlan& plan, K* const (&family)[7], dim3 grid, const Args&... args) {
+  // (the search stops in front of the last entry: an nj that is none of the first six takes the widest kernel, 64)
+  const int i = (int)(std::find(kSlabNj, kSlabNj + 6, plan.nj) - kSlabNj);
+  hipLaunchKernelGGL(family[i], grid, dim3(kSlabThreads), 0, h->stream, args...);
   TD_HIP(h, hipGetLastError());
   return TD_OK;
+}
+
+int mlp_launch_slab(td_handle* h, const MlpPlan& plan, const SlabArgs& a, bool with_small) {
+  return mlp_launch_slab_of(h, plan, kSlabOne, dim3(plan.nslices + (with_small ? plan.n_small_wg : 0)), a);
 }
 
 int mlp_launch_head(td_handle* h, const MlpPlan& plan, const HeadArgs& a) {
@@ -858,6 +873,17 @@ int mlp_launch_head(td_handle* h, const MlpPlan& plan, const HeadArgs& a) {
     hipLaunchKernelGGL(mlp_head_kernel<0>, dim3(plan.n_head), dim3(kHeadRows), plan.head_lds, h->stream, a);
   }
   TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
+constexpr void (*kHeadOne[3])(HeadArgs) = {mlp_head_kernel<0>, mlp_head_kernel<1>, mlp_head_kernel<2>};
+
+// lets the first `passes` head kernels of a family take kHeadMaxLds of dynamic LDS
+template <typename K>
+int mlp_raise_head_lds(td_handle* h, K* const (&family)[3], int passes) {
+  for (int pp = 0; pp < passes; ++pp)
+    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(family[pp]), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  kHeadMaxLds));
   return TD_OK;
 }
 
@@ -926,15 +952,7 @@ int mlp_setup(td_handle* h, MlpPlan* plan, const MlpCall& a, const std::vector<l
   if (!so.empty()) TD_TRY(td_upload_async(h, so.data(), sizeof(long long) * (nf + 1), w->stream_offs));
   plan->g.file_offs = w->file_offs;
   plan->g.stream_offs = so.empty() ? w->file_offs : w->stream_offs;
-  TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_kernel<0>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
-  if (plan->g.pearson) {
-    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_kernel<1>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
-    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_kernel<2>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
-  }
-  return TD_OK;
+  return mlp_raise_head_lds(h, kHeadOne, plan->g.pearson ? 3 : 1);
 }
 
 void mlp_fill(const MlpPlan& plan, const MlpWork& w, SlabArgs* sa, HeadArgs* ha) {
@@ -978,6 +996,32 @@ float mlp_adam_lr(const MlpOpt& opt, int64_t index) {
   return (float)(opt.lr * std::sqrt(1.0 - std::pow(opt.b2, t)) / (1.0 - std::pow(opt.b1, t)));
 }
 
+// The checks of a training call's settings; model >= 0 names the model of a many-model call in the message.
+int mlp_check_opt(td_handle* h, const char* fn, const MlpOpt& opt, int model) {
+  char who[24] = "";
+  if (model >= 0) snprintf(who, sizeof(who), "model %d: ", model);
+  TD_REQUIRE(h, std::isfinite(opt.lr) && std::isfinite(opt.b1) && std::isfinite(opt.b2) && std::isfinite(opt.eps),
+             "%s: %snon-finite optimizer setting", fn, who);
+  if (opt.update == kUpdAdam)
+    TD_REQUIRE(h, opt.b1 >= 0.0 && opt.b1 < 1.0 && opt.b2 >= 0.0 && opt.b2 < 1.0 && opt.step0 >= 0,
+               "%s: %sAdam needs 0 <= beta < 1 and step0 >= 0", fn, who);
+  return TD_OK;
+}
+
+// the update rule and every setting of it but the learning rate (a launch's or a model's own), as the kernels read them
+void mlp_set_opt(SlabArgs* sa, const MlpOpt& opt) {
+  sa->update = opt.update;
+  sa->rho = (float)opt.b1; sa->eps = (float)opt.eps;
+  sa->beta2 = (float)opt.b2; sa->omb1 = (float)(1.0 - opt.b1); sa->omb2 = (float)(1.0 - opt.b2);
+}
+
+// the visiting order of a stream: seed < 0 in order, else the Feistel bijection of (seed, epoch)
+void mlp_set_seed(MlpGeom* g, int64_t seed) {
+  g->shuffle = seed >= 0;
+  g->seed_lo = (unsigned)((uint64_t)seed & 0xffffffffu);
+  g->seed_hi = (unsigned)((uint64_t)seed >> 32);
+}
+
 void mlp_set_update(SlabArgs* sa, const MlpOpt& opt, int64_t index) {
   if (opt.update != kUpdAdam) return;
   sa->at.lr = mlp_adam_lr(opt, index);
@@ -994,11 +1038,7 @@ int mlp_train(td_handle* h, const char* fn, const MlpCall& a, int epochs, float*
   TD_REQUIRE(h, a.y && params_dev && (state_dev || !update) && a.ldy >= a.d, "%s: NULL argument or ldy too small",
              fn);
   TD_REQUIRE(h, epochs >= 0, "%s: negative epoch count", fn);
-  TD_REQUIRE(h, std::isfinite(opt.lr) && std::isfinite(opt.b1) && std::isfinite(opt.b2) && std::isfinite(opt.eps),
-             "%s: non-finite optimizer setting", fn);
-  if (opt.update == kUpdAdam)
-    TD_REQUIRE(h, opt.b1 >= 0.0 && opt.b1 < 1.0 && opt.b2 >= 0.0 && opt.b2 < 1.0 && opt.step0 >= 0,
-               "%s: Adam needs 0 <= beta < 1 and step0 >= 0", fn);
+  TD_TRY(mlp_check_opt(h, fn, opt, -1));
   std::vector<long long> so;
   TD_TRY(mlp_stream_offsets(h, fn, a, &so));
   const long long n_rows = so[a.num_files];
@@ -1008,9 +1048,7 @@ int mlp_train(td_handle* h, const char* fn, const MlpCall& a, int epochs, float*
   if (epochs == 0) return TD_OK;
   plan.g.y = a.y; plan.g.ldy = a.ldy;
   plan.g.n_rows = n_rows;
-  plan.g.shuffle = shuffle_seed >= 0;
-  plan.g.seed_lo = (unsigned)((uint64_t)shuffle_seed & 0xffffffffu);
-  plan.g.seed_hi = (unsigned)((uint64_t)shuffle_seed >> 32);
+  mlp_set_seed(&plan.g, shuffle_seed);
   MlpWork w;
   TD_TRY(mlp_setup(h, &plan, a, so, &w));
   // work on copies: the caller's parameters change only when every launch has been queued
@@ -1021,9 +1059,8 @@ int mlp_train(td_handle* h, const char* fn, const MlpCall& a, int epochs, float*
   SlabArgs sa;
   HeadArgs ha;
   mlp_fill(plan, w, &sa, &ha);
-  sa.update = opt.update;
-  sa.at.lr = (float)opt.lr; sa.rho = (float)opt.b1; sa.eps = (float)opt.eps;
-  sa.beta2 = (float)opt.b2; sa.omb1 = (float)(1.0 - opt.b1); sa.omb2 = (float)(1.0 - opt.b2);
+  mlp_set_opt(&sa, opt);
+  sa.at.lr = (float)opt.lr;
   ha.backward = update;
   const int nstat = plan.g.pearson ? 7 : 6;
   int pe = -1, ps = -1;
@@ -1132,6 +1169,18 @@ struct ManyCall {
   const int64_t* shuffle_seed;     // host [num_models], < 0: in order (score only: not read)
 };
 
+// The per-model settings of a many-model call: model m's from the arrays of an entry point (lr null: all zero, the
+// call only scores; b2 / step0 null: the rule has none), and one entry even without models, so that opt[0] names
+// the rule.
+template <typename T>
+std::vector<MlpOpt> mlp_opts(int rule, int num_models, const T* lr, const T* b1, const T* b2, const T* eps,
+                             const int64_t* step0) {
+  std::vector<MlpOpt> opt(std::max(num_models, 1), {rule, 0.0, 0.0, 0.0, 0.0, 0});
+  for (int m = 0; lr && m < num_models; ++m)
+    opt[m] = {rule, lr[m], b1[m], b2 ? b2[m] : 0.0, eps[m], step0 ? step0[m] : 0};
+  return opt;
+}
+
 // a call's scratch, sized on a first pass (base null) and handed out on a second
 struct MlpBump {
   char* base;
@@ -1145,20 +1194,9 @@ struct MlpBump {
   }
 };
 
-int mlp_launch_slab_many(td_handle* h, const MlpPlan& plan, int num_models, const ManyModel* tab, int t) {
-  const dim3 grid(plan.nslices + plan.n_small_wg, num_models), block(kSlabThreads);
-  switch (plan.nj) {
-    case 4: hipLaunchKernelGGL(mlp_slab_many_kernel<4>, grid, block, 0, h->stream, tab, t); break;
-    case 8: hipLaunchKernelGGL(mlp_slab_many_kernel<8>, grid, block, 0, h->stream, tab, t); break;
-    case 16: hipLaunchKernelGGL(mlp_slab_many_kernel<16>, grid, block, 0, h->stream, tab, t); break;
-    case 24: hipLaunchKernelGGL(mlp_slab_many_kernel<24>, grid, block, 0, h->stream, tab, t); break;
-    case 32: hipLaunchKernelGGL(mlp_slab_many_kernel<32>, grid, block, 0, h->stream, tab, t); break;
-    case 48: hipLaunchKernelGGL(mlp_slab_many_kernel<48>, grid, block, 0, h->stream, tab, t); break;
-    default: hipLaunchKernelGGL(mlp_slab_many_kernel<64>, grid, block, 0, h->stream, tab, t); break;
-  }
-  TD_HIP(h, hipGetLastError());
-  return TD_OK;
-}
+constexpr void (*kSlabMany[7])(const ManyModel*, int) = {
+    mlp_slab_many_kernel<4>,  mlp_slab_many_kernel<8>,  mlp_slab_many_kernel<16>, mlp_slab_many_kernel<24>,
+    mlp_slab_many_kernel<32>, mlp_slab_many_kernel<48>, mlp_slab_many_kernel<64>};
 
 int mlp_launch_head_many(td_handle* h, const MlpPlan& plan, int num_models, const ManyModel* tab, int t) {
   const MlpGeom& g = plan.g;
@@ -1174,6 +1212,9 @@ int mlp_launch_head_many(td_handle* h, const MlpPlan& plan, int num_models, cons
   TD_HIP(h, hipGetLastError());
   return TD_OK;
 }
+
+constexpr void (*kHeadMany[3])(const ManyModel*, int) = {mlp_head_many_kernel<0>, mlp_head_many_kernel<1>,
+                                                         mlp_head_many_kernel<2>};
 
 // mlp_train for num_models models at once (regressors on RMSprop, classifiers on Adam or scored only, kUpdNone):
 // every check of every model first, then working copies, the rounds of launches (round t = launch t of every
@@ -1195,17 +1236,12 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
   int max_steps = 0;
   long long max_total = 0;
   for (int m = 0; m < nm; ++m) {
-    const MlpOpt& opt = mc.opt[m];
     TD_REQUIRE(h, mc.params[m] && (!update || mc.state[m]), "%s: model %d: NULL parameters or state", fn, m);
     // (scoring writes to no model, so two entries may score one model on different files)
     for (int j = 0; update && j < m; ++j)
       TD_REQUIRE(h, mc.params[j] != mc.params[m] && mc.state[j] != mc.state[m],
                  "%s: models %d and %d share their parameters or state", fn, j, m);
-    TD_REQUIRE(h, std::isfinite(opt.lr) && std::isfinite(opt.b1) && std::isfinite(opt.b2) && std::isfinite(opt.eps),
-               "%s: model %d: non-finite optimizer setting", fn, m);
-    if (adam)
-      TD_REQUIRE(h, opt.b1 >= 0.0 && opt.b1 < 1.0 && opt.b2 >= 0.0 && opt.b2 < 1.0 && opt.step0 >= 0,
-                 "%s: model %d: Adam needs 0 <= beta < 1 and step0 >= 0", fn, m);
+    TD_TRY(mlp_check_opt(h, fn, mc.opt[m], m));
     MlpCall am = a;
     am.rows_used = mc.rows_used + (size_t)m * nf;
     TD_TRY(mlp_stream_offsets(h, fn, am, &so[m]));
@@ -1265,25 +1301,18 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
   for (size_t f = 0; f < n_off; ++f) so_host[f] = a.file_offsets[f];
   for (int m = 0; m < nm; ++m) std::copy(so[m].begin(), so[m].end(), so_host.begin() + (size_t)(m + 1) * n_off);
   std::vector<ManyModel> tab(nm);
-  std::vector<MlpGeom> geom(nm);
   for (int m = 0; m < nm; ++m) {
     const MlpWork& w = work[m];
     MlpPlan pm = plan;
     pm.g.file_offs = w.file_offs; pm.g.stream_offs = w.stream_offs;
     pm.g.n_rows = so[m][nf];
-    pm.g.shuffle = seed_of(m) >= 0;
-    pm.g.seed_lo = (unsigned)((uint64_t)seed_of(m) & 0xffffffffu);
-    pm.g.seed_hi = (unsigned)((uint64_t)seed_of(m) >> 32);
-    geom[m] = pm.g;
+    mlp_set_seed(&pm.g, seed_of(m));
     ManyModel& t = tab[m];
     memset(&t, 0, sizeof(t));
     mlp_fill(pm, w, &t.slab, &t.head);
-    const MlpOpt& opt = mc.opt[m];
-    t.slab.update = rule;
-    t.slab.rho = (float)opt.b1; t.slab.eps = (float)opt.eps;
-    t.slab.beta2 = (float)opt.b2; t.slab.omb1 = (float)(1.0 - opt.b1); t.slab.omb2 = (float)(1.0 - opt.b2);
+    mlp_set_opt(&t.slab, mc.opt[m]);
     t.head.backward = update;
-    t.lr = (float)opt.lr; t.lr_t = adam ? lr_dev + lr_at[m] : nullptr;
+    t.lr = (float)mc.opt[m].lr; t.lr_t = adam ? lr_dev + lr_at[m] : nullptr;
     t.rows[0] = w.rows[0]; t.rows[1] = w.rows[1];
     t.steps = (int)td_ceil_div(pm.g.n_rows, batch_rows);
     t.total = epochs * t.steps;
@@ -1300,28 +1329,23 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
       for (int k = 0; k < tab[m].total; ++k) lr_t[lr_at[m] + k] = mlp_adam_lr(mc.opt[m], k);
     TD_TRY(td_upload_async(h, lr_t.data(), sizeof(float) * lr_t.size(), lr_dev));
   }
-  TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_many_kernel<0>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
-  TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_many_kernel<1>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
-  TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_head_many_kernel<2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kHeadMaxLds));
+  TD_TRY(mlp_raise_head_lds(h, kHeadMany, 3));
   // work on copies: the callers' parameters change only when every launch has been queued
   const size_t pbytes = sizeof(float) * g.n_params, sbytes = adam ? 2 * pbytes : pbytes;
   for (int m = 0; m < nm; ++m) {
     TD_HIP(h, hipMemcpyAsync(work[m].params, mc.params[m], pbytes, hipMemcpyDeviceToDevice, h->stream));
     if (update) TD_HIP(h, hipMemcpyAsync(work[m].state, mc.state[m], sbytes, hipMemcpyDeviceToDevice, h->stream));
-    if (!geom[m].shuffle) TD_TRY(mlp_launch_rows(h, geom[m], 0, work[m].rows[0]));
+    if (!tab[m].slab.g.shuffle) TD_TRY(mlp_launch_rows(h, tab[m].slab.g, 0, work[m].rows[0]));
   }
   for (long long t = 0; t <= max_total; ++t) {
     // shuffled: the table of a model's epoch e, in front of the round that starts it (its other table still
     // serves the update of the last step of epoch e - 1)
     for (int m = 0; m < nm; ++m)
-      if (geom[m].shuffle && t < tab[m].total && t % tab[m].steps == 0) {
+      if (tab[m].slab.g.shuffle && t < tab[m].total && t % tab[m].steps == 0) {
         const int e = (int)(t / tab[m].steps);
-        TD_TRY(mlp_launch_rows(h, geom[m], e, work[m].rows[e & 1]));
+        TD_TRY(mlp_launch_rows(h, tab[m].slab.g, e, work[m].rows[e & 1]));
       }
-    TD_TRY(mlp_launch_slab_many(h, plan, nm, tab_dev, (int)t));
+    TD_TRY(mlp_launch_slab_of(h, plan, kSlabMany, dim3(plan.nslices + plan.n_small_wg, nm), tab_dev, (int)t));
     if (t < max_total) TD_TRY(mlp_launch_head_many(h, plan, nm, tab_dev, (int)t));
   }
   for (int m = 0; update && m < nm; ++m) {
@@ -1333,15 +1357,14 @@ int mlp_train_many(td_handle* h, const char* fn, const MlpCall& a, int epochs, c
 
 }  // namespace
 
-// The exported entry points: each packs its arguments into an MlpCall, group by group in the struct's order
-// ({first view}, {second view}, files, targets, network, step, loss, classifier).
+// The exported entry points: each packs its arguments with mlp_call and passes its own name for the messages.
 int td_mlp_train(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
                  int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
                  int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int epochs,
                  float* params_dev, float* state_dev, float lr, float rho, float eps, int64_t shuffle_seed,
                  double* stats_dev) {
-  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, rows_used_host,
-                     y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, false};
+  const MlpCall a = mlp_call({x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset,
+                             rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, false);
   return mlp_train(h, "td_mlp_train", a, epochs, params_dev, state_dev, {kUpdRmsprop, lr, rho, 0.0, eps, 0},
                    shuffle_seed, stats_dev);
 }
@@ -1351,8 +1374,8 @@ int td_mlp_train_loss(td_handle* h, const float* x_dev, int64_t ldx, const int64
                       const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden,
                       int batch_rows, int epochs, float* params_dev, float* state_dev, float lr, float rho,
                       float eps, int64_t shuffle_seed, double* stats_dev, int loss) {
-  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, rows_used_host,
-                     y_dev, ldy, d, hidden_host, num_hidden, batch_rows, loss, false};
+  const MlpCall a = mlp_call({x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset,
+                             rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, loss, false);
   return mlp_train(h, "td_mlp_train_loss", a, epochs, params_dev, state_dev, {kUpdRmsprop, lr, rho, 0.0, eps, 0},
                    shuffle_seed, stats_dev);
 }
@@ -1361,8 +1384,8 @@ int td_mlp_grad(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* fi
                 int c, int pre, int post, int input_offset, const int64_t* rows_used_host, const float* y_dev,
                 int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows, int batch_index,
                 const float* params_dev, float* grad_dev, double* stats_dev) {
-  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, rows_used_host,
-                     y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, false};
+  const MlpCall a = mlp_call({x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset,
+                             rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, false);
   return mlp_grad(h, "td_mlp_grad", a, batch_index, params_dev, grad_dev, stats_dev);
 }
 
@@ -1370,16 +1393,16 @@ int td_mlp_grad_loss(td_handle* h, const float* x_dev, int64_t ldx, const int64_
                      int num_files, int c, int pre, int post, int input_offset, const int64_t* rows_used_host,
                      const float* y_dev, int64_t ldy, int d, const int* hidden_host, int num_hidden, int batch_rows,
                      int batch_index, const float* params_dev, float* grad_dev, double* stats_dev, int loss) {
-  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, rows_used_host,
-                     y_dev, ldy, d, hidden_host, num_hidden, batch_rows, loss, false};
+  const MlpCall a = mlp_call({x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset,
+                             rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, loss, false);
   return mlp_grad(h, "td_mlp_grad_loss", a, batch_index, params_dev, grad_dev, stats_dev);
 }
 
 int td_mlp_forward(td_handle* h, const float* x_dev, int64_t ldx, const int64_t* file_offsets_host, int num_files,
                    int c, int pre, int post, int input_offset, int d, const int* hidden_host, int num_hidden,
                    const float* params_dev, float* out_dev, int64_t ldout) {
-  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, nullptr,
-                     nullptr, 0, d, hidden_host, num_hidden, kFwdChunk, 0, false};
+  const MlpCall a = mlp_call({x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, nullptr,
+                             nullptr, 0, d, hidden_host, num_hidden, kFwdChunk, 0, false);
   return mlp_forward(h, "td_mlp_forward", a, params_dev, out_dev, ldout);
 }
 
@@ -1389,8 +1412,9 @@ int td_mlpc_train(td_handle* h, const float* x_dev, int64_t ldx, const float* x2
                   const int* hidden_host, int num_hidden, int batch_rows, int epochs, float* params_dev,
                   float* state_dev, double lr, double beta1, double beta2, double eps, int64_t step0, int update,
                   int64_t shuffle_seed, double* stats_dev) {
-  const MlpCall a = {{x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host, num_files,
-                     input_offset, rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, true};
+  const MlpCall a = mlp_call({x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host,
+                             num_files, input_offset, rows_used_host, y_dev, ldy, d, hidden_host, num_hidden,
+                             batch_rows, 0, true);
   return mlp_train(h, "td_mlpc_train", a, epochs, params_dev, state_dev,
                    {update ? kUpdAdam : kUpdNone, lr, beta1, beta2, eps, step0}, shuffle_seed, stats_dev);
 }
@@ -1400,8 +1424,9 @@ int td_mlpc_grad(td_handle* h, const float* x_dev, int64_t ldx, const float* x2_
                  int post2, int input_offset, const int64_t* rows_used_host, const float* y_dev, int64_t ldy, int d,
                  const int* hidden_host, int num_hidden, int batch_rows, int batch_index, const float* params_dev,
                  float* grad_dev, double* stats_dev) {
-  const MlpCall a = {{x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host, num_files,
-                     input_offset, rows_used_host, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, true};
+  const MlpCall a = mlp_call({x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host,
+                             num_files, input_offset, rows_used_host, y_dev, ldy, d, hidden_host, num_hidden,
+                             batch_rows, 0, true);
   return mlp_grad(h, "td_mlpc_grad", a, batch_index, params_dev, grad_dev, stats_dev);
 }
 
@@ -1409,8 +1434,9 @@ int td_mlpc_forward(td_handle* h, const float* x_dev, int64_t ldx, const float* 
                     const int64_t* file_offsets_host, int num_files, int c, int pre, int post, int c2, int pre2,
                     int post2, int input_offset, int d, const int* hidden_host, int num_hidden,
                     const float* params_dev, float* out_dev, int64_t ldout) {
-  const MlpCall a = {{x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host, num_files,
-                     input_offset, nullptr, nullptr, 0, d, hidden_host, num_hidden, kFwdChunk, 0, true};
+  const MlpCall a = mlp_call({x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host,
+                             num_files, input_offset, nullptr, nullptr, 0, d, hidden_host, num_hidden, kFwdChunk, 0,
+                             true);
   return mlp_forward(h, "td_mlpc_forward", a, params_dev, out_dev, ldout);
 }
 
@@ -1420,14 +1446,13 @@ int td_dnn_train_many(td_handle* h, const float* x_dev, int64_t ldx, const int64
                       const int64_t* rows_used_host, float* const* params_dev_host, float* const* state_dev_host,
                       const float* lr_host, const float* rho_host, const float* eps_host,
                       const int64_t* shuffle_seed_host, double* stats_dev) {
-  const MlpCall a = {{x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, nullptr,
-                     y_dev, ldy, d, hidden_host, num_hidden, batch_rows, loss, false};
+  const MlpCall a = mlp_call({x_dev, ldx, c, pre, post}, {}, file_offsets_host, num_files, input_offset, nullptr,
+                             y_dev, ldy, d, hidden_host, num_hidden, batch_rows, loss, false);
   const char* fn = "td_dnn_train_many";
   TD_REQUIRE(h, lr_host && rho_host && eps_host && num_models <= TD_DNN_MANY_MAX_MODELS,
              "%s: NULL argument or more than %d models", fn, TD_DNN_MANY_MAX_MODELS);
-  std::vector<MlpOpt> opt;
-  for (int m = 0; m < num_models; ++m) opt.push_back({kUpdRmsprop, lr_host[m], rho_host[m], 0.0, eps_host[m], 0});
-  opt.resize(std::max(num_models, 1), {kUpdRmsprop, 0.0, 0.0, 0.0, 0.0, 0});
+  const std::vector<MlpOpt> opt = mlp_opts<float>(kUpdRmsprop, num_models, lr_host, rho_host, nullptr, eps_host,
+                                                  nullptr);
   const ManyCall mc = {num_models, rows_used_host, params_dev_host, state_dev_host, opt.data(), shuffle_seed_host};
   return mlp_train_many(h, fn, a, epochs, mc, stats_dev);
 }
@@ -1440,19 +1465,15 @@ int td_clf_train_many(td_handle* h, const float* x_dev, int64_t ldx, const float
                       const double* lr_host, const double* beta1_host, const double* beta2_host,
                       const double* eps_host, const int64_t* step0_host, const int64_t* shuffle_seed_host,
                       double* stats_dev) {
-  const MlpCall a = {{x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host, num_files,
-                     input_offset, nullptr, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0, true};
+  const MlpCall a = mlp_call({x_dev, ldx, c, pre, post}, {x2_dev, ldx2, c2, pre2, post2}, file_offsets_host,
+                             num_files, input_offset, nullptr, y_dev, ldy, d, hidden_host, num_hidden, batch_rows, 0,
+                             true);
   const char* fn = "td_clf_train_many";
   TD_REQUIRE(h, num_models <= TD_DNN_MANY_MAX_MODELS, "%s: more than %d models", fn, TD_DNN_MANY_MAX_MODELS);
-  // score only: the optimizer's arrays are not read
-  const int rule = update ? kUpdAdam : kUpdNone;
   TD_REQUIRE(h, !update || (lr_host && beta1_host && beta2_host && eps_host && step0_host), "%s: NULL argument", fn);
-  std::vector<MlpOpt> opt;
-  for (int m = 0; m < num_models; ++m) {
-    if (update) opt.push_back({rule, lr_host[m], beta1_host[m], beta2_host[m], eps_host[m], step0_host[m]});
-    else opt.push_back({rule, 0.0, 0.0, 0.0, 0.0, 0});
-  }
-  opt.resize(std::max(num_models, 1), {rule, 0.0, 0.0, 0.0, 0.0, 0});
+  // score only: the optimizer's arrays are not read
+  const std::vector<MlpOpt> opt = mlp_opts<double>(update ? kUpdAdam : kUpdNone, num_models, update ? lr_host : nullptr,
+                                                   beta1_host, beta2_host, eps_host, step0_host);
   const ManyCall mc = {num_models, rows_used_host, params_dev_host, state_dev_host, opt.data(), shuffle_seed_host};
   return mlp_train_many(h, fn, a, epochs, mc, stats_dev);
 }

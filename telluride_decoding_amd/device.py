@@ -1212,6 +1212,44 @@ def mlpc_forward(x, x2, file_offsets, pre, post, pre2, post2, hidden, d, params,
 DNN_MANY_MAX_MODELS = 64
 
 
+def _train_many(who, fn, h, x, x2, y, context, file_offsets, input_offset, hidden, params, per_model, rows_used,
+                shuffle_seeds, batch_rows, epochs, mode, nstat, settings):
+  """What dnn_train_many and clf_train_many share: the per-model lists checked against len(params), then one call of
+  h.lib.<fn> (looked up here, at call time) per DNN_MANY_MAX_MODELS models -- the shared arguments, `mode` (the
+  loss or the update flag), the chunk's rows_used and parameter pointers, settings(m0, m1) (the family's own
+  arguments of models m0 .. m1: state pointers and optimizer arrays, as ctypes objects that own their memory), its seeds and its zeroed stats buffer
+  [models, epochs, most steps, nstat] -- and every model's [epochs, its steps, nstat] slice of it."""
+  n_models, epochs, batch_rows = len(params), int(epochs), int(batch_rows)
+  seeds = [None] * n_models if shuffle_seeds is None else list(shuffle_seeds)
+  used_all = np.ascontiguousarray(rows_used, dtype=np.int64).reshape(n_models, -1)
+  if any(v is None or len(v) != n_models for v in [seeds] + list(per_model)):
+    raise ValueError('%s: %d models, but a per-model argument of another length' % (who, n_models))
+  head, net, keep = _mlp_views(h, x, x2, context, file_offsets, input_offset, hidden)
+  if used_all.shape[1] != len(keep[0]) - 1:
+    raise ValueError('%s: rows_used has %d files, the recordings %d' % (who, used_all.shape[1], len(keep[0]) - 1))
+  out = []
+  cap = max(1, int(DNN_MANY_MAX_MODELS))
+  for m0 in range(0, n_models, cap):
+    m1 = min(m0 + cap, n_models)
+    n = m1 - m0
+    used, used_p = _lib.i64_array(used_all[m0:m1])
+    steps = [-(-int(u.sum()) // batch_rows) if batch_rows > 0 else 0 for u in used]
+    stats = h.zeros((n, max(epochs, 0), max(steps + [0]), nstat), 'float64')
+    seed, seed_p = _lib.i64_array([-1 if s is None else int(s) for s in seeds[m0:m1]])
+    h.check(getattr(h.lib, fn)(*head, _ptr(y), y.stride(0), int(y.shape[1]), *net, batch_rows, epochs, mode, n, used_p,
+                               _device_pointers(params[m0:m1]), *settings(m0, m1), seed_p, _ptr(stats)))
+    out += [stats[i, :, :steps[i]] for i in range(n)]
+  return out
+
+
+def _device_pointers(tensors):
+  return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _c_array(ctype, values):
+  return (ctype * len(values))(*[float(v) for v in values])
+
+
 def dnn_train_many(x, y, file_offsets, pre, post, hidden, params, states, batch_rows, epochs, lrs, rhos, epss,
                    rows_used, input_offset=0, shuffle_seeds=None, handle=None, loss='mse'):
   """mlp_train for many regressors of one architecture at once (td_dnn_train_many): params[m] / states[m] are model
@@ -1221,31 +1259,12 @@ def dnn_train_many(x, y, file_offsets, pre, post, hidden, params, states, batch_
   DNN_MANY_MAX_MODELS models go through several calls."""
   h = handle or default_handle()
   code = _mlp_loss(loss)
-  nstat = 7 if code else 6
-  n_models, epochs, batch_rows = len(params), int(epochs), int(batch_rows)
-  seeds = [None] * n_models if shuffle_seeds is None else list(shuffle_seeds)
-  used_all = np.ascontiguousarray(rows_used, dtype=np.int64).reshape(n_models, -1)
-  if not (len(states) == len(lrs) == len(rhos) == len(epss) == len(seeds) == n_models):
-    raise ValueError('dnn_train_many: %d models, but a per-model argument of another length' % n_models)
-  head, net, keep = _mlp_views(h, x, None, (pre, post), file_offsets, input_offset, hidden)
-  if used_all.shape[1] != len(keep[0]) - 1:
-    raise ValueError('dnn_train_many: rows_used has %d files, the recordings %d' % (used_all.shape[1], len(keep[0]) - 1))
-  out = []
-  cap = max(1, int(DNN_MANY_MAX_MODELS))
-  for m0 in range(0, n_models, cap):
-    m1 = min(m0 + cap, n_models)
-    n = m1 - m0
-    used, used_p = _lib.i64_array(used_all[m0:m1])
-    steps = [-(-int(u.sum()) // batch_rows) if batch_rows > 0 else 0 for u in used]
-    stats = h.zeros((n, max(epochs, 0), max(steps + [0]), nstat), 'float64')
-    par = (ctypes.c_void_p * n)(*[p.data_ptr() for p in params[m0:m1]])
-    sta = (ctypes.c_void_p * n)(*[s.data_ptr() for s in states[m0:m1]])
-    f32 = lambda values: (ctypes.c_float * n)(*[float(v) for v in values[m0:m1]])
-    seed, seed_p = _lib.i64_array([-1 if s is None else int(s) for s in seeds[m0:m1]])
-    h.check(h.lib.td_dnn_train_many(*head, _ptr(y), y.stride(0), int(y.shape[1]), *net, batch_rows, epochs, code, n,
-                                    used_p, par, sta, f32(lrs), f32(rhos), f32(epss), seed_p, _ptr(stats)))
-    out += [stats[i, :, :steps[i]] for i in range(n)]
-  return out
+
+  def settings(m0, m1):
+    return [_device_pointers(states[m0:m1])] + [_c_array(ctypes.c_float, v[m0:m1]) for v in (lrs, rhos, epss)]
+  return _train_many('dnn_train_many', 'td_dnn_train_many', h, x, None, y, (pre, post), file_offsets, input_offset,
+                     hidden, params, [states, lrs, rhos, epss], rows_used, shuffle_seeds, batch_rows, epochs, code,
+                     7 if code else 6, settings)
 
 
 def clf_train_many(x, x2, y, file_offsets, pre, post, pre2, post2, hidden, params, states, batch_rows, epochs,
@@ -1259,33 +1278,13 @@ def clf_train_many(x, x2, y, file_offsets, pre, post, pre2, post2, hidden, param
   DNN_MANY_MAX_MODELS models go through several calls."""
   h = handle or default_handle()
   _check_x2(x, x2)
-  n_models, epochs, batch_rows = len(params), int(epochs), int(batch_rows)
-  seeds = [None] * n_models if shuffle_seeds is None else list(shuffle_seeds)
-  used_all = np.ascontiguousarray(rows_used, dtype=np.int64).reshape(n_models, -1)
-  per_model = [seeds] + ([states, lrs, beta1s, beta2s, epss, step0s] if update else [])
-  if any(v is None or len(v) != n_models for v in per_model):
-    raise ValueError('clf_train_many: %d models, but a per-model argument of another length' % n_models)
-  head, net, keep = _mlp_views(h, x, x2, (pre, post, pre2, post2), file_offsets, input_offset, hidden)
-  if used_all.shape[1] != len(keep[0]) - 1:
-    raise ValueError('clf_train_many: rows_used has %d files, the recordings %d' % (used_all.shape[1], len(keep[0]) - 1))
-  out = []
-  cap = max(1, int(DNN_MANY_MAX_MODELS))
-  for m0 in range(0, n_models, cap):
-    m1 = min(m0 + cap, n_models)
-    n = m1 - m0
-    used, used_p = _lib.i64_array(used_all[m0:m1])
-    steps = [-(-int(u.sum()) // batch_rows) if batch_rows > 0 else 0 for u in used]
-    stats = h.zeros((n, max(epochs, 0), max(steps + [0]), 6), 'float64')
-    par = (ctypes.c_void_p * n)(*[p.data_ptr() for p in params[m0:m1]])
-    sta, settings, step0_p = None, [None] * 4, None          # scoring reads none of them
-    if update:
-      sta = (ctypes.c_void_p * n)(*[s.data_ptr() for s in states[m0:m1]])
-      settings = [(ctypes.c_double * n)(*[float(v) for v in values[m0:m1]])
-                  for values in (lrs, beta1s, beta2s, epss)]
-      step0, step0_p = _lib.i64_array([int(v) for v in step0s[m0:m1]])
-    seed, seed_p = _lib.i64_array([-1 if s is None else int(s) for s in seeds[m0:m1]])
-    h.check(h.lib.td_clf_train_many(*head, _ptr(y), y.stride(0), int(y.shape[1]), *net, batch_rows, epochs,
-                                    1 if update else 0, n, used_p, par, sta, *settings, step0_p,
-                                    seed_p, _ptr(stats)))
-    out += [stats[i, :, :steps[i]] for i in range(n)]
-  return out
+
+  def settings(m0, m1):
+    if not update:
+      return [None] * 6                                      # scoring reads none of them
+    return ([_device_pointers(states[m0:m1])] +
+            [_c_array(ctypes.c_double, v[m0:m1]) for v in (lrs, beta1s, beta2s, epss)] +
+            [(ctypes.c_int64 * (m1 - m0))(*[int(v) for v in step0s[m0:m1]])])
+  return _train_many('clf_train_many', 'td_clf_train_many', h, x, x2, y, (pre, post, pre2, post2), file_offsets,
+                     input_offset, hidden, params, [states, lrs, beta1s, beta2s, epss, step0s] if update else [],
+                     rows_used, shuffle_seeds, batch_rows, epochs, 1 if update else 0, 6, settings)

@@ -227,9 +227,7 @@ def jackknife_over_regularizations(dataset, regularization_list=None, rank=0, wo
     st.unpack(table[i].contiguous(), 1, zipped[i])
     stats.append(st)
   # 3-4. folds of this rank
-  fold_list = list(range(n_files)) if folds is None else sorted(set(int(f) for f in folds))
-  if not fold_list or fold_list[0] < 0 or fold_list[-1] >= n_files:
-    raise ValueError('folds must name files of the dataset (0..%d), not %s' % (n_files - 1, folds))
+  fold_list = _fold_list(dataset, folds)
   my_folds = distributed.split_round_robin(fold_list, rank, world_size)
   n_lam, d = len(lambdas), dataset.d
   # (the cycled window sums need windows that are whole blocks of >= 32 frames: a divisor of the batch size in [32, 4096])
@@ -527,6 +525,87 @@ def _subset(dataset, files):
                             dataset.pre2, dataset.post2, dataset.input_offset)
 
 
+def _fold_list(dataset, folds):
+  """The held-out files of a jackknife: every file, or the distinct entries of `folds` in file order."""
+  n_files = len(dataset.files)
+  fold_list = list(range(n_files)) if folds is None else sorted(set(int(f) for f in folds))
+  if not fold_list or fold_list[0] < 0 or fold_list[-1] >= n_files:
+    raise ValueError('folds must name files of the dataset (0..%d), not %s' % (n_files - 1, folds))
+  return fold_list
+
+
+def _score_each(dataset, fold_list, models):
+  """models [learning rate][fold] -> each one's evaluate on a Dataset of its held-out file alone."""
+  scores = [[] for _ in models]
+  for fi, f in enumerate(fold_list):
+    held = _subset(dataset, [f])
+    for row, out in zip(models, scores):
+      out.append(row[fi].evaluate(held))
+  return scores
+
+
+def _jackknife_mlp(dataset, make, learning_rates, epochs, shuffle_seed, folds, test_metric, metrics, route, route_key,
+                   score_many=None):
+  """What jackknife_dnn and jackknife_classifier share: the checks, one model of make(learning rate) per (learning
+  rate, held-out file), the batched route (one brain_model.fit_many) or 'per_fold' (one fit after another on a Dataset
+  of the fold's files), and the results dictionary.  LAST_SWEEP[route_key] says which route ran.
+  score_many(dataset, fold_list, models) -> score dictionaries [learning rate][fold]: with it, scoring is part of the
+  route -- the batched route calls it inside the try that falls back on MemoryError, and 'per_fold' scores each model
+  by its own evaluate right after its fit.  None: every model is scored after either route (_score_each)."""
+  from telluride_decoding_amd import brain_model
+  if test_metric not in metrics:
+    raise ValueError('Could not find metric %s in results %s.' % (test_metric, list(metrics)))
+  if route not in ('batched', 'per_fold'):
+    raise ValueError('_route must be \'batched\' or \'per_fold\', not %r' % (route,))
+  n_files = len(dataset.files)
+  if n_files < 2:
+    raise ValueError('Need at least two files for a jackknife test.')
+  fold_list = _fold_list(dataset, folds)
+  rates = [float(lr) for lr in learning_rates]
+  if not rates:
+    raise ValueError('Need at least one learning rate.')
+
+  def build():
+    return [[make(lr) for _ in fold_list] for lr in rates]
+
+  models = build()
+  scores = None
+  if route == 'batched':
+    try:
+      flat = brain_model.fit_many([m for row in models for m in row], dataset,
+                                  held_out=[[f] for _ in rates for f in fold_list], epochs=epochs,
+                                  shuffle_seeds=shuffle_seed)
+      hist = [flat[li * len(fold_list):(li + 1) * len(fold_list)] for li in range(len(rates))]
+      if score_many is not None:
+        scores = score_many(dataset, fold_list, models)
+    except MemoryError:
+      # the scratch of a batched call did not fit; models of an earlier chunk may have trained: start again
+      route = 'per_fold'
+      models = build()
+  if route == 'per_fold':
+    hist = [[] for _ in rates]
+    scores = None if score_many is None else [[] for _ in rates]
+    for fi, f in enumerate(fold_list):
+      train = _subset(dataset, [g for g in range(n_files) if g != f])
+      held = None if score_many is None else _subset(dataset, [f])
+      for li in range(len(rates)):
+        hist[li].append(models[li][fi].fit(train, epochs=epochs, shuffle_seed=shuffle_seed))
+        if score_many is not None:
+          scores[li].append(models[li][fi].evaluate(held))
+  LAST_SWEEP[route_key] = route
+  if scores is None:
+    scores = _score_each(dataset, fold_list, models)
+  runs = np.array([[score[test_metric] for score in row] for row in scores], np.float64)
+  results = collections.OrderedDict()
+  run_mean, run_std = calculate_stats(runs)
+  for li, lr in enumerate(rates):
+    results[lr] = (float(run_mean[li]), float(run_std[li]))
+  results['all_runs'] = runs
+  results['models'] = models
+  results['history'] = [[h.history for h in row] for row in hist]
+  return results
+
+
 def jackknife_dnn(dataset, num_hidden_list=None, *, learning_rates=(1e-3,), epochs=1, loss='mse', seed=0,
                   shuffle_seed=None, folds=None, test_metric='pearson_correlation_first', _route=None):
   """The leave-one-file-out jackknife of the fully connected regressor (reference regression.jackknife_one_model
@@ -544,65 +623,13 @@ def jackknife_dnn(dataset, num_hidden_list=None, *, learning_rates=(1e-3,), epoc
   the fold's files (the same bits; what a sweep falls back to when the batched call's scratch does not fit);
   None = DNN_ROUTE.  LAST_SWEEP['dnn_route'] says which one ran."""
   from telluride_decoding_amd import brain_model
-  if test_metric not in DNN_METRICS:
-    raise ValueError('Could not find metric %s in results %s.' % (test_metric, list(DNN_METRICS)))
-  route = DNN_ROUTE if _route is None else _route
-  if route not in ('batched', 'per_fold'):
-    raise ValueError('_route must be \'batched\' or \'per_fold\', not %r' % (route,))
-  n_files = len(dataset.files)
-  if n_files < 2:
-    raise ValueError('Need at least two files for a jackknife test.')
-  fold_list = list(range(n_files)) if folds is None else sorted(set(int(f) for f in folds))
-  if not fold_list or fold_list[0] < 0 or fold_list[-1] >= n_files:
-    raise ValueError('folds must name files of the dataset (0..%d), not %s' % (n_files - 1, folds))
-  rates = [float(lr) for lr in learning_rates]
-  if not rates:
-    raise ValueError('Need at least one learning rate.')
 
-  def build():
-    grid = []
-    for lr in rates:
-      row = [brain_model.BrainModelDNN(dataset, num_hidden_list, seed=seed) for _ in fold_list]
-      for m in row:
-        m.compile(optimizer=brain_model.RMSprop(learning_rate=lr), loss=loss)
-      grid.append(row)
-    return grid
-
-  def per_fold(grid):
-    out = [[] for _ in rates]
-    for fi, f in enumerate(fold_list):
-      train = _subset(dataset, [g for g in range(n_files) if g != f])
-      for li in range(len(rates)):
-        out[li].append(grid[li][fi].fit(train, epochs=epochs, shuffle_seed=shuffle_seed))
-    return out
-
-  models = build()
-  if route == 'batched':
-    try:
-      flat = brain_model.fit_many([m for row in models for m in row], dataset,
-                                  held_out=[[f] for _ in rates for f in fold_list], epochs=epochs,
-                                  shuffle_seeds=shuffle_seed)
-      hist = [flat[li * len(fold_list):(li + 1) * len(fold_list)] for li in range(len(rates))]
-    except MemoryError:
-      # the scratch of the batched call did not fit; models of an earlier chunk may have trained: start again
-      route = 'per_fold'
-      models = build()
-  if route == 'per_fold':
-    hist = per_fold(models)
-  LAST_SWEEP['dnn_route'] = route
-  runs = np.zeros((len(rates), len(fold_list)))
-  for fi, f in enumerate(fold_list):
-    held = _subset(dataset, [f])
-    for li in range(len(rates)):
-      runs[li, fi] = models[li][fi].evaluate(held)[test_metric]
-  results = collections.OrderedDict()
-  run_mean, run_std = calculate_stats(runs)
-  for li, lr in enumerate(rates):
-    results[lr] = (float(run_mean[li]), float(run_std[li]))
-  results['all_runs'] = runs
-  results['models'] = models
-  results['history'] = [[h.history for h in row] for row in hist]
-  return results
+  def make(lr):
+    model = brain_model.BrainModelDNN(dataset, num_hidden_list, seed=seed)
+    model.compile(optimizer=brain_model.RMSprop(learning_rate=lr), loss=loss)
+    return model
+  return _jackknife_mlp(dataset, make, learning_rates, epochs, shuffle_seed, folds, test_metric, DNN_METRICS,
+                        DNN_ROUTE if _route is None else _route, 'dnn_route')
 
 
 # The route jackknife_classifier takes without _route, as DNN_ROUTE (DESIGN section 19)
@@ -626,66 +653,18 @@ def jackknife_classifier(dataset, num_hidden_list=None, *, learning_rates=(1e-3,
   another on Datasets of the fold's files (the same bits; what a sweep falls back to when a batched call's scratch
   does not fit); None = CLASSIFIER_ROUTE.  LAST_SWEEP['classifier_route'] says which one ran."""
   from telluride_decoding_amd import brain_model
-  if test_metric not in CLASSIFIER_METRICS:
-    raise ValueError('Could not find metric %s in results %s.' % (test_metric, list(CLASSIFIER_METRICS)))
-  route = CLASSIFIER_ROUTE if _route is None else _route
-  if route not in ('batched', 'per_fold'):
-    raise ValueError('_route must be \'batched\' or \'per_fold\', not %r' % (route,))
-  n_files = len(dataset.files)
-  if n_files < 2:
-    raise ValueError('Need at least two files for a jackknife test.')
-  fold_list = list(range(n_files)) if folds is None else sorted(set(int(f) for f in folds))
-  if not fold_list or fold_list[0] < 0 or fold_list[-1] >= n_files:
-    raise ValueError('folds must name files of the dataset (0..%d), not %s' % (n_files - 1, folds))
-  rates = [float(lr) for lr in learning_rates]
-  if not rates:
-    raise ValueError('Need at least one learning rate.')
 
-  def build():
-    grid = []
-    for lr in rates:
-      row = [brain_model.BrainModelClassifier(dataset, num_hidden_list, seed=seed) for _ in fold_list]
-      for m in row:
-        m.compile(optimizer=brain_model.Adam(learning_rate=lr))
-      grid.append(row)
-    return grid
+  def make(lr):
+    model = brain_model.BrainModelClassifier(dataset, num_hidden_list, seed=seed)
+    model.compile(optimizer=brain_model.Adam(learning_rate=lr))
+    return model
 
-  def rows(flat):
-    return [flat[li * len(fold_list):(li + 1) * len(fold_list)] for li in range(len(rates))]
-
-  def per_fold(grid):
-    hist, scores = [[] for _ in rates], [[] for _ in rates]
-    for fi, f in enumerate(fold_list):
-      train = _subset(dataset, [g for g in range(n_files) if g != f])
-      held = _subset(dataset, [f])
-      for li in range(len(rates)):
-        hist[li].append(grid[li][fi].fit(train, epochs=epochs, shuffle_seed=shuffle_seed))
-        scores[li].append(grid[li][fi].evaluate(held))
-    return hist, scores
-
-  models = build()
-  if route == 'batched':
-    try:
-      flat = [m for row in models for m in row]
-      hist = rows(brain_model.fit_many(flat, dataset, held_out=[[f] for _ in rates for f in fold_list],
-                                       epochs=epochs, shuffle_seeds=shuffle_seed))
-      scores = rows(brain_model.evaluate_many(flat, dataset, files=[[f] for _ in rates for f in fold_list]))
-    except MemoryError:
-      # the scratch of a batched call did not fit; models of an earlier chunk may have trained: start again
-      route = 'per_fold'
-      models = build()
-  if route == 'per_fold':
-    hist, scores = per_fold(models)
-  LAST_SWEEP['classifier_route'] = route
-  runs = np.array([[score[test_metric] for score in row] for row in scores], np.float64)
-  results = collections.OrderedDict()
-  run_mean, run_std = calculate_stats(runs)
-  for li, lr in enumerate(rates):
-    results[lr] = (float(run_mean[li]), float(run_std[li]))
-  results['all_runs'] = runs
-  results['models'] = models
-  results['history'] = [[h.history for h in row] for row in hist]
-  return results
+  def score_many(dataset, fold_list, models):
+    flat = brain_model.evaluate_many([m for row in models for m in row], dataset,
+                                     files=[[f] for _ in models for f in fold_list])
+    return [flat[li * len(fold_list):(li + 1) * len(fold_list)] for li in range(len(models))]
+  return _jackknife_mlp(dataset, make, learning_rates, epochs, shuffle_seed, folds, test_metric, CLASSIFIER_METRICS,
+                        CLASSIFIER_ROUTE if _route is None else _route, 'classifier_route', score_many)
 
 
 def jackknife_one_model(dataset, regularization_lambda, max_test_count=-1, test_name='telluride4',
