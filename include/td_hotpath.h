@@ -736,6 +736,21 @@ int td_tfrecord_encode(td_handle* h, const uint8_t* template_host, int stride, i
  * staged 0 (group 0): the smallest such group does not fit, one workgroup per record writes it directly.  lanes:
  * the lanes that share one record's CRC.  Read-only; no handle. */
 int td_tfrecord_route(int stride, int* staged, int* group, int* lanes);
+/* The way back: checks and unpacks a TFRecord file image on the device, image_dev [frames * stride] bytes (16-byte
+ * aligned), every record `stride` bytes with the same bytes outside its float payloads and its data CRC.  One pass:
+ * (1) skeleton: every record against template_host [stride] (the first record with payloads and data CRC zeroed)
+ * wherever mask_host [stride] is non-zero (length, length CRC, protobuf tags, names and lengths; zero on every float
+ * payload and on the last 4 bytes); (2) the masked CRC-32C of bytes [12, stride - 4) of every record against the
+ * stored one; (3) output o: the count_host[o] little-endian float32 at byte offset_host[o] of record r go, bit for
+ * bit, to dst_dev[o][r * ld_host[o] + col_host[o] + e] (the caller folds the file's first row into dst_dev[o]; a
+ * payload may serve several outputs).  0 <= num_outputs <= 16.  status_dev (one int64, 8-byte aligned): -1 when
+ * every record passed, else (r << 2 | kind) of the lowest failing record r, kind 1 skeleton, 2 data CRC, skeleton
+ * first when both fail there; the same value on every call.  The outputs of a file that failed are unspecified.
+ * The routes are td_tfrecord_route's.  frames == 0: TD_OK, nothing is launched and status_dev is not written. */
+int td_tfrecord_decode(td_handle* h, const uint8_t* image_dev, int stride, int64_t frames,
+                       const uint8_t* template_host, const uint8_t* mask_host, int num_outputs,
+                       const int* offset_host, const int* count_host, void* const* dst_dev, const int64_t* ld_host,
+                       const int* col_host, int64_t* status_dev);
 
 /* ------------------------------------------------------------------ fully connected regressor
  * brain_model.BrainModelDNN (reference brain_model.py:486-549): Dense layers z = a.W + b in float32, ReLU on

@@ -474,9 +474,20 @@ class TestBrainData(BrainData):
 class TFExampleData(BrainData):
   """An experiment whose recordings are TFRecord files of tf.train.Example frames under `data_dir`
   (reference brain_data.TFExampleData, brain_data.py:645-731), read by the dependency-free parser of
-  tfrecord.py.  `features` is {name: (width, dtype)} of the first file's first record."""
+  tfrecord.py.  `features` is {name: (width, dtype)} of the first file's first record.
+
+  decode_on_device: True -- create_dataset checks and unpacks the files on the GPU (tfrecord.dataset_from_files with
+  device=the default handle: framing, the CRC-32C of every record and the payloads in one kernel, the dataset already
+  resident for the device fast paths); False -- the host reader; None (default) -- on the GPU when there is one
+  (device.gpu_available()).  On valid files the datasets are the same bit for bit.  The one visible difference: a
+  file with a damaged record raises on the device route -- as the reference does, whose tf.data.TFRecordDataset
+  verifies every record's CRC -- where the host route, which never looks at a data CRC, reads on."""
+
+  DECODE_ON_DEVICE = None        # what decode_on_device is when it is not given
 
   def __init__(self, *args, **kwargs):
+    on_device = kwargs.pop('decode_on_device', None)
+    self.decode_on_device = self.DECODE_ON_DEVICE if on_device is None else on_device
     super(TFExampleData, self).__init__(*args, **kwargs)
     self.all_files()             # find the files and the feature shapes now: a bad data_dir fails here
 
@@ -531,13 +542,21 @@ class TFExampleData(BrainData):
       raise ValueError('No files to process in mode %s from directory %s: %s' %
                        (mode, self.data_dir, self.all_files()))
     ctx = temporal_context
+    on_device = self.decode_on_device
+    from telluride_decoding_amd import _lib, device
+    if on_device is None:
+      try:
+        on_device = device.gpu_available()
+      except _lib.HotPathUnavailable:        # (the library is not built: the host reader needs none)
+        on_device = False
     ds = tfrecord.dataset_from_files(
         names, self.in1_fields, self.out_field, in2_fields=self.in2_fields or None,
         attended_field=self.attended_field or None, batch_size=self.final_batch_size,
         pre_context=self.in1_pre_context if ctx else 0, post_context=self.in1_post_context if ctx else 0,
         in2_pre_context=self.in2_pre_context if ctx else 0,
         in2_post_context=self.in2_post_context if ctx else 0,
-        input_offset=self.input_offset if ctx else 0)
+        input_offset=self.input_offset if ctx else 0,
+        device=device.default_handle() if on_device else None)
     ds.mixup_batch = bool(mixup_batch)
     return ds
 
@@ -546,9 +565,11 @@ def create_brain_dataset(data_type, in_fields, out_field, frame_rate, pre_contex
                          in2_fields=None, in2_pre_context=0, in2_post_context=0, input_offset=0,
                          attended_field=None, initial_batch_size=1000000, final_batch_size=1000,
                          repeat_count=1, shuffle_buffer_size=1000, data_dir=None, data_pattern='',
-                         train_file_pattern=None, validate_file_pattern=None, test_file_pattern=None):
+                         train_file_pattern=None, validate_file_pattern=None, test_file_pattern=None,
+                         decode_on_device=None):
   """Any of the BrainData classes by name (reference brain_data.py:959-1040): 'tfrecord', 'tfrecords' or
-  'tfexample' -> TFExampleData, 'test' -> TestBrainData."""
+  'tfexample' -> TFExampleData, 'test' -> TestBrainData.  decode_on_device: TFExampleData's (None: read and verify
+  the files on the GPU when there is one; a damaged record then raises, as in the reference)."""
   if not isinstance(data_type, str):
     raise TypeError('create_brain_dataset type must be a string.')
   if frame_rate <= 0:
@@ -561,7 +582,8 @@ def create_brain_dataset(data_type, in_fields, out_field, frame_rate, pre_contex
                 train_file_pattern=train_file_pattern, validate_file_pattern=validate_file_pattern,
                 test_file_pattern=test_file_pattern)
   if data_type in ('tfrecord', 'tfrecords', 'tfexample'):
-    return TFExampleData(in_fields, out_field, frame_rate, attended_field=attended_field, **kwargs)
+    return TFExampleData(in_fields, out_field, frame_rate, attended_field=attended_field,
+                         decode_on_device=decode_on_device, **kwargs)
   if data_type == 'test':
     return TestBrainData(in_fields, out_field, frame_rate, **kwargs)
   raise TypeError('create_brain_dataset unknown data type %s' % data_type)

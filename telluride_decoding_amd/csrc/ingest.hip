@@ -278,6 +278,207 @@ void encode_route(int stride, int* group, int* lanes) {
   *lanes = l;
 }
 
+// ---------------------------------------------------------------- decoder
+// The encoder's mirror: one pass over a file image checks every record's skeleton against the template under a
+// byte mask, its data CRC, and scatters the float payloads into the caller's tensors.  Failures meet in one
+// 64-bit word by atomicMin over (record << 2 | kind): a minimum does not depend on the order of its operands, so
+// the status is the same on every call.  Skeleton (1) sorts below CRC (2) at the same record.
+constexpr unsigned kBadSkeleton = 1u, kBadCrc = 2u;
+constexpr unsigned kNoneBad = 0xffffffffu;
+constexpr int kDecStageOffset = 6144 + 16;   // tables, the partial registers, the workgroup's lowest failure
+
+struct DecOutput {
+  float* dst;         // row 0 of the file, column `col` already added
+  long long ld;       // elements between rows
+  int offset, count;  // byte offset of the payload in the record; floats per row
+};
+struct DecParams {
+  DecOutput o[kMaxFeatures];
+  int num, stride;
+  long long frames;
+};
+
+// The 32 bits at byte `at` of a word array (any alignment): two aligned words, funnel-shifted.  Reads word
+// (at >> 2) + 1 only when `at` is not a multiple of 4.
+template <typename Words>
+__device__ __forceinline__ uint32_t bits_at(Words words, long long at) {
+  const long long w = at >> 2;
+  const unsigned sh = 8u * (unsigned)(at & 3);
+  const uint32_t lo = words[w];
+  if (sh == 0) return lo;
+  return (lo >> sh) | (words[w + 1] << (32u - sh));
+}
+
+__device__ __forceinline__ void report_bad(unsigned long long* status, long long record, unsigned kind) {
+  atomicMin(status, ((unsigned long long)record << 2) | kind);
+}
+
+// tabs: kTabWords of tables, the template four times over as `stride` words, the mask likewise.
+__global__ __launch_bounds__(kThreads) void decode_staged_kernel(DecParams p, const uint32_t* __restrict__ tabs,
+                                                                 int group, int lanes, int piece,
+                                                                 const uint8_t* __restrict__ image,
+                                                                 unsigned long long* __restrict__ status) {
+  extern __shared__ uint4 smem4[];
+  uint32_t* crc_tab = reinterpret_cast<uint32_t*>(smem4);
+  const uint32_t* adv = crc_tab + 256;
+  uint32_t* part = crc_tab + kTabWords;                         // [kThreads]
+  unsigned* bad = part + kThreads;                              // (local record << 2 | kind) of the lowest failure
+  uint32_t* stage32 = crc_tab + (kDecStageOffset >> 2);
+  const uint8_t* stage = reinterpret_cast<const uint8_t*>(stage32);
+  const int tid = threadIdx.x;
+  const int stride = p.stride;
+  const long long r0 = (long long)blockIdx.x * group;
+  const int nrec = (int)(p.frames - r0 < group ? p.frames - r0 : group);
+  const int nbytes = nrec * stride;
+  const uint32_t* tmpl4 = tabs + kTabWords;
+  const uint32_t* mask4 = tmpl4 + stride;
+
+  for (int i = tid; i < kTabWords; i += kThreads) crc_tab[i] = tabs[i];
+  if (tid == 0) *bad = kNoneBad;
+  const uint8_t* g = image + r0 * stride;                       // 16-byte aligned: group * stride % 16 == 0
+  const int n16 = nbytes >> 4;
+  for (int i = tid; i < n16; i += kThreads) smem4[(kDecStageOffset >> 4) + i] = reinterpret_cast<const uint4*>(g)[i];
+  // the tail of the file's last group, as whole words of zero-padded bytes (nothing past the image is read)
+  for (int w = (n16 << 2) + tid; 4 * w < nbytes; w += kThreads) {
+    uint32_t v = 0;
+    for (int j = 0; j < 4 && 4 * w + j < nbytes; ++j) v |= (uint32_t)g[4 * w + j] << (8 * j);
+    stage32[w] = v;
+  }
+  __syncthreads();
+
+  // skeleton: word w of the group is word (w0 + w) mod stride of the repeated template
+  const int nwords = (nbytes + 3) >> 2;
+  const unsigned w0 = (unsigned)((((unsigned long long)r0 * (unsigned)stride) >> 2) % (unsigned)stride);
+  for (int w = tid; w < nwords; w += kThreads) {
+    const unsigned t = (w0 + (unsigned)w) % (unsigned)stride;
+    uint32_t diff = (stage32[w] ^ tmpl4[t]) & mask4[t];
+    if (4 * w + 4 > nbytes) diff &= 0xffffffffu >> (8 * (4 * w + 4 - nbytes));
+    for (int j = 0; diff; ++j, diff >>= 8)                      // (a word may straddle two records)
+      if (diff & 0xff) atomicMin(bad, ((unsigned)((4 * w + j) / stride) << 2) | kBadSkeleton);
+  }
+
+  // data CRC: the encoder's split
+  const int rec = tid / lanes, k = tid - rec * lanes;
+  const int len = stride - 16;
+  if (rec < nrec) {
+    const int first = len - (lanes - 1) * piece;
+    const int begin = k == 0 ? 0 : first + (k - 1) * piece;
+    const int n = k == 0 ? first : piece;
+    const uint8_t* src = stage + rec * stride + 12 + begin;
+    uint32_t c = k == 0 ? 0xffffffffu : 0u;
+    for (int i = 0; i < n; ++i) c = crc_tab[(c ^ src[i]) & 0xff] ^ (c >> 8);
+    part[tid] = c;
+  }
+  __syncthreads();
+  if (rec < nrec && k == 0) {
+    uint32_t c = part[tid];
+    for (int j = 1; j < lanes; ++j) c = crc_advance(adv, c) ^ part[tid + j];
+    if (crc_mask(c) != bits_at(stage32, (long long)rec * stride + stride - 4))
+      atomicMin(bad, ((unsigned)rec << 2) | kBadCrc);
+  }
+
+  // payloads: consecutive lanes, consecutive floats of the group's rows
+  for (int f = 0; f < p.num; ++f) {
+    const DecOutput& O = p.o[f];
+    const int total = nrec * O.count;
+    for (int idx = tid; idx < total; idx += kThreads) {
+      const int r = idx / O.count, e = idx - r * O.count;
+      const uint32_t bits = bits_at(stage32, (long long)r * stride + O.offset + 4 * e);
+      reinterpret_cast<uint32_t*>(O.dst)[(r0 + r) * O.ld + e] = bits;
+    }
+  }
+  __syncthreads();
+  if (tid == 0 && *bad != kNoneBad) report_bad(status, r0 + (*bad >> 2), *bad & 3u);
+}
+
+// CRC register after the n bytes at image + at: single bytes up to a word boundary, aligned words, single bytes.
+__device__ __forceinline__ uint32_t crc_span(const uint32_t* crc_tab, const uint8_t* __restrict__ image, long long at,
+                                             int n, uint32_t c) {
+  int i = 0;
+  for (; i < n && ((at + i) & 3); ++i) c = crc_tab[(c ^ image[at + i]) & 0xff] ^ (c >> 8);
+  const uint32_t* words = reinterpret_cast<const uint32_t*>(image + at + i);
+  for (int w = 0; i + 4 <= n; ++w, i += 4) {
+    uint32_t v = words[w];
+    for (int j = 0; j < 4; ++j, v >>= 8) c = crc_tab[(c ^ v) & 0xff] ^ (c >> 8);
+  }
+  for (; i < n; ++i) c = crc_tab[(c ^ image[at + i]) & 0xff] ^ (c >> 8);
+  return c;
+}
+
+// One workgroup per record, aligned words straight from the image.
+__global__ __launch_bounds__(kThreads) void decode_large_kernel(DecParams p, const uint32_t* __restrict__ tabs,
+                                                                int piece, const uint8_t* __restrict__ image,
+                                                                unsigned long long* __restrict__ status) {
+  __shared__ uint32_t crc_tab[kTabWords];
+  __shared__ uint32_t part[kThreads];
+  __shared__ unsigned bad;
+  const uint32_t* adv = crc_tab + 256;
+  const int tid = threadIdx.x;
+  const int stride = p.stride;
+  const long long r = blockIdx.x;
+  const uint32_t* tmpl4 = tabs + kTabWords;
+  const uint32_t* mask4 = tmpl4 + stride;
+  const uint8_t* tmpl = reinterpret_cast<const uint8_t*>(tmpl4);     // (the first of the four copies)
+  const uint8_t* mask = reinterpret_cast<const uint8_t*>(mask4);
+  const uint32_t* image32 = reinterpret_cast<const uint32_t*>(image);
+  for (int i = tid; i < kTabWords; i += kThreads) crc_tab[i] = tabs[i];
+  if (tid == 0) bad = kNoneBad;
+  __syncthreads();
+
+  // skeleton: the record's whole aligned words of the file, single bytes at both ends
+  const long long base = r * stride, end = base + stride;
+  const long long a0 = (base + 3) & ~3ll;                       // (< end: stride >= 17)
+  const int head = (int)(a0 - base);
+  const int nw = (int)((end - a0) >> 2);
+  const unsigned t0 = (unsigned)((unsigned long long)(a0 >> 2) % (unsigned)stride);
+  bool differs = false;
+  if (tid < head) differs = ((image[base + tid] ^ tmpl[tid]) & mask[tid]) != 0;
+  for (int w = tid; w < nw; w += kThreads) {
+    const unsigned t = (t0 + (unsigned)w) % (unsigned)stride;
+    differs |= ((image32[(a0 >> 2) + w] ^ tmpl4[t]) & mask4[t]) != 0;
+  }
+  const int tail0 = head + 4 * nw;
+  if (tail0 + tid < stride) differs |= ((image[base + tail0 + tid] ^ tmpl[tail0 + tid]) & mask[tail0 + tid]) != 0;
+  if (differs) atomicMin(&bad, kBadSkeleton);
+
+  const int len = stride - 16;
+  const int first = len - (kThreads - 1) * piece;
+  const int begin = tid == 0 ? 0 : first + (tid - 1) * piece;
+  part[tid] = crc_span(crc_tab, image, base + 12 + begin, tid == 0 ? first : piece, tid == 0 ? 0xffffffffu : 0u);
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t c = part[0];
+    for (int j = 1; j < kThreads; ++j) c = crc_advance(adv, c) ^ part[j];
+    uint32_t stored = 0;
+    for (int j = 0; j < 4; ++j) stored |= (uint32_t)image[end - 4 + j] << (8 * j);
+    if (crc_mask(c) != stored) atomicMin(&bad, kBadCrc);
+  }
+
+  for (int f = 0; f < p.num; ++f) {
+    const DecOutput& O = p.o[f];
+    uint32_t* dst = reinterpret_cast<uint32_t*>(O.dst) + r * O.ld;
+    for (int e = tid; e < O.count; e += kThreads) dst[e] = bits_at(image32, base + O.offset + 4ll * e);
+  }
+  __syncthreads();
+  if (tid == 0 && bad != kNoneBad) report_bad(status, r, bad);
+}
+
+// The decoder's table for records of `stride` bytes whose CRC pieces are `piece` bytes: the CRC byte table, the
+// advance table, then the template and the mask, each four times over as `stride` words.  Host only.
+void decode_table(const uint8_t* template_host, const uint8_t* mask_host, int stride, int piece,
+                  std::vector<uint32_t>* tab) {
+  tab->assign((size_t)kTabWords + 2 * (size_t)stride, 0u);
+  CrcTables& ct = crc_tables();
+  memcpy(tab->data(), ct.byte_tab, sizeof(ct.byte_tab));
+  memcpy(tab->data() + 256, ct.advance_by(piece).data(), 1024 * sizeof(uint32_t));
+  uint8_t* t4 = reinterpret_cast<uint8_t*>(tab->data() + kTabWords);
+  uint8_t* m4 = t4 + 4 * (size_t)stride;
+  for (int k = 0; k < 4; ++k) {
+    memcpy(t4 + (size_t)k * stride, template_host, stride);
+    for (int b = 0; b < stride; ++b) m4[(size_t)k * stride + b] = mask_host[b] ? 0xff : 0x00;
+  }
+}
+
 // ---------------------------------------------------------------- moments
 struct MomTrial {
   const void* ptr;
@@ -484,6 +685,64 @@ int td_tfrecord_encode(td_handle* h, const uint8_t* template_host, int stride, i
   } else {
     TD_REQUIRE(h, frames <= 0x7fffffffll, "td_tfrecord_encode: too many records for the large route");
     hipLaunchKernelGGL(encode_large_kernel, dim3((unsigned)frames), dim3(kThreads), 0, h->stream, p, tabs, piece, out_dev);
+  }
+  TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
+int td_tfrecord_decode(td_handle* h, const uint8_t* image_dev, int stride, int64_t frames,
+                       const uint8_t* template_host, const uint8_t* mask_host, int num_outputs,
+                       const int* offset_host, const int* count_host, void* const* dst_dev, const int64_t* ld_host,
+                       const int* col_host, int64_t* status_dev) {
+  if (!h || !template_host || !mask_host || !status_dev || (!image_dev && frames > 0) ||
+      (num_outputs > 0 && (!offset_host || !count_host || !dst_dev || !ld_host || !col_host)))
+    return td_fail(h, TD_ERR_INVALID, "td_tfrecord_decode: NULL argument");
+  TD_REQUIRE(h, stride >= 17 && stride <= (1 << 28) && frames >= 0, "td_tfrecord_decode: bad sizes");
+  TD_REQUIRE(h, num_outputs >= 0 && num_outputs <= kMaxFeatures, "td_tfrecord_decode: 0 .. %d outputs, not %d",
+             kMaxFeatures, num_outputs);
+  TD_REQUIRE(h, (reinterpret_cast<uintptr_t>(image_dev) & 15) == 0, "td_tfrecord_decode: the image must be 16-byte aligned");
+  TD_REQUIRE(h, (reinterpret_cast<uintptr_t>(status_dev) & 7) == 0, "td_tfrecord_decode: the status must be 8-byte aligned");
+  uint64_t length = 0;
+  memcpy(&length, template_host, 8);
+  TD_REQUIRE(h, length + 16 == (uint64_t)stride, "td_tfrecord_decode: the template's length field is not stride - 16");
+  DecParams p;
+  memset(&p, 0, sizeof(p));
+  p.num = num_outputs;
+  p.stride = stride;
+  p.frames = frames;
+  for (int f = 0; f < num_outputs; ++f) {
+    TD_REQUIRE(h, count_host[f] >= 1 && offset_host[f] >= 12 && (long long)offset_host[f] + 4ll * count_host[f] <= stride - 4,
+               "td_tfrecord_decode: output %d: payload [%d, +%lld) outside the record's data", f, offset_host[f],
+               4ll * count_host[f]);
+    TD_REQUIRE(h, col_host[f] >= 0 && ld_host[f] >= (long long)col_host[f] + count_host[f],
+               "td_tfrecord_decode: output %d: row stride %lld below column %d + %d floats", f, (long long)ld_host[f],
+               col_host[f], count_host[f]);
+    TD_REQUIRE(h, dst_dev[f] || frames == 0, "td_tfrecord_decode: output %d: NULL destination", f);
+    TD_REQUIRE(h, (reinterpret_cast<uintptr_t>(dst_dev[f]) & 3) == 0, "td_tfrecord_decode: output %d: misaligned destination", f);
+    p.o[f].dst = static_cast<float*>(dst_dev[f]) + col_host[f];
+    p.o[f].ld = ld_host[f];
+    p.o[f].offset = offset_host[f];
+    p.o[f].count = count_host[f];
+  }
+  int group = 0, lanes = 0;
+  encode_route(stride, &group, &lanes);
+  TD_REQUIRE(h, group > 0 || frames <= 0x7fffffffll, "td_tfrecord_decode: too many records for the large route");
+  if (frames == 0) return TD_OK;
+  const int piece = (stride - 16) / lanes;
+  std::vector<uint32_t> tab;
+  decode_table(template_host, mask_host, stride, piece, &tab);
+  const void* tab_dev = nullptr;
+  TD_TRY(td_table_upload(h, tab.data(), tab.size() * sizeof(uint32_t), &tab_dev));
+  const uint32_t* tabs = static_cast<const uint32_t*>(tab_dev);
+  unsigned long long* status = reinterpret_cast<unsigned long long*>(status_dev);
+  TD_HIP(h, hipMemsetAsync(status, 0xff, sizeof(*status), h->stream));     // -1: all clear
+  if (group > 0) {
+    const size_t lds = kDecStageOffset + (size_t)group * stride;
+    hipLaunchKernelGGL(decode_staged_kernel, dim3((unsigned)td_ceil_div(frames, group)), dim3(kThreads), lds, h->stream,
+                       p, tabs, group, lanes, piece, image_dev, status);
+  } else {
+    hipLaunchKernelGGL(decode_large_kernel, dim3((unsigned)frames), dim3(kThreads), 0, h->stream, p, tabs, piece,
+                       image_dev, status);
   }
   TD_HIP(h, hipGetLastError());
   return TD_OK;

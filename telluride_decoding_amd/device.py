@@ -1010,6 +1010,48 @@ def tfrecord_encode(template, features, frames, handle=None):
   return out
 
 
+TFRECORD_MAX_OUTPUTS = 16
+
+
+def tfrecord_decode(image, plan, outputs, handle=None, status=None):
+  """Checks the TFRecord file image `image` (device uint8, 16-byte aligned, plan['frames'] * plan['stride'] bytes)
+  and scatters its float payloads (td_tfrecord_decode).  plan: tfrecord.decode_plan of the file; outputs:
+  [(feature name, destination float32 device tensor with contiguous rows, first row, column)], at most
+  TFRECORD_MAX_OUTPUTS, a feature as often as wanted.  Returns the status, a device int64 [1] (`status`, when
+  given): -1 when every record passed, else (record << 2 | kind) of the lowest failing record, kind 1 = its bytes
+  outside the payloads differ from the first record's, 2 = its data CRC.  Nothing waits for the device here; the
+  destinations of a file that failed are unspecified."""
+  torch = _torch()
+  h = handle or default_handle()
+  stride, frames = int(plan['stride']), int(plan['frames'])
+  if image.dtype != torch.uint8 or image.dim() != 1 or not image.is_contiguous() or image.numel() < frames * stride:
+    raise ValueError('tfrecord_decode: a contiguous uint8 device image of %d bytes is needed' % (frames * stride))
+  where = {name: (offset, count) for name, offset, count in plan['layout']}
+  n = len(outputs)
+  ptrs, lds, cols, offs, counts = [], [], [], [], []
+  for name, dst, row0, col in outputs:
+    offset, count = where[name]
+    row0, col = int(row0), int(col)
+    if (dst.dim() != 2 or dst.dtype != torch.float32 or (dst.shape[1] > 1 and dst.stride(1) != 1) or row0 < 0 or
+        col < 0 or row0 + frames > dst.shape[0] or col + count > dst.shape[1]):
+      raise ValueError('tfrecord_decode: %s: rows [%d, +%d) x columns [%d, +%d) do not fit a float32 %s tensor with '
+                       'contiguous rows' % (name, row0, frames, col, count, tuple(dst.shape)))
+    ld = _row_stride(dst)
+    ptrs.append(dst.data_ptr() + 4 * row0 * ld)
+    lds.append(ld); cols.append(col); offs.append(offset); counts.append(count)
+  if status is None:
+    with torch.cuda.stream(h._stream):     # (the handle's stream need not be torch's current one)
+      status = torch.full((1,), -1, dtype=torch.int64, device=h.device)
+  ptr_p = (ctypes.c_void_p * max(n, 1))(*ptrs)
+  keep_ld, ld_p = _lib.i64_array(lds)
+  keep_col, col_p = _i32_array(cols)
+  keep_off, off_p = _i32_array(offs)
+  keep_count, count_p = _i32_array(counts)
+  h.check(h.lib.td_tfrecord_decode(h.ptr, _ptr(image), stride, frames, bytes(plan['template']), bytes(plan['mask']), n,
+                                   off_p, count_p, ptr_p, ld_p, col_p, _ptr(status)))
+  return status
+
+
 def sos_filter_plan(n_total, n_max, c, handle=None):
   """(chunk, scan levels) that sos_filter uses for files of n_total rows in all, the longest n_max, over c
   channels (td_sos_filter_plan)."""

@@ -274,6 +274,8 @@ def _read_file_regular(filename, fields):
     if key in out:
       return None
     block = np.ascontiguousarray(arr[:, 12 + start:12 + start + 4 * count])
+    if block.shape[0] == 1:
+      block = block.copy()       # (one row counts as contiguous whatever its row stride: still the file's, not 4 * count)
     out[key] = block.view('<f4').astype(np.float32, copy=False)
   return out
 
@@ -307,6 +309,102 @@ def read_file(filename, fields=None, verify=False):
     if missing:
       raise ValueError('Could not find all desired features (%s) in data (%s)' %
                        (sorted(fields), sorted(out)))
+  return out
+
+
+# ---------------------------------------------------------------- device reader
+def decode_plan(filename):
+  """What device.tfrecord_decode needs to know about a regular file -- every record as long as the first and, outside
+  its float payloads and its data CRC, the same bytes -- from its size and its first record; host only.
+  {'stride': bytes per record, 'frames': records, 'template': the first record with payloads and data CRC zeroed,
+  'mask': a byte per record byte, 1 where every record must equal the template (length, length CRC, protobuf tags,
+  names and lengths), 0 on every float payload and the last 4 bytes, 'layout': [(feature name, byte offset of its
+  payload in the record, floats)]}.  None when the file is not of that shape as far as the first record tells: too
+  short, its size no multiple of the stride, a feature that is not one packed FloatList, a feature name twice, or a
+  first record whose length CRC is wrong.  (Whether the other records keep to it is the device's skeleton check.)"""
+  size = os.path.getsize(filename)
+  if size < 16:
+    return None
+  with open(filename, 'rb') as f:
+    head = f.read(12)
+    (length,) = struct.unpack_from('<Q', head, 0)
+    stride = length + 16
+    if length == 0 or stride > (1 << 28) or size % stride:
+      return None
+    first = head + f.read(length + 4)
+  if struct.unpack_from('<I', head, 8)[0] != masked_crc32c(head[:8]):
+    return None
+  layout = _float_layout(memoryview(first)[12:12 + length])
+  if layout is None or len({k for k, _, _ in layout}) != len(layout):
+    return None
+  mask = np.ones(stride, np.uint8)
+  mask[stride - 4:] = 0
+  for _, start, count in layout:
+    mask[12 + start:12 + start + 4 * count] = 0
+  template = np.frombuffer(first, np.uint8) * mask
+  return {'stride': stride, 'frames': size // stride, 'template': template.tobytes(), 'mask': mask.tobytes(),
+          'layout': [(k, 12 + start, count) for k, start, count in layout]}
+
+
+def _upload_image(filename, size, handle, pinned=None, image=None):
+  """The file's bytes as a device uint8 tensor, through a pinned host buffer (both reused when given and large
+  enough).  Queued on torch's current stream; returns (image, pinned buffer, event after the copy)."""
+  import torch
+  if pinned is None or pinned.numel() < size:
+    pinned = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+  if image is None or image.numel() < size:
+    image = handle.empty((size,), 'uint8')
+  with open(filename, 'rb') as f:
+    got = f.readinto(memoryview(pinned.numpy())[:size])
+  if got != size:
+    raise ValueError('%s: read %d of %d bytes' % (filename, got, size))
+  image[:size].copy_(pinned[:size], non_blocking=True)
+  done = torch.cuda.Event()
+  done.record()
+  return image, pinned, done
+
+
+def _raise_missing(fields, found):
+  missing = set(fields) - set(found)
+  if missing:
+    raise ValueError('Could not find all desired features (%s) in data (%s)' % (sorted(fields), sorted(found)))
+
+
+def _device_fallback(filename, fields, handle):
+  """read_file(verify=True) on the host -- the generic parser decides what is wrong with the file and words the
+  error -- and its result uploaded."""
+  return {k: handle.to_device(v) for k, v in read_file(filename, fields, verify=True).items()}
+
+
+def read_file_device(filename, fields=None, handle=None):
+  """read_file(filename, fields, verify=True) with the framing check, the CRC-32C of every record and the unpacking
+  on the GPU (device.tfrecord_decode): {feature: device float32 [frames, width]}, the same values bit for bit, or
+  the same exception.  A record r whose data CRC is wrong raises iter_records' ValueError('%s: corrupt data CRC at
+  byte %d') with byte r * stride.  A file that is not regular (decode_plan None, or a record whose bytes outside the
+  payloads differ from the first record's) is read by read_file(verify=True) on the host and uploaded."""
+  import torch
+  from telluride_decoding_amd import device
+  h = handle or device.default_handle()
+  plan = decode_plan(filename)
+  if plan is None:
+    return _device_fallback(filename, fields, h)
+  wanted = [(k, count) for k, _, count in plan['layout'] if fields is None or k in fields]
+  with torch.cuda.stream(h._stream):
+    image, _, _ = _upload_image(filename, plan['frames'] * plan['stride'], h)
+    out = {k: h.empty((plan['frames'], count), 'float32') for k, count in wanted}
+    # (more features than one launch takes: several launches, each with all the checks, the lowest status counts)
+    n = device.TFRECORD_MAX_OUTPUTS
+    chunks = [wanted[c:c + n] for c in range(0, len(wanted), n)] or [[]]
+    status = torch.full((len(chunks),), -1, dtype=torch.int64, device=h.device)
+    for c, chunk in enumerate(chunks):
+      device.tfrecord_decode(image, plan, [(k, out[k], 0, 0) for k, _ in chunk], handle=h, status=status[c:c + 1])
+    code = int(status.cpu().numpy().view(np.uint64).min().astype(np.int64))
+  if code != -1:
+    if code & 3 == 2:
+      raise ValueError('%s: corrupt data CRC at byte %d' % (filename, (code >> 2) * plan['stride']))
+    return _device_fallback(filename, fields, h)
+  if fields is not None:
+    _raise_missing(fields, out)
   return out
 
 
@@ -430,11 +528,142 @@ def select_streams(features, in1_fields, out_field, in2_fields=None, attended_fi
   return x, x2, y, att
 
 
+def _dataset_on_device(names, in1_fields, out_field, in2_fields, attended_field, wanted, preprocessors, handle):
+  """dataset_from_files' device route: (files, device cache) of the recordings `names`.  The concatenated input_1,
+  input_2, output and attention streams are allocated once on the device; every regular file is uploaded through a
+  pinned buffer and decoded (device.tfrecord_decode) straight into its rows and its columns of them -- the
+  concatenations of select_streams and Dataset.device_arrays are the kernel's stores -- and the statuses of all files
+  are fetched with one wait.  A file without a plan, or whose skeleton check failed, is read by
+  read_file(verify=True) on the host and uploaded into its rows.  Preprocessed fields are decoded into tensors of
+  their own, processed file by file as device tensors and placed on the device.  `files` are row slices of one host
+  copy of each stream; cache = (handle, x, x2, y, offsets) is what Dataset.device_arrays would have uploaded."""
+  import torch
+  from telluride_decoding_amd import device as dev
+  h = handle
+  in1 = [in1_fields] if isinstance(in1_fields, str) else list(in1_fields)
+  in2 = [] if not in2_fields else ([in2_fields] if isinstance(in2_fields, str) else list(in2_fields))
+  for field in preprocessors:
+    if field not in wanted:
+      raise ValueError('Could not find preprocess field %s in data (%s)' % (field, sorted(wanted)))
+
+  # what every file holds: a plan, or (irregular) the host's features
+  plans, host, rows, widths = [], [], [], None
+  for name in names:
+    plan = decode_plan(name)
+    if plan is not None and wanted - {k for k, _, _ in plan['layout']}:
+      plan = None                                   # (read_file words the missing-feature error)
+    feats = None if plan is not None else read_file(name, wanted, verify=True)
+    w = ({k: c for k, _, c in plan['layout'] if k in wanted} if plan is not None
+         else {k: v.shape[1] for k, v in feats.items()})
+    if widths is None:
+      widths = w
+    elif w != widths:
+      raise ValueError('%s: feature widths %s differ from those of %s: %s' % (name, w, names[0], widths))
+    plans.append(plan); host.append(feats)
+    rows.append(plan['frames'] if plan is not None else next(iter(feats.values())).shape[0])
+  offs = np.concatenate(([0], np.cumsum(rows))).astype(np.int64)
+  total = int(offs[-1])
+
+  # streams 0 .. 3 = input_1, input_2, output, attention.  A stream without a preprocessed field is decoded into
+  # directly: (field, tensor, column) per place.  The fields of a stream with one are decoded into tensors of their
+  # own (`own`) and the stream is put together on the device once the preprocessors have run, because a
+  # preprocessor may change the width of its field.
+  stream_fields = [in1, in2, [] if out_field == 'ones' else [out_field], [attended_field] if attended_field else []]
+  composed = [any(k in preprocessors for k in fields) for fields in stream_fields]
+  with torch.cuda.stream(h._stream):
+    streams, targets = [None] * 4, []
+    for s, fields in enumerate(stream_fields):
+      if composed[s]:
+        continue
+      streams[s] = h.empty((total, sum(widths[k] for k in fields) if fields else 1), 'float32')
+      col = 0
+      for k in fields:
+        targets.append((k, streams[s], col))
+        col += widths[k]
+    own = {k: h.empty((total, widths[k]), 'float32') for s in range(4) if composed[s] for k in stream_fields[s]}
+    targets += [(k, t, 0) for k, t in own.items()]
+    if out_field == 'ones':
+      streams[2].fill_(1.0)
+    if not attended_field:
+      streams[3].zero_()
+
+    def upload_host(i, feats):
+      r0, r1 = int(offs[i]), int(offs[i + 1])
+      for k in {k for k, _, _ in targets}:
+        if feats[k].shape != (r1 - r0, widths[k]):
+          raise ValueError('%s: feature %s is %s, not the %s its first record promises' %
+                           (names[i], k, feats[k].shape, (r1 - r0, widths[k])))
+      for k, dst, col in targets:
+        dst[r0:r1, col:col + widths[k]].copy_(torch.from_numpy(np.ascontiguousarray(feats[k], np.float32)))
+
+    chunks = [targets[c:c + dev.TFRECORD_MAX_OUTPUTS] for c in range(0, len(targets), dev.TFRECORD_MAX_OUTPUTS)]
+    regular = [i for i, plan in enumerate(plans) if plan is not None]
+    status = torch.full((max(1, len(regular) * len(chunks)),), -1, dtype=torch.int64, device=h.device)
+    biggest = max([plans[i]['frames'] * plans[i]['stride'] for i in regular] or [0])
+    image = h.empty((biggest,), 'uint8') if regular else None
+    pinned = [None, None]                           # two host buffers: the next file is read while one is copied up
+    copied = [None, None]
+    for n, i in enumerate(regular):
+      plan, b = plans[i], n & 1
+      if copied[b] is not None:
+        copied[b].synchronize()
+      if pinned[b] is None:
+        pinned[b] = torch.empty(biggest, dtype=torch.uint8, pin_memory=True)
+      image, pinned[b], copied[b] = _upload_image(names[i], plan['frames'] * plan['stride'], h, pinned[b], image)
+      for c, chunk in enumerate(chunks):
+        slot = n * len(chunks) + c
+        dev.tfrecord_decode(image, plan, [(k, dst, int(offs[i]), col) for k, dst, col in chunk], handle=h,
+                            status=status[slot:slot + 1])
+    for i, feats in enumerate(host):
+      if feats is not None:
+        upload_host(i, feats)
+    codes = status.cpu().numpy().reshape(-1, len(chunks)) if regular else []        # the one wait for all files
+    for n, i in enumerate(regular):
+      code = int(codes[n].view(np.uint64).min().astype(np.int64))                    # (-1, all clear, sorts last)
+      if code == -1:
+        continue
+      if code & 3 == 2:
+        raise ValueError('%s: corrupt data CRC at byte %d' % (names[i], (code >> 2) * plans[i]['stride']))
+      upload_host(i, read_file(names[i], wanted, verify=True))
+
+  # The preprocessors queue on torch's current stream, which need not be the handle's: each stream waits for the
+  # other where the work changes hands.
+  done = {}
+  if preprocessors:
+    current = torch.cuda.current_stream(h.device)
+    current.wait_stream(h._stream)
+    for field, p in preprocessors.items():
+      for i in range(len(names)):
+        r0, r1 = int(offs[i]), int(offs[i + 1])
+        out, _ = p.process_files(own[field][r0:r1], [0, r1 - r0], dtype='float64')
+        if int(out.shape[0]) != r1 - r0:
+          raise ValueError('%s: the preprocessing of %s changes the number of frames (%d -> %d)' %
+                           (names[i], field, r1 - r0, int(out.shape[0])))
+        if field not in done:
+          done[field] = h.empty((total, int(out.shape[1])), 'float32')
+        done[field][r0:r1].copy_(out)                       # (float64 -> float32: as np.asarray(out, np.float32))
+    h._stream.wait_stream(current)
+  with torch.cuda.stream(h._stream):
+    for s, fields in enumerate(stream_fields):
+      if composed[s]:
+        streams[s] = torch.cat([done.get(k, own[k]) for k in fields], dim=1)
+    if not in2:
+      streams[1].copy_(streams[0][:, 0:1])
+    hosts = [t.cpu().numpy() for t in streams]         # (waits for the handle's stream: `done` may be freed after it)
+  files = [tuple(a[int(offs[i]):int(offs[i + 1])] for a in hosts) for i in range(len(names))]
+  return files, (h, streams[0], streams[1], streams[2], offs)
+
+
 def dataset_from_files(filenames, in1_fields, out_field, in2_fields=None, attended_field=None,
                        batch_size=512, pre_context=0, post_context=0, in2_pre_context=0,
-                       in2_post_context=0, input_offset=0, preprocess=None, frame_rate=None):
+                       in2_post_context=0, input_offset=0, preprocess=None, frame_rate=None, device=None):
   """TFRecord files -> brain_data.Dataset (one file = one recording; context never crosses
   files, brain_data.py:722-724).  Files whose name contains '-bad-' are skipped (:677).
+
+  device (opt-in): a device.Handle.  The files are then checked and unpacked on the GPU (_dataset_on_device): the
+  same Dataset bit for bit, already resident for device_arrays(device) -- but a file with a damaged record raises
+  (a data CRC: iter_records' ValueError), as the reference's tf.data.TFRecordDataset does, where the host route,
+  which never looks at a data CRC, reads on.
 
   preprocess (opt-in): {field: preprocess.Preprocessor or 'name(key=val;...)' string} applied to that
   field of every recording on the GPU before the fields are selected, its state reset at each file
@@ -456,6 +685,14 @@ def dataset_from_files(filenames, in1_fields, out_field, in2_fields=None, attend
       from telluride_decoding_amd import preprocess as pp
       spec = pp.Preprocessor(spec, frame_rate, frame_rate)
     preprocessors[field] = spec
+  if device is not None and any('-bad-' not in name for name in filenames):
+    files, cache = _dataset_on_device([name for name in filenames if '-bad-' not in name], in1_fields, out_field,
+                                      in2_fields, attended_field, wanted, preprocessors, device)
+    ds = brain_data.Dataset(files, batch_size, pre_context=pre_context, post_context=post_context,
+                            in2_pre_context=in2_pre_context, in2_post_context=in2_post_context,
+                            input_offset=input_offset)
+    ds._device_cache = cache          # the first device_arrays(device) uploads nothing
+    return ds
   files = []
   for name in filenames:
     if '-bad-' in name:
