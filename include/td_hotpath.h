@@ -752,6 +752,47 @@ int td_tfrecord_decode(td_handle* h, const uint8_t* image_dev, int stride, int64
                        const int* offset_host, const int* count_host, void* const* dst_dev, const int64_t* ld_host,
                        const int* col_host, int64_t* status_dev);
 
+/* ------------------------------------------------------------------ raw recordings
+ * ingest_brainvision.BvBrainDataFile and ingest_edf.parse_edf_file: one uploaded file image becomes a channel-major
+ * matrix in one launch, and the chosen channels become the feature 'eeg' in one more.
+ *
+ * td_raw_decode: out_dev[s * ld_out + r * n + i] = f(sample i of signal s in data record r), n = samples_per_record.
+ * Record r is the record_bytes bytes at data_offset + r * record_bytes of image_dev [image_bytes] (16-byte aligned);
+ * signal s holds its n consecutive samples from byte signal_offset_host[s] of the record (signals of the file that
+ * are not wanted are simply not listed).  BrainVision MULTIPLEXED: a record is a frame, n = 1, offset c * w;
+ * VECTORIZED: one record, n = frames, offset c * frames * w; EDF: the header's records, offset = the sizes of the
+ * signals before.  Samples are little-endian TD_RAW_INT16 or TD_RAW_FLOAT32 (w = 2 or 4 bytes); data_offset,
+ * record_bytes and every signal offset are multiples of w.
+ *   arith 0: out_dev float32, float(x) * float(scale_host[s]) -- one float32 multiply; offset_host[s] must be 0.
+ *   arith 1: out_dev float64, scale_host[s] * (offset_host[s] + double(x)) -- a float64 add, then a multiply.
+ * Each operation is rounded once and subnormal results are kept, so both are numpy's bits.
+ * TD_ERR_INVALID before anything is queued: a NULL pointer, an image that is not 16-byte aligned, records that do not
+ * fit the image, a signal outside its record or not aligned to w, ld_out < records * n, arith 0 with an offset, more
+ * than 1024 signals.  records == 0: TD_OK, nothing is launched.  Waits for nothing. */
+#define TD_RAW_INT16 0
+#define TD_RAW_FLOAT32 1
+int td_raw_decode(td_handle* h, const uint8_t* image_dev, int64_t image_bytes, int64_t data_offset, int64_t records,
+                  int64_t record_bytes, int samples_per_record, int sample_kind, int num_signals,
+                  const int64_t* signal_offset_host, const double* scale_host, const double* offset_host, int arith,
+                  void* out_dev, int64_t ld_out);
+/* The route td_raw_decode takes.  transposed 0 (tile_records 0): consecutive lanes take consecutive output samples of
+ * one signal, loads come in runs of n samples; correct for every n.  transposed 1: runs shorter than 64 bytes
+ * (n * sample_bytes < 64) of records of which at least 16 fit the 48 KB staging area -- workgroups copy tile_records
+ * consecutive records into LDS with 16-byte loads and turn them there.  The number of signals does not matter; the
+ * record size does.  Read-only; no handle.  TD_ERR_INVALID: n < 1, a sample size other than 2 or 4, a record
+ * smaller than n samples. */
+int td_raw_route(int samples_per_record, int sample_bytes, int64_t record_bytes, int* transposed, int* tile_records);
+/* BrainTrial.assemble_brain_data: out_dev [frames, sum of width_host] float32 (row stride ld_out) = the sources side
+ * by side in their order.  Source k is src_dev[k] [frames, width_host[k]] float32 (float64 when is_f64_host[k]:
+ * rounded to nearest even, overflow to +-Inf, as astype), row stride ld_host[k] elements.  One launch.
+ * 1 <= num_sources <= 1024, at most 65536 columns.  frames == 0: TD_OK, nothing is launched. */
+int td_columns_assemble(td_handle* h, int num_sources, const void* const* src_dev, const int64_t* ld_host,
+                        const int* width_host, const int* is_f64_host, int64_t frames, float* out_dev, int64_t ld_out);
+/* The route td_columns_assemble takes.  transposed 1: every source is one column (max_width 1) and there are at
+ * least 16 -- a 64 x 64 tiled transpose through LDS, loads along the frames of each source, stores along the
+ * columns.  transposed 0: one lane per output element.  Read-only; no handle. */
+int td_columns_route(int num_sources, int max_width, int* transposed);
+
 /* ------------------------------------------------------------------ fully connected regressor
  * brain_model.BrainModelDNN (reference brain_model.py:486-549): Dense layers z = a.W + b in float32, ReLU on
  * the num_hidden hidden layers (hidden_host[i] units each), a linear output layer of d units.  The input is

@@ -163,6 +163,10 @@ SIGNATURES = {
     'td_tfrecord_route': [_i, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)],
     'td_tfrecord_decode': [_vp, _vp, _i, _i64, _c.c_char_p, _c.c_char_p, _i, _c.POINTER(_i), _c.POINTER(_i),
                            _c.POINTER(_vp), _pi64, _c.POINTER(_i), _vp],
+    'td_raw_decode': [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _pi64, _pd, _pd, _i, _vp, _i64],
+    'td_raw_route': [_i, _i, _i64, _c.POINTER(_i), _c.POINTER(_i)],
+    'td_columns_assemble': [_vp, _i, _c.POINTER(_vp), _pi64, _c.POINTER(_i), _c.POINTER(_i), _i64, _vp, _i64],
+    'td_columns_route': [_i, _i, _c.POINTER(_i)],
     'td_mlp_train': _MLP + _FIT + _EPOCHS + [_f, _f, _f] + _SEED_STATS,
     'td_mlp_grad': _MLP + _FIT + _GRAD,
     'td_mlp_train_loss': _MLP + _FIT + _EPOCHS + [_f, _f, _f] + _SEED_STATS + [_i],

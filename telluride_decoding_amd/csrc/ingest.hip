@@ -38,31 +38,6 @@ constexpr int kStageBytes = 48 * 1024;       // LDS bytes of staged records per 
 constexpr int kTabWords = 256 + 4 * 256;     // CRC byte table, then the advance table
 constexpr unsigned kMaskDelta = 0xa282ead8u;
 
-// ---------------------------------------------------------------- float64 -> float32 bits
-// Round to nearest even as a C cast / numpy's astype(float32): overflow to +-Inf, denormal results rounded at
-// 2^-149, NaN quieted with the top payload bits kept.  Integer arithmetic: independent of the denormal mode.
-__host__ __device__ inline uint32_t f64_to_f32_bits(uint64_t b) {
-  const uint32_t sign = (uint32_t)(b >> 32) & 0x80000000u;
-  const int e = (int)((b >> 52) & 0x7ff);
-  const uint64_t m = b & 0xfffffffffffffull;
-  if (e == 0x7ff) return m ? (sign | 0x7fc00000u | (uint32_t)(m >> 29)) : (sign | 0x7f800000u);
-  const int ef = e - 1023 + 127;
-  if (ef >= 255) return sign | 0x7f800000u;
-  if (ef <= 0) {
-    if (ef < -23) return sign;                               // below half of the smallest denormal
-    const uint64_t full = m | (1ull << 52);
-    const int s = 30 - ef;                                   // 30 .. 53
-    uint64_t q = full >> s;
-    const uint64_t rem = full & ((1ull << s) - 1), half = 1ull << (s - 1);
-    if (rem > half || (rem == half && (q & 1))) ++q;
-    return sign | (uint32_t)q;
-  }
-  uint32_t r = ((uint32_t)ef << 23) | (uint32_t)(m >> 29);
-  const uint32_t rem = (uint32_t)m & 0x1fffffffu;
-  if (rem > 0x10000000u || (rem == 0x10000000u && (r & 1))) ++r;   // (carries into the exponent, up to Inf)
-  return sign | r;
-}
-
 // ---------------------------------------------------------------- encoder
 struct EncFeature {
   const void* ptr;
@@ -79,7 +54,7 @@ struct EncParams {
 __device__ __forceinline__ uint32_t load_bits(const EncFeature& F, long long frames, long long row, int e) {
   if (F.reversed) row = frames - 1 - row;
   const long long at = row * F.ld + e;
-  return F.is_f64 ? f64_to_f32_bits(static_cast<const uint64_t*>(F.ptr)[at]) : static_cast<const uint32_t*>(F.ptr)[at];
+  return F.is_f64 ? td_f64_to_f32_bits(static_cast<const uint64_t*>(F.ptr)[at]) : static_cast<const uint32_t*>(F.ptr)[at];
 }
 
 __device__ __forceinline__ uint32_t crc_advance(const uint32_t* adv, uint32_t c) {

@@ -276,6 +276,31 @@ __host__ __device__ __forceinline__ int td_f16_scale_exp(unsigned max_bits) {
   return k > 126 ? 126 : (k < -126 ? -126 : k);
 }
 
+// ---- float64 -> float32 bits (ingest.hip, raw.hip) ----------------------------------------------
+// Round to nearest even as a C cast / numpy's astype(float32): overflow to +-Inf, denormal results rounded at
+// 2^-149, NaN quieted with the top payload bits kept.  Integer arithmetic: independent of the denormal mode.
+__host__ __device__ inline uint32_t td_f64_to_f32_bits(uint64_t b) {
+  const uint32_t sign = (uint32_t)(b >> 32) & 0x80000000u;
+  const int e = (int)((b >> 52) & 0x7ff);
+  const uint64_t m = b & 0xfffffffffffffull;
+  if (e == 0x7ff) return m ? (sign | 0x7fc00000u | (uint32_t)(m >> 29)) : (sign | 0x7f800000u);
+  const int ef = e - 1023 + 127;
+  if (ef >= 255) return sign | 0x7f800000u;
+  if (ef <= 0) {
+    if (ef < -23) return sign;                               // below half of the smallest denormal
+    const uint64_t full = m | (1ull << 52);
+    const int s = 30 - ef;                                   // 30 .. 53
+    uint64_t q = full >> s;
+    const uint64_t rem = full & ((1ull << s) - 1), half = 1ull << (s - 1);
+    if (rem > half || (rem == half && (q & 1))) ++q;
+    return sign | (uint32_t)q;
+  }
+  uint32_t r = ((uint32_t)ef << 23) | (uint32_t)(m >> 29);
+  const uint32_t rem = (uint32_t)m & 0x1fffffffu;
+  if (rem > 0x10000000u || (rem == 0x10000000u && (r & 1))) ++r;   // (carries into the exponent, up to Inf)
+  return sign | r;
+}
+
 static inline int64_t td_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t td_round_up(int64_t a, int64_t b) { return td_ceil_div(a, b) * b; }
 

@@ -1052,6 +1052,98 @@ def tfrecord_decode(image, plan, outputs, handle=None, status=None):
   return status
 
 
+RAW_INT16, RAW_FLOAT32 = 0, 1
+RAW_MAX_SIGNALS = 1024
+COLUMNS_MAX_SOURCES = 1024
+
+
+def raw_route(samples_per_record, sample_bytes, record_bytes):
+  """(transposed, records per workgroup) of raw_decode for records of `record_bytes` bytes whose signals hold
+  `samples_per_record` samples of `sample_bytes` bytes each (td_raw_route).  transposed False: the direct route,
+  loads in runs of one signal's samples.  Needs the library, not a GPU."""
+  lib = _lib.load()
+  transposed, tile = ctypes.c_int(0), ctypes.c_int(0)
+  if lib.td_raw_route(int(samples_per_record), int(sample_bytes), int(record_bytes), ctypes.byref(transposed),
+                      ctypes.byref(tile)) != 0:
+    raise ValueError('raw_route: bad sizes (%s samples of %s bytes in a record of %s bytes)' %
+                     (samples_per_record, sample_bytes, record_bytes))
+  return bool(transposed.value), int(tile.value)
+
+
+def raw_decode(image, data_offset, records, record_bytes, samples_per_record, sample_kind, signal_offsets, scales,
+               offsets=None, out=None, handle=None):
+  """The signals of a raw recording's file image as a channel-major device matrix [signals, records *
+  samples_per_record] (td_raw_decode).  image: contiguous device uint8, 16-byte aligned; record r is the
+  record_bytes bytes at data_offset + r * record_bytes, signal s its samples_per_record samples (RAW_INT16 or
+  RAW_FLOAT32, little-endian) from byte signal_offsets[s] of the record.  offsets None: float32,
+  float32(x) * float32(scales[s]); else float64, scales[s] * (offsets[s] + float64(x)).  out: a matrix of that dtype
+  with contiguous rows of at least records * samples_per_record elements, filled and returned.  Waits for nothing."""
+  torch = _torch()
+  h = handle or default_handle()
+  if image.dtype != torch.uint8 or image.dim() != 1 or not image.is_contiguous():
+    raise ValueError('raw_decode: a contiguous uint8 device image is needed')
+  if sample_kind not in (RAW_INT16, RAW_FLOAT32):
+    raise ValueError('raw_decode: unknown sample kind %s' % (sample_kind,))
+  n, records = int(samples_per_record), int(records)
+  num = len(signal_offsets)
+  if not 1 <= num <= RAW_MAX_SIGNALS:
+    raise ValueError('raw_decode: 1 .. %d signals, not %d' % (RAW_MAX_SIGNALS, num))
+  arith = 0 if offsets is None else 1
+  if len(scales) != num or (arith and len(offsets) != num):
+    raise ValueError('raw_decode: %d signals need as many scales and offsets' % num)
+  dtype = torch.float64 if arith else torch.float32
+  if out is None:
+    out = h.empty((num, records * n), 'float64' if arith else 'float32')
+  if (out.dim() != 2 or out.dtype != dtype or out.shape[0] < num or out.shape[1] < records * n or
+      (out.shape[1] > 1 and out.stride(1) != 1)):
+    raise ValueError('raw_decode: a %s [>= %d, >= %d] matrix with contiguous rows is needed, not %s %s' %
+                     (dtype, num, records * n, tuple(out.shape), out.dtype))
+  keep_off, off_p = _lib.i64_array([int(o) for o in signal_offsets])
+  keep_scale, scale_p = _lib.f64_array(np.asarray(scales, np.float64).reshape(-1))
+  keep_add, add_p = _lib.f64_array(np.zeros(num) if offsets is None else np.asarray(offsets, np.float64).reshape(-1))
+  h.check(h.lib.td_raw_decode(h.ptr, _ptr(image), int(image.numel()), int(data_offset), records, int(record_bytes), n,
+                              int(sample_kind), num, off_p, scale_p, add_p, arith, _ptr(out), _row_stride(out)))
+  return out
+
+
+def columns_route(num_sources, max_width):
+  """Whether columns_assemble takes the tiled transpose for that many sources, the widest of `max_width` columns
+  (td_columns_route).  Needs the library, not a GPU."""
+  lib = _lib.load()
+  transposed = ctypes.c_int(0)
+  if lib.td_columns_route(int(num_sources), int(max_width), ctypes.byref(transposed)) != 0:
+    raise ValueError('columns_route: bad sizes (%s sources, width %s)' % (num_sources, max_width))
+  return bool(transposed.value)
+
+
+def columns_assemble(sources, frames=None, out=None, handle=None):
+  """[frames, sum of widths] float32 = the first `frames` rows (default: the fewest any has) of the [rows_k, w_k]
+  float32 / float64 device tensors `sources` side by side, in one launch (td_columns_assemble); float64 is rounded
+  to nearest even as astype does.  Waits for nothing."""
+  h = handle or default_handle()
+  sources = [_check_rows(s, 'columns_assemble') for s in sources]
+  n = len(sources)
+  if not 1 <= n <= COLUMNS_MAX_SOURCES:
+    raise ValueError('columns_assemble: 1 .. %d sources, not %d' % (COLUMNS_MAX_SOURCES, n))
+  fewest = min(int(s.shape[0]) for s in sources)
+  frames = fewest if frames is None else int(frames)
+  if not 0 <= frames <= fewest:
+    raise ValueError('columns_assemble: %d frames of sources with %d rows' % (frames, fewest))
+  width = sum(int(s.shape[1]) for s in sources)
+  if out is None:
+    out = h.empty((frames, width), 'float32')
+  if (out.dim() != 2 or out.dtype != _torch().float32 or out.shape[0] < frames or out.shape[1] < width or
+      (out.shape[1] > 1 and out.stride(1) != 1)):
+    raise ValueError('columns_assemble: a float32 [>= %d, >= %d] matrix with contiguous rows is needed, not %s %s' %
+                     (frames, width, tuple(out.shape), out.dtype))
+  ptrs = (ctypes.c_void_p * n)(*[s.data_ptr() for s in sources])
+  keep_ld, ld_p = _lib.i64_array([_row_stride(s) for s in sources])
+  keep_width, width_p = _i32_array([int(s.shape[1]) for s in sources])
+  keep_f64, f64_p = _i32_array([1 if s.dtype == _torch().float64 else 0 for s in sources])
+  h.check(h.lib.td_columns_assemble(h.ptr, n, ptrs, ld_p, width_p, f64_p, frames, _ptr(out), _row_stride(out)))
+  return out
+
+
 def sos_filter_plan(n_total, n_max, c, handle=None):
   """(chunk, scan levels) that sos_filter uses for files of n_total rows in all, the longest n_max, over c
   channels (td_sos_filter_plan)."""

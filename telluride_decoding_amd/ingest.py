@@ -21,8 +21,12 @@ What differs from the reference:
   * save_zscore_data writes its pickle in binary mode (the reference's text mode cannot hold one).
   * discover_feature_shapes returns {name: (width, dtype name)} (tfrecord.discover_feature_shapes), not
     tf.io.FixedLenFeature objects: TensorFlow is not a dependency.
-  * EdfBrainDataFile and parse_edf_file import pyedflib when used and raise an ImportError that says so.
-  * ingest_brainvision, regression_data and add_trigger are not here.
+  * EdfBrainDataFile and parse_edf_file import pyedflib when used and raise an ImportError that says so;
+    ingest_edf has an EdfBrainDataFile and a parse_edf_file that need no pyedflib and decode the file on the GPU.
+  * assemble_brain_data builds 'eeg' from float32 / float64 device tensors in one launch
+    (device.columns_assemble) instead of one strided copy per channel.
+  * BrainVision recordings are read by ingest_brainvision, a module of its own as in the reference.
+    regression_data (downloads data sets) and add_trigger (stimulus preparation) are not here.
 """
 import collections
 import logging
@@ -80,6 +84,35 @@ def _rows_tensor(t):
   if t.shape[1] > 1 and t.stride(1) != 1:
     t = t.contiguous()
   return t
+
+
+def _all_float_device_tensors(signals):
+  """Whether device.columns_assemble takes them: float32 / float64 device tensors, within its limits."""
+  if not signals or len(signals) > device.COLUMNS_MAX_SOURCES or sum(s.shape[1] for s in signals) > 65536:
+    return False
+  if not all(_is_device_tensor(s) for s in signals):
+    return False
+  torch = _torch()
+  return all(s.dtype in (torch.float32, torch.float64) and s.shape[1] >= 1 for s in signals)
+
+
+def _assemble_columns_loop(chosen, frames, width):
+  """The first `frames` rows of the signals side by side as float32, one strided copy per signal: NumPy inputs,
+  and host and device inputs mixed (then, and for device inputs of other dtypes, a device tensor)."""
+  where = next((s.device for s in chosen if _is_device_tensor(s)), None)
+  if where is None:
+    eeg = np.zeros((frames, width), dtype=np.float32)
+  else:
+    torch = _torch()
+    eeg = torch.zeros((frames, width), dtype=torch.float32, device=where)
+  c = 0
+  for s in chosen:
+    piece = s[:frames, :]
+    if where is not None and not _is_device_tensor(piece):
+      piece = _torch().from_numpy(np.ascontiguousarray(piece, dtype=np.float32)).to(where)
+    eeg[:, c:c + s.shape[1]] = piece
+    c += s.shape[1]
+  return eeg
 
 
 def assert_type(var_name, var, expected_type):
@@ -331,7 +364,9 @@ class BrainTrial(object):
   def assemble_brain_data(self, eeg_channel_names):
     """The named channels (a list, or one comma-separated string) side by side as the float32 model feature
     'eeg', trimmed to the shortest of them.  Columns come in the order of brain_data, not of the request.  A
-    duplicate or unknown name is a ValueError.  If any of the channels is a device tensor, so is the result."""
+    duplicate or unknown name is a ValueError.  If any of the channels is a device tensor, so is the result; when
+    all of them are float32 / float64 device tensors one launch builds it (device.columns_assemble), else one
+    strided copy per channel does (_assemble_columns_loop): the same bits."""
     if not isinstance(eeg_channel_names, (str, list)):
       raise TypeError('eeg_channel_names must be a string or a list of strings.')
     if isinstance(eeg_channel_names, str):
@@ -344,19 +379,10 @@ class BrainTrial(object):
     chosen = [s.signal for k, s in self._brain_data.items() if k in eeg_channel_names]
     frames = min([_BIG] + [s.shape[0] for s in chosen])
     width = sum(s.shape[1] for s in chosen)
-    where = next((s.device for s in chosen if _is_device_tensor(s)), None)
-    if where is None:
-      eeg = np.zeros((frames, width), dtype=np.float32)
+    if frames > 0 and _all_float_device_tensors(chosen):
+      eeg = device.columns_assemble([_rows_tensor(s) for s in chosen], frames)
     else:
-      torch = _torch()
-      eeg = torch.zeros((frames, width), dtype=torch.float32, device=where)
-    c = 0
-    for s in chosen:
-      piece = s[:frames, :]
-      if where is not None and not _is_device_tensor(piece):
-        piece = _torch().from_numpy(np.ascontiguousarray(piece, dtype=np.float32)).to(where)
-      eeg[:, c:c + s.shape[1]] = piece
-      c += s.shape[1]
+      eeg = _assemble_columns_loop(chosen, frames, width)
     self._model_features['eeg'] = eeg
 
   def write_data_as_tfrecords(self, tf_dir, reverse_data_for_test=False):

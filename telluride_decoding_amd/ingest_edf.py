@@ -1,0 +1,173 @@
+"""EDF recordings without pyedflib: the header parsed here, the data records decoded on the GPU.
+
+An EDF file is a 256-byte ASCII header, 256 more bytes per signal (ten fields, each stored for all the signals in
+turn), then the data records: in every record each signal's `samples per record` little-endian int16 values, one
+signal after the other.  The physical value of a stored number is
+
+  bitvalue = (physical_max - physical_min) / (digital_max - digital_min)
+  offset   = physical_max / bitvalue - digital_max
+  value    = bitvalue * (offset + digital)                     all in float64
+
+which is this module's contract (the NumPy expression above, bit for bit, on either route); it is edflib's formula
+as published, but pyedflib is not a dependency and has not been compared against.
+
+  parse_edf_file    the dictionary ingest.EdfBrainDataFile works from
+  EdfBrainDataFile  ingest.EdfBrainDataFile with a load_all_data that needs no pyedflib
+
+With a GPU (device.gpu_available()) the file is uploaded once and one launch (device.raw_decode) makes the float64
+[signals, samples] device matrix; a signal's values are a row of it.  Without one the same values are NumPy's.
+
+Read: plain EDF and continuous EDF+ ('EDF+C'); signals labelled 'EDF Annotations' are left out.  A ValueError
+that names the reason: EDF+D (discontinuous), BDF (24-bit samples), ordinary signals that differ in samples per
+record, a header that does not hold together.  A record count of -1 (a recording that was cut off) or one larger
+than the file holds is replaced by the number of whole records in the file.
+"""
+import os
+
+import numpy as np
+
+from telluride_decoding_amd import device
+from telluride_decoding_amd import ingest
+
+ANNOTATIONS = 'EDF Annotations'
+# the per-signal header fields in file order: (plain name, bytes)
+_SIGNAL_FIELDS = (('label', 16), ('transducer', 80), ('dimension', 8), ('physical_min', 8), ('physical_max', 8),
+                  ('digital_min', 8), ('digital_max', 8), ('prefilter', 80), ('samples_per_record', 8),
+                  ('reserved', 32))
+_MAIN_FIELDS = (('version', 8), ('patient', 80), ('recording', 80), ('startdate', 8), ('starttime', 8),
+                ('header_bytes', 8), ('reserved', 44), ('records', 8), ('record_duration', 8), ('signals', 4))
+
+
+def _text(raw):
+  return raw.decode('latin-1').strip()
+
+
+def _number(fields, name, kind, path):
+  try:
+    return kind(fields[name])
+  except ValueError:
+    raise ValueError('%s: the header field %s does not hold a number: %r' % (path, name, fields[name]))
+
+
+def read_edf_header(path):
+  """(main header, [per-signal header], file size) of an EDF file: every field trimmed, the numeric ones converted;
+  'header_bytes', 'records', 'signals' ints, 'record_duration' and the four ranges floats."""
+  size = os.path.getsize(path)
+  with open(path, 'rb') as f:
+    fixed = f.read(256)
+    if len(fixed) < 256:
+      raise ValueError('%s: %d bytes are less than an EDF header' % (path, len(fixed)))
+    if fixed[:1] == b'\xff':
+      raise ValueError('%s: a BDF file (24-bit samples) is not read' % path)
+    main, at = {}, 0
+    for name, width in _MAIN_FIELDS:
+      main[name] = _text(fixed[at:at + width])
+      at += width
+    for name, kind in (('header_bytes', int), ('records', int), ('signals', int), ('record_duration', float)):
+      main[name] = _number(main, name, kind, path)
+    count = main['signals']
+    if count < 1 or main['header_bytes'] != 256 * (count + 1):
+      raise ValueError('%s: a header of %d bytes does not go with %d signals' % (path, main['header_bytes'], count))
+    block = f.read(256 * count)
+  if len(block) < 256 * count:
+    raise ValueError('%s: the file ends inside its header' % path)
+  if main['reserved'].startswith('EDF+D'):
+    raise ValueError('%s: a discontinuous recording (EDF+D) is not read' % path)
+  signals, at = [{} for _ in range(count)], 0
+  for name, width in _SIGNAL_FIELDS:
+    for s in range(count):
+      signals[s][name] = _text(block[at:at + width])
+      at += width
+  for s in signals:
+    s['samples_per_record'] = _number(s, 'samples_per_record', int, path)
+    for name in ('physical_min', 'physical_max', 'digital_min', 'digital_max'):
+      s[name] = _number(s, name, float, path)
+  return main, signals, size
+
+
+def _layout(path):
+  """What both routes work from: (main, the ordinary signals' headers, their byte offsets in a record, samples per
+  record, record bytes, whole records to read, bitvalues, offsets)."""
+  main, signals, size = read_edf_header(path)
+  offsets, at = [], 0
+  for s in signals:
+    if s['samples_per_record'] < 0:
+      raise ValueError('%s: signal %s has %d samples per record' % (path, s['label'], s['samples_per_record']))
+    offsets.append(at)
+    at += 2 * s['samples_per_record']
+  record_bytes = at
+  kept = [(s, off) for s, off in zip(signals, offsets) if s['label'] != ANNOTATIONS]
+  if not kept:
+    raise ValueError('%s: no signals but annotations' % path)
+  counts = sorted({s['samples_per_record'] for s, _ in kept})
+  if len(counts) > 1:
+    raise ValueError('%s: the signals differ in samples per record (%s); they do not make one matrix' % (path, counts))
+  n = counts[0]
+  if n < 1:
+    raise ValueError('%s: the signals have no samples' % path)
+  if not main['record_duration'] > 0:
+    raise ValueError('%s: a record duration of %s gives no sample rate' % (path, main['record_duration']))
+  whole = (size - main['header_bytes']) // record_bytes
+  records = whole if (main['records'] < 0 or main['records'] > whole) else main['records']
+  scale, add = [], []
+  for s, _ in kept:
+    if s['digital_max'] == s['digital_min'] or s['physical_max'] == s['physical_min']:
+      raise ValueError('%s: signal %s has an empty physical or digital range' % (path, s['label']))
+    bitvalue = np.float64(s['physical_max'] - s['physical_min']) / np.float64(s['digital_max'] - s['digital_min'])
+    scale.append(bitvalue)
+    add.append(np.float64(s['physical_max']) / bitvalue - np.float64(s['digital_max']))
+  return main, [s for s, _ in kept], [off for _, off in kept], n, record_bytes, records, scale, add
+
+
+def parse_edf_file(sample_edf_file):
+  """{'labels', 'signals' float64 [signal, samples], 'sample_rates', 'header', 'signal_headers'} of an EDF file:
+  what ingest.parse_edf_file returns, without pyedflib.  'signals' is a device tensor with a GPU and a NumPy array
+  without one; the headers hold the trimmed fields under plain names ('label', 'dimension', 'physical_min', ...,
+  plus 'sample_rate'), not pyedflib's parsed sub-fields."""
+  path = sample_edf_file
+  main, kept, offsets, n, record_bytes, records, scale, add = _layout(path)
+  data_offset = main['header_bytes']
+  if device.gpu_available():
+    import torch
+    from telluride_decoding_amd import tfrecord
+    h = device.default_handle()
+    if records == 0:
+      values = h.empty((len(kept), 0), 'float64')
+    else:
+      with torch.cuda.stream(h._stream):
+        image, _, _ = tfrecord._upload_image(path, data_offset + records * record_bytes, h)
+        values = device.raw_decode(image, data_offset, records, record_bytes, n, device.RAW_INT16, offsets, scale, add,
+                                   handle=h)
+  else:
+    with open(path, 'rb') as f:
+      f.seek(data_offset)
+      raw = np.frombuffer(f.read(records * record_bytes), dtype='<i2').reshape(records, record_bytes // 2)
+    values = np.empty((len(kept), records * n), np.float64)
+    for i, off in enumerate(offsets):
+      digital = raw[:, off // 2:off // 2 + n].reshape(-1).astype(np.float64)
+      values[i] = scale[i] * (add[i] + digital)
+  rate = n / main['record_duration']
+  signal_headers = []
+  for s in kept:
+    entry = {k: v for k, v in s.items() if k not in ('samples_per_record', 'reserved')}
+    entry['sample_rate'] = rate
+    signal_headers.append(entry)
+  header = {k: main[k] for k in ('patient', 'recording', 'startdate', 'starttime', 'reserved', 'record_duration')}
+  header['records'] = records
+  return {'labels': [s['label'] for s in kept], 'signals': values, 'sample_rates': np.full(len(kept), rate),
+          'header': header, 'signal_headers': signal_headers}
+
+
+class EdfBrainDataFile(ingest.EdfBrainDataFile):
+  """ingest.EdfBrainDataFile read by this module's parse_edf_file: names, values, rates and find_channel_index are
+  inherited."""
+
+  def load_all_data(self, data_dir):
+    if not os.path.exists(data_dir):
+      raise IOError('Data_dir does not exist:', data_dir)
+    path = os.path.join(data_dir, self._data_filename)
+    if not path.endswith('.edf'):
+      path += '.edf'
+    if not os.path.exists(path):
+      raise IOError('Can not open %s for reading' % path)
+    self._edf_dict = parse_edf_file(path)
