@@ -399,6 +399,9 @@ __global__ __launch_bounds__(kThreads, 2) void lagcov_mfma_kernel(LagParams p) {
 // +1 and +3 the same spans moved by one sample (v_alignbit_b32, 8 per piece).  That is 7.6 KB of
 // LDS reads per 24 MFMAs; with one lag and a 64 x 64 tile per wave it was 15 KB and the LDS
 // array was the bottleneck (the float32 kernel needs a ninth of that per matrix-pipe cycle).
+// (The plain float16 instances -- 33..64 channels, no virtual image -- give wave w the lags
+// e0 + 2 (w & 1) + {0, 1, 4, 5} instead: seven dwords of B, six shuffles per piece and operands
+// that need no register copy; bf_kstep_skip.  The furthest sample a wave reads is the same.)
 //
 // Two-level accumulation.  The bf16 MFMA aligns its 16 products and the accumulator to the
 // largest exponent and TRUNCATES below a few guard bits: chains of a 2048-sample slab left the
@@ -439,6 +442,123 @@ __device__ __forceinline__ float comp4(const float4& v, int q) {
   return q == 0 ? v.x : q == 1 ? v.y : q == 2 ? v.z : v.w;
 }
 
+// ---- the float16 k-step with lags +0, +1, +4, +5 -------------------------------------------------
+// An MFMA operand is an even-aligned register quad.  With the B span d[0..6] of a piece in ONE aligned
+// block of eight registers, lag +0 is d[0..3] and lag +4 is d[2..5] as they lie; with q[i] =
+// alignbit(d[i+1], d[i], 16), i = 0..5, in a second aligned block, lag +1 is q[0..3] and lag +5 is
+// q[2..5]: seven dwords read and six shuffles per piece, and no register copy.  (Lags +0 .. +3 need the
+// odd-aligned quad d[1..4]: hipcc built every operand in registers of its own, 19 v_mov_b32 per k-step
+// in front of 12 matrix instructions, inside the wave's own chain ds_read -> v_perm -> v_mov -> v_mfma.)
+// hipcc cannot be told to keep such a layout (sub-tuples of ext_vector_type(8) values were copied out
+// again), so the k-step is one asm block on FIXED registers v[216:255] -- the operand list cannot name a
+// part of a register tuple:
+//   v[216:219] A h   v[220:223] A l   v[224:230] B h d[0..6]   v[232:238] B l d[0..6]
+//   v[240:245] q of B h               v[248:253] q of B l
+// Same operand words and the same order per lag as bf_kstep: l h', h l', h h', the four lags in turn.
+// What the block owes the hardware, since hipcc inserts nothing inside it: two wait states between a
+// VALU write and the MFMA that reads it (every shuffle and mask is at least two instructions ahead of
+// its reader), and the wait between the last MFMA and a VALU read of its result (kLast: the chain's
+// sums are added up next; s_nop 15 + s_nop 3 covers the 16-pass figure; within a chain the
+// accumulators are tied operands of the next block and nothing else reads them, and the masked
+// k-steps of a cut tile all end with the wait).  The LDS reads of a k-step
+// are issued together, B h and A l first: the first four MFMAs wait for those six only.  (Measured,
+// profiles/NOTES.md 13: the seventh dword as a ds_read_b32 -- a fourth ds_read2_b32 per piece was 3.7 us
+// a step slower; a static s_setprio 1 for waves 4-7 changed nothing.)
+#define TD_KS_C0(r) "0"
+#define TD_KS_C1(r) "%" #r
+#define TD_KS_BODY(C, MASK_L, MASK_H, TAIL)                                              \
+  "ds_read2_b32 v[224:225], %[bp0] offset0:%[o0] offset1:%[o1]\n"                        \
+  "ds_read2_b32 v[226:227], %[bp0] offset0:%[o2] offset1:%[o3]\n"                        \
+  "ds_read2_b32 v[228:229], %[bp0] offset0:%[o4] offset1:%[o5]\n"                        \
+  "ds_read_b32 v230, %[bp0] offset:%[ob]\n"                                              \
+  "ds_read2_b32 v[220:221], %[ap1] offset0:%[o0] offset1:%[o1]\n"                        \
+  "ds_read2_b32 v[222:223], %[ap1] offset0:%[o2] offset1:%[o3]\n"                        \
+  "ds_read2_b32 v[232:233], %[bp1] offset0:%[o0] offset1:%[o1]\n"                        \
+  "ds_read2_b32 v[234:235], %[bp1] offset0:%[o2] offset1:%[o3]\n"                        \
+  "ds_read2_b32 v[236:237], %[bp1] offset0:%[o4] offset1:%[o5]\n"                        \
+  "ds_read_b32 v238, %[bp1] offset:%[ob]\n"                                              \
+  "ds_read2_b32 v[216:217], %[ap0] offset0:%[o0] offset1:%[o1]\n"                        \
+  "ds_read2_b32 v[218:219], %[ap0] offset0:%[o2] offset1:%[o3]\n"                        \
+  "s_waitcnt lgkmcnt(6)\n"                                                               \
+  MASK_L                                                                                 \
+  "v_alignbit_b32 v240, v225, v224, 16\n"                                                \
+  "v_alignbit_b32 v241, v226, v225, 16\n"                                                \
+  "v_alignbit_b32 v242, v227, v226, 16\n"                                                \
+  "v_alignbit_b32 v243, v228, v227, 16\n"                                                \
+  "v_alignbit_b32 v244, v229, v228, 16\n"                                                \
+  "v_alignbit_b32 v245, v230, v229, 16\n"                                                \
+  "v_mfma_f32_32x32x16_f16 %0, v[220:223], v[224:227], " C(0) "\n"                       \
+  "s_waitcnt lgkmcnt(0)\n"                                                               \
+  MASK_H                                                                                 \
+  "v_alignbit_b32 v248, v233, v232, 16\n"                                                \
+  "v_alignbit_b32 v249, v234, v233, 16\n"                                                \
+  "v_mfma_f32_32x32x16_f16 %1, v[220:223], v[240:243], " C(1) "\n"                       \
+  "v_alignbit_b32 v250, v235, v234, 16\n"                                                \
+  "v_alignbit_b32 v251, v236, v235, 16\n"                                                \
+  "v_mfma_f32_32x32x16_f16 %2, v[220:223], v[226:229], " C(2) "\n"                       \
+  "v_alignbit_b32 v252, v237, v236, 16\n"                                                \
+  "v_alignbit_b32 v253, v238, v237, 16\n"                                                \
+  "v_mfma_f32_32x32x16_f16 %3, v[220:223], v[242:245], " C(3) "\n"                       \
+  "v_mfma_f32_32x32x16_f16 %0, v[216:219], v[232:235], %0\n"                             \
+  "v_mfma_f32_32x32x16_f16 %1, v[216:219], v[248:251], %1\n"                             \
+  "v_mfma_f32_32x32x16_f16 %2, v[216:219], v[234:237], %2\n"                             \
+  "v_mfma_f32_32x32x16_f16 %3, v[216:219], v[250:253], %3\n"                             \
+  "v_mfma_f32_32x32x16_f16 %0, v[216:219], v[224:227], %0\n"                             \
+  "v_mfma_f32_32x32x16_f16 %1, v[216:219], v[240:243], %1\n"                             \
+  "v_mfma_f32_32x32x16_f16 %2, v[216:219], v[226:229], %2\n"                             \
+  "v_mfma_f32_32x32x16_f16 %3, v[216:219], v[242:245], %3\n"                             \
+  TAIL
+#define TD_KS_MASK_L                                                                     \
+  "v_and_b32 v220, %[m0], v220\n" "v_and_b32 v221, %[m1], v221\n"                        \
+  "v_and_b32 v222, %[m2], v222\n" "v_and_b32 v223, %[m3], v223\n"
+#define TD_KS_MASK_H                                                                     \
+  "v_and_b32 v216, %[m0], v216\n" "v_and_b32 v217, %[m1], v217\n"                        \
+  "v_and_b32 v218, %[m2], v218\n" "v_and_b32 v219, %[m3], v219\n"
+#define TD_KS_TAIL "s_nop 15\ns_nop 3\n"
+#define TD_KS_INS                                                                        \
+  [ap0] "v"(ap0), [ap1] "v"(ap1), [bp0] "v"(bp0), [bp1] "v"(bp1),                        \
+  [o0] "n"(kOff), [o1] "n"(kOff + 1), [o2] "n"(kOff + 2), [o3] "n"(kOff + 3),            \
+  [o4] "n"(kOff + 4), [o5] "n"(kOff + 5), [ob] "n"(4 * (kOff + 6)),                      \
+  [m0] "v"(m0), [m1] "v"(m1), [m2] "v"(m2), [m3] "v"(m3)
+#define TD_KS_CLOBBER                                                                    \
+  "memory", "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223", "v224", "v225", "v226", "v227", \
+  "v228", "v229", "v230", "v231", "v232", "v233", "v234", "v235", "v236", "v237", "v238", "v239", "v240",   \
+  "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252", "v253",   \
+  "v254", "v255"
+#define TD_KS_ASM(OUT, C, ML, MH, TAIL)                                                  \
+  asm volatile(TD_KS_BODY(C, ML, MH, TAIL)                                               \
+               : OUT(acc[0]), OUT(acc[1]), OUT(acc[2]), OUT(acc[3]) : TD_KS_INS : TD_KS_CLOBBER)
+
+// the address of p in LDS (p points into the kernel's dynamic LDS)
+__device__ __forceinline__ unsigned lds_addr(const unsigned* p) {
+  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned*)p;
+}
+
+// ap0 / ap1, bp0 / bp1: LDS byte addresses of the lane's A row and B span in the pieces h / l.
+template <bool kZero, bool kMask, bool kLast, int kOff>
+__device__ __forceinline__ void bf_kstep_skip(unsigned ap0, unsigned ap1, unsigned bp0, unsigned bp1,
+                                              const unsigned* a_mask, f32x16 (&acc)[4]) {
+  unsigned m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+  if constexpr (kMask) { m0 = a_mask[0]; m1 = a_mask[1]; m2 = a_mask[2]; m3 = a_mask[3]; }
+  if constexpr (kZero) {
+    if constexpr (kMask) {
+      if constexpr (kLast) TD_KS_ASM("=&v", TD_KS_C0, TD_KS_MASK_L, TD_KS_MASK_H, TD_KS_TAIL);
+      else TD_KS_ASM("=&v", TD_KS_C0, TD_KS_MASK_L, TD_KS_MASK_H, "");
+    } else {
+      if constexpr (kLast) TD_KS_ASM("=&v", TD_KS_C0, "", "", TD_KS_TAIL);
+      else TD_KS_ASM("=&v", TD_KS_C0, "", "", "");
+    }
+  } else {
+    if constexpr (kMask) {
+      if constexpr (kLast) TD_KS_ASM("+v", TD_KS_C1, TD_KS_MASK_L, TD_KS_MASK_H, TD_KS_TAIL);
+      else TD_KS_ASM("+v", TD_KS_C1, TD_KS_MASK_L, TD_KS_MASK_H, "");
+    } else {
+      if constexpr (kLast) TD_KS_ASM("+v", TD_KS_C1, "", "", TD_KS_TAIL);
+      else TD_KS_ASM("+v", TD_KS_C1, "", "", "");
+    }
+  }
+}
+
 // One k-step (16 time samples) of one wave: 4 lags x 6 (3) products.  ap / bp: the lane's A row
 // and B span of piece 0 at this k-step (pieces kBfPieceDw apart).  kZero: first step of a chain
 // (the accumulators start from the inline constant 0).  a_mask: null, or 4 dword masks that cut A
@@ -449,10 +569,21 @@ __device__ __forceinline__ float comp4(const float4& v, int q) {
 // measurable: the -5e-8 the sums of squares come out low by is the matrix pipe truncating the
 // 22-bit products h h' when it aligns the 16 products of an instruction -- the same bias with
 // MFMA chains of 128, 64 and 32 samples; tools/bias_probe.py.)
-template <bool kZero, int kBfPieceDw, bool kF16>
+//
+// kSkip (float16 form): the wave's lags are +0, +1, +4, +5 and the k-step is ONE block of instructions that
+// hipcc does not touch (bf_kstep_skip below); kOff: the k-step's dword offset from ap / bp as an
+// immediate, kLast: the chain ends here.
+template <bool kZero, int kBfPieceDw, bool kF16, bool kSkip = false, int kOff = 0, bool kLast = true>
 __device__ __forceinline__ void bf_kstep(const unsigned* __restrict__ ap,
                                          const unsigned* __restrict__ bp,
                                          const unsigned* a_mask, f32x16 (&acc)[4]) {
+  if constexpr (kSkip) {
+    static_assert(kF16, "lags +0, +1, +4, +5: the float16 form");
+    const unsigned a0 = lds_addr(ap), b0 = lds_addr(bp);
+    if (a_mask) bf_kstep_skip<kZero, true, kLast, kOff>(a0, a0 + 4 * kBfPieceDw, b0, b0 + 4 * kBfPieceDw, a_mask, acc);
+    else bf_kstep_skip<kZero, false, kLast, kOff>(a0, a0 + 4 * kBfPieceDw, b0, b0 + 4 * kBfPieceDw, a_mask, acc);
+    return;
+  }
   constexpr int kP = kF16 ? 2 : 3;
   u32x4 a[kP];
   unsigned d[kP][6];
@@ -509,10 +640,24 @@ __device__ __forceinline__ void bf_kstep(const unsigned* __restrict__ ap,
 }
 
 // kChain: k-steps per MFMA chain; the chain's sums are added into `total` (v_add_f32) when it ends.
-template <int kFrom, int kTo, int kBfPieceDw, bool kF16, int kChain>
+template <int kFrom, int kTo, int kBfPieceDw, bool kF16, int kChain, bool kSkip = false>
 __device__ __forceinline__ void bf_ksteps(const unsigned* __restrict__ ap,
                                           const unsigned* __restrict__ bp, f32x16 (&acc)[4],
                                           f32x16 (&total)[4]) {
+  if constexpr (kSkip) {
+    // (the step's offset is an immediate of its LDS reads: one step per instantiation)
+    if constexpr (kFrom < kTo) {
+      constexpr bool kLast = (kFrom + 1) % kChain == 0;
+      bf_kstep<kFrom % kChain == 0, kBfPieceDw, kF16, true, 8 * kFrom, kLast>(ap, bp, nullptr, acc);
+      if (kLast) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) total[r] += acc[r];
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      bf_ksteps<kFrom + 1, kTo, kBfPieceDw, kF16, kChain, true>(ap, bp, acc, total);
+    }
+    return;
+  }
 #pragma unroll
   for (int s = kFrom; s < kTo; ++s) {
     if (s % kChain == 0) bf_kstep<true, kBfPieceDw, kF16>(ap + 8 * s, bp + 8 * s, nullptr, acc);
@@ -550,6 +695,8 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int quad = wave & 1, mt = (wave >> 1) & 1, nt = wave >> 2;
+  // the plain float16 instances: the wave's lags are +0, +1, +4, +5 from e0 + 2 quad (bf_kstep_skip)
+  constexpr bool kSkip = kF16 && !kVirt;
 
   // One workgroup = one lag group of the work items part, part + n_part, ... (n_part = n_work:
   // one item each; n_part = workgroups / n_groups: a workgroup per CU that walks its share of
@@ -561,7 +708,7 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
   LagWork w = p.works[id];
   const int e0 = group * kLagsPerWg;                   // e_min == 0
   // the wave's first lag, where its four lags go in the slab, and (virtual images) its task
-  int lag_off = e0 + 4 * quad, out_lag = lag_off;
+  int lag_off = e0 + (kSkip ? 2 : 4) * quad, out_lag = lag_off;
   bool active = true, a_ext = false;
   const VirtImage* img = nullptr;
   VirtSeg vs = {0, 0, 0};
@@ -784,9 +931,13 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
       }
       return;
     }
-    float4 v[6];
+    // (the plain float16 instances mask the fetched rows where they are: nothing reads them after this)
+    float4 vcopy[6];
+    float4 (&v)[6] = kSkip ? const_cast<float4 (&)[6]>(pfr) : vcopy;
+    if constexpr (!kSkip) {
 #pragma unroll
-    for (int s = 0; s < 6; ++s) v[s] = pfr[s];
+      for (int s = 0; s < 6; ++s) vcopy[s] = pfr[s];
+    }
     if constexpr (kVirt) {
       if (!vinside(ut))
 #pragma unroll
@@ -949,11 +1100,11 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
     const unsigned* bp = cur + b_off;
     if (left >= kBfTile) {
       // whole tile: unrolled k-steps
-      bf_ksteps<0, 2, kBfPieceDw, kF16, kChain>(ap, bp, acc, total);
+      bf_ksteps<0, 2, kBfPieceDw, kF16, kChain, kSkip>(ap, bp, acc, total);
       if (more && early) { store(ut + kBfTile, nxt); sched_anchor(nxt); }
-      bf_ksteps<2, 6, kBfPieceDw, kF16, kChain>(ap, bp, acc, total);
+      bf_ksteps<2, 6, kBfPieceDw, kF16, kChain, kSkip>(ap, bp, acc, total);
       if (more && !early) { store(ut + kBfTile, nxt); sched_anchor(nxt); }
-      bf_ksteps<6, 8, kBfPieceDw, kF16, kChain>(ap, bp, acc, total);
+      bf_ksteps<6, 8, kBfPieceDw, kF16, kChain, kSkip>(ap, bp, acc, total);
     } else {
       // the last, cut tile of a slab: A stops at nk
       const int nk = (int)left;
@@ -967,7 +1118,7 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
 #pragma unroll
         for (int d = 0; d < 4; ++d)
           mask[d] = cnt >= 2 * d + 2 ? 0xffffffffu : cnt == 2 * d + 1 ? 0x0000ffffu : 0u;
-        bf_kstep<false, kBfPieceDw, kF16>(ap + (t0 >> 1), bp + (t0 >> 1), mask, acc);
+        bf_kstep<false, kBfPieceDw, kF16, kSkip>(ap + (t0 >> 1), bp + (t0 >> 1), mask, acc);
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) total[r] += acc[r];
@@ -1018,7 +1169,8 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
   float* slab = p.partial + (size_t)part * p.e_pad * p.ca_pad * p.cb_pad;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    float* pe = slab + (size_t)(e0 + 4 * quad + r) * p.ca_pad * p.cb_pad;
+    const int lag = kSkip ? out_lag + (r & 1) + 4 * (r >> 1) : out_lag + r;
+    float* pe = slab + (size_t)lag * p.ca_pad * p.cb_pad;
     const int lr = lane & 31, lk = lane >> 5;
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
