@@ -31,6 +31,15 @@ def is_stale():
   return any(os.path.getmtime(d) > t for d in deps)
 
 
+def compile_flags(csrc=CSRC):
+  """The hipcc flags every source is compiled with (tools/isa_diff.py compiles with the same)."""
+  # -fno-slp-vectorize: hipcc's SLP pass packs adjacent f32 FMAs into v_pk_fma_f32, which
+  # issues slower than the two v_fma_f32 it replaces on gfx950 (measured on the FIR kernel)
+  flags = ['--offload-arch=' + ARCH, '-O3', '-fPIC', '-std=c++17', '-fno-slp-vectorize',
+           '-Wno-unused-result', '-I' + os.path.join(ROOT, 'include'), '-I' + csrc]
+  return flags + os.environ.get('TD_EXTRA_HIPCC_FLAGS', '').split()   # development: ablation macros
+
+
 def build(force=False, verbose=False):
   """Compiles every HIP source for gfx950 into one shared library."""
   if not force and not is_stale():
@@ -38,11 +47,7 @@ def build(force=False, verbose=False):
   objs = []
   obj_dir = os.path.join(PKG, 'csrc', '_obj')
   os.makedirs(obj_dir, exist_ok=True)
-  # -fno-slp-vectorize: hipcc's SLP pass packs adjacent f32 FMAs into v_pk_fma_f32, which
-  # issues slower than the two v_fma_f32 it replaces on gfx950 (measured on the FIR kernel)
-  flags = ['--offload-arch=' + ARCH, '-O3', '-fPIC', '-std=c++17', '-fno-slp-vectorize',
-           '-Wno-unused-result', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC]
-  flags += os.environ.get('TD_EXTRA_HIPCC_FLAGS', '').split()   # development: ablation macros
+  flags = compile_flags()
   procs = []
   for src in sources():
     obj = os.path.join(obj_dir, os.path.basename(src) + '.o')

@@ -416,7 +416,7 @@ __global__ __launch_bounds__(NL * DQ == 32 ? 256 : 128) void predict_fir_wave_ke
     const float* __restrict__ w, const float* __restrict__ bias, int d_total, int q0, int dq,
     int accumulate, float* __restrict__ out, long long ldout) {
   constexpr int V = NL * DQ;          // completed values per body and lane (32 or 64)
-  constexpr int P = NL;               // rows of load prefetch: a whole body (HBM latency, see lagcov.hip)
+  constexpr int P = NL;               // rows of load prefetch: a whole body (HBM latency, see lag_targets.hip)
   static_assert(V == 32 || V == 64, "tile width");
   extern __shared__ float wave_lds[];
   const int tid = threadIdx.x, lane = tid & 63;

@@ -1159,7 +1159,7 @@ int td_stats_accumulate_parts(td_handle* h, td_stats* s, const float* x_dev, int
 namespace {
 // out[r][k] = x[row_lo + r][32 (k < 32 ? ti : tj) + (k & 31)], zero past channel c; the largest
 // magnitude of every column of the copy goes into tab (the float16 kernel's channel scales:
-// chan_max_kernel's table, lagcov.hip)
+// chan_max_kernel's table, lag_util.hip)
 __global__ __launch_bounds__(256) void gather_tile_pair_kernel(const float* __restrict__ x, long long ldx,
                                                                int c, long long row_lo, long long rows,
                                                                int ti, int tj, float* __restrict__ out,
@@ -1297,7 +1297,7 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
   LagcovPlan mp;
   TargetsPlan tp;
   VirtPlan vp;                   // <= 32 channels: the float16 kernel on virtual images (lagcov.hip)
-  Narrow16Plan np16;             // <= 16 channels: matrix + targets in one streaming kernel (lagcov.hip)
+  Narrow16Plan np16;             // <= 16 channels: matrix + targets in one streaming kernel (lag_narrow16.hip)
   if (h->narrow16) TD_TRY(td_narrow16_plan(h, s->c1, s->d, s->pre1, s->l1, ldx, ldy, syx, &np16));
   const bool n16 = np16.ok;
   if (do_main && n16) TD_TRY(ensure_window_capacity(h, s, s->n_files + num_files));
@@ -1422,12 +1422,7 @@ int accumulate_fused(td_handle* h, td_stats* s, const float* x_dev, int64_t ldx,
         // nobody measured the channel maxima on the way (a pre-context, a MAIN-only call): a pass of
         // its own over the rows of the array that hold this call's recordings
         TD_TRY(td_chan_tab_scratch(h, &tab));
-        long long lo = vp.works[0].a_row0, hi = lo;
-        for (const LagWork& wk : vp.works) {
-          lo = wk.a_row0 < lo ? wk.a_row0 : lo;
-          hi = wk.a_row0 + wk.a_valid > hi ? wk.a_row0 + wk.a_valid : hi;
-        }
-        TD_TRY(td_chan_max(h, x_dev, ldx, s->c1, lo, hi, tab));
+        TD_TRY(td_chan_max_works(h, x_dev, ldx, s->c1, vp.works, tab));
         own_tab = true;
       }
       TD_TRY(td_lagcov_virt_launch(h, &vp, x_dev, ldx, base, tab, s->g + s->off_fxx, !s->fresh_main, &job));

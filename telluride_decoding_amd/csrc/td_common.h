@@ -437,6 +437,8 @@ struct LagReduceJob {
   const struct VirtMap* vmap = nullptr;
   long long slab_elems = 0;
 };
+// The reduction launch of a dense job (lagcov.hip; no vmap, no mirror: those are the caller's).
+int td_lagcov_reduce(td_handle* h, const LagReduceJob& job);
 
 // td_lagcov in two steps, for callers that run several kernels out of ONE scratch block and
 // reduce them in one launch: the plan fixes the work list and the scratch bytes, the launch
@@ -455,7 +457,7 @@ struct LagcovPlan {
   unsigned* scale_out = nullptr; // IN, optional: LagParams::scale_out / zero_tab of the float16 kernel
   unsigned* zero_tab = nullptr;
   unsigned* tab = nullptr;       // channel maxima of x, already filled (by the targets kernel);
-                                 // null: the launch measures the maxima of x itself (chan_max_kernel)
+                                 // null: the launch measures the maxima of x itself (td_chan_max_works)
   int few_g = 8, ca_eff = 0, cb = 0, e_count = 0;
   int small_lpt = 8;             // skinny kernel: lags per thread (4 x that per workgroup)
   long long total = 0, nwg = 0;
@@ -484,8 +486,11 @@ struct VirtPlan {
   long long slab_elems = 0, total = 0, grid = 0;
   size_t scratch_bytes = 0;
 };
-// largest magnitudes of the channels of x over the rows [row0, row1) into a zeroed table (<= 128 channels)
+// largest magnitudes of the channels of x over the rows [row0, row1) into a zeroed table (<= 128 channels);
+// td_chan_max_works: over the rows of the array that hold the recordings of a (non-empty) work list (lag_util.hip)
 int td_chan_max(td_handle* h, const float* x, int64_t ldx, int c, long long row0, long long row1, unsigned* tab);
+int td_chan_max_works(td_handle* h, const float* x, int64_t ldx, int c, const std::vector<LagWork>& works,
+                      unsigned* tab);
 int td_lagcov_virt_plan(td_handle* h, const float* x, int64_t ldx, int c, const std::vector<LagSeg>& segs,
                         int l, VirtPlan* plan);
 int td_lagcov_virt_launch(td_handle* h, VirtPlan* plan, const float* x, int64_t ldx, void* scratch,
@@ -497,7 +502,7 @@ int td_lagcov_virt(td_handle* h, const float* x, int64_t ldx, int c, const std::
 // The handle's channel-maximum table for the call that is being queued (allocated on first use).
 int td_chan_tab(td_handle* h, unsigned** tab);
 
-// The same for the targets path (td_lagcov_targets): one matrix-core kernel per target column.
+// The same for the targets path (td_lagcov_targets, lag_targets.hip): one matrix-core kernel per target column.
 struct TargetsPlan {
   LagParams p;
   std::vector<LagWork> works;
@@ -524,7 +529,7 @@ int td_lagcov_targets_launch(td_handle* h, TargetsPlan* plan, void* scratch, dou
                              bool accumulate, TargetsOutputs* out);
 
 // <= 16 channels, <= 32 lags, 1..4 targets: ONE streaming kernel for the lagged covariance, the targets,
-// the column sums (lagcov_narrow16_kernel).  plan->ok = false when the shape is not its.
+// the column sums (lagcov_narrow16_kernel, lag_narrow16.hip).  plan->ok = false when the shape is not its.
 struct Narrow16Plan {
   bool ok = false;
   int c = 0, d = 0, pre = 0, l1 = 0, n_lg = 1, lpw = 0;
@@ -560,7 +565,7 @@ int td_add_reversed_transposed(td_handle* h, const double* src, int e_count, int
 int td_mirror_upper(td_handle* h, double* g_dev, int c, int ld);
 
 // [y]^T x~ per signed lag on the lane-per-channel kernel, plus the per-segment column sums
-// of B over [u_begin, u_end) and the column sums of Y (lagcov.hip).  *handled = false when
+// of B over [u_begin, u_end) and the column sums of Y (lag_targets.hip).  *handled = false when
 // the shape is outside that kernel's range (nothing was done).
 // g_dev [e_count][cb] += sum_u y~[u] b~[u + e], e = e_min .. e_min + e_count - 1, for ONE column y
 // (zero outside the rows [u_begin, u_end) of a segment) against a view of any width, any lag
@@ -587,7 +592,7 @@ int td_gram(td_handle* h, const float* x, int64_t ldx, int c1, const float* x2, 
 // (defer: the matrix kernel only; the caller runs the reduction it describes.  Its scratch stays
 // untouched until then.)
 
-// Column sums in float64 of rows [r0, r1) per segment (lagcov.hip).
+// Column sums in float64 of rows [r0, r1) per segment (lag_util.hip).
 int td_colsum(td_handle* h, const float* a, int64_t lda, int ca, const std::vector<LagSeg>& segs,
               double* out_dev, bool accumulate);
 
