@@ -448,7 +448,8 @@ __device__ __forceinline__ float comp4(const float4& v, int q) {
 // in front of 12 matrix instructions, inside the wave's own chain ds_read -> v_perm -> v_mov -> v_mfma.)
 // hipcc cannot be told to keep such a layout (sub-tuples of ext_vector_type(8) values were copied out
 // again), so the k-step is one asm block on FIXED registers v[216:255] -- the operand list cannot name a
-// part of a register tuple:
+// part of a register tuple.  (This block, one k-step, is the masked k-step of a cut tile; the whole
+// k-steps of a tile run as the pipelined blocks below, on the same registers.)
 //   v[216:219] A h   v[220:223] A l   v[224:230] B h d[0..6]   v[232:238] B l d[0..6]
 //   v[240:245] q of B h               v[248:253] q of B l
 // Same operand words and the same order per lag as bf_kstep: l h', h l', h h', the four lags in turn.
@@ -526,33 +527,118 @@ __device__ __forceinline__ float comp4(const float4& v, int q) {
   asm volatile(TD_KS_BODY(C, ML, MH, TAIL)                                               \
                : OUT(acc[0]), OUT(acc[1]), OUT(acc[2]), OUT(acc[3]) : TD_KS_INS : TD_KS_CLOBBER)
 
+// ---- a RUN of whole k-steps as one block: the LDS reads of k-step s + 1 inside the MFMAs of k-step s ----
+// The block above starts every k-step with an exposed LDS round trip (twelve reads, the wait, the shuffles)
+// that only the SIMD's other wave can fill, and both waves run this same program.  A run of whole k-steps
+// (bf_ksteps: 0-1, 2-5, 6-7 of a tile, the staging stores between them) is ONE block instead, and only its
+// first k-step has that head.  No register is added: the two B blocks (d v[224:230] + q v[240:245], d
+// v[232:238] + q v[248:253]) swap roles from one k-step to the next.  With H the block that holds B h and L
+// the one that holds B l, a k-step's twelve MFMAs are  1-4: A l x H,  5-8: A h x L,  9-12: A h x H  (the
+// order per lag as before: l h', h l', h h'), so
+//   A l  is dead after MFMA 4:   A l of the next k-step is read there;
+//   L    is dead after MFMA 8:   B h of the next k-step is read into L.d there (L is the next k-step's H);
+//   H, A h are dead after MFMA 12: B l of the next k-step into H.d and A h there (needed at its MFMA 5).
+// Every read has at least four MFMAs between its issue and the wait for it.  The operand words and the
+// MFMA order are those of TD_KS_BODY, k-step by k-step.
+// What the block owes the hardware (hipcc inserts nothing inside it):
+//  - an LDS read overwrites an operand register only after the LAST MFMA that reads it has issued (the
+//    three places above; the shuffles that rewrite a q block come after the wait for its d block, which
+//    is issued after the q block's last reader);
+//  - two wait states between a VALU write and the MFMA that reads it: the six shuffles of a block are
+//    issued together behind the MFMA that takes d[0..3] as it lies -- q[3] is followed by two shuffles
+//    before the MFMA that reads q[0..3], q[5] by those and two MFMAs before the one that reads q[2..5];
+//  - every lgkmcnt(N) is counted from the reads outstanding at that point (LDS operations return in
+//    order; anything older that hipcc left outstanding only makes the wait longer).  At the top of a
+//    k-step twelve are out, in the order A l 2, B h 4 | B l 4, A h 2 (the head: B h, A l | B l, A h):
+//    lgkmcnt(6) is A l and B h.  In front of MFMA 5, B l 4 and A h 2 and the next A l 2 are out:
+//    lgkmcnt(2) is B l and A h -- lgkmcnt(0) in the run's last k-step, which reads nothing ahead;
+//  - so no read is in flight into v[216:255] when control leaves the run: hipcc's staging code between
+//    the runs may use those registers (they are clobbers, not operands);
+//  - kLast: the wait between the last MFMA and a VALU read of its result, as above.
+// The state at a run's entry is that of the single block: B h goes to v[224:230], every run has an even
+// number of k-steps.  kb = 4 (k0 + 6): the byte offset of the span's seventh dword.
+#define TD_KP_RD_A(D, P, K)                                                              \
+  "ds_read2_b32 v[" #D ":" #D "+1], " P " offset0:%[k0]+" #K " offset1:%[k0]+" #K "+1\n"     \
+  "ds_read2_b32 v[" #D "+2:" #D "+3], " P " offset0:%[k0]+" #K "+2 offset1:%[k0]+" #K "+3\n"
+#define TD_KP_RD_B(D, P, K)                                                              \
+  TD_KP_RD_A(D, P, K)                                                                    \
+  "ds_read2_b32 v[" #D "+4:" #D "+5], " P " offset0:%[k0]+" #K "+4 offset1:%[k0]+" #K "+5\n" \
+  "ds_read_b32 v[" #D "+6], " P " offset:%[kb]+4*" #K "\n"
+#define TD_KP_HEAD                                                                       \
+  TD_KP_RD_B(224, "%[bp0]", 0) TD_KP_RD_A(220, "%[ap1]", 0)                              \
+  TD_KP_RD_B(232, "%[bp1]", 0) TD_KP_RD_A(216, "%[ap0]", 0)
+#define TD_KP_Q(D, Q)                                                                    \
+  "v_alignbit_b32 v[" #Q "], v[" #D "+1], v[" #D "], 16\n"                               \
+  "v_alignbit_b32 v[" #Q "+1], v[" #D "+2], v[" #D "+1], 16\n"                           \
+  "v_alignbit_b32 v[" #Q "+2], v[" #D "+3], v[" #D "+2], 16\n"                           \
+  "v_alignbit_b32 v[" #Q "+3], v[" #D "+4], v[" #D "+3], 16\n"                           \
+  "v_alignbit_b32 v[" #Q "+4], v[" #D "+5], v[" #D "+4], 16\n"                           \
+  "v_alignbit_b32 v[" #Q "+5], v[" #D "+6], v[" #D "+5], 16\n"
+#define TD_KP_MFMA(r, A, B, I, C)                                                        \
+  "v_mfma_f32_32x32x16_f16 %" #r ", " A ", v[" #B "+" #I ":" #B "+" #I "+3], " C "\n"
+// one k-step: B h in (HD, HQ), B l in (LD, LQ); W: what stays out at the second wait; RD_*: the reads ahead
+#define TD_KP_STEP(C, HD, HQ, LD, LQ, RD_AL, W, RD_BH, RD_BL_AH)                         \
+  "s_waitcnt lgkmcnt(6)\n"                                                               \
+  TD_KP_MFMA(0, "v[220:223]", HD, 0, C(0))                                               \
+  TD_KP_Q(HD, HQ)                                                                        \
+  TD_KP_MFMA(1, "v[220:223]", HQ, 0, C(1))                                               \
+  TD_KP_MFMA(2, "v[220:223]", HD, 2, C(2))                                               \
+  TD_KP_MFMA(3, "v[220:223]", HQ, 2, C(3))                                               \
+  RD_AL                                                                                  \
+  "s_waitcnt lgkmcnt(" #W ")\n"                                                          \
+  TD_KP_MFMA(0, "v[216:219]", LD, 0, "%0")                                               \
+  TD_KP_Q(LD, LQ)                                                                        \
+  TD_KP_MFMA(1, "v[216:219]", LQ, 0, "%1")                                               \
+  TD_KP_MFMA(2, "v[216:219]", LD, 2, "%2")                                               \
+  TD_KP_MFMA(3, "v[216:219]", LQ, 2, "%3")                                               \
+  RD_BH                                                                                  \
+  TD_KP_MFMA(0, "v[216:219]", HD, 0, "%0")                                               \
+  TD_KP_MFMA(1, "v[216:219]", HQ, 0, "%1")                                               \
+  TD_KP_MFMA(2, "v[216:219]", HD, 2, "%2")                                               \
+  TD_KP_MFMA(3, "v[216:219]", HQ, 2, "%3")                                               \
+  RD_BL_AH
+// an even / odd k-step that reads the k-step at dword offset K ahead, and the odd one that ends a run
+#define TD_KP_EVEN(C, K)                                                                 \
+  TD_KP_STEP(C, 224, 240, 232, 248, TD_KP_RD_A(220, "%[ap1]", K), 2,                     \
+             TD_KP_RD_B(232, "%[bp0]", K), TD_KP_RD_B(224, "%[bp1]", K) TD_KP_RD_A(216, "%[ap0]", K))
+#define TD_KP_ODD(C, K)                                                                  \
+  TD_KP_STEP(C, 232, 248, 224, 240, TD_KP_RD_A(220, "%[ap1]", K), 2,                     \
+             TD_KP_RD_B(224, "%[bp0]", K), TD_KP_RD_B(232, "%[bp1]", K) TD_KP_RD_A(216, "%[ap0]", K))
+#define TD_KP_ODD_END(C) TD_KP_STEP(C, 232, 248, 224, 240, "", 0, "", "")
+#define TD_KP_RUN2(C) TD_KP_HEAD TD_KP_EVEN(C, 8) TD_KP_ODD_END(TD_KS_C1)
+#define TD_KP_RUN4 TD_KP_HEAD TD_KP_EVEN(TD_KS_C1, 8) TD_KP_ODD(TD_KS_C1, 16) TD_KP_EVEN(TD_KS_C1, 24) TD_KP_ODD_END(TD_KS_C1)
+#define TD_KP_ASM(OUT, BODY)                                                             \
+  asm volatile(BODY : OUT(acc[0]), OUT(acc[1]), OUT(acc[2]), OUT(acc[3])                 \
+               : [ap0] "v"(ap0), [ap1] "v"(ap1), [bp0] "v"(bp0), [bp1] "v"(bp1),         \
+                 [k0] "n"(kOff), [kb] "n"(4 * (kOff + 6)) : TD_KS_CLOBBER)
+
 // the address of p in LDS (p points into the kernel's dynamic LDS)
 __device__ __forceinline__ unsigned lds_addr(const unsigned* p) {
   return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned*)p;
 }
 
-// ap0 / ap1, bp0 / bp1: LDS byte addresses of the lane's A row and B span in the pieces h / l.
-template <bool kZero, bool kMask, bool kLast, int kOff>
+// The masked k-step of a cut tile, one block per step.  ap0 / ap1, bp0 / bp1: LDS byte addresses of the
+// lane's A row and B span in the pieces h / l; kOff: the k-step's dword offset from them, an immediate.
+template <int kOff = 0>
 __device__ __forceinline__ void bf_kstep_skip(unsigned ap0, unsigned ap1, unsigned bp0, unsigned bp1,
                                               const unsigned* a_mask, f32x16 (&acc)[4]) {
-  unsigned m0 = 0, m1 = 0, m2 = 0, m3 = 0;
-  if constexpr (kMask) { m0 = a_mask[0]; m1 = a_mask[1]; m2 = a_mask[2]; m3 = a_mask[3]; }
-  if constexpr (kZero) {
-    if constexpr (kMask) {
-      if constexpr (kLast) TD_KS_ASM("=&v", TD_KS_C0, TD_KS_MASK_L, TD_KS_MASK_H, TD_KS_TAIL);
-      else TD_KS_ASM("=&v", TD_KS_C0, TD_KS_MASK_L, TD_KS_MASK_H, "");
-    } else {
-      if constexpr (kLast) TD_KS_ASM("=&v", TD_KS_C0, "", "", TD_KS_TAIL);
-      else TD_KS_ASM("=&v", TD_KS_C0, "", "", "");
-    }
+  const unsigned m0 = a_mask[0], m1 = a_mask[1], m2 = a_mask[2], m3 = a_mask[3];
+  TD_KS_ASM("+v", TD_KS_C1, TD_KS_MASK_L, TD_KS_MASK_H, TD_KS_TAIL);
+}
+
+// kSteps (2 or 4) whole k-steps from dword offset kOff as one pipelined block.  kZero: the run starts an
+// MFMA chain, kLast: it ends one.
+template <bool kZero, bool kLast, int kSteps, int kOff>
+__device__ __forceinline__ void bf_krun_skip(unsigned ap0, unsigned ap1, unsigned bp0, unsigned bp1,
+                                             f32x16 (&acc)[4]) {
+  static_assert(kSteps == 2 || (kSteps == 4 && !kZero && !kLast), "the runs of a tile: 2, 4, 2 k-steps");
+  if constexpr (kSteps == 4) TD_KP_ASM("+v", TD_KP_RUN4);
+  else if constexpr (kZero) {
+    if constexpr (kLast) TD_KP_ASM("=&v", TD_KP_RUN2(TD_KS_C0) TD_KS_TAIL);
+    else TD_KP_ASM("=&v", TD_KP_RUN2(TD_KS_C0));
   } else {
-    if constexpr (kMask) {
-      if constexpr (kLast) TD_KS_ASM("+v", TD_KS_C1, TD_KS_MASK_L, TD_KS_MASK_H, TD_KS_TAIL);
-      else TD_KS_ASM("+v", TD_KS_C1, TD_KS_MASK_L, TD_KS_MASK_H, "");
-    } else {
-      if constexpr (kLast) TD_KS_ASM("+v", TD_KS_C1, "", "", TD_KS_TAIL);
-      else TD_KS_ASM("+v", TD_KS_C1, "", "", "");
-    }
+    if constexpr (kLast) TD_KP_ASM("+v", TD_KP_RUN2(TD_KS_C1) TD_KS_TAIL);
+    else TD_KP_ASM("+v", TD_KP_RUN2(TD_KS_C1));
   }
 }
 
@@ -568,17 +654,16 @@ __device__ __forceinline__ void bf_kstep_skip(unsigned ap0, unsigned ap1, unsign
 // MFMA chains of 128, 64 and 32 samples; tools/bias_probe.py.)
 //
 // kSkip (float16 form): the wave's lags are +0, +1, +4, +5 and the k-step is ONE block of instructions that
-// hipcc does not touch (bf_kstep_skip below); kOff: the k-step's dword offset from ap / bp as an
-// immediate, kLast: the chain ends here.
-template <bool kZero, int kBfPieceDw, bool kF16, bool kSkip = false, int kOff = 0, bool kLast = true>
+// hipcc does not touch (bf_kstep_skip above).  Only the masked k-steps of a cut tile come this way, each the
+// end of a chain of its own; the whole k-steps of a tile run as pipelined blocks (bf_ksteps, bf_krun_skip).
+template <bool kZero, int kBfPieceDw, bool kF16, bool kSkip = false>
 __device__ __forceinline__ void bf_kstep(const unsigned* __restrict__ ap,
                                          const unsigned* __restrict__ bp,
                                          const unsigned* a_mask, f32x16 (&acc)[4]) {
   if constexpr (kSkip) {
-    static_assert(kF16, "lags +0, +1, +4, +5: the float16 form");
+    static_assert(kF16 && !kZero, "lags +0, +1, +4, +5: the float16 form, a masked step onto zeroed sums");
     const unsigned a0 = lds_addr(ap), b0 = lds_addr(bp);
-    if (a_mask) bf_kstep_skip<kZero, true, kLast, kOff>(a0, a0 + 4 * kBfPieceDw, b0, b0 + 4 * kBfPieceDw, a_mask, acc);
-    else bf_kstep_skip<kZero, false, kLast, kOff>(a0, a0 + 4 * kBfPieceDw, b0, b0 + 4 * kBfPieceDw, a_mask, acc);
+    bf_kstep_skip(a0, a0 + 4 * kBfPieceDw, b0, b0 + 4 * kBfPieceDw, a_mask, acc);
     return;
   }
   constexpr int kP = kF16 ? 2 : 3;
@@ -642,17 +727,17 @@ __device__ __forceinline__ void bf_ksteps(const unsigned* __restrict__ ap,
                                           const unsigned* __restrict__ bp, f32x16 (&acc)[4],
                                           f32x16 (&total)[4]) {
   if constexpr (kSkip) {
-    // (the step's offset is an immediate of its LDS reads: one step per instantiation)
-    if constexpr (kFrom < kTo) {
-      constexpr bool kLast = (kFrom + 1) % kChain == 0;
-      bf_kstep<kFrom % kChain == 0, kBfPieceDw, kF16, true, 8 * kFrom, kLast>(ap, bp, nullptr, acc);
-      if (kLast) {
+    // the run is one pipelined block (the k-steps' offsets are immediates of its LDS reads)
+    static_assert(kF16 && kFrom / kChain == (kTo - 1) / kChain, "a run lies within one MFMA chain");
+    constexpr bool kLast = kTo % kChain == 0;
+    const unsigned a0 = lds_addr(ap), b0 = lds_addr(bp);
+    bf_krun_skip<kFrom % kChain == 0, kLast, kTo - kFrom, 8 * kFrom>(a0, a0 + 4 * kBfPieceDw, b0,
+                                                                     b0 + 4 * kBfPieceDw, acc);
+    if (kLast) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) total[r] += acc[r];
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      bf_ksteps<kFrom + 1, kTo, kBfPieceDw, kF16, kChain, true>(ap, bp, acc, total);
+      for (int r = 0; r < 4; ++r) total[r] += acc[r];
     }
+    __builtin_amdgcn_sched_barrier(0);
     return;
   }
 #pragma unroll
@@ -1096,7 +1181,8 @@ __global__ __launch_bounds__(kBfThreads) void lagcov_split_kernel(LagParams p) {
     const unsigned* ap = cur + a_off;
     const unsigned* bp = cur + b_off;
     if (left >= kBfTile) {
-      // whole tile: unrolled k-steps
+      // whole tile: unrolled k-steps (the plain float16 instances: three pipelined runs, the staging
+      // stores between them -- no LDS read of a run is in flight there)
       bf_ksteps<0, 2, kBfPieceDw, kF16, kChain, kSkip>(ap, bp, acc, total);
       if (more && early) { store(ut + kBfTile, nxt); sched_anchor(nxt); }
       bf_ksteps<2, 6, kBfPieceDw, kF16, kChain, kSkip>(ap, bp, acc, total);
