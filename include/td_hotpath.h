@@ -613,6 +613,30 @@ int td_decode_ssd_stream(td_handle* h, const double* s1_dev, const double* s2_de
                          const double* params_host, const double* prior_host, double* state_dev,
                          double* out_dev);
 
+/* The whole window-size sweep of infer.run_reduction_test (infer.py:376-407) in two launches.
+ *   s1_dev / s2_dev  per-frame scores of speaker 1 / 2, float64 [frames, cols], row strides ld1 / ld2
+ *                    (td_frame_scores' output; cols > 1 only for reduction 'all')
+ *   labels_dev       attention labels, float64 [frames]
+ *   sizes_host       num_sizes (1..16) pairs {width, hop}
+ *   decoder          0 winner-take-all, 1 stepped, 2 none (decisions 0, correct 0: the caller decides
+ *                    from the means, e.g. with td_decode_ssd)
+ * Size k has n_k = td_window_count(frames, width_k, hop_k) full windows; the outputs hold the sizes one
+ * after the other, total_windows = sum n_k:
+ *   means_dev     [3][total_windows] float64: window means of s1, s2 and the labels.  Each is bit for
+ *                 bit td_window_means of the column (several columns: their means added in column order
+ *                 and multiplied by the float64 1.0 / cols, as infer._window_means_host combines them).
+ *   decisions_dev [total_windows] u8: td_decide_wta / td_decide_step (one trial per size, state 0.5)
+ *   summary_dev   [num_sizes][2] int64: {end_first_section = first window whose label mean's truth
+ *                 value differs from window 0's, 0 if none; correct = windows with decision xor
+ *                 (label mean != 0)}.  A size without a full window has {0, 0}.
+ * Fixed-order float64 and integer reductions, no atomics: two calls give the same bits.
+ * TD_ERR_INVALID, before anything is queued: a NULL argument, num_sizes outside 1..16, width < 1,
+ * hop < 1, cols < 1, ld1 or ld2 < cols, frames < 0, decoder outside 0..2. */
+int td_attention_sweep(td_handle* h, const double* s1_dev, int64_t ld1, const double* s2_dev,
+                       int64_t ld2, int cols, const double* labels_dev, int64_t frames,
+                       const int* sizes_host, int num_sizes, int decoder, double* means_dev,
+                       uint8_t* decisions_dev, int64_t* summary_dev);
+
 /* ------------------------------------------------------------------ fused decode
  * Raw EEG -> decisions in one pass: FIR predict, global-statistics correlation
  * against two candidate envelopes, window means, winner-take-all.  Equivalent to

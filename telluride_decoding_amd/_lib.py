@@ -145,6 +145,7 @@ SIGNATURES = {
     'td_decode_ssd': [_vp, _vp, _vp, _pi64, _i, _pd, _pd, _vp],
     'td_decode_ssd_stream': [_vp, _vp, _vp, _pi64, _i, _pd, _pd, _vp, _vp],
     'td_ssd_state_doubles': [],
+    'td_attention_sweep': [_vp, _vp, _i64, _vp, _i64, _i, _vp, _i64, _c.POINTER(_i), _i, _i, _vp, _vp, _vp],
     'td_decode_fused': [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _pi64, _i, _i,
                         _i, _pd, _vp, _vp],
     'td_sos_filter': [_vp, _vp, _i, _i64, _i, _pi64, _i, _pd, _i, _i, _pd, _i, _vp, _vp, _pi64, _vp, _i64],

@@ -8,6 +8,10 @@ regressor `BrainModelDNN` (:486-549) and the match-mismatch classifier `BrainMod
 (:554-620), both trained on the GPU.  The Keras `BrainModel` base class and the TensorBoard
 plumbing of that file are out of scope.
 """
+import base64
+import json
+import os
+
 import numpy as np
 
 from telluride_decoding_amd import brain_data
@@ -27,6 +31,167 @@ def _as_2d_device(h, a):
   if a.ndim == 1:
     a = a.reshape(-1, 1)
   return h.to_device(a)
+
+
+# ---------------------------------------------------------------- saved models
+# The project's own model file: model_dir/brain_model.json holds model_to_dict's
+# JSON.  A TensorFlow SavedModel can be neither written nor read.  The optimizer's accumulators are
+# not saved: a loaded model is compiled as it was, with a fresh optimizer.
+MODEL_FORMAT_VERSION = 1
+MODEL_FILE_NAME = 'brain_model.json'
+_METADATA_KEYS = ('telluride_metadata', 'telluride_inputs', 'telluride_output')
+
+
+def array_to_dict(a):
+  """{'dtype', 'shape', 'data'} of an array: data = base64 of its little-endian bytes (bit exact)."""
+  a = np.asarray(a)
+  little = np.ascontiguousarray(a, dtype=a.dtype.newbyteorder('<'))
+  return {'dtype': a.dtype.name, 'shape': [int(n) for n in a.shape],
+          'data': base64.b64encode(little.tobytes()).decode('ascii')}
+
+
+def array_from_dict(d):
+  dtype = np.dtype(d['dtype'])
+  flat = np.frombuffer(base64.b64decode(d['data']), dtype=dtype.newbyteorder('<'))
+  return flat.astype(dtype).reshape([int(n) for n in d['shape']])
+
+
+def _add_metadata(self, flags, dataset=None):
+  """Keeps `flags` (JSON-able, probably a dict of option values) with the model as
+  `telluride_metadata`, and with a dataset -- a brain_data.Dataset or any iterable of (dict, y)
+  minibatches -- the shapes of its inputs, {name: [batch or None, width]}, and of its output as
+  `telluride_inputs` / `telluride_output` (reference brain_model.py:255-280).  All three are saved
+  with the model; infer_decoder.Decoder.load_decoding_model reads them back."""
+  json.dumps(flags)                                  # TypeError now, as the reference, if not JSON-able
+  self.telluride_metadata = flags
+  if not dataset:
+    return
+  if _is_dataset(dataset):
+    spec_in, spec_out = dataset.element_spec
+    inputs = {k: list(v.shape) for k, v in spec_in.items()}
+    output = list(spec_out.shape)
+  elif hasattr(dataset, '__iter__') and not isinstance(dataset, (str, bytes, dict)):
+    inputs = output = None
+    for feats, y in dataset:
+      inputs = {k: [int(n) for n in np.shape(_host(v))] for k, v in feats.items()}
+      output = [int(n) for n in np.shape(_host(y))]
+      break
+    if inputs is None:
+      return
+  else:
+    raise TypeError('dataset parameter must be tf.data.Dataset type.')
+  self.telluride_inputs = inputs
+  self.telluride_output = output
+
+
+def _optimizer_settings(model):
+  opt = getattr(model, 'optimizer', None)
+  if opt is None:
+    return None
+  return {'class': type(opt).__name__, 'config': dict(vars(opt))}
+
+
+def model_to_dict(model):
+  """A fitted (or unfitted) BrainModelLinearRegression, BrainModelDNN, BrainModelClassifier or
+  cca.BrainModelCCA as a JSON-able dict: format version, class name, constructor arguments, compile
+  settings, weights ({'dtype', 'shape', 'data'} each, exactly what get_weights / weight_matrices
+  return; None for a weight a model does not have yet) and add_metadata's three entries."""
+  name = type(model).__name__
+  if name == 'BrainModelLinearRegression' and isinstance(model, BrainModelLinearRegression):
+    args = {'input_channels': int(model._c1), 'pre_context': int(model._pre),
+            'post_context': int(model._post), 'output_width': int(model._output_width),
+            'regularization_lambda': float(model._regularization_lambda)}
+    settings = {'optimizer': None, 'loss': 'mse'}
+    weights = model.weight_matrices
+  elif isinstance(model, _BrainModelMlp) and name in ('BrainModelDNN', 'BrainModelClassifier'):
+    args = {'input_widths': [int(getattr(model, view[1])) for view in model._VIEWS],
+            'output_width': int(model._output_width),
+            'num_hidden_list': [int(u) for u in model.num_hidden_list], 'seed': None if model._seed is None else int(model._seed)}
+    settings = {'optimizer': _optimizer_settings(model),
+                'loss': model.loss if name == 'BrainModelDNN' else 'binary_crossentropy'}
+    weights = model.get_weights()
+  elif name == 'BrainModelCCA' and hasattr(model, 'rot_x'):
+    args = {'input_widths': [int(model._input1_width), int(model._input2_width)],
+            'cca_dims': int(model._cca_dims),
+            'regularization_lambda': float(model._regularization_lambda)}
+    settings = {'optimizer': None, 'loss': 'cca_pearson_correlation_first'}
+    weights = model.weight_matrices
+  else:
+    raise TypeError('model_to_dict: not one of this package\'s models, but a %s.' % type(model))
+  out = {'format_version': MODEL_FORMAT_VERSION, 'class_name': name, 'constructor': args,
+         'compile': settings,
+         'weights': [None if w is None else array_to_dict(w) for w in weights]}
+  for key in _METADATA_KEYS:
+    out[key] = getattr(model, key, None)
+  return out
+
+
+def _shape_dataset(c1, c2, d, pre=0, post=0):
+  """A Dataset without frames that has the widths a model's constructor reads."""
+  empty = lambda c: np.zeros((0, c), np.float32)
+  return brain_data.Dataset([(empty(c1), empty(c2), empty(d), empty(1))], 1, pre, post)
+
+
+def model_from_dict(d):
+  """The model model_to_dict described, built without a dataset, compiled as it was (a fresh optimizer
+  of the saved class and hyper-parameters) and holding the saved weights bit for bit."""
+  if not isinstance(d, dict) or 'class_name' not in d:
+    raise TypeError('model_from_dict needs the dict of model_to_dict, not a %s.' % type(d))
+  if d.get('format_version') != MODEL_FORMAT_VERSION:
+    raise ValueError('Saved model of format version %r; this package reads version %d.' %
+                     (d.get('format_version'), MODEL_FORMAT_VERSION))
+  name, args, settings = d['class_name'], d['constructor'], d.get('compile') or {}
+  weights = [None if w is None else array_from_dict(w) for w in d['weights']]
+  if name == 'BrainModelLinearRegression':
+    model = BrainModelLinearRegression(
+        _shape_dataset(args['input_channels'], 1, args['output_width'], args['pre_context'],
+                       args['post_context']), args['regularization_lambda'])
+    model.compile()
+    if weights[0] is not None:
+      model.w_estimate, model.b_estimate = weights[0], weights[1]
+  elif name in ('BrainModelDNN', 'BrainModelClassifier'):
+    cls = BrainModelDNN if name == 'BrainModelDNN' else BrainModelClassifier
+    widths = list(args['input_widths']) + [1]
+    model = cls(_shape_dataset(widths[0], widths[1], args['output_width']),
+                list(args['num_hidden_list']), seed=args.get('seed', 0))
+    opt = settings.get('optimizer')
+    if opt is not None:
+      if opt['class'] != cls._OPTIMIZER.__name__:
+        raise ValueError('%s was compiled with %s; only %s is implemented.' %
+                         (name, opt['class'], cls._OPTIMIZER.__name__))
+      optimizer = cls._OPTIMIZER(**opt['config'])
+      if name == 'BrainModelDNN':
+        model.compile(optimizer=optimizer, loss=settings.get('loss', 'mse'))
+      else:
+        model.compile(optimizer=optimizer)
+    model.set_weights(weights)
+  elif name == 'BrainModelCCA':
+    from telluride_decoding_amd import cca
+    model = cca.BrainModelCCA(_shape_dataset(args['input_widths'][0], args['input_widths'][1], 1),
+                              cca_dims=args['cca_dims'],
+                              regularization_lambda=args['regularization_lambda'])
+    model.compile()
+    if weights[0] is not None:
+      model.set_weights(weights)
+  else:
+    raise ValueError('Saved model of unknown class %r.' % (name,))
+  for key in _METADATA_KEYS:
+    if d.get(key) is not None:
+      setattr(model, key, d[key])
+  return model
+
+
+def _save_model(self, model_dir):
+  """Writes the model to model_dir/brain_model.json (the directory is created); load_model reads it."""
+  os.makedirs(model_dir, exist_ok=True)
+  with open(os.path.join(model_dir, MODEL_FILE_NAME), 'w') as f:
+    json.dump(model_to_dict(self), f)
+
+
+def load_model(model_dir):
+  """The model that `model.save(model_dir)` wrote."""
+  with open(os.path.join(model_dir, MODEL_FILE_NAME), 'r') as f:
+    return model_from_dict(json.load(f))
 
 
 def pearson_correlation(x, y):
@@ -276,6 +441,9 @@ class BrainModelLinearRegression(object):
     self._w_dev = self._b_dev = None
     self.metrics_names = ['loss', 'pearson_correlation_first']
 
+  save = _save_model
+  add_metadata = _add_metadata
+
   def compile(self, optimizer=None, loss='mse', metrics=pearson_correlation_first,
               learning_rate=1e-3, **kwargs):
     """Accepted for drop-in use (brain_model.py:343-359); nothing to compile: the fit is closed
@@ -482,6 +650,7 @@ class _BrainModelMlp(object):
       setattr(self, width, int(input_dataset.element_spec[0][feature].shape[-1]))
     self._output_width = int(input_dataset.element_spec[1].shape[-1])
     self.num_hidden_list = [int(u) for u in num_hidden_list]
+    self._seed = seed
     self._widths = ([sum(getattr(self, view[1]) for view in self._VIEWS)] + self.num_hidden_list +
                     [self._output_width])
     rng = np.random.default_rng(seed)
@@ -495,6 +664,9 @@ class _BrainModelMlp(object):
     self._state = None         # the optimizer's accumulators, in the parameters' layout
     self.optimizer = None
     self.metrics_names = list(self._HISTORY_KEYS)
+
+  save = _save_model
+  add_metadata = _add_metadata
 
   # -- parameters (W1's rows: input_1's lag layout, then input_2's) ------------
   def _shapes(self):

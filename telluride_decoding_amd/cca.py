@@ -181,6 +181,25 @@ class BrainModelCCA(object):
     """Accepted for drop-in use (cca.py:196-212); the fit is closed form, nothing to compile."""
     del optimizer, loss, metrics, learning_rate, kwargs
 
+  # saved models (brain_model.model_to_dict / load_model; DESIGN section 24)
+  save = brain_model._save_model
+  add_metadata = brain_model._add_metadata
+
+  @property
+  def weight_matrices(self):
+    """[mean_x, mean_y, rot_x, rot_y]: what a saved model keeps (None each before the fit)."""
+    return [self.mean_x, self.mean_y, self.rot_x, self.rot_y]
+
+  def get_weights(self):
+    return self.weight_matrices
+
+  def set_weights(self, weights):
+    """weights: [mean_x, mean_y, rot_x, rot_y], kept as they are (no conversion)."""
+    if len(weights) != 4:
+      raise ValueError('Expected 4 weight arrays (two means, two rotations), got %d' % len(weights))
+    self.mean_x, self.mean_y, self.rot_x, self.rot_y = (np.asarray(w) for w in weights)
+    self._dev = None
+
   def fit(self, dataset, epochs=1):
     del epochs
     if not isinstance(dataset, brain_data.Dataset) and not hasattr(dataset, '__iter__'):

@@ -11,8 +11,10 @@ cca.BrainModelCCA, the correlation + LDA stage is infer_decoder.Decoder.train, w
 
 Where this module departs from the reference:
   * the options are a plain class and the command line is argparse (no absl, no attr);
-  * tensorboard_dir is accepted and ignored; saved_model_dir receives decoder_model.json only (a
-    SavedModel is a TensorFlow file format);
+  * tensorboard_dir is accepted and ignored; saved_model_dir receives one file, decoder_model.json,
+    which holds the decoder's parameters and, under 'decoding_model', the fitted model in this
+    package's own format (brain_model.model_to_dict; a TensorFlow SavedModel is not written).
+    infer.load_model reads the directory back;
   * 'classifier' gets the parsed hidden-unit list (the reference hands the constructor the raw string
     and fails there), and, having no decoder in infer_decoder.create_decoder, skips the LDA stage:
     d' is None;
@@ -258,6 +260,9 @@ def run_decoding_experiment(my_flags):
   test_model = create_brain_model(my_flags, some_dataset)
   train_results, test_results = train_and_test(my_flags, test_brain_data, test_model,
                                                epochs=my_flags.epoch_count)
+  # what a saved model carries besides its weights: the options (infer builds its datasets from
+  # them) and the shapes of the model's inputs and output
+  test_model.add_metadata(my_flags.as_dict(), dataset=some_dataset)
 
   dprime, final_decoder = None, None
   if my_flags.dnn_regressor != 'classifier':      # (no decoder is built around a classifier)
@@ -275,7 +280,11 @@ def run_decoding_experiment(my_flags):
 
   if my_flags.saved_model_dir and final_decoder is not None:
     os.makedirs(my_flags.saved_model_dir, exist_ok=True)
-    final_decoder.save_parameters(os.path.join(my_flags.saved_model_dir, 'decoder_model.json'))
+    # the fitted model goes INSIDE decoder_model.json (key 'decoding_model'): the directory keeps
+    # its one file, and infer.load_model finds both halves there
+    final_decoder.save_parameters(
+        os.path.join(my_flags.saved_model_dir, infer_decoder.DECODER_PARAM_FILE_NAME),
+        decoding_model=brain_model.model_to_dict(test_model))
     print('Wrote saved model to %s.' % my_flags.saved_model_dir)
   return train_results, test_results, dprime
 

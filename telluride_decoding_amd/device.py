@@ -4,6 +4,7 @@ PyTorch is used ONLY as plumbing -- device memory (`torch.empty(..., device=
 'cuda')`), the current HIP stream and `torch.distributed` (RCCL).  All hot-path
 arithmetic runs in the hand-written HIP kernels of libtd_hotpath.so.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -810,6 +811,82 @@ def decide_step(s1, s2, window_offsets, state=None, handle=None):
   h.check(h.lib.td_decide_step(h.ptr, _ptr(s1), _ptr(s2), wo_p, len(wo) - 1, _ptr(out),
                                st.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
   return out, st
+
+
+SWEEP_DECODERS = {'wta': 0, 'stepped': 1, 'step': 1, 'none': 2}
+SWEEP_MAX_SIZES = 16
+
+AttentionSweep = collections.namedtuple(
+    'AttentionSweep', ['means', 'decisions', 'summary', 'window_offsets', 'packed'])
+
+
+def attention_sweep(s1, s2, labels, sizes, decoder='wta', handle=None):
+  """The window-size sweep of infer.run_reduction_test in one launch set (td_attention_sweep).
+
+  s1, s2: the two speakers' per-frame scores, float64 device tensors [frames, cols] (or [frames]) with
+  unit column stride; labels: float64 device tensor of `frames` entries; sizes: up to 16 (width, hop)
+  pairs; decoder: 'wta', 'stepped' or 'none'.  Returns an AttentionSweep of device tensors, all views of
+  one buffer `packed` (one copy brings everything to the host: attention_sweep_host): means
+  [3, total] float64 (speaker 1, speaker 2, labels), decisions [total] uint8, summary [sizes, 2] int64
+  {end_first_section, correct}; size k's windows are [window_offsets[k], window_offsets[k + 1]).
+  Queued, not waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  if decoder not in SWEEP_DECODERS:
+    raise ValueError('attention_sweep: unknown decoder %r' % (decoder,))
+  sizes = np.ascontiguousarray(np.asarray(sizes, np.int64).reshape(-1, 2), np.intc)
+  ns = int(sizes.shape[0])
+  if s1.dim() == 1:
+    s1 = s1.reshape(-1, 1)
+  if s2.dim() == 1:
+    s2 = s2.reshape(-1, 1)
+  frames, cols = int(s1.shape[0]), int(s1.shape[1])
+  if tuple(s2.shape) != (frames, cols) or int(labels.numel()) != frames:
+    raise ValueError('attention_sweep: scores of %s and %s with %d labels' %
+                     (tuple(s1.shape), tuple(s2.shape), int(labels.numel())))
+  for name, t in (('s1', s1), ('s2', s2), ('labels', labels)):
+    if t.dtype != torch.float64 or t.device != h.device:
+      raise TypeError('attention_sweep: %s must be a float64 tensor on %s, not %s on %s' %
+                      (name, h.device, t.dtype, t.device))
+  if cols > 1 and (s1.stride(1) != 1 or s2.stride(1) != 1):
+    raise ValueError('attention_sweep: the columns of the scores must be contiguous')
+  labels = labels.reshape(-1).contiguous()
+  if frames == 0:       # (an empty tensor has no address to hand to the library: no window of any size)
+    s1 = s2 = h.zeros((1, max(cols, 1)), 'float64')
+    labels = h.zeros((1,), 'float64')
+  offsets = np.zeros(ns + 1, np.int64)
+  for k in range(ns):
+    width, hop = int(sizes[k, 0]), int(sizes[k, 1])
+    n = (frames - width) // hop + 1 if width >= 1 and hop >= 1 and frames >= width else 0
+    offsets[k + 1] = offsets[k] + n
+  total = int(offsets[-1])
+  # one buffer: summary | means | decisions (each at a multiple of 8 bytes)
+  o_means = 16 * ns
+  o_dec = o_means + 24 * total
+  packed = h.empty((max(o_dec + total, 8),), 'uint8')      # (every byte is written: two calls, equal buffers)
+  base = packed.data_ptr()
+  # (a one-column view's row stride is whatever the tensor says)
+  ld1 = int(s1.stride(0)) if frames > 1 else max(cols, int(s1.stride(0)))
+  ld2 = int(s2.stride(0)) if frames > 1 else max(cols, int(s2.stride(0)))
+  h.check(h.lib.td_attention_sweep(
+      h.ptr, _ptr(s1), ld1, _ptr(s2), ld2, cols, _ptr(labels), frames,
+      sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ns, SWEEP_DECODERS[decoder],
+      ctypes.c_void_p(base + o_means), ctypes.c_void_p(base + o_dec), ctypes.c_void_p(base)))
+  return AttentionSweep(packed[o_means:o_dec].view(torch.float64).reshape(3, total),
+                        packed[o_dec:o_dec + total], packed[:o_means].view(torch.int64).reshape(ns, 2),
+                        offsets, packed)
+
+
+def attention_sweep_host(sweep):
+  """An AttentionSweep's means, decisions and summary as host arrays, through ONE copy."""
+  host = sweep.packed.cpu().numpy()
+  ns = int(sweep.summary.shape[0])
+  total = int(sweep.window_offsets[-1])
+  o_means = 16 * ns
+  o_dec = o_means + 24 * total
+  return AttentionSweep(host[o_means:o_dec].view(np.float64).reshape(3, total),
+                        host[o_dec:o_dec + total], host[:o_means].view(np.int64).reshape(ns, 2),
+                        sweep.window_offsets, None)
 
 
 def ssd_state(num_trials, handle=None):

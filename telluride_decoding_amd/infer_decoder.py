@@ -5,9 +5,9 @@ streaming correlator (`add_data_correlator` :288-310, `compute_correlation`
 :312-328), `train` (:330-400), `infer_one` (:416-455), `test_all` (:457-482),
 `test_by_window` (:484-504), LDA helpers (:506-550), `check_model_and_data` (:552-580),
 JSON persistence (:75-92, 240-248); `LinearRegressionDecoder` (:583-604), `CCADecoder` (:607-632),
-`create_decoder` (:635-666), `calculate_dprime` (:717-745), `average_data`
-(:748-783).  SavedModel loading and TFRecord datasets (:250-286, :669-713) are TF
-file formats and out of scope.
+`create_decoder` (:635-666), `create_dataset` (:669-713), `calculate_dprime` (:717-745),
+`average_data` (:748-783).  `load_decoding_model` (:250-286) reads this package's own model file
+(brain_model.model_to_dict), not a TensorFlow SavedModel.
 
 All per-frame arithmetic (five running sums, normalised products, reductions,
 window means) runs in HIP kernels; this file is host orchestration.  Besides
@@ -16,6 +16,7 @@ the reference's minibatch-streaming methods there is a batched fast path,
 """
 import collections
 import json
+import os
 
 import numpy as np
 
@@ -46,6 +47,8 @@ ModelParamsTuple = collections.namedtuple('ModelParamsTuple',
                                           ['correlation_params', 'lda_params'])
 
 _REDUCTIONS = ('mean-squared', 'first', 'second', 'lda', 'all', 'mean')
+DECODER_PARAM_FILE_NAME = 'decoder_model.json'
+DECODING_MODEL_KEY = 'decoding_model'      # the model inside decoder_model.json
 
 
 def _host(a):
@@ -150,14 +153,55 @@ class Decoder(object):
     self._mean_x = self._mean_y = 0.0
     self._power = 1.0
 
-  def save_parameters(self, param_filename):
+  def save_parameters(self, param_filename, decoding_model=None):
+    """Writes correlation_params and lda_params as JSON (reference :240-243).  decoding_model: a
+    brain_model.model_to_dict dict (or one of this package's models) to store in the same file under
+    a third key, 'decoding_model' -- how decoding.run_decoding_experiment keeps the fitted model in
+    its one-file saved_model_dir."""
+    contents = self.model_params._asdict()
+    if decoding_model is not None:
+      if not isinstance(decoding_model, dict):
+        decoding_model = brain_model.model_to_dict(decoding_model)
+      contents[DECODING_MODEL_KEY] = decoding_model
     with open(param_filename, 'w') as f:
-      json.dump(self.model_params._asdict(), f, cls=NumpyEncoder)
+      json.dump(contents, f, cls=NumpyEncoder)
 
   def restore_parameters(self, param_filename):
+    """Reads correlation_params and lda_params back; any other key of the file is ignored."""
     with open(param_filename, 'r') as f:
       loaded = json.load(f)
-    self.model_params = ModelParamsTuple(**loaded)
+    self.model_params = ModelParamsTuple(**{k: loaded[k] for k in ModelParamsTuple._fields})
+
+  def load_decoding_model(self, saved_model_file, object_dict):
+    """Loads the decoding model saved in the directory `saved_model_file` (reference :250-286):
+    its brain_model.json (model.save), else the 'decoding_model' entry of its decoder_model.json
+    (save_parameters(..., decoding_model=)); decoding_model_params, model_inputs and model_output
+    come from the model's add_metadata entries.  object_dict (the reference's Keras custom objects)
+    is accepted and unused."""
+    if not saved_model_file or not isinstance(saved_model_file, str):
+      raise TypeError('Must provide a file name (string) to load-model, not '
+                      'a %s.' % type(saved_model_file))
+    if object_dict and not isinstance(object_dict, dict):
+      raise TypeError('If providing an object dictionary, it must be a dict '
+                      'not a %s.' % type(object_dict))
+    model_file = os.path.join(saved_model_file, brain_model.MODEL_FILE_NAME)
+    param_file = os.path.join(saved_model_file, DECODER_PARAM_FILE_NAME)
+    model_dict = None
+    if os.path.exists(model_file):
+      with open(model_file, 'r') as f:
+        model_dict = json.load(f)
+    elif os.path.exists(param_file):
+      with open(param_file, 'r') as f:
+        model_dict = json.load(f).get(DECODING_MODEL_KEY)
+    if model_dict is None:
+      raise IOError('SavedModel file does not exist at: %s' % saved_model_file)
+    model = brain_model.model_from_dict(model_dict)
+    self._decoding_model = model
+    self._decoding_model_params = getattr(model, 'telluride_metadata', None) or {}
+    self._signature_from_model(model)
+    if getattr(model, 'telluride_inputs', None) and getattr(model, 'telluride_output', None):
+      self._model_inputs = {k: list(v) for k, v in model.telluride_inputs.items()}
+      self._model_output = list(model.telluride_output)
 
   # -- streaming correlator (reference :288-328) --------------------------------
   def _add_sums(self, count, s):
@@ -325,24 +369,35 @@ class Decoder(object):
   def _score_streams(self, r1, r2):
     """Per-frame reduced score of two decoded streams (device tensors): host [frames] float64
     ([frames, dims] for reduction 'all')."""
+    return self._score_streams_device(r1, r2).cpu().numpy()
+
+  def _score_streams_device(self, r1, r2):
     h = device.default_handle()
     cols = int(r1.shape[1])
     if self._reduction == 'second' and cols < 2:
       raise IndexError('index 1 is out of bounds for axis 1 with size %d' % cols)
     mx, my, pw = self._stat_vectors(cols)
     return device.frame_scores(r1, r2, self._reduction, mx, my, pw, handle=h,
-                               **self._reduce_kwargs()).cpu().numpy()
+                               **self._reduce_kwargs())
+
+  def test_all_device(self, exp_data):
+    """test_all with the scores left on the device: (float64 device tensor [frames, 1 or dims],
+    attention labels [frames, 1] on the host); (None, None) for a dataset without minibatches."""
+    streams = self._decode_dataset(exp_data)
+    if streams is None:
+      return None, None
+    scores = self._score_streams_device(streams[0], streams[1])
+    if scores.dim() == 1:
+      scores = scores.reshape(-1, 1)      # NumpyStore keeps vectors as columns
+    return scores, streams[2]
 
   def test_all(self, exp_data):
     """(scores [frames, 1 or dims], attention labels [frames, 1]) of a whole dataset
     (reference :457-482), scored in one launch."""
-    streams = self._decode_dataset(exp_data)
-    if streams is None:
+    scores, labels = self.test_all_device(exp_data)
+    if scores is None:
       return None, None
-    scores = self._score_streams(streams[0], streams[1])
-    if scores.ndim == 1:
-      scores = scores.reshape(-1, 1)      # NumpyStore keeps vectors as columns
-    return scores, streams[2]
+    return scores.cpu().numpy(), labels
 
   def test_by_window(self, dataset, window_size):
     """Generator of (scores, labels) windows of `window_size` frames every
@@ -482,6 +537,22 @@ def create_decoder(model_tag, reduction='lda', model=None):
   elif 'cca' in tag:
     return CCADecoder(model, reduction=reduction)
   raise ValueError('Couldn\'t determine model type for tag %s.' % model_tag)
+
+
+def create_dataset(tfrecord_file, params, audio_label, frame_rate=100, mode='test',
+                   mixup_batch=False):
+  """The dataset of ONE TFRecord file for a decoding model (reference :669-713): input
+  params['input_field'] with the contexts in `params`, `audio_label` as output and as input 2, the
+  attention labels from the file's 'attended_speaker' field, minibatches of 200 frames, in order."""
+  tf_dir, tf_file = os.path.split(tfrecord_file)
+  exp_brain_data = brain_data.TFExampleData(
+      params['input_field'], audio_label, frame_rate,
+      pre_context=params['pre_context'], post_context=params['post_context'],
+      in2_fields=audio_label, in2_pre_context=params['input2_pre_context'],
+      in2_post_context=params['input2_post_context'], attended_field='attended_speaker',
+      final_batch_size=200, repeat_count=1, shuffle_buffer_size=0, data_dir=tf_dir,
+      data_pattern=tf_file, train_file_pattern='', validate_file_pattern='', test_file_pattern='')
+  return exp_brain_data.create_dataset(mode, mixup_batch=mixup_batch)
 
 
 def calculate_dprime(d1, d2):
