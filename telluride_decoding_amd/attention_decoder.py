@@ -11,7 +11,7 @@ Two ways in:
     stateful.  For the winner-take-all and step decoders that is ONE float64
     compare (and a clipped +-0.1): it is done where the two scalars are, on the
     host, in the same IEEE float64 operations as the kernels of the batched path
-    (decide_wta_kernel / decide_step_kernel, decode.hip) -- uploading two scalars
+    (decide_wta_kernel / decide_step_kernel, windows.hip) -- uploading two scalars
     and launching a kernel cost a streaming caller ~30 us per window for a `>`.
     The state-space decoder's call is real work (EM + Kalman + Newton) and runs
     the same HIP kernel as the batched path on a one-trial problem.

@@ -21,7 +21,7 @@ struct SweepSizes {
   long long total;
 };
 
-// (decode.hip's wave_sum: the same shuffle tree, the same bits)
+// (windows.hip's wave_sum: the same shuffle tree, the same bits)
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);

@@ -128,7 +128,7 @@ def find_first_segment(labels):
 def decode_attention(decoder, d1_results, d2_results):
   """[n_windows, 3] array of (decision, lower, upper): `decoder.attention(c1, c2)` for every window
   in turn (infer.py:393-394), as ONE batched device call -- the decoders' state machines are
-  sequential in time, so one GPU lane walks the windows (decode.hip)."""
+  sequential in time, so one GPU lane walks the windows (windows.hip)."""
   a, lo, hi = decoder.attention_batch(np.asarray(d1_results, np.float64),
                                       np.asarray(d2_results, np.float64))
   return np.stack([np.asarray(a, np.float64), np.asarray(lo, np.float64),

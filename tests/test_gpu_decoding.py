@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 
 EPS = 2.0 ** -52
 LD = np.longdouble
-# the kernel's shares at up to 16384 windows (decode.hip: kWcmMinWinPerWave, four waves a workgroup)
+# the kernel's shares at up to 16384 windows (windows.hip: kWcmMinWinPerWave, four waves a workgroup)
 WAVE_SHARE, GROUP_SHARE = 4, 16
 
 
