@@ -606,7 +606,7 @@ int td_decode_ssd(td_handle* h, const double* s1_dev, const double* s2_dev,
  * k_w correlations between calls): state_dev [num_trials, td_ssd_state_doubles()] float64 on the
  * device, all zeros for a fresh decoder, is read before the trial's windows of this call and
  * written after them -- any split of a trial's windows over calls gives the outputs of one call.
- * state_dev NULL = td_decode_ssd. */
+ * state_dev NULL = td_decode_ssd.  (With td_profile_enable, a call that carries state counts as one launch.) */
 int td_ssd_state_doubles(void);
 int td_decode_ssd_stream(td_handle* h, const double* s1_dev, const double* s2_dev,
                          const int64_t* window_offsets_host, int num_trials,
@@ -650,6 +650,73 @@ int td_decode_fused(td_handle* h, const float* eeg_dev, int64_t ldx, int c, int 
                     const int64_t* trial_offsets_host, int num_trials, int width,
                     int hop, const double* corr_host, double* scores_dev,
                     uint8_t* decisions_dev);
+
+/* ------------------------------------------------------------------ online decode
+ * td_decode_fused's chain for EEG that arrives in chunks (the reference's streaming shape:
+ * Preprocessor.process(..., reset=False), Decoder.infer_one per minibatch, the stateful attention
+ * decoders): `num_sessions` independent listeners, one state block each on the device, advanced by ONE
+ * launch per push (one workgroup per session).  However a recording is cut into pushes, the outputs and
+ * the final state are those of one push of the whole recording, bit for bit.
+ *
+ * The prediction of frame t needs the EEG rows up to t + post, so frames are emitted `post` frames late:
+ * after `pushed` frames, emitted = max(0, pushed - post), or pushed once the recording was flushed; the
+ * full windows of the emitted frames are windows(emitted) = td_window_count of one trial of that length.
+ *
+ * td_online_state_bytes: the size of one session's state block (a multiple of 8).  All zeros = a fresh
+ * session.  It holds the last pre + post EEG rows, the last post envelope rows, a ring of the last
+ * `width` per-frame scores of both speakers and the stepped decoder's float64 state (0 = fresh = 0.5) --
+ * data only: the HOST counts the frames (frames_before) and is authoritative.
+ *
+ * td_online_plan (host, integers): what a push of n frames behind frames_before pushed ones emits.
+ *   emitted_before / emitted_after  frames emitted before / after the push (flush != 0: all of them)
+ *   first_window, new_windows       the push's windows are [first_window, first_window + new_windows)
+ *
+ * td_online_push: the sessions' next n frames.
+ *   eeg_dev   [S][n][c] float32, row stride eeg_ld, session stride eeg_session_stride (elements)
+ *   env_dev   [S][n][2] float32 (speaker 1, speaker 2), strides env_ld / env_session_stride
+ *   n >= 0    (n == 0 and flush == 0: nothing is queued; the input pointers may then be NULL)
+ *   w_dev     [(pre + 1 + post) c] float32 in the lag layout of td_predict_fir (row l c + ch multiplies
+ *             x[t + l - pre][ch]), session stride w_session_stride; b_dev one bias per session, stride
+ *             b_session_stride.  A session stride of 0 = one model for all sessions.
+ *   corr_dev  [S][2][3] float64 {mean_truth, mean_pred, power} of speaker 1 then 2 (td_decode_fused's corr_host)
+ *   reduction td_frame_scores' codes for ONE column: 0 first, 2 mean, 3 mean-squared, 4 lda with
+ *             lda_dev [S][3] float64 {lda_w, slope, intercept} (NULL for the other reductions)
+ *   width >= 1, hop >= 1; decoder 0 winner-take-all, 1 stepped, 2 none (decisions 0)
+ *   frames_before  frames pushed so far (every session of a bank has seen the same number)
+ *   flush     after these n rows behave as if `post` zero rows followed -- the end of the recording, the
+ *             zero padding of td_predict_fir; the state is then good for nothing but td_memset
+ *   state_dev, state_session_stride (BYTES, a multiple of 8, >= td_online_state_bytes)
+ * Outputs, sized by td_online_plan:
+ *   scores_dev    [2][S][new_windows] float64 (planar: a plane goes straight into td_decode_ssd_stream)
+ *   decisions_dev [S][new_windows] u8
+ *   pred_dev      [S][emitted_after - emitted_before] float32, or NULL: the predictions
+ *   frame_dev     [2][S][emitted_after - emitted_before] float64, or NULL: the per-frame scores
+ * Arithmetic: the prediction is a float32 sum whose order depends on (lag, channel) alone -- never on
+ * where a frame falls in a push -- with the rows before the recording read as the zeros of a fresh state;
+ * the per-frame score, the window mean and the decisions are td_frame_scores', td_window_means',
+ * td_decide_wta's / td_decide_step's operation for operation.  No atomics: two runs give the same bits.
+ * TD_ERR_INVALID, before anything is queued: a NULL required pointer, num_sessions < 1, c outside
+ * 1..128, pre or post < 0, pre + 1 + post > 64, n outside 0..TD_ONLINE_MAX_PUSH, width outside
+ * 1..TD_ONLINE_MAX_WIDTH, hop < 1, reduction not one of 0 / 2 / 3 / 4 (4 without lda_dev), decoder outside
+ * 0..2, frames_before < 0, eeg_ld < c, env_ld < 2, a session stride of the inputs below one row (more
+ * than one session), a model stride that is neither 0 nor a whole model, a state stride below the state
+ * block or not a multiple of 8.
+ * With td_profile_enable the launch is bracketed like the accumulate's dominant kernel (so is the
+ * launch of td_decode_ssd_stream when it carries state): td_profile_read counts launches per push. */
+#define TD_ONLINE_MAX_WIDTH 65536
+#define TD_ONLINE_MAX_PUSH 1048576
+int td_online_state_bytes(int c, int pre, int post, int width, int64_t* bytes);
+int td_online_plan(int64_t frames_before, int64_t n, int post, int width, int hop, int flush,
+                   int64_t* emitted_before, int64_t* emitted_after, int64_t* first_window,
+                   int64_t* new_windows);
+int td_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t eeg_ld,
+                   int64_t eeg_session_stride, const float* env_dev, int64_t env_ld,
+                   int64_t env_session_stride, int64_t n, int c, int pre, int post,
+                   const float* w_dev, int64_t w_session_stride, const float* b_dev,
+                   int64_t b_session_stride, const double* corr_dev, int reduction,
+                   const double* lda_dev, int width, int hop, int decoder, int64_t frames_before,
+                   int flush, void* state_dev, int64_t state_session_stride, double* scores_dev,
+                   uint8_t* decisions_dev, float* pred_dev, double* frame_dev);
 
 /* ------------------------------------------------------------------ preprocessing
  * preprocess.Preprocessor (preprocess.py:54-587): the signal conditioning before the fits.

@@ -148,6 +148,12 @@ SIGNATURES = {
     'td_attention_sweep': [_vp, _vp, _i64, _vp, _i64, _i, _vp, _i64, _c.POINTER(_i), _i, _i, _vp, _vp, _vp],
     'td_decode_fused': [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _pi64, _i, _i,
                         _i, _pd, _vp, _vp],
+    'td_online_state_bytes': [_i, _i, _i, _i, _pi64],
+    'td_online_plan': [_i64, _i64, _i, _i, _i, _i, _pi64, _pi64, _pi64, _pi64],
+    # h, sessions | eeg, ld, stride | env, ld, stride | n, c, pre, post | w, stride, b, stride | corr, reduction,
+    # lda | width, hop, decoder, frames_before, flush | state, stride | scores, decisions, pred, frame
+    'td_online_push': [_vp, _i] + [_vp, _i64, _i64] * 2 + [_i64, _i, _i, _i] + [_vp, _i64] * 2 +
+                      [_vp, _i, _vp] + [_i, _i, _i, _i64, _i] + [_vp, _i64] + [_vp, _vp, _vp, _vp],
     'td_sos_filter': [_vp, _vp, _i, _i64, _i, _pi64, _i, _pd, _i, _i, _pd, _i, _vp, _vp, _pi64, _vp, _i64],
     'td_sos_filter_plan': [_i64, _i64, _i, _c.POINTER(_i), _c.POINTER(_i)],
     'td_reref_select': [_vp, _vp, _i, _i64, _i, _vp, _i64, _i, _c.POINTER(_i), _c.POINTER(_i),

@@ -1169,10 +1169,13 @@ int td_decode_ssd_stream(td_handle* h, const double* s1_dev, const double* s2_de
   if (num_trials <= 0) return TD_OK;
   void* scratch = nullptr;
   TD_TRY(upload_window_offsets(h, window_offsets_host, num_trials, sizeof(long long) * (num_trials + 1), &scratch));
+  // (a decoder that carries state is a step of an online session: td_profile_read counts its launch)
+  if (state_dev) TD_TRY(td_profile_mark(h, true, 0.0));
   hipLaunchKernelGGL(ssd_kernel, dim3((unsigned)td_ceil_div(num_trials, 64)), dim3(64), 0,
                      h->stream, s1_dev, s2_dev, reinterpret_cast<const long long*>(scratch),
                      num_trials, sp, out_dev, state_dev);
   TD_HIP(h, hipGetLastError());
+  if (state_dev) TD_TRY(td_profile_mark(h, false, 0.0));
   return TD_OK;
 }
 

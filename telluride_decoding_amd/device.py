@@ -933,6 +933,99 @@ def decode_fused(eeg, env, trial_offsets, w, b, pre, post, width, hop, corr, han
   return scores, decisions
 
 
+ONLINE_REDUCTIONS = ('first', 'mean', 'mean-squared', 'lda')     # one model output: td_online_push
+ONLINE_MAX_CHANNELS, ONLINE_MAX_LAGS = 128, 64
+
+OnlinePlan = collections.namedtuple(
+    'OnlinePlan', ['emitted_before', 'emitted_after', 'first_window', 'new_windows'])
+OnlinePush = collections.namedtuple('OnlinePush', ['scores', 'decisions', 'pred', 'frame', 'plan'])
+
+
+def online_state_bytes(c, pre, post, width):
+  """Bytes of one online session's state block (td_online_state_bytes); all zeros = a fresh session."""
+  n = ctypes.c_int64(0)
+  _lib.check(None, _lib.load().td_online_state_bytes(int(c), int(pre), int(post), int(width), ctypes.byref(n)))
+  return int(n.value)
+
+
+def online_plan(frames_before, n, post, width, hop, flush=False):
+  """What a push of n frames behind `frames_before` pushed ones emits (td_online_plan, host integers):
+  OnlinePlan(emitted_before, emitted_after, first_window, new_windows)."""
+  out = [ctypes.c_int64(0) for _ in range(4)]
+  _lib.check(None, _lib.load().td_online_plan(int(frames_before), int(n), int(post), int(width), int(hop),
+                                              1 if flush else 0, *[ctypes.byref(v) for v in out]))
+  return OnlinePlan(*[int(v.value) for v in out])
+
+
+def online_push(eeg, env, w, b, corr, state, frames_before, pre, post, width, hop, reduction='first',
+                lda=None, decoder='wta', flush=False, want_frames=False, handle=None):
+  """One push of a bank of online decoding sessions, in one launch (td_online_push).
+
+  eeg [S, n, c] and env [S, n, 2]: float32 device tensors with unit column stride (None for a flush
+  without rows); w [S or 1, (pre + 1 + post) c] and b [S or 1] float32 (one row: the model every session
+  shares); corr [S, 2, 3] float64 {mean_truth, mean_pred, power} per speaker; lda [S, 3] float64
+  {lda_w, slope, intercept} for reduction 'lda'; state: uint8 device tensor [S, >= online_state_bytes()]
+  with a row stride that is a multiple of 8, updated in place; frames_before: frames pushed so far.
+  decoder 'wta', 'stepped' or 'none'.  Returns OnlinePush(scores [2, S, new] float64, decisions [S, new]
+  uint8, pred [S, emitted] float32 and frame [2, S, emitted] float64 (None without want_frames), plan).
+  Queued, not waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  if reduction not in ONLINE_REDUCTIONS:
+    raise ValueError('online_push: reduction %r (one of %s)' % (reduction, ', '.join(ONLINE_REDUCTIONS)))
+  if decoder not in SWEEP_DECODERS:
+    raise ValueError('online_push: unknown decoder %r' % (decoder,))
+  sessions = int(state.shape[0])
+  k = int(w.shape[1])
+  nl = int(pre) + 1 + int(post)
+  if nl < 1 or k % nl:
+    raise ValueError('online_push: %d weights for %d lags' % (k, nl))
+  c = k // nl
+  n = 0 if eeg is None else int(eeg.shape[1])
+  if eeg is not None and (tuple(eeg.shape) != (sessions, n, c) or env is None or
+                          tuple(env.shape) != (sessions, n, 2)):
+    raise ValueError('online_push: eeg of %s and env of %s for %d sessions of %d channels' %
+                     (tuple(eeg.shape), None if env is None else tuple(env.shape), sessions, c))
+  for name, t, dtype in (('eeg', eeg, torch.float32), ('env', env, torch.float32), ('w', w, torch.float32),
+                         ('b', b, torch.float32), ('corr', corr, torch.float64), ('lda', lda, torch.float64),
+                         ('state', state, torch.uint8)):
+    if t is not None and (t.dtype != dtype or t.device != h.device):
+      raise TypeError('online_push: %s must be a %s tensor on %s, not %s on %s' %
+                      (name, dtype, h.device, t.dtype, t.device))
+  if n > 0 and (eeg.stride(2) != 1 and c > 1 or env.stride(2) != 1):
+    raise ValueError('online_push: the columns of eeg and env must be contiguous')
+  if int(w.shape[0]) not in (1, sessions) or int(b.numel()) != int(w.shape[0]):
+    raise ValueError('online_push: %d models and %d biases for %d sessions' %
+                     (int(w.shape[0]), int(b.numel()), sessions))
+  if tuple(corr.shape) != (sessions, 2, 3) or (lda is not None and tuple(lda.shape) != (sessions, 3)):
+    raise ValueError('online_push: corr must be [%d, 2, 3] and lda [%d, 3]' % (sessions, sessions))
+  w, b, corr = w.contiguous(), b.reshape(-1).contiguous(), corr.contiguous()
+  lda = lda.contiguous() if lda is not None else None
+  shared = int(w.shape[0]) == 1
+  plan = online_plan(frames_before, n, post, width, hop, flush)
+  emitted = plan.emitted_after - plan.emitted_before
+  # (every element a push emits is written; an empty tensor has no address: one spare element)
+  scores = h.empty((2 * sessions * plan.new_windows + 1,), 'float64')
+  decisions = h.empty((sessions * plan.new_windows + 1,), 'uint8')
+  pred = h.empty((sessions * emitted + 1,), 'float32') if want_frames else None
+  frame = h.empty((2 * sessions * emitted + 1,), 'float64') if want_frames else None
+  live = n > 0
+  h.check(h.lib.td_online_push(
+      h.ptr, sessions,
+      _ptr(eeg if live else None), int(eeg.stride(1)) if live and n > 1 else c,
+      int(eeg.stride(0)) if live and sessions > 1 else max(n, 1) * c,
+      _ptr(env if live else None), int(env.stride(1)) if live and n > 1 else 2,
+      int(env.stride(0)) if live and sessions > 1 else max(n, 1) * 2,
+      n, c, int(pre), int(post), _ptr(w), 0 if shared else k, _ptr(b), 0 if shared else 1,
+      _ptr(corr), REDUCTIONS[reduction], _ptr(lda), int(width), int(hop), SWEEP_DECODERS[decoder],
+      int(frames_before), 1 if flush else 0, _ptr(state), int(state.stride(0)) if sessions > 1 else int(state.shape[1]),
+      _ptr(scores), _ptr(decisions), _ptr(pred), _ptr(frame)))
+  return OnlinePush(scores[:-1].reshape(2, sessions, plan.new_windows),
+                    decisions[:-1].reshape(sessions, plan.new_windows),
+                    pred[:-1].reshape(sessions, emitted) if want_frames else None,
+                    frame[:-1].reshape(2, sessions, emitted) if want_frames else None, plan)
+
+
 def sos_filter(x, file_offsets, sos, zi, stage_split, state, reset, out_rows=None, out_offsets=None, handle=None):
   """The SOS cascade over x [N, C] (float32 / float64 device tensor), files concatenated along time:
   float64 output [N, C], or only the file-local rows out_rows (device int64, file f's at
