@@ -718,6 +718,75 @@ int td_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t
                    int flush, void* state_dev, int64_t state_session_stride, double* scores_dev,
                    uint8_t* decisions_dev, float* pred_dev, double* frame_dev);
 
+/* ------------------------------------------------------------------ online decode, CCA model
+ * The session of td_online_push with a CCA model (cca.BrainModelCCA behind infer_decoder.CCADecoder) in front
+ * of the correlator: ONE launch per push, one workgroup per session, the state on the device, and however a
+ * recording is cut into pushes the outputs and the final state are those of one push, bit for bit.
+ *
+ * View 1 is the EEG, c1 channels with context pre1 / post1, k1 = c1 (pre1 + 1 + post1); view 2 is one block of
+ * c2 audio features per speaker with context pre2 / post2, k2 = c2 (pre2 + 1 + post2).  Frames are emitted
+ * post = max(post1, post2) frames late: td_online_plan with that post says what a push emits.  Per emitted
+ * frame t
+ *   a[d]   = sum_k (x~_t[k]     - mean_x[k]) rot_x[k][d]      (once, shared by both speakers)
+ *   b_s[d] = sum_k (y~_{s,t}[k] - mean_y[k]) rot_y[k][d]      (speaker s = 1, 2)
+ * in float32: one subtraction in front of each fused multiply-add (BrainCcaLayer.call's (x - mean) @ rot), in
+ * an order that depends on (lag, channel, d) alone -- lane q of a wave takes the terms k = q, q + 64, ... into
+ * four accumulators in turn, ((a0 + a1) + (a2 + a3)), then the 64-lane tree.  From the projections on it is
+ * td_frame_scores(a, b_s) over the dims columns, td_window_means, td_decide_wta / td_decide_step, operation for
+ * operation, and td_online_push's ring.
+ *
+ * td_cca_online_state_bytes: one session's state block (a multiple of 8; all zeros = fresh):
+ *   8                          the stepped decoder's float64 state (0 = fresh = 0.5)
+ *   16 width                   the ring of the last `width` per-frame scores, float64 [2][width]
+ *   4 c1 (pre1 + post)         the last pre1 + post EEG rows
+ *   8 c2 (pre2 + post)         the last pre2 + post feature rows of each speaker, [2][pre2 + post][c2]
+ * Data only: the host counts the frames.
+ *
+ * td_cca_online_lds_bytes: the LDS of a launch that emits `emitted` frames and the frames per pass it takes:
+ *   bytes(pass) = 32 pass + 4 ((dims + 1) (k1 + k2) + R1 c1 + 2 R2 c2 + 3 dims pass),
+ *   R1 = max(pass + pre1 + post1, pre1 + post), R2 = max(pass + pre2 + post2, pre2 + post)
+ * (scores and window means of a pass; the means and the rotations, transposed; the staged rows; the pass's
+ * projections).  pass = min(64, max(emitted, 1)), halved (rounding up) while bytes(pass) exceeds
+ * TD_CCA_ONLINE_LDS_BYTES; a shape whose bytes(1) exceeds it is refused by all three entry points
+ * (td_cca_online_state_bytes checks dims = 1, the least a model can have).
+ *
+ * td_cca_online_push: the sessions' next n frames.
+ *   eeg_dev    [S][n][c1] float32, row stride eeg_ld, session stride eeg_session_stride (elements)
+ *   feat1_dev, feat2_dev  [S][n][c2] float32 each (speaker 1, speaker 2), strides feat_ld / feat_session_stride
+ *   mean_x_dev [k1], rot_x_dev [k1][dims], mean_y_dev [k2], rot_y_dev [k2][dims] float32 in the lag layout of
+ *              td_cca_transform (row l c + ch belongs to x[t + l - pre][ch]); model_session_stride 0 = one
+ *              model for all sessions, 1 = the four arrays hold one model per session, one after the other
+ *   corr_dev   [S][2][3][dims] float64 {mean_a, mean_b, power} of speaker 1 then 2
+ *   reduction  td_frame_scores' codes: 0 first, 1 second (dims >= 2), 2 mean, 3 mean-squared, 4 lda with
+ *              lda_dev [S][dims + 2] float64 {weights, slope, intercept} (NULL for the other reductions)
+ *   width, hop, decoder, frames_before, flush, state_dev, state_session_stride: as td_online_push; a flush
+ *              behaves as if `post` zero rows followed in both views
+ * Outputs, sized by td_online_plan(..., post = max(post1, post2), ...):
+ *   scores_dev    [2][S][new_windows] float64, decisions_dev [S][new_windows] u8
+ *   proj_dev      [S][emitted][3 dims] float32 (a | b_1 | b_2), or NULL
+ *   frame_dev     [2][S][emitted] float64, or NULL: the per-frame scores
+ * No atomics: two runs give the same bits.  TD_ERR_INVALID, before anything is queued and with the state
+ * untouched: a NULL required pointer, num_sessions < 1, c1 outside 1..128, c2 outside 1..32, a negative context,
+ * more than 64 lags in a view, dims outside 1..16, a shape over the LDS budget, n outside 0..TD_ONLINE_MAX_PUSH,
+ * width outside 1..TD_ONLINE_MAX_WIDTH, hop < 1, reduction outside 0..4 (1 with dims 1, 4 without lda_dev),
+ * decoder outside 0..2, frames_before < 0, eeg_ld < c1, feat_ld < c2, a session stride of the inputs below
+ * one row (more than one session), a model stride other than 0 or 1, a state stride below the state block or
+ * not a multiple of 8.  With td_profile_enable the launch is bracketed as td_online_push's is. */
+#define TD_CCA_ONLINE_LDS_BYTES 163840
+int td_cca_online_state_bytes(int c1, int pre1, int post1, int c2, int pre2, int post2, int width,
+                              int64_t* bytes);
+int td_cca_online_lds_bytes(int c1, int pre1, int post1, int c2, int pre2, int post2, int dims,
+                            int64_t emitted, int* pass, int64_t* bytes);
+int td_cca_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t eeg_ld,
+                       int64_t eeg_session_stride, const float* feat1_dev, const float* feat2_dev,
+                       int64_t feat_ld, int64_t feat_session_stride, int64_t n, int c1, int pre1, int post1,
+                       int c2, int pre2, int post2, int dims, const float* mean_x_dev, const float* rot_x_dev,
+                       const float* mean_y_dev, const float* rot_y_dev, int64_t model_session_stride,
+                       const double* corr_dev, int reduction, const double* lda_dev, int width, int hop,
+                       int decoder, int64_t frames_before, int flush, void* state_dev,
+                       int64_t state_session_stride, double* scores_dev, uint8_t* decisions_dev,
+                       float* proj_dev, double* frame_dev);
+
 /* ------------------------------------------------------------------ preprocessing
  * preprocess.Preprocessor (preprocess.py:54-587): the signal conditioning before the fits.
  *

@@ -154,6 +154,14 @@ SIGNATURES = {
     # lda | width, hop, decoder, frames_before, flush | state, stride | scores, decisions, pred, frame
     'td_online_push': [_vp, _i] + [_vp, _i64, _i64] * 2 + [_i64, _i, _i, _i] + [_vp, _i64] * 2 +
                       [_vp, _i, _vp] + [_i, _i, _i, _i64, _i] + [_vp, _i64] + [_vp, _vp, _vp, _vp],
+    'td_cca_online_state_bytes': _VIEW + _VIEW + [_i, _pi64],
+    'td_cca_online_lds_bytes': _VIEW + _VIEW + [_i, _i64, _c.POINTER(_i), _pi64],
+    # h, sessions | eeg, ld, stride | feat1, feat2, ld, stride | n | c1, pre1, post1 | c2, pre2, post2 | dims |
+    # mean_x, rot_x, mean_y, rot_y, model stride | corr, reduction, lda | width, hop, decoder, frames_before,
+    # flush | state, stride | scores, decisions, proj, frame
+    'td_cca_online_push': [_vp, _i] + [_vp, _i64, _i64] + [_vp, _vp, _i64, _i64] + [_i64] + _VIEW + _VIEW + [_i] +
+                          [_vp, _vp, _vp, _vp, _i64] + [_vp, _i, _vp] + [_i, _i, _i, _i64, _i] + [_vp, _i64] +
+                          [_vp, _vp, _vp, _vp],
     'td_sos_filter': [_vp, _vp, _i, _i64, _i, _pi64, _i, _pd, _i, _i, _pd, _i, _vp, _vp, _pi64, _vp, _i64],
     'td_sos_filter_plan': [_i64, _i64, _i, _c.POINTER(_i), _c.POINTER(_i)],
     'td_reref_select': [_vp, _vp, _i, _i64, _i, _vp, _i64, _i, _c.POINTER(_i), _c.POINTER(_i),

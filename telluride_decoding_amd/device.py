@@ -1026,6 +1026,115 @@ def online_push(eeg, env, w, b, corr, state, frames_before, pre, post, width, ho
                     frame[:-1].reshape(2, sessions, emitted) if want_frames else None, plan)
 
 
+CCA_ONLINE_REDUCTIONS = ('first', 'second', 'mean', 'mean-squared', 'lda')     # td_cca_online_push
+CCA_ONLINE_MAX_CHANNELS, CCA_ONLINE_MAX_FEATURES, CCA_ONLINE_MAX_DIMS = 128, 32, 16
+CCA_ONLINE_LDS_BYTES = 163840                                                   # TD_CCA_ONLINE_LDS_BYTES
+
+CcaOnlinePush = collections.namedtuple('CcaOnlinePush', ['scores', 'decisions', 'proj', 'frame', 'plan'])
+
+
+def cca_online_state_bytes(c1, pre1, post1, c2, pre2, post2, width):
+  """Bytes of one CCA online session's state block (td_cca_online_state_bytes); all zeros = a fresh session."""
+  n = ctypes.c_int64(0)
+  _lib.check(None, _lib.load().td_cca_online_state_bytes(int(c1), int(pre1), int(post1), int(c2), int(pre2),
+                                                         int(post2), int(width), ctypes.byref(n)))
+  return int(n.value)
+
+
+def cca_online_lds_bytes(c1, pre1, post1, c2, pre2, post2, dims, emitted=64):
+  """(frames per pass, LDS bytes) of a td_cca_online_push launch that emits `emitted` frames
+  (td_cca_online_lds_bytes); ValueError with the byte budget for a shape that does not fit at a pass of one."""
+  p, n = ctypes.c_int(0), ctypes.c_int64(0)
+  _lib.check(None, _lib.load().td_cca_online_lds_bytes(int(c1), int(pre1), int(post1), int(c2), int(pre2),
+                                                       int(post2), int(dims), int(emitted), ctypes.byref(p),
+                                                       ctypes.byref(n)))
+  return int(p.value), int(n.value)
+
+
+def cca_online_push(eeg, feat1, feat2, mean_x, rot_x, mean_y, rot_y, corr, state, frames_before, pre1, post1,
+                    pre2, post2, width, hop, reduction='first', lda=None, decoder='wta', flush=False,
+                    want_frames=False, handle=None):
+  """One push of a bank of online CCA decoding sessions, in one launch (td_cca_online_push).
+
+  eeg [S, n, c1], feat1 and feat2 [S, n, c2]: float32 device tensors with unit column stride (None for a
+  flush without rows; the two feature tensors share their strides); mean_x [M, k1], rot_x [M, k1, dims],
+  mean_y [M, k2], rot_y [M, k2, dims] float32 with M = S or 1 (one model for every session), k1 =
+  c1 (pre1 + 1 + post1), k2 = c2 (pre2 + 1 + post2); corr [S, 2, 3, dims] float64 {mean_a, mean_b, power}
+  per speaker; lda [S, dims + 2] float64 {weights, slope, intercept} for reduction 'lda'; state: uint8 device
+  tensor [S, >= cca_online_state_bytes()] with a row stride that is a multiple of 8, updated in place.
+  Returns CcaOnlinePush(scores [2, S, new] float64, decisions [S, new] uint8, proj [S, emitted, 3 dims]
+  float32 (a | b1 | b2) and frame [2, S, emitted] float64 (None without want_frames), plan) with
+  plan = online_plan(frames_before, n, max(post1, post2), ...).  Queued, not waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  if reduction not in CCA_ONLINE_REDUCTIONS:
+    raise ValueError('cca_online_push: reduction %r (one of %s)' % (reduction, ', '.join(CCA_ONLINE_REDUCTIONS)))
+  if decoder not in SWEEP_DECODERS:
+    raise ValueError('cca_online_push: unknown decoder %r' % (decoder,))
+  sessions = int(state.shape[0])
+  pre1, post1, pre2, post2 = int(pre1), int(post1), int(pre2), int(post2)
+  nl1, nl2 = pre1 + 1 + post1, pre2 + 1 + post2
+  if rot_x.dim() != 3 or rot_y.dim() != 3 or mean_x.dim() != 2 or mean_y.dim() != 2:
+    raise ValueError('cca_online_push: the means are [M, k] and the rotations [M, k, dims]')
+  models, k1, dims = (int(v) for v in rot_x.shape)
+  k2 = int(rot_y.shape[1])
+  if (nl1 < 1 or nl2 < 1 or k1 % nl1 or k2 % nl2 or tuple(rot_y.shape) != (models, k2, dims) or
+      tuple(mean_x.shape) != (models, k1) or tuple(mean_y.shape) != (models, k2) or models not in (1, sessions)):
+    raise ValueError('cca_online_push: rotations of %s and %s with means of %s and %s for %d + %d lags and %d '
+                     'sessions' % (tuple(rot_x.shape), tuple(rot_y.shape), tuple(mean_x.shape),
+                                   tuple(mean_y.shape), nl1, nl2, sessions))
+  c1, c2 = k1 // nl1, k2 // nl2
+  n = 0 if eeg is None else int(eeg.shape[1])
+  if eeg is not None and (tuple(eeg.shape) != (sessions, n, c1) or feat1 is None or feat2 is None or
+                          tuple(feat1.shape) != (sessions, n, c2) or tuple(feat2.shape) != (sessions, n, c2)):
+    raise ValueError('cca_online_push: eeg of %s and features of %s and %s for %d sessions of %d channels and %d '
+                     'features' % (tuple(eeg.shape), None if feat1 is None else tuple(feat1.shape),
+                                   None if feat2 is None else tuple(feat2.shape), sessions, c1, c2))
+  for name, t, dtype in (('eeg', eeg, torch.float32), ('feat1', feat1, torch.float32),
+                         ('feat2', feat2, torch.float32), ('mean_x', mean_x, torch.float32),
+                         ('rot_x', rot_x, torch.float32), ('mean_y', mean_y, torch.float32),
+                         ('rot_y', rot_y, torch.float32), ('corr', corr, torch.float64),
+                         ('lda', lda, torch.float64), ('state', state, torch.uint8)):
+    if t is not None and (t.dtype != dtype or t.device != h.device):
+      raise TypeError('cca_online_push: %s must be a %s tensor on %s, not %s on %s' %
+                      (name, dtype, h.device, t.dtype, t.device))
+  if n > 0:
+    if (c1 > 1 and eeg.stride(2) != 1) or (c2 > 1 and (feat1.stride(2) != 1 or feat2.stride(2) != 1)):
+      raise ValueError('cca_online_push: the columns of eeg and the features must be contiguous')
+    if feat2.stride() != feat1.stride():      # (one pair of strides serves both speakers)
+      feat1, feat2 = feat1.contiguous(), feat2.contiguous()
+  if tuple(corr.shape) != (sessions, 2, 3, dims) or (lda is not None and tuple(lda.shape) != (sessions, dims + 2)):
+    raise ValueError('cca_online_push: corr must be [%d, 2, 3, %d] and lda [%d, %d]' %
+                     (sessions, dims, sessions, dims + 2))
+  mean_x, rot_x, mean_y, rot_y = (t.contiguous() for t in (mean_x, rot_x, mean_y, rot_y))
+  corr = corr.contiguous()
+  lda = lda.contiguous() if lda is not None else None
+  plan = online_plan(frames_before, n, max(post1, post2), width, hop, flush)
+  emitted = plan.emitted_after - plan.emitted_before
+  # (every element a push emits is written; an empty tensor has no address: one spare element)
+  scores = h.empty((2 * sessions * plan.new_windows + 1,), 'float64')
+  decisions = h.empty((sessions * plan.new_windows + 1,), 'uint8')
+  proj = h.empty((sessions * emitted * 3 * dims + 1,), 'float32') if want_frames else None
+  frame = h.empty((2 * sessions * emitted + 1,), 'float64') if want_frames else None
+  live = n > 0
+  h.check(h.lib.td_cca_online_push(
+      h.ptr, sessions,
+      _ptr(eeg if live else None), int(eeg.stride(1)) if live and n > 1 else c1,
+      int(eeg.stride(0)) if live and sessions > 1 else max(n, 1) * c1,
+      _ptr(feat1 if live else None), _ptr(feat2 if live else None),
+      int(feat1.stride(1)) if live and n > 1 else c2,
+      int(feat1.stride(0)) if live and sessions > 1 else max(n, 1) * c2,
+      n, c1, pre1, post1, c2, pre2, post2, dims, _ptr(mean_x), _ptr(rot_x), _ptr(mean_y), _ptr(rot_y),
+      0 if models == 1 else 1, _ptr(corr), REDUCTIONS[reduction], _ptr(lda), int(width), int(hop),
+      SWEEP_DECODERS[decoder], int(frames_before), 1 if flush else 0, _ptr(state),
+      int(state.stride(0)) if sessions > 1 else int(state.shape[1]),
+      _ptr(scores), _ptr(decisions), _ptr(proj), _ptr(frame)))
+  return CcaOnlinePush(scores[:-1].reshape(2, sessions, plan.new_windows),
+                       decisions[:-1].reshape(sessions, plan.new_windows),
+                       proj[:-1].reshape(sessions, emitted, 3 * dims) if want_frames else None,
+                       frame[:-1].reshape(2, sessions, emitted) if want_frames else None, plan)
+
+
 def sos_filter(x, file_offsets, sos, zi, stage_split, state, reset, out_rows=None, out_offsets=None, handle=None):
   """The SOS cascade over x [N, C] (float32 / float64 device tensor), files concatenated along time:
   float64 output [N, C], or only the file-local rows out_rows (device int64, file f's at

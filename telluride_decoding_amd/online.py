@@ -23,6 +23,12 @@ input; `flush()` ends the recording (zero rows behind it, like the batch route's
         print('window %d: speaker %d' % (result.first_window + k, 1 if decision else 2))
     result = online.flush()
 
+A CCA experiment decodes the same way: a `CCADecoder` around a fitted `BrainModelCCA` (or the model directory
+`decoding.py --dnn_regressor cca --saved_model_dir` wrote) gives a session whose push takes one block of audio
+features per speaker, `online.push(eeg, feat1, feat2)`, and is ONE td_cca_online_push launch: the EEG view
+centred and rotated once per frame, each speaker's view against it over the model's dims, then the same
+windows and decisions.
+
 Without a GPU (`device.gpu_available()` false) the same object runs a NumPy session with the same
 semantics -- float64 throughout, window sums in frame order, td_online_plan's arithmetic -- so that the logic can
 be built and tested anywhere.  (The state-space decoder has no host form: 'ssd' needs the GPU.)
@@ -45,17 +51,23 @@ DECODER_TYPES = ('wta', 'stepped', 'step', 'ssd')
 OnlineResult = collections.namedtuple('OnlineResult', ['scores', 'decisions', 'first_window'])
 
 
-def session_parameters(decoder):
-  """What one listener's session needs from its decoder, checked against the online path's limits:
-  dict(c, pre, post, w [lags c] float32, b float32, corr [2, 3] float64, lda [3] float64 or None,
-  reduction)."""
+def session_parameters(decoder, **context):
+  """What one listener's session needs from its decoder, checked against the online path's limits.  A
+  LinearRegressionDecoder gives dict(kind='linear', c, pre, post, w [lags c] float32, b float32, corr [2, 3]
+  float64, lda [3] float64 or None, reduction); a CCADecoder what cca_session_parameters says (`context`: its
+  keyword arguments)."""
+  if isinstance(decoder, infer_decoder.CCADecoder):
+    return cca_session_parameters(decoder, **context)
   if not isinstance(decoder, infer_decoder.LinearRegressionDecoder):
-    raise ValueError('OnlineDecoder decodes with a LinearRegressionDecoder (no CCA model online), not a %s.' %
+    raise ValueError('OnlineDecoder decodes with a LinearRegressionDecoder or a CCADecoder, not a %s.' %
                      type(decoder).__name__)
+  if context:
+    raise TypeError('OnlineDecoder: %s is a CCA model\'s context; a linear model carries its own.' %
+                    ', '.join(sorted(context)))
   model = decoder.decoding_model
   if not isinstance(model, brain_model.BrainModelLinearRegression):
-    raise ValueError('OnlineDecoder needs a BrainModelLinearRegression (no DNN or CCA model online), not a %s.' %
-                     type(model).__name__)
+    raise ValueError('OnlineDecoder needs a BrainModelLinearRegression behind a LinearRegressionDecoder (no DNN '
+                     'model online), not a %s.' % type(model).__name__)
   if model.w_estimate is None:
     raise ValueError('OnlineDecoder needs a fitted model: BrainModelLinearRegression.fit first.')
   w = np.asarray(model.w_estimate, np.float32)
@@ -80,8 +92,94 @@ def session_parameters(decoder):
     kw = decoder._reduce_kwargs()
     lda = np.array([float(np.reshape(kw['lda_w'], -1)[0]), float(kw['lda_slope']), float(kw['lda_intercept'])],
                    np.float64)
-  return dict(c=c, pre=pre, post=post, w=w[:, 0].copy(), b=np.float32(np.reshape(model.b_estimate, -1)[0]),
+  return dict(kind='linear', c=c, pre=pre, post=post, w=w[:, 0].copy(), b=np.float32(np.reshape(model.b_estimate, -1)[0]),
               corr=np.array([stats, stats], np.float64), lda=lda, reduction=reduction)
+
+
+CONTEXT_KEYS = ('pre_context', 'post_context', 'input2_pre_context', 'input2_post_context')
+
+
+def cca_session_parameters(decoder, **context):
+  """What one listener's session needs from a CCADecoder around a fitted cca.BrainModelCCA, checked against
+  the limits of td_cca_online_push: dict(kind='cca', c, pre, post (the EEG view), c2, pre2, post2 (a speaker's
+  feature block), dims, mean_x [k1], rot_x [k1, dims], mean_y [k2], rot_y [k2, dims] float32, corr [2, 3, dims]
+  float64, lda [dims + 2] float64 or None, reduction).  The context is the decoder's decoding_model_params
+  (pre_context, post_context, input2_pre_context, input2_post_context -- what infer.get_data_for_model builds
+  its datasets from), else the model's add_metadata entry, else the keyword arguments of the same names."""
+  model = decoder.decoding_model
+  if model is None or not hasattr(model, 'rot_x') or not hasattr(model, '_input1_width'):
+    raise ValueError('OnlineDecoder needs a cca.BrainModelCCA behind a CCADecoder, not a %s.' %
+                     type(model).__name__)
+  if model.rot_x is None:
+    raise ValueError('OnlineDecoder needs a fitted CCA model: BrainModelCCA.fit first.')
+  unknown = sorted(set(context) - set(CONTEXT_KEYS))
+  if unknown:
+    raise TypeError('OnlineDecoder: unknown context argument %s (the context is %s).' %
+                    (', '.join(unknown), ', '.join(CONTEXT_KEYS)))
+  carried = decoder.decoding_model_params or getattr(model, 'telluride_metadata', None) or {}
+  if not isinstance(carried, dict) or not all(k in carried for k in CONTEXT_KEYS):
+    carried = {k: context.get(k, 0) for k in CONTEXT_KEYS}
+  if int(carried.get('input_offset', 0) or 0) != 0:
+    raise ValueError('OnlineDecoder decodes with an input_offset of 0, not %s.' % (carried['input_offset'],))
+  pre1, post1, pre2, post2 = (int(carried[k]) for k in CONTEXT_KEYS)
+  rot_x, rot_y = np.asarray(model.rot_x, np.float32), np.asarray(model.rot_y, np.float32)
+  mean_x, mean_y = np.asarray(model.mean_x, np.float32).reshape(-1), np.asarray(model.mean_y, np.float32).reshape(-1)
+  k1, k2, dims = int(rot_x.shape[0]), int(rot_y.shape[0]), int(rot_x.shape[1])
+  if min(pre1, post1, pre2, post2) < 0 or pre1 + 1 + post1 > MAX_LAGS or pre2 + 1 + post2 > MAX_LAGS:
+    raise ValueError('OnlineDecoder takes at most %d lags in a view, not %d + 1 + %d and %d + 1 + %d.' %
+                     (MAX_LAGS, pre1, post1, pre2, post2))
+  if (k1 % (pre1 + 1 + post1) or k2 % (pre2 + 1 + post2) or rot_y.shape[1] != dims or mean_x.size != k1 or
+      mean_y.size != k2):
+    raise ValueError('The CCA model has rotations of %s and %s for contexts of %d + 1 + %d and %d + 1 + %d frames.' %
+                     (rot_x.shape, rot_y.shape, pre1, post1, pre2, post2))
+  c1, c2 = k1 // (pre1 + 1 + post1), k2 // (pre2 + 1 + post2)
+  if not 1 <= c1 <= MAX_CHANNELS:
+    raise ValueError('OnlineDecoder takes 1 to %d channels, not %d.' % (MAX_CHANNELS, c1))
+  if not 1 <= c2 <= device.CCA_ONLINE_MAX_FEATURES:
+    raise ValueError('OnlineDecoder takes 1 to %d features per speaker, not %d.' %
+                     (device.CCA_ONLINE_MAX_FEATURES, c2))
+  if not 1 <= dims <= device.CCA_ONLINE_MAX_DIMS:
+    raise ValueError('OnlineDecoder takes 1 to %d dims, not %d.' % (device.CCA_ONLINE_MAX_DIMS, dims))
+  reduction = decoder._reduction
+  if reduction not in device.CCA_ONLINE_REDUCTIONS:
+    raise ValueError('OnlineDecoder reduces the dims of a CCA model with %s, not with %r.' %
+                     (', '.join(repr(r) for r in device.CCA_ONLINE_REDUCTIONS), reduction))
+  if reduction == 'second' and dims < 2:
+    raise ValueError('The reduction \'second\' needs at least 2 dims, not %d.' % dims)
+  # (the rotations plus a pass of one frame must fit the workgroup's LDS: the library says so, with the budget)
+  device.cca_online_lds_bytes(c1, pre1, post1, c2, pre2, post2, dims, 1)
+  mean_a, mean_b, power = decoder._stat_vectors(dims)
+  stats = np.stack([mean_a, mean_b, power]).astype(np.float64)
+  lda = None
+  if reduction == 'lda':
+    kw = decoder._reduce_kwargs()
+    lda_w = np.asarray(kw['lda_w'], np.float64).reshape(-1)
+    if lda_w.size != dims:
+      raise ValueError('The LDA has %d weights for %d dims.' % (lda_w.size, dims))
+    lda = np.concatenate([lda_w, [float(kw['lda_slope']), float(kw['lda_intercept'])]]).astype(np.float64)
+  return dict(kind='cca', c=c1, pre=pre1, post=post1, c2=c2, pre2=pre2, post2=post2, dims=dims,
+              mean_x=mean_x.copy(), rot_x=np.ascontiguousarray(rot_x), mean_y=mean_y.copy(),
+              rot_y=np.ascontiguousarray(rot_y), corr=np.stack([stats, stats]), lda=lda, reduction=reduction)
+
+
+def _cca_frame_score(a, b, stats, reduction, lda):
+  """frame_scores_kernel over the dims columns, float64: a, b [frames, dims], stats [3, dims]."""
+  v = (a - stats[0]) * (b - stats[1]) / stats[2]
+  if reduction == 'first':
+    return v[:, 0]
+  if reduction == 'second':
+    return v[:, 1]
+  acc = np.zeros((v.shape[0],), np.float64)
+  for c in range(v.shape[1]):                       # in column order
+    if reduction == 'mean':
+      acc = acc + v[:, c]
+    elif reduction == 'mean-squared':
+      acc = acc + np.where(v[:, c] > 0.0, v[:, c] * v[:, c], np.where(v[:, c] < 0.0, -v[:, c] * v[:, c], 0.0))
+    else:
+      acc = acc + v[:, c] * lda[c]
+  if reduction == 'lda':
+    return lda[-2] * acc + lda[-1]
+  return acc / float(v.shape[1])
 
 
 def _frame_score(truth, pred, stats, reduction, lda):
@@ -129,6 +227,14 @@ class _HostSession(object):
     truth = envs[i0:i0 + emitted]
     frame = np.stack([_frame_score(truth[:, k], pred, p['corr'][k], p['reduction'], p['lda'])
                       for k in (0, 1)], axis=1).reshape(emitted, 2)
+    scores, decisions = self._windows(frame, pl)
+    both = np.concatenate([self.tail, eeg])
+    self.tail = both[both.shape[0] - (pre + post):]
+    self.env_tail = envs[envs.shape[0] - post:] if post else envs[:0]
+    return scores, decisions, pred, frame, pl
+
+  def _windows(self, frame, pl):
+    """The windows a push completes from its per-frame scores [emitted, 2]: (scores, decisions)."""
     history = np.concatenate([self.recent, frame])   # frames [emitted_after - len(history), emitted_after)
     base = pl.emitted_after - history.shape[0]
     starts = (pl.first_window + np.arange(pl.new_windows)) * self.hop - base
@@ -147,10 +253,56 @@ class _HostSession(object):
           self.step = max(0.1, self.step - 0.1)
         decisions[i] = self.step > 0.5
     self.recent = history[max(0, history.shape[0] - self.width):]
+    return scores, decisions
+
+
+class _HostCcaSession(_HostSession):
+  """One listener's CCA session in NumPy float64: the semantics of td_cca_online_push."""
+
+  def reset(self):
+    p = self.p
+    self.delay = max(p['post'], p['post2'])
+    self.tail = np.zeros((p['pre'] + self.delay, p['c']), np.float64)
+    self.feat_tail = np.zeros((2, p['pre2'] + self.delay, p['c2']), np.float64)
+    self.recent = np.zeros((0, 2), np.float64)
+    self.step = 0.5
+
+  @staticmethod
+  def _project(rows, first, emitted, c, lags, mean, rot):
+    """(x~ - mean) @ rot for the frames whose lagged rows start at rows[first + i], summed in (lag, channel)
+    order whatever the push's length."""
+    out = np.zeros((emitted, rot.shape[1]), np.float64)
+    for l in range(lags):
+      for ch in range(c):
+        k = l * c + ch
+        out += (rows[first + l:first + l + emitted, ch] - mean[k])[:, None] * rot[k][None, :]
+    return out
+
+  def push(self, eeg, feat, frames_before, flush):
+    """eeg [n, c1], feat [2, n, c2]."""
+    p = self.p
+    c1, pre1, post1, c2, pre2, post2 = p['c'], p['pre'], p['post'], p['c2'], p['pre2'], p['post2']
+    post = self.delay
+    n = eeg.shape[0]
+    pl = device.online_plan(frames_before, n, post, self.width, self.hop, flush)
+    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c1))] if flush else []))
+    frows = np.concatenate([self.feat_tail, feat] + ([np.zeros((2, post, c2))] if flush else []), axis=1)
+    emitted = pl.emitted_after - pl.emitted_before
+    # rows[0] is the EEG row frames_before - pre1 - post, frows[:, 0] the feature row frames_before - pre2 -
+    # post: frame emitted_before + i reads rows[i0 + i : i0 + i + lags1] and frows[:, i0 + i : i0 + i + lags2]
+    i0 = pl.emitted_before - (frames_before - post)
+    mean_x, rot_x = p['mean_x'].astype(np.float64), p['rot_x'].astype(np.float64)
+    mean_y, rot_y = p['mean_y'].astype(np.float64), p['rot_y'].astype(np.float64)
+    a = self._project(rows, i0, emitted, c1, pre1 + 1 + post1, mean_x, rot_x)
+    bs = [self._project(frows[k], i0, emitted, c2, pre2 + 1 + post2, mean_y, rot_y) for k in (0, 1)]
+    frame = np.stack([_cca_frame_score(a, bs[k], p['corr'][k], p['reduction'], p['lda']) for k in (0, 1)],
+                     axis=1).reshape(emitted, 2)
+    scores, decisions = self._windows(frame, pl)
     both = np.concatenate([self.tail, eeg])
-    self.tail = both[both.shape[0] - (pre + post):]
-    self.env_tail = envs[envs.shape[0] - post:] if post else envs[:0]
-    return scores, decisions, pred, frame, pl
+    self.tail = both[both.shape[0] - (pre1 + post):]
+    fboth = np.concatenate([self.feat_tail, feat], axis=1)
+    self.feat_tail = fboth[:, fboth.shape[1] - (pre2 + post):]
+    return scores, decisions, np.concatenate([a] + bs, axis=1), frame, pl
 
 
 class OnlineDecoder(object):
@@ -163,17 +315,35 @@ class OnlineDecoder(object):
   infer.run_reduction_test does.  window_step defaults to window_size // 2.  decoder_type: 'wta',
   'stepped' or 'ssd' (two launches per push: the windows, then td_decode_ssd_stream on them, device to
   device).
+
+  Or one infer_decoder.CCADecoder around a fitted cca.BrainModelCCA, or a list of S of them (a bank is all
+  linear or all CCA, with the same shapes, dims and reduction throughout): the push is then
+  push(eeg, feat1, feat2) with one block of audio features [n, c2] / [S, n, c2] per speaker, the EEG view is
+  projected once per frame and each speaker's view against the same rotations (td_cca_online_push), and the
+  dims columns are scored and reduced as Decoder.infer_one does.  The context of the two views comes from the
+  decoder's decoding_model_params (pre_context, post_context, input2_pre_context, input2_post_context), or
+  from keyword arguments of those names when the model carries none; results run max(post_context,
+  input2_post_context) frames behind the input.
   """
 
   def __init__(self, decoders, window_size, window_step=None, decoder_type='wta', frame_rate=100.0,
-               ssd_offset=0.0):
+               ssd_offset=0.0, **context):
     if isinstance(decoders, infer_decoder.Decoder) or not isinstance(decoders, (list, tuple)):
       decoders = [decoders]
     if not decoders:
       raise ValueError('OnlineDecoder needs at least one decoder.')
-    self._params = [session_parameters(d) for d in decoders]
+    self._params = [session_parameters(d, **context) for d in decoders]
     first = self._params[0]
+    self.kind = first['kind']
+    shape_keys = ('c', 'pre', 'post', 'c2', 'pre2', 'post2', 'dims', 'reduction')
     for p in self._params[1:]:
+      if p['kind'] != self.kind:
+        raise ValueError('A bank is all linear or all CCA, not a %s decoder beside a %s one.' %
+                         (p['kind'], self.kind))
+      if self.kind == 'cca' and any(p[k] != first[k] for k in shape_keys):
+        raise ValueError('Every CCA decoder of a bank has the same channels, features, contexts, dims and '
+                         'reduction: %s and %s.' % (tuple(first[k] for k in shape_keys),
+                                                    tuple(p[k] for k in shape_keys)))
       if (p['c'], p['pre'], p['post'], p['reduction']) != (first['c'], first['pre'], first['post'],
                                                            first['reduction']):
         raise ValueError('Every decoder of a bank has the same channels, context and reduction: %s and %s.' %
@@ -190,6 +360,10 @@ class OnlineDecoder(object):
     self.sessions = len(self._params)
     self.channels, self.pre, self.post = first['c'], first['pre'], first['post']
     self.reduction = first['reduction']
+    self.delay = self.post                      # frames the results run behind the input
+    if self.kind == 'cca':
+      self.features, self.pre2, self.post2, self.dims = first['c2'], first['pre2'], first['post2'], first['dims']
+      self.delay = max(self.post, self.post2)
     self.window_size, self.window_step = window_size, window_step
     self.decoder_type = 'stepped' if decoder_type == 'step' else decoder_type
     self._ssd = None
@@ -214,6 +388,23 @@ class OnlineDecoder(object):
     h = device.default_handle()
     torch = device._torch()
     ps = self._params
+    if self.kind == 'cca':
+      names = ('mean_x', 'rot_x', 'mean_y', 'rot_y')
+      shared = all(np.array_equal(p[k], ps[0][k]) for p in ps[1:] for k in names)
+      models = ps[:1] if shared else ps
+      dev = dict(h=h)
+      for k in names:
+        stacked = np.stack([p[k] for p in models])
+        dev[k] = h.to_device(stacked.reshape(-1, stacked.shape[-1])).reshape(stacked.shape)
+      dev['corr'] = h.to_device(np.stack([p['corr'] for p in ps]).reshape(-1, self.dims),
+                                np.float64).reshape(-1, 2, 3, self.dims)
+      dev['lda'] = (h.to_device(np.stack([p['lda'] for p in ps]), np.float64)
+                    if self.reduction == 'lda' else None)
+      nbytes = device.cca_online_state_bytes(self.channels, self.pre, self.post, self.features, self.pre2,
+                                             self.post2, self.window_size)
+      dev['state'] = torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device)
+      dev['ssd_state'] = device.ssd_state(self.sessions, handle=h) if self._ssd is not None else None
+      return dev
     # (sessions around ONE model read one copy of it)
     shared = all(np.array_equal(p['w'], ps[0]['w']) and p['b'] == ps[0]['b'] for p in ps[1:])
     models = ps[:1] if shared else ps
@@ -241,7 +432,8 @@ class OnlineDecoder(object):
           self._dev['ssd_state'].zero_()
     else:
       kind = self.decoder_type
-      self._host = [_HostSession(p, self.window_size, self.window_step, kind) for p in self._params]
+      session = _HostCcaSession if self.kind == 'cca' else _HostSession
+      self._host = [session(p, self.window_size, self.window_step, kind) for p in self._params]
 
   def tune(self, r1, r2):
     """For 'ssd': the state-space decoder's prior tuning on an initial attended / unattended stretch of
@@ -286,14 +478,41 @@ class OnlineDecoder(object):
                        'each, not eeg %s with envelopes %s.' % (s, c, c, tuple(eeg.shape), tuple(env.shape[:2])))
     return eeg, env
 
+  def _as_cca_bank(self, eeg, feat1, feat2):
+    """(eeg [S, n, C], (feat1, feat2) [S, n, c2] each) as float32 host arrays or device tensors."""
+    s, c, c2 = self.sessions, self.channels, self.features
+    if any(hasattr(a, 'is_cuda') for a in (eeg, feat1, feat2)):
+      torch = device._torch()
+      h = self._dev['h'] if self._on_device else None
+      conv = lambda a: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a))).to(
+          device=h.device if h else None, dtype=torch.float32)
+      arrays = [conv(a) for a in (eeg, feat1, feat2)]
+      arrays = [a.unsqueeze(0) if a.dim() == 2 else a for a in arrays]
+      if not self._on_device:
+        arrays = [a.cpu().numpy() for a in arrays]
+    else:
+      arrays = [np.asarray(a, np.float32) for a in (eeg, feat1, feat2)]
+      arrays = [a[None] if a.ndim == 2 else a for a in arrays]
+    eeg, feat1, feat2 = arrays
+    n = eeg.shape[1] if eeg.ndim == 3 else -1
+    if (eeg.ndim != 3 or tuple(eeg.shape) != (s, n, c) or tuple(feat1.shape) != (s, n, c2) or
+        tuple(feat2.shape) != (s, n, c2)):
+      raise ValueError('A push is eeg [%d, n, %d] (or [n, %d] for one session) with two feature blocks [%d, n, %d] '
+                       '(or [n, %d]), not eeg %s with features %s and %s.' %
+                       (s, c, c, s, c2, c2, tuple(eeg.shape), tuple(feat1.shape), tuple(feat2.shape)))
+    return eeg, (feat1, feat2)
+
   def push(self, eeg, env1, env2):
     """The next n frames of every session: eeg [n, C] / [S, n, C], env1 and env2 [n] / [S, n] (speaker 1,
-    speaker 2), host arrays or device tensors.  Returns OnlineResult(scores [S, new, 2] float64, decisions
-    [S, new] uint8 -- [S, new, 3] float64 (p, lower, upper) for 'ssd' --, first_window) for the windows this
-    push completes (host arrays)."""
+    speaker 2) -- for a CCA bank each speaker's feature block [n, c2] / [S, n, c2] --, host arrays or device
+    tensors.  Returns OnlineResult(scores [S, new, 2] float64, decisions [S, new] uint8 -- [S, new, 3] float64
+    (p, lower, upper) for 'ssd' --, first_window) for the windows this push completes (host arrays)."""
     if self.flushed:
       raise ValueError('The session was flushed: reset() starts the next recording.')
-    eeg, env = self._as_bank(eeg, env1, env2)
+    if self.kind == 'cca':
+      eeg, env = self._as_cca_bank(eeg, env1, env2)
+    else:
+      eeg, env = self._as_bank(eeg, env1, env2)
     return self._advance(eeg, env, False)
 
   def flush(self):
@@ -308,6 +527,9 @@ class OnlineDecoder(object):
   def _advance(self, eeg, env, flush):
     n = 0 if eeg is None else int(eeg.shape[1])
     kind = 'none' if self.decoder_type == 'ssd' else self.decoder_type
+    if self.kind == 'cca':
+      out = self._advance_cca(eeg, env, n, kind, flush)
+      return out if isinstance(out, OnlineResult) else self._finish(out)
     if not self._on_device:
       if eeg is None:
         eeg = np.zeros((self.sessions, 0, self.channels), np.float32)
@@ -328,6 +550,39 @@ class OnlineDecoder(object):
                              self.post, self.window_size, self.window_step, self.reduction, d['lda'], kind,
                              flush=flush, handle=h)
     self.frames_pushed += n
+    return self._finish(out)
+
+  def _advance_cca(self, eeg, feats, n, kind, flush):
+    """The CCA bank's push: an OnlineResult from the NumPy sessions, or the device's CcaOnlinePush."""
+    if not self._on_device:
+      if eeg is None:
+        eeg = np.zeros((self.sessions, 0, self.channels), np.float32)
+        feats = (np.zeros((self.sessions, 0, self.features), np.float32),) * 2
+      outs = [sess.push(np.asarray(eeg[i], np.float64),
+                        np.stack([np.asarray(feats[0][i], np.float64), np.asarray(feats[1][i], np.float64)]),
+                        self.frames_pushed, flush) for i, sess in enumerate(self._host)]
+      self.frames_pushed += n
+      return OnlineResult(np.stack([o[0] for o in outs]), np.stack([o[1] for o in outs]),
+                          outs[0][4].first_window)
+    d = self._dev
+    h = d['h']
+    feat1 = feat2 = None
+    if n == 0:
+      eeg = None
+    else:
+      up = lambda a: a if hasattr(a, 'is_cuda') else h.to_device(a.reshape(-1, a.shape[-1])).reshape(a.shape)
+      eeg, feat1, feat2 = up(eeg), up(feats[0]), up(feats[1])
+    out = device.cca_online_push(eeg, feat1, feat2, d['mean_x'], d['rot_x'], d['mean_y'], d['rot_y'], d['corr'],
+                                 d['state'], self.frames_pushed, self.pre, self.post, self.pre2, self.post2,
+                                 self.window_size, self.window_step, self.reduction, d['lda'], kind, flush=flush,
+                                 handle=h)
+    self.frames_pushed += n
+    return out
+
+  def _finish(self, out):
+    """A device push's windows as an OnlineResult; for 'ssd' through td_decode_ssd_stream first."""
+    d = self._dev
+    h = d['h']
     new = out.plan.new_windows
     scores = out.scores.permute(1, 2, 0)
     if self._ssd is None:
