@@ -953,6 +953,42 @@ int td_columns_assemble(td_handle* h, int num_sources, const void* const* src_de
  * columns.  transposed 0: one lane per output element.  Read-only; no handle. */
 int td_columns_route(int num_sources, int max_width, int* transposed);
 
+/* ------------------------------------------------------------------ BioSemi BDF
+ * ingest_bdf.parse_bdf_file and BrainTrial.find_status_trigger_times.
+ *
+ * td_raw24_decode: out_dev[s * ld_out + r * n + i] = scale_host[s] * (offset_host[s] + double(x)), n =
+ * samples_per_record, x the sign-extended 24-bit little-endian sample b0 | b1 << 8 | b2 << 16 at byte
+ * data_offset + r * record_bytes + signal_offset_host[s] + 3 * i of image_dev [image_bytes].  A float64 add, then a
+ * multiply, each rounded once: numpy's bits.  The description of the file is td_raw_decode's (signals that are not
+ * wanted are not listed, their bytes still count in record_bytes) but nothing in it needs an alignment: data_offset,
+ * record_bytes and every signal offset may be any byte value.  The image must be 16-byte aligned, out_dev 8-byte
+ * aligned.  No byte at or past image_bytes is read.  One route for every n >= 1, shaped for runs of 3 n >= 768 bytes
+ * (BioSemi's records of one second).
+ * TD_ERR_INVALID before anything is queued: a NULL pointer, an image that is not 16-byte aligned, a misaligned
+ * output, records that do not fit the image, a signal outside its record, ld_out < records * n, fewer than 1 or more
+ * than 1024 signals.  records == 0: TD_OK, nothing is launched.  Waits for nothing. */
+int td_raw24_decode(td_handle* h, const uint8_t* image_dev, int64_t image_bytes, int64_t data_offset, int64_t records,
+                    int64_t record_bytes, int samples_per_record, int num_signals, const int64_t* signal_offset_host,
+                    const double* scale_host, const double* offset_host, double* out_dev, int64_t ld_out);
+/* The code changes of a trigger channel, compacted in order.  signal_dev: n float64 values `stride` elements apart
+ * (8-byte aligned; finite, |v| < 2^31).  code[i] = (int64)v[i] & mask (truncation toward zero), 0 < mask <= 0xffffff;
+ * sample i is an event when code[i] != code[i - 1] and code[i] != 0, a code of 0 assumed before the first sample.
+ *   td_code_onsets_plan   chunk = the samples a workgroup takes, groups = ceil(n / chunk).  Read-only; no handle.
+ *                         TD_ERR_INVALID: n < 0.
+ *   td_code_onsets_count  offsets_dev [groups + 1] int64: [g] = the events before chunk g, [groups] = the number of
+ *                         events -- the 8 bytes the host reads to allocate exactly.  Two launches (n == 0: one).
+ *   td_code_onsets_fill   with offsets_dev as td_code_onsets_count left it for the same signal and mask: at_dev[k] =
+ *                         the sample index of event k, code_dev[k] = its code, in increasing order of the index, for
+ *                         k < capacity (events from `capacity` on are not written).  One launch; capacity == 0 or
+ *                         n == 0: TD_OK, nothing is launched.
+ * Deterministic: per-workgroup counts, an exclusive scan by one workgroup, ranks from ballots; no workgroup waits
+ * for another and no atomic is used.  Both wait for nothing. */
+int td_code_onsets_plan(int64_t n, int* chunk, int64_t* groups);
+int td_code_onsets_count(td_handle* h, const double* signal_dev, int64_t n, int64_t stride, int mask,
+                         int64_t* offsets_dev);
+int td_code_onsets_fill(td_handle* h, const double* signal_dev, int64_t n, int64_t stride, int mask,
+                        const int64_t* offsets_dev, int64_t capacity, int64_t* at_dev, int32_t* code_dev);
+
 /* ------------------------------------------------------------------ fully connected regressor
  * brain_model.BrainModelDNN (reference brain_model.py:486-549): Dense layers z = a.W + b in float32, ReLU on
  * the num_hidden hidden layers (hidden_host[i] units each), a linear output layer of d units.  The input is

@@ -182,6 +182,10 @@ SIGNATURES = {
     'td_raw_route': [_i, _i, _i64, _c.POINTER(_i), _c.POINTER(_i)],
     'td_columns_assemble': [_vp, _i, _c.POINTER(_vp), _pi64, _c.POINTER(_i), _c.POINTER(_i), _i64, _vp, _i64],
     'td_columns_route': [_i, _i, _c.POINTER(_i)],
+    'td_raw24_decode': [_vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _pi64, _pd, _pd, _vp, _i64],
+    'td_code_onsets_plan': [_i64, _c.POINTER(_i), _pi64],
+    'td_code_onsets_count': [_vp, _vp, _i64, _i64, _i, _vp],
+    'td_code_onsets_fill': [_vp, _vp, _i64, _i64, _i, _vp, _i64, _vp, _vp],
     'td_mlp_train': _MLP + _FIT + _EPOCHS + [_f, _f, _f] + _SEED_STATS,
     'td_mlp_grad': _MLP + _FIT + _GRAD,
     'td_mlp_train_loss': _MLP + _FIT + _EPOCHS + [_f, _f, _f] + _SEED_STATS + [_i],

@@ -1385,6 +1385,81 @@ def raw_decode(image, data_offset, records, record_bytes, samples_per_record, sa
   return out
 
 
+def raw24_decode(image, data_offset, records, record_bytes, samples_per_record, signal_offsets, scales, offsets,
+                 out=None, handle=None):
+  """The signals of a BDF recording's file image as a float64 channel-major device matrix [signals, records *
+  samples_per_record] (td_raw24_decode): scales[s] * (offsets[s] + float64(x)), x the sign-extended 24-bit
+  little-endian sample.  The layout is raw_decode's, but data_offset, record_bytes and the signal offsets may be any
+  byte values.  image: contiguous device uint8, 16-byte aligned.  out: a float64 matrix with contiguous rows of at
+  least records * samples_per_record elements, filled and returned.  Waits for nothing."""
+  torch = _torch()
+  h = handle or default_handle()
+  if image.dtype != torch.uint8 or image.dim() != 1 or not image.is_contiguous():
+    raise ValueError('raw24_decode: a contiguous uint8 device image is needed')
+  n, records = int(samples_per_record), int(records)
+  num = len(signal_offsets)
+  if not 1 <= num <= RAW_MAX_SIGNALS:
+    raise ValueError('raw24_decode: 1 .. %d signals, not %d' % (RAW_MAX_SIGNALS, num))
+  if len(scales) != num or len(offsets) != num:
+    raise ValueError('raw24_decode: %d signals need as many scales and offsets' % num)
+  if out is None:
+    out = h.empty((num, max(records * n, 0)), 'float64')
+  if (out.dim() != 2 or out.dtype != torch.float64 or out.shape[0] < num or out.shape[1] < records * n or
+      (out.shape[1] > 1 and out.stride(1) != 1)):
+    raise ValueError('raw24_decode: a %s [>= %d, >= %d] matrix with contiguous rows is needed, not %s %s' %
+                     (torch.float64, num, records * n, tuple(out.shape), out.dtype))
+  keep_off, off_p = _lib.i64_array([int(o) for o in signal_offsets])
+  keep_scale, scale_p = _lib.f64_array(np.asarray(scales, np.float64).reshape(-1))
+  keep_add, add_p = _lib.f64_array(np.asarray(offsets, np.float64).reshape(-1))
+  h.check(h.lib.td_raw24_decode(h.ptr, _ptr(image), int(image.numel()), int(data_offset), records, int(record_bytes),
+                                n, num, off_p, scale_p, add_p, _ptr(out), _row_stride(out)))
+  return out
+
+
+CODE_MASK_MAX = 0xffffff
+
+
+def code_onsets_plan(n):
+  """(chunk, groups) of code_onsets for a signal of n samples: the samples one workgroup takes and the number of
+  workgroups, ceil(n / chunk) (td_code_onsets_plan).  Needs the library, not a GPU."""
+  lib = _lib.load()
+  chunk, groups = ctypes.c_int(0), ctypes.c_int64(0)
+  if lib.td_code_onsets_plan(int(n), ctypes.byref(chunk), ctypes.byref(groups)) != 0:
+    raise ValueError('code_onsets_plan: bad size (%s samples)' % (n,))
+  return int(chunk.value), int(groups.value)
+
+
+def code_onsets(signal, mask=0xffff, handle=None):
+  """(sample indices int64, codes int32) of the events of a trigger channel on the device, in increasing order of
+  the index: code = int64(signal) & mask (truncation toward zero), an event wherever the code differs from the one
+  before (0 before the first sample) and is not 0 (td_code_onsets_count, td_code_onsets_fill).  signal: a float64
+  device tensor [n] or [n, 1] with any element stride (a column of a matrix is read where it lies).  The number of
+  events (8 bytes) and the events come back; the signal does not."""
+  torch = _torch()
+  h = handle or default_handle()
+  if signal.dim() == 2 and signal.shape[1] == 1:
+    signal = signal[:, 0]
+  if signal.dim() != 1 or signal.dtype != torch.float64 or not signal.is_cuda:
+    raise ValueError('code_onsets: a float64 device tensor [n] or [n, 1] is needed, not %s %s' %
+                     (tuple(signal.shape), signal.dtype))
+  mask = int(mask)
+  if not 0 < mask <= CODE_MASK_MAX:
+    raise ValueError('code_onsets: a mask of %#x is outside 1 .. %#x' % (mask, CODE_MASK_MAX))
+  n = int(signal.shape[0])
+  stride = int(signal.stride(0)) if n > 1 else 1
+  if stride < 1:
+    raise ValueError('code_onsets: a signal with an element stride of %d' % stride)
+  groups = code_onsets_plan(n)[1]
+  with torch.cuda.stream(h._stream):
+    offsets = h.empty((groups + 1,), 'int64')
+    h.check(h.lib.td_code_onsets_count(h.ptr, _ptr(signal), n, stride, mask, _ptr(offsets)))
+    total = int(offsets[groups:].cpu()[0])
+    at, codes = h.empty((total,), 'int64'), h.empty((total,), 'int32')
+    h.check(h.lib.td_code_onsets_fill(h.ptr, _ptr(signal), n, stride, mask, _ptr(offsets), total, _ptr(at),
+                                      _ptr(codes)))
+    return at.cpu().numpy(), codes.cpu().numpy()
+
+
 def columns_route(num_sources, max_width):
   """Whether columns_assemble takes the tiled transpose for that many sources, the widest of `max_width` columns
   (td_columns_route).  Needs the library, not a GPU."""

@@ -22,7 +22,9 @@ What differs from the reference:
   * discover_feature_shapes returns {name: (width, dtype name)} (tfrecord.discover_feature_shapes), not
     tf.io.FixedLenFeature objects: TensorFlow is not a dependency.
   * EdfBrainDataFile and parse_edf_file import pyedflib when used and raise an ImportError that says so;
-    ingest_edf has an EdfBrainDataFile and a parse_edf_file that need no pyedflib and decode the file on the GPU.
+    ingest_edf has an EdfBrainDataFile and a parse_edf_file that need no pyedflib and decode the file on the GPU;
+    ingest_bdf has the same for BioSemi BDF files (24-bit samples), whose 'Status' events
+    BrainTrial.find_status_trigger_times finds on the device.
   * assemble_brain_data builds 'eeg' from float32 / float64 device tensors in one launch
     (device.columns_assemble) instead of one strided copy per channel.
   * BrainVision recordings are read by ingest_brainvision, a module of its own as in the reference.
@@ -346,6 +348,25 @@ class BrainTrial(object):
     bit = fixed % 2
     rising = np.logical_and(np.logical_not(bit[:-1]), bit[1:])
     return np.nonzero(rising)[0] / float(chan.sr), raw, fixed
+
+  def find_status_trigger_times(self, channel_name='Status', mask=0xffff):
+    """(times in seconds float64, codes int64) of the events of a code channel such as BioSemi's 'Status': with
+    code = int64(signal) & mask (truncation toward zero), an event is a sample whose code differs from the one
+    before (a 0 is assumed before the first sample, as find_audio_trigger_times does) and is not 0.  A device
+    signal is searched where it is (device.code_onsets) and only the events are copied back; a NumPy one by NumPy."""
+    if channel_name not in self._brain_data:
+      raise ValueError('channel name %s not in brain data %s.' % (channel_name, list(self._brain_data)))
+    chan = self._brain_data[channel_name]
+    if _is_device_tensor(chan.signal):
+      signal = chan.signal
+      if signal.dtype != _torch().float64:
+        signal = signal.to(_torch().float64)
+      at, codes = device.code_onsets(signal.reshape(signal.shape[0], -1)[:, 0], mask)
+    else:
+      code = np.asarray(chan.signal).reshape(chan.signal.shape[0], -1)[:, 0].astype(np.int64) & int(mask)
+      at = np.flatnonzero((code != np.concatenate(([0], code[:-1]))) & (code != 0))
+      codes = code[at]
+    return at / float(chan.sr), codes.astype(np.int64)
 
   def find_cognionix_trigger_time(self, channel_name='EXP32', level=8000):
     if channel_name not in self._brain_data:

@@ -18,8 +18,8 @@ With a GPU (device.gpu_available()) the file is uploaded once and one launch (de
 [signals, samples] device matrix; a signal's values are a row of it.  Without one the same values are NumPy's.
 
 Read: plain EDF and continuous EDF+ ('EDF+C'); signals labelled 'EDF Annotations' are left out.  A ValueError
-that names the reason: EDF+D (discontinuous), BDF (24-bit samples), ordinary signals that differ in samples per
-record, a header that does not hold together.  A record count of -1 (a recording that was cut off) or one larger
+that names the reason: EDF+D (discontinuous), BDF (24-bit samples: ingest_bdf reads those, with this module's header
+parser and layout), ordinary signals that differ in samples per record, a header that does not hold together.  A record count of -1 (a recording that was cut off) or one larger
 than the file holds is replaced by the number of whole records in the file.
 """
 import os
@@ -49,30 +49,33 @@ def _number(fields, name, kind, path):
     raise ValueError('%s: the header field %s does not hold a number: %r' % (path, name, fields[name]))
 
 
-def read_edf_header(path):
-  """(main header, [per-signal header], file size) of an EDF file: every field trimmed, the numeric ones converted;
-  'header_bytes', 'records', 'signals' ints, 'record_duration' and the four ranges floats."""
+def _read_header(path, kind):
+  """read_edf_header (kind 'EDF') and ingest_bdf.read_bdf_header (kind 'BDF'): the two formats differ in their first
+  eight bytes and in the name of the discontinuous variant."""
   size = os.path.getsize(path)
   with open(path, 'rb') as f:
     fixed = f.read(256)
     if len(fixed) < 256:
-      raise ValueError('%s: %d bytes are less than an EDF header' % (path, len(fixed)))
-    if fixed[:1] == b'\xff':
+      raise ValueError('%s: %d bytes are less than %s header' % (path, len(fixed), 'an EDF' if kind == 'EDF' else 'a BDF'))
+    if kind == 'EDF' and fixed[:1] == b'\xff':
       raise ValueError('%s: a BDF file (24-bit samples) is not read' % path)
+    if kind == 'BDF' and fixed[:8] != b'\xffBIOSEMI':
+      raise ValueError('%s: not a BioSemi BDF file (it starts with %r); EDF files are read by ingest_edf' %
+                       (path, fixed[:8]))
     main, at = {}, 0
     for name, width in _MAIN_FIELDS:
       main[name] = _text(fixed[at:at + width])
       at += width
-    for name, kind in (('header_bytes', int), ('records', int), ('signals', int), ('record_duration', float)):
-      main[name] = _number(main, name, kind, path)
+    for name, convert in (('header_bytes', int), ('records', int), ('signals', int), ('record_duration', float)):
+      main[name] = _number(main, name, convert, path)
     count = main['signals']
     if count < 1 or main['header_bytes'] != 256 * (count + 1):
       raise ValueError('%s: a header of %d bytes does not go with %d signals' % (path, main['header_bytes'], count))
     block = f.read(256 * count)
   if len(block) < 256 * count:
     raise ValueError('%s: the file ends inside its header' % path)
-  if main['reserved'].startswith('EDF+D'):
-    raise ValueError('%s: a discontinuous recording (EDF+D) is not read' % path)
+  if main['reserved'].startswith(kind + '+D'):
+    raise ValueError('%s: a discontinuous recording (%s+D) is not read' % (path, kind))
   signals, at = [{} for _ in range(count)], 0
   for name, width in _SIGNAL_FIELDS:
     for s in range(count):
@@ -85,18 +88,26 @@ def read_edf_header(path):
   return main, signals, size
 
 
-def _layout(path):
+def read_edf_header(path):
+  """(main header, [per-signal header], file size) of an EDF file: every field trimmed, the numeric ones converted;
+  'header_bytes', 'records', 'signals' ints, 'record_duration' and the four ranges floats."""
+  return _read_header(path, 'EDF')
+
+
+def _layout(path, kind='EDF', width=2, annotations=(ANNOTATIONS,), unscaled=()):
   """What both routes work from: (main, the ordinary signals' headers, their byte offsets in a record, samples per
-  record, record bytes, whole records to read, bitvalues, offsets)."""
-  main, signals, size = read_edf_header(path)
+  record, record bytes, whole records to read, bitvalues, offsets).  ingest_bdf asks for kind 'BDF': samples of
+  `width` 3 bytes, its own annotation label beside EDF's, and the labels in `unscaled` served as stored (bitvalue 1,
+  offset 0, whatever their ranges say)."""
+  main, signals, size = _read_header(path, kind)
   offsets, at = [], 0
   for s in signals:
     if s['samples_per_record'] < 0:
       raise ValueError('%s: signal %s has %d samples per record' % (path, s['label'], s['samples_per_record']))
     offsets.append(at)
-    at += 2 * s['samples_per_record']
+    at += width * s['samples_per_record']
   record_bytes = at
-  kept = [(s, off) for s, off in zip(signals, offsets) if s['label'] != ANNOTATIONS]
+  kept = [(s, off) for s, off in zip(signals, offsets) if s['label'] not in annotations]
   if not kept:
     raise ValueError('%s: no signals but annotations' % path)
   counts = sorted({s['samples_per_record'] for s, _ in kept})
@@ -111,6 +122,10 @@ def _layout(path):
   records = whole if (main['records'] < 0 or main['records'] > whole) else main['records']
   scale, add = [], []
   for s, _ in kept:
+    if s['label'] in unscaled:
+      scale.append(np.float64(1.0))
+      add.append(np.float64(0.0))
+      continue
     if s['digital_max'] == s['digital_min'] or s['physical_max'] == s['physical_min']:
       raise ValueError('%s: signal %s has an empty physical or digital range' % (path, s['label']))
     bitvalue = np.float64(s['physical_max'] - s['physical_min']) / np.float64(s['digital_max'] - s['digital_min'])
@@ -146,6 +161,11 @@ def parse_edf_file(sample_edf_file):
     for i, off in enumerate(offsets):
       digital = raw[:, off // 2:off // 2 + n].reshape(-1).astype(np.float64)
       values[i] = scale[i] * (add[i] + digital)
+  return _parsed(main, kept, n, records, values)
+
+
+def _parsed(main, kept, n, records, values):
+  """The dictionary parse_edf_file and ingest_bdf.parse_bdf_file return, around the decoded `values`."""
   rate = n / main['record_duration']
   signal_headers = []
   for s in kept:

@@ -3,7 +3,8 @@ route against device route.
 
 Workload (the defaults, DESIGN section 23's): 64 channels x 1.8e6 frames, an hour at 500 Hz, as a BrainVision
 float32 multiplexed file and as an EDF file with 500 samples per record, generated from a seed into a temporary
-directory.
+directory.  --formats also takes `bdf`: a BioSemi BDF file of --channels signals plus a 'Status'
+signal, --bdf_samples (2048) 24-bit samples per record.
    python tools/time_raw_ingest.py [--channels 64] [--frames 1800000] [--repeats 5] [--formats brainvision,edf]
 
 Prints one JSON object, per format:
@@ -18,6 +19,9 @@ Prints one JSON object, per format:
                                 strided-copy loop on the same rows: ms (median, fastest, slowest), the bytes read
                                 plus written, GB/s, and the time over that of `copy`, a device-to-device copy that
                                 moves the same number of bytes, timed the same way in this run
+  status_events (bdf)           BrainTrial.find_status_trigger_times on the device signal (the launches, the 8-byte
+                                count and the events copied back) and the host form that copies the channel back
+                                first: the host clock, seconds (median, fastest, slowest), and the number of events
 Exits with an error when there is no GPU.
 """
 import argparse
@@ -38,13 +42,15 @@ def main():
   ap.add_argument('--channels', type=int, default=64)
   ap.add_argument('--frames', type=int, default=1800000)
   ap.add_argument('--edf_samples', type=int, default=500)
+  ap.add_argument('--bdf_samples', type=int, default=2048)
   ap.add_argument('--repeats', type=int, default=5)
   ap.add_argument('--formats', default='brainvision,edf')
   args = ap.parse_args()
 
   import numpy as np
   import torch
-  from telluride_decoding_amd import device, ingest, ingest_brainvision, ingest_edf
+  from telluride_decoding_amd import device, ingest, ingest_bdf, ingest_brainvision, ingest_edf
+  from tests import host_bdf as hb
   from tests import host_raw as hr
   if not device.gpu_available():
     raise SystemExit('time_raw_ingest needs a GPU: there is nothing to time without one')
@@ -79,6 +85,35 @@ def main():
     dst = torch.empty_like(src)
     return spread(timed(lambda: dst.copy_(src)))
 
+  def status_events(make):
+    """find_status_trigger_times on the device signal (the launches, the 8-byte count and the events copied back)
+    against the host form, which copies the whole channel back first: the host clock, the median of --repeats."""
+    trial = ingest.BrainTrial('trial')
+    trial.load_brain_data(out_dir, make())
+    signal = trial.brain_data[hb.STATUS].signal
+    assert ingest._is_device_tensor(signal)
+
+    def clocked(fn):
+      fn()
+      times = []
+      for _ in range(args.repeats):
+        h.synchronize()
+        t0 = time.perf_counter()
+        found = fn()
+        times.append(time.perf_counter() - t0)
+      return found, spread(times, 6)
+
+    def on_host():
+      code = ingest._host_array(signal)[:, 0].astype(np.int64) & 0xffff
+      at = np.flatnonzero((code != np.concatenate(([0], code[:-1]))) & (code != 0))
+      return at / trial.brain_data[hb.STATUS].sr, code[at]
+
+    (times, codes), device_s = clocked(trial.find_status_trigger_times)
+    (host_times, host_codes), host_s = clocked(on_host)
+    assert np.array_equal(times, host_times) and np.array_equal(codes, host_codes)
+    return {'samples': int(signal.shape[0]), 'events': int(len(times)), 'device_s': device_s,
+            'host_copy_back_s': host_s}
+
   try:
     for fmt in args.formats.split(','):
       if fmt == 'brainvision':
@@ -86,6 +121,17 @@ def main():
         hr.write_brainvision(out_dir, 'rec', samples, hr.resolutions(args.channels), names=names)
         data_path, make = os.path.join(out_dir, 'rec.eeg'), lambda: ingest_brainvision.BvBrainDataFile('rec')
         del samples
+      elif fmt == 'bdf':
+        n = args.bdf_samples
+        records = args.frames // n
+        signals = [{'label': names[c], 'digital': rng.integers(-(1 << 23), 1 << 23, size=(records, n), dtype=np.int32),
+                    'physical_min': -262144, 'physical_max': 262143, 'digital_min': -8388608, 'digital_max': 8388607}
+                   for c in range(args.channels)]
+        signals.append(dict(signals[0], label=hb.STATUS, digital=hb.status_codes(rng, records * n, every=n // 2 + 1)
+                            .reshape(records, n)))
+        hb.write_bdf(os.path.join(out_dir, 'rec.bdf'), signals)
+        data_path, make = os.path.join(out_dir, 'rec.bdf'), lambda: ingest_bdf.BdfBrainDataFile('rec')
+        del signals
       else:
         n = args.edf_samples
         records = args.frames // n
@@ -113,7 +159,7 @@ def main():
           t1 = time.perf_counter()
         finally:
           device.gpu_available = really_available
-        per = 1 if fmt == 'brainvision' else args.edf_samples
+        per = {'brainvision': 1, 'edf': args.edf_samples, 'bdf': args.bdf_samples}[fmt]
         assert tuple(eeg.shape) == (args.frames // per * per, args.channels)
         return t1 - t0
 
@@ -133,6 +179,13 @@ def main():
                       sample_kind=device.RAW_FLOAT32, signal_offsets=[4 * c for c in range(args.channels)],
                       scales=hr.resolutions(args.channels))
         rows, elem = args.frames, 4
+      elif fmt == 'bdf':
+        n = args.bdf_samples
+        layout = dict(data_offset=256 * (args.channels + 2), records=args.frames // n,
+                      record_bytes=3 * n * (args.channels + 1), samples_per_record=n,
+                      signal_offsets=[3 * n * c for c in range(args.channels)], scales=[0.1] * args.channels,
+                      offsets=[0.5] * args.channels)
+        rows, elem = args.frames // n * n, 8
       else:
         n = args.edf_samples
         layout = dict(data_offset=256 * (args.channels + 1), records=args.frames // n,
@@ -150,7 +203,8 @@ def main():
       image.copy_(pinned, non_blocking=True)
       h.synchronize()
       t2 = time.perf_counter()
-      decode = lambda: device.raw_decode(image, out=matrix, handle=h, **layout)
+      decoder = device.raw24_decode if fmt == 'bdf' else device.raw_decode
+      decode = lambda: decoder(image, out=matrix, handle=h, **layout)
       decode()
       h.synchronize()
       t3 = time.perf_counter()
@@ -161,12 +215,14 @@ def main():
       t4 = time.perf_counter()
       out['device_split_s'] = {'file_read': round(t1 - t0, 4), 'upload': round(t2 - t1, 4),
                                'decode': round(t3 - t2, 4), 'assemble': round(t4 - t3, 4)}
-      out['route'] = {'decode_transposed': device.raw_route(layout['samples_per_record'], 4 if elem == 4 else 2,
-                                                            layout['record_bytes'])[0],
+      out['route'] = {'decode_transposed': fmt != 'bdf' and device.raw_route(
+          layout['samples_per_record'], 4 if elem == 4 else 2, layout['record_bytes'])[0],
                       'assemble_transposed': device.columns_route(args.channels, 1)}
 
       # ---- each launch against a copy of the same bytes
-      decode_bytes = layout['records'] * layout['record_bytes'] + args.channels * rows * elem
+      # (what the launch reads of the image -- the listed signals' bytes -- plus what it writes)
+      sample_bytes = {'brainvision': 4, 'edf': 2, 'bdf': 3}[fmt]
+      decode_bytes = args.channels * rows * (sample_bytes + elem)
       assemble_bytes = args.channels * rows * (elem + 4)
       copy_decode, copy_assemble = copy_ms(decode_bytes), copy_ms(assemble_bytes)
       out['decode'] = against_copy(timed(decode), decode_bytes, copy_decode['median'])
@@ -174,6 +230,8 @@ def main():
       out['loop'] = against_copy(timed(lambda: ingest._assemble_columns_loop(sources, rows, args.channels)),
                                  assemble_bytes, copy_assemble['median'])
       out['copy'] = {'decode_bytes_ms': copy_decode, 'assemble_bytes_ms': copy_assemble}
+      if fmt == 'bdf':
+        out['status_events'] = status_events(make)
       result[fmt] = out
       del pinned, image, matrix, eeg, sources
   finally:
