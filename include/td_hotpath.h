@@ -787,6 +787,56 @@ int td_cca_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int
                        int64_t state_session_stride, double* scores_dev, uint8_t* decisions_dev,
                        float* proj_dev, double* frame_dev);
 
+/* ------------------------------------------------------------------ online decode, fully connected regressor
+ * The session of td_online_push with a fully connected regressor (brain_model.BrainModelDNN behind
+ * infer_decoder.LinearRegressionDecoder) in front of the correlator: ONE launch per push, one workgroup per
+ * session, and however a recording is cut into pushes the outputs and the final state are those of one push, bit
+ * for bit.  The state block is td_online_push's (td_online_state_bytes; td_online_plan says what a push emits), and
+ * so is everything behind the prediction: td_frame_scores' expression for one column, the ring, td_window_means'
+ * sum, td_decide_wta's / td_decide_step's decisions, the tail update.  (td_fc_: "fully connected".  The td_online_*,
+ * td_mlp_* and td_dnn_* families are each checked as a closed set against their bindings, so this one has its own.)
+ *
+ * The prediction of an emitted frame t is td_mlp_forward's, bit for bit (one output, input_offset 0).  The model is
+ * td_mlp_*'s packed parameter buffer [W1 (K x h1), b1, W2, b2, ..., WL, bL], K = c (pre + 1 + post); the input is
+ * x~[k], k = lag c + channel, of the rows t - pre .. t + post, zero before the recording and, after a flush, past
+ * its end.  With ks = min(64, round_up(ceil(K / 64), 4)) rows of W1 a slice:
+ *   a slice partial   fmaf(x, w, s) from 0.f over the slice's rows in order
+ *   z1[j]             (0.f + the slice partials added in slice order) + b1[j]
+ *   ReLU              s <= 0.f ? 0.f : s, only when a layer follows
+ *   a later layer     an fmaf chain over its inputs in order from 0.f, then + b, then ReLU except on the last.
+ * W1 is streamed through LDS in chunks of whole slices (at most 4096 floats, double-buffered, 16-byte loads when
+ * h1 is a multiple of 4 and the model is 16-byte aligned); the small parameters are staged once per launch.
+ *
+ * td_fc_online_lds_bytes: the LDS of a launch that emits `emitted` frames and the frames per pass it takes:
+ *   bytes(pass) = 32 pass + 4 (2 chunk + round_up(n_small, 4) + (pass + pre + post) (c | 1) + 2 max(pass, post)
+ *                              + pass + 2 pass lda),
+ *   chunk = g ks round_up(h1, 4), g = min(slices, floor(4096 / (ks round_up(h1, 4)))), n_small = the parameters
+ *   behind W1, lda = (the widest hidden layer, 1 without one) | 1
+ * (scores and window means of a pass; two chunks of W1; the small parameters; the staged rows on an odd stride; the
+ * envelopes; the predictions; two activation buffers).  pass = min(64, max(emitted, 1)), halved (rounding up) while
+ * bytes(pass) exceeds TD_FC_ONLINE_LDS_BYTES; a shape whose bytes(1) exceeds it is refused by both entry points.
+ *
+ * td_fc_online_push: the sessions' next n frames.
+ *   eeg_dev, env_dev, n, c, pre, post, corr_dev, reduction, lda_dev, width, hop, decoder, frames_before, flush,
+ *   state_dev, state_session_stride and the four outputs: as td_online_push
+ *   hidden_host [num_hidden] the hidden layers' units (NULL with num_hidden 0: z1 is the prediction, no ReLU)
+ *   params_dev  the packed parameters, session stride params_session_stride (elements; 0 = one model for all)
+ * No atomics: two runs give the same bits.  TD_ERR_INVALID, before anything is queued and with the state
+ * untouched: what td_online_push refuses, and num_hidden outside 0..4, NULL hidden_host with num_hidden > 0, a
+ * hidden layer outside 1..64 units, K > 8192, a shape over the LDS budget, NULL params_dev, a parameter stride that
+ * is neither 0 nor a whole model.  With td_profile_enable the launch is bracketed as td_online_push's is. */
+#define TD_FC_ONLINE_LDS_BYTES 163840
+int td_fc_online_lds_bytes(int c, int pre, int post, int num_hidden, const int* hidden_host, int64_t emitted,
+                            int* pass, int64_t* bytes);
+int td_fc_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t eeg_ld,
+                       int64_t eeg_session_stride, const float* env_dev, int64_t env_ld,
+                       int64_t env_session_stride, int64_t n, int c, int pre, int post, const int* hidden_host,
+                       int num_hidden, const float* params_dev, int64_t params_session_stride,
+                       const double* corr_dev, int reduction, const double* lda_dev, int width, int hop,
+                       int decoder, int64_t frames_before, int flush, void* state_dev,
+                       int64_t state_session_stride, double* scores_dev, uint8_t* decisions_dev, float* pred_dev,
+                       double* frame_dev);
+
 /* ------------------------------------------------------------------ preprocessing
  * preprocess.Preprocessor (preprocess.py:54-587): the signal conditioning before the fits.
  *

@@ -162,6 +162,11 @@ SIGNATURES = {
     'td_cca_online_push': [_vp, _i] + [_vp, _i64, _i64] + [_vp, _vp, _i64, _i64] + [_i64] + _VIEW + _VIEW + [_i] +
                           [_vp, _vp, _vp, _vp, _i64] + [_vp, _i, _vp] + [_i, _i, _i, _i64, _i] + [_vp, _i64] +
                           [_vp, _vp, _vp, _vp],
+    'td_fc_online_lds_bytes': [_i, _i, _i, _i, _c.POINTER(_i), _i64, _c.POINTER(_i), _pi64],
+    # h, sessions | eeg, ld, stride | env, ld, stride | n, c, pre, post | hidden, num_hidden | params, stride | corr,
+    # reduction, lda | width, hop, decoder, frames_before, flush | state, stride | scores, decisions, pred, frame
+    'td_fc_online_push': [_vp, _i] + [_vp, _i64, _i64] * 2 + [_i64, _i, _i, _i] + [_c.POINTER(_i), _i] +
+                          [_vp, _i64] + [_vp, _i, _vp] + [_i, _i, _i, _i64, _i] + [_vp, _i64] + [_vp, _vp, _vp, _vp],
     'td_sos_filter': [_vp, _vp, _i, _i64, _i, _pi64, _i, _pd, _i, _i, _pd, _i, _vp, _vp, _pi64, _vp, _i64],
     'td_sos_filter_plan': [_i64, _i64, _i, _c.POINTER(_i), _c.POINTER(_i)],
     'td_reref_select': [_vp, _vp, _i, _i64, _i, _vp, _i64, _i, _c.POINTER(_i), _c.POINTER(_i),

@@ -1,0 +1,576 @@
+// Online attention decode with a fully connected regressor (td_fc_online_*): online.hip's session -- state on the
+// device, one workgroup per listener, ONE launch per push -- with brain_model.BrainModelDNN in front of the
+// correlator instead of the FIR prediction.  The state block is online.hip's, byte for byte (td_online_state_bytes,
+// td_online_plan serve as they are), and everything behind the prediction is online_push_kernel's, operation for
+// operation: frame_scores_kernel's expression, the ring, window_means_kernel's sum (256 threads stride the window,
+// 64-lane wave sums, ((w0 + w1) + (w2 + w3)) / width), decide_wta_kernel's / decide_step_kernel's decisions
+// (windows.hip), the tail update.
+//
+// The prediction of an emitted frame has td_mlp_forward's bits (mlp.hip).  Only the order within each sum is the
+// contract:
+//   slice partial  fmaf(x, w, s) from 0.f over the slice's rows of W1 in order; ks = min(64, round_up(ceil(K / 64), 4))
+//                  rows a slice (mlp_check_and_plan's rule);
+//   z1[j]          (0.f + the slice partials added in slice order) + b1[j];
+//   ReLU           s <= 0.f ? 0.f : s, only when a layer follows;
+//   later layers   an fmaf chain over the inputs in order from 0.f, then + b, then ReLU except on the last.
+// Every sum belongs to one frame, so no sum depends on where a frame falls in a push: any cut of a recording into
+// pushes gives the bits of one push.  No atomics, vector stores only.
+//
+// The mapping of sums to threads is this file's own.  A thread owns one frame and up to four groups of 4 columns of
+// W1 -- one read of x feeds up to 16 fused multiply-adds -- and keeps their accumulators in registers across the
+// slices; the threads of a pass of nf frames are laid frame-fastest over the workgroup (thread = frame + nf x column
+// lane), so a push of 10 frames into 64 units is 160 busy threads, and the lanes of a wave read few distinct rows of
+// W1 (broadcast) and distinct frames.  W1 (up to 2 MB) never fits in LDS: it is
+// streamed in chunks of whole slices (at most 4096 floats), global -> registers -> LDS, double-buffered -- the
+// loads of chunk i + 1 are in flight while chunk i is multiplied, one barrier a chunk -- with 16-byte loads along
+// W1's rows when the layer's width is a multiple of 4 (the chunk is then one contiguous span).  The staged EEG rows
+// hold every frame's lagged vector as the span that starts at its first row; their row stride is odd (c | 1), so
+// the frames of a half-wave sit on 32 different banks.  The small parameters (b1, W2, b2, ...) are staged once per
+// launch; the activations of a pass live in two LDS buffers with an odd row stride.
+#include "td_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kMaxChannels = 128, kMaxLags = 64, kMaxK = 8192;
+constexpr int kMaxHidden = 4, kMaxWidth = 64, kMaxKs = 64;
+constexpr int kPass = 64;                              // emitted frames per pass; halved until the LDS budget holds
+constexpr int kChunkFloats = kMaxKs * kMaxWidth;       // a staged chunk of W1: whole slices, at most this much
+constexpr int kLoads = kChunkFloats / 4 / kThreads;    // float4 a thread carries from global to LDS per chunk
+constexpr int kPairs = kPass * (kMaxWidth / 4) / kThreads;   // (frame, 4 columns) pairs a thread owns
+constexpr long long kLdsBudget = TD_FC_ONLINE_LDS_BYTES;
+
+// (online.hip's state block: [stepped state f64][ring f64 [2][width]][EEG tail f32 [pre + post][c]]
+// [envelope tail f32 [post][2]], rounded up to 8 bytes)
+__host__ __device__ inline long long state_ring_offset() { return 8; }
+__host__ __device__ inline long long state_eeg_offset(int width) { return 8 + 16LL * width; }
+__host__ __device__ inline long long state_env_offset(int c, int pre, int post, int width) {
+  return state_eeg_offset(width) + 4LL * c * (pre + post);
+}
+__host__ __device__ inline long long state_bytes(int c, int pre, int post, int width) {
+  return (state_env_offset(c, pre, post, width) + 8LL * post + 7) / 8 * 8;
+}
+
+// The network's shape and how W1 is cut: host arithmetic, passed to the kernel by value.
+struct DnnNet {
+  int nl;                          // layers (hidden + 1)
+  int w[kMaxHidden + 2];           // w[0] = K, w[1 .. nl - 1] hidden, w[nl] = 1
+  int off_w[kMaxHidden + 1], off_b[kMaxHidden + 1];   // offsets into the packed parameters
+  int n_params, small0, n_small;   // everything behind W1 starts at small0
+  int ks, nslices;                 // rows per slice of W1, slices
+  int nj;                          // w[1] rounded up to 4: the row stride of a staged chunk
+  int g, nchunks;                  // slices per staged chunk, chunks
+  int lda;                         // row stride of the staged activations (odd)
+};
+
+DnnNet net_of(int c, int pre, int post, const int* hidden, int num_hidden) {
+  DnnNet t;
+  memset(&t, 0, sizeof(t));
+  t.nl = num_hidden + 1;
+  t.w[0] = c * (pre + 1 + post);
+  int maxw = 1;
+  for (int i = 0; i < num_hidden; ++i) {
+    t.w[i + 1] = hidden[i];
+    maxw = hidden[i] > maxw ? hidden[i] : maxw;
+  }
+  t.w[t.nl] = 1;
+  int at = 0;
+  for (int l = 1; l <= t.nl; ++l) {
+    t.off_w[l - 1] = at; at += t.w[l - 1] * t.w[l];
+    t.off_b[l - 1] = at; at += t.w[l];
+  }
+  t.n_params = at;
+  t.small0 = t.w[0] * t.w[1];
+  t.n_small = at - t.small0;
+  t.ks = (int)td_round_up(td_ceil_div(t.w[0], 64), 4);
+  t.ks = t.ks > kMaxKs ? kMaxKs : t.ks;
+  t.nslices = (int)td_ceil_div(t.w[0], t.ks);
+  t.nj = (int)td_round_up(t.w[1], 4);
+  t.g = kChunkFloats / (t.ks * t.nj);
+  t.g = t.g > t.nslices ? t.nslices : t.g;
+  t.nchunks = (int)td_ceil_div(t.nslices, t.g);
+  t.lda = maxw | 1;
+  return t;
+}
+
+__host__ __device__ inline int row_stride(int c) { return c | 1; }
+
+// LDS of a launch: 8 (4 pass) for the pass's per-frame scores and window means, then float32: two chunks of W1, the
+// small parameters (rounded up to 4), the staged rows, the envelopes, the predictions, two activation buffers.
+long long lds_bytes(const DnnNet& t, int c, int pre, int post, int pass) {
+  const long long env_rows = pass > post ? pass : post;
+  return 32LL * pass + 4LL * (2LL * t.g * t.ks * t.nj + td_round_up(t.n_small, 4) +
+                              (long long)(pass + pre + post) * row_stride(c) + 2 * env_rows + pass +
+                              2LL * pass * t.lda);
+}
+
+// The largest pass (kPass halved, at least 1, no more than the frames to emit) whose LDS fits; 0: none does.
+int pass_of(const DnnNet& t, int c, int pre, int post, long long emitted_now) {
+  int pass = emitted_now < kPass ? (emitted_now > 1 ? (int)emitted_now : 1) : kPass;
+  while (pass > 1 && lds_bytes(t, c, pre, post, pass) > kLdsBudget) pass = (pass + 1) / 2;
+  return lds_bytes(t, c, pre, post, pass) <= kLdsBudget ? pass : 0;
+}
+
+struct DnnOnlineParams {
+  const float* eeg; long long eeg_ld, eeg_ss;
+  const float* env; long long env_ld, env_ss;
+  const float* params; long long params_ss;
+  const double* corr;            // [S][2][3]
+  const double* lda;             // [S][3] or null
+  long long n, p0;               // rows of this push, rows pushed before it
+  long long e0, e1;              // frames emitted before / after
+  long long w0, n_win;           // first new window, new windows
+  int c, pre, post, reduction, width, hop, decoder, pass;
+  DnnNet net;
+  unsigned char* state; long long state_ss;
+  double* scores; unsigned char* decisions; float* pred; double* frame;
+};
+
+// (windows.hip's wave_sum: the same shuffle tree, the same bits)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// (online.hip's frame_score) frame_scores_kernel's value for ONE column (windows.hip): a = the truth, b = the
+// prediction.  The sums over the columns start from 0.0 there, so they do here; the lda map is that kernel's one
+// fused multiply-add (slope * acc + intercept, contracted).
+__device__ __forceinline__ double frame_score(float truth, float pred, double mean_a, double mean_b,
+                                              double power, int reduction, double lda_w,
+                                              double lda_slope, double lda_intercept) {
+  const double v = ((double)truth - mean_a) * ((double)pred - mean_b) / power;
+  if (reduction == 0) return v;
+  double acc = 0.0;
+  if (reduction == 2) {
+    acc += v;
+  } else if (reduction == 3) {
+    acc += (v > 0.0 ? v * v : (v < 0.0 ? -v * v : 0.0));
+  } else {
+    acc += v * lda_w;
+    acc = fma(lda_slope, acc, lda_intercept);
+  }
+  return acc;
+}
+
+// Chunk ci of W1 (rows [ci g ks, ...) as [rows][nj], columns past w1 - 1 repeating it) from global into registers: float4
+// number tid + i kThreads of the chunk.  vec: w1 is a multiple of 4 and W1 is 16-byte aligned -- the chunk is one
+// contiguous span of W1.
+__device__ __forceinline__ void chunk_load(const float* __restrict__ w1p, const DnnNet& t, int ci, bool vec, int tid,
+                                           float4 (&regs)[kLoads]) {
+  const int k0 = ci * t.g * t.ks, w1 = t.w[1], nj = t.nj;
+  const int rows = t.w[0] - k0 < t.g * t.ks ? t.w[0] - k0 : t.g * t.ks;
+  const int n4 = rows * nj / 4;
+  const float* base = w1p + (long long)k0 * w1;
+  // (no branch around a load: an index past the chunk reads the chunk's last element and is dropped by
+  // chunk_store -- the loads of a chunk then issue back to back, with no wait between them)
+  if (vec) {
+#pragma unroll
+    for (int i = 0; i < kLoads; ++i) {
+      const int i4 = tid + i * kThreads;
+      regs[i] = reinterpret_cast<const float4*>(base)[i4 < n4 ? i4 : n4 - 1];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < kLoads; ++i) {
+      const int i4 = tid + i * kThreads;
+      const int e = (i4 < n4 ? i4 : n4 - 1) * 4, kk = e / nj, j = e - kk * nj;
+      const float* src = base + (long long)kk * w1;
+      const float v0 = src[j < w1 ? j : w1 - 1], v1 = src[j + 1 < w1 ? j + 1 : w1 - 1];
+      const float v2 = src[j + 2 < w1 ? j + 2 : w1 - 1], v3 = src[j + 3 < w1 ? j + 3 : w1 - 1];
+      regs[i] = make_float4(v0, v1, v2, v3);       // (a column past w1 - 1 repeats the last one: its sums are dropped)
+    }
+  }
+}
+
+__device__ __forceinline__ void chunk_store(float* buf, const DnnNet& t, int ci, int tid, const float4 (&regs)[kLoads]) {
+  const int k0 = ci * t.g * t.ks;
+  const int rows = t.w[0] - k0 < t.g * t.ks ? t.w[0] - k0 : t.g * t.ks;
+  const int n4 = rows * t.nj / 4;
+#pragma unroll
+  for (int i = 0; i < kLoads; ++i) {
+    const int i4 = tid + i * kThreads;
+    if (i4 < n4) reinterpret_cast<float4*>(buf)[i4] = regs[i];
+  }
+}
+
+// One slice of W1 for one frame and NG adjacent groups of 4 columns: per column a chain of fused multiply-adds from
+// 0.f over the slice's ksl rows in order, then added to the accumulators.  xp: the frame's staged x at the slice's
+// first row, which is channel ch0 of its lag; the rows of a lag are contiguous, the lags ldr apart.  wrow: the
+// thread's first column in the slice's first row of the staged chunk, the rows nj floats apart.
+template <int NG>
+__device__ __forceinline__ void slice_fma(const float* xp, const float* wrow, int nj, int ksl, int ch0, int c, int ldr,
+                                          float (&acc)[kPairs][4]) {
+  float s[NG][4];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) s[g][0] = s[g][1] = s[g][2] = s[g][3] = 0.f;
+  int kk = 0, ch = ch0;
+  while (kk < ksl) {
+    const int run = c - ch < ksl - kk ? c - ch : ksl - kk;       // rows left in this lag, or in the slice
+    // UN rows at a time: their reads are issued together, in front of their multiply-adds (one trip to LDS per UN
+    // rows, not per row); the rows of each column's chain stay in order
+    constexpr int UN = NG == 1 ? 8 : NG == 2 ? 6 : 4;
+    int i = 0;
+    for (; i + UN <= run; i += UN) {
+      float xv[UN];
+      float4 wv[UN][NG];
+#pragma unroll
+      for (int u = 0; u < UN; ++u) {
+        xv[u] = xp[i + u];
+#pragma unroll
+        for (int g = 0; g < NG; ++g) wv[u][g] = reinterpret_cast<const float4*>(wrow + (i + u) * nj)[g];
+      }
+#pragma unroll
+      for (int u = 0; u < UN; ++u) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+          s[g][0] = fmaf(xv[u], wv[u][g].x, s[g][0]); s[g][1] = fmaf(xv[u], wv[u][g].y, s[g][1]);
+          s[g][2] = fmaf(xv[u], wv[u][g].z, s[g][2]); s[g][3] = fmaf(xv[u], wv[u][g].w, s[g][3]);
+        }
+      }
+    }
+    for (; i < run; ++i) {
+      const float x1 = xp[i];
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const float4 w1v = reinterpret_cast<const float4*>(wrow + i * nj)[g];
+        s[g][0] = fmaf(x1, w1v.x, s[g][0]); s[g][1] = fmaf(x1, w1v.y, s[g][1]);
+        s[g][2] = fmaf(x1, w1v.z, s[g][2]); s[g][3] = fmaf(x1, w1v.w, s[g][3]);
+      }
+    }
+    kk += run;
+    xp += run + (ldr - c);
+    wrow += run * nj;
+    ch = 0;
+  }
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    acc[g][0] += s[g][0]; acc[g][1] += s[g][1]; acc[g][2] += s[g][2]; acc[g][3] += s[g][3];
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void dnn_online_push_kernel(DnnOnlineParams p) {
+  extern __shared__ double lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s = blockIdx.x;
+  const int c = p.c, pre = p.pre, post = p.post, width = p.width, hop = p.hop;
+  const int tl = pre + post, pass = p.pass, ldr = row_stride(c);
+  const DnnNet& t = p.net;
+  const int nl = t.nl, w1 = t.w[1], w1q = t.nj / 4, nj = t.nj, ks = t.ks, lda_s = t.lda, k_all = t.w[0];
+  const int chunk_floats = t.g * ks * nj;
+  double* sc_s = lds;                                        // [2][pass] the pass's per-frame scores
+  double* wm_s = sc_s + 2 * pass;                            // [2][pass] the pass's window means
+  float* ws_s = reinterpret_cast<float*>(wm_s + 2 * pass);   // [2][chunk_floats] chunks of W1 (16-byte aligned)
+  float* sm_s = ws_s + 2 * chunk_floats;                     // [n_small] b1, W2, b2, ...
+  float* rows_s = sm_s + (t.n_small + 3) / 4 * 4;            // [pass + tl][ldr] the pass's EEG rows
+  float* env_s = rows_s + (size_t)(pass + tl) * ldr;         // [max(pass, post)][2]
+  float* pred_s = env_s + 2 * (pass > post ? pass : post);   // [pass]
+  float* act_s = pred_s + pass;                              // [2][pass][lda_s] activations, in turn
+
+  unsigned char* st = p.state + (long long)s * p.state_ss;
+  double* step_p = reinterpret_cast<double*>(st);
+  double* ring = reinterpret_cast<double*>(st + state_ring_offset());             // [2][width]
+  float* tail = reinterpret_cast<float*>(st + state_eeg_offset(width));           // [tl][c]
+  float* etail = reinterpret_cast<float*>(st + state_env_offset(c, pre, post, width));   // [post][2]
+  const float* eeg = p.eeg + (long long)s * p.eeg_ss;
+  const float* env = p.env + (long long)s * p.env_ss;
+  const float* prm = p.params + (long long)s * p.params_ss;
+  const bool vec = (w1 & 3) == 0 && (reinterpret_cast<size_t>(prm) & 15) == 0;
+  const double* cr = p.corr + (long long)s * 6;
+  const double lda_w = p.lda ? p.lda[s * 3LL] : 0.0, lda_slope = p.lda ? p.lda[s * 3LL + 1] : 1.0,
+               lda_icpt = p.lda ? p.lda[s * 3LL + 2] : 0.0;
+  const long long p0 = p.p0, p1 = p.p0 + p.n;
+  const long long emitted_now = p.e1 - p.e0;
+
+  for (int i = tid; i < t.n_small; i += kThreads) sm_s[i] = prm[t.small0 + i];
+  const float* small = sm_s - t.small0;                      // indexed by parameter offset
+  double step = 0.5;
+  if (tid == 0 && p.decoder == 1) {
+    const double stored = *step_p;
+    step = stored == 0.0 ? 0.5 : stored;
+  }
+
+  for (long long a = p.e0; a < p.e1; a += pass) {
+    const int nf = (int)(p.e1 - a < pass ? p.e1 - a : pass);     // frames [a, a + nf) of this pass
+    float4 regs[kLoads];
+    chunk_load(prm, t, 0, vec, tid, regs);
+    // ---- stage the EEG rows a - pre .. a + nf - 1 + post and the envelope rows a .. a + nf - 1: from the
+    // tails (rows before this push), from the push, zeros before the recording and behind a flushed end
+    const int n_rows = nf + tl;
+    for (int rr = wave; rr < n_rows; rr += kWaves) {
+      const long long row = a - pre + rr;
+      for (int ch = lane; ch < c; ch += 64) {
+        float v = 0.f;
+        if (row >= 0 && row < p0) v = tail[(row - (p0 - tl)) * c + ch];
+        else if (row >= p0 && row < p1) v = eeg[(row - p0) * p.eeg_ld + ch];
+        rows_s[rr * ldr + ch] = v;
+      }
+    }
+    for (int i = tid; i < 2 * nf; i += kThreads) {
+      const long long row = a + (i >> 1);
+      env_s[i] = row < p0 ? etail[(row - (p0 - post)) * 2 + (i & 1)] : env[(row - p0) * p.env_ld + (i & 1)];
+    }
+    chunk_store(ws_s, t, 0, tid, regs);
+    __syncthreads();
+    // ---- layer 1: thread = (frame f, column lane cg), frame-fastest; the thread owns the column groups cg,
+    // cg + cl, ... (4 columns each, cl = kThreads / nf lanes), which share the frame's x.  Per slice a chain of
+    // fused multiply-adds from 0.f over the slice's rows, added to the accumulators in slice order.
+    const int cl = kThreads / nf, ng = (w1q + cl - 1) / cl;         // (nf <= 64, w1q <= 16: ng <= kPairs)
+    const int pf = tid % nf, cg = tid / nf;
+    const bool busy = cg < cl && cg * ng < w1q;
+    // the thread's groups are cg ng .. cg ng + ng - 1; it reads the ng ADJACENT groups from jb on (one address and
+    // constant offsets per row of W1), moved back where they would pass the last group: a group in front of its
+    // own repeats a neighbour's sums and is dropped
+    const int jb = busy ? (cg * ng < w1q - ng ? cg * ng : w1q - ng) : 0;
+    bool own[kPairs];
+    float acc[kPairs][4];
+#pragma unroll
+    for (int o = 0; o < kPairs; ++o) {
+      own[o] = busy && o < ng && jb + o >= cg * ng;
+      acc[o][0] = acc[o][1] = acc[o][2] = acc[o][3] = 0.f;
+    }
+    int lag0 = 0, ch0 = 0;                                          // the slice's first row is (lag0, ch0)
+    for (int ci = 0; ci < t.nchunks; ++ci) {
+      if (ci + 1 < t.nchunks) chunk_load(prm, t, ci + 1, vec, tid, regs);
+      const float* buf = ws_s + (ci & 1) * chunk_floats;
+      const int sl_end = (ci + 1) * t.g < t.nslices ? (ci + 1) * t.g : t.nslices;
+      for (int sl = ci * t.g; sl < sl_end; ++sl) {
+        const int kbase = sl * ks;
+        const int ksl = k_all - kbase < ks ? k_all - kbase : ks;
+        if (busy) {
+          const float* xp = rows_s + (pf + lag0) * ldr + ch0;
+          const float* wrow = buf + (size_t)(sl - ci * t.g) * ks * nj + 4 * jb;
+          if (ng == 1) slice_fma<1>(xp, wrow, nj, ksl, ch0, c, ldr, acc);
+          else if (ng == 2) slice_fma<2>(xp, wrow, nj, ksl, ch0, c, ldr, acc);
+          else if (ng == 3) slice_fma<3>(xp, wrow, nj, ksl, ch0, c, ldr, acc);
+          else slice_fma<4>(xp, wrow, nj, ksl, ch0, c, ldr, acc);
+        }
+        ch0 += ksl;
+        while (ch0 >= c) { ch0 -= c; ++lag0; }
+      }
+      if (ci + 1 < t.nchunks) chunk_store(ws_s + ((ci + 1) & 1) * chunk_floats, t, ci + 1, tid, regs);
+      __syncthreads();
+    }
+    // z1 = the partials + b1; ReLU when a layer follows, else (no hidden layer: w1 = 1) the prediction itself
+#pragma unroll
+    for (int o = 0; o < kPairs; ++o) {
+      if (!own[o]) continue;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int j = 4 * (jb + o) + q;
+        if (j >= w1) continue;
+        const float z = acc[o][q] + small[t.off_b[0] + j];
+        if (nl > 1) act_s[pf * lda_s + j] = z <= 0.f ? 0.f : z;
+        else pred_s[pf] = z;
+      }
+    }
+    __syncthreads();
+    // ---- the later layers: (frame, unit) pairs over the workgroup, frame-fastest; the last layer's one unit is
+    // the prediction
+    for (int l = 2; l <= nl; ++l) {
+      const int wi = t.w[l - 1], wo = t.w[l];
+      const float* W = small + t.off_w[l - 1];
+      const float* b = small + t.off_b[l - 1];
+      const float* in = act_s + (size_t)(l & 1) * pass * lda_s;
+      float* outp = act_s + (size_t)((l + 1) & 1) * pass * lda_s;
+      for (int pr = tid; pr < nf * wo; pr += kThreads) {
+        const int o = pr / nf, f = pr - o * nf;
+        const float* xin = in + f * lda_s;
+        float sum = 0.f;
+        for (int i = 0; i < wi; ++i) sum = fmaf(xin[i], W[i * wo + o], sum);
+        sum += b[o];
+        if (l < nl) outp[f * lda_s + o] = sum <= 0.f ? 0.f : sum;
+        else pred_s[f] = sum;
+      }
+      __syncthreads();
+    }
+    // ---- per-frame scores of both speakers
+    for (int i = tid; i < 2 * nf; i += kThreads) {
+      const int spk = i / nf, f = i - spk * nf;
+      const float pr = pred_s[f];
+      const double v = frame_score(env_s[2 * f + spk], pr, cr[3 * spk], cr[3 * spk + 1], cr[3 * spk + 2],
+                                   p.reduction, lda_w, lda_slope, lda_icpt);
+      sc_s[spk * pass + f] = v;
+      const long long at = (long long)s * emitted_now + (a - p.e0) + f;
+      if (p.frame) p.frame[(long long)spk * gridDim.x * emitted_now + at] = v;
+      if (p.pred && spk == 0) p.pred[at] = pr;
+    }
+    __syncthreads();
+    // ---- the windows that end in (a, a + nf] (online.hip: a WAVE forms a window's mean with
+    // window_means_kernel's operations -- lane q stands in for the threads q, q + 64, q + 128, q + 192 of that
+    // kernel's workgroup; frames before `a` come from the ring)
+    const long long end_lo = a + 1 > width ? a + 1 : width;      // the first window end in reach
+    const long long wi_lo = (end_lo - width + hop - 1) / hop;
+    const long long wi_hi = a + nf >= width ? (a + nf - width) / hop + 1 : 0;   // one past the last
+    const int nw = wi_hi > wi_lo ? (int)(wi_hi - wi_lo) : 0;
+    for (int j = wave; j < nw; j += kWaves) {
+      const long long r0 = (wi_lo + j) * hop;
+      const int slot0 = (int)(r0 % width);                       // ring slot of the window's first frame
+#pragma unroll
+      for (int spk = 0; spk < 2; ++spk) {
+        double part[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          double sum = 0.0;
+          for (int r = 64 * q + lane; r < width; r += kThreads) {
+            const long long fr = r0 + r;
+            const int slot = slot0 + r - (slot0 + r >= width ? width : 0);
+            sum += fr >= a ? sc_s[spk * pass + (int)(fr - a)] : ring[(long long)spk * width + slot];
+          }
+          part[q] = wave_sum(sum);
+        }
+        if (lane == 0) {
+          const double m = ((part[0] + part[1]) + (part[2] + part[3])) / (double)width;
+          wm_s[spk * pass + j] = m;
+          p.scores[((long long)spk * gridDim.x + s) * p.n_win + (wi_lo + j - p.w0)] = m;
+        }
+      }
+    }
+    __syncthreads();
+    // ---- decisions (decide_wta_kernel / decide_step_kernel), the ring, then the next pass
+    unsigned char* dec = p.decisions + (long long)s * p.n_win + (wi_lo - p.w0);
+    if (p.decoder == 1) {
+      if (tid == 0) {
+        for (int j = 0; j < nw; ++j) {
+          if (wm_s[j] > wm_s[pass + j]) step = fmin(0.9, step + 0.1);
+          else step = fmax(0.1, step - 0.1);
+          dec[j] = step > 0.5 ? 1 : 0;
+        }
+      }
+    } else {
+      for (int j = tid; j < nw; j += kThreads)
+        dec[j] = p.decoder == 0 ? (wm_s[j] > wm_s[pass + j] ? 1 : 0) : 0;
+    }
+    // (a pass longer than the ring: only its last `width` frames, one per slot)
+    const int slot_a = (int)(a % width);
+    for (int i = tid; i < 2 * nf; i += kThreads) {
+      const int spk = i / nf, f = i - spk * nf;
+      if (nf - f <= width) ring[(long long)spk * width + (slot_a + f) % width] = sc_s[spk * pass + f];
+    }
+    __threadfence_block();
+    __syncthreads();
+  }
+
+  // ---- the tails for the next push: the last pre + post EEG rows and the last post envelope rows of
+  // (old tail, this push).  A push shorter than a tail shifts it: the rows that stay go through LDS.
+  __syncthreads();
+  const long long n = p.n;
+  const int keep = n < tl ? (int)(tl - n) : 0;                   // old EEG rows that stay
+  for (int i = tid; i < keep * c; i += kThreads) rows_s[i] = tail[(tl - keep) * c + i];
+  const int ekeep = n < post ? (int)(post - n) : 0;
+  for (int i = tid; i < ekeep * 2; i += kThreads) env_s[i] = etail[(post - ekeep) * 2 + i];
+  __syncthreads();
+  for (int rr = wave; rr < tl; rr += kWaves)
+    for (int ch = lane; ch < c; ch += 64)
+      tail[rr * c + ch] = rr < keep ? rows_s[rr * c + ch] : eeg[(n - (tl - rr)) * p.eeg_ld + ch];
+  for (int i = tid; i < post * 2; i += kThreads) {
+    const int rr = i >> 1;
+    etail[i] = rr < ekeep ? env_s[i] : env[(n - (post - rr)) * p.env_ld + (i & 1)];
+  }
+  if (tid == 0 && p.decoder == 1) *step_p = step;
+}
+
+// The shape checks td_fc_online_lds_bytes and td_fc_online_push share: the intersection of td_online_push's
+// limits and td_mlp_forward's.
+int check_shape(td_handle* h, const char* who, int c, int pre, int post, int num_hidden, const int* hidden) {
+  TD_REQUIRE(h, c >= 1 && c <= kMaxChannels, "%s: %d channels (1 .. %d)", who, c, kMaxChannels);
+  TD_REQUIRE(h, pre >= 0 && post >= 0 && pre + 1 + post <= kMaxLags,
+             "%s: context of %d + 1 + %d frames (at most %d lags)", who, pre, post, kMaxLags);
+  TD_REQUIRE(h, (long long)c * (pre + 1 + post) <= kMaxK, "%s: %d lagged inputs (at most %d)", who,
+             c * (pre + 1 + post), kMaxK);
+  TD_REQUIRE(h, num_hidden >= 0 && num_hidden <= kMaxHidden, "%s: %d hidden layers (at most %d)", who, num_hidden,
+             kMaxHidden);
+  TD_REQUIRE(h, num_hidden == 0 || hidden, "%s: NULL hidden widths", who);
+  for (int i = 0; i < num_hidden; ++i)
+    TD_REQUIRE(h, hidden[i] >= 1 && hidden[i] <= kMaxWidth, "%s: hidden layer of %d units (1 .. %d)", who, hidden[i],
+               kMaxWidth);
+  const DnnNet t = net_of(c, pre, post, hidden, num_hidden);
+  const long long need = lds_bytes(t, c, pre, post, 1);
+  TD_REQUIRE(h, need <= kLdsBudget,
+             "%s: two chunks of W1, the small layers' %d parameters and a pass of one frame of %d x %d lags take %lld "
+             "bytes of LDS (budget %lld bytes)", who, t.n_small, c, pre + 1 + post, need, kLdsBudget);
+  return TD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int td_fc_online_lds_bytes(int c, int pre, int post, int num_hidden, const int* hidden_host, int64_t emitted,
+                            int* pass, int64_t* bytes) {
+  if (!pass || !bytes) return td_fail(nullptr, TD_ERR_INVALID, "td_fc_online_lds_bytes: NULL argument");
+  TD_TRY(check_shape(nullptr, "td_fc_online_lds_bytes", c, pre, post, num_hidden, hidden_host));
+  TD_REQUIRE(nullptr, emitted >= 0, "td_fc_online_lds_bytes: %lld frames", (long long)emitted);
+  const DnnNet t = net_of(c, pre, post, hidden_host, num_hidden);
+  *pass = pass_of(t, c, pre, post, emitted);
+  *bytes = lds_bytes(t, c, pre, post, *pass);
+  return TD_OK;
+}
+
+int td_fc_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t eeg_ld,
+                       int64_t eeg_session_stride, const float* env_dev, int64_t env_ld,
+                       int64_t env_session_stride, int64_t n, int c, int pre, int post, const int* hidden_host,
+                       int num_hidden, const float* params_dev, int64_t params_session_stride,
+                       const double* corr_dev, int reduction, const double* lda_dev, int width, int hop,
+                       int decoder, int64_t frames_before, int flush, void* state_dev,
+                       int64_t state_session_stride, double* scores_dev, uint8_t* decisions_dev, float* pred_dev,
+                       double* frame_dev) {
+  if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_fc_online_push: handle is NULL");
+  TD_REQUIRE(h, num_sessions >= 1, "td_fc_online_push: %d sessions", num_sessions);
+  TD_TRY(check_shape(h, "td_fc_online_push", c, pre, post, num_hidden, hidden_host));
+  TD_REQUIRE(h, n >= 0 && n <= TD_ONLINE_MAX_PUSH, "td_fc_online_push: %lld frames in one push (0 .. %d)",
+             (long long)n, TD_ONLINE_MAX_PUSH);
+  TD_REQUIRE(h, width >= 1 && width <= TD_ONLINE_MAX_WIDTH, "td_fc_online_push: window of %d frames (1 .. %d)",
+             width, TD_ONLINE_MAX_WIDTH);
+  TD_REQUIRE(h, hop >= 1, "td_fc_online_push: window step of %d frames", hop);
+  TD_REQUIRE(h, reduction == 0 || reduction == 2 || reduction == 3 || reduction == 4,
+             "td_fc_online_push: reduction %d (0 first, 2 mean, 3 mean-squared, 4 lda)", reduction);
+  TD_REQUIRE(h, reduction != 4 || lda_dev, "td_fc_online_push: the lda reduction needs lda_dev");
+  TD_REQUIRE(h, decoder >= 0 && decoder <= 2,
+             "td_fc_online_push: decoder %d (0 winner-take-all, 1 stepped, 2 none)", decoder);
+  TD_REQUIRE(h, frames_before >= 0, "td_fc_online_push: %lld frames before", (long long)frames_before);
+  if (!params_dev || !corr_dev || !state_dev || !scores_dev || !decisions_dev || (n > 0 && (!eeg_dev || !env_dev)))
+    return td_fail(h, TD_ERR_INVALID, "td_fc_online_push: NULL argument");
+  TD_REQUIRE(h, eeg_ld >= c && env_ld >= 2,
+             "td_fc_online_push: a row stride below a row (%lld for %d channels, %lld for 2 envelopes)",
+             (long long)eeg_ld, c, (long long)env_ld);
+  TD_REQUIRE(h, num_sessions == 1 || (eeg_session_stride >= c && env_session_stride >= 2),
+             "td_fc_online_push: a session stride below a row");
+  const DnnNet t = net_of(c, pre, post, hidden_host, num_hidden);
+  TD_REQUIRE(h, params_session_stride == 0 || params_session_stride >= t.n_params,
+             "td_fc_online_push: a parameter stride of %lld for %d parameters (0 = one model)",
+             (long long)params_session_stride, t.n_params);
+  const long long sbytes = state_bytes(c, pre, post, width);
+  TD_REQUIRE(h, state_session_stride >= sbytes && state_session_stride % 8 == 0,
+             "td_fc_online_push: a state stride of %lld bytes (a multiple of 8, at least %lld)",
+             (long long)state_session_stride, sbytes);
+  if (n == 0 && !flush) return TD_OK;
+  // (online.hip's plan_push = td_online_plan)
+  int64_t e0 = 0, e1 = 0, w0 = 0, n_win = 0;
+  TD_TRY(td_online_plan(frames_before, n, post, width, hop, flush, &e0, &e1, &w0, &n_win));
+  DnnOnlineParams p;
+  p.eeg = eeg_dev; p.eeg_ld = eeg_ld; p.eeg_ss = num_sessions > 1 ? eeg_session_stride : 0;
+  p.env = env_dev; p.env_ld = env_ld; p.env_ss = num_sessions > 1 ? env_session_stride : 0;
+  p.params = params_dev; p.params_ss = params_session_stride;
+  p.corr = corr_dev; p.lda = reduction == 4 ? lda_dev : nullptr;
+  p.n = n; p.p0 = frames_before; p.e0 = e0; p.e1 = e1; p.w0 = w0; p.n_win = n_win;
+  p.c = c; p.pre = pre; p.post = post; p.reduction = reduction; p.width = width; p.hop = hop; p.decoder = decoder;
+  p.pass = pass_of(t, c, pre, post, e1 - e0);     // (>= 1: check_shape)
+  p.net = t;
+  p.state = reinterpret_cast<unsigned char*>(state_dev); p.state_ss = state_session_stride;
+  p.scores = scores_dev; p.decisions = decisions_dev; p.pred = pred_dev; p.frame = frame_dev;
+  if (!h->lds_opt_online_dnn) {
+    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&dnn_online_push_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
+    h->lds_opt_online_dnn = true;
+  }
+  TD_TRY(td_profile_mark(h, true, (double)n * num_sessions));
+  hipLaunchKernelGGL(dnn_online_push_kernel, dim3((unsigned)num_sessions), dim3(kThreads),
+                     (size_t)lds_bytes(t, c, pre, post, p.pass), h->stream, p);
+  TD_HIP(h, hipGetLastError());
+  TD_TRY(td_profile_mark(h, false, 0.0));
+  return TD_OK;
+}
+
+}  // extern "C"

@@ -1135,6 +1135,100 @@ def cca_online_push(eeg, feat1, feat2, mean_x, rot_x, mean_y, rot_y, corr, state
                        frame[:-1].reshape(2, sessions, emitted) if want_frames else None, plan)
 
 
+DNN_ONLINE_MAX_HIDDEN, DNN_ONLINE_MAX_UNITS, DNN_ONLINE_MAX_INPUTS = 4, 64, 8192     # td_mlp_*'s limits
+DNN_ONLINE_LDS_BYTES = 163840                                                         # TD_FC_ONLINE_LDS_BYTES
+
+
+def dnn_param_count(k, hidden):
+  """Parameters of the packed buffer [W1, b1, W2, b2, ...] of a regressor with k inputs and one output."""
+  widths = [int(k)] + [int(v) for v in hidden] + [1]
+  return sum(widths[i] * widths[i + 1] + widths[i + 1] for i in range(len(widths) - 1))
+
+
+def dnn_online_lds_bytes(c, pre, post, hidden, emitted=64):
+  """(frames per pass, LDS bytes) of a td_fc_online_push launch that emits `emitted` frames
+  (td_fc_online_lds_bytes); ValueError for a shape outside the limits or over the byte budget."""
+  hid = np.ascontiguousarray(list(hidden) or [0], dtype=np.int32)
+  p, n = ctypes.c_int(0), ctypes.c_int64(0)
+  _lib.check(None, _lib.load().td_fc_online_lds_bytes(int(c), int(pre), int(post), len(hidden),
+                                                       hid.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                       int(emitted), ctypes.byref(p), ctypes.byref(n)))
+  return int(p.value), int(n.value)
+
+
+def dnn_online_push(eeg, env, params, hidden, corr, state, frames_before, pre, post, width, hop, reduction='first',
+                    lda=None, decoder='wta', flush=False, want_frames=False, handle=None):
+  """One push of a bank of online decoding sessions around fully connected regressors, in one launch
+  (td_fc_online_push).
+
+  eeg, env, corr, lda, state, frames_before, width, hop, reduction, decoder, flush: as online_push.  params [S or 1,
+  P] float32: the packed parameters of td_mlp_* ([W1, b1, W2, b2, ...], one output) of a network with the hidden
+  layers `hidden` on c (pre + 1 + post) inputs; one row: the model every session shares.  Returns
+  OnlinePush(scores [2, S, new] float64, decisions [S, new] uint8, pred [S, emitted] float32 -- mlp_forward's bits
+  -- and frame [2, S, emitted] float64 (None without want_frames), plan).  Queued, not waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  if reduction not in ONLINE_REDUCTIONS:
+    raise ValueError('dnn_online_push: reduction %r (one of %s)' % (reduction, ', '.join(ONLINE_REDUCTIONS)))
+  if decoder not in SWEEP_DECODERS:
+    raise ValueError('dnn_online_push: unknown decoder %r' % (decoder,))
+  hidden = [int(v) for v in hidden]
+  sessions = int(state.shape[0])
+  nl = int(pre) + 1 + int(post)
+  if params.dim() != 2 or int(params.shape[0]) not in (1, sessions):
+    raise ValueError('dnn_online_push: params of %s for %d sessions ([S or 1, P])' % (tuple(params.shape), sessions))
+  # P = k h1 + the rest: k from the parameter count
+  first = hidden[0] if hidden else 1
+  rest = dnn_param_count(0, hidden)
+  count = int(params.shape[1])
+  k = (count - rest) // first if first > 0 else 0
+  if nl < 1 or k < 1 or k % nl or dnn_param_count(k, hidden) != count:
+    raise ValueError('dnn_online_push: %d parameters for hidden layers %s on %d lags' % (count, hidden, nl))
+  c = k // nl
+  n = 0 if eeg is None else int(eeg.shape[1])
+  if eeg is not None and (tuple(eeg.shape) != (sessions, n, c) or env is None or
+                          tuple(env.shape) != (sessions, n, 2)):
+    raise ValueError('dnn_online_push: eeg of %s and env of %s for %d sessions of %d channels' %
+                     (tuple(eeg.shape), None if env is None else tuple(env.shape), sessions, c))
+  for name, t, dtype in (('eeg', eeg, torch.float32), ('env', env, torch.float32), ('params', params, torch.float32),
+                         ('corr', corr, torch.float64), ('lda', lda, torch.float64), ('state', state, torch.uint8)):
+    if t is not None and (t.dtype != dtype or t.device != h.device):
+      raise TypeError('dnn_online_push: %s must be a %s tensor on %s, not %s on %s' %
+                      (name, dtype, h.device, t.dtype, t.device))
+  if n > 0 and (eeg.stride(2) != 1 and c > 1 or env.stride(2) != 1):
+    raise ValueError('dnn_online_push: the columns of eeg and env must be contiguous')
+  if tuple(corr.shape) != (sessions, 2, 3) or (lda is not None and tuple(lda.shape) != (sessions, 3)):
+    raise ValueError('dnn_online_push: corr must be [%d, 2, 3] and lda [%d, 3]' % (sessions, sessions))
+  if params.stride(1) != 1 and count > 1:
+    params = params.contiguous()
+  corr = corr.contiguous()
+  lda = lda.contiguous() if lda is not None else None
+  shared = int(params.shape[0]) == 1
+  hid, hid_p = _i32_array(hidden or [0])
+  plan = online_plan(frames_before, n, post, width, hop, flush)
+  emitted = plan.emitted_after - plan.emitted_before
+  # (every element a push emits is written; an empty tensor has no address: one spare element)
+  scores = h.empty((2 * sessions * plan.new_windows + 1,), 'float64')
+  decisions = h.empty((sessions * plan.new_windows + 1,), 'uint8')
+  pred = h.empty((sessions * emitted + 1,), 'float32') if want_frames else None
+  frame = h.empty((2 * sessions * emitted + 1,), 'float64') if want_frames else None
+  live = n > 0
+  h.check(h.lib.td_fc_online_push(
+      h.ptr, sessions,
+      _ptr(eeg if live else None), int(eeg.stride(1)) if live and n > 1 else c,
+      int(eeg.stride(0)) if live and sessions > 1 else max(n, 1) * c,
+      _ptr(env if live else None), int(env.stride(1)) if live and n > 1 else 2,
+      int(env.stride(0)) if live and sessions > 1 else max(n, 1) * 2,
+      n, c, int(pre), int(post), hid_p, len(hidden), _ptr(params), 0 if shared else int(params.stride(0)),
+      _ptr(corr), REDUCTIONS[reduction], _ptr(lda), int(width), int(hop), SWEEP_DECODERS[decoder],
+      int(frames_before), 1 if flush else 0, _ptr(state), int(state.stride(0)) if sessions > 1 else int(state.shape[1]),
+      _ptr(scores), _ptr(decisions), _ptr(pred), _ptr(frame)))
+  return OnlinePush(scores[:-1].reshape(2, sessions, plan.new_windows),
+                    decisions[:-1].reshape(sessions, plan.new_windows),
+                    pred[:-1].reshape(sessions, emitted) if want_frames else None,
+                    frame[:-1].reshape(2, sessions, emitted) if want_frames else None, plan)
+
+
 def sos_filter(x, file_offsets, sos, zi, stage_split, state, reset, out_rows=None, out_offsets=None, handle=None):
   """The SOS cascade over x [N, C] (float32 / float64 device tensor), files concatenated along time:
   float64 output [N, C], or only the file-local rows out_rows (device int64, file f's at

@@ -29,6 +29,13 @@ features per speaker, `online.push(eeg, feat1, feat2)`, and is ONE td_cca_online
 centred and rotated once per frame, each speaker's view against it over the model's dims, then the same
 windows and decisions.
 
+So does the fully connected regressor: a `LinearRegressionDecoder` around a `brain_model.BrainModelDNN` (or the
+model directory `decoding.py --dnn_regressor fullyconnected --saved_model_dir` wrote) gives a session whose push
+is ONE td_fc_online_push launch -- the network on every emitted frame's lagged EEG, with the bits of
+`device.mlp_forward` on the whole recording, then the same scores, windows and decisions.  A DNN knows its input
+width but not its context: it comes from the decoder's decoding_model_params, else from the model's
+add_metadata entry, else from the keyword arguments pre_context= / post_context=.
+
 Without a GPU (`device.gpu_available()` false) the same object runs a NumPy session with the same
 semantics -- float64 throughout, window sums in frame order, td_online_plan's arithmetic -- so that the logic can
 be built and tested anywhere.  (The state-space decoder has no host form: 'ssd' needs the GPU.)
@@ -54,20 +61,22 @@ OnlineResult = collections.namedtuple('OnlineResult', ['scores', 'decisions', 'f
 def session_parameters(decoder, **context):
   """What one listener's session needs from its decoder, checked against the online path's limits.  A
   LinearRegressionDecoder gives dict(kind='linear', c, pre, post, w [lags c] float32, b float32, corr [2, 3]
-  float64, lda [3] float64 or None, reduction); a CCADecoder what cca_session_parameters says (`context`: its
-  keyword arguments)."""
+  float64, lda [3] float64 or None, reduction); around a BrainModelDNN what dnn_session_parameters says; a
+  CCADecoder what cca_session_parameters says (`context`: their keyword arguments)."""
   if isinstance(decoder, infer_decoder.CCADecoder):
     return cca_session_parameters(decoder, **context)
   if not isinstance(decoder, infer_decoder.LinearRegressionDecoder):
     raise ValueError('OnlineDecoder decodes with a LinearRegressionDecoder or a CCADecoder, not a %s.' %
                      type(decoder).__name__)
-  if context:
-    raise TypeError('OnlineDecoder: %s is a CCA model\'s context; a linear model carries its own.' %
-                    ', '.join(sorted(context)))
   model = decoder.decoding_model
+  if isinstance(model, brain_model.BrainModelDNN):
+    return dnn_session_parameters(decoder, **context)
+  if context:
+    raise TypeError('OnlineDecoder: %s is a CCA or DNN model\'s context; a linear model carries its own.' %
+                    ', '.join(sorted(context)))
   if not isinstance(model, brain_model.BrainModelLinearRegression):
-    raise ValueError('OnlineDecoder needs a BrainModelLinearRegression behind a LinearRegressionDecoder (no DNN '
-                     'model online), not a %s.' % type(model).__name__)
+    raise ValueError('OnlineDecoder needs a BrainModelLinearRegression or a BrainModelDNN behind a '
+                     'LinearRegressionDecoder, not a %s.' % type(model).__name__)
   if model.w_estimate is None:
     raise ValueError('OnlineDecoder needs a fitted model: BrainModelLinearRegression.fit first.')
   w = np.asarray(model.w_estimate, np.float32)
@@ -160,6 +169,70 @@ def cca_session_parameters(decoder, **context):
   return dict(kind='cca', c=c1, pre=pre1, post=post1, c2=c2, pre2=pre2, post2=post2, dims=dims,
               mean_x=mean_x.copy(), rot_x=np.ascontiguousarray(rot_x), mean_y=mean_y.copy(),
               rot_y=np.ascontiguousarray(rot_y), corr=np.stack([stats, stats]), lda=lda, reduction=reduction)
+
+
+DNN_CONTEXT_KEYS = ('pre_context', 'post_context')
+
+
+def dnn_session_parameters(decoder, **context):
+  """What one listener's session needs from a LinearRegressionDecoder around a brain_model.BrainModelDNN, checked
+  against the limits of td_fc_online_push: dict(kind='dnn', c, pre, post, hidden (list), weights [W1, b1, W2, b2,
+  ...] float32, params (the same, packed as td_mlp_* reads them), corr [2, 3] float64, lda [3] float64 or None,
+  reduction).  A DNN model knows its input width, not its context: pre_context, post_context (and input_offset,
+  which must be 0) come from the decoder's decoding_model_params, else from the model's add_metadata entry, else
+  from the keyword arguments pre_context= / post_context=."""
+  model = decoder.decoding_model
+  unknown = sorted(set(context) - set(DNN_CONTEXT_KEYS))
+  if unknown:
+    raise TypeError('OnlineDecoder: unknown context argument %s (the context of a DNN model is %s).' %
+                    (', '.join(unknown), ', '.join(DNN_CONTEXT_KEYS)))
+  carried = decoder.decoding_model_params or getattr(model, 'telluride_metadata', None) or {}
+  if not isinstance(carried, dict) or not all(k in carried for k in DNN_CONTEXT_KEYS):
+    if not all(k in context for k in DNN_CONTEXT_KEYS):
+      raise ValueError('A DNN model does not carry its context: give OnlineDecoder pre_context= and post_context= '
+                       '(or a decoder whose decoding_model_params, or a model whose add_metadata entry, holds '
+                       'them).')
+    carried = {k: context[k] for k in DNN_CONTEXT_KEYS}
+  if int(carried.get('input_offset', 0) or 0) != 0:
+    raise ValueError('OnlineDecoder decodes with an input_offset of 0, not %s.' % (carried['input_offset'],))
+  pre, post = (int(carried[k]) for k in DNN_CONTEXT_KEYS)
+  if pre < 0 or post < 0 or pre + 1 + post > MAX_LAGS:
+    raise ValueError('OnlineDecoder takes at most %d lags, not %d + 1 + %d.' % (MAX_LAGS, pre, post))
+  weights = [np.asarray(w, np.float32) for w in model.get_weights()]
+  hidden = [int(u) for u in model.num_hidden_list]
+  k, outputs = int(weights[0].shape[0]), int(weights[-1].shape[0])
+  if outputs != 1:
+    raise ValueError('OnlineDecoder decodes one model output, not %d.' % outputs)
+  if k % (pre + 1 + post):
+    raise ValueError('The DNN model has %d inputs: no multiple of the %d + 1 + %d lags of its context.' %
+                     (k, pre, post))
+  c = k // (pre + 1 + post)
+  if not 1 <= c <= MAX_CHANNELS:
+    raise ValueError('OnlineDecoder takes 1 to %d channels, not %d.' % (MAX_CHANNELS, c))
+  if k > device.DNN_ONLINE_MAX_INPUTS:
+    raise ValueError('OnlineDecoder takes at most %d lagged inputs, not %d.' % (device.DNN_ONLINE_MAX_INPUTS, k))
+  if len(hidden) > device.DNN_ONLINE_MAX_HIDDEN:
+    raise ValueError('OnlineDecoder takes at most %d hidden layers, not %d.' %
+                     (device.DNN_ONLINE_MAX_HIDDEN, len(hidden)))
+  if any(not 1 <= u <= device.DNN_ONLINE_MAX_UNITS for u in hidden):
+    raise ValueError('OnlineDecoder takes hidden layers of 1 to %d units, not %s.' %
+                     (device.DNN_ONLINE_MAX_UNITS, hidden))
+  reduction = decoder._reduction
+  if reduction not in device.ONLINE_REDUCTIONS:
+    raise ValueError('OnlineDecoder reduces one output with %s, not with %r.' %
+                     (', '.join(repr(r) for r in device.ONLINE_REDUCTIONS), reduction))
+  # (two chunks of W1, the small layers and a pass of one frame must fit the workgroup's LDS: the library says so)
+  device.dnn_online_lds_bytes(c, pre, post, hidden, 1)
+  mean_x, mean_y, power = decoder._stat_vectors(1)
+  stats = [float(mean_x[0]), float(mean_y[0]), float(power[0])]
+  lda = None
+  if reduction == 'lda':
+    kw = decoder._reduce_kwargs()
+    lda = np.array([float(np.reshape(kw['lda_w'], -1)[0]), float(kw['lda_slope']), float(kw['lda_intercept'])],
+                   np.float64)
+  return dict(kind='dnn', c=c, pre=pre, post=post, hidden=hidden, weights=weights,
+              params=np.concatenate([w.reshape(-1) for w in weights]).astype(np.float32),
+              corr=np.array([stats, stats], np.float64), lda=lda, reduction=reduction)
 
 
 def _cca_frame_score(a, b, stats, reduction, lda):
@@ -305,6 +378,48 @@ class _HostCcaSession(_HostSession):
     return scores, decisions, np.concatenate([a] + bs, axis=1), frame, pl
 
 
+class _HostDnnSession(_HostSession):
+  """One listener's DNN session in NumPy float64: the semantics of td_fc_online_push.  Only the prediction differs
+  from _HostSession's: Dense layers on the frame's lagged rows, every sum in input order, ReLU between them."""
+
+  def _predict(self, rows, first, emitted):
+    p = self.p
+    c, lags = p['c'], p['pre'] + 1 + p['post']
+    ws = [w.astype(np.float64) for w in p['weights']]
+    act = np.zeros((emitted, ws[0].shape[1]), np.float64)
+    for l in range(lags):                            # (lag, channel) order, whatever the push's length
+      for ch in range(c):
+        act += rows[first + l:first + l + emitted, ch][:, None] * ws[0][l * c + ch][None, :]
+    act = act + ws[1]
+    for layer in range(1, len(ws) // 2):
+      act = np.where(act <= 0.0, 0.0, act)
+      w, b = ws[2 * layer], ws[2 * layer + 1]
+      out = np.zeros((emitted, w.shape[1]), np.float64)
+      for i in range(w.shape[0]):                    # in input order
+        out += act[:, i][:, None] * w[i][None, :]
+      act = out + b
+    return act[:, 0]
+
+  def push(self, eeg, env, frames_before, flush):
+    p = self.p
+    c, pre, post = p['c'], p['pre'], p['post']
+    n = eeg.shape[0]
+    pl = device.online_plan(frames_before, n, post, self.width, self.hop, flush)
+    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c))] if flush else []))
+    envs = np.concatenate([self.env_tail, env])
+    emitted = pl.emitted_after - pl.emitted_before
+    i0 = pl.emitted_before - (frames_before - post)   # (as _HostSession.push)
+    pred = self._predict(rows, i0, emitted)
+    truth = envs[i0:i0 + emitted]
+    frame = np.stack([_frame_score(truth[:, k], pred, p['corr'][k], p['reduction'], p['lda'])
+                      for k in (0, 1)], axis=1).reshape(emitted, 2)
+    scores, decisions = self._windows(frame, pl)
+    both = np.concatenate([self.tail, eeg])
+    self.tail = both[both.shape[0] - (pre + post):]
+    self.env_tail = envs[envs.shape[0] - post:] if post else envs[:0]
+    return scores, decisions, pred, frame, pl
+
+
 class OnlineDecoder(object):
   """A bank of online decoding sessions, one per listener.
 
@@ -324,6 +439,13 @@ class OnlineDecoder(object):
   decoder's decoding_model_params (pre_context, post_context, input2_pre_context, input2_post_context), or
   from keyword arguments of those names when the model carries none; results run max(post_context,
   input2_post_context) frames behind the input.
+
+  Or one LinearRegressionDecoder around a brain_model.BrainModelDNN with one output, or a list of S of them (a
+  bank is all of one kind; a DNN bank shares channels, context, hidden layers and reduction): the push is the
+  linear bank's push(eeg, env1, env2) and ONE td_fc_online_push launch, the prediction that of
+  device.mlp_forward on the whole recording bit for bit.  The context comes from the decoder's
+  decoding_model_params, the model's add_metadata entry, or the keyword arguments pre_context= / post_context=;
+  sessions around bitwise-equal parameters read one copy of them.
   """
 
   def __init__(self, decoders, window_size, window_step=None, decoder_type='wta', frame_rate=100.0,
@@ -338,8 +460,11 @@ class OnlineDecoder(object):
     shape_keys = ('c', 'pre', 'post', 'c2', 'pre2', 'post2', 'dims', 'reduction')
     for p in self._params[1:]:
       if p['kind'] != self.kind:
-        raise ValueError('A bank is all linear or all CCA, not a %s decoder beside a %s one.' %
+        raise ValueError('A bank is all linear or all CCA or all DNN, not a %s decoder beside a %s one.' %
                          (p['kind'], self.kind))
+      if self.kind == 'dnn' and p['hidden'] != first['hidden']:
+        raise ValueError('Every DNN decoder of a bank has the same hidden layers: %s and %s.' %
+                         (first['hidden'], p['hidden']))
       if self.kind == 'cca' and any(p[k] != first[k] for k in shape_keys):
         raise ValueError('Every CCA decoder of a bank has the same channels, features, contexts, dims and '
                          'reduction: %s and %s.' % (tuple(first[k] for k in shape_keys),
@@ -361,6 +486,8 @@ class OnlineDecoder(object):
     self.channels, self.pre, self.post = first['c'], first['pre'], first['post']
     self.reduction = first['reduction']
     self.delay = self.post                      # frames the results run behind the input
+    if self.kind == 'dnn':
+      self.hidden = list(first['hidden'])
     if self.kind == 'cca':
       self.features, self.pre2, self.post2, self.dims = first['c2'], first['pre2'], first['post2'], first['dims']
       self.delay = max(self.post, self.post2)
@@ -405,6 +532,23 @@ class OnlineDecoder(object):
       dev['state'] = torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device)
       dev['ssd_state'] = device.ssd_state(self.sessions, handle=h) if self._ssd is not None else None
       return dev
+    if self.kind == 'dnn':
+      # (sessions around bitwise-equal parameters read one copy; a row starts on a 16-byte boundary)
+      shared = all(np.array_equal(p['params'].view(np.uint32), ps[0]['params'].view(np.uint32)) for p in ps[1:])
+      models = ps[:1] if shared else ps
+      count = int(ps[0]['params'].size)
+      packed = np.zeros((len(models), -(-count // 4) * 4), np.float32)
+      for i, p in enumerate(models):
+        packed[i, :count] = p['params']
+      dev = dict(h=h)
+      dev['params'] = h.to_device(packed)[:, :count]
+      dev['corr'] = h.to_device(np.stack([p['corr'] for p in ps]).reshape(-1, 6), np.float64).reshape(-1, 2, 3)
+      dev['lda'] = (h.to_device(np.stack([p['lda'] for p in ps]), np.float64)
+                    if self.reduction == 'lda' else None)
+      nbytes = device.online_state_bytes(self.channels, self.pre, self.post, self.window_size)
+      dev['state'] = torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device)
+      dev['ssd_state'] = device.ssd_state(self.sessions, handle=h) if self._ssd is not None else None
+      return dev
     # (sessions around ONE model read one copy of it)
     shared = all(np.array_equal(p['w'], ps[0]['w']) and p['b'] == ps[0]['b'] for p in ps[1:])
     models = ps[:1] if shared else ps
@@ -432,7 +576,7 @@ class OnlineDecoder(object):
           self._dev['ssd_state'].zero_()
     else:
       kind = self.decoder_type
-      session = _HostCcaSession if self.kind == 'cca' else _HostSession
+      session = {'cca': _HostCcaSession, 'dnn': _HostDnnSession}.get(self.kind, _HostSession)
       self._host = [session(p, self.window_size, self.window_step, kind) for p in self._params]
 
   def tune(self, r1, r2):
@@ -546,9 +690,14 @@ class OnlineDecoder(object):
           h.to_device(env.reshape(-1, 2)).reshape(env.shape)
     if n == 0:
       eeg = env = None
-    out = device.online_push(eeg, env, d['w'], d['b'], d['corr'], d['state'], self.frames_pushed, self.pre,
-                             self.post, self.window_size, self.window_step, self.reduction, d['lda'], kind,
-                             flush=flush, handle=h)
+    if self.kind == 'dnn':
+      out = device.dnn_online_push(eeg, env, d['params'], self.hidden, d['corr'], d['state'], self.frames_pushed,
+                                   self.pre, self.post, self.window_size, self.window_step, self.reduction,
+                                   d['lda'], kind, flush=flush, handle=h)
+    else:
+      out = device.online_push(eeg, env, d['w'], d['b'], d['corr'], d['state'], self.frames_pushed, self.pre,
+                               self.post, self.window_size, self.window_step, self.reduction, d['lda'], kind,
+                               flush=flush, handle=h)
     self.frames_pushed += n
     return self._finish(out)
 
