@@ -816,10 +816,11 @@ extern "C" int td_shrinkage_moment(td_handle* h, const float* x_dev, int64_t ldx
   const int n_lag = pre + 1 + post;
   const int tile_stride = ((c / 4) | 1) * 4;                 // a multiple of 4 floats, an odd number of granules
   const size_t tile_lds = sizeof(float) * ((size_t)(kSqTile + n_lag - 1) * tile_stride + 2 * kSqTile);
-  const bool tiled = c % 4 == 0 && ldx % 1 == 0 && tile_lds <= 64 * 1024;
+  const bool tiled = c % 4 == 0 && tile_lds <= 64 * 1024;      // (its staging loads pick 16 bytes or 4 by x and ldx)
   const int rows_per_wg = tiled ? kSqTile : kRowsPerWg;
   const int chunks = (int)((batch_rows + rows_per_wg - 1) / rows_per_wg);
-  TD_REQUIRE(h, chunks <= 65535 && (p.k + 255) / 256 <= 65535, "td_shrinkage_moment: grid too large");
+  // grids: y = chunks (the centred squares), x = ceil(K / 256) (running_mean_kernel: K itself has to fit an int)
+  TD_REQUIRE(h, chunks <= 65535 && (long long)c * n_lag <= 2147483647LL - 255, "td_shrinkage_moment: grid too large");
   // workspace: file table | S [n_batches][K] f64 | M [n_batches][K] f32 | partials
   const size_t table_bytes = td_round_up(files.size() * sizeof(ShrinkFile), 256);
   const size_t s_bytes = td_round_up((size_t)p.n_batches * p.k * sizeof(double), 256);
@@ -833,8 +834,8 @@ extern "C" int td_shrinkage_moment(td_handle* h, const float* x_dev, int64_t ldx
   double* s = reinterpret_cast<double*>(base + table_bytes);
   float* m = reinterpret_cast<float*>(base + table_bytes + s_bytes);
   double* partial = reinterpret_cast<double*>(base + table_bytes + s_bytes + m_bytes);
-  hipLaunchKernelGGL(batch_colsum_kernel, dim3(p.n_batches, (p.k + 255) / 256), dim3(256), 0,
-                     h->stream, p, s);
+  // ONE workgroup per minibatch: the pieces of a minibatch that spans files are added by read-modify-write
+  hipLaunchKernelGGL(batch_colsum_kernel, dim3(p.n_batches), dim3(256), 0, h->stream, p, s);
   hipLaunchKernelGGL(running_mean_kernel, dim3((p.k + 255) / 256), dim3(256), 0, h->stream, s,
                      p.n_batches, p.k, p.batch, p.total, m);
   if (tiled) {
