@@ -881,6 +881,92 @@ int td_context_out(td_handle* h, const double* z_dev, int64_t m, int cs, int64_t
                    int64_t state_rows, int pre, int post, double mean, double std_dev, float* out32_dev,
                    double* out64_dev, int64_t ldout, double* state_out_dev);
 
+/* ------------------------------------------------------------------ online front end
+ * The chain above for raw EEG that arrives in chunks of ANY length, in front of td_online_push: `num_sessions`
+ * independent listeners configured by one Preprocessor's parameters, one state block each on the device, advanced
+ * by ONE launch per push (one workgroup per session).  The steps keep their order: high-pass sections, low-pass
+ * sections, nearest-neighbour resample, re-reference by groups, channel selection, (v - mean) / std, float32.
+ * However a recording is cut into pushes, the concatenated output and the final state are those of one push of the
+ * whole recording, bit for bit, and the output has exactly the rows of Preprocessor.process(whole, reset=True).
+ * (The td_online_*, td_cca_online_* and td_fc_online_* families are checked as closed sets: this one has its own.)
+ *
+ * The filter is scipy's sosfilt recurrence (direct form II transposed, a0 = 1) in float64, strictly sequential in
+ * time per (session, channel) -- no chunk scan, so the cut cannot matter -- with every fused multiply-add written
+ * out (contraction is off in that file, the compiler chooses nothing).  Per section, in section order:
+ *     y  = fma(b0, x, z0)
+ *     z0 = fma(-a1, y, fma(b1, x, z1))
+ *     z1 = fma(-a2, y, b2 * x)
+ *     x  = y
+ * Reset (rows_before == 0): sections [0, stage_split) start from x[0] * zi; sections [stage_split, S) from y0 * zi,
+ * y0 being the output the first stage's step itself produces on row 0 (the reference's lowpass_filter_reset on the
+ * high-pass output).  Either stage may be absent; num_sections == 0 is no filter.
+ *
+ * The resample over any cut.  Output frame j reads input row r_j = rint((j * (1.0 / fs_out)) * fs_in) and, with
+ * F(N) = rint(N / fs_in * fs_out), is emitted by the first push after which both r_j <= N - 1 and j < F(N) hold
+ * (N rows pushed so far); a flush then emits the frames j < F(N) not yet emitted at row min(N - 1, r_j).  These are
+ * the reference's float64 products in its order (preprocess.resample_indices), so the rows over any cut are those
+ * of resample_indices(N, fs_in, fs_out).  At most one frame is ever held back (only when downsampling: its row was
+ * pushed, F does not count it yet); only upsampling clamps at a flush.  fs_in == fs_out: every row is a frame.  The
+ * kernel computes r_j itself from (first frame, count): no index array is uploaded.
+ *
+ * Behind the resample it is td_reref_select and td_context_out (pre = post = 0) operation for operation: a group's
+ * mean is the sequential float64 sum over its reference channels in list order divided by their count, the
+ * subtractions go in group order from the values before any group was subtracted (a channel listed twice in ONE
+ * group is subtracted once), then the selection, (v - mean) / std and a (float) cast.  None of these can
+ * contract: with no filter the output is Preprocessor.process's byte for byte.
+ *
+ * td_frontend_state_bytes: one session's state block, 8 (2 num_sections + 2) c bytes: the filter state
+ * [num_sections][2][c] float64 in scipy's zi layout (Preprocessor.filter_state's), then the held row [c] (the
+ * filtered row of the last frame whose row has been pushed: the one a held frame waits with) and the last filtered
+ * row [c].  All zeros = fresh.  Data only: the HOST counts the rows (rows_before) and
+ * is authoritative.
+ *
+ * td_frontend_plan (host only): what a push of n rows behind rows_before pushed ones emits.
+ *   frames_before / frames_after   frames emitted before / after the push (flush != 0: F(rows_before + n))
+ *   held   frames whose row has been pushed but that are not emitted after the push (0 or 1; after a flush: dropped)
+ *
+ * td_frontend_lds_bytes: the LDS of a launch over c channels and num_groups groups that emits `emitted` frames,
+ * and the frames per pass:  bytes(pass) = 8 pass (c + num_groups)  (a tile [pass][c] of filtered rows and the
+ * pass's group means, float64);  pass = min(64, max(emitted, 1)), halved (rounding up) while bytes(pass) exceeds
+ * TD_FRONTEND_LDS_BYTES.
+ *
+ * td_frontend_push: the sessions' next n raw rows.
+ *   x_dev     [S][n][c] float32 (float64 when x_is_f64), row stride ldx, session stride x_session_stride (elements)
+ *   n >= 0    (n == 0 and flush == 0: nothing is queued; so is a flush that has no row to add and no frame to emit)
+ *   sos_host  [num_sections][6], zi_host [num_sections][2], stage_split: as td_sos_filter (NULL with no section);
+ *             they travel to the kernel by value
+ *   fs_in, fs_out  > 0
+ *   num_groups (0 .. TD_FRONTEND_MAX_GROUPS), ref_ptr_host, ref_idx_host, chan_ptr_host, chan_idx_host, sel_host
+ *             (NULL: channel j), cs: as td_reref_select; the tables go to the device through the handle's
+ *             content-addressed table cache, so a steady push uploads nothing
+ *   mean_dev, std_dev  float64, one per session stat_session_stride elements apart (0 = shared by all sessions)
+ *   rows_before  rows pushed so far (0 = the filter resets on this push's first row)
+ *   flush     the end of the recording; the state is then good for nothing but td_memset
+ *   state_dev, state_session_stride (BYTES, a multiple of 8, >= td_frontend_state_bytes)
+ *   out32_dev / out64_dev  [S][frames_after - frames_before][cs] float32 / float64 (either may be NULL, not both),
+ *             row stride ldout, session stride out_session_stride (elements)
+ * No atomics, vector stores only: two runs give the same bits.  TD_ERR_INVALID, before anything is queued and with
+ * the state untouched: a NULL required pointer, num_sessions < 1, c or cs outside 1..128, num_sections outside
+ * 0..16, a section with a0 != 1, stage_split outside 0..num_sections, a rate that is not positive and finite, n or
+ * the emitted count outside 0..TD_ONLINE_MAX_PUSH, rows_before < 0, num_groups outside 0..TD_FRONTEND_MAX_GROUPS,
+ * a group without reference channels, a selected or group channel outside the row, ldx < c, ldout < cs, a session
+ * stride of x or the outputs below one row (more than one session), a negative stat stride, a state stride below
+ * the state block or not a multiple of 8.  With td_profile_enable the launch is bracketed as td_online_push's is. */
+#define TD_FRONTEND_MAX_GROUPS 32
+#define TD_FRONTEND_LDS_BYTES 49152
+int td_frontend_state_bytes(int c, int num_sections, int64_t* bytes);
+int td_frontend_plan(int64_t rows_before, int64_t n, double fs_in, double fs_out, int flush,
+                     int64_t* frames_before, int64_t* frames_after, int64_t* held);
+int td_frontend_lds_bytes(int c, int num_groups, int64_t emitted, int* pass, int64_t* bytes);
+int td_frontend_push(td_handle* h, int num_sessions, const void* x_dev, int x_is_f64, int64_t ldx,
+                     int64_t x_session_stride, int64_t n, int c, const double* sos_host, int num_sections,
+                     int stage_split, const double* zi_host, double fs_in, double fs_out, int num_groups,
+                     const int* ref_ptr_host, const int* ref_idx_host, const int* chan_ptr_host,
+                     const int* chan_idx_host, const int* sel_host, int cs, const double* mean_dev,
+                     const double* std_dev, int64_t stat_session_stride, int64_t rows_before, int flush,
+                     void* state_dev, int64_t state_session_stride, float* out32_dev, double* out64_dev,
+                     int64_t ldout, int64_t out_session_stride);
+
 /* ------------------------------------------------------------------ audio features
  * preprocess.AudioFeatures (preprocess.py:589-755): the intensity envelope and the auditory spectrogram.
  *

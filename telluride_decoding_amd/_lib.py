@@ -173,6 +173,14 @@ SIGNATURES = {
                         _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i), _i, _vp, _i64],
     'td_mean_f64': [_vp, _vp, _i64, _i, _i64, _vp],
     'td_context_out': [_vp, _vp, _i64, _i, _i64, _vp, _i64, _i, _i, _d, _d, _vp, _vp, _i64, _vp],
+    'td_frontend_state_bytes': [_i, _i, _pi64],
+    'td_frontend_plan': [_i64, _i64, _d, _d, _i, _pi64, _pi64, _pi64],
+    'td_frontend_lds_bytes': [_i, _i, _i64, _c.POINTER(_i), _pi64],
+    # h, sessions | x, is_f64, ld, stride | n, c | sos, sections, split, zi | fs_in, fs_out | groups, ref_ptr, ref_idx,
+    # chan_ptr, chan_idx | sel, cs | mean, std, stride | rows_before, flush | state, stride | out32, out64, ld, stride
+    'td_frontend_push': [_vp, _i] + [_vp, _i, _i64, _i64] + [_i64, _i] + [_pd, _i, _i, _pd] + [_d, _d] +
+                        [_i] + [_c.POINTER(_i)] * 4 + [_c.POINTER(_i), _i] + [_vp, _vp, _i64] + [_i64, _i] +
+                        [_vp, _i64] + [_vp, _vp, _i64, _i64],
     'td_audio_intensity': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _d, _d, _d, _i, _d, _vp, _vp],
     'td_audio_passthrough': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _i64, _i, _d, _vp, _vp],
     'td_audio_spectrogram': [_vp, _vp, _i64, _i, _i, _i, _pd, _i, _i64, _vp],

@@ -1659,6 +1659,103 @@ def context_out(z, state, pre, post, mean, std, dtype='float32', handle=None):
   return out, new_state
 
 
+# ---------------------------------------------------------------- online front end
+FRONTEND_MAX_CHANNELS, FRONTEND_MAX_SECTIONS, FRONTEND_MAX_GROUPS = 128, 16, 32    # td_frontend_push's limits
+FRONTEND_LDS_BYTES = 49152                                                          # TD_FRONTEND_LDS_BYTES
+
+FrontendPlan = collections.namedtuple('FrontendPlan', ['frames_before', 'frames_after', 'held'])
+FrontendPush = collections.namedtuple('FrontendPush', ['out32', 'out64', 'plan'])
+
+
+def frontend_state_bytes(c, num_sections):
+  """Bytes of one front-end session's state block (td_frontend_state_bytes): the filter state [sections, 2, c], the
+  held row and the last row, float64; all zeros = a fresh session."""
+  n = ctypes.c_int64(0)
+  _lib.check(None, _lib.load().td_frontend_state_bytes(int(c), int(num_sections), ctypes.byref(n)))
+  return int(n.value)
+
+
+def frontend_plan(rows_before, n, fs_in, fs_out, flush=False):
+  """What a push of n raw rows behind `rows_before` pushed ones emits (td_frontend_plan, host arithmetic in the
+  reference's float64 order): FrontendPlan(frames_before, frames_after, held)."""
+  out = [ctypes.c_int64(0) for _ in range(3)]
+  _lib.check(None, _lib.load().td_frontend_plan(int(rows_before), int(n), float(fs_in), float(fs_out),
+                                                1 if flush else 0, *[ctypes.byref(v) for v in out]))
+  return FrontendPlan(*[int(v.value) for v in out])
+
+
+def frontend_lds_bytes(c, num_groups, emitted=64):
+  """(frames per pass, LDS bytes) of a td_frontend_push launch that emits `emitted` frames (td_frontend_lds_bytes)."""
+  p, n = ctypes.c_int(0), ctypes.c_int64(0)
+  _lib.check(None, _lib.load().td_frontend_lds_bytes(int(c), int(num_groups), int(emitted), ctypes.byref(p),
+                                                     ctypes.byref(n)))
+  return int(p.value), int(n.value)
+
+
+def frontend_push(x, sos, stage_split, zi, fs_in, fs_out, groups, select, mean, std, state, rows_before, c=None,
+                  flush=False, want32=True, want64=False, handle=None):
+  """One push of a bank of online front-end sessions, in one launch (td_frontend_push).
+
+  x [S, n, c]: float32 or float64 device tensor with unit column stride (None for a flush without rows: give c);
+  sos [sections, 6] and zi [sections, 2] host float64 (None: no filter), stage_split as sos_filter's; groups
+  [(reference channels, channels to re-reference)] and select (None: every channel) as reref_select's; mean and
+  std float64 device tensors of S values or of one that every session shares; state: uint8 device tensor
+  [S, >= frontend_state_bytes()] with a row stride that is a multiple of 8, updated in place; rows_before: raw rows
+  pushed so far (0: the filter resets).  Returns FrontendPush(out32 [S, m, cs] float32, out64 [S, m, cs] float64
+  (None when not wanted), plan).  Queued, not waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  sessions = int(state.shape[0])
+  n = 0 if x is None else int(x.shape[1])
+  if x is not None:
+    c = int(x.shape[2])
+    if x.dim() != 3 or int(x.shape[0]) != sessions:
+      raise ValueError('frontend_push: x of %s for %d sessions' % (tuple(x.shape), sessions))
+    if x.dtype not in (torch.float32, torch.float64) or x.device != h.device:
+      raise TypeError('frontend_push: x must be a float32 or float64 tensor on %s, not %s on %s' %
+                      (h.device, x.dtype, x.device))
+    if n > 0 and c > 1 and x.stride(2) != 1:
+      raise ValueError('frontend_push: the columns of x must be contiguous')
+  if c is None:
+    raise ValueError('frontend_push: a flush without rows needs the channel count c')
+  for name, t, dtype in (('mean', mean, torch.float64), ('std', std, torch.float64), ('state', state, torch.uint8)):
+    if t.dtype != dtype or t.device != h.device:
+      raise TypeError('frontend_push: %s must be a %s tensor on %s, not %s on %s' %
+                      (name, dtype, h.device, t.dtype, t.device))
+  mean, std = mean.reshape(-1).contiguous(), std.reshape(-1).contiguous()
+  if int(mean.numel()) not in (1, sessions) or int(std.numel()) != int(mean.numel()):
+    raise ValueError('frontend_push: %d means and %d stds for %d sessions' %
+                     (int(mean.numel()), int(std.numel()), sessions))
+  if not want32 and not want64:
+    raise ValueError('frontend_push: neither the float32 nor the float64 output is wanted')
+  sections = 0 if sos is None else int(np.shape(sos)[0])
+  sos_a, sos_p = _lib.f64_array(sos if sections else np.zeros((1, 6)))
+  zi_a, zi_p = _lib.f64_array(zi if sections else np.zeros((1, 2)))
+  sel = list(range(int(c))) if select is None else [int(v) for v in select]
+  ref_ptr, ref_idx, ch_ptr, ch_idx = [0], [], [0], []
+  for ref, chans in groups:
+    ref_idx += [int(v) for v in ref]
+    ch_idx += [int(v) for v in chans]
+    ref_ptr.append(len(ref_idx))
+    ch_ptr.append(len(ch_idx))
+  keep = [_i32_array(v or [0]) for v in (ref_ptr, ref_idx, ch_ptr, ch_idx, sel)]
+  plan = frontend_plan(rows_before, n, fs_in, fs_out, flush)
+  m, cs = plan.frames_after - plan.frames_before, len(sel)
+  # (every element a push emits is written; an empty tensor has no address: one spare element)
+  out32 = h.empty((sessions * m * cs + 1,), 'float32') if want32 else None
+  out64 = h.empty((sessions * m * cs + 1,), 'float64') if want64 else None
+  live = n > 0
+  h.check(h.lib.td_frontend_push(
+      h.ptr, sessions, _ptr(x if live else None), 1 if live and x.dtype == torch.float64 else 0,
+      int(x.stride(1)) if live and n > 1 else int(c), int(x.stride(0)) if live and sessions > 1 else max(n, 1) * int(c),
+      n, int(c), sos_p if sections else None, sections, int(stage_split), zi_p if sections else None, float(fs_in),
+      float(fs_out), len(groups), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1], cs, _ptr(mean),
+      _ptr(std), 0 if int(mean.numel()) == 1 else 1, int(rows_before), 1 if flush else 0, _ptr(state),
+      int(state.stride(0)) if sessions > 1 else int(state.shape[1]), _ptr(out32), _ptr(out64), cs, max(m, 1) * cs))
+  shaped = lambda t: t[:-1].reshape(sessions, m, cs) if t is not None else None
+  return FrontendPush(shaped(out32), shaped(out64), plan)
+
+
 # ---------------------------------------------------------------- fully connected regressor / match-mismatch classifier
 MLP_LOSSES = {'mse': 0, 'pearson': 1}
 

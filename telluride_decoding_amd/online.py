@@ -36,6 +36,15 @@ is ONE td_fc_online_push launch -- the network on every emitted frame's lagged E
 width but not its context: it comes from the decoder's decoding_model_params, else from the model's
 add_metadata entry, else from the keyword arguments pre_context= / post_context=.
 
+The stage in front of all three is `OnlinePreprocessor`: raw amplifier rows in pushes of ANY length -- 37 or 250
+samples at 1 kHz for a 64 Hz model -- through a `preprocess.Preprocessor`'s filters, resample, re-reference, channel
+selection and normalisation in ONE td_frontend_push launch per push for a bank of sessions, the filter state and the
+resample phase on the device.  Its float32 device tensor goes into `OnlineDecoder.push` as it is:
+
+    front = OnlinePreprocessor(prep)             # prep: the Preprocessor the model was trained behind
+    for raw, env1, env2 in chunks:               # raw [n_raw, C] device tensor, any n_raw
+      result = online.push(front.push(raw), env1, env2)
+
 Without a GPU (`device.gpu_available()` false) the same object runs a NumPy session with the same
 semantics -- float64 throughout, window sums in frame order, td_online_plan's arithmetic -- so that the logic can
 be built and tested anywhere.  (The state-space decoder has no host form: 'ssd' needs the GPU.)
@@ -745,3 +754,329 @@ class OnlineDecoder(object):
                               state=d['ssd_state'])
     return OnlineResult(scores.cpu().numpy(), probs.reshape(self.sessions, new, 3).cpu().numpy(),
                         out.plan.first_window)
+
+
+# ------------------------------------------------------------------------------------------------ the front end
+FRONT_SHARED = ('fs_in', 'fs_out', 'highpass_cutoff', 'highpass_order', 'lowpass_cutoff', 'lowpass_order',
+                'ref_channels', 'channels_to_ref', 'channel_numbers', 'pre_context', 'post_context')
+
+
+def _plain(value):
+  """Lists of lists / ranges as nested tuples, for comparing two Preprocessors' parameters."""
+  if isinstance(value, (list, tuple, range, np.ndarray)):
+    return tuple(_plain(v) for v in value)
+  return value
+
+
+def frontend_parameters(prep):
+  """What a front-end session takes from a preprocess.Preprocessor, read and never written: dict(fs_in, fs_out,
+  sos [S, 6] or None, zi [S, 2] or None, split, ref_channels, channels_to_ref, select, mean, std).  Refuses, naming
+  the parameter: temporal context (the decoder adds its own), data_mean=None (a mean frozen from the first chunk
+  depends on the cut: pass the training value), a data_std of 0 or None, more than 16 sections."""
+  from telluride_decoding_amd import preprocess
+  if not isinstance(prep, preprocess.Preprocessor):
+    raise ValueError('OnlinePreprocessor is configured by a preprocess.Preprocessor, not a %s.' % type(prep).__name__)
+  for key in ('pre_context', 'post_context'):
+    if getattr(prep, key):
+      raise ValueError('OnlinePreprocessor adds no temporal context (%s=%s): the decoder adds its own.' %
+                       (key, getattr(prep, key)))
+  if prep.data_mean is None:
+    raise ValueError('OnlinePreprocessor needs data_mean: a mean frozen from the first chunk (data_mean=None) '
+                     'depends on the cut; pass the training value.')
+  if prep.data_std is None or float(prep.data_std) == 0.0 or not np.isfinite(float(prep.data_std)):
+    raise ValueError('OnlinePreprocessor needs a finite data_std other than 0, not %s.' % (prep.data_std,))
+  sos = prep.sos
+  zi, split = None, 0
+  if sos is not None:
+    sos = np.ascontiguousarray(sos, np.float64)
+    if sos.shape[0] > device.FRONTEND_MAX_SECTIONS:
+      raise ValueError('OnlinePreprocessor filters with at most %d second-order sections, not %d.' %
+                       (device.FRONTEND_MAX_SECTIONS, sos.shape[0]))
+    zi = np.concatenate([np.asarray(z, np.float64) for z in (prep._highpass_zi, prep._lowpass_zi) if z is not None])
+    split = prep._n_hp() if prep._lowpass_sos is not None else int(sos.shape[0])
+  return dict(fs_in=float(prep.fs_in), fs_out=float(prep.fs_out), sos=sos, zi=zi, split=int(split),
+              ref_channels=prep._ref_channels, channels_to_ref=prep._channels_to_ref,
+              select=[int(v) for v in prep.channel_numbers] if prep.channel_numbers else None,
+              mean=float(prep.data_mean), std=float(prep.data_std))
+
+
+def host_frontend_plan(rows_before, n, fs_in, fs_out, flush=False):
+  """td_frontend_plan in NumPy: (frames_before, frames_after, held, the frames whose row is among the rows pushed
+  after this push).  The reference's float64 products in its order (preprocess.resample_indices)."""
+  fs_in, fs_out = float(fs_in), float(fs_out)
+
+  def total(rows):                                   # F(N)
+    return int(rows) if fs_in == fs_out else int(np.round(float(rows) / fs_in * fs_out))
+
+  def reach(rows):                                   # G(N): the frames j with r_j <= N - 1
+    if rows <= 0 or fs_in == fs_out:
+      return max(int(rows), 0)
+    delta = 1.0 / fs_out
+    row = lambda j: int(np.round(j * delta * fs_in))
+    g = max(int(float(rows) / fs_in * fs_out), 0)
+    while g > 0 and row(g - 1) > rows - 1:
+      g -= 1
+    while row(g) <= rows - 1:
+      g += 1
+    return g
+
+  g0, f0, g1, f1 = reach(rows_before), total(rows_before), reach(rows_before + n), total(rows_before + n)
+  e0 = min(g0, f0)
+  e1 = max(e0, f1 if flush else min(g1, f1))
+  return e0, e1, max(g1 - e1, 0), g1
+
+
+def frame_rows(first, count, fs_in, fs_out):
+  """The input rows r_j of the frames [first, first + count): rint((j * (1.0 / fs_out)) * fs_in), int64."""
+  j = np.arange(first, first + count)
+  if float(fs_in) == float(fs_out):
+    return j.astype(np.int64)
+  return np.round(j * (1.0 / float(fs_out)) * float(fs_in)).astype(np.int64)
+
+
+def frontend_groups(cfg, c):
+  """The re-reference groups [(reference channels, channels to re-reference)] of frontend_parameters' dict for rows
+  of c channels (Preprocessor._groups: a missing side is every channel), checked against the row by name."""
+  ref, chans = cfg['ref_channels'], cfg['channels_to_ref']
+  groups = []
+  if ref is not None or chans is not None:
+    ref = [range(c)] if ref is None else ref
+    chans = [range(c)] if chans is None else chans
+    groups = [([int(v) for v in r], [int(v) for v in ch]) for r, ch in zip(ref, chans)]
+  if len(groups) > device.FRONTEND_MAX_GROUPS:
+    raise ValueError('OnlinePreprocessor re-references at most %d groups, not %d.' %
+                     (device.FRONTEND_MAX_GROUPS, len(groups)))
+  for name, lists in (('ref_channels', [g[0] for g in groups]), ('channels_to_ref', [g[1] for g in groups]),
+                      ('channel_numbers', [cfg['select'] or []])):
+    for values in lists:
+      if any(not 0 <= v < c for v in values):
+        raise ValueError('%s %s reaches outside a row of %d channels.' % (name, list(values), c))
+  if any(not g[0] for g in groups):
+    raise ValueError('ref_channels holds a group without a reference channel.')
+  return groups
+
+
+class _HostFrontSession(object):
+  """One front-end session in NumPy float64: the semantics of td_frontend_push (the filter's multiply-adds are
+  rounded twice here and once on the device)."""
+
+  def __init__(self, cfg, c, groups, mean, std):
+    self.cfg, self.c, self.groups, self.mean, self.std = cfg, c, groups, mean, std
+    self.reset()
+
+  def reset(self):
+    sections = 0 if self.cfg['sos'] is None else self.cfg['sos'].shape[0]
+    self.z = np.zeros((sections, 2, self.c), np.float64)
+    self.held = np.zeros((self.c,), np.float64)
+    self.last = np.zeros((self.c,), np.float64)
+
+  def state(self):
+    return np.concatenate([self.z.reshape(-1, self.c), self.held[None], self.last[None]])
+
+  def _filter(self, x, reset):
+    sos, zi, split = self.cfg['sos'], self.cfg['zi'], self.cfg['split']
+    if sos is None:
+      return x.copy()
+    y = np.empty(x.shape, np.float64)
+    z = self.z
+    for t in range(x.shape[0]):
+      v = x[t]
+      base = v
+      for i in range(sos.shape[0]):
+        b0, b1, b2, _, a1, a2 = sos[i]
+        if reset and t == 0:
+          if i == split:
+            base = v
+          z[i, 0], z[i, 1] = base * zi[i, 0], base * zi[i, 1]
+        out = b0 * v + z[i, 0]
+        z[i, 0] = -a1 * out + (b1 * v + z[i, 1])
+        z[i, 1] = -a2 * out + b2 * v
+        v = out
+      y[t] = v
+    return y
+
+  def push(self, x, rows_before, flush):
+    """x [n, c] float64 -> [m, cs] float64."""
+    cfg = self.cfg
+    n = x.shape[0]
+    y = self._filter(x, rows_before == 0)
+    e0, e1, _, g1 = host_frontend_plan(rows_before, n, cfg['fs_in'], cfg['fs_out'], flush)
+    src = np.minimum(rows_before + n - 1, frame_rows(e0, e1 - e0, cfg['fs_in'], cfg['fs_out'])) - rows_before
+    rows = np.empty((e1 - e0, self.c), np.float64)
+    for f, r in enumerate(src):
+      rows[f] = y[r] if r >= 0 else (self.last if r == -1 else self.held)
+    if n > 0:
+      r = int(frame_rows(g1 - 1, 1, cfg['fs_in'], cfg['fs_out'])[0]) - rows_before
+      if r >= 0:
+        self.held = y[r].copy()
+      self.last = y[n - 1].copy()
+    out = rows.copy()
+    for ref, chans in self.groups:
+      total = np.zeros((rows.shape[0],), np.float64)
+      for ch in ref:                                   # in list order
+        total = total + rows[:, ch]
+      out[:, list(chans)] -= (total / float(len(ref)))[:, None]      # (a channel listed twice: once)
+    if cfg['select'] is not None:
+      out = out[:, cfg['select']]
+    return (out - self.mean) / self.std
+
+
+class OnlinePreprocessor(object):
+  """The online EEG front end: a bank of S sessions that take raw rows in pushes of any length and give the
+  conditioned float32 frames OnlineDecoder.push takes as `eeg` -- one td_frontend_push launch per push, the filter
+  state and the resample phase on the device, and any cut of a recording gives the bytes of one push.
+
+  preprocessors: one preprocess.Preprocessor (num_sessions sessions share it, default 1) or a list of S of them,
+  which share everything except data_mean / data_std.  The objects are read, never written, and never run: the
+  filters (high-pass sections, then low-pass ones), the stage split, the rates, the re-reference groups and the
+  channel selection come from them.  The steps and their order are Preprocessor.process's; the output over any cut
+  has the rows of process(whole, reset=True).  Refused by name: pre_context / post_context (the decoder adds its
+  own), data_mean=None, a data_std of 0 or None, more than 16 sections; at the first push, a row of more than 128
+  channels and selected or group channels outside it.
+
+  Without a GPU the same object runs a NumPy float64 session of the same semantics."""
+
+  def __init__(self, preprocessors, num_sessions=None):
+    if not isinstance(preprocessors, (list, tuple)):
+      preprocessors = [preprocessors] * (1 if num_sessions is None else int(num_sessions))
+    elif num_sessions is not None and int(num_sessions) != len(preprocessors):
+      raise ValueError('OnlinePreprocessor: %d preprocessors for num_sessions=%d.' %
+                       (len(preprocessors), int(num_sessions)))
+    if not preprocessors:
+      raise ValueError('OnlinePreprocessor needs at least one session.')
+    self._cfgs = [frontend_parameters(p) for p in preprocessors]
+    first = preprocessors[0]
+    for p in preprocessors[1:]:
+      for key in FRONT_SHARED:
+        if _plain(getattr(p, key)) != _plain(getattr(first, key)):
+          raise ValueError('The sessions of a bank share everything except data_mean and data_std: %s is %s and %s.' %
+                           (key, getattr(first, key), getattr(p, key)))
+    self._cfg = self._cfgs[0]
+    self.sessions = len(preprocessors)
+    self.fs_in, self.fs_out = self._cfg['fs_in'], self._cfg['fs_out']
+    self.sections = 0 if self._cfg['sos'] is None else int(self._cfg['sos'].shape[0])
+    self.channels = None                         # the raw row's width: known at the first push
+    self.channels_out = None
+    self._on_device = device.gpu_available()
+    self._dev = self._host = None
+    self.rows_pushed = self.frames_emitted = 0
+    self.flushed = False
+    self._tensors = False
+
+  # -- state -------------------------------------------------------------------------------------
+  def _setup(self, c):
+    cfg = self._cfg
+    if not 1 <= c <= device.FRONTEND_MAX_CHANNELS:
+      raise ValueError('OnlinePreprocessor takes rows of 1 to %d channels, not %d.' % (device.FRONTEND_MAX_CHANNELS, c))
+    groups = frontend_groups(cfg, c)
+    self.channels, self._groups = c, groups
+    self.channels_out = len(cfg['select']) if cfg['select'] is not None else c
+    if self.channels_out < 1:
+      raise ValueError('channel_numbers selects no channel.')
+    if not self._on_device:
+      self._host = [_HostFrontSession(cfg, c, groups, k['mean'], k['std']) for k in self._cfgs]
+      return
+    h = device.default_handle()
+    torch = device._torch()
+    stats = np.array([[k['mean'], k['std']] for k in self._cfgs], np.float64)
+    if np.all(stats == stats[0]):
+      stats = stats[:1]                          # (one pair every session reads)
+    nbytes = device.frontend_state_bytes(c, self.sections)
+    self._dev = dict(h=h, mean=h.to_device(stats[:, 0:1], np.float64).reshape(-1),
+                     std=h.to_device(stats[:, 1:2], np.float64).reshape(-1),
+                     state=torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device))
+
+  def reset(self):
+    """A fresh recording: zero state, no row pushed; the filters reset on the next push's first row."""
+    self.rows_pushed = self.frames_emitted = 0
+    self.flushed = False
+    if self._dev is not None:
+      self._dev['state'].zero_()
+    if self._host is not None:
+      for sess in self._host:
+        sess.reset()
+
+  @property
+  def state(self):
+    """The sessions' state blocks [S, 2 sections + 2, C] float64 -- the filter state in scipy's zi layout
+    (Preprocessor.filter_state's), the held row, the last row -- as a device tensor (a view) or a host array; None
+    before the first push."""
+    if self._dev is not None:
+      return self._dev['state'].view(device._torch().float64).reshape(self.sessions, -1, self.channels)
+    if self._host is not None:
+      return np.stack([sess.state() for sess in self._host])
+    return None
+
+  # -- pushes ------------------------------------------------------------------------------------
+  def push(self, raw, want64=False):
+    """The next n raw rows of every session: raw [n, C] (one session) or [S, n, C], float32 or float64, a host
+    array or a device tensor; n may be 0.  Returns the frames this push emits, [S, m, cs] float32 (m may be 0): a
+    device tensor for a device tensor -- what OnlineDecoder.push takes as eeg, unchanged -- else a host array.
+    want64: (the float32 frames, the same frames before the cast, float64)."""
+    if self.flushed:
+      raise ValueError('The front end was flushed: reset() starts the next recording.')
+    return self._advance(raw, False, want64)
+
+  def flush(self, want64=False):
+    """The end of the recording: emits the frames resample_indices counts for the rows pushed that no push has
+    emitted yet (when upsampling, from the last row), as the pushes returned theirs.  After it the front end
+    refuses pushes until reset()."""
+    if self.flushed:
+      raise ValueError('The front end was flushed: reset() starts the next recording.')
+    out = self._advance(None, True, want64)
+    self.flushed = True
+    return out
+
+  def _advance(self, raw, flush, want64):
+    on_dev_in = self._tensors if raw is None else hasattr(raw, 'is_cuda')
+    self._tensors = on_dev_in                    # (a flush answers as the last push did)
+    if raw is not None:
+      if not on_dev_in:
+        raw = np.asarray(raw)
+        if raw.dtype not in (np.float32, np.float64):
+          raw = raw.astype(np.float64)
+      if len(raw.shape) == 2 and self.sessions == 1:
+        raw = raw[None]
+      if len(raw.shape) != 3 or int(raw.shape[0]) != self.sessions or (
+          self.channels is not None and int(raw.shape[2]) != self.channels):
+        raise ValueError('A push is raw [%d, n, %s] (or [n, %s] for one session), not %s.' %
+                         (self.sessions, self.channels or 'C', self.channels or 'C', tuple(raw.shape)))
+      if self.channels is None:
+        self._setup(int(raw.shape[2]))
+    n = 0 if raw is None else int(raw.shape[1])
+    if self.channels is None:                    # (a flush before any row)
+      return np.zeros((self.sessions, 0, 0), np.float32)
+    cfg = self._cfg
+    if not self._on_device:
+      if raw is None:
+        x = np.zeros((self.sessions, 0, self.channels), np.float64)
+      else:
+        x = raw.cpu().numpy() if hasattr(raw, 'cpu') else raw
+      outs = [sess.push(np.asarray(x[i], np.float64), self.rows_pushed, flush) for i, sess in enumerate(self._host)]
+      out64 = np.stack(outs)
+      self.rows_pushed += n
+      self.frames_emitted += out64.shape[1]
+      out32 = out64.astype(np.float32)
+      if on_dev_in:
+        out32, out64 = device._torch().from_numpy(out32), device._torch().from_numpy(out64)
+      return (out32, out64) if want64 else out32
+    d = self._dev
+    h = d['h']
+    x = None
+    if n > 0:
+      torch = device._torch()
+      if on_dev_in:
+        x = raw if raw.dtype in (torch.float32, torch.float64) else raw.to(torch.float32)
+        if x.stride(2) != 1 and self.channels > 1:
+          x = x.contiguous()
+      else:
+        x = torch.from_numpy(np.ascontiguousarray(raw)).to(h.device)
+    out = device.frontend_push(x, cfg['sos'], cfg['split'], cfg['zi'], cfg['fs_in'], cfg['fs_out'], self._groups,
+                               cfg['select'], d['mean'], d['std'], d['state'], self.rows_pushed, c=self.channels,
+                               flush=flush, want64=want64, handle=h)
+    self.rows_pushed += n
+    self.frames_emitted = out.plan.frames_after
+    out32, out64 = out.out32, out.out64
+    if not on_dev_in:
+      out32, out64 = out32.cpu().numpy(), out64.cpu().numpy() if want64 else None
+    return (out32, out64) if want64 else out32
