@@ -997,6 +997,65 @@ int td_audio_passthrough(td_handle* h, const double* buf_dev, int64_t buf_rows, 
 int td_audio_spectrogram(td_handle* h, const float* wave_dev, int64_t n, int seg, int hop, int nfft,
                          const double* taps_host, int num_taps, int64_t frames, double* out_dev);
 
+/* ------------------------------------------------------------------ online audio front end
+ * The intensity envelope above for audio that arrives in chunks of ANY length, in front of td_online_push's env1 /
+ * env2: `num_sessions` independent listeners configured by one AudioFeatures' parameters (fs_in, fs_out, window,
+ * exponent), one state block each on the device, advanced by ONE launch per push.  However a recording is cut into
+ * pushes, the concatenated output and the live state are those of one push of the whole recording, bit for bit, and
+ * the frames are those of AudioFeatures(...).compute_intensity(whole) on a fresh object: the same windows, the same
+ * count.  (td_audio_intensity restarts its window centres on every call; this family does not.)  The auditory
+ * spectrogram has no such form: it is scaled by the maximum over the whole recording.
+ *
+ * Frames.  With N rows pushed so far, F(N) = rint(N / fs_in * fs_out), hw = 0.5 window / fs_out and, for frame i,
+ * t = i / fs_out, a_i = rint(fs_in (t - hw)), u_i = rint(fs_in (t + hw)) -- float64 in the reference's order, half
+ * even --, frame i is emitted by the first push after which u_i <= N and i < F(N).  A flush emits every frame
+ * i < F(N) still missing.  Frame i is sqrt(mean) ** exponent (numpy's fast paths for 1, 2, 0.5, 0, -1) of the
+ * float64 mean of float32(x)^2 -- squared in float32 -- over rows [max(0, a_i), min(N at emission, u_i)); an empty
+ * window gives NaN.  The sum: lane l of a wave adds rows max(0, a_i) + l + 64 k in increasing k, then the xor
+ * butterfly 32, 16, .. 1 -- a function of the window and the data, not of the cut or of an address.
+ *
+ * State.  The float32 squares of the last K rows pushed, K = ceil((window / 2 + max(window / 2, 0.5)) fs_in /
+ * fs_out) + 2 (td_audio_online_plan's tail_rows; it bounds what the first frame not yet emitted reaches back).  A
+ * tail copy is [K][c] float32, slot j holding row N - K + j, rows before row 0 zero: all zeros = fresh, and a copy
+ * is a function of the rows pushed alone.  The block holds TWO copies (td_audio_online_state_bytes = 8 K c): a
+ * launch reads copy `live` and writes every slot of the other one, so no workgroup reads what another writes.  The
+ * HOST flips `live` after every push with n > 0 and counts the rows; a push with n == 0 writes no state.
+ *
+ * td_audio_online_plan (host only): what a push of n rows behind rows_before pushed ones emits.
+ *   frames_before / frames_after   frames emitted before / after the push (flush != 0: F(rows_before + n))
+ *   held       F(rows_before + n) - frames_after
+ *   tail_rows  K
+ *
+ * td_audio_online_push: the sessions' next n rows.
+ *   x_dev     [S][n][c] int16 / float32 / float64 (x_type TD_AUDIO_X_I16 / _F32 / _F64), row stride ldx, session
+ *             stride x_session_stride (elements); the online object never transposes
+ *   n >= 0    (n == 0 with no frame to emit: nothing is queued)
+ *   state_dev, state_session_stride (BYTES, a multiple of 8, >= td_audio_online_state_bytes), live (0 or 1)
+ *   out32_dev / out64_dev  [S][frames_after - frames_before][c] float32 / float64 (either may be NULL, not both),
+ *             row stride ldout, session stride out_session_stride (elements); out32 is the float64 value rounded once
+ *   windows_dev  NULL or [frames_after - frames_before][2] int64: the clamped window of every emitted frame
+ * No atomics, vector stores only: two runs give the same bits.  TD_ERR_INVALID, before anything is queued and with
+ * the state untouched: a NULL required pointer, num_sessions outside 1..65535, c outside
+ * 1..TD_AUDIO_ONLINE_MAX_CHANNELS, an unknown x_type, a rate or window that is not positive and finite, the
+ * reference's pass-through case (fs_out >= fs_in and window <= 1: it returns its input, there is nothing to
+ * compute), K above TD_AUDIO_ONLINE_MAX_TAIL (which admits 48 kHz -> 64 Hz at window 8: K = 6002), n or the
+ * emitted count outside 0..TD_ONLINE_MAX_PUSH, rows_before < 0, live outside 0..1, ldx or ldout < c, a session
+ * stride of x or the outputs below one row (more than one session), a state stride below the state block or not
+ * a multiple of 8.  With td_profile_enable the launch is bracketed as td_online_push's is. */
+#define TD_AUDIO_ONLINE_MAX_CHANNELS 8
+#define TD_AUDIO_ONLINE_MAX_TAIL 8192
+#define TD_AUDIO_X_I16 0
+#define TD_AUDIO_X_F32 1
+#define TD_AUDIO_X_F64 2
+int td_audio_online_plan(int64_t rows_before, int64_t n, double fs_in, double fs_out, double window, int flush,
+                         int64_t* frames_before, int64_t* frames_after, int64_t* held, int64_t* tail_rows);
+int td_audio_online_state_bytes(int c, int64_t tail_rows, int64_t* bytes);
+int td_audio_online_push(td_handle* h, int num_sessions, const void* x_dev, int x_type, int64_t ldx,
+                         int64_t x_session_stride, int64_t n, int c, int64_t rows_before, int flush, double fs_in,
+                         double fs_out, double window, double exponent, void* state_dev,
+                         int64_t state_session_stride, int live, float* out32_dev, double* out64_dev, int64_t ldout,
+                         int64_t out_session_stride, int64_t* windows_dev);
+
 /* ------------------------------------------------------------------ ingestion
  * ingest.find_mean_std, ingest.normalize_data and ingest.convert_data_to_tfrecords (ingest.py:1061-1172).
  *

@@ -184,6 +184,12 @@ SIGNATURES = {
     'td_audio_intensity': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _d, _d, _d, _i, _d, _vp, _vp],
     'td_audio_passthrough': [_vp, _vp, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _i64, _i, _d, _vp, _vp],
     'td_audio_spectrogram': [_vp, _vp, _i64, _i, _i, _i, _pd, _i, _i64, _vp],
+    'td_audio_online_plan': [_i64, _i64, _d, _d, _d, _i, _pi64, _pi64, _pi64, _pi64],
+    'td_audio_online_state_bytes': [_i, _i64, _pi64],
+    # h, sessions | x, type, ld, stride | n, c | rows_before, flush | fs_in, fs_out, window, exponent |
+    # state, stride, live | out32, out64, ld, stride | windows
+    'td_audio_online_push': [_vp, _i] + [_vp, _i, _i64, _i64] + [_i64, _i] + [_i64, _i] + [_d, _d, _d, _d] +
+                            [_vp, _i64, _i] + [_vp, _vp, _i64, _i64] + [_vp],
     'td_ingest_moments': [_vp, _c.POINTER(_vp), _pi64, _pi64, _c.POINTER(_i), _i, _i, _vp],
     'td_ingest_normalize': [_vp, _vp, _i, _i64, _i64, _i, _pd, _pd, _i, _i, _i, _i, _vp, _i64],
     'td_tfrecord_encode': [_vp, _c.c_char_p, _i, _i, _c.POINTER(_vp), _pi64, _c.POINTER(_i), _c.POINTER(_i),

@@ -1756,6 +1756,83 @@ def frontend_push(x, sos, stage_split, zi, fs_in, fs_out, groups, select, mean, 
   return FrontendPush(shaped(out32), shaped(out64), plan)
 
 
+# ---------------------------------------------------------------- online audio front end
+AUDIO_ONLINE_MAX_CHANNELS, AUDIO_ONLINE_MAX_TAIL = 8, 8192       # td_audio_online_push's limits
+AUDIO_X_TYPES = {'int16': 0, 'float32': 1, 'float64': 2}          # TD_AUDIO_X_*
+
+AudioOnlinePlan = collections.namedtuple('AudioOnlinePlan', ['frames_before', 'frames_after', 'held', 'tail_rows'])
+AudioOnlinePush = collections.namedtuple('AudioOnlinePush', ['out32', 'out64', 'windows', 'plan', 'live'])
+
+
+def audio_online_plan(rows_before, n, fs_in, fs_out, window, flush=False):
+  """What a push of n audio rows behind `rows_before` pushed ones emits (td_audio_online_plan, host arithmetic in
+  the reference's float64 order): AudioOnlinePlan(frames_before, frames_after, held, tail_rows)."""
+  out = [ctypes.c_int64(0) for _ in range(4)]
+  _lib.check(None, _lib.load().td_audio_online_plan(int(rows_before), int(n), float(fs_in), float(fs_out),
+                                                    float(window), 1 if flush else 0,
+                                                    *[ctypes.byref(v) for v in out]))
+  return AudioOnlinePlan(*[int(v.value) for v in out])
+
+
+def audio_online_state_bytes(c, tail_rows):
+  """Bytes of one online audio session's state block (td_audio_online_state_bytes): two tail copies of
+  [tail_rows, c] float32 squares; all zeros = a fresh session."""
+  n = ctypes.c_int64(0)
+  _lib.check(None, _lib.load().td_audio_online_state_bytes(int(c), int(tail_rows), ctypes.byref(n)))
+  return int(n.value)
+
+
+def audio_online_push(x, fs_in, fs_out, window, exponent, state, live, rows_before, c=None, flush=False, want32=True,
+                      want64=False, windows=False, handle=None):
+  """One push of a bank of online audio sessions, in one launch (td_audio_online_push).
+
+  x [S, n, c]: int16, float32 or float64 device tensor with unit column stride (None for a flush without rows: give
+  c); state: uint8 device tensor [S, >= audio_online_state_bytes()] with a row stride that is a multiple of 8 -- the
+  launch reads tail copy `live` and writes the other one; rows_before: rows pushed so far.  Returns
+  AudioOnlinePush(out32 [S, m, c] float32, out64 [S, m, c] float64, windows [m, 2] int64 (None when not wanted),
+  plan, the copy that is live after the push: flipped when n > 0).  Queued, not waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  sessions = int(state.shape[0])
+  n = 0 if x is None else int(x.shape[1])
+  x_type = 1
+  if x is not None:
+    if x.dim() != 3 or int(x.shape[0]) != sessions:
+      raise ValueError('audio_online_push: x of %s for %d sessions' % (tuple(x.shape), sessions))
+    c = int(x.shape[2])
+    name = str(x.dtype).replace('torch.', '')
+    if name not in AUDIO_X_TYPES or x.device != h.device:
+      raise TypeError('audio_online_push: x must be an int16, float32 or float64 tensor on %s, not %s on %s' %
+                      (h.device, x.dtype, x.device))
+    x_type = AUDIO_X_TYPES[name]
+    if n > 0 and c > 1 and x.stride(2) != 1:
+      raise ValueError('audio_online_push: the columns of x must be contiguous')
+  if c is None:
+    raise ValueError('audio_online_push: a flush without rows needs the channel count c')
+  if state.dtype != torch.uint8 or state.device != h.device:
+    raise TypeError('audio_online_push: state must be a uint8 tensor on %s, not %s on %s' %
+                    (h.device, state.dtype, state.device))
+  if not want32 and not want64:
+    raise ValueError('audio_online_push: neither the float32 nor the float64 output is wanted')
+  c = int(c)
+  plan = audio_online_plan(rows_before, n, fs_in, fs_out, window, flush)
+  m = plan.frames_after - plan.frames_before
+  # (every element a push emits is written; an empty tensor has no address: one spare element)
+  out32 = h.empty((sessions * m * c + 1,), 'float32') if want32 else None
+  out64 = h.empty((sessions * m * c + 1,), 'float64') if want64 else None
+  win = h.empty((m + 1, 2), 'int64') if windows else None
+  rows = n > 0
+  h.check(h.lib.td_audio_online_push(
+      h.ptr, sessions, _ptr(x if rows else None), x_type, int(x.stride(1)) if rows and n > 1 else c,
+      int(x.stride(0)) if rows and sessions > 1 else max(n, 1) * c, n, c, int(rows_before), 1 if flush else 0,
+      float(fs_in), float(fs_out), float(window), float(exponent), _ptr(state),
+      int(state.stride(0)) if sessions > 1 else int(state.shape[1]), int(live), _ptr(out32), _ptr(out64), c,
+      max(m, 1) * c, _ptr(win)))
+  shaped = lambda t: t[:-1].reshape(sessions, m, c) if t is not None else None
+  return AudioOnlinePush(shaped(out32), shaped(out64), win[:m] if windows else None, plan,
+                         1 - int(live) if rows else int(live))
+
+
 # ---------------------------------------------------------------- fully connected regressor / match-mismatch classifier
 MLP_LOSSES = {'mse': 0, 'pearson': 1}
 

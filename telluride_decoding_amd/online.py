@@ -45,6 +45,17 @@ resample phase on the device.  Its float32 device tensor goes into `OnlineDecode
     for raw, env1, env2 in chunks:               # raw [n_raw, C] device tensor, any n_raw
       result = online.push(front.push(raw), env1, env2)
 
+The envelopes come the same way: `OnlineAudioFeatures` takes the two speakers' audio (int16 as a sound card delivers
+it, column k = speaker k) in pushes of any length and gives the intensity envelope of a `preprocess.AudioFeatures` at
+the model's frame rate in ONE td_audio_online_push launch per push -- over any cut the frames of
+compute_intensity(whole), which the batch call, whose window centres restart on every call, is not.  An envelope
+frame needs half a window of future audio, so it trails the EEG frame of its index; `FrameJoin` lines the streams
+up, on the device:
+
+    eeg = front.push(raw)
+    env = audio.push(pcm)                        # [S, m, 2] float32
+    result = online.push(*join.push(eeg, env[..., 0], env[..., 1]))
+
 Without a GPU (`device.gpu_available()` false) the same object runs a NumPy session with the same
 semantics -- float64 throughout, window sums in frame order, td_online_plan's arithmetic -- so that the logic can
 be built and tested anywhere.  (The state-space decoder has no host form: 'ssd' needs the GPU.)
@@ -1080,3 +1091,341 @@ class OnlinePreprocessor(object):
     if not on_dev_in:
       out32, out64 = out32.cpu().numpy(), out64.cpu().numpy() if want64 else None
     return (out32, out64) if want64 else out32
+
+
+# ------------------------------------------------------------------------------------------------ the audio front end
+AUDIO_SHARED = ('fs_in', 'fs_out', 'window', 'exponent')
+
+
+def audio_parameters(features):
+  """What an online audio session takes from a preprocess.AudioFeatures, read and never written: dict(fs_in,
+  fs_out, window, exponent) as floats.  Refuses by name the reference's pass-through case (fs_out >= fs_in and
+  window <= 1: compute_intensity returns its input there, there is nothing to compute) and a rate, window or
+  exponent that is not a finite number."""
+  from telluride_decoding_amd import preprocess
+  if not isinstance(features, preprocess.AudioFeatures):
+    raise ValueError('OnlineAudioFeatures is configured by a preprocess.AudioFeatures, not a %s.' %
+                     type(features).__name__)
+  cfg = dict((key, float(getattr(features, '_' + key))) for key in AUDIO_SHARED)
+  for key in AUDIO_SHARED:
+    if not np.isfinite(cfg[key]) or (key != 'exponent' and cfg[key] <= 0):
+      raise ValueError('OnlineAudioFeatures needs a finite%s %s, not %s.' %
+                       ('' if key == 'exponent' else ' positive', key, cfg[key]))
+  if cfg['fs_out'] >= cfg['fs_in'] and cfg['window'] <= 1:
+    raise ValueError('OnlineAudioFeatures: fs_out=%g >= fs_in=%g with window=%g <= 1 is the pass-through case: '
+                     'compute_intensity returns its input there, there is nothing to compute.' %
+                     (cfg['fs_out'], cfg['fs_in'], cfg['window']))
+  return cfg
+
+
+def audio_tail_rows(fs_in, fs_out, window):
+  """K, the rows an online audio session carries: ceil((window / 2 + max(window / 2, 0.5)) fs_in / fs_out) + 2."""
+  half = 0.5 * float(window)
+  return int(np.ceil((half + max(half, 0.5)) * float(fs_in) / float(fs_out))) + 2
+
+
+def audio_window(i, fs_in, fs_out, window):
+  """(a_i, u_i) of frame i, unclamped: Python floats in the reference's order, half-even."""
+  hw = 0.5 * window / fs_out
+  t = float(i) / fs_out
+  return int(round(fs_in * (t - hw))), int(round(fs_in * (t + hw)))
+
+
+def host_audio_plan(rows_before, n, fs_in, fs_out, window, flush=False):
+  """td_audio_online_plan in Python floats: (frames_before, frames_after, held, K)."""
+  fs_in, fs_out, window = float(fs_in), float(fs_out), float(window)
+  hw = 0.5 * window / fs_out
+  upper = lambda i: audio_window(i, fs_in, fs_out, window)[1]
+
+  def total(rows):                                   # F(N)
+    return int(round(float(rows) / fs_in * fs_out))
+
+  def reach(rows):                                   # G(N): the frames i with u_i <= N
+    g = max(int((float(rows) / fs_in - hw) * fs_out), 0)
+    while g > 0 and upper(g - 1) > rows:
+      g -= 1
+    while upper(g) <= rows:
+      g += 1
+    return g
+
+  rows_after = rows_before + n
+  e0 = min(reach(rows_before), total(rows_before))
+  f1 = total(rows_after)
+  e1 = max(e0, f1 if flush else min(reach(rows_after), f1))
+  return e0, e1, f1 - e1, audio_tail_rows(fs_in, fs_out, window)
+
+
+class _HostAudioSession(object):
+  """One online audio session in NumPy: the semantics of td_audio_online_push -- float32 squares, float64 sums (in
+  numpy's row order, where the device adds a lane's rows and then the butterfly), the tail of the last K rows."""
+
+  def __init__(self, cfg, c):
+    self.cfg, self.c = cfg, c
+    self.k = audio_tail_rows(cfg['fs_in'], cfg['fs_out'], cfg['window'])
+    self.reset()
+
+  def reset(self):
+    self.tail = np.zeros((self.k, self.c), np.float32)
+
+  def push(self, x, rows_before, flush):
+    """x [n, c] -> (frames [m, c] float64, windows [m, 2] int64)."""
+    cfg = self.cfg
+    n = x.shape[0]
+    sq = np.asarray(x).astype(np.float32)
+    sq = sq * sq
+    rows = np.concatenate([self.tail, sq])             # row r of the recording at r - base
+    base, rows_after = rows_before - self.k, rows_before + n
+    e0, e1, _, _ = host_audio_plan(rows_before, n, cfg['fs_in'], cfg['fs_out'], cfg['window'], flush)
+    out = np.full((e1 - e0, self.c), np.nan)
+    win = np.zeros((e1 - e0, 2), np.int64)
+    for f in range(e1 - e0):
+      a, u = audio_window(e0 + f, cfg['fs_in'], cfg['fs_out'], cfg['window'])
+      t1, t2 = max(0, a), min(rows_after, u)
+      win[f] = t1, t2
+      if t1 - base < 0:
+        raise ValueError('frame %d reaches back to row %d, behind the %d carried rows' % (e0 + f, t1, self.k))
+      if t2 > t1:
+        span = np.array(rows[t1 - base:t2 - base], np.float64, order='C')     # (a copy: the sum sees the span alone)
+        out[f] = np.add.reduce(span, axis=0) / float(t2 - t1)
+    if n > 0:
+      self.tail = np.ascontiguousarray(rows[-self.k:])
+    with np.errstate(invalid='ignore', divide='ignore'):
+      return np.sqrt(out) ** cfg['exponent'], win
+
+
+class OnlineAudioFeatures(object):
+  """The online audio front end: a bank of S sessions that take audio rows in pushes of any length and give the
+  intensity envelopes OnlineDecoder.push takes as env1 / env2 -- one td_audio_online_push launch per push, the last
+  K rows' squares on the device, and any cut of a recording gives the bytes of one push: the frames of
+  AudioFeatures(...).compute_intensity(whole) on a fresh object, with the same windows and the same count (the
+  batch call restarts its window centres on every call: DESIGN.md section 13).
+
+  features: one preprocess.AudioFeatures (num_sessions sessions share it, default 1) or a list of S of them that
+  share fs_in, fs_out, window and exponent.  The objects are read, never written, and never run.  A push is always
+  [n, c] (or [S, n, c]): nothing is transposed.  Column k of the output is speaker k.  Refused by name: the
+  pass-through case (fs_out >= fs_in and window <= 1), more than 8 channels, a window that carries more than 8192
+  rows.  The auditory spectrogram has no online form: it is scaled by the maximum over the whole recording.
+
+  Without a GPU the same object runs a NumPy float64 session of the same semantics."""
+
+  def __init__(self, features, num_sessions=None):
+    if not isinstance(features, (list, tuple)):
+      features = [features] * (1 if num_sessions is None else int(num_sessions))
+    elif num_sessions is not None and int(num_sessions) != len(features):
+      raise ValueError('OnlineAudioFeatures: %d AudioFeatures for num_sessions=%d.' %
+                       (len(features), int(num_sessions)))
+    if not features:
+      raise ValueError('OnlineAudioFeatures needs at least one session.')
+    cfgs = [audio_parameters(f) for f in features]
+    for cfg in cfgs[1:]:
+      for key in AUDIO_SHARED:
+        if cfg[key] != cfgs[0][key]:
+          raise ValueError('The sessions of a bank share fs_in, fs_out, window and exponent: %s is %s and %s.' %
+                           (key, cfgs[0][key], cfg[key]))
+    self._cfg = cfgs[0]
+    self.sessions = len(features)
+    self.fs_in, self.fs_out = self._cfg['fs_in'], self._cfg['fs_out']
+    self.window, self.exponent = self._cfg['window'], self._cfg['exponent']
+    self.tail_rows = audio_tail_rows(self.fs_in, self.fs_out, self.window)
+    if self.tail_rows > device.AUDIO_ONLINE_MAX_TAIL:
+      raise ValueError('OnlineAudioFeatures: %g -> %g Hz with window=%g carries %d rows (at most %d).' %
+                       (self.fs_in, self.fs_out, self.window, self.tail_rows, device.AUDIO_ONLINE_MAX_TAIL))
+    self.channels = None                         # the row's width: known at the first push
+    self._on_device = device.gpu_available()
+    self._dev = self._host = None
+    self._live = 0
+    self.rows_pushed = self.frames_emitted = 0
+    self.flushed = False
+    self._tensors = False
+
+  def _setup(self, c):
+    if not 1 <= c <= device.AUDIO_ONLINE_MAX_CHANNELS:
+      raise ValueError('OnlineAudioFeatures takes rows of 1 to %d channels, not %d (a push is [n, c]: nothing is '
+                       'transposed).' % (device.AUDIO_ONLINE_MAX_CHANNELS, c))
+    self.channels = c
+    if not self._on_device:
+      self._host = [_HostAudioSession(self._cfg, c) for _ in range(self.sessions)]
+      return
+    h = device.default_handle()
+    nbytes = device.audio_online_state_bytes(c, self.tail_rows)
+    self._dev = dict(h=h, state=device._torch().zeros((self.sessions, nbytes), dtype=device._torch().uint8,
+                                                      device=h.device))
+
+  def reset(self):
+    """A fresh recording: zero state, no row pushed."""
+    self.rows_pushed = self.frames_emitted = 0
+    self.flushed = False
+    self._live = 0
+    if self._dev is not None:
+      self._dev['state'].zero_()
+    if self._host is not None:
+      for sess in self._host:
+        sess.reset()
+
+  @property
+  def state(self):
+    """The live tail copy of every session, [S, K, c] float32: the squares of the last K rows pushed, slot j holding
+    row rows_pushed - K + j (zero before row 0) -- a device tensor (a view) or a host array; None before the first
+    push."""
+    if self._dev is not None:
+      blocks = self._dev['state'].view(device._torch().float32)
+      return blocks.reshape(self.sessions, 2, self.tail_rows, self.channels)[:, self._live]
+    if self._host is not None:
+      return np.stack([sess.tail for sess in self._host])
+    return None
+
+  def push(self, audio, want64=False):
+    """The next n rows of every session: audio [n, c] (one session; [n] is one channel) or [S, n, c], int16,
+    float32 or float64 (anything else goes through float32, as compute_intensity's astype does), a host array or a
+    device tensor; n may be 0.  Returns the frames this push emits, [S, m, c] float32 (m may be 0): a device tensor
+    for a device tensor, else a host array.  want64: (the float32 frames, the float64 frames they were rounded
+    from -- the reference's dtype)."""
+    if self.flushed:
+      raise ValueError('The audio front end was flushed: reset() starts the next recording.')
+    return self._advance(audio, False, want64)
+
+  def flush(self, want64=False):
+    """The end of the recording: emits every frame of int(round(rows_pushed / fs_in * fs_out)) that no push has
+    emitted yet, its window clamped at the last row, as compute_intensity(whole) does.  After it the front end
+    refuses pushes until reset()."""
+    if self.flushed:
+      raise ValueError('The audio front end was flushed: reset() starts the next recording.')
+    out = self._advance(None, True, want64)
+    self.flushed = True
+    return out
+
+  def _advance(self, audio, flush, want64):
+    on_dev_in = self._tensors if audio is None else hasattr(audio, 'is_cuda')
+    self._tensors = on_dev_in                    # (a flush answers as the last push did)
+    if audio is not None:
+      if not on_dev_in:
+        audio = np.asarray(audio)
+        if audio.dtype not in (np.int16, np.float32, np.float64):
+          audio = audio.astype(np.float32)
+      if len(audio.shape) == 1 and self.sessions == 1:
+        audio = audio.reshape(-1, 1)
+      if len(audio.shape) == 2 and self.sessions == 1:
+        audio = audio[None]
+      if len(audio.shape) != 3 or int(audio.shape[0]) != self.sessions or (
+          self.channels is not None and int(audio.shape[2]) != self.channels):
+        raise ValueError('A push is audio [%d, n, %s] (or [n, %s] for one session), not %s.' %
+                         (self.sessions, self.channels or 'c', self.channels or 'c', tuple(audio.shape)))
+      if self.channels is None:
+        self._setup(int(audio.shape[2]))
+    n = 0 if audio is None else int(audio.shape[1])
+    if self.channels is None:                    # (a flush before any row)
+      empty = np.zeros((self.sessions, 0, 0), np.float32)
+      return (empty, empty.astype(np.float64)) if want64 else empty
+    cfg = self._cfg
+    if not self._on_device:
+      if audio is None:
+        x = np.zeros((self.sessions, 0, self.channels), np.float32)
+      else:
+        x = audio.cpu().numpy() if hasattr(audio, 'cpu') else audio
+      outs = [sess.push(x[i], self.rows_pushed, flush) for i, sess in enumerate(self._host)]
+      out64 = np.stack([o[0] for o in outs])
+      self.rows_pushed += n
+      self.frames_emitted += out64.shape[1]
+      with np.errstate(over='ignore'):
+        out32 = out64.astype(np.float32)
+      if on_dev_in:
+        out32, out64 = device._torch().from_numpy(out32), device._torch().from_numpy(out64)
+      return (out32, out64) if want64 else out32
+    d = self._dev
+    h = d['h']
+    x = None
+    if n > 0:
+      torch = device._torch()
+      if on_dev_in:
+        x = audio if audio.dtype in (torch.int16, torch.float32, torch.float64) else audio.to(torch.float32)
+        if x.stride(2) != 1 and self.channels > 1:
+          x = x.contiguous()
+      else:
+        x = torch.from_numpy(np.array(audio, order='C')).to(h.device)     # (a copy: the caller's may be read-only)
+    out = device.audio_online_push(x, cfg['fs_in'], cfg['fs_out'], cfg['window'], cfg['exponent'], d['state'],
+                                   self._live, self.rows_pushed, c=self.channels, flush=flush, want64=want64,
+                                   handle=h)
+    self._live = out.live
+    self.rows_pushed += n
+    self.frames_emitted = out.plan.frames_after
+    out32, out64 = out.out32, out.out64
+    if not on_dev_in:
+      out32, out64 = out32.cpu().numpy(), out64.cpu().numpy() if want64 else None
+    return (out32, out64) if want64 else out32
+
+
+# ------------------------------------------------------------------------------------------------ joining the streams
+FrameJoinFlush = collections.namedtuple('FrameJoinFlush', ['blocks', 'beyond'])
+
+
+class FrameJoin(object):
+  """Lines up the frames of several online streams that emit at their own pace -- the EEG front end and the audio
+  front end, whose envelope frame i needs half a window of audio behind frame i and so arrives later than EEG frame
+  i:
+
+      eeg = front.push(raw)
+      env = audio.push(pcm)
+      result = decoder.push(*join.push(eeg, env[..., 0], env[..., 1]))
+
+  push(*blocks) takes every stream's newly emitted frames (any count, possibly none) and returns, per stream, the
+  frames no earlier call has returned, up to the smallest count any stream has delivered so far; the rest waits
+  inside the object.  Frames lie along `axis` (1: the banks' [S, m, ...] layout, the default; 0 for one session's
+  [m, ...]).  Host arrays stay host arrays and device tensors stay on the device: nothing is copied to the host."""
+
+  def __init__(self, num_streams, axis=1):
+    if int(num_streams) < 1:
+      raise ValueError('FrameJoin needs at least one stream.')
+    self.num_streams, self.axis = int(num_streams), int(axis)
+    self.reset()
+
+  def reset(self):
+    self._wait = [None] * self.num_streams       # what each stream delivered beyond the frames returned
+    self.frames_returned = 0
+    self.frames_delivered = [0] * self.num_streams
+
+  def _count(self, block):
+    return 0 if block is None else int(block.shape[self.axis])
+
+  def _cut(self, block, lo, hi):
+    if hasattr(block, 'narrow'):
+      return block.narrow(self.axis, lo, hi - lo)
+    index = [slice(None)] * len(block.shape)
+    index[self.axis] = slice(lo, hi)
+    return block[tuple(index)]
+
+  def _append(self, waiting, block):
+    if self._count(waiting) == 0:
+      return block
+    if self._count(block) == 0:
+      return waiting
+    if hasattr(waiting, 'narrow') and hasattr(block, 'narrow'):
+      return device._torch().cat([waiting, block], dim=self.axis)
+    return np.concatenate([np.asarray(waiting), np.asarray(block)], axis=self.axis)
+
+  def push(self, *blocks):
+    """The frames every stream has now, not returned before: a tuple of num_streams blocks of one frame count."""
+    if len(blocks) != self.num_streams:
+      raise ValueError('FrameJoin.push takes %d blocks, one per stream, not %d.' % (self.num_streams, len(blocks)))
+    for i, block in enumerate(blocks):
+      if len(block.shape) <= self.axis:
+        raise ValueError('Stream %d: a block of shape %s has no axis %d.' % (i, tuple(block.shape), self.axis))
+      self._wait[i] = self._append(self._wait[i], block)
+      self.frames_delivered[i] += self._count(block)
+    m = min(self._count(w) for w in self._wait)
+    out = tuple(self._cut(w, 0, m) for w in self._wait)
+    self._wait = [self._cut(w, m, self._count(w)) for w in self._wait]
+    self.frames_returned += m
+    return out
+
+  def flush(self, *blocks):
+    """The end: push(*blocks) when the streams' last blocks are given (their flush() outputs), then
+    FrameJoinFlush(blocks: the common rest, beyond: how many frames each stream had beyond it -- they are dropped)."""
+    if blocks:
+      out = self.push(*blocks)
+    elif any(w is None for w in self._wait):
+      raise ValueError('FrameJoin.flush before any push needs the blocks.')
+    else:
+      out = tuple(self._cut(w, 0, 0) for w in self._wait)
+    beyond = [self._count(w) for w in self._wait]
+    self._wait = [self._cut(w, 0, 0) for w in self._wait]
+    return FrameJoinFlush(out, beyond)
