@@ -672,10 +672,22 @@ def shrunk_covariance(moments, n, scale, diag, want64=True, want32=True, handle=
 WINDOW_SUMS_CYCLED = True      # window_sums takes a `b` with fewer columns than `a` (td_window_sums_cycled)
 
 
+def _check_unit_columns(who, **tensors):
+  """The window kernels take a row stride and step 1 from column to column: a transposed or column-strided view
+  would be read as if its columns were adjacent.  (A single column has no step to get wrong.)"""
+  for name, t in tensors.items():
+    if t.dim() != 2:
+      raise ValueError('%s: %s must have two dimensions, not %d' % (who, name, t.dim()))
+    if int(t.shape[1]) > 1 and t.stride(1) != 1:
+      raise ValueError('%s: the columns of %s must be contiguous (column stride %d)' % (who, name, t.stride(1)))
+
+
 def window_sums(a, b, trial_offsets, width, hop, handle=None):
   """Five float64 sums per window and column: [n_windows, cols, 5].  b may hold fewer columns than a (a
   divisor of a's): column j of a is then paired with column j % b.shape[1] of b (td_window_sums_cycled: several
-  models' predictions against one truth, no tiled copy of the truth)."""
+  models' predictions against one truth, no tiled copy of the truth).  a, b: unit column stride, row stride
+  free."""
+  _check_unit_columns('window_sums', a=a, b=b)
   h = handle or default_handle()
   cols, b_cols = int(a.shape[1]), int(b.shape[1])
   _, total = window_layout(trial_offsets, width, hop)
@@ -716,7 +728,8 @@ def window_scores(sums, width, mode, reduction='first', mean_a=None, mean_b=None
 
 def frame_scores(a, b, reduction, mean_a, mean_b, power, lda_w=None, lda_slope=1.0,
                  lda_intercept=0.0, handle=None):
-  """Per-frame reduced correlation score (Decoder.infer_one)."""
+  """Per-frame reduced correlation score (Decoder.infer_one).  a, b: unit column stride, row stride free."""
+  _check_unit_columns('frame_scores', a=a, b=b)
   h = handle or default_handle()
   if reduction not in REDUCTIONS:
     raise ValueError('Unknown reduction technique: %s' % reduction)
@@ -759,6 +772,7 @@ def window_class_moments(a, b, width, mean_a, mean_b, power, want_means=False, h
   [rows, cols] with unit column stride (row stride free), cols <= 32, width >= 2.  Returns the float64
   device tensor [cols + 1, cols + 1], or (moments, means [rows // width, cols]) with want_means.  Queued,
   not waited for."""
+  _check_unit_columns('window_class_moments', a=a, b=b)
   h = handle or default_handle()
   rows, cols = int(a.shape[0]), int(a.shape[1])
   if tuple(b.shape) != (rows, cols):
@@ -768,8 +782,6 @@ def window_class_moments(a, b, width, mean_a, mean_b, power, want_means=False, h
     if t.dtype != torch.float32 or t.device != h.device:
       raise TypeError('window_class_moments: %s must be a float32 tensor on %s, not %s on %s' %
                       (name, h.device, t.dtype, t.device))
-  if cols > 1 and (a.stride(1) != 1 or b.stride(1) != 1):
-    raise ValueError('window_class_moments: the columns of a and b must be contiguous')
   width = int(width)
   if rows == 0 and 1 <= cols <= WINDOW_CLASS_MOMENTS_MAX_COLS and width >= 2:
     # (an empty tensor has no address to hand to the kernel: no window, all-zero moments)

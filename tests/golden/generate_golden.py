@@ -325,6 +325,35 @@ def g7_decoders():
   save('g7_decoders', **out)
 
 
+def g7b_decoder_lags():
+  """The state-space decoder at the lags, iteration counts and offsets of tests/window_edges.py (G7 has the
+  defaults only: forward_lag 0, backward_lag 13): per case the stream, the settings and the reference's [60, 3]
+  trajectory; the tuned priors where the case tunes."""
+  import io
+  import contextlib
+  from tests import window_edges as we
+  out = {}
+  for case in we.SSD_CASES:
+    k_f, k_b, setting = case
+    outer, inner, newton, offset, tuned = we.SETTINGS[setting]
+    c = we.ssd_stream(k_f, k_b)
+    with contextlib.redirect_stdout(io.StringIO()):
+      dec = ref_ad.StateSpaceAttentionDecoder(outer, inner, newton, 1.0, forward_lag=k_f, backward_lag=k_b,
+                                              offset=offset)
+    key = we.ssd_key(case)
+    if tuned:
+      dec.tune(c[:we.TUNE_WINDOWS, 0], c[:we.TUNE_WINDOWS, 1])
+      out[key + '_mu_d_tuned'] = np.array(dec.mu_d)
+      out[key + '_rho_d_tuned'] = np.array(dec.rho_d)
+    with np.errstate(all='raise'):
+      traj = np.array([dec.attention(a, b) for a, b in c], np.float64)
+    assert traj.shape == (we.SSD_WINDOWS, 3) and np.all(np.isfinite(traj))
+    out[key + '_corr'] = c
+    out[key + '_settings'] = np.array([outer, inner, newton, k_f, k_b, offset, float(tuned)])
+    out[key + '_traj'] = traj
+  save('g7b_decoder_lags', **out)
+
+
 # ----------------------------------------------------------------- G8 LDA
 def g8_lda():
   import io
@@ -691,6 +720,7 @@ if __name__ == '__main__':
   g5_correlator()
   g6_windows()
   g7_decoders()
+  g7b_decoder_lags()
   g8_lda()
   g9_end_to_end()
   g10_decoder_train()

@@ -10,6 +10,7 @@ from oracle import lag as o_lag
 from oracle import lda as o_lda
 from oracle import pearson as o_p
 from oracle import regression as o_reg
+from tests import window_edges as we
 from tests.conftest import golden
 
 
@@ -228,6 +229,29 @@ def test_g7_ssd(name, tune, offset):
     est = traj[:, 0] < 0.5    # p = P(speaker 1 attended); state 2 <=> speaker 2
     err = np.mean(est[14:] != (state[14:] == 2))
     assert err < 0.15
+
+
+@pytest.mark.parametrize('case', we.SSD_CASES, ids=we.ssd_id)
+def test_g7b_ssd_at_other_lags(case):
+  """The oracle's StateSpace takes the lags, iteration counts and offset as arguments: pinned to the reference's
+  decoder at every entry of the table of tests/window_edges.py (kw from 1 to 32, forward lags, other counts)."""
+  g = golden('g7b_decoder_lags')
+  key = we.ssd_key(case)
+  c = g[key + '_corr']
+  np.testing.assert_array_equal(c, we.ssd_stream(case[0], case[1]))
+  kw = we.ssd_kwargs(case)
+  np.testing.assert_array_equal(g[key + '_settings'], [kw['outer_iter'], kw['inner_iter'], kw['newton_iter'],
+                                                      case[0], case[1], kw['offset'], we.SETTINGS[case[2]][4]])
+  if we.SETTINGS[case[2]][4]:
+    rho_d, mu_d = we.ssd_prior(case)
+    np.testing.assert_array_equal(mu_d, g[key + '_mu_d_tuned'])
+    np.testing.assert_array_equal(rho_d, g[key + '_rho_d_tuned'])
+  traj = we.ssd_oracle(case)
+  assert traj.shape == (we.SSD_WINDOWS, 3)
+  np.testing.assert_allclose(traj, g[key + '_traj'], rtol=1e-12, atol=1e-14)
+  # the first kw - 1 calls return 0.5 (attention_decoder.py:451), the kw-th is an estimate
+  first = case[0] + case[1]
+  assert np.all(traj[:first] == 0.5) and not np.all(traj[first] == 0.5)
 
 
 def test_g8_lda():
