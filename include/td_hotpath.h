@@ -324,6 +324,14 @@ int td_set_option(td_handle* h, const char* name, int64_t value);
  * x 1.25 and never shrinks; the workspace arena of "reserve_workspace" is separate). */
 int td_scratch_bytes(td_handle* h, int64_t* bytes);
 int td_last_solve_info(td_handle* h, int* solver, int* iterations, int* cg_status);
+/* Which conjugate-gradient kernel the last td_ridge_solve / td_ridge_solve_async on this handle LAUNCHED
+ * (recorded at the point of launch, cleared at the start of every ridge solve; a launch that then gave up
+ * -- td_last_solve_info says 'cholesky' -- is still reported): *kernel TD_CG_KERNEL_NONE / _RESIDENT (dense
+ * matrix in LDS) / _COMPACT (compact statistics), *param the rows per workgroup R = 1..8 of the resident
+ * kernel or the channels per workgroup 1 / 2 of the compact one (0 for none), *workgroups the grid.  Any
+ * pointer may be NULL.  No reference counterpart. */
+enum { TD_CG_KERNEL_NONE = 0, TD_CG_KERNEL_RESIDENT = 1, TD_CG_KERNEL_COMPACT = 2 };
+int td_last_cg_plan(td_handle* h, int* kernel, int* param, int* workgroups);
 /* The same without waiting for the device.  *singular_flag_host points at a pinned host int
  * owned by the handle (a ring of 8: read it before the 8th later call; a call that would reuse a
  * slot whose solve has not finished yet -- more than 8 solves outstanding, nobody can have read

@@ -111,6 +111,7 @@ SIGNATURES = {
     'td_set_option': [_vp, _c.c_char_p, _i64],
     'td_scratch_bytes': [_vp, _pi64],
     'td_last_solve_info': [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)],
+    'td_last_cg_plan': [_vp, _c.POINTER(_i), _c.POINTER(_i), _c.POINTER(_i)],
     'td_ridge_solve_async': [_vp, _vp, _pd, _i, _vp, _vp, _vp],
     'td_ridge_solve_multi': [_vp, _c.POINTER(_vp), _i, _pd, _i, _vp, _vp, _vp],
     'td_ridge_solve_loso': [_vp, _vp, _c.POINTER(_vp), _i, _pd, _i, _i, _d, _vp, _vp, _c.POINTER(_i),

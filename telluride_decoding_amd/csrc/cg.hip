@@ -960,6 +960,7 @@ int td_cg_solve_dense(td_handle* h, const double* xtx, int n, int ld, const doub
     default: rc = launch_cg<8>(h, p, wgs, lds, cus); break;
   }
   if (rc != TD_OK) return rc;              // (TD_CG_NOT_RESIDENT: nothing was queued)
+  h->last_cg_kernel = TD_CG_KERNEL_RESIDENT; h->last_cg_param = rows; h->last_cg_wgs = wgs;
   TD_HIP(h, hipGetLastError());
   return TD_OK;
 }
@@ -1026,6 +1027,7 @@ int td_cg_solve_compact(td_handle* h, const StatsCompact& sc, const double* lams
   p.limit_ticks = 100000LL * 20;
   if (h->cg_limit_ticks >= 0) p.limit_ticks = h->cg_limit_ticks;
   h->cgt_epoch += rounds;
+  h->last_cg_kernel = TD_CG_KERNEL_COMPACT; h->last_cg_param = cpw; h->last_cg_wgs = (C + cpw - 1) / cpw;
   if (cpw == 1)
     hipLaunchKernelGGL(cg_toeplitz_kernel<1>, dim3((unsigned)C), dim3(kCgThreads), lds_bytes(1), h->stream, p);
   else

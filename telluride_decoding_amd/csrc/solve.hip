@@ -1407,6 +1407,7 @@ static int ridge_solve_impl(td_handle* h, td_stats* s, const double* lambdas_hos
                             float* w_dev, float* b_dev, int* flag_dev) {
   if (!h || !s || !lambdas_host || !w_dev || !b_dev)
     return td_fail(h, TD_ERR_INVALID, "td_ridge_solve: NULL argument");
+  h->last_cg_kernel = TD_CG_KERNEL_NONE; h->last_cg_param = 0; h->last_cg_wgs = 0;
   int k1 = 0, d = 0;
   int64_t frames = 0;
   td_stats_layout(s, &k1, &d, &frames);
@@ -1569,6 +1570,14 @@ int td_last_solve_info(td_handle* h, int* solver, int* iterations, int* cg_statu
   if (solver) *solver = h->last_solver;
   if (iterations) *iterations = h->last_iterations;
   if (cg_status) *cg_status = h->last_cg_status;
+  return TD_OK;
+}
+
+int td_last_cg_plan(td_handle* h, int* kernel, int* param, int* workgroups) {
+  if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_last_cg_plan: NULL handle");
+  if (kernel) *kernel = h->last_cg_kernel;
+  if (param) *param = h->last_cg_param;
+  if (workgroups) *workgroups = h->last_cg_wgs;
   return TD_OK;
 }
 

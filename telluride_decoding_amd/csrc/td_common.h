@@ -96,6 +96,9 @@ struct td_handle {
   int narrow16 = 1;             // "narrow16": <= 16 channels take the one-kernel streaming accumulate (0: the tiled kernels)
   int targets_f16 = 1;          // "targets_f16": 33 .. 64 channels per tile take the float16 targets kernel (0: the float32 one)
   int last_solver = 0, last_iterations = 0, last_cg_status = 0;
+  // which conjugate-gradient kernel the last ridge solve LAUNCHED (td_last_cg_plan): TD_CG_KERNEL_*, its
+  // R (resident) or channels per workgroup (compact), its workgroup count
+  int last_cg_kernel = 0, last_cg_param = 0, last_cg_wgs = 0;
   // Optional per-kernel hipEvent timing of the dominant kernel (td_profile_*):
   // event pairs recorded on h->stream around every lagcov MFMA launch.
   bool profile = false;

@@ -101,6 +101,16 @@ class Handle(object):
     return {'solver': {1: 'cholesky', 2: 'cg'}.get(s.value, 'none'), 'iterations': int(it.value),
             'cg_status': int(st.value)}
 
+  def last_cg_plan(self):
+    """Which conjugate-gradient kernel the last ridge solve on this handle launched (td_last_cg_plan; cleared at
+    the start of every ridge solve): {'kernel': 'resident' | 'compact' | 'none', 'rows': R of the resident kernel
+    or 0, 'channels_per_workgroup': 1 / 2 of the compact kernel or 0, 'workgroups': n}."""
+    kn, pr, wg = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    self.check(self.lib.td_last_cg_plan(self.ptr, ctypes.byref(kn), ctypes.byref(pr), ctypes.byref(wg)))
+    kernel = {1: 'resident', 2: 'compact'}.get(kn.value, 'none')
+    return {'kernel': kernel, 'rows': int(pr.value) if kernel == 'resident' else 0,
+            'channels_per_workgroup': int(pr.value) if kernel == 'compact' else 0, 'workgroups': int(wg.value)}
+
   def timer_start(self):
     self.check(self.lib.td_timer_start(self.ptr))
 

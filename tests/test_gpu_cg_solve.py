@@ -11,6 +11,7 @@ import pytest
 
 from oracle import lag as o_lag
 from oracle import regression as o_reg
+from tests import cg_edges
 from tests import parity_log
 
 pytestmark = pytest.mark.gpu
@@ -238,19 +239,7 @@ def test_async_flag_ring_overrun_is_an_error(dev):
   assert flag() == 0 and np.all(np.isfinite(w.cpu().numpy()))
 
 
-def _masked_handle(dev, cus=64):
-  """A handle on a stream masked to the first `cus` CUs (the solve partition of a pipelined fit)."""
-  import ctypes
-  import torch
-  from telluride_decoding_amd import _lib
-  lib = _lib.load()
-  p = ctypes.c_void_p()
-  assert lib.td_stream_create_masked(0, 0, cus, ctypes.byref(p)) == 0
-  stream = torch.cuda.ExternalStream(p.value)
-  with torch.cuda.stream(stream):
-    h = dev.Handle()
-  h.check(lib.td_set_cu_count(h.ptr, cus))
-  return h, stream, (lib, p)
+_masked_handle = cg_edges.masked_handle      # (a handle on a stream masked to the first 64 CUs)
 
 
 @pytest.mark.parametrize('c,post,frames,files,lams,d', [
