@@ -1064,6 +1064,74 @@ int td_audio_online_push(td_handle* h, int num_sessions, const void* x_dev, int 
                          int64_t state_session_stride, int live, float* out32_dev, double* out64_dev, int64_t ldout,
                          int64_t out_session_stride, int64_t* windows_dev);
 
+/* ------------------------------------------------------------------ online ridge fit
+ * The training stage of the online chain: the exact moments of the lagged regression for (eeg, target) rows that
+ * arrive in pushes of any length -- `num_sessions` independent sessions, one state block each on the device, advanced
+ * by ONE launch per push -- and ridge weights from them on demand.  However a recording is cut into pushes, the state
+ * is that of one push of the whole recording, bit for bit.
+ *
+ * Frames.  c channels, context (pre, post), lags = pre + 1 + post, K = lags c, d outputs.  The lagged vector v of
+ * frame t has v[l c + ch] = x[t + l - pre][ch], zero outside the recording, and v[K] = 1 (the reference's ones
+ * column, brain_model.py:434-436).  Frames are emitted `post` rows late, as td_online_push emits them: after
+ * `pushed` rows, emitted = max(0, pushed - post); a push that carries flush emits the rest with `post` zero rows
+ * behind the end.
+ *
+ * The sum.  For every newly emitted frame, in frame order, with the forgetting factor g = forget:
+ *   A[i][j] = A[i][j] g + v[i] v[j]     (K + 1) x (K + 1) float64
+ *   B[i][o] = B[i][o] g + v[i] y[t][o]  (K + 1) x d       float64
+ * The inputs are float32, so a product is exact.  g == 1: one rounding per frame and element (acc + p).  g < 1: two,
+ * round(round(acc g) + p).  The order is a function of the frame index alone, so NumPy's A * g + np.outer(v, v) in
+ * frame order gives the same bits.  A[K][K] is the frame count (g == 1) or the effective count (g < 1).
+ *
+ * State (td_fit_online_state_bytes; all zeros = a fresh session): A as a full square of float64 of which the launch
+ * computes and stores the 64 x 64 tiles (ti, tj) with tj >= ti only (a diagonal tile whole) -- the lower tiles stay
+ * zero, td_fit_online_moments mirrors --, B, then TWO tail copies of {EEG [pre + post][c], target [post][d]} float32,
+ * slot j holding row pushed - (pre + post) + j (target: pushed - post + j), zero before row 0.  A launch reads copy
+ * (pushes_before & 1) and one workgroup per session writes every slot of the other one; pushes_before counts the
+ * pushes with n > 0 (the HOST counts frames and pushes; a push without rows writes no tail).
+ *
+ * td_fit_online_push: the sessions' next n rows.
+ *   eeg_dev     [S][n][c] float32, row stride ld_eeg, session stride eeg_session_stride (elements)
+ *   target_dev  [S][n][d] float32, row stride ld_target, session stride target_session_stride (elements)
+ *   n >= 0      (n == 0 with no frame to emit: nothing is queued); a push that emits nothing still rolls the tails
+ *   frames_before   rows pushed so far;  flush != 0: the recording ends behind this push
+ *   state_dev, state_session_stride (BYTES, a multiple of 8, >= td_fit_online_state_bytes)
+ * grid: sessions x (upper-triangular tiles of A + the 64-row tiles of B + the tail workgroup), 256 threads, a 4 x 4
+ * block of float64 accumulators per thread.  No workgroup reads what another writes, no atomics, vector stores only:
+ * two runs give the same bits.  With td_profile_enable the launch is bracketed as td_online_push's is.
+ *
+ * td_fit_online_moments: xtx_dev [S][K + 1][K + 1] and xty_dev [S][K + 1][d] float64 (either may be NULL, not both),
+ * mirrored and dense, in the layout of td_stats_moments (the ones row / column last).
+ *
+ * td_fit_online_solve: ridge weights for every (session, lambda): the systems A_sym / A[K][K] + lambda I (the
+ * reference's cov_x, lambda on the bias entry too: brain_model.py:447-455) and B / A[K][K] are built in one launch,
+ * td_spd_solve solves them (batched float64 Cholesky in the handle's solver workspace), one more launch writes
+ * w_dev [S][n_lambda][K][d] and b_dev [S][n_lambda][d] float32.  frames_emitted: the host's count of emitted frames.
+ * Synchronous.  TD_ERR_STATE: no frame emitted yet (never a division by zero).  TD_ERR_NOMEM: the dense systems need
+ * more than TD_ONLINE_FIT_MAX_SOLVE_BYTES.  TD_ERR_SINGULAR: a system is not positive definite, as td_ridge_solve.
+ *
+ * TD_ERR_INVALID, before anything is queued and with the state untouched: a NULL required pointer, num_sessions
+ * outside 1..65535, c outside 1..TD_ONLINE_FIT_MAX_CHANNELS, pre or post < 0, more than TD_ONLINE_FIT_MAX_LAGS lags,
+ * K above TD_ONLINE_FIT_MAX_K, d outside 1..TD_ONLINE_FIT_MAX_OUTPUTS, n outside 0..TD_ONLINE_MAX_PUSH, forget
+ * outside (0, 1], frames_before or pushes_before < 0, a row or session stride below a row, a state stride below
+ * the state block or not a multiple of 8, n_lambda < 1 or more than 65535 systems, a lambda that is not finite. */
+#define TD_ONLINE_FIT_MAX_CHANNELS 128
+#define TD_ONLINE_FIT_MAX_LAGS 64
+#define TD_ONLINE_FIT_MAX_K 2048
+#define TD_ONLINE_FIT_MAX_OUTPUTS 8
+#define TD_ONLINE_FIT_MAX_SOLVE_BYTES (4LL << 30)
+int td_fit_online_state_bytes(int c, int pre, int post, int d, int64_t* bytes);
+int td_fit_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t ld_eeg,
+                       int64_t eeg_session_stride, const float* target_dev, int64_t ld_target,
+                       int64_t target_session_stride, int64_t n, int c, int pre, int post, int d,
+                       int64_t frames_before, int64_t pushes_before, int flush, double forget, void* state_dev,
+                       int64_t state_session_stride);
+int td_fit_online_moments(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride, int c,
+                          int pre, int post, int d, double* xtx_dev, double* xty_dev);
+int td_fit_online_solve(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride, int c,
+                        int pre, int post, int d, int64_t frames_emitted, const double* lambdas_host, int n_lambda,
+                        float* w_dev, float* b_dev);
+
 /* ------------------------------------------------------------------ ingestion
  * ingest.find_mean_std, ingest.normalize_data and ingest.convert_data_to_tfrecords (ingest.py:1061-1172).
  *

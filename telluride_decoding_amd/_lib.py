@@ -191,6 +191,14 @@ SIGNATURES = {
     # state, stride, live | out32, out64, ld, stride | windows
     'td_audio_online_push': [_vp, _i] + [_vp, _i, _i64, _i64] + [_i64, _i] + [_i64, _i] + [_d, _d, _d, _d] +
                             [_vp, _i64, _i] + [_vp, _vp, _i64, _i64] + [_vp],
+    'td_fit_online_state_bytes': [_i, _i, _i, _i, _pi64],
+    # h, sessions | eeg, ld, stride | target, ld, stride | n, c, pre, post, d | frames_before, pushes_before, flush |
+    # forget | state, stride
+    'td_fit_online_push': [_vp, _i] + [_vp, _i64, _i64] * 2 + [_i64, _i, _i, _i, _i] + [_i64, _i64, _i] + [_d] +
+                          [_vp, _i64],
+    'td_fit_online_moments': [_vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp],
+    # h, sessions | state, stride | c, pre, post, d | frames_emitted | lambdas, n_lambda | w, b
+    'td_fit_online_solve': [_vp, _i, _vp, _i64, _i, _i, _i, _i, _i64, _pd, _i, _vp, _vp],
     'td_ingest_moments': [_vp, _c.POINTER(_vp), _pi64, _pi64, _c.POINTER(_i), _i, _i, _vp],
     'td_ingest_normalize': [_vp, _vp, _i, _i64, _i64, _i, _pd, _pd, _i, _i, _i, _i, _vp, _i64],
     'td_tfrecord_encode': [_vp, _c.c_char_p, _i, _i, _c.POINTER(_vp), _pi64, _c.POINTER(_i), _c.POINTER(_i),

@@ -1855,6 +1855,98 @@ def audio_online_push(x, fs_in, fs_out, window, exponent, state, live, rows_befo
                          1 - int(live) if rows else int(live))
 
 
+# ---------------------------------------------------------------- online ridge fit
+# td_fit_online_push's limits
+ONLINE_FIT_MAX_CHANNELS, ONLINE_FIT_MAX_LAGS, ONLINE_FIT_MAX_K, ONLINE_FIT_MAX_OUTPUTS = 128, 64, 2048, 8
+
+
+def online_fit_state_bytes(c, pre, post, d):
+  """Bytes of one online fit session's state block (td_fit_online_state_bytes): A [(K + 1)^2] and B [(K + 1) d]
+  float64, then two tail copies of {EEG [pre + post, c], target [post, d]} float32; all zeros = a fresh session."""
+  n = ctypes.c_int64(0)
+  _lib.check(None, _lib.load().td_fit_online_state_bytes(int(c), int(pre), int(post), int(d), ctypes.byref(n)))
+  return int(n.value)
+
+
+def _check_fit_state(who, h, state):
+  if state.dtype != _torch().uint8 or state.device != h.device or state.dim() != 2:
+    raise TypeError('%s: state must be a [S, bytes] uint8 tensor on %s, not %s %s on %s' %
+                    (who, h.device, tuple(state.shape), state.dtype, state.device))
+  sessions = int(state.shape[0])
+  return sessions, int(state.stride(0)) if sessions > 1 else int(state.shape[1])
+
+
+def online_fit_push(eeg, target, state, frames_before, pushes_before, pre, post, c=None, d=None, flush=False,
+                    forget=1.0, handle=None):
+  """One push of a bank of online fit sessions, in one launch (td_fit_online_push).
+
+  eeg [S, n, c] and target [S, n, d]: float32 device tensors with unit column stride (None for a flush without
+  rows: give c and d); state: uint8 device tensor [S, >= online_fit_state_bytes()] with a row stride that is a
+  multiple of 8, updated in place; frames_before: rows pushed so far; pushes_before: pushes WITH rows so far (its
+  parity says which tail copy is live).  Returns the rows pushed after the call.  Queued, not waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  sessions, stride = _check_fit_state('online_fit_push', h, state)
+  n = 0 if eeg is None else int(eeg.shape[1])
+  if eeg is not None:
+    if eeg.dim() != 3 or target is None or target.dim() != 3 or int(eeg.shape[0]) != sessions or \
+        tuple(target.shape[:2]) != (sessions, n):
+      raise ValueError('online_fit_push: eeg of %s and target of %s for %d sessions' %
+                       (tuple(eeg.shape), None if target is None else tuple(target.shape), sessions))
+    c, d = int(eeg.shape[2]), int(target.shape[2])
+    for name, t in (('eeg', eeg), ('target', target)):
+      if t.dtype != torch.float32 or t.device != h.device:
+        raise TypeError('online_fit_push: %s must be a float32 tensor on %s, not %s on %s' %
+                        (name, h.device, t.dtype, t.device))
+    if n > 0 and (eeg.stride(2) != 1 and c > 1 or target.stride(2) != 1 and d > 1):
+      raise ValueError('online_fit_push: the columns of eeg and target must be contiguous')
+  if c is None or d is None:
+    raise ValueError('online_fit_push: a flush without rows needs the channel count c and the output count d')
+  c, d = int(c), int(d)
+  rows = n > 0
+  h.check(h.lib.td_fit_online_push(
+      h.ptr, sessions,
+      _ptr(eeg if rows else None), int(eeg.stride(1)) if rows and n > 1 else c,
+      int(eeg.stride(0)) if rows and sessions > 1 else max(n, 1) * c,
+      _ptr(target if rows else None), int(target.stride(1)) if rows and n > 1 else d,
+      int(target.stride(0)) if rows and sessions > 1 else max(n, 1) * d,
+      n, c, int(pre), int(post), d, int(frames_before), int(pushes_before), 1 if flush else 0, float(forget),
+      _ptr(state), stride))
+  return int(frames_before) + n
+
+
+def online_fit_moments(state, c, pre, post, d, handle=None):
+  """(xtx [S, K + 1, K + 1], xty [S, K + 1, d]) float64 device tensors: the mirrored dense moments of a bank of
+  online fit sessions in the layout of LagStats.moments (td_fit_online_moments)."""
+  h = handle or default_handle()
+  sessions, stride = _check_fit_state('online_fit_moments', h, state)
+  n1 = (int(pre) + 1 + int(post)) * int(c) + 1
+  if not 1 <= n1 - 1 <= ONLINE_FIT_MAX_K:       # (the call refuses it by name; no tensor of a wild size first)
+    n1 = 1
+  xtx = h.empty((sessions, n1, n1), 'float64')
+  xty = h.empty((sessions, n1, max(int(d), 1)), 'float64')
+  h.check(h.lib.td_fit_online_moments(h.ptr, sessions, _ptr(state), stride, int(c), int(pre), int(post), int(d),
+                                      _ptr(xtx), _ptr(xty)))
+  return xtx, xty
+
+
+def online_fit_solve(state, c, pre, post, d, frames_emitted, lambdas, handle=None):
+  """Ridge weights of every (session, lambda) from a bank's moments (td_fit_online_solve): device tensors
+  W [S, n_lambda, K, d] and b [S, n_lambda, d] float32.  ValueError / HotPathError (no frame emitted yet) /
+  MemoryError (the dense systems over the limit) / numpy.linalg.LinAlgError (not positive definite)."""
+  h = handle or default_handle()
+  sessions, stride = _check_fit_state('online_fit_solve', h, state)
+  lam, lam_p = _lib.f64_array(np.atleast_1d(lambdas))
+  k = (int(pre) + 1 + int(post)) * int(c)
+  if not 1 <= k <= ONLINE_FIT_MAX_K or not 1 <= int(d) <= ONLINE_FIT_MAX_OUTPUTS:
+    k = 1
+  w = h.empty((sessions, len(lam), k, max(int(d), 1)), 'float32')
+  b = h.empty((sessions, len(lam), max(int(d), 1)), 'float32')
+  h.check(h.lib.td_fit_online_solve(h.ptr, sessions, _ptr(state), stride, int(c), int(pre), int(post), int(d),
+                                    int(frames_emitted), lam_p, len(lam), _ptr(w), _ptr(b)))
+  return w, b
+
+
 # ---------------------------------------------------------------- fully connected regressor / match-mismatch classifier
 MLP_LOSSES = {'mse': 0, 'pearson': 1}
 

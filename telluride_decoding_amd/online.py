@@ -56,6 +56,14 @@ up, on the device:
     env = audio.push(pcm)                        # [S, m, 2] float32
     result = online.push(*join.push(eeg, env[..., 0], env[..., 1]))
 
+The model itself can come from the chain: `OnlineRidgeFit` takes (eeg, target) rows in pushes of any length and
+keeps the exact float64 moments of the lagged ridge regression in ONE td_fit_online_push launch per push;
+`solve(lambdas)` gives ridge weights on the device and `OnlineDecoder.set_weights` takes them between pushes:
+
+    fit.push(eeg, attended_envelope)             # during calibration, any chunk length
+    w, b = fit.solve([0.1])
+    online.set_weights(w[:, 0, :, 0], b[:, 0, 0])
+
 Without a GPU (`device.gpu_available()` false) the same object runs a NumPy session with the same
 semantics -- float64 throughout, window sums in frame order, td_online_plan's arithmetic -- so that the logic can
 be built and tested anywhere.  (The state-space decoder has no host form: 'ssd' needs the GPU.)
@@ -613,6 +621,41 @@ class OnlineDecoder(object):
       base = int(state.shape[1]) - 8
       state[:, base + 1:base + 5] = torch.tensor([rho_a, rho_u, mu_a, mu_u], dtype=torch.float64,
                                                  device=state.device)
+
+  def set_weights(self, w, b):
+    """Replaces the weights of a LINEAR bank in place, between pushes: w [K] (every session takes it) or [S, K],
+    b a scalar or [S], K = lags x channels in (lag, channel) order -- device tensors (copied device to device, no
+    host copy: what OnlineRidgeFit.solve returns, sliced) or arrays.  A bank that shared one model copy holds S
+    copies afterwards when S rows are given.  The session state, the score ring and the correlation statistics are
+    untouched: the next push predicts with the new weights and scores them with the decoder's TRAINED statistics.
+    Re-estimating those statistics, or the LDA, online is out of scope: a decoder whose predictions change scale
+    needs them from a batch run (infer_decoder)."""
+    if self.kind != 'linear':
+      raise ValueError('OnlineDecoder.set_weights replaces the weights of a linear bank only, not of a %s bank.' %
+                       self.kind)
+    s, k = self.sessions, (self.pre + 1 + self.post) * self.channels
+    w_shape, b_shape = tuple(w.shape), tuple(np.shape(b)) if not hasattr(b, 'is_cuda') else tuple(b.shape)
+    rows = s if len(w_shape) == 2 else 1
+    if w_shape not in ((k,), (s, k)) or b_shape not in (((), (1,)) if rows == 1 else ((s,),)):
+      raise ValueError('OnlineDecoder.set_weights takes w [%d] with a scalar b, or w [%d, %d] with b [%d], not w %s '
+                       'with b %s.' % (k, s, k, s, w_shape, b_shape))
+    if not self._on_device:
+      w = np.asarray(w.cpu() if hasattr(w, 'cpu') else w, np.float32).reshape(rows, k)
+      b = np.asarray(b.cpu() if hasattr(b, 'cpu') else b, np.float32).reshape(rows)
+      for i, p in enumerate(self._params):
+        p['w'], p['b'] = w[i % rows].copy(), np.float32(b[i % rows])
+      return
+    # (the device bank is the truth from here on: self._params keeps what the bank was built from)
+    d = self._dev
+    torch = device._torch()
+    conv = lambda a, shape: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a, np.float32))).to(
+        device=d['h'].device, dtype=torch.float32).reshape(shape)
+    w, b = conv(w, (rows, k)), conv(b, (rows,))
+    if rows > int(d['w'].shape[0]):              # one shared copy becomes S copies
+      d['w'], d['b'] = w.clone().contiguous(), b.clone().contiguous()
+    else:
+      d['w'].copy_(w.expand_as(d['w']))
+      d['b'].copy_(b.expand_as(d['b']))
 
   # -- pushes ------------------------------------------------------------------------------------
   def _as_bank(self, eeg, env1, env2):
@@ -1429,3 +1472,268 @@ class FrameJoin(object):
     beyond = [self._count(w) for w in self._wait]
     self._wait = [self._cut(w, 0, 0) for w in self._wait]
     return FrameJoinFlush(out, beyond)
+
+
+# ------------------------------------------------------------------------------------------------ the online fit
+MAX_FIT_PUSH = 1048576                     # TD_ONLINE_MAX_PUSH
+
+
+def _check_fit_shape(who, c, pre, post, d, g):
+  """td_fit_online_push's limits, refused by name (the device call repeats them)."""
+  if not 1 <= c <= device.ONLINE_FIT_MAX_CHANNELS:
+    raise ValueError('%s takes 1 to %d channels, not %d.' % (who, device.ONLINE_FIT_MAX_CHANNELS, c))
+  if pre < 0 or post < 0 or pre + 1 + post > device.ONLINE_FIT_MAX_LAGS:
+    raise ValueError('%s takes at most %d lags, not %d + 1 + %d.' % (who, device.ONLINE_FIT_MAX_LAGS, pre, post))
+  if (pre + 1 + post) * c > device.ONLINE_FIT_MAX_K:
+    raise ValueError('%s takes at most %d lagged inputs, not %d lags x %d channels = %d.' %
+                     (who, device.ONLINE_FIT_MAX_K, pre + 1 + post, c, (pre + 1 + post) * c))
+  if not 1 <= d <= device.ONLINE_FIT_MAX_OUTPUTS:
+    raise ValueError('%s takes 1 to %d outputs, not %d.' % (who, device.ONLINE_FIT_MAX_OUTPUTS, d))
+  if not 0.0 < g <= 1.0:
+    raise ValueError('%s takes a forgetting factor in (0, 1], not %r.' % (who, g))
+
+
+class _HostRidgeFitSession(object):
+  """One online fit session in NumPy: the semantics of td_fit_online_push bit for bit -- float32 rows, float64
+  moments, one A * g + outer(v, v) per emitted frame in frame order -- and np.linalg.solve for the weights."""
+
+  def __init__(self, c, pre, post, d, g):
+    self.c, self.pre, self.post, self.d, self.g = c, pre, post, d, float(g)
+    self.k = (pre + 1 + post) * c
+    self.reset()
+
+  def reset(self):
+    n1 = self.k + 1
+    self.a = np.zeros((n1, n1), np.float64)
+    self.b = np.zeros((n1, self.d), np.float64)
+    self.tail = np.zeros((self.pre + self.post, self.c), np.float32)
+    self.target_tail = np.zeros((self.post, self.d), np.float32)
+
+  def push(self, eeg, target, frames_before, flush):
+    """eeg [n, c], target [n, d] float32 behind frames_before rows; returns the frames this push emitted."""
+    c, pre, post = self.c, self.pre, self.post
+    lags, tl = pre + 1 + post, pre + post
+    after = frames_before + eeg.shape[0]
+    # rows[0] is EEG row frames_before - (pre + post), ys[0] target row frames_before - post
+    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c), np.float32)] if flush else []))
+    ys = np.concatenate([self.target_tail, target])
+    e0 = max(0, frames_before - post)
+    e1 = after if flush else max(0, after - post)
+    v = np.ones((self.k + 1,), np.float64)
+    for f in range(e0, e1):
+      i = f - frames_before + post
+      v[:self.k] = rows[i:i + lags].reshape(-1)
+      y = ys[i].astype(np.float64)
+      self.a = self.a * self.g + np.outer(v, v)
+      self.b = self.b * self.g + np.outer(v, y)
+    both = np.concatenate([self.tail, eeg])
+    self.tail = np.ascontiguousarray(both[both.shape[0] - tl:])
+    self.target_tail = np.ascontiguousarray(ys[ys.shape[0] - post:]) if post else ys[:0]
+    return max(0, e1 - e0)
+
+  def solve(self, lambdas):
+    """(W [n_lambda, K, d], b [n_lambda, d]) float64: np.linalg.solve of the reference's cov_x and cov_xy."""
+    count = self.a[self.k, self.k]
+    n1 = self.k + 1
+    sols = [np.linalg.solve(self.a / count + lam * np.identity(n1), self.b / count) for lam in lambdas]
+    return np.stack([s[:self.k] for s in sols]), np.stack([s[self.k] for s in sols])
+
+
+class OnlineRidgeFit(object):
+  """The online chain's training stage: a bank of S sessions that take (eeg, target) rows in pushes of any length
+  and keep the EXACT moments of the lagged ridge regression -- [x~ | 1]^T [x~ | 1] and [x~ | 1]^T y in float64, the
+  lagged vector that of brain_data's context, the trailing 1 the reference's ones column -- in ONE
+  td_fit_online_push launch per push, the state on the device.  Any cut of a recording gives the same bytes.
+  `solve(lambdas)` turns them into ridge weights on the device (the reference's cov_x + lambda I, lambda on the
+  bias entry too) and `OnlineDecoder.set_weights` takes those without a host copy:
+
+      fit = OnlineRidgeFit(channels=64, pre_context=0, post_context=20)
+      for eeg, attended in calibration_chunks:           # [n, 64] and [n] float32, any n
+        fit.push(eeg, attended)
+      w, b = fit.solve([0.1])                            # [1, 1, K, 1] and [1, 1, 1] device tensors
+      decoder.set_weights(w[:, 0, :, 0], b[:, 0, 0])     # device to device
+
+  A frame needs post_context rows of future EEG, so the moments run `delay` = post_context frames behind the
+  input; flush() ends the recording (zero rows behind it, like the batch route's padding) and counts the rest.
+  forgetting g in (0, 1]: every emitted frame first scales the moments by g, so a frame that is m frames old
+  weighs g^m and A[K][K] -- what solve divides by -- is the effective frame count.  The batch route
+  (`LagStats.accumulate`) treats every call's rows as whole files, padded with zeros at both ends, and so cannot be
+  called per chunk; this object is that accumulate for rows that arrive in pieces.
+
+  Refused by name: more than 128 channels, more than 64 lags, more than 2048 lagged inputs, outputs outside
+  1 .. 8, a push of more than 1048576 rows, a forgetting factor outside (0, 1].  Without a GPU the same object
+  runs a NumPy session of the same semantics, bit for bit (np.linalg.solve for the weights)."""
+
+  def __init__(self, channels, pre_context, post_context, outputs=1, num_sessions=1, forgetting=1.0):
+    c, pre, post, d = int(channels), int(pre_context), int(post_context), int(outputs)
+    g = float(forgetting)
+    _check_fit_shape('OnlineRidgeFit', c, pre, post, d, g)
+    if int(num_sessions) < 1:
+      raise ValueError('OnlineRidgeFit needs at least one session.')
+    self.channels, self.pre, self.post, self.outputs = c, pre, post, d
+    self.sessions, self.forgetting = int(num_sessions), g
+    self.lags = pre + 1 + post
+    self.inputs = self.lags * c                  # K
+    self.delay = post
+    self._on_device = device.gpu_available()
+    self._dev = self._host = None
+    if self._on_device:
+      h = device.default_handle()
+      torch = device._torch()
+      nbytes = device.online_fit_state_bytes(c, pre, post, d)
+      self._dev = dict(h=h, state=torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device))
+    else:
+      self._host = [_HostRidgeFitSession(c, pre, post, d, g) for _ in range(self.sessions)]
+    self.reset()
+
+  def reset(self):
+    """A fresh recording and empty moments: zero state (a memset), no row pushed."""
+    self.rows_pushed = self.frames = 0           # frames: the frames counted into the moments so far
+    self._pushes = 0                             # pushes with rows: its parity is the live tail copy
+    self.flushed = False
+    if self._dev is not None:
+      self._dev['state'].zero_()
+    if self._host is not None:
+      for sess in self._host:
+        sess.reset()
+
+  # -- pushes ------------------------------------------------------------------------------------
+  def _as_bank(self, eeg, target):
+    """(eeg [S, n, c], target [S, n, d]) float32: device tensors on the device, else host arrays."""
+    s, c, d = self.sessions, self.channels, self.outputs
+    if any(hasattr(a, 'is_cuda') for a in (eeg, target)):
+      torch = device._torch()
+      dev = self._dev['h'].device if self._on_device else None
+      conv = lambda a: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a))).to(
+          device=dev, dtype=torch.float32)
+      eeg, target = conv(eeg), conv(target)
+      if not self._on_device:
+        eeg, target = eeg.cpu().numpy(), target.cpu().numpy()
+    else:
+      eeg, target = np.asarray(eeg, np.float32), np.asarray(target, np.float32)
+    shapes = (tuple(eeg.shape), tuple(target.shape))
+    if len(eeg.shape) == 2 and s == 1:
+      eeg = eeg.reshape((1,) + tuple(eeg.shape))
+      if len(target.shape) <= 2:
+        target = target.reshape((1,) + tuple(target.shape))       # [1, n] or [1, n, d]
+    if len(target.shape) == 2 and d == 1:
+      target = target.reshape(tuple(target.shape) + (1,))         # [S, n] -> [S, n, 1]
+    n = int(eeg.shape[1]) if len(eeg.shape) == 3 else -1
+    if len(eeg.shape) != 3 or tuple(eeg.shape) != (s, n, c) or tuple(target.shape) != (s, n, d):
+      raise ValueError('A push is eeg [%d, n, %d] (or [n, %d] for one session) with a target [%d, n, %d] (or [n, %d] '
+                       '/ [n] for one session), not eeg %s with a target %s.' % ((s, c, c, s, d, d) + shapes))
+    if n > MAX_FIT_PUSH:
+      raise ValueError('OnlineRidgeFit takes at most %d rows in one push, not %d.' % (MAX_FIT_PUSH, n))
+    return eeg, target
+
+  def push(self, eeg, target):
+    """The next n rows of every session: eeg [n, c] / [S, n, c] and target [n] / [n, d] / [S, n, d], float32 device
+    tensors (read where they are, no host copy) or arrays; n may be 0.  Returns the frames counted so far."""
+    if self.flushed:
+      raise ValueError('The fit was flushed: reset() starts the next recording.')
+    eeg, target = self._as_bank(eeg, target)
+    return self._advance(eeg, target, False)
+
+  def flush(self, eeg=None, target=None):
+    """The end of the recording: the last post_context frames are counted as if zero rows followed -- behind the
+    recording's last rows, when they are given (one launch for both).  After it the fit refuses pushes until
+    reset(); moments() and solve() stay."""
+    if self.flushed:
+      raise ValueError('The fit was flushed: reset() starts the next recording.')
+    if (eeg is None) != (target is None):
+      raise ValueError('OnlineRidgeFit.flush takes the last rows as eeg AND target, or neither.')
+    if eeg is not None:
+      eeg, target = self._as_bank(eeg, target)
+    frames = self._advance(eeg, target, True)
+    self.flushed = True
+    return frames
+
+  def _advance(self, eeg, target, flush):
+    n = 0 if eeg is None else int(eeg.shape[1])
+    after = self.rows_pushed + n
+    counted = after if flush else max(0, after - self.post)
+    if not self._on_device:
+      if eeg is None:
+        eeg = np.zeros((self.sessions, 0, self.channels), np.float32)
+        target = np.zeros((self.sessions, 0, self.outputs), np.float32)
+      for i, sess in enumerate(self._host):
+        sess.push(eeg[i], target[i], self.rows_pushed, flush)
+    else:
+      d = self._dev
+      if n == 0:
+        eeg = target = None
+      else:
+        if eeg.stride(2) != 1 and self.channels > 1:
+          eeg = eeg.contiguous()
+        if target.stride(2) != 1 and self.outputs > 1:
+          target = target.contiguous()
+      device.online_fit_push(eeg, target, d['state'], self.rows_pushed, self._pushes, self.pre, self.post,
+                             c=self.channels, d=self.outputs, flush=flush, forget=self.forgetting, handle=d['h'])
+    self.rows_pushed = after
+    self.frames = counted
+    if n > 0:
+      self._pushes += 1
+    return self.frames
+
+  # -- what the state holds ----------------------------------------------------------------------
+  @property
+  def tails(self):
+    """(EEG tail [S, pre + post, c], target tail [S, post, d]) float32: the live copy -- slot j holds row
+    rows_pushed - (pre + post) + j (target: rows_pushed - post + j), zero before row 0.  Device tensors (views) or
+    host arrays."""
+    s, c, d, tl = self.sessions, self.channels, self.outputs, self.pre + self.post
+    if self._dev is None:
+      return (np.stack([sess.tail for sess in self._host]), np.stack([sess.target_tail for sess in self._host]))
+    n1 = self.inputs + 1
+    floats = self._dev['state'].view(device._torch().float32)
+    copy = tl * c + self.post * d
+    at = 2 * (n1 * n1 + n1 * d) + (self._pushes & 1) * copy
+    return (floats[:, at:at + tl * c].reshape(s, tl, c),
+            floats[:, at + tl * c:at + copy].reshape(s, self.post, d))
+
+  def moments(self):
+    """(xtx [S, K + 1, K + 1], xty [S, K + 1, d]) float64, dense and symmetric, the ones row / column last -- the
+    layout of LagStats.moments.  Device tensors on the device, else host arrays."""
+    if self._dev is None:
+      return np.stack([sess.a for sess in self._host]), np.stack([sess.b for sess in self._host])
+    return device.online_fit_moments(self._dev['state'], self.channels, self.pre, self.post, self.outputs,
+                                     handle=self._dev['h'])
+
+  def solve(self, lambdas):
+    """Ridge weights from the moments so far, for every session and every lambda: (W [S, n_lambda, K, d],
+    b [S, n_lambda, d]) -- the solution of (A / A[K][K] + lambda I) [W; b] = B / A[K][K], the reference's
+    cov_x with lambda on the bias entry too (brain_model.py:447-455, 477).  float32 device tensors on the device
+    (built and solved there: td_fit_online_solve), else host arrays (float64, as every NumPy session: not rounded
+    to float32).  ValueError before any frame was counted; numpy.linalg.LinAlgError for a system that is not
+    positive definite."""
+    lambdas = [float(v) for v in np.atleast_1d(lambdas)]
+    if not lambdas:
+      raise ValueError('OnlineRidgeFit.solve needs at least one lambda.')
+    if self.frames <= 0:
+      raise ValueError('OnlineRidgeFit.solve: no frame counted yet (%d rows pushed, results run %d behind): the '
+                       'moments are empty.' % (self.rows_pushed, self.delay))
+    if self._dev is None:
+      outs = [sess.solve(lambdas) for sess in self._host]
+      return np.stack([o[0] for o in outs]), np.stack([o[1] for o in outs])
+    return device.online_fit_solve(self._dev['state'], self.channels, self.pre, self.post, self.outputs,
+                                   self.frames, lambdas, handle=self._dev['h'])
+
+  def update_model(self, model, regularization_lambda, session=0):
+    """Gives a brain_model.BrainModelLinearRegression the ridge weights of one session (model.set_weights): the
+    model's channels, context and output width must be the session's.  Returns the model."""
+    if not isinstance(model, brain_model.BrainModelLinearRegression):
+      raise ValueError('OnlineRidgeFit.update_model takes a BrainModelLinearRegression, not a %s.' %
+                       type(model).__name__)
+    for name, mine, theirs in (('channels', self.channels, model._c1), ('pre_context', self.pre, model._pre),
+                               ('post_context', self.post, model._post),
+                               ('outputs', self.outputs, model._output_width)):
+      if int(theirs) != mine:
+        raise ValueError('OnlineRidgeFit.update_model: the model has %s = %d, the fit %d.' % (name, int(theirs), mine))
+    if not 0 <= int(session) < self.sessions:
+      raise ValueError('OnlineRidgeFit.update_model: session %d of %d.' % (int(session), self.sessions))
+    w, b = self.solve([regularization_lambda])
+    w, b = w[int(session), 0], b[int(session), 0]
+    if hasattr(w, 'cpu'):
+      w, b = w.cpu().numpy(), b.cpu().numpy()
+    model.set_weights([w, b])
+    return model
