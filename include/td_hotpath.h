@@ -1132,6 +1132,81 @@ int td_fit_online_solve(td_handle* h, int num_sessions, const void* state_dev, i
                         int pre, int post, int d, int64_t frames_emitted, const double* lambdas_host, int n_lambda,
                         float* w_dev, float* b_dev);
 
+/* ------------------------------------------------------------------ online calibration
+ * The stage behind the online ridge fit: what infer_decoder.Decoder.train(data0, data1, window_size = W) takes from
+ * a labelled stretch -- the correlation statistics {mean_truth, mean_pred, power}, the scaled LDA between the window
+ * means of the unattended (class 0) and the attended (class 1) correlations, d' -- for (eeg, attended envelope,
+ * unattended envelope) rows that arrive in pushes of any length, predicted with the weights handed to each push.
+ * `num_sessions` independent sessions, one state block each on the device, ONE launch per push (one workgroup of 256
+ * threads per session), nothing stored per row.  However a recording is cut into pushes, the state is that of one
+ * push of the whole recording, bit for bit.
+ *
+ * Frames are emitted `post` rows late with td_online_plan's arithmetic: after `pushed` rows emitted =
+ * max(0, pushed - post); a push that carries flush emits the rest with `post` zero rows behind the end.  The
+ * prediction p of an emitted frame is the float32 value td_online_push returns in `pred` (the same operation order).
+ * env[..., 0] is the attended envelope a, env[..., 1] the unattended one u.  Windows are average_data's: consecutive,
+ * hop = width, the tail dropped; width 1 is train's frame-level case.
+ *
+ * State (td_calib_online_state_bytes; all zeros = a fresh session; the HOST counts the frames): TD_CALIB_ONLINE_SUMS
+ * float64 sums, every one advanced in frame order by acc += (double)x * (double)y (the product is exact),
+ *   [0, 6)    over every emitted frame: sum p, sum p^2, sum a, sum a^2, sum u, sum u^2
+ *   [6, 15)   class 0 (truth x = u) over the completed windows: sum_w z [3], then the upper triangle of sum_w z z^T
+ *             in the order (0,0) (0,1) (0,2) (1,1) (1,2) (2,2), z = (sum x p, sum x, sum p) of a window; the Gram
+ *             takes G + z_i z_j unfused (the product rounds, then the add)
+ *   [15, 24)  class 1 (truth x = a), the same
+ *   [24, 29)  the open window: sum p, sum a, sum a p, sum u, sum u p (zero again when a frame completes a window)
+ * then the EEG tail [pre + post][c] and the envelope tail [post][2] float32 (td_online_push's), rounded up to 8 bytes.
+ *
+ * td_calib_online_push: the sessions' next n rows.
+ *   eeg_dev [S][n][c] float32, row stride eeg_ld, session stride eeg_session_stride (elements)
+ *   env_dev [S][n][2] float32, row stride env_ld, session stride env_session_stride (elements)
+ *   w_dev [S or 1][(pre + 1 + post) c], b_dev [S or 1] float32: session strides in elements, 0 = one model for all
+ *   n >= 0 (n == 0 without flush: nothing is queued); a push that emits nothing still rolls the tails
+ *   frames_before: rows pushed so far;  flush != 0: the recording ends behind this push
+ *   state_dev, state_session_stride (BYTES, a multiple of 8, >= td_calib_online_state_bytes)
+ * With td_profile_enable the launch is bracketed as td_online_push's is.
+ *
+ * td_calib_online_sums: out_dev [S][TD_CALIB_ONLINE_SUMS] float64, the sums in the order above.
+ *
+ * td_calib_online_finish: ONE launch evaluates, per session and in float64, with N = frames_emitted (the host's
+ * count), n_win = N / width and the correlator as train feeds it (class 0 first):
+ *   count = 2 N, sum_x = sum u + sum a, sum_x2 = sum u^2 + sum a^2, sum_y = sum p + sum p, sum_y2 = sum p^2 + sum p^2
+ *   mean_x = sum_x / count, mean_y = sum_y / count,
+ *   power = sqrt((sum_x2 - sum_x^2 / count) (sum_y2 - sum_y^2 / count)) / count
+ *   c = (1, -mean_y, -mean_x) / (width power), c0 = mean_x mean_y / power, and per class
+ *   sum_w m = c . sum z + n_win c0,  sum_w m^2 = c^T (sum z z^T) c + 2 c0 (c . sum z) + n_win c0^2
+ *   mbar = sum_w m / n_win, v = sum_w m^2 / n_win - mbar^2
+ *   slope = 1 / (mbar_1 - mbar_0), intercept = -slope mbar_0, d' = |mbar_1 - mbar_0| / sqrt((v_0 + v_1) / 2)
+ * and writes corr_dev [S][2][3] (both speaker rows {mean_x, mean_y, power}: the layout td_online_push reads),
+ * lda_dev [S][3] {1, slope, intercept}, dprime_dev [S] and status_dev [S] int32: TD_CALIB_OK; TD_CALIB_NO_WINDOW (no
+ * completed window: train's "No data for class"); TD_CALIB_NO_POWER (power not finite or <= 0); TD_CALIB_SAME_MEANS
+ * (equal class means: scaled LDA's "X0 and X1 ... identical").  What a session cannot give is NaN.  The state is not
+ * modified: calibration can go on after a look.  Bracketed by td_profile_enable as a push is.
+ *
+ * TD_ERR_INVALID, before anything is queued and with the state untouched: a NULL required pointer, num_sessions
+ * outside 1..65535, c outside 1..TD_CALIB_ONLINE_MAX_CHANNELS, pre or post < 0, more than TD_CALIB_ONLINE_MAX_LAGS
+ * lags, width outside 1..TD_ONLINE_MAX_WIDTH, n outside 0..TD_ONLINE_MAX_PUSH, frames_before or frames_emitted < 0, a
+ * row or session stride below a row, a weight stride below a model, a state stride below the state block (for
+ * _sums and _finish: below the sums) or not a multiple of 8. */
+#define TD_CALIB_ONLINE_MAX_CHANNELS 128
+#define TD_CALIB_ONLINE_MAX_LAGS 64
+#define TD_CALIB_ONLINE_SUMS 29
+#define TD_CALIB_OK 0
+#define TD_CALIB_NO_WINDOW 1
+#define TD_CALIB_NO_POWER 2
+#define TD_CALIB_SAME_MEANS 3
+int td_calib_online_state_bytes(int c, int pre, int post, int64_t* bytes);
+int td_calib_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t eeg_ld,
+                         int64_t eeg_session_stride, const float* env_dev, int64_t env_ld,
+                         int64_t env_session_stride, const float* w_dev, int64_t w_session_stride,
+                         const float* b_dev, int64_t b_session_stride, int64_t n, int64_t frames_before, int c,
+                         int pre, int post, int width, int flush, void* state_dev, int64_t state_session_stride);
+int td_calib_online_sums(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,
+                         double* out_dev);
+int td_calib_online_finish(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,
+                           int64_t frames_emitted, int width, double* corr_dev, double* lda_dev, double* dprime_dev,
+                           int32_t* status_dev);
+
 /* ------------------------------------------------------------------ ingestion
  * ingest.find_mean_std, ingest.normalize_data and ingest.convert_data_to_tfrecords (ingest.py:1061-1172).
  *

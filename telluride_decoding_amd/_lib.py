@@ -199,6 +199,14 @@ SIGNATURES = {
     'td_fit_online_moments': [_vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp],
     # h, sessions | state, stride | c, pre, post, d | frames_emitted | lambdas, n_lambda | w, b
     'td_fit_online_solve': [_vp, _i, _vp, _i64, _i, _i, _i, _i, _i64, _pd, _i, _vp, _vp],
+    'td_calib_online_state_bytes': [_i, _i, _i, _pi64],
+    # h, sessions | eeg, ld, stride | env, ld, stride | w, stride | b, stride | n, frames_before | c, pre, post, width,
+    # flush | state, stride
+    'td_calib_online_push': [_vp, _i] + [_vp, _i64, _i64] * 2 + [_vp, _i64] * 2 + [_i64, _i64] + [_i] * 5 +
+                            [_vp, _i64],
+    'td_calib_online_sums': [_vp, _i, _vp, _i64, _vp],
+    # h, sessions | state, stride | frames_emitted, width | corr, lda, dprime, status
+    'td_calib_online_finish': [_vp, _i, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp],
     'td_ingest_moments': [_vp, _c.POINTER(_vp), _pi64, _pi64, _c.POINTER(_i), _i, _i, _vp],
     'td_ingest_normalize': [_vp, _vp, _i, _i64, _i64, _i, _pd, _pd, _i, _i, _i, _i, _vp, _i64],
     'td_tfrecord_encode': [_vp, _c.c_char_p, _i, _i, _c.POINTER(_vp), _pi64, _c.POINTER(_i), _c.POINTER(_i),

@@ -1,0 +1,433 @@
+// Online calibration (td_calib_online_*): what infer_decoder.Decoder.train(data0, data1, window_size = W) takes from a
+// labelled stretch -- the correlator's statistics {mean_truth, mean_pred, power}, the scaled LDA between the window
+// means of the unattended (class 0) and the attended (class 1) correlations, d' -- for (eeg, attended envelope,
+// unattended envelope) rows that arrive in pushes of any length, with the bank's CURRENT weights.  As the online family
+// does everything else: a bank of sessions, one workgroup of 256 threads each, the state on the device, ONE launch per
+// push, the host counts the frames, a block of zeros is a fresh session, no atomics, vector stores only.
+//
+// One pass is enough.  train needs two because the per-frame correlation (x - mean_x)(p - mean_y) / power (x the
+// truth, p the prediction) takes the FINAL statistics; but a window mean of it is affine in three per-window sums,
+//   m_w = (sum x p - mean_y sum x - mean_x sum p + W mean_x mean_y) / (W power),
+// so the state keeps, in float64, none of them a function of the final statistics:
+//   [0, 6)    the correlator's sums over every emitted frame: sum p, sum p^2, sum a, sum a^2, sum u, sum u^2
+//   [6, 15)   class 0 (truth u) over the windows completed so far: sum_w z [3], then the upper triangle of
+//             sum_w z z^T in the order (0,0) (0,1) (0,2) (1,1) (1,2) (2,2), with z = (sum x p, sum x, sum p)
+//   [15, 24)  class 1 (truth a), the same
+//   [24, 29)  the open window's running sums: sum p, sum a, sum a p, sum u, sum u p
+// then the EEG tail [pre + post][c] and the envelope tail [post][2] in float32, as td_online_push's block carries
+// them, rounded up to 8 bytes.  Windows are infer_decoder.average_data's: consecutive, hop = width, the tail dropped.
+//
+// The prediction of an emitted frame is the float32 value td_online_push returns in `pred`: the same loop, restated
+// here (lane q takes the terms q, q + 64, ... into four fmaf accumulators in turn, ((a0 + a1) + (a2 + a3)), the
+// 64-lane tree, + bias).
+//
+// The sums advance in frame order, one lane per state double: the 29 accumulators are independent, so lane t of the
+// first wave owns double t and walks a pass's frames from LDS; a lane of a class sum keeps its own copy of the one or
+// two open-window sums it needs (the same additions in the same order: the same bits as the open window's lanes).
+// A per-frame term is a product of two widened float32 values (or of one and 1.0): exact in float64.  When a frame
+// completes a window the class's sum z takes plain adds, its Gram G + z_i z_j UNFUSED -- z_i z_j rounds, then the
+// add rounds: this file is compiled with fp contract(off), as online_fit.hip is and for its reason -- and the
+// open-window sums return to zero.  So acc += float64(x) * float64(p) and G + np.outer(z, z) in NumPy are a bit-exact
+// twin, and any cut of a recording gives the same state bytes.  The serial walk is intended: pushes are tens to
+// hundreds of frames and the prediction dominates.
+//
+// Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are in DESIGN.md section 35.
+#include <cmath>
+
+#include "td_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kMaxChannels = TD_CALIB_ONLINE_MAX_CHANNELS, kMaxLags = TD_CALIB_ONLINE_MAX_LAGS;
+constexpr int kPass = 64;       // emitted frames per pass of a workgroup (fewer for a short push: less LDS)
+constexpr int kSums = TD_CALIB_ONLINE_SUMS;
+constexpr int kOpen = 24;       // the first of the open window's five sums
+
+__host__ __device__ inline long long state_eeg_offset() { return 8LL * kSums; }
+__host__ __device__ inline long long state_env_offset(int c, int pre, int post) {
+  return state_eeg_offset() + 4LL * c * (pre + post);
+}
+__host__ __device__ inline long long state_bytes(int c, int pre, int post) {
+  return (state_env_offset(c, pre, post) + 8LL * post + 7) / 8 * 8;
+}
+
+struct CalibParams {
+  const float* eeg; long long eeg_ld, eeg_ss;
+  const float* env; long long env_ld, env_ss;
+  const float* w; long long w_ss;
+  const float* b; long long b_ss;
+  long long n, p0;               // rows of this push, rows pushed before it
+  long long e0, e1;              // frames emitted before / after
+  int c, pre, post, width, pass;
+  unsigned char* state; long long state_ss;
+};
+
+// (online.hip's wave_sum_f32: the same shuffle tree, the same bits)
+__device__ __forceinline__ float wave_sum_f32(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// What a lane of the walk does with its state double.  A frame's values sit in LDS as {1, p, a, u}; a term is the
+// product of two of them (f0, f1: indices into that quadruple).
+enum : int { kPlain = 0, kOpenSum = 1, kClassSum = 2, kClassGram = 3, kIdle = 4 };
+
+// component `comp` of z = (sum x p, sum x, sum p) for the truth at index `truth` (2: a, 3: u): its two factors and the
+// open-window sum that holds its running value
+__device__ __forceinline__ void z_component(int truth, int comp, int* f0, int* f1, int* open) {
+  if (comp == 0) { *f0 = truth; *f1 = 1; *open = kOpen + (truth == 2 ? 2 : 4); }
+  else if (comp == 1) { *f0 = truth; *f1 = 0; *open = kOpen + (truth == 2 ? 1 : 3); }
+  else { *f0 = 1; *f1 = 0; *open = kOpen; }
+}
+
+__global__ __launch_bounds__(kThreads) void online_calib_push_kernel(CalibParams p) {
+  extern __shared__ double lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s = blockIdx.x;
+  const int c = p.c, pre = p.pre, post = p.post, width = p.width;
+  const int tl = pre + post, nl = tl + 1, k_all = nl * c, pass = p.pass;
+  double* val_s = lds;                                       // [pass][4] a frame's {1, p, a, u}
+  float* w_s = reinterpret_cast<float*>(val_s + 4 * pass);   // [nl c] the weights
+  float* rows_s = w_s + k_all;                               // [pass + tl][c] the pass's EEG rows
+  float* env_s = rows_s + (size_t)(pass + tl) * c;           // [max(pass, post)][2]
+
+  unsigned char* st = p.state + (long long)s * p.state_ss;
+  double* sums = reinterpret_cast<double*>(st);                                    // [kSums]
+  float* tail = reinterpret_cast<float*>(st + state_eeg_offset());                 // [tl][c]
+  float* etail = reinterpret_cast<float*>(st + state_env_offset(c, pre, post));    // [post][2]
+  const float* eeg = p.eeg + (long long)s * p.eeg_ss;
+  const float* env = p.env + (long long)s * p.env_ss;
+  const float* w = p.w + (long long)s * p.w_ss;
+  const float bias = p.b[(long long)s * p.b_ss];
+  const long long p0 = p.p0, p1 = p.p0 + p.n;
+
+  for (int k = tid; k < k_all; k += kThreads) w_s[k] = w[k];
+
+  // ---- the walk's lanes: lane t owns state double t
+  int role = kIdle, f0 = 0, f1 = 0, g0 = 0, g1 = 0;
+  double acc = 0.0, r1 = 0.0, r2 = 0.0;
+  if (tid < kSums) {
+    acc = sums[tid];
+    if (tid < 6) {                                           // sum p, p^2, a, a^2, u, u^2
+      role = kPlain;
+      f0 = 1 + (tid >> 1);
+      f1 = (tid & 1) ? f0 : 0;
+    } else if (tid >= kOpen) {                               // sum p, a, a p, u, u p
+      role = kOpenSum;
+      const int j = tid - kOpen;
+      f0 = j == 0 ? 1 : (j <= 2 ? 2 : 3);
+      f1 = (j == 2 || j == 4) ? 1 : 0;
+    } else {
+      const int cls = (tid - 6) / 9, j = (tid - 6) - 9 * cls;
+      const int truth = cls == 1 ? 2 : 3;
+      int open = 0;
+      if (j < 3) {
+        role = kClassSum;
+        z_component(truth, j, &f0, &f1, &open);
+        r1 = sums[open];
+      } else {
+        role = kClassGram;
+        const int e = j - 3;                                 // (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
+        const int zi = e < 3 ? 0 : (e < 5 ? 1 : 2), zj = e < 3 ? e : (e < 5 ? e - 2 : 2);
+        z_component(truth, zi, &f0, &f1, &open);
+        r1 = sums[open];
+        z_component(truth, zj, &g0, &g1, &open);
+        r2 = sums[open];
+      }
+    }
+  }
+
+  for (long long a = p.e0; a < p.e1; a += pass) {
+    const int nf = (int)(p.e1 - a < pass ? p.e1 - a : pass);     // frames [a, a + nf) of this pass
+    // ---- stage the EEG rows a - pre .. a + nf - 1 + post and the envelope rows a .. a + nf - 1: from the
+    // tails (rows before this push), from the push, zeros before the recording and behind a flushed end
+    const int n_rows = nf + tl;
+    for (int rr = wave; rr < n_rows; rr += kWaves) {
+      const long long row = a - pre + rr;
+      for (int ch = lane; ch < c; ch += 64) {
+        float v = 0.f;
+        if (row >= 0 && row < p0) v = tail[(row - (p0 - tl)) * c + ch];
+        else if (row >= p0 && row < p1) v = eeg[(row - p0) * p.eeg_ld + ch];
+        rows_s[rr * c + ch] = v;
+      }
+    }
+    for (int i = tid; i < 2 * nf; i += kThreads) {
+      const long long row = a + (i >> 1);
+      env_s[i] = row < p0 ? etail[(row - (p0 - post)) * 2 + (i & 1)] : env[(row - p0) * p.env_ld + (i & 1)];
+    }
+    __syncthreads();
+    // ---- predictions, td_online_push's: a wave per frame; lane q takes the terms k = q, q + 64, ... of the
+    // (lag, channel) sum into four accumulators in turn, ((a0 + a1) + (a2 + a3)), the 64-lane tree, the bias
+    for (int f = wave; f < nf; f += kWaves) {
+      const float* xr = rows_s + f * c;
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+      int k = lane;
+      for (; k + 192 < k_all; k += 256) {
+        a0 = fmaf(w_s[k], xr[k], a0);
+        a1 = fmaf(w_s[k + 64], xr[k + 64], a1);
+        a2 = fmaf(w_s[k + 128], xr[k + 128], a2);
+        a3 = fmaf(w_s[k + 192], xr[k + 192], a3);
+      }
+      if (k < k_all) a0 = fmaf(w_s[k], xr[k], a0);
+      if (k + 64 < k_all) a1 = fmaf(w_s[k + 64], xr[k + 64], a1);
+      if (k + 128 < k_all) a2 = fmaf(w_s[k + 128], xr[k + 128], a2);
+      const float total = wave_sum_f32((a0 + a1) + (a2 + a3));
+      if (lane == 0) {
+        val_s[4 * f] = 1.0;
+        val_s[4 * f + 1] = (double)(total + bias);
+        val_s[4 * f + 2] = (double)env_s[2 * f];
+        val_s[4 * f + 3] = (double)env_s[2 * f + 1];
+      }
+    }
+    __syncthreads();
+    // ---- the walk: every sum advances by this pass's frames in frame order
+    if (role != kIdle) {
+      int pos = (int)(a % width);                            // frames of the open window before frame a
+      for (int f = 0; f < nf; ++f) {
+        const double* v = val_s + 4 * f;
+        const double t1 = v[f0] * v[f1];                     // exact
+        const bool done = ++pos == width;
+        if (done) pos = 0;
+        if (role == kPlain) {
+          acc = acc + t1;
+        } else if (role == kOpenSum) {
+          acc = acc + t1;
+          if (done) acc = 0.0;
+        } else if (role == kClassSum) {
+          r1 = r1 + t1;
+          if (done) { acc = acc + r1; r1 = 0.0; }
+        } else {
+          const double t2 = v[g0] * v[g1];
+          r1 = r1 + t1;
+          r2 = r2 + t2;
+          if (done) {
+            const double zz = r1 * r2;                       // rounded, then the add rounds: G + z_i z_j unfused
+            acc = acc + zz;
+            r1 = 0.0;
+            r2 = 0.0;
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- the tails for the next push (td_online_push's): the last pre + post EEG rows and the last post envelope
+  // rows of (old tail, this push).  A push shorter than a tail shifts it: the rows that stay go through LDS.
+  __syncthreads();
+  const long long n = p.n;
+  const int keep = n < tl ? (int)(tl - n) : 0;                   // old EEG rows that stay
+  for (int i = tid; i < keep * c; i += kThreads) rows_s[i] = tail[(tl - keep) * c + i];
+  const int ekeep = n < post ? (int)(post - n) : 0;
+  for (int i = tid; i < ekeep * 2; i += kThreads) env_s[i] = etail[(post - ekeep) * 2 + i];
+  __syncthreads();
+  for (int rr = wave; rr < tl; rr += kWaves)
+    for (int ch = lane; ch < c; ch += 64)
+      tail[rr * c + ch] = rr < keep ? rows_s[rr * c + ch] : eeg[(n - (tl - rr)) * p.eeg_ld + ch];
+  for (int i = tid; i < post * 2; i += kThreads) {
+    const int rr = i >> 1;
+    etail[i] = rr < ekeep ? env_s[i] : env[(n - (post - rr)) * p.env_ld + (i & 1)];
+  }
+  // (every lane read the open sums it copies before the first pass; the barriers since then order these stores
+  // behind those loads)
+  if (role != kIdle && p.e1 > p.e0) sums[tid] = acc;
+}
+
+size_t lds_bytes(int c, int nl, int post, int pass) {
+  const size_t env_rows = pass > post ? pass : post;
+  return sizeof(double) * 4 * pass + sizeof(float) * ((size_t)nl * c + (size_t)(pass + nl - 1) * c + 2 * env_rows);
+}
+
+// grid (ceil(S / 256)): out [S][kSums]
+__global__ __launch_bounds__(kThreads) void online_calib_sums_kernel(const unsigned char* state, long long state_ss,
+                                                                     int num_sessions, double* out) {
+  const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (e >= (long long)num_sessions * kSums) return;
+  const int s = (int)(e / kSums), j = (int)(e - (long long)s * kSums);
+  out[e] = reinterpret_cast<const double*>(state + (long long)s * state_ss)[j];
+}
+
+// One class's window-mean moments from its sums: {sum_w m, sum_w m^2} with m = c . z + c0.
+__device__ __forceinline__ void class_moments(const double* q, const double* cv, double c0, double n_win, double* sm,
+                                              double* sm2) {
+  const double cz = (cv[0] * q[0] + cv[1] * q[1]) + cv[2] * q[2];
+  const double* g = q + 3;                                   // (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
+  const double quad = ((g[0] * cv[0] * cv[0] + g[3] * cv[1] * cv[1]) + g[5] * cv[2] * cv[2]) +
+                      2.0 * ((g[1] * cv[0] * cv[1] + g[2] * cv[0] * cv[2]) + g[4] * cv[1] * cv[2]);
+  *sm = cz + n_win * c0;
+  *sm2 = (quad + 2.0 * c0 * cz) + n_win * c0 * c0;
+}
+
+// grid (ceil(S / 256)): a thread per session, float64
+__global__ __launch_bounds__(kThreads) void online_calib_finish_kernel(const unsigned char* state, long long state_ss,
+                                                                       int num_sessions, long long frames, int width,
+                                                                       double* corr, double* lda, double* dprime,
+                                                                       int* status) {
+  const int s = blockIdx.x * kThreads + threadIdx.x;
+  if (s >= num_sessions) return;
+  const double* q = reinterpret_cast<const double*>(state + (long long)s * state_ss);
+  // the correlator after train's add(data0) then add(data1): class 0 = (u, p) first, then class 1 = (a, p)
+  const double count = 2.0 * (double)frames;
+  const double sum_x = q[4] + q[2], sum_x2 = q[5] + q[3], sum_y = q[0] + q[0], sum_y2 = q[1] + q[1];
+  const double mean_x = sum_x / count, mean_y = sum_y / count;
+  const double power = sqrt((sum_x2 - sum_x * sum_x / count) * (sum_y2 - sum_y * sum_y / count)) / count;
+  const double n_win = (double)(frames / width);
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  int st = TD_CALIB_OK;
+  double slope = nan, icpt = nan, dp = nan;
+  if (n_win < 1.0) {
+    st = TD_CALIB_NO_WINDOW;
+  } else if (!(power > 0.0) || isinf(power)) {
+    st = TD_CALIB_NO_POWER;
+  } else {
+    const double scale = 1.0 / ((double)width * power);
+    const double cv[3] = {scale, -mean_y * scale, -mean_x * scale};
+    const double c0 = mean_x * mean_y / power;
+    double sm0, sq0, sm1, sq1;
+    class_moments(q + 6, cv, c0, n_win, &sm0, &sq0);
+    class_moments(q + 15, cv, c0, n_win, &sm1, &sq1);
+    const double m0 = sm0 / n_win, m1 = sm1 / n_win;
+    const double v0 = sq0 / n_win - m0 * m0, v1 = sq1 / n_win - m1 * m1;
+    if (m0 == m1 || isnan(m0) || isnan(m1)) {                // equal, or not a number
+      st = TD_CALIB_SAME_MEANS;
+    } else {
+      slope = 1.0 / (m1 - m0);
+      icpt = -slope * m0;
+      dp = fabs(m1 - m0) / sqrt((v0 + v1) / 2.0);
+    }
+  }
+  const bool have_stats = st == TD_CALIB_OK || st == TD_CALIB_SAME_MEANS;
+  double* cr = corr + 6LL * s;
+  for (int spk = 0; spk < 2; ++spk) {
+    cr[3 * spk] = have_stats ? mean_x : nan;
+    cr[3 * spk + 1] = have_stats ? mean_y : nan;
+    cr[3 * spk + 2] = have_stats ? power : nan;
+  }
+  lda[3LL * s] = 1.0;
+  lda[3LL * s + 1] = slope;
+  lda[3LL * s + 2] = icpt;
+  dprime[s] = dp;
+  status[s] = st;
+}
+
+int check_state(td_handle* h, const char* who, int num_sessions, const void* state_dev, int64_t stride,
+                long long need) {
+  TD_REQUIRE(h, num_sessions >= 1 && num_sessions <= 65535, "%s: %d sessions (1 .. 65535)", who, num_sessions);
+  if (!state_dev) return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
+  TD_REQUIRE(h, stride >= need && stride % 8 == 0, "%s: a state stride of %lld bytes (a multiple of 8, at least %lld)",
+             who, (long long)stride, need);
+  return TD_OK;
+}
+
+int check_shape(td_handle* h, const char* who, int c, int pre, int post) {
+  TD_REQUIRE(h, c >= 1 && c <= kMaxChannels, "%s: %d channels (1 .. %d)", who, c, kMaxChannels);
+  TD_REQUIRE(h, pre >= 0 && post >= 0 && pre + 1 + post <= kMaxLags,
+             "%s: a context of %d + 1 + %d lags (1 .. %d)", who, pre, post, kMaxLags);
+  return TD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int td_calib_online_state_bytes(int c, int pre, int post, int64_t* bytes) {
+  if (!bytes) return td_fail(nullptr, TD_ERR_INVALID, "td_calib_online_state_bytes: NULL argument");
+  TD_TRY(check_shape(nullptr, "td_calib_online_state_bytes", c, pre, post));
+  *bytes = state_bytes(c, pre, post);
+  return TD_OK;
+}
+
+int td_calib_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t eeg_ld,
+                         int64_t eeg_session_stride, const float* env_dev, int64_t env_ld,
+                         int64_t env_session_stride, const float* w_dev, int64_t w_session_stride,
+                         const float* b_dev, int64_t b_session_stride, int64_t n, int64_t frames_before, int c,
+                         int pre, int post, int width, int flush, void* state_dev, int64_t state_session_stride) {
+  if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_calib_online_push: handle is NULL");
+  TD_TRY(check_shape(h, "td_calib_online_push", c, pre, post));
+  TD_REQUIRE(h, width >= 1 && width <= TD_ONLINE_MAX_WIDTH, "td_calib_online_push: window of %d frames (1 .. %d)",
+             width, TD_ONLINE_MAX_WIDTH);
+  TD_REQUIRE(h, n >= 0 && n <= TD_ONLINE_MAX_PUSH, "td_calib_online_push: %lld rows in one push (0 .. %d)",
+             (long long)n, TD_ONLINE_MAX_PUSH);
+  TD_REQUIRE(h, frames_before >= 0, "td_calib_online_push: %lld frames before", (long long)frames_before);
+  TD_TRY(check_state(h, "td_calib_online_push", num_sessions, state_dev, state_session_stride,
+                     state_bytes(c, pre, post)));
+  if (!w_dev || !b_dev || (n > 0 && (!eeg_dev || !env_dev)))
+    return td_fail(h, TD_ERR_INVALID, "td_calib_online_push: NULL argument");
+  TD_REQUIRE(h, n == 0 || (eeg_ld >= c && env_ld >= 2),
+             "td_calib_online_push: a row stride below a row (%lld for %d channels, %lld for 2 envelopes)",
+             (long long)eeg_ld, c, (long long)env_ld);
+  TD_REQUIRE(h, n == 0 || num_sessions == 1 || (eeg_session_stride >= c && env_session_stride >= 2),
+             "td_calib_online_push: a session stride below a row");
+  const int nl = pre + 1 + post;
+  TD_REQUIRE(h, w_session_stride == 0 || w_session_stride >= (int64_t)nl * c,
+             "td_calib_online_push: a weight stride of %lld for %d weights (0 = one model)",
+             (long long)w_session_stride, nl * c);
+  TD_REQUIRE(h, b_session_stride == 0 || b_session_stride >= 1, "td_calib_online_push: a bias stride of %lld",
+             (long long)b_session_stride);
+  if (n == 0 && !flush) return TD_OK;
+  // td_online_plan's arithmetic
+  const long long pushed = frames_before + n;
+  CalibParams p;
+  p.eeg = eeg_dev; p.eeg_ld = eeg_ld; p.eeg_ss = num_sessions > 1 ? eeg_session_stride : 0;
+  p.env = env_dev; p.env_ld = env_ld; p.env_ss = num_sessions > 1 ? env_session_stride : 0;
+  p.w = w_dev; p.w_ss = w_session_stride; p.b = b_dev; p.b_ss = b_session_stride;
+  p.n = n; p.p0 = frames_before;
+  p.e0 = frames_before > post ? frames_before - post : 0;
+  p.e1 = flush ? pushed : (pushed > post ? pushed - post : 0);
+  p.c = c; p.pre = pre; p.post = post; p.width = width;
+  const long long emitted_now = p.e1 - p.e0;
+  p.pass = emitted_now < kPass ? (emitted_now > 1 ? (int)emitted_now : 1) : kPass;
+  p.state = reinterpret_cast<unsigned char*>(state_dev); p.state_ss = state_session_stride;
+  if (!h->lds_opt_online_calib) {
+    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&online_calib_push_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds_bytes(kMaxChannels, kMaxLags, kMaxLags - 1, kPass)));
+    h->lds_opt_online_calib = true;
+  }
+  TD_TRY(td_profile_mark(h, true, (double)n * num_sessions));
+  hipLaunchKernelGGL(online_calib_push_kernel, dim3((unsigned)num_sessions), dim3(kThreads),
+                     lds_bytes(c, nl, post, p.pass), h->stream, p);
+  TD_HIP(h, hipGetLastError());
+  TD_TRY(td_profile_mark(h, false, 0.0));
+  return TD_OK;
+}
+
+int td_calib_online_sums(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,
+                         double* out_dev) {
+  if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_calib_online_sums: handle is NULL");
+  TD_TRY(check_state(h, "td_calib_online_sums", num_sessions, state_dev, state_session_stride, 8LL * kSums));
+  if (!out_dev) return td_fail(h, TD_ERR_INVALID, "td_calib_online_sums: NULL argument");
+  const unsigned blocks = (unsigned)td_ceil_div((long long)num_sessions * kSums, kThreads);
+  hipLaunchKernelGGL(online_calib_sums_kernel, dim3(blocks), dim3(kThreads), 0, h->stream,
+                     reinterpret_cast<const unsigned char*>(state_dev), (long long)state_session_stride, num_sessions,
+                     out_dev);
+  TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
+int td_calib_online_finish(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,
+                           int64_t frames_emitted, int width, double* corr_dev, double* lda_dev, double* dprime_dev,
+                           int32_t* status_dev) {
+  if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_calib_online_finish: handle is NULL");
+  TD_TRY(check_state(h, "td_calib_online_finish", num_sessions, state_dev, state_session_stride, 8LL * kSums));
+  TD_REQUIRE(h, width >= 1 && width <= TD_ONLINE_MAX_WIDTH, "td_calib_online_finish: window of %d frames (1 .. %d)",
+             width, TD_ONLINE_MAX_WIDTH);
+  TD_REQUIRE(h, frames_emitted >= 0, "td_calib_online_finish: %lld frames emitted", (long long)frames_emitted);
+  if (!corr_dev || !lda_dev || !dprime_dev || !status_dev)
+    return td_fail(h, TD_ERR_INVALID, "td_calib_online_finish: NULL argument");
+  TD_TRY(td_profile_mark(h, true, (double)num_sessions));
+  hipLaunchKernelGGL(online_calib_finish_kernel, dim3((unsigned)td_ceil_div(num_sessions, kThreads)), dim3(kThreads),
+                     0, h->stream, reinterpret_cast<const unsigned char*>(state_dev),
+                     (long long)state_session_stride, num_sessions, (long long)frames_emitted, width, corr_dev,
+                     lda_dev, dprime_dev, status_dev);
+  TD_HIP(h, hipGetLastError());
+  TD_TRY(td_profile_mark(h, false, 0.0));
+  return TD_OK;
+}
+
+}  // extern "C"

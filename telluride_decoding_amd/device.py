@@ -1947,6 +1947,97 @@ def online_fit_solve(state, c, pre, post, d, frames_emitted, lambdas, handle=Non
   return w, b
 
 
+# ---------------------------------------------------------------- online calibration
+# td_calib_online_push's limits, the number of float64 sums in a state block, td_calib_online_finish's statuses
+ONLINE_CALIB_MAX_CHANNELS, ONLINE_CALIB_MAX_LAGS, ONLINE_CALIB_SUMS = 128, 64, 29
+CALIB_OK, CALIB_NO_WINDOW, CALIB_NO_POWER, CALIB_SAME_MEANS = 0, 1, 2, 3
+
+OnlineCalibFinish = collections.namedtuple('OnlineCalibFinish', ['corr', 'lda', 'dprime', 'status'])
+
+
+def online_calib_state_bytes(c, pre, post):
+  """Bytes of one online calibration session's state block (td_calib_online_state_bytes): ONLINE_CALIB_SUMS float64
+  sums, then the EEG tail [pre + post, c] and the envelope tail [post, 2] float32; all zeros = a fresh session."""
+  n = ctypes.c_int64(0)
+  _lib.check(None, _lib.load().td_calib_online_state_bytes(int(c), int(pre), int(post), ctypes.byref(n)))
+  return int(n.value)
+
+
+def online_calib_push(eeg, env, w, b, state, frames_before, pre, post, width, c=None, flush=False, handle=None):
+  """One push of a bank of online calibration sessions, in one launch (td_calib_online_push).
+
+  eeg [S, n, c] and env [S, n, 2] (attended, unattended): float32 device tensors with unit column stride (None for a
+  flush without rows: give c); w [S or 1, (pre + 1 + post) c] and b [S or 1] float32 (one row: the model every
+  session shares) -- read where they are at every push; state: uint8 device tensor [S, >=
+  online_calib_state_bytes()] with a row stride that is a multiple of 8, updated in place; frames_before: rows
+  pushed so far; width: the window of the LDA's training data.  Returns the rows pushed after the call.  Queued,
+  not waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  sessions, stride = _check_fit_state('online_calib_push', h, state)
+  n = 0 if eeg is None else int(eeg.shape[1])
+  if eeg is not None:
+    if eeg.dim() != 3 or env is None or env.dim() != 3 or int(eeg.shape[0]) != sessions or \
+        tuple(env.shape) != (sessions, n, 2):
+      raise ValueError('online_calib_push: eeg of %s and env of %s for %d sessions' %
+                       (tuple(eeg.shape), None if env is None else tuple(env.shape), sessions))
+    c = int(eeg.shape[2])
+  if c is None:
+    raise ValueError('online_calib_push: a flush without rows needs the channel count c')
+  c = int(c)
+  for name, t in (('eeg', eeg), ('env', env), ('w', w), ('b', b)):
+    if t is not None and (t.dtype != torch.float32 or t.device != h.device):
+      raise TypeError('online_calib_push: %s must be a float32 tensor on %s, not %s on %s' %
+                      (name, h.device, t.dtype, t.device))
+  if n > 0 and (eeg.stride(2) != 1 and c > 1 or env.stride(2) != 1):
+    raise ValueError('online_calib_push: the columns of eeg and env must be contiguous')
+  if w.dim() != 2 or int(w.shape[0]) not in (1, sessions) or int(b.numel()) != int(w.shape[0]):
+    raise ValueError('online_calib_push: %s weights and %d biases for %d sessions' %
+                     (tuple(w.shape), int(b.numel()), sessions))
+  k = int(w.shape[1])
+  if k != (int(pre) + 1 + int(post)) * c:
+    raise ValueError('online_calib_push: %d weights for %d lags of %d channels' % (k, int(pre) + 1 + int(post), c))
+  w, b = w.contiguous(), b.reshape(-1).contiguous()
+  shared = int(w.shape[0]) == 1
+  rows = n > 0
+  h.check(h.lib.td_calib_online_push(
+      h.ptr, sessions,
+      _ptr(eeg if rows else None), int(eeg.stride(1)) if rows and n > 1 else c,
+      int(eeg.stride(0)) if rows and sessions > 1 else max(n, 1) * c,
+      _ptr(env if rows else None), int(env.stride(1)) if rows and n > 1 else 2,
+      int(env.stride(0)) if rows and sessions > 1 else max(n, 1) * 2,
+      _ptr(w), 0 if shared else k, _ptr(b), 0 if shared else 1,
+      n, int(frames_before), c, int(pre), int(post), int(width), 1 if flush else 0, _ptr(state), stride))
+  return int(frames_before) + n
+
+
+def online_calib_sums(state, handle=None):
+  """The float64 sums of a bank of online calibration sessions, [S, ONLINE_CALIB_SUMS] on the device, in
+  td_calib_online_sums' order: sum p, p^2, a, a^2, u, u^2 | class 0: sum z [3], upper sum z z^T [6] | class 1 | the
+  open window's sum p, a, a p, u, u p."""
+  h = handle or default_handle()
+  sessions, stride = _check_fit_state('online_calib_sums', h, state)
+  out = h.empty((sessions, ONLINE_CALIB_SUMS), 'float64')
+  h.check(h.lib.td_calib_online_sums(h.ptr, sessions, _ptr(state), stride, _ptr(out)))
+  return out
+
+
+def online_calib_finish(state, frames_emitted, width, handle=None):
+  """The closed form of Decoder.train on a bank's sums, in one launch (td_calib_online_finish):
+  OnlineCalibFinish(corr [S, 2, 3] float64, lda [S, 3] float64 {1, slope, intercept}, dprime [S] float64, status [S]
+  int32 -- CALIB_OK, CALIB_NO_WINDOW, CALIB_NO_POWER, CALIB_SAME_MEANS), device tensors.  The state is not modified.
+  Queued, not waited for."""
+  h = handle or default_handle()
+  sessions, stride = _check_fit_state('online_calib_finish', h, state)
+  corr = h.empty((sessions, 2, 3), 'float64')
+  lda = h.empty((sessions, 3), 'float64')
+  dprime = h.empty((sessions,), 'float64')
+  status = h.empty((sessions,), 'int32')
+  h.check(h.lib.td_calib_online_finish(h.ptr, sessions, _ptr(state), stride, int(frames_emitted), int(width),
+                                       _ptr(corr), _ptr(lda), _ptr(dprime), _ptr(status)))
+  return OnlineCalibFinish(corr, lda, dprime, status)
+
+
 # ---------------------------------------------------------------- fully connected regressor / match-mismatch classifier
 MLP_LOSSES = {'mse': 0, 'pearson': 1}
 

@@ -64,6 +64,15 @@ keeps the exact float64 moments of the lagged ridge regression in ONE td_fit_onl
     w, b = fit.solve([0.1])
     online.set_weights(w[:, 0, :, 0], b[:, 0, 0])
 
+and so can the statistics the new weights are scored with: `OnlineCalibration` takes a labelled stretch of (eeg,
+attended envelope, unattended envelope) rows in pushes of any length -- ONE td_calib_online_push launch per push,
+nothing stored per row -- and gives what infer_decoder.Decoder.train would: the correlation statistics, the scaled
+LDA and d'; `OnlineDecoder.set_statistics` takes them between pushes:
+
+    calib.push(eeg, attended_envelope, unattended_envelope)
+    r = calib.finish()
+    online.set_statistics(r.corr, r.lda)
+
 Without a GPU (`device.gpu_available()` false) the same object runs a NumPy session with the same
 semantics -- float64 throughout, window sums in frame order, td_online_plan's arithmetic -- so that the logic can
 be built and tested anywhere.  (The state-space decoder has no host form: 'ssd' needs the GPU.)
@@ -628,8 +637,9 @@ class OnlineDecoder(object):
     host copy: what OnlineRidgeFit.solve returns, sliced) or arrays.  A bank that shared one model copy holds S
     copies afterwards when S rows are given.  The session state, the score ring and the correlation statistics are
     untouched: the next push predicts with the new weights and scores them with the decoder's TRAINED statistics.
-    Re-estimating those statistics, or the LDA, online is out of scope: a decoder whose predictions change scale
-    needs them from a batch run (infer_decoder)."""
+    Re-estimating those statistics, or the LDA, online was out of scope here and is OnlineCalibration's work: a
+    decoder whose predictions change scale pushes a labelled stretch through it and takes the result with
+    set_statistics, without a batch run."""
     if self.kind != 'linear':
       raise ValueError('OnlineDecoder.set_weights replaces the weights of a linear bank only, not of a %s bank.' %
                        self.kind)
@@ -656,6 +666,46 @@ class OnlineDecoder(object):
     else:
       d['w'].copy_(w.expand_as(d['w']))
       d['b'].copy_(b.expand_as(d['b']))
+
+  def set_statistics(self, corr, lda=None):
+    """Replaces the correlation statistics -- and, for reduction 'lda', the LDA -- of a linear or DNN bank in place,
+    between pushes: corr {mean_truth, mean_pred, power} as [3] (every session and both speakers take it), [S, 3]
+    (both speakers of a session) or [S, 2, 3]; lda {lda_w, slope, intercept} as [3] or [S, 3], required when the
+    bank's reduction is 'lda' and not read otherwise -- device tensors (copied device to device, no host copy: what
+    OnlineCalibration.finish returns) or arrays.  The weights, the session state, the score ring and the stepped /
+    state-space decoder's state are untouched: the frames the next push emits are scored with the new parameters,
+    so the first window that lies wholly behind the swap is that of a bank built with them."""
+    if self.kind not in ('linear', 'dnn'):
+      raise ValueError('OnlineDecoder.set_statistics replaces the statistics of a linear or DNN bank, not of a %s '
+                       'bank (its statistics have one column per dim).' % self.kind)
+    s = self.sessions
+    shape_of = lambda a: tuple(a.shape) if hasattr(a, 'shape') else tuple(np.shape(a))
+    if shape_of(corr) not in ((3,), (s, 3), (s, 2, 3)):
+      raise ValueError('OnlineDecoder.set_statistics takes corr [3], [%d, 3] or [%d, 2, 3], not %s.' %
+                       (s, s, shape_of(corr)))
+    if lda is not None and shape_of(lda) not in ((3,), (s, 3)):
+      raise ValueError('OnlineDecoder.set_statistics takes lda [3] or [%d, 3], not %s.' % (s, shape_of(lda)))
+    if self.reduction == 'lda' and lda is None:
+      raise ValueError('OnlineDecoder.set_statistics: a bank that reduces with \'lda\' needs lda '
+                       '{lda_w, slope, intercept} beside corr.')
+    if not self._on_device:
+      host = lambda a: np.asarray(a.cpu() if hasattr(a, 'cpu') else a, np.float64)
+      corr = host(corr)
+      corr = np.broadcast_to(corr if corr.ndim == 3 else (corr[:, None, :] if corr.ndim == 2 else corr), (s, 2, 3))
+      for i, p in enumerate(self._params):
+        p['corr'] = corr[i].copy()
+        if self.reduction == 'lda':
+          p['lda'] = np.broadcast_to(host(lda), (s, 3))[i].copy()
+      return
+    # (the device bank is the truth from here on: self._params keeps what the bank was built from)
+    d = self._dev
+    torch = device._torch()
+    conv = lambda a: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a, np.float64))).to(
+        device=d['h'].device, dtype=torch.float64)
+    corr = conv(corr)
+    d['corr'].copy_((corr.unsqueeze(1) if corr.dim() == 2 else corr).expand_as(d['corr']))
+    if self.reduction == 'lda':
+      d['lda'].copy_(conv(lda).expand_as(d['lda']))
 
   # -- pushes ------------------------------------------------------------------------------------
   def _as_bank(self, eeg, env1, env2):
@@ -1737,3 +1787,294 @@ class OnlineRidgeFit(object):
       w, b = w.cpu().numpy(), b.cpu().numpy()
     model.set_weights([w, b])
     return model
+
+
+# ------------------------------------------------------------------------------------------------ the online calibration
+CalibrationResult = collections.namedtuple('CalibrationResult', ['corr', 'lda', 'dprime'])
+
+CALIB_SUMS = device.ONLINE_CALIB_SUMS      # TD_CALIB_ONLINE_SUMS
+_CALIB_REASONS = {
+    device.CALIB_NO_WINDOW: 'No data for class 0: no window of %(width)d frames is complete after %(frames)d frames',
+    device.CALIB_NO_POWER: 'the correlation power is not finite or not above zero (a constant prediction or constant '
+                           'envelopes)',
+    device.CALIB_SAME_MEANS: 'X0 and X1 in Scaled LDA are identical: the attended and the unattended window means '
+                             'are equal',
+}
+
+
+def calibration_walk(sums, pred, attended, unattended, first_frame, width):
+  """Advances one session's CALIB_SUMS float64 sums (td_calib_online_push's layout) in place by the emitted frames
+  first_frame, first_frame + 1, ...: every sum in frame order, acc += x * y in float64; when a frame completes a
+  window the classes' sum z take plain adds, their Grams G + z_i * z_j, and the open window returns to zero."""
+  for i in range(len(pred)):
+    p, a, u = float(pred[i]), float(attended[i]), float(unattended[i])
+    for at, term in ((0, p), (1, p * p), (2, a), (3, a * a), (4, u), (5, u * u),
+                     (24, p), (25, a), (26, a * p), (27, u), (28, u * p)):
+      sums[at] = sums[at] + term
+    if (first_frame + i + 1) % width == 0:
+      for base, z in ((6, (sums[28], sums[27], sums[24])), (15, (sums[26], sums[25], sums[24]))):
+        at = base + 3
+        for j in range(3):
+          sums[base + j] = sums[base + j] + z[j]
+          for k in range(j, 3):
+            sums[at] = sums[at] + z[j] * z[k]
+            at += 1
+      sums[24:29] = 0.0
+
+
+def calibration_closed_form(sums, frames, width):
+  """td_calib_online_finish for one session in NumPy float64: dict(status, count, sum_x, sum_y, sum_x2, sum_y2,
+  mean_x, mean_y, power, class_means (mbar_0, mbar_1), class_variances, slope, intercept, dprime) from the
+  CALIB_SUMS sums after `frames` emitted frames."""
+  q = np.asarray(sums, np.float64)
+  out = dict(status=device.CALIB_OK, slope=np.nan, intercept=np.nan, dprime=np.nan, class_means=(np.nan, np.nan),
+             class_variances=(np.nan, np.nan))
+  with np.errstate(all='ignore'):
+    count = np.float64(2.0 * frames)
+    sum_x, sum_x2, sum_y, sum_y2 = q[4] + q[2], q[5] + q[3], q[0] + q[0], q[1] + q[1]
+    mean_x, mean_y = sum_x / count, sum_y / count
+    power = np.sqrt((sum_x2 - sum_x * sum_x / count) * (sum_y2 - sum_y * sum_y / count)) / count
+    out.update(count=int(2 * frames), sum_x=sum_x, sum_y=sum_y, sum_x2=sum_x2, sum_y2=sum_y2, mean_x=mean_x,
+               mean_y=mean_y, power=power)
+    n_win = float(int(frames) // int(width))
+    if n_win < 1.0:
+      out.update(status=device.CALIB_NO_WINDOW, mean_x=np.nan, mean_y=np.nan, power=np.nan)
+      return out
+    if not power > 0.0 or np.isinf(power):
+      out.update(status=device.CALIB_NO_POWER, mean_x=np.nan, mean_y=np.nan, power=np.nan)
+      return out
+    scale = 1.0 / (float(width) * power)
+    cv = np.array([scale, -mean_y * scale, -mean_x * scale])
+    c0 = mean_x * mean_y / power
+    means, variances = [], []
+    for base in (6, 15):
+      z, g = q[base:base + 3], q[base + 3:base + 9]
+      cz = (cv[0] * z[0] + cv[1] * z[1]) + cv[2] * z[2]
+      quad = ((g[0] * cv[0] * cv[0] + g[3] * cv[1] * cv[1]) + g[5] * cv[2] * cv[2]) + \
+          2.0 * ((g[1] * cv[0] * cv[1] + g[2] * cv[0] * cv[2]) + g[4] * cv[1] * cv[2])
+      sm, sm2 = cz + n_win * c0, (quad + 2.0 * c0 * cz) + n_win * c0 * c0
+      means.append(sm / n_win)
+      variances.append(sm2 / n_win - means[-1] * means[-1])
+    out.update(class_means=tuple(means), class_variances=tuple(variances))
+    if means[0] == means[1] or np.isnan(means[0]) or np.isnan(means[1]):
+      out.update(status=device.CALIB_SAME_MEANS)
+      return out
+    slope = 1.0 / (means[1] - means[0])
+    out.update(slope=slope, intercept=-slope * means[0],
+               dprime=abs(means[1] - means[0]) / np.sqrt((variances[0] + variances[1]) / 2.0))
+  return out
+
+
+class _HostCalibSession(object):
+  """One online calibration session in NumPy: the semantics of td_calib_online_push with a float64 prediction (as
+  _HostSession predicts), the sums of calibration_walk."""
+
+  def __init__(self, c, pre, post, width):
+    self.c, self.pre, self.post, self.width = c, pre, post, width
+    self.reset()
+
+  def reset(self):
+    self.sums = np.zeros((CALIB_SUMS,), np.float64)
+    self.tail = np.zeros((self.pre + self.post, self.c), np.float64)
+    self.env_tail = np.zeros((self.post, 2), np.float64)
+
+  def push(self, eeg, env, w, b, frames_before, flush):
+    """eeg [n, c], env [n, 2] float64 behind frames_before rows, predicted with w [lags c] and b."""
+    c, pre, post = self.c, self.pre, self.post
+    pl = device.online_plan(frames_before, eeg.shape[0], post, 1, 1, flush)
+    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c))] if flush else []))
+    envs = np.concatenate([self.env_tail, env])
+    emitted = pl.emitted_after - pl.emitted_before
+    i0 = pl.emitted_before - (frames_before - post)   # (as _HostSession.push)
+    w = np.asarray(w, np.float32).astype(np.float64)
+    pred = np.zeros((emitted,), np.float64)
+    for l in range(pre + 1 + post):                 # (lag, channel) order, whatever the push's length
+      for ch in range(c):
+        pred += rows[i0 + l:i0 + l + emitted, ch] * w[l * c + ch]
+    pred = pred + float(b)
+    truth = envs[i0:i0 + emitted]
+    calibration_walk(self.sums, pred, truth[:, 0], truth[:, 1], pl.emitted_before, self.width)
+    both = np.concatenate([self.tail, eeg])
+    self.tail = both[both.shape[0] - (pre + post):]
+    self.env_tail = envs[envs.shape[0] - post:] if post else envs[:0]
+    return emitted
+
+
+class OnlineCalibration(object):
+  """The online chain's last training stage: the correlation statistics, the scaled LDA and d' that
+  infer_decoder.Decoder.train(data0, data1, window_size=W) would take from a labelled stretch -- data0 the
+  (unattended envelope, prediction) frames, data1 the (attended envelope, prediction) frames -- for rows that arrive
+  in pushes of any length, predicted with the bank's CURRENT weights, in ONE td_calib_online_push launch per push and
+  with nothing stored per row:
+
+      fit.push(eeg, att); w, b = fit.solve([lam]); decoder.set_weights(w[:, 0, :, 0], b[:, 0, 0])
+      calib = OnlineCalibration(decoder, window_size=100)
+      for eeg, att, unatt in calibration_chunks:         # [n, C], [n], [n] float32, any n
+        calib.push(eeg, att, unatt)
+      r = calib.finish()                                 # CalibrationResult(corr, lda, dprime), on the device
+      decoder.set_statistics(r.corr, r.lda)              # device to device
+
+  decoder: a linear OnlineDecoder bank; the sessions, the channels and the context are the bank's, and every push
+  reads the bank's weights where they are, so the calibrator follows set_weights.  window_size: the frames averaged
+  into one training point of the LDA (decoding.train_lda_model's correlation_frames, default 100; <= 1: every
+  frame).  Windows are infer_decoder.average_data's: consecutive, the tail dropped.  A frame needs post_context rows
+  of future EEG, so the sums run that far behind the input; flush() ends the recording.  finish() can be called at
+  any time and leaves the state alone.  Any cut of a recording gives the same state bytes (sums()).
+
+  Without a GPU the same object runs a NumPy session of the same semantics (float64 prediction)."""
+
+  def __init__(self, decoder, window_size=100):
+    if not isinstance(decoder, OnlineDecoder):
+      raise ValueError('OnlineCalibration calibrates an OnlineDecoder bank, not a %s.' % type(decoder).__name__)
+    if decoder.kind != 'linear':
+      raise ValueError('OnlineCalibration calibrates a linear bank, not a %s bank (CCA and DNN calibration are out '
+                       'of scope).' % decoder.kind)
+    width = max(1, int(window_size))
+    if width > MAX_WINDOW:
+      raise ValueError('OnlineCalibration takes windows of 1 to %d frames, not %d.' % (MAX_WINDOW, width))
+    self.decoder = decoder
+    self.sessions, self.channels, self.pre, self.post = decoder.sessions, decoder.channels, decoder.pre, decoder.post
+    self.window_size = width
+    self.delay = self.post
+    self._on_device = decoder._on_device
+    self._dev = self._host = None
+    if self._on_device:
+      h = decoder._dev['h']
+      nbytes = device.online_calib_state_bytes(self.channels, self.pre, self.post)
+      self._dev = dict(h=h, state=device._torch().zeros((self.sessions, nbytes), dtype=device._torch().uint8,
+                                                        device=h.device))
+    else:
+      self._host = [_HostCalibSession(self.channels, self.pre, self.post, width) for _ in range(self.sessions)]
+    self.reset()
+
+  def reset(self):
+    """A fresh calibration stretch: zero state (a memset), no row pushed."""
+    self.rows_pushed = 0
+    self.flushed = False
+    if self._dev is not None:
+      self._dev['state'].zero_()
+    if self._host is not None:
+      for sess in self._host:
+        sess.reset()
+
+  @property
+  def frames_emitted(self):
+    """The frames counted into the sums so far: post_context behind the rows pushed, all of them after flush()."""
+    return self.rows_pushed if self.flushed else max(0, self.rows_pushed - self.post)
+
+  @property
+  def windows(self):
+    """The completed windows per class."""
+    return self.frames_emitted // self.window_size
+
+  # -- pushes ------------------------------------------------------------------------------------
+  def push(self, eeg, attended, unattended):
+    """The next n rows of every session: eeg [n, C] / [S, n, C], the attended and the unattended envelope [n] /
+    [S, n], float32 device tensors (read where they are) or arrays; n may be 0.  Returns the frames counted so
+    far."""
+    if self.flushed:
+      raise ValueError('The calibration was flushed: reset() starts the next stretch.')
+    eeg, env = self.decoder._as_bank(eeg, attended, unattended)
+    if int(eeg.shape[1]) > MAX_FIT_PUSH:
+      raise ValueError('OnlineCalibration takes at most %d rows in one push, not %d.' % (MAX_FIT_PUSH, eeg.shape[1]))
+    return self._advance(eeg, env, False)
+
+  def flush(self, eeg=None, attended=None, unattended=None):
+    """The end of the stretch: the last post_context frames are counted as if zero rows followed -- behind the
+    stretch's last rows, when they are given (one launch for both).  After it the calibration refuses pushes until
+    reset(); sums() and finish() stay."""
+    if self.flushed:
+      raise ValueError('The calibration was flushed: reset() starts the next stretch.')
+    given = [a is not None for a in (eeg, attended, unattended)]
+    if any(given) and not all(given):
+      raise ValueError('OnlineCalibration.flush takes the last rows as eeg AND both envelopes, or nothing.')
+    env = None
+    if eeg is not None:
+      eeg, env = self.decoder._as_bank(eeg, attended, unattended)
+      if int(eeg.shape[1]) > MAX_FIT_PUSH:
+        raise ValueError('OnlineCalibration takes at most %d rows in one push, not %d.' % (MAX_FIT_PUSH, eeg.shape[1]))
+    return self._advance(eeg, env, True)
+
+  def _advance(self, eeg, env, flush):
+    n = 0 if eeg is None else int(eeg.shape[1])
+    if not self._on_device:
+      if eeg is None:
+        eeg = np.zeros((self.sessions, 0, self.channels), np.float32)
+        env = np.zeros((self.sessions, 0, 2), np.float32)
+      for i, sess in enumerate(self._host):
+        p = self.decoder._params[i]
+        sess.push(np.asarray(eeg[i], np.float64), np.asarray(env[i], np.float64), p['w'], p['b'], self.rows_pushed,
+                  flush)
+    else:
+      d, bank = self._dev, self.decoder._dev
+      h = d['h']
+      if n == 0:
+        eeg = env = None
+      elif not hasattr(eeg, 'is_cuda'):
+        eeg, env = h.to_device(eeg.reshape(-1, self.channels)).reshape(eeg.shape), \
+            h.to_device(env.reshape(-1, 2)).reshape(env.shape)
+      device.online_calib_push(eeg, env, bank['w'], bank['b'], d['state'], self.rows_pushed, self.pre, self.post,
+                               self.window_size, c=self.channels, flush=flush, handle=h)
+    self.rows_pushed += n
+    self.flushed = bool(flush)
+    return self.frames_emitted
+
+  # -- what the state holds ----------------------------------------------------------------------
+  def sums(self):
+    """[S, 29] float64, td_calib_online_sums' order: sum p, p^2, a, a^2, u, u^2 over every counted frame (p the
+    prediction, a / u the attended / unattended envelope) | class 0 (unattended): sum_w z [3] and the upper triangle
+    of sum_w z z^T [6], z = a window's (sum x p, sum x, sum p) | class 1 (attended) | the open window's sum p, a,
+    a p, u, u p.  A device tensor on the device, else a host array."""
+    if self._dev is None:
+      return np.stack([sess.sums for sess in self._host])
+    return device.online_calib_sums(self._dev['state'], handle=self._dev['h'])
+
+  def _raise(self, status):
+    for i, st in enumerate(status):
+      if int(st) != device.CALIB_OK:
+        reason = _CALIB_REASONS[int(st)] % dict(width=self.window_size, frames=self.frames_emitted)
+        raise ValueError('OnlineCalibration.finish: session %d: %s.' % (i, reason))
+
+  def finish(self):
+    """CalibrationResult(corr [S, 2, 3] {mean_truth, mean_pred, power} for both speakers, lda [S, 3] {1, slope,
+    intercept}, dprime [S]) float64 from the sums so far -- what OnlineDecoder.set_statistics takes; device tensors
+    on the device (one launch; the statuses come back in one small copy), else host arrays.  The state is not
+    modified.  ValueError naming the session and the reason: no completed window (train's 'No data for class'), a
+    power that is not finite or not above zero, equal class means (scaled LDA's 'X0 and X1 ... identical')."""
+    if self._dev is None:
+      outs = [calibration_closed_form(sess.sums, self.frames_emitted, self.window_size) for sess in self._host]
+      self._raise([o['status'] for o in outs])
+      stats = [[o['mean_x'], o['mean_y'], o['power']] for o in outs]
+      return CalibrationResult(np.array([[st, st] for st in stats], np.float64),
+                               np.array([[1.0, o['slope'], o['intercept']] for o in outs], np.float64),
+                               np.array([o['dprime'] for o in outs], np.float64))
+    out = device.online_calib_finish(self._dev['state'], self.frames_emitted, self.window_size,
+                                     handle=self._dev['h'])
+    self._raise(out.status.cpu().numpy())
+    return CalibrationResult(out.corr, out.lda, out.dprime)
+
+  def update_decoder(self, decoder, session=0):
+    """Gives an infer_decoder.LinearRegressionDecoder the correlation parameters and the scaled LDA of one session
+    (what Decoder.train leaves in it), so that save_parameters writes them.  Returns d'."""
+    from telluride_decoding_amd import scaled_lda
+    if not isinstance(decoder, infer_decoder.LinearRegressionDecoder):
+      raise ValueError('OnlineCalibration.update_decoder takes a LinearRegressionDecoder, not a %s.' %
+                       type(decoder).__name__)
+    if not 0 <= int(session) < self.sessions:
+      raise ValueError('OnlineCalibration.update_decoder: session %d of %d.' % (int(session), self.sessions))
+    sums = self.sums()[int(session)]
+    if hasattr(sums, 'cpu'):
+      sums = sums.cpu().numpy()
+    o = calibration_closed_form(sums, self.frames_emitted, self.window_size)
+    if o['status'] != device.CALIB_OK:
+      status = [device.CALIB_OK] * self.sessions
+      status[int(session)] = o['status']
+      self._raise(status)
+    vec = lambda v: np.array([v], np.float64)
+    decoder.model_params = infer_decoder.ModelParamsTuple(
+        infer_decoder.CorrelationParamsTuple(o['count'], vec(o['sum_x']), vec(o['sum_y']), vec(o['sum_x2']),
+                                             vec(o['sum_y2']), vec(o['mean_x']), vec(o['mean_y']), vec(o['power'])),
+        scaled_lda.LdaParamsTuple(np.ones((1, 1)), np.zeros((1, 1)), [1, 2],
+                                  [vec(o['class_means'][0]), vec(o['class_means'][1])], float(o['slope']),
+                                  float(o['intercept'])))
+    return float(o['dprime'])
