@@ -10,7 +10,7 @@
 // mean is window_means_kernel's sum (256 threads stride the window, 64-lane wave sums, ((w0 + w1) +
 // (w2 + w3)) / width) and the decisions are decide_wta_kernel's / decide_step_kernel's operations
 // (windows.hip).  No atomics.
-#include "td_common.h"
+#include "online_common.h"
 
 namespace {
 
@@ -19,34 +19,8 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kMaxChannels = 128, kMaxLags = 64;
 constexpr int kPass = 64;       // emitted frames per pass of a workgroup (fewer for a short push: less LDS)
 
-// One session's state block: [stepped state f64][ring f64 [2][width]][EEG tail f32 [pre + post][c]]
+// One session's state block (online_common.h): [stepped state f64][ring f64 [2][width]][EEG tail f32 [pre + post][c]]
 // [envelope tail f32 [post][2]], rounded up to 8 bytes.
-__host__ __device__ inline long long state_ring_offset() { return 8; }
-__host__ __device__ inline long long state_eeg_offset(int width) { return 8 + 16LL * width; }
-__host__ __device__ inline long long state_env_offset(int c, int pre, int post, int width) {
-  return state_eeg_offset(width) + 4LL * c * (pre + post);
-}
-__host__ __device__ inline long long state_bytes(int c, int pre, int post, int width) {
-  return (state_env_offset(c, pre, post, width) + 8LL * post + 7) / 8 * 8;
-}
-
-long long windows_of(long long frames, int width, int hop) {      // td_window_count of one trial
-  return frames >= width ? (frames - width) / hop + 1 : 0;
-}
-
-struct OnlinePlan {
-  long long emitted_before, emitted_after, first_window, new_windows;
-};
-
-OnlinePlan plan_push(long long frames_before, long long n, int post, int width, int hop, int flush) {
-  OnlinePlan pl;
-  const long long pushed = frames_before + n;
-  pl.emitted_before = frames_before > post ? frames_before - post : 0;
-  pl.emitted_after = flush ? pushed : (pushed > post ? pushed - post : 0);
-  pl.first_window = windows_of(pl.emitted_before, width, hop);
-  pl.new_windows = windows_of(pl.emitted_after, width, hop) - pl.first_window;
-  return pl;
-}
 
 struct OnlineParams {
   const float* eeg; long long eeg_ld, eeg_ss;
@@ -62,39 +36,6 @@ struct OnlineParams {
   unsigned char* state; long long state_ss;
   double* scores; unsigned char* decisions; float* pred; double* frame;
 };
-
-// (windows.hip's wave_sum: the same shuffle tree, the same bits)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// frame_scores_kernel's value for ONE column (windows.hip): a = the truth, b = the prediction.  The sums
-// over the columns start from 0.0 there, so they do here; the lda map is that kernel's one fused
-// multiply-add (slope * acc + intercept, contracted).
-__device__ __forceinline__ double frame_score(float truth, float pred, double mean_a, double mean_b,
-                                              double power, int reduction, double lda_w,
-                                              double lda_slope, double lda_intercept) {
-  const double v = ((double)truth - mean_a) * ((double)pred - mean_b) / power;
-  if (reduction == 0) return v;
-  double acc = 0.0;
-  if (reduction == 2) {
-    acc += v;
-  } else if (reduction == 3) {
-    acc += (v > 0.0 ? v * v : (v < 0.0 ? -v * v : 0.0));
-  } else {
-    acc += v * lda_w;
-    acc = fma(lda_slope, acc, lda_intercept);
-  }
-  return acc;
-}
 
 __global__ __launch_bounds__(kThreads) void online_push_kernel(OnlineParams p) {
   extern __shared__ double lds[];
@@ -125,48 +66,18 @@ __global__ __launch_bounds__(kThreads) void online_push_kernel(OnlineParams p) {
   const long long emitted_now = p.e1 - p.e0;
 
   for (int k = tid; k < k_all; k += kThreads) w_s[k] = w[k];
-  double step = 0.5;
-  if (tid == 0 && p.decoder == 1) {
-    const double stored = *step_p;
-    step = stored == 0.0 ? 0.5 : stored;
-  }
+  double step = load_step(step_p, p.decoder);
 
   for (long long a = p.e0; a < p.e1; a += pass) {
     const int nf = (int)(p.e1 - a < pass ? p.e1 - a : pass);     // frames [a, a + nf) of this pass
-    // ---- stage the EEG rows a - pre .. a + nf - 1 + post and the envelope rows a .. a + nf - 1: from the
-    // tails (rows before this push), from the push, zeros before the recording and behind a flushed end
-    const int n_rows = nf + tl;
-    for (int rr = wave; rr < n_rows; rr += kWaves) {
-      const long long row = a - pre + rr;
-      for (int ch = lane; ch < c; ch += 64) {
-        float v = 0.f;
-        if (row >= 0 && row < p0) v = tail[(row - (p0 - tl)) * c + ch];
-        else if (row >= p0 && row < p1) v = eeg[(row - p0) * p.eeg_ld + ch];
-        rows_s[rr * c + ch] = v;
-      }
-    }
-    for (int i = tid; i < 2 * nf; i += kThreads) {
-      const long long row = a + (i >> 1);
-      env_s[i] = row < p0 ? etail[(row - (p0 - post)) * 2 + (i & 1)] : env[(row - p0) * p.env_ld + (i & 1)];
-    }
+    // ---- stage the EEG rows a - pre .. a + nf - 1 + post and the envelope rows a .. a + nf - 1
+    stage_rows<kThreads>(rows_s, c, tail, tl, eeg, p.eeg_ld, c, a - pre, nf + tl, p0, p1);
+    stage_env<kThreads>(env_s, etail, post, env, p.env_ld, a, nf, p0);
     __syncthreads();
-    // ---- predictions: a wave per frame; lane q takes the terms k = q, q + 64, ... of the (lag, channel)
-    // sum into four accumulators in turn, ((a0 + a1) + (a2 + a3)), then the 64-lane tree, then the bias
+    // ---- predictions: a wave per frame
     for (int f = wave; f < nf; f += kWaves) {
-      const float* xr = rows_s + f * c;
-      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-      int k = lane;
-      for (; k + 192 < k_all; k += 256) {
-        a0 = fmaf(w_s[k], xr[k], a0);
-        a1 = fmaf(w_s[k + 64], xr[k + 64], a1);
-        a2 = fmaf(w_s[k + 128], xr[k + 128], a2);
-        a3 = fmaf(w_s[k + 192], xr[k + 192], a3);
-      }
-      if (k < k_all) a0 = fmaf(w_s[k], xr[k], a0);
-      if (k + 64 < k_all) a1 = fmaf(w_s[k + 64], xr[k + 64], a1);
-      if (k + 128 < k_all) a2 = fmaf(w_s[k + 128], xr[k + 128], a2);
-      const float total = wave_sum_f32((a0 + a1) + (a2 + a3));
-      if (lane == 0) pred_s[f] = total + bias;
+      const float pr = fir_predict(w_s, rows_s + f * c, k_all, bias);
+      if (lane == 0) pred_s[f] = pr;
     }
     __syncthreads();
     // ---- per-frame scores of both speakers
@@ -181,79 +92,19 @@ __global__ __launch_bounds__(kThreads) void online_push_kernel(OnlineParams p) {
       if (p.pred && spk == 0) p.pred[at] = pr;
     }
     __syncthreads();
-    // ---- the windows that end in (a, a + nf]: window wi = frames [wi hop, wi hop + width).  A WAVE forms a
-    // window's mean with window_means_kernel's operations: lane q stands in for the threads q, q + 64,
-    // q + 128, q + 192 of that kernel's workgroup (four partial sums, four wave sums).  Frames before
-    // `a` come from the ring, which holds the `width` frames before `a` until this pass has stored its own.
-    const long long end_lo = a + 1 > width ? a + 1 : width;      // the first window end in reach
-    const long long wi_lo = (end_lo - width + hop - 1) / hop;
-    const long long wi_hi = a + nf >= width ? (a + nf - width) / hop + 1 : 0;   // one past the last
-    const int nw = wi_hi > wi_lo ? (int)(wi_hi - wi_lo) : 0;
-    for (int j = wave; j < nw; j += kWaves) {
-      const long long r0 = (wi_lo + j) * hop;
-      const int slot0 = (int)(r0 % width);                       // ring slot of the window's first frame
-#pragma unroll
-      for (int spk = 0; spk < 2; ++spk) {
-        double part[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          double acc = 0.0;
-          for (int r = 64 * q + lane; r < width; r += kThreads) {
-            const long long fr = r0 + r;
-            const int slot = slot0 + r - (slot0 + r >= width ? width : 0);
-            acc += fr >= a ? sc_s[spk * pass + (int)(fr - a)] : ring[(long long)spk * width + slot];
-          }
-          part[q] = wave_sum(acc);
-        }
-        if (lane == 0) {
-          const double m = ((part[0] + part[1]) + (part[2] + part[3])) / (double)width;
-          wm_s[spk * pass + j] = m;
-          p.scores[((long long)spk * gridDim.x + s) * p.n_win + (wi_lo + j - p.w0)] = m;
-        }
-      }
-    }
-    __syncthreads();
-    // ---- decisions (decide_wta_kernel / decide_step_kernel), the ring, then the next pass
-    unsigned char* dec = p.decisions + (long long)s * p.n_win + (wi_lo - p.w0);
-    if (p.decoder == 1) {
-      if (tid == 0) {
-        for (int j = 0; j < nw; ++j) {
-          if (wm_s[j] > wm_s[pass + j]) step = fmin(0.9, step + 0.1);
-          else step = fmax(0.1, step - 0.1);
-          dec[j] = step > 0.5 ? 1 : 0;
-        }
-      }
-    } else {
-      for (int j = tid; j < nw; j += kThreads)
-        dec[j] = p.decoder == 0 ? (wm_s[j] > wm_s[pass + j] ? 1 : 0) : 0;
-    }
-    // (a pass longer than the ring: only its last `width` frames, one per slot)
-    const int slot_a = (int)(a % width);
-    for (int i = tid; i < 2 * nf; i += kThreads) {
-      const int spk = i / nf, f = i - spk * nf;
-      if (nf - f <= width) ring[(long long)spk * width + (slot_a + f) % width] = sc_s[spk * pass + f];
-    }
-    __threadfence_block();
-    __syncthreads();
+    // ---- the windows that end in (a, a + nf], their decisions, the ring, then the next pass
+    window_block<kThreads, kThreads>(sc_s, wm_s, ring, pass, a, nf, width, hop, p.decoder, step, p.w0, p.n_win,
+                                     p.scores, p.decisions);
   }
 
-  // ---- the tails for the next push: the last pre + post EEG rows and the last post envelope rows of
-  // (old tail, this push).  A push shorter than a tail shifts it: the rows that stay go through LDS.
+  // ---- the tails for the next push: the last pre + post EEG rows and the last post envelope rows
   __syncthreads();
-  const long long n = p.n;
-  const int keep = n < tl ? (int)(tl - n) : 0;                   // old EEG rows that stay
-  for (int i = tid; i < keep * c; i += kThreads) rows_s[i] = tail[(tl - keep) * c + i];
-  const int ekeep = n < post ? (int)(post - n) : 0;
-  for (int i = tid; i < ekeep * 2; i += kThreads) env_s[i] = etail[(post - ekeep) * 2 + i];
+  tail_park<kThreads>(rows_s, tail, tl, c, p.n);
+  env_tail_park<kThreads>(env_s, etail, post, p.n);
   __syncthreads();
-  for (int rr = wave; rr < tl; rr += kWaves)
-    for (int ch = lane; ch < c; ch += 64)
-      tail[rr * c + ch] = rr < keep ? rows_s[rr * c + ch] : eeg[(n - (tl - rr)) * p.eeg_ld + ch];
-  for (int i = tid; i < post * 2; i += kThreads) {
-    const int rr = i >> 1;
-    etail[i] = rr < ekeep ? env_s[i] : env[(n - (post - rr)) * p.env_ld + (i & 1)];
-  }
-  if (tid == 0 && p.decoder == 1) *step_p = step;
+  tail_store<kThreads>(tail, rows_s, tl, c, eeg, p.eeg_ld, p.n);
+  env_tail_store<kThreads>(etail, env_s, post, env, p.env_ld, p.n);
+  store_step(step_p, p.decoder, step);
 }
 
 size_t lds_bytes(int c, int nl, int post, int pass) {
@@ -268,9 +119,7 @@ extern "C" {
 
 int td_online_state_bytes(int c, int pre, int post, int width, int64_t* bytes) {
   if (!bytes) return td_fail(nullptr, TD_ERR_INVALID, "td_online_state_bytes: NULL argument");
-  TD_REQUIRE(nullptr, c >= 1 && c <= kMaxChannels, "td_online_state_bytes: %d channels (1 .. %d)", c, kMaxChannels);
-  TD_REQUIRE(nullptr, pre >= 0 && post >= 0 && pre + 1 + post <= kMaxLags,
-             "td_online_state_bytes: context of %d + 1 + %d frames (at most %d lags)", pre, post, kMaxLags);
+  TD_TRY(check_context(nullptr, "td_online_state_bytes", c, pre, post, kMaxChannels, kMaxLags));
   TD_REQUIRE(nullptr, width >= 1 && width <= TD_ONLINE_MAX_WIDTH,
              "td_online_state_bytes: window of %d frames (1 .. %d)", width, TD_ONLINE_MAX_WIDTH);
   *bytes = state_bytes(c, pre, post, width);
@@ -301,35 +150,15 @@ int td_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t
                    uint8_t* decisions_dev, float* pred_dev, double* frame_dev) {
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_online_push: handle is NULL");
   TD_REQUIRE(h, num_sessions >= 1, "td_online_push: %d sessions", num_sessions);
-  TD_REQUIRE(h, c >= 1 && c <= kMaxChannels, "td_online_push: %d channels (1 .. %d)", c, kMaxChannels);
-  TD_REQUIRE(h, pre >= 0 && post >= 0 && pre + 1 + post <= kMaxLags,
-             "td_online_push: context of %d + 1 + %d frames (at most %d lags)", pre, post, kMaxLags);
-  TD_REQUIRE(h, n >= 0 && n <= TD_ONLINE_MAX_PUSH, "td_online_push: %lld frames in one push (0 .. %d)",
-             (long long)n, TD_ONLINE_MAX_PUSH);
-  TD_REQUIRE(h, width >= 1 && width <= TD_ONLINE_MAX_WIDTH, "td_online_push: window of %d frames (1 .. %d)",
-             width, TD_ONLINE_MAX_WIDTH);
-  TD_REQUIRE(h, hop >= 1, "td_online_push: window step of %d frames", hop);
-  TD_REQUIRE(h, reduction == 0 || reduction == 2 || reduction == 3 || reduction == 4,
-             "td_online_push: reduction %d (0 first, 2 mean, 3 mean-squared, 4 lda)", reduction);
-  TD_REQUIRE(h, reduction != 4 || lda_dev, "td_online_push: the lda reduction needs lda_dev");
-  TD_REQUIRE(h, decoder >= 0 && decoder <= 2, "td_online_push: decoder %d (0 winner-take-all, 1 stepped, 2 none)",
-             decoder);
-  TD_REQUIRE(h, frames_before >= 0, "td_online_push: %lld frames before", (long long)frames_before);
+  TD_TRY(check_context(h, "td_online_push", c, pre, post, kMaxChannels, kMaxLags));
+  TD_TRY(check_push_args(h, "td_online_push", n, width, hop, reduction, 0, lda_dev, decoder, frames_before));
   if (!w_dev || !b_dev || !corr_dev || !state_dev || !scores_dev || !decisions_dev || (n > 0 && (!eeg_dev || !env_dev)))
     return td_fail(h, TD_ERR_INVALID, "td_online_push: NULL argument");
-  TD_REQUIRE(h, eeg_ld >= c && env_ld >= 2, "td_online_push: a row stride below a row (%lld for %d channels, %lld for 2 envelopes)",
-             (long long)eeg_ld, c, (long long)env_ld);
-  TD_REQUIRE(h, num_sessions == 1 || (eeg_session_stride >= c && env_session_stride >= 2),
-             "td_online_push: a session stride below a row");
+  TD_TRY(check_push_strides(h, "td_online_push", num_sessions, eeg_ld, eeg_session_stride, c, env_ld,
+                            env_session_stride, 2, "envelopes"));
   const int nl = pre + 1 + post;
-  TD_REQUIRE(h, w_session_stride == 0 || w_session_stride >= (int64_t)nl * c,
-             "td_online_push: a weight stride of %lld for %d weights (0 = one model)", (long long)w_session_stride, nl * c);
-  TD_REQUIRE(h, b_session_stride == 0 || b_session_stride >= 1, "td_online_push: a bias stride of %lld",
-             (long long)b_session_stride);
-  const long long sbytes = state_bytes(c, pre, post, width);
-  TD_REQUIRE(h, state_session_stride >= sbytes && state_session_stride % 8 == 0,
-             "td_online_push: a state stride of %lld bytes (a multiple of 8, at least %lld)",
-             (long long)state_session_stride, sbytes);
+  TD_TRY(check_fir_strides(h, "td_online_push", w_session_stride, b_session_stride, nl * c));
+  TD_TRY(check_state_stride(h, "td_online_push", state_session_stride, state_bytes(c, pre, post, width)));
   if (n == 0 && !flush) return TD_OK;
   const OnlinePlan pl = plan_push(frames_before, n, post, width, hop, flush);
   OnlineParams p;

@@ -17,9 +17,8 @@
 // then the EEG tail [pre + post][c] and the envelope tail [post][2] in float32, as td_online_push's block carries
 // them, rounded up to 8 bytes.  Windows are infer_decoder.average_data's: consecutive, hop = width, the tail dropped.
 //
-// The prediction of an emitted frame is the float32 value td_online_push returns in `pred`: the same loop, restated
-// here (lane q takes the terms q, q + 64, ... into four fmaf accumulators in turn, ((a0 + a1) + (a2 + a3)), the
-// 64-lane tree, + bias).
+// The prediction of an emitted frame is the float32 value td_online_push returns in `pred`: the same function
+// (online_common.h's fir_predict, whose bits do not depend on this file's contraction mode).
 //
 // The sums advance in frame order, one lane per state double: the 29 accumulators are independent, so lane t of the
 // first wave owns double t and walks a pass's frames from LDS; a lane of a class sum keeps its own copy of the one or
@@ -34,7 +33,7 @@
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are in DESIGN.md section 35.
 #include <cmath>
 
-#include "td_common.h"
+#include "online_common.h"
 
 #pragma clang fp contract(off)
 
@@ -47,12 +46,13 @@ constexpr int kPass = 64;       // emitted frames per pass of a workgroup (fewer
 constexpr int kSums = TD_CALIB_ONLINE_SUMS;
 constexpr int kOpen = 24;       // the first of the open window's five sums
 
+// (online_common.h's tails behind a head of kSums doubles)
 __host__ __device__ inline long long state_eeg_offset() { return 8LL * kSums; }
 __host__ __device__ inline long long state_env_offset(int c, int pre, int post) {
-  return state_eeg_offset() + 4LL * c * (pre + post);
+  return tail_end(state_eeg_offset(), c, pre + post);
 }
 __host__ __device__ inline long long state_bytes(int c, int pre, int post) {
-  return (state_env_offset(c, pre, post) + 8LL * post + 7) / 8 * 8;
+  return tails_bytes(state_eeg_offset(), c, pre + post, 2LL * post);
 }
 
 struct CalibParams {
@@ -65,13 +65,6 @@ struct CalibParams {
   int c, pre, post, width, pass;
   unsigned char* state; long long state_ss;
 };
-
-// (online.hip's wave_sum_f32: the same shuffle tree, the same bits)
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // What a lane of the walk does with its state double.  A frame's values sit in LDS as {1, p, a, u}; a term is the
 // product of two of them (f0, f1: indices into that quadruple).
@@ -144,42 +137,16 @@ __global__ __launch_bounds__(kThreads) void online_calib_push_kernel(CalibParams
 
   for (long long a = p.e0; a < p.e1; a += pass) {
     const int nf = (int)(p.e1 - a < pass ? p.e1 - a : pass);     // frames [a, a + nf) of this pass
-    // ---- stage the EEG rows a - pre .. a + nf - 1 + post and the envelope rows a .. a + nf - 1: from the
-    // tails (rows before this push), from the push, zeros before the recording and behind a flushed end
-    const int n_rows = nf + tl;
-    for (int rr = wave; rr < n_rows; rr += kWaves) {
-      const long long row = a - pre + rr;
-      for (int ch = lane; ch < c; ch += 64) {
-        float v = 0.f;
-        if (row >= 0 && row < p0) v = tail[(row - (p0 - tl)) * c + ch];
-        else if (row >= p0 && row < p1) v = eeg[(row - p0) * p.eeg_ld + ch];
-        rows_s[rr * c + ch] = v;
-      }
-    }
-    for (int i = tid; i < 2 * nf; i += kThreads) {
-      const long long row = a + (i >> 1);
-      env_s[i] = row < p0 ? etail[(row - (p0 - post)) * 2 + (i & 1)] : env[(row - p0) * p.env_ld + (i & 1)];
-    }
+    // ---- stage the EEG rows a - pre .. a + nf - 1 + post and the envelope rows a .. a + nf - 1
+    stage_rows<kThreads>(rows_s, c, tail, tl, eeg, p.eeg_ld, c, a - pre, nf + tl, p0, p1);
+    stage_env<kThreads>(env_s, etail, post, env, p.env_ld, a, nf, p0);
     __syncthreads();
-    // ---- predictions, td_online_push's: a wave per frame; lane q takes the terms k = q, q + 64, ... of the
-    // (lag, channel) sum into four accumulators in turn, ((a0 + a1) + (a2 + a3)), the 64-lane tree, the bias
+    // ---- predictions, td_online_push's: a wave per frame
     for (int f = wave; f < nf; f += kWaves) {
-      const float* xr = rows_s + f * c;
-      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-      int k = lane;
-      for (; k + 192 < k_all; k += 256) {
-        a0 = fmaf(w_s[k], xr[k], a0);
-        a1 = fmaf(w_s[k + 64], xr[k + 64], a1);
-        a2 = fmaf(w_s[k + 128], xr[k + 128], a2);
-        a3 = fmaf(w_s[k + 192], xr[k + 192], a3);
-      }
-      if (k < k_all) a0 = fmaf(w_s[k], xr[k], a0);
-      if (k + 64 < k_all) a1 = fmaf(w_s[k + 64], xr[k + 64], a1);
-      if (k + 128 < k_all) a2 = fmaf(w_s[k + 128], xr[k + 128], a2);
-      const float total = wave_sum_f32((a0 + a1) + (a2 + a3));
+      const float pr = fir_predict(w_s, rows_s + f * c, k_all, bias);
       if (lane == 0) {
         val_s[4 * f] = 1.0;
-        val_s[4 * f + 1] = (double)(total + bias);
+        val_s[4 * f + 1] = (double)pr;
         val_s[4 * f + 2] = (double)env_s[2 * f];
         val_s[4 * f + 3] = (double)env_s[2 * f + 1];
       }
@@ -217,22 +184,13 @@ __global__ __launch_bounds__(kThreads) void online_calib_push_kernel(CalibParams
     __syncthreads();
   }
 
-  // ---- the tails for the next push (td_online_push's): the last pre + post EEG rows and the last post envelope
-  // rows of (old tail, this push).  A push shorter than a tail shifts it: the rows that stay go through LDS.
+  // ---- the tails for the next push: the last pre + post EEG rows and the last post envelope rows
   __syncthreads();
-  const long long n = p.n;
-  const int keep = n < tl ? (int)(tl - n) : 0;                   // old EEG rows that stay
-  for (int i = tid; i < keep * c; i += kThreads) rows_s[i] = tail[(tl - keep) * c + i];
-  const int ekeep = n < post ? (int)(post - n) : 0;
-  for (int i = tid; i < ekeep * 2; i += kThreads) env_s[i] = etail[(post - ekeep) * 2 + i];
+  tail_park<kThreads>(rows_s, tail, tl, c, p.n);
+  env_tail_park<kThreads>(env_s, etail, post, p.n);
   __syncthreads();
-  for (int rr = wave; rr < tl; rr += kWaves)
-    for (int ch = lane; ch < c; ch += 64)
-      tail[rr * c + ch] = rr < keep ? rows_s[rr * c + ch] : eeg[(n - (tl - rr)) * p.eeg_ld + ch];
-  for (int i = tid; i < post * 2; i += kThreads) {
-    const int rr = i >> 1;
-    etail[i] = rr < ekeep ? env_s[i] : env[(n - (post - rr)) * p.env_ld + (i & 1)];
-  }
+  tail_store<kThreads>(tail, rows_s, tl, c, eeg, p.eeg_ld, p.n);
+  env_tail_store<kThreads>(etail, env_s, post, env, p.env_ld, p.n);
   // (every lane read the open sums it copies before the first pass; the barriers since then order these stores
   // behind those loads)
   if (role != kIdle && p.e1 > p.e0) sums[tid] = acc;
@@ -319,8 +277,7 @@ int check_state(td_handle* h, const char* who, int num_sessions, const void* sta
                 long long need) {
   TD_REQUIRE(h, num_sessions >= 1 && num_sessions <= 65535, "%s: %d sessions (1 .. 65535)", who, num_sessions);
   if (!state_dev) return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
-  TD_REQUIRE(h, stride >= need && stride % 8 == 0, "%s: a state stride of %lld bytes (a multiple of 8, at least %lld)",
-             who, (long long)stride, need);
+  TD_TRY(check_state_stride(h, who, stride, need));
   return TD_OK;
 }
 
@@ -358,27 +315,19 @@ int td_calib_online_push(td_handle* h, int num_sessions, const float* eeg_dev, i
                      state_bytes(c, pre, post)));
   if (!w_dev || !b_dev || (n > 0 && (!eeg_dev || !env_dev)))
     return td_fail(h, TD_ERR_INVALID, "td_calib_online_push: NULL argument");
-  TD_REQUIRE(h, n == 0 || (eeg_ld >= c && env_ld >= 2),
-             "td_calib_online_push: a row stride below a row (%lld for %d channels, %lld for 2 envelopes)",
-             (long long)eeg_ld, c, (long long)env_ld);
-  TD_REQUIRE(h, n == 0 || num_sessions == 1 || (eeg_session_stride >= c && env_session_stride >= 2),
-             "td_calib_online_push: a session stride below a row");
+  if (n > 0)
+    TD_TRY(check_push_strides(h, "td_calib_online_push", num_sessions, eeg_ld, eeg_session_stride, c, env_ld,
+                              env_session_stride, 2, "envelopes"));
   const int nl = pre + 1 + post;
-  TD_REQUIRE(h, w_session_stride == 0 || w_session_stride >= (int64_t)nl * c,
-             "td_calib_online_push: a weight stride of %lld for %d weights (0 = one model)",
-             (long long)w_session_stride, nl * c);
-  TD_REQUIRE(h, b_session_stride == 0 || b_session_stride >= 1, "td_calib_online_push: a bias stride of %lld",
-             (long long)b_session_stride);
+  TD_TRY(check_fir_strides(h, "td_calib_online_push", w_session_stride, b_session_stride, nl * c));
   if (n == 0 && !flush) return TD_OK;
-  // td_online_plan's arithmetic
-  const long long pushed = frames_before + n;
+  const OnlinePlan pl = plan_push(frames_before, n, post, width, width, flush);   // (its windows: hop = width)
   CalibParams p;
   p.eeg = eeg_dev; p.eeg_ld = eeg_ld; p.eeg_ss = num_sessions > 1 ? eeg_session_stride : 0;
   p.env = env_dev; p.env_ld = env_ld; p.env_ss = num_sessions > 1 ? env_session_stride : 0;
   p.w = w_dev; p.w_ss = w_session_stride; p.b = b_dev; p.b_ss = b_session_stride;
   p.n = n; p.p0 = frames_before;
-  p.e0 = frames_before > post ? frames_before - post : 0;
-  p.e1 = flush ? pushed : (pushed > post ? pushed - post : 0);
+  p.e0 = pl.emitted_before; p.e1 = pl.emitted_after;
   p.c = c; p.pre = pre; p.post = post; p.width = width;
   const long long emitted_now = p.e1 - p.e0;
   p.pass = emitted_now < kPass ? (emitted_now > 1 ? (int)emitted_now : 1) : kPass;

@@ -16,7 +16,7 @@
 // column, the same addresses modulo nothing -- no bank conflict whatever k1 is -- and the lagged row of a frame is
 // contiguous in the staged rows (row f + l at (f + l) c + ch = f c + k), so x~, the mean and the rotation column
 // are three unit-stride LDS streams.  No atomics, vector stores only.
-#include "td_common.h"
+#include "online_common.h"
 
 namespace {
 
@@ -31,13 +31,11 @@ constexpr long long kLdsBudget = TD_CCA_ONLINE_LDS_BYTES;
 // One session's state block: [stepped state f64][ring f64 [2][width]][EEG tail f32 [pre1 + post][c1]]
 // [feature tail f32 [2][pre2 + post][c2]], rounded up to 8 bytes; post = max(post1, post2).
 __host__ __device__ inline int delay_of(int post1, int post2) { return post1 > post2 ? post1 : post2; }
-__host__ __device__ inline long long state_ring_offset() { return 8; }
-__host__ __device__ inline long long state_eeg_offset(int width) { return 8 + 16LL * width; }
 __host__ __device__ inline long long state_feat_offset(int c1, int pre1, int post, int width) {
-  return state_eeg_offset(width) + 4LL * c1 * (pre1 + post);
+  return tail_end(state_eeg_offset(width), c1, pre1 + post);
 }
 __host__ __device__ inline long long state_bytes(int c1, int pre1, int c2, int pre2, int post, int width) {
-  return (state_feat_offset(c1, pre1, post, width) + 8LL * c2 * (pre2 + post) + 7) / 8 * 8;
+  return tails_bytes(state_eeg_offset(width), c1, pre1 + post, 2LL * c2 * (pre2 + post));
 }
 
 // Rows of the staging areas: a pass reads nf + pre + post_v rows of a view; the tail shift at the end of a
@@ -78,19 +76,6 @@ struct CcaOnlineParams {
   unsigned char* state; long long state_ss;
   double* scores; unsigned char* decisions; float* proj; double* frame;
 };
-
-// (windows.hip's wave_sum: the same shuffle tree, the same bits)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // frame_scores_kernel's value (windows.hip) of one row: a = the EEG view's projection, b = a speaker's.  That
 // kernel's operations one for one -- the column's value v, a plain add of v, of +-v v or of the PRODUCT v lda_w
@@ -202,27 +187,14 @@ __global__ __launch_bounds__(kThreads) void cca_online_push_kernel(CcaOnlinePara
     const int k = i / dims, d = i - k * dims;
     rot2_s[d * k2 + k] = rot_y[i];
   }
-  double step = 0.5;
-  if (tid == 0 && p.decoder == 1) {
-    const double stored = *step_p;
-    step = stored == 0.0 ? 0.5 : stored;
-  }
+  double step = load_step(step_p, p.decoder);
 
   for (long long a = p.e0; a < p.e1; a += pass) {
     const int nf = (int)(p.e1 - a < pass ? p.e1 - a : pass);     // frames [a, a + nf) of this pass
     // ---- stage the EEG rows a - pre1 .. a + nf - 1 + post1 and each speaker's feature rows a - pre2 ..
     // a + nf - 1 + post2: from the tails (rows before this push), from the push, zeros before the recording
     // and behind a flushed end
-    const int n_rows1 = nf + pre1 + post1;
-    for (int rr = wave; rr < n_rows1; rr += kWaves) {
-      const long long row = a - pre1 + rr;
-      for (int ch = lane; ch < c1; ch += 64) {
-        float v = 0.f;
-        if (row >= 0 && row < p0) v = tail1[(row - (p0 - t1)) * c1 + ch];
-        else if (row >= p0 && row < p1) v = eeg[(row - p0) * p.eeg_ld + ch];
-        rows1_s[rr * c1 + ch] = v;
-      }
-    }
+    stage_rows<kThreads>(rows1_s, c1, tail1, t1, eeg, p.eeg_ld, c1, a - pre1, nf + pre1 + post1, p0, p1);
     const int n_rows2 = nf + pre2 + post2;
     for (int i = tid; i < 2 * n_rows2 * c2; i += kThreads) {
       const int spk = i / (n_rows2 * c2), rem = i - spk * (n_rows2 * c2);
@@ -256,81 +228,29 @@ __global__ __launch_bounds__(kThreads) void cca_online_push_kernel(CcaOnlinePara
       for (int i = tid; i < nf * 3 * dims; i += kThreads) dst[i] = proj_s[i];
     }
     __syncthreads();
-    // ---- the windows that end in (a, a + nf] (online.hip: a WAVE forms a window's mean with
-    // window_means_kernel's operations; frames before `a` come from the ring)
-    const long long end_lo = a + 1 > width ? a + 1 : width;      // the first window end in reach
-    const long long wi_lo = (end_lo - width + hop - 1) / hop;
-    const long long wi_hi = a + nf >= width ? (a + nf - width) / hop + 1 : 0;   // one past the last
-    const int nw = wi_hi > wi_lo ? (int)(wi_hi - wi_lo) : 0;
-    for (int j = wave; j < nw; j += kWaves) {
-      const long long r0 = (wi_lo + j) * hop;
-      const int slot0 = (int)(r0 % width);                       // ring slot of the window's first frame
-#pragma unroll
-      for (int spk = 0; spk < 2; ++spk) {
-        double part[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          double acc = 0.0;
-          for (int r = 64 * q + lane; r < width; r += kWinThreads) {
-            const long long fr = r0 + r;
-            const int slot = slot0 + r - (slot0 + r >= width ? width : 0);
-            acc += fr >= a ? sc_s[spk * pass + (int)(fr - a)] : ring[(long long)spk * width + slot];
-          }
-          part[q] = wave_sum(acc);
-        }
-        if (lane == 0) {
-          const double m = ((part[0] + part[1]) + (part[2] + part[3])) / (double)width;
-          wm_s[spk * pass + j] = m;
-          p.scores[((long long)spk * gridDim.x + s) * p.n_win + (wi_lo + j - p.w0)] = m;
-        }
-      }
-    }
-    __syncthreads();
-    // ---- decisions (decide_wta_kernel / decide_step_kernel), the ring, then the next pass
-    unsigned char* dec = p.decisions + (long long)s * p.n_win + (wi_lo - p.w0);
-    if (p.decoder == 1) {
-      if (tid == 0) {
-        for (int j = 0; j < nw; ++j) {
-          if (wm_s[j] > wm_s[pass + j]) step = fmin(0.9, step + 0.1);
-          else step = fmax(0.1, step - 0.1);
-          dec[j] = step > 0.5 ? 1 : 0;
-        }
-      }
-    } else {
-      for (int j = tid; j < nw; j += kThreads)
-        dec[j] = p.decoder == 0 ? (wm_s[j] > wm_s[pass + j] ? 1 : 0) : 0;
-    }
-    // (a pass longer than the ring: only its last `width` frames, one per slot)
-    const int slot_a = (int)(a % width);
-    for (int i = tid; i < 2 * nf; i += kThreads) {
-      const int spk = i / nf, f = i - spk * nf;
-      if (nf - f <= width) ring[(long long)spk * width + (slot_a + f) % width] = sc_s[spk * pass + f];
-    }
-    __threadfence_block();
-    __syncthreads();
+    // ---- the windows that end in (a, a + nf], their decisions, the ring, then the next pass
+    window_block<kThreads, kWinThreads>(sc_s, wm_s, ring, pass, a, nf, width, hop, p.decoder, step, p.w0, p.n_win,
+                                        p.scores, p.decisions);
   }
 
   // ---- the tails for the next push: the last pre1 + post EEG rows and the last pre2 + post feature rows of
   // (old tail, this push).  A push shorter than a tail shifts it: the rows that stay go through LDS.
   __syncthreads();
   const long long n = p.n;
-  const int keep1 = n < t1 ? (int)(t1 - n) : 0;                  // old EEG rows that stay
-  for (int i = tid; i < keep1 * c1; i += kThreads) rows1_s[i] = tail1[(t1 - keep1) * c1 + i];
+  tail_park<kThreads>(rows1_s, tail1, t1, c1, n);
   const int keep2 = n < t2 ? (int)(t2 - n) : 0;
   for (int i = tid; i < 2 * keep2 * c2; i += kThreads) {
     const int spk = i / (keep2 * c2), rem = i - spk * (keep2 * c2);
     rows2_s[(size_t)spk * r2 * c2 + rem] = tail2[((long long)spk * t2 + (t2 - keep2)) * c2 + rem];
   }
   __syncthreads();
-  for (int rr = wave; rr < t1; rr += kWaves)
-    for (int ch = lane; ch < c1; ch += 64)
-      tail1[rr * c1 + ch] = rr < keep1 ? rows1_s[rr * c1 + ch] : eeg[(n - (t1 - rr)) * p.eeg_ld + ch];
+  tail_store<kThreads>(tail1, rows1_s, t1, c1, eeg, p.eeg_ld, n);
   for (int i = tid; i < 2 * t2 * c2; i += kThreads) {
     const int spk = i / (t2 * c2), rem = i - spk * (t2 * c2);
     const int rr = rem / c2, ch = rem - rr * c2;
     tail2[i] = rr < keep2 ? rows2_s[(size_t)spk * r2 * c2 + rem] : feat[spk][(n - (t2 - rr)) * p.feat_ld + ch];
   }
-  if (tid == 0 && p.decoder == 1) *step_p = step;
+  store_step(step_p, p.decoder, step);
 }
 
 // The shape checks td_cca_online_state_bytes, td_cca_online_lds_bytes and td_cca_online_push share.
@@ -387,36 +307,21 @@ int td_cca_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_cca_online_push: handle is NULL");
   TD_REQUIRE(h, num_sessions >= 1, "td_cca_online_push: %d sessions", num_sessions);
   TD_TRY(check_shape(h, "td_cca_online_push", c1, pre1, post1, c2, pre2, post2, dims, width));
-  TD_REQUIRE(h, n >= 0 && n <= TD_ONLINE_MAX_PUSH, "td_cca_online_push: %lld frames in one push (0 .. %d)",
-             (long long)n, TD_ONLINE_MAX_PUSH);
-  TD_REQUIRE(h, hop >= 1, "td_cca_online_push: window step of %d frames", hop);
-  TD_REQUIRE(h, reduction >= 0 && reduction <= 4,
-             "td_cca_online_push: reduction %d (0 first, 1 second, 2 mean, 3 mean-squared, 4 lda)", reduction);
-  TD_REQUIRE(h, reduction != 1 || dims >= 2, "td_cca_online_push: reduction 1 (second) needs at least 2 dims");
-  TD_REQUIRE(h, reduction != 4 || lda_dev, "td_cca_online_push: the lda reduction needs lda_dev");
-  TD_REQUIRE(h, decoder >= 0 && decoder <= 2,
-             "td_cca_online_push: decoder %d (0 winner-take-all, 1 stepped, 2 none)", decoder);
-  TD_REQUIRE(h, frames_before >= 0, "td_cca_online_push: %lld frames before", (long long)frames_before);
+  TD_TRY(check_push_args(h, "td_cca_online_push", n, width, hop, reduction, dims, lda_dev, decoder, frames_before));
   if (!mean_x_dev || !rot_x_dev || !mean_y_dev || !rot_y_dev || !corr_dev || !state_dev || !scores_dev ||
       !decisions_dev || (n > 0 && (!eeg_dev || !feat1_dev || !feat2_dev)))
     return td_fail(h, TD_ERR_INVALID, "td_cca_online_push: NULL argument");
-  TD_REQUIRE(h, eeg_ld >= c1 && feat_ld >= c2,
-             "td_cca_online_push: a row stride below a row (%lld for %d channels, %lld for %d features)",
-             (long long)eeg_ld, c1, (long long)feat_ld, c2);
-  TD_REQUIRE(h, num_sessions == 1 || (eeg_session_stride >= c1 && feat_session_stride >= c2),
-             "td_cca_online_push: a session stride below a row");
+  TD_TRY(check_push_strides(h, "td_cca_online_push", num_sessions, eeg_ld, eeg_session_stride, c1, feat_ld,
+                            feat_session_stride, c2, "features"));
   TD_REQUIRE(h, model_session_stride == 0 || model_session_stride == 1,
              "td_cca_online_push: a model stride of %lld models (0 = one model, 1 = one per session)",
              (long long)model_session_stride);
   const int post = delay_of(post1, post2);
-  const long long sbytes = state_bytes(c1, pre1, c2, pre2, post, width);
-  TD_REQUIRE(h, state_session_stride >= sbytes && state_session_stride % 8 == 0,
-             "td_cca_online_push: a state stride of %lld bytes (a multiple of 8, at least %lld)",
-             (long long)state_session_stride, sbytes);
+  TD_TRY(check_state_stride(h, "td_cca_online_push", state_session_stride,
+                            state_bytes(c1, pre1, c2, pre2, post, width)));
   if (n == 0 && !flush) return TD_OK;
-  // (online.hip's plan_push = td_online_plan)
-  int64_t e0 = 0, e1 = 0, w0 = 0, n_win = 0;
-  TD_TRY(td_online_plan(frames_before, n, post, width, hop, flush, &e0, &e1, &w0, &n_win));
+  const OnlinePlan pl = plan_push(frames_before, n, post, width, hop, flush);
+  const long long e0 = pl.emitted_before, e1 = pl.emitted_after, w0 = pl.first_window, n_win = pl.new_windows;
   CcaOnlineParams p;
   p.eeg = eeg_dev; p.eeg_ld = eeg_ld; p.eeg_ss = num_sessions > 1 ? eeg_session_stride : 0;
   p.feat[0] = feat1_dev; p.feat[1] = feat2_dev; p.feat_ld = feat_ld;

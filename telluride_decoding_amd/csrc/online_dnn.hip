@@ -1,8 +1,8 @@
 // Online attention decode with a fully connected regressor (td_fc_online_*): online.hip's session -- state on the
 // device, one workgroup per listener, ONE launch per push -- with brain_model.BrainModelDNN in front of the
-// correlator instead of the FIR prediction.  The state block is online.hip's, byte for byte (td_online_state_bytes,
-// td_online_plan serve as they are), and everything behind the prediction is online_push_kernel's, operation for
-// operation: frame_scores_kernel's expression, the ring, window_means_kernel's sum (256 threads stride the window,
+// correlator instead of the FIR prediction.  The state block is online.hip's (td_online_state_bytes, td_online_plan
+// serve as they are), and everything around the prediction is online_common.h's, as in online_push_kernel: the
+// staging, frame_scores_kernel's expression, the ring, window_means_kernel's sum (256 threads stride the window,
 // 64-lane wave sums, ((w0 + w1) + (w2 + w3)) / width), decide_wta_kernel's / decide_step_kernel's decisions
 // (windows.hip), the tail update.
 //
@@ -27,7 +27,7 @@
 // hold every frame's lagged vector as the span that starts at its first row; their row stride is odd (c | 1), so
 // the frames of a half-wave sit on 32 different banks.  The small parameters (b1, W2, b2, ...) are staged once per
 // launch; the activations of a pass live in two LDS buffers with an odd row stride.
-#include "td_common.h"
+#include "online_common.h"
 
 namespace {
 
@@ -40,17 +40,6 @@ constexpr int kChunkFloats = kMaxKs * kMaxWidth;       // a staged chunk of W1: 
 constexpr int kLoads = kChunkFloats / 4 / kThreads;    // float4 a thread carries from global to LDS per chunk
 constexpr int kPairs = kPass * (kMaxWidth / 4) / kThreads;   // (frame, 4 columns) pairs a thread owns
 constexpr long long kLdsBudget = TD_FC_ONLINE_LDS_BYTES;
-
-// (online.hip's state block: [stepped state f64][ring f64 [2][width]][EEG tail f32 [pre + post][c]]
-// [envelope tail f32 [post][2]], rounded up to 8 bytes)
-__host__ __device__ inline long long state_ring_offset() { return 8; }
-__host__ __device__ inline long long state_eeg_offset(int width) { return 8 + 16LL * width; }
-__host__ __device__ inline long long state_env_offset(int c, int pre, int post, int width) {
-  return state_eeg_offset(width) + 4LL * c * (pre + post);
-}
-__host__ __device__ inline long long state_bytes(int c, int pre, int post, int width) {
-  return (state_env_offset(c, pre, post, width) + 8LL * post + 7) / 8 * 8;
-}
 
 // The network's shape and how W1 is cut: host arithmetic, passed to the kernel by value.
 struct DnnNet {
@@ -126,33 +115,6 @@ struct DnnOnlineParams {
   unsigned char* state; long long state_ss;
   double* scores; unsigned char* decisions; float* pred; double* frame;
 };
-
-// (windows.hip's wave_sum: the same shuffle tree, the same bits)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// (online.hip's frame_score) frame_scores_kernel's value for ONE column (windows.hip): a = the truth, b = the
-// prediction.  The sums over the columns start from 0.0 there, so they do here; the lda map is that kernel's one
-// fused multiply-add (slope * acc + intercept, contracted).
-__device__ __forceinline__ double frame_score(float truth, float pred, double mean_a, double mean_b,
-                                              double power, int reduction, double lda_w,
-                                              double lda_slope, double lda_intercept) {
-  const double v = ((double)truth - mean_a) * ((double)pred - mean_b) / power;
-  if (reduction == 0) return v;
-  double acc = 0.0;
-  if (reduction == 2) {
-    acc += v;
-  } else if (reduction == 3) {
-    acc += (v > 0.0 ? v * v : (v < 0.0 ? -v * v : 0.0));
-  } else {
-    acc += v * lda_w;
-    acc = fma(lda_slope, acc, lda_intercept);
-  }
-  return acc;
-}
 
 // Chunk ci of W1 (rows [ci g ks, ...) as [rows][nj], columns past w1 - 1 repeating it) from global into registers: float4
 // number tid + i kThreads of the chunk.  vec: w1 is a multiple of 4 and W1 is 16-byte aligned -- the chunk is one
@@ -285,32 +247,15 @@ __global__ __launch_bounds__(kThreads) void dnn_online_push_kernel(DnnOnlinePara
 
   for (int i = tid; i < t.n_small; i += kThreads) sm_s[i] = prm[t.small0 + i];
   const float* small = sm_s - t.small0;                      // indexed by parameter offset
-  double step = 0.5;
-  if (tid == 0 && p.decoder == 1) {
-    const double stored = *step_p;
-    step = stored == 0.0 ? 0.5 : stored;
-  }
+  double step = load_step(step_p, p.decoder);
 
   for (long long a = p.e0; a < p.e1; a += pass) {
     const int nf = (int)(p.e1 - a < pass ? p.e1 - a : pass);     // frames [a, a + nf) of this pass
     float4 regs[kLoads];
     chunk_load(prm, t, 0, vec, tid, regs);
-    // ---- stage the EEG rows a - pre .. a + nf - 1 + post and the envelope rows a .. a + nf - 1: from the
-    // tails (rows before this push), from the push, zeros before the recording and behind a flushed end
-    const int n_rows = nf + tl;
-    for (int rr = wave; rr < n_rows; rr += kWaves) {
-      const long long row = a - pre + rr;
-      for (int ch = lane; ch < c; ch += 64) {
-        float v = 0.f;
-        if (row >= 0 && row < p0) v = tail[(row - (p0 - tl)) * c + ch];
-        else if (row >= p0 && row < p1) v = eeg[(row - p0) * p.eeg_ld + ch];
-        rows_s[rr * ldr + ch] = v;
-      }
-    }
-    for (int i = tid; i < 2 * nf; i += kThreads) {
-      const long long row = a + (i >> 1);
-      env_s[i] = row < p0 ? etail[(row - (p0 - post)) * 2 + (i & 1)] : env[(row - p0) * p.env_ld + (i & 1)];
-    }
+    // ---- stage the EEG rows a - pre .. a + nf - 1 + post and the envelope rows a .. a + nf - 1
+    stage_rows<kThreads>(rows_s, ldr, tail, tl, eeg, p.eeg_ld, c, a - pre, nf + tl, p0, p1);
+    stage_env<kThreads>(env_s, etail, post, env, p.env_ld, a, nf, p0);
     chunk_store(ws_s, t, 0, tid, regs);
     __syncthreads();
     // ---- layer 1: thread = (frame f, column lane cg), frame-fastest; the thread owns the column groups cg,
@@ -397,9 +342,10 @@ __global__ __launch_bounds__(kThreads) void dnn_online_push_kernel(DnnOnlinePara
       if (p.pred && spk == 0) p.pred[at] = pr;
     }
     __syncthreads();
-    // ---- the windows that end in (a, a + nf] (online.hip: a WAVE forms a window's mean with
-    // window_means_kernel's operations -- lane q stands in for the threads q, q + 64, q + 128, q + 192 of that
-    // kernel's workgroup; frames before `a` come from the ring)
+    // ---- the windows that end in (a, a + nf]: online_common.h's window_block<kThreads, kThreads>, line for line,
+    // written out here.  Called as the helper, this kernel's register allocation around layer 1 changed and a push
+    // of 100 frames took 4 to 5 % longer on the MI355X; the other three kernels call it.
+    // A change to that block is a change to this one.
     const long long end_lo = a + 1 > width ? a + 1 : width;      // the first window end in reach
     const long long wi_lo = (end_lo - width + hop - 1) / hop;
     const long long wi_hi = a + nf >= width ? (a + nf - width) / hop + 1 : 0;   // one past the last
@@ -452,31 +398,20 @@ __global__ __launch_bounds__(kThreads) void dnn_online_push_kernel(DnnOnlinePara
     __syncthreads();
   }
 
-  // ---- the tails for the next push: the last pre + post EEG rows and the last post envelope rows of
-  // (old tail, this push).  A push shorter than a tail shifts it: the rows that stay go through LDS.
+  // ---- the tails for the next push: the last pre + post EEG rows and the last post envelope rows
   __syncthreads();
-  const long long n = p.n;
-  const int keep = n < tl ? (int)(tl - n) : 0;                   // old EEG rows that stay
-  for (int i = tid; i < keep * c; i += kThreads) rows_s[i] = tail[(tl - keep) * c + i];
-  const int ekeep = n < post ? (int)(post - n) : 0;
-  for (int i = tid; i < ekeep * 2; i += kThreads) env_s[i] = etail[(post - ekeep) * 2 + i];
+  tail_park<kThreads>(rows_s, tail, tl, c, p.n);
+  env_tail_park<kThreads>(env_s, etail, post, p.n);
   __syncthreads();
-  for (int rr = wave; rr < tl; rr += kWaves)
-    for (int ch = lane; ch < c; ch += 64)
-      tail[rr * c + ch] = rr < keep ? rows_s[rr * c + ch] : eeg[(n - (tl - rr)) * p.eeg_ld + ch];
-  for (int i = tid; i < post * 2; i += kThreads) {
-    const int rr = i >> 1;
-    etail[i] = rr < ekeep ? env_s[i] : env[(n - (post - rr)) * p.env_ld + (i & 1)];
-  }
-  if (tid == 0 && p.decoder == 1) *step_p = step;
+  tail_store<kThreads>(tail, rows_s, tl, c, eeg, p.eeg_ld, p.n);
+  env_tail_store<kThreads>(etail, env_s, post, env, p.env_ld, p.n);
+  store_step(step_p, p.decoder, step);
 }
 
 // The shape checks td_fc_online_lds_bytes and td_fc_online_push share: the intersection of td_online_push's
 // limits and td_mlp_forward's.
 int check_shape(td_handle* h, const char* who, int c, int pre, int post, int num_hidden, const int* hidden) {
-  TD_REQUIRE(h, c >= 1 && c <= kMaxChannels, "%s: %d channels (1 .. %d)", who, c, kMaxChannels);
-  TD_REQUIRE(h, pre >= 0 && post >= 0 && pre + 1 + post <= kMaxLags,
-             "%s: context of %d + 1 + %d frames (at most %d lags)", who, pre, post, kMaxLags);
+  TD_TRY(check_context(h, who, c, pre, post, kMaxChannels, kMaxLags));
   TD_REQUIRE(h, (long long)c * (pre + 1 + post) <= kMaxK, "%s: %d lagged inputs (at most %d)", who,
              c * (pre + 1 + post), kMaxK);
   TD_REQUIRE(h, num_hidden >= 0 && num_hidden <= kMaxHidden, "%s: %d hidden layers (at most %d)", who, num_hidden,
@@ -519,36 +454,19 @@ int td_fc_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int6
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_fc_online_push: handle is NULL");
   TD_REQUIRE(h, num_sessions >= 1, "td_fc_online_push: %d sessions", num_sessions);
   TD_TRY(check_shape(h, "td_fc_online_push", c, pre, post, num_hidden, hidden_host));
-  TD_REQUIRE(h, n >= 0 && n <= TD_ONLINE_MAX_PUSH, "td_fc_online_push: %lld frames in one push (0 .. %d)",
-             (long long)n, TD_ONLINE_MAX_PUSH);
-  TD_REQUIRE(h, width >= 1 && width <= TD_ONLINE_MAX_WIDTH, "td_fc_online_push: window of %d frames (1 .. %d)",
-             width, TD_ONLINE_MAX_WIDTH);
-  TD_REQUIRE(h, hop >= 1, "td_fc_online_push: window step of %d frames", hop);
-  TD_REQUIRE(h, reduction == 0 || reduction == 2 || reduction == 3 || reduction == 4,
-             "td_fc_online_push: reduction %d (0 first, 2 mean, 3 mean-squared, 4 lda)", reduction);
-  TD_REQUIRE(h, reduction != 4 || lda_dev, "td_fc_online_push: the lda reduction needs lda_dev");
-  TD_REQUIRE(h, decoder >= 0 && decoder <= 2,
-             "td_fc_online_push: decoder %d (0 winner-take-all, 1 stepped, 2 none)", decoder);
-  TD_REQUIRE(h, frames_before >= 0, "td_fc_online_push: %lld frames before", (long long)frames_before);
+  TD_TRY(check_push_args(h, "td_fc_online_push", n, width, hop, reduction, 0, lda_dev, decoder, frames_before));
   if (!params_dev || !corr_dev || !state_dev || !scores_dev || !decisions_dev || (n > 0 && (!eeg_dev || !env_dev)))
     return td_fail(h, TD_ERR_INVALID, "td_fc_online_push: NULL argument");
-  TD_REQUIRE(h, eeg_ld >= c && env_ld >= 2,
-             "td_fc_online_push: a row stride below a row (%lld for %d channels, %lld for 2 envelopes)",
-             (long long)eeg_ld, c, (long long)env_ld);
-  TD_REQUIRE(h, num_sessions == 1 || (eeg_session_stride >= c && env_session_stride >= 2),
-             "td_fc_online_push: a session stride below a row");
+  TD_TRY(check_push_strides(h, "td_fc_online_push", num_sessions, eeg_ld, eeg_session_stride, c, env_ld,
+                            env_session_stride, 2, "envelopes"));
   const DnnNet t = net_of(c, pre, post, hidden_host, num_hidden);
   TD_REQUIRE(h, params_session_stride == 0 || params_session_stride >= t.n_params,
              "td_fc_online_push: a parameter stride of %lld for %d parameters (0 = one model)",
              (long long)params_session_stride, t.n_params);
-  const long long sbytes = state_bytes(c, pre, post, width);
-  TD_REQUIRE(h, state_session_stride >= sbytes && state_session_stride % 8 == 0,
-             "td_fc_online_push: a state stride of %lld bytes (a multiple of 8, at least %lld)",
-             (long long)state_session_stride, sbytes);
+  TD_TRY(check_state_stride(h, "td_fc_online_push", state_session_stride, state_bytes(c, pre, post, width)));
   if (n == 0 && !flush) return TD_OK;
-  // (online.hip's plan_push = td_online_plan)
-  int64_t e0 = 0, e1 = 0, w0 = 0, n_win = 0;
-  TD_TRY(td_online_plan(frames_before, n, post, width, hop, flush, &e0, &e1, &w0, &n_win));
+  const OnlinePlan pl = plan_push(frames_before, n, post, width, hop, flush);
+  const long long e0 = pl.emitted_before, e1 = pl.emitted_after, w0 = pl.first_window, n_win = pl.new_windows;
   DnnOnlineParams p;
   p.eeg = eeg_dev; p.eeg_ld = eeg_ld; p.eeg_ss = num_sessions > 1 ? eeg_session_stride : 0;
   p.env = env_dev; p.env_ld = env_ld; p.env_ss = num_sessions > 1 ? env_session_stride : 0;

@@ -552,50 +552,36 @@ class OnlineDecoder(object):
     h = device.default_handle()
     torch = device._torch()
     ps = self._params
+    dev = dict(h=h)
+    # the model: sessions around ONE model (bitwise-equal parameters for a DNN) read one copy of it
+    names = {'cca': ('mean_x', 'rot_x', 'mean_y', 'rot_y'), 'dnn': ('params',)}.get(self.kind, ('w', 'b'))
+    bits = lambda a: a.view(np.uint32) if self.kind == 'dnn' else a
+    shared = all(np.array_equal(bits(p[k]), bits(ps[0][k])) for p in ps[1:] for k in names)
+    models = ps[:1] if shared else ps
     if self.kind == 'cca':
-      names = ('mean_x', 'rot_x', 'mean_y', 'rot_y')
-      shared = all(np.array_equal(p[k], ps[0][k]) for p in ps[1:] for k in names)
-      models = ps[:1] if shared else ps
-      dev = dict(h=h)
       for k in names:
         stacked = np.stack([p[k] for p in models])
         dev[k] = h.to_device(stacked.reshape(-1, stacked.shape[-1])).reshape(stacked.shape)
-      dev['corr'] = h.to_device(np.stack([p['corr'] for p in ps]).reshape(-1, self.dims),
-                                np.float64).reshape(-1, 2, 3, self.dims)
-      dev['lda'] = (h.to_device(np.stack([p['lda'] for p in ps]), np.float64)
-                    if self.reduction == 'lda' else None)
-      nbytes = device.cca_online_state_bytes(self.channels, self.pre, self.post, self.features, self.pre2,
-                                             self.post2, self.window_size)
-      dev['state'] = torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device)
-      dev['ssd_state'] = device.ssd_state(self.sessions, handle=h) if self._ssd is not None else None
-      return dev
-    if self.kind == 'dnn':
-      # (sessions around bitwise-equal parameters read one copy; a row starts on a 16-byte boundary)
-      shared = all(np.array_equal(p['params'].view(np.uint32), ps[0]['params'].view(np.uint32)) for p in ps[1:])
-      models = ps[:1] if shared else ps
+    elif self.kind == 'dnn':
+      # (a row starts on a 16-byte boundary)
       count = int(ps[0]['params'].size)
       packed = np.zeros((len(models), -(-count // 4) * 4), np.float32)
       for i, p in enumerate(models):
         packed[i, :count] = p['params']
-      dev = dict(h=h)
       dev['params'] = h.to_device(packed)[:, :count]
-      dev['corr'] = h.to_device(np.stack([p['corr'] for p in ps]).reshape(-1, 6), np.float64).reshape(-1, 2, 3)
-      dev['lda'] = (h.to_device(np.stack([p['lda'] for p in ps]), np.float64)
-                    if self.reduction == 'lda' else None)
-      nbytes = device.online_state_bytes(self.channels, self.pre, self.post, self.window_size)
-      dev['state'] = torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device)
-      dev['ssd_state'] = device.ssd_state(self.sessions, handle=h) if self._ssd is not None else None
-      return dev
-    # (sessions around ONE model read one copy of it)
-    shared = all(np.array_equal(p['w'], ps[0]['w']) and p['b'] == ps[0]['b'] for p in ps[1:])
-    models = ps[:1] if shared else ps
-    dev = dict(h=h)
-    dev['w'] = h.to_device(np.stack([p['w'] for p in models]))
-    dev['b'] = h.to_device(np.array([[p['b']] for p in models], np.float32)).reshape(-1)
-    dev['corr'] = h.to_device(np.stack([p['corr'] for p in ps]).reshape(-1, 6), np.float64).reshape(-1, 2, 3)
+    else:
+      dev['w'] = h.to_device(np.stack([p['w'] for p in models]))
+      dev['b'] = h.to_device(np.array([[p['b']] for p in models], np.float32)).reshape(-1)
+    # the statistics [S, 2, 3] (a CCA bank's [S, 2, 3, dims]), the LDA, the state
+    corr = np.stack([p['corr'] for p in ps])
+    dev['corr'] = h.to_device(corr.reshape(self.sessions, -1), np.float64).reshape(corr.shape)
     dev['lda'] = (h.to_device(np.stack([p['lda'] for p in ps]), np.float64)
                   if self.reduction == 'lda' else None)
-    nbytes = device.online_state_bytes(self.channels, self.pre, self.post, self.window_size)
+    if self.kind == 'cca':
+      nbytes = device.cca_online_state_bytes(self.channels, self.pre, self.post, self.features, self.pre2,
+                                             self.post2, self.window_size)
+    else:
+      nbytes = device.online_state_bytes(self.channels, self.pre, self.post, self.window_size)
     dev['state'] = torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device)
     dev['ssd_state'] = device.ssd_state(self.sessions, handle=h) if self._ssd is not None else None
     return dev
@@ -708,28 +694,28 @@ class OnlineDecoder(object):
       d['lda'].copy_(conv(lda).expand_as(d['lda']))
 
   # -- pushes ------------------------------------------------------------------------------------
+  def _rows(self, *arrays):
+    """Each of `arrays` -- host arrays or device tensors, [n, k] or [S, n, k] -- as float32 on the bank's side: device
+    tensors when one of them is a tensor and the bank runs on the device, host arrays otherwise (the push uploads
+    them)."""
+    if self._on_device and any(hasattr(a, 'is_cuda') for a in arrays):
+      torch = device._torch()
+      where = self._dev['h'].device
+      return [(a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a))).to(device=where, dtype=torch.float32)
+              for a in arrays]
+    return [np.asarray(a.cpu() if hasattr(a, 'cpu') else a, np.float32) for a in arrays]
+
   def _as_bank(self, eeg, env1, env2):
     """(eeg [S, n, C], env [S, n, 2]) as float32 host arrays or device tensors."""
     s, c = self.sessions, self.channels
-    tensors = [hasattr(a, 'is_cuda') for a in (eeg, env1, env2)]
-    if any(tensors):
-      torch = device._torch()
-      h = self._dev['h'] if self._on_device else None
-      conv = lambda a: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a))).to(
-          device=h.device if h else None, dtype=torch.float32)
-      eeg, env1, env2 = conv(eeg), conv(env1), conv(env2)
-      if eeg.dim() == 2:
-        eeg, env1, env2 = eeg.unsqueeze(0), env1.reshape(1, -1), env2.reshape(1, -1)
-      env = torch.stack([env1.reshape(eeg.shape[0], -1), env2.reshape(eeg.shape[0], -1)], dim=2)
+    eeg, env1, env2 = self._rows(eeg, env1, env2)
+    if eeg.ndim == 2:
+      eeg = eeg[None]
+    tensors = hasattr(eeg, 'is_cuda')
+    stack = device._torch().stack if tensors else np.stack
+    env = stack([env1.reshape(eeg.shape[0], -1), env2.reshape(eeg.shape[0], -1)], 2)
+    if tensors:
       eeg = eeg.contiguous()
-      if not self._on_device:
-        eeg, env = eeg.cpu().numpy(), env.cpu().numpy()
-    else:
-      eeg = np.asarray(eeg, np.float32)
-      if eeg.ndim == 2:
-        eeg = eeg[None]
-      env = np.stack([np.asarray(env1, np.float32).reshape(eeg.shape[0], -1),
-                      np.asarray(env2, np.float32).reshape(eeg.shape[0], -1)], axis=2)
     if eeg.ndim != 3 or tuple(eeg.shape[0:3:2]) != (s, c) or tuple(env.shape) != (s, eeg.shape[1], 2):
       raise ValueError('A push is eeg [%d, n, %d] (or [n, %d] for one session) with two envelopes of n frames '
                        'each, not eeg %s with envelopes %s.' % (s, c, c, tuple(eeg.shape), tuple(env.shape[:2])))
@@ -738,19 +724,7 @@ class OnlineDecoder(object):
   def _as_cca_bank(self, eeg, feat1, feat2):
     """(eeg [S, n, C], (feat1, feat2) [S, n, c2] each) as float32 host arrays or device tensors."""
     s, c, c2 = self.sessions, self.channels, self.features
-    if any(hasattr(a, 'is_cuda') for a in (eeg, feat1, feat2)):
-      torch = device._torch()
-      h = self._dev['h'] if self._on_device else None
-      conv = lambda a: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a))).to(
-          device=h.device if h else None, dtype=torch.float32)
-      arrays = [conv(a) for a in (eeg, feat1, feat2)]
-      arrays = [a.unsqueeze(0) if a.dim() == 2 else a for a in arrays]
-      if not self._on_device:
-        arrays = [a.cpu().numpy() for a in arrays]
-    else:
-      arrays = [np.asarray(a, np.float32) for a in (eeg, feat1, feat2)]
-      arrays = [a[None] if a.ndim == 2 else a for a in arrays]
-    eeg, feat1, feat2 = arrays
+    eeg, feat1, feat2 = (a[None] if a.ndim == 2 else a for a in self._rows(eeg, feat1, feat2))
     n = eeg.shape[1] if eeg.ndim == 3 else -1
     if (eeg.ndim != 3 or tuple(eeg.shape) != (s, n, c) or tuple(feat1.shape) != (s, n, c2) or
         tuple(feat2.shape) != (s, n, c2)):
@@ -781,51 +755,49 @@ class OnlineDecoder(object):
     self.flushed = True
     return result
 
-  def _advance(self, eeg, env, flush):
+  def _advance(self, eeg, side, flush):
+    """One push of the bank; side is env [S, n, 2], or a CCA bank's (feat1, feat2)."""
     n = 0 if eeg is None else int(eeg.shape[1])
     kind = 'none' if self.decoder_type == 'ssd' else self.decoder_type
-    if self.kind == 'cca':
-      out = self._advance_cca(eeg, env, n, kind, flush)
-      return out if isinstance(out, OnlineResult) else self._finish(out)
+    cca = self.kind == 'cca'
     if not self._on_device:
+      # the NumPy sessions, one listener each
       if eeg is None:
         eeg = np.zeros((self.sessions, 0, self.channels), np.float32)
-        env = np.zeros((self.sessions, 0, 2), np.float32)
-      outs = [sess.push(np.asarray(eeg[i], np.float64), np.asarray(env[i], np.float64), self.frames_pushed,
-                        flush) for i, sess in enumerate(self._host)]
+        side = ((np.zeros((self.sessions, 0, self.features), np.float32),) * 2 if cca else
+                np.zeros((self.sessions, 0, 2), np.float32))
+      outs = []
+      for i, sess in enumerate(self._host):
+        mine = (np.stack([np.asarray(f[i], np.float64) for f in side]) if cca else
+                np.asarray(side[i], np.float64))
+        outs.append(sess.push(np.asarray(eeg[i], np.float64), mine, self.frames_pushed, flush))
       self.frames_pushed += n
       return OnlineResult(np.stack([o[0] for o in outs]), np.stack([o[1] for o in outs]),
                           outs[0][4].first_window)
     d = self._dev
     h = d['h']
-    if eeg is not None and not hasattr(eeg, 'is_cuda'):
-      eeg, env = h.to_device(eeg.reshape(-1, self.channels)).reshape(eeg.shape), \
-          h.to_device(env.reshape(-1, 2)).reshape(env.shape)
-    if n == 0:
-      eeg = env = None
-    if self.kind == 'dnn':
-      out = device.dnn_online_push(eeg, env, d['params'], self.hidden, d['corr'], d['state'], self.frames_pushed,
-                                   self.pre, self.post, self.window_size, self.window_step, self.reduction,
-                                   d['lda'], kind, flush=flush, handle=h)
+    if cca:
+      out = self._advance_cca(eeg, side, n, kind, flush)
     else:
-      out = device.online_push(eeg, env, d['w'], d['b'], d['corr'], d['state'], self.frames_pushed, self.pre,
-                               self.post, self.window_size, self.window_step, self.reduction, d['lda'], kind,
-                               flush=flush, handle=h)
+      env = side
+      if eeg is not None and not hasattr(eeg, 'is_cuda'):
+        eeg, env = h.to_device(eeg.reshape(-1, self.channels)).reshape(eeg.shape), \
+            h.to_device(env.reshape(-1, 2)).reshape(env.shape)
+      if n == 0:
+        eeg = env = None
+      if self.kind == 'dnn':
+        out = device.dnn_online_push(eeg, env, d['params'], self.hidden, d['corr'], d['state'], self.frames_pushed,
+                                     self.pre, self.post, self.window_size, self.window_step, self.reduction,
+                                     d['lda'], kind, flush=flush, handle=h)
+      else:
+        out = device.online_push(eeg, env, d['w'], d['b'], d['corr'], d['state'], self.frames_pushed, self.pre,
+                                 self.post, self.window_size, self.window_step, self.reduction, d['lda'], kind,
+                                 flush=flush, handle=h)
     self.frames_pushed += n
     return self._finish(out)
 
   def _advance_cca(self, eeg, feats, n, kind, flush):
-    """The CCA bank's push: an OnlineResult from the NumPy sessions, or the device's CcaOnlinePush."""
-    if not self._on_device:
-      if eeg is None:
-        eeg = np.zeros((self.sessions, 0, self.channels), np.float32)
-        feats = (np.zeros((self.sessions, 0, self.features), np.float32),) * 2
-      outs = [sess.push(np.asarray(eeg[i], np.float64),
-                        np.stack([np.asarray(feats[0][i], np.float64), np.asarray(feats[1][i], np.float64)]),
-                        self.frames_pushed, flush) for i, sess in enumerate(self._host)]
-      self.frames_pushed += n
-      return OnlineResult(np.stack([o[0] for o in outs]), np.stack([o[1] for o in outs]),
-                          outs[0][4].first_window)
+    """The CCA bank's push on the device: its CcaOnlinePush."""
     d = self._dev
     h = d['h']
     feat1 = feat2 = None
@@ -834,12 +806,10 @@ class OnlineDecoder(object):
     else:
       up = lambda a: a if hasattr(a, 'is_cuda') else h.to_device(a.reshape(-1, a.shape[-1])).reshape(a.shape)
       eeg, feat1, feat2 = up(eeg), up(feats[0]), up(feats[1])
-    out = device.cca_online_push(eeg, feat1, feat2, d['mean_x'], d['rot_x'], d['mean_y'], d['rot_y'], d['corr'],
-                                 d['state'], self.frames_pushed, self.pre, self.post, self.pre2, self.post2,
-                                 self.window_size, self.window_step, self.reduction, d['lda'], kind, flush=flush,
-                                 handle=h)
-    self.frames_pushed += n
-    return out
+    return device.cca_online_push(eeg, feat1, feat2, d['mean_x'], d['rot_x'], d['mean_y'], d['rot_y'], d['corr'],
+                                  d['state'], self.frames_pushed, self.pre, self.post, self.pre2, self.post2,
+                                  self.window_size, self.window_step, self.reduction, d['lda'], kind, flush=flush,
+                                  handle=h)
 
   def _finish(self, out):
     """A device push's windows as an OnlineResult; for 'ssd' through td_decode_ssd_stream first."""
