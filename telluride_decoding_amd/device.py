@@ -963,20 +963,111 @@ OnlinePlan = collections.namedtuple(
 OnlinePush = collections.namedtuple('OnlinePush', ['scores', 'decisions', 'pred', 'frame', 'plan'])
 
 
+# -- what the online push wrappers share (each stated once; the wrappers keep their own messages and their order)
+_I64, _I32_I64 = (ctypes.c_int64,), (ctypes.c_int, ctypes.c_int64)
+
+
+def _lib_values(name, args, outs=_I64):
+  """The integers the library's host function `name`(*args, &out, ...) gives through out-parameters of the ctypes
+  `outs`: called without a handle, its status checked."""
+  values = [kind(0) for kind in outs]
+  _lib.check(None, getattr(_lib.load(), name)(*args, *[ctypes.byref(v) for v in values]))
+  return [int(v.value) for v in values]
+
+
+def _row_block(t, n, sessions, width):
+  """(pointer, row stride, session stride) of the rows [S, n, width] of a push; a null pointer without rows.  A
+  tensor with one row, or with one session, carries in that dimension whatever stride its view left it -- 0 after an
+  expand, anything after a slice -- and an absent tensor carries none, while the kernels refuse a row stride under
+  the width and a session stride under a block.  A stride nothing steps by is therefore reported as that of packed
+  rows: `width` between rows, max(n, 1) * width between sessions."""
+  live = n > 0
+  return (_ptr(t if live else None), int(t.stride(1)) if live and n > 1 else width,
+          int(t.stride(0)) if live and sessions > 1 else max(n, 1) * width)
+
+
+def _state_stride(state, sessions):
+  """Bytes between the sessions' blocks of a [S, bytes] state; one session's stride may be anything: its length."""
+  return int(state.stride(0)) if sessions > 1 else int(state.shape[1])
+
+
+def _check_tensors(who, h, tensors, short=False):
+  """TypeError for the first of (name, tensor, dtype) that is not a `dtype` tensor on the handle's device; None is
+  skipped.  short: the dtype is named float32, not torch.float32 (the wrappers differ in this)."""
+  for name, t, dtype in tensors:
+    if t is not None and (t.dtype != dtype or t.device != h.device):
+      raise TypeError('%s: %s must be a %s tensor on %s, not %s on %s' %
+                      (who, name, str(dtype).replace('torch.', '') if short else dtype, h.device, t.dtype, t.device))
+
+
+def _spare(h, count, dtype, wanted=True):
+  """A flat output of count + 1 elements (None when not wanted): every element a push emits is written, and an empty
+  tensor has no address -- hence one spare element, which _shaped drops."""
+  return h.empty((count + 1,), dtype) if wanted else None
+
+
+def _shaped(t, *shape):
+  return t[:-1].reshape(shape) if t is not None else None
+
+
+def _check_reduction(who, reduction, reductions, decoder):
+  if reduction not in reductions:
+    raise ValueError('%s: reduction %r (one of %s)' % (who, reduction, ', '.join(reductions)))
+  if decoder not in SWEEP_DECODERS:
+    raise ValueError('%s: unknown decoder %r' % (who, decoder))
+
+
+def _check_decoder_rows(who, h, torch, sessions, c, eeg, env, model, corr, lda, state):
+  """The rows of a push of online_push / dnn_online_push, once the model has said how many channels it implies:
+  their shapes, every tensor's dtype and device (`model`: the wrapper's own triples, checked behind the rows), unit
+  column strides.  Returns n."""
+  n = 0 if eeg is None else int(eeg.shape[1])
+  if eeg is not None and (tuple(eeg.shape) != (sessions, n, c) or env is None or
+                          tuple(env.shape) != (sessions, n, 2)):
+    raise ValueError('%s: eeg of %s and env of %s for %d sessions of %d channels' %
+                     (who, tuple(eeg.shape), None if env is None else tuple(env.shape), sessions, c))
+  _check_tensors(who, h, (('eeg', eeg, torch.float32), ('env', env, torch.float32)) + model +
+                 (('corr', corr, torch.float64), ('lda', lda, torch.float64), ('state', state, torch.uint8)))
+  if n > 0 and (eeg.stride(2) != 1 and c > 1 or env.stride(2) != 1):
+    raise ValueError('%s: the columns of eeg and env must be contiguous' % who)
+  return n
+
+
+def _decoder_push(who, h, push, model_args, sessions, eeg, env, n, c, pre, post, corr, lda, state, frames_before,
+                  width, hop, reduction, decoder, flush, want_frames):
+  """The rest of online_push / dnn_online_push behind their model checks: the statistics' shapes, the plan, the
+  outputs, the launch and the OnlinePush.  push: the wrapper's library function, which takes model_args between the
+  context and the statistics.  (The outputs are _spare's and _shaped's, written out: eight calls fewer per push.)"""
+  if tuple(corr.shape) != (sessions, 2, 3) or (lda is not None and tuple(lda.shape) != (sessions, 3)):
+    raise ValueError('%s: corr must be [%d, 2, 3] and lda [%d, 3]' % (who, sessions, sessions))
+  corr = corr.contiguous()
+  lda = lda.contiguous() if lda is not None else None
+  plan = online_plan(frames_before, n, post, width, hop, flush)
+  new, emitted = plan.new_windows, plan.emitted_after - plan.emitted_before
+  scores = h.empty((2 * sessions * new + 1,), 'float64')
+  decisions = h.empty((sessions * new + 1,), 'uint8')
+  pred = h.empty((sessions * emitted + 1,), 'float32') if want_frames else None
+  frame = h.empty((2 * sessions * emitted + 1,), 'float64') if want_frames else None
+  h.check(push(
+      h.ptr, sessions, *_row_block(eeg, n, sessions, c), *_row_block(env, n, sessions, 2), n, c, int(pre), int(post),
+      *model_args, _ptr(corr), REDUCTIONS[reduction], _ptr(lda), int(width), int(hop), SWEEP_DECODERS[decoder],
+      int(frames_before), 1 if flush else 0, _ptr(state), _state_stride(state, sessions),
+      _ptr(scores), _ptr(decisions), _ptr(pred), _ptr(frame)))
+  return OnlinePush(scores[:-1].reshape(2, sessions, new), decisions[:-1].reshape(sessions, new),
+                    pred[:-1].reshape(sessions, emitted) if want_frames else None,
+                    frame[:-1].reshape(2, sessions, emitted) if want_frames else None, plan)
+
+
 def online_state_bytes(c, pre, post, width):
   """Bytes of one online session's state block (td_online_state_bytes); all zeros = a fresh session."""
-  n = ctypes.c_int64(0)
-  _lib.check(None, _lib.load().td_online_state_bytes(int(c), int(pre), int(post), int(width), ctypes.byref(n)))
-  return int(n.value)
+  return _lib_values('td_online_state_bytes', (int(c), int(pre), int(post), int(width)))[0]
 
 
 def online_plan(frames_before, n, post, width, hop, flush=False):
   """What a push of n frames behind `frames_before` pushed ones emits (td_online_plan, host integers):
   OnlinePlan(emitted_before, emitted_after, first_window, new_windows)."""
-  out = [ctypes.c_int64(0) for _ in range(4)]
-  _lib.check(None, _lib.load().td_online_plan(int(frames_before), int(n), int(post), int(width), int(hop),
-                                              1 if flush else 0, *[ctypes.byref(v) for v in out]))
-  return OnlinePlan(*[int(v.value) for v in out])
+  return OnlinePlan(*_lib_values('td_online_plan', (int(frames_before), int(n), int(post), int(width), int(hop),
+                                                    1 if flush else 0), _I64 * 4))
 
 
 def online_push(eeg, env, w, b, corr, state, frames_before, pre, post, width, hop, reduction='first',
@@ -993,59 +1084,23 @@ def online_push(eeg, env, w, b, corr, state, frames_before, pre, post, width, ho
   Queued, not waited for."""
   h = handle or default_handle()
   torch = _torch()
-  if reduction not in ONLINE_REDUCTIONS:
-    raise ValueError('online_push: reduction %r (one of %s)' % (reduction, ', '.join(ONLINE_REDUCTIONS)))
-  if decoder not in SWEEP_DECODERS:
-    raise ValueError('online_push: unknown decoder %r' % (decoder,))
+  _check_reduction('online_push', reduction, ONLINE_REDUCTIONS, decoder)
   sessions = int(state.shape[0])
   k = int(w.shape[1])
   nl = int(pre) + 1 + int(post)
   if nl < 1 or k % nl:
     raise ValueError('online_push: %d weights for %d lags' % (k, nl))
   c = k // nl
-  n = 0 if eeg is None else int(eeg.shape[1])
-  if eeg is not None and (tuple(eeg.shape) != (sessions, n, c) or env is None or
-                          tuple(env.shape) != (sessions, n, 2)):
-    raise ValueError('online_push: eeg of %s and env of %s for %d sessions of %d channels' %
-                     (tuple(eeg.shape), None if env is None else tuple(env.shape), sessions, c))
-  for name, t, dtype in (('eeg', eeg, torch.float32), ('env', env, torch.float32), ('w', w, torch.float32),
-                         ('b', b, torch.float32), ('corr', corr, torch.float64), ('lda', lda, torch.float64),
-                         ('state', state, torch.uint8)):
-    if t is not None and (t.dtype != dtype or t.device != h.device):
-      raise TypeError('online_push: %s must be a %s tensor on %s, not %s on %s' %
-                      (name, dtype, h.device, t.dtype, t.device))
-  if n > 0 and (eeg.stride(2) != 1 and c > 1 or env.stride(2) != 1):
-    raise ValueError('online_push: the columns of eeg and env must be contiguous')
+  n = _check_decoder_rows('online_push', h, torch, sessions, c, eeg, env,
+                          (('w', w, torch.float32), ('b', b, torch.float32)), corr, lda, state)
   if int(w.shape[0]) not in (1, sessions) or int(b.numel()) != int(w.shape[0]):
     raise ValueError('online_push: %d models and %d biases for %d sessions' %
                      (int(w.shape[0]), int(b.numel()), sessions))
-  if tuple(corr.shape) != (sessions, 2, 3) or (lda is not None and tuple(lda.shape) != (sessions, 3)):
-    raise ValueError('online_push: corr must be [%d, 2, 3] and lda [%d, 3]' % (sessions, sessions))
-  w, b, corr = w.contiguous(), b.reshape(-1).contiguous(), corr.contiguous()
-  lda = lda.contiguous() if lda is not None else None
+  w, b = w.contiguous(), b.reshape(-1).contiguous()
   shared = int(w.shape[0]) == 1
-  plan = online_plan(frames_before, n, post, width, hop, flush)
-  emitted = plan.emitted_after - plan.emitted_before
-  # (every element a push emits is written; an empty tensor has no address: one spare element)
-  scores = h.empty((2 * sessions * plan.new_windows + 1,), 'float64')
-  decisions = h.empty((sessions * plan.new_windows + 1,), 'uint8')
-  pred = h.empty((sessions * emitted + 1,), 'float32') if want_frames else None
-  frame = h.empty((2 * sessions * emitted + 1,), 'float64') if want_frames else None
-  live = n > 0
-  h.check(h.lib.td_online_push(
-      h.ptr, sessions,
-      _ptr(eeg if live else None), int(eeg.stride(1)) if live and n > 1 else c,
-      int(eeg.stride(0)) if live and sessions > 1 else max(n, 1) * c,
-      _ptr(env if live else None), int(env.stride(1)) if live and n > 1 else 2,
-      int(env.stride(0)) if live and sessions > 1 else max(n, 1) * 2,
-      n, c, int(pre), int(post), _ptr(w), 0 if shared else k, _ptr(b), 0 if shared else 1,
-      _ptr(corr), REDUCTIONS[reduction], _ptr(lda), int(width), int(hop), SWEEP_DECODERS[decoder],
-      int(frames_before), 1 if flush else 0, _ptr(state), int(state.stride(0)) if sessions > 1 else int(state.shape[1]),
-      _ptr(scores), _ptr(decisions), _ptr(pred), _ptr(frame)))
-  return OnlinePush(scores[:-1].reshape(2, sessions, plan.new_windows),
-                    decisions[:-1].reshape(sessions, plan.new_windows),
-                    pred[:-1].reshape(sessions, emitted) if want_frames else None,
-                    frame[:-1].reshape(2, sessions, emitted) if want_frames else None, plan)
+  return _decoder_push('online_push', h, h.lib.td_online_push,
+                       (_ptr(w), 0 if shared else k, _ptr(b), 0 if shared else 1), sessions, eeg, env, n, c, pre, post,
+                       corr, lda, state, frames_before, width, hop, reduction, decoder, flush, want_frames)
 
 
 CCA_ONLINE_REDUCTIONS = ('first', 'second', 'mean', 'mean-squared', 'lda')     # td_cca_online_push
@@ -1057,20 +1112,15 @@ CcaOnlinePush = collections.namedtuple('CcaOnlinePush', ['scores', 'decisions', 
 
 def cca_online_state_bytes(c1, pre1, post1, c2, pre2, post2, width):
   """Bytes of one CCA online session's state block (td_cca_online_state_bytes); all zeros = a fresh session."""
-  n = ctypes.c_int64(0)
-  _lib.check(None, _lib.load().td_cca_online_state_bytes(int(c1), int(pre1), int(post1), int(c2), int(pre2),
-                                                         int(post2), int(width), ctypes.byref(n)))
-  return int(n.value)
+  return _lib_values('td_cca_online_state_bytes', (int(c1), int(pre1), int(post1), int(c2), int(pre2), int(post2),
+                                                   int(width)))[0]
 
 
 def cca_online_lds_bytes(c1, pre1, post1, c2, pre2, post2, dims, emitted=64):
   """(frames per pass, LDS bytes) of a td_cca_online_push launch that emits `emitted` frames
   (td_cca_online_lds_bytes); ValueError with the byte budget for a shape that does not fit at a pass of one."""
-  p, n = ctypes.c_int(0), ctypes.c_int64(0)
-  _lib.check(None, _lib.load().td_cca_online_lds_bytes(int(c1), int(pre1), int(post1), int(c2), int(pre2),
-                                                       int(post2), int(dims), int(emitted), ctypes.byref(p),
-                                                       ctypes.byref(n)))
-  return int(p.value), int(n.value)
+  return tuple(_lib_values('td_cca_online_lds_bytes', (int(c1), int(pre1), int(post1), int(c2), int(pre2), int(post2),
+                                                       int(dims), int(emitted)), _I32_I64))
 
 
 def cca_online_push(eeg, feat1, feat2, mean_x, rot_x, mean_y, rot_y, corr, state, frames_before, pre1, post1,
@@ -1089,10 +1139,7 @@ def cca_online_push(eeg, feat1, feat2, mean_x, rot_x, mean_y, rot_y, corr, state
   plan = online_plan(frames_before, n, max(post1, post2), ...).  Queued, not waited for."""
   h = handle or default_handle()
   torch = _torch()
-  if reduction not in CCA_ONLINE_REDUCTIONS:
-    raise ValueError('cca_online_push: reduction %r (one of %s)' % (reduction, ', '.join(CCA_ONLINE_REDUCTIONS)))
-  if decoder not in SWEEP_DECODERS:
-    raise ValueError('cca_online_push: unknown decoder %r' % (decoder,))
+  _check_reduction('cca_online_push', reduction, CCA_ONLINE_REDUCTIONS, decoder)
   sessions = int(state.shape[0])
   pre1, post1, pre2, post2 = int(pre1), int(post1), int(pre2), int(post2)
   nl1, nl2 = pre1 + 1 + post1, pre2 + 1 + post2
@@ -1112,14 +1159,11 @@ def cca_online_push(eeg, feat1, feat2, mean_x, rot_x, mean_y, rot_y, corr, state
     raise ValueError('cca_online_push: eeg of %s and features of %s and %s for %d sessions of %d channels and %d '
                      'features' % (tuple(eeg.shape), None if feat1 is None else tuple(feat1.shape),
                                    None if feat2 is None else tuple(feat2.shape), sessions, c1, c2))
-  for name, t, dtype in (('eeg', eeg, torch.float32), ('feat1', feat1, torch.float32),
-                         ('feat2', feat2, torch.float32), ('mean_x', mean_x, torch.float32),
-                         ('rot_x', rot_x, torch.float32), ('mean_y', mean_y, torch.float32),
-                         ('rot_y', rot_y, torch.float32), ('corr', corr, torch.float64),
-                         ('lda', lda, torch.float64), ('state', state, torch.uint8)):
-    if t is not None and (t.dtype != dtype or t.device != h.device):
-      raise TypeError('cca_online_push: %s must be a %s tensor on %s, not %s on %s' %
-                      (name, dtype, h.device, t.dtype, t.device))
+  _check_tensors('cca_online_push', h, (
+      ('eeg', eeg, torch.float32), ('feat1', feat1, torch.float32), ('feat2', feat2, torch.float32),
+      ('mean_x', mean_x, torch.float32), ('rot_x', rot_x, torch.float32), ('mean_y', mean_y, torch.float32),
+      ('rot_y', rot_y, torch.float32), ('corr', corr, torch.float64), ('lda', lda, torch.float64),
+      ('state', state, torch.uint8)))
   if n > 0:
     if (c1 > 1 and eeg.stride(2) != 1) or (c2 > 1 and (feat1.stride(2) != 1 or feat2.stride(2) != 1)):
       raise ValueError('cca_online_push: the columns of eeg and the features must be contiguous')
@@ -1133,26 +1177,20 @@ def cca_online_push(eeg, feat1, feat2, mean_x, rot_x, mean_y, rot_y, corr, state
   lda = lda.contiguous() if lda is not None else None
   plan = online_plan(frames_before, n, max(post1, post2), width, hop, flush)
   emitted = plan.emitted_after - plan.emitted_before
-  # (every element a push emits is written; an empty tensor has no address: one spare element)
-  scores = h.empty((2 * sessions * plan.new_windows + 1,), 'float64')
-  decisions = h.empty((sessions * plan.new_windows + 1,), 'uint8')
+  new = plan.new_windows
+  # (_spare's and _shaped's, written out as in _decoder_push: eight calls fewer per push)
+  scores = h.empty((2 * sessions * new + 1,), 'float64')
+  decisions = h.empty((sessions * new + 1,), 'uint8')
   proj = h.empty((sessions * emitted * 3 * dims + 1,), 'float32') if want_frames else None
   frame = h.empty((2 * sessions * emitted + 1,), 'float64') if want_frames else None
-  live = n > 0
+  feat1_p, feat_row, feat_session = _row_block(feat1, n, sessions, c2)     # (one pair of strides for both speakers)
   h.check(h.lib.td_cca_online_push(
-      h.ptr, sessions,
-      _ptr(eeg if live else None), int(eeg.stride(1)) if live and n > 1 else c1,
-      int(eeg.stride(0)) if live and sessions > 1 else max(n, 1) * c1,
-      _ptr(feat1 if live else None), _ptr(feat2 if live else None),
-      int(feat1.stride(1)) if live and n > 1 else c2,
-      int(feat1.stride(0)) if live and sessions > 1 else max(n, 1) * c2,
-      n, c1, pre1, post1, c2, pre2, post2, dims, _ptr(mean_x), _ptr(rot_x), _ptr(mean_y), _ptr(rot_y),
+      h.ptr, sessions, *_row_block(eeg, n, sessions, c1), feat1_p, _ptr(feat2 if n > 0 else None), feat_row,
+      feat_session, n, c1, pre1, post1, c2, pre2, post2, dims, _ptr(mean_x), _ptr(rot_x), _ptr(mean_y), _ptr(rot_y),
       0 if models == 1 else 1, _ptr(corr), REDUCTIONS[reduction], _ptr(lda), int(width), int(hop),
-      SWEEP_DECODERS[decoder], int(frames_before), 1 if flush else 0, _ptr(state),
-      int(state.stride(0)) if sessions > 1 else int(state.shape[1]),
+      SWEEP_DECODERS[decoder], int(frames_before), 1 if flush else 0, _ptr(state), _state_stride(state, sessions),
       _ptr(scores), _ptr(decisions), _ptr(proj), _ptr(frame)))
-  return CcaOnlinePush(scores[:-1].reshape(2, sessions, plan.new_windows),
-                       decisions[:-1].reshape(sessions, plan.new_windows),
+  return CcaOnlinePush(scores[:-1].reshape(2, sessions, new), decisions[:-1].reshape(sessions, new),
                        proj[:-1].reshape(sessions, emitted, 3 * dims) if want_frames else None,
                        frame[:-1].reshape(2, sessions, emitted) if want_frames else None, plan)
 
@@ -1170,12 +1208,9 @@ def dnn_param_count(k, hidden):
 def dnn_online_lds_bytes(c, pre, post, hidden, emitted=64):
   """(frames per pass, LDS bytes) of a td_fc_online_push launch that emits `emitted` frames
   (td_fc_online_lds_bytes); ValueError for a shape outside the limits or over the byte budget."""
-  hid = np.ascontiguousarray(list(hidden) or [0], dtype=np.int32)
-  p, n = ctypes.c_int(0), ctypes.c_int64(0)
-  _lib.check(None, _lib.load().td_fc_online_lds_bytes(int(c), int(pre), int(post), len(hidden),
-                                                       hid.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                                       int(emitted), ctypes.byref(p), ctypes.byref(n)))
-  return int(p.value), int(n.value)
+  hid, hid_p = _i32_array(list(hidden) or [0])
+  return tuple(_lib_values('td_fc_online_lds_bytes', (int(c), int(pre), int(post), len(hidden), hid_p, int(emitted)),
+                           _I32_I64))
 
 
 def dnn_online_push(eeg, env, params, hidden, corr, state, frames_before, pre, post, width, hop, reduction='first',
@@ -1190,10 +1225,7 @@ def dnn_online_push(eeg, env, params, hidden, corr, state, frames_before, pre, p
   -- and frame [2, S, emitted] float64 (None without want_frames), plan).  Queued, not waited for."""
   h = handle or default_handle()
   torch = _torch()
-  if reduction not in ONLINE_REDUCTIONS:
-    raise ValueError('dnn_online_push: reduction %r (one of %s)' % (reduction, ', '.join(ONLINE_REDUCTIONS)))
-  if decoder not in SWEEP_DECODERS:
-    raise ValueError('dnn_online_push: unknown decoder %r' % (decoder,))
+  _check_reduction('dnn_online_push', reduction, ONLINE_REDUCTIONS, decoder)
   hidden = [int(v) for v in hidden]
   sessions = int(state.shape[0])
   nl = int(pre) + 1 + int(post)
@@ -1207,48 +1239,16 @@ def dnn_online_push(eeg, env, params, hidden, corr, state, frames_before, pre, p
   if nl < 1 or k < 1 or k % nl or dnn_param_count(k, hidden) != count:
     raise ValueError('dnn_online_push: %d parameters for hidden layers %s on %d lags' % (count, hidden, nl))
   c = k // nl
-  n = 0 if eeg is None else int(eeg.shape[1])
-  if eeg is not None and (tuple(eeg.shape) != (sessions, n, c) or env is None or
-                          tuple(env.shape) != (sessions, n, 2)):
-    raise ValueError('dnn_online_push: eeg of %s and env of %s for %d sessions of %d channels' %
-                     (tuple(eeg.shape), None if env is None else tuple(env.shape), sessions, c))
-  for name, t, dtype in (('eeg', eeg, torch.float32), ('env', env, torch.float32), ('params', params, torch.float32),
-                         ('corr', corr, torch.float64), ('lda', lda, torch.float64), ('state', state, torch.uint8)):
-    if t is not None and (t.dtype != dtype or t.device != h.device):
-      raise TypeError('dnn_online_push: %s must be a %s tensor on %s, not %s on %s' %
-                      (name, dtype, h.device, t.dtype, t.device))
-  if n > 0 and (eeg.stride(2) != 1 and c > 1 or env.stride(2) != 1):
-    raise ValueError('dnn_online_push: the columns of eeg and env must be contiguous')
-  if tuple(corr.shape) != (sessions, 2, 3) or (lda is not None and tuple(lda.shape) != (sessions, 3)):
-    raise ValueError('dnn_online_push: corr must be [%d, 2, 3] and lda [%d, 3]' % (sessions, sessions))
+  n = _check_decoder_rows('dnn_online_push', h, torch, sessions, c, eeg, env, (('params', params, torch.float32),),
+                          corr, lda, state)
   if params.stride(1) != 1 and count > 1:
     params = params.contiguous()
-  corr = corr.contiguous()
-  lda = lda.contiguous() if lda is not None else None
   shared = int(params.shape[0]) == 1
   hid, hid_p = _i32_array(hidden or [0])
-  plan = online_plan(frames_before, n, post, width, hop, flush)
-  emitted = plan.emitted_after - plan.emitted_before
-  # (every element a push emits is written; an empty tensor has no address: one spare element)
-  scores = h.empty((2 * sessions * plan.new_windows + 1,), 'float64')
-  decisions = h.empty((sessions * plan.new_windows + 1,), 'uint8')
-  pred = h.empty((sessions * emitted + 1,), 'float32') if want_frames else None
-  frame = h.empty((2 * sessions * emitted + 1,), 'float64') if want_frames else None
-  live = n > 0
-  h.check(h.lib.td_fc_online_push(
-      h.ptr, sessions,
-      _ptr(eeg if live else None), int(eeg.stride(1)) if live and n > 1 else c,
-      int(eeg.stride(0)) if live and sessions > 1 else max(n, 1) * c,
-      _ptr(env if live else None), int(env.stride(1)) if live and n > 1 else 2,
-      int(env.stride(0)) if live and sessions > 1 else max(n, 1) * 2,
-      n, c, int(pre), int(post), hid_p, len(hidden), _ptr(params), 0 if shared else int(params.stride(0)),
-      _ptr(corr), REDUCTIONS[reduction], _ptr(lda), int(width), int(hop), SWEEP_DECODERS[decoder],
-      int(frames_before), 1 if flush else 0, _ptr(state), int(state.stride(0)) if sessions > 1 else int(state.shape[1]),
-      _ptr(scores), _ptr(decisions), _ptr(pred), _ptr(frame)))
-  return OnlinePush(scores[:-1].reshape(2, sessions, plan.new_windows),
-                    decisions[:-1].reshape(sessions, plan.new_windows),
-                    pred[:-1].reshape(sessions, emitted) if want_frames else None,
-                    frame[:-1].reshape(2, sessions, emitted) if want_frames else None, plan)
+  return _decoder_push('dnn_online_push', h, h.lib.td_fc_online_push,
+                       (hid_p, len(hidden), _ptr(params), 0 if shared else int(params.stride(0))), sessions, eeg, env,
+                       n, c, pre, post, corr, lda, state, frames_before, width, hop, reduction, decoder, flush,
+                       want_frames)
 
 
 def sos_filter(x, file_offsets, sos, zi, stage_split, state, reset, out_rows=None, out_offsets=None, handle=None):
@@ -1692,26 +1692,19 @@ FrontendPush = collections.namedtuple('FrontendPush', ['out32', 'out64', 'plan']
 def frontend_state_bytes(c, num_sections):
   """Bytes of one front-end session's state block (td_frontend_state_bytes): the filter state [sections, 2, c], the
   held row and the last row, float64; all zeros = a fresh session."""
-  n = ctypes.c_int64(0)
-  _lib.check(None, _lib.load().td_frontend_state_bytes(int(c), int(num_sections), ctypes.byref(n)))
-  return int(n.value)
+  return _lib_values('td_frontend_state_bytes', (int(c), int(num_sections)))[0]
 
 
 def frontend_plan(rows_before, n, fs_in, fs_out, flush=False):
   """What a push of n raw rows behind `rows_before` pushed ones emits (td_frontend_plan, host arithmetic in the
   reference's float64 order): FrontendPlan(frames_before, frames_after, held)."""
-  out = [ctypes.c_int64(0) for _ in range(3)]
-  _lib.check(None, _lib.load().td_frontend_plan(int(rows_before), int(n), float(fs_in), float(fs_out),
-                                                1 if flush else 0, *[ctypes.byref(v) for v in out]))
-  return FrontendPlan(*[int(v.value) for v in out])
+  return FrontendPlan(*_lib_values('td_frontend_plan', (int(rows_before), int(n), float(fs_in), float(fs_out),
+                                                        1 if flush else 0), _I64 * 3))
 
 
 def frontend_lds_bytes(c, num_groups, emitted=64):
   """(frames per pass, LDS bytes) of a td_frontend_push launch that emits `emitted` frames (td_frontend_lds_bytes)."""
-  p, n = ctypes.c_int(0), ctypes.c_int64(0)
-  _lib.check(None, _lib.load().td_frontend_lds_bytes(int(c), int(num_groups), int(emitted), ctypes.byref(p),
-                                                     ctypes.byref(n)))
-  return int(p.value), int(n.value)
+  return tuple(_lib_values('td_frontend_lds_bytes', (int(c), int(num_groups), int(emitted)), _I32_I64))
 
 
 def frontend_push(x, sos, stage_split, zi, fs_in, fs_out, groups, select, mean, std, state, rows_before, c=None,
@@ -1740,10 +1733,8 @@ def frontend_push(x, sos, stage_split, zi, fs_in, fs_out, groups, select, mean, 
       raise ValueError('frontend_push: the columns of x must be contiguous')
   if c is None:
     raise ValueError('frontend_push: a flush without rows needs the channel count c')
-  for name, t, dtype in (('mean', mean, torch.float64), ('std', std, torch.float64), ('state', state, torch.uint8)):
-    if t.dtype != dtype or t.device != h.device:
-      raise TypeError('frontend_push: %s must be a %s tensor on %s, not %s on %s' %
-                      (name, dtype, h.device, t.dtype, t.device))
+  _check_tensors('frontend_push', h, (('mean', mean, torch.float64), ('std', std, torch.float64),
+                                      ('state', state, torch.uint8)))
   mean, std = mean.reshape(-1).contiguous(), std.reshape(-1).contiguous()
   if int(mean.numel()) not in (1, sessions) or int(std.numel()) != int(mean.numel()):
     raise ValueError('frontend_push: %d means and %d stds for %d sessions' %
@@ -1763,19 +1754,16 @@ def frontend_push(x, sos, stage_split, zi, fs_in, fs_out, groups, select, mean, 
   keep = [_i32_array(v or [0]) for v in (ref_ptr, ref_idx, ch_ptr, ch_idx, sel)]
   plan = frontend_plan(rows_before, n, fs_in, fs_out, flush)
   m, cs = plan.frames_after - plan.frames_before, len(sel)
-  # (every element a push emits is written; an empty tensor has no address: one spare element)
-  out32 = h.empty((sessions * m * cs + 1,), 'float32') if want32 else None
-  out64 = h.empty((sessions * m * cs + 1,), 'float64') if want64 else None
-  live = n > 0
+  out32 = _spare(h, sessions * m * cs, 'float32', want32)
+  out64 = _spare(h, sessions * m * cs, 'float64', want64)
+  x_p, x_row, x_session = _row_block(x, n, sessions, int(c))
   h.check(h.lib.td_frontend_push(
-      h.ptr, sessions, _ptr(x if live else None), 1 if live and x.dtype == torch.float64 else 0,
-      int(x.stride(1)) if live and n > 1 else int(c), int(x.stride(0)) if live and sessions > 1 else max(n, 1) * int(c),
+      h.ptr, sessions, x_p, 1 if n > 0 and x.dtype == torch.float64 else 0, x_row, x_session,
       n, int(c), sos_p if sections else None, sections, int(stage_split), zi_p if sections else None, float(fs_in),
       float(fs_out), len(groups), keep[0][1], keep[1][1], keep[2][1], keep[3][1], keep[4][1], cs, _ptr(mean),
       _ptr(std), 0 if int(mean.numel()) == 1 else 1, int(rows_before), 1 if flush else 0, _ptr(state),
-      int(state.stride(0)) if sessions > 1 else int(state.shape[1]), _ptr(out32), _ptr(out64), cs, max(m, 1) * cs))
-  shaped = lambda t: t[:-1].reshape(sessions, m, cs) if t is not None else None
-  return FrontendPush(shaped(out32), shaped(out64), plan)
+      _state_stride(state, sessions), _ptr(out32), _ptr(out64), cs, max(m, 1) * cs))
+  return FrontendPush(_shaped(out32, sessions, m, cs), _shaped(out64, sessions, m, cs), plan)
 
 
 # ---------------------------------------------------------------- online audio front end
@@ -1789,19 +1777,14 @@ AudioOnlinePush = collections.namedtuple('AudioOnlinePush', ['out32', 'out64', '
 def audio_online_plan(rows_before, n, fs_in, fs_out, window, flush=False):
   """What a push of n audio rows behind `rows_before` pushed ones emits (td_audio_online_plan, host arithmetic in
   the reference's float64 order): AudioOnlinePlan(frames_before, frames_after, held, tail_rows)."""
-  out = [ctypes.c_int64(0) for _ in range(4)]
-  _lib.check(None, _lib.load().td_audio_online_plan(int(rows_before), int(n), float(fs_in), float(fs_out),
-                                                    float(window), 1 if flush else 0,
-                                                    *[ctypes.byref(v) for v in out]))
-  return AudioOnlinePlan(*[int(v.value) for v in out])
+  return AudioOnlinePlan(*_lib_values('td_audio_online_plan', (int(rows_before), int(n), float(fs_in), float(fs_out),
+                                                               float(window), 1 if flush else 0), _I64 * 4))
 
 
 def audio_online_state_bytes(c, tail_rows):
   """Bytes of one online audio session's state block (td_audio_online_state_bytes): two tail copies of
   [tail_rows, c] float32 squares; all zeros = a fresh session."""
-  n = ctypes.c_int64(0)
-  _lib.check(None, _lib.load().td_audio_online_state_bytes(int(c), int(tail_rows), ctypes.byref(n)))
-  return int(n.value)
+  return _lib_values('td_audio_online_state_bytes', (int(c), int(tail_rows)))[0]
 
 
 def audio_online_push(x, fs_in, fs_out, window, exponent, state, live, rows_before, c=None, flush=False, want32=True,
@@ -1831,28 +1814,22 @@ def audio_online_push(x, fs_in, fs_out, window, exponent, state, live, rows_befo
       raise ValueError('audio_online_push: the columns of x must be contiguous')
   if c is None:
     raise ValueError('audio_online_push: a flush without rows needs the channel count c')
-  if state.dtype != torch.uint8 or state.device != h.device:
-    raise TypeError('audio_online_push: state must be a uint8 tensor on %s, not %s on %s' %
-                    (h.device, state.dtype, state.device))
+  _check_tensors('audio_online_push', h, (('state', state, torch.uint8),), short=True)
   if not want32 and not want64:
     raise ValueError('audio_online_push: neither the float32 nor the float64 output is wanted')
   c = int(c)
   plan = audio_online_plan(rows_before, n, fs_in, fs_out, window, flush)
   m = plan.frames_after - plan.frames_before
-  # (every element a push emits is written; an empty tensor has no address: one spare element)
-  out32 = h.empty((sessions * m * c + 1,), 'float32') if want32 else None
-  out64 = h.empty((sessions * m * c + 1,), 'float64') if want64 else None
-  win = h.empty((m + 1, 2), 'int64') if windows else None
-  rows = n > 0
+  out32 = _spare(h, sessions * m * c, 'float32', want32)
+  out64 = _spare(h, sessions * m * c, 'float64', want64)
+  win = h.empty((m + 1, 2), 'int64') if windows else None       # (a spare ROW: the same reason)
+  x_p, x_row, x_session = _row_block(x, n, sessions, c)
   h.check(h.lib.td_audio_online_push(
-      h.ptr, sessions, _ptr(x if rows else None), x_type, int(x.stride(1)) if rows and n > 1 else c,
-      int(x.stride(0)) if rows and sessions > 1 else max(n, 1) * c, n, c, int(rows_before), 1 if flush else 0,
-      float(fs_in), float(fs_out), float(window), float(exponent), _ptr(state),
-      int(state.stride(0)) if sessions > 1 else int(state.shape[1]), int(live), _ptr(out32), _ptr(out64), c,
-      max(m, 1) * c, _ptr(win)))
-  shaped = lambda t: t[:-1].reshape(sessions, m, c) if t is not None else None
-  return AudioOnlinePush(shaped(out32), shaped(out64), win[:m] if windows else None, plan,
-                         1 - int(live) if rows else int(live))
+      h.ptr, sessions, x_p, x_type, x_row, x_session, n, c, int(rows_before), 1 if flush else 0,
+      float(fs_in), float(fs_out), float(window), float(exponent), _ptr(state), _state_stride(state, sessions),
+      int(live), _ptr(out32), _ptr(out64), c, max(m, 1) * c, _ptr(win)))
+  return AudioOnlinePush(_shaped(out32, sessions, m, c), _shaped(out64, sessions, m, c),
+                         win[:m] if windows else None, plan, 1 - int(live) if n > 0 else int(live))
 
 
 # ---------------------------------------------------------------- online ridge fit
@@ -1863,17 +1840,16 @@ ONLINE_FIT_MAX_CHANNELS, ONLINE_FIT_MAX_LAGS, ONLINE_FIT_MAX_K, ONLINE_FIT_MAX_O
 def online_fit_state_bytes(c, pre, post, d):
   """Bytes of one online fit session's state block (td_fit_online_state_bytes): A [(K + 1)^2] and B [(K + 1) d]
   float64, then two tail copies of {EEG [pre + post, c], target [post, d]} float32; all zeros = a fresh session."""
-  n = ctypes.c_int64(0)
-  _lib.check(None, _lib.load().td_fit_online_state_bytes(int(c), int(pre), int(post), int(d), ctypes.byref(n)))
-  return int(n.value)
+  return _lib_values('td_fit_online_state_bytes', (int(c), int(pre), int(post), int(d)))[0]
 
 
 def _check_fit_state(who, h, state):
+  """(sessions, state stride) of the fit's and the calibration's state, refused in their words unless [S, bytes]."""
   if state.dtype != _torch().uint8 or state.device != h.device or state.dim() != 2:
     raise TypeError('%s: state must be a [S, bytes] uint8 tensor on %s, not %s %s on %s' %
                     (who, h.device, tuple(state.shape), state.dtype, state.device))
   sessions = int(state.shape[0])
-  return sessions, int(state.stride(0)) if sessions > 1 else int(state.shape[1])
+  return sessions, _state_stride(state, sessions)
 
 
 def online_fit_push(eeg, target, state, frames_before, pushes_before, pre, post, c=None, d=None, flush=False,
@@ -1894,22 +1870,14 @@ def online_fit_push(eeg, target, state, frames_before, pushes_before, pre, post,
       raise ValueError('online_fit_push: eeg of %s and target of %s for %d sessions' %
                        (tuple(eeg.shape), None if target is None else tuple(target.shape), sessions))
     c, d = int(eeg.shape[2]), int(target.shape[2])
-    for name, t in (('eeg', eeg), ('target', target)):
-      if t.dtype != torch.float32 or t.device != h.device:
-        raise TypeError('online_fit_push: %s must be a float32 tensor on %s, not %s on %s' %
-                        (name, h.device, t.dtype, t.device))
+    _check_tensors('online_fit_push', h, (('eeg', eeg, torch.float32), ('target', target, torch.float32)), short=True)
     if n > 0 and (eeg.stride(2) != 1 and c > 1 or target.stride(2) != 1 and d > 1):
       raise ValueError('online_fit_push: the columns of eeg and target must be contiguous')
   if c is None or d is None:
     raise ValueError('online_fit_push: a flush without rows needs the channel count c and the output count d')
   c, d = int(c), int(d)
-  rows = n > 0
   h.check(h.lib.td_fit_online_push(
-      h.ptr, sessions,
-      _ptr(eeg if rows else None), int(eeg.stride(1)) if rows and n > 1 else c,
-      int(eeg.stride(0)) if rows and sessions > 1 else max(n, 1) * c,
-      _ptr(target if rows else None), int(target.stride(1)) if rows and n > 1 else d,
-      int(target.stride(0)) if rows and sessions > 1 else max(n, 1) * d,
+      h.ptr, sessions, *_row_block(eeg, n, sessions, c), *_row_block(target, n, sessions, d),
       n, c, int(pre), int(post), d, int(frames_before), int(pushes_before), 1 if flush else 0, float(forget),
       _ptr(state), stride))
   return int(frames_before) + n
@@ -1958,9 +1926,7 @@ OnlineCalibFinish = collections.namedtuple('OnlineCalibFinish', ['corr', 'lda', 
 def online_calib_state_bytes(c, pre, post):
   """Bytes of one online calibration session's state block (td_calib_online_state_bytes): ONLINE_CALIB_SUMS float64
   sums, then the EEG tail [pre + post, c] and the envelope tail [post, 2] float32; all zeros = a fresh session."""
-  n = ctypes.c_int64(0)
-  _lib.check(None, _lib.load().td_calib_online_state_bytes(int(c), int(pre), int(post), ctypes.byref(n)))
-  return int(n.value)
+  return _lib_values('td_calib_online_state_bytes', (int(c), int(pre), int(post)))[0]
 
 
 def online_calib_push(eeg, env, w, b, state, frames_before, pre, post, width, c=None, flush=False, handle=None):
@@ -1985,10 +1951,8 @@ def online_calib_push(eeg, env, w, b, state, frames_before, pre, post, width, c=
   if c is None:
     raise ValueError('online_calib_push: a flush without rows needs the channel count c')
   c = int(c)
-  for name, t in (('eeg', eeg), ('env', env), ('w', w), ('b', b)):
-    if t is not None and (t.dtype != torch.float32 or t.device != h.device):
-      raise TypeError('online_calib_push: %s must be a float32 tensor on %s, not %s on %s' %
-                      (name, h.device, t.dtype, t.device))
+  _check_tensors('online_calib_push', h, (('eeg', eeg, torch.float32), ('env', env, torch.float32),
+                                          ('w', w, torch.float32), ('b', b, torch.float32)), short=True)
   if n > 0 and (eeg.stride(2) != 1 and c > 1 or env.stride(2) != 1):
     raise ValueError('online_calib_push: the columns of eeg and env must be contiguous')
   if w.dim() != 2 or int(w.shape[0]) not in (1, sessions) or int(b.numel()) != int(w.shape[0]):
@@ -1999,13 +1963,8 @@ def online_calib_push(eeg, env, w, b, state, frames_before, pre, post, width, c=
     raise ValueError('online_calib_push: %d weights for %d lags of %d channels' % (k, int(pre) + 1 + int(post), c))
   w, b = w.contiguous(), b.reshape(-1).contiguous()
   shared = int(w.shape[0]) == 1
-  rows = n > 0
   h.check(h.lib.td_calib_online_push(
-      h.ptr, sessions,
-      _ptr(eeg if rows else None), int(eeg.stride(1)) if rows and n > 1 else c,
-      int(eeg.stride(0)) if rows and sessions > 1 else max(n, 1) * c,
-      _ptr(env if rows else None), int(env.stride(1)) if rows and n > 1 else 2,
-      int(env.stride(0)) if rows and sessions > 1 else max(n, 1) * 2,
+      h.ptr, sessions, *_row_block(eeg, n, sessions, c), *_row_block(env, n, sessions, 2),
       _ptr(w), 0 if shared else k, _ptr(b), 0 if shared else 1,
       n, int(frames_before), c, int(pre), int(post), int(width), 1 if flush else 0, _ptr(state), stride))
   return int(frames_before) + n

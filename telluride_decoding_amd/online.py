@@ -457,7 +457,54 @@ class _HostDnnSession(_HostSession):
     return scores, decisions, pred, frame, pl
 
 
-class OnlineDecoder(object):
+class _Bank(object):
+  """What the five online banks share: S sessions that run on the device (`_dev`: a dict with the handle 'h' and the
+  zeroed uint8 'state' [S, bytes]) or as NumPy sessions (`_host`: a list of S objects with reset()), and refuse pushes
+  once flushed.  A class gives FLUSHED, its sentence for that refusal."""
+  FLUSHED = None
+
+  def __init__(self, sessions, on_device):
+    self.sessions, self._on_device = sessions, on_device
+    self._dev = self._host = None
+    self.flushed = False
+
+  def _zero_state(self, h, nbytes):
+    """A bank of fresh sessions: [S, nbytes] uint8 zeros on the handle's device."""
+    torch = device._torch()
+    return torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device)
+
+  def reset(self):
+    """Zero state, not flushed (the class's own counters are its own reset's)."""
+    self.flushed = False
+    if self._dev is not None:
+      self._dev['state'].zero_()
+    if self._host is not None:
+      for sess in self._host:
+        sess.reset()
+
+  def _refuse_flushed(self):
+    if self.flushed:
+      raise ValueError(self.FLUSHED)
+
+  def _no_rows(self, width, dtype=np.float32):
+    """What the NumPy sessions take for a flush without rows."""
+    return np.zeros((self.sessions, 0, width), dtype)
+
+  @staticmethod
+  def _last_rows(sentence, *arrays):
+    """Whether a flush carries last rows: all of `arrays` or none of them, else `sentence`."""
+    given = [a is not None for a in arrays]
+    if any(given) and not all(given):
+      raise ValueError(sentence)
+    return given[0]
+
+  @staticmethod
+  def _upload(h, a):
+    """A host array [..., k] as a float32 device tensor of its shape (Handle.to_device takes two dimensions)."""
+    return h.to_device(a.reshape(-1, a.shape[-1])).reshape(a.shape)
+
+
+class OnlineDecoder(_Bank):
   """A bank of online decoding sessions, one per listener.
 
   decoders: one infer_decoder.LinearRegressionDecoder around a fitted BrainModelLinearRegression, or a list
@@ -484,6 +531,7 @@ class OnlineDecoder(object):
   decoding_model_params, the model's add_metadata entry, or the keyword arguments pre_context= / post_context=;
   sessions around bitwise-equal parameters read one copy of them.
   """
+  FLUSHED = 'The session was flushed: reset() starts the next recording.'
 
   def __init__(self, decoders, window_size, window_step=None, decoder_type='wta', frame_rate=100.0,
                ssd_offset=0.0, **context):
@@ -519,7 +567,6 @@ class OnlineDecoder(object):
       raise ValueError('Window size %d gives a window step of %d.' % (window_size, window_step))
     if decoder_type not in DECODER_TYPES:
       raise ValueError('Unknown type (%s) requested from OnlineDecoder' % decoder_type)
-    self.sessions = len(self._params)
     self.channels, self.pre, self.post = first['c'], first['pre'], first['post']
     self.reduction = first['reduction']
     self.delay = self.post                      # frames the results run behind the input
@@ -534,10 +581,9 @@ class OnlineDecoder(object):
     if self.decoder_type == 'ssd':
       self._ssd = attention_decoder.create_attention_decoder('ssd', window_step=window_step,
                                                              frame_rate=frame_rate, ssd_offset=ssd_offset)
-    self._on_device = device.gpu_available()
+    _Bank.__init__(self, len(self._params), device.gpu_available())
     if self._ssd is not None and not self._on_device:
       raise _lib.HotPathUnavailable('The state-space decoder has no host form: \'ssd\' needs the GPU.')
-    self._dev = None
     self.reset()
 
   @classmethod
@@ -550,7 +596,6 @@ class OnlineDecoder(object):
   # -- state -------------------------------------------------------------------------------------
   def _device_setup(self):
     h = device.default_handle()
-    torch = device._torch()
     ps = self._params
     dev = dict(h=h)
     # the model: sessions around ONE model (bitwise-equal parameters for a DNN) read one copy of it
@@ -560,8 +605,7 @@ class OnlineDecoder(object):
     models = ps[:1] if shared else ps
     if self.kind == 'cca':
       for k in names:
-        stacked = np.stack([p[k] for p in models])
-        dev[k] = h.to_device(stacked.reshape(-1, stacked.shape[-1])).reshape(stacked.shape)
+        dev[k] = self._upload(h, np.stack([p[k] for p in models]))
     elif self.kind == 'dnn':
       # (a row starts on a 16-byte boundary)
       count = int(ps[0]['params'].size)
@@ -582,12 +626,14 @@ class OnlineDecoder(object):
                                              self.post2, self.window_size)
     else:
       nbytes = device.online_state_bytes(self.channels, self.pre, self.post, self.window_size)
-    dev['state'] = torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device)
+    dev['state'] = self._zero_state(h, nbytes)
     dev['ssd_state'] = device.ssd_state(self.sessions, handle=h) if self._ssd is not None else None
     return dev
 
   def reset(self):
-    """A fresh recording: zero state, no frame pushed."""
+    """A fresh recording: zero state, no frame pushed.  (Its own, not _Bank's: the device bank is set up here at the
+    first call, the state-space decoder's state is zeroed too, and the NumPy sessions are rebuilt from the
+    parameters set_weights and set_statistics may have replaced.)"""
     self.frames_pushed = 0
     self.flushed = False
     if self._on_device:
@@ -738,8 +784,7 @@ class OnlineDecoder(object):
     speaker 2) -- for a CCA bank each speaker's feature block [n, c2] / [S, n, c2] --, host arrays or device
     tensors.  Returns OnlineResult(scores [S, new, 2] float64, decisions [S, new] uint8 -- [S, new, 3] float64
     (p, lower, upper) for 'ssd' --, first_window) for the windows this push completes (host arrays)."""
-    if self.flushed:
-      raise ValueError('The session was flushed: reset() starts the next recording.')
+    self._refuse_flushed()
     if self.kind == 'cca':
       eeg, env = self._as_cca_bank(eeg, env1, env2)
     else:
@@ -749,8 +794,7 @@ class OnlineDecoder(object):
   def flush(self):
     """The end of the recording: the last post_context frames are emitted as if zero rows followed.  After
     it the session refuses pushes until reset()."""
-    if self.flushed:
-      raise ValueError('The session was flushed: reset() starts the next recording.')
+    self._refuse_flushed()
     result = self._advance(None, None, True)
     self.flushed = True
     return result
@@ -763,9 +807,8 @@ class OnlineDecoder(object):
     if not self._on_device:
       # the NumPy sessions, one listener each
       if eeg is None:
-        eeg = np.zeros((self.sessions, 0, self.channels), np.float32)
-        side = ((np.zeros((self.sessions, 0, self.features), np.float32),) * 2 if cca else
-                np.zeros((self.sessions, 0, 2), np.float32))
+        eeg = self._no_rows(self.channels)
+        side = (self._no_rows(self.features),) * 2 if cca else self._no_rows(2)
       outs = []
       for i, sess in enumerate(self._host):
         mine = (np.stack([np.asarray(f[i], np.float64) for f in side]) if cca else
@@ -781,8 +824,7 @@ class OnlineDecoder(object):
     else:
       env = side
       if eeg is not None and not hasattr(eeg, 'is_cuda'):
-        eeg, env = h.to_device(eeg.reshape(-1, self.channels)).reshape(eeg.shape), \
-            h.to_device(env.reshape(-1, 2)).reshape(env.shape)
+        eeg, env = self._upload(h, eeg), self._upload(h, env)
       if n == 0:
         eeg = env = None
       if self.kind == 'dnn':
@@ -804,7 +846,7 @@ class OnlineDecoder(object):
     if n == 0:
       eeg = None
     else:
-      up = lambda a: a if hasattr(a, 'is_cuda') else h.to_device(a.reshape(-1, a.shape[-1])).reshape(a.shape)
+      up = lambda a: a if hasattr(a, 'is_cuda') else self._upload(h, a)
       eeg, feat1, feat2 = up(eeg), up(feats[0]), up(feats[1])
     return device.cca_online_push(eeg, feat1, feat2, d['mean_x'], d['rot_x'], d['mean_y'], d['rot_y'], d['corr'],
                                   d['state'], self.frames_pushed, self.pre, self.post, self.pre2, self.post2,
@@ -995,7 +1037,105 @@ class _HostFrontSession(object):
     return (out - self.mean) / self.std
 
 
-class OnlinePreprocessor(object):
+class _FrontEnd(_Bank):
+  """What the two front ends share: a bank configured by one object or a list of S, whose row width is known at the
+  first push, and one push path.  A class gives
+    NAME, OBJECTS     its name and what it is configured by, for the messages; SHARE: its sentence for two objects
+                      that differ in a setting (key, the first's value, this one's)
+    ROWS, WIDTH       what a push's argument and its width are called in the shape message
+    DTYPES            the dtypes a push passes on as they are; a host array of another goes through HOST_CAST (a
+                      device tensor through float32)
+    COLUMN            whether one session's 1-D push is a column
+    CAST_ERRSTATE     np.errstate's arguments around the NumPy sessions' float64 -> float32
+    _parameters(object) -> cfg; _settings(object, cfg) -> {key: the value a bank shares}
+    _setup(c)         the sessions, once the width is known
+    _host_push(x or None, flush) -> float64 [S, m, cs]
+    _to_device(host rows, h) -> tensor; _device_push(x or None, flush, want64) -> a push with out32, out64, plan."""
+  DTYPES = ('float32', 'float64')
+  HOST_CAST, COLUMN, CAST_ERRSTATE = np.float64, False, {}
+
+  def __init__(self, objects, num_sessions):
+    if not isinstance(objects, (list, tuple)):
+      objects = [objects] * (1 if num_sessions is None else int(num_sessions))
+    elif num_sessions is not None and int(num_sessions) != len(objects):
+      raise ValueError('%s: %d %s for num_sessions=%d.' % (self.NAME, len(objects), self.OBJECTS, int(num_sessions)))
+    if not objects:
+      raise ValueError('%s needs at least one session.' % self.NAME)
+    self._cfgs = [self._parameters(o) for o in objects]
+    first = self._settings(objects[0], self._cfgs[0])
+    for o, cfg in zip(objects[1:], self._cfgs[1:]):
+      for key, value in self._settings(o, cfg).items():
+        if _plain(value) != _plain(first[key]):
+          raise ValueError(self.SHARE % (key, first[key], value))
+    self._cfg = self._cfgs[0]
+    _Bank.__init__(self, len(objects), device.gpu_available())
+    self.fs_in, self.fs_out = self._cfg['fs_in'], self._cfg['fs_out']
+    self.channels = None                         # the row's width: known at the first push
+    self.rows_pushed = self.frames_emitted = 0
+    self._tensors = False
+    self._host_dtypes = [np.dtype(name) for name in self.DTYPES]
+    self._device_dtypes = [getattr(device._torch(), name) for name in self.DTYPES] if self._on_device else None
+
+  def reset(self):
+    self.rows_pushed = self.frames_emitted = 0
+    _Bank.reset(self)
+
+  def _flush(self, want64):
+    self._refuse_flushed()
+    out = self._advance(None, True, want64)
+    self.flushed = True
+    return out
+
+  def _advance(self, rows, flush, want64):
+    on_dev_in = self._tensors if rows is None else hasattr(rows, 'is_cuda')
+    self._tensors = on_dev_in                    # (a flush answers as the last push did)
+    if rows is not None:
+      if not on_dev_in:
+        rows = np.asarray(rows)
+        if rows.dtype not in self._host_dtypes:
+          rows = rows.astype(self.HOST_CAST)
+      if self.COLUMN and len(rows.shape) == 1 and self.sessions == 1:
+        rows = rows.reshape(-1, 1)
+      if len(rows.shape) == 2 and self.sessions == 1:
+        rows = rows[None]
+      if len(rows.shape) != 3 or int(rows.shape[0]) != self.sessions or (
+          self.channels is not None and int(rows.shape[2]) != self.channels):
+        width = self.channels or self.WIDTH
+        raise ValueError('A push is %s [%d, n, %s] (or [n, %s] for one session), not %s.' %
+                         (self.ROWS, self.sessions, width, width, tuple(rows.shape)))
+      if self.channels is None:
+        self._setup(int(rows.shape[2]))
+    n = 0 if rows is None else int(rows.shape[1])
+    if self.channels is None:                    # (a flush before any row)
+      empty = np.zeros((self.sessions, 0, 0), np.float32)
+      return (empty, empty.astype(np.float64)) if want64 else empty
+    if not self._on_device:
+      out64 = self._host_push(rows.cpu().numpy() if hasattr(rows, 'cpu') else rows, flush)
+      self.rows_pushed += n
+      self.frames_emitted += out64.shape[1]
+      with np.errstate(**self.CAST_ERRSTATE):
+        out32 = out64.astype(np.float32)
+      if on_dev_in:
+        out32, out64 = device._torch().from_numpy(out32), device._torch().from_numpy(out64)
+      return (out32, out64) if want64 else out32
+    x = None
+    if n > 0:
+      if on_dev_in:
+        x = rows if rows.dtype in self._device_dtypes else rows.to(device._torch().float32)
+        if x.stride(2) != 1 and self.channels > 1:
+          x = x.contiguous()
+      else:
+        x = self._to_device(rows, self._dev['h'])
+    out = self._device_push(x, flush, want64)
+    self.rows_pushed += n
+    self.frames_emitted = out.plan.frames_after
+    out32, out64 = out.out32, out.out64
+    if not on_dev_in:
+      out32, out64 = out32.cpu().numpy(), out64.cpu().numpy() if want64 else None
+    return (out32, out64) if want64 else out32
+
+
+class OnlinePreprocessor(_FrontEnd):
   """The online EEG front end: a bank of S sessions that take raw rows in pushes of any length and give the
   conditioned float32 frames OnlineDecoder.push takes as `eeg` -- one td_frontend_push launch per push, the filter
   state and the resample phase on the device, and any cut of a recording gives the bytes of one push.
@@ -1010,32 +1150,19 @@ class OnlinePreprocessor(object):
 
   Without a GPU the same object runs a NumPy float64 session of the same semantics."""
 
+  NAME, OBJECTS, ROWS, WIDTH = 'OnlinePreprocessor', 'preprocessors', 'raw', 'C'
+  SHARE = 'The sessions of a bank share everything except data_mean and data_std: %s is %s and %s.'
+  FLUSHED = 'The front end was flushed: reset() starts the next recording.'
+  _parameters = staticmethod(frontend_parameters)
+
   def __init__(self, preprocessors, num_sessions=None):
-    if not isinstance(preprocessors, (list, tuple)):
-      preprocessors = [preprocessors] * (1 if num_sessions is None else int(num_sessions))
-    elif num_sessions is not None and int(num_sessions) != len(preprocessors):
-      raise ValueError('OnlinePreprocessor: %d preprocessors for num_sessions=%d.' %
-                       (len(preprocessors), int(num_sessions)))
-    if not preprocessors:
-      raise ValueError('OnlinePreprocessor needs at least one session.')
-    self._cfgs = [frontend_parameters(p) for p in preprocessors]
-    first = preprocessors[0]
-    for p in preprocessors[1:]:
-      for key in FRONT_SHARED:
-        if _plain(getattr(p, key)) != _plain(getattr(first, key)):
-          raise ValueError('The sessions of a bank share everything except data_mean and data_std: %s is %s and %s.' %
-                           (key, getattr(first, key), getattr(p, key)))
-    self._cfg = self._cfgs[0]
-    self.sessions = len(preprocessors)
-    self.fs_in, self.fs_out = self._cfg['fs_in'], self._cfg['fs_out']
+    _FrontEnd.__init__(self, preprocessors, num_sessions)
     self.sections = 0 if self._cfg['sos'] is None else int(self._cfg['sos'].shape[0])
-    self.channels = None                         # the raw row's width: known at the first push
     self.channels_out = None
-    self._on_device = device.gpu_available()
-    self._dev = self._host = None
-    self.rows_pushed = self.frames_emitted = 0
-    self.flushed = False
-    self._tensors = False
+
+  @staticmethod
+  def _settings(prep, cfg):
+    return dict((key, getattr(prep, key)) for key in FRONT_SHARED)
 
   # -- state -------------------------------------------------------------------------------------
   def _setup(self, c):
@@ -1051,24 +1178,16 @@ class OnlinePreprocessor(object):
       self._host = [_HostFrontSession(cfg, c, groups, k['mean'], k['std']) for k in self._cfgs]
       return
     h = device.default_handle()
-    torch = device._torch()
     stats = np.array([[k['mean'], k['std']] for k in self._cfgs], np.float64)
     if np.all(stats == stats[0]):
       stats = stats[:1]                          # (one pair every session reads)
     nbytes = device.frontend_state_bytes(c, self.sections)
     self._dev = dict(h=h, mean=h.to_device(stats[:, 0:1], np.float64).reshape(-1),
-                     std=h.to_device(stats[:, 1:2], np.float64).reshape(-1),
-                     state=torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device))
+                     std=h.to_device(stats[:, 1:2], np.float64).reshape(-1), state=self._zero_state(h, nbytes))
 
   def reset(self):
     """A fresh recording: zero state, no row pushed; the filters reset on the next push's first row."""
-    self.rows_pushed = self.frames_emitted = 0
-    self.flushed = False
-    if self._dev is not None:
-      self._dev['state'].zero_()
-    if self._host is not None:
-      for sess in self._host:
-        sess.reset()
+    _FrontEnd.reset(self)
 
   @property
   def state(self):
@@ -1087,73 +1206,30 @@ class OnlinePreprocessor(object):
     array or a device tensor; n may be 0.  Returns the frames this push emits, [S, m, cs] float32 (m may be 0): a
     device tensor for a device tensor -- what OnlineDecoder.push takes as eeg, unchanged -- else a host array.
     want64: (the float32 frames, the same frames before the cast, float64)."""
-    if self.flushed:
-      raise ValueError('The front end was flushed: reset() starts the next recording.')
+    self._refuse_flushed()
     return self._advance(raw, False, want64)
 
   def flush(self, want64=False):
     """The end of the recording: emits the frames resample_indices counts for the rows pushed that no push has
     emitted yet (when upsampling, from the last row), as the pushes returned theirs.  After it the front end
     refuses pushes until reset()."""
-    if self.flushed:
-      raise ValueError('The front end was flushed: reset() starts the next recording.')
-    out = self._advance(None, True, want64)
-    self.flushed = True
-    return out
+    return self._flush(want64)
 
-  def _advance(self, raw, flush, want64):
-    on_dev_in = self._tensors if raw is None else hasattr(raw, 'is_cuda')
-    self._tensors = on_dev_in                    # (a flush answers as the last push did)
-    if raw is not None:
-      if not on_dev_in:
-        raw = np.asarray(raw)
-        if raw.dtype not in (np.float32, np.float64):
-          raw = raw.astype(np.float64)
-      if len(raw.shape) == 2 and self.sessions == 1:
-        raw = raw[None]
-      if len(raw.shape) != 3 or int(raw.shape[0]) != self.sessions or (
-          self.channels is not None and int(raw.shape[2]) != self.channels):
-        raise ValueError('A push is raw [%d, n, %s] (or [n, %s] for one session), not %s.' %
-                         (self.sessions, self.channels or 'C', self.channels or 'C', tuple(raw.shape)))
-      if self.channels is None:
-        self._setup(int(raw.shape[2]))
-    n = 0 if raw is None else int(raw.shape[1])
-    if self.channels is None:                    # (a flush before any row)
-      return np.zeros((self.sessions, 0, 0), np.float32)
-    cfg = self._cfg
-    if not self._on_device:
-      if raw is None:
-        x = np.zeros((self.sessions, 0, self.channels), np.float64)
-      else:
-        x = raw.cpu().numpy() if hasattr(raw, 'cpu') else raw
-      outs = [sess.push(np.asarray(x[i], np.float64), self.rows_pushed, flush) for i, sess in enumerate(self._host)]
-      out64 = np.stack(outs)
-      self.rows_pushed += n
-      self.frames_emitted += out64.shape[1]
-      out32 = out64.astype(np.float32)
-      if on_dev_in:
-        out32, out64 = device._torch().from_numpy(out32), device._torch().from_numpy(out64)
-      return (out32, out64) if want64 else out32
-    d = self._dev
-    h = d['h']
-    x = None
-    if n > 0:
-      torch = device._torch()
-      if on_dev_in:
-        x = raw if raw.dtype in (torch.float32, torch.float64) else raw.to(torch.float32)
-        if x.stride(2) != 1 and self.channels > 1:
-          x = x.contiguous()
-      else:
-        x = torch.from_numpy(np.ascontiguousarray(raw)).to(h.device)
-    out = device.frontend_push(x, cfg['sos'], cfg['split'], cfg['zi'], cfg['fs_in'], cfg['fs_out'], self._groups,
-                               cfg['select'], d['mean'], d['std'], d['state'], self.rows_pushed, c=self.channels,
-                               flush=flush, want64=want64, handle=h)
-    self.rows_pushed += n
-    self.frames_emitted = out.plan.frames_after
-    out32, out64 = out.out32, out.out64
-    if not on_dev_in:
-      out32, out64 = out32.cpu().numpy(), out64.cpu().numpy() if want64 else None
-    return (out32, out64) if want64 else out32
+  def _host_push(self, x, flush):
+    if x is None:
+      x = self._no_rows(self.channels, np.float64)
+    return np.stack([sess.push(np.asarray(x[i], np.float64), self.rows_pushed, flush)
+                     for i, sess in enumerate(self._host)])
+
+  @staticmethod
+  def _to_device(raw, h):
+    return device._torch().from_numpy(np.ascontiguousarray(raw)).to(h.device)
+
+  def _device_push(self, x, flush, want64):
+    cfg, d = self._cfg, self._dev
+    return device.frontend_push(x, cfg['sos'], cfg['split'], cfg['zi'], cfg['fs_in'], cfg['fs_out'], self._groups,
+                                cfg['select'], d['mean'], d['std'], d['state'], self.rows_pushed, c=self.channels,
+                                flush=flush, want64=want64, handle=d['h'])
 
 
 # ------------------------------------------------------------------------------------------------ the audio front end
@@ -1256,7 +1332,7 @@ class _HostAudioSession(object):
       return np.sqrt(out) ** cfg['exponent'], win
 
 
-class OnlineAudioFeatures(object):
+class OnlineAudioFeatures(_FrontEnd):
   """The online audio front end: a bank of S sessions that take audio rows in pushes of any length and give the
   intensity envelopes OnlineDecoder.push takes as env1 / env2 -- one td_audio_online_push launch per push, the last
   K rows' squares on the device, and any cut of a recording gives the bytes of one push: the frames of
@@ -1271,35 +1347,25 @@ class OnlineAudioFeatures(object):
 
   Without a GPU the same object runs a NumPy float64 session of the same semantics."""
 
+  NAME, OBJECTS, ROWS, WIDTH = 'OnlineAudioFeatures', 'AudioFeatures', 'audio', 'c'
+  SHARE = 'The sessions of a bank share fs_in, fs_out, window and exponent: %s is %s and %s.'
+  FLUSHED = 'The audio front end was flushed: reset() starts the next recording.'
+  DTYPES = ('int16', 'float32', 'float64')
+  HOST_CAST, COLUMN, CAST_ERRSTATE = np.float32, True, dict(over='ignore')
+  _parameters = staticmethod(audio_parameters)
+
   def __init__(self, features, num_sessions=None):
-    if not isinstance(features, (list, tuple)):
-      features = [features] * (1 if num_sessions is None else int(num_sessions))
-    elif num_sessions is not None and int(num_sessions) != len(features):
-      raise ValueError('OnlineAudioFeatures: %d AudioFeatures for num_sessions=%d.' %
-                       (len(features), int(num_sessions)))
-    if not features:
-      raise ValueError('OnlineAudioFeatures needs at least one session.')
-    cfgs = [audio_parameters(f) for f in features]
-    for cfg in cfgs[1:]:
-      for key in AUDIO_SHARED:
-        if cfg[key] != cfgs[0][key]:
-          raise ValueError('The sessions of a bank share fs_in, fs_out, window and exponent: %s is %s and %s.' %
-                           (key, cfgs[0][key], cfg[key]))
-    self._cfg = cfgs[0]
-    self.sessions = len(features)
-    self.fs_in, self.fs_out = self._cfg['fs_in'], self._cfg['fs_out']
+    _FrontEnd.__init__(self, features, num_sessions)
     self.window, self.exponent = self._cfg['window'], self._cfg['exponent']
     self.tail_rows = audio_tail_rows(self.fs_in, self.fs_out, self.window)
     if self.tail_rows > device.AUDIO_ONLINE_MAX_TAIL:
       raise ValueError('OnlineAudioFeatures: %g -> %g Hz with window=%g carries %d rows (at most %d).' %
                        (self.fs_in, self.fs_out, self.window, self.tail_rows, device.AUDIO_ONLINE_MAX_TAIL))
-    self.channels = None                         # the row's width: known at the first push
-    self._on_device = device.gpu_available()
-    self._dev = self._host = None
     self._live = 0
-    self.rows_pushed = self.frames_emitted = 0
-    self.flushed = False
-    self._tensors = False
+
+  @staticmethod
+  def _settings(features, cfg):
+    return cfg
 
   def _setup(self, c):
     if not 1 <= c <= device.AUDIO_ONLINE_MAX_CHANNELS:
@@ -1310,20 +1376,12 @@ class OnlineAudioFeatures(object):
       self._host = [_HostAudioSession(self._cfg, c) for _ in range(self.sessions)]
       return
     h = device.default_handle()
-    nbytes = device.audio_online_state_bytes(c, self.tail_rows)
-    self._dev = dict(h=h, state=device._torch().zeros((self.sessions, nbytes), dtype=device._torch().uint8,
-                                                      device=h.device))
+    self._dev = dict(h=h, state=self._zero_state(h, device.audio_online_state_bytes(c, self.tail_rows)))
 
   def reset(self):
     """A fresh recording: zero state, no row pushed."""
-    self.rows_pushed = self.frames_emitted = 0
-    self.flushed = False
     self._live = 0
-    if self._dev is not None:
-      self._dev['state'].zero_()
-    if self._host is not None:
-      for sess in self._host:
-        sess.reset()
+    _FrontEnd.reset(self)
 
   @property
   def state(self):
@@ -1343,78 +1401,32 @@ class OnlineAudioFeatures(object):
     device tensor; n may be 0.  Returns the frames this push emits, [S, m, c] float32 (m may be 0): a device tensor
     for a device tensor, else a host array.  want64: (the float32 frames, the float64 frames they were rounded
     from -- the reference's dtype)."""
-    if self.flushed:
-      raise ValueError('The audio front end was flushed: reset() starts the next recording.')
+    self._refuse_flushed()
     return self._advance(audio, False, want64)
 
   def flush(self, want64=False):
     """The end of the recording: emits every frame of int(round(rows_pushed / fs_in * fs_out)) that no push has
     emitted yet, its window clamped at the last row, as compute_intensity(whole) does.  After it the front end
     refuses pushes until reset()."""
-    if self.flushed:
-      raise ValueError('The audio front end was flushed: reset() starts the next recording.')
-    out = self._advance(None, True, want64)
-    self.flushed = True
-    return out
+    return self._flush(want64)
 
-  def _advance(self, audio, flush, want64):
-    on_dev_in = self._tensors if audio is None else hasattr(audio, 'is_cuda')
-    self._tensors = on_dev_in                    # (a flush answers as the last push did)
-    if audio is not None:
-      if not on_dev_in:
-        audio = np.asarray(audio)
-        if audio.dtype not in (np.int16, np.float32, np.float64):
-          audio = audio.astype(np.float32)
-      if len(audio.shape) == 1 and self.sessions == 1:
-        audio = audio.reshape(-1, 1)
-      if len(audio.shape) == 2 and self.sessions == 1:
-        audio = audio[None]
-      if len(audio.shape) != 3 or int(audio.shape[0]) != self.sessions or (
-          self.channels is not None and int(audio.shape[2]) != self.channels):
-        raise ValueError('A push is audio [%d, n, %s] (or [n, %s] for one session), not %s.' %
-                         (self.sessions, self.channels or 'c', self.channels or 'c', tuple(audio.shape)))
-      if self.channels is None:
-        self._setup(int(audio.shape[2]))
-    n = 0 if audio is None else int(audio.shape[1])
-    if self.channels is None:                    # (a flush before any row)
-      empty = np.zeros((self.sessions, 0, 0), np.float32)
-      return (empty, empty.astype(np.float64)) if want64 else empty
-    cfg = self._cfg
-    if not self._on_device:
-      if audio is None:
-        x = np.zeros((self.sessions, 0, self.channels), np.float32)
-      else:
-        x = audio.cpu().numpy() if hasattr(audio, 'cpu') else audio
-      outs = [sess.push(x[i], self.rows_pushed, flush) for i, sess in enumerate(self._host)]
-      out64 = np.stack([o[0] for o in outs])
-      self.rows_pushed += n
-      self.frames_emitted += out64.shape[1]
-      with np.errstate(over='ignore'):
-        out32 = out64.astype(np.float32)
-      if on_dev_in:
-        out32, out64 = device._torch().from_numpy(out32), device._torch().from_numpy(out64)
-      return (out32, out64) if want64 else out32
-    d = self._dev
-    h = d['h']
-    x = None
-    if n > 0:
-      torch = device._torch()
-      if on_dev_in:
-        x = audio if audio.dtype in (torch.int16, torch.float32, torch.float64) else audio.to(torch.float32)
-        if x.stride(2) != 1 and self.channels > 1:
-          x = x.contiguous()
-      else:
-        x = torch.from_numpy(np.array(audio, order='C')).to(h.device)     # (a copy: the caller's may be read-only)
+  def _host_push(self, x, flush):
+    if x is None:
+      x = self._no_rows(self.channels)
+    return np.stack([sess.push(x[i], self.rows_pushed, flush)[0] for i, sess in enumerate(self._host)])
+
+  @staticmethod
+  def _to_device(audio, h):
+    # (a copy: the caller's may be read-only)
+    return device._torch().from_numpy(np.array(audio, order='C')).to(h.device)
+
+  def _device_push(self, x, flush, want64):
+    cfg, d = self._cfg, self._dev
     out = device.audio_online_push(x, cfg['fs_in'], cfg['fs_out'], cfg['window'], cfg['exponent'], d['state'],
                                    self._live, self.rows_pushed, c=self.channels, flush=flush, want64=want64,
-                                   handle=h)
+                                   handle=d['h'])
     self._live = out.live
-    self.rows_pushed += n
-    self.frames_emitted = out.plan.frames_after
-    out32, out64 = out.out32, out.out64
-    if not on_dev_in:
-      out32, out64 = out32.cpu().numpy(), out64.cpu().numpy() if want64 else None
-    return (out32, out64) if want64 else out32
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ joining the streams
@@ -1559,7 +1571,7 @@ class _HostRidgeFitSession(object):
     return np.stack([s[:self.k] for s in sols]), np.stack([s[self.k] for s in sols])
 
 
-class OnlineRidgeFit(object):
+class OnlineRidgeFit(_Bank):
   """The online chain's training stage: a bank of S sessions that take (eeg, target) rows in pushes of any length
   and keep the EXACT moments of the lagged ridge regression -- [x~ | 1]^T [x~ | 1] and [x~ | 1]^T y in float64, the
   lagged vector that of brain_data's context, the trailing 1 the reference's ones column -- in ONE
@@ -1583,6 +1595,7 @@ class OnlineRidgeFit(object):
   Refused by name: more than 128 channels, more than 64 lags, more than 2048 lagged inputs, outputs outside
   1 .. 8, a push of more than 1048576 rows, a forgetting factor outside (0, 1].  Without a GPU the same object
   runs a NumPy session of the same semantics, bit for bit (np.linalg.solve for the weights)."""
+  FLUSHED = 'The fit was flushed: reset() starts the next recording.'
 
   def __init__(self, channels, pre_context, post_context, outputs=1, num_sessions=1, forgetting=1.0):
     c, pre, post, d = int(channels), int(pre_context), int(post_context), int(outputs)
@@ -1591,17 +1604,14 @@ class OnlineRidgeFit(object):
     if int(num_sessions) < 1:
       raise ValueError('OnlineRidgeFit needs at least one session.')
     self.channels, self.pre, self.post, self.outputs = c, pre, post, d
-    self.sessions, self.forgetting = int(num_sessions), g
+    self.forgetting = g
     self.lags = pre + 1 + post
     self.inputs = self.lags * c                  # K
     self.delay = post
-    self._on_device = device.gpu_available()
-    self._dev = self._host = None
+    _Bank.__init__(self, int(num_sessions), device.gpu_available())
     if self._on_device:
       h = device.default_handle()
-      torch = device._torch()
-      nbytes = device.online_fit_state_bytes(c, pre, post, d)
-      self._dev = dict(h=h, state=torch.zeros((self.sessions, nbytes), dtype=torch.uint8, device=h.device))
+      self._dev = dict(h=h, state=self._zero_state(h, device.online_fit_state_bytes(c, pre, post, d)))
     else:
       self._host = [_HostRidgeFitSession(c, pre, post, d, g) for _ in range(self.sessions)]
     self.reset()
@@ -1610,12 +1620,7 @@ class OnlineRidgeFit(object):
     """A fresh recording and empty moments: zero state (a memset), no row pushed."""
     self.rows_pushed = self.frames = 0           # frames: the frames counted into the moments so far
     self._pushes = 0                             # pushes with rows: its parity is the live tail copy
-    self.flushed = False
-    if self._dev is not None:
-      self._dev['state'].zero_()
-    if self._host is not None:
-      for sess in self._host:
-        sess.reset()
+    _Bank.reset(self)
 
   # -- pushes ------------------------------------------------------------------------------------
   def _as_bank(self, eeg, target):
@@ -1649,8 +1654,7 @@ class OnlineRidgeFit(object):
   def push(self, eeg, target):
     """The next n rows of every session: eeg [n, c] / [S, n, c] and target [n] / [n, d] / [S, n, d], float32 device
     tensors (read where they are, no host copy) or arrays; n may be 0.  Returns the frames counted so far."""
-    if self.flushed:
-      raise ValueError('The fit was flushed: reset() starts the next recording.')
+    self._refuse_flushed()
     eeg, target = self._as_bank(eeg, target)
     return self._advance(eeg, target, False)
 
@@ -1658,11 +1662,8 @@ class OnlineRidgeFit(object):
     """The end of the recording: the last post_context frames are counted as if zero rows followed -- behind the
     recording's last rows, when they are given (one launch for both).  After it the fit refuses pushes until
     reset(); moments() and solve() stay."""
-    if self.flushed:
-      raise ValueError('The fit was flushed: reset() starts the next recording.')
-    if (eeg is None) != (target is None):
-      raise ValueError('OnlineRidgeFit.flush takes the last rows as eeg AND target, or neither.')
-    if eeg is not None:
+    self._refuse_flushed()
+    if self._last_rows('OnlineRidgeFit.flush takes the last rows as eeg AND target, or neither.', eeg, target):
       eeg, target = self._as_bank(eeg, target)
     frames = self._advance(eeg, target, True)
     self.flushed = True
@@ -1674,8 +1675,7 @@ class OnlineRidgeFit(object):
     counted = after if flush else max(0, after - self.post)
     if not self._on_device:
       if eeg is None:
-        eeg = np.zeros((self.sessions, 0, self.channels), np.float32)
-        target = np.zeros((self.sessions, 0, self.outputs), np.float32)
+        eeg, target = self._no_rows(self.channels), self._no_rows(self.outputs)
       for i, sess in enumerate(self._host):
         sess.push(eeg[i], target[i], self.rows_pushed, flush)
     else:
@@ -1870,7 +1870,7 @@ class _HostCalibSession(object):
     return emitted
 
 
-class OnlineCalibration(object):
+class OnlineCalibration(_Bank):
   """The online chain's last training stage: the correlation statistics, the scaled LDA and d' that
   infer_decoder.Decoder.train(data0, data1, window_size=W) would take from a labelled stretch -- data0 the
   (unattended envelope, prediction) frames, data1 the (attended envelope, prediction) frames -- for rows that arrive
@@ -1892,6 +1892,7 @@ class OnlineCalibration(object):
   any time and leaves the state alone.  Any cut of a recording gives the same state bytes (sums()).
 
   Without a GPU the same object runs a NumPy session of the same semantics (float64 prediction)."""
+  FLUSHED = 'The calibration was flushed: reset() starts the next stretch.'
 
   def __init__(self, decoder, window_size=100):
     if not isinstance(decoder, OnlineDecoder):
@@ -1903,16 +1904,14 @@ class OnlineCalibration(object):
     if width > MAX_WINDOW:
       raise ValueError('OnlineCalibration takes windows of 1 to %d frames, not %d.' % (MAX_WINDOW, width))
     self.decoder = decoder
-    self.sessions, self.channels, self.pre, self.post = decoder.sessions, decoder.channels, decoder.pre, decoder.post
+    _Bank.__init__(self, decoder.sessions, decoder._on_device)
+    self.channels, self.pre, self.post = decoder.channels, decoder.pre, decoder.post
     self.window_size = width
     self.delay = self.post
-    self._on_device = decoder._on_device
-    self._dev = self._host = None
     if self._on_device:
       h = decoder._dev['h']
-      nbytes = device.online_calib_state_bytes(self.channels, self.pre, self.post)
-      self._dev = dict(h=h, state=device._torch().zeros((self.sessions, nbytes), dtype=device._torch().uint8,
-                                                        device=h.device))
+      self._dev = dict(h=h, state=self._zero_state(h, device.online_calib_state_bytes(self.channels, self.pre,
+                                                                                       self.post)))
     else:
       self._host = [_HostCalibSession(self.channels, self.pre, self.post, width) for _ in range(self.sessions)]
     self.reset()
@@ -1920,12 +1919,7 @@ class OnlineCalibration(object):
   def reset(self):
     """A fresh calibration stretch: zero state (a memset), no row pushed."""
     self.rows_pushed = 0
-    self.flushed = False
-    if self._dev is not None:
-      self._dev['state'].zero_()
-    if self._host is not None:
-      for sess in self._host:
-        sess.reset()
+    _Bank.reset(self)
 
   @property
   def frames_emitted(self):
@@ -1942,8 +1936,7 @@ class OnlineCalibration(object):
     """The next n rows of every session: eeg [n, C] / [S, n, C], the attended and the unattended envelope [n] /
     [S, n], float32 device tensors (read where they are) or arrays; n may be 0.  Returns the frames counted so
     far."""
-    if self.flushed:
-      raise ValueError('The calibration was flushed: reset() starts the next stretch.')
+    self._refuse_flushed()
     eeg, env = self.decoder._as_bank(eeg, attended, unattended)
     if int(eeg.shape[1]) > MAX_FIT_PUSH:
       raise ValueError('OnlineCalibration takes at most %d rows in one push, not %d.' % (MAX_FIT_PUSH, eeg.shape[1]))
@@ -1953,13 +1946,10 @@ class OnlineCalibration(object):
     """The end of the stretch: the last post_context frames are counted as if zero rows followed -- behind the
     stretch's last rows, when they are given (one launch for both).  After it the calibration refuses pushes until
     reset(); sums() and finish() stay."""
-    if self.flushed:
-      raise ValueError('The calibration was flushed: reset() starts the next stretch.')
-    given = [a is not None for a in (eeg, attended, unattended)]
-    if any(given) and not all(given):
-      raise ValueError('OnlineCalibration.flush takes the last rows as eeg AND both envelopes, or nothing.')
+    self._refuse_flushed()
     env = None
-    if eeg is not None:
+    if self._last_rows('OnlineCalibration.flush takes the last rows as eeg AND both envelopes, or nothing.', eeg,
+                       attended, unattended):
       eeg, env = self.decoder._as_bank(eeg, attended, unattended)
       if int(eeg.shape[1]) > MAX_FIT_PUSH:
         raise ValueError('OnlineCalibration takes at most %d rows in one push, not %d.' % (MAX_FIT_PUSH, eeg.shape[1]))
@@ -1969,8 +1959,7 @@ class OnlineCalibration(object):
     n = 0 if eeg is None else int(eeg.shape[1])
     if not self._on_device:
       if eeg is None:
-        eeg = np.zeros((self.sessions, 0, self.channels), np.float32)
-        env = np.zeros((self.sessions, 0, 2), np.float32)
+        eeg, env = self._no_rows(self.channels), self._no_rows(2)
       for i, sess in enumerate(self._host):
         p = self.decoder._params[i]
         sess.push(np.asarray(eeg[i], np.float64), np.asarray(env[i], np.float64), p['w'], p['b'], self.rows_pushed,
@@ -1981,8 +1970,7 @@ class OnlineCalibration(object):
       if n == 0:
         eeg = env = None
       elif not hasattr(eeg, 'is_cuda'):
-        eeg, env = h.to_device(eeg.reshape(-1, self.channels)).reshape(eeg.shape), \
-            h.to_device(env.reshape(-1, 2)).reshape(env.shape)
+        eeg, env = self._upload(h, eeg), self._upload(h, env)
       device.online_calib_push(eeg, env, bank['w'], bank['b'], d['state'], self.rows_pushed, self.pre, self.post,
                                self.window_size, c=self.channels, flush=flush, handle=h)
     self.rows_pushed += n
