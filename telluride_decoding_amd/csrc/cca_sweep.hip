@@ -18,9 +18,8 @@
 // gets status 1: the caller refits it the long way.
 #include <algorithm>
 
+#include "stats_common.h"
 #include "td_common.h"
-
-int td_stats_dims(const td_stats* s, int* k1, int* k2, int64_t* frames);
 
 namespace {
 

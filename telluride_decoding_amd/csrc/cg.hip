@@ -454,7 +454,7 @@ int launch_cg(td_handle* h, const CgParams& p, int wgs, size_t lds_bytes, int cu
 // The resident kernel above needs the LDS of the whole chip (33 MB at C2), so the solves of a pipelined
 // fit -- which run on a 64-CU partition beside the next accumulate -- stayed with the ~100-launch
 // Cholesky chain.  But the moment matrix of files that were summed whole is block-Toeplitz up to their
-// HEAD windows (stats.hip):
+// HEAD windows (stats_common.h):
 //   M[(a,i),(b,j)] = G[b - a][i][j] - sum_files sum_{s < a} x_f[s][i] x~_f[s + b - a][j]        (pre = 0)
 // with G[e] = fxx[e] (e >= 0), fxx[-e]^T (e < 0), so a product M p needs 0.5 MB of statistics instead of
 // the 33 MB matrix:

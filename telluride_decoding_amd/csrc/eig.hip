@@ -30,12 +30,9 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "stats_common.h"
 #include "td_common.h"
 #include "td_tile64.h"
-
-int td_stats_dims(const td_stats* s, int* k1, int* k2, int64_t* frames);
-int td_stats_cca_direct(td_handle* h, td_stats* s, const double** xx, const double** yy, const double** xy,
-                        const double** sum1, const double** sum2, int* ok);
 
 namespace {
 

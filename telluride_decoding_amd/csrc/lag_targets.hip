@@ -16,7 +16,7 @@ namespace {
 // E registers whose slot indices are compile-time constants in the unrolled body.  Rows of Y
 // outside [us, ue) are zero, which handles every strip and file edge.  The kernel also
 // returns the plain column sums of X over [us, ue) and of Y: the all-ones row of [y | 1]^T x~
-// (the bias moments) follows from those and the per-file boundary windows (stats.hip) instead
+// (the bias moments) follows from those and the per-file boundary windows (stats_accumulate.hip) instead
 // of a second set of FMAs.  f32 FMA chains of at most kWaveStrip rows, summed in float64 by
 // the reduction kernels.
 // (The first version was an LDS-tiled workgroup kernel whose FMAs each read an operand from

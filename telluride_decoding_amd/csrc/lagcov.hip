@@ -7,7 +7,7 @@
 // per-minibatch `sum_xtx += x.T @ x` (brain_model.py:437, cca.py:325-327): the
 // C x (C*L) lagged cross-covariance carries the same information as the
 // (C*L)^2 matrix (block-Toeplitz up to file edges, fixed up exactly in
-// stats.hip) at 1/L of the flops, and the lag matrix only ever exists as
+// stats_moments.hip) at 1/L of the flops, and the lag matrix only ever exists as
 // shifted views of an LDS tile.
 //
 // MI355X mapping (gfx950, wave64):
@@ -1920,7 +1920,7 @@ __global__ __launch_bounds__(64 * Q) void lagcov_reduce_kernel(
 #pragma unroll
     for (int k = 0; k < Q; ++k) t += part[k][ol];
     // float16 kernel: the sums carry the two channels' power-of-two scales (as in the finalize
-    // launch, stats.hip)
+    // launch, stats_accumulate.hip)
     if (scale_a) {
       t = ldexp(t, -(td_f16_scale_exp(scale_a[i]) + td_f16_scale_exp(scale_b[j])));
       if (td_chan_not_finite(scale_a[i]) || td_chan_not_finite(scale_b[j])) t = __builtin_nan("");

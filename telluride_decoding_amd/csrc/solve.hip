@@ -26,10 +26,9 @@
 // on LDS-fed VALU FMAs: 56 + 24 + 22 us per block step, 3.3 ms at n = 2049.)
 #include <cstdlib>
 
+#include "stats_common.h"
 #include "td_common.h"
 #include "td_tile64.h"
-
-int td_stats_layout(const td_stats* s, int* k1, int* d, int64_t* frames);
 
 namespace {
 

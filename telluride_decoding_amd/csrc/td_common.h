@@ -243,7 +243,7 @@ __device__ __forceinline__ unsigned td_pack_f16(float a, float b) {    // low ha
 // (x0, x1), already scaled -> packed pairs of the two pieces.  Clamped to the finite float16
 // range first (one v_med3 each): a staged row that is never multiplied must still not become an
 // infinity (0 x inf).  A NaN does not survive the clamp; the channel's maximum remembers it and
-// the float64 reduction puts it back (fin_reduce, stats.hip).
+// the float64 reduction puts it back (fin_reduce, stats_accumulate.hip).
 __device__ __forceinline__ void td_split2_f16(float x0, float x1, unsigned& h, unsigned& l) {
   x0 = __builtin_amdgcn_fmed3f(x0, -65504.f, 65504.f);
   x1 = __builtin_amdgcn_fmed3f(x1, -65504.f, 65504.f);
@@ -422,7 +422,7 @@ __host__ __device__ __forceinline__ long long td_virt_offset(const VirtMap* vm, 
 }
 
 // One float64 reduction of partial slabs, run by a reduction launch of its own (td_lagcov) or
-// as one job of the fused finalize kernel of an accumulate call (stats.hip):
+// as one job of the fused finalize kernel of an accumulate call (stats_accumulate.hip):
 //   g[(e * ca_dst + i) * ldg + j] (+)= sum_w partial[w][e][i][j]
 // summed in a fixed order (q slab phases per output, combined in order): bitwise reproducible.
 struct LagReduceJob {
@@ -560,7 +560,7 @@ int td_chan_tab_scratch(td_handle* h, unsigned** tab);
 int td_stats_settle(td_handle* h, td_stats* s);
 int td_stats_moments_ld(td_handle* h, td_stats* s, double* xtx_dev, int64_t ld_xtx, double* xty_dev,
                         double* x2tx2_dev, double* xtx2_dev, double* sum_x2_dev);
-// (stats.hip) the dense moments of the folds of a leave-one-out sweep from the total's and a few signed terms each
+// (stats_moments.hip) the dense moments of the folds of a leave-one-out sweep from the total's and a few signed terms each
 int td_stats_loso_moments(td_handle* h, td_stats* total, td_stats* const* terms, const int* term_begin,
                           const double* signs, int n_folds, const double* mt, int64_t ld, double* out,
                           double* xty_out);

@@ -7,7 +7,7 @@ module, not a conftest.
 The reference isolates the solver: A = xtx / frames + lambda I WITH the bias row (brain_model.py:447-477), rhs =
 xty / frames, both from the device's own float64 moments (LagStats.moments()), solved by np.linalg.solve.  For the
 resident kernel that matrix is literally its input; for the compact kernel it comes from the expansion kernels of
-stats.hip, code independent of the kernel's own block-Toeplitz-plus-head-window product.
+stats_moments.hip, code independent of the kernel's own block-Toeplitz-plus-head-window product.
 
 The bound, elementwise for w and for b:   |gpu - ref| <= 2^-24 |ref| + E,
   E = 4 cond(A) sqrt(accept) 1e-12 ||[w_ref; b_ref]||_2
