@@ -125,6 +125,10 @@ class LagStats(object):
         except np.linalg.LinAlgError:
           status[f, li] = 1
           continue
+        # (the device's pivot rule: LAPACK accepts a pivot of rounding noise that happens to come out positive)
+        if not np.min(np.diag(chol)) ** 2 > 64.0 * k1 * 2.0 ** -52 * np.max(np.abs(np.diag(cxx))):
+          status[f, li] = 1
+          continue
         z = np.linalg.solve(chol.T, np.linalg.solve(chol, cxy))
         vals, vecs = np.linalg.eigh(cyy)
         if np.any(vals <= eps_eig):
