@@ -1132,6 +1132,87 @@ int td_fit_online_solve(td_handle* h, int num_sessions, const void* state_dev, i
                         int pre, int post, int d, int64_t frames_emitted, const double* lambdas_host, int n_lambda,
                         float* w_dev, float* b_dev);
 
+/* ------------------------------------------------------------------ online CCA fit
+ * The training stage of the online CCA decoder (td_cca_online_push): the exact float64 moments of BOTH lagged views
+ * for rows that arrive in pushes of any length -- ONE launch per push for `num_sessions` sessions, one state block
+ * each on the device -- and rotations from them on demand, through the dense stage td_cca_solve runs.  However a
+ * recording is cut into pushes, the state is that of one push of the whole recording, bit for bit.  (The prefix is
+ * td_ccafit_online_: td_cca_online_* is the decoder's closed set.)
+ *
+ * Views.  View 1 is the EEG: c1 channels, context (pre1, post1), k1 = c1 (pre1 + 1 + post1).  View 2 is the attended
+ * speaker's feature block: c2 columns, context (pre2, post2), k2 = c2 (pre2 + 1 + post2).  The joint vector of frame
+ * t is u = [x~_t | y~_t | 1], n = k1 + k2 + 1; each half is the lagged row t of its view, lag-major, channel-minor,
+ * v[l c + ch] = x[t + l - pre][ch], zero outside the recording.  Frames run post = max(post1, post2) rows behind the
+ * input, as td_cca_online_push has it: emitted = max(0, pushed - post); a push that carries flush emits the rest, as
+ * if `post` zero rows followed in both views.
+ *
+ * The sum.  For every newly emitted frame, in frame order, with the forgetting factor g = forget:
+ *   M = M g + u u^T     n x n float64
+ * The inputs are float32, so a product is exact.  g == 1: one rounding per frame and element (the fused multiply-add
+ * of the widened values).  g < 1: two, round(round(acc g) + p).  The order is a function of the frame index alone, so
+ * NumPy's M * g + np.outer(u, u) in frame order gives the same bits.  M[n - 1][n - 1] is the frame count (g == 1) or
+ * the effective count (g < 1).
+ *
+ * State (td_ccafit_online_state_bytes, rounded up to 8; all zeros = a fresh session): M as a full square of float64
+ * of which the launch computes and stores the 64 x 64 tiles (ti, tj) with tj >= ti only (a diagonal tile whole) -- the
+ * lower tiles stay zero, td_ccafit_online_moments mirrors --, then TWO tail copies of {EEG [pre1 + post][c1],
+ * features [pre2 + post][c2]} float32, slot j of a view's tail holding row pushed - (pre_v + post) + j, zero before
+ * row 0.  A launch reads copy (pushes_before & 1) and one workgroup per session writes every slot of the other one;
+ * pushes_before counts the pushes with n > 0 (the HOST counts frames and pushes; a push without rows writes no tail).
+ *
+ * td_ccafit_online_push: the sessions' next n rows.
+ *   eeg_dev   [S][n][c1] float32, row stride ld_eeg, session stride eeg_session_stride (elements)
+ *   feat_dev  [S][n][c2] float32, row stride ld_feat, session stride feat_session_stride (elements)
+ *   n >= 0    (n == 0 with no frame to emit: nothing is queued); a push that emits nothing still rolls the tails
+ *   frames_before   rows pushed so far;  flush != 0: the recording ends behind this push
+ *   state_dev, state_session_stride (BYTES, a multiple of 8, >= td_ccafit_online_state_bytes)
+ * grid: sessions x (upper-triangular tiles of M + the tail workgroup), 256 threads, a 4 x 4 block of float64
+ * accumulators per thread.  No workgroup reads what another writes, no atomics, vector stores only: two runs give the
+ * same bits.  With td_profile_enable the launch is bracketed as td_online_push's is.
+ *
+ * td_ccafit_online_moments: one launch fills xtx_dev [S][k1 + 1][k1 + 1] (the ones row and column last, the layout of
+ * td_stats_moments), x2tx2_dev [S][k2][k2], xtx2_dev [S][k1][k2] and sum2_dev [S][k2], float64, dense and mirrored
+ * (any may be NULL, not all).
+ *
+ * td_ccafit_online_solve: the reference's CCA model (cca.py:337-343) of one minibatch that holds all counted frames,
+ * for every (session, lambda): means = sums / count, denom = count - 1, cov = S / denom - mean^T mean, + lambda I on
+ * both auto-covariances, eps_eig filtering, whitening, SVD, rotations -- td_cca_solve's dense stage, called once per
+ * (session, lambda) on the moments one launch expands into the handle's workspace; count = M[n - 1][n - 1].
+ *   rot_x_dev [S][n_lambda][k1][dim], rot_y_dev [S][n_lambda][k2][dim], mean_x_dev [S][k1], mean_y_dev [S][k2],
+ *   e_dev [S][n_lambda][dim] float32; corr_dev [S][n_lambda][3][dim] float64; info_host [S][n_lambda][4] (may be
+ *   NULL) as td_cca_solve's.
+ * corr is the fitted stretch's statistics in closed form from the same moments, for the float32 model returned: with
+ * m = sums / count and C = S / count - m m^T,  mean_a[d] = (m_x - mean_x) . rot_x[:, d], mean_b likewise,
+ * power[d] = sqrt((rot_x[:, d]^T C_xx rot_x[:, d]) (rot_y[:, d]^T C_yy rot_y[:, d])): one more launch per pair.
+ * frames_emitted: the host's count of emitted frames.  Synchronous (per pair, as td_cca_solve).  TD_ERR_STATE: fewer
+ * than 2 frames counted, or an effective count <= 1 (never a division by zero).
+ *
+ * TD_ERR_INVALID, before anything is queued and with the state untouched: a NULL required pointer, num_sessions
+ * outside 1..65535, c1 outside 1..TD_ONLINE_CCAFIT_MAX_CHANNELS, c2 outside 1..TD_ONLINE_CCAFIT_MAX_FEATURES, a
+ * context < 0, more than TD_ONLINE_CCAFIT_MAX_LAGS lags in a view, k1 + k2 above TD_ONLINE_CCAFIT_MAX_K, n outside
+ * 0..TD_ONLINE_MAX_PUSH, forget outside (0, 1], frames_before or pushes_before < 0, a row or session stride below a
+ * row, a state stride below the state block or not a multiple of 8, n_lambda < 1, a lambda < 0 or not finite, dim
+ * outside 1..min(TD_ONLINE_CCAFIT_MAX_DIMS, k1, k2). */
+#define TD_ONLINE_CCAFIT_MAX_CHANNELS 128
+#define TD_ONLINE_CCAFIT_MAX_FEATURES 32
+#define TD_ONLINE_CCAFIT_MAX_LAGS 64
+#define TD_ONLINE_CCAFIT_MAX_K 2048
+#define TD_ONLINE_CCAFIT_MAX_DIMS 16
+int td_ccafit_online_state_bytes(int c1, int pre1, int post1, int c2, int pre2, int post2, int64_t* bytes);
+int td_ccafit_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t ld_eeg,
+                          int64_t eeg_session_stride, const float* feat_dev, int64_t ld_feat,
+                          int64_t feat_session_stride, int64_t n, int c1, int pre1, int post1, int c2, int pre2,
+                          int post2, int64_t frames_before, int64_t pushes_before, int flush, double forget,
+                          void* state_dev, int64_t state_session_stride);
+int td_ccafit_online_moments(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,
+                             int c1, int pre1, int post1, int c2, int pre2, int post2, double* xtx_dev,
+                             double* x2tx2_dev, double* xtx2_dev, double* sum2_dev);
+int td_ccafit_online_solve(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,
+                           int c1, int pre1, int post1, int c2, int pre2, int post2, int64_t frames_emitted,
+                           const double* lambdas_host, int n_lambda, int dim, double eps_eig, float* rot_x_dev,
+                           float* rot_y_dev, float* mean_x_dev, float* mean_y_dev, float* e_dev, double* corr_dev,
+                           int* info_host);
+
 /* ------------------------------------------------------------------ online calibration
  * The stage behind the online ridge fit: what infer_decoder.Decoder.train(data0, data1, window_size = W) takes from
  * a labelled stretch -- the correlation statistics {mean_truth, mean_pred, power}, the scaled LDA between the window

@@ -199,6 +199,16 @@ SIGNATURES = {
     'td_fit_online_moments': [_vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp],
     # h, sessions | state, stride | c, pre, post, d | frames_emitted | lambdas, n_lambda | w, b
     'td_fit_online_solve': [_vp, _i, _vp, _i64, _i, _i, _i, _i, _i64, _pd, _i, _vp, _vp],
+    'td_ccafit_online_state_bytes': _VIEW + _VIEW + [_pi64],
+    # h, sessions | eeg, ld, stride | feat, ld, stride | n | c1, pre1, post1 | c2, pre2, post2 | frames_before,
+    # pushes_before, flush | forget | state, stride
+    'td_ccafit_online_push': [_vp, _i] + [_vp, _i64, _i64] * 2 + [_i64] + _VIEW + _VIEW + [_i64, _i64, _i] + [_d] +
+                             [_vp, _i64],
+    'td_ccafit_online_moments': [_vp, _i, _vp, _i64] + _VIEW + _VIEW + [_vp, _vp, _vp, _vp],
+    # h, sessions | state, stride | the two views | frames_emitted | lambdas, n_lambda | dim, eps_eig | rot_x, rot_y,
+    # mean_x, mean_y, e, corr | info
+    'td_ccafit_online_solve': [_vp, _i, _vp, _i64] + _VIEW + _VIEW + [_i64, _pd, _i] + [_i, _d] + [_vp] * 6 +
+                              [_c.POINTER(_i)],
     'td_calib_online_state_bytes': [_i, _i, _i, _pi64],
     # h, sessions | eeg, ld, stride | env, ld, stride | w, stride | b, stride | n, frames_before | c, pre, post, width,
     # flush | state, stride

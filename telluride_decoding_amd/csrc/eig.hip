@@ -1305,6 +1305,46 @@ struct Carver {
 
 }  // namespace
 
+// ---- the CCA dense stage's internal interface (td_common.h)
+bool td_cca_one_launch(const td_handle* h, int k1, int k2) {
+  return k1 <= NB && k2 <= 16 && k2 <= k1 && h->cca_whitening != 1 && h->cca_fused;
+}
+
+int td_cca_workspace(td_handle* h, int k1, int k2, int dim, td_cca_ws* wp) {
+  td_cca_ws& w = *wp;
+  const int k = std::min(k1, k2), len = std::max(k1, k2);
+  const size_t n1 = (size_t)k1 + 1;
+  auto carve = [&](void* base) {
+    Carver cv(base);
+    w.xtx = cv.take<double>(n1 * n1);
+    w.x2tx2 = cv.take<double>((size_t)k2 * k2);
+    w.xtx2 = cv.take<double>((size_t)k1 * k2);
+    w.sum2 = cv.take<double>(k2);
+    w.cxx = cv.take<double>((size_t)k1 * k1);
+    w.cyy = cv.take<double>((size_t)k2 * k2);
+    w.cxy = cv.take<double>((size_t)k1 * k2);
+    w.vals1 = cv.take<double>(k1);
+    w.vecs1 = cv.take<double>((size_t)k1 * k1);
+    w.vals2 = cv.take<double>(k2);
+    w.vecs2 = cv.take<double>((size_t)k2 * k2);
+    w.m1 = cv.take<double>((size_t)k1 * k2);
+    w.g = cv.take<double>((size_t)k1 * k2);
+    w.sig = cv.take<double>(dim);
+    w.gn = cv.take<double>((size_t)dim * len);
+    w.vn = cv.take<double>((size_t)dim * k);
+    w.rt = cv.take<double>((size_t)dim * std::max(k1, k2));
+    w.eig = cv.take<char>(eig_ws_bytes(std::max(k1, k2)));
+    w.svd = cv.take<char>(svd_ws_bytes(k));
+    w.chol = cv.take<char>(td_chol_ws_bytes(k1));
+    w.chol2 = cv.take<char>(td_chol_ws_bytes(k2 <= 64 ? k2 : 1));
+    return (size_t)(cv.p - reinterpret_cast<char*>(base));
+  };
+  void* base = nullptr;
+  TD_TRY(td_workspace(h, carve(nullptr), &base));
+  carve(base);
+  return TD_OK;
+}
+
 extern "C" {
 
 int td_sym_eigh(td_handle* h, const double* a_dev, int n, double* vals_dev, double* vecs_dev,
@@ -1362,58 +1402,38 @@ int td_cca_solve(td_handle* h, td_stats* s, double denom, double regularization,
   TD_REQUIRE(h, denom != 0.0, "td_cca_solve: zero covariance denominator");
   TD_REQUIRE(h, dim > 0 && dim <= std::min(k1, k2), "td_cca_solve: dim must be in [1, %d], not %d",
              std::min(k1, k2), dim);
-  const bool cols = k2 <= k1;                 // side whose vectors the SVD orthogonalises
-  const int k = cols ? k2 : k1, len = cols ? k1 : k2;
   const size_t n1 = (size_t)k1 + 1;
-  struct Ws {
-    double *xtx, *x2tx2, *xtx2, *sum2, *cxx, *cyy, *cxy, *vals1, *vecs1, *vals2, *vecs2, *m1, *g,
-        *sig, *gn, *vn, *rt;
-    void *eig, *svd, *chol, *chol2;
-  } w;
-  auto carve = [&](void* base) {
-    Carver cv(base);
-    w.xtx = cv.take<double>(n1 * n1);
-    w.x2tx2 = cv.take<double>((size_t)k2 * k2);
-    w.xtx2 = cv.take<double>((size_t)k1 * k2);
-    w.sum2 = cv.take<double>(k2);
-    w.cxx = cv.take<double>((size_t)k1 * k1);
-    w.cyy = cv.take<double>((size_t)k2 * k2);
-    w.cxy = cv.take<double>((size_t)k1 * k2);
-    w.vals1 = cv.take<double>(k1);
-    w.vecs1 = cv.take<double>((size_t)k1 * k1);
-    w.vals2 = cv.take<double>(k2);
-    w.vecs2 = cv.take<double>((size_t)k2 * k2);
-    w.m1 = cv.take<double>((size_t)k1 * k2);
-    w.g = cv.take<double>((size_t)k1 * k2);
-    w.sig = cv.take<double>(dim);
-    w.gn = cv.take<double>((size_t)dim * len);
-    w.vn = cv.take<double>((size_t)dim * k);
-    w.rt = cv.take<double>((size_t)dim * std::max(k1, k2));
-    w.eig = cv.take<char>(eig_ws_bytes(std::max(k1, k2)));
-    w.svd = cv.take<char>(svd_ws_bytes(k));
-    w.chol = cv.take<char>(td_chol_ws_bytes(k1));
-    w.chol2 = cv.take<char>(td_chol_ws_bytes(k2 <= 64 ? k2 : 1));
-    return (size_t)(cv.p - reinterpret_cast<char*>(base));
-  };
-  void* base = nullptr;
-  TD_TRY(td_workspace(h, carve(nullptr), &base));
-  carve(base);
-  const double inv_d = 1.0 / denom, inv_f = 1.0 / (double)frames;
-  // (td_set_option(h, "cca_whitening", 1): always the reference's eigen route)
-  const bool force_eig = h->cca_whitening == 1;
-  const bool psd_proof = regularization > 2.0 * eps_eig && denom <= (double)frames;   // (see below)
-  const bool one_launch = k1 <= NB && k2 <= 16 && cols && !force_eig && h->cca_fused;
+  td_cca_ws w;
+  TD_TRY(td_cca_workspace(h, k1, k2, dim, &w));
   // the dense moments: where the statistics keep them (no context: td_stats_cca_direct) or expanded
   const double *m_xx = nullptr, *m_yy = nullptr, *m_xy = nullptr, *m_s1 = nullptr, *m_s2 = nullptr;
   int direct = 0, ld_xx = (int)n1;
-  if (one_launch) TD_TRY(td_stats_cca_direct(h, s, &m_xx, &m_yy, &m_xy, &m_s1, &m_s2, &direct));
+  if (td_cca_one_launch(h, k1, k2)) TD_TRY(td_stats_cca_direct(h, s, &m_xx, &m_yy, &m_xy, &m_s1, &m_s2, &direct));
   if (direct) ld_xx = k1;
-  bool have_moments = false;
   if (!direct) {
     TD_TRY(td_stats_moments(h, s, w.xtx, nullptr, w.x2tx2, w.xtx2, w.sum2));
-    have_moments = true;
     m_xx = w.xtx; m_yy = w.x2tx2; m_xy = w.xtx2; m_s1 = w.xtx + (size_t)k1 * n1; m_s2 = w.sum2;
   }
+  return td_cca_dense(h, k1, k2, (double)frames, m_xx, ld_xx, m_yy, m_xy, m_s1, m_s2, direct ? s : nullptr, denom,
+                      regularization, eps_eig, dim, rot_x_dev, rot_y_dev, mean_x_dev, mean_y_dev, e_dev, info_host);
+}
+
+}  // extern "C"
+
+int td_cca_dense(td_handle* h, int k1, int k2, double count, const double* m_xx, int ld_xx, const double* m_yy,
+                 const double* m_xy, const double* m_s1, const double* m_s2, td_stats* expand_from, double denom,
+                 double regularization, double eps_eig, int dim, float* rot_x_dev, float* rot_y_dev,
+                 float* mean_x_dev, float* mean_y_dev, float* e_dev, int* info_host) {
+  const bool cols = k2 <= k1;                 // side whose vectors the SVD orthogonalises
+  const int k = cols ? k2 : k1, len = cols ? k1 : k2;
+  const size_t n1 = (size_t)k1 + 1;
+  td_cca_ws w;
+  TD_TRY(td_cca_workspace(h, k1, k2, dim, &w));
+  const double inv_d = 1.0 / denom, inv_f = 1.0 / count;
+  // (td_set_option(h, "cca_whitening", 1): always the reference's eigen route)
+  const bool force_eig = h->cca_whitening == 1;
+  const bool psd_proof = regularization > 2.0 * eps_eig && denom <= count;   // (see below)
+  const bool one_launch = td_cca_one_launch(h, k1, k2);
   if (one_launch) {
     // the whole dense stage in one launch (cca_small_kernel); status 1 = no Cholesky factor: the chain decides
     if (!h->lds_opt_cca) {
@@ -1440,7 +1460,7 @@ int td_cca_solve(td_handle* h, td_stats* s, double denom, double regularization,
       return TD_OK;
     }
   }
-  if (!have_moments) TD_TRY(td_stats_moments(h, s, w.xtx, nullptr, w.x2tx2, w.xtx2, w.sum2));
+  if (expand_from) TD_TRY(td_stats_moments(h, expand_from, w.xtx, nullptr, w.x2tx2, w.xtx2, w.sum2));
   const double* sum1 = w.xtx + (size_t)k1 * n1;        // the ones row of sum_xtx = column sums
   hipLaunchKernelGGL(cov_kernel, dim3(grid_for((long long)k1 * k1)), dim3(256), 0, h->stream, w.xtx,
                      (int)n1, k1, k1, sum1, sum1, inv_d, inv_f, regularization, w.cxx);
@@ -1562,5 +1582,3 @@ int td_cca_solve(td_handle* h, td_stats* s, double denom, double regularization,
   }
   return TD_OK;
 }
-
-}  // extern "C"

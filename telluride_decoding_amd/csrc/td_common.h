@@ -615,3 +615,24 @@ int td_chol_batch_forward(td_handle* h, double* a_dev, double* rt_dev, double* l
                           int n_real, int nrhs, int batch, int rt_rows);
 int td_chol_batch_backward(td_handle* h, double* a_dev, double* rt_dev, double* sol_dev, double* linv_dev, int np,
                            int nrhs, int batch, int rt_rows);
+
+// The CCA dense stage behind its moments (eig.hip), shared by td_cca_solve and td_ccafit_online_solve.
+// td_cca_workspace carves the handle's solver workspace for a (k1, k2, dim) problem: the same pointers for the same
+// shape, call after call.  xtx [(k1 + 1)^2] (ones row and column last), x2tx2 [k2^2], xtx2 [k1 k2] and sum2 [k2] are
+// where the expanded moments go; the rest is the dense stage's own.
+struct td_cca_ws {
+  double *xtx, *x2tx2, *xtx2, *sum2, *cxx, *cyy, *cxy, *vals1, *vecs1, *vals2, *vecs2, *m1, *g, *sig, *gn, *vn, *rt;
+  void *eig, *svd, *chol, *chol2;
+};
+int td_cca_workspace(td_handle* h, int k1, int k2, int dim, td_cca_ws* w);
+// Covariances (S / denom - mean^T mean, mean = sums / count, + lambda I on the auto-covariances), eps_eig filtering,
+// whitening, SVD, rotations: from the moments m_xx (row stride ld_xx) / m_yy / m_xy and the column sums m_s1 / m_s2.
+// expand_from: NULL when the moments are the workspace's own (w.xtx ...); else the statistics they are views of
+// (td_stats_cca_direct), which are expanded into the workspace when the one-launch stage hands over to the chain.
+// Synchronous; info_host [4] as td_cca_solve's.
+int td_cca_dense(td_handle* h, int k1, int k2, double count, const double* m_xx, int ld_xx, const double* m_yy,
+                 const double* m_xy, const double* m_s1, const double* m_s2, td_stats* expand_from, double denom,
+                 double regularization, double eps_eig, int dim, float* rot_x_dev, float* rot_y_dev,
+                 float* mean_x_dev, float* mean_y_dev, float* e_dev, int* info_host);
+// Whether a (k1, k2) problem takes the one-launch dense stage on this handle.
+bool td_cca_one_launch(const td_handle* h, int k1, int k2);

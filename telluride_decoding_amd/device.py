@@ -1915,6 +1915,106 @@ def online_fit_solve(state, c, pre, post, d, frames_emitted, lambdas, handle=Non
   return w, b
 
 
+# ---------------------------------------------------------------- online CCA fit
+# td_ccafit_online_push's limits (TD_ONLINE_CCAFIT_MAX_*)
+ONLINE_CCAFIT_MAX_CHANNELS, ONLINE_CCAFIT_MAX_FEATURES, ONLINE_CCAFIT_MAX_LAGS = 128, 32, 64
+ONLINE_CCAFIT_MAX_K, ONLINE_CCAFIT_MAX_DIMS = 2048, 16
+
+OnlineCcaFitSolve = collections.namedtuple('OnlineCcaFitSolve',
+                                           ['rot_x', 'rot_y', 'mean_x', 'mean_y', 'e', 'corr', 'info'])
+
+
+def _ccafit_views(c1, pre1, post1, c2, pre2, post2):
+  """The two views as the library takes them, and (k1, k2) -- (1, 1) for a shape the call will refuse by name, so
+  that no tensor of a wild size is made first."""
+  views = tuple(int(v) for v in (c1, pre1, post1, c2, pre2, post2))
+  k1, k2 = (views[1] + 1 + views[2]) * views[0], (views[4] + 1 + views[5]) * views[3]
+  if min(views) < 0 or k1 < 1 or k2 < 1 or k1 + k2 > ONLINE_CCAFIT_MAX_K:
+    k1 = k2 = 1
+  return views, k1, k2
+
+
+def online_ccafit_state_bytes(c1, pre1, post1, c2, pre2, post2):
+  """Bytes of one online CCA fit session's state block (td_ccafit_online_state_bytes): M [(k1 + k2 + 1)^2] float64,
+  then two tail copies of {EEG [pre1 + post, c1], features [pre2 + post, c2]} float32, post = max(post1, post2); all
+  zeros = a fresh session."""
+  return _lib_values('td_ccafit_online_state_bytes', _ccafit_views(c1, pre1, post1, c2, pre2, post2)[0])[0]
+
+
+def online_ccafit_push(eeg, feat, state, frames_before, pushes_before, pre1, post1, pre2, post2, c1=None, c2=None,
+                       flush=False, forget=1.0, handle=None):
+  """One push of a bank of online CCA fit sessions, in one launch (td_ccafit_online_push).
+
+  eeg [S, n, c1] and feat [S, n, c2]: float32 device tensors with unit column stride (None for a flush without
+  rows: give c1 and c2); state: uint8 device tensor [S, >= online_ccafit_state_bytes()] with a row stride that is a
+  multiple of 8, updated in place; frames_before: rows pushed so far; pushes_before: pushes WITH rows so far (its
+  parity says which tail copy is live).  Returns the rows pushed after the call.  Queued, not waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  sessions, stride = _check_fit_state('online_ccafit_push', h, state)
+  n = 0 if eeg is None else int(eeg.shape[1])
+  if eeg is not None:
+    if eeg.dim() != 3 or feat is None or feat.dim() != 3 or int(eeg.shape[0]) != sessions or \
+        tuple(feat.shape[:2]) != (sessions, n):
+      raise ValueError('online_ccafit_push: eeg of %s and features of %s for %d sessions' %
+                       (tuple(eeg.shape), None if feat is None else tuple(feat.shape), sessions))
+    c1, c2 = int(eeg.shape[2]), int(feat.shape[2])
+    _check_tensors('online_ccafit_push', h, (('eeg', eeg, torch.float32), ('feat', feat, torch.float32)), short=True)
+    if n > 0 and (eeg.stride(2) != 1 and c1 > 1 or feat.stride(2) != 1 and c2 > 1):
+      raise ValueError('online_ccafit_push: the columns of eeg and the features must be contiguous')
+  if c1 is None or c2 is None:
+    raise ValueError('online_ccafit_push: a flush without rows needs the channel count c1 and the feature count c2')
+  c1, c2 = int(c1), int(c2)
+  h.check(h.lib.td_ccafit_online_push(
+      h.ptr, sessions, *_row_block(eeg, n, sessions, c1), *_row_block(feat, n, sessions, c2), n,
+      c1, int(pre1), int(post1), c2, int(pre2), int(post2), int(frames_before), int(pushes_before),
+      1 if flush else 0, float(forget), _ptr(state), stride))
+  return int(frames_before) + n
+
+
+def online_ccafit_moments(state, c1, pre1, post1, c2, pre2, post2, handle=None):
+  """(xtx [S, k1 + 1, k1 + 1], x2tx2 [S, k2, k2], xtx2 [S, k1, k2], sum2 [S, k2]) float64 device tensors: the mirrored
+  dense moments of a bank of online CCA fit sessions in the layout of LagStats.moments, the ones row and column of
+  xtx last (td_ccafit_online_moments)."""
+  h = handle or default_handle()
+  sessions, stride = _check_fit_state('online_ccafit_moments', h, state)
+  views, k1, k2 = _ccafit_views(c1, pre1, post1, c2, pre2, post2)
+  xtx = h.empty((sessions, k1 + 1, k1 + 1), 'float64')
+  x2tx2 = h.empty((sessions, k2, k2), 'float64')
+  xtx2 = h.empty((sessions, k1, k2), 'float64')
+  sum2 = h.empty((sessions, k2), 'float64')
+  h.check(h.lib.td_ccafit_online_moments(h.ptr, sessions, _ptr(state), stride, *views, _ptr(xtx), _ptr(x2tx2),
+                                         _ptr(xtx2), _ptr(sum2)))
+  return xtx, x2tx2, xtx2, sum2
+
+
+def online_ccafit_solve(state, c1, pre1, post1, c2, pre2, post2, frames_emitted, lambdas, dim, eps_eig=1e-12,
+                        handle=None):
+  """The CCA model of every (session, lambda) from a bank's moments (td_ccafit_online_solve):
+  OnlineCcaFitSolve(rot_x [S, n_lambda, k1, dim], rot_y [S, n_lambda, k2, dim], mean_x [S, k1], mean_y [S, k2],
+  e [S, n_lambda, dim] float32 device tensors, corr [S, n_lambda, 3, dim] float64 {mean_a, mean_b, power} of the
+  fitted stretch, info [S, n_lambda, 4] host int32 as cca_solve's).  ValueError / HotPathError (fewer than 2 frames
+  counted)."""
+  h = handle or default_handle()
+  sessions, stride = _check_fit_state('online_ccafit_solve', h, state)
+  lam, lam_p = _lib.f64_array(np.atleast_1d(lambdas))
+  views, k1, k2 = _ccafit_views(c1, pre1, post1, c2, pre2, post2)
+  dims = int(dim) if 1 <= int(dim) <= ONLINE_CCAFIT_MAX_DIMS else 1
+  nl = max(len(lam), 1)
+  rot_x = h.empty((sessions, nl, k1, dims), 'float32')
+  rot_y = h.empty((sessions, nl, k2, dims), 'float32')
+  mean_x = h.empty((sessions, k1), 'float32')
+  mean_y = h.empty((sessions, k2), 'float32')
+  e = h.empty((sessions, nl, dims), 'float32')
+  corr = h.empty((sessions, nl, 3, dims), 'float64')
+  info = np.zeros((sessions, nl, 4), np.int32)
+  h.check(h.lib.td_ccafit_online_solve(
+      h.ptr, sessions, _ptr(state), stride, *views, int(frames_emitted), lam_p, len(lam), int(dim), float(eps_eig),
+      _ptr(rot_x), _ptr(rot_y), _ptr(mean_x), _ptr(mean_y), _ptr(e), _ptr(corr),
+      info.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+  return OnlineCcaFitSolve(rot_x, rot_y, mean_x, mean_y, e, corr, info)
+
+
 # ---------------------------------------------------------------- online calibration
 # td_calib_online_push's limits, the number of float64 sums in a state block, td_calib_online_finish's statuses
 ONLINE_CALIB_MAX_CHANNELS, ONLINE_CALIB_MAX_LAGS, ONLINE_CALIB_SUMS = 128, 64, 29

@@ -73,6 +73,14 @@ LDA and d'; `OnlineDecoder.set_statistics` takes them between pushes:
     r = calib.finish()
     online.set_statistics(r.corr, r.lda)
 
+A CCA bank trains the same way: `OnlineCCAFit` keeps the exact float64 moments of both lagged views in ONE
+td_ccafit_online_push launch per push, `solve(lambdas, dims)` gives the reference's CCA model and the fitted stretch's
+statistics on the device, and `OnlineDecoder.set_cca_model` takes them between pushes:
+
+    cca_fit.push(eeg, attended_features)
+    r = cca_fit.solve([1.0], dims=5)
+    online.set_cca_model(r.mean_x, r.rot_x[:, 0], r.mean_y, r.rot_y[:, 0], corr=r.corr[:, 0])
+
 Without a GPU (`device.gpu_available()` false) the same object runs a NumPy session with the same
 semantics -- float64 throughout, window sums in frame order, td_online_plan's arithmetic -- so that the logic can
 be built and tested anywhere.  (The state-space decoder has no host form: 'ssd' needs the GPU.)
@@ -458,7 +466,7 @@ class _HostDnnSession(_HostSession):
 
 
 class _Bank(object):
-  """What the five online banks share: S sessions that run on the device (`_dev`: a dict with the handle 'h' and the
+  """What the six online banks share: S sessions that run on the device (`_dev`: a dict with the handle 'h' and the
   zeroed uint8 'state' [S, bytes]) or as NumPy sessions (`_host`: a list of S objects with reset()), and refuse pushes
   once flushed.  A class gives FLUSHED, its sentence for that refusal."""
   FLUSHED = None
@@ -738,6 +746,70 @@ class OnlineDecoder(_Bank):
     d['corr'].copy_((corr.unsqueeze(1) if corr.dim() == 2 else corr).expand_as(d['corr']))
     if self.reduction == 'lda':
       d['lda'].copy_(conv(lda).expand_as(d['lda']))
+
+  def set_cca_model(self, mean_x, rot_x, mean_y, rot_y, corr=None, lda=None):
+    """Replaces the model of a CCA bank in place, between pushes: mean_x [k1], rot_x [k1, dims], mean_y [k2], rot_y
+    [k2, dims] (every session takes them) or with a leading [S] each; corr {mean_a, mean_b, power} as [3, dims]
+    (every session and both speakers), [S, 3, dims] (both speakers of a session) or [S, 2, 3, dims], kept as it is
+    when None; lda {weights, slope, intercept} as [dims + 2] or [S, dims + 2] -- a bank that reduces with 'lda' keeps
+    its LDA unless one is given, the other reductions do not read it.  dims is the bank's.  Device tensors (copied
+    device to device, no host copy: what OnlineCCAFit.solve returns, sliced) or arrays.  A bank that shared one model
+    copy holds S copies afterwards when S models are given.  The session state, the score ring, the tails and the
+    stepped / state-space decoder's state are untouched: the frames the next push emits are projected and scored
+    with the new parameters, so the first window that lies wholly behind the swap is that of a bank built with
+    them."""
+    if self.kind != 'cca':
+      raise ValueError('OnlineDecoder.set_cca_model replaces the model of a CCA bank only, not of a %s bank.' %
+                       self.kind)
+    s, dims = self.sessions, self.dims
+    k1 = (self.pre + 1 + self.post) * self.channels
+    k2 = (self.pre2 + 1 + self.post2) * self.features
+    shape_of = lambda a: tuple(a.shape) if hasattr(a, 'shape') else tuple(np.shape(a))
+    shapes = tuple(shape_of(a) for a in (mean_x, rot_x, mean_y, rot_y))
+    one, many = ((k1,), (k1, dims), (k2,), (k2, dims)), ((s, k1), (s, k1, dims), (s, k2), (s, k2, dims))
+    if shapes not in (one, many):
+      raise ValueError('OnlineDecoder.set_cca_model takes mean_x %s, rot_x %s, mean_y %s and rot_y %s, or each with a '
+                       'leading [%d], not %s.' % (one + (s, shapes)))
+    rows = s if shapes == many else 1
+    if corr is not None and shape_of(corr) not in ((3, dims), (s, 3, dims), (s, 2, 3, dims)):
+      raise ValueError('OnlineDecoder.set_cca_model takes corr [3, %d], [%d, 3, %d] or [%d, 2, 3, %d], not %s.' %
+                       (dims, s, dims, s, dims, shape_of(corr)))
+    if lda is not None and shape_of(lda) not in ((dims + 2,), (s, dims + 2)):
+      raise ValueError('OnlineDecoder.set_cca_model takes lda [%d] or [%d, %d], not %s.' %
+                       (dims + 2, s, dims + 2, shape_of(lda)))
+    names = ('mean_x', 'rot_x', 'mean_y', 'rot_y')
+    model = dict(zip(names, (mean_x, rot_x, mean_y, rot_y)))
+    if not self._on_device:
+      host = lambda a, dtype: np.asarray(a.cpu() if hasattr(a, 'cpu') else a, dtype)
+      for name, shape in zip(names, one):
+        a = host(model[name], np.float32).reshape((rows,) + shape)
+        for i, p in enumerate(self._params):
+          p[name] = np.ascontiguousarray(a[i % rows])
+      if corr is not None:
+        corr = host(corr, np.float64)
+        corr = np.broadcast_to(corr[:, None] if corr.ndim == 3 else corr, (s, 2, 3, dims))
+        for i, p in enumerate(self._params):
+          p['corr'] = corr[i].copy()
+      if lda is not None and self.reduction == 'lda':
+        for i, p in enumerate(self._params):
+          p['lda'] = np.broadcast_to(host(lda, np.float64), (s, dims + 2))[i].copy()
+      return
+    # (the device bank is the truth from here on: self._params keeps what the bank was built from)
+    d = self._dev
+    torch = device._torch()
+    conv = lambda a, dtype, np_dtype: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a, np_dtype))).to(
+        device=d['h'].device, dtype=dtype)
+    for name, shape in zip(names, one):
+      a = conv(model[name], torch.float32, np.float32).reshape((rows,) + shape)
+      if rows > int(d[name].shape[0]):            # one shared copy becomes S copies
+        d[name] = a.clone().contiguous()
+      else:
+        d[name].copy_(a.expand_as(d[name]))
+    if corr is not None:
+      corr = conv(corr, torch.float64, np.float64)
+      d['corr'].copy_((corr.unsqueeze(1) if corr.dim() == 3 else corr).expand_as(d['corr']))
+    if lda is not None and self.reduction == 'lda':
+      d['lda'].copy_(conv(lda, torch.float64, np.float64).expand_as(d['lda']))
 
   # -- pushes ------------------------------------------------------------------------------------
   def _rows(self, *arrays):
@@ -1759,8 +1831,335 @@ class OnlineRidgeFit(_Bank):
     return model
 
 
+# ------------------------------------------------------------------------------------------------ the online CCA fit
+CCAFitResult = collections.namedtuple('CCAFitResult', ['rot_x', 'rot_y', 'mean_x', 'mean_y', 'e', 'corr'])
+
+CCA_EPS_EIG = 1e-12                        # the reference's eigenvalue filter (cca.py:349-355)
+
+
+def _check_ccafit_shape(who, c1, pre1, post1, c2, pre2, post2, g):
+  """td_ccafit_online_push's limits, refused by name (the device call repeats them)."""
+  if not 1 <= c1 <= device.ONLINE_CCAFIT_MAX_CHANNELS:
+    raise ValueError('%s takes 1 to %d channels, not %d.' % (who, device.ONLINE_CCAFIT_MAX_CHANNELS, c1))
+  if not 1 <= c2 <= device.ONLINE_CCAFIT_MAX_FEATURES:
+    raise ValueError('%s takes 1 to %d features, not %d.' % (who, device.ONLINE_CCAFIT_MAX_FEATURES, c2))
+  for pre, post in ((pre1, post1), (pre2, post2)):
+    if pre < 0 or post < 0 or pre + 1 + post > device.ONLINE_CCAFIT_MAX_LAGS:
+      raise ValueError('%s takes at most %d lags in a view, not %d + 1 + %d.' %
+                       (who, device.ONLINE_CCAFIT_MAX_LAGS, pre, post))
+  k1, k2 = (pre1 + 1 + post1) * c1, (pre2 + 1 + post2) * c2
+  if k1 + k2 > device.ONLINE_CCAFIT_MAX_K:
+    raise ValueError('%s takes at most %d lagged inputs in the two views, not %d + %d = %d.' %
+                     (who, device.ONLINE_CCAFIT_MAX_K, k1, k2, k1 + k2))
+  if not 0.0 < g <= 1.0:
+    raise ValueError('%s takes a forgetting factor in (0, 1], not %r.' % (who, g))
+
+
+def cca_model_from_moments(m, k1, k2, lam, dim, eps_eig=CCA_EPS_EIG):
+  """The reference's CCA model (cca.py:337-362, as oracle/cca.py restates it) from the joint moments m [n, n] of
+  u = [x~ | y~ | 1] in float64, for ONE minibatch that holds all counted frames: (rot_x [k1, dim], rot_y [k2, dim],
+  mean_x [k1], mean_y [k2], e [dim]).  The covariances are symmetric, so the eigen-decompositions are eigh's."""
+  n = k1 + k2 + 1
+  count = m[n - 1, n - 1]
+  mean = m[n - 1, :n - 1] / count
+  mean_x, mean_y = mean[:k1], mean[k1:]
+  denom = count - 1.0
+  cov_xx = m[:k1, :k1] / denom - np.outer(mean_x, mean_x) + lam * np.eye(k1)
+  cov_yy = m[k1:n - 1, k1:n - 1] / denom - np.outer(mean_y, mean_y) + lam * np.eye(k2)
+  cov_xy = m[:k1, k1:n - 1] / denom - np.outer(mean_x, mean_y)
+
+  def whitening(cov):
+    vals, vecs = np.linalg.eigh(cov)
+    keep = vals > eps_eig
+    vals, vecs = vals[keep], vecs[:, keep]
+    return (vecs * np.reciprocal(np.sqrt(vals))[None, :]) @ vecs.T
+
+  k11, k22 = whitening(cov_xx), whitening(cov_yy)
+  u, e, vt = np.linalg.svd((k11 @ cov_xy) @ k22, full_matrices=False)
+  return k11 @ u[:, :dim], k22 @ vt.T[:, :dim], mean_x, mean_y, e[:dim]
+
+
+def cca_fit_statistics(m, k1, k2, mean_x, rot_x, mean_y, rot_y):
+  """corr [3, dim] = {mean_a, mean_b, power} of the projections (x~ - mean_x) rot_x and (y~ - mean_y) rot_y of the
+  counted frames, in closed form from the joint moments: with mu = sums / count and C = S / count - mu mu^T,
+  mean = (mu - mean_v) . R[:, d] and power[d] = sqrt((R_x[:, d]^T C_xx R_x[:, d]) (R_y[:, d]^T C_yy R_y[:, d])) --
+  infer_decoder.Decoder._add_sums' {mean_x, mean_y, power}."""
+  n = k1 + k2 + 1
+  count = m[n - 1, n - 1]
+  mu = m[n - 1, :n - 1] / count
+  out = []
+  quad = []
+  for lo, hi, mean, rot in ((0, k1, mean_x, rot_x), (k1, n - 1, mean_y, rot_y)):
+    rot = np.asarray(rot, np.float64)
+    out.append((mu[lo:hi] - np.asarray(mean, np.float64).reshape(-1)) @ rot)
+    mr = mu[lo:hi] @ rot
+    quad.append(np.einsum('id,ij,jd->d', rot, m[lo:hi, lo:hi], rot) / count - mr * mr)
+  return np.stack([out[0], out[1], np.sqrt(quad[0] * quad[1])])
+
+
+class _HostCCAFitSession(object):
+  """One online CCA fit session in NumPy: the semantics of td_ccafit_online_push bit for bit -- float32 rows, float64
+  moments, one M * g + outer(u, u) per emitted frame in frame order -- and the reference's model in float64 NumPy
+  (cca_model_from_moments)."""
+
+  def __init__(self, c1, pre1, post1, c2, pre2, post2, g):
+    self.v1, self.v2, self.g = (c1, pre1, post1), (c2, pre2, post2), float(g)
+    self.post = max(post1, post2)
+    self.k1, self.k2 = (pre1 + 1 + post1) * c1, (pre2 + 1 + post2) * c2
+    self.reset()
+
+  def reset(self):
+    n = self.k1 + self.k2 + 1
+    self.m = np.zeros((n, n), np.float64)
+    self.tail = np.zeros((self.v1[1] + self.post, self.v1[0]), np.float32)
+    self.feat_tail = np.zeros((self.v2[1] + self.post, self.v2[0]), np.float32)
+
+  def push(self, eeg, feat, frames_before, flush):
+    """eeg [n, c1], feat [n, c2] float32 behind frames_before rows; returns the frames this push emitted."""
+    (c1, pre1, post1), (c2, pre2, post2), post = self.v1, self.v2, self.post
+    after = frames_before + eeg.shape[0]
+    pad = lambda c: [np.zeros((post, c), np.float32)] if flush else []
+    # rows[0] is EEG row frames_before - (pre1 + post), frows[0] feature row frames_before - (pre2 + post); frame f
+    # reads the rows f - pre_v .. f + post_v of its view: the slots i + (post - post_v) .. of i = f - frames_before + post
+    rows = np.concatenate([self.tail, eeg] + pad(c1))
+    frows = np.concatenate([self.feat_tail, feat] + pad(c2))
+    e0 = max(0, frames_before - post)
+    e1 = after if flush else max(0, after - post)
+    lags1, lags2 = pre1 + 1 + post1, pre2 + 1 + post2
+    k1, k2 = self.k1, self.k2
+    u = np.ones((k1 + k2 + 1,), np.float64)
+    for f in range(e0, e1):
+      i = f - frames_before + post
+      u[:k1] = rows[i:i + lags1].reshape(-1)
+      u[k1:k1 + k2] = frows[i:i + lags2].reshape(-1)
+      self.m = self.m * self.g + np.outer(u, u)
+    both, fboth = np.concatenate([self.tail, eeg]), np.concatenate([self.feat_tail, feat])
+    self.tail = np.ascontiguousarray(both[both.shape[0] - (pre1 + post):])
+    self.feat_tail = np.ascontiguousarray(fboth[fboth.shape[0] - (pre2 + post):])
+    return max(0, e1 - e0)
+
+  def moments(self):
+    """(xtx [k1 + 1, k1 + 1] with the ones row and column last, x2tx2, xtx2, sum2): LagStats.moments' layout."""
+    k1, n = self.k1, self.k1 + self.k2 + 1
+    x = np.r_[np.arange(k1), n - 1]
+    return (self.m[np.ix_(x, x)], self.m[k1:n - 1, k1:n - 1].copy(), self.m[:k1, k1:n - 1].copy(),
+            self.m[k1:n - 1, n - 1].copy())
+
+  def solve(self, lambdas, dim):
+    """CCAFitResult's fields for this session, float64: rot_x [n_lambda, k1, dim], ..., corr [n_lambda, 3, dim]."""
+    outs = [cca_model_from_moments(self.m, self.k1, self.k2, lam, dim) for lam in lambdas]
+    corr = [cca_fit_statistics(self.m, self.k1, self.k2, o[2], o[0], o[3], o[1]) for o in outs]
+    return (np.stack([o[0] for o in outs]), np.stack([o[1] for o in outs]), outs[0][2], outs[0][3],
+            np.stack([o[4] for o in outs]), np.stack(corr))
+
+
+class OnlineCCAFit(_Bank):
+  """The online CCA decoder's training stage: a bank of S sessions that take (eeg, attended features) rows in pushes
+  of any length and keep the EXACT float64 moments of both lagged views -- M = sum u u^T of u = [x~ | y~ | 1], each
+  half the lagged vector of brain_data's context for its view -- in ONE td_ccafit_online_push launch per push, the
+  state on the device.  Any cut of a recording gives the same bytes.  `solve(lambdas, dims)` turns the moments into
+  the reference's CCA model on the device, through the dense stage of the batch fit (cca.py:337-362 for one minibatch
+  that holds all counted frames), with the fitted stretch's correlation statistics in closed form, and
+  `OnlineDecoder.set_cca_model` takes both without a host copy:
+
+      fit = OnlineCCAFit(64, 0, 20, features=8, input2_pre_context=0, input2_post_context=15)
+      for eeg, attended in calibration_chunks:            # [n, 64] and [n, 8] float32, any n
+        fit.push(eeg, attended)
+      r = fit.solve([1.0], dims=5)                         # device tensors
+      decoder.set_cca_model(r.mean_x, r.rot_x[:, 0], r.mean_y, r.rot_y[:, 0], corr=r.corr[:, 0])
+
+  A frame needs max(post_context, input2_post_context) rows of the future, so the moments run `delay` frames behind
+  the input; flush() ends the recording (zero rows behind it in both views, like the batch route's padding) and
+  counts the rest.  forgetting g in (0, 1]: every emitted frame first scales the moments by g; M[n - 1][n - 1] --
+  the count the covariances divide by -- is then the effective frame count.
+
+  Refused by name: more than 128 channels, more than 32 features, more than 64 lags in a view, more than 2048
+  lagged inputs in the two views, a push of more than 1048576 rows, a forgetting factor outside (0, 1].  Without a
+  GPU the same object runs a NumPy session of the same semantics, bit for bit for the moments (float64 NumPy for the
+  model, not rounded to float32)."""
+  FLUSHED = 'The fit was flushed: reset() starts the next recording.'
+
+  def __init__(self, channels, pre_context, post_context, features, input2_pre_context, input2_post_context,
+               num_sessions=1, forgetting=1.0):
+    c1, pre1, post1 = int(channels), int(pre_context), int(post_context)
+    c2, pre2, post2 = int(features), int(input2_pre_context), int(input2_post_context)
+    g = float(forgetting)
+    _check_ccafit_shape('OnlineCCAFit', c1, pre1, post1, c2, pre2, post2, g)
+    if int(num_sessions) < 1:
+      raise ValueError('OnlineCCAFit needs at least one session.')
+    self.channels, self.pre, self.post = c1, pre1, post1
+    self.features, self.pre2, self.post2 = c2, pre2, post2
+    self.forgetting = g
+    self.inputs, self.inputs2 = (pre1 + 1 + post1) * c1, (pre2 + 1 + post2) * c2       # k1, k2
+    self.delay = max(post1, post2)
+    self._views = (c1, pre1, post1, c2, pre2, post2)
+    _Bank.__init__(self, int(num_sessions), device.gpu_available())
+    if self._on_device:
+      h = device.default_handle()
+      self._dev = dict(h=h, state=self._zero_state(h, device.online_ccafit_state_bytes(*self._views)))
+    else:
+      self._host = [_HostCCAFitSession(c1, pre1, post1, c2, pre2, post2, g) for _ in range(self.sessions)]
+    self.reset()
+
+  def reset(self):
+    """A fresh recording and empty moments: zero state (a memset), no row pushed."""
+    self.rows_pushed = self.frames = 0           # frames: the frames counted into the moments so far
+    self._pushes = 0                             # pushes with rows: its parity is the live tail copy
+    _Bank.reset(self)
+
+  # -- pushes ------------------------------------------------------------------------------------
+  def _as_bank(self, eeg, feat):
+    """(eeg [S, n, c1], feat [S, n, c2]) float32: device tensors on the device, else host arrays."""
+    s, c1, c2 = self.sessions, self.channels, self.features
+    if self._on_device or any(hasattr(a, 'is_cuda') for a in (eeg, feat)):
+      torch = device._torch()
+      dev = self._dev['h'].device if self._on_device else None
+      conv = lambda a: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a, np.float32))).to(
+          device=dev, dtype=torch.float32)
+      eeg, feat = conv(eeg), conv(feat)
+      if not self._on_device:
+        eeg, feat = eeg.cpu().numpy(), feat.cpu().numpy()
+    else:
+      eeg, feat = np.asarray(eeg, np.float32), np.asarray(feat, np.float32)
+    shapes = (tuple(eeg.shape), tuple(feat.shape))
+    if len(eeg.shape) == 2 and len(feat.shape) == 2 and s == 1:
+      eeg, feat = eeg.reshape((1,) + shapes[0]), feat.reshape((1,) + shapes[1])
+    n = int(eeg.shape[1]) if len(eeg.shape) == 3 else -1
+    if len(eeg.shape) != 3 or tuple(eeg.shape) != (s, n, c1) or tuple(feat.shape) != (s, n, c2):
+      raise ValueError('A push is eeg [%d, n, %d] (or [n, %d] for one session) with features [%d, n, %d] (or [n, %d] '
+                       'for one session), not eeg %s with features %s.' % ((s, c1, c1, s, c2, c2) + shapes))
+    if n > MAX_FIT_PUSH:
+      raise ValueError('OnlineCCAFit takes at most %d rows in one push, not %d.' % (MAX_FIT_PUSH, n))
+    return eeg, feat
+
+  def push(self, eeg, feat):
+    """The next n rows of every session: eeg [n, c1] / [S, n, c1] and the attended speaker's features [n, c2] /
+    [S, n, c2], float32 device tensors (read where they are, no host copy) or arrays; n may be 0.  Returns the
+    frames counted so far."""
+    self._refuse_flushed()
+    eeg, feat = self._as_bank(eeg, feat)
+    return self._advance(eeg, feat, False)
+
+  def flush(self, eeg=None, feat=None):
+    """The end of the recording: the last `delay` frames are counted as if zero rows followed in both views -- behind
+    the recording's last rows, when they are given (one launch for both).  After it the fit refuses pushes until
+    reset(); moments() and solve() stay."""
+    self._refuse_flushed()
+    if self._last_rows('OnlineCCAFit.flush takes the last rows as eeg AND feat, or neither.', eeg, feat):
+      eeg, feat = self._as_bank(eeg, feat)
+    frames = self._advance(eeg, feat, True)
+    self.flushed = True
+    return frames
+
+  def _advance(self, eeg, feat, flush):
+    n = 0 if eeg is None else int(eeg.shape[1])
+    after = self.rows_pushed + n
+    counted = after if flush else max(0, after - self.delay)
+    if not self._on_device:
+      if eeg is None:
+        eeg, feat = self._no_rows(self.channels), self._no_rows(self.features)
+      for i, sess in enumerate(self._host):
+        sess.push(eeg[i], feat[i], self.rows_pushed, flush)
+    else:
+      d = self._dev
+      if n == 0:
+        eeg = feat = None
+      else:
+        if eeg.stride(2) != 1 and self.channels > 1:
+          eeg = eeg.contiguous()
+        if feat.stride(2) != 1 and self.features > 1:
+          feat = feat.contiguous()
+      device.online_ccafit_push(eeg, feat, d['state'], self.rows_pushed, self._pushes, self.pre, self.post,
+                                self.pre2, self.post2, c1=self.channels, c2=self.features, flush=flush,
+                                forget=self.forgetting, handle=d['h'])
+    self.rows_pushed = after
+    self.frames = counted
+    if n > 0:
+      self._pushes += 1
+    return self.frames
+
+  # -- what the state holds ----------------------------------------------------------------------
+  @property
+  def tails(self):
+    """(EEG tail [S, pre1 + delay, c1], feature tail [S, pre2 + delay, c2]) float32: the live copy -- slot j of a
+    view holds row rows_pushed - (pre_v + delay) + j, zero before row 0.  Device tensors (views) or host arrays."""
+    s, c1, c2 = self.sessions, self.channels, self.features
+    tl1, tl2 = self.pre + self.delay, self.pre2 + self.delay
+    if self._dev is None:
+      return (np.stack([sess.tail for sess in self._host]), np.stack([sess.feat_tail for sess in self._host]))
+    n = self.inputs + self.inputs2 + 1
+    floats = self._dev['state'].view(device._torch().float32)
+    copy = tl1 * c1 + tl2 * c2
+    at = 2 * n * n + (self._pushes & 1) * copy
+    return (floats[:, at:at + tl1 * c1].reshape(s, tl1, c1), floats[:, at + tl1 * c1:at + copy].reshape(s, tl2, c2))
+
+  def moments(self):
+    """(xtx [S, k1 + 1, k1 + 1], x2tx2 [S, k2, k2], xtx2 [S, k1, k2], sum2 [S, k2]) float64, dense and symmetric, the
+    ones row / column of xtx last -- the layout of LagStats.moments; xtx[:, k1, k1] is the (effective) frame count.
+    Device tensors on the device, else host arrays."""
+    if self._dev is None:
+      per = [sess.moments() for sess in self._host]
+      return tuple(np.stack([p[i] for p in per]) for i in range(4))
+    return device.online_ccafit_moments(self._dev['state'], *self._views, handle=self._dev['h'])
+
+  def _check_solve(self, who, lambdas, dims):
+    lambdas = [float(v) for v in np.atleast_1d(lambdas)]
+    dims = int(dims)
+    if not lambdas:
+      raise ValueError('%s needs at least one lambda.' % who)
+    if any(not lam >= 0.0 or not np.isfinite(lam) for lam in lambdas):
+      raise ValueError('%s: regularization lambda must be >= 0, not %s.' % (who, lambdas))
+    most = min(device.ONLINE_CCAFIT_MAX_DIMS, self.inputs, self.inputs2)
+    if not 1 <= dims <= most:
+      raise ValueError('%s: dims must be in [1, %d], not %d.' % (who, most, dims))
+    if self.frames < 2:
+      raise ValueError('%s: %d frames counted yet (%d rows pushed, results run %d behind): the covariance needs at '
+                       'least 2.' % (who, self.frames, self.rows_pushed, self.delay))
+    return lambdas, dims
+
+  def solve(self, lambdas, dims, want_info=False):
+    """The CCA model from the moments so far, for every session and every lambda: CCAFitResult(rot_x [S, n_lambda,
+    k1, dims], rot_y [S, n_lambda, k2, dims], mean_x [S, k1], mean_y [S, k2], e [S, n_lambda, dims] -- the canonical
+    correlations --, corr [S, n_lambda, 3, dims] float64 {mean_a, mean_b, power} of the counted frames' projections,
+    what OnlineDecoder.set_cca_model takes).  float32 device tensors on the device (td_ccafit_online_solve: one
+    dense stage per (session, lambda), synchronous), else host arrays (float64, as every NumPy session: not rounded
+    to float32).  want_info: (result, info [S, n_lambda, 4]) -- td_cca_solve's sweeps and route bits (zeros on the
+    host).  ValueError before 2 frames were counted."""
+    lambdas, dims = self._check_solve('OnlineCCAFit.solve', lambdas, dims)
+    if self._dev is None:
+      outs = [sess.solve(lambdas, dims) for sess in self._host]
+      result = CCAFitResult(*(np.stack([o[i] for o in outs]) for i in range(6)))
+      info = np.zeros((self.sessions, len(lambdas), 4), np.int32)
+    else:
+      out = device.online_ccafit_solve(self._dev['state'], *self._views, self.frames, lambdas, dims,
+                                       eps_eig=CCA_EPS_EIG, handle=self._dev['h'])
+      result, info = CCAFitResult(*out[:6]), out.info
+    return (result, info) if want_info else result
+
+  def update_model(self, model, regularization, dims, session=0):
+    """Gives a cca.BrainModelCCA of matching widths the rotations and means of one session (model.set_weights, and
+    model.eigenvalues): the model's two input widths must be k1 and k2, its output_dims `dims`.  Returns the model."""
+    from telluride_decoding_amd import cca
+    if not isinstance(model, cca.BrainModelCCA):
+      raise ValueError('OnlineCCAFit.update_model takes a BrainModelCCA, not a %s.' % type(model).__name__)
+    for name, mine, theirs in (('input_1 width', self.inputs, model._input1_width),
+                               ('input_2 width', self.inputs2, model._input2_width),
+                               ('output dims', int(dims), model.output_dims)):
+      if int(theirs) != mine:
+        raise ValueError('OnlineCCAFit.update_model: the model has %s = %d, the fit %d.' % (name, int(theirs), mine))
+    if not 0 <= int(session) < self.sessions:
+      raise ValueError('OnlineCCAFit.update_model: session %d of %d.' % (int(session), self.sessions))
+    r = self.solve([regularization], dims)
+    i = int(session)
+    host = lambda a: (a.cpu().numpy() if hasattr(a, 'cpu') else np.asarray(a)).astype(np.float32)
+    model.set_weights([host(r.mean_x[i]).reshape(1, -1), host(r.mean_y[i]).reshape(1, -1), host(r.rot_x[i, 0]),
+                       host(r.rot_y[i, 0])])
+    model.eigenvalues = host(r.e[i, 0])
+    return model
+
+
 # ------------------------------------------------------------------------------------------------ the online calibration
-CalibrationResult = collections.namedtuple('CalibrationResult', ['corr', 'lda', 'dprime'])
+CalibrationResult =collections.namedtuple('CalibrationResult', ['corr', 'lda', 'dprime'])
 
 CALIB_SUMS = device.ONLINE_CALIB_SUMS      # TD_CALIB_ONLINE_SUMS
 _CALIB_REASONS = {
