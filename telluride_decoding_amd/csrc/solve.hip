@@ -1407,6 +1407,8 @@ static int ridge_solve_impl(td_handle* h, td_stats* s, const double* lambdas_hos
   if (!h || !s || !lambdas_host || !w_dev || !b_dev)
     return td_fail(h, TD_ERR_INVALID, "td_ridge_solve: NULL argument");
   h->last_cg_kernel = TD_CG_KERNEL_NONE; h->last_cg_param = 0; h->last_cg_wgs = 0;
+  // (here, not behind the wide branch: td_last_solve_info reported the PREVIOUS solve after a wide one)
+  h->last_solver = TD_SOLVER_CHOLESKY; h->last_iterations = 0; h->last_cg_status = 0;
   int k1 = 0, d = 0;
   int64_t frames = 0;
   td_stats_layout(s, &k1, &d, &frames);
@@ -1432,7 +1434,6 @@ static int ridge_solve_impl(td_handle* h, td_stats* s, const double* lambdas_hos
   double* xty = xtx + nn;
   const SolveWs w = carve(reinterpret_cast<char*>(base) + head, np, n_lambda);
   TD_TRY(td_upload_async(h, lambdas_host, sizeof(double) * n_lambda, w.lams));
-  h->last_solver = TD_SOLVER_CHOLESKY; h->last_iterations = 0; h->last_cg_status = 0;
   {
     // Conjugate gradients on the COMPACT statistics (cg.hip: one workgroup per channel, no dense matrix,
     // no expansion): the route of a handle whose CUs cannot hold the dense matrix in LDS (the solve

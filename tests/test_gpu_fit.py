@@ -358,21 +358,13 @@ def test_ridge_at_size_boundaries(dev, c, post, d):
 
 
 def test_spd_solve_sizes(dev):
-  """Blocked Cholesky across partial panels, several right-hand sides, batch."""
+  """The padding's scale.  (The sizes -- partial panels, several right-hand sides, batches -- are rows of
+  tests/chol_edges.py: SPD_SIZE_LOOP in SPD_CASES, held by tests/test_gpu_chol_edges.py to a backward error of
+  8 x LAPACK's instead of rtol 1e-9.)"""
   import ctypes
   import torch
   h = dev.default_handle()
   rng = np.random.default_rng(11)
-  for n, nrhs, batch in ((1, 1, 1), (63, 1, 2), (64, 2, 1), (65, 3, 2), (200, 1, 3), (513, 4, 1)):
-    a = rng.standard_normal((batch, n, n + 8))
-    a = a @ a.transpose(0, 2, 1) + 0.5 * np.eye(n)
-    rhs = rng.standard_normal((batch, n, nrhs))
-    want = np.linalg.solve(a, rhs)
-    ad = torch.from_numpy(a.copy()).cuda()
-    rd = torch.from_numpy(rhs.copy()).cuda()
-    h.check(h.lib.td_spd_solve(h.ptr, ctypes.c_void_p(ad.data_ptr()),
-                               ctypes.c_void_p(rd.data_ptr()), n, nrhs, batch))
-    np.testing.assert_allclose(rd.cpu().numpy(), want, rtol=1e-9, atol=1e-11)
   # The identity padding (n is rounded up to whole 64 x 64 tiles) sits on the system's own
   # scale: a system whose diagonal is ~1e15 (a huge ridge lambda) or ~1e-20 is as solvable as
   # np.linalg.solve finds it -- with a fixed 1.0 on the padding's diagonal the first had its
