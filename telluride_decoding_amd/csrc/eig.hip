@@ -28,6 +28,7 @@
 // positive definite covariances keep their relative accuracy, which K = V lambda^-1/2 V^T
 // needs).  Small dense and latency-bound: reported as time, not against a roofline.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 
 #include "stats_common.h"
@@ -630,7 +631,8 @@ __global__ __launch_bounds__(256) void svd_extract_kernel(const double* __restri
                                                           double* __restrict__ vn) {
   __shared__ int pick;
   const int want = blockIdx.x;
-  if (threadIdx.x == 0) pick = -1;
+  // (0 like the two sibling selectors: NaN norms all rank 0, so a later `want` may match no index at all)
+  if (threadIdx.x == 0) pick = 0;
   __syncthreads();
   for (int i = threadIdx.x; i < k; i += 256) {
     const double si = norms[i];
@@ -828,8 +830,10 @@ int jacobi_svd(td_handle* h, double* g, int ldg, int k, int m, int dim, double* 
     std::vector<double> lam((size_t)k);
     TD_HIP(h, hipMemcpyAsync(lam.data(), vals, sizeof(double) * k, hipMemcpyDeviceToHost, h->stream));
     TD_HIP(h, hipStreamSynchronize(h->stream));
-    std::sort(lam.begin(), lam.end(), [](double a, double b) { return a > b; });
-    if (lam[0] > 0.0 && lam[dim - 1] > 1e-10 * lam[0]) {
+    // (a > b is no strict weak ordering once a NaN is among the values: those take the rounds, unsorted)
+    const bool finite = std::all_of(lam.begin(), lam.end(), [](double v) { return std::isfinite(v); });
+    if (finite) std::sort(lam.begin(), lam.end(), [](double a, double b) { return a > b; });
+    if (finite && lam[0] > 0.0 && lam[dim - 1] > 1e-10 * lam[0]) {
       hipLaunchKernelGGL(svd_from_eig_kernel, dim3((unsigned)dim), dim3(256), 0, h->stream, g, ldg, k, m, vals,
                          vt, sig, gn, vn);
       TD_HIP(h, hipGetLastError());
