@@ -1288,6 +1288,92 @@ int td_calib_online_finish(td_handle* h, int num_sessions, const void* state_dev
                            int64_t frames_emitted, int width, double* corr_dev, double* lda_dev, double* dprime_dev,
                            int32_t* status_dev);
 
+/* ------------------------------------------------------------------ online calibration of a CCA model
+ * The stage behind the online CCA fit: what infer_decoder.Decoder.train(data0, data1, window_size = W) takes from a
+ * labelled stretch with a CCADecoder -- per dim the correlation statistics {mean_a, mean_b, power} of ONE correlator
+ * fed both classes, the scaled LDA over the `dims` columns between the window means of the unattended (class 0) and
+ * the attended (class 1) correlations, d' -- for (eeg, attended features, unattended features) rows that arrive in
+ * pushes of any length, projected with the model handed to each push.  `num_sessions` independent sessions, one
+ * state block each on the device, ONE launch per push (one workgroup of 1024 threads per session), nothing stored
+ * per row.  However a recording is cut into pushes, the state is that of one push of the whole recording, bit for bit.
+ *
+ * Frames are emitted post = max(post1, post2) rows late with td_online_plan's arithmetic, as td_cca_online_push
+ * emits them.  Per emitted frame and with D = dims: a [D] is the EEG view's projection, b1 [D] the attended feature
+ * block's, b0 [D] the unattended one's -- the float32 values td_cca_online_push returns in `proj` (the same
+ * function).  Windows are average_data's: consecutive, hop = width, the tail dropped; width 1 is train's frame-level
+ * case.
+ *
+ * State (td_ccacalib_online_state_bytes; all zeros = a fresh session; the HOST counts the frames): a head of
+ * T(D) = 9 D^2 + 20 D float64 sums (29 at D = 1, td_calib_online's count; 2624 at D = 16), every per-frame sum
+ * advanced in frame order by acc += (double)x * (double)y (the product is exact),
+ *   [0, 6 D)    over every emitted frame: sum a, sum a^2, sum b1, sum b1^2, sum b0, sum b0^2, [D] each
+ *   then class 0 (b = b0) over the completed windows: sum_w z [3 D], then the upper triangle of sum_w z z^T row-major
+ *               (3 D (3 D + 1) / 2 entries), z = (sum a b [D] | sum a [D] | sum b [D]) of a window; the sum takes plain
+ *               adds, the Gram G + z_i z_j unfused (the product rounds, then the add)
+ *   then class 1 (b = b1), the same
+ *   then the open window: sum a, sum b1, sum a b1, sum b0, sum a b0, [D] each (zero again when a frame completes a
+ *               window)
+ * then the EEG tail [pre1 + post][c1] and the feature tails [2][pre2 + post][c2] float32 (attended, unattended), as
+ * td_cca_online_push carries them, rounded up to 8 bytes.
+ *
+ * td_ccacalib_online_lds_bytes: (*pass, *bytes) of a launch that emits `emitted` frames: the frames a workgroup
+ * stages at once -- 64, fewer for a short push, halved until the LDS fits TD_CCA_ONLINE_LDS_BYTES -- and the
+ * dynamic LDS: 8 (5 D pass) for the windows a pass completes, then float32: both means, both rotations transposed,
+ * the staged rows and the pass's projections (td_cca_online_lds_bytes' terms).  A shape that does not fit at a pass
+ * of one frame is refused by every entry point that takes the shape.
+ *
+ * td_ccacalib_online_push: the sessions' next n rows.
+ *   eeg_dev [S][n][c1] float32, row stride eeg_ld, session stride eeg_session_stride (elements)
+ *   att_dev, unatt_dev [S][n][c2] float32, row stride feat_ld, session stride feat_session_stride (elements)
+ *   mean_x_dev [k1], rot_x_dev [k1][dims], mean_y_dev [k2], rot_y_dev [k2][dims] float32, k = c (pre + 1 + post);
+ *   model_session_stride 0 (one model for all) or 1 (session s reads model s) -- read where they lie at every push
+ *   n >= 0 (n == 0 without flush: nothing is queued); a push that emits nothing still rolls the tails
+ *   frames_before: rows pushed so far;  flush != 0: the recording ends behind this push
+ *   state_dev, state_session_stride (BYTES, a multiple of 8, >= td_ccacalib_online_state_bytes)
+ * With td_profile_enable the launch is bracketed as td_online_push's is.
+ *
+ * td_ccacalib_online_sums: out_dev [S][T(dims)] float64, the head in the order above.
+ *
+ * td_ccacalib_online_finish: ONE launch (a workgroup of 256 threads per session) evaluates in float64, with
+ * N = frames_emitted (the host's count), n_win = N / width and the correlator as train feeds it (class 0 first):
+ *   per dim d: count = 2 N, sum_x = 2 sum a, sum_x2 = 2 sum a^2, sum_y = sum b0 + sum b1, sum_y2 = sum b0^2 + sum b1^2,
+ *   mean_a = sum_x / count, mean_b = sum_y / count,
+ *   power = sqrt((sum_x2 - sum_x^2 / count) (sum_y2 - sum_y^2 / count)) / count, c0_d = mean_a mean_b / power
+ *   C [D][3 D]: row d holds (1, -mean_b_d, -mean_a_d) / (width power_d) at the columns (d, D + d, 2 D + d); per class
+ *   sum_w m = C sum z + n_win c0,  sum_w m m^T = C (sum z z^T) C^T + (C sum z) c0^T + c0 (C sum z)^T + n_win c0 c0^T,
+ *   mu = sum_w m / n_win,  S = sum_w m m^T - n_win mu mu^T
+ *   Sw = S_0 + S_1,  v = Sw^-1 (mu_1 - mu_0) by Cholesky,  w = v / |v|_2 ([1] at D = 1),
+ *   slope = 1 / ((mu_1 - mu_0) . w),  intercept = -slope (mu_0 . w),
+ *   d' = |(mu_1 - mu_0) . w| / sqrt((w^T S_0 w + w^T S_1 w) / (2 n_win))
+ * and writes corr_dev [S][2][3][D] (both speaker rows {mean_a, mean_b, power}: the layout td_cca_online_push reads),
+ * lda_dev [S][D + 2] {w, slope, intercept}, dprime_dev [S] and status_dev [S] int32: TD_CALIB_OK; TD_CALIB_NO_WINDOW;
+ * TD_CALIB_NO_POWER (a dim's power not finite or <= 0); TD_CALIB_NOT_POSITIVE (the pooled scatter Sw is not positive
+ * definite: a Cholesky pivot <= 0 or not finite, or fewer than dims + 2 windows in all); TD_CALIB_SAME_MEANS
+ * (the class means are equal along w: scaled LDA's "X0 and X1 ... identical").  What a session cannot give is NaN.
+ * The state is not modified.  Bracketed by td_profile_enable as a push is.
+ *
+ * TD_ERR_INVALID, before anything is queued and with the state untouched: a NULL required pointer, num_sessions
+ * outside 1..65535, td_cca_online_push's shape limits (128 channels, 32 features, 64 lags per view, 16 dims), a shape
+ * over the LDS budget, width outside 1..TD_ONLINE_MAX_WIDTH, n outside 0..TD_ONLINE_MAX_PUSH, frames_before or
+ * frames_emitted < 0, a row or session stride below a row, a model stride other than 0 or 1, a state stride below the
+ * state block (for _sums and _finish: below the head) or not a multiple of 8. */
+#define TD_CALIB_NOT_POSITIVE 4
+int td_ccacalib_online_state_bytes(int c1, int pre1, int post1, int c2, int pre2, int post2, int dims,
+                                   int64_t* bytes);
+int td_ccacalib_online_lds_bytes(int c1, int pre1, int post1, int c2, int pre2, int post2, int dims,
+                                 int64_t emitted, int* pass, int64_t* bytes);
+int td_ccacalib_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t eeg_ld,
+                            int64_t eeg_session_stride, const float* att_dev, const float* unatt_dev,
+                            int64_t feat_ld, int64_t feat_session_stride, int64_t n, int c1, int pre1, int post1,
+                            int c2, int pre2, int post2, int dims, const float* mean_x_dev, const float* rot_x_dev,
+                            const float* mean_y_dev, const float* rot_y_dev, int64_t model_session_stride, int width,
+                            int64_t frames_before, int flush, void* state_dev, int64_t state_session_stride);
+int td_ccacalib_online_sums(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,
+                            int dims, double* out_dev);
+int td_ccacalib_online_finish(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,
+                              int dims, int64_t frames_emitted, int width, double* corr_dev, double* lda_dev,
+                              double* dprime_dev, int32_t* status_dev);
+
 /* ------------------------------------------------------------------ ingestion
  * ingest.find_mean_std, ingest.normalize_data and ingest.convert_data_to_tfrecords (ingest.py:1061-1172).
  *

@@ -217,6 +217,15 @@ SIGNATURES = {
     'td_calib_online_sums': [_vp, _i, _vp, _i64, _vp],
     # h, sessions | state, stride | frames_emitted, width | corr, lda, dprime, status
     'td_calib_online_finish': [_vp, _i, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp],
+    'td_ccacalib_online_state_bytes': _VIEW + _VIEW + [_i, _pi64],
+    'td_ccacalib_online_lds_bytes': _VIEW + _VIEW + [_i, _i64, _c.POINTER(_i), _pi64],
+    # h, sessions | eeg, ld, stride | attended, unattended, ld, stride | n | c1, pre1, post1 | c2, pre2, post2 | dims |
+    # mean_x, rot_x, mean_y, rot_y, model stride | width, frames_before, flush | state, stride
+    'td_ccacalib_online_push': [_vp, _i] + [_vp, _i64, _i64] + [_vp, _vp, _i64, _i64] + [_i64] + _VIEW + _VIEW + [_i] +
+                               [_vp, _vp, _vp, _vp, _i64] + [_i, _i64, _i] + [_vp, _i64],
+    'td_ccacalib_online_sums': [_vp, _i, _vp, _i64, _i, _vp],
+    # h, sessions | state, stride | dims | frames_emitted, width | corr, lda, dprime, status
+    'td_ccacalib_online_finish': [_vp, _i, _vp, _i64, _i, _i64, _i, _vp, _vp, _vp, _vp],
     'td_ingest_moments': [_vp, _c.POINTER(_vp), _pi64, _pi64, _c.POINTER(_i), _i, _i, _vp],
     'td_ingest_normalize': [_vp, _vp, _i, _i64, _i64, _i, _pd, _pd, _i, _i, _i, _i, _vp, _i64],
     'td_tfrecord_encode': [_vp, _c.c_char_p, _i, _i, _c.POINTER(_vp), _pi64, _c.POINTER(_i), _c.POINTER(_i),

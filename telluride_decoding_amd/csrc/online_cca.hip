@@ -15,8 +15,9 @@
 // The rotations live in LDS transposed, rot_s[d][k]: the 64 lanes of a wave read 64 consecutive words of one
 // column, the same addresses modulo nothing -- no bank conflict whatever k1 is -- and the lagged row of a frame is
 // contiguous in the staged rows (row f + l at (f + l) c + ch = f c + k), so x~, the mean and the rotation column
-// are three unit-stride LDS streams.  No atomics, vector stores only.
-#include "online_common.h"
+// are three unit-stride LDS streams.  No atomics, vector stores only.  The projection, the model's and the feature
+// blocks' staging and the feature tails are online_cca_common.h's, shared with online_cca_calib.hip.
+#include "online_cca_common.h"
 
 namespace {
 
@@ -25,24 +26,15 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kWinThreads = 256;   // window_means_kernel's workgroup: a window mean keeps ITS order
 constexpr int kMaxC1 = 128, kMaxC2 = 32, kMaxLags = 64, kMaxDims = 16;   // (kFirMaxD columns)
 constexpr int kPass = 64;          // emitted frames per pass of a workgroup; halved until the LDS budget holds
-constexpr int kDimBlock = 4;       // columns a wave accumulates at once (4 x 4 accumulators)
 constexpr long long kLdsBudget = TD_CCA_ONLINE_LDS_BYTES;
 
 // One session's state block: [stepped state f64][ring f64 [2][width]][EEG tail f32 [pre1 + post][c1]]
 // [feature tail f32 [2][pre2 + post][c2]], rounded up to 8 bytes; post = max(post1, post2).
-__host__ __device__ inline int delay_of(int post1, int post2) { return post1 > post2 ? post1 : post2; }
 __host__ __device__ inline long long state_feat_offset(int c1, int pre1, int post, int width) {
   return tail_end(state_eeg_offset(width), c1, pre1 + post);
 }
 __host__ __device__ inline long long state_bytes(int c1, int pre1, int c2, int pre2, int post, int width) {
   return tails_bytes(state_eeg_offset(width), c1, pre1 + post, 2LL * c2 * (pre2 + post));
-}
-
-// Rows of the staging areas: a pass reads nf + pre + post_v rows of a view; the tail shift at the end of a
-// push parks up to pre + post rows there.
-__host__ __device__ inline int stage_rows(int pass, int pre, int post_v, int post) {
-  const int a = pass + pre + post_v, b = pre + post;
-  return a > b ? a : b;
 }
 
 // LDS of a launch: 8 (4 pass) for the pass's per-frame scores and window means, then float32: both means
@@ -101,44 +93,6 @@ __device__ __forceinline__ double frame_score(const float* a, const float* b, co
   return acc / (double)dims;
 }
 
-// One view's projection of one frame by one wave: out[d] = sum_k (xr[k] - mean[k]) rot[d K + k], kDimBlock
-// columns at a time (a column past dims - 1 repeats the last one and is dropped).
-__device__ __forceinline__ void project_row(const float* xr, const float* mean, const float* rot, int K, int dims,
-                                            int lane, float* out) {
-  for (int d0 = 0; d0 < dims; d0 += kDimBlock) {
-    const float* r[kDimBlock];
-#pragma unroll
-    for (int i = 0; i < kDimBlock; ++i) r[i] = rot + (size_t)(d0 + i < dims ? d0 + i : dims - 1) * K;
-    float acc[kDimBlock][4];
-#pragma unroll
-    for (int i = 0; i < kDimBlock; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i][j] = 0.f;
-    int k = lane;
-    for (; k + 192 < K; k += 256) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float xc = xr[k + 64 * j] - mean[k + 64 * j];
-#pragma unroll
-        for (int i = 0; i < kDimBlock; ++i) acc[i][j] = fmaf(xc, r[i][k + 64 * j], acc[i][j]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      if (k + 64 * j < K) {
-        const float xc = xr[k + 64 * j] - mean[k + 64 * j];
-#pragma unroll
-        for (int i = 0; i < kDimBlock; ++i) acc[i][j] = fmaf(xc, r[i][k + 64 * j], acc[i][j]);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < kDimBlock; ++i) {
-      const float total = wave_sum_f32((acc[i][0] + acc[i][1]) + (acc[i][2] + acc[i][3]));
-      if (lane == 0 && d0 + i < dims) out[d0 + i] = total;
-    }
-  }
-}
-
 __global__ __launch_bounds__(kThreads) void cca_online_push_kernel(CcaOnlineParams p) {
   extern __shared__ double lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -177,16 +131,7 @@ __global__ __launch_bounds__(kThreads) void cca_online_push_kernel(CcaOnlinePara
   const long long emitted_now = p.e1 - p.e0;
 
   // ---- the model: the means as they are, the rotations transposed (global [k][dims] -> LDS [dims][k])
-  for (int k = tid; k < k1; k += kThreads) mean1_s[k] = mean_x[k];
-  for (int k = tid; k < k2; k += kThreads) mean2_s[k] = mean_y[k];
-  for (int i = tid; i < k1 * dims; i += kThreads) {
-    const int k = i / dims, d = i - k * dims;
-    rot1_s[d * k1 + k] = rot_x[i];
-  }
-  for (int i = tid; i < k2 * dims; i += kThreads) {
-    const int k = i / dims, d = i - k * dims;
-    rot2_s[d * k2 + k] = rot_y[i];
-  }
+  stage_model<kThreads>(mean1_s, mean2_s, rot1_s, rot2_s, mean_x, rot_x, mean_y, rot_y, k1, k2, dims);
   double step = load_step(step_p, p.decoder);
 
   for (long long a = p.e0; a < p.e1; a += pass) {
@@ -195,16 +140,7 @@ __global__ __launch_bounds__(kThreads) void cca_online_push_kernel(CcaOnlinePara
     // a + nf - 1 + post2: from the tails (rows before this push), from the push, zeros before the recording
     // and behind a flushed end
     stage_rows<kThreads>(rows1_s, c1, tail1, t1, eeg, p.eeg_ld, c1, a - pre1, nf + pre1 + post1, p0, p1);
-    const int n_rows2 = nf + pre2 + post2;
-    for (int i = tid; i < 2 * n_rows2 * c2; i += kThreads) {
-      const int spk = i / (n_rows2 * c2), rem = i - spk * (n_rows2 * c2);
-      const int rr = rem / c2, ch = rem - rr * c2;
-      const long long row = a - pre2 + rr;
-      float v = 0.f;
-      if (row >= 0 && row < p0) v = tail2[((long long)spk * t2 + (row - (p0 - t2))) * c2 + ch];
-      else if (row >= p0 && row < p1) v = feat[spk][(row - p0) * p.feat_ld + ch];
-      rows2_s[((size_t)spk * r2 + rr) * c2 + ch] = v;
-    }
+    stage_feat<kThreads>(rows2_s, r2, tail2, t2, feat, p.feat_ld, c2, a - pre2, nf + pre2 + post2, p0, p1);
     __syncthreads();
     // ---- projections: a wave per (frame, view): the EEG view once, then each speaker's features
     for (int t = wave; t < 3 * nf; t += kWaves) {
@@ -238,33 +174,17 @@ __global__ __launch_bounds__(kThreads) void cca_online_push_kernel(CcaOnlinePara
   __syncthreads();
   const long long n = p.n;
   tail_park<kThreads>(rows1_s, tail1, t1, c1, n);
-  const int keep2 = n < t2 ? (int)(t2 - n) : 0;
-  for (int i = tid; i < 2 * keep2 * c2; i += kThreads) {
-    const int spk = i / (keep2 * c2), rem = i - spk * (keep2 * c2);
-    rows2_s[(size_t)spk * r2 * c2 + rem] = tail2[((long long)spk * t2 + (t2 - keep2)) * c2 + rem];
-  }
+  feat_tail_park<kThreads>(rows2_s, r2, tail2, t2, c2, n);
   __syncthreads();
   tail_store<kThreads>(tail1, rows1_s, t1, c1, eeg, p.eeg_ld, n);
-  for (int i = tid; i < 2 * t2 * c2; i += kThreads) {
-    const int spk = i / (t2 * c2), rem = i - spk * (t2 * c2);
-    const int rr = rem / c2, ch = rem - rr * c2;
-    tail2[i] = rr < keep2 ? rows2_s[(size_t)spk * r2 * c2 + rem] : feat[spk][(n - (t2 - rr)) * p.feat_ld + ch];
-  }
+  feat_tail_store<kThreads>(tail2, rows2_s, r2, t2, c2, feat, p.feat_ld, n);
   store_step(step_p, p.decoder, step);
 }
 
 // The shape checks td_cca_online_state_bytes, td_cca_online_lds_bytes and td_cca_online_push share.
 int check_shape(td_handle* h, const char* who, int c1, int pre1, int post1, int c2, int pre2, int post2, int dims,
                 int width) {
-  TD_REQUIRE(h, c1 >= 1 && c1 <= kMaxC1, "%s: %d EEG channels (1 .. %d)", who, c1, kMaxC1);
-  TD_REQUIRE(h, pre1 >= 0 && post1 >= 0 && pre1 + 1 + post1 <= kMaxLags,
-             "%s: EEG context of %d + 1 + %d frames (at most %d lags)", who, pre1, post1, kMaxLags);
-  TD_REQUIRE(h, c2 >= 1 && c2 <= kMaxC2, "%s: %d feature channels (1 .. %d)", who, c2, kMaxC2);
-  TD_REQUIRE(h, pre2 >= 0 && post2 >= 0 && pre2 + 1 + post2 <= kMaxLags,
-             "%s: feature context of %d + 1 + %d frames (at most %d lags)", who, pre2, post2, kMaxLags);
-  TD_REQUIRE(h, dims >= 1 && dims <= kMaxDims, "%s: %d dims (1 .. %d)", who, dims, kMaxDims);
-  TD_REQUIRE(h, width >= 1 && width <= TD_ONLINE_MAX_WIDTH, "%s: window of %d frames (1 .. %d)", who, width,
-             TD_ONLINE_MAX_WIDTH);
+  TD_TRY(check_cca_views(h, who, c1, pre1, post1, c2, pre2, post2, dims, width, kMaxC1, kMaxC2, kMaxLags, kMaxDims));
   const long long need = lds_bytes(c1, pre1, post1, c2, pre2, post2, dims, 1);
   TD_REQUIRE(h, need <= kLdsBudget,
              "%s: the rotations of %d x %d and %d x %d lags in %d dims and a pass of one frame take %lld bytes of "

@@ -1,13 +1,14 @@
-// What the online push kernels share (online.hip, online_cca.hip, online_dnn.hip, online_calib.hip): the state
-// block's layout, the plan of a push, and the blocks of a push kernel that every session repeats -- stage, (predict:
-// each file's own, the FIR prediction here for the two files that use it), score, windows, tails.  The host interface
-// is td_common.h.  online_fit.hip, online_pre.hip and online_audio.hip carry other state and do not use this.
+// What the online push kernels share (online.hip, online_cca.hip, online_dnn.hip, online_calib.hip and, through
+// online_cca_common.h, online_cca_calib.hip): the state block's layout, the plan of a push, and the blocks of a push
+// kernel that every session repeats -- stage, (predict: each file's own, the FIR prediction here for the two files
+// that use it), score, windows, tails.  The host interface is td_common.h.  online_fit.hip, online_pre.hip and
+// online_audio.hip carry other state and do not use this.
 //
 // Every block here is under the family's promise: any cut of a recording into pushes gives the bytes of one push.
-// online_calib.hip includes this under a file-level `#pragma clang fp contract(off)`, the other files under the
-// default (on), so nothing here may depend on the contraction mode at the include point: where a fused operation is
-// the contract it is an explicit fmaf / fma, and nowhere else does a product feed an add or a subtract in one
-// expression (no bare a * b + c).  Keep it so when adding to this file.
+// online_calib.hip and online_cca_calib.hip include this under a file-level `#pragma clang fp contract(off)`, the
+// other files under the default (on), so nothing here may depend on the contraction mode at the include point: where
+// a fused operation is the contract it is an explicit fmaf / fma, and nowhere else does a product feed an add or a
+// subtract in one expression (no bare a * b + c).  Keep it so when adding to this file.
 #pragma once
 #include "td_common.h"
 

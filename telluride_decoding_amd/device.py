@@ -2097,6 +2097,109 @@ def online_calib_finish(state, frames_emitted, width, handle=None):
   return OnlineCalibFinish(corr, lda, dprime, status)
 
 
+# ---------------------------------------------------------------- online calibration of a CCA model
+CALIB_NOT_POSITIVE = 4                     # TD_CALIB_NOT_POSITIVE: td_ccacalib_online_finish's fifth status
+
+
+def online_ccacalib_sums_count(dims):
+  """T(dims) = 9 dims^2 + 20 dims: the float64 sums at the head of an online CCA calibration session's state."""
+  return 9 * int(dims) * int(dims) + 20 * int(dims)
+
+
+def online_ccacalib_state_bytes(c1, pre1, post1, c2, pre2, post2, dims):
+  """Bytes of one online CCA calibration session's state block (td_ccacalib_online_state_bytes):
+  online_ccacalib_sums_count(dims) float64 sums, then the EEG tail [pre1 + post, c1] and the feature tails
+  [2, pre2 + post, c2] float32, post = max(post1, post2); all zeros = a fresh session."""
+  return _lib_values('td_ccacalib_online_state_bytes', (int(c1), int(pre1), int(post1), int(c2), int(pre2),
+                                                        int(post2), int(dims)))[0]
+
+
+def online_ccacalib_lds_bytes(c1, pre1, post1, c2, pre2, post2, dims, emitted=64):
+  """(frames per pass, LDS bytes) of a td_ccacalib_online_push launch that emits `emitted` frames
+  (td_ccacalib_online_lds_bytes); ValueError with the byte budget for a shape that does not fit at a pass of one."""
+  return tuple(_lib_values('td_ccacalib_online_lds_bytes', (int(c1), int(pre1), int(post1), int(c2), int(pre2),
+                                                            int(post2), int(dims), int(emitted)), _I32_I64))
+
+
+def online_ccacalib_push(eeg, attended, unattended, mean_x, rot_x, mean_y, rot_y, state, frames_before, pre1, post1,
+                         pre2, post2, width, flush=False, handle=None):
+  """One push of a bank of online CCA calibration sessions, in one launch (td_ccacalib_online_push).
+
+  eeg [S, n, c1], attended and unattended [S, n, c2]: float32 device tensors with unit column stride (None for a
+  flush without rows; the two feature tensors share their strides); mean_x [M, k1], rot_x [M, k1, dims], mean_y
+  [M, k2], rot_y [M, k2, dims] float32 with M = S or 1 (one model for every session) -- read where they are at every
+  push; state: uint8 device tensor [S, >= online_ccacalib_state_bytes()] with a row stride that is a multiple of 8,
+  updated in place; frames_before: rows pushed so far; width: the window of the LDA's training data.  Returns the
+  rows pushed after the call.  Queued, not waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  who = 'online_ccacalib_push'
+  sessions, stride = _check_fit_state(who, h, state)
+  pre1, post1, pre2, post2 = int(pre1), int(post1), int(pre2), int(post2)
+  nl1, nl2 = pre1 + 1 + post1, pre2 + 1 + post2
+  if rot_x.dim() != 3 or rot_y.dim() != 3 or mean_x.dim() != 2 or mean_y.dim() != 2:
+    raise ValueError('%s: the means are [M, k] and the rotations [M, k, dims]' % who)
+  models, k1, dims = (int(v) for v in rot_x.shape)
+  k2 = int(rot_y.shape[1])
+  if (nl1 < 1 or nl2 < 1 or k1 % nl1 or k2 % nl2 or tuple(rot_y.shape) != (models, k2, dims) or
+      tuple(mean_x.shape) != (models, k1) or tuple(mean_y.shape) != (models, k2) or models not in (1, sessions)):
+    raise ValueError('%s: rotations of %s and %s with means of %s and %s for %d + %d lags and %d sessions' %
+                     (who, tuple(rot_x.shape), tuple(rot_y.shape), tuple(mean_x.shape), tuple(mean_y.shape), nl1, nl2,
+                      sessions))
+  c1, c2 = k1 // nl1, k2 // nl2
+  n = 0 if eeg is None else int(eeg.shape[1])
+  if eeg is not None and (tuple(eeg.shape) != (sessions, n, c1) or attended is None or unattended is None or
+                          tuple(attended.shape) != (sessions, n, c2) or tuple(unattended.shape) != (sessions, n, c2)):
+    raise ValueError('%s: eeg of %s and features of %s and %s for %d sessions of %d channels and %d features' %
+                     (who, tuple(eeg.shape), None if attended is None else tuple(attended.shape),
+                      None if unattended is None else tuple(unattended.shape), sessions, c1, c2))
+  _check_tensors(who, h, (
+      ('eeg', eeg, torch.float32), ('attended', attended, torch.float32), ('unattended', unattended, torch.float32),
+      ('mean_x', mean_x, torch.float32), ('rot_x', rot_x, torch.float32), ('mean_y', mean_y, torch.float32),
+      ('rot_y', rot_y, torch.float32)), short=True)
+  if n > 0:
+    if (c1 > 1 and eeg.stride(2) != 1) or (c2 > 1 and (attended.stride(2) != 1 or unattended.stride(2) != 1)):
+      raise ValueError('%s: the columns of eeg and the features must be contiguous' % who)
+    if unattended.stride() != attended.stride():      # (one pair of strides serves both classes)
+      attended, unattended = attended.contiguous(), unattended.contiguous()
+  mean_x, rot_x, mean_y, rot_y = (t.contiguous() for t in (mean_x, rot_x, mean_y, rot_y))
+  att_p, feat_row, feat_session = _row_block(attended, n, sessions, c2)
+  h.check(h.lib.td_ccacalib_online_push(
+      h.ptr, sessions, *_row_block(eeg, n, sessions, c1), att_p, _ptr(unattended if n > 0 else None), feat_row,
+      feat_session, n, c1, pre1, post1, c2, pre2, post2, dims, _ptr(mean_x), _ptr(rot_x), _ptr(mean_y), _ptr(rot_y),
+      0 if models == 1 else 1, int(width), int(frames_before), 1 if flush else 0, _ptr(state), stride))
+  return int(frames_before) + n
+
+
+def online_ccacalib_sums(state, dims, handle=None):
+  """The float64 sums of a bank of online CCA calibration sessions, [S, online_ccacalib_sums_count(dims)] on the
+  device, in td_ccacalib_online_sums' order: sum a, a^2, b1, b1^2, b0, b0^2 [dims each] | class 0: sum z [3 dims],
+  upper sum z z^T | class 1 | the open window's sum a, b1, a b1, b0, a b0 [dims each]."""
+  h = handle or default_handle()
+  sessions, stride = _check_fit_state('online_ccacalib_sums', h, state)
+  count = online_ccacalib_sums_count(dims) if 1 <= int(dims) <= CCA_ONLINE_MAX_DIMS else 1   # (refused by name)
+  out = h.empty((sessions, count), 'float64')
+  h.check(h.lib.td_ccacalib_online_sums(h.ptr, sessions, _ptr(state), stride, int(dims), _ptr(out)))
+  return out
+
+
+def online_ccacalib_finish(state, dims, frames_emitted, width, handle=None):
+  """The closed form of Decoder.train on a CCA bank's sums, in one launch (td_ccacalib_online_finish):
+  OnlineCalibFinish(corr [S, 2, 3, dims] float64, lda [S, dims + 2] float64 {w, slope, intercept}, dprime [S] float64,
+  status [S] int32 -- CALIB_OK, CALIB_NO_WINDOW, CALIB_NO_POWER, CALIB_SAME_MEANS, CALIB_NOT_POSITIVE), device
+  tensors.  The state is not modified.  Queued, not waited for."""
+  h = handle or default_handle()
+  sessions, stride = _check_fit_state('online_ccacalib_finish', h, state)
+  d = int(dims) if 1 <= int(dims) <= CCA_ONLINE_MAX_DIMS else 1                               # (refused by name)
+  corr = h.empty((sessions, 2, 3, d), 'float64')
+  lda = h.empty((sessions, d + 2), 'float64')
+  dprime = h.empty((sessions,), 'float64')
+  status = h.empty((sessions,), 'int32')
+  h.check(h.lib.td_ccacalib_online_finish(h.ptr, sessions, _ptr(state), stride, int(dims), int(frames_emitted),
+                                          int(width), _ptr(corr), _ptr(lda), _ptr(dprime), _ptr(status)))
+  return OnlineCalibFinish(corr, lda, dprime, status)
+
+
 # ---------------------------------------------------------------- fully connected regressor / match-mismatch classifier
 MLP_LOSSES = {'mse': 0, 'pearson': 1}
 

@@ -81,6 +81,15 @@ statistics on the device, and `OnlineDecoder.set_cca_model` takes them between p
     r = cca_fit.solve([1.0], dims=5)
     online.set_cca_model(r.mean_x, r.rot_x[:, 0], r.mean_y, r.rot_y[:, 0], corr=r.corr[:, 0])
 
+and `OnlineCCACalibration` closes that chain as `OnlineCalibration` closes the linear one: a labelled stretch of (eeg,
+attended features, unattended features) rows through the bank's current rotations in ONE td_ccacalib_online_push
+launch per push gives the statistics of ONE correlator fed both classes and the scaled LDA over the dims columns --
+one Cholesky solve, no eigenproblem --, and `OnlineDecoder.set_cca_statistics` takes them between pushes:
+
+    cca_calib.push(eeg, attended_features, unattended_features)
+    c = cca_calib.finish()
+    online.set_cca_statistics(c.corr, c.lda)
+
 Without a GPU (`device.gpu_available()` false) the same object runs a NumPy session with the same
 semantics -- float64 throughout, window sums in frame order, td_online_plan's arithmetic -- so that the logic can
 be built and tested anywhere.  (The state-space decoder has no host form: 'ssd' needs the GPU.)
@@ -810,6 +819,47 @@ class OnlineDecoder(_Bank):
       d['corr'].copy_((corr.unsqueeze(1) if corr.dim() == 3 else corr).expand_as(d['corr']))
     if lda is not None and self.reduction == 'lda':
       d['lda'].copy_(conv(lda, torch.float64, np.float64).expand_as(d['lda']))
+
+  def set_cca_statistics(self, corr, lda=None):
+    """Replaces the correlation statistics -- and, for reduction 'lda', the LDA -- of a CCA bank in place, between
+    pushes: corr {mean_a, mean_b, power} as [3, dims] (every session and both speakers take it), [S, 3, dims] (both
+    speakers of a session) or [S, 2, 3, dims]; lda {weights, slope, intercept} as [dims + 2] or [S, dims + 2], required
+    when the bank's reduction is 'lda' and not read otherwise -- device tensors (copied device to device, no host
+    copy: what OnlineCCACalibration.finish returns) or arrays.  The rotations, the session state, the score ring, the
+    tails and the stepped / state-space decoder's state are untouched: the frames the next push emits are scored with
+    the new parameters, so the first window that lies wholly behind the swap is that of a bank built with them."""
+    if self.kind != 'cca':
+      raise ValueError('OnlineDecoder.set_cca_statistics replaces the statistics of a CCA bank only, not of a %s '
+                       'bank (set_statistics is that bank\'s).' % self.kind)
+    s, dims = self.sessions, self.dims
+    shape_of = lambda a: tuple(a.shape) if hasattr(a, 'shape') else tuple(np.shape(a))
+    if shape_of(corr) not in ((3, dims), (s, 3, dims), (s, 2, 3, dims)):
+      raise ValueError('OnlineDecoder.set_cca_statistics takes corr [3, %d], [%d, 3, %d] or [%d, 2, 3, %d], not %s.' %
+                       (dims, s, dims, s, dims, shape_of(corr)))
+    if lda is not None and shape_of(lda) not in ((dims + 2,), (s, dims + 2)):
+      raise ValueError('OnlineDecoder.set_cca_statistics takes lda [%d] or [%d, %d], not %s.' %
+                       (dims + 2, s, dims + 2, shape_of(lda)))
+    if self.reduction == 'lda' and lda is None:
+      raise ValueError('OnlineDecoder.set_cca_statistics: a bank that reduces with \'lda\' needs lda '
+                       '{weights, slope, intercept} beside corr.')
+    if not self._on_device:
+      host = lambda a: np.asarray(a.cpu() if hasattr(a, 'cpu') else a, np.float64)
+      corr = host(corr)
+      corr = np.broadcast_to(corr[:, None] if corr.ndim == 3 else corr, (s, 2, 3, dims))
+      for i, p in enumerate(self._params):
+        p['corr'] = corr[i].copy()
+        if self.reduction == 'lda':
+          p['lda'] = np.broadcast_to(host(lda), (s, dims + 2))[i].copy()
+      return
+    # (the device bank is the truth from here on: self._params keeps what the bank was built from)
+    d = self._dev
+    torch = device._torch()
+    conv = lambda a: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a, np.float64))).to(
+        device=d['h'].device, dtype=torch.float64)
+    corr = conv(corr)
+    d['corr'].copy_((corr.unsqueeze(1) if corr.dim() == 3 else corr).expand_as(d['corr']))
+    if self.reduction == 'lda':
+      d['lda'].copy_(conv(lda).expand_as(d['lda']))
 
   # -- pushes ------------------------------------------------------------------------------------
   def _rows(self, *arrays):
@@ -2434,4 +2484,330 @@ class OnlineCalibration(_Bank):
         scaled_lda.LdaParamsTuple(np.ones((1, 1)), np.zeros((1, 1)), [1, 2],
                                   [vec(o['class_means'][0]), vec(o['class_means'][1])], float(o['slope']),
                                   float(o['intercept'])))
+    return float(o['dprime'])
+
+
+# ------------------------------------------------------------------------------------------ the online CCA calibration
+_CCA_CALIB_REASONS = dict(_CALIB_REASONS)
+_CCA_CALIB_REASONS[device.CALIB_NO_POWER] = ('the correlation power of a dim is not finite or not above zero (a '
+                                             'constant projection)')
+_CCA_CALIB_REASONS[device.CALIB_NOT_POSITIVE] = ('the pooled scatter of the window means is not positive definite '
+                                                 '(%(windows)d windows per class for %(dims)d dims: at least '
+                                                 'dims + 2 windows in all are needed)')
+_CCA_CALIB_REASONS[device.CALIB_SAME_MEANS] = ('X0 and X1 in Scaled LDA are identical: the attended and the '
+                                               'unattended window means are equal along the LDA axis')
+
+
+def cca_calibration_layout(dims):
+  """(entries of one class, offset of class 0, offset of the open window, T) of the float64 head of
+  td_ccacalib_online_push's state for `dims` columns: [0, 6 dims) the correlator | class 0 | class 1 | the open
+  window [5 dims]; a class is sum z [3 dims] then the row-major upper triangle of sum z z^T."""
+  n3 = 3 * dims
+  per_class = n3 + n3 * (n3 + 1) // 2
+  return per_class, 6 * dims, 6 * dims + 2 * per_class, device.online_ccacalib_sums_count(dims)
+
+
+def cca_calibration_walk(sums, a, b1, b0, first_frame, width):
+  """Advances one session's float64 sums (td_ccacalib_online_push's layout) in place by the emitted frames
+  first_frame, first_frame + 1, ... with the projections a, b1 (attended), b0 (unattended) [frames, dims]: every sum
+  in frame order, acc += x * y in float64; when a frame completes a window each class's sum z takes plain adds, its
+  Gram G + z_i * z_j, and the open window returns to zero."""
+  a, b1, b0 = (np.asarray(v, np.float64) for v in (a, b1, b0))
+  d = a.shape[1]
+  per_class, class0, open0, _ = cca_calibration_layout(d)
+  upper = np.triu_indices(3 * d)
+  for i in range(a.shape[0]):
+    x, y1, y0 = a[i], b1[i], b0[i]
+    sums[:6 * d] = sums[:6 * d] + np.concatenate([x, x * x, y1, y1 * y1, y0, y0 * y0])
+    sums[open0:] = sums[open0:] + np.concatenate([x, y1, x * y1, y0, x * y0])
+    if (first_frame + i + 1) % width == 0:
+      o = sums[open0:].reshape(5, d)
+      for cls, z in ((0, np.concatenate([o[4], o[0], o[3]])), (1, np.concatenate([o[2], o[0], o[1]]))):
+        base = class0 + cls * per_class
+        sums[base:base + 3 * d] = sums[base:base + 3 * d] + z
+        sums[base + 3 * d:base + per_class] = sums[base + 3 * d:base + per_class] + np.outer(z, z)[upper]
+      sums[open0:] = 0.0
+
+
+def cca_calibration_closed_form(sums, frames, width, dims):
+  """td_ccacalib_online_finish for one session in NumPy float64: dict(status, count, sum_x, sum_y, sum_x2, sum_y2,
+  mean_a, mean_b, power [dims each], class_means [2, dims], w [dims], slope, intercept, dprime) from the sums after
+  `frames` emitted frames.  Scaled LDA on two classes without the eigenproblem: the between-class scatter has rank
+  one, so the leading eigenvector of inv(Sw) Sb is Sw^-1 (mu_1 - mu_0) up to scale and sign, which slope and
+  intercept remove."""
+  q = np.asarray(sums, np.float64)
+  d = int(dims)
+  per_class, class0, _, _ = cca_calibration_layout(d)
+  nans = np.full((d,), np.nan)
+  out = dict(status=device.CALIB_OK, w=nans, slope=np.nan, intercept=np.nan, dprime=np.nan,
+             class_means=np.full((2, d), np.nan))
+  with np.errstate(all='ignore'):
+    count = np.float64(2.0 * frames)
+    s = q[:6 * d].reshape(6, d)
+    sum_x, sum_x2, sum_y, sum_y2 = s[0] + s[0], s[1] + s[1], s[4] + s[2], s[5] + s[3]
+    mean_a, mean_b = sum_x / count, sum_y / count
+    power = np.sqrt((sum_x2 - sum_x * sum_x / count) * (sum_y2 - sum_y * sum_y / count)) / count
+    out.update(count=int(2 * frames), sum_x=sum_x, sum_y=sum_y, sum_x2=sum_x2, sum_y2=sum_y2, mean_a=mean_a,
+               mean_b=mean_b, power=power)
+    n_win = float(int(frames) // int(width))
+    if n_win < 1.0:
+      out.update(status=device.CALIB_NO_WINDOW, mean_a=nans, mean_b=nans, power=nans)
+      return out
+    if not np.all(power > 0.0) or np.any(np.isinf(power)):
+      out.update(status=device.CALIB_NO_POWER, mean_a=nans, mean_b=nans, power=nans)
+      return out
+    scale = 1.0 / (float(width) * power)
+    c = np.zeros((d, 3 * d))
+    at = np.arange(d)
+    c[at, at], c[at, d + at], c[at, 2 * d + at] = scale, -mean_b * scale, -mean_a * scale
+    c0 = mean_a * mean_b / power
+    upper = np.triu_indices(3 * d)
+    means, scatters = [], []
+    for cls in (0, 1):
+      base = class0 + cls * per_class
+      g = np.zeros((3 * d, 3 * d))
+      g[upper] = q[base + 3 * d:base + per_class]
+      g = g + np.triu(g, 1).T
+      cz = c @ q[base:base + 3 * d]
+      smm = c @ g @ c.T + np.outer(cz, c0) + np.outer(c0, cz) + n_win * np.outer(c0, c0)
+      mu = (cz + n_win * c0) / n_win
+      means.append(mu)
+      scatters.append(smm - n_win * np.outer(mu, mu))
+    out.update(class_means=np.stack(means))
+    within = scatters[0] + scatters[1]
+    delta = means[1] - means[0]
+    try:
+      if 2.0 * n_win < d + 2.0 or not np.all(np.isfinite(within)):
+        raise np.linalg.LinAlgError('fewer points than dims')
+      factor = np.linalg.cholesky(within)
+      if not np.all(np.isfinite(factor)):
+        raise np.linalg.LinAlgError('not finite')
+    except np.linalg.LinAlgError:
+      out.update(status=device.CALIB_NOT_POSITIVE)
+      return out
+    v = np.linalg.solve(factor.T, np.linalg.solve(factor, delta))
+    w = np.ones((1,)) if d == 1 else v / np.sqrt(np.sum(v * v))
+    along = float(delta @ w)
+    if along == 0.0 or np.isnan(along):
+      out.update(status=device.CALIB_SAME_MEANS)
+      return out
+    slope = 1.0 / along
+    spread = float(w @ scatters[0] @ w + w @ scatters[1] @ w)
+    out.update(w=w, slope=slope, intercept=-slope * float(means[0] @ w),
+               dprime=abs(along) / np.sqrt(spread / (2.0 * n_win)))
+  return out
+
+
+class _HostCCACalibSession(object):
+  """One online CCA calibration session in NumPy: the semantics of td_ccacalib_online_push with float64 projections
+  (as _HostCcaSession projects), the sums of cca_calibration_walk."""
+
+  def __init__(self, c1, pre1, post1, c2, pre2, post2, dims, width):
+    self.view1, self.view2, self.dims, self.width = (c1, pre1, post1), (c2, pre2, post2), dims, width
+    self.delay = max(post1, post2)
+    self.reset()
+
+  def reset(self):
+    (c1, pre1, _), (c2, pre2, _) = self.view1, self.view2
+    self.sums = np.zeros((device.online_ccacalib_sums_count(self.dims),), np.float64)
+    self.tail = np.zeros((pre1 + self.delay, c1), np.float64)
+    self.feat_tail = np.zeros((2, pre2 + self.delay, c2), np.float64)
+
+  def push(self, eeg, feat, model, frames_before, flush):
+    """eeg [n, c1], feat [2, n, c2] (attended, unattended) float64 behind frames_before rows, projected with
+    model's mean_x, rot_x, mean_y, rot_y."""
+    (c1, pre1, post1), (c2, pre2, post2) = self.view1, self.view2
+    post = self.delay
+    pl = device.online_plan(frames_before, eeg.shape[0], post, 1, 1, flush)
+    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c1))] if flush else []))
+    frows = np.concatenate([self.feat_tail, feat] + ([np.zeros((2, post, c2))] if flush else []), axis=1)
+    emitted = pl.emitted_after - pl.emitted_before
+    i0 = pl.emitted_before - (frames_before - post)   # (as _HostCcaSession.push)
+    f64 = lambda name: np.asarray(model[name], np.float32).astype(np.float64)
+    project = _HostCcaSession._project
+    a = project(rows, i0, emitted, c1, pre1 + 1 + post1, f64('mean_x'), f64('rot_x'))
+    b1, b0 = (project(frows[k], i0, emitted, c2, pre2 + 1 + post2, f64('mean_y'), f64('rot_y')) for k in (0, 1))
+    cca_calibration_walk(self.sums, a, b1, b0, pl.emitted_before, self.width)
+    both = np.concatenate([self.tail, eeg])
+    self.tail = both[both.shape[0] - (pre1 + post):]
+    fboth = np.concatenate([self.feat_tail, feat], axis=1)
+    self.feat_tail = fboth[:, fboth.shape[1] - (pre2 + post):]
+    return emitted
+
+
+class OnlineCCACalibration(_Bank):
+  """The CCA chain's last training stage: per dim the correlation statistics, the scaled LDA over the dims columns
+  and d' that infer_decoder.Decoder.train(data0, data1, window_size=W) would take from a labelled stretch with a
+  CCADecoder -- data0 the (EEG projection, unattended projection) frames, data1 the (EEG projection, attended
+  projection) frames, ONE correlator fed both -- for rows that arrive in pushes of any length, projected with the
+  bank's CURRENT model, in ONE td_ccacalib_online_push launch per push and with nothing stored per row:
+
+      r = fit.solve([lam], dims); decoder.set_cca_model(r.mean_x, r.rot_x[:, 0], r.mean_y, r.rot_y[:, 0])
+      calib = OnlineCCACalibration(decoder, window_size=100)
+      for eeg, att, unatt in calibration_chunks:         # [n, C], [n, c2], [n, c2] float32, any n
+        calib.push(eeg, att, unatt)
+      c = calib.finish()                                 # CalibrationResult(corr, lda, dprime), on the device
+      decoder.set_cca_statistics(c.corr, c.lda)          # device to device
+
+  decoder: a CCA OnlineDecoder bank; the sessions, the two views and the dims are the bank's, and every push reads
+  the bank's means and rotations where they are, so the calibrator follows set_cca_model.  window_size: the frames
+  averaged into one training point of the LDA (default 100; <= 1: every frame).  Windows are
+  infer_decoder.average_data's: consecutive, the tail dropped.  The sums run max(post_context, input2_post_context)
+  rows behind the input; flush() ends the recording.  finish() can be called at any time and leaves the state alone.
+  Any cut of a recording gives the same state bytes (sums()).  The LDA needs a positive definite pooled scatter: at
+  least dims + 2 windows in all.
+
+  Without a GPU the same object runs a NumPy session of the same semantics (float64 projections)."""
+  FLUSHED = 'The calibration was flushed: reset() starts the next stretch.'
+
+  def __init__(self, decoder, window_size=100):
+    if not isinstance(decoder, OnlineDecoder):
+      raise ValueError('OnlineCCACalibration calibrates an OnlineDecoder bank, not a %s.' % type(decoder).__name__)
+    if decoder.kind != 'cca':
+      raise ValueError('OnlineCCACalibration calibrates a CCA bank, not a %s bank (OnlineCalibration is the linear '
+                       'bank\'s).' % decoder.kind)
+    width = max(1, int(window_size))
+    if width > MAX_WINDOW:
+      raise ValueError('OnlineCCACalibration takes windows of 1 to %d frames, not %d.' % (MAX_WINDOW, width))
+    self.decoder = decoder
+    _Bank.__init__(self, decoder.sessions, decoder._on_device)
+    self.channels, self.pre, self.post = decoder.channels, decoder.pre, decoder.post
+    self.features, self.pre2, self.post2, self.dims = decoder.features, decoder.pre2, decoder.post2, decoder.dims
+    self.window_size = width
+    self.delay = decoder.delay
+    shape = (self.channels, self.pre, self.post, self.features, self.pre2, self.post2, self.dims)
+    if self._on_device:
+      h = decoder._dev['h']
+      device.online_ccacalib_lds_bytes(*shape, 1)      # (a shape over the LDS budget: the library says so, by name)
+      self._dev = dict(h=h, state=self._zero_state(h, device.online_ccacalib_state_bytes(*shape)))
+    else:
+      self._host = [_HostCCACalibSession(*shape, width) for _ in range(self.sessions)]
+    self.reset()
+
+  def reset(self):
+    """A fresh calibration stretch: zero state (a memset), no row pushed."""
+    self.rows_pushed = 0
+    _Bank.reset(self)
+
+  @property
+  def frames_emitted(self):
+    """The frames counted into the sums so far: `delay` behind the rows pushed, all of them after flush()."""
+    return self.rows_pushed if self.flushed else max(0, self.rows_pushed - self.delay)
+
+  @property
+  def windows(self):
+    """The completed windows per class."""
+    return self.frames_emitted // self.window_size
+
+  # -- pushes ------------------------------------------------------------------------------------
+  def _as_rows(self, eeg, attended, unattended):
+    eeg, feats = self.decoder._as_cca_bank(eeg, attended, unattended)
+    if int(eeg.shape[1]) > MAX_FIT_PUSH:
+      raise ValueError('OnlineCCACalibration takes at most %d rows in one push, not %d.' %
+                       (MAX_FIT_PUSH, eeg.shape[1]))
+    return eeg, feats
+
+  def push(self, eeg, attended_features, unattended_features):
+    """The next n rows of every session: eeg [n, C] / [S, n, C], the attended and the unattended speaker's feature
+    block [n, c2] / [S, n, c2], float32 device tensors (read where they are) or arrays; n may be 0.  Returns the
+    frames counted so far."""
+    self._refuse_flushed()
+    return self._advance(*self._as_rows(eeg, attended_features, unattended_features), False)
+
+  def flush(self, eeg=None, attended_features=None, unattended_features=None):
+    """The end of the stretch: the last `delay` frames are counted as if zero rows followed -- behind the stretch's
+    last rows, when they are given (one launch for both).  After it the calibration refuses pushes until reset();
+    sums() and finish() stay."""
+    self._refuse_flushed()
+    feats = None
+    if self._last_rows('OnlineCCACalibration.flush takes the last rows as eeg AND both feature blocks, or nothing.',
+                       eeg, attended_features, unattended_features):
+      eeg, feats = self._as_rows(eeg, attended_features, unattended_features)
+    return self._advance(eeg, feats, True)
+
+  def _advance(self, eeg, feats, flush):
+    n = 0 if eeg is None else int(eeg.shape[1])
+    if not self._on_device:
+      if eeg is None:
+        eeg, feats = self._no_rows(self.channels), (self._no_rows(self.features),) * 2
+      for i, sess in enumerate(self._host):
+        sess.push(np.asarray(eeg[i], np.float64), np.stack([np.asarray(f[i], np.float64) for f in feats]),
+                  self.decoder._params[i], self.rows_pushed, flush)
+    else:
+      d, bank = self._dev, self.decoder._dev
+      h = d['h']
+      att = unatt = None
+      if n == 0:
+        eeg = None
+      else:
+        up = lambda a: a if hasattr(a, 'is_cuda') else self._upload(h, a)
+        eeg, att, unatt = up(eeg), up(feats[0]), up(feats[1])
+      device.online_ccacalib_push(eeg, att, unatt, bank['mean_x'], bank['rot_x'], bank['mean_y'], bank['rot_y'],
+                                  d['state'], self.rows_pushed, self.pre, self.post, self.pre2, self.post2,
+                                  self.window_size, flush=flush, handle=h)
+    self.rows_pushed += n
+    self.flushed = bool(flush)
+    return self.frames_emitted
+
+  # -- what the state holds ----------------------------------------------------------------------
+  def sums(self):
+    """[S, 9 dims^2 + 20 dims] float64, td_ccacalib_online_sums' order (cca_calibration_layout): sum a, a^2, b1, b1^2,
+    b0, b0^2 over every counted frame, [dims] each (a the EEG view's projection, b1 / b0 the attended / unattended
+    speaker's) | class 0 (unattended): sum_w z [3 dims] and the upper triangle of sum_w z z^T, z = a window's
+    (sum a b | sum a | sum b) | class 1 (attended) | the open window's sum a, b1, a b1, b0, a b0.  A device tensor on
+    the device, else a host array."""
+    if self._dev is None:
+      return np.stack([sess.sums for sess in self._host])
+    return device.online_ccacalib_sums(self._dev['state'], self.dims, handle=self._dev['h'])
+
+  def _raise(self, status):
+    for i, st in enumerate(status):
+      if int(st) != device.CALIB_OK:
+        reason = _CCA_CALIB_REASONS[int(st)] % dict(width=self.window_size, frames=self.frames_emitted,
+                                                    windows=self.windows, dims=self.dims)
+        raise ValueError('OnlineCCACalibration.finish: session %d: %s.' % (i, reason))
+
+  def finish(self):
+    """CalibrationResult(corr [S, 2, 3, dims] {mean_a, mean_b, power} for both speakers, lda [S, dims + 2] {weights,
+    slope, intercept}, dprime [S]) float64 from the sums so far -- what OnlineDecoder.set_cca_statistics takes; device
+    tensors on the device (one launch; the statuses come back in one small copy), else host arrays.  The state is not
+    modified.  ValueError naming the session and the reason: no completed window (train's 'No data for class'), a
+    dim's power that is not finite or not above zero, a pooled scatter that is not positive definite (fewer than
+    dims + 2 windows in all), equal class means along the LDA axis (scaled LDA's 'X0 and X1 ... identical')."""
+    if self._dev is None:
+      outs = [cca_calibration_closed_form(sess.sums, self.frames_emitted, self.window_size, self.dims)
+              for sess in self._host]
+      self._raise([o['status'] for o in outs])
+      stats = [np.stack([o['mean_a'], o['mean_b'], o['power']]) for o in outs]
+      return CalibrationResult(np.stack([np.stack([st, st]) for st in stats]),
+                               np.stack([np.concatenate([o['w'], [o['slope'], o['intercept']]]) for o in outs]),
+                               np.array([o['dprime'] for o in outs], np.float64))
+    out = device.online_ccacalib_finish(self._dev['state'], self.dims, self.frames_emitted, self.window_size,
+                                        handle=self._dev['h'])
+    self._raise(out.status.cpu().numpy())
+    return CalibrationResult(out.corr, out.lda, out.dprime)
+
+  def update_decoder(self, decoder, session=0):
+    """Gives an infer_decoder.CCADecoder the correlator's sums and statistics and the scaled LDA of one session (what
+    Decoder.train leaves in it; the LDA keeps the one axis the scaled transform reads), so that save_parameters
+    writes them.  Returns d'."""
+    from telluride_decoding_amd import scaled_lda
+    if not isinstance(decoder, infer_decoder.CCADecoder):
+      raise ValueError('OnlineCCACalibration.update_decoder takes a CCADecoder, not a %s.' % type(decoder).__name__)
+    if not 0 <= int(session) < self.sessions:
+      raise ValueError('OnlineCCACalibration.update_decoder: session %d of %d.' % (int(session), self.sessions))
+    sums = self.sums()[int(session)]
+    if hasattr(sums, 'cpu'):
+      sums = sums.cpu().numpy()
+    o = cca_calibration_closed_form(sums, self.frames_emitted, self.window_size, self.dims)
+    if o['status'] != device.CALIB_OK:
+      status = [device.CALIB_OK] * self.sessions
+      status[int(session)] = o['status']
+      self._raise(status)
+    w = o['w'].reshape(-1, 1)
+    decoder.model_params = infer_decoder.ModelParamsTuple(
+        infer_decoder.CorrelationParamsTuple(o['count'], o['sum_x'], o['sum_y'], o['sum_x2'], o['sum_y2'],
+                                             o['mean_a'], o['mean_b'], o['power']),
+        scaled_lda.LdaParamsTuple(w, np.zeros_like(w), [1, 2], [o['class_means'][0], o['class_means'][1]],
+                                  float(o['slope']), float(o['intercept'])))
     return float(o['dprime'])
