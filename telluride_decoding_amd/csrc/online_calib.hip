@@ -273,14 +273,6 @@ __global__ __launch_bounds__(kThreads) void online_calib_finish_kernel(const uns
   status[s] = st;
 }
 
-int check_state(td_handle* h, const char* who, int num_sessions, const void* state_dev, int64_t stride,
-                long long need) {
-  TD_REQUIRE(h, num_sessions >= 1 && num_sessions <= 65535, "%s: %d sessions (1 .. 65535)", who, num_sessions);
-  if (!state_dev) return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
-  TD_TRY(check_state_stride(h, who, stride, need));
-  return TD_OK;
-}
-
 int check_shape(td_handle* h, const char* who, int c, int pre, int post) {
   TD_REQUIRE(h, c >= 1 && c <= kMaxChannels, "%s: %d channels (1 .. %d)", who, c, kMaxChannels);
   TD_REQUIRE(h, pre >= 0 && post >= 0 && pre + 1 + post <= kMaxLags,

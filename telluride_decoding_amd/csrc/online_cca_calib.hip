@@ -399,14 +399,6 @@ __global__ __launch_bounds__(kFinThreads) void online_ccacalib_finish_kernel(con
   }
 }
 
-int check_state(td_handle* h, const char* who, int num_sessions, const void* state_dev, int64_t stride,
-                long long need) {
-  TD_REQUIRE(h, num_sessions >= 1 && num_sessions <= 65535, "%s: %d sessions (1 .. 65535)", who, num_sessions);
-  if (!state_dev) return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
-  TD_TRY(check_state_stride(h, who, stride, need));
-  return TD_OK;
-}
-
 // The shape checks td_ccacalib_online_state_bytes, td_ccacalib_online_lds_bytes and td_ccacalib_online_push share.
 int check_shape(td_handle* h, const char* who, int c1, int pre1, int post1, int c2, int pre2, int post2, int dims,
                 int width) {

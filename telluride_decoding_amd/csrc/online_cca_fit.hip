@@ -33,19 +33,18 @@
 // pushes with n > 0; a push without rows writes no tail.  No workgroup reads what another writes, no atomics, vector
 // stores only.
 //
-// Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are in DESIGN.md section 39.
+// What this file shares with online_fit.hip -- step(), view_row(), the tiling and a thread's accumulators, the checks
+// of a push -- is online_fit_common.h.  Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are in DESIGN.md
+// section 39.
 #include <algorithm>
 #include <cmath>
 
-#include "td_common.h"
-
 #pragma clang fp contract(off)
+
+#include "online_fit_common.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 64;
-constexpr int kPass = 32;                      // frames staged per pass: 2 x 32 x 64 x 8 = 32 KiB of LDS
 constexpr int kMaxChannels = TD_ONLINE_CCAFIT_MAX_CHANNELS;
 constexpr int kMaxFeatures = TD_ONLINE_CCAFIT_MAX_FEATURES;
 constexpr int kMaxLags = TD_ONLINE_CCAFIT_MAX_LAGS;
@@ -85,25 +84,13 @@ int ccafit_shape(td_handle* h, const char* who, int c1, int pre1, int post1, int
   s->c1 = c1; s->pre1 = pre1; s->post1 = post1; s->c2 = c2; s->pre2 = pre2; s->post2 = post2;
   s->post = std::max(post1, post2);
   s->k1 = k1; s->k2 = k2; s->n = k1 + k2 + 1;
-  s->tiles = (s->n + kTile - 1) / kTile;
+  s->tiles = tiles_of(s->n);
   s->tl1 = pre1 + s->post; s->tl2 = pre2 + s->post;
   s->off_tail = 2LL * s->n * s->n;
   s->off_ftail = (long long)s->tl1 * c1;
   s->tail_floats = s->off_ftail + (long long)s->tl2 * c2;
   s->bytes = td_round_up(4 * (s->off_tail + 2 * s->tail_floats), 8);
   return TD_OK;
-}
-
-// acc <- acc g + a b, in the rounding the header states.  The unfused form is written with plain operators under this
-// file's `fp contract(off)` (the toolchain's __dmul_rn / __dadd_rn may be fused again once inlined: online_fit.hip).
-template <bool kForget>
-__device__ __forceinline__ double step(double acc, double a, double b, double g) {
-  if (kForget) {
-    const double scaled = acc * g;             // rounded
-    const double p = a * b;                    // exact: float32 x float32
-    return scaled + p;                         // rounded
-  }
-  return __fma_rn(a, b, acc);
 }
 
 // What a thread stages: joint column -> the rows of one channel of one view, the ones column, or nothing.
@@ -132,17 +119,6 @@ __device__ __forceinline__ Column resolve(const CcaFitShape& sh, int kk, const f
     col.shift = lag - sh.pre2; col.ch = kq - lag * sh.c2;
   }
   return col;
-}
-
-// Row r of a view for a launch that has `before` rows behind it and `after` with its own: the push, the tail (slot j
-// = row before - tl + j), zero before the recording and behind a flushed end.  (An emitted frame never reaches below
-// the tail: f >= before - post, so r >= before - post - pre_v.)
-__device__ __forceinline__ float view_row(const float* src, long long ld, const float* tail, int c, int tl, int ch,
-                                          long long r, long long before, long long after) {
-  if (r >= after || r < 0) return 0.0f;
-  if (r >= before) return src[(r - before) * ld + ch];
-  if (r >= before - tl) return tail[(r - (before - tl)) * c + ch];
-  return 0.0f;
 }
 
 // grid (work tiles + the tail workgroup, sessions)
@@ -223,7 +199,6 @@ __global__ void __launch_bounds__(kThreads) online_ccafit_kernel(CcaFitParams p)
         for (int w = 0; w < 4; ++w) acc[u][w] = step<kForget>(acc[u][w], a[u], b[w], g);
     }
   }
-
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
     const int i = ti * kTile + ty + 16 * a;
@@ -233,11 +208,6 @@ __global__ void __launch_bounds__(kThreads) online_ccafit_kernel(CcaFitParams p)
       if (i < sh.n && j < sh.n) M[(long long)i * sh.n + j] = acc[a][b];
     }
   }
-}
-
-// M as stored (upper tiles only) read as the symmetric matrix it stands for
-__device__ __forceinline__ double sym_at(const double* M, int n, int i, int j) {
-  return (i / kTile <= j / kTile) ? M[(long long)i * n + j] : M[(long long)j * n + i];
 }
 
 // grid (blocks, sessions): xtx [S][k1 + 1][k1 + 1] (the ones row and column last), x2tx2 [S][k2][k2],
@@ -265,12 +235,6 @@ __global__ void __launch_bounds__(kThreads) online_ccafit_moments_kernel(const c
       if (sum2) sum2[(long long)s * k2 + r] = sym_at(M, n, k1 + (int)r, n - 1);
     }
   }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
 }
 
 // One view's part of the fitted stretch's statistics for column d of the float32 model: with m = sums / count,
@@ -339,20 +303,6 @@ __global__ void __launch_bounds__(kThreads) online_ccafit_corr_kernel(const doub
   }
 }
 
-int check_state(td_handle* h, const char* who, int num_sessions, const void* state_dev, int64_t stride,
-                const CcaFitShape& sh) {
-  TD_REQUIRE(h, num_sessions >= 1 && num_sessions <= 65535, "%s: %d sessions (1 .. 65535)", who, num_sessions);
-  if (!state_dev) return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
-  TD_REQUIRE(h, stride >= sh.bytes && stride % 8 == 0,
-             "%s: a state stride of %lld bytes (a multiple of 8, at least %lld)", who, (long long)stride, sh.bytes);
-  return TD_OK;
-}
-
-unsigned blocks_for(long long elements) {
-  const long long b = td_ceil_div(elements, kThreads * 4);
-  return (unsigned)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
-
 int launch_moments(td_handle* h, int num_sessions, const char* state, long long stride, const CcaFitShape& sh,
                    double* xtx, double* x2tx2, double* xtx2, double* sum2) {
   const long long per = (long long)(sh.k1 + 1) * (sh.k1 + 1) + (long long)sh.k2 * (sh.k1 + sh.k2 + 1);
@@ -383,30 +333,19 @@ int td_ccafit_online_push(td_handle* h, int num_sessions, const float* eeg_dev, 
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "%s: handle is NULL", who);
   CcaFitShape sh;
   TD_TRY(ccafit_shape(h, who, c1, pre1, post1, c2, pre2, post2, &sh));
-  TD_REQUIRE(h, n >= 0 && n <= TD_ONLINE_MAX_PUSH, "%s: %lld rows in one push (0 .. %d)", who, (long long)n,
-             TD_ONLINE_MAX_PUSH);
-  TD_REQUIRE(h, forget > 0.0 && forget <= 1.0, "%s: a forgetting factor of %g (0 < g <= 1)", who, forget);
-  TD_REQUIRE(h, frames_before >= 0 && pushes_before >= 0, "%s: %lld frames and %lld pushes before", who,
-             (long long)frames_before, (long long)pushes_before);
-  TD_TRY(check_state(h, who, num_sessions, state_dev, state_session_stride, sh));
-  if (n > 0 && (!eeg_dev || !feat_dev)) return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
-  TD_REQUIRE(h, n == 0 || (ld_eeg >= c1 && ld_feat >= c2),
-             "%s: a row stride below a row (%lld for %d channels, %lld for %d features)", who, (long long)ld_eeg, c1,
-             (long long)ld_feat, c2);
-  TD_REQUIRE(h, n == 0 || num_sessions == 1 || (eeg_session_stride >= c1 && feat_session_stride >= c2),
-             "%s: a session stride below a row", who);
-  const long long after = frames_before + n;
-  const long long e0 = frames_before > sh.post ? frames_before - sh.post : 0;
-  const long long e1 = flush ? after : (after > sh.post ? after - sh.post : 0);
-  const long long emitted = e1 > e0 ? e1 - e0 : 0;
+  TD_TRY(check_fit_push(h, who, num_sessions, eeg_dev, ld_eeg, eeg_session_stride, c1, feat_dev, ld_feat,
+                        feat_session_stride, c2, "features", n, frames_before, pushes_before, forget, state_dev,
+                        state_session_stride, sh.bytes));
+  const OnlinePlan pl = plan_push(frames_before, n, sh.post, 1, 1, flush);
+  const long long emitted = pl.emitted_after - pl.emitted_before;
   if (n == 0 && emitted == 0) return TD_OK;
 
   CcaFitParams p;
   memset(&p, 0, sizeof(p));
   p.eeg = eeg_dev; p.ld_e = ld_eeg; p.ss_e = num_sessions > 1 ? eeg_session_stride : 0;
   p.feat = feat_dev; p.ld_f = ld_feat; p.ss_f = num_sessions > 1 ? feat_session_stride : 0;
-  p.n = n; p.frames_before = frames_before; p.e0 = e0; p.emitted = emitted;
-  p.work_tiles = emitted > 0 ? sh.tiles * (sh.tiles + 1) / 2 : 0;
+  p.n = n; p.frames_before = frames_before; p.e0 = pl.emitted_before; p.emitted = emitted;
+  p.work_tiles = emitted > 0 ? upper_tiles(sh.tiles) : 0;
   p.live = (int)(pushes_before & 1);
   p.g = forget;
   p.state = reinterpret_cast<char*>(state_dev); p.state_ss = state_session_stride;
@@ -427,7 +366,7 @@ int td_ccafit_online_moments(td_handle* h, int num_sessions, const void* state_d
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "%s: handle is NULL", who);
   CcaFitShape sh;
   TD_TRY(ccafit_shape(h, who, c1, pre1, post1, c2, pre2, post2, &sh));
-  TD_TRY(check_state(h, who, num_sessions, state_dev, state_session_stride, sh));
+  TD_TRY(check_state(h, who, num_sessions, state_dev, state_session_stride, sh.bytes));
   if (!xtx_dev && !x2tx2_dev && !xtx2_dev && !sum2_dev) return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
   return launch_moments(h, num_sessions, reinterpret_cast<const char*>(state_dev), state_session_stride, sh, xtx_dev,
                         x2tx2_dev, xtx2_dev, sum2_dev);
@@ -442,7 +381,7 @@ int td_ccafit_online_solve(td_handle* h, int num_sessions, const void* state_dev
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "%s: handle is NULL", who);
   CcaFitShape sh;
   TD_TRY(ccafit_shape(h, who, c1, pre1, post1, c2, pre2, post2, &sh));
-  TD_TRY(check_state(h, who, num_sessions, state_dev, state_session_stride, sh));
+  TD_TRY(check_state(h, who, num_sessions, state_dev, state_session_stride, sh.bytes));
   if (!lambdas_host || !rot_x_dev || !rot_y_dev || !mean_x_dev || !mean_y_dev || !e_dev || !corr_dev)
     return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
   TD_REQUIRE(h, n_lambda >= 1, "%s: %d lambdas (at least 1)", who, n_lambda);

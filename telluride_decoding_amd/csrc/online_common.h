@@ -1,12 +1,14 @@
 // What the online push kernels share (online.hip, online_cca.hip, online_dnn.hip, online_calib.hip and, through
 // online_cca_common.h, online_cca_calib.hip): the state block's layout, the plan of a push, and the blocks of a push
 // kernel that every session repeats -- stage, (predict: each file's own, the FIR prediction here for the two files
-// that use it), score, windows, tails.  The host interface is td_common.h.  online_fit.hip, online_pre.hip and
-// online_audio.hip carry other state and do not use this.
+// that use it), score, windows, tails.  The host interface is td_common.h.  online_fit.hip and online_cca_fit.hip
+// take, through online_fit_common.h, the plan of a push, the wave sum and the host checks of the strides and the
+// state; their moments and double-buffered tails are their own.  online_pre.hip and online_audio.hip carry other
+// state and do not use this.
 //
 // Every block here is under the family's promise: any cut of a recording into pushes gives the bytes of one push.
-// online_calib.hip and online_cca_calib.hip include this under a file-level `#pragma clang fp contract(off)`, the
-// other files under the default (on), so nothing here may depend on the contraction mode at the include point: where
+// The calibration and the fit files include this under a file-level `#pragma clang fp contract(off)`, the other
+// files under the default (on), so nothing here may depend on the contraction mode at the include point: where
 // a fused operation is the contract it is an explicit fmaf / fma, and nowhere else does a product feed an add or a
 // subtract in one expression (no bare a * b + c).  Keep it so when adding to this file.
 #pragma once
@@ -295,6 +297,16 @@ inline int check_fir_strides(td_handle* h, const char* who, long long w_ss, long
 inline int check_state_stride(td_handle* h, const char* who, long long stride, long long need) {
   TD_REQUIRE(h, stride >= need && stride % 8 == 0, "%s: a state stride of %lld bytes (a multiple of 8, at least %lld)",
              who, stride, need);
+  return TD_OK;
+}
+
+// A bank's state as the training stages take it (the fits and the calibrations): the session count, the pointer,
+// the stride against the `need` bytes of one block.
+inline int check_state(td_handle* h, const char* who, int num_sessions, const void* state_dev, long long stride,
+                       long long need) {
+  TD_REQUIRE(h, num_sessions >= 1 && num_sessions <= 65535, "%s: %d sessions (1 .. 65535)", who, num_sessions);
+  if (!state_dev) return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
+  TD_TRY(check_state_stride(h, who, stride, need));
   return TD_OK;
 }
 

@@ -30,18 +30,17 @@
 // the other one.  The host counts the pushes with n > 0; a push without rows writes no tail.  No workgroup reads
 // what another writes, no atomics, vector stores only.
 //
-// Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are in DESIGN.md section 34.
+// What this file shares with online_cca_fit.hip -- step(), view_row(), the tiling and a thread's accumulators, the
+// checks of a push -- is online_fit_common.h.  Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are in
+// DESIGN.md section 34.
 #include <cmath>
-
-#include "td_common.h"
 
 #pragma clang fp contract(off)
 
+#include "online_fit_common.h"
+
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kTile = 64;
-constexpr int kPass = 32;                      // frames staged per pass: 2 x 32 x 64 x 8 = 32 KiB of LDS
 constexpr int kMaxChannels = TD_ONLINE_FIT_MAX_CHANNELS;
 constexpr int kMaxLags = TD_ONLINE_FIT_MAX_LAGS;
 constexpr int kMaxK = TD_ONLINE_FIT_MAX_K;
@@ -74,26 +73,13 @@ int fit_shape(td_handle* h, const char* who, int c, int pre, int post, int d, Fi
              kMaxK);
   TD_REQUIRE(h, d >= 1 && d <= kMaxOutputs, "%s: %d outputs (1 .. %d)", who, d, kMaxOutputs);
   s->c = c; s->pre = pre; s->post = post; s->d = d; s->k = k; s->n1 = k + 1;
-  s->tiles = (k + 1 + kTile - 1) / kTile;
+  s->tiles = tiles_of(k + 1);
   s->off_b = (long long)s->n1 * s->n1;
   s->off_tail = 2 * (s->off_b + (long long)s->n1 * d);
   s->off_ttail = (long long)(pre + post) * c;
   s->tail_floats = s->off_ttail + (long long)post * d;
   s->bytes = td_round_up(4 * (s->off_tail + 2 * s->tail_floats), 8);
   return TD_OK;
-}
-
-// acc <- acc g + a b, in the rounding the header states.  The unfused form is written with plain operators under this
-// file's `fp contract(off)`: the toolchain's __dmul_rn / __dadd_rn are `x * y` / `x + y` in a header compiled with the
-// default contraction, so inlined they may be fused again -- into fma(acc, g, a b), ONE rounding (seen on the B tiles).
-template <bool kForget>
-__device__ __forceinline__ double step(double acc, double a, double b, double g) {
-  if (kForget) {
-    const double scaled = acc * g;             // rounded
-    const double p = a * b;                    // exact: float32 x float32
-    return scaled + p;                         // rounded
-  }
-  return __fma_rn(a, b, acc);
 }
 
 // grid (work tiles + the tail workgroup, sessions)
@@ -250,11 +236,6 @@ __global__ void __launch_bounds__(kThreads) online_fit_kernel(FitParams p) {
   }
 }
 
-// A as stored (upper tiles only) read as the symmetric matrix it stands for
-__device__ __forceinline__ double sym_at(const double* A, int n1, int i, int j) {
-  return (i / kTile <= j / kTile) ? A[(long long)i * n1 + j] : A[(long long)j * n1 + i];
-}
-
 // grid (blocks, sessions): xtx [S][n1][n1], xty [S][n1][d]
 __global__ void __launch_bounds__(kThreads) online_fit_moments_kernel(const char* state, long long state_ss,
                                                                       FitShape sh, double* xtx, double* xty) {
@@ -302,20 +283,6 @@ __global__ void __launch_bounds__(kThreads) online_fit_emit_kernel(const double*
   }
 }
 
-int check_state(td_handle* h, const char* who, int num_sessions, const void* state_dev, int64_t stride,
-                const FitShape& sh) {
-  TD_REQUIRE(h, num_sessions >= 1 && num_sessions <= 65535, "%s: %d sessions (1 .. 65535)", who, num_sessions);
-  if (!state_dev) return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
-  TD_REQUIRE(h, stride >= sh.bytes && stride % 8 == 0,
-             "%s: a state stride of %lld bytes (a multiple of 8, at least %lld)", who, (long long)stride, sh.bytes);
-  return TD_OK;
-}
-
-unsigned blocks_for(long long elements) {
-  const long long b = td_ceil_div(elements, kThreads * 4);
-  return (unsigned)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
-
 }  // namespace
 
 extern "C" {
@@ -336,30 +303,19 @@ int td_fit_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_fit_online_push: handle is NULL");
   FitShape sh;
   TD_TRY(fit_shape(h, "td_fit_online_push", c, pre, post, d, &sh));
-  TD_REQUIRE(h, n >= 0 && n <= TD_ONLINE_MAX_PUSH, "td_fit_online_push: %lld rows in one push (0 .. %d)",
-             (long long)n, TD_ONLINE_MAX_PUSH);
-  TD_REQUIRE(h, forget > 0.0 && forget <= 1.0, "td_fit_online_push: a forgetting factor of %g (0 < g <= 1)", forget);
-  TD_REQUIRE(h, frames_before >= 0 && pushes_before >= 0, "td_fit_online_push: %lld frames and %lld pushes before",
-             (long long)frames_before, (long long)pushes_before);
-  TD_TRY(check_state(h, "td_fit_online_push", num_sessions, state_dev, state_session_stride, sh));
-  if (n > 0 && (!eeg_dev || !target_dev)) return td_fail(h, TD_ERR_INVALID, "td_fit_online_push: NULL argument");
-  TD_REQUIRE(h, n == 0 || (ld_eeg >= c && ld_target >= d),
-             "td_fit_online_push: a row stride below a row (%lld for %d channels, %lld for %d outputs)",
-             (long long)ld_eeg, c, (long long)ld_target, d);
-  TD_REQUIRE(h, n == 0 || num_sessions == 1 || (eeg_session_stride >= c && target_session_stride >= d),
-             "td_fit_online_push: a session stride below a row");
-  const long long after = frames_before + n;
-  const long long e0 = frames_before > post ? frames_before - post : 0;
-  const long long e1 = flush ? after : (after > post ? after - post : 0);
-  const long long emitted = e1 > e0 ? e1 - e0 : 0;
+  TD_TRY(check_fit_push(h, "td_fit_online_push", num_sessions, eeg_dev, ld_eeg, eeg_session_stride, c, target_dev,
+                        ld_target, target_session_stride, d, "outputs", n, frames_before, pushes_before, forget,
+                        state_dev, state_session_stride, sh.bytes));
+  const OnlinePlan pl = plan_push(frames_before, n, post, 1, 1, flush);
+  const long long emitted = pl.emitted_after - pl.emitted_before;
   if (n == 0 && emitted == 0) return TD_OK;
 
   FitParams p;
   memset(&p, 0, sizeof(p));
   p.eeg = eeg_dev; p.ld_e = ld_eeg; p.ss_e = num_sessions > 1 ? eeg_session_stride : 0;
   p.tgt = target_dev; p.ld_t = ld_target; p.ss_t = num_sessions > 1 ? target_session_stride : 0;
-  p.n = n; p.frames_before = frames_before; p.e0 = e0; p.emitted = emitted;
-  p.a_tiles = sh.tiles * (sh.tiles + 1) / 2;
+  p.n = n; p.frames_before = frames_before; p.e0 = pl.emitted_before; p.emitted = emitted;
+  p.a_tiles = upper_tiles(sh.tiles);
   p.work_tiles = emitted > 0 ? p.a_tiles + sh.tiles : 0;
   p.live = (int)(pushes_before & 1);
   p.g = forget;
@@ -379,7 +335,7 @@ int td_fit_online_moments(td_handle* h, int num_sessions, const void* state_dev,
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_fit_online_moments: handle is NULL");
   FitShape sh;
   TD_TRY(fit_shape(h, "td_fit_online_moments", c, pre, post, d, &sh));
-  TD_TRY(check_state(h, "td_fit_online_moments", num_sessions, state_dev, state_session_stride, sh));
+  TD_TRY(check_state(h, "td_fit_online_moments", num_sessions, state_dev, state_session_stride, sh.bytes));
   if (!xtx_dev && !xty_dev) return td_fail(h, TD_ERR_INVALID, "td_fit_online_moments: NULL argument");
   const long long per = (long long)sh.n1 * (sh.n1 + d);
   hipLaunchKernelGGL(online_fit_moments_kernel, dim3(blocks_for(per), (unsigned)num_sessions), dim3(kThreads), 0,
@@ -395,7 +351,7 @@ int td_fit_online_solve(td_handle* h, int num_sessions, const void* state_dev, i
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_fit_online_solve: handle is NULL");
   FitShape sh;
   TD_TRY(fit_shape(h, "td_fit_online_solve", c, pre, post, d, &sh));
-  TD_TRY(check_state(h, "td_fit_online_solve", num_sessions, state_dev, state_session_stride, sh));
+  TD_TRY(check_state(h, "td_fit_online_solve", num_sessions, state_dev, state_session_stride, sh.bytes));
   if (!lambdas_host || !w_dev || !b_dev) return td_fail(h, TD_ERR_INVALID, "td_fit_online_solve: NULL argument");
   TD_REQUIRE(h, n_lambda >= 1 && (long long)n_lambda * num_sessions <= 65535,
              "td_fit_online_solve: %d lambdas for %d sessions (1 .. 65535 systems)", n_lambda, num_sessions);

@@ -1852,6 +1852,35 @@ def _check_fit_state(who, h, state):
   return sessions, _state_stride(state, sessions)
 
 
+def _moments_push(who, push, words, shape, eeg, side, widths, state, frames_before, pushes_before, flush, forget,
+                  handle):
+  """What online_fit_push and online_ccafit_push are: the checks of the rows beside the EEG (`side`), in their order,
+  and the launch.  words: (side's argument name, what the messages call it, the same with its article, what a flush
+  without rows needs); widths: (c, c2) as given, None where not; shape(c, c2): the library's shape arguments."""
+  h = handle or default_handle()
+  torch = _torch()
+  name, noun, the_noun, needs = words
+  sessions, stride = _check_fit_state(who, h, state)
+  c, c2 = widths
+  n = 0 if eeg is None else int(eeg.shape[1])
+  if eeg is not None:
+    if eeg.dim() != 3 or side is None or side.dim() != 3 or int(eeg.shape[0]) != sessions or \
+        tuple(side.shape[:2]) != (sessions, n):
+      raise ValueError('%s: eeg of %s and %s of %s for %d sessions' %
+                       (who, tuple(eeg.shape), noun, None if side is None else tuple(side.shape), sessions))
+    c, c2 = int(eeg.shape[2]), int(side.shape[2])
+    _check_tensors(who, h, (('eeg', eeg, torch.float32), (name, side, torch.float32)), short=True)
+    if n > 0 and (eeg.stride(2) != 1 and c > 1 or side.stride(2) != 1 and c2 > 1):
+      raise ValueError('%s: the columns of eeg and %s must be contiguous' % (who, the_noun))
+  if c is None or c2 is None:
+    raise ValueError('%s: a flush without rows needs %s' % (who, needs))
+  c, c2 = int(c), int(c2)
+  h.check(getattr(h.lib, push)(
+      h.ptr, sessions, *_row_block(eeg, n, sessions, c), *_row_block(side, n, sessions, c2), n, *shape(c, c2),
+      int(frames_before), int(pushes_before), 1 if flush else 0, float(forget), _ptr(state), stride))
+  return int(frames_before) + n
+
+
 def online_fit_push(eeg, target, state, frames_before, pushes_before, pre, post, c=None, d=None, flush=False,
                     forget=1.0, handle=None):
   """One push of a bank of online fit sessions, in one launch (td_fit_online_push).
@@ -1860,27 +1889,11 @@ def online_fit_push(eeg, target, state, frames_before, pushes_before, pre, post,
   rows: give c and d); state: uint8 device tensor [S, >= online_fit_state_bytes()] with a row stride that is a
   multiple of 8, updated in place; frames_before: rows pushed so far; pushes_before: pushes WITH rows so far (its
   parity says which tail copy is live).  Returns the rows pushed after the call.  Queued, not waited for."""
-  h = handle or default_handle()
-  torch = _torch()
-  sessions, stride = _check_fit_state('online_fit_push', h, state)
-  n = 0 if eeg is None else int(eeg.shape[1])
-  if eeg is not None:
-    if eeg.dim() != 3 or target is None or target.dim() != 3 or int(eeg.shape[0]) != sessions or \
-        tuple(target.shape[:2]) != (sessions, n):
-      raise ValueError('online_fit_push: eeg of %s and target of %s for %d sessions' %
-                       (tuple(eeg.shape), None if target is None else tuple(target.shape), sessions))
-    c, d = int(eeg.shape[2]), int(target.shape[2])
-    _check_tensors('online_fit_push', h, (('eeg', eeg, torch.float32), ('target', target, torch.float32)), short=True)
-    if n > 0 and (eeg.stride(2) != 1 and c > 1 or target.stride(2) != 1 and d > 1):
-      raise ValueError('online_fit_push: the columns of eeg and target must be contiguous')
-  if c is None or d is None:
-    raise ValueError('online_fit_push: a flush without rows needs the channel count c and the output count d')
-  c, d = int(c), int(d)
-  h.check(h.lib.td_fit_online_push(
-      h.ptr, sessions, *_row_block(eeg, n, sessions, c), *_row_block(target, n, sessions, d),
-      n, c, int(pre), int(post), d, int(frames_before), int(pushes_before), 1 if flush else 0, float(forget),
-      _ptr(state), stride))
-  return int(frames_before) + n
+  return _moments_push(
+      'online_fit_push', 'td_fit_online_push',
+      ('target', 'target', 'target', 'the channel count c and the output count d'),
+      lambda c, d: (c, int(pre), int(post), d), eeg, target, (c, d), state, frames_before, pushes_before, flush, forget,
+      handle)
 
 
 def online_fit_moments(state, c, pre, post, d, handle=None):
@@ -1949,27 +1962,11 @@ def online_ccafit_push(eeg, feat, state, frames_before, pushes_before, pre1, pos
   rows: give c1 and c2); state: uint8 device tensor [S, >= online_ccafit_state_bytes()] with a row stride that is a
   multiple of 8, updated in place; frames_before: rows pushed so far; pushes_before: pushes WITH rows so far (its
   parity says which tail copy is live).  Returns the rows pushed after the call.  Queued, not waited for."""
-  h = handle or default_handle()
-  torch = _torch()
-  sessions, stride = _check_fit_state('online_ccafit_push', h, state)
-  n = 0 if eeg is None else int(eeg.shape[1])
-  if eeg is not None:
-    if eeg.dim() != 3 or feat is None or feat.dim() != 3 or int(eeg.shape[0]) != sessions or \
-        tuple(feat.shape[:2]) != (sessions, n):
-      raise ValueError('online_ccafit_push: eeg of %s and features of %s for %d sessions' %
-                       (tuple(eeg.shape), None if feat is None else tuple(feat.shape), sessions))
-    c1, c2 = int(eeg.shape[2]), int(feat.shape[2])
-    _check_tensors('online_ccafit_push', h, (('eeg', eeg, torch.float32), ('feat', feat, torch.float32)), short=True)
-    if n > 0 and (eeg.stride(2) != 1 and c1 > 1 or feat.stride(2) != 1 and c2 > 1):
-      raise ValueError('online_ccafit_push: the columns of eeg and the features must be contiguous')
-  if c1 is None or c2 is None:
-    raise ValueError('online_ccafit_push: a flush without rows needs the channel count c1 and the feature count c2')
-  c1, c2 = int(c1), int(c2)
-  h.check(h.lib.td_ccafit_online_push(
-      h.ptr, sessions, *_row_block(eeg, n, sessions, c1), *_row_block(feat, n, sessions, c2), n,
-      c1, int(pre1), int(post1), c2, int(pre2), int(post2), int(frames_before), int(pushes_before),
-      1 if flush else 0, float(forget), _ptr(state), stride))
-  return int(frames_before) + n
+  return _moments_push(
+      'online_ccafit_push', 'td_ccafit_online_push',
+      ('feat', 'features', 'the features', 'the channel count c1 and the feature count c2'),
+      lambda c1, c2: (c1, int(pre1), int(post1), c2, int(pre2), int(post2)), eeg, feat, (c1, c2), state, frames_before,
+      pushes_before, flush, forget, handle)
 
 
 def online_ccafit_moments(state, c1, pre1, post1, c2, pre2, post2, handle=None):
@@ -2070,15 +2067,35 @@ def online_calib_push(eeg, env, w, b, state, frames_before, pre, post, width, c=
   return int(frames_before) + n
 
 
+def _calib_sums(who, sums, count, dims, state, handle):
+  """What online_calib_sums and online_ccacalib_sums are: [S, count] float64 from the library's `sums`, which takes
+  `dims` (nothing, or the CCA model's columns) behind the state."""
+  h = handle or default_handle()
+  sessions, stride = _check_fit_state(who, h, state)
+  out = h.empty((sessions, count), 'float64')
+  h.check(getattr(h.lib, sums)(h.ptr, sessions, _ptr(state), stride, *dims, _ptr(out)))
+  return out
+
+
+def _calib_finish(who, finish, corr_shape, lda_width, dims, state, frames_emitted, width, handle):
+  """What online_calib_finish and online_ccacalib_finish are: the four outputs and the library's `finish`, which
+  takes `dims` (nothing, or the CCA model's columns) behind the state."""
+  h = handle or default_handle()
+  sessions, stride = _check_fit_state(who, h, state)
+  corr = h.empty((sessions,) + corr_shape, 'float64')
+  lda = h.empty((sessions, lda_width), 'float64')
+  dprime = h.empty((sessions,), 'float64')
+  status = h.empty((sessions,), 'int32')
+  h.check(getattr(h.lib, finish)(h.ptr, sessions, _ptr(state), stride, *dims, int(frames_emitted), int(width),
+                                 _ptr(corr), _ptr(lda), _ptr(dprime), _ptr(status)))
+  return OnlineCalibFinish(corr, lda, dprime, status)
+
+
 def online_calib_sums(state, handle=None):
   """The float64 sums of a bank of online calibration sessions, [S, ONLINE_CALIB_SUMS] on the device, in
   td_calib_online_sums' order: sum p, p^2, a, a^2, u, u^2 | class 0: sum z [3], upper sum z z^T [6] | class 1 | the
   open window's sum p, a, a p, u, u p."""
-  h = handle or default_handle()
-  sessions, stride = _check_fit_state('online_calib_sums', h, state)
-  out = h.empty((sessions, ONLINE_CALIB_SUMS), 'float64')
-  h.check(h.lib.td_calib_online_sums(h.ptr, sessions, _ptr(state), stride, _ptr(out)))
-  return out
+  return _calib_sums('online_calib_sums', 'td_calib_online_sums', ONLINE_CALIB_SUMS, (), state, handle)
 
 
 def online_calib_finish(state, frames_emitted, width, handle=None):
@@ -2086,15 +2103,8 @@ def online_calib_finish(state, frames_emitted, width, handle=None):
   OnlineCalibFinish(corr [S, 2, 3] float64, lda [S, 3] float64 {1, slope, intercept}, dprime [S] float64, status [S]
   int32 -- CALIB_OK, CALIB_NO_WINDOW, CALIB_NO_POWER, CALIB_SAME_MEANS), device tensors.  The state is not modified.
   Queued, not waited for."""
-  h = handle or default_handle()
-  sessions, stride = _check_fit_state('online_calib_finish', h, state)
-  corr = h.empty((sessions, 2, 3), 'float64')
-  lda = h.empty((sessions, 3), 'float64')
-  dprime = h.empty((sessions,), 'float64')
-  status = h.empty((sessions,), 'int32')
-  h.check(h.lib.td_calib_online_finish(h.ptr, sessions, _ptr(state), stride, int(frames_emitted), int(width),
-                                       _ptr(corr), _ptr(lda), _ptr(dprime), _ptr(status)))
-  return OnlineCalibFinish(corr, lda, dprime, status)
+  return _calib_finish('online_calib_finish', 'td_calib_online_finish', (2, 3), 3, (), state, frames_emitted, width,
+                       handle)
 
 
 # ---------------------------------------------------------------- online calibration of a CCA model
@@ -2175,12 +2185,8 @@ def online_ccacalib_sums(state, dims, handle=None):
   """The float64 sums of a bank of online CCA calibration sessions, [S, online_ccacalib_sums_count(dims)] on the
   device, in td_ccacalib_online_sums' order: sum a, a^2, b1, b1^2, b0, b0^2 [dims each] | class 0: sum z [3 dims],
   upper sum z z^T | class 1 | the open window's sum a, b1, a b1, b0, a b0 [dims each]."""
-  h = handle or default_handle()
-  sessions, stride = _check_fit_state('online_ccacalib_sums', h, state)
   count = online_ccacalib_sums_count(dims) if 1 <= int(dims) <= CCA_ONLINE_MAX_DIMS else 1   # (refused by name)
-  out = h.empty((sessions, count), 'float64')
-  h.check(h.lib.td_ccacalib_online_sums(h.ptr, sessions, _ptr(state), stride, int(dims), _ptr(out)))
-  return out
+  return _calib_sums('online_ccacalib_sums', 'td_ccacalib_online_sums', count, (int(dims),), state, handle)
 
 
 def online_ccacalib_finish(state, dims, frames_emitted, width, handle=None):
@@ -2188,16 +2194,9 @@ def online_ccacalib_finish(state, dims, frames_emitted, width, handle=None):
   OnlineCalibFinish(corr [S, 2, 3, dims] float64, lda [S, dims + 2] float64 {w, slope, intercept}, dprime [S] float64,
   status [S] int32 -- CALIB_OK, CALIB_NO_WINDOW, CALIB_NO_POWER, CALIB_SAME_MEANS, CALIB_NOT_POSITIVE), device
   tensors.  The state is not modified.  Queued, not waited for."""
-  h = handle or default_handle()
-  sessions, stride = _check_fit_state('online_ccacalib_finish', h, state)
   d = int(dims) if 1 <= int(dims) <= CCA_ONLINE_MAX_DIMS else 1                               # (refused by name)
-  corr = h.empty((sessions, 2, 3, d), 'float64')
-  lda = h.empty((sessions, d + 2), 'float64')
-  dprime = h.empty((sessions,), 'float64')
-  status = h.empty((sessions,), 'int32')
-  h.check(h.lib.td_ccacalib_online_finish(h.ptr, sessions, _ptr(state), stride, int(dims), int(frames_emitted),
-                                          int(width), _ptr(corr), _ptr(lda), _ptr(dprime), _ptr(status)))
-  return OnlineCalibFinish(corr, lda, dprime, status)
+  return _calib_finish('online_ccacalib_finish', 'td_ccacalib_online_finish', (2, 3, d), d + 2, (int(dims),), state,
+                       frames_emitted, width, handle)
 
 
 # ---------------------------------------------------------------- fully connected regressor / match-mismatch classifier

@@ -320,6 +320,23 @@ def _frame_score(truth, pred, stats, reduction, lda):
   return lda[1] * (v * lda[0]) + lda[2]
 
 
+def _session_rows(tail, rows, post, flush, axis=0):
+  """One stream of a NumPy session's push, its rows along `axis`: (what the push reads -- the old tail, the push and,
+  on a flush, `post` zero rows, so that slot 0 is the tail's first row --, the next tail: the last len(tail) rows of
+  old tail and push)."""
+  both = np.concatenate([tail, rows], axis=axis)
+  cut, pad = [slice(None)] * both.ndim, list(both.shape)
+  cut[axis], pad[axis] = slice(both.shape[axis] - tail.shape[axis], None), post
+  return np.concatenate([both, np.zeros(pad, both.dtype)], axis=axis) if flush else both, both[tuple(cut)]
+
+
+def _session_frames(frames_before, n, post, flush):
+  """(the first frame a push of n rows behind frames_before emits, how many, the slot of the first one's first row in
+  what _session_rows reads) for frames that run `post` rows behind the input."""
+  pl = device.online_plan(frames_before, n, post, 1, 1, flush)
+  return pl.emitted_before, pl.emitted_after - pl.emitted_before, pl.emitted_before - (frames_before - post)
+
+
 class _HostSession(object):
   """One listener's session in NumPy float64: the semantics of td_online_push, for machines without a GPU."""
 
@@ -339,8 +356,8 @@ class _HostSession(object):
     c, pre, post = p['c'], p['pre'], p['post']
     n = eeg.shape[0]
     pl = device.online_plan(frames_before, n, post, self.width, self.hop, flush)
-    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c))] if flush else []))
-    envs = np.concatenate([self.env_tail, env])
+    rows, tail = _session_rows(self.tail, eeg, post, flush)
+    envs, env_tail = _session_rows(self.env_tail, env, post, False)
     emitted = pl.emitted_after - pl.emitted_before
     # frame emitted_before + i reads rows[i0 + i : i0 + i + lags] and envs[i0 + i]: rows[0] is the EEG row
     # frames_before - pre - post, envs[0] the envelope row frames_before - post
@@ -355,9 +372,7 @@ class _HostSession(object):
     frame = np.stack([_frame_score(truth[:, k], pred, p['corr'][k], p['reduction'], p['lda'])
                       for k in (0, 1)], axis=1).reshape(emitted, 2)
     scores, decisions = self._windows(frame, pl)
-    both = np.concatenate([self.tail, eeg])
-    self.tail = both[both.shape[0] - (pre + post):]
-    self.env_tail = envs[envs.shape[0] - post:] if post else envs[:0]
+    self.tail, self.env_tail = tail, env_tail
     return scores, decisions, pred, frame, pl
 
   def _windows(self, frame, pl):
@@ -412,8 +427,8 @@ class _HostCcaSession(_HostSession):
     post = self.delay
     n = eeg.shape[0]
     pl = device.online_plan(frames_before, n, post, self.width, self.hop, flush)
-    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c1))] if flush else []))
-    frows = np.concatenate([self.feat_tail, feat] + ([np.zeros((2, post, c2))] if flush else []), axis=1)
+    rows, tail = _session_rows(self.tail, eeg, post, flush)
+    frows, feat_tail = _session_rows(self.feat_tail, feat, post, flush, axis=1)
     emitted = pl.emitted_after - pl.emitted_before
     # rows[0] is the EEG row frames_before - pre1 - post, frows[:, 0] the feature row frames_before - pre2 -
     # post: frame emitted_before + i reads rows[i0 + i : i0 + i + lags1] and frows[:, i0 + i : i0 + i + lags2]
@@ -425,10 +440,7 @@ class _HostCcaSession(_HostSession):
     frame = np.stack([_cca_frame_score(a, bs[k], p['corr'][k], p['reduction'], p['lda']) for k in (0, 1)],
                      axis=1).reshape(emitted, 2)
     scores, decisions = self._windows(frame, pl)
-    both = np.concatenate([self.tail, eeg])
-    self.tail = both[both.shape[0] - (pre1 + post):]
-    fboth = np.concatenate([self.feat_tail, feat], axis=1)
-    self.feat_tail = fboth[:, fboth.shape[1] - (pre2 + post):]
+    self.tail, self.feat_tail = tail, feat_tail
     return scores, decisions, np.concatenate([a] + bs, axis=1), frame, pl
 
 
@@ -459,8 +471,8 @@ class _HostDnnSession(_HostSession):
     c, pre, post = p['c'], p['pre'], p['post']
     n = eeg.shape[0]
     pl = device.online_plan(frames_before, n, post, self.width, self.hop, flush)
-    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c))] if flush else []))
-    envs = np.concatenate([self.env_tail, env])
+    rows, tail = _session_rows(self.tail, eeg, post, flush)
+    envs, env_tail = _session_rows(self.env_tail, env, post, False)
     emitted = pl.emitted_after - pl.emitted_before
     i0 = pl.emitted_before - (frames_before - post)   # (as _HostSession.push)
     pred = self._predict(rows, i0, emitted)
@@ -468,9 +480,7 @@ class _HostDnnSession(_HostSession):
     frame = np.stack([_frame_score(truth[:, k], pred, p['corr'][k], p['reduction'], p['lda'])
                       for k in (0, 1)], axis=1).reshape(emitted, 2)
     scores, decisions = self._windows(frame, pl)
-    both = np.concatenate([self.tail, eeg])
-    self.tail = both[both.shape[0] - (pre + post):]
-    self.env_tail = envs[envs.shape[0] - post:] if post else envs[:0]
+    self.tail, self.env_tail = tail, env_tail
     return scores, decisions, pred, frame, pl
 
 
@@ -1632,6 +1642,150 @@ class FrameJoin(object):
 MAX_FIT_PUSH = 1048576                     # TD_ONLINE_MAX_PUSH
 
 
+class _TrainingBank(_Bank):
+  """What the four training banks share (OnlineRidgeFit, OnlineCCAFit, OnlineCalibration, OnlineCCACalibration): rows
+  arrive in pushes of any length, the frames counted run `delay` rows behind them until a flush counts the rest, and a
+  push is one device call or one call per NumPy session.  A class gives LAST_ROWS (flush's sentence for some of the
+  last rows), _blocks(*rows) (the arguments of a push as [S, n, .] blocks, the EEG first), _no_blocks() (what the
+  NumPy sessions take for a flush without rows), _session_push(sess, i, blocks, flush) and _device_push(blocks,
+  flush) (blocks None without rows); both read rows_pushed and _pushes as they stood before the push."""
+  LAST_ROWS = None
+
+  def __init__(self, sessions, on_device, delay, handle, state_bytes, host_session):
+    """handle() and state_bytes() are called on the device, host_session() S times off it."""
+    _Bank.__init__(self, sessions, on_device)
+    self.delay = delay
+    if on_device:
+      h = handle()
+      self._dev = dict(h=h, state=self._zero_state(h, state_bytes()))
+    else:
+      self._host = [host_session() for _ in range(sessions)]
+    self.reset()
+
+  def reset(self):
+    """A fresh recording: zero state (a memset), no row pushed."""
+    self.rows_pushed = 0
+    self._pushes = 0                             # pushes with rows: its parity is the fits' live tail copy
+    _Bank.reset(self)
+
+  @property
+  def _counted(self):
+    """The frames counted so far: `delay` behind the rows pushed, all of them after flush()."""
+    return self.rows_pushed if self.flushed else max(0, self.rows_pushed - self.delay)
+
+  def _float32(self, *arrays):
+    """Each of `arrays` (tensors or arrays) as float32 where the bank runs: device tensors, else host arrays."""
+    if not self._on_device and not any(hasattr(a, 'is_cuda') for a in arrays):
+      return [np.asarray(a, np.float32) for a in arrays]
+    torch = device._torch()
+    where = self._dev['h'].device if self._on_device else None
+    out = [(a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a, np.float32))).to(
+        device=where, dtype=torch.float32) for a in arrays]
+    return out if self._on_device else [a.cpu().numpy() for a in out]
+
+  def _push(self, rows, flush):
+    """push(*rows) / flush(*rows): the frames counted after it."""
+    self._refuse_flushed()
+    blocks = None
+    if not flush or self._last_rows(self.LAST_ROWS, *rows):
+      blocks = self._blocks(*rows)
+      if int(blocks[0].shape[1]) > MAX_FIT_PUSH:
+        raise ValueError('%s takes at most %d rows in one push, not %d.' %
+                         (type(self).__name__, MAX_FIT_PUSH, blocks[0].shape[1]))
+    n = 0 if blocks is None else int(blocks[0].shape[1])
+    if self._on_device:
+      self._device_push(blocks if n > 0 else None, flush)
+    else:
+      for i, sess in enumerate(self._host):
+        self._session_push(sess, i, self._no_blocks() if blocks is None else blocks, flush)
+    self.rows_pushed += n
+    if n > 0:
+      self._pushes += 1
+    self.flushed = flush
+    return self._counted
+
+
+class _FitBank(_TrainingBank):
+  """What the two fit banks share: sessions of their own with a forgetting factor, two streams of rows (the EEG and
+  what is fitted to it), moments in float64 at the head of the state and two copies of the streams' tails behind
+  them.  A class gives SHAPES (the sentence for a push of other shapes), and to _setup the streams' widths, the
+  head's length in doubles, the tails' shapes and names in a NumPy session, and its device push, called as
+  device_push(eeg, side, state, rows_pushed, pushes, flush=, forget=, handle=)."""
+  FLUSHED = 'The fit was flushed: reset() starts the next recording.'
+  SHAPES = None
+
+  def _setup(self, num_sessions, forgetting, delay, widths, head_doubles, tails, state_bytes, host_session,
+             device_push):
+    if int(num_sessions) < 1:
+      raise ValueError('%s needs at least one session.' % type(self).__name__)
+    self.forgetting = forgetting
+    self._widths, self._head_doubles, self._tails, self._device_call = widths, head_doubles, tails, device_push
+    _TrainingBank.__init__(self, int(num_sessions), device.gpu_available(), delay, device.default_handle,
+                           state_bytes, host_session)
+
+  frames = _TrainingBank._counted                # the frames counted into the moments so far
+
+  def _to_bank(self, eeg, side):
+    """One session's [n, .] rows as [1, n, .]."""
+    if len(eeg.shape) == 2 and len(side.shape) == 2 and self.sessions == 1:
+      eeg, side = eeg.reshape((1,) + tuple(eeg.shape)), side.reshape((1,) + tuple(side.shape))
+    return eeg, side
+
+  def _blocks(self, eeg, side):
+    """(eeg [S, n, c], side [S, n, c2]) float32: device tensors on the device, else host arrays."""
+    s, (c, c2) = self.sessions, self._widths
+    eeg, side = self._float32(eeg, side)
+    shapes = (tuple(eeg.shape), tuple(side.shape))
+    eeg, side = self._to_bank(eeg, side)
+    n = int(eeg.shape[1]) if len(eeg.shape) == 3 else -1
+    if len(eeg.shape) != 3 or tuple(eeg.shape) != (s, n, c) or tuple(side.shape) != (s, n, c2):
+      raise ValueError(self.SHAPES % ((s, c, c, s, c2, c2) + shapes))
+    return eeg, side
+
+  def _no_blocks(self):
+    return self._no_rows(self._widths[0]), self._no_rows(self._widths[1])
+
+  def _session_push(self, sess, i, blocks, flush):
+    sess.push(blocks[0][i], blocks[1][i], self.rows_pushed, flush)
+
+  def _device_push(self, blocks, flush):
+    d = self._dev
+    eeg, side = blocks or (None, None)
+    if blocks is not None:                       # (the device call takes unit column strides)
+      eeg, side = (t.contiguous() if t.stride(2) != 1 and w > 1 else t for t, w in zip(blocks, self._widths))
+    self._device_call(eeg, side, d['state'], self.rows_pushed, self._pushes, flush=flush, forget=self.forgetting,
+                      handle=d['h'])
+
+  @property
+  def tails(self):
+    """(EEG tail, the other stream's tail) float32, [S, rows, width] each: the live copy -- slot j of a tail of
+    `rows` rows holds row rows_pushed - rows + j, zero before row 0.  The EEG's tail has pre_context + delay rows;
+    the ridge fit's target tail delay rows, the CCA fit's feature tail input2_pre_context + delay.  Device tensors
+    (views) or host arrays."""
+    if self._dev is None:
+      return tuple(np.stack([getattr(sess, name) for sess in self._host]) for name, _, _ in self._tails)
+    floats = self._dev['state'].view(device._torch().float32)
+    (_, r1, c1), (_, r2, c2) = self._tails
+    copy = r1 * c1 + r2 * c2
+    at = 2 * self._head_doubles + (self._pushes & 1) * copy
+    return (floats[:, at:at + r1 * c1].reshape(self.sessions, r1, c1),
+            floats[:, at + r1 * c1:at + copy].reshape(self.sessions, r2, c2))
+
+  def _check_model(self, model, kind, pairs, session):
+    """update_model's refusals: a model of another class, a (name, mine, the model's attribute) that differs, the
+    session; returns the session."""
+    who = '%s.update_model' % type(self).__name__
+    if not isinstance(model, kind):
+      raise ValueError('%s takes a %s, not a %s.' % (who, kind.__name__, type(model).__name__))
+    for name, mine, attribute in pairs:
+      theirs = int(getattr(model, attribute))
+      if theirs != mine:
+        raise ValueError('%s: the model has %s = %d, the fit %d.' % (who, name, theirs, mine))
+    if not 0 <= int(session) < self.sessions:
+      raise ValueError('%s: session %d of %d.' % (who, int(session), self.sessions))
+    return int(session)
+
+
 def _check_fit_shape(who, c, pre, post, d, g):
   """td_fit_online_push's limits, refused by name (the device call repeats them)."""
   if not 1 <= c <= device.ONLINE_FIT_MAX_CHANNELS:
@@ -1665,25 +1819,18 @@ class _HostRidgeFitSession(object):
 
   def push(self, eeg, target, frames_before, flush):
     """eeg [n, c], target [n, d] float32 behind frames_before rows; returns the frames this push emitted."""
-    c, pre, post = self.c, self.pre, self.post
-    lags, tl = pre + 1 + post, pre + post
-    after = frames_before + eeg.shape[0]
+    lags = self.pre + 1 + self.post
     # rows[0] is EEG row frames_before - (pre + post), ys[0] target row frames_before - post
-    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c), np.float32)] if flush else []))
-    ys = np.concatenate([self.target_tail, target])
-    e0 = max(0, frames_before - post)
-    e1 = after if flush else max(0, after - post)
+    rows, self.tail = _session_rows(self.tail, eeg, self.post, flush)
+    ys, self.target_tail = _session_rows(self.target_tail, target, self.post, False)
+    _, emitted, i0 = _session_frames(frames_before, eeg.shape[0], self.post, flush)
     v = np.ones((self.k + 1,), np.float64)
-    for f in range(e0, e1):
-      i = f - frames_before + post
+    for i in range(i0, i0 + emitted):
       v[:self.k] = rows[i:i + lags].reshape(-1)
       y = ys[i].astype(np.float64)
       self.a = self.a * self.g + np.outer(v, v)
       self.b = self.b * self.g + np.outer(v, y)
-    both = np.concatenate([self.tail, eeg])
-    self.tail = np.ascontiguousarray(both[both.shape[0] - tl:])
-    self.target_tail = np.ascontiguousarray(ys[ys.shape[0] - post:]) if post else ys[:0]
-    return max(0, e1 - e0)
+    return emitted
 
   def solve(self, lambdas):
     """(W [n_lambda, K, d], b [n_lambda, d]) float64: np.linalg.solve of the reference's cov_x and cov_xy."""
@@ -1693,7 +1840,7 @@ class _HostRidgeFitSession(object):
     return np.stack([s[:self.k] for s in sols]), np.stack([s[self.k] for s in sols])
 
 
-class OnlineRidgeFit(_Bank):
+class OnlineRidgeFit(_FitBank):
   """The online chain's training stage: a bank of S sessions that take (eeg, target) rows in pushes of any length
   and keep the EXACT moments of the lagged ridge regression -- [x~ | 1]^T [x~ | 1] and [x~ | 1]^T y in float64, the
   lagged vector that of brain_data's context, the trailing 1 the reference's ones column -- in ONE
@@ -1717,122 +1864,47 @@ class OnlineRidgeFit(_Bank):
   Refused by name: more than 128 channels, more than 64 lags, more than 2048 lagged inputs, outputs outside
   1 .. 8, a push of more than 1048576 rows, a forgetting factor outside (0, 1].  Without a GPU the same object
   runs a NumPy session of the same semantics, bit for bit (np.linalg.solve for the weights)."""
-  FLUSHED = 'The fit was flushed: reset() starts the next recording.'
+  LAST_ROWS = 'OnlineRidgeFit.flush takes the last rows as eeg AND target, or neither.'
+  SHAPES = ('A push is eeg [%d, n, %d] (or [n, %d] for one session) with a target [%d, n, %d] (or [n, %d] '
+            '/ [n] for one session), not eeg %s with a target %s.')
 
   def __init__(self, channels, pre_context, post_context, outputs=1, num_sessions=1, forgetting=1.0):
     c, pre, post, d = int(channels), int(pre_context), int(post_context), int(outputs)
     g = float(forgetting)
     _check_fit_shape('OnlineRidgeFit', c, pre, post, d, g)
-    if int(num_sessions) < 1:
-      raise ValueError('OnlineRidgeFit needs at least one session.')
     self.channels, self.pre, self.post, self.outputs = c, pre, post, d
-    self.forgetting = g
     self.lags = pre + 1 + post
     self.inputs = self.lags * c                  # K
-    self.delay = post
-    _Bank.__init__(self, int(num_sessions), device.gpu_available())
-    if self._on_device:
-      h = device.default_handle()
-      self._dev = dict(h=h, state=self._zero_state(h, device.online_fit_state_bytes(c, pre, post, d)))
-    else:
-      self._host = [_HostRidgeFitSession(c, pre, post, d, g) for _ in range(self.sessions)]
-    self.reset()
-
-  def reset(self):
-    """A fresh recording and empty moments: zero state (a memset), no row pushed."""
-    self.rows_pushed = self.frames = 0           # frames: the frames counted into the moments so far
-    self._pushes = 0                             # pushes with rows: its parity is the live tail copy
-    _Bank.reset(self)
+    n1 = self.inputs + 1
+    self._setup(num_sessions, g, post, (c, d), n1 * n1 + n1 * d,
+                (('tail', pre + post, c), ('target_tail', post, d)),
+                lambda: device.online_fit_state_bytes(c, pre, post, d),
+                lambda: _HostRidgeFitSession(c, pre, post, d, g),
+                lambda *args, **kwargs: device.online_fit_push(*args, pre, post, c=c, d=d, **kwargs))
 
   # -- pushes ------------------------------------------------------------------------------------
-  def _as_bank(self, eeg, target):
-    """(eeg [S, n, c], target [S, n, d]) float32: device tensors on the device, else host arrays."""
-    s, c, d = self.sessions, self.channels, self.outputs
-    if any(hasattr(a, 'is_cuda') for a in (eeg, target)):
-      torch = device._torch()
-      dev = self._dev['h'].device if self._on_device else None
-      conv = lambda a: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a))).to(
-          device=dev, dtype=torch.float32)
-      eeg, target = conv(eeg), conv(target)
-      if not self._on_device:
-        eeg, target = eeg.cpu().numpy(), target.cpu().numpy()
-    else:
-      eeg, target = np.asarray(eeg, np.float32), np.asarray(target, np.float32)
-    shapes = (tuple(eeg.shape), tuple(target.shape))
-    if len(eeg.shape) == 2 and s == 1:
+  def _to_bank(self, eeg, target):
+    """One session's [n, c] rows as [1, n, c]; a target [n] / [S, n] of one output as [S, n, 1]."""
+    if len(eeg.shape) == 2 and self.sessions == 1:
       eeg = eeg.reshape((1,) + tuple(eeg.shape))
       if len(target.shape) <= 2:
         target = target.reshape((1,) + tuple(target.shape))       # [1, n] or [1, n, d]
-    if len(target.shape) == 2 and d == 1:
+    if len(target.shape) == 2 and self.outputs == 1:
       target = target.reshape(tuple(target.shape) + (1,))         # [S, n] -> [S, n, 1]
-    n = int(eeg.shape[1]) if len(eeg.shape) == 3 else -1
-    if len(eeg.shape) != 3 or tuple(eeg.shape) != (s, n, c) or tuple(target.shape) != (s, n, d):
-      raise ValueError('A push is eeg [%d, n, %d] (or [n, %d] for one session) with a target [%d, n, %d] (or [n, %d] '
-                       '/ [n] for one session), not eeg %s with a target %s.' % ((s, c, c, s, d, d) + shapes))
-    if n > MAX_FIT_PUSH:
-      raise ValueError('OnlineRidgeFit takes at most %d rows in one push, not %d.' % (MAX_FIT_PUSH, n))
     return eeg, target
 
   def push(self, eeg, target):
     """The next n rows of every session: eeg [n, c] / [S, n, c] and target [n] / [n, d] / [S, n, d], float32 device
     tensors (read where they are, no host copy) or arrays; n may be 0.  Returns the frames counted so far."""
-    self._refuse_flushed()
-    eeg, target = self._as_bank(eeg, target)
-    return self._advance(eeg, target, False)
+    return self._push((eeg, target), False)
 
   def flush(self, eeg=None, target=None):
     """The end of the recording: the last post_context frames are counted as if zero rows followed -- behind the
     recording's last rows, when they are given (one launch for both).  After it the fit refuses pushes until
     reset(); moments() and solve() stay."""
-    self._refuse_flushed()
-    if self._last_rows('OnlineRidgeFit.flush takes the last rows as eeg AND target, or neither.', eeg, target):
-      eeg, target = self._as_bank(eeg, target)
-    frames = self._advance(eeg, target, True)
-    self.flushed = True
-    return frames
-
-  def _advance(self, eeg, target, flush):
-    n = 0 if eeg is None else int(eeg.shape[1])
-    after = self.rows_pushed + n
-    counted = after if flush else max(0, after - self.post)
-    if not self._on_device:
-      if eeg is None:
-        eeg, target = self._no_rows(self.channels), self._no_rows(self.outputs)
-      for i, sess in enumerate(self._host):
-        sess.push(eeg[i], target[i], self.rows_pushed, flush)
-    else:
-      d = self._dev
-      if n == 0:
-        eeg = target = None
-      else:
-        if eeg.stride(2) != 1 and self.channels > 1:
-          eeg = eeg.contiguous()
-        if target.stride(2) != 1 and self.outputs > 1:
-          target = target.contiguous()
-      device.online_fit_push(eeg, target, d['state'], self.rows_pushed, self._pushes, self.pre, self.post,
-                             c=self.channels, d=self.outputs, flush=flush, forget=self.forgetting, handle=d['h'])
-    self.rows_pushed = after
-    self.frames = counted
-    if n > 0:
-      self._pushes += 1
-    return self.frames
+    return self._push((eeg, target), True)
 
   # -- what the state holds ----------------------------------------------------------------------
-  @property
-  def tails(self):
-    """(EEG tail [S, pre + post, c], target tail [S, post, d]) float32: the live copy -- slot j holds row
-    rows_pushed - (pre + post) + j (target: rows_pushed - post + j), zero before row 0.  Device tensors (views) or
-    host arrays."""
-    s, c, d, tl = self.sessions, self.channels, self.outputs, self.pre + self.post
-    if self._dev is None:
-      return (np.stack([sess.tail for sess in self._host]), np.stack([sess.target_tail for sess in self._host]))
-    n1 = self.inputs + 1
-    floats = self._dev['state'].view(device._torch().float32)
-    copy = tl * c + self.post * d
-    at = 2 * (n1 * n1 + n1 * d) + (self._pushes & 1) * copy
-    return (floats[:, at:at + tl * c].reshape(s, tl, c),
-            floats[:, at + tl * c:at + copy].reshape(s, self.post, d))
-
   def moments(self):
     """(xtx [S, K + 1, K + 1], xty [S, K + 1, d]) float64, dense and symmetric, the ones row / column last -- the
     layout of LagStats.moments.  Device tensors on the device, else host arrays."""
@@ -1863,18 +1935,11 @@ class OnlineRidgeFit(_Bank):
   def update_model(self, model, regularization_lambda, session=0):
     """Gives a brain_model.BrainModelLinearRegression the ridge weights of one session (model.set_weights): the
     model's channels, context and output width must be the session's.  Returns the model."""
-    if not isinstance(model, brain_model.BrainModelLinearRegression):
-      raise ValueError('OnlineRidgeFit.update_model takes a BrainModelLinearRegression, not a %s.' %
-                       type(model).__name__)
-    for name, mine, theirs in (('channels', self.channels, model._c1), ('pre_context', self.pre, model._pre),
-                               ('post_context', self.post, model._post),
-                               ('outputs', self.outputs, model._output_width)):
-      if int(theirs) != mine:
-        raise ValueError('OnlineRidgeFit.update_model: the model has %s = %d, the fit %d.' % (name, int(theirs), mine))
-    if not 0 <= int(session) < self.sessions:
-      raise ValueError('OnlineRidgeFit.update_model: session %d of %d.' % (int(session), self.sessions))
+    i = self._check_model(model, brain_model.BrainModelLinearRegression, (
+        ('channels', self.channels, '_c1'), ('pre_context', self.pre, '_pre'), ('post_context', self.post, '_post'),
+        ('outputs', self.outputs, '_output_width')), session)
     w, b = self.solve([regularization_lambda])
-    w, b = w[int(session), 0], b[int(session), 0]
+    w, b = w[i, 0], b[i, 0]
     if hasattr(w, 'cpu'):
       w, b = w.cpu().numpy(), b.cpu().numpy()
     model.set_weights([w, b])
@@ -1966,27 +2031,20 @@ class _HostCCAFitSession(object):
 
   def push(self, eeg, feat, frames_before, flush):
     """eeg [n, c1], feat [n, c2] float32 behind frames_before rows; returns the frames this push emitted."""
-    (c1, pre1, post1), (c2, pre2, post2), post = self.v1, self.v2, self.post
-    after = frames_before + eeg.shape[0]
-    pad = lambda c: [np.zeros((post, c), np.float32)] if flush else []
+    (_, pre1, post1), (_, pre2, post2) = self.v1, self.v2
     # rows[0] is EEG row frames_before - (pre1 + post), frows[0] feature row frames_before - (pre2 + post); frame f
     # reads the rows f - pre_v .. f + post_v of its view: the slots i + (post - post_v) .. of i = f - frames_before + post
-    rows = np.concatenate([self.tail, eeg] + pad(c1))
-    frows = np.concatenate([self.feat_tail, feat] + pad(c2))
-    e0 = max(0, frames_before - post)
-    e1 = after if flush else max(0, after - post)
+    rows, self.tail = _session_rows(self.tail, eeg, self.post, flush)
+    frows, self.feat_tail = _session_rows(self.feat_tail, feat, self.post, flush)
+    _, emitted, i0 = _session_frames(frames_before, eeg.shape[0], self.post, flush)
     lags1, lags2 = pre1 + 1 + post1, pre2 + 1 + post2
     k1, k2 = self.k1, self.k2
     u = np.ones((k1 + k2 + 1,), np.float64)
-    for f in range(e0, e1):
-      i = f - frames_before + post
+    for i in range(i0, i0 + emitted):
       u[:k1] = rows[i:i + lags1].reshape(-1)
       u[k1:k1 + k2] = frows[i:i + lags2].reshape(-1)
       self.m = self.m * self.g + np.outer(u, u)
-    both, fboth = np.concatenate([self.tail, eeg]), np.concatenate([self.feat_tail, feat])
-    self.tail = np.ascontiguousarray(both[both.shape[0] - (pre1 + post):])
-    self.feat_tail = np.ascontiguousarray(fboth[fboth.shape[0] - (pre2 + post):])
-    return max(0, e1 - e0)
+    return emitted
 
   def moments(self):
     """(xtx [k1 + 1, k1 + 1] with the ones row and column last, x2tx2, xtx2, sum2): LagStats.moments' layout."""
@@ -2003,7 +2061,7 @@ class _HostCCAFitSession(object):
             np.stack([o[4] for o in outs]), np.stack(corr))
 
 
-class OnlineCCAFit(_Bank):
+class OnlineCCAFit(_FitBank):
   """The online CCA decoder's training stage: a bank of S sessions that take (eeg, attended features) rows in pushes
   of any length and keep the EXACT float64 moments of both lagged views -- M = sum u u^T of u = [x~ | y~ | 1], each
   half the lagged vector of brain_data's context for its view -- in ONE td_ccafit_online_push launch per push, the
@@ -2027,7 +2085,9 @@ class OnlineCCAFit(_Bank):
   lagged inputs in the two views, a push of more than 1048576 rows, a forgetting factor outside (0, 1].  Without a
   GPU the same object runs a NumPy session of the same semantics, bit for bit for the moments (float64 NumPy for the
   model, not rounded to float32)."""
-  FLUSHED = 'The fit was flushed: reset() starts the next recording.'
+  LAST_ROWS = 'OnlineCCAFit.flush takes the last rows as eeg AND feat, or neither.'
+  SHAPES = ('A push is eeg [%d, n, %d] (or [n, %d] for one session) with features [%d, n, %d] (or [n, %d] for one '
+            'session), not eeg %s with features %s.')
 
   def __init__(self, channels, pre_context, post_context, features, input2_pre_context, input2_post_context,
                num_sessions=1, forgetting=1.0):
@@ -2035,114 +2095,32 @@ class OnlineCCAFit(_Bank):
     c2, pre2, post2 = int(features), int(input2_pre_context), int(input2_post_context)
     g = float(forgetting)
     _check_ccafit_shape('OnlineCCAFit', c1, pre1, post1, c2, pre2, post2, g)
-    if int(num_sessions) < 1:
-      raise ValueError('OnlineCCAFit needs at least one session.')
     self.channels, self.pre, self.post = c1, pre1, post1
     self.features, self.pre2, self.post2 = c2, pre2, post2
-    self.forgetting = g
     self.inputs, self.inputs2 = (pre1 + 1 + post1) * c1, (pre2 + 1 + post2) * c2       # k1, k2
-    self.delay = max(post1, post2)
-    self._views = (c1, pre1, post1, c2, pre2, post2)
-    _Bank.__init__(self, int(num_sessions), device.gpu_available())
-    if self._on_device:
-      h = device.default_handle()
-      self._dev = dict(h=h, state=self._zero_state(h, device.online_ccafit_state_bytes(*self._views)))
-    else:
-      self._host = [_HostCCAFitSession(c1, pre1, post1, c2, pre2, post2, g) for _ in range(self.sessions)]
-    self.reset()
-
-  def reset(self):
-    """A fresh recording and empty moments: zero state (a memset), no row pushed."""
-    self.rows_pushed = self.frames = 0           # frames: the frames counted into the moments so far
-    self._pushes = 0                             # pushes with rows: its parity is the live tail copy
-    _Bank.reset(self)
+    self._views = views = (c1, pre1, post1, c2, pre2, post2)
+    delay, n = max(post1, post2), self.inputs + self.inputs2 + 1
+    self._setup(num_sessions, g, delay, (c1, c2), n * n,
+                (('tail', pre1 + delay, c1), ('feat_tail', pre2 + delay, c2)),
+                lambda: device.online_ccafit_state_bytes(*views),
+                lambda: _HostCCAFitSession(*views, g),
+                lambda *args, **kwargs: device.online_ccafit_push(*args, pre1, post1, pre2, post2, c1=c1, c2=c2,
+                                                                  **kwargs))
 
   # -- pushes ------------------------------------------------------------------------------------
-  def _as_bank(self, eeg, feat):
-    """(eeg [S, n, c1], feat [S, n, c2]) float32: device tensors on the device, else host arrays."""
-    s, c1, c2 = self.sessions, self.channels, self.features
-    if self._on_device or any(hasattr(a, 'is_cuda') for a in (eeg, feat)):
-      torch = device._torch()
-      dev = self._dev['h'].device if self._on_device else None
-      conv = lambda a: (a if hasattr(a, 'is_cuda') else torch.as_tensor(np.asarray(a, np.float32))).to(
-          device=dev, dtype=torch.float32)
-      eeg, feat = conv(eeg), conv(feat)
-      if not self._on_device:
-        eeg, feat = eeg.cpu().numpy(), feat.cpu().numpy()
-    else:
-      eeg, feat = np.asarray(eeg, np.float32), np.asarray(feat, np.float32)
-    shapes = (tuple(eeg.shape), tuple(feat.shape))
-    if len(eeg.shape) == 2 and len(feat.shape) == 2 and s == 1:
-      eeg, feat = eeg.reshape((1,) + shapes[0]), feat.reshape((1,) + shapes[1])
-    n = int(eeg.shape[1]) if len(eeg.shape) == 3 else -1
-    if len(eeg.shape) != 3 or tuple(eeg.shape) != (s, n, c1) or tuple(feat.shape) != (s, n, c2):
-      raise ValueError('A push is eeg [%d, n, %d] (or [n, %d] for one session) with features [%d, n, %d] (or [n, %d] '
-                       'for one session), not eeg %s with features %s.' % ((s, c1, c1, s, c2, c2) + shapes))
-    if n > MAX_FIT_PUSH:
-      raise ValueError('OnlineCCAFit takes at most %d rows in one push, not %d.' % (MAX_FIT_PUSH, n))
-    return eeg, feat
-
   def push(self, eeg, feat):
     """The next n rows of every session: eeg [n, c1] / [S, n, c1] and the attended speaker's features [n, c2] /
     [S, n, c2], float32 device tensors (read where they are, no host copy) or arrays; n may be 0.  Returns the
     frames counted so far."""
-    self._refuse_flushed()
-    eeg, feat = self._as_bank(eeg, feat)
-    return self._advance(eeg, feat, False)
+    return self._push((eeg, feat), False)
 
   def flush(self, eeg=None, feat=None):
     """The end of the recording: the last `delay` frames are counted as if zero rows followed in both views -- behind
     the recording's last rows, when they are given (one launch for both).  After it the fit refuses pushes until
     reset(); moments() and solve() stay."""
-    self._refuse_flushed()
-    if self._last_rows('OnlineCCAFit.flush takes the last rows as eeg AND feat, or neither.', eeg, feat):
-      eeg, feat = self._as_bank(eeg, feat)
-    frames = self._advance(eeg, feat, True)
-    self.flushed = True
-    return frames
-
-  def _advance(self, eeg, feat, flush):
-    n = 0 if eeg is None else int(eeg.shape[1])
-    after = self.rows_pushed + n
-    counted = after if flush else max(0, after - self.delay)
-    if not self._on_device:
-      if eeg is None:
-        eeg, feat = self._no_rows(self.channels), self._no_rows(self.features)
-      for i, sess in enumerate(self._host):
-        sess.push(eeg[i], feat[i], self.rows_pushed, flush)
-    else:
-      d = self._dev
-      if n == 0:
-        eeg = feat = None
-      else:
-        if eeg.stride(2) != 1 and self.channels > 1:
-          eeg = eeg.contiguous()
-        if feat.stride(2) != 1 and self.features > 1:
-          feat = feat.contiguous()
-      device.online_ccafit_push(eeg, feat, d['state'], self.rows_pushed, self._pushes, self.pre, self.post,
-                                self.pre2, self.post2, c1=self.channels, c2=self.features, flush=flush,
-                                forget=self.forgetting, handle=d['h'])
-    self.rows_pushed = after
-    self.frames = counted
-    if n > 0:
-      self._pushes += 1
-    return self.frames
+    return self._push((eeg, feat), True)
 
   # -- what the state holds ----------------------------------------------------------------------
-  @property
-  def tails(self):
-    """(EEG tail [S, pre1 + delay, c1], feature tail [S, pre2 + delay, c2]) float32: the live copy -- slot j of a
-    view holds row rows_pushed - (pre_v + delay) + j, zero before row 0.  Device tensors (views) or host arrays."""
-    s, c1, c2 = self.sessions, self.channels, self.features
-    tl1, tl2 = self.pre + self.delay, self.pre2 + self.delay
-    if self._dev is None:
-      return (np.stack([sess.tail for sess in self._host]), np.stack([sess.feat_tail for sess in self._host]))
-    n = self.inputs + self.inputs2 + 1
-    floats = self._dev['state'].view(device._torch().float32)
-    copy = tl1 * c1 + tl2 * c2
-    at = 2 * n * n + (self._pushes & 1) * copy
-    return (floats[:, at:at + tl1 * c1].reshape(s, tl1, c1), floats[:, at + tl1 * c1:at + copy].reshape(s, tl2, c2))
-
   def moments(self):
     """(xtx [S, k1 + 1, k1 + 1], x2tx2 [S, k2, k2], xtx2 [S, k1, k2], sum2 [S, k2]) float64, dense and symmetric, the
     ones row / column of xtx last -- the layout of LagStats.moments; xtx[:, k1, k1] is the (effective) frame count.
@@ -2190,17 +2168,10 @@ class OnlineCCAFit(_Bank):
     """Gives a cca.BrainModelCCA of matching widths the rotations and means of one session (model.set_weights, and
     model.eigenvalues): the model's two input widths must be k1 and k2, its output_dims `dims`.  Returns the model."""
     from telluride_decoding_amd import cca
-    if not isinstance(model, cca.BrainModelCCA):
-      raise ValueError('OnlineCCAFit.update_model takes a BrainModelCCA, not a %s.' % type(model).__name__)
-    for name, mine, theirs in (('input_1 width', self.inputs, model._input1_width),
-                               ('input_2 width', self.inputs2, model._input2_width),
-                               ('output dims', int(dims), model.output_dims)):
-      if int(theirs) != mine:
-        raise ValueError('OnlineCCAFit.update_model: the model has %s = %d, the fit %d.' % (name, int(theirs), mine))
-    if not 0 <= int(session) < self.sessions:
-      raise ValueError('OnlineCCAFit.update_model: session %d of %d.' % (int(session), self.sessions))
+    i = self._check_model(model, cca.BrainModelCCA, (
+        ('input_1 width', self.inputs, '_input1_width'), ('input_2 width', self.inputs2, '_input2_width'),
+        ('output dims', int(dims), 'output_dims')), session)
     r = self.solve([regularization], dims)
-    i = int(session)
     host = lambda a: (a.cpu().numpy() if hasattr(a, 'cpu') else np.asarray(a)).astype(np.float32)
     model.set_weights([host(r.mean_x[i]).reshape(1, -1), host(r.mean_y[i]).reshape(1, -1), host(r.rot_x[i, 0]),
                        host(r.rot_y[i, 0])])
@@ -2300,11 +2271,9 @@ class _HostCalibSession(object):
   def push(self, eeg, env, w, b, frames_before, flush):
     """eeg [n, c], env [n, 2] float64 behind frames_before rows, predicted with w [lags c] and b."""
     c, pre, post = self.c, self.pre, self.post
-    pl = device.online_plan(frames_before, eeg.shape[0], post, 1, 1, flush)
-    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c))] if flush else []))
-    envs = np.concatenate([self.env_tail, env])
-    emitted = pl.emitted_after - pl.emitted_before
-    i0 = pl.emitted_before - (frames_before - post)   # (as _HostSession.push)
+    rows, self.tail = _session_rows(self.tail, eeg, post, flush)
+    envs, self.env_tail = _session_rows(self.env_tail, env, post, False)
+    first, emitted, i0 = _session_frames(frames_before, eeg.shape[0], post, flush)
     w = np.asarray(w, np.float32).astype(np.float64)
     pred = np.zeros((emitted,), np.float64)
     for l in range(pre + 1 + post):                 # (lag, channel) order, whatever the push's length
@@ -2312,14 +2281,83 @@ class _HostCalibSession(object):
         pred += rows[i0 + l:i0 + l + emitted, ch] * w[l * c + ch]
     pred = pred + float(b)
     truth = envs[i0:i0 + emitted]
-    calibration_walk(self.sums, pred, truth[:, 0], truth[:, 1], pl.emitted_before, self.width)
-    both = np.concatenate([self.tail, eeg])
-    self.tail = both[both.shape[0] - (pre + post):]
-    self.env_tail = envs[envs.shape[0] - post:] if post else envs[:0]
+    calibration_walk(self.sums, pred, truth[:, 0], truth[:, 1], first, self.width)
     return emitted
 
 
-class OnlineCalibration(_Bank):
+class _CalibrationBank(_TrainingBank):
+  """What the two calibration banks share: an OnlineDecoder bank of one kind whose sessions, context and current
+  model they take, windows of window_size frames, sums in float64 at the head of the state, and a closed form over
+  them with a status per session.  A class gives BANK (the decoder's kind, its words for it, whose the other kinds
+  are), REASONS (status -> sentence), _reason_values() beyond width and frames, _closed_form(sums) and
+  _host_result(outs), and _device_finish()."""
+  FLUSHED = 'The calibration was flushed: reset() starts the next stretch.'
+  BANK = REASONS = None
+
+  def _take(self, decoder, window_size):
+    """The constructor's refusals, and what every calibration takes from its decoder."""
+    who, (kind, words, others) = type(self).__name__, self.BANK
+    if not isinstance(decoder, OnlineDecoder):
+      raise ValueError('%s calibrates an OnlineDecoder bank, not a %s.' % (who, type(decoder).__name__))
+    if decoder.kind != kind:
+      raise ValueError('%s calibrates %s, not a %s bank (%s).' % (who, words, decoder.kind, others))
+    width = max(1, int(window_size))
+    if width > MAX_WINDOW:
+      raise ValueError('%s takes windows of 1 to %d frames, not %d.' % (who, MAX_WINDOW, width))
+    self.decoder, self.window_size = decoder, width
+    self.channels, self.pre, self.post = decoder.channels, decoder.pre, decoder.post
+
+  def _allocate(self, delay, state_bytes, host_session):
+    decoder = self.decoder
+    _TrainingBank.__init__(self, decoder.sessions, decoder._on_device, delay, lambda: decoder._dev['h'], state_bytes,
+                           host_session)
+
+  frames_emitted = _TrainingBank._counted        # the frames counted into the sums so far
+
+  @property
+  def windows(self):
+    """The completed windows per class."""
+    return self.frames_emitted // self.window_size
+
+  def _reason_values(self):
+    return {}
+
+  def _raise(self, status):
+    for i, st in enumerate(status):
+      if int(st) != device.CALIB_OK:
+        reason = self.REASONS[int(st)] % dict(self._reason_values(), width=self.window_size,
+                                              frames=self.frames_emitted)
+        raise ValueError('%s.finish: session %d: %s.' % (type(self).__name__, i, reason))
+
+  def _finish(self):
+    """finish(): the closed form of every session, refused by _raise unless every status is CALIB_OK."""
+    if self._dev is None:
+      outs = [self._closed_form(sess.sums) for sess in self._host]
+      self._raise([o['status'] for o in outs])
+      return self._host_result(outs)
+    out = self._device_finish()
+    self._raise(out.status.cpu().numpy())
+    return CalibrationResult(out.corr, out.lda, out.dprime)
+
+  def _session_form(self, decoder, kind, session):
+    """The front of update_decoder: the closed form (a dict) of one session's sums for a decoder of class `kind`."""
+    who = '%s.update_decoder' % type(self).__name__
+    if not isinstance(decoder, kind):
+      raise ValueError('%s takes a %s, not a %s.' % (who, kind.__name__, type(decoder).__name__))
+    if not 0 <= int(session) < self.sessions:
+      raise ValueError('%s: session %d of %d.' % (who, int(session), self.sessions))
+    sums = self.sums()[int(session)]
+    if hasattr(sums, 'cpu'):
+      sums = sums.cpu().numpy()
+    o = self._closed_form(sums)
+    if o['status'] != device.CALIB_OK:
+      status = [device.CALIB_OK] * self.sessions
+      status[int(session)] = o['status']
+      self._raise(status)
+    return o
+
+
+class OnlineCalibration(_CalibrationBank):
   """The online chain's last training stage: the correlation statistics, the scaled LDA and d' that
   infer_decoder.Decoder.train(data0, data1, window_size=W) would take from a labelled stretch -- data0 the
   (unattended envelope, prediction) frames, data1 the (attended envelope, prediction) frames -- for rows that arrive
@@ -2341,90 +2379,47 @@ class OnlineCalibration(_Bank):
   any time and leaves the state alone.  Any cut of a recording gives the same state bytes (sums()).
 
   Without a GPU the same object runs a NumPy session of the same semantics (float64 prediction)."""
-  FLUSHED = 'The calibration was flushed: reset() starts the next stretch.'
+  LAST_ROWS = 'OnlineCalibration.flush takes the last rows as eeg AND both envelopes, or nothing.'
+  BANK = ('linear', 'a linear bank', 'CCA and DNN calibration are out of scope')
+  REASONS = _CALIB_REASONS
 
   def __init__(self, decoder, window_size=100):
-    if not isinstance(decoder, OnlineDecoder):
-      raise ValueError('OnlineCalibration calibrates an OnlineDecoder bank, not a %s.' % type(decoder).__name__)
-    if decoder.kind != 'linear':
-      raise ValueError('OnlineCalibration calibrates a linear bank, not a %s bank (CCA and DNN calibration are out '
-                       'of scope).' % decoder.kind)
-    width = max(1, int(window_size))
-    if width > MAX_WINDOW:
-      raise ValueError('OnlineCalibration takes windows of 1 to %d frames, not %d.' % (MAX_WINDOW, width))
-    self.decoder = decoder
-    _Bank.__init__(self, decoder.sessions, decoder._on_device)
-    self.channels, self.pre, self.post = decoder.channels, decoder.pre, decoder.post
-    self.window_size = width
-    self.delay = self.post
-    if self._on_device:
-      h = decoder._dev['h']
-      self._dev = dict(h=h, state=self._zero_state(h, device.online_calib_state_bytes(self.channels, self.pre,
-                                                                                       self.post)))
-    else:
-      self._host = [_HostCalibSession(self.channels, self.pre, self.post, width) for _ in range(self.sessions)]
-    self.reset()
-
-  def reset(self):
-    """A fresh calibration stretch: zero state (a memset), no row pushed."""
-    self.rows_pushed = 0
-    _Bank.reset(self)
-
-  @property
-  def frames_emitted(self):
-    """The frames counted into the sums so far: post_context behind the rows pushed, all of them after flush()."""
-    return self.rows_pushed if self.flushed else max(0, self.rows_pushed - self.post)
-
-  @property
-  def windows(self):
-    """The completed windows per class."""
-    return self.frames_emitted // self.window_size
+    self._take(decoder, window_size)
+    shape = (self.channels, self.pre, self.post)
+    self._allocate(self.post, lambda: device.online_calib_state_bytes(*shape),
+                   lambda: _HostCalibSession(*shape, self.window_size))
 
   # -- pushes ------------------------------------------------------------------------------------
   def push(self, eeg, attended, unattended):
     """The next n rows of every session: eeg [n, C] / [S, n, C], the attended and the unattended envelope [n] /
     [S, n], float32 device tensors (read where they are) or arrays; n may be 0.  Returns the frames counted so
     far."""
-    self._refuse_flushed()
-    eeg, env = self.decoder._as_bank(eeg, attended, unattended)
-    if int(eeg.shape[1]) > MAX_FIT_PUSH:
-      raise ValueError('OnlineCalibration takes at most %d rows in one push, not %d.' % (MAX_FIT_PUSH, eeg.shape[1]))
-    return self._advance(eeg, env, False)
+    return self._push((eeg, attended, unattended), False)
 
   def flush(self, eeg=None, attended=None, unattended=None):
     """The end of the stretch: the last post_context frames are counted as if zero rows followed -- behind the
     stretch's last rows, when they are given (one launch for both).  After it the calibration refuses pushes until
     reset(); sums() and finish() stay."""
-    self._refuse_flushed()
-    env = None
-    if self._last_rows('OnlineCalibration.flush takes the last rows as eeg AND both envelopes, or nothing.', eeg,
-                       attended, unattended):
-      eeg, env = self.decoder._as_bank(eeg, attended, unattended)
-      if int(eeg.shape[1]) > MAX_FIT_PUSH:
-        raise ValueError('OnlineCalibration takes at most %d rows in one push, not %d.' % (MAX_FIT_PUSH, eeg.shape[1]))
-    return self._advance(eeg, env, True)
+    return self._push((eeg, attended, unattended), True)
 
-  def _advance(self, eeg, env, flush):
-    n = 0 if eeg is None else int(eeg.shape[1])
-    if not self._on_device:
-      if eeg is None:
-        eeg, env = self._no_rows(self.channels), self._no_rows(2)
-      for i, sess in enumerate(self._host):
-        p = self.decoder._params[i]
-        sess.push(np.asarray(eeg[i], np.float64), np.asarray(env[i], np.float64), p['w'], p['b'], self.rows_pushed,
-                  flush)
-    else:
-      d, bank = self._dev, self.decoder._dev
-      h = d['h']
-      if n == 0:
-        eeg = env = None
-      elif not hasattr(eeg, 'is_cuda'):
-        eeg, env = self._upload(h, eeg), self._upload(h, env)
-      device.online_calib_push(eeg, env, bank['w'], bank['b'], d['state'], self.rows_pushed, self.pre, self.post,
-                               self.window_size, c=self.channels, flush=flush, handle=h)
-    self.rows_pushed += n
-    self.flushed = bool(flush)
-    return self.frames_emitted
+  def _blocks(self, eeg, attended, unattended):
+    return self.decoder._as_bank(eeg, attended, unattended)
+
+  def _no_blocks(self):
+    return self._no_rows(self.channels), self._no_rows(2)
+
+  def _session_push(self, sess, i, blocks, flush):
+    p = self.decoder._params[i]
+    sess.push(np.asarray(blocks[0][i], np.float64), np.asarray(blocks[1][i], np.float64), p['w'], p['b'],
+              self.rows_pushed, flush)
+
+  def _device_push(self, blocks, flush):
+    d, bank = self._dev, self.decoder._dev
+    eeg, env = blocks or (None, None)
+    if blocks is not None and not hasattr(eeg, 'is_cuda'):
+      eeg, env = self._upload(d['h'], eeg), self._upload(d['h'], env)
+    device.online_calib_push(eeg, env, bank['w'], bank['b'], d['state'], self.rows_pushed, self.pre, self.post,
+                             self.window_size, c=self.channels, flush=flush, handle=d['h'])
 
   # -- what the state holds ----------------------------------------------------------------------
   def sums(self):
@@ -2436,11 +2431,18 @@ class OnlineCalibration(_Bank):
       return np.stack([sess.sums for sess in self._host])
     return device.online_calib_sums(self._dev['state'], handle=self._dev['h'])
 
-  def _raise(self, status):
-    for i, st in enumerate(status):
-      if int(st) != device.CALIB_OK:
-        reason = _CALIB_REASONS[int(st)] % dict(width=self.window_size, frames=self.frames_emitted)
-        raise ValueError('OnlineCalibration.finish: session %d: %s.' % (i, reason))
+  def _closed_form(self, sums):
+    return calibration_closed_form(sums, self.frames_emitted, self.window_size)
+
+  def _host_result(self, outs):
+    stats = [[o['mean_x'], o['mean_y'], o['power']] for o in outs]
+    return CalibrationResult(np.array([[st, st] for st in stats], np.float64),
+                             np.array([[1.0, o['slope'], o['intercept']] for o in outs], np.float64),
+                             np.array([o['dprime'] for o in outs], np.float64))
+
+  def _device_finish(self):
+    return device.online_calib_finish(self._dev['state'], self.frames_emitted, self.window_size,
+                                      handle=self._dev['h'])
 
   def finish(self):
     """CalibrationResult(corr [S, 2, 3] {mean_truth, mean_pred, power} for both speakers, lda [S, 3] {1, slope,
@@ -2448,35 +2450,13 @@ class OnlineCalibration(_Bank):
     on the device (one launch; the statuses come back in one small copy), else host arrays.  The state is not
     modified.  ValueError naming the session and the reason: no completed window (train's 'No data for class'), a
     power that is not finite or not above zero, equal class means (scaled LDA's 'X0 and X1 ... identical')."""
-    if self._dev is None:
-      outs = [calibration_closed_form(sess.sums, self.frames_emitted, self.window_size) for sess in self._host]
-      self._raise([o['status'] for o in outs])
-      stats = [[o['mean_x'], o['mean_y'], o['power']] for o in outs]
-      return CalibrationResult(np.array([[st, st] for st in stats], np.float64),
-                               np.array([[1.0, o['slope'], o['intercept']] for o in outs], np.float64),
-                               np.array([o['dprime'] for o in outs], np.float64))
-    out = device.online_calib_finish(self._dev['state'], self.frames_emitted, self.window_size,
-                                     handle=self._dev['h'])
-    self._raise(out.status.cpu().numpy())
-    return CalibrationResult(out.corr, out.lda, out.dprime)
+    return self._finish()
 
   def update_decoder(self, decoder, session=0):
     """Gives an infer_decoder.LinearRegressionDecoder the correlation parameters and the scaled LDA of one session
     (what Decoder.train leaves in it), so that save_parameters writes them.  Returns d'."""
     from telluride_decoding_amd import scaled_lda
-    if not isinstance(decoder, infer_decoder.LinearRegressionDecoder):
-      raise ValueError('OnlineCalibration.update_decoder takes a LinearRegressionDecoder, not a %s.' %
-                       type(decoder).__name__)
-    if not 0 <= int(session) < self.sessions:
-      raise ValueError('OnlineCalibration.update_decoder: session %d of %d.' % (int(session), self.sessions))
-    sums = self.sums()[int(session)]
-    if hasattr(sums, 'cpu'):
-      sums = sums.cpu().numpy()
-    o = calibration_closed_form(sums, self.frames_emitted, self.window_size)
-    if o['status'] != device.CALIB_OK:
-      status = [device.CALIB_OK] * self.sessions
-      status[int(session)] = o['status']
-      self._raise(status)
+    o = self._session_form(decoder, infer_decoder.LinearRegressionDecoder, session)
     vec = lambda v: np.array([v], np.float64)
     decoder.model_params = infer_decoder.ModelParamsTuple(
         infer_decoder.CorrelationParamsTuple(o['count'], vec(o['sum_x']), vec(o['sum_y']), vec(o['sum_x2']),
@@ -2617,25 +2597,18 @@ class _HostCCACalibSession(object):
     """eeg [n, c1], feat [2, n, c2] (attended, unattended) float64 behind frames_before rows, projected with
     model's mean_x, rot_x, mean_y, rot_y."""
     (c1, pre1, post1), (c2, pre2, post2) = self.view1, self.view2
-    post = self.delay
-    pl = device.online_plan(frames_before, eeg.shape[0], post, 1, 1, flush)
-    rows = np.concatenate([self.tail, eeg] + ([np.zeros((post, c1))] if flush else []))
-    frows = np.concatenate([self.feat_tail, feat] + ([np.zeros((2, post, c2))] if flush else []), axis=1)
-    emitted = pl.emitted_after - pl.emitted_before
-    i0 = pl.emitted_before - (frames_before - post)   # (as _HostCcaSession.push)
+    rows, self.tail = _session_rows(self.tail, eeg, self.delay, flush)
+    frows, self.feat_tail = _session_rows(self.feat_tail, feat, self.delay, flush, axis=1)
+    first, emitted, i0 = _session_frames(frames_before, eeg.shape[0], self.delay, flush)
     f64 = lambda name: np.asarray(model[name], np.float32).astype(np.float64)
     project = _HostCcaSession._project
     a = project(rows, i0, emitted, c1, pre1 + 1 + post1, f64('mean_x'), f64('rot_x'))
     b1, b0 = (project(frows[k], i0, emitted, c2, pre2 + 1 + post2, f64('mean_y'), f64('rot_y')) for k in (0, 1))
-    cca_calibration_walk(self.sums, a, b1, b0, pl.emitted_before, self.width)
-    both = np.concatenate([self.tail, eeg])
-    self.tail = both[both.shape[0] - (pre1 + post):]
-    fboth = np.concatenate([self.feat_tail, feat], axis=1)
-    self.feat_tail = fboth[:, fboth.shape[1] - (pre2 + post):]
+    cca_calibration_walk(self.sums, a, b1, b0, first, self.width)
     return emitted
 
 
-class OnlineCCACalibration(_Bank):
+class OnlineCCACalibration(_CalibrationBank):
   """The CCA chain's last training stage: per dim the correlation statistics, the scaled LDA over the dims columns
   and d' that infer_decoder.Decoder.train(data0, data1, window_size=W) would take from a labelled stretch with a
   CCADecoder -- data0 the (EEG projection, unattended projection) frames, data1 the (EEG projection, attended
@@ -2658,96 +2631,50 @@ class OnlineCCACalibration(_Bank):
   least dims + 2 windows in all.
 
   Without a GPU the same object runs a NumPy session of the same semantics (float64 projections)."""
-  FLUSHED = 'The calibration was flushed: reset() starts the next stretch.'
+  LAST_ROWS = 'OnlineCCACalibration.flush takes the last rows as eeg AND both feature blocks, or nothing.'
+  BANK = ('cca', 'a CCA bank', 'OnlineCalibration is the linear bank\'s')
+  REASONS = _CCA_CALIB_REASONS
 
   def __init__(self, decoder, window_size=100):
-    if not isinstance(decoder, OnlineDecoder):
-      raise ValueError('OnlineCCACalibration calibrates an OnlineDecoder bank, not a %s.' % type(decoder).__name__)
-    if decoder.kind != 'cca':
-      raise ValueError('OnlineCCACalibration calibrates a CCA bank, not a %s bank (OnlineCalibration is the linear '
-                       'bank\'s).' % decoder.kind)
-    width = max(1, int(window_size))
-    if width > MAX_WINDOW:
-      raise ValueError('OnlineCCACalibration takes windows of 1 to %d frames, not %d.' % (MAX_WINDOW, width))
-    self.decoder = decoder
-    _Bank.__init__(self, decoder.sessions, decoder._on_device)
-    self.channels, self.pre, self.post = decoder.channels, decoder.pre, decoder.post
+    self._take(decoder, window_size)
     self.features, self.pre2, self.post2, self.dims = decoder.features, decoder.pre2, decoder.post2, decoder.dims
-    self.window_size = width
-    self.delay = decoder.delay
     shape = (self.channels, self.pre, self.post, self.features, self.pre2, self.post2, self.dims)
-    if self._on_device:
-      h = decoder._dev['h']
+    if self.decoder._on_device:
       device.online_ccacalib_lds_bytes(*shape, 1)      # (a shape over the LDS budget: the library says so, by name)
-      self._dev = dict(h=h, state=self._zero_state(h, device.online_ccacalib_state_bytes(*shape)))
-    else:
-      self._host = [_HostCCACalibSession(*shape, width) for _ in range(self.sessions)]
-    self.reset()
-
-  def reset(self):
-    """A fresh calibration stretch: zero state (a memset), no row pushed."""
-    self.rows_pushed = 0
-    _Bank.reset(self)
-
-  @property
-  def frames_emitted(self):
-    """The frames counted into the sums so far: `delay` behind the rows pushed, all of them after flush()."""
-    return self.rows_pushed if self.flushed else max(0, self.rows_pushed - self.delay)
-
-  @property
-  def windows(self):
-    """The completed windows per class."""
-    return self.frames_emitted // self.window_size
+    self._allocate(decoder.delay, lambda: device.online_ccacalib_state_bytes(*shape),
+                   lambda: _HostCCACalibSession(*shape, self.window_size))
 
   # -- pushes ------------------------------------------------------------------------------------
-  def _as_rows(self, eeg, attended, unattended):
-    eeg, feats = self.decoder._as_cca_bank(eeg, attended, unattended)
-    if int(eeg.shape[1]) > MAX_FIT_PUSH:
-      raise ValueError('OnlineCCACalibration takes at most %d rows in one push, not %d.' %
-                       (MAX_FIT_PUSH, eeg.shape[1]))
-    return eeg, feats
-
   def push(self, eeg, attended_features, unattended_features):
     """The next n rows of every session: eeg [n, C] / [S, n, C], the attended and the unattended speaker's feature
     block [n, c2] / [S, n, c2], float32 device tensors (read where they are) or arrays; n may be 0.  Returns the
     frames counted so far."""
-    self._refuse_flushed()
-    return self._advance(*self._as_rows(eeg, attended_features, unattended_features), False)
+    return self._push((eeg, attended_features, unattended_features), False)
 
   def flush(self, eeg=None, attended_features=None, unattended_features=None):
     """The end of the stretch: the last `delay` frames are counted as if zero rows followed -- behind the stretch's
     last rows, when they are given (one launch for both).  After it the calibration refuses pushes until reset();
     sums() and finish() stay."""
-    self._refuse_flushed()
-    feats = None
-    if self._last_rows('OnlineCCACalibration.flush takes the last rows as eeg AND both feature blocks, or nothing.',
-                       eeg, attended_features, unattended_features):
-      eeg, feats = self._as_rows(eeg, attended_features, unattended_features)
-    return self._advance(eeg, feats, True)
+    return self._push((eeg, attended_features, unattended_features), True)
 
-  def _advance(self, eeg, feats, flush):
-    n = 0 if eeg is None else int(eeg.shape[1])
-    if not self._on_device:
-      if eeg is None:
-        eeg, feats = self._no_rows(self.channels), (self._no_rows(self.features),) * 2
-      for i, sess in enumerate(self._host):
-        sess.push(np.asarray(eeg[i], np.float64), np.stack([np.asarray(f[i], np.float64) for f in feats]),
-                  self.decoder._params[i], self.rows_pushed, flush)
-    else:
-      d, bank = self._dev, self.decoder._dev
-      h = d['h']
-      att = unatt = None
-      if n == 0:
-        eeg = None
-      else:
-        up = lambda a: a if hasattr(a, 'is_cuda') else self._upload(h, a)
-        eeg, att, unatt = up(eeg), up(feats[0]), up(feats[1])
-      device.online_ccacalib_push(eeg, att, unatt, bank['mean_x'], bank['rot_x'], bank['mean_y'], bank['rot_y'],
-                                  d['state'], self.rows_pushed, self.pre, self.post, self.pre2, self.post2,
-                                  self.window_size, flush=flush, handle=h)
-    self.rows_pushed += n
-    self.flushed = bool(flush)
-    return self.frames_emitted
+  def _blocks(self, eeg, attended, unattended):
+    return self.decoder._as_cca_bank(eeg, attended, unattended)
+
+  def _no_blocks(self):
+    return self._no_rows(self.channels), (self._no_rows(self.features),) * 2
+
+  def _session_push(self, sess, i, blocks, flush):
+    sess.push(np.asarray(blocks[0][i], np.float64), np.stack([np.asarray(f[i], np.float64) for f in blocks[1]]),
+              self.decoder._params[i], self.rows_pushed, flush)
+
+  def _device_push(self, blocks, flush):
+    d, bank = self._dev, self.decoder._dev
+    eeg = att = unatt = None
+    if blocks is not None:
+      eeg, att, unatt = (a if hasattr(a, 'is_cuda') else self._upload(d['h'], a) for a in (blocks[0],) + blocks[1])
+    device.online_ccacalib_push(eeg, att, unatt, bank['mean_x'], bank['rot_x'], bank['mean_y'], bank['rot_y'],
+                                d['state'], self.rows_pushed, self.pre, self.post, self.pre2, self.post2,
+                                self.window_size, flush=flush, handle=d['h'])
 
   # -- what the state holds ----------------------------------------------------------------------
   def sums(self):
@@ -2760,12 +2687,21 @@ class OnlineCCACalibration(_Bank):
       return np.stack([sess.sums for sess in self._host])
     return device.online_ccacalib_sums(self._dev['state'], self.dims, handle=self._dev['h'])
 
-  def _raise(self, status):
-    for i, st in enumerate(status):
-      if int(st) != device.CALIB_OK:
-        reason = _CCA_CALIB_REASONS[int(st)] % dict(width=self.window_size, frames=self.frames_emitted,
-                                                    windows=self.windows, dims=self.dims)
-        raise ValueError('OnlineCCACalibration.finish: session %d: %s.' % (i, reason))
+  def _reason_values(self):
+    return dict(windows=self.windows, dims=self.dims)
+
+  def _closed_form(self, sums):
+    return cca_calibration_closed_form(sums, self.frames_emitted, self.window_size, self.dims)
+
+  def _host_result(self, outs):
+    stats = [np.stack([o['mean_a'], o['mean_b'], o['power']]) for o in outs]
+    return CalibrationResult(np.stack([np.stack([st, st]) for st in stats]),
+                             np.stack([np.concatenate([o['w'], [o['slope'], o['intercept']]]) for o in outs]),
+                             np.array([o['dprime'] for o in outs], np.float64))
+
+  def _device_finish(self):
+    return device.online_ccacalib_finish(self._dev['state'], self.dims, self.frames_emitted, self.window_size,
+                                         handle=self._dev['h'])
 
   def finish(self):
     """CalibrationResult(corr [S, 2, 3, dims] {mean_a, mean_b, power} for both speakers, lda [S, dims + 2] {weights,
@@ -2774,36 +2710,14 @@ class OnlineCCACalibration(_Bank):
     modified.  ValueError naming the session and the reason: no completed window (train's 'No data for class'), a
     dim's power that is not finite or not above zero, a pooled scatter that is not positive definite (fewer than
     dims + 2 windows in all), equal class means along the LDA axis (scaled LDA's 'X0 and X1 ... identical')."""
-    if self._dev is None:
-      outs = [cca_calibration_closed_form(sess.sums, self.frames_emitted, self.window_size, self.dims)
-              for sess in self._host]
-      self._raise([o['status'] for o in outs])
-      stats = [np.stack([o['mean_a'], o['mean_b'], o['power']]) for o in outs]
-      return CalibrationResult(np.stack([np.stack([st, st]) for st in stats]),
-                               np.stack([np.concatenate([o['w'], [o['slope'], o['intercept']]]) for o in outs]),
-                               np.array([o['dprime'] for o in outs], np.float64))
-    out = device.online_ccacalib_finish(self._dev['state'], self.dims, self.frames_emitted, self.window_size,
-                                        handle=self._dev['h'])
-    self._raise(out.status.cpu().numpy())
-    return CalibrationResult(out.corr, out.lda, out.dprime)
+    return self._finish()
 
   def update_decoder(self, decoder, session=0):
     """Gives an infer_decoder.CCADecoder the correlator's sums and statistics and the scaled LDA of one session (what
     Decoder.train leaves in it; the LDA keeps the one axis the scaled transform reads), so that save_parameters
     writes them.  Returns d'."""
     from telluride_decoding_amd import scaled_lda
-    if not isinstance(decoder, infer_decoder.CCADecoder):
-      raise ValueError('OnlineCCACalibration.update_decoder takes a CCADecoder, not a %s.' % type(decoder).__name__)
-    if not 0 <= int(session) < self.sessions:
-      raise ValueError('OnlineCCACalibration.update_decoder: session %d of %d.' % (int(session), self.sessions))
-    sums = self.sums()[int(session)]
-    if hasattr(sums, 'cpu'):
-      sums = sums.cpu().numpy()
-    o = cca_calibration_closed_form(sums, self.frames_emitted, self.window_size, self.dims)
-    if o['status'] != device.CALIB_OK:
-      status = [device.CALIB_OK] * self.sessions
-      status[int(session)] = o['status']
-      self._raise(status)
+    o = self._session_form(decoder, infer_decoder.CCADecoder, session)
     w = o['w'].reshape(-1, 1)
     decoder.model_params = infer_decoder.ModelParamsTuple(
         infer_decoder.CorrelationParamsTuple(o['count'], o['sum_x'], o['sum_y'], o['sum_x2'], o['sum_y2'],

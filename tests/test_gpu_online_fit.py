@@ -1,5 +1,5 @@
 """The online ridge fit on the GPU (td_fit_online_push / _moments / _solve, online.OnlineRidgeFit): white-noise
-recordings of 300 frames (120 for the two large shapes) at the shapes where the tiling can go wrong -- the moments and
+recordings of 300 frames (120 for the two large shapes and the full tile) at the shapes where the tiling can go wrong -- the moments and
 the tails bit for bit against the NumPy session with and without forgetting, every cut byte for byte through both
 tail copies, the moments against LagStats and the weights against float64 and against LagStats.ridge_solve, a bank
 against its sessions, one launch per push, repeatability, OnlineDecoder.set_weights device to device, and a singular
@@ -8,9 +8,10 @@ system reported, not faulted.
 The lambdas.  The weights are compared where a bound on the moments is a bound on the weights: white noise of n frames
 and K lagged inputs has the eigenvalues of its covariance inside (1 -+ sqrt(K / n))^2 (Marchenko-Pastur), so the small
 shapes (K / n <= 0.42: [0.12, 2.7]) have condition numbers <= 22 at any lambda and the large ones (n = 120 < K:
-singular without a ridge, largest eigenvalue <= (1 + sqrt(2048 / 120))^2 = 26.3) <= 27.3 from lambda = 1 on.  LagStats
+singular without a ridge, largest eigenvalue <= (1 + sqrt(2048 / 120))^2 = 26.3) <= 27.3 from lambda = 1 on; the
+full-tile shape (K = 63, n = 120: [0.08, 3.0]) <= 3.7 from lambda = 1 on.  LagStats
 holds its moments to 2^-22 (the two-piece float16 product), so cond x 2.4e-7 <= 1e-5 needs cond <= 41: lambdas 0.1, 1
-and 10 for the small shapes, 1 and 10 for the large ones."""
+and 10 for the small shapes, 1 and 10 for the shapes of 120 frames."""
 import numpy as np
 import pytest
 
@@ -21,9 +22,10 @@ from tests import parity_log
 pytestmark = pytest.mark.gpu
 
 # (c, pre, post, d, frames): no tail at all; K + 1 = 127, one short of two tiles; K + 1 = 65, the bias row alone in a
-# second tile, with the widest d; K + 1 = 1345 = 21 x 64 + 1; K + 1 = 2049, the limit
+# second tile, with the widest d; K + 1 = 1345 = 21 x 64 + 1; K + 1 = 2049, the limit; K + 1 = 64, one full tile with
+# the ones column its last, and d = 5: one lane of a B thread's second output
 SHAPES = [(5, 2, 9, 1, 300), (3, 0, 0, 2, 300), (63, 1, 0, 1, 300), (16, 3, 0, 8, 300), (64, 0, 20, 1, 120),
-          (128, 0, 15, 1, 120)]
+          (128, 0, 15, 1, 120), (21, 1, 1, 5, 120)]
 IDS = ['c%d_pre%d_post%d_d%d_n%d' % s for s in SHAPES]
 
 
