@@ -400,6 +400,61 @@ int td_set_accumulate_mode(td_handle* h, int mode) {
   return TD_OK;
 }
 
+int td_set_option(td_handle* h, const char* name, int64_t value) {
+  if (!h || !name) return td_fail(h, TD_ERR_INVALID, "td_set_option: NULL argument");
+  if (!strcmp(name, "cca_whitening")) {
+    TD_REQUIRE(h, value == 0 || value == 1, "td_set_option: cca_whitening is 0 (automatic) or 1 (eigen route)");
+    h->cca_whitening = (int)value;
+  } else if (!strcmp(name, "cca_fused")) {
+    TD_REQUIRE(h, value == 0 || value == 1, "td_set_option: cca_fused is 0 or 1");
+    h->cca_fused = (int)value;
+  } else if (!strcmp(name, "reserve_workspace")) {
+    // grows the handle's workspace arena to `value` bytes now (hipMalloc of a few GB is tens of ms; left to
+    // the first call that needs it, it lands in that call)
+    TD_REQUIRE(h, value >= 0, "td_set_option: reserve_workspace takes a byte count");
+    void* unused = nullptr;
+    if (value > 0) TD_TRY(td_workspace(h, (size_t)value, &unused));
+  } else if (!strcmp(name, "cg_limit_ticks")) {
+    h->cg_limit_ticks = value;
+  } else if (!strcmp(name, "narrow16")) {
+    TD_REQUIRE(h, value == 0 || value == 1, "td_set_option: narrow16 is 0 or 1");
+    h->narrow16 = (int)value;
+  } else if (!strcmp(name, "targets_f16")) {
+    TD_REQUIRE(h, value == 0 || value == 1, "td_set_option: targets_f16 is 0 or 1");
+    h->targets_f16 = (int)value;
+  } else if (!strcmp(name, "async_cg")) {
+    TD_REQUIRE(h, value == 0 || value == 1, "td_set_option: async_cg is 0 or 1");
+    h->async_cg = (int)value;
+  } else {
+    return td_fail(h, TD_ERR_INVALID, "td_set_option: unknown option '%s'", name);
+  }
+  return TD_OK;
+}
+
+int td_set_solver(td_handle* h, int mode) {
+  if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_set_solver: NULL handle");
+  TD_REQUIRE(h, mode == TD_SOLVER_AUTO || mode == TD_SOLVER_CHOLESKY || mode == TD_SOLVER_CG,
+             "td_set_solver: unknown mode %d", mode);
+  h->solver_mode = mode;
+  return TD_OK;
+}
+
+int td_last_solve_info(td_handle* h, int* solver, int* iterations, int* cg_status) {
+  if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_last_solve_info: NULL handle");
+  if (solver) *solver = h->last_solver;
+  if (iterations) *iterations = h->last_iterations;
+  if (cg_status) *cg_status = h->last_cg_status;
+  return TD_OK;
+}
+
+int td_last_cg_plan(td_handle* h, int* kernel, int* param, int* workgroups) {
+  if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_last_cg_plan: NULL handle");
+  if (kernel) *kernel = h->last_cg_kernel;
+  if (param) *param = h->last_cg_param;
+  if (workgroups) *workgroups = h->last_cg_wgs;
+  return TD_OK;
+}
+
 const char* td_last_error(const td_handle* h) {
   return h ? h->error.c_str() : td_global_error.c_str();
 }

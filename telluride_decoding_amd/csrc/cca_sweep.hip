@@ -8,7 +8,7 @@
 // are formed from them per fold.  The reference whitens both sides by eigen-decomposition and takes
 // svd(K11 C_xy K22); when no eigenvalue of C_xx is dropped any whitening of the x side gives the same canonical
 // directions, so with C_xx = L L^T and W = L^-1 C_xy (the forward substitution that rides along the batched
-// float64 factorisation of solve.hip):
+// float64 factorisation of chol.hip):
 //   K   = C_yy^-1/2               (K2 x K2 Jacobi eigen-decomposition, eigenvalues <= eps_eig dropped)
 //   B   = K (W^T W) K             (= K C_xy^T C_xx^-1 C_xy K, symmetric K2 x K2) = V diag(sigma^2) V^T
 //   e   = sigma (descending),  rot_y = K V[:, :dim],  rot_x = L^-T (W rot_y diag(1 / sigma))

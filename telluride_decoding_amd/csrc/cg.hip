@@ -1,7 +1,7 @@
 // One ridge system in ONE launch: conjugate gradients with the matrix resident in LDS.
 //
 // brain_model.py:447-477 solves (X^T X / n + lambda I) w = X^T y / n with a dense LU.  The blocked
-// Cholesky of solve.hip does the same in float64 but is a chain of ~100 dependent launches for
+// Cholesky of chol.hip does the same in float64 but is a chain of ~100 dependent launches for
 // one n = 2049 system (33 block steps x [diagonal factorisation 12 us + panel + update]): 1.06 ms
 // whatever the chip could do in parallel -- half of a C2 fit.  The chain cannot be shortened much:
 // column k of a factorisation needs column k - 1.

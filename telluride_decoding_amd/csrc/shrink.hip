@@ -355,7 +355,7 @@ constexpr int kLuNb = 32;             // panel width of the global-memory panel 
 constexpr int kLuNbReg = 16;          // ... of the register-resident one
 constexpr int kLuBack = 32;           // rows per block of the back substitution
 constexpr int kLuMaxN = 16320;        // the back substitution keeps the unknowns in LDS (128 KB), the swaps' index array too:
-                                      // the limit of the blocked Cholesky (solve.hip)
+                                      // the limit of the blocked Cholesky (chol.hip)
 constexpr int kLuPanelThreads = 1024;
 constexpr int kLuRegThreads = 512, kLuRegMaxRows = 6;
 

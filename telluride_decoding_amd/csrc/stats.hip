@@ -41,7 +41,7 @@ int stats_materialize(td_handle* h, td_stats* s) {
   return TD_OK;
 }
 
-// Used by solve.hip.
+// Used by solve.hip and loso.hip.
 int td_stats_layout(const td_stats* s, int* k1, int* d, int64_t* frames) {
   *k1 = s->k1;
   *d = s->d;

@@ -97,7 +97,7 @@ int stats_materialize(td_handle* h, td_stats* s);
 // Room for the boundary windows of `need` files (the windows held so far are kept).
 int ensure_window_capacity(td_handle* h, td_stats* s, int64_t need);
 
-// The layout as the solvers see it (solve.hip, eig.hip, cca_sweep.hip).
+// The layout as the solvers see it (solve.hip, loso.hip, eig.hip, cca_sweep.hip).
 int td_stats_layout(const td_stats* s, int* k1, int* d, int64_t* frames);
 int td_stats_dims(const td_stats* s, int* k1, int* k2, int64_t* frames);
 int td_stats_cca_direct(td_handle* h, td_stats* s, const double** xx, const double** yy, const double** xy,

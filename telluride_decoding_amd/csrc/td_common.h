@@ -601,7 +601,7 @@ int td_gram(td_handle* h, const float* x, int64_t ldx, int c1, const float* x2, 
 int td_colsum(td_handle* h, const float* a, int64_t lda, int ca, const std::vector<LagSeg>& segs,
               double* out_dev, bool accumulate);
 
-// Cholesky whitening helpers of the CCA dense stage (solve.hip), see td_chol_factor there.
+// Cholesky whitening helpers of the CCA dense stage (chol.hip), see td_chol_factor there.
 struct td_chol_state {
   double *a, *rt, *rt8, *sol, *linv, *tol;
   int n, np;
@@ -610,7 +610,7 @@ size_t td_chol_ws_bytes(int n);
 int td_chol_factor(td_handle* h, void* ws, const double* c_dev, int n, const double* bt_dev, int nb,
                    td_chol_state* st, double diag_shift = 0.0, double scale = 1.0);
 int td_chol_back(td_handle* h, const td_chol_state* st, const double* ut_dev, int nu, double* xt_dev);
-// (solve.hip) the batched factorisation (forward substitution of up to 64 right-hand-side rows included) and the
+// (chol.hip) the batched factorisation (forward substitution of up to 64 right-hand-side rows included) and the
 // backward substitution (at most 8 rows) on padded buffers the caller filled; see there.
 int td_chol_batch_forward(td_handle* h, double* a_dev, double* rt_dev, double* linv_dev, double* tol_dev, int np,
                           int n_real, int nrhs, int batch, int rt_rows);

@@ -1,6 +1,7 @@
 // 64 x 64 float64 tile in LDS: Cholesky factor and its inverse on the float64 matrix cores.
-// Shared by the blocked solver (solve.hip: the diagonal blocks of its factorisations) and the one-launch
-// dense stage of a small CCA (eig.hip: cca_small_kernel).
+// Shared by the blocked solver (chol.hip: the diagonal blocks of its factorisations), the one-launch
+// dense stage of a small CCA (eig.hip: cca_small_kernel) and, for the moves of a tile between global memory,
+// registers and LDS, the leave-one-out sweep (loso.hip).
 #ifndef TD_TILE64_H_
 #define TD_TILE64_H_
 
@@ -12,6 +13,72 @@ constexpr int NB = 64;
 constexpr int LS = NB + 2;   // LDS row stride in doubles: conflict-free ds_read_b64 of MFMA operands
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+// ---- 64x64 tile <-> LDS ------------------------------------------------------------
+// Rows are 16-byte aligned (the matrix is padded to a multiple of 64): thread t moves the
+// 16-byte pair (t & 31) of rows (t >> 5) + 8 i -- every wave instruction covers two whole
+// 512-byte rows.
+__device__ __forceinline__ void tile_to_lds(double* lds, const double* __restrict__ g, int ld,
+                                            int rows_valid, int tid) {
+  const int c = (tid & 31) * 2, r0 = tid >> 5;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int r = r0 + 8 * i;
+    f64x2 v = {0.0, 0.0};
+    if (r < rows_valid) v = *reinterpret_cast<const f64x2*>(g + (size_t)r * ld + c);
+    *reinterpret_cast<f64x2*>(lds + r * LS + c) = v;
+  }
+}
+
+// operand tile -> registers (same thread map as tile_to_lds) and registers -> LDS
+__device__ __forceinline__ void tile_to_regs(f64x2 (&v)[8], const double* __restrict__ g, int ld,
+                                             int rows_valid, int tid) {
+  const int c = (tid & 31) * 2, r0 = tid >> 5;
+  if (rows_valid == NB) {
+    // full tile (every tile but the right-hand-side rows): no clamps, no masks, 32-bit offsets
+    // -- the update kernel ran 8 VALU instructions per MFMA (PMC), and VALU issue competes
+    // with the matrix pipe
+    // (uniform row base + ONE 32-bit per-lane byte offset: hipcc then addresses every load as
+    // SGPR base + VGPR offset instead of keeping a 64-bit address pair per load -- the update
+    // kernel sat at 256 VGPRs with spills)
+    const unsigned voff = (unsigned)((r0 * ld + c) * 8);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const char* gi = reinterpret_cast<const char*>(g) + (size_t)(8 * i) * ld * 8;
+      v[i] = *reinterpret_cast<const f64x2*>(gi + voff);
+    }
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int r = r0 + 8 * i;
+    const int rc = r < rows_valid ? r : 0;                 // clamped, zeroed below
+    const f64x2 x = *reinterpret_cast<const f64x2*>(g + (size_t)rc * ld + c);
+    const double m = r < rows_valid ? 1.0 : 0.0;
+    v[i][0] = x[0] * m; v[i][1] = x[1] * m;
+  }
+}
+__device__ __forceinline__ void regs_to_lds(double* lds, const f64x2 (&v)[8], int tid) {
+  const int c = (tid & 31) * 2, r0 = tid >> 5;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) *reinterpret_cast<f64x2*>(lds + (r0 + 8 * i) * LS + c) = v[i];
+}
+
+// C[32 x 64] (+)= As[32 x 64] . Bs^T (kNT) or As . Bs (!kNT); As rows r, Bs 64 x 64, both LDS with
+// stride LS.  4 waves: wave w owns output columns 16 w .. 16 w + 15, both 16-row tiles.
+template <bool kNT>
+__device__ __forceinline__ void gemm_32x64(const double* __restrict__ as, const double* __restrict__ bs,
+                                           int wave, int lane, f64x4 (&acc)[2]) {
+  const int li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int s = 0; s < NB / 4; ++s) {
+    const int k = 4 * s + lk;
+    const double b = kNT ? bs[(16 * wave + li) * LS + k] : bs[k * LS + 16 * wave + li];
+    acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[li * LS + k], b, acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(as[(16 + li) * LS + k], b, acc[1], 0, 0, 0);
+  }
+}
 
 // 1 / sqrt(x) to float64 accuracy: v_rsq_f64 seed + two Newton steps (the seed is good to
 // ~2^-26; a correctly rounded sqrt + divide is a long dependent software sequence and this

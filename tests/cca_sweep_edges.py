@@ -1,5 +1,5 @@
 """The edge cases of the CCA sweep's device call (td_cca_solve_loso_terms, csrc/cca_sweep.hip over the batched
-Cholesky of csrc/solve.hip; tests/test_gpu_cca_sweep_edges.py, tests/test_cpu_cca_sweep_edges.py): the case table, the
+Cholesky of csrc/chol.hip; tests/test_gpu_cca_sweep_edges.py, tests/test_cpu_cca_sweep_edges.py): the case table, the
 data builder, the float64 reference with its derived bound, a restatement of the host arithmetic that picks a route,
 the device's three status rules, and numpy models of a wrong kernel.  A plain module, not a conftest.
 

@@ -1,5 +1,5 @@
-"""The edge cases of the blocked float64 Cholesky and of the leave-one-out preconditioned-CG sweep of csrc/solve.hip
-(tests/test_gpu_chol_edges.py, tests/test_cpu_chol_edges.py): the case tables, the data builders, the float64
+"""The edge cases of the blocked float64 Cholesky (csrc/chol.hip), of the ridge routes over it (csrc/solve.hip) and of
+the leave-one-out preconditioned-CG sweep (csrc/loso.hip) (tests/test_gpu_chol_edges.py, tests/test_cpu_chol_edges.py): the case tables, the data builders, the float64
 references with their derived bounds, restatements of the integer arithmetic by which chol_factor_forward and
 ridge_solve_loso_impl pick their launches, and numpy models of the kernel's algebra, right and wrong.  A plain module,
 not a conftest.
@@ -30,7 +30,7 @@ from tests import cg_edges as ce
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# ---- the constants of solve.hip / td_tile64.h, restated (tests/test_cpu_chol_edges.py reads them from the source) ----
+# ---- the constants of solve_common.h / chol.hip / solve.hip / td_tile64.h, restated (tests/test_cpu_chol_edges.py reads them from the source) ----
 NB = 64               # td_tile64::NB
 MAX_RHS = 8           # kMaxRhs
 OUTER_COLS = 4        # kOuterCols
@@ -46,9 +46,10 @@ CONSTANT_NAMES = {'NB': 'NB', 'kMaxRhs': 'MAX_RHS', 'kOuterCols': 'OUTER_COLS', 
 
 
 def source_constants():
-  """{name in the source: value} of the constants above, read from the text of csrc/solve.hip and csrc/td_tile64.h."""
+  """{name in the source: value} of the constants above, read from the text of the solver files of csrc/ and of
+  csrc/td_tile64.h."""
   found = {}
-  for name in ('solve.hip', 'td_tile64.h'):
+  for name in ('solve_common.h', 'chol.hip', 'solve.hip', 'loso.hip', 'td_tile64.h'):
     with open(os.path.join(ROOT, 'telluride_decoding_amd', 'csrc', name)) as f:
       text = f.read()
     for m in re.finditer(r'constexpr\s+(int|double)\s+(\w+)\s*=\s*([-+.\w]+)\s*;', text):

@@ -1,5 +1,5 @@
 """GPU sweep of the CCA sweep's device call (td_cca_solve_loso_terms, csrc/cca_sweep.hip over the batched Cholesky of
-csrc/solve.hip) at the cases of tests/cca_sweep_edges.py: every output of every (fold, lambda) pair against the float64
+csrc/chol.hip) at the cases of tests/cca_sweep_edges.py: every output of every (fold, lambda) pair against the float64
 reference of that module, built from the device's own float64 moments, within its derived bound -- in effect one
 float32 rounding of the output.  The means bit for bit, the statuses as the reference's three rules give them, the
 refusals, a NaN, and the whole sweep end to end where the call must refuse half of its pairs.

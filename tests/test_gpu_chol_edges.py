@@ -1,5 +1,5 @@
-"""GPU sweep of the blocked float64 Cholesky and the leave-one-out preconditioned-CG solver (csrc/solve.hip) at their
-edges, at the cases of tests/chol_edges.py: td_spd_solve against LAPACK and a numpy model of the kernel's own algebra
+"""GPU sweep of the blocked float64 Cholesky (csrc/chol.hip), the ridge routes over it (csrc/solve.hip) and the
+leave-one-out preconditioned-CG solver (csrc/loso.hip) at their edges, at the cases of tests/chol_edges.py: td_spd_solve against LAPACK and a numpy model of the kernel's own algebra
 by the normwise backward error of each right-hand-side column; the ridge routes (ridge_solve on the factorisation,
 ridge_solve_async, ridge_solve_multi, wide targets) and td_ridge_solve_loso / _terms against np.linalg.solve in float64
 of the systems built from the device's own float64 moments, within the derived bounds of chol_edges (in effect one
