@@ -1374,6 +1374,54 @@ int td_ccacalib_online_finish(td_handle* h, int num_sessions, const void* state_
                               int dims, int64_t frames_emitted, int width, double* corr_dev, double* lda_dev,
                               double* dprime_dev, int32_t* status_dev);
 
+/* ------------------------------------------------------------------ online calibration of a DNN decoder
+ * td_calib_online_push with the fully connected regressor of td_fc_online_push in front of the sums: what
+ * infer_decoder.Decoder.train(data0, data1, window_size = W) takes from a labelled stretch of (eeg, attended
+ * envelope, unattended envelope) rows that arrive in pushes of any length, predicted with the packed parameters
+ * handed to each push.  `num_sessions` independent sessions, one state block each on the device, ONE launch per push
+ * (one workgroup of 256 threads per session), nothing stored per row; however a recording is cut into pushes, the
+ * state is that of one push of the whole recording, bit for bit.  (td_fccalib_: the td_fc_online_* and
+ * td_calib_online_* families are each checked as a closed set against their bindings, so this one has its own.)
+ *
+ * The prediction p of an emitted frame is the float32 value td_fc_online_push returns in `pred` -- td_mlp_forward's
+ * bits, in the operation order stated there.  Frames are emitted `post` rows late with td_online_plan's arithmetic;
+ * env[..., 0] is the attended envelope a, env[..., 1] the unattended one u; windows are average_data's: consecutive,
+ * hop = width, the tail dropped.
+ *
+ * State (td_fccalib_online_state_bytes = td_calib_online_state_bytes; all zeros = a fresh session; the HOST counts
+ * the frames): td_calib_online_push's block byte for byte -- the TD_CALIB_ONLINE_SUMS float64 sums in its order,
+ * advanced in frame order by the same operations (acc += (double)x * (double)y, the Grams G + z_i z_j unfused), then
+ * the EEG tail [pre + post][c] and the envelope tail [post][2] float32, rounded up to 8 bytes.  td_calib_online_sums
+ * and td_calib_online_finish read the head alone and serve this state as they are.
+ *
+ * td_fccalib_online_lds_bytes: (*pass, *bytes) of a launch that emits `emitted` frames: td_fc_online_lds_bytes'
+ * formula and rule -- the 8 (4 pass) bytes that hold a pass's scores and window means there hold its frames'
+ * {1, p, a, u} in float64 here -- against the same budget, TD_FC_ONLINE_LDS_BYTES.
+ *
+ * td_fccalib_online_push: the sessions' next n rows.
+ *   eeg_dev, env_dev and their strides, n, frames_before, c, pre, post, width, flush, state_dev,
+ *   state_session_stride: as td_calib_online_push (n == 0 without flush: nothing is queued; a push that emits
+ *   nothing still rolls the tails)
+ *   hidden_host [num_hidden], params_dev, params_session_stride (elements; 0 = one model for all): as
+ *   td_fc_online_push
+ * No atomics: two runs give the same bits.  With td_profile_enable the launch is bracketed as td_online_push's is.
+ *
+ * TD_ERR_INVALID, before anything is queued and with the state untouched -- the intersection of the two families'
+ * limits: a NULL required pointer, num_sessions outside 1..65535, c outside 1..128, pre or post < 0, more than 64
+ * lags, K = c (pre + 1 + post) > 8192, num_hidden outside 0..4, NULL hidden_host with num_hidden > 0, a hidden layer
+ * outside 1..64 units, a shape whose pass of one frame exceeds the LDS budget, width outside 1..TD_ONLINE_MAX_WIDTH,
+ * n outside 0..TD_ONLINE_MAX_PUSH, frames_before < 0, a row or session stride below a row, a parameter stride that is
+ * neither 0 nor a whole model, a state stride below the state block or not a multiple of 8. */
+int td_fccalib_online_state_bytes(int c, int pre, int post, int64_t* bytes);
+int td_fccalib_online_lds_bytes(int c, int pre, int post, int num_hidden, const int* hidden_host, int64_t emitted,
+                                int* pass, int64_t* bytes);
+int td_fccalib_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t eeg_ld,
+                           int64_t eeg_session_stride, const float* env_dev, int64_t env_ld,
+                           int64_t env_session_stride, int64_t n, int64_t frames_before, int c, int pre, int post,
+                           const int* hidden_host, int num_hidden, const float* params_dev,
+                           int64_t params_session_stride, int width, int flush, void* state_dev,
+                           int64_t state_session_stride);
+
 /* ------------------------------------------------------------------ ingestion
  * ingest.find_mean_std, ingest.normalize_data and ingest.convert_data_to_tfrecords (ingest.py:1061-1172).
  *

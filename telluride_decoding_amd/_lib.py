@@ -226,6 +226,12 @@ SIGNATURES = {
     'td_ccacalib_online_sums': [_vp, _i, _vp, _i64, _i, _vp],
     # h, sessions | state, stride | dims | frames_emitted, width | corr, lda, dprime, status
     'td_ccacalib_online_finish': [_vp, _i, _vp, _i64, _i, _i64, _i, _vp, _vp, _vp, _vp],
+    'td_fccalib_online_state_bytes': [_i, _i, _i, _pi64],
+    'td_fccalib_online_lds_bytes': [_i, _i, _i, _i, _c.POINTER(_i), _i64, _c.POINTER(_i), _pi64],
+    # h, sessions | eeg, ld, stride | env, ld, stride | n, frames_before | c, pre, post | hidden, num_hidden | params,
+    # stride | width, flush | state, stride
+    'td_fccalib_online_push': [_vp, _i] + [_vp, _i64, _i64] * 2 + [_i64, _i64] + [_i, _i, _i] +
+                              [_c.POINTER(_i), _i] + [_vp, _i64] + [_i, _i] + [_vp, _i64],
     'td_ingest_moments': [_vp, _c.POINTER(_vp), _pi64, _pi64, _c.POINTER(_i), _i, _i, _vp],
     'td_ingest_normalize': [_vp, _vp, _i, _i64, _i64, _i, _pd, _pd, _i, _i, _i, _i, _vp, _i64],
     'td_tfrecord_encode': [_vp, _c.c_char_p, _i, _i, _c.POINTER(_vp), _pi64, _c.POINTER(_i), _c.POINTER(_i),

@@ -1,5 +1,5 @@
-// What the online push kernels share (online.hip, online_cca.hip, online_dnn.hip, online_calib.hip and, through
-// online_cca_common.h, online_cca_calib.hip): the state block's layout, the plan of a push, and the blocks of a push
+// What the online push kernels share (online.hip, online_cca.hip, online_calib.hip, through online_dnn_common.h
+// online_dnn.hip and online_dnn_calib.hip and, through online_cca_common.h, online_cca_calib.hip): the state block's layout, the plan of a push, and the blocks of a push
 // kernel that every session repeats -- stage, (predict: each file's own, the FIR prediction here for the two files
 // that use it), score, windows, tails.  The host interface is td_common.h.  online_fit.hip and online_cca_fit.hip
 // take, through online_fit_common.h, the plan of a push, the wave sum and the host checks of the strides and the

@@ -26,7 +26,7 @@ struct td_handle {
   // kernels that opted in to more than 64 KB of dynamic LDS on this handle's device
   bool lds_opt_lagcov = false, lds_opt_virt = false, lds_opt_fir = false, lds_opt_fir_stream = false, lds_opt_proj_stream = false;
   bool lds_opt_online = false, lds_opt_online_cca = false, lds_opt_online_dnn = false, lds_opt_online_calib = false;
-  bool lds_opt_online_ccacalib = false;
+  bool lds_opt_online_ccacalib = false, lds_opt_online_dnn_calib = false;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;  // the one work is queued on (own or adopted)
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;

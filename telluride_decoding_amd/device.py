@@ -2199,6 +2199,66 @@ def online_ccacalib_finish(state, dims, frames_emitted, width, handle=None):
                        frames_emitted, width, handle)
 
 
+# ---------------------------------------------------------------- online calibration of a DNN decoder
+def online_dnn_calib_state_bytes(c, pre, post):
+  """Bytes of one online DNN calibration session's state block (td_fccalib_online_state_bytes):
+  online_calib_state_bytes', byte for byte -- online_calib_sums and online_calib_finish serve the state as they are."""
+  return _lib_values('td_fccalib_online_state_bytes', (int(c), int(pre), int(post)))[0]
+
+
+def online_dnn_calib_lds_bytes(c, pre, post, hidden, emitted=64):
+  """(frames per pass, LDS bytes) of a td_fccalib_online_push launch that emits `emitted` frames
+  (td_fccalib_online_lds_bytes); ValueError for a shape outside the limits or over the byte budget."""
+  hid, hid_p = _i32_array(list(hidden) or [0])
+  return tuple(_lib_values('td_fccalib_online_lds_bytes', (int(c), int(pre), int(post), len(hidden), hid_p,
+                                                           int(emitted)), _I32_I64))
+
+
+def online_dnn_calib_push(eeg, env, params, hidden, state, frames_before, pre, post, width, flush=False, handle=None):
+  """One push of a bank of online DNN calibration sessions, in one launch (td_fccalib_online_push).
+
+  eeg [S, n, c] and env [S, n, 2] (attended, unattended): float32 device tensors with unit column stride (None for a
+  flush without rows); params [S or 1, P] float32: the packed parameters of td_mlp_* ([W1, b1, W2, b2, ...], one
+  output) of a network with the hidden layers `hidden` on c (pre + 1 + post) inputs -- one row: the model every
+  session shares; read where they are at every push; state: uint8 device tensor [S, >=
+  online_dnn_calib_state_bytes()] with a row stride that is a multiple of 8, updated in place; frames_before: rows
+  pushed so far; width: the window of the LDA's training data.  Returns the rows pushed after the call.  Queued, not
+  waited for."""
+  h = handle or default_handle()
+  torch = _torch()
+  who = 'online_dnn_calib_push'
+  sessions, stride = _check_fit_state(who, h, state)
+  hidden = [int(v) for v in hidden]
+  nl = int(pre) + 1 + int(post)
+  if params.dim() != 2 or int(params.shape[0]) not in (1, sessions):
+    raise ValueError('%s: params of %s for %d sessions ([S or 1, P])' % (who, tuple(params.shape), sessions))
+  # P = k h1 + the rest: k from the parameter count (as dnn_online_push)
+  first = hidden[0] if hidden else 1
+  count = int(params.shape[1])
+  k = (count - dnn_param_count(0, hidden)) // first if first > 0 else 0
+  if nl < 1 or k < 1 or k % nl or dnn_param_count(k, hidden) != count:
+    raise ValueError('%s: %d parameters for hidden layers %s on %d lags' % (who, count, hidden, nl))
+  c = k // nl
+  n = 0 if eeg is None else int(eeg.shape[1])
+  if eeg is not None and (tuple(eeg.shape) != (sessions, n, c) or env is None or
+                          tuple(env.shape) != (sessions, n, 2)):
+    raise ValueError('%s: eeg of %s and env of %s for %d sessions of %d channels' %
+                     (who, tuple(eeg.shape), None if env is None else tuple(env.shape), sessions, c))
+  _check_tensors(who, h, (('eeg', eeg, torch.float32), ('env', env, torch.float32),
+                          ('params', params, torch.float32)), short=True)
+  if n > 0 and (eeg.stride(2) != 1 and c > 1 or env.stride(2) != 1):
+    raise ValueError('%s: the columns of eeg and env must be contiguous' % who)
+  if params.stride(1) != 1 and count > 1:
+    params = params.contiguous()
+  shared = int(params.shape[0]) == 1
+  hid, hid_p = _i32_array(hidden or [0])
+  h.check(h.lib.td_fccalib_online_push(
+      h.ptr, sessions, *_row_block(eeg, n, sessions, c), *_row_block(env, n, sessions, 2), n, int(frames_before), c,
+      int(pre), int(post), hid_p, len(hidden), _ptr(params), 0 if shared else int(params.stride(0)), int(width),
+      1 if flush else 0, _ptr(state), stride))
+  return int(frames_before) + n
+
+
 # ---------------------------------------------------------------- fully connected regressor / match-mismatch classifier
 MLP_LOSSES = {'mse': 0, 'pearson': 1}
 

@@ -90,6 +90,15 @@ one Cholesky solve, no eigenproblem --, and `OnlineDecoder.set_cca_statistics` t
     c = cca_calib.finish()
     online.set_cca_statistics(c.corr, c.lda)
 
+A DNN bank cannot be fitted online, but it can be calibrated: `OnlineDNNCalibration` is `OnlineCalibration` with the
+bank's network in front of the sums -- ONE td_fccalib_online_push launch per push, the prediction that of
+td_fc_online_push bit for bit, the same state block and the same finish -- so a network trained offline on other
+sessions is scored with the new listener's statistics and LDA:
+
+    dnn_calib.push(eeg, attended_envelope, unattended_envelope)
+    r = dnn_calib.finish()
+    online.set_statistics(r.corr, r.lda)
+
 Without a GPU (`device.gpu_available()` false) the same object runs a NumPy session with the same
 semantics -- float64 throughout, window sums in frame order, td_online_plan's arithmetic -- so that the logic can
 be built and tested anywhere.  (The state-space decoder has no host form: 'ssd' needs the GPU.)
@@ -485,7 +494,7 @@ class _HostDnnSession(_HostSession):
 
 
 class _Bank(object):
-  """What the six online banks share: S sessions that run on the device (`_dev`: a dict with the handle 'h' and the
+  """What the seven online banks share: S sessions that run on the device (`_dev`: a dict with the handle 'h' and the
   zeroed uint8 'state' [S, bytes]) or as NumPy sessions (`_host`: a list of S objects with reset()), and refuse pushes
   once flushed.  A class gives FLUSHED, its sentence for that refusal."""
   FLUSHED = None
@@ -1643,8 +1652,8 @@ MAX_FIT_PUSH = 1048576                     # TD_ONLINE_MAX_PUSH
 
 
 class _TrainingBank(_Bank):
-  """What the four training banks share (OnlineRidgeFit, OnlineCCAFit, OnlineCalibration, OnlineCCACalibration): rows
-  arrive in pushes of any length, the frames counted run `delay` rows behind them until a flush counts the rest, and a
+  """What the five training banks share (OnlineRidgeFit, OnlineCCAFit, OnlineCalibration, OnlineDNNCalibration,
+  OnlineCCACalibration): rows arrive in pushes of any length, the frames counted run `delay` rows behind them until a flush counts the rest, and a
   push is one device call or one call per NumPy session.  A class gives LAST_ROWS (flush's sentence for some of the
   last rows), _blocks(*rows) (the arguments of a push as [S, n, .] blocks, the EEG first), _no_blocks() (what the
   NumPy sessions take for a flush without rows), _session_push(sess, i, blocks, flush) and _device_push(blocks,
@@ -2286,7 +2295,7 @@ class _HostCalibSession(object):
 
 
 class _CalibrationBank(_TrainingBank):
-  """What the two calibration banks share: an OnlineDecoder bank of one kind whose sessions, context and current
+  """What the three calibration banks share: an OnlineDecoder bank of one kind whose sessions, context and current
   model they take, windows of window_size frames, sums in float64 at the head of the state, and a closed form over
   them with a status per session.  A class gives BANK (the decoder's kind, its words for it, whose the other kinds
   are), REASONS (status -> sentence), _reason_values() beyond width and frames, _closed_form(sums) and
@@ -2357,37 +2366,12 @@ class _CalibrationBank(_TrainingBank):
     return o
 
 
-class OnlineCalibration(_CalibrationBank):
-  """The online chain's last training stage: the correlation statistics, the scaled LDA and d' that
-  infer_decoder.Decoder.train(data0, data1, window_size=W) would take from a labelled stretch -- data0 the
-  (unattended envelope, prediction) frames, data1 the (attended envelope, prediction) frames -- for rows that arrive
-  in pushes of any length, predicted with the bank's CURRENT weights, in ONE td_calib_online_push launch per push and
-  with nothing stored per row:
-
-      fit.push(eeg, att); w, b = fit.solve([lam]); decoder.set_weights(w[:, 0, :, 0], b[:, 0, 0])
-      calib = OnlineCalibration(decoder, window_size=100)
-      for eeg, att, unatt in calibration_chunks:         # [n, C], [n], [n] float32, any n
-        calib.push(eeg, att, unatt)
-      r = calib.finish()                                 # CalibrationResult(corr, lda, dprime), on the device
-      decoder.set_statistics(r.corr, r.lda)              # device to device
-
-  decoder: a linear OnlineDecoder bank; the sessions, the channels and the context are the bank's, and every push
-  reads the bank's weights where they are, so the calibrator follows set_weights.  window_size: the frames averaged
-  into one training point of the LDA (decoding.train_lda_model's correlation_frames, default 100; <= 1: every
-  frame).  Windows are infer_decoder.average_data's: consecutive, the tail dropped.  A frame needs post_context rows
-  of future EEG, so the sums run that far behind the input; flush() ends the recording.  finish() can be called at
-  any time and leaves the state alone.  Any cut of a recording gives the same state bytes (sums()).
-
-  Without a GPU the same object runs a NumPy session of the same semantics (float64 prediction)."""
-  LAST_ROWS = 'OnlineCalibration.flush takes the last rows as eeg AND both envelopes, or nothing.'
-  BANK = ('linear', 'a linear bank', 'CCA and DNN calibration are out of scope')
+class _EnvelopeCalibration(_CalibrationBank):
+  """What OnlineCalibration and OnlineDNNCalibration share -- everything but the prediction: pushes of (eeg, attended
+  envelope, unattended envelope) rows, td_calib_online_push's state block, whose 29 sums td_calib_online_sums reads
+  and td_calib_online_finish closes, and the LinearRegressionDecoder that takes the result.  A class gives LAST_ROWS,
+  BANK, its constructor, _session_push and _device_push."""
   REASONS = _CALIB_REASONS
-
-  def __init__(self, decoder, window_size=100):
-    self._take(decoder, window_size)
-    shape = (self.channels, self.pre, self.post)
-    self._allocate(self.post, lambda: device.online_calib_state_bytes(*shape),
-                   lambda: _HostCalibSession(*shape, self.window_size))
 
   # -- pushes ------------------------------------------------------------------------------------
   def push(self, eeg, attended, unattended):
@@ -2408,18 +2392,12 @@ class OnlineCalibration(_CalibrationBank):
   def _no_blocks(self):
     return self._no_rows(self.channels), self._no_rows(2)
 
-  def _session_push(self, sess, i, blocks, flush):
-    p = self.decoder._params[i]
-    sess.push(np.asarray(blocks[0][i], np.float64), np.asarray(blocks[1][i], np.float64), p['w'], p['b'],
-              self.rows_pushed, flush)
-
-  def _device_push(self, blocks, flush):
-    d, bank = self._dev, self.decoder._dev
+  def _device_rows(self, blocks):
+    """(eeg, env) of a device push as device tensors; (None, None) without rows."""
     eeg, env = blocks or (None, None)
     if blocks is not None and not hasattr(eeg, 'is_cuda'):
-      eeg, env = self._upload(d['h'], eeg), self._upload(d['h'], env)
-    device.online_calib_push(eeg, env, bank['w'], bank['b'], d['state'], self.rows_pushed, self.pre, self.post,
-                             self.window_size, c=self.channels, flush=flush, handle=d['h'])
+      eeg, env = self._upload(self._dev['h'], eeg), self._upload(self._dev['h'], env)
+    return eeg, env
 
   # -- what the state holds ----------------------------------------------------------------------
   def sums(self):
@@ -2465,6 +2443,111 @@ class OnlineCalibration(_CalibrationBank):
                                   [vec(o['class_means'][0]), vec(o['class_means'][1])], float(o['slope']),
                                   float(o['intercept'])))
     return float(o['dprime'])
+
+
+class OnlineCalibration(_EnvelopeCalibration):
+  """The online chain's last training stage: the correlation statistics, the scaled LDA and d' that
+  infer_decoder.Decoder.train(data0, data1, window_size=W) would take from a labelled stretch -- data0 the
+  (unattended envelope, prediction) frames, data1 the (attended envelope, prediction) frames -- for rows that arrive
+  in pushes of any length, predicted with the bank's CURRENT weights, in ONE td_calib_online_push launch per push and
+  with nothing stored per row:
+
+      fit.push(eeg, att); w, b = fit.solve([lam]); decoder.set_weights(w[:, 0, :, 0], b[:, 0, 0])
+      calib = OnlineCalibration(decoder, window_size=100)
+      for eeg, att, unatt in calibration_chunks:         # [n, C], [n], [n] float32, any n
+        calib.push(eeg, att, unatt)
+      r = calib.finish()                                 # CalibrationResult(corr, lda, dprime), on the device
+      decoder.set_statistics(r.corr, r.lda)              # device to device
+
+  decoder: a linear OnlineDecoder bank; the sessions, the channels and the context are the bank's, and every push
+  reads the bank's weights where they are, so the calibrator follows set_weights.  window_size: the frames averaged
+  into one training point of the LDA (decoding.train_lda_model's correlation_frames, default 100; <= 1: every
+  frame).  Windows are infer_decoder.average_data's: consecutive, the tail dropped.  A frame needs post_context rows
+  of future EEG, so the sums run that far behind the input; flush() ends the recording.  finish() can be called at
+  any time and leaves the state alone.  Any cut of a recording gives the same state bytes (sums()).
+
+  Without a GPU the same object runs a NumPy session of the same semantics (float64 prediction)."""
+  LAST_ROWS = 'OnlineCalibration.flush takes the last rows as eeg AND both envelopes, or nothing.'
+  BANK = ('linear', 'a linear bank', 'OnlineCCACalibration and OnlineDNNCalibration are the other banks\'')
+
+  def __init__(self, decoder, window_size=100):
+    self._take(decoder, window_size)
+    shape = (self.channels, self.pre, self.post)
+    self._allocate(self.post, lambda: device.online_calib_state_bytes(*shape),
+                   lambda: _HostCalibSession(*shape, self.window_size))
+
+  def _session_push(self, sess, i, blocks, flush):
+    p = self.decoder._params[i]
+    sess.push(np.asarray(blocks[0][i], np.float64), np.asarray(blocks[1][i], np.float64), p['w'], p['b'],
+              self.rows_pushed, flush)
+
+  def _device_push(self, blocks, flush):
+    d, bank = self._dev, self.decoder._dev
+    eeg, env = self._device_rows(blocks)
+    device.online_calib_push(eeg, env, bank['w'], bank['b'], d['state'], self.rows_pushed, self.pre, self.post,
+                             self.window_size, c=self.channels, flush=flush, handle=d['h'])
+
+
+# ------------------------------------------------------------------------------------------ the online DNN calibration
+class _HostDnnCalibSession(_HostCalibSession):
+  """One online DNN calibration session in NumPy: the semantics of td_fccalib_online_push with a float64 prediction
+  (_HostDnnSession._predict's), the sums of calibration_walk."""
+
+  def push(self, eeg, env, params, frames_before, flush):
+    """eeg [n, c], env [n, 2] float64 behind frames_before rows, predicted with the session parameters `params`
+    (dnn_session_parameters: its weights)."""
+    post = self.post
+    rows, self.tail = _session_rows(self.tail, eeg, post, flush)
+    envs, self.env_tail = _session_rows(self.env_tail, env, post, False)
+    first, emitted, i0 = _session_frames(frames_before, eeg.shape[0], post, flush)
+    self.p = params                                  # (what _predict reads: c, pre, post, weights)
+    pred = _HostDnnSession._predict(self, rows, i0, emitted)
+    truth = envs[i0:i0 + emitted]
+    calibration_walk(self.sums, pred, truth[:, 0], truth[:, 1], first, self.width)
+    return emitted
+
+
+class OnlineDNNCalibration(_EnvelopeCalibration):
+  """OnlineCalibration for a DNN bank: the correlation statistics, the scaled LDA and d' that
+  infer_decoder.Decoder.train(data0, data1, window_size=W) would take from a labelled stretch, for rows that arrive in
+  pushes of any length, predicted with the bank's network -- td_fc_online_push's prediction, bit for bit -- in ONE
+  td_fccalib_online_push launch per push and with nothing stored per row.  A network trained offline on other
+  sessions is so scored with the new listener's statistics, not the training set's:
+
+      decoder = OnlineDecoder(dnn_decoder, window_size=500)   # a LinearRegressionDecoder around a BrainModelDNN
+      calib = OnlineDNNCalibration(decoder, window_size=100)
+      for eeg, att, unatt in calibration_chunks:         # [n, C], [n], [n] float32, any n
+        calib.push(eeg, att, unatt)
+      r = calib.finish()                                 # CalibrationResult(corr, lda, dprime), on the device
+      decoder.set_statistics(r.corr, r.lda)              # device to device
+
+  decoder: a DNN OnlineDecoder bank; the sessions, the channels, the context and the hidden layers are the bank's,
+  and every push reads the bank's packed parameters where they are on the device.  window_size, the windows, the
+  delay of post_context rows, flush(), sums(), finish() and update_decoder(): OnlineCalibration's -- the state block
+  is td_calib_online_push's byte for byte, and td_calib_online_sums / td_calib_online_finish serve it.  Any cut of a
+  recording gives the same state bytes.
+
+  Without a GPU the same object runs a NumPy session of the same semantics (float64 prediction)."""
+  LAST_ROWS = 'OnlineDNNCalibration.flush takes the last rows as eeg AND both envelopes, or nothing.'
+  BANK = ('dnn', 'a DNN bank', 'OnlineCalibration is the linear bank\'s, OnlineCCACalibration the CCA bank\'s')
+
+  def __init__(self, decoder, window_size=100):
+    self._take(decoder, window_size)
+    self.hidden = list(decoder.hidden)
+    shape = (self.channels, self.pre, self.post)
+    device.online_dnn_calib_lds_bytes(*shape, self.hidden, 1)   # (a shape over the LDS budget: refused by name)
+    self._allocate(self.post, lambda: device.online_dnn_calib_state_bytes(*shape),
+                   lambda: _HostDnnCalibSession(*shape, self.window_size))
+
+  def _session_push(self, sess, i, blocks, flush):
+    sess.push(np.asarray(blocks[0][i], np.float64), np.asarray(blocks[1][i], np.float64), self.decoder._params[i],
+              self.rows_pushed, flush)
+
+  def _device_push(self, blocks, flush):
+    d, bank = self._dev, self.decoder._dev
+    eeg, env = self._device_rows(blocks)
+    device.online_dnn_calib_push(eeg, env, bank['params'], self.hidden, d['state'], self.rows_pushed, self.pre,
+                                 self.post, self.window_size, flush=flush, handle=d['h'])
 
 
 # ------------------------------------------------------------------------------------------ the online CCA calibration
@@ -2632,7 +2715,7 @@ class OnlineCCACalibration(_CalibrationBank):
 
   Without a GPU the same object runs a NumPy session of the same semantics (float64 projections)."""
   LAST_ROWS = 'OnlineCCACalibration.flush takes the last rows as eeg AND both feature blocks, or nothing.'
-  BANK = ('cca', 'a CCA bank', 'OnlineCalibration is the linear bank\'s')
+  BANK = ('cca', 'a CCA bank', 'OnlineCalibration is the linear bank\'s, OnlineDNNCalibration the DNN bank\'s')
   REASONS = _CCA_CALIB_REASONS
 
   def __init__(self, decoder, window_size=100):
