@@ -1,6 +1,8 @@
 // Decode side of the hot path, the prediction (SURVEY.md 8a rows A3'/A4 forward):
 // FIR prediction on the never-materialised lag view and the CCA projection.  The windowed
 // correlation sums, per-window scores and the attended-speaker decision are windows.hip.
+#include <type_traits>
+
 #include "decode_common.h"
 
 namespace {
@@ -175,6 +177,7 @@ __global__ __launch_bounds__(kThreads, 2) void predict_fir_mfma_kernel(
   const long long rb = ts - pre;
   const int nb = (st_len + nl - 1 + 31) / 32;
   const int li = lane & 31, lh = lane >> 5;
+  const int lag_pad = nl & 31;                 // live columns of an output's last tile (0: all 32)
 
   // Loads of one 32-row block, fully coalesced: instruction m of chunk ch covers rows
   // 4m..4m+3 (1 KiB contiguous when ldx = 64); lane l fetches row 4m + (l >> 4), 16-byte
@@ -350,8 +353,18 @@ __global__ __launch_bounds__(kThreads, 2) void predict_fir_mfma_kernel(
       // the end of a block the same LDS space first transposes the next block's rows
       if (nt == nt_count - 1 && j + 1 < nb) transpose_block(nxt, cur);
       // C/D map: col = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * lh
+      // The lags that pad an output's last tile have zero weights, but 0 * NaN is NaN inside the MFMA and
+      // the diagonal sums take all 32 columns: a non-finite sample would spoil outputs whose window does
+      // not hold it (and, through ring slots already written out, one `ring` frames later).  Their columns
+      // are written as the zeros they are on finite data; a wave-uniform test, never true at 32 k lags.
+      if (lag_pad && nt - (nt / tpq) * tpq == tpq - 1) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) tbuf[((r & 3) + 8 * (r >> 2) + 4 * lh) * 33 + li] = acc[r];
+        for (int r = 0; r < 16; ++r)
+          tbuf[((r & 3) + 8 * (r >> 2) + 4 * lh) * 33 + li] = li < lag_pad ? acc[r] : 0.f;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tbuf[((r & 3) + 8 * (r >> 2) + 4 * lh) * 33 + li] = acc[r];
+      }
       __builtin_amdgcn_wave_barrier();
       p_rel0 = rel0;
       p_nt = nt;
@@ -439,6 +452,11 @@ __global__ __launch_bounds__(NL * DQ == 32 ? 256 : 128) void predict_fir_wave_ke
 #pragma unroll
   for (int k = 0; k < P; ++k) xr[k] = load_row(u0 + k);
 
+  // kPad: the filter is shorter than NL taps.  The padding taps have zero weight, but fmaf(NaN, 0, acc) is
+  // NaN: a non-finite sample would spoil the NL - nl outputs in front of its window, so they are kept out
+  // of the accumulators (a wave-uniform test per tap); a filter of NL taps runs the loop without it.
+  auto walk = [&](auto pad) {
+  constexpr bool kPad = decltype(pad)::value;
   for (int b = 0; b < n_body; ++b) {
     const long long ub = u0 + (long long)b * NL;
 #pragma unroll
@@ -449,6 +467,7 @@ __global__ __launch_bounds__(NL * DQ == 32 ? 256 : 128) void predict_fir_wave_ke
 #pragma unroll
       for (int l = 0; l < NL; ++l) {
         const int slot = (i - l) & (NL - 1);
+        if (kPad && l >= nl) continue;
 #pragma unroll
         for (int q = 0; q < DQ; ++q)
           acc[slot][q] = (l == 0) ? xv * wt[0][q] : fmaf(xv, wt[l][q], acc[slot][q]);
@@ -480,6 +499,8 @@ __global__ __launch_bounds__(NL * DQ == 32 ? 256 : 128) void predict_fir_wave_ke
       *o = s + (accumulate ? *o : (bias ? bias[q0 + q] : 0.f));
     }
   }
+  };
+  if (nl == NL) walk(std::false_type{}); else walk(std::true_type{});
 }
 
 // bias[k] = -sum_f mean[f] * rot[f][k]   (CCA centring folded into the FIR bias)
@@ -721,10 +742,14 @@ __global__ __launch_bounds__(64 * kProjWaves, 3) void cca_project_kernel(ProjPar
     pj_f32x4 acc[2];
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      pj_f32x4 c = {0.f, 0.f, 0.f, 0.f};
+      // one accumulator per view: W is block diagonal, but a NaN / Inf of one view times the zero block is NaN,
+      // and a row's outputs of the OTHER view must stay finite (as must those of rows only that view has,
+      // whose loads of this view are clamped).  On finite data the zero block adds exact zeros: the same bits.
+      pj_f32x4 cx = {0.f, 0.f, 0.f, 0.f}, cy = cx;
       const float* row = tile + (16 * half + li) * kLd + 8 * kq;
 #pragma unroll
       for (int s2 = 0; s2 < kSteps; ++s2) {
+        pj_f32x4& c = s2 < 2 ? cx : cy;
         float v[8];
         if (s2 < 2 || (64 + 8 * kq) < 64 + ((p.c2 + 7) & ~7)) {
           const float4 v0 = *reinterpret_cast<const float4*>(row + 32 * s2);
@@ -750,7 +775,8 @@ __global__ __launch_bounds__(64 * kProjWaves, 3) void cca_project_kernel(ProjPar
         TD_PMFMA(zm, wh[s2]); TD_PMFMA(zh, wm[s2]); TD_PMFMA(zh, wh[s2]);
 #undef TD_PMFMA
       }
-      acc[half] = c;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[half][r] = li < p.dims ? cx[r] : cy[r];
     }
     // C/D map: col = lane & 15 (output), row = 4 (lane >> 4) + r: back through the tile, [32][16]
     __builtin_amdgcn_wave_barrier();

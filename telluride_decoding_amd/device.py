@@ -559,11 +559,12 @@ def predict_fir_per_file(x, file_offsets, w, b, pre, post, out=None, handle=None
 
 
 def cca_transform(x, x2, file_offsets, mean1, rot1, mean2, rot2, pre1, post1, pre2, post2,
-                  handle=None, input_offset=0):
+                  handle=None, input_offset=0, out=None):
   h = handle or default_handle()
   rows = int(x.shape[0])
   dims = int(rot1.shape[1])
-  out = h.empty((rows, 2 * dims), 'float32')
+  if out is None:
+    out = h.empty((rows, 2 * dims), 'float32')
   offs, offs_p = _lib.i64_array(file_offsets)
   h.check(h.lib.td_cca_transform(
       h.ptr, _ptr(x), x.stride(0), int(x.shape[1]), pre1, post1, _ptr(x2), x2.stride(0),

@@ -30,19 +30,21 @@ def _d64(h, v):
   return h.to_device(np.asarray(v, np.float64).reshape(-1, 1), np.float64).reshape(-1)
 
 
+# (the route of each shape is the one tests/fir_edges.fir_route restates; the accuracy test of every route of the ladder is
+# tests/test_gpu_fir_edges.py, of the streamed kernel the three tests below)
 @pytest.mark.parametrize('c,pre,post,d,lens,off', [
-    (64, 0, 31, 1, (1000, 300, 257), 0),
-    (16, 2, 3, 2, (700, 64), 0),
-    (5, 0, 0, 1, (513,), 0),
-    (70, 3, 40, 3, (900,), 0),          # > 64 channels and > 32 lags: chunk loops
-    (8, 1, 2, 1, (400, 300), 2),        # input_offset drops leading x rows per file
-    (4, 6, 6, 1, (5, 3, 700), 0),       # files shorter than the context
-    (63, 0, 31, 1, (1500, 200), 0),     # unaligned rows: lane-per-channel kernel, 32 taps
-    (69, 2, 10, 3, (800, 333), 1),      # two channel passes, outputs in pairs
-    (64, 0, 31, 20, (3000, 500), 0),    # 20 outputs (a lambda sweep): several output groups
-    (48, 5, 8, 11, (2048,), 0),
-    (7, 0, 0, 9, (640,), 0),            # no lags, more outputs than one pass holds
-    (130, 1, 1, 2, (300, 77), 0),       # three channel passes of the short-filter variant
+    (64, 0, 31, 1, (1000, 300, 257), 0),  # one output: the streamed kernel (fir_stream_kernel), as every d = 1 below
+    (16, 2, 3, 2, (700, 64), 0),        # matrix-core kernel, one group of two outputs
+    (5, 0, 0, 1, (513,), 0),            # streamed kernel, 4-byte DMA
+    (70, 3, 40, 3, (900,), 0),          # > 64 channels and > 32 lags: the VALU kernel's chunk loops, passes <2> + <1>
+    (8, 1, 2, 1, (400, 300), 2),        # input_offset drops leading x rows per file (streamed kernel)
+    (4, 6, 6, 1, (5, 3, 700), 0),       # files shorter than the context (streamed kernel)
+    (63, 0, 31, 1, (1500, 200), 0),     # unaligned rows, 32 taps: the streamed kernel by 4-byte DMA
+    (69, 2, 10, 3, (800, 333), 1),      # lane-per-channel kernel <32, 2>: two channel passes, outputs in pairs
+    (64, 0, 31, 20, (3000, 500), 0),    # 20 outputs (a lambda sweep): matrix-core kernel, seven groups of <= 3
+    (48, 5, 8, 11, (2048,), 0),         # matrix-core kernel, four groups
+    (7, 0, 0, 9, (640,), 0),            # no lags, unaligned: lane-per-channel kernel <4, 8>, two output passes
+    (130, 1, 1, 2, (300, 77), 0),       # three channel passes of the short-filter variant <4, 8>
 ])
 def test_predict_fir_matches_dense_forward(dev, c, pre, post, d, lens, off):
   rng = np.random.default_rng(c * 100 + pre)
