@@ -173,18 +173,9 @@ int td_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t
   p.pass = emitted_now < kPass ? (emitted_now > 1 ? (int)emitted_now : 1) : kPass;
   p.state = reinterpret_cast<unsigned char*>(state_dev); p.state_ss = state_session_stride;
   p.scores = scores_dev; p.decisions = decisions_dev; p.pred = pred_dev; p.frame = frame_dev;
-  if (!h->lds_opt_online) {
-    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&online_push_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_bytes(kMaxChannels, kMaxLags, kMaxLags - 1, kPass)));
-    h->lds_opt_online = true;
-  }
-  TD_TRY(td_profile_mark(h, true, (double)n * num_sessions));
-  hipLaunchKernelGGL(online_push_kernel, dim3((unsigned)num_sessions), dim3(kThreads), lds_bytes(c, nl, post, p.pass),
-                     h->stream, p);
-  TD_HIP(h, hipGetLastError());
-  TD_TRY(td_profile_mark(h, false, 0.0));
-  return TD_OK;
+  return launch_push(h, &h->lds_opt_online, online_push_kernel, num_sessions, kThreads,
+                     lds_bytes(kMaxChannels, kMaxLags, kMaxLags - 1, kPass), lds_bytes(c, nl, post, p.pass),
+                     (double)n * num_sessions, p);
 }
 
 }  // extern "C"

@@ -8,32 +8,25 @@
 // One pass is enough.  train needs two because the per-frame correlation (x - mean_x)(p - mean_y) / power (x the
 // truth, p the prediction) takes the FINAL statistics; but a window mean of it is affine in three per-window sums,
 //   m_w = (sum x p - mean_y sum x - mean_x sum p + W mean_x mean_y) / (W power),
-// so the state keeps, in float64, none of them a function of the final statistics:
-//   [0, 6)    the correlator's sums over every emitted frame: sum p, sum p^2, sum a, sum a^2, sum u, sum u^2
-//   [6, 15)   class 0 (truth u) over the windows completed so far: sum_w z [3], then the upper triangle of
-//             sum_w z z^T in the order (0,0) (0,1) (0,2) (1,1) (1,2) (2,2), with z = (sum x p, sum x, sum p)
-//   [15, 24)  class 1 (truth a), the same
-//   [24, 29)  the open window's running sums: sum p, sum a, sum a p, sum u, sum u p
-// then the EEG tail [pre + post][c] and the envelope tail [post][2] in float32, as td_online_push's block carries
+// so the state keeps, in float64, none of them a function of the final statistics, online_calib_common.h's 29 sums
+// (the layout is there: the correlator's six, per class sum_w z and the upper triangle of sum_w z z^T with
+// z = (sum x p, sum x, sum p), the open window's five), then the EEG tail [pre + post][c] and the envelope tail [post][2] in float32, as td_online_push's block carries
 // them, rounded up to 8 bytes.  Windows are infer_decoder.average_data's: consecutive, hop = width, the tail dropped.
 //
 // The prediction of an emitted frame is the float32 value td_online_push returns in `pred`: the same function
 // (online_common.h's fir_predict, whose bits do not depend on this file's contraction mode).
 //
-// The sums advance in frame order, one lane per state double: the 29 accumulators are independent, so lane t of the
-// first wave owns double t and walks a pass's frames from LDS; a lane of a class sum keeps its own copy of the one or
-// two open-window sums it needs (the same additions in the same order: the same bits as the open window's lanes).
-// A per-frame term is a product of two widened float32 values (or of one and 1.0): exact in float64.  When a frame
-// completes a window the class's sum z takes plain adds, its Gram G + z_i z_j UNFUSED -- z_i z_j rounds, then the
-// add rounds: this file is compiled with fp contract(off), as online_fit.hip is and for its reason -- and the
-// open-window sums return to zero.  So acc += float64(x) * float64(p) and G + np.outer(z, z) in NumPy are a bit-exact
-// twin, and any cut of a recording gives the same state bytes.  The serial walk is intended: pushes are tens to
-// hundreds of frames and the prediction dominates.
+// The sums advance in frame order, one lane per state double: online_calib_common.h's walk, which
+// online_dnn_calib.hip shares -- the head's layout, the lanes' roles, the Gram's G + z_i z_j UNFUSED under that
+// header's fp contract(off) (this file switches it off too, as online_fit.hip does and for its reason).  So
+// acc += float64(x) * float64(p) and G + np.outer(z, z) in NumPy are a bit-exact twin, and any cut of a recording
+// gives the same state bytes.  The serial walk is intended: pushes are tens to hundreds of frames and the prediction
+// dominates.
 //
 // Resources (gfx950, -Rpass-analysis=kernel-resource-usage) are in DESIGN.md section 35.
 #include <cmath>
 
-#include "online_common.h"
+#include "online_calib_common.h"
 
 #pragma clang fp contract(off)
 
@@ -43,17 +36,6 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kMaxChannels = TD_CALIB_ONLINE_MAX_CHANNELS, kMaxLags = TD_CALIB_ONLINE_MAX_LAGS;
 constexpr int kPass = 64;       // emitted frames per pass of a workgroup (fewer for a short push: less LDS)
-constexpr int kSums = TD_CALIB_ONLINE_SUMS;
-constexpr int kOpen = 24;       // the first of the open window's five sums
-
-// (online_common.h's tails behind a head of kSums doubles)
-__host__ __device__ inline long long state_eeg_offset() { return 8LL * kSums; }
-__host__ __device__ inline long long state_env_offset(int c, int pre, int post) {
-  return tail_end(state_eeg_offset(), c, pre + post);
-}
-__host__ __device__ inline long long state_bytes(int c, int pre, int post) {
-  return tails_bytes(state_eeg_offset(), c, pre + post, 2LL * post);
-}
 
 struct CalibParams {
   const float* eeg; long long eeg_ld, eeg_ss;
@@ -65,18 +47,6 @@ struct CalibParams {
   int c, pre, post, width, pass;
   unsigned char* state; long long state_ss;
 };
-
-// What a lane of the walk does with its state double.  A frame's values sit in LDS as {1, p, a, u}; a term is the
-// product of two of them (f0, f1: indices into that quadruple).
-enum : int { kPlain = 0, kOpenSum = 1, kClassSum = 2, kClassGram = 3, kIdle = 4 };
-
-// component `comp` of z = (sum x p, sum x, sum p) for the truth at index `truth` (2: a, 3: u): its two factors and the
-// open-window sum that holds its running value
-__device__ __forceinline__ void z_component(int truth, int comp, int* f0, int* f1, int* open) {
-  if (comp == 0) { *f0 = truth; *f1 = 1; *open = kOpen + (truth == 2 ? 2 : 4); }
-  else if (comp == 1) { *f0 = truth; *f1 = 0; *open = kOpen + (truth == 2 ? 1 : 3); }
-  else { *f0 = 1; *f1 = 0; *open = kOpen; }
-}
 
 __global__ __launch_bounds__(kThreads) void online_calib_push_kernel(CalibParams p) {
   extern __shared__ double lds[];
@@ -101,39 +71,7 @@ __global__ __launch_bounds__(kThreads) void online_calib_push_kernel(CalibParams
 
   for (int k = tid; k < k_all; k += kThreads) w_s[k] = w[k];
 
-  // ---- the walk's lanes: lane t owns state double t
-  int role = kIdle, f0 = 0, f1 = 0, g0 = 0, g1 = 0;
-  double acc = 0.0, r1 = 0.0, r2 = 0.0;
-  if (tid < kSums) {
-    acc = sums[tid];
-    if (tid < 6) {                                           // sum p, p^2, a, a^2, u, u^2
-      role = kPlain;
-      f0 = 1 + (tid >> 1);
-      f1 = (tid & 1) ? f0 : 0;
-    } else if (tid >= kOpen) {                               // sum p, a, a p, u, u p
-      role = kOpenSum;
-      const int j = tid - kOpen;
-      f0 = j == 0 ? 1 : (j <= 2 ? 2 : 3);
-      f1 = (j == 2 || j == 4) ? 1 : 0;
-    } else {
-      const int cls = (tid - 6) / 9, j = (tid - 6) - 9 * cls;
-      const int truth = cls == 1 ? 2 : 3;
-      int open = 0;
-      if (j < 3) {
-        role = kClassSum;
-        z_component(truth, j, &f0, &f1, &open);
-        r1 = sums[open];
-      } else {
-        role = kClassGram;
-        const int e = j - 3;                                 // (0,0) (0,1) (0,2) (1,1) (1,2) (2,2)
-        const int zi = e < 3 ? 0 : (e < 5 ? 1 : 2), zj = e < 3 ? e : (e < 5 ? e - 2 : 2);
-        z_component(truth, zi, &f0, &f1, &open);
-        r1 = sums[open];
-        z_component(truth, zj, &g0, &g1, &open);
-        r2 = sums[open];
-      }
-    }
-  }
+  WalkLane wl = walk_lane(sums, tid);                        // lane t owns state double t
 
   for (long long a = p.e0; a < p.e1; a += pass) {
     const int nf = (int)(p.e1 - a < pass ? p.e1 - a : pass);     // frames [a, a + nf) of this pass
@@ -153,34 +91,7 @@ __global__ __launch_bounds__(kThreads) void online_calib_push_kernel(CalibParams
     }
     __syncthreads();
     // ---- the walk: every sum advances by this pass's frames in frame order
-    if (role != kIdle) {
-      int pos = (int)(a % width);                            // frames of the open window before frame a
-      for (int f = 0; f < nf; ++f) {
-        const double* v = val_s + 4 * f;
-        const double t1 = v[f0] * v[f1];                     // exact
-        const bool done = ++pos == width;
-        if (done) pos = 0;
-        if (role == kPlain) {
-          acc = acc + t1;
-        } else if (role == kOpenSum) {
-          acc = acc + t1;
-          if (done) acc = 0.0;
-        } else if (role == kClassSum) {
-          r1 = r1 + t1;
-          if (done) { acc = acc + r1; r1 = 0.0; }
-        } else {
-          const double t2 = v[g0] * v[g1];
-          r1 = r1 + t1;
-          r2 = r2 + t2;
-          if (done) {
-            const double zz = r1 * r2;                       // rounded, then the add rounds: G + z_i z_j unfused
-            acc = acc + zz;
-            r1 = 0.0;
-            r2 = 0.0;
-          }
-        }
-      }
-    }
+    walk_advance(wl, val_s, (int)(a % width), nf, width);
     __syncthreads();
   }
 
@@ -193,21 +104,12 @@ __global__ __launch_bounds__(kThreads) void online_calib_push_kernel(CalibParams
   env_tail_store<kThreads>(etail, env_s, post, env, p.env_ld, p.n);
   // (every lane read the open sums it copies before the first pass; the barriers since then order these stores
   // behind those loads)
-  if (role != kIdle && p.e1 > p.e0) sums[tid] = acc;
+  if (wl.role != kIdle && p.e1 > p.e0) sums[tid] = wl.acc;
 }
 
 size_t lds_bytes(int c, int nl, int post, int pass) {
   const size_t env_rows = pass > post ? pass : post;
   return sizeof(double) * 4 * pass + sizeof(float) * ((size_t)nl * c + (size_t)(pass + nl - 1) * c + 2 * env_rows);
-}
-
-// grid (ceil(S / 256)): out [S][kSums]
-__global__ __launch_bounds__(kThreads) void online_calib_sums_kernel(const unsigned char* state, long long state_ss,
-                                                                     int num_sessions, double* out) {
-  const long long e = (long long)blockIdx.x * kThreads + threadIdx.x;
-  if (e >= (long long)num_sessions * kSums) return;
-  const int s = (int)(e / kSums), j = (int)(e - (long long)s * kSums);
-  out[e] = reinterpret_cast<const double*>(state + (long long)s * state_ss)[j];
 }
 
 // One class's window-mean moments from its sums: {sum_w m, sum_w m^2} with m = c . z + c0.
@@ -298,13 +200,8 @@ int td_calib_online_push(td_handle* h, int num_sessions, const float* eeg_dev, i
                          int pre, int post, int width, int flush, void* state_dev, int64_t state_session_stride) {
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_calib_online_push: handle is NULL");
   TD_TRY(check_shape(h, "td_calib_online_push", c, pre, post));
-  TD_REQUIRE(h, width >= 1 && width <= TD_ONLINE_MAX_WIDTH, "td_calib_online_push: window of %d frames (1 .. %d)",
-             width, TD_ONLINE_MAX_WIDTH);
-  TD_REQUIRE(h, n >= 0 && n <= TD_ONLINE_MAX_PUSH, "td_calib_online_push: %lld rows in one push (0 .. %d)",
-             (long long)n, TD_ONLINE_MAX_PUSH);
-  TD_REQUIRE(h, frames_before >= 0, "td_calib_online_push: %lld frames before", (long long)frames_before);
-  TD_TRY(check_state(h, "td_calib_online_push", num_sessions, state_dev, state_session_stride,
-                     state_bytes(c, pre, post)));
+  TD_TRY(check_calib_push(h, "td_calib_online_push", width, n, frames_before, num_sessions, state_dev,
+                          state_session_stride, c, pre, post));
   if (!w_dev || !b_dev || (n > 0 && (!eeg_dev || !env_dev)))
     return td_fail(h, TD_ERR_INVALID, "td_calib_online_push: NULL argument");
   if (n > 0)
@@ -324,18 +221,9 @@ int td_calib_online_push(td_handle* h, int num_sessions, const float* eeg_dev, i
   const long long emitted_now = p.e1 - p.e0;
   p.pass = emitted_now < kPass ? (emitted_now > 1 ? (int)emitted_now : 1) : kPass;
   p.state = reinterpret_cast<unsigned char*>(state_dev); p.state_ss = state_session_stride;
-  if (!h->lds_opt_online_calib) {
-    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&online_calib_push_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds_bytes(kMaxChannels, kMaxLags, kMaxLags - 1, kPass)));
-    h->lds_opt_online_calib = true;
-  }
-  TD_TRY(td_profile_mark(h, true, (double)n * num_sessions));
-  hipLaunchKernelGGL(online_calib_push_kernel, dim3((unsigned)num_sessions), dim3(kThreads),
-                     lds_bytes(c, nl, post, p.pass), h->stream, p);
-  TD_HIP(h, hipGetLastError());
-  TD_TRY(td_profile_mark(h, false, 0.0));
-  return TD_OK;
+  return launch_push(h, &h->lds_opt_online_calib, online_calib_push_kernel, num_sessions, kThreads,
+                     lds_bytes(kMaxChannels, kMaxLags, kMaxLags - 1, kPass), lds_bytes(c, nl, post, p.pass),
+                     (double)n * num_sessions, p);
 }
 
 int td_calib_online_sums(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,
@@ -343,12 +231,7 @@ int td_calib_online_sums(td_handle* h, int num_sessions, const void* state_dev, 
   if (!h) return td_fail(nullptr, TD_ERR_INVALID, "td_calib_online_sums: handle is NULL");
   TD_TRY(check_state(h, "td_calib_online_sums", num_sessions, state_dev, state_session_stride, 8LL * kSums));
   if (!out_dev) return td_fail(h, TD_ERR_INVALID, "td_calib_online_sums: NULL argument");
-  const unsigned blocks = (unsigned)td_ceil_div((long long)num_sessions * kSums, kThreads);
-  hipLaunchKernelGGL(online_calib_sums_kernel, dim3(blocks), dim3(kThreads), 0, h->stream,
-                     reinterpret_cast<const unsigned char*>(state_dev), (long long)state_session_stride, num_sessions,
-                     out_dev);
-  TD_HIP(h, hipGetLastError());
-  return TD_OK;
+  return launch_head_sums(h, num_sessions, state_dev, state_session_stride, kSums, out_dev);
 }
 
 int td_calib_online_finish(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,

@@ -255,17 +255,8 @@ int td_cca_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int
   p.pass = pass_of(c1, pre1, post1, c2, pre2, post2, dims, e1 - e0);     // (>= 1: check_shape)
   p.state = reinterpret_cast<unsigned char*>(state_dev); p.state_ss = state_session_stride;
   p.scores = scores_dev; p.decisions = decisions_dev; p.proj = proj_dev; p.frame = frame_dev;
-  if (!h->lds_opt_online_cca) {
-    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&cca_online_push_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    h->lds_opt_online_cca = true;
-  }
-  TD_TRY(td_profile_mark(h, true, (double)n * num_sessions));
-  hipLaunchKernelGGL(cca_online_push_kernel, dim3((unsigned)num_sessions), dim3(kThreads),
-                     (size_t)lds_bytes(c1, pre1, post1, c2, pre2, post2, dims, p.pass), h->stream, p);
-  TD_HIP(h, hipGetLastError());
-  TD_TRY(td_profile_mark(h, false, 0.0));
-  return TD_OK;
+  return launch_push(h, &h->lds_opt_online_cca, cca_online_push_kernel, num_sessions, kThreads, kLdsBudget,
+                     lds_bytes(c1, pre1, post1, c2, pre2, post2, dims, p.pass), (double)n * num_sessions, p);
 }
 
 }  // extern "C"

@@ -243,16 +243,6 @@ __global__ __launch_bounds__(kThreads) void online_ccacalib_push_kernel(CcaCalib
   if (role != kIdle && p.e1 > p.e0) head[mine] = acc;
 }
 
-// grid (ceil(S T / 256)): out [S][T]
-__global__ __launch_bounds__(kFinThreads) void online_ccacalib_sums_kernel(const unsigned char* state,
-                                                                           long long state_ss, int num_sessions,
-                                                                           int sums, double* out) {
-  const long long e = (long long)blockIdx.x * kFinThreads + threadIdx.x;
-  if (e >= (long long)num_sessions * sums) return;
-  const int s = (int)(e / sums), j = (int)(e - (long long)s * sums);
-  out[e] = reinterpret_cast<const double*>(state + (long long)s * state_ss)[j];
-}
-
 // Entry (r, c) of a symmetric matrix kept as its row-major upper triangle of side n.
 __device__ __forceinline__ double upper_at(const double* g, int n, int r, int c) {
   const int lo = r < c ? r : c, hi = r < c ? c : r;
@@ -468,17 +458,8 @@ int td_ccacalib_online_push(td_handle* h, int num_sessions, const float* eeg_dev
   p.width = width;
   p.pass = pass_of(c1, pre1, post1, c2, pre2, post2, dims, p.e1 - p.e0);   // (>= 1: check_shape)
   p.state = reinterpret_cast<unsigned char*>(state_dev); p.state_ss = state_session_stride;
-  if (!h->lds_opt_online_ccacalib) {
-    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&online_ccacalib_push_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    h->lds_opt_online_ccacalib = true;
-  }
-  TD_TRY(td_profile_mark(h, true, (double)n * num_sessions));
-  hipLaunchKernelGGL(online_ccacalib_push_kernel, dim3((unsigned)num_sessions), dim3(kThreads),
-                     (size_t)lds_bytes(c1, pre1, post1, c2, pre2, post2, dims, p.pass), h->stream, p);
-  TD_HIP(h, hipGetLastError());
-  TD_TRY(td_profile_mark(h, false, 0.0));
-  return TD_OK;
+  return launch_push(h, &h->lds_opt_online_ccacalib, online_ccacalib_push_kernel, num_sessions, kThreads, kLdsBudget,
+                     lds_bytes(c1, pre1, post1, c2, pre2, post2, dims, p.pass), (double)n * num_sessions, p);
 }
 
 int td_ccacalib_online_sums(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,
@@ -488,12 +469,7 @@ int td_ccacalib_online_sums(td_handle* h, int num_sessions, const void* state_de
   TD_REQUIRE(h, dims >= 1 && dims <= kMaxDims, "%s: %d dims (1 .. %d)", who, dims, kMaxDims);
   TD_TRY(check_state(h, who, num_sessions, state_dev, state_session_stride, 8LL * head_sums(dims)));
   if (!out_dev) return td_fail(h, TD_ERR_INVALID, "%s: NULL argument", who);
-  const unsigned blocks = (unsigned)td_ceil_div((long long)num_sessions * head_sums(dims), kFinThreads);
-  hipLaunchKernelGGL(online_ccacalib_sums_kernel, dim3(blocks), dim3(kFinThreads), 0, h->stream,
-                     reinterpret_cast<const unsigned char*>(state_dev), (long long)state_session_stride, num_sessions,
-                     head_sums(dims), out_dev);
-  TD_HIP(h, hipGetLastError());
-  return TD_OK;
+  return launch_head_sums(h, num_sessions, state_dev, state_session_stride, head_sums(dims), out_dev);
 }
 
 int td_ccacalib_online_finish(td_handle* h, int num_sessions, const void* state_dev, int64_t state_session_stride,

@@ -1,7 +1,9 @@
 // What the online push kernels share (online.hip, online_cca.hip, online_calib.hip, through online_dnn_common.h
 // online_dnn.hip and online_dnn_calib.hip and, through online_cca_common.h, online_cca_calib.hip): the state block's layout, the plan of a push, and the blocks of a push
 // kernel that every session repeats -- stage, (predict: each file's own, the FIR prediction here for the two files
-// that use it), score, windows, tails.  The host interface is td_common.h.  online_fit.hip and online_cca_fit.hip
+// that use it), score, windows, tails -- and, on the host, the launch tail of a push entry point and the read-out of a
+// calibration state's float64 head.  What the two envelope calibrations share beyond this is online_calib_common.h.
+// The host interface is td_common.h.  online_fit.hip and online_cca_fit.hip
 // take, through online_fit_common.h, the plan of a push, the wave sum and the host checks of the strides and the
 // state; their moments and double-buffered tails are their own.  online_pre.hip and online_audio.hip carry other
 // state and do not use this.
@@ -245,6 +247,45 @@ __device__ __forceinline__ void env_tail_store(float* etail, const float* park_s
     const int rr = i >> 1;
     etail[i] = rr < ekeep ? park_s[i] : env[(n - (post - rr)) * env_ld + (i & 1)];
   }
+}
+
+// ---- a calibration state's float64 head, copied out.  grid (ceil(S sums / NT)): out [S][sums].  (A template, so
+// that only the files that launch it hold a copy: a plain kernel here is emitted into every including file.)
+template <int NT>
+__global__ __launch_bounds__(NT) void online_head_sums_kernel(const unsigned char* state, long long state_ss,
+                                                              int num_sessions, int sums, double* out) {
+  const long long e = (long long)blockIdx.x * NT + threadIdx.x;
+  if (e >= (long long)num_sessions * sums) return;
+  const int s = (int)(e / sums), j = (int)(e - (long long)s * sums);
+  out[e] = reinterpret_cast<const double*>(state + (long long)s * state_ss)[j];
+}
+
+template <int NT = 256>
+inline int launch_head_sums(td_handle* h, int num_sessions, const void* state_dev, long long state_ss, int sums,
+                            double* out_dev) {
+  const unsigned blocks = (unsigned)td_ceil_div((long long)num_sessions * sums, NT);
+  hipLaunchKernelGGL(online_head_sums_kernel<NT>, dim3(blocks), dim3(NT), 0, h->stream,
+                     reinterpret_cast<const unsigned char*>(state_dev), state_ss, num_sessions, sums, out_dev);
+  TD_HIP(h, hipGetLastError());
+  return TD_OK;
+}
+
+// ---- the launch tail of a push entry point: the kernel's dynamic LDS cap raised once per handle (`raised` is the
+// handle's flag for this kernel), then the profile mark, the launch of `grid` workgroups of `block` threads with
+// `lds` bytes, its error, the profile mark.
+template <typename Params>
+inline int launch_push(td_handle* h, bool* raised, void (*kernel)(Params), int grid, int block, long long lds_cap,
+                       long long lds, double work, const Params& p) {
+  if (!*raised) {
+    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)lds_cap));
+    *raised = true;
+  }
+  TD_TRY(td_profile_mark(h, true, work));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3((unsigned)block), (size_t)lds, h->stream, p);
+  TD_HIP(h, hipGetLastError());
+  TD_TRY(td_profile_mark(h, false, 0.0));
+  return TD_OK;
 }
 
 // ---- host checks.  `who` is the entry point's name; each file calls these where its own checks stood, so the

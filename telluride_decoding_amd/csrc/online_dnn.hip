@@ -29,8 +29,9 @@
 // launch; the activations of a pass live in two LDS buffers with an odd row stride.
 //
 // The network's shape, the LDS of a launch, the shape checks and layer 1's device functions (chunk_load, chunk_store,
-// slice_fma) are online_dnn_common.h's, shared with online_dnn_calib.hip; this kernel's code is what it was with
-// them in this file.
+// slice_fma) are online_dnn_common.h's, and the forward of a pass -- the layer-1 driver and the later-layers loop --
+// is the text of online_dnn_forward_body.h, both shared with online_dnn_calib.hip; this kernel's code is what it was
+// with them in this file (DESIGN.md sections 45 and 47).
 #include "online_dnn_common.h"
 
 namespace {
@@ -91,85 +92,9 @@ __global__ __launch_bounds__(kThreads) void dnn_online_push_kernel(DnnOnlinePara
 
   for (long long a = p.e0; a < p.e1; a += pass) {
     const int nf = (int)(p.e1 - a < pass ? p.e1 - a : pass);     // frames [a, a + nf) of this pass
-    float4 regs[kLoads];
-    chunk_load(prm, t, 0, vec, tid, regs);
-    // ---- stage the EEG rows a - pre .. a + nf - 1 + post and the envelope rows a .. a + nf - 1
-    stage_rows<kThreads>(rows_s, ldr, tail, tl, eeg, p.eeg_ld, c, a - pre, nf + tl, p0, p1);
-    stage_env<kThreads>(env_s, etail, post, env, p.env_ld, a, nf, p0);
-    chunk_store(ws_s, t, 0, tid, regs);
-    __syncthreads();
-    // ---- layer 1: thread = (frame f, column lane cg), frame-fastest; the thread owns the column groups cg,
-    // cg + cl, ... (4 columns each, cl = kThreads / nf lanes), which share the frame's x.  Per slice a chain of
-    // fused multiply-adds from 0.f over the slice's rows, added to the accumulators in slice order.
-    const int cl = kThreads / nf, ng = (w1q + cl - 1) / cl;         // (nf <= 64, w1q <= 16: ng <= kPairs)
-    const int pf = tid % nf, cg = tid / nf;
-    const bool busy = cg < cl && cg * ng < w1q;
-    // the thread's groups are cg ng .. cg ng + ng - 1; it reads the ng ADJACENT groups from jb on (one address and
-    // constant offsets per row of W1), moved back where they would pass the last group: a group in front of its
-    // own repeats a neighbour's sums and is dropped
-    const int jb = busy ? (cg * ng < w1q - ng ? cg * ng : w1q - ng) : 0;
-    bool own[kPairs];
-    float acc[kPairs][4];
-#pragma unroll
-    for (int o = 0; o < kPairs; ++o) {
-      own[o] = busy && o < ng && jb + o >= cg * ng;
-      acc[o][0] = acc[o][1] = acc[o][2] = acc[o][3] = 0.f;
-    }
-    int lag0 = 0, ch0 = 0;                                          // the slice's first row is (lag0, ch0)
-    for (int ci = 0; ci < t.nchunks; ++ci) {
-      if (ci + 1 < t.nchunks) chunk_load(prm, t, ci + 1, vec, tid, regs);
-      const float* buf = ws_s + (ci & 1) * chunk_floats;
-      const int sl_end = (ci + 1) * t.g < t.nslices ? (ci + 1) * t.g : t.nslices;
-      for (int sl = ci * t.g; sl < sl_end; ++sl) {
-        const int kbase = sl * ks;
-        const int ksl = k_all - kbase < ks ? k_all - kbase : ks;
-        if (busy) {
-          const float* xp = rows_s + (pf + lag0) * ldr + ch0;
-          const float* wrow = buf + (size_t)(sl - ci * t.g) * ks * nj + 4 * jb;
-          if (ng == 1) slice_fma<1>(xp, wrow, nj, ksl, ch0, c, ldr, acc);
-          else if (ng == 2) slice_fma<2>(xp, wrow, nj, ksl, ch0, c, ldr, acc);
-          else if (ng == 3) slice_fma<3>(xp, wrow, nj, ksl, ch0, c, ldr, acc);
-          else slice_fma<4>(xp, wrow, nj, ksl, ch0, c, ldr, acc);
-        }
-        ch0 += ksl;
-        while (ch0 >= c) { ch0 -= c; ++lag0; }
-      }
-      if (ci + 1 < t.nchunks) chunk_store(ws_s + ((ci + 1) & 1) * chunk_floats, t, ci + 1, tid, regs);
-      __syncthreads();
-    }
-    // z1 = the partials + b1; ReLU when a layer follows, else (no hidden layer: w1 = 1) the prediction itself
-#pragma unroll
-    for (int o = 0; o < kPairs; ++o) {
-      if (!own[o]) continue;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int j = 4 * (jb + o) + q;
-        if (j >= w1) continue;
-        const float z = acc[o][q] + small[t.off_b[0] + j];
-        if (nl > 1) act_s[pf * lda_s + j] = z <= 0.f ? 0.f : z;
-        else pred_s[pf] = z;
-      }
-    }
-    __syncthreads();
-    // ---- the later layers: (frame, unit) pairs over the workgroup, frame-fastest; the last layer's one unit is
-    // the prediction
-    for (int l = 2; l <= nl; ++l) {
-      const int wi = t.w[l - 1], wo = t.w[l];
-      const float* W = small + t.off_w[l - 1];
-      const float* b = small + t.off_b[l - 1];
-      const float* in = act_s + (size_t)(l & 1) * pass * lda_s;
-      float* outp = act_s + (size_t)((l + 1) & 1) * pass * lda_s;
-      for (int pr = tid; pr < nf * wo; pr += kThreads) {
-        const int o = pr / nf, f = pr - o * nf;
-        const float* xin = in + f * lda_s;
-        float sum = 0.f;
-        for (int i = 0; i < wi; ++i) sum = fmaf(xin[i], W[i * wo + o], sum);
-        sum += b[o];
-        if (l < nl) outp[f * lda_s + o] = sum <= 0.f ? 0.f : sum;
-        else pred_s[f] = sum;
-      }
-      __syncthreads();
-    }
+    // ---- the forward: stage the pass's rows, layer 1 over the streamed W1, the later layers; the predictions in
+    // pred_s behind a barrier
+#include "online_dnn_forward_body.h"
     // ---- per-frame scores of both speakers
     for (int i = tid; i < 2 * nf; i += kThreads) {
       const int spk = i / nf, f = i - spk * nf;
@@ -254,13 +179,7 @@ extern "C" {
 
 int td_fc_online_lds_bytes(int c, int pre, int post, int num_hidden, const int* hidden_host, int64_t emitted,
                             int* pass, int64_t* bytes) {
-  if (!pass || !bytes) return td_fail(nullptr, TD_ERR_INVALID, "td_fc_online_lds_bytes: NULL argument");
-  TD_TRY(check_shape(nullptr, "td_fc_online_lds_bytes", c, pre, post, num_hidden, hidden_host));
-  TD_REQUIRE(nullptr, emitted >= 0, "td_fc_online_lds_bytes: %lld frames", (long long)emitted);
-  const DnnNet t = net_of(c, pre, post, hidden_host, num_hidden);
-  *pass = pass_of(t, c, pre, post, emitted);
-  *bytes = lds_bytes(t, c, pre, post, *pass);
-  return TD_OK;
+  return lds_query("td_fc_online_lds_bytes", c, pre, post, num_hidden, hidden_host, emitted, pass, bytes);
 }
 
 int td_fc_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int64_t eeg_ld,
@@ -298,17 +217,8 @@ int td_fc_online_push(td_handle* h, int num_sessions, const float* eeg_dev, int6
   p.net = t;
   p.state = reinterpret_cast<unsigned char*>(state_dev); p.state_ss = state_session_stride;
   p.scores = scores_dev; p.decisions = decisions_dev; p.pred = pred_dev; p.frame = frame_dev;
-  if (!h->lds_opt_online_dnn) {
-    TD_HIP(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&dnn_online_push_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudget));
-    h->lds_opt_online_dnn = true;
-  }
-  TD_TRY(td_profile_mark(h, true, (double)n * num_sessions));
-  hipLaunchKernelGGL(dnn_online_push_kernel, dim3((unsigned)num_sessions), dim3(kThreads),
-                     (size_t)lds_bytes(t, c, pre, post, p.pass), h->stream, p);
-  TD_HIP(h, hipGetLastError());
-  TD_TRY(td_profile_mark(h, false, 0.0));
-  return TD_OK;
+  return launch_push(h, &h->lds_opt_online_dnn, dnn_online_push_kernel, num_sessions, kThreads, kLdsBudget,
+                     lds_bytes(t, c, pre, post, p.pass), (double)n * num_sessions, p);
 }
 
 }  // extern "C"

@@ -1,9 +1,10 @@
 // What the two online kernels that run a fully connected regressor share (online_dnn.hip: td_fc_online_*;
 // online_dnn_calib.hip: td_fccalib_online_*): the network's shape and how W1 is cut, the LDS of a launch and the pass
-// that fits it, the shape checks, and the three device functions of layer 1 -- a chunk of W1 from global into
-// registers, from registers into LDS, one slice of W1 for one frame's columns.  The layer-1 driver and the later
-// layers stay inline in each kernel's body (DESIGN.md sections 36 and 45: a helper call there changed
-// dnn_online_push_kernel's register allocation); a change to either body is a change to the other.
+// that fits it, the shape checks and the LDS query, and the three device functions of layer 1 -- a chunk of W1 from
+// global into registers, from registers into LDS, one slice of W1 for one frame's columns.  The layer-1 driver and
+// the later layers are no function (DESIGN.md sections 36 and 47: a helper call there changed
+// dnn_online_push_kernel's register allocation): they are the text of online_dnn_forward_body.h, which each kernel
+// includes inside its pass loop.
 //
 // The prediction has td_mlp_forward's bits whatever the including file's contraction mode: every fused operation
 // here is an explicit fmaf and no product feeds an add in one expression (online_common.h's rule).
@@ -195,6 +196,19 @@ int check_shape(td_handle* h, const char* who, int c, int pre, int post, int num
   TD_REQUIRE(h, need <= kLdsBudget,
              "%s: two chunks of W1, the small layers' %d parameters and a pass of one frame of %d x %d lags take %lld "
              "bytes of LDS (budget %lld bytes)", who, t.n_small, c, pre + 1 + post, need, kLdsBudget);
+  return TD_OK;
+}
+
+// The LDS query of both families (td_fc_online_lds_bytes, td_fccalib_online_lds_bytes): the pass and the bytes of a
+// launch that emits `emitted` frames.
+int lds_query(const char* who, int c, int pre, int post, int num_hidden, const int* hidden, long long emitted,
+              int* pass, int64_t* bytes) {
+  if (!pass || !bytes) return td_fail(nullptr, TD_ERR_INVALID, "%s: NULL argument", who);
+  TD_TRY(check_shape(nullptr, who, c, pre, post, num_hidden, hidden));
+  TD_REQUIRE(nullptr, emitted >= 0, "%s: %lld frames", who, emitted);
+  const DnnNet t = net_of(c, pre, post, hidden, num_hidden);
+  *pass = pass_of(t, c, pre, post, emitted);
+  *bytes = lds_bytes(t, c, pre, post, *pass);
   return TD_OK;
 }
 

@@ -1,15 +1,20 @@
-"""The four online push entry points against the bytes of the build before online_common.h.
+"""Five online push entry points against the bytes of the build before their code was shared.
 
 td_online_push, td_fc_online_push, td_cca_online_push and td_calib_online_push share their state layout, staging,
-FIR prediction, per-frame score, window block and tail update through csrc/online_common.h.  The other online
+FIR prediction, per-frame score, window block and tail update through csrc/online_common.h; the fifth,
+td_fccalib_online_push, takes its forward from the text td_fc_online_push includes (csrc/online_dnn_forward_body.h)
+and its walk from the header td_calib_online_push includes (csrc/online_calib_common.h).  The other online
 suites compare every cut of a recording with one push and with the batch kernels; this file pins the shared blocks
 themselves: a fixed-seed recording (np.random.RandomState) goes through a sequence of pushes, and the SHA-256 of every
 output -- per push the scores, the decisions, pred / proj and the per-frame scores, at the end the state bytes; for
-the calibration the state bytes after every push -- is compared with PARENT_SHA256.
+the two calibrations the state bytes after every push -- is compared with PARENT_SHA256.
 
 PARENT_SHA256 was produced once, by this file's own run_case, from the library of the parent commit 3f4d7ac ("Add an
 online calibration: a decoder's statistics and LDA from pushes"), which holds the four kernels as four hand-kept
-copies, selected through TD_HOTPATH_LIB on the MI355X.  It is never to be produced from the code under test.
+copies, selected through TD_HOTPATH_LIB on the MI355X; the digests of the DNNCALIB family the same way from the
+library of 9a35557 ("Sweep the FIR and CCA projection kernels at their edges; fix NaN spread"), the last commit in
+which dnn_calib_push_kernel holds its forward and its walk as hand-kept copies.  None is ever to be produced from the
+code under test.
 
 The cases are the smallest at which each shared block can go wrong, a few dozen combinations that between them touch:
 channels 1, 3, 65, 128 (the 64-lane channel loop: one trip, one, two, the limit); context (0, 0), (2, 3), (0, 63) (no
@@ -21,7 +26,10 @@ the hashed state bytes and carries across pushes); reductions first / mean / mea
 second); 1 and 3 sessions with one shared model and with a model per session, the rows of a push a slice whose row
 and session strides are larger than a row and a block; hidden layers [], [5], [64, 3]; c2 1 and 3, dims 1 and 5,
 post1 != post2 both ways, pre2 != pre1; and the calibration at width 4 with pushes that end inside a window, exactly
-on one and across two."""
+on one and across two.  The DNN calibration's six: no hidden layer with those pushes; scalar chunk loads (w1 no
+multiple of 4) and a model per session; the lag limit, the vector chunk path and a layer behind layer 1; a flush that
+carries rows under one shared model; width 1 (every frame closes a window) at K = 8192; a window longer than a pass
+over 70 + 1 + 300 rows."""
 import hashlib
 
 import numpy as np
@@ -83,6 +91,15 @@ CALIB = [
     (128, 0, 63, 1, 1, True, 'B'),
     (3, 2, 3, 100, 3, False, 'M'),
 ]
+# (c, pre, post, hidden, width, sessions, shared model, sequence)
+DNNCALIB = [
+    (3, 0, 0, (), 4, 1, True, 'W'),
+    (1, 2, 3, (5,), 4, 3, False, 'A'),
+    (65, 0, 63, (64, 3), 4, 1, True, 'A'),
+    (128, 2, 3, (5,), 4, 3, True, 'B'),
+    (128, 0, 63, (), 1, 1, True, 'B'),
+    (3, 2, 3, (64, 3), 100, 3, False, 'M'),
+]
 
 
 def _name(case):
@@ -90,7 +107,8 @@ def _name(case):
 
 
 CASES = ([('linear-' + _name(c), 'linear', c) for c in LINEAR] + [('dnn-' + _name(c), 'dnn', c) for c in DNN] +
-         [('cca-' + _name(c), 'cca', c) for c in CCA] + [('calib-' + _name(c), 'calib', c) for c in CALIB])
+         [('cca-' + _name(c), 'cca', c) for c in CCA] + [('calib-' + _name(c), 'calib', c) for c in CALIB] +
+         [('dnncalib-' + _name(c), 'dnncalib', c) for c in DNNCALIB])
 
 # the parent commit's outputs: {case: {output: SHA-256}}
 PARENT_SHA256 = {
@@ -294,6 +312,24 @@ PARENT_SHA256 = {
     'calib-3-2-3-100-3-False-M': {
         'state': 'a2c76e43b1b08747ba363a742443d2d8255fdaf40a91fe2ee1da3158d5d705f2',
     },
+    'dnncalib-3-0-0-none-4-1-True-W': {
+        'state': 'ff768dd2f74708c9736f2344fd57c85d22e1193c82083322d77bdf8206f29867',
+    },
+    'dnncalib-1-2-3-5-4-3-False-A': {
+        'state': 'cd551f4df77dfa2b11dad3302d6cd78bfc22ec43526a8425ec9bbb9a0bedff64',
+    },
+    'dnncalib-65-0-63-64x3-4-1-True-A': {
+        'state': 'e6c3a6006c0c5ea1d649149c1380a01b0e1453dcccd3a0f11c48f3238fd63176',
+    },
+    'dnncalib-128-2-3-5-4-3-True-B': {
+        'state': '34c745f6c047f077b9b747bcbbd6c86dfdb77f1fb445148e76d1b5a7928e87b9',
+    },
+    'dnncalib-128-0-63-none-1-1-True-B': {
+        'state': '8abef587d05a8b04955b880cf814d1e35bfae3e4eb26706164a6077d1a5ad648',
+    },
+    'dnncalib-3-2-3-64x3-100-3-False-M': {
+        'state': '7030acd1f3c027de329ab6dafa98087784eb254e5b002fcbaf92e51564b08b48',
+    },
 }
 
 
@@ -399,20 +435,32 @@ def _run_decoder(dev, kind, case, rs):
   return out.digests()
 
 
-def _run_calib(dev, case, rs):
+def _run_calib(dev, kind, case, rs):
   import torch
-  c, pre, post, width, sessions, shared, seq = case
+  if kind == 'dnncalib':
+    c, pre, post, hidden, width, sessions, shared, seq = case
+  else:
+    c, pre, post, width, sessions, shared, seq = case
   lens, last = _lengths(seq, pre + post)
   rec = _Recording(rs, sessions, sum(lens) + (last or 0), (c, 2))
-  models = 1 if shared else sessions
-  w = _up((0.3 * rs.standard_normal((models, c * (pre + 1 + post)))).astype(np.float32))
-  b = _up(rs.standard_normal(models).astype(np.float32))
-  state = torch.zeros((sessions, dev.online_calib_state_bytes(c, pre, post)), dtype=torch.uint8, device='cuda')
+  models, k = 1 if shared else sessions, c * (pre + 1 + post)
+  if kind == 'dnncalib':
+    params = _up((0.3 * rs.standard_normal((models, dev.dnn_param_count(k, hidden)))).astype(np.float32))
+    sbytes = dev.online_dnn_calib_state_bytes(c, pre, post)
+  else:
+    w = _up((0.3 * rs.standard_normal((models, k))).astype(np.float32))
+    b = _up(rs.standard_normal(models).astype(np.float32))
+    sbytes = dev.online_calib_state_bytes(c, pre, post)
+  state = torch.zeros((sessions, sbytes), dtype=torch.uint8, device='cuda')
   out = _Hashes(('state',))
   pushed = 0
   for n, flush in [(n, False) for n in lens] + [(last or 0, True)]:
     rows = rec.take(n) if n else [None, None]
-    pushed = dev.online_calib_push(rows[0], rows[1], w, b, state, pushed, pre, post, width, c=c, flush=flush)
+    if kind == 'dnncalib':
+      pushed = dev.online_dnn_calib_push(rows[0], rows[1], params, list(hidden), state, pushed, pre, post, width,
+                                         flush=flush)
+    else:
+      pushed = dev.online_calib_push(rows[0], rows[1], w, b, state, pushed, pre, post, width, c=c, flush=flush)
     out.add('state', state)                                # (after every push: where a window ends matters)
   return out.digests()
 
@@ -420,7 +468,7 @@ def _run_calib(dev, case, rs):
 def run_case(dev, name, kind, case):
   """{output: SHA-256} of one case; the seed is the case's place in CASES."""
   rs = np.random.RandomState(20261 + [c[0] for c in CASES].index(name))
-  return _run_calib(dev, case, rs) if kind == 'calib' else _run_decoder(dev, kind, case, rs)
+  return _run_calib(dev, kind, case, rs) if kind in ('calib', 'dnncalib') else _run_decoder(dev, kind, case, rs)
 
 
 @pytest.fixture(scope='module')

@@ -4,7 +4,8 @@ python tools/isa_diff.py <parent-csrc-dir> <new-csrc-dir> --out <dir outside the
 Every *.hip of both directories is compiled with build.py's flags plus --cuda-device-only -S (the .s files
 go to --out), cut into kernels by symbol and compared as text: comments and blank lines dropped, whitespace
 collapsed, .LBB<n>_ / .Lfunc_end<n> renumbered.  One line per kernel symbol: same / changed (opcode counts and
-.amdhsa_* lines that differ) / missing / new, and the file that holds it on each side.  Exit status 0 only
+.amdhsa_* lines that differ) / missing / new, and the file that holds it on each side (`a + b`: a kernel
+defined in a header, the same code in both files; copies that differ end the run).  Exit status 0 only
 when both sides hold the same symbols and every one is `same`."""
 import collections, glob, os, re, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
@@ -37,7 +38,9 @@ def compile_dir(csrc, out):
       j = next(k for k in range(i, len(lines)) if lines[k].startswith('.Lfunc_end'))
       n = re.match(r'\.Lfunc_end(\d+)', lines[j]).group(1)
       body = [re.sub(r'\.LBB%s_' % n, '.LBB_', l) for l in lines[i + 1:j]]
-      if sym in kernels: sys.exit('%s: in %s and in %s' % (sym, kernels[sym][0], name))
+      if sym in kernels:                        # a header's kernel: one line, if every file holds the same code
+        if kernels[sym][1:] != (body, d): sys.exit('%s: in %s and in %s, not the same' % (sym, kernels[sym][0], name))
+        name = kernels[sym][0] + ' + ' + name
       kernels[sym] = (name, body, d)
   return kernels
 
